@@ -6,14 +6,14 @@ per GPU.  The stream is parsed ONCE on the host into packed frame jobs (capture 
 replicated into HBM (every stream owns its jobs and its DPB), and a "step" is one pass of the hot path
 over the whole batch: 73 pictures x 256 streams = 18,688 pictures = 152.5 M macroblocks per GPU,
 reconstructed (inter + intra) and deblocked by the HIP kernels.  Inputs are resident in HBM when the
-timed region starts; outputs stay in HBM and are verified on the device against the reference's golden
-checksums (every picture of every stream, in an untimed verification pass, and the final picture after
+timed region starts; outputs stay in HBM and, with --full, are verified on the device against the reference's
+golden checksums (every picture of every stream, in an untimed verification pass, and the final picture after
 the timed region).  A run that is not bit-exact aborts.
 
 `value` is the LOCK-STEP variant (every stream on the same picture index: every tick holds 256 pictures of the same
 kind and cost, which is the FRIENDLIEST schedule for batched launches — the two IDR pictures of the stream give two
 all-intra ticks per step, but no tick ever waits for a stray heavy picture).  The same work with odd-numbered streams
-started at the second IDR ("staggered") is measured in the same run and reported under
+started at the second IDR ("staggered") is measured in the same --full run and reported under
 `staggered`; streams that are not in step at all (every stream at its own picture index: what 256 independent cameras
 deliver; with and without heavy lanes) under `desynchronised` — 0.32-0.65 of the lock-step figure.
 
@@ -22,8 +22,21 @@ One process per GPU: `python bench.py` (N=1) or
 so ranks share nothing on the data path (weak scaling: 256 streams per GPU); torch.distributed (RCCL)
 is used only for the barriers and the MAX-over-ranks of the elapsed time.
 
-Output: ONE JSON line on rank 0 (see the driver contract), with `roofline` (dominant kernel, HBM bound)
-and `cpu_baseline` (the compiled reference, oracle/_ref, timed on this host; N=1 only).
+Output: ONE JSON line on rank 0 (see the driver contract).
+
+A plain run (`python bench.py --gpus 1 --steps N --warmup W`) sets up, ramps the clocks, runs the W warm-up steps, times
+the N lock-step steps and prints the headline (`value`, `ms_per_step`, ...).  Everything else moves behind `--full`:
+the untimed verification pass of every picture of every stream against the reference's checksums (and of the final
+pictures after the timed region), the other variants (4 stream groups, without copy elision, staggered, BGRA,
+desynchronised), `roofline` (dominant kernel, HBM bound, copy ceiling), `per_gpu`, the end-to-end legs through the C
+API and `cpu_baseline` (the compiled reference, oracle/_ref, timed on this host; N=1 only).  The `--no-*` options
+switch legs of a `--full` run off.
+
+`--dump-outputs DIR` (rank 0) writes what the timed steps computed in the last of them, as float32 / float64 .npy files:
+`last_pictures.npy` (the last picture of the stream, as the frame buffer holds it, for a fixed seeded sample of 3
+streams), `last_pictures_streams.npy` (which streams), and `slot_checksums.npy` (the 64-bit device checksum of every
+frame buffer the stream uses, for every stream, as low / high 32-bit halves).  The input is the bundled stream, so the
+outputs of two builds compare one to one.
 """
 import argparse
 import json
@@ -228,6 +241,9 @@ def main():
     ap.add_argument("--no-argb", action="store_true", help="skip the config-3 variant (colour conversion of every picture inside the timed region)")
     ap.add_argument("--argb-no-hosting", action="store_true", help="config-3 variant with a k_convert_tiles launch behind every tick instead of the conversion hosted by the next tick's k_frame_dbk (A/B)")
     ap.add_argument("--no-end-to-end", action="store_true", help="skip the end-to-end leg through the drop-in C API (host parse + H2D + kernels)")
+    ap.add_argument("--full", action="store_true", help="also verify every picture against the reference and run every other leg "
+                    "(variants, roofline, per-GPU values, end to end, CPU baseline); without it only the headline is measured")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy (float32 / float64)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -294,6 +310,21 @@ def main():
     BESIDE = ("k_copy", "k_dbk")                 # launched on side streams next to k_recon_inter (engine.hip launch_tick)
     golden_sums = golden["frame_checksum64"]
 
+    def dump_outputs(rep):
+        """--dump-outputs: the frame buffers as the last timed step left them.  The last picture of 3 streams drawn with a fixed seed
+        (3 x 12.5 MB as float32: the samples are bytes, exact in float32) and the device checksum of every frame buffer the stream
+        uses, for every stream (uint64 split into two exact float64 halves)."""
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        sample = np.sort(np.random.default_rng(0).choice(args.streams, size=min(3, args.streams), replace=False))
+        last_slot = heads[-1]["cur_slot"]
+        pics = np.stack([rep.fetch(int(s), last_slot).astype(np.float32) for s in sample])
+        sums = np.stack([rep.checksums(sl) for sl in sorted(set(h["cur_slot"] for h in heads))])
+        halves = np.stack([sums & np.uint64(0xFFFFFFFF), sums >> np.uint64(32)], axis=-1).astype(np.float64)
+        np.save(os.path.join(args.dump_outputs, "last_pictures.npy"), pics)
+        np.save(os.path.join(args.dump_outputs, "last_pictures_streams.npy"), sample.astype(np.float64))
+        np.save(os.path.join(args.dump_outputs, "slot_checksums.npy"), halves)
+
     # ONE replay set (jobs + DPBs resident in HBM: 22 GB for 256 x 1080p) serves every leg that replays these jobs — lock-step,
     # staggered, + conversion, the three desynchronised schedules: a leg asks for its schedule (Replay.reschedule: new
     # descriptors, zeroed frame buffers), nothing is allocated or uploaded twice.  Only the leg without copy elision replays
@@ -330,10 +361,11 @@ def main():
                 if not (sel == golden_sums[p]).all():
                     raise SystemExit(f"rank {rank}: picture {p} is not bit-exact on {(sel != golden_sums[p]).sum()} streams")
 
-        # ---- untimed verification pass: every picture of every stream against the reference ----
-        for i in range(n_pics):
-            rep.run(i, 1)
-            verify(i)
+        # ---- untimed verification pass (--full): every picture of every stream against the reference ----
+        if args.full:
+            for i in range(n_pics):
+                rep.run(i, 1)
+                verify(i)
         rep.set_groups(args.groups)
         # untimed clock ramp: a fresh box reaches its steady clocks only after a few seconds of load (the first
         # bench run on a new box measured 4-5 % low with one warm-up step); W warm-up steps follow as asked.
@@ -368,9 +400,11 @@ def main():
             dev_total_ms += t["total_ms"]
         barrier()
         elapsed = time.perf_counter() - t0
+        if main and odd_offset == 0 and args.dump_outputs and rank == 0:
+            dump_outputs(rep)                                  # what the last timed step left in the frame buffers
         # the same lock-step work with the streams split into 4 groups that run their ticks on their own HIP streams
         # (the per-picture kernels of one group overlap with the other groups' work); reported next to `value`
-        if main and odd_offset == 0 and args.groups == 1 and args.streams >= 8 and not args.no_groups_variant:
+        if args.full and main and odd_offset == 0 and args.groups == 1 and args.streams >= 8 and not args.no_groups_variant:
             rep.set_groups(4)
             rep.run(); rep.sync()
             barrier()
@@ -385,7 +419,8 @@ def main():
         if dom is None:
             dom = max((k for k in kernels if k not in BESIDE), key=lambda k: k_ms[k])
             breakdown = {k: (k_ms[k] / steps, k_n[k] // steps) for k in kernels}
-        verify(n_pics - 1)                                     # the final pictures, after the timed region
+        if args.full:
+            verify(n_pics - 1)                                 # the final pictures, after the timed region
         job_bytes = rep.job_bytes
         release(rep)
         local = elapsed
@@ -399,11 +434,11 @@ def main():
     # the same lock-step work with EVERY copy macroblock copied (no copy elision): what the number is without that
     # optimisation of the parser, on the same line
     full_copies = None
-    if elide and not args.no_full_copies_variant:
+    if args.full and elide and not args.no_full_copies_variant:
         fc_elapsed, _, _, fc_dev_ms, _, _, fc_breakdown, _, _ = run_variant(0, side_steps, jobs=h264bsd_amd.capture_stream(data)[0], main=False)
         full_copies = dict(elapsed=fc_elapsed, breakdown=fc_breakdown, dev_ms=fc_dev_ms)
     staggered = None
-    if not args.no_staggered and args.streams > 1:
+    if args.full and not args.no_staggered and args.streams > 1:
         idr = [i for i, h in enumerate(heads) if h["is_idr"] and i > 0]
         if idr:
             st_elapsed, _, _, st_dev_ms, _, _, st_breakdown, _, _ = run_variant(idr[0], side_steps)
@@ -417,7 +452,7 @@ def main():
     # convert_sha256) in untimed passes first: pictures 0, 1 and 72 through the launch, pictures 0 and 1 as the hosts of
     # ticks 1 and 2 leave them in the conversion buffer.
     argb = None
-    if not args.no_argb:
+    if args.full and not args.no_argb:
         import hashlib
         rep = replay_for(jobs)
         w_px, h_px = info["width_mbs"] * 16, info["height_mbs"] * 16
@@ -475,7 +510,7 @@ def main():
     # Verified at the end of laps 2 and N (a lap = every stream n_pics pictures; the last picture of stream s is
     # picture offsets[s] - 1, so the 256 streams together cover every picture index).
     desync = None
-    if not args.no_desync and args.streams > 1:
+    if args.full and not args.no_desync and args.streams > 1:
         offsets = [(st * n_pics) // args.streams for st in range(args.streams)]
         slots = sorted(set(h["cur_slot"] for h in heads))
         desync = {"offsets": "stream s starts at picture floor(s * n_pics / n_streams)"}
@@ -544,7 +579,7 @@ def main():
 
     # on-box ceiling of a plain device-to-device copy (report the fraction of both peaks)
     copy_gbs = None
-    if rank == 0:
+    if args.full and rank == 0:
         src = torch.empty(1 << 30, dtype=torch.uint8, device="cuda")
         dst = torch.empty_like(src)
         dst.copy_(src)
@@ -559,7 +594,7 @@ def main():
 
     # per-GPU values (config 5 asks for them next to the node total): every rank's own elapsed time of the timed steps
     per_gpu = None
-    if dist is not None:
+    if args.full and dist is not None:
         mine = torch.tensor([local_elapsed], dtype=torch.float64, device=red_dev)
         allv = [torch.zeros_like(mine) for _ in range(world)]
         dist.all_gather(allv, mine)
@@ -569,7 +604,7 @@ def main():
     # GPUs"): each rank's library sizes its parser pool for its share of the CPUs the container may use (H264BSDMI_HOST_SHARE =
     # ranks on this host) and pins it to its GPU's NUMA node; the node figure is all ranks' pictures over the slowest rank's time.
     e2e = {}
-    if not args.no_end_to_end:
+    if args.full and not args.no_end_to_end:
         for key, pull, laps in (("end_to_end", False, 2), ("end_to_end_host_output", True, 1)):
             barrier()
             leg = end_to_end(data, min(args.streams, 256), 0, laps=laps, pull=pull, barrier=barrier if dist is not None else None)      # 0 threads: the library's default
@@ -590,85 +625,6 @@ def main():
     if rank == 0:
         pics_per_step = n_pics * args.streams * world
         mbs = pics_per_step * n_mbs * args.steps
-        # algorithmic bytes: 384 B written per MB + 384 B of reference read per inter MB +
-        # the packed syntax actually consumed (the frame jobs)
-        n_inter = sum(h["n_inter"] for h in heads)
-        alg_bytes_stream = 384 * n_mbs * n_pics + 384 * n_inter + job_bytes
-        alg_per_mb = alg_bytes_stream / (n_mbs * n_pics)
-        # dominant kernel: the one with the largest share of device time (chosen in the warm-up passes, where all five
-        # kernels are bracketed by events; in the timed region only this one is)
-        launches = max(k_n[dom], 1)
-        avg_launch_us = k_ms[dom] * 1e3 / launches
-        # every launch of every kernel covers one picture of every stream: the units of one launch are the
-        # macroblocks of one tick (SURVEY.md §8d per-MB figure x MBs per launch)
-        units_per_launch = n_mbs * n_pics * args.streams * args.steps / launches
-        achieved = alg_per_mb * units_per_launch / (avg_launch_us * 1e-6) / 1e9       # GB/s
-        path_gbs = alg_bytes_stream * args.streams * args.steps / (dev_total_ms * 1e-3) / 1e9
-        # `frac` above charges the WHOLE path's algorithmic bytes to the dominant kernel's time (the contract's formula).  frac_own prices
-        # every kernel against the bytes ITS OWN work has to move: tiles read and written by the macroblocks on
-        # its list, the records and coefficient blocks it consumes — per stream pass, from the frame-job headers.
-        n_coef_blocks = sum(h["n_coef_blocks"] for h in heads)
-        gen_mbs, intra_mbs, dbk_mbs = sum(h["n_gen"] for h in heads), sum(h["n_intra"] for h in heads), sum(h["n_dbk"] for h in heads)
-        coded_share = 32.0 * n_coef_blocks / max(1, gen_mbs + intra_mbs)         # coefficient bytes per reconstructed (non-copy) macroblock
-        own_bytes = {"k_copy": 768.0 * copy_mbs,
-                     "k_recon_inter": gen_mbs * (768.0 + 32.0 + coded_share),       # reference window + tile out + record + coefficients
-                     "k_dbk": dbk_mbs * (3 * 32.0 + 48.0 + 1.0),                     # own and two neighbour records in, deblocking record + flag out
-                     "k_frame_intra": intra_mbs * (384.0 + 32.0 + coded_share),
-                     "k_frame_dbk": 2 * dbk_mbs * 48.0 + dbk_mbs * 768.0}           # tile in and out (luma and chroma graph), the record for each graph
-        frac_own = {k: (own_bytes[k] * args.streams / (breakdown[k][0] * 1e-3) / 1e9 / HBM_PEAK_GBS if breakdown[k][0] > 0 else None) for k in kernels}
-        # HBM bytes per launch of the dominant kernel: PMC counters need rocprofv3 (separate --pmc passes,
-        # tools/refresh_profiles.sh), so they cannot be collected inside this run; the committed table is only used
-        # while it belongs to the kernels that just ran (sha256 of the kernel sources), otherwise traffic is null
-        traffic, traffic_note, traffic_all, traffic_whole = None, "no traffic table in profiles/", None, None
-        try:
-            import glob
-            tpath = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_traffic.json")))[-1]
-            tname = os.path.relpath(tpath, ROOT)
-            tfile = json.load(open(tpath))
-            from h264bsd_amd.srchash import kernel_source_sha256
-            src_sha = kernel_source_sha256(ROOT)
-            if tfile.get("kernel_source_sha256") != src_sha:
-                traffic_note = f"{tname} was measured with other kernel sources: stale, not reported (rerun tools/refresh_profiles.sh)"
-            else:
-                per_kernel = {k: v.get("fetch_bytes_per_launch_calibrated", v["fetch_bytes_per_launch"]) +
-                              v.get("write_bytes_per_launch_calibrated", v["write_bytes_per_launch"]) for k, v in tfile["kernels"].items() if k in kernels}
-                traffic = per_kernel[dom]
-                traffic_all = per_kernel
-                traffic_whole = sum(per_kernel.values())          # every kernel is launched once per tick: HBM bytes of one tick of the whole path
-                traffic_note = f"{tname}: FETCH_SIZE + WRITE_SIZE per launch, separate rocprofv3 --pmc passes of this command, calibrated on k_copy's known byte count"
-        except (OSError, KeyError, ValueError, IndexError):
-            pass
-        # the other roofline: wave-level vector instructions.  Counts per launch come from separate rocprofv3 --pmc passes
-        # (tools/sq_profile.sh -> profiles/rNN_sq_counters.json, valid for these kernel sources only), the cost of an instruction
-        # from tools/probes/valu_rate_probe.hip, the launch durations from THIS run (warm-up pass, all kernels bracketed)
-        valu = None
-        try:
-            import glob
-            vpath = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_sq_counters.json")))[-1]
-            vfile = json.load(open(vpath))
-            from h264bsd_amd.srchash import kernel_source_sha256
-            if vfile.get("kernel_source_sha256") != kernel_source_sha256(ROOT):
-                valu = {"note": f"{os.path.relpath(vpath, ROOT)} was measured with other kernel sources: stale, not reported (rerun tools/sq_profile.sh)"}
-            else:
-                cyc = float(vfile["cycles_per_wave_instruction"])
-                peak = 1024 * 2.4e9 / cyc                                     # 256 CUs x 4 SIMDs, wave64 instructions per second
-                scale = args.streams / float(vfile.get("streams", 256))
-                per = {}
-                for k in kernels:
-                    if k in vfile["kernels"] and breakdown[k][1]:
-                        n_i = vfile["kernels"][k]["valu_wave_instr_per_launch"] * scale
-                        t_s = breakdown[k][0] * 1e-3 / breakdown[k][1]
-                        per[k] = {"wave_instr_per_launch": n_i, "avg_launch_us": t_s * 1e6, "achieved": n_i / t_s, "frac": n_i / t_s / peak,
-                                  "wave_instr_per_macroblock": n_i / (n_mbs * args.streams),
-                                  "lane_util": (vfile["kernels"][k].get("active_lanes_per_valu_instr") or 0.0) / 64.0}
-                tot_i = sum(v["wave_instr_per_launch"] for v in per.values())
-                valu = {"peak_wave_instr_per_s": peak, "cycles_per_wave_instruction": cyc, "source": os.path.relpath(vpath, ROOT),
-                        "per_kernel": per, "whole_path": {"wave_instr_per_tick": tot_i, "achieved": tot_i * n_pics * args.steps / (dev_total_ms * 1e-3),
-                                                          "frac": tot_i * n_pics * args.steps / (dev_total_ms * 1e-3) / peak,
-                                                          "note": "every kernel runs once per tick; k_copy and k_dbk run on streams of their own beside k_recon_inter, so the kernel times add up to more than the total"}}
-        except (OSError, KeyError, ValueError, IndexError, ZeroDivisionError):
-            pass
-        moved_per_mb = alg_per_mb - 768.0 * (copy_mbs_full - copy_mbs) / (n_mbs * n_pics)
         out = {
             "metric": "1080p macroblocks/s", "value": mbs / elapsed, "unit": "macroblocks/s",
             "fps": pics_per_step * args.steps / elapsed,
@@ -677,90 +633,170 @@ def main():
             "vs_baseline": None, "dtype": "u8", "data": "synthetic",
             "config": {"workload": f"{args.streams} concurrent copies of {STREAM}.h264 per GPU "
                                    f"({n_pics} pictures x {n_mbs} MB), kernel-only replay from HBM-resident frame jobs, "
-                                   "inter+intra reconstruction + in-loop deblocking, bit-exact vs reference verified on device",
+                                   "inter+intra reconstruction + in-loop deblocking" + (", bit-exact vs reference verified on device" if args.full else ""),
                        "streams_per_gpu": args.streams, "pictures_per_step": pics_per_step, "parallelism": f"streams/{world}",
                        "stream_groups": args.groups,
                        "row_bands": os.environ.get("H264BSDMI_TAIL", "library default (engine.hip TailConfig)"),
                        "copy_elision": {"on": elide, "copy_mbs_per_stream_pass": copy_mbs_full, "elided": copy_mbs_full - copy_mbs,
                                         "note": "the parser leaves out whole-tile copies whose destination frame buffer already holds the "
                                                 "source's bytes (unchanged since the buffer's previous picture, untouched by deblocking): "
-                                                "same pictures, verified on device; alg_bytes_per_mb below still counts them (SURVEY 8d formula), "
+                                                "same pictures, verified on device by --full; alg_bytes_per_mb in `roofline` still counts them (SURVEY 8d formula), "
                                                 "alg_bytes_per_mb_moved does not"}},
-            "roofline": {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS,
-                         "frac_note": "`frac` = the contract's formula: the WHOLE path's algorithmic bytes per launch / the dominant kernel's launch time / peak; "
-                                      "`frac_own` = the dominant kernel's OWN algorithmic bytes / its own time / peak; `whole_path_frac` = the whole path's bytes / the whole step / peak",
-                         "frac_own": frac_own[dom], "frac_own_per_kernel": frac_own,
-                         "own_alg_bytes_per_stream_pass": own_bytes,
-                         "traffic": traffic, "traffic_source": traffic_note,
-                         "traffic_per_kernel": traffic_all, "traffic_whole_path": traffic_whole,
-                         "traffic_ratio": (traffic_whole / (alg_per_mb * units_per_launch)) if traffic_whole else None,
-                         "alg_bytes_per_launch": alg_per_mb * units_per_launch,
-                         "alg_bytes_per_mb": alg_per_mb, "alg_bytes_per_mb_moved": alg_per_mb - 768.0 * (copy_mbs_full - copy_mbs) / (n_mbs * n_pics),
-                         "mbs_per_launch": units_per_launch,
-                         "avg_launch_us": avg_launch_us, "launches": launches,
-                         "whole_path_GBs": path_gbs, "whole_path_frac": path_gbs / HBM_PEAK_GBS,
-                         "whole_path_GBs_moved": path_gbs * moved_per_mb / alg_per_mb, "whole_path_frac_moved": path_gbs * moved_per_mb / alg_per_mb / HBM_PEAK_GBS,
-                         "valu": valu,
-                         "copy_ceiling_GBs": copy_gbs, "frac_of_copy_ceiling": achieved / copy_gbs,
-                         "whole_path_frac_of_copy_ceiling": path_gbs / copy_gbs,
-                         "device_ms_per_step": dict({k: breakdown[k][0] for k in kernels}, total=dev_total_ms / args.steps,
-                                                    note="per-kernel: last untimed warm-up pass (all kernels bracketed by events); total: timed steps; k_copy and k_dbk run on streams of their own beside k_recon_inter (its time includes their interference), so the kernel times add up to more than the total"),
-                         "launches_per_step": {k: k_n[k] // args.steps for k in kernels}},
         }
-        if "groups4_elapsed" in lock_extra:
-            ge = lock_extra["groups4_elapsed"]
-            out["lock_step_4_stream_groups"] = {"value": n_pics * args.streams * n_mbs * side_steps / ge, "unit": "macroblocks/s",
-                                                "ms_per_step": ge * 1e3 / side_steps, "steps": side_steps,
-                                                "note": "rank 0's own clock; same work as `value`, streams split into 4 groups on 4 HIP streams"}
-        if full_copies is not None:
-            out["lock_step_without_copy_elision"] = {
-                "value": pics_per_step * n_mbs * side_steps / full_copies["elapsed"], "unit": "macroblocks/s",
-                "ms_per_step": full_copies["elapsed"] * 1e3 / side_steps, "steps": side_steps,
-                "device_ms_per_step": dict({k: full_copies["breakdown"][k][0] for k in kernels}, total=full_copies["dev_ms"] / side_steps),
-                "note": "frame jobs captured with h264bsdmiSetCopyElision(0): every copy macroblock is copied; verified on device like `value`"}
-        if staggered is not None:
-            # same work per step, odd streams start at the second IDR: I pictures never fill a whole tick
-            side_mbs = pics_per_step * n_mbs * side_steps
-            st_gbs = alg_bytes_stream * args.streams * world * side_steps / staggered["elapsed"] / 1e9
-            out["staggered"] = {"value": side_mbs / staggered["elapsed"], "unit": "macroblocks/s",
-                                "fps": pics_per_step * side_steps / staggered["elapsed"],
-                                "ms_per_step": staggered["elapsed"] * 1e3 / side_steps, "steps": side_steps,
-                                "odd_stream_offset_pictures": staggered["odd_stream_offset"],
-                                "vs_lock_step": side_mbs / staggered["elapsed"] / (mbs / elapsed),
-                                "whole_path_GBs": st_gbs, "whole_path_frac": st_gbs / HBM_PEAK_GBS / world,
-                                "whole_path_frac_moved": st_gbs * moved_per_mb / alg_per_mb / HBM_PEAK_GBS / world,
-                                "device_ms_per_step": dict({k: staggered["breakdown"][k][0] for k in kernels},
-                                                           total=staggered["dev_ms"] / side_steps)}
-        if argb is not None:
-            # config 3: algorithmic bytes per macroblock + 1024 (32-bit pixels written); k_convert's own roofline:
-            # 384 B read + 1024 B written per macroblock, every launch covers one picture of every stream
-            a_launches = max(argb["conv_n"], 1)
-            conv_us = argb["conv_ms"] * 1e3 / a_launches
-            conv_bytes = (384 + 1024) * n_mbs * args.streams
-            out["argb"] = {"value": pics_per_step * n_mbs * side_steps / argb["elapsed"], "unit": "macroblocks/s", "fps": pics_per_step * side_steps / argb["elapsed"],
-                           "ms_per_step": argb["elapsed"] * 1e3 / side_steps, "steps": side_steps, "format": "BGRA (the reference's ARGB word, h264bsdConvertToBGRA)",
-                           "alg_bytes_per_mb": alg_per_mb + 1024,
-                           "whole_path_GBs": (alg_bytes_stream + 1024 * n_mbs * n_pics) * args.streams * side_steps / (argb["dev_ms"] * 1e-3) / 1e9,
-                           "conversion": {"ticks_hosted_by_the_next_ticks_k_frame_dbk": n_pics * side_steps - argb["conv_n"], "ticks_followed_by_a_k_convert_tiles_launch": argb["conv_n"],
-                                          "hosted_pictures_checked_against_the_reference": argb["hosted_checked"]},
-                           "k_convert": {"avg_launch_us": conv_us, "launches": argb["conv_n"], "alg_bytes_per_launch": conv_bytes,
-                                         "achieved_GBs": conv_bytes / (conv_us * 1e-6) / 1e9, "frac": conv_bytes / (conv_us * 1e-6) / 1e9 / HBM_PEAK_GBS}}
-        if per_gpu is not None:
-            out["per_gpu"] = {"value": per_gpu, "unit": "macroblocks/s", "note": "lock-step variant, each rank's own clock over the timed steps"}
-        if desync is not None:
-            # the same algorithmic bytes per lap as a lock-step step: fraction of the HBM peak and of the lock-step value
-            for key, d in desync.items():
-                if isinstance(d, dict):
-                    d["whole_path_GBs"] = alg_bytes_stream * args.streams * world / (d["ms_per_step"] * 1e-3) / 1e9
-                    d["whole_path_frac"] = d["whole_path_GBs"] / HBM_PEAK_GBS / world
-                    d["whole_path_frac_moved"] = d["whole_path_frac"] * moved_per_mb / alg_per_mb      # (the copies that elision leaves out do not move)
-                    d["vs_lock_step"] = d["value"] / (mbs / elapsed)
-            out["desynchronised"] = desync
-        for key, leg in e2e.items():
-            out[key] = leg
+        if args.full:
+            # algorithmic bytes: 384 B written per MB + 384 B of reference read per inter MB +
+            # the packed syntax actually consumed (the frame jobs)
+            n_inter = sum(h["n_inter"] for h in heads)
+            alg_bytes_stream = 384 * n_mbs * n_pics + 384 * n_inter + job_bytes
+            alg_per_mb = alg_bytes_stream / (n_mbs * n_pics)
+            # dominant kernel: the one with the largest share of device time (chosen in the warm-up passes, where all five
+            # kernels are bracketed by events; in the timed region only this one is)
+            launches = max(k_n[dom], 1)
+            avg_launch_us = k_ms[dom] * 1e3 / launches
+            # every launch of every kernel covers one picture of every stream: the units of one launch are the
+            # macroblocks of one tick (SURVEY.md §8d per-MB figure x MBs per launch)
+            units_per_launch = n_mbs * n_pics * args.streams * args.steps / launches
+            achieved = alg_per_mb * units_per_launch / (avg_launch_us * 1e-6) / 1e9       # GB/s
+            path_gbs = alg_bytes_stream * args.streams * args.steps / (dev_total_ms * 1e-3) / 1e9
+            # `frac` above charges the WHOLE path's algorithmic bytes to the dominant kernel's time (the contract's formula).  frac_own prices
+            # every kernel against the bytes ITS OWN work has to move: tiles read and written by the macroblocks on
+            # its list, the records and coefficient blocks it consumes — per stream pass, from the frame-job headers.
+            n_coef_blocks = sum(h["n_coef_blocks"] for h in heads)
+            gen_mbs, intra_mbs, dbk_mbs = sum(h["n_gen"] for h in heads), sum(h["n_intra"] for h in heads), sum(h["n_dbk"] for h in heads)
+            coded_share = 32.0 * n_coef_blocks / max(1, gen_mbs + intra_mbs)         # coefficient bytes per reconstructed (non-copy) macroblock
+            own_bytes = {"k_copy": 768.0 * copy_mbs,
+                         "k_recon_inter": gen_mbs * (768.0 + 32.0 + coded_share),       # reference window + tile out + record + coefficients
+                         "k_dbk": dbk_mbs * (3 * 32.0 + 48.0 + 1.0),                     # own and two neighbour records in, deblocking record + flag out
+                         "k_frame_intra": intra_mbs * (384.0 + 32.0 + coded_share),
+                         "k_frame_dbk": 2 * dbk_mbs * 48.0 + dbk_mbs * 768.0}           # tile in and out (luma and chroma graph), the record for each graph
+            frac_own = {k: (own_bytes[k] * args.streams / (breakdown[k][0] * 1e-3) / 1e9 / HBM_PEAK_GBS if breakdown[k][0] > 0 else None) for k in kernels}
+            # HBM bytes per launch of the dominant kernel: PMC counters need rocprofv3 (separate --pmc passes,
+            # tools/refresh_profiles.sh), so they cannot be collected inside this run; the committed table is only used
+            # while it belongs to the kernels that just ran (sha256 of the kernel sources), otherwise traffic is null
+            traffic, traffic_note, traffic_all, traffic_whole = None, "no traffic table in profiles/", None, None
+            try:
+                import glob
+                tpath = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_traffic.json")))[-1]
+                tname = os.path.relpath(tpath, ROOT)
+                tfile = json.load(open(tpath))
+                from h264bsd_amd.srchash import kernel_source_sha256
+                src_sha = kernel_source_sha256(ROOT)
+                if tfile.get("kernel_source_sha256") != src_sha:
+                    traffic_note = f"{tname} was measured with other kernel sources: stale, not reported (rerun tools/refresh_profiles.sh)"
+                else:
+                    per_kernel = {k: v.get("fetch_bytes_per_launch_calibrated", v["fetch_bytes_per_launch"]) +
+                                  v.get("write_bytes_per_launch_calibrated", v["write_bytes_per_launch"]) for k, v in tfile["kernels"].items() if k in kernels}
+                    traffic = per_kernel[dom]
+                    traffic_all = per_kernel
+                    traffic_whole = sum(per_kernel.values())          # every kernel is launched once per tick: HBM bytes of one tick of the whole path
+                    traffic_note = f"{tname}: FETCH_SIZE + WRITE_SIZE per launch, separate rocprofv3 --pmc passes of this command, calibrated on k_copy's known byte count"
+            except (OSError, KeyError, ValueError, IndexError):
+                pass
+            # the other roofline: wave-level vector instructions.  Counts per launch come from separate rocprofv3 --pmc passes
+            # (tools/sq_profile.sh -> profiles/rNN_sq_counters.json, valid for these kernel sources only), the cost of an instruction
+            # from tools/probes/valu_rate_probe.hip, the launch durations from THIS run (warm-up pass, all kernels bracketed)
+            valu = None
+            try:
+                import glob
+                vpath = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_sq_counters.json")))[-1]
+                vfile = json.load(open(vpath))
+                from h264bsd_amd.srchash import kernel_source_sha256
+                if vfile.get("kernel_source_sha256") != kernel_source_sha256(ROOT):
+                    valu = {"note": f"{os.path.relpath(vpath, ROOT)} was measured with other kernel sources: stale, not reported (rerun tools/sq_profile.sh)"}
+                else:
+                    cyc = float(vfile["cycles_per_wave_instruction"])
+                    peak = 1024 * 2.4e9 / cyc                                     # 256 CUs x 4 SIMDs, wave64 instructions per second
+                    scale = args.streams / float(vfile.get("streams", 256))
+                    per = {}
+                    for k in kernels:
+                        if k in vfile["kernels"] and breakdown[k][1]:
+                            n_i = vfile["kernels"][k]["valu_wave_instr_per_launch"] * scale
+                            t_s = breakdown[k][0] * 1e-3 / breakdown[k][1]
+                            per[k] = {"wave_instr_per_launch": n_i, "avg_launch_us": t_s * 1e6, "achieved": n_i / t_s, "frac": n_i / t_s / peak,
+                                      "wave_instr_per_macroblock": n_i / (n_mbs * args.streams),
+                                      "lane_util": (vfile["kernels"][k].get("active_lanes_per_valu_instr") or 0.0) / 64.0}
+                    tot_i = sum(v["wave_instr_per_launch"] for v in per.values())
+                    valu = {"peak_wave_instr_per_s": peak, "cycles_per_wave_instruction": cyc, "source": os.path.relpath(vpath, ROOT),
+                            "per_kernel": per, "whole_path": {"wave_instr_per_tick": tot_i, "achieved": tot_i * n_pics * args.steps / (dev_total_ms * 1e-3),
+                                                              "frac": tot_i * n_pics * args.steps / (dev_total_ms * 1e-3) / peak,
+                                                              "note": "every kernel runs once per tick; k_copy and k_dbk run on streams of their own beside k_recon_inter, so the kernel times add up to more than the total"}}
+            except (OSError, KeyError, ValueError, IndexError, ZeroDivisionError):
+                pass
+            moved_per_mb = alg_per_mb - 768.0 * (copy_mbs_full - copy_mbs) / (n_mbs * n_pics)
+            out["roofline"] = {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                               "frac": achieved / HBM_PEAK_GBS,
+                               "frac_note": "`frac` = the contract's formula: the WHOLE path's algorithmic bytes per launch / the dominant kernel's launch time / peak; "
+                                            "`frac_own` = the dominant kernel's OWN algorithmic bytes / its own time / peak; `whole_path_frac` = the whole path's bytes / the whole step / peak",
+                               "frac_own": frac_own[dom], "frac_own_per_kernel": frac_own,
+                               "own_alg_bytes_per_stream_pass": own_bytes,
+                               "traffic": traffic, "traffic_source": traffic_note,
+                               "traffic_per_kernel": traffic_all, "traffic_whole_path": traffic_whole,
+                               "traffic_ratio": (traffic_whole / (alg_per_mb * units_per_launch)) if traffic_whole else None,
+                               "alg_bytes_per_launch": alg_per_mb * units_per_launch,
+                               "alg_bytes_per_mb": alg_per_mb, "alg_bytes_per_mb_moved": alg_per_mb - 768.0 * (copy_mbs_full - copy_mbs) / (n_mbs * n_pics),
+                               "mbs_per_launch": units_per_launch,
+                               "avg_launch_us": avg_launch_us, "launches": launches,
+                               "whole_path_GBs": path_gbs, "whole_path_frac": path_gbs / HBM_PEAK_GBS,
+                               "whole_path_GBs_moved": path_gbs * moved_per_mb / alg_per_mb, "whole_path_frac_moved": path_gbs * moved_per_mb / alg_per_mb / HBM_PEAK_GBS,
+                               "valu": valu,
+                               "copy_ceiling_GBs": copy_gbs, "frac_of_copy_ceiling": achieved / copy_gbs,
+                               "whole_path_frac_of_copy_ceiling": path_gbs / copy_gbs,
+                               "device_ms_per_step": dict({k: breakdown[k][0] for k in kernels}, total=dev_total_ms / args.steps,
+                                                          note="per-kernel: last untimed warm-up pass (all kernels bracketed by events); total: timed steps; k_copy and k_dbk run on streams of their own beside k_recon_inter (its time includes their interference), so the kernel times add up to more than the total"),
+                               "launches_per_step": {k: k_n[k] // args.steps for k in kernels}}
+            if "groups4_elapsed" in lock_extra:
+                ge = lock_extra["groups4_elapsed"]
+                out["lock_step_4_stream_groups"] = {"value": n_pics * args.streams * n_mbs * side_steps / ge, "unit": "macroblocks/s",
+                                                    "ms_per_step": ge * 1e3 / side_steps, "steps": side_steps,
+                                                    "note": "rank 0's own clock; same work as `value`, streams split into 4 groups on 4 HIP streams"}
+            if full_copies is not None:
+                out["lock_step_without_copy_elision"] = {
+                    "value": pics_per_step * n_mbs * side_steps / full_copies["elapsed"], "unit": "macroblocks/s",
+                    "ms_per_step": full_copies["elapsed"] * 1e3 / side_steps, "steps": side_steps,
+                    "device_ms_per_step": dict({k: full_copies["breakdown"][k][0] for k in kernels}, total=full_copies["dev_ms"] / side_steps),
+                    "note": "frame jobs captured with h264bsdmiSetCopyElision(0): every copy macroblock is copied; verified on device like `value`"}
+            if staggered is not None:
+                # same work per step, odd streams start at the second IDR: I pictures never fill a whole tick
+                side_mbs = pics_per_step * n_mbs * side_steps
+                st_gbs = alg_bytes_stream * args.streams * world * side_steps / staggered["elapsed"] / 1e9
+                out["staggered"] = {"value": side_mbs / staggered["elapsed"], "unit": "macroblocks/s",
+                                    "fps": pics_per_step * side_steps / staggered["elapsed"],
+                                    "ms_per_step": staggered["elapsed"] * 1e3 / side_steps, "steps": side_steps,
+                                    "odd_stream_offset_pictures": staggered["odd_stream_offset"],
+                                    "vs_lock_step": side_mbs / staggered["elapsed"] / (mbs / elapsed),
+                                    "whole_path_GBs": st_gbs, "whole_path_frac": st_gbs / HBM_PEAK_GBS / world,
+                                    "whole_path_frac_moved": st_gbs * moved_per_mb / alg_per_mb / HBM_PEAK_GBS / world,
+                                    "device_ms_per_step": dict({k: staggered["breakdown"][k][0] for k in kernels},
+                                                               total=staggered["dev_ms"] / side_steps)}
+            if argb is not None:
+                # config 3: algorithmic bytes per macroblock + 1024 (32-bit pixels written); k_convert's own roofline:
+                # 384 B read + 1024 B written per macroblock, every launch covers one picture of every stream
+                a_launches = max(argb["conv_n"], 1)
+                conv_us = argb["conv_ms"] * 1e3 / a_launches
+                conv_bytes = (384 + 1024) * n_mbs * args.streams
+                out["argb"] = {"value": pics_per_step * n_mbs * side_steps / argb["elapsed"], "unit": "macroblocks/s", "fps": pics_per_step * side_steps / argb["elapsed"],
+                               "ms_per_step": argb["elapsed"] * 1e3 / side_steps, "steps": side_steps, "format": "BGRA (the reference's ARGB word, h264bsdConvertToBGRA)",
+                               "alg_bytes_per_mb": alg_per_mb + 1024,
+                               "whole_path_GBs": (alg_bytes_stream + 1024 * n_mbs * n_pics) * args.streams * side_steps / (argb["dev_ms"] * 1e-3) / 1e9,
+                               "conversion": {"ticks_hosted_by_the_next_ticks_k_frame_dbk": n_pics * side_steps - argb["conv_n"], "ticks_followed_by_a_k_convert_tiles_launch": argb["conv_n"],
+                                              "hosted_pictures_checked_against_the_reference": argb["hosted_checked"]},
+                               "k_convert": {"avg_launch_us": conv_us, "launches": argb["conv_n"], "alg_bytes_per_launch": conv_bytes,
+                                             "achieved_GBs": conv_bytes / (conv_us * 1e-6) / 1e9, "frac": conv_bytes / (conv_us * 1e-6) / 1e9 / HBM_PEAK_GBS}}
+            if per_gpu is not None:
+                out["per_gpu"] = {"value": per_gpu, "unit": "macroblocks/s", "note": "lock-step variant, each rank's own clock over the timed steps"}
+            if desync is not None:
+                # the same algorithmic bytes per lap as a lock-step step: fraction of the HBM peak and of the lock-step value
+                for key, d in desync.items():
+                    if isinstance(d, dict):
+                        d["whole_path_GBs"] = alg_bytes_stream * args.streams * world / (d["ms_per_step"] * 1e-3) / 1e9
+                        d["whole_path_frac"] = d["whole_path_GBs"] / HBM_PEAK_GBS / world
+                        d["whole_path_frac_moved"] = d["whole_path_frac"] * moved_per_mb / alg_per_mb      # (the copies that elision leaves out do not move)
+                        d["vs_lock_step"] = d["value"] / (mbs / elapsed)
+                out["desynchronised"] = desync
+            for key, leg in e2e.items():
+                out[key] = leg
         out["device_errors"] = h264bsd_amd.device_errors()
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(data)
         print(json.dumps(out), flush=True)
     if dist is not None:

@@ -7,7 +7,7 @@ timeout 900 python -m pytest tests/test_gpu_random_jobs.py tests/test_gpu_parity
 tail -5 $out/tests.log
 for cfg in "0,0,12,0,0,12" "17,9,4,0,9,4" "0,0,4,0,0,4" "17,17,4,0,17,4" "9,9,4,0,9,4" "17,9,6,0,9,6" "34,17,4,0,17,4" "17,9,3,0,9,3"; do
   echo "== $cfg"
-  H264BSDMI_TAIL=$cfg timeout 300 python bench.py --steps 3 --warmup 1 --ramp-seconds 2 --no-cpu-baseline --no-staggered --no-desync --no-argb --no-end-to-end 2> $out/err_$cfg.log | tail -1 > $out/b_$cfg.json
+  H264BSDMI_TAIL=$cfg timeout 300 python bench.py --full --steps 3 --warmup 1 --ramp-seconds 2 --no-cpu-baseline --no-staggered --no-desync --no-argb --no-end-to-end 2> $out/err_$cfg.log | tail -1 > $out/b_$cfg.json
   python - "$out/b_$cfg.json" <<'P'
 import sys, json
 try:

@@ -5,7 +5,7 @@ out=gpurun_out/groups2; rm -rf $out; mkdir -p $out
 run() {  # name, env..., -- bench args
   name=$1; shift
   echo "== $name"
-  env "$@" timeout 300 python bench.py --steps 3 --warmup 1 --ramp-seconds 2 --no-cpu-baseline --no-staggered --no-desync --no-argb --no-end-to-end --no-groups-variant --no-full-copies-variant $EXTRA 2> $out/err_$name.log | tail -1 > $out/b_$name.json
+  env "$@" timeout 300 python bench.py --full --steps 3 --warmup 1 --ramp-seconds 2 --no-cpu-baseline --no-staggered --no-desync --no-argb --no-end-to-end --no-groups-variant --no-full-copies-variant $EXTRA 2> $out/err_$name.log | tail -1 > $out/b_$name.json
   python - "$out/b_$name.json" <<'P'
 import sys, json
 try:
@@ -29,9 +29,9 @@ EXTRA="--groups 4" run g4_w8_bands H264BSDMI_TAIL=17,9,8,0,9,8
 EXTRA="--groups 4" run g4_w4_bands H264BSDMI_TAIL=17,9,4,0,9,4
 EXTRA="--groups 8" run g8_w6_bands H264BSDMI_TAIL=17,9,6,0,9,6
 echo "== full default (desync legs)"
-timeout 600 python bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-end-to-end --no-argb 2> $out/err_full.log | tail -1 > $out/full.json
+timeout 600 python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-end-to-end --no-argb 2> $out/err_full.log | tail -1 > $out/full.json
 echo "== full, bands off"
-H264BSDMI_BAND_BUDGET=0 timeout 600 python bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-end-to-end --no-argb 2> $out/err_full_nb.log | tail -1 > $out/full_nb.json
+H264BSDMI_BAND_BUDGET=0 timeout 600 python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-end-to-end --no-argb 2> $out/err_full_nb.log | tail -1 > $out/full_nb.json
 python - <<'P'
 import json
 for n in ("full", "full_nb"):

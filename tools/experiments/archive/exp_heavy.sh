@@ -3,7 +3,7 @@ set -u
 out=gpurun_out/heavy; rm -rf $out; mkdir -p $out
 one() {
   name=$1; shift
-  env "$@" timeout 400 python bench.py --steps 5 --side-steps 5 --warmup 1 --ramp-seconds 2 --no-cpu-baseline ${DESYNC:---no-desync} --no-argb --no-end-to-end --no-groups-variant --no-full-copies-variant 2> $out/err_$name.log | tail -1 > $out/b.json
+  env "$@" timeout 400 python bench.py --full --steps 5 --side-steps 5 --warmup 1 --ramp-seconds 2 --no-cpu-baseline ${DESYNC:---no-desync} --no-argb --no-end-to-end --no-groups-variant --no-full-copies-variant 2> $out/err_$name.log | tail -1 > $out/b.json
   python - "$name" <<'P'
 import json, sys
 try:

@@ -6,7 +6,7 @@ for i in 1 2; do
 timeout 300 python tools/experiments/hostout.py timeline 2>&1 | tail -1
 H264BSDMI_THREADS=20 timeout 300 python tools/experiments/hostout.py timeline 2>&1 | tail -1
 done
-timeout 300 python bench.py --steps 2 --ramp-seconds 1 --no-cpu-baseline --no-staggered --no-desync --no-argb --no-groups-variant --no-full-copies-variant 2>&1 | tail -1 | python -c "
+timeout 300 python bench.py --full --steps 2 --ramp-seconds 1 --no-cpu-baseline --no-staggered --no-desync --no-argb --no-groups-variant --no-full-copies-variant 2>&1 | tail -1 | python -c "
 import sys, json
 d = json.loads(sys.stdin.read())
 for k in ('end_to_end', 'end_to_end_host_output'): print(k, round(d[k]['fps']), 'fps', d[k]['parser_threads'], 'threads')"
