@@ -28,7 +28,7 @@ EXPORTED_SYMBOLS = [
     "h264bsdCroppingParams", "h264bsdSampleAspectRatio", "h264bsdCheckValidParamSets", "h264bsdFlushBuffer",
     "h264bsdProfile", "h264bsdAlloc", "h264bsdFree", "h264bsdConvertToRGBA", "h264bsdConvertToBGRA",
     "h264bsdConvertToYCbCrA",
-    "h264bsdmiInitCapture", "h264bsdmiNextOutputInfo", "h264bsdmiNextOutputPictureDevice", "h264bsdmiJobFinalize", "h264bsdmiDeviceCount", "h264bsdmiSetDevice", "h264bsdmiFlush", "h264bsdmiFlushAsync", "h264bsdmiDeviceErrors",
+    "h264bsdmiInitCapture", "h264bsdmiNextOutputInfo", "h264bsdmiNextOutputPictureDevice", "h264bsdmiNextOutputTensorBatch", "h264bsdmiJobFinalize", "h264bsdmiDeviceCount", "h264bsdmiSetDevice", "h264bsdmiFlush", "h264bsdmiFlushAsync", "h264bsdmiDeviceErrors",
     "h264bsdmiDecodePicture", "h264bsdmiDecodePictureBatch", "h264bsdmiNextOutputPictureBatch", "h264bsdmiPullAndDecodePictureBatch", "h264bsdmiSetParserThreads", "h264bsdmiSetInputReadOnly", "h264bsdmiSetCopyElision",
     "h264bsdmiReplayCreate", "h264bsdmiReplayCreateStaggered", "h264bsdmiReplayCreateDesync", "h264bsdmiReplayCreateSched", "h264bsdmiReplayReschedule", "h264bsdmiReplayDestroy", "h264bsdmiReplayRun", "h264bsdmiReplaySync",
     "h264bsdmiReplayFetch", "h264bsdmiReplayChecksums", "h264bsdmiReplayConvert", "h264bsdmiReplayFetchConverted",
@@ -43,6 +43,17 @@ class DevicePicture(ctypes.Structure):
 
 
 FMT_RGBA, FMT_BGRA, FMT_YCBCRA, FMT_I420 = 0, 1, 2, 3
+
+
+class TensorSpec(ctypes.Structure):
+    """h264bsdmi_tensor_spec (include/h264bsd_mi355x.h)"""
+    _fields_ = [("data", ctypes.c_void_p), ("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("layout", ctypes.c_uint32),
+                ("dtype", ctypes.c_uint32), ("channels", ctypes.c_uint32), ("crop", ctypes.c_uint32), ("resize", ctypes.c_uint32),
+                ("mean", ctypes.c_float * 3), ("std", ctypes.c_float * 3)]
+
+
+LAYOUTS = {"NCHW": 0, "NHWC": 1}
+CHANNELS = {"RGB": (0, 3), "BGR": (1, 3), "RGBA": (2, 4), "BGRA": (3, 4), "Y": (4, 1)}     # name -> (H264BSDMI_CH_*, channels)
 
 JOB_CB = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint8), ctypes.c_uint32)
 P32 = ctypes.POINTER(ctypes.c_uint32)
@@ -141,6 +152,8 @@ def _declare(L, harness):
     L.h264bsdmiNextOutputInfo.restype = ctypes.c_int
     L.h264bsdmiNextOutputPictureDevice.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DevicePicture)]
     L.h264bsdmiNextOutputPictureDevice.restype = ctypes.c_int
+    L.h264bsdmiNextOutputTensorBatch.argtypes = [u32, ctypes.POINTER(vp), ctypes.POINTER(TensorSpec), vp, P32, P32, P32, P32]
+    L.h264bsdmiNextOutputTensorBatch.restype = ctypes.c_int
     L.h264bsdmiDecodePicture.argtypes = [vp, u8p, u32, u32, P32, P32]
     L.h264bsdmiDecodePicture.restype = u32
     L.h264bsdmiDecodePictureBatch.argtypes = [u32, ctypes.POINTER(vp), ctypes.POINTER(vp), P32, P32, P32, P32, P32]
@@ -440,6 +453,55 @@ def pull_batch(decoders, frame_bytes=None):
         return ptrs, list(ids)
     views = [None if not p else np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctypes.c_uint8)), (frame_bytes,)) for p in ptrs]
     return views, list(ids)
+
+
+def pull_tensor(decoders, size=None, layout="NCHW", dtype=None, channels="RGB", mean=(0, 0, 0), std=(1, 1, 1), crop=True,
+                out=None, stream=None):
+    """h264bsdmiNextOutputTensorBatch: the next output picture of every decoder, written by one kernel launch into ONE dense CUDA
+    tensor, [N, C, H, W] (layout "NCHW") or [N, H, W, C] ("NHWC"), N = len(decoders), in torch.uint8 / float16 (default) / float32.
+    channels: "RGB", "BGR", "RGBA", "BGRA" (NHWC only) or "Y" (the luma samples).  Float outputs are (v / 255 - mean[c]) / std[c].
+    size: (height, width) or an int for a square; None = no resize, every source window (the SPS cropping window when crop, else
+    the coded frame) must have the size of the first decoder's; otherwise bilinear (align_corners=False, no antialiasing).
+    out: a contiguous CUDA tensor of that shape and dtype to write into (None: allocated); decoders that have no picture leave
+    their slice of it untouched.  stream: a torch.cuda.Stream (default: the current one) — the call returns without waiting,
+    the tensor is valid for work on that stream (torch's legacy default stream: the call waits).  Returns (tensor, got, pic_ids, is_idr, num_err_mbs), lists of ints."""
+    import torch
+    if dtype is None:
+        dtype = torch.float16
+    dtypes = {torch.uint8: 0, torch.float16: 1, torch.float32: 2}
+    if dtype not in dtypes or layout not in LAYOUTS or channels not in CHANNELS:
+        raise ValueError(f"pull_tensor: unsupported dtype / layout / channels {dtype} {layout} {channels}")
+    ch, C = CHANNELS[channels]
+    n = len(decoders)
+    if size is None:
+        geo = next((d for d in decoders if d.pic_width()), None)
+        if geo is None:
+            raise ValueError("pull_tensor: size=None needs a decoder that has seen a sequence parameter set")
+        flag, _, cw, _, chh = geo.cropping_params()
+        H, W = (chh, cw) if crop and flag else (16 * geo.pic_height(), 16 * geo.pic_width())
+    else:
+        H, W = (size, size) if isinstance(size, int) else (int(size[0]), int(size[1]))
+    shape = (n, C, H, W) if layout == "NCHW" else (n, H, W, C)
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device="cuda")
+    elif not out.is_cuda or out.dtype != dtype or tuple(out.shape) != shape or not out.is_contiguous():
+        raise ValueError(f"pull_tensor: out must be a contiguous CUDA {dtype} tensor of shape {shape}")
+    if stream is None:
+        stream = torch.cuda.current_stream(out.device)
+    if not stream.cuda_stream:
+        # torch's legacy default stream is handle 0, which the C call reads as "the library's own stream, wait": that stream is not
+        # ordered behind torch's work, so what is queued for `out` must be done before the call
+        stream.synchronize()
+    spec = TensorSpec(out.data_ptr(), W, H, LAYOUTS[layout], dtypes[dtype], ch, 1 if crop else 0, 0 if size is None else 1,
+                      (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std))
+    L = api_lib()
+    VP = ctypes.c_void_p * n
+    U32 = ctypes.c_uint32 * n
+    got, ids, idr, nerr = U32(), U32(), U32(), U32()
+    rc = L.h264bsdmiNextOutputTensorBatch(n, VP(*[d._st for d in decoders]), ctypes.byref(spec), stream.cuda_stream, got, ids, idr, nerr)
+    if rc != 0:
+        raise RuntimeError(f"h264bsdmiNextOutputTensorBatch failed ({rc})")
+    return out, list(got), list(ids), list(idr), list(nerr)
 
 
 def job_header(blob):

@@ -188,6 +188,56 @@ int h264bsdmiNextOutputPictureDevice(storage_t *s, int format, int crop, h264bsd
     return 1;
 }
 
+/* The next pictures of n instances into one caller-owned device tensor.  Everything that can be refused is refused before the first
+ * pop: the spec, the instances (bound to a device, distinct), every source window against the output size; the pictures are only
+ * popped once the engine has enqueued their layout. */
+int h264bsdmiNextOutputTensorBatch(u32 n, storage_t *const *dec, const h264bsdmi_tensor_spec *spec, void *stream,
+                                   u32 *got, u32 *picId, u32 *isIdrPic, u32 *numErrMbs)
+{
+    if (!dec || !spec || !got || !spec->data || !spec->width || !spec->height) return -1;
+    if (spec->layout > H264BSDMI_LAYOUT_NHWC || spec->dtype > H264BSDMI_DTYPE_F32 || spec->channels > H264BSDMI_CH_Y) return -1;
+    if (spec->layout == H264BSDMI_LAYOUT_NCHW && (spec->channels == H264BSDMI_CH_RGBA || spec->channels == H264BSDMI_CH_BGRA)) return -1;
+    for (int c = 0; c < 3; c++) {
+        if (spec->std[c] == 0.0f) return -1;
+        if (spec->dtype == H264BSDMI_DTYPE_U8 && (spec->mean[c] != 0.0f || spec->std[c] != 1.0f)) return -1;
+    }
+    if (!n) return 0;
+    SinkTensorPic *pics = (SinkTensorPic *)malloc(n * sizeof(SinkTensorPic));
+    if (!pics) return -1;
+    u32 m = 0;
+    int rc = 0;
+    for (u32 i = 0; i < n && !rc; i++) {
+        ApiDec *a = dec_of(dec[i]);
+        if (!a || !a->hd->sink.tensor_out) { rc = -1; break; }              /* capture mode: there are no pixels */
+        for (u32 k = 0; k < i; k++)
+            if (dec[k] == dec[i]) rc = -1;
+        const Dpb *d = &a->hd->dpb;
+        const Sps *sps = a->hd->active_sps;
+        if (rc || !sps || d->out_idx >= d->n_out) continue;                  /* nothing to give: got[i] = 0 */
+        u32 x0 = 0, y0 = 0, w = 16 * sps->width_mbs, h = 16 * sps->height_mbs;
+        if (spec->crop && sps->cropping) {
+            x0 = 2 * sps->crop_left;
+            y0 = 2 * sps->crop_top;
+            w -= 2 * (sps->crop_left + sps->crop_right);
+            h -= 2 * (sps->crop_top + sps->crop_bottom);
+        }
+        if (!spec->resize && (w != spec->width || h != spec->height)) { rc = -1; break; }
+        pics[m++] = (SinkTensorPic){ &a->hd->sink, d->out[d->out_idx].slot, i, x0, y0, w, h };
+    }
+    if (!rc && m && pics[0].sink->tensor_out(m, pics, spec, stream)) rc = -2;
+    free(pics);
+    if (rc) return rc;
+    for (u32 i = 0; i < n; i++) {
+        u32 id = 0, idr = 0, nerr = 0;
+        ApiDec *a = dec_of(dec[i]);
+        got[i] = a->hd->active_sps && pop_output(a, &id, &idr, &nerr) ? 1 : 0;
+        if (picId) picId[i] = id;
+        if (isIdrPic) isIdrPic[i] = idr;
+        if (numErrMbs) numErrMbs[i] = nerr;
+    }
+    return 0;
+}
+
 static u32 *next_converted(storage_t *s, u32 *picId, u32 *isIdrPic, u32 *numErrMbs, int fmt)
 {
     ApiDec *a = dec_of(s);

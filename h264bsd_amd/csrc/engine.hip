@@ -30,6 +30,7 @@
 #include <vector>
 #include <algorithm>
 #include "kernels.hip.h"
+#include "kernels/k_tensor_out.hip.h"
 #include "engine.h"
 #include "../../include/h264bsd_mi355x_bench.h"
 
@@ -48,6 +49,11 @@ namespace {
 constexpr int MAX_DEVICES = 16;
 struct PendingJob { uint8_t *host; uint32_t bytes, cap; const uint8_t *dev; };     /* dev: the device's address of the pinned buffer (k_h2d) */
 constexpr size_t MAX_QUEUED_PICTURES = 8;    /* per decoder instance, before sink_submit starts the device on its own */
+
+/* The completion of one h264bsdmiNextOutputTensorBatch call, shared by the instances it read from (tensor_out_locked): until it has
+ * passed, their frame buffers must neither be decoded into (lane_launch) nor freed (fence_drop).  Back to Engine.fences when no
+ * instance refers to it any more. */
+struct Fence { hipEvent_t ev = nullptr; unsigned refs = 0; };
 
 struct StreamCtx {
     uint32_t wmb = 0, hmb = 0, n_slots = 0, frame_bytes = 0;
@@ -69,6 +75,7 @@ struct StreamCtx {
     unsigned long long last_launch = 0;
     unsigned ready_round = 0;
     size_t flush_quota = 0;                 /* jobs that were queued when the current flush began: it takes no others (flush_locked) */
+    Fence *fence = nullptr;                 /* the latest tensor pull that read this instance's frames (nullptr: none outstanding) */
 };
 
 /* k_dbk (boundary strengths) needs only the frame job, not pixels: it runs on a second HIP stream next to the
@@ -161,6 +168,11 @@ struct Engine {
     uint32_t error_events = 0;                 /* how often a tripwire fired, ever: monotonic, so that a NEW occurrence of a bit that is
                                                   already set is visible (per-decoder copy-elision guard, the tests' delta) */
     unsigned long long *tail_prof = nullptr;   /* debug: per-wave cycle accounting of the per-picture kernels (block 0) */
+    /* tensor pulls (tensor_out_locked): items staged in pinned memory, two halves used in turn, each guarded by the event recorded
+     * behind the launch that read it; fence events that no instance holds any more */
+    h264k::TensorItem *h_titems = nullptr, *dv_titems = nullptr; size_t titem_cap = 0;
+    hipEvent_t titem_ev[2] = { nullptr, nullptr }; bool titem_used[2] = { false, false }; int titem_flip = 0;
+    std::vector<Fence *> fences;
 };
 
 /* One engine per HIP device, created on first use.  A decoder instance (or replay set) lives on the device that is
@@ -665,6 +677,21 @@ int reap_locked(Engine *e, bool wait)
     return 0;
 }
 
+/* s no longer refers to its fence; the fence goes back to the pool when no instance does */
+static void fence_unref(Engine *e, StreamCtx *s)
+{
+    Fence *f = s->fence;
+    if (!f) return;
+    s->fence = nullptr;
+    if (--f->refs == 0) e->fences.push_back(f);
+}
+/* s's frame buffers are about to be cleared or freed: a tensor pull that still reads them must finish first */
+static void fence_drop(Engine *e, StreamCtx *s)
+{
+    if (s->fence) (void)hipEventSynchronize(s->fence->ev);
+    fence_unref(e, s);
+}
+
 /* One tick on one lane: the front jobs of `part` (popped here) are copied to the lane's arena and launched. */
 static int lane_launch(Engine *e, unsigned lane_idx, const std::vector<StreamCtx *> &part)
 {
@@ -701,10 +728,18 @@ static int lane_launch(Engine *e, unsigned lane_idx, const std::vector<StreamCtx
     TickShape shape;
     size_t off = 0;
     std::vector<std::pair<int, unsigned long long>> waited;
+    std::vector<const Fence *> fenced;
     for (size_t i = 0; i < part.size(); i++) {
         StreamCtx *s = part[i];
         PendingJob j;
         { std::lock_guard<std::mutex> ql(s->qmu); j = s->pending.front(); s->pending.pop_front(); }
+        if (s->fence) {         /* a tensor pull (on the caller's stream) may still read the frame buffer this picture is decoded into */
+            if (hipEventQuery(s->fence->ev) == hipSuccess) fence_unref(e, s);
+            else if (std::find(fenced.begin(), fenced.end(), s->fence) == fenced.end()) {
+                HIP_TRY(hipStreamWaitEvent(l.st, s->fence->ev, 0));
+                fenced.push_back(s->fence);
+            }
+        }
         if (s->last_lane >= 0 && (unsigned)s->last_lane != lane_idx) {     /* its previous picture ran on another lane */
             const std::pair<int, unsigned long long> key(s->last_lane, s->last_launch);
             if (std::find(waited.begin(), waited.end(), key) == waited.end()) {
@@ -822,6 +857,7 @@ int sink_configure(void *user, uint32_t wmb, uint32_t hmb, uint32_t n_slots)
     if (flush_locked(u->e)) return -1;
     HIP_TRY(hipSetDevice(u->e->device));
     if (u->e->out_stream) HIP_TRY(hipStreamSynchronize(u->e->out_stream));
+    fence_drop(u->e, u->s);
     stream_release(u->s, true);
     u->s->wmb = wmb; u->s->hmb = hmb; u->s->n_slots = n_slots;
     u->s->frame_bytes = fj_frame_bytes(wmb, hmb);
@@ -1054,6 +1090,7 @@ void sink_close(void *user)
         reap_locked(u->e, true);
         hipStreamSynchronize(u->e->stream);
         if (u->e->out_stream) hipStreamSynchronize(u->e->out_stream);      /* (a pull that failed half way may have left its kernel behind) */
+        fence_drop(u->e, u->s);
         stream_release(u->s);
         auto &v = u->e->streams;
         v.erase(std::remove(v.begin(), v.end(), u->s), v.end());
@@ -1062,6 +1099,144 @@ void sink_close(void *user)
     delete u;
 }
 
+/* ---- the next pictures of many instances into one caller-owned tensor (h264bsdmiNextOutputTensorBatch) ---- */
+template <int DT, int L, int CH> static const void *tensor_kernel_of(bool resize)
+{
+    return resize ? reinterpret_cast<const void *>(&h264k::k_tensor_resize<DT, L, CH>) : reinterpret_cast<const void *>(&h264k::k_tensor_out<DT, L, CH>);
+}
+template <int DT, int L> static const void *tensor_kernel_ch(bool resize, uint32_t ch)
+{
+    switch (ch) {
+    case h264k::TO_RGB: return tensor_kernel_of<DT, L, h264k::TO_RGB>(resize);
+    case h264k::TO_BGR: return tensor_kernel_of<DT, L, h264k::TO_BGR>(resize);
+    case h264k::TO_Y: return tensor_kernel_of<DT, L, h264k::TO_Y>(resize);
+    }
+    if constexpr (L == h264k::TO_NHWC) {           /* four channels: interleaved only */
+        if (ch == h264k::TO_RGBA) return tensor_kernel_of<DT, L, h264k::TO_RGBA>(resize);
+        if (ch == h264k::TO_BGRA) return tensor_kernel_of<DT, L, h264k::TO_BGRA>(resize);
+    }
+    return nullptr;
+}
+template <int DT> static const void *tensor_kernel_layout(bool resize, uint32_t layout, uint32_t ch)
+{
+    if (layout == h264k::TO_NCHW) return tensor_kernel_ch<DT, h264k::TO_NCHW>(resize, ch);
+    if (layout == h264k::TO_NHWC) return tensor_kernel_ch<DT, h264k::TO_NHWC>(resize, ch);
+    return nullptr;
+}
+static const void *tensor_kernel(const h264bsdmi_tensor_spec &t)
+{
+    switch (t.dtype) {
+    case h264k::TO_U8: return tensor_kernel_layout<h264k::TO_U8>(t.resize != 0, t.layout, t.channels);
+    case h264k::TO_F16: return tensor_kernel_layout<h264k::TO_F16>(t.resize != 0, t.layout, t.channels);
+    case h264k::TO_F32: return tensor_kernel_layout<h264k::TO_F32>(t.resize != 0, t.layout, t.channels);
+    }
+    return nullptr;
+}
+
+/* Under the engine's mutex.  Ordering without host waits: the instances' queued jobs are enqueued once for the batch, the output
+ * stream waits for each picture's producing tick (deduplicated per lane launch, as lane_launch does), ONE launch lays out every
+ * picture, and a fence recorded behind it is handed to every instance: lane_launch makes an instance's next tick wait for it, and
+ * the frame buffers are not cleared or freed before it has passed (fence_drop).  *fence_ev: the fence's event. */
+static int tensor_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, const h264bsdmi_tensor_spec &t, hipStream_t st, hipEvent_t *fence_ev)
+{
+    const void *fn = tensor_kernel(t);
+    if (!fn) return -1;
+    for (uint32_t i = 0; i < n; i++) {
+        const StreamCtx *s = static_cast<SinkUser *>(pics[i].sink->user)->s;
+        const SinkTensorPic &p = pics[i];
+        if (p.slot >= s->n_slots || !s->d_frames || !p.w || !p.h || p.x0 + p.w > s->wmb * 16 || p.y0 + p.h > s->hmb * 16) return -1;
+    }
+    bool mine = false;
+    for (uint32_t i = 0; i < n && !mine; i++) {
+        StreamCtx *s = static_cast<SinkUser *>(pics[i].sink->user)->s;
+        std::lock_guard<std::mutex> ql(s->qmu);
+        mine = !s->pending.empty();
+    }
+    if (mine && flush_locked(e, false)) return -1;
+    if (n > e->titem_cap) {
+        for (int k = 0; k < 2; k++)
+            if (e->titem_used[k]) HIP_TRY(hipEventSynchronize(e->titem_ev[k]));
+        if (e->h_titems) HIP_TRY(hipHostFree(e->h_titems));
+        e->h_titems = e->dv_titems = nullptr; e->titem_cap = 0;
+        const size_t cap = std::max<size_t>(n, 256);
+        HIP_TRY(hipHostMalloc((void **)&e->h_titems, 2 * cap * sizeof(h264k::TensorItem), hipHostMallocDefault));
+        HIP_TRY(hipHostGetDevicePointer((void **)&e->dv_titems, e->h_titems, 0));
+        for (int k = 0; k < 2; k++)
+            if (!e->titem_ev[k]) HIP_TRY(hipEventCreateWithFlags(&e->titem_ev[k], hipEventDisableTiming));
+        e->titem_cap = cap; e->titem_used[0] = e->titem_used[1] = false; e->titem_flip = 0;
+    }
+    const int f = e->titem_flip;
+    if (e->titem_used[f]) HIP_TRY(hipEventSynchronize(e->titem_ev[f]));      /* the launch before the last one read this half */
+    h264k::TensorItem *items = e->h_titems + (size_t)f * e->titem_cap;
+    const size_t C = t.channels == h264k::TO_Y ? 1 : t.channels >= h264k::TO_RGBA ? 4 : 3;
+    const size_t pic_bytes = C * t.width * t.height * (t.dtype == h264k::TO_U8 ? 1 : t.dtype == h264k::TO_F16 ? 2 : 4);
+    std::vector<std::pair<int, unsigned long long>> waited;
+    for (uint32_t i = 0; i < n; i++) {
+        const StreamCtx *s = static_cast<SinkUser *>(pics[i].sink->user)->s;
+        const SinkTensorPic &p = pics[i];
+        items[i] = h264k::TensorItem{ s->d_frames + (size_t)p.slot * s->frame_bytes, static_cast<uint8_t *>(t.data) + p.index * pic_bytes,
+                                      s->wmb, p.x0, p.y0, p.w, p.h, 0u };
+        if (s->last_lane >= 0) {
+            const std::pair<int, unsigned long long> key(s->last_lane, s->last_launch);
+            if (std::find(waited.begin(), waited.end(), key) == waited.end()) {
+                hipEvent_t made = e->lanes[s->last_lane].ring[s->last_launch % Lane::RING];
+                if (hipEventQuery(made) != hipSuccess) HIP_TRY(hipStreamWaitEvent(st, made, 0));
+                waited.push_back(key);
+            }
+        }
+    }
+    h264k::TensorArgs ta;
+    ta.items = e->dv_titems + (size_t)f * e->titem_cap;
+    ta.width = t.width; ta.height = t.height;
+    for (int c = 0; c < 3; c++) { ta.mean[c] = t.mean[c]; ta.std[c] = t.std[c]; }
+    const uint32_t blocks = t.resize ? (t.width * t.height + 255u) / 256u : ((t.width + 63u) / 64u * ((t.height + 15u) / 16u) + 3u) / 4u;
+    void *args[] = { &ta };
+    HIP_TRY(hipLaunchKernel(fn, dim3(std::min(blocks, 1024u), n), dim3(256), args, 0, st));
+    HIP_TRY(hipEventRecord(e->titem_ev[f], st));
+    e->titem_used[f] = true; e->titem_flip ^= 1;
+    hipLaunchKernelGGL(k_err_words, dim3(1), dim3(64), 0, st, e->d_err, e->hd_err);
+    HIP_TRY(hipGetLastError());
+    Fence *fc;
+    if (e->fences.empty()) {
+        fc = new Fence();
+        HIP_TRY(hipEventCreateWithFlags(&fc->ev, hipEventDisableTiming));
+    } else { fc = e->fences.back(); e->fences.pop_back(); }
+    HIP_TRY(hipEventRecord(fc->ev, st));
+    for (uint32_t i = 0; i < n; i++) {
+        StreamCtx *s = static_cast<SinkUser *>(pics[i].sink->user)->s;
+        fence_unref(e, s);
+        s->fence = fc; fc->refs++;
+    }
+    *fence_ev = fc->ev;
+    return 0;
+}
+
+/* JobSink.tensor_out (h264bsdmiNextOutputTensorBatch) */
+int sink_tensor_out(uint32_t n, const SinkTensorPic *pics, const h264bsdmi_tensor_spec *spec, void *stream)
+{
+    if (!n) return 0;
+    if (!pics || !spec) return -1;
+    Engine *e = static_cast<SinkUser *>(pics[0].sink->user)->e;
+    for (uint32_t i = 1; i < n; i++)
+        if (static_cast<SinkUser *>(pics[i].sink->user)->e != e) return -1;        /* one device per call */
+    hipEvent_t fence_ev = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(e->mu);
+        HIP_TRY(hipSetDevice(e->device));
+        hipStream_t st = stream ? static_cast<hipStream_t>(stream) : e->stream;
+        if (stream) {
+            hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+            HIP_TRY(hipStreamIsCapturing(st, &cs));
+            if (cs != hipStreamCaptureStatusNone) return -1;                      /* graph capture of this call is not supported */
+        }
+        if (tensor_out_locked(e, n, pics, *spec, st, &fence_ev)) return -1;
+    }
+    if (stream) return 0;
+    if (hipEventSynchronize(fence_ev) != hipSuccess) return -1;        /* (a later call may have recorded it again: that only waits longer) */
+    std::lock_guard<std::mutex> lk(e->mu);
+    fold_errors(e);
+    return 0;
+}
 } // namespace
 
 /* ================================================================== C interface */
@@ -1088,6 +1263,7 @@ int eng_attach(JobSink *sink)
     sink->fetch_device = sink_fetch_device;
     sink->close = sink_close;
     sink->errors = sink_errors;
+    sink->tensor_out = sink_tensor_out;
     return 0;
 }
 

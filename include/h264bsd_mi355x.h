@@ -52,6 +52,40 @@ typedef struct h264bsdmi_device_picture {
  * per-instance HBM buffer (planar I420 by k_detile, windows and conversions by k_output).  Returns 1 = picture, 0 = no picture, <0 = error. */
 int h264bsdmiNextOutputPictureDevice(storage_t *pStorage, int format, int crop, h264bsdmi_device_picture *out);
 
+/* ---- batched device-resident output: the next pictures of n instances as one dense tensor ----
+ * What a GPU consumer of many streams (normally a neural network) takes in: the next picture of every instance, colour
+ * converted, optionally resized (bilinear) and normalised, written into ONE caller-owned device buffer by ONE kernel launch. */
+#define H264BSDMI_LAYOUT_NCHW 0
+#define H264BSDMI_LAYOUT_NHWC 1
+#define H264BSDMI_DTYPE_U8    0
+#define H264BSDMI_DTYPE_F16   1
+#define H264BSDMI_DTYPE_F32   2
+#define H264BSDMI_CH_RGB  0   /* 3 channels */
+#define H264BSDMI_CH_BGR  1   /* 3 channels */
+#define H264BSDMI_CH_RGBA 2   /* 4 channels, NHWC only, alpha = 255 (U8) / 1.0 (float, not normalised) */
+#define H264BSDMI_CH_BGRA 3   /* 4 channels, NHWC only */
+#define H264BSDMI_CH_Y    4   /* 1 channel: the decoded luma sample itself, no colour conversion */
+typedef struct h264bsdmi_tensor_spec {
+    void *data;                 /* DEVICE pointer, caller-owned, dense: picture i at data + i * C*H*W elements */
+    u32   width, height;        /* output size of every picture */
+    u32   layout, dtype, channels;
+    u32   crop;                 /* 1: the SPS frame-cropping window is the source; 0: the whole coded frame */
+    u32   resize;               /* 0: every source window must be width x height exactly; 1: bilinear (align_corners = false, no antialiasing) */
+    float mean[3], std[3];      /* float dtypes: out = (v / 255 - mean[c]) / std[c], c = OUTPUT channel; U8: must be 0 / 1 */
+} h264bsdmi_tensor_spec;
+/* Pop the next output picture of each of n distinct instances, as h264bsdNextOutputPicture() would, and write all of
+ * them into spec->data with ONE kernel launch.  Colour: the integer BT.601 conversion of h264bsdNextOutputPictureRGBA, per
+ * source pixel, to 8-bit R, G, B; resizing interpolates those 8-bit values in fp32.
+ * stream != NULL: enqueued on that hipStream_t (which must not be capturing), returns without waiting — the data are valid
+ * as soon as work on that stream is, and later decoding of these instances waits for the kernel, not for the caller.
+ * stream == NULL: on the library's own stream, returns when the data are there.
+ * got[i] = 1 when instance i gave a picture (its slice is written), 0 otherwise (its slice is left untouched); picId /
+ * isIdrPic / numErrMbs may be NULL.  0 = ok.  <0 = error; nothing was popped and nothing was enqueued.  Errors: an instance
+ * in capture mode, repeated instances, data == NULL, a size of 0, a layout / dtype / channels value out of range, RGBA / BGRA
+ * with NCHW, U8 with mean != 0 or std != 1, a std of 0, resize == 0 with a source window other than width x height. */
+int h264bsdmiNextOutputTensorBatch(u32 n, storage_t *const *pStorage, const h264bsdmi_tensor_spec *spec, void *stream,
+                                   u32 *got, u32 *picId, u32 *isIdrPic, u32 *numErrMbs);
+
 /* ---- host parse pipeline at scale ----
  * h264bsdDecode() consumes one NAL unit of one stream per call; a caller that feeds hundreds of streams needs the
  * loop of posix/test_h264bsd.c:146-177 for each of them and its own threading.  These entry points move both into

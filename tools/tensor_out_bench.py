@@ -1,0 +1,123 @@
+#!/usr/bin/env python3
+"""Batched device-resident output (h264bsdmiNextOutputTensorBatch / pull_tensor) against what a caller had to do before.
+
+256 instances decode the 1080p golden stream (no output reordering: one picture per instance and round).  Before every timed
+repetition each instance decodes one more picture and the device finishes it (h264bsdmiFlush), so that only the pull is timed:
+  (a) pull_tensor -> [256, 3, 1080, 1920] float16, ImageNet-normalised, no resize     HIP events on a torch stream around the call
+  (b) pull_tensor -> [256, 3, 224, 224] float16, resized + normalised                   (the same)
+  (c) the same two results the old way: 256 x next_output_picture_device(FMT_RGBA, crop=True) + clone, stack, cast,
+      F.interpolate (for b), normalise                                                    wall clock, synchronised (host waits inside)
+(a) is also given in GB/s (tiles read + tensor written) next to the device-to-device copy ceiling, measured here the way
+`bench.py --full` does (1 GiB copy, read + write).  Prints one JSON line.
+
+usage: tensor_out_bench.py [--streams 256] [--reps 20] [--warmup 3] [--old-reps 3]"""
+import argparse
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch                                    # noqa: E402  (torch's HIP runtime first: capi._share_torch_hip_runtime)
+import torch.nn.functional as F                 # noqa: E402
+import h264bsd_amd as h                         # noqa: E402
+
+MEAN, STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--streams", type=int, default=256)
+ap.add_argument("--reps", type=int, default=20)
+ap.add_argument("--warmup", type=int, default=3)
+ap.add_argument("--old-reps", type=int, default=3)
+args = ap.parse_args()
+
+data = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "golden", "test_1920x1080.h264"), "rb").read()
+N = args.streams
+rounds = 2 * (args.warmup + args.reps) + 2 * (1 + args.old_reps) + 2
+decs = [h.Decoder(no_output_reordering=1) for _ in range(N)]
+drv = h.BatchDriver(decs, [data * (rounds // 73 + 2)] * N)
+L = h.api_lib()
+
+
+def next_round():
+    """every instance decodes one more picture; the device has finished it on return"""
+    assert len(drv.step()) == N
+    assert L.h264bsdmiFlush() == 0
+
+
+def time_pull(size, out):
+    st = torch.cuda.Stream()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    ms, wall = [], []
+    for rep in range(args.warmup + args.reps):
+        next_round()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        e0.record(st)
+        _, got, _, _, _ = h.pull_tensor(decs, size=size, dtype=torch.float16, mean=MEAN, std=STD, out=out, stream=st)
+        e1.record(st)
+        st.synchronize()
+        t1 = time.perf_counter()
+        assert got == [1] * N
+        if rep >= args.warmup:
+            ms.append(e0.elapsed_time(e1))
+            wall.append((t1 - t0) * 1e3)
+    return sorted(ms)[len(ms) // 2], sorted(wall)[len(wall) // 2], min(ms)
+
+
+def time_old(size):
+    mean = torch.tensor(MEAN, device="cuda").view(1, 3, 1, 1)
+    std = torch.tensor(STD, device="cuda").view(1, 3, 1, 1)
+    wall = []
+    for rep in range(1 + args.old_reps):
+        next_round()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        pics = [d.next_output_picture_device(h.FMT_RGBA, crop=True)[0].clone() for d in decs]
+        x = torch.stack(pics)[..., :3].permute(0, 3, 1, 2).float()
+        del pics
+        if size is not None:
+            x = F.interpolate(x, size=size, mode="bilinear", align_corners=False, antialias=False)
+        y = ((x / 255 - mean) / std).half()
+        torch.cuda.synchronize()
+        wall.append((time.perf_counter() - t0) * 1e3)
+        del x, y
+        torch.cuda.empty_cache()
+    return sorted(wall[1:])[len(wall[1:]) // 2]
+
+
+def copy_ceiling_gbs():
+    src = torch.empty(1 << 30, dtype=torch.uint8, device="cuda")
+    dst = torch.empty_like(src)
+    dst.copy_(src)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(10):
+        dst.copy_(src)
+    e1.record()
+    torch.cuda.synchronize()
+    return 10 * 2 * src.numel() / (e0.elapsed_time(e1) * 1e-3) / 1e9
+
+
+next_round()            # warm-up of the decoders (pinned staging, lanes); its pictures are dropped by the next round
+out_a = torch.empty((N, 3, 1080, 1920), dtype=torch.float16, device="cuda")
+a_ms, a_wall, a_min = time_pull(None, out_a)
+del out_a
+out_b = torch.empty((N, 3, 224, 224), dtype=torch.float16, device="cuda")
+b_ms, b_wall, b_min = time_pull((224, 224), out_b)
+del out_b
+torch.cuda.empty_cache()
+c_a = time_old(None)
+c_b = time_old((224, 224))
+ceiling = copy_ceiling_gbs()
+moved = N * (8160 * 384 + 3 * 1080 * 1920 * 2)           # tiles read + tensor written (tiles of macroblock rows outside the crop included)
+a_gbs = moved / (a_ms * 1e-3) / 1e9
+print(json.dumps(dict(streams=N, reps=args.reps,
+                      a_ms=round(a_ms, 3), a_min_ms=round(a_min, 3), a_wall_ms=round(a_wall, 3), a_gbs=round(a_gbs, 1),
+                      copy_ceiling_gbs=round(ceiling, 1), a_fraction_of_copy=round(a_gbs / ceiling, 3),
+                      b_ms=round(b_ms, 3), b_min_ms=round(b_min, 3), b_wall_ms=round(b_wall, 3),
+                      c_a_ms=round(c_a, 2), c_b_ms=round(c_b, 2),
+                      speedup_a=round(c_a / a_wall, 1), speedup_b=round(c_b / b_wall, 1),
+                      device_errors=h.device_errors())))
+for d in decs:
+    d.close()
