@@ -26,12 +26,14 @@
 #include <stdlib.h>
 #include <string.h>
 #include <deque>
+#include <memory>
 #include <mutex>
 #include <vector>
 #include <algorithm>
 #include "kernels.hip.h"
 #include "kernels/k_tensor_out.hip.h"
 #include "engine.h"
+#include "hip_owned.h"
 #include "../../include/h264bsd_mi355x_bench.h"
 
 #define HIP_TRY(expr)                                                                              \
@@ -47,26 +49,24 @@
 namespace {
 
 constexpr int MAX_DEVICES = 16;
-struct PendingJob { uint8_t *host; uint32_t bytes, cap; const uint8_t *dev; };     /* dev: the device's address of the pinned buffer (k_h2d) */
+struct PendingJob { Pinned<uint8_t> host; uint32_t bytes = 0, cap = 0; };     /* host.dev(): the device's address of the pinned buffer (k_h2d) */
 constexpr size_t MAX_QUEUED_PICTURES = 8;    /* per decoder instance, before sink_submit starts the device on its own */
 
 /* The completion of one h264bsdmiNextOutputTensorBatch call, shared by the instances it read from (tensor_out_locked): until it has
  * passed, their frame buffers must neither be decoded into (lane_launch) nor freed (fence_drop).  Back to Engine.fences when no
  * instance refers to it any more. */
-struct Fence { hipEvent_t ev = nullptr; unsigned refs = 0; };
+struct Fence { Event ev; unsigned refs = 0; };
 
 struct StreamCtx {
     uint32_t wmb = 0, hmb = 0, n_slots = 0, frame_bytes = 0;
-    uint8_t *d_frames = nullptr;
-    uint8_t *d_dbk = nullptr;
-    uint8_t *h_frame[FJ_MAX_SLOTS] = {};      /* pinned host mirrors of the frame buffers, written by the layout kernel itself ... */
-    uint8_t *hd_frame[FJ_MAX_SLOTS] = {};     /* ... through these device pointers (no staging copy in HBM, no copy engine: out_begin) */
+    DeviceMem<uint8_t> d_frames, d_dbk;
+    Pinned<uint8_t> h_frame[FJ_MAX_SLOTS];  /* host mirrors of the frame buffers, written by the layout kernel itself through their device pointers (out_begin) */
     int out_slot = -1;                      /* the frame buffer whose picture is on its way to host memory (sink_fetch_begin .. sink_fetch_end) */
-    std::vector<uint8_t *> retired_host;    /* host mirrors of the frame buffers a new parameter set replaced: a picture pulled just before lives in one (freed at the next pull) */
-    uint32_t *h_conv = nullptr, *hd_conv = nullptr, *d_conv = nullptr;      /* converted picture: host mirror + its device pointer; device copy (device-resident output) */
-    hipEvent_t out_ev = nullptr;            /* recorded behind the copy of a picture on its way out: the caller waits for it OUTSIDE the engine's mutex */
+    std::vector<Pinned<uint8_t>> retired_host;      /* host mirrors of the frame buffers a new parameter set replaced: a picture pulled just before lives in one (freed at the next pull) */
+    Pinned<uint32_t> h_conv; DeviceMem<uint32_t> d_conv;       /* converted picture: host mirror (with its device pointer); device copy (device-resident output) */
+    Event out_ev;                           /* recorded behind the copy of a picture on its way out: the caller waits for it OUTSIDE the engine's mutex */
     std::mutex qmu;                         /* guards pending / free_bufs (submit runs on the caller's threads) */
-    PendingJob acquired = { nullptr, 0, 0, nullptr };   /* staging buffer the parser is currently filling (sink_acquire) */
+    PendingJob acquired;                    /* staging buffer the parser is currently filling (sink_acquire) */
     std::deque<PendingJob> pending;
     std::vector<PendingJob> free_bufs;      /* recycled pinned staging buffers */
     /* lane scheduling (flush_locked): the light lane this instance belongs to, where its latest picture was launched
@@ -85,22 +85,13 @@ struct StreamCtx {
  * behind the inter kernels, k_dbk of the NEXT tick next to this tick's per-picture kernels — kept the sum or lost
  * (docs/EXPERIMENTS.md); those variants are not in the product. */
 struct SideLane {
-    hipStream_t stream = nullptr; hipEvent_t fork = nullptr, join = nullptr;            /* k_dbk */
-    hipStream_t copy_stream = nullptr; hipEvent_t copy_join = nullptr;                 /* k_copy (launch_tick) */
+    Stream stream; Event fork, join;            /* k_dbk */
+    Stream copy_stream; Event copy_join;        /* k_copy (launch_tick) */
     bool create(int dbk_priority, bool with_priority)
     {
-        if ((with_priority ? hipStreamCreateWithPriority(&stream, hipStreamNonBlocking, dbk_priority) : hipStreamCreateWithFlags(&stream, hipStreamNonBlocking)) != hipSuccess) return false;
-        return hipEventCreateWithFlags(&fork, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&join, hipEventDisableTiming) == hipSuccess &&
-               hipStreamCreateWithFlags(&copy_stream, hipStreamNonBlocking) == hipSuccess && hipEventCreateWithFlags(&copy_join, hipEventDisableTiming) == hipSuccess;
-    }
-    void destroy()
-    {
-        if (stream) hipStreamDestroy(stream);
-        if (copy_stream) hipStreamDestroy(copy_stream);
-        if (fork) hipEventDestroy(fork);
-        if (join) hipEventDestroy(join);
-        if (copy_join) hipEventDestroy(copy_join);
-        *this = SideLane();
+        if ((with_priority ? stream.create(dbk_priority) : stream.create()) != hipSuccess) return false;
+        return fork.create(hipEventDisableTiming) == hipSuccess && join.create(hipEventDisableTiming) == hipSuccess &&
+               copy_stream.create() == hipSuccess && copy_join.create(hipEventDisableTiming) == hipSuccess;
     }
 };
 
@@ -117,17 +108,17 @@ struct SideLane {
  * on this runtime (tools/probes/queue_probe.hip), and the runtime's default of 4 hardware queues serialises lanes:
  * the library asks for 16 (GPU_MAX_HW_QUEUES) when it is loaded before the HIP runtime starts. */
 struct Lane {
-    hipStream_t st = nullptr;
-    bool owns_stream = false;
-    uint8_t *d_arena = nullptr; size_t arena_cap = 0;      /* device copies of the blobs of one tick */
-    FrameDesc *d_desc = nullptr, *h_desc = nullptr; size_t desc_cap = 0;    /* h_desc: pinned staging, 2 halves */
-    h264k::H2dItem *h_items = nullptr, *dv_items = nullptr;                    /* pinned, 2 halves like h_desc: the tick's jobs for k_h2d (dv_: the device's view of it) */
+    hipStream_t st = nullptr;                  /* own_st, or the engine's stream (single-lane engine) */
+    Stream own_st;
+    DeviceMem<uint8_t> d_arena; size_t arena_cap = 0;      /* device copies of the blobs of one tick */
+    DeviceMem<FrameDesc> d_desc; Pinned<FrameDesc> h_desc; size_t desc_cap = 0;    /* h_desc: pinned staging, 2 halves */
+    Pinned<h264k::H2dItem> h_items;            /* pinned, 2 halves like h_desc: the tick's jobs for k_h2d (h_items.dev(): the device's view of it) */
     int flip = 0; unsigned ticks = 0;
-    hipEvent_t desc_ev[2] = { nullptr, nullptr };
+    Event desc_ev[2];
     static constexpr unsigned RING = 64;
-    hipEvent_t ring[RING] = {};
+    Event ring[RING];
     unsigned long long launches = 0;
-    hipEvent_t tail = nullptr;
+    Event tail;
     const SideLane *side = nullptr;
 };
 constexpr unsigned HEAVY_DELAY = 4;
@@ -151,27 +142,27 @@ constexpr uint32_t LANE_DBK_WAVES = LANE_DBK_WAVES_N;
 struct Engine {
     std::mutex mu;
     int device = 0;
-    hipStream_t stream = nullptr;
-    hipStream_t out_stream = nullptr;        /* pictures on their way to host memory (out_begin): behind the picture's OWN tick, not behind every lane */
+    Stream stream;
+    Stream out_stream;                       /* pictures on their way to host memory (out_begin): behind the picture's OWN tick, not behind every lane */
     std::vector<Lane> lanes;                 /* [0, n_light) light lanes, then n_heavy heavy lanes */
     unsigned n_light = 1, n_heavy = 0, heavy_rr = 0, group_rr = 0;
     std::vector<StreamCtx *> streams;
-    uint8_t *conv_in = nullptr; uint32_t *conv_out = nullptr; size_t conv_cap = 0; /* eng_convert_host scratch */
+    DeviceMem<uint8_t> conv_in; DeviceMem<uint32_t> conv_out; size_t conv_cap = 0; /* eng_convert_host scratch */
     std::vector<std::pair<StreamCtx *, PendingJob>> inflight;   /* staging buffers of enqueued, unfinished ticks */
-    hipEvent_t inflight_done = nullptr;
+    Event inflight_done;
     bool inflight_recorded = false;          /* inflight_done has been recorded behind everything in `inflight` */
     SideLane side;
     /* device error word (DEVERR_* bits, kernels.hip.h): the kernels OR into d_err, poll_errors() folds it into `errors`
      * whenever the host has waited for the device anyway */
-    uint32_t *d_err = nullptr, *h_err = nullptr, *hd_err = nullptr;      /* device error words, their pinned host copy, the device pointer of that copy */
+    DeviceMem<uint32_t> d_err; Pinned<uint32_t> h_err;      /* device error words, their pinned host copy (with its device pointer) */
     uint32_t errors = 0;                       /* sticky bits (written with __atomic_fetch_or under mu, read without the lock) */
     uint32_t error_events = 0;                 /* how often a tripwire fired, ever: monotonic, so that a NEW occurrence of a bit that is
                                                   already set is visible (per-decoder copy-elision guard, the tests' delta) */
-    unsigned long long *tail_prof = nullptr;   /* debug: per-wave cycle accounting of the per-picture kernels (block 0) */
+    DeviceMem<unsigned long long> tail_prof;   /* debug: per-wave cycle accounting of the per-picture kernels (block 0) */
     /* tensor pulls (tensor_out_locked): items staged in pinned memory, two halves used in turn, each guarded by the event recorded
      * behind the launch that read it; fence events that no instance holds any more */
-    h264k::TensorItem *h_titems = nullptr, *dv_titems = nullptr; size_t titem_cap = 0;
-    hipEvent_t titem_ev[2] = { nullptr, nullptr }; bool titem_used[2] = { false, false }; int titem_flip = 0;
+    Pinned<h264k::TensorItem> h_titems; size_t titem_cap = 0;
+    Event titem_ev[2]; bool titem_used[2] = { false, false }; int titem_flip = 0;
     std::vector<Fence *> fences;
 };
 
@@ -212,12 +203,12 @@ __global__ void k_spin(long long ticks) { const long long t0 = wall_clock64(); w
 static int streams_run_concurrently(Engine *e)
 {
     constexpr int N = 8;
-    hipStream_t st[N] = {};
-    hipEvent_t ev[2] = {};
+    Stream st[N];
+    Event ev[2];
     int ok = 1;
     float one = 0, all = 0;
-    for (auto &s : st) if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) ok = 0;
-    for (auto &v : ev) if (hipEventCreate(&v) != hipSuccess) ok = 0;
+    for (auto &s : st) if (s.create() != hipSuccess) ok = 0;
+    for (auto &v : ev) if (v.create() != hipSuccess) ok = 0;
     int rate_khz = 100000;                                         /* wall_clock64 ticks at 100 MHz on gfx9 */
     if (hipDeviceGetAttribute(&rate_khz, hipDeviceAttributeWallClockRate, e->device) != hipSuccess || rate_khz <= 0) rate_khz = 100000;
     const long long ticks = (long long)rate_khz * 500 / 1000;      /* 500 us: long against the ~0.15 ms of event traffic around the eight */
@@ -234,21 +225,18 @@ static int streams_run_concurrently(Engine *e)
     }
     if (ok) {
         /* st[0] starts the clock, waits for the other five, stops it */
-        hipEvent_t done[N] = {};
+        Event done[N];
         hipEventRecord(ev[0], st[0]);
         for (int i = 1; i < N; i++) hipStreamWaitEvent(st[i], ev[0], 0);
         for (int i = 0; i < N; i++) hipLaunchKernelGGL(k_spin, dim3(1), dim3(64), 0, st[i], ticks);
         for (int i = 1; i < N; i++) {
-            if (hipEventCreateWithFlags(&done[i], hipEventDisableTiming) != hipSuccess) { ok = 0; break; }
+            if (done[i].create(hipEventDisableTiming) != hipSuccess) { ok = 0; break; }
             hipEventRecord(done[i], st[i]);
             hipStreamWaitEvent(st[0], done[i], 0);
         }
         hipEventRecord(ev[1], st[0]);
         ok = ok && hipEventSynchronize(ev[1]) == hipSuccess && hipEventElapsedTime(&all, ev[0], ev[1]) == hipSuccess;
-        for (auto &d : done) if (d) hipEventDestroy(d);
     }
-    for (auto &s : st) if (s) hipStreamDestroy(s);     /* (probe streams never launch banded kernels: no ticket counters) */
-    for (auto &v : ev) if (v) hipEventDestroy(v);
     if (getenv("H264BSDMI_TRACE_LANES")) fprintf(stderr, "h264bsd-mi355x: stream probe: one %.3f ms, eight %.3f ms, ok %d\n", one, all, ok);
     return ok && one > 0 && all < 1.7f * one;       /* measured: 16 hardware queues 1.24 x, 4 queues 3.1 x */
 }
@@ -275,11 +263,11 @@ static int lanes_create(Engine *e)
     for (unsigned i = 0; i < g + k; i++) {
         Lane &l = lanes[i];
         if (g == 1 && i == 0) { l.st = e->stream; l.side = &e->side; }      /* the single-lane engine: k_dbk next to the reconstruction kernels */
-        else { HIP_TRY(hipStreamCreateWithFlags(&l.st, hipStreamNonBlocking)); l.owns_stream = true; }
-        HIP_TRY(hipEventCreateWithFlags(&l.desc_ev[0], hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&l.desc_ev[1], hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&l.tail, hipEventDisableTiming));
-        for (auto &ev : l.ring) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        else { HIP_TRY(l.own_st.create()); l.st = l.own_st; }
+        HIP_TRY(l.desc_ev[0].create(hipEventDisableTiming));
+        HIP_TRY(l.desc_ev[1].create(hipEventDisableTiming));
+        HIP_TRY(l.tail.create(hipEventDisableTiming));
+        for (auto &ev : l.ring) HIP_TRY(ev.create(hipEventDisableTiming));
     }
     e->n_light = g; e->n_heavy = k;
     e->lanes.swap(lanes);
@@ -294,23 +282,19 @@ Engine *engine_get(int device = -1)
     if (g_engines[device]) return g_engines[device];
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0 || device >= n) return nullptr;
-    Engine *e = new Engine();
+    std::unique_ptr<Engine> e(new Engine());          /* (released again if it cannot be completed; published, it lives until the process ends) */
     e->device = device;
-    if (hipSetDevice(e->device) != hipSuccess) { delete e; return nullptr; }
-    if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess) { delete e; return nullptr; }
-    if (hipEventCreateWithFlags(&e->inflight_done, hipEventDisableTiming) != hipSuccess ||
+    if (hipSetDevice(e->device) != hipSuccess || e->stream.create() != hipSuccess || e->inflight_done.create(hipEventDisableTiming) != hipSuccess ||
         ![&] {   /* the side stream (k_dbk next to the copy and inter kernels) gets the highest priority the device has: its few workgroups
                    * must not queue behind the hundred thousand of k_recon_inter */
             int lo = 0, hi = 0;
             const bool prio = hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess;
             return e->side.create(hi, prio);
         }() ||
-        hipMalloc((void **)&e->d_err, 256) != hipSuccess || hipMemset(e->d_err, 0, 256) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||   /* (hipMemset returns before the fill has run) */
-        hipHostMalloc((void **)&e->h_err, 64, hipHostMallocDefault) != hipSuccess) { delete e; return nullptr; }
+        e->d_err.alloc(256) != hipSuccess || hipMemset(e->d_err, 0, 256) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||   /* (hipMemset returns before the fill has run) */
+        e->h_err.alloc(64, true) != hipSuccess) return nullptr;
     e->h_err[0] = e->h_err[1] = 0;
-    if (hipHostGetDevicePointer((void **)&e->hd_err, e->h_err, 0) != hipSuccess) { delete e; return nullptr; }
-    g_engines[device] = e;
-    return e;
+    return g_engines[device] = e.release();
 }
 
 /* ---- how the two per-picture kernels split a picture (row bands, kernels.hip.h) ----
@@ -362,7 +346,7 @@ static uint16_t bands_for(uint32_t hmb, uint32_t rows)
  * launches on one stream run one after the other, launches on different streams may overlap.  [0,1] k_frame_dbk,
  * [2,3] k_frame_intra. */
 std::mutex g_ticket_mu;
-std::vector<std::pair<hipStream_t, uint32_t *>> g_tickets[MAX_DEVICES];
+auto *const g_tickets = new std::vector<std::pair<hipStream_t, DeviceMem<uint32_t>>>[MAX_DEVICES];     /* (never destroyed, like the engines: no HIP call at exit) */
 static uint32_t *tickets_for(hipStream_t st)
 {
     int dev = 0;
@@ -372,19 +356,20 @@ static uint32_t *tickets_for(hipStream_t st)
     /* zeroed ON the stream whose kernels count in it: hipMemset() on device memory returns before the fill has run, on the
      * null stream, which the (non-blocking) lane streams do not wait for — a fill that landed in the middle of the first
      * banded launch handed out tickets twice and left a band of a picture without a workgroup (rare, under load only) */
-    uint32_t *d = nullptr;
-    if (hipMalloc((void **)&d, 64) != hipSuccess || hipMemsetAsync(d, 0, 64, st) != hipSuccess) return nullptr;
-    g_tickets[dev].emplace_back(st, d);
-    return d;
+    DeviceMem<uint32_t> d;
+    if (d.alloc(64) != hipSuccess || hipMemsetAsync(d, 0, 64, st) != hipSuccess) return nullptr;
+    g_tickets[dev].emplace_back(st, std::move(d));
+    return g_tickets[dev].back().second;
 }
-/* a stream is about to be destroyed: its counters go with it (a later stream may get the same handle and must not inherit them) */
-static void tickets_release(hipStream_t st)
+} // namespace
+/* a stream is about to be destroyed (Stream, hip_owned.h): its counters go with it (a later stream may get the same handle and must not inherit them) */
+void tickets_release(hipStream_t st)
 {
     std::lock_guard<std::mutex> lk(g_ticket_mu);
-    for (auto &v : g_tickets)
-        for (size_t i = 0; i < v.size();)
-            if (v[i].first == st) { hipFree(v[i].second); v.erase(v.begin() + (long)i); } else i++;
+    for (int d = 0; d < MAX_DEVICES; d++)
+        g_tickets[d].erase(std::remove_if(g_tickets[d].begin(), g_tickets[d].end(), [&](const auto &p) { return p.first == st; }), g_tickets[d].end());
 }
+namespace {
 /* a banded launch that ended early (a scheduler gave up: DEVERR_*_SCHED) leaves its ticket counters non-zero, and every later
  * banded launch on that stream would map tickets to the wrong picture and band: after a device error all of them start over */
 static void tickets_rezero(int dev)
@@ -473,7 +458,7 @@ void make_desc(FrameDesc &d, const uint8_t *host_blob, const uint8_t *dev_blob, 
     }
 }
 
-struct TickTimers { hipEvent_t ev[6]; hipEvent_t sev[5] = { nullptr, nullptr, nullptr, nullptr, nullptr }; bool on = false; bool copy_timed = false; unsigned mask = 31u; };   /* copy_timed: sev[3..4] were recorded by the latest launch_tick */   /* mask bit k: kernel k of KERNELS is timed */   /* boundaries of the 5 kernels of a tick; sev[1..2] = k_dbk on the side stream, sev[3..4] = k_copy on the copy stream */
+struct TickTimers { Event ev[6]; Event sev[5]; bool on = false; bool copy_timed = false; unsigned mask = 31u; };   /* copy_timed: sev[3..4] were recorded by the latest launch_tick */   /* mask bit k: kernel k of KERNELS is timed */   /* boundaries of the 5 kernels of a tick; sev[1..2] = k_dbk on the side stream, sev[3..4] = k_copy on the copy stream */
 
 /* k_dbk of one tick on the side stream (which must already wait for whatever frees the tick's deblocking scratch);
  * records the join event behind it */
@@ -671,7 +656,7 @@ int reap_locked(Engine *e, bool wait)
     } else if (!e->inflight_recorded || hipEventQuery(e->inflight_done) != hipSuccess) return 0;
     for (auto &f : e->inflight) {
         std::lock_guard<std::mutex> ql(f.first->qmu);
-        f.first->free_bufs.push_back(f.second);
+        f.first->free_bufs.push_back(std::move(f.second));
     }
     e->inflight.clear();
     return 0;
@@ -703,20 +688,15 @@ static int lane_launch(Engine *e, unsigned lane_idx, const std::vector<StreamCtx
     }
     if (bytes > l.arena_cap) {
         HIP_TRY(hipStreamSynchronize(l.st));               /* earlier ticks may still read the old arena */
-        if (l.d_arena) HIP_TRY(hipFree(l.d_arena));
         l.arena_cap = bytes + bytes / 4;
-        HIP_TRY(hipMalloc((void **)&l.d_arena, l.arena_cap));
+        HIP_TRY(l.d_arena.alloc(l.arena_cap));
     }
     if (part.size() > l.desc_cap) {
         HIP_TRY(hipStreamSynchronize(l.st));
-        if (l.d_desc) HIP_TRY(hipFree(l.d_desc));
-        if (l.h_desc) HIP_TRY(hipHostFree(l.h_desc));
-        if (l.h_items) HIP_TRY(hipHostFree(l.h_items));
         l.desc_cap = part.size() * 2;
-        HIP_TRY(hipMalloc((void **)&l.d_desc, l.desc_cap * sizeof(FrameDesc)));
-        HIP_TRY(hipHostMalloc((void **)&l.h_desc, 2 * l.desc_cap * sizeof(FrameDesc), hipHostMallocDefault));
-        HIP_TRY(hipHostMalloc((void **)&l.h_items, 2 * l.desc_cap * sizeof(h264k::H2dItem), hipHostMallocDefault));
-        HIP_TRY(hipHostGetDevicePointer((void **)&l.dv_items, l.h_items, 0));
+        HIP_TRY(l.d_desc.alloc(l.desc_cap * sizeof(FrameDesc)));
+        HIP_TRY(l.h_desc.alloc(2 * l.desc_cap * sizeof(FrameDesc)));
+        HIP_TRY(l.h_items.alloc(2 * l.desc_cap * sizeof(h264k::H2dItem), true));
         l.flip = 0; l.ticks = 0;
     }
     /* descriptors are staged in pinned memory (two halves, alternating) so that the copy can be asynchronous;
@@ -732,7 +712,7 @@ static int lane_launch(Engine *e, unsigned lane_idx, const std::vector<StreamCtx
     for (size_t i = 0; i < part.size(); i++) {
         StreamCtx *s = part[i];
         PendingJob j;
-        { std::lock_guard<std::mutex> ql(s->qmu); j = s->pending.front(); s->pending.pop_front(); }
+        { std::lock_guard<std::mutex> ql(s->qmu); j = std::move(s->pending.front()); s->pending.pop_front(); }
         if (s->fence) {         /* a tensor pull (on the caller's stream) may still read the frame buffer this picture is decoded into */
             if (hipEventQuery(s->fence->ev) == hipSuccess) fence_unref(e, s);
             else if (std::find(fenced.begin(), fenced.end(), s->fence) == fenced.end()) {
@@ -747,14 +727,14 @@ static int lane_launch(Engine *e, unsigned lane_idx, const std::vector<StreamCtx
                 waited.push_back(key);
             }
         }
-        items[i] = h264k::H2dItem{ j.dev, l.d_arena + off, j.bytes, 0u };
+        items[i] = h264k::H2dItem{ j.host.dev(), l.d_arena + off, j.bytes, 0u };
         make_desc(descs[i], j.host, l.d_arena + off, s->d_frames, s->frame_bytes, s->d_dbk, &shape, e->d_err);
         off += (j.bytes + 255u) & ~255u;
-        e->inflight.emplace_back(s, j);
+        e->inflight.emplace_back(s, std::move(j));
         e->inflight_recorded = false;
         s->last_lane = (int)lane_idx; s->last_launch = l.launches;
     }
-    hipLaunchKernelGGL(h264k::k_h2d, dim3(h264k::H2D_CHUNKS, (uint32_t)part.size()), dim3(256), 0, l.st, l.dv_items + (size_t)l.flip * l.desc_cap);
+    hipLaunchKernelGGL(h264k::k_h2d, dim3(h264k::H2D_CHUNKS, (uint32_t)part.size()), dim3(256), 0, l.st, l.h_items.dev() + (size_t)l.flip * l.desc_cap);
     HIP_TRY(hipMemcpyAsync(l.d_desc, descs, part.size() * sizeof(FrameDesc), hipMemcpyHostToDevice, l.st));
     HIP_TRY(hipEventRecord(l.desc_ev[l.flip], l.st));
     l.flip ^= 1;
@@ -794,7 +774,7 @@ int flush_locked(Engine *e, bool wait = true)
             any_pending = true;
             if (s->ready_round > round) continue;
             s->flush_quota--;
-            const FjHeader *h = reinterpret_cast<const FjHeader *>(s->pending.front().host);
+            const FjHeader *h = reinterpret_cast<const FjHeader *>(s->pending.front().host.get());
             if (e->n_heavy && h->n_intra * 4u > h->n_mbs) heavy.push_back(s);
             else part[(unsigned)s->group % e->n_light].push_back(s);
         }
@@ -822,32 +802,17 @@ int flush_locked(Engine *e, bool wait = true)
 /* ---- JobSink implementation ---- */
 struct SinkUser { Engine *e; StreamCtx *s; };
 
-static void free_retired(StreamCtx *s)
-{
-    for (uint8_t *p : s->retired_host) hipHostFree(p);
-    s->retired_host.clear();
-}
-
 void stream_release(StreamCtx *s, bool keep_pulled = false)
 {
-    for (auto &j : s->pending) hipHostFree(j.host);
     s->pending.clear();
-    for (auto &j : s->free_bufs) hipHostFree(j.host);
     s->free_bufs.clear();
-    if (s->acquired.host) hipHostFree(s->acquired.host);
-    s->acquired = PendingJob{ nullptr, 0, 0, nullptr };
-    if (s->d_frames) hipFree(s->d_frames);
-    if (s->d_dbk) hipFree(s->d_dbk);
-    s->d_dbk = nullptr;
+    s->acquired = PendingJob();
+    s->d_frames.reset(); s->d_dbk.reset();
     /* keep_pulled (a new sequence re-allocates the frame buffers, sink_configure): h264bsdmiPullAndDecodePictureBatch hands out a picture and
      * parses on in the same call — the picture must outlive the activation of a parameter set that the parsing may bring */
-    for (auto &p : s->h_frame) if (p) { if (keep_pulled) s->retired_host.push_back(p); else hipHostFree(p); p = nullptr; }
-    for (auto &p : s->hd_frame) p = nullptr;
-    if (!keep_pulled) free_retired(s);
-    if (s->h_conv) hipHostFree(s->h_conv);
-    if (s->d_conv) hipFree(s->d_conv);
-    if (s->out_ev) { hipEventDestroy(s->out_ev); s->out_ev = nullptr; }
-    s->d_frames = nullptr; s->h_conv = nullptr; s->hd_conv = nullptr; s->d_conv = nullptr;
+    for (auto &p : s->h_frame) { if (keep_pulled && p) s->retired_host.push_back(std::move(p)); p.reset(); }
+    if (!keep_pulled) s->retired_host.clear();
+    s->h_conv.reset(); s->d_conv.reset(); s->out_ev.reset();
 }
 
 int sink_configure(void *user, uint32_t wmb, uint32_t hmb, uint32_t n_slots)
@@ -862,9 +827,9 @@ int sink_configure(void *user, uint32_t wmb, uint32_t hmb, uint32_t n_slots)
     u->s->wmb = wmb; u->s->hmb = hmb; u->s->n_slots = n_slots;
     u->s->frame_bytes = fj_frame_bytes(wmb, hmb);
     const size_t total = (size_t)n_slots * u->s->frame_bytes + 256;
-    HIP_TRY(hipMalloc((void **)&u->s->d_frames, total));
+    HIP_TRY(u->s->d_frames.alloc(total));
     HIP_TRY(hipMemsetAsync(u->s->d_frames, 0, total, u->e->stream));
-    HIP_TRY(hipMalloc((void **)&u->s->d_dbk, DBK_SCRATCH_BYTES(wmb * hmb)));
+    HIP_TRY(u->s->d_dbk.alloc(DBK_SCRATCH_BYTES(wmb * hmb)));
     HIP_TRY(hipMemsetAsync(u->s->d_dbk, 0, DBK_SCRATCH_BYTES(wmb * hmb), u->e->stream));
     HIP_TRY(hipStreamSynchronize(u->e->stream));           /* the lanes do not order themselves behind this stream */
     u->s->last_lane = -1;
@@ -874,12 +839,12 @@ int sink_configure(void *user, uint32_t wmb, uint32_t hmb, uint32_t n_slots)
 /* staging buffer for a frame job of up to `bytes`: recycled pinned memory of this stream, else a new allocation */
 static int take_buffer(SinkUser *u, uint32_t bytes, PendingJob *out)
 {
-    PendingJob j = { nullptr, 0, 0, nullptr };
+    PendingJob j;
     {
         std::lock_guard<std::mutex> ql(u->s->qmu);
         for (size_t i = 0; i < u->s->free_bufs.size(); i++)
             if (u->s->free_bufs[i].cap >= bytes) {
-                j = u->s->free_bufs[i];
+                j = std::move(u->s->free_bufs[i]);
                 u->s->free_bufs.erase(u->s->free_bufs.begin() + (long)i);
                 break;
             }
@@ -887,10 +852,9 @@ static int take_buffer(SinkUser *u, uint32_t bytes, PendingJob *out)
     if (!j.host) {
         HIP_TRY(hipSetDevice(u->e->device));
         j.cap = bytes + 65536;                              /* pinned: recycled across pictures */
-        HIP_TRY(hipHostMalloc((void **)&j.host, j.cap, hipHostMallocDefault));
-        HIP_TRY(hipHostGetDevicePointer((void **)&j.dev, j.host, 0));
+        HIP_TRY(j.host.alloc(j.cap, true));
     }
-    *out = j;
+    *out = std::move(j);
     return 0;
 }
 
@@ -903,8 +867,8 @@ uint8_t *sink_acquire(void *user, uint32_t bytes)
     if (s->acquired.host && s->acquired.cap >= bytes) return s->acquired.host;     /* previous picture was abandoned */
     if (s->acquired.host) {
         std::lock_guard<std::mutex> ql(s->qmu);
-        s->free_bufs.push_back(s->acquired);
-        s->acquired = PendingJob{ nullptr, 0, 0, nullptr };
+        s->free_bufs.push_back(std::move(s->acquired));
+        s->acquired = PendingJob();
     }
     if (take_buffer(u, bytes, &s->acquired)) return nullptr;
     return s->acquired.host;
@@ -917,8 +881,8 @@ int sink_submit(void *user, const uint8_t *blob, uint32_t bytes)
     SinkUser *u = static_cast<SinkUser *>(user);
     PendingJob j;
     if (u->s->acquired.host && blob == u->s->acquired.host) {
-        j = u->s->acquired;
-        u->s->acquired = PendingJob{ nullptr, 0, 0, nullptr };
+        j = std::move(u->s->acquired);
+        u->s->acquired = PendingJob();
     } else {
         if (take_buffer(u, bytes, &j)) return -1;
         memcpy(j.host, blob, bytes);
@@ -927,7 +891,7 @@ int sink_submit(void *user, const uint8_t *blob, uint32_t bytes)
     size_t backlog;
     {
         std::lock_guard<std::mutex> ql(u->s->qmu);
-        u->s->pending.push_back(j);
+        u->s->pending.push_back(std::move(j));
         backlog = u->s->pending.size();
     }
     /* An application that decodes without pulling pictures (frame skipping, decoding ahead) must not pile up pinned
@@ -968,13 +932,13 @@ static int out_begin(SinkUser *u, bool to_host, hipStream_t *st)          /* mut
     { std::lock_guard<std::mutex> ql(s->qmu); mine = !s->pending.empty(); }
     if (mine && flush_locked(e, false)) return -1;
     if (!mine) HIP_TRY(hipSetDevice(e->device));
-    if (!s->out_ev) HIP_TRY(hipEventCreateWithFlags(&s->out_ev, OUT_EVENT_FLAGS));
+    if (!s->out_ev) HIP_TRY(s->out_ev.create(OUT_EVENT_FLAGS));
     *st = e->stream;                                   /* device-resident output: on the engine's stream, which is behind every lane since the last flush */
     if (to_host) {
         /* A picture bound for host memory waits for the tick that made it (or a later one of its lane), not for whatever else the engine's
          * stream is behind: instances whose tick is done hand their pictures over while other instances' ticks still run.  Nothing the
          * device does later can touch the frame before the call returns — the instance's next job is submitted after that. */
-        if (!e->out_stream) HIP_TRY(hipStreamCreateWithFlags(&e->out_stream, hipStreamNonBlocking));
+        if (!e->out_stream) HIP_TRY(e->out_stream.create());
         if (s->last_lane >= 0) {
             hipEvent_t made = e->lanes[s->last_lane].ring[s->last_launch % Lane::RING];
             if (hipEventQuery(made) != hipSuccess) HIP_TRY(hipStreamWaitEvent(e->out_stream, made, 0));      /* (long done, usually: no barrier packet then) */
@@ -985,7 +949,7 @@ static int out_begin(SinkUser *u, bool to_host, hipStream_t *st)          /* mut
 }
 static int out_end_locked(SinkUser *u, hipStream_t st)  /* mutex held: the device's error words travel with the picture */
 {
-    hipLaunchKernelGGL(k_err_words, dim3(1), dim3(64), 0, st, u->e->d_err, u->e->hd_err);
+    hipLaunchKernelGGL(k_err_words, dim3(1), dim3(64), 0, st, u->e->d_err, u->e->h_err.dev());
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(u->s->out_ev, st));
     return 0;
@@ -1006,14 +970,13 @@ int sink_fetch_begin(void *user, uint32_t slot)
     hipStream_t st;
     s->out_slot = -1;
     if (slot >= s->n_slots || out_begin(u, true, &st)) return -1;
-    free_retired(s);
-    if (!s->h_frame[slot] && hipHostMalloc((void **)&s->h_frame[slot], s->frame_bytes, hipHostMallocDefault) != hipSuccess) { s->h_frame[slot] = nullptr; return -1; }
-    if (!s->hd_frame[slot] && hipHostGetDevicePointer((void **)&s->hd_frame[slot], s->h_frame[slot], 0) != hipSuccess) { s->hd_frame[slot] = nullptr; return -1; }
+    s->retired_host.clear();
+    if (!s->h_frame[slot] && s->h_frame[slot].alloc(s->frame_bytes, true) != hipSuccess) return -1;
     /* the layout kernel writes the host mirror itself: 16-byte pieces over the link run at 49 GB/s (tools/probes/d2h_probe.hip: as fast as
      * whole rows, and as fast as the copy engine moves one large buffer), and a picture costs ONE launch on the compute queue instead
      * of a kernel, two copy-engine transfers and the hand-overs between the engines */
     hipLaunchKernelGGL(h264k::k_detile, dim3(512, 1), dim3(256), 0, st, s->d_frames + (size_t)slot * s->frame_bytes,
-                       s->hd_frame[slot], s->wmb, s->hmb, (size_t)0, (size_t)0);
+                       s->h_frame[slot].dev(), s->wmb, s->hmb, (size_t)0, (size_t)0);
     if (hipGetLastError() != hipSuccess) return -1;
     if (out_end_locked(u, st)) return -1;
     s->out_slot = (int)slot;
@@ -1038,10 +1001,9 @@ uint32_t *sink_fetch_converted(void *user, uint32_t slot, int fmt)
         if (slot >= s->n_slots || out_begin(u, true, &st)) return nullptr;
         const uint32_t w = s->wmb * 16, h = s->hmb * 16;
         const size_t bytes = (size_t)w * h * 4;
-        if (!s->h_conv && hipHostMalloc((void **)&s->h_conv, bytes, hipHostMallocDefault) != hipSuccess) { s->h_conv = nullptr; return nullptr; }
-        if (!s->hd_conv && hipHostGetDevicePointer((void **)&s->hd_conv, s->h_conv, 0) != hipSuccess) { s->hd_conv = nullptr; return nullptr; }
+        if (!s->h_conv && s->h_conv.alloc(bytes, true) != hipSuccess) return nullptr;
         hipLaunchKernelGGL(h264k::k_convert_tiles, dim3(1024, 1), dim3(256), 0, st,
-                           s->d_frames + (size_t)slot * s->frame_bytes, s->hd_conv, s->wmb, s->hmb, fmt, (size_t)0, (size_t)0);
+                           s->d_frames + (size_t)slot * s->frame_bytes, s->h_conv.dev(), s->wmb, s->hmb, fmt, (size_t)0, (size_t)0);
         if (hipGetLastError() != hipSuccess) return nullptr;
         if (out_end_locked(u, st)) return nullptr;
     }
@@ -1064,14 +1026,14 @@ void *sink_fetch_device(void *user, uint32_t slot, int fmt, uint32_t x0, uint32_
         /* frames are macroblock tiles in HBM: every picture that leaves is laid out by a kernel, the whole uncropped I420
          * frame by k_detile, everything else (window, conversion) by k_output */
         const size_t bytes = (size_t)fw * fh * 4;
-        if (!s->d_conv && hipMalloc((void **)&s->d_conv, bytes) != hipSuccess) return nullptr;
+        if (!s->d_conv && s->d_conv.alloc(bytes) != hipSuccess) return nullptr;
         if (fmt == 3 && x0 == 0 && y0 == 0 && w == fw && h == fh) {
-            hipLaunchKernelGGL(h264k::k_detile, dim3(512, 1), dim3(256), 0, u->e->stream, frame, reinterpret_cast<uint8_t *>(s->d_conv),
+            hipLaunchKernelGGL(h264k::k_detile, dim3(512, 1), dim3(256), 0, u->e->stream, frame, reinterpret_cast<uint8_t *>(s->d_conv.get()),
                                s->wmb, s->hmb, (size_t)0, (size_t)0);
         } else {
             const uint32_t n = fmt == 3 ? w * h * 3 / 8 : w * h / 4;
             hipLaunchKernelGGL(h264k::k_output, dim3((n + 255) / 256 < 2048 ? (n + 255) / 256 + 1 : 2048), dim3(256), 0, u->e->stream,
-                               frame, reinterpret_cast<uint8_t *>(s->d_conv), fw, fh, fmt, x0, y0, w, h);
+                               frame, reinterpret_cast<uint8_t *>(s->d_conv.get()), fw, fh, fmt, x0, y0, w, h);
         }
         ret = s->d_conv;
         if (out_end_locked(u, st)) return nullptr;
@@ -1156,13 +1118,11 @@ static int tensor_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, c
     if (n > e->titem_cap) {
         for (int k = 0; k < 2; k++)
             if (e->titem_used[k]) HIP_TRY(hipEventSynchronize(e->titem_ev[k]));
-        if (e->h_titems) HIP_TRY(hipHostFree(e->h_titems));
-        e->h_titems = e->dv_titems = nullptr; e->titem_cap = 0;
+        e->titem_cap = 0;
         const size_t cap = std::max<size_t>(n, 256);
-        HIP_TRY(hipHostMalloc((void **)&e->h_titems, 2 * cap * sizeof(h264k::TensorItem), hipHostMallocDefault));
-        HIP_TRY(hipHostGetDevicePointer((void **)&e->dv_titems, e->h_titems, 0));
+        HIP_TRY(e->h_titems.alloc(2 * cap * sizeof(h264k::TensorItem), true));
         for (int k = 0; k < 2; k++)
-            if (!e->titem_ev[k]) HIP_TRY(hipEventCreateWithFlags(&e->titem_ev[k], hipEventDisableTiming));
+            if (!e->titem_ev[k]) HIP_TRY(e->titem_ev[k].create(hipEventDisableTiming));
         e->titem_cap = cap; e->titem_used[0] = e->titem_used[1] = false; e->titem_flip = 0;
     }
     const int f = e->titem_flip;
@@ -1186,7 +1146,7 @@ static int tensor_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, c
         }
     }
     h264k::TensorArgs ta;
-    ta.items = e->dv_titems + (size_t)f * e->titem_cap;
+    ta.items = e->h_titems.dev() + (size_t)f * e->titem_cap;
     ta.width = t.width; ta.height = t.height;
     for (int c = 0; c < 3; c++) { ta.mean[c] = t.mean[c]; ta.std[c] = t.std[c]; }
     const uint32_t blocks = t.resize ? (t.width * t.height + 255u) / 256u : ((t.width + 63u) / 64u * ((t.height + 15u) / 16u) + 3u) / 4u;
@@ -1194,12 +1154,13 @@ static int tensor_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, c
     HIP_TRY(hipLaunchKernel(fn, dim3(std::min(blocks, 1024u), n), dim3(256), args, 0, st));
     HIP_TRY(hipEventRecord(e->titem_ev[f], st));
     e->titem_used[f] = true; e->titem_flip ^= 1;
-    hipLaunchKernelGGL(k_err_words, dim3(1), dim3(64), 0, st, e->d_err, e->hd_err);
+    hipLaunchKernelGGL(k_err_words, dim3(1), dim3(64), 0, st, e->d_err, e->h_err.dev());
     HIP_TRY(hipGetLastError());
     Fence *fc;
     if (e->fences.empty()) {
-        fc = new Fence();
-        HIP_TRY(hipEventCreateWithFlags(&fc->ev, hipEventDisableTiming));
+        std::unique_ptr<Fence> fresh(new Fence());
+        HIP_TRY(fresh->ev.create(hipEventDisableTiming));
+        fc = fresh.release();
     } else { fc = e->fences.back(); e->fences.pop_back(); }
     HIP_TRY(hipEventRecord(fc->ev, st));
     for (uint32_t i = 0; i < n; i++) {
@@ -1278,10 +1239,8 @@ void eng_convert_host(int fmt, uint32_t width, uint32_t height, const uint8_t *d
     const size_t in_b = (size_t)width * height * 3 / 2, out_b = (size_t)width * height * 4;
     if (hipSetDevice(e->device) != hipSuccess) return;
     if (out_b > e->conv_cap) {
-        if (e->conv_in) hipFree(e->conv_in);
-        if (e->conv_out) hipFree(e->conv_out);
-        e->conv_in = nullptr; e->conv_out = nullptr; e->conv_cap = 0;
-        if (hipMalloc((void **)&e->conv_in, in_b + 64) != hipSuccess || hipMalloc((void **)&e->conv_out, out_b) != hipSuccess) return;
+        e->conv_in.reset(); e->conv_out.reset(); e->conv_cap = 0;
+        if (e->conv_in.alloc(in_b + 64) != hipSuccess || e->conv_out.alloc(out_b) != hipSuccess) return;
         e->conv_cap = out_b;
     }
     if (hipMemcpyAsync(e->conv_in, data, in_b, hipMemcpyHostToDevice, e->stream) != hipSuccess) return;
@@ -1413,54 +1372,55 @@ struct h264bsdmi_replay {
     uint32_t n_pics, n_streams, n_slots, wmb, hmb, frame_bytes;
     size_t blob_stride;               /* bytes of all blobs of one stream (256-aligned) */
     unsigned long long job_bytes;     /* sum of the blob sizes of one stream */
-    uint8_t *d_blobs;                 /* n_streams * blob_stride */
-    uint8_t *d_frames;                /* n_streams * n_slots * frame_bytes */
-    uint8_t *d_dbk;                   /* n_streams * n_mbs * 32 */
-    FrameDesc *d_desc;                /* n_pics * n_streams */
-    uint32_t *d_conv;                 /* n_streams * w*h (lazy) */
-    uint8_t *d_planar = nullptr;      /* one frame, planar (h264bsdmiReplayFetch) */
-    unsigned long long *d_sums;
+    DeviceMem<uint8_t> d_blobs;       /* n_streams * blob_stride */
+    DeviceMem<uint8_t> d_frames;      /* n_streams * n_slots * frame_bytes */
+    DeviceMem<uint8_t> d_dbk;         /* n_streams * n_mbs * 32 */
+    DeviceMem<FrameDesc> d_desc;      /* n_pics * n_streams */
+    DeviceMem<uint32_t> d_conv;       /* n_streams * w*h (lazy) */
+    DeviceMem<uint8_t> d_planar;      /* one frame, planar (h264bsdmiReplayFetch) */
+    DeviceMem<unsigned long long> d_sums;
     std::vector<TickShape> shapes;
     std::vector<uint8_t> cur_slot;
     std::vector<TickTimers> timers;
     uint32_t timed_first, timed_count;
-    hipEvent_t ev_begin, ev_end, gdone_any = nullptr;
+    Event ev_begin, ev_end, gdone_any;
     uint32_t launches[5];
     unsigned stages;
     uint32_t n_groups;
-    hipStream_t gstream[8];
-    hipEvent_t gdone[8];
+    Stream gstream[8];
+    Event gdone[8];
     bool overlap_dbk = true;
     unsigned timed_mask = 31u;
     /* desynchronised sets with heavy lanes (h264bsdmiReplayCreateDesync, lanes > 0): a static launch schedule */
     struct Launch { size_t first; TickShape shape; int lane; std::vector<int> waits; int record_ev; bool light; };
     std::vector<Launch> sched;
-    std::vector<hipEvent_t> sched_ev;
+    std::vector<Event> sched_ev;
     static constexpr int MAX_LANES = 72;  /* lanes 0..n_light-1: one per stream group (light pictures), then the heavy lanes */
-    hipStream_t lanes[MAX_LANES] = {};
+    Stream lanes[MAX_LANES];
     SideLane lane_side[MAX_LANES];        /* k_dbk next to the reconstruction kernels, per light lane */
     uint32_t n_lanes = 0, n_light = 0;
     /* HIP streams of earlier schedules of this set, reused by the next one (normal priority: light lanes and stream groups; highest: heavy
      * lanes; side-stream pairs).  A process that creates and destroys a dozen streams per schedule falls off the runtime's stream cliff after
      * a few of them (a 12-lane schedule then takes seconds per lap, the same schedule in a fresh process 0.13 s): nothing is destroyed before the set is. */
-    std::vector<hipStream_t> pool_normal, pool_high;
+    std::vector<Stream> pool_normal, pool_high;
     std::vector<SideLane> pool_side;
+    void retire_stream(Stream &st) { if (st) (st.high ? pool_high : pool_normal).push_back(std::move(st)); }
     void retire_streams()
     {
         for (uint32_t k = 0; k < (uint32_t)MAX_LANES; k++) {
-            if (lanes[k]) { (k < n_light ? pool_normal : pool_high).push_back(lanes[k]); lanes[k] = nullptr; }
-            if (lane_side[k].stream) { pool_side.push_back(lane_side[k]); lane_side[k] = SideLane(); }
+            retire_stream(lanes[k]);
+            if (lane_side[k].stream) pool_side.push_back(std::move(lane_side[k]));
         }
     }
-    bool take_stream(hipStream_t *st, bool high, int prio)
+    bool take_stream(Stream *st, bool high, int prio)
     {
-        std::vector<hipStream_t> &pool = high ? pool_high : pool_normal;
-        if (!pool.empty()) { *st = pool.back(); pool.pop_back(); return true; }
-        return (high ? hipStreamCreateWithPriority(st, hipStreamNonBlocking, prio) : hipStreamCreateWithFlags(st, hipStreamNonBlocking)) == hipSuccess;
+        std::vector<Stream> &pool = high ? pool_high : pool_normal;
+        if (!pool.empty()) { *st = std::move(pool.back()); pool.pop_back(); return true; }
+        return (high ? st->create(prio) : st->create()) == hipSuccess;
     }
     bool take_side(SideLane *sl)
     {
-        if (!pool_side.empty()) { *sl = pool_side.back(); pool_side.pop_back(); return true; }
+        if (!pool_side.empty()) { *sl = std::move(pool_side.back()); pool_side.pop_back(); return true; }
         return sl->create(0, false);
     }
     std::vector<uint32_t> offsets;    /* first picture of every stream */
@@ -1470,10 +1430,10 @@ struct h264bsdmi_replay {
     size_t frames_per_stream = 0, dbk_half = 0, dbk_stride = 0;
     /* config 3 ("ARGB conversion on-GPU"): colour conversion of every produced picture inside the run, timed */
     int convert_fmt = -1;
-    std::vector<hipEvent_t> cev;      /* 2 per tick */
+    std::vector<Event> cev;           /* 2 per tick */
     /* ... hosted by the NEXT tick's k_frame_dbk where that is possible (kernels/convert.hip.h, conv_drain): descriptors with the
      * conversion of the stream's previous picture written in, which ticks host */
-    FrameDesc *d_desc_conv = nullptr;
+    DeviceMem<FrameDesc> d_desc_conv;
     std::vector<uint8_t> hosted;      /* tick i converts the pictures of tick i - 1 while it filters its own */
     std::vector<uint8_t> cev_on;      /* tick i was followed by a stand-alone conversion launch in the last run */
     bool host_convert = true, convert_trailing = true;
@@ -1542,7 +1502,7 @@ static bool replay_schedule(h264bsdmi_replay *r, u32 heavy_lanes, u32 heavy_dela
                 }
                 return c;
             };
-            auto new_event = [&]() { r->sched_ev.push_back(nullptr); return (int)r->sched_ev.size() - 1; };
+            auto new_event = [&]() { r->sched_ev.emplace_back(); return (int)r->sched_ev.size() - 1; };
             for (u32 t = 0; left && t < 16u * n_pics; t++) {
                 /* one heavy launch per round for the heavy pictures of all groups: it waits for the light launch of
                  * every group it takes a stream from (the previous picture of that stream ran there or earlier) */
@@ -1618,7 +1578,7 @@ static bool replay_schedule(h264bsdmi_replay *r, u32 heavy_lanes, u32 heavy_dela
                         ok = r->take_side(&r->lane_side[k]);
                 } else ok = r->take_stream(&r->lanes[k], true, prio_greatest);
             }
-            for (auto &ev : r->sched_ev) if (ok) ok = hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess;
+            for (auto &ev : r->sched_ev) if (ok) ok = ev.create(hipEventDisableTiming) == hipSuccess;
         }
         if (ok) ok = hipMemcpyAsync(r->d_desc, descs.data(), descs.size() * sizeof(FrameDesc), hipMemcpyHostToDevice, e->stream) == hipSuccess &&
                      hipStreamSynchronize(e->stream) == hipSuccess;
@@ -1685,15 +1645,14 @@ h264bsdmi_replay *h264bsdmiReplayCreateSched(const u8 *const *blobs, const u32 *
     for (u32 i = 0; i < n_pics; i++) { offs[i] = total; total += ((size_t)bytes[i] + 255u) & ~(size_t)255u; r->job_bytes += bytes[i]; }
     r->blob_stride = total;
     r->blob_off = offs;
-    r->d_blobs = nullptr; r->d_frames = nullptr; r->d_desc = nullptr; r->d_conv = nullptr; r->d_sums = nullptr; r->d_dbk = nullptr;
     const size_t frames_per_stream = (size_t)r->n_slots * r->frame_bytes;
     const size_t dbk_half = (DBK_SCRATCH_BYTES(h0->n_mbs) + 255) & ~(size_t)255, dbk_stride = dbk_half;
     r->frames_per_stream = frames_per_stream; r->dbk_half = dbk_half; r->dbk_stride = dbk_stride;
-    bool ok = hipMalloc((void **)&r->d_blobs, total * n_streams) == hipSuccess &&
-              hipMalloc((void **)&r->d_frames, frames_per_stream * n_streams + 256) == hipSuccess &&
-              hipMalloc((void **)&r->d_desc, sizeof(FrameDesc) * (size_t)n_pics * n_streams) == hipSuccess &&
-              hipMalloc((void **)&r->d_sums, sizeof(unsigned long long) * n_streams) == hipSuccess &&
-              hipMalloc((void **)&r->d_dbk, (size_t)n_streams * dbk_stride) == hipSuccess;
+    bool ok = r->d_blobs.alloc(total * n_streams) == hipSuccess &&
+              r->d_frames.alloc(frames_per_stream * n_streams + 256) == hipSuccess &&
+              r->d_desc.alloc(sizeof(FrameDesc) * (size_t)n_pics * n_streams) == hipSuccess &&
+              r->d_sums.alloc(sizeof(unsigned long long) * n_streams) == hipSuccess &&
+              r->d_dbk.alloc((size_t)n_streams * dbk_stride) == hipSuccess;
     if (ok) ok = hipMemsetAsync(r->d_dbk, 0, (size_t)n_streams * dbk_stride, e->stream) == hipSuccess;
     if (ok) ok = hipMemsetAsync(r->d_frames, 0, frames_per_stream * n_streams + 256, e->stream) == hipSuccess;
     /* stream 0 from the host, the other copies device-to-device: every stream owns private jobs */
@@ -1710,22 +1669,15 @@ h264bsdmi_replay *h264bsdmiReplayCreateSched(const u8 *const *blobs, const u32 *
     if (ok) ok = replay_schedule(r, heavy_lanes, heavy_delay, groups);
     r->timers.resize(n_pics);
     for (auto &t : r->timers) {
-        for (auto &ev : t.ev) if (ok) ok = hipEventCreate(&ev) == hipSuccess;
-        for (auto &ev : t.sev) if (ok) ok = hipEventCreate(&ev) == hipSuccess;
+        for (auto &ev : t.ev) if (ok) ok = ev.create() == hipSuccess;
+        for (auto &ev : t.sev) if (ok) ok = ev.create() == hipSuccess;
     }
-    if (ok) ok = hipEventCreate(&r->ev_begin) == hipSuccess && hipEventCreate(&r->ev_end) == hipSuccess &&
-                 hipEventCreateWithFlags(&r->gdone_any, hipEventDisableTiming) == hipSuccess;
+    if (ok) ok = r->ev_begin.create() == hipSuccess && r->ev_end.create() == hipSuccess && r->gdone_any.create(hipEventDisableTiming) == hipSuccess;
     r->timed_first = r->timed_count = 0;
     r->stages = 7u;
     r->n_groups = 1;
-    for (int g = 0; g < 8; g++) { r->gstream[g] = nullptr; r->gdone[g] = nullptr; }
     if (!ok) {
         fprintf(stderr, "h264bsd-mi355x: h264bsdmiReplayCreate failed (%s)\n", hipGetErrorString(hipGetLastError()));
-        if (r->d_blobs) hipFree(r->d_blobs);
-        if (r->d_frames) hipFree(r->d_frames);
-        if (r->d_desc) hipFree(r->d_desc);
-        if (r->d_sums) hipFree(r->d_sums);
-        if (r->d_dbk) hipFree(r->d_dbk);
         delete r;
         return nullptr;
     }
@@ -1737,19 +1689,7 @@ void h264bsdmiReplayDestroy(h264bsdmi_replay *r)
     if (!r) return;
     std::lock_guard<std::mutex> lk(r->e->mu);
     hipSetDevice(r->e->device);
-    hipStreamSynchronize(r->e->stream);
-    hipFree(r->d_blobs); hipFree(r->d_frames); hipFree(r->d_desc); hipFree(r->d_sums); hipFree(r->d_dbk);
-    if (r->d_conv) hipFree(r->d_conv);
-    if (r->d_desc_conv) hipFree(r->d_desc_conv);
-    if (r->d_planar) hipFree(r->d_planar);
-    for (auto &t : r->timers) for (auto &ev : t.ev) hipEventDestroy(ev);
-    hipEventDestroy(r->ev_begin); hipEventDestroy(r->ev_end); if (r->gdone_any) hipEventDestroy(r->gdone_any);
-    for (int g = 0; g < 8; g++) { if (r->gstream[g]) { tickets_release(r->gstream[g]); hipStreamDestroy(r->gstream[g]); } if (r->gdone[g]) hipEventDestroy(r->gdone[g]); }
-    for (auto &ev : r->sched_ev) if (ev) hipEventDestroy(ev);
-    for (auto &ev : r->cev) hipEventDestroy(ev);
-    r->retire_streams();
-    for (auto *pool : { &r->pool_normal, &r->pool_high }) for (auto &st : *pool) { tickets_release(st); hipStreamDestroy(st); }
-    for (auto &sl : r->pool_side) sl.destroy();
+    hipStreamSynchronize(r->e->stream);           /* (every lane and stream group of the set is joined into it: h264bsdmiReplayRun) */
     delete r;
 }
 
@@ -1770,10 +1710,9 @@ int h264bsdmiReplayReschedule(h264bsdmi_replay *r, const u32 *offsets, u32 heavy
     for (int g = 0; g < 8; g++) if (r->gstream[g]) HIP_TRY(hipStreamSynchronize(r->gstream[g]));
     HIP_TRY(hipStreamSynchronize(e->stream));
     if (poll_errors(e)) return -1;
-    for (auto &ev : r->sched_ev) if (ev) hipEventDestroy(ev);
     r->sched_ev.clear(); r->sched.clear();
     r->retire_streams();                               /* (kept for the next schedule: h264bsdmi_replay::pool_*) */
-    for (int g = 0; g < 8; g++) if (r->gstream[g]) { r->pool_normal.push_back(r->gstream[g]); r->gstream[g] = nullptr; }      /* h264bsdmiReplaySetGroups takes them back */
+    for (auto &st : r->gstream) r->retire_stream(st);  /* h264bsdmiReplaySetGroups takes them back */
     r->n_lanes = r->n_light = 0;
     r->n_groups = 1;                                  /* (h264bsdmiReplaySetGroups: a property of the schedule it was set for) */
     r->convert_fmt = -1; r->timed_mask = 31u; r->stages = 7u;
@@ -1874,12 +1813,12 @@ int h264bsdmiReplaySetGroups(h264bsdmi_replay *r, u32 n_groups)
     HIP_TRY(hipSetDevice(r->e->device));
     while (r->timers.size() < (size_t)n_groups * r->n_pics) {
         TickTimers t;
-        for (auto &ev : t.ev) HIP_TRY(hipEventCreate(&ev));
-        r->timers.push_back(t);
+        for (auto &ev : t.ev) HIP_TRY(ev.create());
+        r->timers.push_back(std::move(t));
     }
     for (u32 g = 0; g < n_groups; g++) {
         if (!r->gstream[g] && !r->take_stream(&r->gstream[g], false, 0)) return -1;
-        if (!r->gdone[g]) HIP_TRY(hipEventCreateWithFlags(&r->gdone[g], hipEventDisableTiming));
+        if (!r->gdone[g]) HIP_TRY(r->gdone[g].create(hipEventDisableTiming));
     }
     r->n_groups = n_groups;
     return 0;
@@ -1928,7 +1867,7 @@ int h264bsdmiReplayFetch(h264bsdmi_replay *r, u32 stream, u32 slot, u8 *dst)
     if (!r || stream >= r->n_streams || slot >= r->n_slots) return -1;
     HIP_TRY(hipSetDevice(r->e->device));
     std::lock_guard<std::mutex> lk(r->e->mu);
-    if (!r->d_planar) HIP_TRY(hipMalloc((void **)&r->d_planar, r->frame_bytes));
+    if (!r->d_planar) HIP_TRY(r->d_planar.alloc(r->frame_bytes));
     hipLaunchKernelGGL(h264k::k_detile, dim3(512, 1), dim3(256), 0, r->e->stream, r->d_frames + ((size_t)stream * r->n_slots + slot) * r->frame_bytes,
                        r->d_planar, r->wmb, r->hmb, (size_t)0, (size_t)0);
     HIP_TRY(hipMemcpyAsync(dst, r->d_planar, r->frame_bytes, hipMemcpyDeviceToHost, r->e->stream));
@@ -1954,7 +1893,7 @@ int h264bsdmiReplayConvert(h264bsdmi_replay *r, u32 slot, int fmt)
     std::lock_guard<std::mutex> lk(r->e->mu);
     HIP_TRY(hipSetDevice(r->e->device));
     const uint32_t w = r->wmb * 16, h = r->hmb * 16;
-    if (!r->d_conv) HIP_TRY(hipMalloc((void **)&r->d_conv, (size_t)w * h * 4 * r->n_streams));
+    if (!r->d_conv) HIP_TRY(r->d_conv.alloc((size_t)w * h * 4 * r->n_streams));
     hipLaunchKernelGGL(h264k::k_convert_tiles, CONVERT_GRID(r->n_streams), dim3(256), 0, r->e->stream,
                        r->d_frames + (size_t)slot * r->frame_bytes, r->d_conv, r->wmb, r->hmb, fmt,
                        (size_t)r->n_slots * r->frame_bytes, (size_t)w * h);
@@ -1985,8 +1924,8 @@ int h264bsdmiReplaySetConvert(h264bsdmi_replay *r, int fmt_and_flags)
     HIP_TRY(hipSetDevice(r->e->device));
     if (fmt >= 0) {
         const size_t n = (size_t)r->wmb * 16 * r->hmb * 16;
-        if (!r->d_conv) HIP_TRY(hipMalloc((void **)&r->d_conv, n * 4 * r->n_streams));
-        while (r->cev.size() < 2 * (size_t)r->n_pics) { hipEvent_t ev; HIP_TRY(hipEventCreate(&ev)); r->cev.push_back(ev); }
+        if (!r->d_conv) HIP_TRY(r->d_conv.alloc(n * 4 * r->n_streams));
+        while (r->cev.size() < 2 * (size_t)r->n_pics) { Event ev; HIP_TRY(ev.create()); r->cev.push_back(std::move(ev)); }
         /* Hosting.  Tick i can
          * convert the pictures of tick i - 1 while it decodes its own if no stream decodes INTO the frame buffer its previous
          * picture lies in (an IDR picture may); the stand-alone launch converts one frame buffer number for all streams, so the
@@ -2000,7 +1939,7 @@ int h264bsdmiReplaySetConvert(h264bsdmi_replay *r, int fmt_and_flags)
         r->hosted.assign(r->n_pics, 0);
         for (u32 i = 1; in_step && i < r->n_pics; i++) r->hosted[i] = r->cur_slot[i] != r->cur_slot[i - 1];
         const size_t n_desc = (size_t)r->n_pics * r->n_streams;
-        if (!r->d_desc_conv) HIP_TRY(hipMalloc((void **)&r->d_desc_conv, sizeof(FrameDesc) * n_desc));
+        if (!r->d_desc_conv) HIP_TRY(r->d_desc_conv.alloc(sizeof(FrameDesc) * n_desc));
         std::vector<FrameDesc> descs(n_desc);
         HIP_TRY(hipMemcpy(descs.data(), r->d_desc, sizeof(FrameDesc) * n_desc, hipMemcpyDeviceToHost));
         for (u32 i = 1; i < r->n_pics; i++)
@@ -2054,13 +1993,12 @@ int h264bsdmiDebugTailProfile(int enable, unsigned long long *out)
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(hipDeviceSynchronize());
     if (enable) {
-        if (!e->tail_prof) HIP_TRY(hipMalloc((void **)&e->tail_prof, (16 * 16 + 16 * 8) * sizeof(unsigned long long)));
+        if (!e->tail_prof) HIP_TRY(e->tail_prof.alloc((16 * 16 + 16 * 8) * sizeof(unsigned long long)));
         HIP_TRY(hipMemset(e->tail_prof, 0, (16 * 16 + 16 * 8) * sizeof(unsigned long long)));
         HIP_TRY(hipDeviceSynchronize());
     } else if (e->tail_prof) {
         if (out) HIP_TRY(hipMemcpy(out, e->tail_prof, (16 * 16 + 16 * 8) * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        HIP_TRY(hipFree(e->tail_prof));
-        e->tail_prof = nullptr;
+        e->tail_prof.reset();
     }
     return 0;
 }

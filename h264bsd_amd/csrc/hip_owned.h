@@ -1,0 +1,53 @@
+/* hip_owned.h — move-only owners of the engine's HIP objects (engine.hip): stream, event, device and pinned host allocation.  An owner
+ * releases its object when it goes or is reset, and nothing else in the engine does (tests/test_abi.py); waiting for the device first is
+ * the holder's business.  A creation that fails leaves the owner empty and returns the HIP error. */
+#ifndef H264BSD_AMD_HIP_OWNED_H
+#define H264BSD_AMD_HIP_OWNED_H
+#include <hip/hip_runtime.h>
+#include <utility>
+
+void tickets_release(hipStream_t st);       /* engine.hip: the ticket counters of the stream's banded launches */
+
+template <class H, void (*Release)(H)> class Owned {
+public:
+    Owned() = default;
+    Owned(Owned &&o) noexcept : h_(std::exchange(o.h_, H())) {}
+    Owned &operator=(Owned &&o) noexcept { if (this != &o) { reset(); h_ = std::exchange(o.h_, H()); } return *this; }
+    ~Owned() { reset(); }
+    void reset() { if (h_) Release(std::exchange(h_, H())); }
+    operator H() const { return h_; }
+    H get() const { return h_; }
+protected:
+    H h_ = H();
+    hipError_t created(hipError_t err) { if (err != hipSuccess) h_ = H(); return err; }
+};
+inline void stream_destroy(hipStream_t s) { tickets_release(s); (void)hipStreamDestroy(s); }
+inline void event_destroy(hipEvent_t ev) { (void)hipEventDestroy(ev); }
+template <class T> void device_free(T *p) { (void)hipFree(p); }
+template <class T> void host_free(T *p) { (void)hipHostFree(p); }
+
+struct Stream : Owned<hipStream_t, stream_destroy> {      /* non-blocking; high: created with a priority of its own */
+    bool high = false;
+    hipError_t create() { reset(); high = false; return created(hipStreamCreateWithFlags(&h_, hipStreamNonBlocking)); }
+    hipError_t create(int priority) { reset(); high = true; return created(hipStreamCreateWithPriority(&h_, hipStreamNonBlocking, priority)); }
+};
+struct Event : Owned<hipEvent_t, event_destroy> {
+    hipError_t create(unsigned flags = hipEventDefault) { reset(); return created(hipEventCreateWithFlags(&h_, flags)); }
+};
+template <class T> struct DeviceMem : Owned<T *, device_free<T>> {
+    hipError_t alloc(size_t bytes) { this->reset(); return this->created(hipMalloc((void **)&this->h_, bytes)); }
+};
+/* pinned host memory; dev(): the device's address of it, where alloc() was asked for one */
+template <class T> struct Pinned : Owned<T *, host_free<T>> {
+    hipError_t alloc(size_t bytes, bool with_dev = false)
+    {
+        this->reset(); d_ = nullptr;
+        hipError_t err = this->created(hipHostMalloc((void **)&this->h_, bytes, hipHostMallocDefault));
+        if (err == hipSuccess && with_dev && (err = hipHostGetDevicePointer((void **)&d_, this->h_, 0)) != hipSuccess) this->reset();
+        return err;
+    }
+    T *dev() const { return this->h_ ? d_ : nullptr; }
+private:
+    T *d_ = nullptr;
+};
+#endif

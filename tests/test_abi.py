@@ -152,6 +152,25 @@ def test_only_documented_environment_switches_exist():
     assert engine.count("getenv") <= 8
 
 
+# ---- every HIP stream, event and buffer of the engine has one owner (h264bsd_amd/csrc/hip_owned.h) ----
+def test_hip_objects_are_released_only_by_their_owner_types():
+    """hipStreamDestroy / hipEventDestroy / hipFree / hipHostFree appear in the engine sources only in the release hooks of the
+    owner types, once each: whatever creates a HIP object releases it when it goes, no hand-kept release list can drift"""
+    csrc = os.path.join(ROOT, "h264bsd_amd", "csrc")
+    calls = {}
+    for d, _, files in os.walk(csrc):
+        for f in files:
+            if f.endswith((".c", ".h", ".hip")):
+                code = re.sub(r"/\*.*?\*/|//[^\n]*", " ", open(os.path.join(d, f)).read(), flags=re.S)
+                for name in re.findall(r"\b(hipStreamDestroy|hipEventDestroy|hipFree|hipHostFree)\s*\(", code):
+                    calls.setdefault(name, []).append(os.path.relpath(os.path.join(d, f), csrc))
+    assert calls == {n: ["hip_owned.h"] for n in ("hipStreamDestroy", "hipEventDestroy", "hipFree", "hipHostFree")}, calls
+    owned = open(os.path.join(csrc, "hip_owned.h")).read()
+    assert re.search(r"stream_destroy\(hipStream_t \w+\) \{ tickets_release\(\w+\);", owned), "a stream's release drops its ticket counters"
+    engine = open(os.path.join(csrc, "engine.hip")).read()
+    assert '#include "hip_owned.h"' in engine and len(re.findall(r"\btickets_release\s*\(", engine)) == 1      # (its definition only)
+
+
 def test_unknown_environment_switch_is_reported(built):
     """a misspelt or retired H264BSDMI_* variable must not be silently ignored: the library names it on stderr when it is loaded"""
     code = ("import sys; sys.path.insert(0, %r); import h264bsd_amd; h264bsd_amd.lib()" % ROOT)
