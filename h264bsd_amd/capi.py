@@ -28,7 +28,7 @@ EXPORTED_SYMBOLS = [
     "h264bsdCroppingParams", "h264bsdSampleAspectRatio", "h264bsdCheckValidParamSets", "h264bsdFlushBuffer",
     "h264bsdProfile", "h264bsdAlloc", "h264bsdFree", "h264bsdConvertToRGBA", "h264bsdConvertToBGRA",
     "h264bsdConvertToYCbCrA",
-    "h264bsdmiInitCapture", "h264bsdmiNextOutputInfo", "h264bsdmiNextOutputPictureDevice", "h264bsdmiNextOutputTensorBatch", "h264bsdmiJobFinalize", "h264bsdmiDeviceCount", "h264bsdmiSetDevice", "h264bsdmiFlush", "h264bsdmiFlushAsync", "h264bsdmiDeviceErrors",
+    "h264bsdmiInitCapture", "h264bsdmiNextOutputInfo", "h264bsdmiNextOutputPictureDevice", "h264bsdmiNextOutputTensorBatch", "h264bsdmiNextOutputTensorBatchColour", "h264bsdmiJobFinalize", "h264bsdmiDeviceCount", "h264bsdmiSetDevice", "h264bsdmiFlush", "h264bsdmiFlushAsync", "h264bsdmiDeviceErrors",
     "h264bsdmiDecodePicture", "h264bsdmiDecodePictureBatch", "h264bsdmiNextOutputPictureBatch", "h264bsdmiPullAndDecodePictureBatch", "h264bsdmiSetParserThreads", "h264bsdmiSetInputReadOnly", "h264bsdmiSetCopyElision",
     "h264bsdmiReplayCreate", "h264bsdmiReplayCreateStaggered", "h264bsdmiReplayCreateDesync", "h264bsdmiReplayCreateSched", "h264bsdmiReplayReschedule", "h264bsdmiReplayDestroy", "h264bsdmiReplayRun", "h264bsdmiReplaySync",
     "h264bsdmiReplayFetch", "h264bsdmiReplayChecksums", "h264bsdmiReplayConvert", "h264bsdmiReplayFetchConverted",
@@ -52,6 +52,14 @@ class TensorSpec(ctypes.Structure):
                 ("mean", ctypes.c_float * 3), ("std", ctypes.c_float * 3)]
 
 
+class ColourSpec(ctypes.Structure):
+    """h264bsdmi_colour_spec (include/h264bsd_mi355x.h)"""
+    _fields_ = [("matrix", ctypes.c_uint32), ("range", ctypes.c_uint32), ("chroma", ctypes.c_uint32), ("unspecified", ctypes.c_uint32)]
+
+
+MATRICES = {"reference": 0, "auto": 1, "bt601": 2, "bt709": 3, "bt2020": 4, "fcc": 5, "smpte240": 6}    # H264BSDMI_MATRIX_*
+RANGES = {"auto": 0, "limited": 1, "full": 2}                                                          # H264BSDMI_RANGE_*
+CHROMA = {"nearest": 0, "bilinear": 1}                                                                 # H264BSDMI_CHROMA_*
 LAYOUTS = {"NCHW": 0, "NHWC": 1}
 CHANNELS = {"RGB": (0, 3), "BGR": (1, 3), "RGBA": (2, 4), "BGRA": (3, 4), "Y": (4, 1)}     # name -> (H264BSDMI_CH_*, channels)
 
@@ -154,6 +162,9 @@ def _declare(L, harness):
     L.h264bsdmiNextOutputPictureDevice.restype = ctypes.c_int
     L.h264bsdmiNextOutputTensorBatch.argtypes = [u32, ctypes.POINTER(vp), ctypes.POINTER(TensorSpec), vp, P32, P32, P32, P32]
     L.h264bsdmiNextOutputTensorBatch.restype = ctypes.c_int
+    L.h264bsdmiNextOutputTensorBatchColour.argtypes = [u32, ctypes.POINTER(vp), ctypes.POINTER(TensorSpec), ctypes.POINTER(ColourSpec), vp,
+                                                       P32, P32, P32, P32]
+    L.h264bsdmiNextOutputTensorBatchColour.restype = ctypes.c_int
     L.h264bsdmiDecodePicture.argtypes = [vp, u8p, u32, u32, P32, P32]
     L.h264bsdmiDecodePicture.restype = u32
     L.h264bsdmiDecodePictureBatch.argtypes = [u32, ctypes.POINTER(vp), ctypes.POINTER(vp), P32, P32, P32, P32, P32]
@@ -456,7 +467,7 @@ def pull_batch(decoders, frame_bytes=None):
 
 
 def pull_tensor(decoders, size=None, layout="NCHW", dtype=None, channels="RGB", mean=(0, 0, 0), std=(1, 1, 1), crop=True,
-                out=None, stream=None):
+                out=None, stream=None, colour="reference", colour_range="auto", chroma="nearest", unspecified="bt601"):
     """h264bsdmiNextOutputTensorBatch: the next output picture of every decoder, written by one kernel launch into ONE dense CUDA
     tensor, [N, C, H, W] (layout "NCHW") or [N, H, W, C] ("NHWC"), N = len(decoders), in torch.uint8 / float16 (default) / float32.
     channels: "RGB", "BGR", "RGBA", "BGRA" (NHWC only) or "Y" (the luma samples).  Float outputs are (v / 255 - mean[c]) / std[c].
@@ -464,13 +475,22 @@ def pull_tensor(decoders, size=None, layout="NCHW", dtype=None, channels="RGB", 
     the coded frame) must have the size of the first decoder's; otherwise bilinear (align_corners=False, no antialiasing).
     out: a contiguous CUDA tensor of that shape and dtype to write into (None: allocated); decoders that have no picture leave
     their slice of it untouched.  stream: a torch.cuda.Stream (default: the current one) — the call returns without waiting,
-    the tensor is valid for work on that stream (torch's legacy default stream: the call waits).  Returns (tensor, got, pic_ids, is_idr, num_err_mbs), lists of ints."""
+    the tensor is valid for work on that stream (torch's legacy default stream: the call waits).
+    colour: "reference" (h264bsdmiNextOutputTensorBatch: the integer BT.601 conversion of next_output_picture(FMT_RGBA)), or
+    h264bsdmiNextOutputTensorBatchColour with "auto" (each stream's VUI matrix_coefficients; `unspecified` where it names none),
+    "bt601", "bt709", "bt2020", "fcc" or "smpte240"; colour_range "auto" (video_full_range_flag), "limited" or "full"; chroma
+    "nearest" or "bilinear".  Float outputs are then (v - mean[c]) / std[c] of the colour v in [0, 1], U8 round(255 v).
+    Returns (tensor, got, pic_ids, is_idr, num_err_mbs), lists of ints."""
     import torch
     if dtype is None:
         dtype = torch.float16
     dtypes = {torch.uint8: 0, torch.float16: 1, torch.float32: 2}
     if dtype not in dtypes or layout not in LAYOUTS or channels not in CHANNELS:
         raise ValueError(f"pull_tensor: unsupported dtype / layout / channels {dtype} {layout} {channels}")
+    if colour not in MATRICES or colour_range not in RANGES or chroma not in CHROMA or unspecified not in MATRICES or MATRICES[unspecified] < 2:
+        raise ValueError(f"pull_tensor: unsupported colour / colour_range / chroma / unspecified {colour} {colour_range} {chroma} {unspecified}")
+    if colour == "reference" and (colour_range != "auto" or chroma != "nearest"):
+        raise ValueError("pull_tensor: colour='reference' is the reference's conversion: colour_range and chroma do not apply")
     ch, C = CHANNELS[channels]
     n = len(decoders)
     if size is None:
@@ -498,9 +518,16 @@ def pull_tensor(decoders, size=None, layout="NCHW", dtype=None, channels="RGB", 
     VP = ctypes.c_void_p * n
     U32 = ctypes.c_uint32 * n
     got, ids, idr, nerr = U32(), U32(), U32(), U32()
-    rc = L.h264bsdmiNextOutputTensorBatch(n, VP(*[d._st for d in decoders]), ctypes.byref(spec), stream.cuda_stream, got, ids, idr, nerr)
+    if colour == "reference":
+        name = "h264bsdmiNextOutputTensorBatch"
+        rc = L.h264bsdmiNextOutputTensorBatch(n, VP(*[d._st for d in decoders]), ctypes.byref(spec), stream.cuda_stream, got, ids, idr, nerr)
+    else:
+        name = "h264bsdmiNextOutputTensorBatchColour"
+        cs = ColourSpec(MATRICES[colour], RANGES[colour_range], CHROMA[chroma], MATRICES[unspecified])
+        rc = L.h264bsdmiNextOutputTensorBatchColour(n, VP(*[d._st for d in decoders]), ctypes.byref(spec), ctypes.byref(cs), stream.cuda_stream,
+                                                    got, ids, idr, nerr)
     if rc != 0:
-        raise RuntimeError(f"h264bsdmiNextOutputTensorBatch failed ({rc})")
+        raise RuntimeError(f"{name} failed ({rc})")
     return out, list(got), list(ids), list(idr), list(nerr)
 
 

@@ -191,10 +191,48 @@ int h264bsdmiNextOutputPictureDevice(storage_t *s, int format, int crop, h264bsd
 /* The next pictures of n instances into one caller-owned device tensor.  Everything that can be refused is refused before the first
  * pop: the spec, the instances (bound to a device, distinct), every source window against the output size; the pictures are only
  * popped once the engine has enqueued their layout. */
+static int sps_full_range(const Sps *p) { return p && p->vui_present && p->video_signal_type_present && p->video_full_range; }
+static u32 sps_matrix_coefficients(const Sps *p)
+{
+    if (p && p->vui_present && p->video_signal_type_present && p->colour_description_present) return p->matrix_coefficients;
+    return 2;   /* unspecified */
+}
+/* H264BSDMI_MATRIX_* of matrix_coefficients (H.264 Table E-5); `unspecified` for 2 and the ones without a Kr / Kb matrix here */
+static u32 matrix_of(u32 mc, u32 unspecified)
+{
+    switch (mc) {
+    case 1: return H264BSDMI_MATRIX_BT709;
+    case 4: return H264BSDMI_MATRIX_FCC;
+    case 5: case 6: return H264BSDMI_MATRIX_BT601;
+    case 7: return H264BSDMI_MATRIX_SMPTE240;
+    case 9: return H264BSDMI_MATRIX_BT2020;
+    }
+    return unspecified;
+}
+
 int h264bsdmiNextOutputTensorBatch(u32 n, storage_t *const *dec, const h264bsdmi_tensor_spec *spec, void *stream,
                                    u32 *got, u32 *picId, u32 *isIdrPic, u32 *numErrMbs)
 {
+    return h264bsdmiNextOutputTensorBatchColour(n, dec, spec, NULL, stream, got, picId, isIdrPic, numErrMbs);
+}
+
+/* colour == NULL or REFERENCE: the reference's conversion.  Otherwise AUTO matrix and range are resolved here, per instance, from the
+ * active SPS the window comes from (the conditions of h264bsdMatrixCoefficients / h264bsdVideoRange). */
+int h264bsdmiNextOutputTensorBatchColour(u32 n, storage_t *const *dec, const h264bsdmi_tensor_spec *spec,
+                                         const h264bsdmi_colour_spec *colour, void *stream,
+                                         u32 *got, u32 *picId, u32 *isIdrPic, u32 *numErrMbs)
+{
     if (!dec || !spec || !got || !spec->data || !spec->width || !spec->height) return -1;
+    if (colour) {
+        if (colour->matrix > H264BSDMI_MATRIX_SMPTE240 || colour->range > H264BSDMI_RANGE_FULL || colour->chroma > H264BSDMI_CHROMA_BILINEAR)
+            return -1;
+        if (colour->unspecified && (colour->unspecified < H264BSDMI_MATRIX_BT601 || colour->unspecified > H264BSDMI_MATRIX_SMPTE240)) return -1;
+        if (colour->matrix == H264BSDMI_MATRIX_AUTO && !colour->unspecified) return -1;
+        if (colour->matrix == H264BSDMI_MATRIX_REFERENCE) {
+            if (colour->range || colour->chroma || colour->unspecified) return -1;
+            colour = NULL;
+        }
+    }
     if (spec->layout > H264BSDMI_LAYOUT_NHWC || spec->dtype > H264BSDMI_DTYPE_F32 || spec->channels > H264BSDMI_CH_Y) return -1;
     if (spec->layout == H264BSDMI_LAYOUT_NCHW && (spec->channels == H264BSDMI_CH_RGBA || spec->channels == H264BSDMI_CH_BGRA)) return -1;
     for (int c = 0; c < 3; c++) {
@@ -222,9 +260,14 @@ int h264bsdmiNextOutputTensorBatch(u32 n, storage_t *const *dec, const h264bsdmi
             h -= 2 * (sps->crop_top + sps->crop_bottom);
         }
         if (!spec->resize && (w != spec->width || h != spec->height)) { rc = -1; break; }
-        pics[m++] = (SinkTensorPic){ &a->hd->sink, d->out[d->out_idx].slot, i, x0, y0, w, h };
+        u32 matrix = 0, range = 0;
+        if (colour) {
+            matrix = colour->matrix == H264BSDMI_MATRIX_AUTO ? matrix_of(sps_matrix_coefficients(sps), colour->unspecified) : colour->matrix;
+            range = colour->range != H264BSDMI_RANGE_AUTO ? colour->range : sps_full_range(sps) ? H264BSDMI_RANGE_FULL : H264BSDMI_RANGE_LIMITED;
+        }
+        pics[m++] = (SinkTensorPic){ &a->hd->sink, d->out[d->out_idx].slot, i, x0, y0, w, h, matrix, range };
     }
-    if (!rc && m && pics[0].sink->tensor_out(m, pics, spec, stream)) rc = -2;
+    if (!rc && m && pics[0].sink->tensor_out(m, pics, spec, colour, stream)) rc = -2;
     free(pics);
     if (rc) return rc;
     for (u32 i = 0; i < n; i++) {
@@ -260,18 +303,8 @@ u32 h264bsdPicWidth(storage_t *s) { const Sps *p = active_sps(s); return p ? p->
 u32 h264bsdPicHeight(storage_t *s) { const Sps *p = active_sps(s); return p ? p->height_mbs : 0; }
 u32 h264bsdProfile(storage_t *s) { const Sps *p = active_sps(s); return p ? p->profile_idc : 0; }
 
-u32 h264bsdVideoRange(storage_t *s)
-{
-    const Sps *p = active_sps(s);
-    return (p && p->vui_present && p->video_signal_type_present && p->video_full_range) ? 1 : 0;
-}
-u32 h264bsdMatrixCoefficients(storage_t *s)
-{
-    const Sps *p = active_sps(s);
-    if (p && p->vui_present && p->video_signal_type_present && p->colour_description_present)
-        return p->matrix_coefficients;
-    return 2;   /* unspecified */
-}
+u32 h264bsdVideoRange(storage_t *s) { return sps_full_range(active_sps(s)) ? 1 : 0; }
+u32 h264bsdMatrixCoefficients(storage_t *s) { return sps_matrix_coefficients(active_sps(s)); }
 
 void h264bsdCroppingParams(storage_t *s, u32 *croppingFlag, u32 *left, u32 *width, u32 *top, u32 *height)
 {

@@ -1,0 +1,246 @@
+/* kernels/k_tensor_colour.hip.h — k_tensor_colour / k_tensor_colour_resize: h264bsdmiNextOutputTensorBatchColour, the tensor pull in a
+ * stream's own colour space (BT.601 / 709 / 2020 / FCC / SMPTE 240M, limited or full range, nearest or bilinear chroma).  One launch per
+ * call, grid.y = one item per picture, like k_tensor_out (whose TensorItem, ToElem, to_enc and to_store it uses); included by engine.hip
+ * after kernels/k_tensor_out.hip.h, and not part of the kernel sources that key the committed counter tables (srchash.py).
+ *
+ * Colour: per source pixel and output channel c, v = med3(k[c][0] Y + k[c][3] + k[c][1] (Cb - 128) + k[c][2] (Cr - 128), lo[c], hi[c])
+ * in fp32 on the 8-bit samples (Cb, Cr upsampled first when bilinear; centred, and luma first, so that no intermediate holds a large
+ * offset that the result cancels: f16 outputs near 0 need the absolute precision).  The host folds the range, the matrix of the
+ * picture, the clamp to [0, 1] and the output's scale (255 for U8, (. - mean[c]) / std[c] for floats) into the item (engine.hip,
+ * colour_item).  U8 writes rint(v),
+ * floats v (f16 rounded to nearest even); alpha is 255 / 1.0.  Since the output scale is affine, resizing interpolates v itself.
+ * Bilinear chroma (chroma_sample_loc_type 0): luma (x, y) takes chroma at (x / 2, y / 2 - 1/4): rows weighted 3/4 (its own) and 1/4
+ * (the one above for even y, below for odd y), columns 1 (even x) or 1/2 + 1/2 (odd x), neighbours clamped to the chroma of the
+ * source window; every weight is a multiple of 1/8, so the upsampled sample is exact in fp32. */
+#pragma once
+namespace h264k {
+
+struct ColourItem { TensorItem t; float k[3][4]; float lo[3], hi[3]; };
+struct ColourArgs { const ColourItem *items; uint32_t width, height, chroma; };
+enum { TC_NEAREST = 0, TC_BILINEAR = 1 };
+
+template <int C> constexpr int tc_nc() { return C == 1 ? 1 : 3; }
+
+__device__ __forceinline__ float tc_value(const ColourItem &it, int c, float y, float cb, float cr)
+{
+    return __builtin_amdgcn_fmed3f(fmaf(it.k[c][2], cr, fmaf(it.k[c][1], cb, fmaf(it.k[c][0], y, it.k[c][3]))), it.lo[c], it.hi[c]);
+}
+
+template <int DT> __device__ __forceinline__ typename ToElem<DT>::T tc_enc(float v)
+{
+    if constexpr (DT == TO_U8) return (uint8_t)(uint32_t)__builtin_rintf(v);
+    else return to_enc<DT>(v);
+}
+template <int DT> __device__ __forceinline__ typename ToElem<DT>::T tc_alpha()
+{
+    if constexpr (DT == TO_U8) return 255;
+    else return to_enc<DT>(1.0f);
+}
+
+/* chroma columns cx .. cx + 7 of row cy of one plane (byte k = column cx + k): word loads, two when cx is a multiple of 4, three
+ * otherwise; words beyond the coded chroma width ccw read as 0 */
+__device__ __forceinline__ unsigned long long tc_chroma8(const uint8_t *__restrict__ src, int wmb, int plane, uint32_t cx, uint32_t cy, uint32_t ccw)
+{
+    const uint32_t cxa = cx & ~3u, cs = (cx & 3u) * 8u;
+    unsigned long long v = *reinterpret_cast<const uint32_t *>(src + chroma_at(wmb, plane, (int)cxa, (int)cy));
+    if (cxa + 4u < ccw) v |= (unsigned long long)*reinterpret_cast<const uint32_t *>(src + chroma_at(wmb, plane, (int)cxa + 4, (int)cy)) << 32;
+    if (cs) {
+        const unsigned long long w2 = cxa + 8u < ccw ? *reinterpret_cast<const uint32_t *>(src + chroma_at(wmb, plane, (int)cxa + 8, (int)cy)) : 0u;
+        v = (v >> cs) | (w2 << (64u - cs));
+    }
+    return v;
+}
+
+/* the chroma of the 8 luma samples sx .. sx + 7 (sx even) of row sy, one plane, minus 128: nearest, or bilinear with the neighbour row
+ * nb and the window's last chroma column chi */
+__device__ __forceinline__ void tc_chroma_seg(float *out, const uint8_t *__restrict__ src, int wmb, int plane, uint32_t sx, uint32_t sy,
+                                              uint32_t ccw, bool bil, uint32_t nb, uint32_t chi)
+{
+    const uint32_t cx = sx >> 1;
+    const unsigned long long row = tc_chroma8(src, wmb, plane, cx, sy >> 1, ccw);
+    if (!bil) {
+#pragma unroll
+        for (int k = 0; k < TO_SEG; k++) out[k] = (float)(uint32_t)((row >> (8 * (k >> 1))) & 255u) - 128.0f;
+        return;
+    }
+    const unsigned long long nbr = tc_chroma8(src, wmb, plane, cx, nb, ccw);
+    float v[TO_SEG / 2 + 1];
+#pragma unroll
+    for (int j = 0; j <= TO_SEG / 2; j++) {
+        v[j] = fmaf(0.25f, (float)(uint32_t)((nbr >> (8 * j)) & 255u), 0.75f * (float)(uint32_t)((row >> (8 * j)) & 255u));
+        if (j && cx + (uint32_t)j > chi) v[j] = v[j - 1];          /* right edge of the window (only column chi + 1 is read by a valid pixel) */
+    }
+#pragma unroll
+    for (int k = 0; k < TO_SEG; k++) out[k] = ((k & 1) ? 0.5f * (v[k >> 1] + v[(k >> 1) + 1]) : v[k >> 1]) - 128.0f;
+}
+
+/* No resize: k_tensor_out's shape — a wavefront covers 64 output columns x 16 rows in two passes of 8 rows, a lane 8 adjacent pixels of
+ * one row (one 8-byte luma load when the window starts on a multiple of 8 columns, two otherwise), 16-byte stores.  Chroma: 2 word loads
+ * per plane and row when the window starts on a multiple of 8 columns, 3 otherwise; bilinear loads the neighbour row as well. */
+template <int DT, int LAYOUT, int C>
+__global__ __launch_bounds__(256) void k_tensor_colour(ColourArgs a)
+{
+    constexpr int NC = tc_nc<C>();
+    typedef typename ToElem<DT>::T E;
+    const ColourItem it = a.items[blockIdx.y];
+    const TensorItem &t = it.t;
+    const uint32_t W = a.width, H = a.height, cw = t.wmb * 16u;
+    const int wmb = (int)t.wmb;
+    const bool bil = a.chroma == TC_BILINEAR;
+    const uint32_t chi = (t.x0 + t.w) / 2u - 1u, rlo = t.y0 / 2u, rhi = (t.y0 + t.h) / 2u - 1u;      /* the window's chroma */
+    const uint32_t nux = (W + 63u) / 64u, units = nux * ((H + 15u) / 16u);
+    const uint32_t lane = threadIdx.x & 63u, wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint32_t seg = lane & 7u, r = lane >> 3;
+    const bool vec = (W % TO_SEG) == 0 && (reinterpret_cast<uintptr_t>(t.dst) & 15u) == 0;
+    const size_t plane = (size_t)W * H;
+    E *dst = reinterpret_cast<E *>(t.dst);
+    for (uint32_t u = blockIdx.x * 4u + wave; u < units; u += gridDim.x * 4u) {
+        const uint32_t ox = (u % nux) * 64u + seg * TO_SEG;
+#pragma unroll
+        for (int pass = 0; pass < 2; pass++) {
+            const uint32_t oy = (u / nux) * 16u + pass * 8u + r;
+            if (ox >= W || oy >= H) continue;
+            const uint32_t valid = min((uint32_t)TO_SEG, W - ox);
+            const uint32_t sx = t.x0 + ox, sy = t.y0 + oy;
+            const uint32_t sxa = sx & ~7u, ls = (sx & 7u) * 8u;
+            unsigned long long yv = *reinterpret_cast<const unsigned long long *>(t.src + luma_at(wmb, (int)sxa, (int)sy));
+            if (ls) {
+                const unsigned long long hi = sxa + 8u < cw ? *reinterpret_cast<const unsigned long long *>(t.src + luma_at(wmb, (int)sxa + 8, (int)sy)) : 0ull;
+                yv = (yv >> ls) | (hi << (64u - ls));
+            }
+            float cb[TO_SEG], cr[TO_SEG];
+            if constexpr (NC == 3) {
+                const uint32_t cy = sy >> 1, nb = (sy & 1u) ? min(cy + 1u, rhi) : max(cy, rlo + 1u) - 1u;
+                tc_chroma_seg(cb, t.src, wmb, 0, sx, sy, cw >> 1, bil, nb, chi);
+                tc_chroma_seg(cr, t.src, wmb, 1, sx, sy, cw >> 1, bil, nb, chi);
+            }
+            E v[TO_SEG * C];
+#pragma unroll
+            for (int k = 0; k < TO_SEG; k++) {
+                const float y = (float)(uint32_t)((yv >> (8 * k)) & 255u);
+#pragma unroll
+                for (int c = 0; c < C; c++) {
+                    E e;
+                    if (c == 3) e = tc_alpha<DT>();
+                    else if constexpr (NC == 1) e = tc_enc<DT>(__builtin_amdgcn_fmed3f(fmaf(it.k[0][0], y, it.k[0][3]), it.lo[0], it.hi[0]));
+                    else e = tc_enc<DT>(tc_value(it, c, y, cb[k], cr[k]));
+                    v[LAYOUT == TO_NCHW ? c * TO_SEG + k : k * C + c] = e;
+                }
+            }
+            if constexpr (LAYOUT == TO_NCHW) {
+#pragma unroll
+                for (int c = 0; c < C; c++) to_store<E, TO_SEG>(dst + c * plane + (size_t)oy * W + ox, v + c * TO_SEG, valid, vec);
+            } else {
+                to_store<E, TO_SEG * C>(dst + ((size_t)oy * W + ox) * C, v, valid * C, vec);
+            }
+        }
+    }
+}
+
+constexpr int TCR_COLS = 64, TCR_ROWS = 8;      /* output tile of one workgroup and step in k_tensor_colour_resize */
+
+/* torch's bilinear source coordinate (align_corners=False): max((o + 0.5) * scale - 0.5, 0), rounded after every operation (no
+ * contraction: the test model rounds the same way), its integer part i and the weight l of i + 1 */
+__device__ __forceinline__ void tcr_coord(uint32_t o, float scale, int &i, float &l)
+{
+#pragma clang fp contract(off)
+    const float f = fmaxf(((float)o + 0.5f) * scale - 0.5f, 0.0f);
+    i = (int)f;
+    l = f - (float)i;
+}
+
+/* the colour of source pixel (x, y) of the window (absolute coordinates), into p[0 .. NC) */
+template <int NC>
+__device__ __forceinline__ void tcr_convert(float *p, const ColourItem &it, int wmb, bool bil, uint32_t x, uint32_t y,
+                                            uint32_t chi, uint32_t rlo, uint32_t rhi)
+{
+    const uint8_t *__restrict__ src = it.t.src;
+    const float Y = (float)src[luma_at(wmb, (int)x, (int)y)];
+    if constexpr (NC == 1) {
+        p[0] = __builtin_amdgcn_fmed3f(fmaf(it.k[0][0], Y, it.k[0][3]), it.lo[0], it.hi[0]);
+    } else {
+        const uint32_t c0 = x >> 1, r0 = y >> 1;
+        float cc[2];
+        if (!bil) {
+#pragma unroll
+            for (int q = 0; q < 2; q++) cc[q] = (float)src[chroma_at(wmb, q, (int)c0, (int)r0)];
+        } else {
+            const uint32_t c1 = min(c0 + (x & 1u), chi), r1 = (y & 1u) ? min(r0 + 1u, rhi) : max(r0, rlo + 1u) - 1u;
+#pragma unroll
+            for (int q = 0; q < 2; q++) {
+                const float a0 = (float)src[chroma_at(wmb, q, (int)c0, (int)r0)], a1 = (float)src[chroma_at(wmb, q, (int)c1, (int)r0)];
+                const float b0 = (float)src[chroma_at(wmb, q, (int)c0, (int)r1)], b1 = (float)src[chroma_at(wmb, q, (int)c1, (int)r1)];
+                cc[q] = fmaf(0.25f, 0.5f * (b0 + b1), 0.75f * (0.5f * (a0 + a1)));
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < 3; c++) p[c] = tc_value(it, c, Y, cc[0] - 128.0f, cc[1] - 128.0f);
+    }
+}
+
+/* Resize.  A workgroup takes an output tile of 64 columns x 8 rows at a time.  Phase 1: the tile's 8 x 2 source rows (y0, y1 of each
+ * output row) times its 64 x 2 source columns (x0, x1 of each output column) are converted, one source pixel per slot and lane, 8 per
+ * lane, into LDS; the loads of the 2048 slots are independent of each other.  Phase 2: each lane interpolates 2 output pixels from LDS
+ * as a + l (b - a), which keeps equal neighbours exact (U8 rounds exact halves to even, as the model does), and stores them.  Slots are not shared between neighbouring output rows or columns: when upscaling, a
+ * source pixel may be converted once per slot that names it. */
+template <int DT, int LAYOUT, int C>
+__global__ __launch_bounds__(256) void k_tensor_colour_resize(ColourArgs a)
+{
+    constexpr int NC = tc_nc<C>();
+    typedef typename ToElem<DT>::T E;
+    __shared__ float lds[2 * TCR_ROWS][2 * TCR_COLS][NC];
+    const ColourItem it = a.items[blockIdx.y];
+    const TensorItem &t = it.t;
+    const uint32_t W = a.width, H = a.height;
+    const int wmb = (int)t.wmb;
+    const bool bil = a.chroma == TC_BILINEAR;
+    const uint32_t chi = (t.x0 + t.w) / 2u - 1u, rlo = t.y0 / 2u, rhi = (t.y0 + t.h) / 2u - 1u;
+    const float scale_x = (float)t.w / (float)W, scale_y = (float)t.h / (float)H;
+    const uint32_t nux = (W + TCR_COLS - 1u) / TCR_COLS, units = nux * ((H + TCR_ROWS - 1u) / TCR_ROWS);
+    const size_t plane = (size_t)W * H;
+    E *dst = reinterpret_cast<E *>(t.dst);
+    for (uint32_t u = blockIdx.x; u < units; u += gridDim.x) {
+        const uint32_t tx = (u % nux) * TCR_COLS, ty = (u / nux) * TCR_ROWS;
+#pragma unroll
+        for (int i = 0; i < 2 * TCR_ROWS * 2 * TCR_COLS / 256; i++) {
+            const uint32_t s = threadIdx.x + 256u * i, ra = s / (2 * TCR_COLS), cb = s % (2 * TCR_COLS);
+            const uint32_t ox = tx + cb / 2u, oy = ty + ra / 2u;
+            if (ox >= W || oy >= H) continue;
+            int xi, yi;
+            float lx, ly;
+            tcr_coord(ox, scale_x, xi, lx);
+            tcr_coord(oy, scale_y, yi, ly);
+            const uint32_t x = (cb & 1u) ? (uint32_t)min(xi + 1, (int)t.w - 1) : (uint32_t)xi;
+            const uint32_t y = (ra & 1u) ? (uint32_t)min(yi + 1, (int)t.h - 1) : (uint32_t)yi;
+            tcr_convert<NC>(lds[ra][cb], it, wmb, bil, t.x0 + x, t.y0 + y, chi, rlo, rhi);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < TCR_ROWS * TCR_COLS / 256; i++) {
+            const uint32_t o = threadIdx.x + 256u * i, r = o / TCR_COLS, j = o % TCR_COLS;
+            const uint32_t ox = tx + j, oy = ty + r;
+            if (ox >= W || oy >= H) continue;
+            int xi, yi;
+            float lx, ly;
+            tcr_coord(ox, scale_x, xi, lx);
+            tcr_coord(oy, scale_y, yi, ly);
+            const size_t pix = (size_t)oy * W + ox;
+#pragma unroll
+            for (int c = 0; c < C; c++) {
+                E e;
+                if (c == 3) e = tc_alpha<DT>();
+                else {
+                    const float v00 = lds[2 * r][2 * j][c], v01 = lds[2 * r][2 * j + 1][c];
+                    const float v10 = lds[2 * r + 1][2 * j][c], v11 = lds[2 * r + 1][2 * j + 1][c];
+                    const float top = fmaf(lx, v01 - v00, v00), bot = fmaf(lx, v11 - v10, v10);
+                    e = tc_enc<DT>(fmaf(ly, bot - top, top));
+                }
+                if constexpr (LAYOUT == TO_NCHW) dst[c * plane + pix] = e;
+                else dst[pix * C + c] = e;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+} // namespace h264k

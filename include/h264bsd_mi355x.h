@@ -75,7 +75,8 @@ typedef struct h264bsdmi_tensor_spec {
 } h264bsdmi_tensor_spec;
 /* Pop the next output picture of each of n distinct instances, as h264bsdNextOutputPicture() would, and write all of
  * them into spec->data with ONE kernel launch.  Colour: the integer BT.601 conversion of h264bsdNextOutputPictureRGBA, per
- * source pixel, to 8-bit R, G, B; resizing interpolates those 8-bit values in fp32.
+ * source pixel, to 8-bit R, G, B; resizing interpolates those 8-bit values in fp32 (h264bsdmiNextOutputTensorBatchColour: the
+ * stream's own colour space).
  * stream != NULL: enqueued on that hipStream_t (which must not be capturing), returns without waiting — the data are valid
  * as soon as work on that stream is, and later decoding of these instances waits for the kernel, not for the caller.
  * stream == NULL: on the library's own stream, returns when the data are there.
@@ -85,6 +86,37 @@ typedef struct h264bsdmi_tensor_spec {
  * with NCHW, U8 with mean != 0 or std != 1, a std of 0, resize == 0 with a source window other than width x height. */
 int h264bsdmiNextOutputTensorBatch(u32 n, storage_t *const *pStorage, const h264bsdmi_tensor_spec *spec, void *stream,
                                    u32 *got, u32 *picId, u32 *isIdrPic, u32 *numErrMbs);
+
+/* The colour space of a tensor pull (h264bsdmiNextOutputTensorBatchColour).  Matrices by Kr, Kb (H.264 Table E-5). */
+#define H264BSDMI_MATRIX_REFERENCE 0  /* h264bsdNextOutputPictureRGBA's integer BT.601 (the default); other fields must be 0 */
+#define H264BSDMI_MATRIX_AUTO      1  /* from the picture's SPS VUI, matrix_coefficients, as h264bsdMatrixCoefficients() reports it */
+#define H264BSDMI_MATRIX_BT601     2  /* Kr 0.299,  Kb 0.114   (matrix_coefficients 5, 6) */
+#define H264BSDMI_MATRIX_BT709     3  /* Kr 0.2126, Kb 0.0722  (1) */
+#define H264BSDMI_MATRIX_BT2020    4  /* Kr 0.2627, Kb 0.0593  (9, non-constant luminance) */
+#define H264BSDMI_MATRIX_FCC       5  /* Kr 0.30,   Kb 0.11    (4) */
+#define H264BSDMI_MATRIX_SMPTE240  6  /* Kr 0.212,  Kb 0.087   (7) */
+#define H264BSDMI_RANGE_AUTO    0     /* video_full_range_flag, as h264bsdVideoRange() reports it: limited when the VUI has no video_signal_type */
+#define H264BSDMI_RANGE_LIMITED 1
+#define H264BSDMI_RANGE_FULL    2
+#define H264BSDMI_CHROMA_NEAREST  0   /* chroma sample (x >> 1, y >> 1), as the reference */
+#define H264BSDMI_CHROMA_BILINEAR 1   /* chroma_sample_loc_type 0: co-sited with even luma columns, midway between luma rows */
+typedef struct h264bsdmi_colour_spec {
+    u32 matrix, range, chroma;
+    u32 unspecified;   /* AUTO only: the matrix (BT601..SMPTE240) used when the VUI names none, or one not listed above (0, 2, 3, 8, 10+) */
+} h264bsdmi_colour_spec;
+/* h264bsdmiNextOutputTensorBatch with a colour space.  colour == NULL or matrix == REFERENCE: exactly h264bsdmiNextOutputTensorBatch.
+ * Otherwise, per SOURCE pixel in fp32: limited range Y' = (Y - 16) / 219, Pb = (Cb - 128) / 224, Pr = (Cr - 128) / 224; full range
+ * Y' = Y / 255, Pb = (Cb - 128) / 255, Pr = (Cr - 128) / 255; with Kg = 1 - Kr - Kb, R = Y' + 2(1 - Kr) Pr, B = Y' + 2(1 - Kb) Pb,
+ * G = Y' - (2 Kb (1 - Kb) / Kg) Pb - (2 Kr (1 - Kr) / Kg) Pr, each clamped to [0, 1] (CH_Y: Y' clamped to [0, 1]).  Bilinear chroma:
+ * the chroma of luma sample (x, y) is taken at (x / 2, y / 2 - 1/4), neighbours clamped to the chroma of the source window (the
+ * cropping window when crop, as if it were the whole picture).  Resizing interpolates these values (unquantised); then float dtypes
+ * write (v - mean[c]) / std[c], U8 rint(255 v).  AUTO matrix and range are resolved per instance from the SPS the window comes
+ * from, so one call may mix colour spaces.  Refused as well, before anything is popped: a field out of range, REFERENCE with any
+ * other field non-zero, unspecified other than 0 or BT601..SMPTE240, or other than BT601..SMPTE240 with AUTO.  Everything else
+ * (stream, fence, got, errors) as h264bsdmiNextOutputTensorBatch. */
+int h264bsdmiNextOutputTensorBatchColour(u32 n, storage_t *const *pStorage, const h264bsdmi_tensor_spec *spec,
+                                         const h264bsdmi_colour_spec *colour, void *stream,
+                                         u32 *got, u32 *picId, u32 *isIdrPic, u32 *numErrMbs);
 
 /* ---- host parse pipeline at scale ----
  * h264bsdDecode() consumes one NAL unit of one stream per call; a caller that feeds hundreds of streams needs the

@@ -8,9 +8,11 @@ repetition each instance decodes one more picture and the device finishes it (h2
   (c) the same two results the old way: 256 x next_output_picture_device(FMT_RGBA, crop=True) + clone, stack, cast,
       F.interpolate (for b), normalise                                                    wall clock, synchronised (host waits inside)
 (a) is also given in GB/s (tiles read + tensor written) next to the device-to-device copy ceiling, measured here the way
-`bench.py --full` does (1 GiB copy, read + write).  Prints one JSON line.
+`bench.py --full` does (1 GiB copy, read + write).  --colour / --range / --chroma pull (a) and (b) in that colour space
+(h264bsdmiNextOutputTensorBatchColour; default: the reference conversion, h264bsdmiNextOutputTensorBatch).  Prints one JSON line.
 
-usage: tensor_out_bench.py [--streams 256] [--reps 20] [--warmup 3] [--old-reps 3]"""
+usage: tensor_out_bench.py [--streams 256] [--reps 20] [--warmup 3] [--old-reps 3] [--colour reference|auto|bt601|bt709|...]
+                           [--range auto|limited|full] [--chroma nearest|bilinear] [--no-old]"""
 import argparse
 import json
 import os
@@ -29,6 +31,10 @@ ap.add_argument("--streams", type=int, default=256)
 ap.add_argument("--reps", type=int, default=20)
 ap.add_argument("--warmup", type=int, default=3)
 ap.add_argument("--old-reps", type=int, default=3)
+ap.add_argument("--colour", default="reference", choices=sorted(h.capi.MATRICES))
+ap.add_argument("--range", default="auto", choices=sorted(h.capi.RANGES))
+ap.add_argument("--chroma", default="nearest", choices=sorted(h.capi.CHROMA))
+ap.add_argument("--no-old", action="store_true", help="skip (c) and the copy ceiling")
 args = ap.parse_args()
 
 data = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "golden", "test_1920x1080.h264"), "rb").read()
@@ -54,7 +60,7 @@ def time_pull(size, out):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         e0.record(st)
-        _, got, _, _, _ = h.pull_tensor(decs, size=size, dtype=torch.float16, mean=MEAN, std=STD, out=out, stream=st)
+        _, got, _, _, _ = h.pull_tensor(decs, size=size, dtype=torch.float16, mean=MEAN, std=STD, out=out, stream=st, **COLOUR)
         e1.record(st)
         st.synchronize()
         t1 = time.perf_counter()
@@ -99,6 +105,7 @@ def copy_ceiling_gbs():
     return 10 * 2 * src.numel() / (e0.elapsed_time(e1) * 1e-3) / 1e9
 
 
+COLOUR = {} if args.colour == "reference" else dict(colour=args.colour, colour_range=args.range, chroma=args.chroma)
 next_round()            # warm-up of the decoders (pinned staging, lanes); its pictures are dropped by the next round
 out_a = torch.empty((N, 3, 1080, 1920), dtype=torch.float16, device="cuda")
 a_ms, a_wall, a_min = time_pull(None, out_a)
@@ -107,12 +114,12 @@ out_b = torch.empty((N, 3, 224, 224), dtype=torch.float16, device="cuda")
 b_ms, b_wall, b_min = time_pull((224, 224), out_b)
 del out_b
 torch.cuda.empty_cache()
-c_a = time_old(None)
-c_b = time_old((224, 224))
-ceiling = copy_ceiling_gbs()
+c_a = time_old(None) if not args.no_old else float("nan")
+c_b = time_old((224, 224)) if not args.no_old else float("nan")
+ceiling = copy_ceiling_gbs() if not args.no_old else float("nan")
 moved = N * (8160 * 384 + 3 * 1080 * 1920 * 2)           # tiles read + tensor written (tiles of macroblock rows outside the crop included)
 a_gbs = moved / (a_ms * 1e-3) / 1e9
-print(json.dumps(dict(streams=N, reps=args.reps,
+print(json.dumps(dict(streams=N, reps=args.reps, colour=args.colour, range=args.range, chroma=args.chroma,
                       a_ms=round(a_ms, 3), a_min_ms=round(a_min, 3), a_wall_ms=round(a_wall, 3), a_gbs=round(a_gbs, 1),
                       copy_ceiling_gbs=round(ceiling, 1), a_fraction_of_copy=round(a_gbs / ceiling, 3),
                       b_ms=round(b_ms, 3), b_min_ms=round(b_min, 3), b_wall_ms=round(b_wall, 3),
