@@ -468,7 +468,7 @@ def pull_batch(decoders, frame_bytes=None):
 
 def pull_tensor(decoders, size=None, layout="NCHW", dtype=None, channels="RGB", mean=(0, 0, 0), std=(1, 1, 1), crop=True,
                 out=None, stream=None, colour="reference", colour_range="auto", chroma="nearest", unspecified="bt601"):
-    """h264bsdmiNextOutputTensorBatch: the next output picture of every decoder, written by one kernel launch into ONE dense CUDA
+    """h264bsdmiNextOutputTensorBatchColour: the next output picture of every decoder, written by one kernel launch into ONE dense CUDA
     tensor, [N, C, H, W] (layout "NCHW") or [N, H, W, C] ("NHWC"), N = len(decoders), in torch.uint8 / float16 (default) / float32.
     channels: "RGB", "BGR", "RGBA", "BGRA" (NHWC only) or "Y" (the luma samples).  Float outputs are (v / 255 - mean[c]) / std[c].
     size: (height, width) or an int for a square; None = no resize, every source window (the SPS cropping window when crop, else
@@ -476,8 +476,8 @@ def pull_tensor(decoders, size=None, layout="NCHW", dtype=None, channels="RGB", 
     out: a contiguous CUDA tensor of that shape and dtype to write into (None: allocated); decoders that have no picture leave
     their slice of it untouched.  stream: a torch.cuda.Stream (default: the current one) — the call returns without waiting,
     the tensor is valid for work on that stream (torch's legacy default stream: the call waits).
-    colour: "reference" (h264bsdmiNextOutputTensorBatch: the integer BT.601 conversion of next_output_picture(FMT_RGBA)), or
-    h264bsdmiNextOutputTensorBatchColour with "auto" (each stream's VUI matrix_coefficients; `unspecified` where it names none),
+    colour: "reference" (the integer BT.601 conversion of next_output_picture(FMT_RGBA), as h264bsdmiNextOutputTensorBatch), or
+    "auto" (each stream's VUI matrix_coefficients; `unspecified` where it names none),
     "bt601", "bt709", "bt2020", "fcc" or "smpte240"; colour_range "auto" (video_full_range_flag), "limited" or "full"; chroma
     "nearest" or "bilinear".  Float outputs are then (v - mean[c]) / std[c] of the colour v in [0, 1], U8 round(255 v).
     Returns (tensor, got, pic_ids, is_idr, num_err_mbs), lists of ints."""
@@ -518,16 +518,11 @@ def pull_tensor(decoders, size=None, layout="NCHW", dtype=None, channels="RGB", 
     VP = ctypes.c_void_p * n
     U32 = ctypes.c_uint32 * n
     got, ids, idr, nerr = U32(), U32(), U32(), U32()
-    if colour == "reference":
-        name = "h264bsdmiNextOutputTensorBatch"
-        rc = L.h264bsdmiNextOutputTensorBatch(n, VP(*[d._st for d in decoders]), ctypes.byref(spec), stream.cuda_stream, got, ids, idr, nerr)
-    else:
-        name = "h264bsdmiNextOutputTensorBatchColour"
-        cs = ColourSpec(MATRICES[colour], RANGES[colour_range], CHROMA[chroma], MATRICES[unspecified])
-        rc = L.h264bsdmiNextOutputTensorBatchColour(n, VP(*[d._st for d in decoders]), ctypes.byref(spec), ctypes.byref(cs), stream.cuda_stream,
-                                                    got, ids, idr, nerr)
+    cs = ColourSpec() if colour == "reference" else ColourSpec(MATRICES[colour], RANGES[colour_range], CHROMA[chroma], MATRICES[unspecified])
+    rc = L.h264bsdmiNextOutputTensorBatchColour(n, VP(*[d._st for d in decoders]), ctypes.byref(spec), ctypes.byref(cs), stream.cuda_stream,
+                                                got, ids, idr, nerr)
     if rc != 0:
-        raise RuntimeError(f"{name} failed ({rc})")
+        raise RuntimeError(f"h264bsdmiNextOutputTensorBatchColour failed ({rc})")
     return out, list(got), list(ids), list(idr), list(nerr)
 
 

@@ -216,23 +216,20 @@ int h264bsdmiNextOutputTensorBatch(u32 n, storage_t *const *dec, const h264bsdmi
     return h264bsdmiNextOutputTensorBatchColour(n, dec, spec, NULL, stream, got, picId, isIdrPic, numErrMbs);
 }
 
-/* colour == NULL or REFERENCE: the reference's conversion.  Otherwise AUTO matrix and range are resolved here, per instance, from the
+/* colour == NULL: REFERENCE, the reference's conversion.  Otherwise AUTO matrix and range are resolved here, per instance, from the
  * active SPS the window comes from (the conditions of h264bsdMatrixCoefficients / h264bsdVideoRange). */
 int h264bsdmiNextOutputTensorBatchColour(u32 n, storage_t *const *dec, const h264bsdmi_tensor_spec *spec,
                                          const h264bsdmi_colour_spec *colour, void *stream,
                                          u32 *got, u32 *picId, u32 *isIdrPic, u32 *numErrMbs)
 {
+    static const h264bsdmi_colour_spec reference = { H264BSDMI_MATRIX_REFERENCE, 0, 0, 0 };
     if (!dec || !spec || !got || !spec->data || !spec->width || !spec->height) return -1;
-    if (colour) {
-        if (colour->matrix > H264BSDMI_MATRIX_SMPTE240 || colour->range > H264BSDMI_RANGE_FULL || colour->chroma > H264BSDMI_CHROMA_BILINEAR)
-            return -1;
-        if (colour->unspecified && (colour->unspecified < H264BSDMI_MATRIX_BT601 || colour->unspecified > H264BSDMI_MATRIX_SMPTE240)) return -1;
-        if (colour->matrix == H264BSDMI_MATRIX_AUTO && !colour->unspecified) return -1;
-        if (colour->matrix == H264BSDMI_MATRIX_REFERENCE) {
-            if (colour->range || colour->chroma || colour->unspecified) return -1;
-            colour = NULL;
-        }
-    }
+    if (!colour) colour = &reference;
+    if (colour->matrix > H264BSDMI_MATRIX_SMPTE240 || colour->range > H264BSDMI_RANGE_FULL || colour->chroma > H264BSDMI_CHROMA_BILINEAR)
+        return -1;
+    if (colour->unspecified && (colour->unspecified < H264BSDMI_MATRIX_BT601 || colour->unspecified > H264BSDMI_MATRIX_SMPTE240)) return -1;
+    if (colour->matrix == H264BSDMI_MATRIX_AUTO && !colour->unspecified) return -1;
+    if (colour->matrix == H264BSDMI_MATRIX_REFERENCE && (colour->range || colour->chroma || colour->unspecified)) return -1;
     if (spec->layout > H264BSDMI_LAYOUT_NHWC || spec->dtype > H264BSDMI_DTYPE_F32 || spec->channels > H264BSDMI_CH_Y) return -1;
     if (spec->layout == H264BSDMI_LAYOUT_NCHW && (spec->channels == H264BSDMI_CH_RGBA || spec->channels == H264BSDMI_CH_BGRA)) return -1;
     for (int c = 0; c < 3; c++) {
@@ -260,14 +257,12 @@ int h264bsdmiNextOutputTensorBatchColour(u32 n, storage_t *const *dec, const h26
             h -= 2 * (sps->crop_top + sps->crop_bottom);
         }
         if (!spec->resize && (w != spec->width || h != spec->height)) { rc = -1; break; }
-        u32 matrix = 0, range = 0;
-        if (colour) {
-            matrix = colour->matrix == H264BSDMI_MATRIX_AUTO ? matrix_of(sps_matrix_coefficients(sps), colour->unspecified) : colour->matrix;
-            range = colour->range != H264BSDMI_RANGE_AUTO ? colour->range : sps_full_range(sps) ? H264BSDMI_RANGE_FULL : H264BSDMI_RANGE_LIMITED;
-        }
+        u32 matrix = colour->matrix, range = colour->range;
+        if (matrix == H264BSDMI_MATRIX_AUTO) matrix = matrix_of(sps_matrix_coefficients(sps), colour->unspecified);
+        if (matrix != H264BSDMI_MATRIX_REFERENCE && range == H264BSDMI_RANGE_AUTO) range = sps_full_range(sps) ? H264BSDMI_RANGE_FULL : H264BSDMI_RANGE_LIMITED;
         pics[m++] = (SinkTensorPic){ &a->hd->sink, d->out[d->out_idx].slot, i, x0, y0, w, h, matrix, range };
     }
-    if (!rc && m && pics[0].sink->tensor_out(m, pics, spec, colour, stream)) rc = -2;
+    if (!rc && m && pics[0].sink->tensor_out(m, pics, spec, colour->chroma, stream)) rc = -2;
     free(pics);
     if (rc) return rc;
     for (u32 i = 0; i < n; i++) {

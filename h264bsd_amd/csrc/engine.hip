@@ -32,7 +32,6 @@
 #include <algorithm>
 #include "kernels.hip.h"
 #include "kernels/k_tensor_out.hip.h"
-#include "kernels/k_tensor_colour.hip.h"
 #include "engine.h"
 #include "hip_owned.h"
 #include "../../include/h264bsd_mi355x_bench.h"
@@ -160,9 +159,8 @@ struct Engine {
     uint32_t error_events = 0;                 /* how often a tripwire fired, ever: monotonic, so that a NEW occurrence of a bit that is
                                                   already set is visible (per-decoder copy-elision guard, the tests' delta) */
     DeviceMem<unsigned long long> tail_prof;   /* debug: per-wave cycle accounting of the per-picture kernels (block 0) */
-    /* tensor pulls (tensor_out_locked): items (TensorItem, or ColourItem with a colour spec) staged in pinned memory, two halves of
-     * titem_cap ColourItems used in turn, each guarded by the event recorded behind the launch that read it; fence events that no
-     * instance holds any more */
+    /* tensor pulls (tensor_out_locked): TensorItems staged in pinned memory, two halves of titem_cap items used in turn, each guarded
+     * by the event recorded behind the launch that read it; fence events that no instance holds any more */
     Pinned<uint8_t> h_titems; size_t titem_cap = 0;
     Event titem_ev[2]; bool titem_used[2] = { false, false }; int titem_flip = 0;
     std::vector<Fence *> fences;
@@ -1063,73 +1061,57 @@ void sink_close(void *user)
     delete u;
 }
 
-/* ---- the next pictures of many instances into one caller-owned tensor (h264bsdmiNextOutputTensorBatch) ---- */
-template <int DT, int L, int CH> static const void *tensor_kernel_of(bool resize)
+/* ---- the next pictures of many instances into one caller-owned tensor (h264bsdmiNextOutputTensorBatch[Colour]) ---- */
+/* one kernel per dtype, layout, number of channels and REF; the channel order and the whole colour transform are in the items
+ * (colour_item) */
+template <int DT, int L, int C> static const void *tensor_kernel_of(bool resize, bool ref)
 {
-    return resize ? reinterpret_cast<const void *>(&h264k::k_tensor_resize<DT, L, CH>) : reinterpret_cast<const void *>(&h264k::k_tensor_out<DT, L, CH>);
+    if (ref) return resize ? reinterpret_cast<const void *>(&h264k::k_tensor_resize<DT, L, C, true>) : reinterpret_cast<const void *>(&h264k::k_tensor_out<DT, L, C, true>);
+    return resize ? reinterpret_cast<const void *>(&h264k::k_tensor_resize<DT, L, C, false>) : reinterpret_cast<const void *>(&h264k::k_tensor_out<DT, L, C, false>);
 }
-template <int DT, int L> static const void *tensor_kernel_ch(bool resize, uint32_t ch)
-{
-    switch (ch) {
-    case h264k::TO_RGB: return tensor_kernel_of<DT, L, h264k::TO_RGB>(resize);
-    case h264k::TO_BGR: return tensor_kernel_of<DT, L, h264k::TO_BGR>(resize);
-    case h264k::TO_Y: return tensor_kernel_of<DT, L, h264k::TO_Y>(resize);
-    }
-    if constexpr (L == h264k::TO_NHWC) {           /* four channels: interleaved only */
-        if (ch == h264k::TO_RGBA) return tensor_kernel_of<DT, L, h264k::TO_RGBA>(resize);
-        if (ch == h264k::TO_BGRA) return tensor_kernel_of<DT, L, h264k::TO_BGRA>(resize);
-    }
-    return nullptr;
-}
-template <int DT> static const void *tensor_kernel_layout(bool resize, uint32_t layout, uint32_t ch)
-{
-    if (layout == h264k::TO_NCHW) return tensor_kernel_ch<DT, h264k::TO_NCHW>(resize, ch);
-    if (layout == h264k::TO_NHWC) return tensor_kernel_ch<DT, h264k::TO_NHWC>(resize, ch);
-    return nullptr;
-}
-static const void *tensor_kernel(const h264bsdmi_tensor_spec &t)
-{
-    switch (t.dtype) {
-    case h264k::TO_U8: return tensor_kernel_layout<h264k::TO_U8>(t.resize != 0, t.layout, t.channels);
-    case h264k::TO_F16: return tensor_kernel_layout<h264k::TO_F16>(t.resize != 0, t.layout, t.channels);
-    case h264k::TO_F32: return tensor_kernel_layout<h264k::TO_F32>(t.resize != 0, t.layout, t.channels);
-    }
-    return nullptr;
-}
-
-/* with a colour spec (h264bsdmiNextOutputTensorBatchColour): one kernel per dtype, layout and number of channels; the channel order
- * and the whole colour transform are in the items (colour_item) */
-template <int DT, int L, int C> static const void *colour_kernel_of(bool resize)
-{
-    return resize ? reinterpret_cast<const void *>(&h264k::k_tensor_colour_resize<DT, L, C>) : reinterpret_cast<const void *>(&h264k::k_tensor_colour<DT, L, C>);
-}
-template <int DT> static const void *colour_kernel_dt(bool resize, uint32_t layout, uint32_t ch)
+template <int DT> static const void *tensor_kernel_dt(bool resize, bool ref, uint32_t layout, uint32_t ch)
 {
     const int C = ch == h264k::TO_Y ? 1 : ch >= h264k::TO_RGBA ? 4 : 3;
     if (layout == h264k::TO_NCHW) {
-        if (C == 1) return colour_kernel_of<DT, h264k::TO_NCHW, 1>(resize);
-        if (C == 3) return colour_kernel_of<DT, h264k::TO_NCHW, 3>(resize);
+        if (C == 1) return tensor_kernel_of<DT, h264k::TO_NCHW, 1>(resize, ref);
+        if (C == 3) return tensor_kernel_of<DT, h264k::TO_NCHW, 3>(resize, ref);
     } else if (layout == h264k::TO_NHWC) {
-        if (C == 1) return colour_kernel_of<DT, h264k::TO_NHWC, 1>(resize);
-        if (C == 3) return colour_kernel_of<DT, h264k::TO_NHWC, 3>(resize);
-        return colour_kernel_of<DT, h264k::TO_NHWC, 4>(resize);
+        if (C == 1) return tensor_kernel_of<DT, h264k::TO_NHWC, 1>(resize, ref);
+        if (C == 3) return tensor_kernel_of<DT, h264k::TO_NHWC, 3>(resize, ref);
+        return tensor_kernel_of<DT, h264k::TO_NHWC, 4>(resize, ref);
     }
     return nullptr;
 }
-static const void *colour_kernel(const h264bsdmi_tensor_spec &t)
+static const void *tensor_kernel(const h264bsdmi_tensor_spec &t, bool ref)
 {
     switch (t.dtype) {
-    case h264k::TO_U8: return colour_kernel_dt<h264k::TO_U8>(t.resize != 0, t.layout, t.channels);
-    case h264k::TO_F16: return colour_kernel_dt<h264k::TO_F16>(t.resize != 0, t.layout, t.channels);
-    case h264k::TO_F32: return colour_kernel_dt<h264k::TO_F32>(t.resize != 0, t.layout, t.channels);
+    case h264k::TO_U8: return tensor_kernel_dt<h264k::TO_U8>(t.resize != 0, ref, t.layout, t.channels);
+    case h264k::TO_F16: return tensor_kernel_dt<h264k::TO_F16>(t.resize != 0, ref, t.layout, t.channels);
+    case h264k::TO_F32: return tensor_kernel_dt<h264k::TO_F32>(t.resize != 0, ref, t.layout, t.channels);
     }
     return nullptr;
 }
 
-/* The item of one picture in colour space (matrix, range): per output channel c the affine map of the 8-bit (Y, Cb - 128, Cr - 128)
- * to the value written, and the clamp bounds of [0, 1] under the output scale (U8: 255 v; floats: (v - mean[c]) / std[c]), folded in double. */
-static h264k::ColourItem colour_item(const h264k::TensorItem &ti, const h264bsdmi_tensor_spec &t, uint32_t matrix, uint32_t range)
+/* The colour map of one picture's item (matrix, range): per output channel c the affine map of the 8-bit (Y, Cb - 128, Cr - 128) to
+ * the value written, and the clamp bounds of [0, 1] under the output scale (U8: 255 v; floats: (v - mean[c]) / std[c]), folded in
+ * double.  H264BSDMI_MATRIX_REFERENCE: the reference's integer BT.601, (298 (Y - 16) + 409 (Cr - 128) + 128) >> 8 and its relatives
+ * clamped to 0..255, on the 255 scale whatever the dtype: coefficients / 256, offset (128 - 16 * 298) / 256, bounds [0, 255].  Every
+ * partial sum of the kernel's FMA chain is then a multiple of 1/256 below 2^10, so the chain is exact, and the clamped value truncated
+ * is the reference's arithmetic shift.  bgr: the channel order for k_tensor_out, which uses yuv_pixel instead. */
+static void colour_item(h264k::TensorItem &it, const h264bsdmi_tensor_spec &t, uint32_t matrix, uint32_t range)
 {
+    const bool bgr = t.channels == h264k::TO_BGR || t.channels == h264k::TO_BGRA;
+    if (matrix == H264BSDMI_MATRIX_REFERENCE) {
+        static const float R[3][3] = { { 298, 0, 409 }, { 298, -100, -208 }, { 298, 516, 0 } };     /* R, G, B of (Y, Cb, Cr) */
+        for (int c = 0; c < 3; c++) {
+            for (int j = 0; j < 3; j++) it.k[c][j] = t.channels == h264k::TO_Y ? (j == 0 ? 1.0f : 0.0f) : R[bgr ? 2 - c : c][j] / 256.0f;
+            it.k[c][3] = t.channels == h264k::TO_Y ? 0.0f : (128.0f - 16.0f * 298.0f) / 256.0f;
+            it.lo[c] = 0.0f;
+            it.hi[c] = 255.0f;
+        }
+        it.bgr = bgr;
+        return;
+    }
     static const double K[][2] = { { 0.299, 0.114 }, { 0.2126, 0.0722 }, { 0.2627, 0.0593 }, { 0.30, 0.11 }, { 0.212, 0.087 } };  /* Kr, Kb */
     const double kr = K[matrix - H264BSDMI_MATRIX_BT601][0], kb = K[matrix - H264BSDMI_MATRIX_BT601][1], kg = 1.0 - kr - kb;
     const bool full = range == H264BSDMI_RANGE_FULL;
@@ -1137,37 +1119,36 @@ static h264k::ColourItem colour_item(const h264k::TensorItem &ti, const h264bsdm
     const double sc = full ? 1.0 / 255 : 1.0 / 224;                                      /* Pb = sc (Cb - 128), Pr = sc (Cr - 128) */
     const double rgb[3][3] = { { 1, 0, 2 * (1 - kr) }, { 1, -2 * kb * (1 - kb) / kg, -2 * kr * (1 - kr) / kg }, { 1, 2 * (1 - kb), 0 } };
     const double luma[3] = { 1, 0, 0 };
-    const bool bgr = t.channels == h264k::TO_BGR || t.channels == h264k::TO_BGRA;
-    h264k::ColourItem ci;
-    ci.t = ti;
     for (int c = 0; c < 3; c++) {
         const double *m = t.channels == h264k::TO_Y ? luma : rgb[bgr ? 2 - c : c];         /* (Y', Pb, Pr) -> the value of output channel c */
         const double scale = t.dtype == h264k::TO_U8 ? 255.0 : 1.0 / t.std[c], shift = t.dtype == h264k::TO_U8 ? 0.0 : -t.mean[c] / (double)t.std[c];
-        ci.k[c][0] = (float)(m[0] * sy * scale);
-        ci.k[c][1] = (float)(m[1] * sc * scale);
-        ci.k[c][2] = (float)(m[2] * sc * scale);
-        ci.k[c][3] = (float)(m[0] * oy * scale + shift);
+        it.k[c][0] = (float)(m[0] * sy * scale);
+        it.k[c][1] = (float)(m[1] * sc * scale);
+        it.k[c][2] = (float)(m[2] * sc * scale);
+        it.k[c][3] = (float)(m[0] * oy * scale + shift);
         const double lo = shift, hi = scale + shift;
-        ci.lo[c] = (float)std::min(lo, hi);
-        ci.hi[c] = (float)std::max(lo, hi);
+        it.lo[c] = (float)std::min(lo, hi);
+        it.hi[c] = (float)std::max(lo, hi);
     }
-    return ci;
 }
 
 /* Under the engine's mutex.  Ordering without host waits: the instances' queued jobs are enqueued once for the batch, the output
  * stream waits for each picture's producing tick (deduplicated per lane launch, as lane_launch does), ONE launch lays out every
  * picture, and a fence recorded behind it is handed to every instance: lane_launch makes an instance's next tick wait for it, and
  * the frame buffers are not cleared or freed before it has passed (fence_drop).  *fence_ev: the fence's event. */
-static int tensor_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, const h264bsdmi_tensor_spec &t,
-                             const h264bsdmi_colour_spec *colour, hipStream_t st, hipEvent_t *fence_ev)
+static int tensor_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, const h264bsdmi_tensor_spec &t, uint32_t chroma,
+                             hipStream_t st, hipEvent_t *fence_ev)
 {
-    const void *fn = colour ? colour_kernel(t) : tensor_kernel(t);
+    const bool ref = pics[0].matrix == H264BSDMI_MATRIX_REFERENCE;      /* one kernel: every picture of the call, or none */
+    const void *fn = tensor_kernel(t, ref);
     if (!fn) return -1;
     for (uint32_t i = 0; i < n; i++) {
         const StreamCtx *s = static_cast<SinkUser *>(pics[i].sink->user)->s;
         const SinkTensorPic &p = pics[i];
         if (p.slot >= s->n_slots || !s->d_frames || !p.w || !p.h || p.x0 + p.w > s->wmb * 16 || p.y0 + p.h > s->hmb * 16) return -1;
-        if (colour && (p.matrix < H264BSDMI_MATRIX_BT601 || p.matrix > H264BSDMI_MATRIX_SMPTE240 || ((p.x0 | p.y0 | p.w | p.h) & 1u))) return -1;
+        if ((p.matrix == H264BSDMI_MATRIX_REFERENCE) != ref || (!ref && (p.matrix < H264BSDMI_MATRIX_BT601 || p.matrix > H264BSDMI_MATRIX_SMPTE240)))
+            return -1;
+        if ((p.x0 | p.y0 | p.w | p.h) & 1u) return -1;
     }
     bool mine = false;
     for (uint32_t i = 0; i < n && !mine; i++) {
@@ -1181,26 +1162,24 @@ static int tensor_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, c
             if (e->titem_used[k]) HIP_TRY(hipEventSynchronize(e->titem_ev[k]));
         e->titem_cap = 0;
         const size_t cap = std::max<size_t>(n, 256);
-        HIP_TRY(e->h_titems.alloc(2 * cap * sizeof(h264k::ColourItem), true));
+        HIP_TRY(e->h_titems.alloc(2 * cap * sizeof(h264k::TensorItem), true));
         for (int k = 0; k < 2; k++)
             if (!e->titem_ev[k]) HIP_TRY(e->titem_ev[k].create(hipEventDisableTiming));
         e->titem_cap = cap; e->titem_used[0] = e->titem_used[1] = false; e->titem_flip = 0;
     }
     const int f = e->titem_flip;
     if (e->titem_used[f]) HIP_TRY(hipEventSynchronize(e->titem_ev[f]));      /* the launch before the last one read this half */
-    const size_t half = (size_t)f * e->titem_cap * sizeof(h264k::ColourItem);
+    const size_t half = (size_t)f * e->titem_cap * sizeof(h264k::TensorItem);
     h264k::TensorItem *items = reinterpret_cast<h264k::TensorItem *>(e->h_titems + half);
-    h264k::ColourItem *citems = reinterpret_cast<h264k::ColourItem *>(e->h_titems + half);
     const size_t C = t.channels == h264k::TO_Y ? 1 : t.channels >= h264k::TO_RGBA ? 4 : 3;
     const size_t pic_bytes = C * t.width * t.height * (t.dtype == h264k::TO_U8 ? 1 : t.dtype == h264k::TO_F16 ? 2 : 4);
     std::vector<std::pair<int, unsigned long long>> waited;
     for (uint32_t i = 0; i < n; i++) {
         const StreamCtx *s = static_cast<SinkUser *>(pics[i].sink->user)->s;
         const SinkTensorPic &p = pics[i];
-        const h264k::TensorItem ti{ s->d_frames + (size_t)p.slot * s->frame_bytes, static_cast<uint8_t *>(t.data) + p.index * pic_bytes,
-                                    s->wmb, p.x0, p.y0, p.w, p.h, 0u };
-        if (colour) citems[i] = colour_item(ti, t, p.matrix, p.range);
-        else items[i] = ti;
+        items[i] = h264k::TensorItem{ s->d_frames + (size_t)p.slot * s->frame_bytes, static_cast<uint8_t *>(t.data) + p.index * pic_bytes,
+                                      s->wmb, p.x0, p.y0, p.w, p.h, 0u };
+        colour_item(items[i], t, p.matrix, p.range);
         if (s->last_lane >= 0) {
             const std::pair<int, unsigned long long> key(s->last_lane, s->last_launch);
             if (std::find(waited.begin(), waited.end(), key) == waited.end()) {
@@ -1210,16 +1189,12 @@ static int tensor_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, c
             }
         }
     }
-    h264k::TensorArgs ta;
-    ta.items = reinterpret_cast<const h264k::TensorItem *>(e->h_titems.dev() + half);
-    ta.width = t.width; ta.height = t.height;
-    for (int c = 0; c < 3; c++) { ta.mean[c] = t.mean[c]; ta.std[c] = t.std[c]; }
-    h264k::ColourArgs ca{ reinterpret_cast<const h264k::ColourItem *>(e->h_titems.dev() + half), t.width, t.height, colour ? colour->chroma : 0u };
-    uint32_t blocks = t.resize ? (t.width * t.height + 255u) / 256u : ((t.width + 63u) / 64u * ((t.height + 15u) / 16u) + 3u) / 4u;
-    if (colour && t.resize)
-        blocks = (t.width + h264k::TCR_COLS - 1u) / h264k::TCR_COLS * ((t.height + h264k::TCR_ROWS - 1u) / h264k::TCR_ROWS);
-    void *args[] = { &ta }, *cargs[] = { &ca };
-    HIP_TRY(hipLaunchKernel(fn, dim3(std::min(blocks, 1024u), n), dim3(256), colour ? cargs : args, 0, st));
+    h264k::TensorArgs ta{ reinterpret_cast<const h264k::TensorItem *>(e->h_titems.dev() + half), t.width, t.height, chroma,
+                          { t.mean[0], t.mean[1], t.mean[2] }, { t.std[0], t.std[1], t.std[2] } };
+    const uint32_t blocks = t.resize ? (t.width + h264k::TCR_COLS - 1u) / h264k::TCR_COLS * ((t.height + h264k::TCR_ROWS - 1u) / h264k::TCR_ROWS)
+                                     : ((t.width + 63u) / 64u * ((t.height + 15u) / 16u) + 3u) / 4u;
+    void *args[] = { &ta };
+    HIP_TRY(hipLaunchKernel(fn, dim3(std::min(blocks, 1024u), n), dim3(256), args, 0, st));
     HIP_TRY(hipEventRecord(e->titem_ev[f], st));
     e->titem_used[f] = true; e->titem_flip ^= 1;
     hipLaunchKernelGGL(k_err_words, dim3(1), dim3(64), 0, st, e->d_err, e->h_err.dev());
@@ -1240,8 +1215,8 @@ static int tensor_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, c
     return 0;
 }
 
-/* JobSink.tensor_out (h264bsdmiNextOutputTensorBatch) */
-int sink_tensor_out(uint32_t n, const SinkTensorPic *pics, const h264bsdmi_tensor_spec *spec, const h264bsdmi_colour_spec *colour, void *stream)
+/* JobSink.tensor_out (h264bsdmiNextOutputTensorBatch[Colour]) */
+int sink_tensor_out(uint32_t n, const SinkTensorPic *pics, const h264bsdmi_tensor_spec *spec, uint32_t chroma, void *stream)
 {
     if (!n) return 0;
     if (!pics || !spec) return -1;
@@ -1258,7 +1233,7 @@ int sink_tensor_out(uint32_t n, const SinkTensorPic *pics, const h264bsdmi_tenso
             HIP_TRY(hipStreamIsCapturing(st, &cs));
             if (cs != hipStreamCaptureStatusNone) return -1;                      /* graph capture of this call is not supported */
         }
-        if (tensor_out_locked(e, n, pics, *spec, colour, st, &fence_ev)) return -1;
+        if (tensor_out_locked(e, n, pics, *spec, chroma, st, &fence_ev)) return -1;
     }
     if (stream) return 0;
     if (hipEventSynchronize(fence_ev) != hipSuccess) return -1;        /* (a later call may have recorded it again: that only waits longer) */
