@@ -28,7 +28,7 @@ EXPORTED_SYMBOLS = [
     "h264bsdCroppingParams", "h264bsdSampleAspectRatio", "h264bsdCheckValidParamSets", "h264bsdFlushBuffer",
     "h264bsdProfile", "h264bsdAlloc", "h264bsdFree", "h264bsdConvertToRGBA", "h264bsdConvertToBGRA",
     "h264bsdConvertToYCbCrA",
-    "h264bsdmiInitCapture", "h264bsdmiNextOutputInfo", "h264bsdmiNextOutputPictureDevice", "h264bsdmiNextOutputTensorBatch", "h264bsdmiNextOutputTensorBatchColour", "h264bsdmiJobFinalize", "h264bsdmiDeviceCount", "h264bsdmiSetDevice", "h264bsdmiFlush", "h264bsdmiFlushAsync", "h264bsdmiDeviceErrors",
+    "h264bsdmiInitCapture", "h264bsdmiNextOutputInfo", "h264bsdmiNextOutputPictureDevice", "h264bsdmiNextOutputTensorBatch", "h264bsdmiNextOutputTensorBatchColour", "h264bsdmiNextOutputTensorBatchResize", "h264bsdmiJobFinalize", "h264bsdmiDeviceCount", "h264bsdmiSetDevice", "h264bsdmiFlush", "h264bsdmiFlushAsync", "h264bsdmiDeviceErrors",
     "h264bsdmiDecodePicture", "h264bsdmiDecodePictureBatch", "h264bsdmiNextOutputPictureBatch", "h264bsdmiPullAndDecodePictureBatch", "h264bsdmiSetParserThreads", "h264bsdmiSetInputReadOnly", "h264bsdmiSetCopyElision",
     "h264bsdmiReplayCreate", "h264bsdmiReplayCreateStaggered", "h264bsdmiReplayCreateDesync", "h264bsdmiReplayCreateSched", "h264bsdmiReplayReschedule", "h264bsdmiReplayDestroy", "h264bsdmiReplayRun", "h264bsdmiReplaySync",
     "h264bsdmiReplayFetch", "h264bsdmiReplayChecksums", "h264bsdmiReplayConvert", "h264bsdmiReplayFetchConverted",
@@ -57,9 +57,16 @@ class ColourSpec(ctypes.Structure):
     _fields_ = [("matrix", ctypes.c_uint32), ("range", ctypes.c_uint32), ("chroma", ctypes.c_uint32), ("unspecified", ctypes.c_uint32)]
 
 
+class ResizeSpec(ctypes.Structure):
+    """h264bsdmi_resize_spec (include/h264bsd_mi355x.h)"""
+    _fields_ = [("filter", ctypes.c_uint32), ("fit", ctypes.c_uint32), ("pad", ctypes.c_float * 3)]
+
+
 MATRICES = {"reference": 0, "auto": 1, "bt601": 2, "bt709": 3, "bt2020": 4, "fcc": 5, "smpte240": 6}    # H264BSDMI_MATRIX_*
 RANGES = {"auto": 0, "limited": 1, "full": 2}                                                          # H264BSDMI_RANGE_*
 CHROMA = {"nearest": 0, "bilinear": 1}                                                                 # H264BSDMI_CHROMA_*
+FILTERS = {("bilinear", False): 0, ("bilinear", True): 1, ("bicubic", True): 2}                           # H264BSDMI_FILTER_*
+FITS = {"stretch": 0, "letterbox": 1}                                                                   # H264BSDMI_FIT_*
 LAYOUTS = {"NCHW": 0, "NHWC": 1}
 CHANNELS = {"RGB": (0, 3), "BGR": (1, 3), "RGBA": (2, 4), "BGRA": (3, 4), "Y": (4, 1)}     # name -> (H264BSDMI_CH_*, channels)
 
@@ -165,6 +172,9 @@ def _declare(L, harness):
     L.h264bsdmiNextOutputTensorBatchColour.argtypes = [u32, ctypes.POINTER(vp), ctypes.POINTER(TensorSpec), ctypes.POINTER(ColourSpec), vp,
                                                        P32, P32, P32, P32]
     L.h264bsdmiNextOutputTensorBatchColour.restype = ctypes.c_int
+    L.h264bsdmiNextOutputTensorBatchResize.argtypes = [u32, ctypes.POINTER(vp), ctypes.POINTER(TensorSpec), ctypes.POINTER(ColourSpec),
+                                                       ctypes.POINTER(ResizeSpec), vp, P32, P32, P32, P32, P32]
+    L.h264bsdmiNextOutputTensorBatchResize.restype = ctypes.c_int
     L.h264bsdmiDecodePicture.argtypes = [vp, u8p, u32, u32, P32, P32]
     L.h264bsdmiDecodePicture.restype = u32
     L.h264bsdmiDecodePictureBatch.argtypes = [u32, ctypes.POINTER(vp), ctypes.POINTER(vp), P32, P32, P32, P32, P32]
@@ -467,8 +477,9 @@ def pull_batch(decoders, frame_bytes=None):
 
 
 def pull_tensor(decoders, size=None, layout="NCHW", dtype=None, channels="RGB", mean=(0, 0, 0), std=(1, 1, 1), crop=True,
-                out=None, stream=None, colour="reference", colour_range="auto", chroma="nearest", unspecified="bt601"):
-    """h264bsdmiNextOutputTensorBatchColour: the next output picture of every decoder, written by one kernel launch into ONE dense CUDA
+                out=None, stream=None, colour="reference", colour_range="auto", chroma="nearest", unspecified="bt601",
+                mode="bilinear", antialias=False, fit="stretch", pad=(0.0, 0.0, 0.0), return_boxes=False):
+    """h264bsdmiNextOutputTensorBatchResize: the next output picture of every decoder, written by one kernel launch into ONE dense CUDA
     tensor, [N, C, H, W] (layout "NCHW") or [N, H, W, C] ("NHWC"), N = len(decoders), in torch.uint8 / float16 (default) / float32.
     channels: "RGB", "BGR", "RGBA", "BGRA" (NHWC only) or "Y" (the luma samples).  Float outputs are (v / 255 - mean[c]) / std[c].
     size: (height, width) or an int for a square; None = no resize, every source window (the SPS cropping window when crop, else
@@ -480,7 +491,10 @@ def pull_tensor(decoders, size=None, layout="NCHW", dtype=None, channels="RGB", 
     "auto" (each stream's VUI matrix_coefficients; `unspecified` where it names none),
     "bt601", "bt709", "bt2020", "fcc" or "smpte240"; colour_range "auto" (video_full_range_flag), "limited" or "full"; chroma
     "nearest" or "bilinear".  Float outputs are then (v - mean[c]) / std[c] of the colour v in [0, 1], U8 round(255 v).
-    Returns (tensor, got, pic_ids, is_idr, num_err_mbs), lists of ints."""
+    mode "bilinear" or "bicubic" (antialias=True only), antialias: torch's interpolate(..., antialias=True) weights; fit "stretch" or
+    "letterbox" (aspect preserved, centred, the rest of each picture is pad[c] in [0, 1] before mean / std, per output channel); all
+    need a size.  Returns (tensor, got, pic_ids, is_idr, num_err_mbs), lists of ints; return_boxes=True appends, per decoder, the
+    (left, top, w, h) of the output rectangle its picture fills, or None where it gave no picture."""
     import torch
     if dtype is None:
         dtype = torch.float16
@@ -491,6 +505,14 @@ def pull_tensor(decoders, size=None, layout="NCHW", dtype=None, channels="RGB", 
         raise ValueError(f"pull_tensor: unsupported colour / colour_range / chroma / unspecified {colour} {colour_range} {chroma} {unspecified}")
     if colour == "reference" and (colour_range != "auto" or chroma != "nearest"):
         raise ValueError("pull_tensor: colour='reference' is the reference's conversion: colour_range and chroma do not apply")
+    if (mode, bool(antialias)) not in FILTERS or fit not in FITS:
+        raise ValueError(f"pull_tensor: unsupported mode / antialias / fit {mode} {antialias} {fit} (bicubic needs antialias=True)")
+    pad = tuple(float(p) for p in pad)
+    if len(pad) != 3 or not all(0.0 <= p <= 1.0 for p in pad):
+        raise ValueError(f"pull_tensor: pad must be three values in [0, 1], not {pad}")
+    resized = FILTERS[(mode, bool(antialias))] != 0 or fit != "stretch"
+    if resized and size is None:
+        raise ValueError("pull_tensor: antialias, bicubic and letterbox need a size")
     ch, C = CHANNELS[channels]
     n = len(decoders)
     if size is None:
@@ -517,13 +539,17 @@ def pull_tensor(decoders, size=None, layout="NCHW", dtype=None, channels="RGB", 
     L = api_lib()
     VP = ctypes.c_void_p * n
     U32 = ctypes.c_uint32 * n
-    got, ids, idr, nerr = U32(), U32(), U32(), U32()
+    got, ids, idr, nerr, box = U32(), U32(), U32(), U32(), (ctypes.c_uint32 * (4 * n))()
     cs = ColourSpec() if colour == "reference" else ColourSpec(MATRICES[colour], RANGES[colour_range], CHROMA[chroma], MATRICES[unspecified])
-    rc = L.h264bsdmiNextOutputTensorBatchColour(n, VP(*[d._st for d in decoders]), ctypes.byref(spec), ctypes.byref(cs), stream.cuda_stream,
-                                                got, ids, idr, nerr)
+    rs = ResizeSpec(FILTERS[(mode, bool(antialias))], FITS[fit], (ctypes.c_float * 3)(*pad)) if resized else None
+    rc = L.h264bsdmiNextOutputTensorBatchResize(n, VP(*[d._st for d in decoders]), ctypes.byref(spec), ctypes.byref(cs),
+                                                None if rs is None else ctypes.byref(rs), stream.cuda_stream, got, ids, idr, nerr, box)
     if rc != 0:
-        raise RuntimeError(f"h264bsdmiNextOutputTensorBatchColour failed ({rc})")
-    return out, list(got), list(ids), list(idr), list(nerr)
+        raise RuntimeError(f"h264bsdmiNextOutputTensorBatchResize failed ({rc})")
+    res = (out, list(got), list(ids), list(idr), list(nerr))
+    if return_boxes:
+        res += ([tuple(box[4 * i: 4 * i + 4]) if got[i] else None for i in range(n)],)
+    return res
 
 
 def job_header(blob):

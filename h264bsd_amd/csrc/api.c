@@ -216,14 +216,44 @@ int h264bsdmiNextOutputTensorBatch(u32 n, storage_t *const *dec, const h264bsdmi
     return h264bsdmiNextOutputTensorBatchColour(n, dec, spec, NULL, stream, got, picId, isIdrPic, numErrMbs);
 }
 
-/* colour == NULL: REFERENCE, the reference's conversion.  Otherwise AUTO matrix and range are resolved here, per instance, from the
- * active SPS the window comes from (the conditions of h264bsdMatrixCoefficients / h264bsdVideoRange). */
 int h264bsdmiNextOutputTensorBatchColour(u32 n, storage_t *const *dec, const h264bsdmi_tensor_spec *spec,
                                          const h264bsdmi_colour_spec *colour, void *stream,
                                          u32 *got, u32 *picId, u32 *isIdrPic, u32 *numErrMbs)
 {
+    return h264bsdmiNextOutputTensorBatchResize(n, dec, spec, colour, NULL, stream, got, picId, isIdrPic, numErrMbs, NULL);
+}
+
+/* The letterbox rectangle of a w x h window in a W x H output (include/h264bsd_mi355x.h), in double (the truncations are floors:
+ * every operand is positive) */
+static u32 lb_side(u32 n, double s, u32 N)
+{
+    const u32 v = (u32)(n * s + 0.5);
+    return v < 1 ? 1 : v > N ? N : v;
+}
+static void letterbox(u32 W, u32 H, u32 w, u32 h, u32 *box)
+{
+    const double sw = (double)W / w, sh = (double)H / h, s = sw < sh ? sw : sh;
+    box[2] = lb_side(w, s, W);
+    box[3] = lb_side(h, s, H);
+    box[0] = (W - box[2]) / 2;
+    box[1] = (H - box[3]) / 2;
+}
+
+/* colour == NULL: REFERENCE, the reference's conversion.  Otherwise AUTO matrix and range are resolved here, per instance, from the
+ * active SPS the window comes from (the conditions of h264bsdMatrixCoefficients / h264bsdVideoRange).  resize == NULL: stretch with
+ * resize = 1's bilinear; the engine keeps {FILTER_BILINEAR, FIT_STRETCH} on that path too. */
+int h264bsdmiNextOutputTensorBatchResize(u32 n, storage_t *const *dec, const h264bsdmi_tensor_spec *spec,
+                                         const h264bsdmi_colour_spec *colour, const h264bsdmi_resize_spec *resize,
+                                         void *stream, u32 *got, u32 *picId, u32 *isIdrPic, u32 *numErrMbs,
+                                         u32 *box)
+{
     static const h264bsdmi_colour_spec reference = { H264BSDMI_MATRIX_REFERENCE, 0, 0, 0 };
     if (!dec || !spec || !got || !spec->data || !spec->width || !spec->height) return -1;
+    if (resize) {
+        if (resize->filter > H264BSDMI_FILTER_BICUBIC_AA || resize->fit > H264BSDMI_FIT_LETTERBOX || spec->resize != 1) return -1;
+        for (int c = 0; c < 3; c++)
+            if (!(resize->pad[c] >= 0.0f && resize->pad[c] <= 1.0f)) return -1;        /* NaN and the infinities too */
+    }
     if (!colour) colour = &reference;
     if (colour->matrix > H264BSDMI_MATRIX_SMPTE240 || colour->range > H264BSDMI_RANGE_FULL || colour->chroma > H264BSDMI_CHROMA_BILINEAR)
         return -1;
@@ -260,9 +290,15 @@ int h264bsdmiNextOutputTensorBatchColour(u32 n, storage_t *const *dec, const h26
         u32 matrix = colour->matrix, range = colour->range;
         if (matrix == H264BSDMI_MATRIX_AUTO) matrix = matrix_of(sps_matrix_coefficients(sps), colour->unspecified);
         if (matrix != H264BSDMI_MATRIX_REFERENCE && range == H264BSDMI_RANGE_AUTO) range = sps_full_range(sps) ? H264BSDMI_RANGE_FULL : H264BSDMI_RANGE_LIMITED;
-        pics[m++] = (SinkTensorPic){ &a->hd->sink, d->out[d->out_idx].slot, i, x0, y0, w, h, matrix, range };
+        SinkTensorPic *p = &pics[m++];
+        *p = (SinkTensorPic){ &a->hd->sink, d->out[d->out_idx].slot, i, x0, y0, w, h, matrix, range, { 0, 0, spec->width, spec->height } };
+        if (resize && resize->fit == H264BSDMI_FIT_LETTERBOX) letterbox(spec->width, spec->height, w, h, p->box);
     }
-    if (!rc && m && pics[0].sink->tensor_out(m, pics, spec, colour->chroma, stream)) rc = -2;
+    if (!rc && m && pics[0].sink->tensor_out(m, pics, spec, colour->chroma, resize, stream)) rc = -2;
+    if (!rc && box) {
+        memset(box, 0, 4 * sizeof(u32) * n);
+        for (u32 k = 0; k < m; k++) memcpy(box + 4 * pics[k].index, pics[k].box, sizeof(pics[k].box));
+    }
     free(pics);
     if (rc) return rc;
     for (u32 i = 0; i < n; i++) {

@@ -32,6 +32,7 @@
 #include <algorithm>
 #include "kernels.hip.h"
 #include "kernels/k_tensor_out.hip.h"
+#include "kernels/k_tensor_aa.hip.h"
 #include "engine.h"
 #include "hip_owned.h"
 #include "../../include/h264bsd_mi355x_bench.h"
@@ -159,8 +160,8 @@ struct Engine {
     uint32_t error_events = 0;                 /* how often a tripwire fired, ever: monotonic, so that a NEW occurrence of a bit that is
                                                   already set is visible (per-decoder copy-elision guard, the tests' delta) */
     DeviceMem<unsigned long long> tail_prof;   /* debug: per-wave cycle accounting of the per-picture kernels (block 0) */
-    /* tensor pulls (tensor_out_locked): TensorItems staged in pinned memory, two halves of titem_cap items used in turn, each guarded
-     * by the event recorded behind the launch that read it; fence events that no instance holds any more */
+    /* tensor pulls (tensor_out_locked): TensorItems (AaItems for k_tensor_aa) staged in pinned memory, two halves of titem_cap items
+     * used in turn, each guarded by the event recorded behind the launch that read it; fence events that no instance holds any more */
     Pinned<uint8_t> h_titems; size_t titem_cap = 0;
     Event titem_ev[2]; bool titem_used[2] = { false, false }; int titem_flip = 0;
     std::vector<Fence *> fences;
@@ -1061,36 +1062,43 @@ void sink_close(void *user)
     delete u;
 }
 
-/* ---- the next pictures of many instances into one caller-owned tensor (h264bsdmiNextOutputTensorBatch[Colour]) ---- */
+/* ---- the next pictures of many instances into one caller-owned tensor (h264bsdmiNextOutputTensorBatch[Colour|Resize]) ---- */
 /* one kernel per dtype, layout, number of channels and REF; the channel order and the whole colour transform are in the items
  * (colour_item) */
-template <int DT, int L, int C> static const void *tensor_kernel_of(bool resize, bool ref)
+/* (k_tensor_aa: one more family on the same four parameters, filter and fit at run time) */
+enum { TK_OUT, TK_RESIZE, TK_AA };
+template <int DT, int L, int C> static const void *tensor_kernel_of(int kind, bool ref)
 {
+    if (kind == TK_AA) return ref ? reinterpret_cast<const void *>(&h264k::k_tensor_aa<DT, L, C, true>) : reinterpret_cast<const void *>(&h264k::k_tensor_aa<DT, L, C, false>);
+    const bool resize = kind == TK_RESIZE;
     if (ref) return resize ? reinterpret_cast<const void *>(&h264k::k_tensor_resize<DT, L, C, true>) : reinterpret_cast<const void *>(&h264k::k_tensor_out<DT, L, C, true>);
     return resize ? reinterpret_cast<const void *>(&h264k::k_tensor_resize<DT, L, C, false>) : reinterpret_cast<const void *>(&h264k::k_tensor_out<DT, L, C, false>);
 }
-template <int DT> static const void *tensor_kernel_dt(bool resize, bool ref, uint32_t layout, uint32_t ch)
+template <int DT> static const void *tensor_kernel_dt(int kind, bool ref, uint32_t layout, uint32_t ch)
 {
     const int C = ch == h264k::TO_Y ? 1 : ch >= h264k::TO_RGBA ? 4 : 3;
     if (layout == h264k::TO_NCHW) {
-        if (C == 1) return tensor_kernel_of<DT, h264k::TO_NCHW, 1>(resize, ref);
-        if (C == 3) return tensor_kernel_of<DT, h264k::TO_NCHW, 3>(resize, ref);
+        if (C == 1) return tensor_kernel_of<DT, h264k::TO_NCHW, 1>(kind, ref);
+        if (C == 3) return tensor_kernel_of<DT, h264k::TO_NCHW, 3>(kind, ref);
     } else if (layout == h264k::TO_NHWC) {
-        if (C == 1) return tensor_kernel_of<DT, h264k::TO_NHWC, 1>(resize, ref);
-        if (C == 3) return tensor_kernel_of<DT, h264k::TO_NHWC, 3>(resize, ref);
-        return tensor_kernel_of<DT, h264k::TO_NHWC, 4>(resize, ref);
+        if (C == 1) return tensor_kernel_of<DT, h264k::TO_NHWC, 1>(kind, ref);
+        if (C == 3) return tensor_kernel_of<DT, h264k::TO_NHWC, 3>(kind, ref);
+        return tensor_kernel_of<DT, h264k::TO_NHWC, 4>(kind, ref);
     }
     return nullptr;
 }
-static const void *tensor_kernel(const h264bsdmi_tensor_spec &t, bool ref)
+static const void *tensor_kernel(const h264bsdmi_tensor_spec &t, bool aa, bool ref)
 {
+    const int kind = aa ? TK_AA : t.resize ? TK_RESIZE : TK_OUT;
     switch (t.dtype) {
-    case h264k::TO_U8: return tensor_kernel_dt<h264k::TO_U8>(t.resize != 0, ref, t.layout, t.channels);
-    case h264k::TO_F16: return tensor_kernel_dt<h264k::TO_F16>(t.resize != 0, ref, t.layout, t.channels);
-    case h264k::TO_F32: return tensor_kernel_dt<h264k::TO_F32>(t.resize != 0, ref, t.layout, t.channels);
+    case h264k::TO_U8: return tensor_kernel_dt<h264k::TO_U8>(kind, ref, t.layout, t.channels);
+    case h264k::TO_F16: return tensor_kernel_dt<h264k::TO_F16>(kind, ref, t.layout, t.channels);
+    case h264k::TO_F32: return tensor_kernel_dt<h264k::TO_F32>(kind, ref, t.layout, t.channels);
     }
     return nullptr;
 }
+/* the staging ring's item stride: k_tensor_out / k_tensor_resize read TensorItems, k_tensor_aa AaItems */
+constexpr size_t TITEM_BYTES = std::max(sizeof(h264k::TensorItem), sizeof(h264k::AaItem));
 
 /* The colour map of one picture's item (matrix, range): per output channel c the affine map of the 8-bit (Y, Cb - 128, Cr - 128) to
  * the value written, and the clamp bounds of [0, 1] under the output scale (U8: 255 v; floats: (v - mean[c]) / std[c]), folded in
@@ -1137,10 +1145,13 @@ static void colour_item(h264k::TensorItem &it, const h264bsdmi_tensor_spec &t, u
  * picture, and a fence recorded behind it is handed to every instance: lane_launch makes an instance's next tick wait for it, and
  * the frame buffers are not cleared or freed before it has passed (fence_drop).  *fence_ev: the fence's event. */
 static int tensor_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, const h264bsdmi_tensor_spec &t, uint32_t chroma,
-                             hipStream_t st, hipEvent_t *fence_ev)
+                             const h264bsdmi_resize_spec *rs, hipStream_t st, hipEvent_t *fence_ev)
 {
     const bool ref = pics[0].matrix == H264BSDMI_MATRIX_REFERENCE;      /* one kernel: every picture of the call, or none */
-    const void *fn = tensor_kernel(t, ref);
+    /* k_tensor_aa for every filter and fit but resize = 1's own bilinear stretch, which stays on k_tensor_resize */
+    const bool aa = rs && (rs->filter != H264BSDMI_FILTER_BILINEAR || rs->fit != H264BSDMI_FIT_STRETCH);
+    if (aa && (!t.resize || rs->filter > H264BSDMI_FILTER_BICUBIC_AA || rs->fit > H264BSDMI_FIT_LETTERBOX)) return -1;
+    const void *fn = tensor_kernel(t, aa, ref);
     if (!fn) return -1;
     for (uint32_t i = 0; i < n; i++) {
         const StreamCtx *s = static_cast<SinkUser *>(pics[i].sink->user)->s;
@@ -1149,6 +1160,7 @@ static int tensor_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, c
         if ((p.matrix == H264BSDMI_MATRIX_REFERENCE) != ref || (!ref && (p.matrix < H264BSDMI_MATRIX_BT601 || p.matrix > H264BSDMI_MATRIX_SMPTE240)))
             return -1;
         if ((p.x0 | p.y0 | p.w | p.h) & 1u) return -1;
+        if (aa && (!p.box[2] || !p.box[3] || p.box[0] + p.box[2] > t.width || p.box[1] + p.box[3] > t.height)) return -1;
     }
     bool mine = false;
     for (uint32_t i = 0; i < n && !mine; i++) {
@@ -1162,24 +1174,27 @@ static int tensor_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, c
             if (e->titem_used[k]) HIP_TRY(hipEventSynchronize(e->titem_ev[k]));
         e->titem_cap = 0;
         const size_t cap = std::max<size_t>(n, 256);
-        HIP_TRY(e->h_titems.alloc(2 * cap * sizeof(h264k::TensorItem), true));
+        HIP_TRY(e->h_titems.alloc(2 * cap * TITEM_BYTES, true));
         for (int k = 0; k < 2; k++)
             if (!e->titem_ev[k]) HIP_TRY(e->titem_ev[k].create(hipEventDisableTiming));
         e->titem_cap = cap; e->titem_used[0] = e->titem_used[1] = false; e->titem_flip = 0;
     }
     const int f = e->titem_flip;
     if (e->titem_used[f]) HIP_TRY(hipEventSynchronize(e->titem_ev[f]));      /* the launch before the last one read this half */
-    const size_t half = (size_t)f * e->titem_cap * sizeof(h264k::TensorItem);
+    const size_t half = (size_t)f * e->titem_cap * TITEM_BYTES;
     h264k::TensorItem *items = reinterpret_cast<h264k::TensorItem *>(e->h_titems + half);
+    h264k::AaItem *aa_items = reinterpret_cast<h264k::AaItem *>(e->h_titems + half);
     const size_t C = t.channels == h264k::TO_Y ? 1 : t.channels >= h264k::TO_RGBA ? 4 : 3;
     const size_t pic_bytes = C * t.width * t.height * (t.dtype == h264k::TO_U8 ? 1 : t.dtype == h264k::TO_F16 ? 2 : 4);
     std::vector<std::pair<int, unsigned long long>> waited;
     for (uint32_t i = 0; i < n; i++) {
         const StreamCtx *s = static_cast<SinkUser *>(pics[i].sink->user)->s;
         const SinkTensorPic &p = pics[i];
-        items[i] = h264k::TensorItem{ s->d_frames + (size_t)p.slot * s->frame_bytes, static_cast<uint8_t *>(t.data) + p.index * pic_bytes,
-                                      s->wmb, p.x0, p.y0, p.w, p.h, 0u };
-        colour_item(items[i], t, p.matrix, p.range);
+        h264k::TensorItem &ti = aa ? aa_items[i].t : items[i];
+        ti = h264k::TensorItem{ s->d_frames + (size_t)p.slot * s->frame_bytes, static_cast<uint8_t *>(t.data) + p.index * pic_bytes,
+                                s->wmb, p.x0, p.y0, p.w, p.h, 0u };
+        colour_item(ti, t, p.matrix, p.range);
+        if (aa) { aa_items[i].left = p.box[0]; aa_items[i].top = p.box[1]; aa_items[i].iw = p.box[2]; aa_items[i].ih = p.box[3]; }
         if (s->last_lane >= 0) {
             const std::pair<int, unsigned long long> key(s->last_lane, s->last_launch);
             if (std::find(waited.begin(), waited.end(), key) == waited.end()) {
@@ -1191,10 +1206,21 @@ static int tensor_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, c
     }
     h264k::TensorArgs ta{ reinterpret_cast<const h264k::TensorItem *>(e->h_titems.dev() + half), t.width, t.height, chroma,
                           { t.mean[0], t.mean[1], t.mean[2] }, { t.std[0], t.std[1], t.std[2] } };
-    const uint32_t blocks = t.resize ? (t.width + h264k::TCR_COLS - 1u) / h264k::TCR_COLS * ((t.height + h264k::TCR_ROWS - 1u) / h264k::TCR_ROWS)
-                                     : ((t.width + 63u) / 64u * ((t.height + 15u) / 16u) + 3u) / 4u;
-    void *args[] = { &ta };
-    HIP_TRY(hipLaunchKernel(fn, dim3(std::min(blocks, 1024u), n), dim3(256), args, 0, st));
+    if (aa) {
+        /* the pad under the output scale, per output channel: U8 floor(255 pad + 0.5), floats (pad - mean) / std, in double */
+        h264k::AaArgs aargs{ reinterpret_cast<const h264k::AaItem *>(e->h_titems.dev() + half), t.width, t.height, chroma, rs->filter,
+                             { t.mean[0], t.mean[1], t.mean[2] }, { t.std[0], t.std[1], t.std[2] }, { 0, 0, 0 } };
+        for (int c = 0; c < 3; c++)
+            aargs.pad[c] = t.dtype == h264k::TO_U8 ? (float)std::floor(255.0 * rs->pad[c] + 0.5) : (float)(((double)rs->pad[c] - t.mean[c]) / t.std[c]);
+        const uint32_t blocks = (t.width + h264k::TAA_COLS - 1u) / h264k::TAA_COLS * ((t.height + h264k::TAA_ROWS - 1u) / h264k::TAA_ROWS);
+        void *args[] = { &aargs };
+        HIP_TRY(hipLaunchKernel(fn, dim3(std::min(blocks, 1024u), n), dim3(256), args, 0, st));
+    } else {
+        const uint32_t blocks = t.resize ? (t.width + h264k::TCR_COLS - 1u) / h264k::TCR_COLS * ((t.height + h264k::TCR_ROWS - 1u) / h264k::TCR_ROWS)
+                                         : ((t.width + 63u) / 64u * ((t.height + 15u) / 16u) + 3u) / 4u;
+        void *args[] = { &ta };
+        HIP_TRY(hipLaunchKernel(fn, dim3(std::min(blocks, 1024u), n), dim3(256), args, 0, st));
+    }
     HIP_TRY(hipEventRecord(e->titem_ev[f], st));
     e->titem_used[f] = true; e->titem_flip ^= 1;
     hipLaunchKernelGGL(k_err_words, dim3(1), dim3(64), 0, st, e->d_err, e->h_err.dev());
@@ -1215,8 +1241,9 @@ static int tensor_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, c
     return 0;
 }
 
-/* JobSink.tensor_out (h264bsdmiNextOutputTensorBatch[Colour]) */
-int sink_tensor_out(uint32_t n, const SinkTensorPic *pics, const h264bsdmi_tensor_spec *spec, uint32_t chroma, void *stream)
+/* JobSink.tensor_out (h264bsdmiNextOutputTensorBatch[Colour|Resize]) */
+int sink_tensor_out(uint32_t n, const SinkTensorPic *pics, const h264bsdmi_tensor_spec *spec, uint32_t chroma,
+                    const h264bsdmi_resize_spec *resize, void *stream)
 {
     if (!n) return 0;
     if (!pics || !spec) return -1;
@@ -1233,7 +1260,7 @@ int sink_tensor_out(uint32_t n, const SinkTensorPic *pics, const h264bsdmi_tenso
             HIP_TRY(hipStreamIsCapturing(st, &cs));
             if (cs != hipStreamCaptureStatusNone) return -1;                      /* graph capture of this call is not supported */
         }
-        if (tensor_out_locked(e, n, pics, *spec, chroma, st, &fence_ev)) return -1;
+        if (tensor_out_locked(e, n, pics, *spec, chroma, resize, st, &fence_ev)) return -1;
     }
     if (stream) return 0;
     if (hipEventSynchronize(fence_ev) != hipSuccess) return -1;        /* (a later call may have recorded it again: that only waits longer) */

@@ -217,12 +217,14 @@ typedef struct Dpb {
 
 /* ---------------------------------------------------------------- job sink (device boundary) */
 struct h264bsdmi_tensor_spec;
+struct h264bsdmi_resize_spec;
 struct JobSink;
 /* one picture of a batched tensor pull (JobSink.tensor_out): the frame buffer `slot` of the instance behind `sink`, its window
  * (x0, y0, w, h), and the picture's index in the output tensor */
 typedef struct SinkTensorPic {
     const struct JobSink *sink; uint32_t slot, index, x0, y0, w, h;
     uint32_t matrix, range;     /* H264BSDMI_MATRIX_REFERENCE (range 0), or the picture's BT601..SMPTE240 and RANGE_LIMITED / FULL */
+    uint32_t box[4];            /* the inner rectangle of the output the window fills: left, top, width, height */
 } SinkTensorPic;
 typedef struct JobSink {
     void *user;
@@ -252,10 +254,11 @@ typedef struct JobSink {
      * (copy elision, hd_job_finish) */
     uint32_t (*errors)(void *user);
     /* optional: the n pictures (distinct instances of one device, pics[i].sink) into spec->data with one launch, on `stream` (NULL: the
-     * sink's own, and wait) — h264bsdmiNextOutputTensorBatchColour.  Each picture's colour is pics[i].matrix / range (REFERENCE for all
-     * of them or none); chroma: H264BSDMI_CHROMA_* (REFERENCE: nearest).  Called through any of the n sinks.  0 = ok; <0 = error,
-     * nothing enqueued */
-    int (*tensor_out)(uint32_t n, const SinkTensorPic *pics, const struct h264bsdmi_tensor_spec *spec, uint32_t chroma, void *stream);
+     * sink's own, and wait) — h264bsdmiNextOutputTensorBatchResize.  Each picture's colour is pics[i].matrix / range (REFERENCE for all
+     * of them or none); chroma: H264BSDMI_CHROMA_* (REFERENCE: nearest); resize: the filter and pad (NULL: resize = 1's bilinear, and
+     * pics[i].box is the whole output).  Called through any of the n sinks.  0 = ok; <0 = error, nothing enqueued */
+    int (*tensor_out)(uint32_t n, const SinkTensorPic *pics, const struct h264bsdmi_tensor_spec *spec, uint32_t chroma,
+                      const struct h264bsdmi_resize_spec *resize, void *stream);
 } JobSink;
 
 /* ---------------------------------------------------------------- decoder instance */

@@ -118,6 +118,38 @@ int h264bsdmiNextOutputTensorBatchColour(u32 n, storage_t *const *pStorage, cons
                                          const h264bsdmi_colour_spec *colour, void *stream,
                                          u32 *got, u32 *picId, u32 *isIdrPic, u32 *numErrMbs);
 
+/* How a source window becomes an output rectangle (h264bsdmiNextOutputTensorBatchResize). */
+#define H264BSDMI_FILTER_BILINEAR    0  /* torch bilinear, align_corners=False, antialias=False (what resize = 1 does without a spec) */
+#define H264BSDMI_FILTER_BILINEAR_AA 1  /* torch bilinear, antialias=True (triangle filter widened by the downscale factor)            */
+#define H264BSDMI_FILTER_BICUBIC_AA  2  /* torch bicubic,  antialias=True (a = -0.5, as PIL)                                           */
+#define H264BSDMI_FIT_STRETCH   0       /* the source window fills width x height                                                     */
+#define H264BSDMI_FIT_LETTERBOX 1       /* aspect preserved, centred, the rest of the picture is pad                                  */
+typedef struct h264bsdmi_resize_spec {
+    u32   filter, fit;
+    float pad[3];                       /* letterbox border per OUTPUT channel, in [0, 1] before mean / std (CH_Y: pad[0]) */
+} h264bsdmi_resize_spec;
+/* h264bsdmiNextOutputTensorBatchColour with a resampling filter and a fit.  resize == NULL, and {FILTER_BILINEAR, FIT_STRETCH},
+ * are exactly h264bsdmiNextOutputTensorBatchColour; a non-NULL resize needs spec->resize == 1.
+ * Weights are torch's (interpolate(..., antialias=True)), with the source window as the input and the inner size as the output: for
+ * output index i, scale = in / out, center = scale (i + 0.5), support = (interp / 2) max(scale, 1) with interp 2 (bilinear) or 4
+ * (bicubic), taps xmin = max((int)(center - support + 0.5), 0) .. xmax = min((int)(center + support + 0.5), in) (exclusive), tap j
+ * weighted filter((j - center + 0.5) / max(scale, 1)) and normalised by the sum of the taps; filter 1 - |x| or Keys' cubic, a = -0.5.
+ * FILTER_BILINEAR keeps the coordinates of resize = 1 (two taps per axis) at the inner size.  What is interpolated is what resize = 1
+ * interpolates: with colour NULL / REFERENCE the reference's 8-bit R, G, B (or luma), otherwise the unquantised colour value.  Float
+ * outputs are then (v - mean[c]) / std[c], unclamped (bicubic may overshoot, as in torch); U8 is clamped to [0, 255] and rounded as
+ * resize = 1 rounds.
+ * FIT_LETTERBOX, per picture of window w x h, in double: s = min(width / w, height / h), iw = clamp(floor(w s + 0.5), 1, width), ih
+ * likewise, left = (width - iw) / 2, top = (height - ih) / 2 (integer division).  The inner iw x ih rectangle is the window resampled
+ * to that size; every other pixel is pad[c] under the output's scale (U8 floor(255 pad + 0.5), floats (pad - mean[c]) / std[c]);
+ * alpha is 255 / 1.0.  box (may be NULL): 4 u32 per instance, left, top, iw, ih; FIT_STRETCH (and resize == NULL) 0, 0, width,
+ * height; an instance with got[i] = 0 leaves its slice untouched, border included, and gets a box of zeros.
+ * Refused as well, before anything is popped: filter > 2, fit > 1, a pad that is not finite or lies outside [0, 1], and a non-NULL
+ * resize with spec->resize != 1.  Everything else (stream, fence, got, errors) as h264bsdmiNextOutputTensorBatchColour. */
+int h264bsdmiNextOutputTensorBatchResize(u32 n, storage_t *const *pStorage, const h264bsdmi_tensor_spec *spec,
+                                         const h264bsdmi_colour_spec *colour, const h264bsdmi_resize_spec *resize,
+                                         void *stream, u32 *got, u32 *picId, u32 *isIdrPic, u32 *numErrMbs,
+                                         u32 *box);
+
 /* ---- host parse pipeline at scale ----
  * h264bsdDecode() consumes one NAL unit of one stream per call; a caller that feeds hundreds of streams needs the
  * loop of posix/test_h264bsd.c:146-177 for each of them and its own threading.  These entry points move both into

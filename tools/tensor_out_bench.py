@@ -7,12 +7,16 @@ repetition each instance decodes one more picture and the device finishes it (h2
   (b) pull_tensor -> [256, 3, 224, 224] float16, resized + normalised                   (the same)
   (c) the same two results the old way: 256 x next_output_picture_device(FMT_RGBA, crop=True) + clone, stack, cast,
       F.interpolate (for b), normalise                                                    wall clock, synchronised (host waits inside)
+  (d) (b)'s result with --filter's antialiasing the old way: pull (a) unnormalised, F.interpolate(antialias=True) to 224 x 224,
+      normalise, cast                                                                   HIP events on the torch stream (no host wait)
 (a) is also given in GB/s (tiles read + tensor written) next to the device-to-device copy ceiling, measured here the way
 `bench.py --full` does (1 GiB copy, read + write).  --colour / --range / --chroma pull (a) and (b) in that colour space
-(h264bsdmiNextOutputTensorBatchColour; default: the reference conversion, h264bsdmiNextOutputTensorBatch).  Prints one JSON line.
+(h264bsdmiNextOutputTensorBatchColour; default: the reference conversion, h264bsdmiNextOutputTensorBatch).  --filter / --fit pull (b)
+with that resampling filter and fit (h264bsdmiNextOutputTensorBatchResize; default: bilinear, stretch).  Prints one JSON line.
 
 usage: tensor_out_bench.py [--streams 256] [--reps 20] [--warmup 3] [--old-reps 3] [--colour reference|auto|bt601|bt709|...]
-                           [--range auto|limited|full] [--chroma nearest|bilinear] [--no-old]"""
+                           [--range auto|limited|full] [--chroma nearest|bilinear] [--filter bilinear|bilinear_aa|bicubic_aa]
+                           [--fit stretch|letterbox] [--only-b] [--no-old]"""
 import argparse
 import json
 import os
@@ -34,12 +38,15 @@ ap.add_argument("--old-reps", type=int, default=3)
 ap.add_argument("--colour", default="reference", choices=sorted(h.capi.MATRICES))
 ap.add_argument("--range", default="auto", choices=sorted(h.capi.RANGES))
 ap.add_argument("--chroma", default="nearest", choices=sorted(h.capi.CHROMA))
-ap.add_argument("--no-old", action="store_true", help="skip (c) and the copy ceiling")
+ap.add_argument("--filter", default="bilinear", choices=["bilinear", "bilinear_aa", "bicubic_aa"])
+ap.add_argument("--fit", default="stretch", choices=sorted(h.capi.FITS))
+ap.add_argument("--only-b", action="store_true", help="time (b) and (d) only")
+ap.add_argument("--no-old", action="store_true", help="skip (c), (d) and the copy ceiling")
 args = ap.parse_args()
 
 data = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "golden", "test_1920x1080.h264"), "rb").read()
 N = args.streams
-rounds = 2 * (args.warmup + args.reps) + 2 * (1 + args.old_reps) + 2
+rounds = 2 * (args.warmup + args.reps) + 3 * (1 + args.old_reps) + 2
 decs = [h.Decoder(no_output_reordering=1) for _ in range(N)]
 drv = h.BatchDriver(decs, [data * (rounds // 73 + 2)] * N)
 L = h.api_lib()
@@ -51,7 +58,7 @@ def next_round():
     assert L.h264bsdmiFlush() == 0
 
 
-def time_pull(size, out):
+def time_pull(size, out, **resize):
     st = torch.cuda.Stream()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     ms, wall = [], []
@@ -60,7 +67,7 @@ def time_pull(size, out):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         e0.record(st)
-        _, got, _, _, _ = h.pull_tensor(decs, size=size, dtype=torch.float16, mean=MEAN, std=STD, out=out, stream=st, **COLOUR)
+        _, got, _, _, _ = h.pull_tensor(decs, size=size, dtype=torch.float16, mean=MEAN, std=STD, out=out, stream=st, **COLOUR, **resize)
         e1.record(st)
         st.synchronize()
         t1 = time.perf_counter()
@@ -92,6 +99,31 @@ def time_old(size):
     return sorted(wall[1:])[len(wall[1:]) // 2]
 
 
+def time_old_aa(size):
+    """(d): the full-size pull, unnormalised, then torch's antialiased interpolate and the normalisation on the same stream"""
+    mode, aa = FILTER[args.filter]
+    mean = torch.tensor(MEAN, device="cuda").view(1, 3, 1, 1)
+    std = torch.tensor(STD, device="cuda").view(1, 3, 1, 1)
+    full = torch.empty((N, 3, 1080, 1920), dtype=torch.float16, device="cuda")
+    st = torch.cuda.Stream()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    ms = []
+    for rep in range(1 + args.old_reps):
+        next_round()
+        torch.cuda.synchronize()
+        e0.record(st)
+        h.pull_tensor(decs, dtype=torch.float16, out=full, stream=st, **COLOUR)
+        with torch.cuda.stream(st):
+            y = ((F.interpolate(full, size=size, mode=mode, antialias=aa, align_corners=False) - mean) / std).half()
+        e1.record(st)
+        st.synchronize()
+        ms.append(e0.elapsed_time(e1))
+        del y
+    del full
+    torch.cuda.empty_cache()
+    return sorted(ms[1:])[len(ms[1:]) // 2]
+
+
 def copy_ceiling_gbs():
     src = torch.empty(1 << 30, dtype=torch.uint8, device="cuda")
     dst = torch.empty_like(src)
@@ -106,24 +138,30 @@ def copy_ceiling_gbs():
 
 
 COLOUR = {} if args.colour == "reference" else dict(colour=args.colour, colour_range=args.range, chroma=args.chroma)
+FILTER = {"bilinear": ("bilinear", False), "bilinear_aa": ("bilinear", True), "bicubic_aa": ("bicubic", True)}
+RESIZE = dict(mode=FILTER[args.filter][0], antialias=FILTER[args.filter][1], fit=args.fit)
+nan = float("nan")
 next_round()            # warm-up of the decoders (pinned staging, lanes); its pictures are dropped by the next round
-out_a = torch.empty((N, 3, 1080, 1920), dtype=torch.float16, device="cuda")
-a_ms, a_wall, a_min = time_pull(None, out_a)
-del out_a
+a_ms = a_wall = a_min = nan
+if not args.only_b:
+    out_a = torch.empty((N, 3, 1080, 1920), dtype=torch.float16, device="cuda")
+    a_ms, a_wall, a_min = time_pull(None, out_a)
+    del out_a
 out_b = torch.empty((N, 3, 224, 224), dtype=torch.float16, device="cuda")
-b_ms, b_wall, b_min = time_pull((224, 224), out_b)
+b_ms, b_wall, b_min = time_pull((224, 224), out_b, **RESIZE)
 del out_b
 torch.cuda.empty_cache()
-c_a = time_old(None) if not args.no_old else float("nan")
-c_b = time_old((224, 224)) if not args.no_old else float("nan")
-ceiling = copy_ceiling_gbs() if not args.no_old else float("nan")
+d_ms = time_old_aa((224, 224)) if not args.no_old and args.fit == "stretch" else nan
+c_a = time_old(None) if not args.no_old and not args.only_b else nan
+c_b = time_old((224, 224)) if not args.no_old and not args.only_b else nan
+ceiling = copy_ceiling_gbs() if not args.no_old and not args.only_b else nan
 moved = N * (8160 * 384 + 3 * 1080 * 1920 * 2)           # tiles read + tensor written (tiles of macroblock rows outside the crop included)
 a_gbs = moved / (a_ms * 1e-3) / 1e9
-print(json.dumps(dict(streams=N, reps=args.reps, colour=args.colour, range=args.range, chroma=args.chroma,
+print(json.dumps(dict(streams=N, reps=args.reps, colour=args.colour, range=args.range, chroma=args.chroma, filter=args.filter, fit=args.fit,
                       a_ms=round(a_ms, 3), a_min_ms=round(a_min, 3), a_wall_ms=round(a_wall, 3), a_gbs=round(a_gbs, 1),
                       copy_ceiling_gbs=round(ceiling, 1), a_fraction_of_copy=round(a_gbs / ceiling, 3),
                       b_ms=round(b_ms, 3), b_min_ms=round(b_min, 3), b_wall_ms=round(b_wall, 3),
-                      c_a_ms=round(c_a, 2), c_b_ms=round(c_b, 2),
+                      c_a_ms=round(c_a, 2), c_b_ms=round(c_b, 2), d_ms=round(d_ms, 3),
                       speedup_a=round(c_a / a_wall, 1), speedup_b=round(c_b / b_wall, 1),
                       device_errors=h.device_errors())))
 for d in decs:
