@@ -28,7 +28,7 @@ EXPORTED_SYMBOLS = [
     "h264bsdCroppingParams", "h264bsdSampleAspectRatio", "h264bsdCheckValidParamSets", "h264bsdFlushBuffer",
     "h264bsdProfile", "h264bsdAlloc", "h264bsdFree", "h264bsdConvertToRGBA", "h264bsdConvertToBGRA",
     "h264bsdConvertToYCbCrA",
-    "h264bsdmiInitCapture", "h264bsdmiNextOutputInfo", "h264bsdmiNextOutputPictureDevice", "h264bsdmiNextOutputTensorBatch", "h264bsdmiNextOutputTensorBatchColour", "h264bsdmiNextOutputTensorBatchResize", "h264bsdmiJobFinalize", "h264bsdmiDeviceCount", "h264bsdmiSetDevice", "h264bsdmiFlush", "h264bsdmiFlushAsync", "h264bsdmiDeviceErrors",
+    "h264bsdmiInitCapture", "h264bsdmiNextOutputInfo", "h264bsdmiNextOutputPictureDevice", "h264bsdmiNextOutputTensorBatch", "h264bsdmiNextOutputTensorBatchColour", "h264bsdmiNextOutputTensorBatchResize", "h264bsdmiOutputTensorRegions", "h264bsdmiJobFinalize", "h264bsdmiDeviceCount", "h264bsdmiSetDevice", "h264bsdmiFlush", "h264bsdmiFlushAsync", "h264bsdmiDeviceErrors",
     "h264bsdmiDecodePicture", "h264bsdmiDecodePictureBatch", "h264bsdmiNextOutputPictureBatch", "h264bsdmiPullAndDecodePictureBatch", "h264bsdmiSetParserThreads", "h264bsdmiSetInputReadOnly", "h264bsdmiSetCopyElision",
     "h264bsdmiReplayCreate", "h264bsdmiReplayCreateStaggered", "h264bsdmiReplayCreateDesync", "h264bsdmiReplayCreateSched", "h264bsdmiReplayReschedule", "h264bsdmiReplayDestroy", "h264bsdmiReplayRun", "h264bsdmiReplaySync",
     "h264bsdmiReplayFetch", "h264bsdmiReplayChecksums", "h264bsdmiReplayConvert", "h264bsdmiReplayFetchConverted",
@@ -60,6 +60,11 @@ class ColourSpec(ctypes.Structure):
 class ResizeSpec(ctypes.Structure):
     """h264bsdmi_resize_spec (include/h264bsd_mi355x.h)"""
     _fields_ = [("filter", ctypes.c_uint32), ("fit", ctypes.c_uint32), ("pad", ctypes.c_float * 3)]
+
+
+class Region(ctypes.Structure):
+    """h264bsdmi_region (include/h264bsd_mi355x.h)"""
+    _fields_ = [("instance", ctypes.c_uint32), ("x", ctypes.c_int), ("y", ctypes.c_int), ("w", ctypes.c_uint32), ("h", ctypes.c_uint32)]
 
 
 MATRICES = {"reference": 0, "auto": 1, "bt601": 2, "bt709": 3, "bt2020": 4, "fcc": 5, "smpte240": 6}    # H264BSDMI_MATRIX_*
@@ -175,6 +180,9 @@ def _declare(L, harness):
     L.h264bsdmiNextOutputTensorBatchResize.argtypes = [u32, ctypes.POINTER(vp), ctypes.POINTER(TensorSpec), ctypes.POINTER(ColourSpec),
                                                        ctypes.POINTER(ResizeSpec), vp, P32, P32, P32, P32, P32]
     L.h264bsdmiNextOutputTensorBatchResize.restype = ctypes.c_int
+    L.h264bsdmiOutputTensorRegions.argtypes = [u32, ctypes.POINTER(vp), u32, ctypes.POINTER(Region), ctypes.POINTER(TensorSpec),
+                                               ctypes.POINTER(ColourSpec), ctypes.POINTER(ResizeSpec), vp, P32, P32, P32, P32]
+    L.h264bsdmiOutputTensorRegions.restype = ctypes.c_int
     L.h264bsdmiDecodePicture.argtypes = [vp, u8p, u32, u32, P32, P32]
     L.h264bsdmiDecodePicture.restype = u32
     L.h264bsdmiDecodePictureBatch.argtypes = [u32, ctypes.POINTER(vp), ctypes.POINTER(vp), P32, P32, P32, P32, P32]
@@ -476,6 +484,55 @@ def pull_batch(decoders, frame_bytes=None):
     return views, list(ids)
 
 
+def _tensor_call(who, n, decoders, size, layout, dtype, channels, mean, std, crop, out, stream, colour, colour_range, chroma, unspecified,
+                 mode, antialias, fit, pad):
+    """the argument checks, the output tensor of n slices, the stream handling and the three specs that pull_tensor and pull_regions
+    share; returns (out, spec, colour spec, resize spec or None, stream)"""
+    import torch
+    if dtype is None:
+        dtype = torch.float16
+    dtypes = {torch.uint8: 0, torch.float16: 1, torch.float32: 2}
+    if dtype not in dtypes or layout not in LAYOUTS or channels not in CHANNELS:
+        raise ValueError(f"{who}: unsupported dtype / layout / channels {dtype} {layout} {channels}")
+    if colour not in MATRICES or colour_range not in RANGES or chroma not in CHROMA or unspecified not in MATRICES or MATRICES[unspecified] < 2:
+        raise ValueError(f"{who}: unsupported colour / colour_range / chroma / unspecified {colour} {colour_range} {chroma} {unspecified}")
+    if colour == "reference" and (colour_range != "auto" or chroma != "nearest"):
+        raise ValueError(f"{who}: colour='reference' is the reference's conversion: colour_range and chroma do not apply")
+    if (mode, bool(antialias)) not in FILTERS or fit not in FITS:
+        raise ValueError(f"{who}: unsupported mode / antialias / fit {mode} {antialias} {fit} (bicubic needs antialias=True)")
+    pad = tuple(float(p) for p in pad)
+    if len(pad) != 3 or not all(0.0 <= p <= 1.0 for p in pad):
+        raise ValueError(f"{who}: pad must be three values in [0, 1], not {pad}")
+    resized = FILTERS[(mode, bool(antialias))] != 0 or fit != "stretch"
+    if resized and size is None:
+        raise ValueError(f"{who}: antialias, bicubic and letterbox need a size")
+    ch, C = CHANNELS[channels]
+    if size is None:
+        geo = next((d for d in decoders if d.pic_width()), None)
+        if geo is None:
+            raise ValueError(f"{who}: size=None needs a decoder that has seen a sequence parameter set")
+        flag, _, cw, _, chh = geo.cropping_params()
+        H, W = (chh, cw) if crop and flag else (16 * geo.pic_height(), 16 * geo.pic_width())
+    else:
+        H, W = (size, size) if isinstance(size, int) else (int(size[0]), int(size[1]))
+    shape = (n, C, H, W) if layout == "NCHW" else (n, H, W, C)
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device="cuda")
+    elif not out.is_cuda or out.dtype != dtype or tuple(out.shape) != shape or not out.is_contiguous():
+        raise ValueError(f"{who}: out must be a contiguous CUDA {dtype} tensor of shape {shape}")
+    if stream is None:
+        stream = torch.cuda.current_stream(out.device)
+    if not stream.cuda_stream:
+        # torch's legacy default stream is handle 0, which the C call reads as "the library's own stream, wait": that stream is not
+        # ordered behind torch's work, so what is queued for `out` must be done before the call
+        stream.synchronize()
+    spec = TensorSpec(out.data_ptr(), W, H, LAYOUTS[layout], dtypes[dtype], ch, 1 if crop else 0, 0 if size is None else 1,
+                      (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std))
+    cs = ColourSpec() if colour == "reference" else ColourSpec(MATRICES[colour], RANGES[colour_range], CHROMA[chroma], MATRICES[unspecified])
+    rs = ResizeSpec(FILTERS[(mode, bool(antialias))], FITS[fit], (ctypes.c_float * 3)(*pad)) if resized else None
+    return out, spec, cs, rs, stream
+
+
 def pull_tensor(decoders, size=None, layout="NCHW", dtype=None, channels="RGB", mean=(0, 0, 0), std=(1, 1, 1), crop=True,
                 out=None, stream=None, colour="reference", colour_range="auto", chroma="nearest", unspecified="bt601",
                 mode="bilinear", antialias=False, fit="stretch", pad=(0.0, 0.0, 0.0), return_boxes=False):
@@ -495,53 +552,13 @@ def pull_tensor(decoders, size=None, layout="NCHW", dtype=None, channels="RGB", 
     "letterbox" (aspect preserved, centred, the rest of each picture is pad[c] in [0, 1] before mean / std, per output channel); all
     need a size.  Returns (tensor, got, pic_ids, is_idr, num_err_mbs), lists of ints; return_boxes=True appends, per decoder, the
     (left, top, w, h) of the output rectangle its picture fills, or None where it gave no picture."""
-    import torch
-    if dtype is None:
-        dtype = torch.float16
-    dtypes = {torch.uint8: 0, torch.float16: 1, torch.float32: 2}
-    if dtype not in dtypes or layout not in LAYOUTS or channels not in CHANNELS:
-        raise ValueError(f"pull_tensor: unsupported dtype / layout / channels {dtype} {layout} {channels}")
-    if colour not in MATRICES or colour_range not in RANGES or chroma not in CHROMA or unspecified not in MATRICES or MATRICES[unspecified] < 2:
-        raise ValueError(f"pull_tensor: unsupported colour / colour_range / chroma / unspecified {colour} {colour_range} {chroma} {unspecified}")
-    if colour == "reference" and (colour_range != "auto" or chroma != "nearest"):
-        raise ValueError("pull_tensor: colour='reference' is the reference's conversion: colour_range and chroma do not apply")
-    if (mode, bool(antialias)) not in FILTERS or fit not in FITS:
-        raise ValueError(f"pull_tensor: unsupported mode / antialias / fit {mode} {antialias} {fit} (bicubic needs antialias=True)")
-    pad = tuple(float(p) for p in pad)
-    if len(pad) != 3 or not all(0.0 <= p <= 1.0 for p in pad):
-        raise ValueError(f"pull_tensor: pad must be three values in [0, 1], not {pad}")
-    resized = FILTERS[(mode, bool(antialias))] != 0 or fit != "stretch"
-    if resized and size is None:
-        raise ValueError("pull_tensor: antialias, bicubic and letterbox need a size")
-    ch, C = CHANNELS[channels]
     n = len(decoders)
-    if size is None:
-        geo = next((d for d in decoders if d.pic_width()), None)
-        if geo is None:
-            raise ValueError("pull_tensor: size=None needs a decoder that has seen a sequence parameter set")
-        flag, _, cw, _, chh = geo.cropping_params()
-        H, W = (chh, cw) if crop and flag else (16 * geo.pic_height(), 16 * geo.pic_width())
-    else:
-        H, W = (size, size) if isinstance(size, int) else (int(size[0]), int(size[1]))
-    shape = (n, C, H, W) if layout == "NCHW" else (n, H, W, C)
-    if out is None:
-        out = torch.empty(shape, dtype=dtype, device="cuda")
-    elif not out.is_cuda or out.dtype != dtype or tuple(out.shape) != shape or not out.is_contiguous():
-        raise ValueError(f"pull_tensor: out must be a contiguous CUDA {dtype} tensor of shape {shape}")
-    if stream is None:
-        stream = torch.cuda.current_stream(out.device)
-    if not stream.cuda_stream:
-        # torch's legacy default stream is handle 0, which the C call reads as "the library's own stream, wait": that stream is not
-        # ordered behind torch's work, so what is queued for `out` must be done before the call
-        stream.synchronize()
-    spec = TensorSpec(out.data_ptr(), W, H, LAYOUTS[layout], dtypes[dtype], ch, 1 if crop else 0, 0 if size is None else 1,
-                      (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std))
+    out, spec, cs, rs, stream = _tensor_call("pull_tensor", n, decoders, size, layout, dtype, channels, mean, std, crop, out, stream, colour,
+                                             colour_range, chroma, unspecified, mode, antialias, fit, pad)
     L = api_lib()
     VP = ctypes.c_void_p * n
     U32 = ctypes.c_uint32 * n
     got, ids, idr, nerr, box = U32(), U32(), U32(), U32(), (ctypes.c_uint32 * (4 * n))()
-    cs = ColourSpec() if colour == "reference" else ColourSpec(MATRICES[colour], RANGES[colour_range], CHROMA[chroma], MATRICES[unspecified])
-    rs = ResizeSpec(FILTERS[(mode, bool(antialias))], FITS[fit], (ctypes.c_float * 3)(*pad)) if resized else None
     rc = L.h264bsdmiNextOutputTensorBatchResize(n, VP(*[d._st for d in decoders]), ctypes.byref(spec), ctypes.byref(cs),
                                                 None if rs is None else ctypes.byref(rs), stream.cuda_stream, got, ids, idr, nerr, box)
     if rc != 0:
@@ -550,6 +567,48 @@ def pull_tensor(decoders, size=None, layout="NCHW", dtype=None, channels="RGB", 
     if return_boxes:
         res += ([tuple(box[4 * i: 4 * i + 4]) if got[i] else None for i in range(n)],)
     return res
+
+
+def pull_regions(decoders, regions, size, layout="NCHW", dtype=None, channels="RGB", mean=(0, 0, 0), std=(1, 1, 1), crop=True,
+                 out=None, stream=None, colour="reference", colour_range="auto", chroma="nearest", unspecified="bt601",
+                 mode="bilinear", antialias=False, fit="stretch", pad=(0.0, 0.0, 0.0)):
+    """h264bsdmiOutputTensorRegions: boxes of the decoders' CURRENT pictures (the picture each popped last, by any output call, valid
+    until that decoder decodes again), resized by one kernel launch into ONE dense CUDA tensor [K, C, H, W] or [K, H, W, C], K =
+    len(regions).  regions: a sequence of (decoder_index, x, y, w, h), host integers: the box in luma samples relative to the
+    decoder's source window (the SPS cropping window when crop, else the coded frame); it may start at a negative or odd position
+    and reach beyond the window, where it reads pad.  Nothing is popped: the call may be repeated on the same pictures.  size (an
+    int or (height, width)) is required; every other argument as pull_tensor, with each box in the place of the source window
+    (fit="letterbox" keeps the BOX's aspect).  Returns (tensor, got, boxes, current, pic_ids): got[k] = 1 when region k was written
+    (0: its decoder has no current picture, its slice is untouched), boxes[k] the (left, top, w, h) of the output rectangle it
+    fills or None, current[i] / pic_ids[i] per decoder."""
+    if size is None:
+        raise ValueError("pull_regions: a size is required")
+    regs = []
+    n = len(decoders)
+    for r in regions:
+        r = tuple(r)
+        if len(r) != 5 or not all(isinstance(v, int) for v in r):
+            raise ValueError(f"pull_regions: a region is (decoder_index, x, y, w, h) in host integers, not {r}")
+        i, x, y, w, h = r
+        if not 0 <= i < n or not 1 <= w <= 16384 or not 1 <= h <= 16384 or abs(x) > 16384 or abs(y) > 16384:
+            raise ValueError(f"pull_regions: region {r} names no decoder of the call or is out of range (1 <= w, h <= 16384, |x|, |y| <= 16384)")
+        regs.append(Region(i, x, y, w, h))
+    K = len(regs)
+    if K > 65535:
+        raise ValueError("pull_regions: at most 65535 regions per call")
+    out, spec, cs, rs, stream = _tensor_call("pull_regions", K, decoders, size, layout, dtype, channels, mean, std, crop, out, stream, colour,
+                                             colour_range, chroma, unspecified, mode, antialias, fit, pad)
+    if rs is None:          # bilinear stretch: still a spec of its own here, the pad is what a box reads outside the picture
+        rs = ResizeSpec(FILTERS[("bilinear", False)], FITS["stretch"], (ctypes.c_float * 3)(*[float(p) for p in pad]))
+    L = api_lib()
+    got, box = (ctypes.c_uint32 * max(K, 1))(), (ctypes.c_uint32 * (4 * max(K, 1)))()
+    cur, ids = (ctypes.c_uint32 * max(n, 1))(), (ctypes.c_uint32 * max(n, 1))()
+    rc = L.h264bsdmiOutputTensorRegions(n, (ctypes.c_void_p * max(n, 1))(*[d._st for d in decoders]), K, (Region * max(K, 1))(*regs),
+                                        ctypes.byref(spec), ctypes.byref(cs), None if rs is None else ctypes.byref(rs),
+                                        stream.cuda_stream, got, box, cur, ids)
+    if rc != 0:
+        raise RuntimeError(f"h264bsdmiOutputTensorRegions failed ({rc})")
+    return (out, list(got)[:K], [tuple(box[4 * k: 4 * k + 4]) if got[k] else None for k in range(K)], list(cur)[:n], list(ids)[:n])
 
 
 def job_header(blob):

@@ -27,6 +27,10 @@ typedef struct ApiDec {
     HostDec *hd;
     h264bsdmi_job_cb cb;
     void *cb_user;
+    /* the current picture: the one popped last (pop_output), until the instance decodes again or is flushed (drop_current) —
+     * what h264bsdmiOutputTensorRegions samples.  A copy: the output queue is rewritten by the decode calls only, but so is this. */
+    OutPic cur;
+    int has_cur;
 } ApiDec;
 
 /* Every H264BSDMI_* variable this library reads (tests/test_abi.py compares the list with the sources and INTEGRATION.md).  A
@@ -48,6 +52,7 @@ __attribute__((constructor)) static void report_unknown_switches(void)
 }
 
 static ApiDec *dec_of(storage_t *s) { return s ? (ApiDec *)s->opaque : NULL; }
+static void drop_current(ApiDec *a) { if (a) a->has_cur = 0; }
 
 /* ---- capture sink ---- */
 static int cap_configure(void *u, uint32_t w, uint32_t h, uint32_t n) { (void)u; (void)w; (void)h; (void)n; return 0; }
@@ -109,6 +114,7 @@ void h264bsdFree(storage_t *s) { free(s); }
 u32 h264bsdDecode(storage_t *s, u8 *byteStrm, u32 len, u32 picId, u32 *readBytes)
 {
     ApiDec *a = dec_of(s);
+    drop_current(a);
     if (!a || !byteStrm || !len || !readBytes) return H264BSD_ERROR;
     return (u32)hd_decode(a->hd, byteStrm, len, picId, readBytes);
 }
@@ -117,6 +123,8 @@ static const OutPic *pop_output(ApiDec *a, u32 *picId, u32 *isIdrPic, u32 *numEr
 {
     const OutPic *o = hd_dpb_next_output(&a->hd->dpb);
     if (!o) return NULL;
+    a->cur = *o;
+    a->has_cur = 1;
     if (picId) *picId = o->pic_id;
     if (isIdrPic) *isIdrPic = o->is_idr;
     if (numErrMbs) *numErrMbs = o->num_err_mbs;
@@ -239,6 +247,50 @@ static void letterbox(u32 W, u32 H, u32 w, u32 h, u32 *box)
     box[1] = (H - box[3]) / 2;
 }
 
+/* What every tensor pull refuses in its three specs (1 = refused).  *colour == NULL becomes REFERENCE, the reference's conversion. */
+static int tensor_specs_refused(const h264bsdmi_tensor_spec *spec, const h264bsdmi_colour_spec **pcolour, const h264bsdmi_resize_spec *resize)
+{
+    static const h264bsdmi_colour_spec reference = { H264BSDMI_MATRIX_REFERENCE, 0, 0, 0 };
+    if (!spec || !spec->data || !spec->width || !spec->height) return 1;
+    if (resize) {
+        if (resize->filter > H264BSDMI_FILTER_BICUBIC_AA || resize->fit > H264BSDMI_FIT_LETTERBOX || spec->resize != 1) return 1;
+        for (int c = 0; c < 3; c++)
+            if (!(resize->pad[c] >= 0.0f && resize->pad[c] <= 1.0f)) return 1;        /* NaN and the infinities too */
+    }
+    if (!*pcolour) *pcolour = &reference;
+    const h264bsdmi_colour_spec *colour = *pcolour;
+    if (colour->matrix > H264BSDMI_MATRIX_SMPTE240 || colour->range > H264BSDMI_RANGE_FULL || colour->chroma > H264BSDMI_CHROMA_BILINEAR)
+        return 1;
+    if (colour->unspecified && (colour->unspecified < H264BSDMI_MATRIX_BT601 || colour->unspecified > H264BSDMI_MATRIX_SMPTE240)) return 1;
+    if (colour->matrix == H264BSDMI_MATRIX_AUTO && !colour->unspecified) return 1;
+    if (colour->matrix == H264BSDMI_MATRIX_REFERENCE && (colour->range || colour->chroma || colour->unspecified)) return 1;
+    if (spec->layout > H264BSDMI_LAYOUT_NHWC || spec->dtype > H264BSDMI_DTYPE_F32 || spec->channels > H264BSDMI_CH_Y) return 1;
+    if (spec->layout == H264BSDMI_LAYOUT_NCHW && (spec->channels == H264BSDMI_CH_RGBA || spec->channels == H264BSDMI_CH_BGRA)) return 1;
+    for (int c = 0; c < 3; c++) {
+        if (spec->std[c] == 0.0f) return 1;
+        if (spec->dtype == H264BSDMI_DTYPE_U8 && (spec->mean[c] != 0.0f || spec->std[c] != 1.0f)) return 1;
+    }
+    return 0;
+}
+
+/* The picture in frame buffer `slot` of instance a (which has an active SPS) as slice `index` of a tensor pull: its source window,
+ * AUTO matrix and range resolved from the SPS the window comes from; the box is the whole output */
+static void tensor_pic(SinkTensorPic *p, const ApiDec *a, u32 slot, u32 index, const h264bsdmi_tensor_spec *spec, const h264bsdmi_colour_spec *colour)
+{
+    const Sps *sps = a->hd->active_sps;
+    u32 x0 = 0, y0 = 0, w = 16 * sps->width_mbs, h = 16 * sps->height_mbs;
+    if (spec->crop && sps->cropping) {
+        x0 = 2 * sps->crop_left;
+        y0 = 2 * sps->crop_top;
+        w -= 2 * (sps->crop_left + sps->crop_right);
+        h -= 2 * (sps->crop_top + sps->crop_bottom);
+    }
+    u32 matrix = colour->matrix, range = colour->range;
+    if (matrix == H264BSDMI_MATRIX_AUTO) matrix = matrix_of(sps_matrix_coefficients(sps), colour->unspecified);
+    if (matrix != H264BSDMI_MATRIX_REFERENCE && range == H264BSDMI_RANGE_AUTO) range = sps_full_range(sps) ? H264BSDMI_RANGE_FULL : H264BSDMI_RANGE_LIMITED;
+    *p = (SinkTensorPic){ &a->hd->sink, slot, index, x0, y0, w, h, matrix, range, { 0, 0, spec->width, spec->height } };
+}
+
 /* colour == NULL: REFERENCE, the reference's conversion.  Otherwise AUTO matrix and range are resolved here, per instance, from the
  * active SPS the window comes from (the conditions of h264bsdMatrixCoefficients / h264bsdVideoRange).  resize == NULL: stretch with
  * resize = 1's bilinear; the engine keeps {FILTER_BILINEAR, FIT_STRETCH} on that path too. */
@@ -247,25 +299,7 @@ int h264bsdmiNextOutputTensorBatchResize(u32 n, storage_t *const *dec, const h26
                                          void *stream, u32 *got, u32 *picId, u32 *isIdrPic, u32 *numErrMbs,
                                          u32 *box)
 {
-    static const h264bsdmi_colour_spec reference = { H264BSDMI_MATRIX_REFERENCE, 0, 0, 0 };
-    if (!dec || !spec || !got || !spec->data || !spec->width || !spec->height) return -1;
-    if (resize) {
-        if (resize->filter > H264BSDMI_FILTER_BICUBIC_AA || resize->fit > H264BSDMI_FIT_LETTERBOX || spec->resize != 1) return -1;
-        for (int c = 0; c < 3; c++)
-            if (!(resize->pad[c] >= 0.0f && resize->pad[c] <= 1.0f)) return -1;        /* NaN and the infinities too */
-    }
-    if (!colour) colour = &reference;
-    if (colour->matrix > H264BSDMI_MATRIX_SMPTE240 || colour->range > H264BSDMI_RANGE_FULL || colour->chroma > H264BSDMI_CHROMA_BILINEAR)
-        return -1;
-    if (colour->unspecified && (colour->unspecified < H264BSDMI_MATRIX_BT601 || colour->unspecified > H264BSDMI_MATRIX_SMPTE240)) return -1;
-    if (colour->matrix == H264BSDMI_MATRIX_AUTO && !colour->unspecified) return -1;
-    if (colour->matrix == H264BSDMI_MATRIX_REFERENCE && (colour->range || colour->chroma || colour->unspecified)) return -1;
-    if (spec->layout > H264BSDMI_LAYOUT_NHWC || spec->dtype > H264BSDMI_DTYPE_F32 || spec->channels > H264BSDMI_CH_Y) return -1;
-    if (spec->layout == H264BSDMI_LAYOUT_NCHW && (spec->channels == H264BSDMI_CH_RGBA || spec->channels == H264BSDMI_CH_BGRA)) return -1;
-    for (int c = 0; c < 3; c++) {
-        if (spec->std[c] == 0.0f) return -1;
-        if (spec->dtype == H264BSDMI_DTYPE_U8 && (spec->mean[c] != 0.0f || spec->std[c] != 1.0f)) return -1;
-    }
+    if (!dec || !got || tensor_specs_refused(spec, &colour, resize)) return -1;
     if (!n) return 0;
     SinkTensorPic *pics = (SinkTensorPic *)malloc(n * sizeof(SinkTensorPic));
     if (!pics) return -1;
@@ -279,20 +313,10 @@ int h264bsdmiNextOutputTensorBatchResize(u32 n, storage_t *const *dec, const h26
         const Dpb *d = &a->hd->dpb;
         const Sps *sps = a->hd->active_sps;
         if (rc || !sps || d->out_idx >= d->n_out) continue;                  /* nothing to give: got[i] = 0 */
-        u32 x0 = 0, y0 = 0, w = 16 * sps->width_mbs, h = 16 * sps->height_mbs;
-        if (spec->crop && sps->cropping) {
-            x0 = 2 * sps->crop_left;
-            y0 = 2 * sps->crop_top;
-            w -= 2 * (sps->crop_left + sps->crop_right);
-            h -= 2 * (sps->crop_top + sps->crop_bottom);
-        }
-        if (!spec->resize && (w != spec->width || h != spec->height)) { rc = -1; break; }
-        u32 matrix = colour->matrix, range = colour->range;
-        if (matrix == H264BSDMI_MATRIX_AUTO) matrix = matrix_of(sps_matrix_coefficients(sps), colour->unspecified);
-        if (matrix != H264BSDMI_MATRIX_REFERENCE && range == H264BSDMI_RANGE_AUTO) range = sps_full_range(sps) ? H264BSDMI_RANGE_FULL : H264BSDMI_RANGE_LIMITED;
         SinkTensorPic *p = &pics[m++];
-        *p = (SinkTensorPic){ &a->hd->sink, d->out[d->out_idx].slot, i, x0, y0, w, h, matrix, range, { 0, 0, spec->width, spec->height } };
-        if (resize && resize->fit == H264BSDMI_FIT_LETTERBOX) letterbox(spec->width, spec->height, w, h, p->box);
+        tensor_pic(p, a, d->out[d->out_idx].slot, i, spec, colour);
+        if (!spec->resize && (p->w != spec->width || p->h != spec->height)) { rc = -1; break; }
+        if (resize && resize->fit == H264BSDMI_FIT_LETTERBOX) letterbox(spec->width, spec->height, p->w, p->h, p->box);
     }
     if (!rc && m && pics[0].sink->tensor_out(m, pics, spec, colour->chroma, resize, stream)) rc = -2;
     if (!rc && box) {
@@ -310,6 +334,72 @@ int h264bsdmiNextOutputTensorBatchResize(u32 n, storage_t *const *dec, const h26
         if (numErrMbs) numErrMbs[i] = nerr;
     }
     return 0;
+}
+
+/* Boxes of the instances' current pictures (pop_output, drop_current), each into its own slice.  Specs and regions are checked
+ * before the instances are looked at; nothing is popped. */
+int h264bsdmiOutputTensorRegions(u32 n, storage_t *const *dec, u32 nRegions, const h264bsdmi_region *regions,
+                                 const h264bsdmi_tensor_spec *spec, const h264bsdmi_colour_spec *colour,
+                                 const h264bsdmi_resize_spec *resize, void *stream,
+                                 u32 *got, u32 *box, u32 *current, u32 *picId)
+{
+    static const h264bsdmi_resize_spec stretch = { H264BSDMI_FILTER_BILINEAR, H264BSDMI_FIT_STRETCH, { 0.0f, 0.0f, 0.0f } };
+    const int LIMIT = 16384;
+    if (tensor_specs_refused(spec, &colour, resize) || spec->resize != 1) return -1;
+    if (nRegions && (!regions || !got)) return -1;
+    if (nRegions > 65535u) return -1;
+    for (u32 r = 0; r < nRegions; r++) {
+        const h264bsdmi_region *g = &regions[r];
+        if (g->instance >= n || !g->w || !g->h || g->w > (u32)LIMIT || g->h > (u32)LIMIT) return -1;
+        if (g->x > LIMIT || g->x < -LIMIT || g->y > LIMIT || g->y < -LIMIT) return -1;
+    }
+    if (n && !dec) return -1;
+    if (!resize) resize = &stretch;
+    for (u32 i = 0; i < n; i++) {
+        const ApiDec *a = dec_of(dec[i]);
+        if (!a || !a->hd->sink.tensor_regions) return -1;                   /* capture mode: there are no pixels */
+        for (u32 k = 0; k < i; k++)
+            if (dec[k] == dec[i]) return -1;
+    }
+    /* one SinkTensorPic per instance that has a current picture and at least one region */
+    SinkTensorPic *pics = (SinkTensorPic *)malloc((n ? n : 1) * sizeof(SinkTensorPic));
+    SinkRegion *regs = (SinkRegion *)malloc((nRegions ? nRegions : 1) * sizeof(SinkRegion));
+    u32 *pic_of = (u32 *)malloc((n ? n : 1) * sizeof(u32));
+    if (!pics || !regs || !pic_of) { free(pics); free(regs); free(pic_of); return -1; }
+    u32 m = 0, k = 0;
+    for (u32 i = 0; i < n; i++) pic_of[i] = 0xFFFFFFFFu;
+    for (u32 r = 0; r < nRegions; r++) {
+        const h264bsdmi_region *g = &regions[r];
+        const ApiDec *a = dec_of(dec[g->instance]);
+        if (!a->has_cur || !a->hd->active_sps) continue;                     /* got[r] = 0 */
+        if (pic_of[g->instance] == 0xFFFFFFFFu) {
+            pic_of[g->instance] = m;
+            tensor_pic(&pics[m++], a, a->cur.slot, g->instance, spec, colour);
+        }
+        SinkRegion *q = &regs[k++];
+        *q = (SinkRegion){ pic_of[g->instance], r, g->x, g->y, g->w, g->h, { 0, 0, spec->width, spec->height } };
+        if (resize->fit == H264BSDMI_FIT_LETTERBOX) letterbox(spec->width, spec->height, g->w, g->h, q->box);
+    }
+    int rc = 0;
+    if (k && pics[0].sink->tensor_regions(m, pics, k, regs, spec, colour->chroma, resize, stream)) rc = -2;
+    if (!rc) {
+        for (u32 r = 0; r < nRegions; r++) got[r] = 0;
+        if (box) memset(box, 0, 4 * sizeof(u32) * nRegions);
+        for (u32 j = 0; j < k; j++) {
+            got[regs[j].index] = 1;
+            if (box) memcpy(box + 4 * regs[j].index, regs[j].box, sizeof(regs[j].box));
+        }
+        for (u32 i = 0; i < n; i++) {
+            const ApiDec *a = dec_of(dec[i]);
+            const int cur = a->has_cur && a->hd->active_sps;
+            if (current) current[i] = cur ? 1 : 0;
+            if (picId) picId[i] = cur ? a->cur.pic_id : 0;
+        }
+    }
+    free(pics);
+    free(regs);
+    free(pic_of);
+    return rc;
 }
 
 static u32 *next_converted(storage_t *s, u32 *picId, u32 *isIdrPic, u32 *numErrMbs, int fmt)
@@ -385,6 +475,7 @@ u32 h264bsdCheckValidParamSets(storage_t *s)
 void h264bsdFlushBuffer(storage_t *s)
 {
     ApiDec *a = dec_of(s);
+    drop_current(a);
     if (a) hd_dpb_flush(&a->hd->dpb);
 }
 
@@ -427,6 +518,7 @@ void h264bsdConvertToYCbCrA(u32 width, u32 height, u8 *data, u32 *pOutput) { eng
 u32 h264bsdmiDecodePicture(storage_t *s, u8 *buf, u32 len, u32 picId, u32 *consumed, u32 *nErrors)
 {
     u32 off = 0, last = H264BSD_RDY, errs = 0, stalls = 0;
+    drop_current(dec_of(s));
     while (off < len) {
         u32 rb = 0;
         last = h264bsdDecode(s, buf + off, len - off, picId, &rb);

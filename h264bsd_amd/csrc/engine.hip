@@ -33,6 +33,7 @@
 #include "kernels.hip.h"
 #include "kernels/k_tensor_out.hip.h"
 #include "kernels/k_tensor_aa.hip.h"
+#include "kernels/k_tensor_roi.hip.h"
 #include "engine.h"
 #include "hip_owned.h"
 #include "../../include/h264bsd_mi355x_bench.h"
@@ -1065,10 +1066,11 @@ void sink_close(void *user)
 /* ---- the next pictures of many instances into one caller-owned tensor (h264bsdmiNextOutputTensorBatch[Colour|Resize]) ---- */
 /* one kernel per dtype, layout, number of channels and REF; the channel order and the whole colour transform are in the items
  * (colour_item) */
-/* (k_tensor_aa: one more family on the same four parameters, filter and fit at run time) */
-enum { TK_OUT, TK_RESIZE, TK_AA };
+/* (k_tensor_aa: one more family on the same four parameters, filter and fit at run time; k_tensor_roi: the same for regions) */
+enum { TK_OUT, TK_RESIZE, TK_AA, TK_ROI };
 template <int DT, int L, int C> static const void *tensor_kernel_of(int kind, bool ref)
 {
+    if (kind == TK_ROI) return ref ? reinterpret_cast<const void *>(&h264k::k_tensor_roi<DT, L, C, true>) : reinterpret_cast<const void *>(&h264k::k_tensor_roi<DT, L, C, false>);
     if (kind == TK_AA) return ref ? reinterpret_cast<const void *>(&h264k::k_tensor_aa<DT, L, C, true>) : reinterpret_cast<const void *>(&h264k::k_tensor_aa<DT, L, C, false>);
     const bool resize = kind == TK_RESIZE;
     if (ref) return resize ? reinterpret_cast<const void *>(&h264k::k_tensor_resize<DT, L, C, true>) : reinterpret_cast<const void *>(&h264k::k_tensor_out<DT, L, C, true>);
@@ -1087,9 +1089,9 @@ template <int DT> static const void *tensor_kernel_dt(int kind, bool ref, uint32
     }
     return nullptr;
 }
-static const void *tensor_kernel(const h264bsdmi_tensor_spec &t, bool aa, bool ref)
+static const void *tensor_kernel(const h264bsdmi_tensor_spec &t, bool aa, bool ref, bool roi = false)
 {
-    const int kind = aa ? TK_AA : t.resize ? TK_RESIZE : TK_OUT;
+    const int kind = roi ? TK_ROI : aa ? TK_AA : t.resize ? TK_RESIZE : TK_OUT;
     switch (t.dtype) {
     case h264k::TO_U8: return tensor_kernel_dt<h264k::TO_U8>(kind, ref, t.layout, t.channels);
     case h264k::TO_F16: return tensor_kernel_dt<h264k::TO_F16>(kind, ref, t.layout, t.channels);
@@ -1097,8 +1099,8 @@ static const void *tensor_kernel(const h264bsdmi_tensor_spec &t, bool aa, bool r
     }
     return nullptr;
 }
-/* the staging ring's item stride: k_tensor_out / k_tensor_resize read TensorItems, k_tensor_aa AaItems */
-constexpr size_t TITEM_BYTES = std::max(sizeof(h264k::TensorItem), sizeof(h264k::AaItem));
+/* the staging ring's item stride: k_tensor_out / k_tensor_resize read TensorItems, k_tensor_aa AaItems, k_tensor_roi RoiItems */
+constexpr size_t TITEM_BYTES = std::max({ sizeof(h264k::TensorItem), sizeof(h264k::AaItem), sizeof(h264k::RoiItem) });
 
 /* The colour map of one picture's item (matrix, range): per output channel c the affine map of the 8-bit (Y, Cb - 128, Cr - 128) to
  * the value written, and the clamp bounds of [0, 1] under the output scale (U8: 255 v; floats: (v - mean[c]) / std[c]), folded in
@@ -1143,16 +1145,22 @@ static void colour_item(h264k::TensorItem &it, const h264bsdmi_tensor_spec &t, u
 /* Under the engine's mutex.  Ordering without host waits: the instances' queued jobs are enqueued once for the batch, the output
  * stream waits for each picture's producing tick (deduplicated per lane launch, as lane_launch does), ONE launch lays out every
  * picture, and a fence recorded behind it is handed to every instance: lane_launch makes an instance's next tick wait for it, and
- * the frame buffers are not cleared or freed before it has passed (fence_drop).  *fence_ev: the fence's event. */
-static int tensor_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, const h264bsdmi_tensor_spec &t, uint32_t chroma,
-                             const h264bsdmi_resize_spec *rs, hipStream_t st, hipEvent_t *fence_ev)
+ * the frame buffers are not cleared or freed before it has passed (fence_drop).  *fence_ev: the fence's event.
+ * regs != nullptr (h264bsdmiOutputTensorRegions): the items are the n_regs regions, each a box of one of the n pictures, which were
+ * popped earlier and are read where they lie; k_tensor_roi for every filter and fit.  The pictures are still one per instance, so
+ * the producers' events and the fence are taken once per instance however many regions name it. */
+static int tensor_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, uint32_t n_regs, const SinkRegion *regs,
+                             const h264bsdmi_tensor_spec &t, uint32_t chroma, const h264bsdmi_resize_spec *rs, hipStream_t st,
+                             hipEvent_t *fence_ev)
 {
     const bool ref = pics[0].matrix == H264BSDMI_MATRIX_REFERENCE;      /* one kernel: every picture of the call, or none */
     /* k_tensor_aa for every filter and fit but resize = 1's own bilinear stretch, which stays on k_tensor_resize */
-    const bool aa = rs && (rs->filter != H264BSDMI_FILTER_BILINEAR || rs->fit != H264BSDMI_FIT_STRETCH);
-    if (aa && (!t.resize || rs->filter > H264BSDMI_FILTER_BICUBIC_AA || rs->fit > H264BSDMI_FIT_LETTERBOX)) return -1;
-    const void *fn = tensor_kernel(t, aa, ref);
+    const bool aa = !regs && rs && (rs->filter != H264BSDMI_FILTER_BILINEAR || rs->fit != H264BSDMI_FIT_STRETCH);
+    if ((aa || regs) && (!rs || !t.resize || rs->filter > H264BSDMI_FILTER_BICUBIC_AA || rs->fit > H264BSDMI_FIT_LETTERBOX)) return -1;
+    const void *fn = tensor_kernel(t, aa, ref, regs != nullptr);
     if (!fn) return -1;
+    const uint32_t n_items = regs ? n_regs : n;
+    if (!n_items || n_items > 65535u) return -1;                        /* grid.y */
     for (uint32_t i = 0; i < n; i++) {
         const StreamCtx *s = static_cast<SinkUser *>(pics[i].sink->user)->s;
         const SinkTensorPic &p = pics[i];
@@ -1162,6 +1170,11 @@ static int tensor_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, c
         if ((p.x0 | p.y0 | p.w | p.h) & 1u) return -1;
         if (aa && (!p.box[2] || !p.box[3] || p.box[0] + p.box[2] > t.width || p.box[1] + p.box[3] > t.height)) return -1;
     }
+    for (uint32_t r = 0; regs && r < n_regs; r++) {
+        const SinkRegion &g = regs[r];
+        if (g.pic >= n || !g.w || !g.h || g.w > 16384u || g.h > 16384u || abs(g.x) > 16384 || abs(g.y) > 16384) return -1;
+        if (!g.box[2] || !g.box[3] || g.box[0] + g.box[2] > t.width || g.box[1] + g.box[3] > t.height) return -1;
+    }
     bool mine = false;
     for (uint32_t i = 0; i < n && !mine; i++) {
         StreamCtx *s = static_cast<SinkUser *>(pics[i].sink->user)->s;
@@ -1169,11 +1182,11 @@ static int tensor_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, c
         mine = !s->pending.empty();
     }
     if (mine && flush_locked(e, false)) return -1;
-    if (n > e->titem_cap) {
+    if (n_items > e->titem_cap) {
         for (int k = 0; k < 2; k++)
             if (e->titem_used[k]) HIP_TRY(hipEventSynchronize(e->titem_ev[k]));
         e->titem_cap = 0;
-        const size_t cap = std::max<size_t>(n, 256);
+        const size_t cap = std::max<size_t>(n_items, 256);
         HIP_TRY(e->h_titems.alloc(2 * cap * TITEM_BYTES, true));
         for (int k = 0; k < 2; k++)
             if (!e->titem_ev[k]) HIP_TRY(e->titem_ev[k].create(hipEventDisableTiming));
@@ -1184,17 +1197,20 @@ static int tensor_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, c
     const size_t half = (size_t)f * e->titem_cap * TITEM_BYTES;
     h264k::TensorItem *items = reinterpret_cast<h264k::TensorItem *>(e->h_titems + half);
     h264k::AaItem *aa_items = reinterpret_cast<h264k::AaItem *>(e->h_titems + half);
+    h264k::RoiItem *roi_items = reinterpret_cast<h264k::RoiItem *>(e->h_titems + half);
     const size_t C = t.channels == h264k::TO_Y ? 1 : t.channels >= h264k::TO_RGBA ? 4 : 3;
     const size_t pic_bytes = C * t.width * t.height * (t.dtype == h264k::TO_U8 ? 1 : t.dtype == h264k::TO_F16 ? 2 : 4);
     std::vector<std::pair<int, unsigned long long>> waited;
     for (uint32_t i = 0; i < n; i++) {
         const StreamCtx *s = static_cast<SinkUser *>(pics[i].sink->user)->s;
         const SinkTensorPic &p = pics[i];
-        h264k::TensorItem &ti = aa ? aa_items[i].t : items[i];
-        ti = h264k::TensorItem{ s->d_frames + (size_t)p.slot * s->frame_bytes, static_cast<uint8_t *>(t.data) + p.index * pic_bytes,
-                                s->wmb, p.x0, p.y0, p.w, p.h, 0u };
-        colour_item(ti, t, p.matrix, p.range);
-        if (aa) { aa_items[i].left = p.box[0]; aa_items[i].top = p.box[1]; aa_items[i].iw = p.box[2]; aa_items[i].ih = p.box[3]; }
+        if (!regs) {
+            h264k::TensorItem &ti = aa ? aa_items[i].t : items[i];
+            ti = h264k::TensorItem{ s->d_frames + (size_t)p.slot * s->frame_bytes, static_cast<uint8_t *>(t.data) + p.index * pic_bytes,
+                                    s->wmb, p.x0, p.y0, p.w, p.h, 0u };
+            colour_item(ti, t, p.matrix, p.range);
+            if (aa) { aa_items[i].left = p.box[0]; aa_items[i].top = p.box[1]; aa_items[i].iw = p.box[2]; aa_items[i].ih = p.box[3]; }
+        }
         if (s->last_lane >= 0) {
             const std::pair<int, unsigned long long> key(s->last_lane, s->last_launch);
             if (std::find(waited.begin(), waited.end(), key) == waited.end()) {
@@ -1204,9 +1220,37 @@ static int tensor_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, c
             }
         }
     }
+    if (regs) {
+        /* the colour map once per picture, then one item per region */
+        std::vector<h264k::TensorItem> of_pic(n);
+        for (uint32_t i = 0; i < n; i++) {
+            const StreamCtx *s = static_cast<SinkUser *>(pics[i].sink->user)->s;
+            const SinkTensorPic &p = pics[i];
+            of_pic[i] = h264k::TensorItem{ s->d_frames + (size_t)p.slot * s->frame_bytes, nullptr, s->wmb, p.x0, p.y0, p.w, p.h, 0u };
+            colour_item(of_pic[i], t, p.matrix, p.range);
+        }
+        for (uint32_t r = 0; r < n_regs; r++) {
+            const SinkRegion &g = regs[r];
+            roi_items[r] = h264k::RoiItem{ of_pic[g.pic], g.x, g.y, g.w, g.h, g.box[0], g.box[1], g.box[2], g.box[3] };
+            roi_items[r].t.dst = static_cast<uint8_t *>(t.data) + g.index * pic_bytes;
+        }
+    }
     h264k::TensorArgs ta{ reinterpret_cast<const h264k::TensorItem *>(e->h_titems.dev() + half), t.width, t.height, chroma,
                           { t.mean[0], t.mean[1], t.mean[2] }, { t.std[0], t.std[1], t.std[2] } };
-    if (aa) {
+    if (regs) {
+        /* pad: outside the inner rectangle, under the output scale (as for k_tensor_aa); spad: the pad around the picture under the
+         * scale of the samples k_tensor_roi interpolates — REF the 8-bit value whatever the dtype, otherwise 255 pad / (pad - mean) / std */
+        h264k::RoiArgs rargs{ reinterpret_cast<const h264k::RoiItem *>(e->h_titems.dev() + half), t.width, t.height, chroma, rs->filter,
+                              { t.mean[0], t.mean[1], t.mean[2] }, { t.std[0], t.std[1], t.std[2] }, { 0, 0, 0 }, { 0, 0, 0 } };
+        for (int c = 0; c < 3; c++) {
+            const double q = std::floor(255.0 * rs->pad[c] + 0.5), nrm = ((double)rs->pad[c] - t.mean[c]) / t.std[c];
+            rargs.pad[c] = t.dtype == h264k::TO_U8 ? (float)q : (float)nrm;
+            rargs.spad[c] = ref ? (float)q : t.dtype == h264k::TO_U8 ? (float)(255.0 * rs->pad[c]) : (float)nrm;
+        }
+        const uint32_t blocks = (t.width + h264k::TAA_COLS - 1u) / h264k::TAA_COLS * ((t.height + h264k::TAA_ROWS - 1u) / h264k::TAA_ROWS);
+        void *args[] = { &rargs };
+        HIP_TRY(hipLaunchKernel(fn, dim3(std::min(blocks, 1024u), n_regs), dim3(256), args, 0, st));
+    } else if (aa) {
         /* the pad under the output scale, per output channel: U8 floor(255 pad + 0.5), floats (pad - mean) / std, in double */
         h264k::AaArgs aargs{ reinterpret_cast<const h264k::AaItem *>(e->h_titems.dev() + half), t.width, t.height, chroma, rs->filter,
                              { t.mean[0], t.mean[1], t.mean[2] }, { t.std[0], t.std[1], t.std[2] }, { 0, 0, 0 } };
@@ -1241,9 +1285,9 @@ static int tensor_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, c
     return 0;
 }
 
-/* JobSink.tensor_out (h264bsdmiNextOutputTensorBatch[Colour|Resize]) */
-int sink_tensor_out(uint32_t n, const SinkTensorPic *pics, const h264bsdmi_tensor_spec *spec, uint32_t chroma,
-                    const h264bsdmi_resize_spec *resize, void *stream)
+/* JobSink.tensor_out (h264bsdmiNextOutputTensorBatch[Colour|Resize]) and JobSink.tensor_regions (regions != nullptr) */
+static int sink_tensor_call(uint32_t n, const SinkTensorPic *pics, uint32_t n_regions, const SinkRegion *regions,
+                            const h264bsdmi_tensor_spec *spec, uint32_t chroma, const h264bsdmi_resize_spec *resize, void *stream)
 {
     if (!n) return 0;
     if (!pics || !spec) return -1;
@@ -1260,13 +1304,25 @@ int sink_tensor_out(uint32_t n, const SinkTensorPic *pics, const h264bsdmi_tenso
             HIP_TRY(hipStreamIsCapturing(st, &cs));
             if (cs != hipStreamCaptureStatusNone) return -1;                      /* graph capture of this call is not supported */
         }
-        if (tensor_out_locked(e, n, pics, *spec, chroma, resize, st, &fence_ev)) return -1;
+        if (tensor_out_locked(e, n, pics, n_regions, regions, *spec, chroma, resize, st, &fence_ev)) return -1;
     }
     if (stream) return 0;
     if (hipEventSynchronize(fence_ev) != hipSuccess) return -1;        /* (a later call may have recorded it again: that only waits longer) */
     std::lock_guard<std::mutex> lk(e->mu);
     fold_errors(e);
     return 0;
+}
+int sink_tensor_out(uint32_t n, const SinkTensorPic *pics, const h264bsdmi_tensor_spec *spec, uint32_t chroma,
+                    const h264bsdmi_resize_spec *resize, void *stream)
+{
+    return sink_tensor_call(n, pics, 0, nullptr, spec, chroma, resize, stream);
+}
+int sink_tensor_regions(uint32_t n, const SinkTensorPic *pics, uint32_t n_regions, const SinkRegion *regions,
+                        const h264bsdmi_tensor_spec *spec, uint32_t chroma, const h264bsdmi_resize_spec *resize, void *stream)
+{
+    if (!n_regions) return 0;
+    if (!regions || !resize) return -1;
+    return sink_tensor_call(n, pics, n_regions, regions, spec, chroma, resize, stream);
 }
 } // namespace
 
@@ -1295,6 +1351,7 @@ int eng_attach(JobSink *sink)
     sink->close = sink_close;
     sink->errors = sink_errors;
     sink->tensor_out = sink_tensor_out;
+    sink->tensor_regions = sink_tensor_regions;
     return 0;
 }
 

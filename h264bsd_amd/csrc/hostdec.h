@@ -226,6 +226,14 @@ typedef struct SinkTensorPic {
     uint32_t matrix, range;     /* H264BSDMI_MATRIX_REFERENCE (range 0), or the picture's BT601..SMPTE240 and RANGE_LIMITED / FULL */
     uint32_t box[4];            /* the inner rectangle of the output the window fills: left, top, width, height */
 } SinkTensorPic;
+/* one region of h264bsdmiOutputTensorRegions (JobSink.tensor_regions): the box (x, y) + w x h, relative to the window of pics[pic]
+ * and free to reach beyond it, resampled into the rectangle box[] of slice `index` of the output tensor */
+typedef struct SinkRegion {
+    uint32_t pic, index;
+    int32_t  x, y;
+    uint32_t w, h;
+    uint32_t box[4];            /* left, top, width, height */
+} SinkRegion;
 typedef struct JobSink {
     void *user;
     /* (re)configure for a sequence: n_slots frames of frame_bytes each. 0 = ok */
@@ -259,6 +267,12 @@ typedef struct JobSink {
      * pics[i].box is the whole output).  Called through any of the n sinks.  0 = ok; <0 = error, nothing enqueued */
     int (*tensor_out)(uint32_t n, const SinkTensorPic *pics, const struct h264bsdmi_tensor_spec *spec, uint32_t chroma,
                       const struct h264bsdmi_resize_spec *resize, void *stream);
+    /* optional: n_regions boxes of the n pictures (distinct instances, as above; pics[i].index and box are not used: every region
+     * names its picture, its slice of spec->data and its rectangle), with one launch — h264bsdmiOutputTensorRegions.  The pictures
+     * have been popped already: they are read where they lie.  resize: the filter and the pad (never NULL).  0 = ok; <0 = error */
+    int (*tensor_regions)(uint32_t n, const SinkTensorPic *pics, uint32_t n_regions, const SinkRegion *regions,
+                          const struct h264bsdmi_tensor_spec *spec, uint32_t chroma, const struct h264bsdmi_resize_spec *resize,
+                          void *stream);
 } JobSink;
 
 /* ---------------------------------------------------------------- decoder instance */

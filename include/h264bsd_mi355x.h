@@ -150,6 +150,40 @@ int h264bsdmiNextOutputTensorBatchResize(u32 n, storage_t *const *pStorage, cons
                                          void *stream, u32 *got, u32 *picId, u32 *isIdrPic, u32 *numErrMbs,
                                          u32 *box);
 
+/* Region pulls: boxes of pictures that HAVE BEEN POPPED, each resampled into its own slice of one tensor, with one launch — the
+ * second stage of a detector / classifier pipeline, which learns where to look only after the picture has left the output queue.
+ * The CURRENT PICTURE of an instance is the picture popped last by any output call (h264bsdNextOutputPicture*,
+ * h264bsdmiNextOutputInfo, ...PictureDevice, ...PictureBatch, ...TensorBatch*).  Its frame buffer is intact until the instance
+ * decodes again (a pop only advances the output queue; a decode call chooses the buffer of the next picture): it stops being
+ * current at the next h264bsdDecode or h264bsdmi*Decode* call that feeds the instance, whatever that call returns (an instance
+ * that h264bsdmiPullAndDecodePictureBatch does not feed keeps the picture the call popped), and at h264bsdFlushBuffer,
+ * h264bsdShutdown and h264bsdInit — the reference's rule for the pointer h264bsdNextOutputPicture returns.  The call pops
+ * nothing and may be repeated on the same picture.
+ * Region r reads the current picture of pStorage[regions[r].instance] and fills slice r of spec->data (data + r * C*H*W elements,
+ * spec->width x spec->height; layout, dtype, channels, mean, std as for every tensor pull; spec->resize must be 1).  An instance
+ * may have any number of regions, or none.  got[r] = 1, or 0 (slice untouched, box of zeros) when that instance has no current
+ * picture.  current[i] / picId[i] (each may be NULL): whether instance i has a current picture, and its picId.
+ * (x, y) is the box's top-left corner in the instance's source window (the SPS cropping window when spec->crop, else the coded
+ * frame), in luma samples, of any parity, and may be negative; the box may reach beyond the window on any side or lie outside it.
+ * 1 <= w, h <= 16384, |x|, |y| <= 16384.
+ * What is sampled is the w x h picture S: where (x + u, y + v) lies inside the window, S(u, v) is what a tensor pull of the WHOLE
+ * window interpolates there (colour NULL / REFERENCE: the reference's 8-bit R, G, B or luma; otherwise the unquantised colour in
+ * [0, 1], the neighbours of bilinear chroma clamped to the chroma of the window, not of the box); elsewhere S is the pad
+ * (REFERENCE: floor(255 pad[c] + 0.5); otherwise pad[c]; c the output channel).  A region is "convert, pad, crop", in that order.
+ * S is then resampled exactly as h264bsdmiNextOutputTensorBatchResize resamples a source window: the same filters and tap rule
+ * with n_in = w or h, FIT_STRETCH / FIT_LETTERBOX with the rectangle arithmetic on (w, h), the same output scale, clamping and
+ * rounding; box (may be NULL): 4 u32 per REGION.  resize == NULL is {FILTER_BILINEAR, FIT_STRETCH}, pad 0.
+ * stream as for the other pulls (not capturing; NULL: the library's own stream, and the call waits).  Later decoding of the
+ * sampled instances waits for the kernel, not for the caller.  -1, before anything is enqueued: everything
+ * h264bsdmiNextOutputTensorBatchResize refuses in spec, colour and resize; spec->resize != 1; regions or got NULL with
+ * nRegions > 0; nRegions > 65535; an instance index >= n; a w or h of 0 or above the limit, an x or y beyond it; an instance in
+ * capture mode; repeated instances.  -2: the engine failed. */
+typedef struct h264bsdmi_region { u32 instance; int x, y; u32 w, h; } h264bsdmi_region;
+int h264bsdmiOutputTensorRegions(u32 n, storage_t *const *pStorage, u32 nRegions, const h264bsdmi_region *regions,
+                                 const h264bsdmi_tensor_spec *spec, const h264bsdmi_colour_spec *colour,
+                                 const h264bsdmi_resize_spec *resize, void *stream,
+                                 u32 *got, u32 *box, u32 *current, u32 *picId);
+
 /* ---- host parse pipeline at scale ----
  * h264bsdDecode() consumes one NAL unit of one stream per call; a caller that feeds hundreds of streams needs the
  * loop of posix/test_h264bsd.c:146-177 for each of them and its own threading.  These entry points move both into

@@ -14,9 +14,17 @@ repetition each instance decodes one more picture and the device finishes it (h2
 (h264bsdmiNextOutputTensorBatchColour; default: the reference conversion, h264bsdmiNextOutputTensorBatch).  --filter / --fit pull (b)
 with that resampling filter and fit (h264bsdmiNextOutputTensorBatchResize; default: bilinear, stretch).  Prints one JSON line.
 
+--regions K is a leg of its own (h264bsdmiOutputTensorRegions / pull_regions): K seeded boxes per instance with sides between 64 and
+400 luma samples, a few of them over the picture's edge, into [K * streams, 3, 256, 128] float16, ImageNet-normalised, bilinear_aa,
+letterboxed.  Every repetition decodes one more picture per instance and pops it (h264bsdmiNextOutputInfo) before the clock starts:
+  (e) one pull_regions call                                                              HIP events on a torch stream around the call
+  (f) the same tensor without it: pull_tensor(size=None), then per box slice (padded where it hangs over the edge),
+      F.interpolate(antialias=True) to the letterbox rectangle, paste into a padded tensor; normalise, cast     (the same clock)
+  (b) with the same filter, stretched to 224 x 224, for the cost per output element next to (e)'s; (a), (c), (d) are not run.
+
 usage: tensor_out_bench.py [--streams 256] [--reps 20] [--warmup 3] [--old-reps 3] [--colour reference|auto|bt601|bt709|...]
                            [--range auto|limited|full] [--chroma nearest|bilinear] [--filter bilinear|bilinear_aa|bicubic_aa]
-                           [--fit stretch|letterbox] [--only-b] [--no-old]"""
+                           [--fit stretch|letterbox] [--only-b] [--no-old] [--regions K]"""
 import argparse
 import json
 import os
@@ -42,11 +50,16 @@ ap.add_argument("--filter", default="bilinear", choices=["bilinear", "bilinear_a
 ap.add_argument("--fit", default="stretch", choices=sorted(h.capi.FITS))
 ap.add_argument("--only-b", action="store_true", help="time (b) and (d) only")
 ap.add_argument("--no-old", action="store_true", help="skip (c), (d) and the copy ceiling")
+ap.add_argument("--regions", type=int, default=0, help="K boxes per instance: time (e), (f) and (b) with bilinear_aa only")
 args = ap.parse_args()
+if args.regions:
+    args.filter, args.fit, args.only_b, args.no_old = "bilinear_aa", "stretch", True, True
 
 data = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "golden", "test_1920x1080.h264"), "rb").read()
 N = args.streams
 rounds = 2 * (args.warmup + args.reps) + 3 * (1 + args.old_reps) + 2
+if args.regions:
+    rounds += args.warmup + args.reps + 1 + args.old_reps
 decs = [h.Decoder(no_output_reordering=1) for _ in range(N)]
 drv = h.BatchDriver(decs, [data * (rounds // 73 + 2)] * N)
 L = h.api_lib()
@@ -124,6 +137,75 @@ def time_old_aa(size):
     return sorted(ms[1:])[len(ms[1:]) // 2]
 
 
+ROI_SIZE, ROI_PAD = (256, 128), (0.5, 0.5, 0.5)
+
+
+def region_boxes(k):
+    """k seeded boxes per instance as (instance, x, y, w, h): sides 64..400, origins that let a few of them hang over the edge"""
+    import numpy as np
+    rng = np.random.default_rng(2048)
+    w, hh = rng.integers(64, 401, N * k), rng.integers(64, 401, N * k)
+    x, y = rng.integers(-32, 1920 - w + 33), rng.integers(-32, 1080 - hh + 33)
+    return [(i // k, int(x[i]), int(y[i]), int(w[i]), int(hh[i])) for i in range(N * k)]
+
+
+def time_regions(regions):
+    """(e): one pull_regions call on the pictures popped just before"""
+    out = torch.empty((len(regions), 3) + ROI_SIZE, dtype=torch.float16, device="cuda")
+    st = torch.cuda.Stream()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    ms, wall = [], []
+    for rep in range(args.warmup + args.reps):
+        next_round()
+        for d in decs:
+            assert d.next_output_info() is not None
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        e0.record(st)
+        _, got, boxes, _, _ = h.pull_regions(decs, regions, ROI_SIZE, dtype=torch.float16, mean=MEAN, std=STD, out=out, stream=st,
+                                             mode="bilinear", antialias=True, fit="letterbox", pad=ROI_PAD, **COLOUR)
+        e1.record(st)
+        st.synchronize()
+        t1 = time.perf_counter()
+        assert all(got)
+        if rep >= args.warmup:
+            ms.append(e0.elapsed_time(e1))
+            wall.append((t1 - t0) * 1e3)
+    return sorted(ms)[len(ms) // 2], sorted(wall)[len(wall) // 2], min(ms), boxes
+
+
+def time_regions_old(regions, boxes):
+    """(f): the full-size pull, then slice, pad, antialiased interpolate and paste per box, normalise and cast once"""
+    mean = torch.tensor(MEAN, device="cuda").view(1, 3, 1, 1)
+    std = torch.tensor(STD, device="cuda").view(1, 3, 1, 1)
+    full = torch.empty((N, 3, 1080, 1920), dtype=torch.float16, device="cuda")
+    st = torch.cuda.Stream()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    ms = []
+    for rep in range(1 + args.old_reps):
+        next_round()
+        torch.cuda.synchronize()
+        e0.record(st)
+        h.pull_tensor(decs, dtype=torch.float16, out=full, stream=st, **COLOUR)
+        with torch.cuda.stream(st):
+            canvas = torch.full((len(regions), 3) + ROI_SIZE, ROI_PAD[0], dtype=torch.float16, device="cuda")
+            for k, ((i, x, y, w, hh), (left, top, iw, ih)) in enumerate(zip(regions, boxes)):
+                xa, xb, ya, yb = max(x, 0), min(x + w, 1920), max(y, 0), min(y + hh, 1080)
+                crop = full[i:i + 1, :, ya:yb, xa:xb]
+                if (xa, xb, ya, yb) != (x, x + w, y, y + hh):
+                    crop = F.pad(crop, (xa - x, x + w - xb, ya - y, y + hh - yb), value=ROI_PAD[0])
+                canvas[k:k + 1, :, top:top + ih, left:left + iw] = F.interpolate(crop, size=(ih, iw), mode="bilinear", antialias=True,
+                                                                                align_corners=False)
+            y_ = ((canvas - mean) / std).half()
+        e1.record(st)
+        st.synchronize()
+        ms.append(e0.elapsed_time(e1))
+        del y_, canvas
+    del full
+    torch.cuda.empty_cache()
+    return sorted(ms[1:])[len(ms[1:]) // 2]
+
+
 def copy_ceiling_gbs():
     src = torch.empty(1 << 30, dtype=torch.uint8, device="cuda")
     dst = torch.empty_like(src)
@@ -151,6 +233,11 @@ out_b = torch.empty((N, 3, 224, 224), dtype=torch.float16, device="cuda")
 b_ms, b_wall, b_min = time_pull((224, 224), out_b, **RESIZE)
 del out_b
 torch.cuda.empty_cache()
+e_ms = e_wall = e_min = f_ms = nan
+if args.regions:
+    REGIONS = region_boxes(args.regions)
+    e_ms, e_wall, e_min, roi_boxes = time_regions(REGIONS)
+    f_ms = time_regions_old(REGIONS, roi_boxes)
 d_ms = time_old_aa((224, 224)) if not args.no_old and args.fit == "stretch" else nan
 c_a = time_old(None) if not args.no_old and not args.only_b else nan
 c_b = time_old((224, 224)) if not args.no_old and not args.only_b else nan
@@ -163,6 +250,9 @@ print(json.dumps(dict(streams=N, reps=args.reps, colour=args.colour, range=args.
                       b_ms=round(b_ms, 3), b_min_ms=round(b_min, 3), b_wall_ms=round(b_wall, 3),
                       c_a_ms=round(c_a, 2), c_b_ms=round(c_b, 2), d_ms=round(d_ms, 3),
                       speedup_a=round(c_a / a_wall, 1), speedup_b=round(c_b / b_wall, 1),
+                      regions=args.regions, e_ms=round(e_ms, 3), e_min_ms=round(e_min, 3), e_wall_ms=round(e_wall, 3), f_ms=round(f_ms, 2),
+                      e_ns_per_element=round(e_ms * 1e6 / max(N * args.regions * 3 * ROI_SIZE[0] * ROI_SIZE[1], 1), 5),
+                      b_ns_per_element=round(b_ms * 1e6 / (N * 3 * 224 * 224), 5),
                       device_errors=h.device_errors())))
 for d in decs:
     d.close()
