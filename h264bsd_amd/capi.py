@@ -28,7 +28,7 @@ EXPORTED_SYMBOLS = [
     "h264bsdCroppingParams", "h264bsdSampleAspectRatio", "h264bsdCheckValidParamSets", "h264bsdFlushBuffer",
     "h264bsdProfile", "h264bsdAlloc", "h264bsdFree", "h264bsdConvertToRGBA", "h264bsdConvertToBGRA",
     "h264bsdConvertToYCbCrA",
-    "h264bsdmiInitCapture", "h264bsdmiNextOutputInfo", "h264bsdmiNextOutputPictureDevice", "h264bsdmiNextOutputTensorBatch", "h264bsdmiNextOutputTensorBatchColour", "h264bsdmiNextOutputTensorBatchResize", "h264bsdmiOutputTensorRegions", "h264bsdmiJobFinalize", "h264bsdmiDeviceCount", "h264bsdmiSetDevice", "h264bsdmiFlush", "h264bsdmiFlushAsync", "h264bsdmiDeviceErrors",
+    "h264bsdmiInitCapture", "h264bsdmiNextOutputInfo", "h264bsdmiNextOutputPictureDevice", "h264bsdmiNextOutputTensorBatch", "h264bsdmiNextOutputTensorBatchColour", "h264bsdmiNextOutputTensorBatchResize", "h264bsdmiOutputTensorRegions", "h264bsdmiSetMotionExport", "h264bsdmiOutputMotionRegions", "h264bsdmiJobFinalize", "h264bsdmiDeviceCount", "h264bsdmiSetDevice", "h264bsdmiFlush", "h264bsdmiFlushAsync", "h264bsdmiDeviceErrors",
     "h264bsdmiDecodePicture", "h264bsdmiDecodePictureBatch", "h264bsdmiNextOutputPictureBatch", "h264bsdmiPullAndDecodePictureBatch", "h264bsdmiSetParserThreads", "h264bsdmiSetInputReadOnly", "h264bsdmiSetCopyElision",
     "h264bsdmiReplayCreate", "h264bsdmiReplayCreateStaggered", "h264bsdmiReplayCreateDesync", "h264bsdmiReplayCreateSched", "h264bsdmiReplayReschedule", "h264bsdmiReplayDestroy", "h264bsdmiReplayRun", "h264bsdmiReplaySync",
     "h264bsdmiReplayFetch", "h264bsdmiReplayChecksums", "h264bsdmiReplayConvert", "h264bsdmiReplayFetchConverted",
@@ -67,6 +67,16 @@ class Region(ctypes.Structure):
     _fields_ = [("instance", ctypes.c_uint32), ("x", ctypes.c_int), ("y", ctypes.c_int), ("w", ctypes.c_uint32), ("h", ctypes.c_uint32)]
 
 
+class MotionSpec(ctypes.Structure):
+    """h264bsdmi_motion_spec (include/h264bsd_mi355x.h)"""
+    _fields_ = [("data", ctypes.c_void_p), ("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("layout", ctypes.c_uint32),
+                ("dtype", ctypes.c_uint32), ("planes", ctypes.c_uint32), ("crop", ctypes.c_uint32), ("fit", ctypes.c_uint32),
+                ("sampler", ctypes.c_uint32), ("units", ctypes.c_uint32), ("per_picture", ctypes.c_uint32)]
+
+
+MOTION_PLANES = {"mv": (1, 2), "valid": (2, 1), "age": (4, 1), "qp": (8, 1)}     # name -> (H264BSDMI_MOTION_PLANE_*, channels), in channel order
+MOTION_SAMPLERS = {"nearest": 0, "area": 1}                                      # H264BSDMI_MOTION_*
+MOTION_UNITS = {"source": 0, "output": 1}                                        # H264BSDMI_MOTION_UNITS_*
 MATRICES = {"reference": 0, "auto": 1, "bt601": 2, "bt709": 3, "bt2020": 4, "fcc": 5, "smpte240": 6}    # H264BSDMI_MATRIX_*
 RANGES = {"auto": 0, "limited": 1, "full": 2}                                                          # H264BSDMI_RANGE_*
 CHROMA = {"nearest": 0, "bilinear": 1}                                                                 # H264BSDMI_CHROMA_*
@@ -183,6 +193,11 @@ def _declare(L, harness):
     L.h264bsdmiOutputTensorRegions.argtypes = [u32, ctypes.POINTER(vp), u32, ctypes.POINTER(Region), ctypes.POINTER(TensorSpec),
                                                ctypes.POINTER(ColourSpec), ctypes.POINTER(ResizeSpec), vp, P32, P32, P32, P32]
     L.h264bsdmiOutputTensorRegions.restype = ctypes.c_int
+    L.h264bsdmiSetMotionExport.argtypes = [vp, u32]
+    L.h264bsdmiSetMotionExport.restype = ctypes.c_int
+    L.h264bsdmiOutputMotionRegions.argtypes = [u32, ctypes.POINTER(vp), u32, ctypes.POINTER(Region), ctypes.POINTER(MotionSpec), vp,
+                                               P32, P32, P32, P32]
+    L.h264bsdmiOutputMotionRegions.restype = ctypes.c_int
     L.h264bsdmiDecodePicture.argtypes = [vp, u8p, u32, u32, P32, P32]
     L.h264bsdmiDecodePicture.restype = u32
     L.h264bsdmiDecodePictureBatch.argtypes = [u32, ctypes.POINTER(vp), ctypes.POINTER(vp), P32, P32, P32, P32, P32]
@@ -257,10 +272,11 @@ def device_error_events():
 class Decoder:
     """One decoder instance.  Method names follow the reference API (h264bsd_decoder.h)."""
 
-    def __init__(self, no_output_reordering=0, capture=None, copy_elision=None):
+    def __init__(self, no_output_reordering=0, capture=None, copy_elision=None, motion=False):
         """capture: None -> pixels on the GPU (h264bsdInit; raises when there is no device);
         a callable(bytes) -> parser only, every picture's frame job is handed to it.
-        copy_elision: None -> the library's default (on with a device, off in capture mode), else h264bsdmiSetCopyElision."""
+        copy_elision: None -> the library's default (on with a device, off in capture mode), else h264bsdmiSetCopyElision.
+        motion: keep the motion side information of every picture on the device for pull_motion (h264bsdmiSetMotionExport)."""
         L = api_lib()
         self._L = L
         self._st = L.h264bsdAlloc()
@@ -278,6 +294,9 @@ class Decoder:
             raise RuntimeError("h264bsdInit failed: the HIP engine is not available (no CPU pixel path exists)")
         if copy_elision is not None:
             L.h264bsdmiSetCopyElision(self._st, 1 if copy_elision else 0)
+        if motion and L.h264bsdmiSetMotionExport(self._st, 1) != 0:
+            self.close()
+            raise RuntimeError("h264bsdmiSetMotionExport failed: motion export needs a decoder bound to a device")
 
     def close(self):
         if self._st:
@@ -608,6 +627,78 @@ def pull_regions(decoders, regions, size, layout="NCHW", dtype=None, channels="R
                                         stream.cuda_stream, got, box, cur, ids)
     if rc != 0:
         raise RuntimeError(f"h264bsdmiOutputTensorRegions failed ({rc})")
+    return (out, list(got)[:K], [tuple(box[4 * k: 4 * k + 4]) if got[k] else None for k in range(K)], list(cur)[:n], list(ids)[:n])
+
+
+def pull_motion(decoders, regions=None, size=None, layout="NCHW", dtype=None, planes=("mv", "valid"), crop=True, fit="stretch",
+                sampler="nearest", units="source", per_picture=False, out=None, stream=None):
+    """h264bsdmiOutputMotionRegions: the decoded motion field of the decoders' CURRENT pictures (Decoder(..., motion=True)), sampled
+    by one kernel launch into ONE dense CUDA tensor [K, C, H, W] or [K, H, W, C] in torch.float16 (default) / float32 that lies
+    pixel for pixel over what pull_regions gives for the same regions, size, crop and fit.  regions as for pull_regions; None: one
+    region per decoder, its whole source window.  size: an int or (height, width); None (regions=None, one common window W x H
+    only): the native grid of one value per 4x4 block, ceil(H / 4) x ceil(W / 4).  planes: a subset of "mv" (2 channels: dx, dy in
+    luma samples, the displacement of the reference as coded), "valid", "age" (decoded pictures back to the reference), "qp"; the
+    channels come in that order whatever the order given.  sampler "nearest" or "area"; units "source" or "output" (pixels of the
+    output rectangle); per_picture: dx, dy divided by max(age, 1).  Returns what pull_regions returns."""
+    import torch
+    n = len(decoders)
+    if dtype is None:
+        dtype = torch.float16
+    dtypes = {torch.float16: 1, torch.float32: 2}
+    planes = (planes,) if isinstance(planes, str) else tuple(planes)
+    if dtype not in dtypes or layout not in LAYOUTS or not planes or any(p not in MOTION_PLANES for p in planes):
+        raise ValueError(f"pull_motion: unsupported dtype / layout / planes {dtype} {layout} {planes}")
+    if fit not in FITS or sampler not in MOTION_SAMPLERS or units not in MOTION_UNITS:
+        raise ValueError(f"pull_motion: unsupported fit / sampler / units {fit} {sampler} {units}")
+    mask = sum(MOTION_PLANES[p][0] for p in set(planes))
+    C = sum(c for bit, c in MOTION_PLANES.values() if mask & bit)
+    regs = None
+    if regions is not None:
+        regs = []
+        for r in regions:
+            r = tuple(r)
+            if len(r) != 5 or not all(isinstance(v, int) for v in r):
+                raise ValueError(f"pull_motion: a region is (decoder_index, x, y, w, h) in host integers, not {r}")
+            i, x, y, w, h = r
+            if not 0 <= i < n or not 1 <= w <= 16384 or not 1 <= h <= 16384 or abs(x) > 16384 or abs(y) > 16384:
+                raise ValueError(f"pull_motion: region {r} names no decoder of the call or is out of range (1 <= w, h <= 16384, |x|, |y| <= 16384)")
+            regs.append(Region(i, x, y, w, h))
+    K = n if regs is None else len(regs)
+    if K > 65535:
+        raise ValueError("pull_motion: at most 65535 regions per call")
+    if size is None:
+        if regs is not None:
+            raise ValueError("pull_motion: regions need a size")
+        windows = set()
+        for d in decoders:
+            if d.pic_width():
+                flag, _, cw, _, chh = d.cropping_params()
+                windows.add((chh, cw) if crop and flag else (16 * d.pic_height(), 16 * d.pic_width()))
+        if len(windows) != 1:
+            raise ValueError("pull_motion: size=None needs decoders that have seen a sequence parameter set and share one window")
+        wh, ww = windows.pop()
+        H, W = (wh + 3) // 4, (ww + 3) // 4
+    else:
+        H, W = (size, size) if isinstance(size, int) else (int(size[0]), int(size[1]))
+    shape = (K, C, H, W) if layout == "NCHW" else (K, H, W, C)
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device="cuda")
+    elif not out.is_cuda or out.dtype != dtype or tuple(out.shape) != shape or not out.is_contiguous():
+        raise ValueError(f"pull_motion: out must be a contiguous CUDA {dtype} tensor of shape {shape}")
+    if stream is None:
+        stream = torch.cuda.current_stream(out.device)
+    if not stream.cuda_stream:
+        stream.synchronize()        # torch's legacy default stream, as in _tensor_call: the C call uses the library's own stream and waits
+    spec = MotionSpec(out.data_ptr(), W, H, LAYOUTS[layout], dtypes[dtype], mask, 1 if crop else 0, FITS[fit],
+                      MOTION_SAMPLERS[sampler], MOTION_UNITS[units], 1 if per_picture else 0)
+    L = api_lib()
+    got, box = (ctypes.c_uint32 * max(K, 1))(), (ctypes.c_uint32 * (4 * max(K, 1)))()
+    cur, ids = (ctypes.c_uint32 * max(n, 1))(), (ctypes.c_uint32 * max(n, 1))()
+    rc = L.h264bsdmiOutputMotionRegions(n, (ctypes.c_void_p * max(n, 1))(*[d._st for d in decoders]), K,
+                                        None if regs is None else (Region * max(K, 1))(*regs), ctypes.byref(spec),
+                                        stream.cuda_stream, got, box, cur, ids)
+    if rc != 0:
+        raise RuntimeError(f"h264bsdmiOutputMotionRegions failed ({rc})")
     return (out, list(got)[:K], [tuple(box[4 * k: 4 * k + 4]) if got[k] else None for k in range(K)], list(cur)[:n], list(ids)[:n])
 
 

@@ -31,6 +31,8 @@ typedef struct ApiDec {
      * what h264bsdmiOutputTensorRegions samples.  A copy: the output queue is rewritten by the decode calls only, but so is this. */
     OutPic cur;
     int has_cur;
+    int fed;        /* h264bsdDecode has been called: too late for h264bsdmiSetMotionExport */
+    int motion;     /* motion export is on (h264bsdmiSetMotionExport) */
 } ApiDec;
 
 /* Every H264BSDMI_* variable this library reads (tests/test_abi.py compares the list with the sources and INTEGRATION.md).  A
@@ -116,6 +118,7 @@ u32 h264bsdDecode(storage_t *s, u8 *byteStrm, u32 len, u32 picId, u32 *readBytes
     ApiDec *a = dec_of(s);
     drop_current(a);
     if (!a || !byteStrm || !len || !readBytes) return H264BSD_ERROR;
+    a->fed = 1;
     return (u32)hd_decode(a->hd, byteStrm, len, picId, readBytes);
 }
 
@@ -153,6 +156,15 @@ int h264bsdmiSetCopyElision(storage_t *s, u32 on)
     ApiDec *a = dec_of(s);
     if (!a) return -1;
     a->hd->copy_elision = on ? 1 : 0;
+    return 0;
+}
+
+int h264bsdmiSetMotionExport(storage_t *s, u32 on)
+{
+    ApiDec *a = dec_of(s);
+    if (!a || a->fed || !a->hd->sink.set_motion) return -1;               /* capture mode: there is no device to keep it on */
+    if (a->hd->sink.set_motion(a->hd->sink.user, on ? 1 : 0)) return -1;
+    a->motion = on ? 1 : 0;
     return 0;
 }
 
@@ -382,6 +394,76 @@ int h264bsdmiOutputTensorRegions(u32 n, storage_t *const *dec, u32 nRegions, con
     }
     int rc = 0;
     if (k && pics[0].sink->tensor_regions(m, pics, k, regs, spec, colour->chroma, resize, stream)) rc = -2;
+    if (!rc) {
+        for (u32 r = 0; r < nRegions; r++) got[r] = 0;
+        if (box) memset(box, 0, 4 * sizeof(u32) * nRegions);
+        for (u32 j = 0; j < k; j++) {
+            got[regs[j].index] = 1;
+            if (box) memcpy(box + 4 * regs[j].index, regs[j].box, sizeof(regs[j].box));
+        }
+        for (u32 i = 0; i < n; i++) {
+            const ApiDec *a = dec_of(dec[i]);
+            const int cur = a->has_cur && a->hd->active_sps;
+            if (current) current[i] = cur ? 1 : 0;
+            if (picId) picId[i] = cur ? a->cur.pic_id : 0;
+        }
+    }
+    free(pics);
+    free(regs);
+    free(pic_of);
+    return rc;
+}
+
+/* h264bsdmiOutputTensorRegions' regions over the motion side information of the current pictures: the same checks in the same
+ * order, the same windows (tensor_pic) and rectangles (letterbox), nothing popped. */
+int h264bsdmiOutputMotionRegions(u32 n, storage_t *const *dec, u32 nRegions, const h264bsdmi_region *regions,
+                                 const h264bsdmi_motion_spec *spec, void *stream,
+                                 u32 *got, u32 *box, u32 *current, u32 *picId)
+{
+    static const h264bsdmi_colour_spec reference = { H264BSDMI_MATRIX_REFERENCE, 0, 0, 0 };
+    const u32 planes = H264BSDMI_MOTION_PLANE_MV | H264BSDMI_MOTION_PLANE_VALID | H264BSDMI_MOTION_PLANE_AGE | H264BSDMI_MOTION_PLANE_QP;
+    const int LIMIT = 16384;
+    if (!spec || !spec->data || !spec->width || !spec->height || spec->layout > H264BSDMI_LAYOUT_NHWC) return -1;
+    if (spec->dtype != H264BSDMI_DTYPE_F16 && spec->dtype != H264BSDMI_DTYPE_F32) return -1;
+    if (!spec->planes || (spec->planes & ~planes) || spec->fit > H264BSDMI_FIT_LETTERBOX || spec->sampler > H264BSDMI_MOTION_AREA ||
+        spec->units > H264BSDMI_MOTION_UNITS_OUTPUT || spec->per_picture > 1) return -1;
+    if (nRegions && !got) return -1;
+    if (nRegions > 65535u || (!regions && nRegions != n)) return -1;
+    for (u32 r = 0; regions && r < nRegions; r++) {
+        const h264bsdmi_region *g = &regions[r];
+        if (g->instance >= n || !g->w || !g->h || g->w > (u32)LIMIT || g->h > (u32)LIMIT) return -1;
+        if (g->x > LIMIT || g->x < -LIMIT || g->y > LIMIT || g->y < -LIMIT) return -1;
+    }
+    if (n && !dec) return -1;
+    for (u32 i = 0; i < n; i++) {
+        const ApiDec *a = dec_of(dec[i]);
+        if (!a || !a->hd->sink.motion_regions || !a->motion) return -1;      /* capture mode, or no motion export */
+        for (u32 k = 0; k < i; k++)
+            if (dec[k] == dec[i]) return -1;
+    }
+    const h264bsdmi_tensor_spec window = { spec->data, spec->width, spec->height, spec->layout, spec->dtype, 0, spec->crop, 1, { 0, 0, 0 }, { 1, 1, 1 } };
+    SinkTensorPic *pics = (SinkTensorPic *)malloc((n ? n : 1) * sizeof(SinkTensorPic));
+    SinkRegion *regs = (SinkRegion *)malloc((nRegions ? nRegions : 1) * sizeof(SinkRegion));
+    u32 *pic_of = (u32 *)malloc((n ? n : 1) * sizeof(u32));
+    if (!pics || !regs || !pic_of) { free(pics); free(regs); free(pic_of); return -1; }
+    u32 m = 0, k = 0;
+    for (u32 i = 0; i < n; i++) pic_of[i] = 0xFFFFFFFFu;
+    for (u32 r = 0; r < nRegions; r++) {
+        const u32 inst = regions ? regions[r].instance : r;
+        const ApiDec *a = dec_of(dec[inst]);
+        if (!a->has_cur || !a->hd->active_sps) continue;                     /* got[r] = 0 */
+        if (pic_of[inst] == 0xFFFFFFFFu) {
+            pic_of[inst] = m;
+            tensor_pic(&pics[m++], a, a->cur.slot, inst, &window, &reference);
+        }
+        const SinkTensorPic *p = &pics[pic_of[inst]];
+        SinkRegion *q = &regs[k++];
+        if (regions) *q = (SinkRegion){ pic_of[inst], r, regions[r].x, regions[r].y, regions[r].w, regions[r].h, { 0, 0, spec->width, spec->height } };
+        else *q = (SinkRegion){ pic_of[inst], r, 0, 0, p->w, p->h, { 0, 0, spec->width, spec->height } };      /* the whole window */
+        if (spec->fit == H264BSDMI_FIT_LETTERBOX) letterbox(spec->width, spec->height, q->w, q->h, q->box);
+    }
+    int rc = 0;
+    if (k && pics[0].sink->motion_regions(m, pics, k, regs, spec, stream)) rc = -2;
     if (!rc) {
         for (u32 r = 0; r < nRegions; r++) got[r] = 0;
         if (box) memset(box, 0, 4 * sizeof(u32) * nRegions);

@@ -34,6 +34,7 @@
 #include "kernels/k_tensor_out.hip.h"
 #include "kernels/k_tensor_aa.hip.h"
 #include "kernels/k_tensor_roi.hip.h"
+#include "kernels/k_motion.hip.h"
 #include "engine.h"
 #include "hip_owned.h"
 #include "../../include/h264bsd_mi355x_bench.h"
@@ -78,6 +79,12 @@ struct StreamCtx {
     unsigned ready_round = 0;
     size_t flush_quota = 0;                 /* jobs that were queued when the current flush began: it takes no others (flush_locked) */
     Fence *fence = nullptr;                 /* the latest tensor pull that read this instance's frames (nullptr: none outstanding) */
+    /* motion export (h264bsdmiSetMotionExport): one slot of side information per frame buffer (kernels/k_motion.hip.h), and what the
+     * ages are counted from — FjHeader.pic_seq of the last picture (ghost jobs excluded) decoded into every frame buffer since
+     * sink_configure */
+    bool motion = false;
+    DeviceMem<uint8_t> d_motion; size_t motion_bytes = 0;      /* n_slots x motion_bytes */
+    uint32_t slot_seq[FJ_MAX_SLOTS] = {}; bool slot_has[FJ_MAX_SLOTS] = {};
 };
 
 /* k_dbk (boundary strengths) needs only the frame job, not pixels: it runs on a second HIP stream next to the
@@ -115,6 +122,10 @@ struct Lane {
     DeviceMem<uint8_t> d_arena; size_t arena_cap = 0;      /* device copies of the blobs of one tick */
     DeviceMem<FrameDesc> d_desc; Pinned<FrameDesc> h_desc; size_t desc_cap = 0;    /* h_desc: pinned staging, 2 halves */
     Pinned<h264k::H2dItem> h_items;            /* pinned, 2 halves like h_desc: the tick's jobs for k_h2d (h_items.dev(): the device's view of it) */
+    /* k_motion_keep's items: pinned, 2 halves of mitem_cap used in turn, each guarded by the event behind the launch that read it
+     * (allocated by the first tick that holds a picture of an instance with motion export) */
+    Pinned<h264k::MotionKeepItem> h_mitems; size_t mitem_cap = 0;
+    Event mitem_ev[2]; bool mitem_used[2] = { false, false }; int mitem_flip = 0;
     int flip = 0; unsigned ticks = 0;
     Event desc_ev[2];
     static constexpr unsigned RING = 64;
@@ -679,6 +690,46 @@ static void fence_drop(Engine *e, StreamCtx *s)
     fence_unref(e, s);
 }
 
+/* ---- motion export: the side information of a picture kept beside its frame buffer (kernels/k_motion.hip.h) ----
+ * The job about to be launched for instance s, as an item of the tick's k_motion_keep launch.  The side information of a frame
+ * buffer is that of the last job decoded into it that is no ghost: ghost jobs (pre-passes of the picture that follows in the same
+ * slot) write nothing and leave the table alone, the deblock-only job of a picture that was rendered as several jobs comes last
+ * and carries the records the reference ends up with.  The kernel gets the ages as they stood BEFORE this job. */
+static void motion_keep_item(StreamCtx *s, const uint8_t *host_blob, const uint8_t *dev_blob, std::vector<h264k::MotionKeepItem> &keep)
+{
+    const FjHeader *h = reinterpret_cast<const FjHeader *>(host_blob);
+    if (h->ghost || !s->d_motion || h->cur_slot >= s->n_slots || h->n_mbs != s->wmb * s->hmb) return;
+    h264k::MotionKeepItem it{ reinterpret_cast<const FjMbRec *>(dev_blob + h->rec_off), reinterpret_cast<const int16_t *>(dev_blob + h->mvx_off),
+                              s->d_motion + (size_t)h->cur_slot * s->motion_bytes, h->n_mbs, s->wmb, s->n_slots, h->n_mvx, {} };
+    for (uint32_t k = 0; k < s->n_slots; k++)
+        it.age[k] = s->slot_has[k] && k != h->cur_slot ? (uint8_t)std::min<uint32_t>(h->pic_seq - s->slot_seq[k], 255u) : 0;
+    s->slot_seq[h->cur_slot] = h->pic_seq; s->slot_has[h->cur_slot] = true;
+    keep.push_back(it);
+}
+/* one k_motion_keep launch for the tick just enqueued on lane l; it reads the jobs where the tick's kernels read them */
+static int motion_keep_launch(Lane &l, const std::vector<h264k::MotionKeepItem> &keep)
+{
+    if (keep.size() > l.mitem_cap) {
+        HIP_TRY(hipStreamSynchronize(l.st));               /* earlier launches may still read the old staging */
+        l.mitem_cap = 0;
+        const size_t cap = std::max<size_t>(2 * keep.size(), 64);
+        HIP_TRY(l.h_mitems.alloc(2 * cap * sizeof(h264k::MotionKeepItem), true));
+        for (auto &ev : l.mitem_ev) if (!ev) HIP_TRY(ev.create(hipEventDisableTiming));
+        l.mitem_cap = cap; l.mitem_used[0] = l.mitem_used[1] = false; l.mitem_flip = 0;
+    }
+    const int f = l.mitem_flip;
+    if (l.mitem_used[f]) HIP_TRY(hipEventSynchronize(l.mitem_ev[f]));       /* the launch before the last one read this half */
+    memcpy(l.h_mitems + (size_t)f * l.mitem_cap, keep.data(), keep.size() * sizeof(h264k::MotionKeepItem));
+    uint32_t max_mbs = 0;
+    for (const auto &it : keep) max_mbs = std::max(max_mbs, it.n_mbs);
+    hipLaunchKernelGGL(h264k::k_motion_keep, dim3(std::min<uint32_t>((max_mbs + 15u) / 16u, 1024u), (uint32_t)keep.size()), dim3(256), 0, l.st,
+                       l.h_mitems.dev() + (size_t)f * l.mitem_cap);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(l.mitem_ev[f], l.st));
+    l.mitem_used[f] = true; l.mitem_flip ^= 1;
+    return 0;
+}
+
 /* One tick on one lane: the front jobs of `part` (popped here) are copied to the lane's arena and launched. */
 static int lane_launch(Engine *e, unsigned lane_idx, const std::vector<StreamCtx *> &part)
 {
@@ -711,6 +762,7 @@ static int lane_launch(Engine *e, unsigned lane_idx, const std::vector<StreamCtx
     size_t off = 0;
     std::vector<std::pair<int, unsigned long long>> waited;
     std::vector<const Fence *> fenced;
+    std::vector<h264k::MotionKeepItem> keep;       /* the jobs of this tick whose side information is kept: none unless an instance asked */
     for (size_t i = 0; i < part.size(); i++) {
         StreamCtx *s = part[i];
         PendingJob j;
@@ -731,6 +783,7 @@ static int lane_launch(Engine *e, unsigned lane_idx, const std::vector<StreamCtx
         }
         items[i] = h264k::H2dItem{ j.host.dev(), l.d_arena + off, j.bytes, 0u };
         make_desc(descs[i], j.host, l.d_arena + off, s->d_frames, s->frame_bytes, s->d_dbk, &shape, e->d_err);
+        if (s->motion) motion_keep_item(s, j.host, l.d_arena + off, keep);
         off += (j.bytes + 255u) & ~255u;
         e->inflight.emplace_back(s, std::move(j));
         e->inflight_recorded = false;
@@ -744,6 +797,9 @@ static int lane_launch(Engine *e, unsigned lane_idx, const std::vector<StreamCtx
     if (e->lanes.size() > 1) shape.dbk_waves = LANE_DBK_WAVES;
     shape.load = (uint32_t)e->streams.size();
     if (launch_tick(l.st, l.d_desc, shape, nullptr, nullptr, 7u, l.side)) return -1;
+    /* behind the tick's kernels and in front of the ring event: a pull that waits for the picture finds its side information, the
+     * arena's next tick is behind it on this stream, and the picture's own kernels are not delayed */
+    if (!keep.empty() && motion_keep_launch(l, keep)) return -1;
     HIP_TRY(hipEventRecord(l.ring[l.launches % Lane::RING], l.st));
     l.launches++;
     return 0;
@@ -809,7 +865,7 @@ void stream_release(StreamCtx *s, bool keep_pulled = false)
     s->pending.clear();
     s->free_bufs.clear();
     s->acquired = PendingJob();
-    s->d_frames.reset(); s->d_dbk.reset();
+    s->d_frames.reset(); s->d_dbk.reset(); s->d_motion.reset();
     /* keep_pulled (a new sequence re-allocates the frame buffers, sink_configure): h264bsdmiPullAndDecodePictureBatch hands out a picture and
      * parses on in the same call — the picture must outlive the activation of a parameter set that the parsing may bring */
     for (auto &p : s->h_frame) { if (keep_pulled && p) s->retired_host.push_back(std::move(p)); p.reset(); }
@@ -833,6 +889,12 @@ int sink_configure(void *user, uint32_t wmb, uint32_t hmb, uint32_t n_slots)
     HIP_TRY(hipMemsetAsync(u->s->d_frames, 0, total, u->e->stream));
     HIP_TRY(u->s->d_dbk.alloc(DBK_SCRATCH_BYTES(wmb * hmb)));
     HIP_TRY(hipMemsetAsync(u->s->d_dbk, 0, DBK_SCRATCH_BYTES(wmb * hmb), u->e->stream));
+    if (u->s->motion) {                                    /* zeroed: every block invalid; the ages start from nothing */
+        u->s->motion_bytes = h264k::motion_slot_bytes(wmb * hmb);
+        HIP_TRY(u->s->d_motion.alloc((size_t)n_slots * u->s->motion_bytes));
+        HIP_TRY(hipMemsetAsync(u->s->d_motion, 0, (size_t)n_slots * u->s->motion_bytes, u->e->stream));
+        memset(u->s->slot_has, 0, sizeof(u->s->slot_has));
+    }
     HIP_TRY(hipStreamSynchronize(u->e->stream));           /* the lanes do not order themselves behind this stream */
     u->s->last_lane = -1;
     return 0;
@@ -1100,7 +1162,7 @@ static const void *tensor_kernel(const h264bsdmi_tensor_spec &t, bool aa, bool r
     return nullptr;
 }
 /* the staging ring's item stride: k_tensor_out / k_tensor_resize read TensorItems, k_tensor_aa AaItems, k_tensor_roi RoiItems */
-constexpr size_t TITEM_BYTES = std::max({ sizeof(h264k::TensorItem), sizeof(h264k::AaItem), sizeof(h264k::RoiItem) });
+constexpr size_t TITEM_BYTES = std::max({ sizeof(h264k::TensorItem), sizeof(h264k::AaItem), sizeof(h264k::RoiItem), sizeof(h264k::MotionItem) });
 
 /* The colour map of one picture's item (matrix, range): per output channel c the affine map of the 8-bit (Y, Cb - 128, Cr - 128) to
  * the value written, and the clamp bounds of [0, 1] under the output scale (U8: 255 v; floats: (v - mean[c]) / std[c]), folded in
@@ -1142,6 +1204,72 @@ static void colour_item(h264k::TensorItem &it, const h264bsdmi_tensor_spec &t, u
     }
 }
 
+/* The three steps every pull shares (tensor_out_locked, motion_out_locked), under the engine's mutex.
+ * pull_begin_locked: the instances' queued jobs are enqueued, once for the batch; half e->titem_flip of the item staging is made
+ * large enough for n_items and free (the launch before the last one read it). */
+static int pull_begin_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, uint32_t n_items)
+{
+    bool mine = false;
+    for (uint32_t i = 0; i < n && !mine; i++) {
+        StreamCtx *s = static_cast<SinkUser *>(pics[i].sink->user)->s;
+        std::lock_guard<std::mutex> ql(s->qmu);
+        mine = !s->pending.empty();
+    }
+    if (mine && flush_locked(e, false)) return -1;
+    if (n_items > e->titem_cap) {
+        for (int k = 0; k < 2; k++)
+            if (e->titem_used[k]) HIP_TRY(hipEventSynchronize(e->titem_ev[k]));
+        e->titem_cap = 0;
+        const size_t cap = std::max<size_t>(n_items, 256);
+        HIP_TRY(e->h_titems.alloc(2 * cap * TITEM_BYTES, true));
+        for (int k = 0; k < 2; k++)
+            if (!e->titem_ev[k]) HIP_TRY(e->titem_ev[k].create(hipEventDisableTiming));
+        e->titem_cap = cap; e->titem_used[0] = e->titem_used[1] = false; e->titem_flip = 0;
+    }
+    const int f = e->titem_flip;
+    if (e->titem_used[f]) HIP_TRY(hipEventSynchronize(e->titem_ev[f]));      /* the launch before the last one read this half */
+    return 0;
+}
+/* st waits for the tick that produced each picture (deduplicated per lane launch) */
+static int pull_wait_pictures(Engine *e, uint32_t n, const SinkTensorPic *pics, hipStream_t st)
+{
+    std::vector<std::pair<int, unsigned long long>> waited;
+    for (uint32_t i = 0; i < n; i++) {
+        const StreamCtx *s = static_cast<SinkUser *>(pics[i].sink->user)->s;
+        if (s->last_lane < 0) continue;
+        const std::pair<int, unsigned long long> key(s->last_lane, s->last_launch);
+        if (std::find(waited.begin(), waited.end(), key) != waited.end()) continue;
+        hipEvent_t made = e->lanes[s->last_lane].ring[s->last_launch % Lane::RING];
+        if (hipEventQuery(made) != hipSuccess) HIP_TRY(hipStreamWaitEvent(st, made, 0));
+        waited.push_back(key);
+    }
+    return 0;
+}
+/* behind the pull's launch on st: the staging half is guarded and handed on, the device's error words travel with the data, and a
+ * fence is handed to every instance */
+static int pull_end_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, hipStream_t st, hipEvent_t *fence_ev)
+{
+    const int f = e->titem_flip;
+    HIP_TRY(hipEventRecord(e->titem_ev[f], st));
+    e->titem_used[f] = true; e->titem_flip ^= 1;
+    hipLaunchKernelGGL(k_err_words, dim3(1), dim3(64), 0, st, e->d_err, e->h_err.dev());
+    HIP_TRY(hipGetLastError());
+    Fence *fc;
+    if (e->fences.empty()) {
+        std::unique_ptr<Fence> fresh(new Fence());
+        HIP_TRY(fresh->ev.create(hipEventDisableTiming));
+        fc = fresh.release();
+    } else { fc = e->fences.back(); e->fences.pop_back(); }
+    HIP_TRY(hipEventRecord(fc->ev, st));
+    for (uint32_t i = 0; i < n; i++) {
+        StreamCtx *s = static_cast<SinkUser *>(pics[i].sink->user)->s;
+        fence_unref(e, s);
+        s->fence = fc; fc->refs++;
+    }
+    *fence_ev = fc->ev;
+    return 0;
+}
+
 /* Under the engine's mutex.  Ordering without host waits: the instances' queued jobs are enqueued once for the batch, the output
  * stream waits for each picture's producing tick (deduplicated per lane launch, as lane_launch does), ONE launch lays out every
  * picture, and a fence recorded behind it is handed to every instance: lane_launch makes an instance's next tick wait for it, and
@@ -1175,32 +1303,14 @@ static int tensor_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, u
         if (g.pic >= n || !g.w || !g.h || g.w > 16384u || g.h > 16384u || abs(g.x) > 16384 || abs(g.y) > 16384) return -1;
         if (!g.box[2] || !g.box[3] || g.box[0] + g.box[2] > t.width || g.box[1] + g.box[3] > t.height) return -1;
     }
-    bool mine = false;
-    for (uint32_t i = 0; i < n && !mine; i++) {
-        StreamCtx *s = static_cast<SinkUser *>(pics[i].sink->user)->s;
-        std::lock_guard<std::mutex> ql(s->qmu);
-        mine = !s->pending.empty();
-    }
-    if (mine && flush_locked(e, false)) return -1;
-    if (n_items > e->titem_cap) {
-        for (int k = 0; k < 2; k++)
-            if (e->titem_used[k]) HIP_TRY(hipEventSynchronize(e->titem_ev[k]));
-        e->titem_cap = 0;
-        const size_t cap = std::max<size_t>(n_items, 256);
-        HIP_TRY(e->h_titems.alloc(2 * cap * TITEM_BYTES, true));
-        for (int k = 0; k < 2; k++)
-            if (!e->titem_ev[k]) HIP_TRY(e->titem_ev[k].create(hipEventDisableTiming));
-        e->titem_cap = cap; e->titem_used[0] = e->titem_used[1] = false; e->titem_flip = 0;
-    }
+    if (pull_begin_locked(e, n, pics, n_items)) return -1;
     const int f = e->titem_flip;
-    if (e->titem_used[f]) HIP_TRY(hipEventSynchronize(e->titem_ev[f]));      /* the launch before the last one read this half */
     const size_t half = (size_t)f * e->titem_cap * TITEM_BYTES;
     h264k::TensorItem *items = reinterpret_cast<h264k::TensorItem *>(e->h_titems + half);
     h264k::AaItem *aa_items = reinterpret_cast<h264k::AaItem *>(e->h_titems + half);
     h264k::RoiItem *roi_items = reinterpret_cast<h264k::RoiItem *>(e->h_titems + half);
     const size_t C = t.channels == h264k::TO_Y ? 1 : t.channels >= h264k::TO_RGBA ? 4 : 3;
     const size_t pic_bytes = C * t.width * t.height * (t.dtype == h264k::TO_U8 ? 1 : t.dtype == h264k::TO_F16 ? 2 : 4);
-    std::vector<std::pair<int, unsigned long long>> waited;
     for (uint32_t i = 0; i < n; i++) {
         const StreamCtx *s = static_cast<SinkUser *>(pics[i].sink->user)->s;
         const SinkTensorPic &p = pics[i];
@@ -1211,15 +1321,8 @@ static int tensor_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, u
             colour_item(ti, t, p.matrix, p.range);
             if (aa) { aa_items[i].left = p.box[0]; aa_items[i].top = p.box[1]; aa_items[i].iw = p.box[2]; aa_items[i].ih = p.box[3]; }
         }
-        if (s->last_lane >= 0) {
-            const std::pair<int, unsigned long long> key(s->last_lane, s->last_launch);
-            if (std::find(waited.begin(), waited.end(), key) == waited.end()) {
-                hipEvent_t made = e->lanes[s->last_lane].ring[s->last_launch % Lane::RING];
-                if (hipEventQuery(made) != hipSuccess) HIP_TRY(hipStreamWaitEvent(st, made, 0));
-                waited.push_back(key);
-            }
-        }
     }
+    if (pull_wait_pictures(e, n, pics, st)) return -1;
     if (regs) {
         /* the colour map once per picture, then one item per region */
         std::vector<h264k::TensorItem> of_pic(n);
@@ -1265,32 +1368,63 @@ static int tensor_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, u
         void *args[] = { &ta };
         HIP_TRY(hipLaunchKernel(fn, dim3(std::min(blocks, 1024u), n), dim3(256), args, 0, st));
     }
-    HIP_TRY(hipEventRecord(e->titem_ev[f], st));
-    e->titem_used[f] = true; e->titem_flip ^= 1;
-    hipLaunchKernelGGL(k_err_words, dim3(1), dim3(64), 0, st, e->d_err, e->h_err.dev());
-    HIP_TRY(hipGetLastError());
-    Fence *fc;
-    if (e->fences.empty()) {
-        std::unique_ptr<Fence> fresh(new Fence());
-        HIP_TRY(fresh->ev.create(hipEventDisableTiming));
-        fc = fresh.release();
-    } else { fc = e->fences.back(); e->fences.pop_back(); }
-    HIP_TRY(hipEventRecord(fc->ev, st));
-    for (uint32_t i = 0; i < n; i++) {
-        StreamCtx *s = static_cast<SinkUser *>(pics[i].sink->user)->s;
-        fence_unref(e, s);
-        s->fence = fc; fc->refs++;
-    }
-    *fence_ev = fc->ev;
-    return 0;
+    return pull_end_locked(e, n, pics, st, fence_ev);
 }
 
-/* JobSink.tensor_out (h264bsdmiNextOutputTensorBatch[Colour|Resize]) and JobSink.tensor_regions (regions != nullptr) */
+/* h264bsdmiOutputMotionRegions, under the engine's mutex: the regions of tensor_out_locked, read from the side information beside
+ * each picture's frame buffer instead of from its pixels, by one k_motion_roi launch.  The same ordering: behind the ticks that made
+ * the pictures (k_motion_keep runs in front of a tick's ring event), and the same fence, so that the next picture decoded into one of
+ * these slots — and the k_motion_keep behind it — waits for this launch. */
+static int motion_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, uint32_t n_regs, const SinkRegion *regs,
+                             const h264bsdmi_motion_spec &m, hipStream_t st, hipEvent_t *fence_ev)
+{
+    static const void *const fns[2][2] = {
+        { reinterpret_cast<const void *>(&h264k::k_motion_roi<h264k::TO_F16, h264k::TO_NCHW>), reinterpret_cast<const void *>(&h264k::k_motion_roi<h264k::TO_F16, h264k::TO_NHWC>) },
+        { reinterpret_cast<const void *>(&h264k::k_motion_roi<h264k::TO_F32, h264k::TO_NCHW>), reinterpret_cast<const void *>(&h264k::k_motion_roi<h264k::TO_F32, h264k::TO_NHWC>) } };
+    const uint32_t all = H264BSDMI_MOTION_PLANE_MV | H264BSDMI_MOTION_PLANE_VALID | H264BSDMI_MOTION_PLANE_AGE | H264BSDMI_MOTION_PLANE_QP;
+    if (!m.data || !m.width || !m.height || m.layout > h264k::TO_NHWC || (m.dtype != h264k::TO_F16 && m.dtype != h264k::TO_F32) ||
+        !m.planes || (m.planes & ~all) || m.sampler > H264BSDMI_MOTION_AREA || m.units > H264BSDMI_MOTION_UNITS_OUTPUT || m.per_picture > 1u) return -1;
+    if (!n_regs || n_regs > 65535u) return -1;                          /* grid.y */
+    for (uint32_t i = 0; i < n; i++) {
+        const StreamCtx *s = static_cast<SinkUser *>(pics[i].sink->user)->s;
+        const SinkTensorPic &p = pics[i];
+        if (!s->motion || !s->d_motion || p.slot >= s->n_slots || !p.w || !p.h || p.x0 + p.w > s->wmb * 16 || p.y0 + p.h > s->hmb * 16) return -1;
+    }
+    for (uint32_t r = 0; r < n_regs; r++) {
+        const SinkRegion &g = regs[r];
+        if (g.pic >= n || !g.w || !g.h || g.w > 16384u || g.h > 16384u || abs(g.x) > 16384 || abs(g.y) > 16384) return -1;
+        if (!g.box[2] || !g.box[3] || g.box[0] + g.box[2] > m.width || g.box[1] + g.box[3] > m.height) return -1;
+    }
+    if (pull_begin_locked(e, n, pics, n_regs)) return -1;
+    const size_t half = (size_t)e->titem_flip * e->titem_cap * TITEM_BYTES;
+    h264k::MotionItem *items = reinterpret_cast<h264k::MotionItem *>(e->h_titems + half);
+    const size_t C = ((m.planes & H264BSDMI_MOTION_PLANE_MV) ? 2 : 0) + ((m.planes & H264BSDMI_MOTION_PLANE_VALID) ? 1 : 0) +
+                     ((m.planes & H264BSDMI_MOTION_PLANE_AGE) ? 1 : 0) + ((m.planes & H264BSDMI_MOTION_PLANE_QP) ? 1 : 0);
+    const size_t slice_bytes = C * m.width * m.height * (m.dtype == h264k::TO_F16 ? 2 : 4);
+    for (uint32_t r = 0; r < n_regs; r++) {
+        const SinkRegion &g = regs[r];
+        const SinkTensorPic &p = pics[g.pic];
+        const StreamCtx *s = static_cast<SinkUser *>(p.sink->user)->s;
+        items[r] = h264k::MotionItem{ s->d_motion + (size_t)p.slot * s->motion_bytes, static_cast<uint8_t *>(m.data) + g.index * slice_bytes,
+                                      s->wmb, s->hmb, p.x0, p.y0, p.w, p.h, g.x, g.y, g.w, g.h, g.box[0], g.box[1], g.box[2], g.box[3] };
+    }
+    if (pull_wait_pictures(e, n, pics, st)) return -1;
+    h264k::MotionArgs margs{ reinterpret_cast<const h264k::MotionItem *>(e->h_titems.dev() + half), m.width, m.height, m.planes, m.sampler,
+                             m.units, m.per_picture };
+    const uint32_t blocks = (m.width + h264k::TAA_COLS - 1u) / h264k::TAA_COLS * ((m.height + h264k::TAA_ROWS - 1u) / h264k::TAA_ROWS);
+    void *args[] = { &margs };
+    HIP_TRY(hipLaunchKernel(fns[m.dtype == h264k::TO_F32][m.layout], dim3(std::min(blocks, 1024u), n_regs), dim3(256), args, 0, st));
+    return pull_end_locked(e, n, pics, st, fence_ev);
+}
+
+/* JobSink.tensor_out (h264bsdmiNextOutputTensorBatch[Colour|Resize]), JobSink.tensor_regions (regions != nullptr) and
+ * JobSink.motion_regions (motion != nullptr: spec, chroma and resize are not used) */
 static int sink_tensor_call(uint32_t n, const SinkTensorPic *pics, uint32_t n_regions, const SinkRegion *regions,
-                            const h264bsdmi_tensor_spec *spec, uint32_t chroma, const h264bsdmi_resize_spec *resize, void *stream)
+                            const h264bsdmi_tensor_spec *spec, uint32_t chroma, const h264bsdmi_resize_spec *resize, void *stream,
+                            const h264bsdmi_motion_spec *motion = nullptr)
 {
     if (!n) return 0;
-    if (!pics || !spec) return -1;
+    if (!pics || (!spec && !motion)) return -1;
     Engine *e = static_cast<SinkUser *>(pics[0].sink->user)->e;
     for (uint32_t i = 1; i < n; i++)
         if (static_cast<SinkUser *>(pics[i].sink->user)->e != e) return -1;        /* one device per call */
@@ -1304,7 +1438,8 @@ static int sink_tensor_call(uint32_t n, const SinkTensorPic *pics, uint32_t n_re
             HIP_TRY(hipStreamIsCapturing(st, &cs));
             if (cs != hipStreamCaptureStatusNone) return -1;                      /* graph capture of this call is not supported */
         }
-        if (tensor_out_locked(e, n, pics, n_regions, regions, *spec, chroma, resize, st, &fence_ev)) return -1;
+        if (motion ? motion_out_locked(e, n, pics, n_regions, regions, *motion, st, &fence_ev)
+                   : tensor_out_locked(e, n, pics, n_regions, regions, *spec, chroma, resize, st, &fence_ev)) return -1;
     }
     if (stream) return 0;
     if (hipEventSynchronize(fence_ev) != hipSuccess) return -1;        /* (a later call may have recorded it again: that only waits longer) */
@@ -1323,6 +1458,22 @@ int sink_tensor_regions(uint32_t n, const SinkTensorPic *pics, uint32_t n_region
     if (!n_regions) return 0;
     if (!regions || !resize) return -1;
     return sink_tensor_call(n, pics, n_regions, regions, spec, chroma, resize, stream);
+}
+int sink_motion_regions(uint32_t n, const SinkTensorPic *pics, uint32_t n_regions, const SinkRegion *regions,
+                        const h264bsdmi_motion_spec *spec, void *stream)
+{
+    if (!n_regions) return 0;
+    if (!regions || !spec) return -1;
+    return sink_tensor_call(n, pics, n_regions, regions, nullptr, 0, nullptr, stream, spec);
+}
+/* JobSink.set_motion (h264bsdmiSetMotionExport): before the instance's first sequence is configured */
+int sink_set_motion(void *user, int on)
+{
+    SinkUser *u = static_cast<SinkUser *>(user);
+    std::lock_guard<std::mutex> lk(u->e->mu);
+    if (u->s->n_slots) return -1;
+    u->s->motion = on != 0;
+    return 0;
 }
 } // namespace
 
@@ -1352,6 +1503,8 @@ int eng_attach(JobSink *sink)
     sink->errors = sink_errors;
     sink->tensor_out = sink_tensor_out;
     sink->tensor_regions = sink_tensor_regions;
+    sink->motion_regions = sink_motion_regions;
+    sink->set_motion = sink_set_motion;
     return 0;
 }
 

@@ -218,6 +218,7 @@ typedef struct Dpb {
 /* ---------------------------------------------------------------- job sink (device boundary) */
 struct h264bsdmi_tensor_spec;
 struct h264bsdmi_resize_spec;
+struct h264bsdmi_motion_spec;
 struct JobSink;
 /* one picture of a batched tensor pull (JobSink.tensor_out): the frame buffer `slot` of the instance behind `sink`, its window
  * (x0, y0, w, h), and the picture's index in the output tensor */
@@ -273,6 +274,12 @@ typedef struct JobSink {
     int (*tensor_regions)(uint32_t n, const SinkTensorPic *pics, uint32_t n_regions, const SinkRegion *regions,
                           const struct h264bsdmi_tensor_spec *spec, uint32_t chroma, const struct h264bsdmi_resize_spec *resize,
                           void *stream);
+    /* optional: the same regions read from the motion side information kept beside the pictures, with one launch —
+     * h264bsdmiOutputMotionRegions (of pics[i] the sink, slot and window are used).  0 = ok; <0 = error, nothing enqueued */
+    int (*motion_regions)(uint32_t n, const SinkTensorPic *pics, uint32_t n_regions, const SinkRegion *regions,
+                          const struct h264bsdmi_motion_spec *spec, void *stream);
+    /* optional: keep the motion side information of this instance's pictures (h264bsdmiSetMotionExport).  0 = ok, <0: too late */
+    int (*set_motion)(void *user, int on);
 } JobSink;
 
 /* ---------------------------------------------------------------- decoder instance */

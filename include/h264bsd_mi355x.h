@@ -184,6 +184,59 @@ int h264bsdmiOutputTensorRegions(u32 n, storage_t *const *pStorage, u32 nRegions
                                  const h264bsdmi_resize_spec *resize, void *stream,
                                  u32 *got, u32 *box, u32 *current, u32 *picId);
 
+/* Motion-field tensors: the motion vectors the decoder resolved for a picture (P_Skip prediction included), resampled onto the
+ * grid of a tensor pull — for carrying boxes across pictures, gating inference on motion, flow-conditioned networks.
+ * Keep the motion side information of every picture of this instance beside its frame buffer (74 bytes per macroblock and frame
+ * buffer).  Call before the first h264bsdDecode() (like h264bsdmiSetCopyElision).  Off by default: nothing is kept and nothing is
+ * launched.  0 = ok, -1: capture mode, or the instance has decoded already. */
+int h264bsdmiSetMotionExport(storage_t *pStorage, u32 on);
+#define H264BSDMI_MOTION_NEAREST 0   /* the 4x4 block under the output pixel's centre */
+#define H264BSDMI_MOTION_AREA    1   /* area-weighted mean over the output pixel's footprint */
+#define H264BSDMI_MOTION_PLANE_MV    1u   /* 2 channels: dx, dy */
+#define H264BSDMI_MOTION_PLANE_VALID 2u   /* 1 channel */
+#define H264BSDMI_MOTION_PLANE_AGE   4u   /* 1 channel */
+#define H264BSDMI_MOTION_PLANE_QP    8u   /* 1 channel */
+#define H264BSDMI_MOTION_UNITS_SOURCE 0   /* luma samples of the source window */
+#define H264BSDMI_MOTION_UNITS_OUTPUT 1   /* pixels of the output rectangle: dx * iw / w, dy * ih / h */
+typedef struct h264bsdmi_motion_spec {
+    void *data;                 /* DEVICE pointer, caller-owned, dense: region r at data + r * C*H*W elements */
+    u32   width, height;        /* output size of every region */
+    u32   layout, dtype;        /* H264BSDMI_LAYOUT_*; H264BSDMI_DTYPE_F16 / F32 (U8: refused) */
+    u32   planes;               /* non-empty subset of H264BSDMI_MOTION_PLANE_*; channels in the order MV, VALID, AGE, QP */
+    u32   crop, fit;            /* as h264bsdmi_tensor_spec.crop; H264BSDMI_FIT_* */
+    u32   sampler, units;
+    u32   per_picture;          /* 1: dx, dy divided by max(age, 1): displacement per decoded picture */
+} h264bsdmi_motion_spec;
+/* The motion side information of the instances' CURRENT pictures (above), region by region as h264bsdmiOutputTensorRegions reads
+ * their pixels: the same region struct and limits, the same source window, the same rectangle arithmetic for FIT_LETTERBOX (on the
+ * box's w, h), the same got / box / current / picId, the same stream rule and fence; it pops nothing and may be repeated.  Slice r
+ * of a motion pull lies pixel for pixel over slice r of a region pull with the same regions, size, crop and fit.  regions == NULL
+ * with nRegions == n: region i is the whole window of instance i.  The side information is valid exactly as long as the pixels are.
+ * Per 4x4 luma block of the coded frame the decoder keeps: whether it is VALID — the block belongs to an inter macroblock (P_Skip
+ * included) or to a lost macroblock of a P picture concealed by copying, and its reference is a frame buffer of the sequence;
+ * intra, I_PCM, intra-concealed and undecoded macroblocks are invalid — its vector (mx, my) in quarter samples (0 when invalid, 0
+ * for a concealed macroblock): the block's samples were predicted from the reference picture displaced by (mx / 4, my / 4) luma
+ * samples, the direction as coded (negate for "where did it go"), dx = mx / 4, dy = my / 4; the AGE of its reference: the distance
+ * in decoding order to the picture predicted from, clamped to [0, 255], 0 when invalid or unknown (the reference was not decoded
+ * since the sequence began); and its macroblock's luma QP (valid or not).  Of a picture decoded from redundant slices, what the
+ * reference decoder ends up with.
+ * Values, for output pixel (i, j) of the inner rectangle (left, top, iw, ih) of a box (x, y, w, h) in a window W x H that starts at
+ * luma sample (x0, y0) of the coded frame; everything outside the inner rectangle is 0 in every plane:
+ * NEAREST, integers only: u = ((2 (i - left) + 1) w) / (2 iw), v likewise; window position (x + u, y + v); outside [0, W) x [0, H)
+ * all planes 0; else the block ((x0 + x + u) >> 2, (y0 + y + v) >> 2): VALID 1 / 0, MV its vector, AGE its age, QP its QP.
+ * AREA: the footprint [x + (i - left) w / iw, x + (i - left + 1) w / iw) x (the same in v), clipped to the window; a block weighs
+ * by the area it shares with the clipped footprint.  VALID = weight of the valid blocks / area of the UNCLIPPED footprint
+ * (w / iw) (h / ih); MV, AGE = weighted mean over the valid blocks (0 when there is none); QP = weighted mean over all blocks inside
+ * the window (0 when the footprint misses the window).  Edges, weights and sums in double, the mean rounded to fp32 once.
+ * Then per_picture (per block, before averaging: the fp32 vector component divided by max(age, 1)), then UNITS_OUTPUT (dx times
+ * (float) iw / (float) w, dy times (float) ih / (float) h, in fp32), then the dtype (F16: round to nearest even).  No mean / std.
+ * -1, before anything is enqueued: everything h264bsdmiOutputTensorRegions refuses in regions, instances and stream; an instance
+ * without motion export; data NULL, width or height 0, layout out of range, a dtype other than F16 / F32, planes 0 or with unknown
+ * bits, sampler, units, fit or per_picture out of range; regions == NULL with nRegions != n.  -2: the engine failed. */
+int h264bsdmiOutputMotionRegions(u32 n, storage_t *const *pStorage, u32 nRegions, const h264bsdmi_region *regions,
+                                 const h264bsdmi_motion_spec *spec, void *stream,
+                                 u32 *got, u32 *box, u32 *current, u32 *picId);
+
 /* ---- host parse pipeline at scale ----
  * h264bsdDecode() consumes one NAL unit of one stream per call; a caller that feeds hundreds of streams needs the
  * loop of posix/test_h264bsd.c:146-177 for each of them and its own threading.  These entry points move both into
