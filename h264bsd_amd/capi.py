@@ -28,7 +28,7 @@ EXPORTED_SYMBOLS = [
     "h264bsdCroppingParams", "h264bsdSampleAspectRatio", "h264bsdCheckValidParamSets", "h264bsdFlushBuffer",
     "h264bsdProfile", "h264bsdAlloc", "h264bsdFree", "h264bsdConvertToRGBA", "h264bsdConvertToBGRA",
     "h264bsdConvertToYCbCrA",
-    "h264bsdmiInitCapture", "h264bsdmiNextOutputInfo", "h264bsdmiNextOutputPictureDevice", "h264bsdmiNextOutputTensorBatch", "h264bsdmiNextOutputTensorBatchColour", "h264bsdmiNextOutputTensorBatchResize", "h264bsdmiOutputTensorRegions", "h264bsdmiSetMotionExport", "h264bsdmiOutputMotionRegions", "h264bsdmiJobFinalize", "h264bsdmiDeviceCount", "h264bsdmiSetDevice", "h264bsdmiFlush", "h264bsdmiFlushAsync", "h264bsdmiDeviceErrors",
+    "h264bsdmiInitCapture", "h264bsdmiNextOutputInfo", "h264bsdmiNextOutputPictureDevice", "h264bsdmiNextOutputTensorBatch", "h264bsdmiNextOutputTensorBatchColour", "h264bsdmiNextOutputTensorBatchResize", "h264bsdmiOutputTensorRegions", "h264bsdmiOutputTensorRemap", "h264bsdmiSetMotionExport", "h264bsdmiOutputMotionRegions", "h264bsdmiJobFinalize", "h264bsdmiDeviceCount", "h264bsdmiSetDevice", "h264bsdmiFlush", "h264bsdmiFlushAsync", "h264bsdmiDeviceErrors",
     "h264bsdmiDecodePicture", "h264bsdmiDecodePictureBatch", "h264bsdmiNextOutputPictureBatch", "h264bsdmiPullAndDecodePictureBatch", "h264bsdmiSetParserThreads", "h264bsdmiSetInputReadOnly", "h264bsdmiSetCopyElision",
     "h264bsdmiReplayCreate", "h264bsdmiReplayCreateStaggered", "h264bsdmiReplayCreateDesync", "h264bsdmiReplayCreateSched", "h264bsdmiReplayReschedule", "h264bsdmiReplayDestroy", "h264bsdmiReplayRun", "h264bsdmiReplaySync",
     "h264bsdmiReplayFetch", "h264bsdmiReplayChecksums", "h264bsdmiReplayConvert", "h264bsdmiReplayFetchConverted",
@@ -67,6 +67,16 @@ class Region(ctypes.Structure):
     _fields_ = [("instance", ctypes.c_uint32), ("x", ctypes.c_int), ("y", ctypes.c_int), ("w", ctypes.c_uint32), ("h", ctypes.c_uint32)]
 
 
+class Remap(ctypes.Structure):
+    """h264bsdmi_remap (include/h264bsd_mi355x.h)"""
+    _fields_ = [("instance", ctypes.c_uint32), ("map", ctypes.c_void_p)]
+
+
+class RemapSpec(ctypes.Structure):
+    """h264bsdmi_remap_spec (include/h264bsd_mi355x.h)"""
+    _fields_ = [("filter", ctypes.c_uint32), ("border", ctypes.c_uint32), ("pad", ctypes.c_float * 3)]
+
+
 class MotionSpec(ctypes.Structure):
     """h264bsdmi_motion_spec (include/h264bsd_mi355x.h)"""
     _fields_ = [("data", ctypes.c_void_p), ("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("layout", ctypes.c_uint32),
@@ -82,6 +92,8 @@ RANGES = {"auto": 0, "limited": 1, "full": 2}                                   
 CHROMA = {"nearest": 0, "bilinear": 1}                                                                 # H264BSDMI_CHROMA_*
 FILTERS = {("bilinear", False): 0, ("bilinear", True): 1, ("bicubic", True): 2}                           # H264BSDMI_FILTER_*
 FITS = {"stretch": 0, "letterbox": 1}                                                                   # H264BSDMI_FIT_*
+REMAP_FILTERS = {"nearest": 0, "bilinear": 1}                                                          # H264BSDMI_REMAP_*
+BORDERS = {"constant": 0, "replicate": 1}                                                              # H264BSDMI_BORDER_*
 LAYOUTS = {"NCHW": 0, "NHWC": 1}
 CHANNELS = {"RGB": (0, 3), "BGR": (1, 3), "RGBA": (2, 4), "BGRA": (3, 4), "Y": (4, 1)}     # name -> (H264BSDMI_CH_*, channels)
 
@@ -193,6 +205,9 @@ def _declare(L, harness):
     L.h264bsdmiOutputTensorRegions.argtypes = [u32, ctypes.POINTER(vp), u32, ctypes.POINTER(Region), ctypes.POINTER(TensorSpec),
                                                ctypes.POINTER(ColourSpec), ctypes.POINTER(ResizeSpec), vp, P32, P32, P32, P32]
     L.h264bsdmiOutputTensorRegions.restype = ctypes.c_int
+    L.h264bsdmiOutputTensorRemap.argtypes = [u32, ctypes.POINTER(vp), u32, ctypes.POINTER(Remap), ctypes.POINTER(TensorSpec),
+                                             ctypes.POINTER(ColourSpec), ctypes.POINTER(RemapSpec), vp, P32, P32, P32]
+    L.h264bsdmiOutputTensorRemap.restype = ctypes.c_int
     L.h264bsdmiSetMotionExport.argtypes = [vp, u32]
     L.h264bsdmiSetMotionExport.restype = ctypes.c_int
     L.h264bsdmiOutputMotionRegions.argtypes = [u32, ctypes.POINTER(vp), u32, ctypes.POINTER(Region), ctypes.POINTER(MotionSpec), vp,
@@ -628,6 +643,89 @@ def pull_regions(decoders, regions, size, layout="NCHW", dtype=None, channels="R
     if rc != 0:
         raise RuntimeError(f"h264bsdmiOutputTensorRegions failed ({rc})")
     return (out, list(got)[:K], [tuple(box[4 * k: 4 * k + 4]) if got[k] else None for k in range(K)], list(cur)[:n], list(ids)[:n])
+
+
+def pull_remap(decoders, maps, instances=None, layout="NCHW", dtype=None, channels="RGB", mean=(0, 0, 0), std=(1, 1, 1), crop=True,
+               out=None, stream=None, colour="reference", colour_range="auto", chroma="nearest", unspecified="bt601",
+               mode="bilinear", border="constant", pad=(0.0, 0.0, 0.0), pop=False):
+    """h264bsdmiOutputTensorRemap: the decoders' CURRENT pictures (as for pull_regions) sampled through coordinate maps by one kernel
+    launch into ONE dense CUDA tensor [R, C, H, W] or [R, H, W, C].  maps: a contiguous float32 CUDA tensor [R, H, W, 2], or a list
+    of R contiguous float32 CUDA tensors [H, W, 2] (a tensor may repeat: one calibration for many pictures); maps[r][i, j] = (x, y),
+    the position in luma samples of the decoder's source window (the SPS cropping window when crop, else the coded frame) that
+    output pixel (i, j) of slice r is taken from, sample (u, v) AT (u, v): cv2.remap's convention; from a normalised
+    grid_sample(align_corners=True) grid, x = (gx + 1) (W_src - 1) / 2 and y = (gy + 1) (H_src - 1) / 2.  The maps are read on
+    `stream`: what writes them must be ordered before it.  Nothing is copied or converted: other maps raise ValueError.
+    instances[r]: the index of the decoder map r samples (default range(R) when R == len(decoders)).  mode "bilinear" or "nearest";
+    border "constant" (pad[c] outside the window, in [0, 1] before mean / std) or "replicate"; a non-finite coordinate gives the pad
+    in both.  There is no antialiasing.  pop=True first pops every decoder's next picture (h264bsdmiNextOutputInfo), so that it is
+    the current one: undistortion as the first stage.  Every other argument as pull_tensor.  Returns (tensor, got, current, pic_ids):
+    got[r] = 1 when slice r was written (0: its decoder has no current picture, the slice is untouched), current[i] / pic_ids[i]
+    per decoder."""
+    import torch
+    n = len(decoders)
+    if mode not in REMAP_FILTERS or border not in BORDERS:
+        raise ValueError(f"pull_remap: unsupported mode / border {mode} {border}")
+    if isinstance(maps, torch.Tensor):
+        if maps.dim() != 4:
+            raise ValueError("pull_remap: maps must be a [R, H, W, 2] tensor or a list of [H, W, 2] tensors")
+        whole, maps = maps, [maps[r] for r in range(maps.shape[0])]
+    else:
+        whole, maps = None, list(maps)
+    R = len(maps)
+    if R > 65535:
+        raise ValueError("pull_remap: at most 65535 maps per call")
+    for t in maps if whole is None else [whole]:
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.shape[-1] != 2 or \
+                t.dim() != (3 if whole is None else 4):
+            raise ValueError("pull_remap: a map must be a contiguous float32 CUDA tensor [H, W, 2]; nothing is converted or copied")
+    if R and any(tuple(t.shape) != tuple(maps[0].shape) or t.device != maps[0].device for t in maps):
+        raise ValueError("pull_remap: every map must have the same [H, W, 2] shape and device")
+    if R and any(t.data_ptr() % 8 for t in maps):
+        raise ValueError("pull_remap: a map must be 8-byte aligned")
+    if instances is None:
+        if R != n:
+            raise ValueError("pull_remap: instances is required unless there is one map per decoder")
+        instances = range(n)
+    instances = list(instances)
+    if len(instances) != R or not all(isinstance(i, int) and 0 <= i < n for i in instances):
+        raise ValueError("pull_remap: instances must name one decoder of the call per map")
+    if not R:
+        raise ValueError("pull_remap: no maps")
+    size = (int(maps[0].shape[0]), int(maps[0].shape[1]))
+    if not size[0] or not size[1]:
+        raise ValueError("pull_remap: empty maps")
+    out, spec, cs, _, stream = _tensor_call("pull_remap", R, decoders, size, layout, dtype, channels, mean, std, crop, out, stream, colour,
+                                            colour_range, chroma, unspecified, "bilinear", False, "stretch", pad)
+    if out.device != maps[0].device:
+        raise ValueError("pull_remap: the maps and out must be on the same device")
+    rs = RemapSpec(REMAP_FILTERS[mode], BORDERS[border], (ctypes.c_float * 3)(*[float(p) for p in pad]))
+    if pop:
+        for d in decoders:
+            d.next_output_info()
+    L = api_lib()
+    got = (ctypes.c_uint32 * R)()
+    cur, ids = (ctypes.c_uint32 * max(n, 1))(), (ctypes.c_uint32 * max(n, 1))()
+    rc = L.h264bsdmiOutputTensorRemap(n, (ctypes.c_void_p * max(n, 1))(*[d._st for d in decoders]), R,
+                                      (Remap * R)(*[Remap(i, t.data_ptr()) for i, t in zip(instances, maps)]), ctypes.byref(spec),
+                                      ctypes.byref(cs), ctypes.byref(rs), stream.cuda_stream, got, cur, ids)
+    if rc != 0:
+        raise RuntimeError(f"h264bsdmiOutputTensorRemap failed ({rc})")
+    return out, list(got), list(cur)[:n], list(ids)[:n]
+
+
+def affine_maps(theta, size, device="cuda"):
+    """Maps for pull_remap from affine transforms: theta [R, 2, 3] (anything torch.as_tensor takes), size (H, W) or an int; output
+    pixel (i, j) of map r is taken from theta[r] @ (j, i, 1) = (x, y) in luma samples of the source window.  Built in float64, then
+    rounded to float32 once.  Returns a contiguous float32 tensor [R, H, W, 2] on `device`."""
+    import torch
+    H, W = (size, size) if isinstance(size, int) else (int(size[0]), int(size[1]))
+    theta = torch.as_tensor(theta, dtype=torch.float64, device="cpu")
+    if theta.dim() != 3 or tuple(theta.shape[1:]) != (2, 3) or H < 1 or W < 1:
+        raise ValueError("affine_maps: theta must be [R, 2, 3] and the size positive")
+    i, j = torch.meshgrid(torch.arange(H, dtype=torch.float64), torch.arange(W, dtype=torch.float64), indexing="ij")
+    base = torch.stack([j, i, torch.ones_like(i)], dim=-1)                # [H, W, 3]
+    maps = torch.einsum("rkc,hwc->rhwk", theta, base)                     # [R, H, W, 2]
+    return maps.to(torch.float32).contiguous().to(device)
 
 
 def pull_motion(decoders, regions=None, size=None, layout="NCHW", dtype=None, planes=("mv", "valid"), crop=True, fit="stretch",

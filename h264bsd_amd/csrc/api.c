@@ -11,6 +11,7 @@
 #include <pthread.h>
 #include <sched.h>
 #include <stdatomic.h>
+#include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -348,6 +349,40 @@ int h264bsdmiNextOutputTensorBatchResize(u32 n, storage_t *const *dec, const h26
     return 0;
 }
 
+/* What the pulls of CURRENT pictures share (h264bsdmiOutputTensorRegions, h264bsdmiOutputTensorRemap, h264bsdmiOutputMotionRegions).
+ * current_instances_refused: 1 when an instance is no decoder of this library, is in capture mode (it has no pixels: `remap`
+ * chooses the sink entry the call needs) or is repeated. */
+static int current_instances_refused(u32 n, storage_t *const *dec, int remap)
+{
+    for (u32 i = 0; i < n; i++) {
+        const ApiDec *a = dec_of(dec[i]);
+        if (!a || !(remap ? a->hd->sink.tensor_remap != NULL : a->hd->sink.tensor_regions != NULL)) return 1;
+        for (u32 k = 0; k < i; k++)
+            if (dec[k] == dec[i]) return 1;
+    }
+    return 0;
+}
+/* the index in pics[0 .. *m) of instance inst's current picture (a: the instance, which has one), appended at its first use */
+static u32 current_pic(SinkTensorPic *pics, u32 *m, u32 *pic_of, const ApiDec *a, u32 inst, const h264bsdmi_tensor_spec *spec,
+                       const h264bsdmi_colour_spec *colour)
+{
+    if (pic_of[inst] == 0xFFFFFFFFu) {
+        pic_of[inst] = *m;
+        tensor_pic(&pics[(*m)++], a, a->cur.slot, inst, spec, colour);
+    }
+    return pic_of[inst];
+}
+/* current[i] / picId[i] (each may be NULL) of every instance */
+static void report_current(u32 n, storage_t *const *dec, u32 *current, u32 *picId)
+{
+    for (u32 i = 0; i < n; i++) {
+        const ApiDec *a = dec_of(dec[i]);
+        const int cur = a->has_cur && a->hd->active_sps;
+        if (current) current[i] = cur ? 1 : 0;
+        if (picId) picId[i] = cur ? a->cur.pic_id : 0;
+    }
+}
+
 /* Boxes of the instances' current pictures (pop_output, drop_current), each into its own slice.  Specs and regions are checked
  * before the instances are looked at; nothing is popped. */
 int h264bsdmiOutputTensorRegions(u32 n, storage_t *const *dec, u32 nRegions, const h264bsdmi_region *regions,
@@ -367,12 +402,7 @@ int h264bsdmiOutputTensorRegions(u32 n, storage_t *const *dec, u32 nRegions, con
     }
     if (n && !dec) return -1;
     if (!resize) resize = &stretch;
-    for (u32 i = 0; i < n; i++) {
-        const ApiDec *a = dec_of(dec[i]);
-        if (!a || !a->hd->sink.tensor_regions) return -1;                   /* capture mode: there are no pixels */
-        for (u32 k = 0; k < i; k++)
-            if (dec[k] == dec[i]) return -1;
-    }
+    if (current_instances_refused(n, dec, 0)) return -1;
     /* one SinkTensorPic per instance that has a current picture and at least one region */
     SinkTensorPic *pics = (SinkTensorPic *)malloc((n ? n : 1) * sizeof(SinkTensorPic));
     SinkRegion *regs = (SinkRegion *)malloc((nRegions ? nRegions : 1) * sizeof(SinkRegion));
@@ -384,12 +414,8 @@ int h264bsdmiOutputTensorRegions(u32 n, storage_t *const *dec, u32 nRegions, con
         const h264bsdmi_region *g = &regions[r];
         const ApiDec *a = dec_of(dec[g->instance]);
         if (!a->has_cur || !a->hd->active_sps) continue;                     /* got[r] = 0 */
-        if (pic_of[g->instance] == 0xFFFFFFFFu) {
-            pic_of[g->instance] = m;
-            tensor_pic(&pics[m++], a, a->cur.slot, g->instance, spec, colour);
-        }
         SinkRegion *q = &regs[k++];
-        *q = (SinkRegion){ pic_of[g->instance], r, g->x, g->y, g->w, g->h, { 0, 0, spec->width, spec->height } };
+        *q = (SinkRegion){ current_pic(pics, &m, pic_of, a, g->instance, spec, colour), r, g->x, g->y, g->w, g->h, { 0, 0, spec->width, spec->height } };
         if (resize->fit == H264BSDMI_FIT_LETTERBOX) letterbox(spec->width, spec->height, g->w, g->h, q->box);
     }
     int rc = 0;
@@ -401,15 +427,55 @@ int h264bsdmiOutputTensorRegions(u32 n, storage_t *const *dec, u32 nRegions, con
             got[regs[j].index] = 1;
             if (box) memcpy(box + 4 * regs[j].index, regs[j].box, sizeof(regs[j].box));
         }
-        for (u32 i = 0; i < n; i++) {
-            const ApiDec *a = dec_of(dec[i]);
-            const int cur = a->has_cur && a->hd->active_sps;
-            if (current) current[i] = cur ? 1 : 0;
-            if (picId) picId[i] = cur ? a->cur.pic_id : 0;
-        }
+        report_current(n, dec, current, picId);
     }
     free(pics);
     free(regs);
+    free(pic_of);
+    return rc;
+}
+
+/* The instances' current pictures through coordinate maps, each map into its own slice: h264bsdmiOutputTensorRegions' checks of
+ * spec, colour and instances in the same order, with the maps in the place of the regions; nothing is popped. */
+int h264bsdmiOutputTensorRemap(u32 n, storage_t *const *dec, u32 nMaps, const h264bsdmi_remap *maps,
+                               const h264bsdmi_tensor_spec *spec, const h264bsdmi_colour_spec *colour,
+                               const h264bsdmi_remap_spec *remap, void *stream,
+                               u32 *got, u32 *current, u32 *picId)
+{
+    static const h264bsdmi_remap_spec plain = { H264BSDMI_REMAP_BILINEAR, H264BSDMI_BORDER_CONSTANT, { 0.0f, 0.0f, 0.0f } };
+    if (tensor_specs_refused(spec, &colour, NULL) || spec->resize != 1) return -1;
+    if (!remap) remap = &plain;
+    if (remap->filter > H264BSDMI_REMAP_BILINEAR || remap->border > H264BSDMI_BORDER_REPLICATE) return -1;
+    for (int c = 0; c < 3; c++)
+        if (!(remap->pad[c] >= 0.0f && remap->pad[c] <= 1.0f)) return -1;      /* NaN and the infinities too */
+    if (nMaps && (!maps || !got)) return -1;
+    if (nMaps > 65535u) return -1;
+    for (u32 r = 0; r < nMaps; r++)
+        if (maps[r].instance >= n || !maps[r].map || ((uintptr_t)maps[r].map & 7u)) return -1;
+    if (n && !dec) return -1;
+    if (current_instances_refused(n, dec, 1)) return -1;
+    /* one SinkTensorPic per instance that has a current picture and at least one map */
+    SinkTensorPic *pics = (SinkTensorPic *)malloc((n ? n : 1) * sizeof(SinkTensorPic));
+    SinkRemap *sm = (SinkRemap *)malloc((nMaps ? nMaps : 1) * sizeof(SinkRemap));
+    u32 *pic_of = (u32 *)malloc((n ? n : 1) * sizeof(u32));
+    if (!pics || !sm || !pic_of) { free(pics); free(sm); free(pic_of); return -1; }
+    u32 m = 0, k = 0;
+    for (u32 i = 0; i < n; i++) pic_of[i] = 0xFFFFFFFFu;
+    for (u32 r = 0; r < nMaps; r++) {
+        const ApiDec *a = dec_of(dec[maps[r].instance]);
+        if (!a->has_cur || !a->hd->active_sps) continue;                     /* got[r] = 0 */
+        const u32 pic = current_pic(pics, &m, pic_of, a, maps[r].instance, spec, colour);
+        sm[k++] = (SinkRemap){ pic, r, maps[r].map };
+    }
+    int rc = 0;
+    if (k && pics[0].sink->tensor_remap(m, pics, k, sm, spec, colour->chroma, remap, stream)) rc = -2;
+    if (!rc) {
+        for (u32 r = 0; r < nMaps; r++) got[r] = 0;
+        for (u32 j = 0; j < k; j++) got[sm[j].index] = 1;
+        report_current(n, dec, current, picId);
+    }
+    free(pics);
+    free(sm);
     free(pic_of);
     return rc;
 }
@@ -452,11 +518,7 @@ int h264bsdmiOutputMotionRegions(u32 n, storage_t *const *dec, u32 nRegions, con
         const u32 inst = regions ? regions[r].instance : r;
         const ApiDec *a = dec_of(dec[inst]);
         if (!a->has_cur || !a->hd->active_sps) continue;                     /* got[r] = 0 */
-        if (pic_of[inst] == 0xFFFFFFFFu) {
-            pic_of[inst] = m;
-            tensor_pic(&pics[m++], a, a->cur.slot, inst, &window, &reference);
-        }
-        const SinkTensorPic *p = &pics[pic_of[inst]];
+        const SinkTensorPic *p = &pics[current_pic(pics, &m, pic_of, a, inst, &window, &reference)];
         SinkRegion *q = &regs[k++];
         if (regions) *q = (SinkRegion){ pic_of[inst], r, regions[r].x, regions[r].y, regions[r].w, regions[r].h, { 0, 0, spec->width, spec->height } };
         else *q = (SinkRegion){ pic_of[inst], r, 0, 0, p->w, p->h, { 0, 0, spec->width, spec->height } };      /* the whole window */
@@ -471,12 +533,7 @@ int h264bsdmiOutputMotionRegions(u32 n, storage_t *const *dec, u32 nRegions, con
             got[regs[j].index] = 1;
             if (box) memcpy(box + 4 * regs[j].index, regs[j].box, sizeof(regs[j].box));
         }
-        for (u32 i = 0; i < n; i++) {
-            const ApiDec *a = dec_of(dec[i]);
-            const int cur = a->has_cur && a->hd->active_sps;
-            if (current) current[i] = cur ? 1 : 0;
-            if (picId) picId[i] = cur ? a->cur.pic_id : 0;
-        }
+        report_current(n, dec, current, picId);
     }
     free(pics);
     free(regs);

@@ -34,6 +34,7 @@
 #include "kernels/k_tensor_out.hip.h"
 #include "kernels/k_tensor_aa.hip.h"
 #include "kernels/k_tensor_roi.hip.h"
+#include "kernels/k_tensor_remap.hip.h"
 #include "kernels/k_motion.hip.h"
 #include "engine.h"
 #include "hip_owned.h"
@@ -1128,10 +1129,12 @@ void sink_close(void *user)
 /* ---- the next pictures of many instances into one caller-owned tensor (h264bsdmiNextOutputTensorBatch[Colour|Resize]) ---- */
 /* one kernel per dtype, layout, number of channels and REF; the channel order and the whole colour transform are in the items
  * (colour_item) */
-/* (k_tensor_aa: one more family on the same four parameters, filter and fit at run time; k_tensor_roi: the same for regions) */
-enum { TK_OUT, TK_RESIZE, TK_AA, TK_ROI };
+/* (k_tensor_aa: one more family on the same four parameters, filter and fit at run time; k_tensor_roi: the same for regions;
+ * k_tensor_remap: the same for coordinate maps, filter and border at run time) */
+enum { TK_OUT, TK_RESIZE, TK_AA, TK_ROI, TK_REMAP };
 template <int DT, int L, int C> static const void *tensor_kernel_of(int kind, bool ref)
 {
+    if (kind == TK_REMAP) return ref ? reinterpret_cast<const void *>(&h264k::k_tensor_remap<DT, L, C, true>) : reinterpret_cast<const void *>(&h264k::k_tensor_remap<DT, L, C, false>);
     if (kind == TK_ROI) return ref ? reinterpret_cast<const void *>(&h264k::k_tensor_roi<DT, L, C, true>) : reinterpret_cast<const void *>(&h264k::k_tensor_roi<DT, L, C, false>);
     if (kind == TK_AA) return ref ? reinterpret_cast<const void *>(&h264k::k_tensor_aa<DT, L, C, true>) : reinterpret_cast<const void *>(&h264k::k_tensor_aa<DT, L, C, false>);
     const bool resize = kind == TK_RESIZE;
@@ -1151,9 +1154,9 @@ template <int DT> static const void *tensor_kernel_dt(int kind, bool ref, uint32
     }
     return nullptr;
 }
-static const void *tensor_kernel(const h264bsdmi_tensor_spec &t, bool aa, bool ref, bool roi = false)
+static const void *tensor_kernel(const h264bsdmi_tensor_spec &t, bool aa, bool ref, bool roi = false, bool remap = false)
 {
-    const int kind = roi ? TK_ROI : aa ? TK_AA : t.resize ? TK_RESIZE : TK_OUT;
+    const int kind = remap ? TK_REMAP : roi ? TK_ROI : aa ? TK_AA : t.resize ? TK_RESIZE : TK_OUT;
     switch (t.dtype) {
     case h264k::TO_U8: return tensor_kernel_dt<h264k::TO_U8>(kind, ref, t.layout, t.channels);
     case h264k::TO_F16: return tensor_kernel_dt<h264k::TO_F16>(kind, ref, t.layout, t.channels);
@@ -1161,8 +1164,10 @@ static const void *tensor_kernel(const h264bsdmi_tensor_spec &t, bool aa, bool r
     }
     return nullptr;
 }
-/* the staging ring's item stride: k_tensor_out / k_tensor_resize read TensorItems, k_tensor_aa AaItems, k_tensor_roi RoiItems */
-constexpr size_t TITEM_BYTES = std::max({ sizeof(h264k::TensorItem), sizeof(h264k::AaItem), sizeof(h264k::RoiItem), sizeof(h264k::MotionItem) });
+/* the staging ring's item stride: k_tensor_out / k_tensor_resize read TensorItems, k_tensor_aa AaItems, k_tensor_roi RoiItems,
+ * k_motion_roi MotionItems, k_tensor_remap RemapItems */
+constexpr size_t TITEM_BYTES = std::max({ sizeof(h264k::TensorItem), sizeof(h264k::AaItem), sizeof(h264k::RoiItem), sizeof(h264k::MotionItem),
+                                          sizeof(h264k::RemapItem) });
 
 /* The colour map of one picture's item (matrix, range): per output channel c the affine map of the 8-bit (Y, Cb - 128, Cr - 128) to
  * the value written, and the clamp bounds of [0, 1] under the output scale (U8: 255 v; floats: (v - mean[c]) / std[c]), folded in
@@ -1204,7 +1209,7 @@ static void colour_item(h264k::TensorItem &it, const h264bsdmi_tensor_spec &t, u
     }
 }
 
-/* The three steps every pull shares (tensor_out_locked, motion_out_locked), under the engine's mutex.
+/* The three steps every pull shares (tensor_out_locked, motion_out_locked, remap_out_locked), under the engine's mutex.
  * pull_begin_locked: the instances' queued jobs are enqueued, once for the batch; half e->titem_flip of the item staging is made
  * large enough for n_items and free (the launch before the last one read it). */
 static int pull_begin_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, uint32_t n_items)
@@ -1417,11 +1422,68 @@ static int motion_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, u
     return pull_end_locked(e, n, pics, st, fence_ev);
 }
 
-/* JobSink.tensor_out (h264bsdmiNextOutputTensorBatch[Colour|Resize]), JobSink.tensor_regions (regions != nullptr) and
- * JobSink.motion_regions (motion != nullptr: spec, chroma and resize are not used) */
+/* h264bsdmiOutputTensorRemap, under the engine's mutex: the current pictures of the n instances sampled through n_maps coordinate
+ * maps by one k_tensor_remap launch, map r into slice maps[r].index.  The ordering of tensor_out_locked's regions: the instances'
+ * queued jobs are enqueued, st waits for the ticks that made the pictures, and one fence behind the launch goes to each distinct
+ * instance, so that the next picture decoded into one of these slots waits for this launch.  The maps are the caller's: read on st. */
+static int remap_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, uint32_t n_maps, const SinkRemap *maps,
+                            const h264bsdmi_tensor_spec &t, uint32_t chroma, const h264bsdmi_remap_spec &rm, hipStream_t st,
+                            hipEvent_t *fence_ev)
+{
+    const bool ref = pics[0].matrix == H264BSDMI_MATRIX_REFERENCE;      /* one kernel: every picture of the call, or none */
+    if (!t.resize || rm.filter > H264BSDMI_REMAP_BILINEAR || rm.border > H264BSDMI_BORDER_REPLICATE) return -1;
+    const void *fn = tensor_kernel(t, false, ref, false, true);
+    if (!fn) return -1;
+    if (!n_maps || n_maps > 65535u) return -1;                          /* grid.y */
+    for (uint32_t i = 0; i < n; i++) {
+        const StreamCtx *s = static_cast<SinkUser *>(pics[i].sink->user)->s;
+        const SinkTensorPic &p = pics[i];
+        if (p.slot >= s->n_slots || !s->d_frames || !p.w || !p.h || p.x0 + p.w > s->wmb * 16 || p.y0 + p.h > s->hmb * 16) return -1;
+        if ((p.matrix == H264BSDMI_MATRIX_REFERENCE) != ref || (!ref && (p.matrix < H264BSDMI_MATRIX_BT601 || p.matrix > H264BSDMI_MATRIX_SMPTE240)))
+            return -1;
+        if ((p.x0 | p.y0 | p.w | p.h) & 1u) return -1;
+    }
+    for (uint32_t r = 0; r < n_maps; r++)
+        if (maps[r].pic >= n || !maps[r].map || (reinterpret_cast<uintptr_t>(maps[r].map) & 7u)) return -1;
+    if (pull_begin_locked(e, n, pics, n_maps)) return -1;
+    const size_t half = (size_t)e->titem_flip * e->titem_cap * TITEM_BYTES;
+    h264k::RemapItem *items = reinterpret_cast<h264k::RemapItem *>(e->h_titems + half);
+    const size_t C = t.channels == h264k::TO_Y ? 1 : t.channels >= h264k::TO_RGBA ? 4 : 3;
+    const size_t pic_bytes = C * t.width * t.height * (t.dtype == h264k::TO_U8 ? 1 : t.dtype == h264k::TO_F16 ? 2 : 4);
+    /* the colour map once per picture, then one item per map */
+    std::vector<h264k::TensorItem> of_pic(n);
+    for (uint32_t i = 0; i < n; i++) {
+        const StreamCtx *s = static_cast<SinkUser *>(pics[i].sink->user)->s;
+        const SinkTensorPic &p = pics[i];
+        of_pic[i] = h264k::TensorItem{ s->d_frames + (size_t)p.slot * s->frame_bytes, nullptr, s->wmb, p.x0, p.y0, p.w, p.h, 0u };
+        colour_item(of_pic[i], t, p.matrix, p.range);
+    }
+    for (uint32_t r = 0; r < n_maps; r++) {
+        items[r] = h264k::RemapItem{ of_pic[maps[r].pic], static_cast<const float *>(maps[r].map) };
+        items[r].t.dst = static_cast<uint8_t *>(t.data) + maps[r].index * pic_bytes;
+    }
+    if (pull_wait_pictures(e, n, pics, st)) return -1;
+    /* pad and spad as for k_tensor_roi: a non-finite coordinate under the output scale, outside the window under the samples' */
+    h264k::RemapArgs rargs{ reinterpret_cast<const h264k::RemapItem *>(e->h_titems.dev() + half), t.width, t.height, chroma, rm.filter, rm.border,
+                            { t.mean[0], t.mean[1], t.mean[2] }, { t.std[0], t.std[1], t.std[2] }, { 0, 0, 0 }, { 0, 0, 0 } };
+    for (int c = 0; c < 3; c++) {
+        const double q = std::floor(255.0 * rm.pad[c] + 0.5), nrm = ((double)rm.pad[c] - t.mean[c]) / t.std[c];
+        rargs.pad[c] = t.dtype == h264k::TO_U8 ? (float)q : (float)nrm;
+        rargs.spad[c] = ref ? (float)q : t.dtype == h264k::TO_U8 ? (float)(255.0 * rm.pad[c]) : (float)nrm;
+    }
+    const uint32_t blocks = (t.width + h264k::TRM_COLS - 1u) / h264k::TRM_COLS * ((t.height + h264k::TRM_ROWS - 1u) / h264k::TRM_ROWS);
+    void *args[] = { &rargs };
+    HIP_TRY(hipLaunchKernel(fn, dim3(std::min(blocks, 1024u), n_maps), dim3(256), args, 0, st));
+    return pull_end_locked(e, n, pics, st, fence_ev);
+}
+
+/* JobSink.tensor_out (h264bsdmiNextOutputTensorBatch[Colour|Resize]), JobSink.tensor_regions (regions != nullptr),
+ * JobSink.motion_regions (motion != nullptr: spec, chroma and resize are not used) and JobSink.tensor_remap (rmaps != nullptr: n_regions
+ * counts the maps) */
 static int sink_tensor_call(uint32_t n, const SinkTensorPic *pics, uint32_t n_regions, const SinkRegion *regions,
                             const h264bsdmi_tensor_spec *spec, uint32_t chroma, const h264bsdmi_resize_spec *resize, void *stream,
-                            const h264bsdmi_motion_spec *motion = nullptr)
+                            const h264bsdmi_motion_spec *motion = nullptr, const SinkRemap *rmaps = nullptr,
+                            const h264bsdmi_remap_spec *remap = nullptr)
 {
     if (!n) return 0;
     if (!pics || (!spec && !motion)) return -1;
@@ -1438,7 +1500,8 @@ static int sink_tensor_call(uint32_t n, const SinkTensorPic *pics, uint32_t n_re
             HIP_TRY(hipStreamIsCapturing(st, &cs));
             if (cs != hipStreamCaptureStatusNone) return -1;                      /* graph capture of this call is not supported */
         }
-        if (motion ? motion_out_locked(e, n, pics, n_regions, regions, *motion, st, &fence_ev)
+        if (rmaps ? remap_out_locked(e, n, pics, n_regions, rmaps, *spec, chroma, *remap, st, &fence_ev)
+            : motion ? motion_out_locked(e, n, pics, n_regions, regions, *motion, st, &fence_ev)
                    : tensor_out_locked(e, n, pics, n_regions, regions, *spec, chroma, resize, st, &fence_ev)) return -1;
     }
     if (stream) return 0;
@@ -1465,6 +1528,13 @@ int sink_motion_regions(uint32_t n, const SinkTensorPic *pics, uint32_t n_region
     if (!n_regions) return 0;
     if (!regions || !spec) return -1;
     return sink_tensor_call(n, pics, n_regions, regions, nullptr, 0, nullptr, stream, spec);
+}
+int sink_tensor_remap(uint32_t n, const SinkTensorPic *pics, uint32_t n_maps, const SinkRemap *maps,
+                      const h264bsdmi_tensor_spec *spec, uint32_t chroma, const h264bsdmi_remap_spec *remap, void *stream)
+{
+    if (!n_maps) return 0;
+    if (!maps || !spec || !remap) return -1;
+    return sink_tensor_call(n, pics, n_maps, nullptr, spec, chroma, nullptr, stream, nullptr, maps, remap);
 }
 /* JobSink.set_motion (h264bsdmiSetMotionExport): before the instance's first sequence is configured */
 int sink_set_motion(void *user, int on)
@@ -1504,6 +1574,7 @@ int eng_attach(JobSink *sink)
     sink->tensor_out = sink_tensor_out;
     sink->tensor_regions = sink_tensor_regions;
     sink->motion_regions = sink_motion_regions;
+    sink->tensor_remap = sink_tensor_remap;
     sink->set_motion = sink_set_motion;
     return 0;
 }

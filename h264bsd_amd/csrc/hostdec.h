@@ -219,6 +219,7 @@ typedef struct Dpb {
 struct h264bsdmi_tensor_spec;
 struct h264bsdmi_resize_spec;
 struct h264bsdmi_motion_spec;
+struct h264bsdmi_remap_spec;
 struct JobSink;
 /* one picture of a batched tensor pull (JobSink.tensor_out): the frame buffer `slot` of the instance behind `sink`, its window
  * (x0, y0, w, h), and the picture's index in the output tensor */
@@ -235,6 +236,12 @@ typedef struct SinkRegion {
     uint32_t w, h;
     uint32_t box[4];            /* left, top, width, height */
 } SinkRegion;
+/* one map of h264bsdmiOutputTensorRemap (JobSink.tensor_remap): the DEVICE coordinate map through which pics[pic] is sampled into
+ * slice `index` of the output tensor */
+typedef struct SinkRemap {
+    uint32_t pic, index;
+    const void *map;
+} SinkRemap;
 typedef struct JobSink {
     void *user;
     /* (re)configure for a sequence: n_slots frames of frame_bytes each. 0 = ok */
@@ -278,6 +285,12 @@ typedef struct JobSink {
      * h264bsdmiOutputMotionRegions (of pics[i] the sink, slot and window are used).  0 = ok; <0 = error, nothing enqueued */
     int (*motion_regions)(uint32_t n, const SinkTensorPic *pics, uint32_t n_regions, const SinkRegion *regions,
                           const struct h264bsdmi_motion_spec *spec, void *stream);
+    /* optional: the n pictures (as for tensor_regions) sampled through n_maps coordinate maps, float32 [height][width][2] in device
+     * memory, read on `stream`, with one launch — h264bsdmiOutputTensorRemap.  remap: filter, border and pad (never NULL).  0 = ok;
+     * <0 = error, nothing enqueued */
+    int (*tensor_remap)(uint32_t n, const SinkTensorPic *pics, uint32_t n_maps, const SinkRemap *maps,
+                        const struct h264bsdmi_tensor_spec *spec, uint32_t chroma, const struct h264bsdmi_remap_spec *remap,
+                        void *stream);
     /* optional: keep the motion side information of this instance's pictures (h264bsdmiSetMotionExport).  0 = ok, <0: too late */
     int (*set_motion)(void *user, int on);
 } JobSink;

@@ -184,6 +184,48 @@ int h264bsdmiOutputTensorRegions(u32 n, storage_t *const *pStorage, u32 nRegions
                                  const h264bsdmi_resize_spec *resize, void *stream,
                                  u32 *got, u32 *box, u32 *current, u32 *picId);
 
+/* Remapped pulls: the CURRENT pictures (above) sampled through caller-supplied coordinate maps, map r into slice r of one tensor,
+ * with one launch — lens undistortion (what cv2.initUndistortRectifyMap produces and cv2.remap consumes), rotated and
+ * perspective-rectified crops, polar unwrapping: everything that is "output pixel (i, j) comes from source position (x, y)".  A
+ * sibling of h264bsdmiOutputTensorRegions: the same current-picture rule and lifetime, the same got (per MAP) / current / picId
+ * (per instance), the same stream rule and fence (one per distinct instance), the same colour handling (NULL / REFERENCE: the
+ * reference's 8-bit values; otherwise the unquantised colour, bilinear chroma clamped to the window) and the same spec (layout,
+ * dtype, channels, mean / std, crop; spec->resize must be 1).  It pops nothing and may be repeated.  remap == NULL is
+ * {REMAP_BILINEAR, BORDER_CONSTANT, pad 0}.
+ * maps[r].map is a DEVICE pointer to float32 [spec->height][spec->width][2], dense, x then y, 8-byte aligned.  The kernel reads
+ * it on `stream`: it must be complete on that stream and stay valid until the kernel has run.  Several entries may name the same
+ * map (one calibration for many pictures) or the same instance.  (mx, my) is a position in luma samples of the source window of
+ * instance maps[r].instance (the SPS cropping window when spec->crop, else the coded frame), W x H; sample (u, v) sits AT (u, v):
+ * cv2.remap's convention, and grid_sample(align_corners=True)'s after de-normalising, x = (gx + 1) (W - 1) / 2.
+ * S(u, v), u, v integers: inside the window what a pull of the whole window interpolates there (as for a region); outside the pad
+ * under the scale of the converted samples (REFERENCE floor(255 pad[c] + 0.5), otherwise pad[c]).
+ * A non-finite mx or my gives the pad under the OUTPUT's scale (as the letterbox border is written) whatever the border mode; no
+ * address is formed.  Otherwise, in fp32: BORDER_CONSTANT cx = min(max(mx, -1), W), BORDER_REPLICATE cx = min(max(mx, 0), W - 1);
+ * cy likewise with H.
+ * REMAP_BILINEAR: x0 = floor(cx), lx = cx - x0 (exact in fp32 for cx >= 0; for -1 < cx < 0 rounded to nearest, at most 2^-25
+ * off), y0, ly likewise; the neighbours are (x0 | x0 + 1, y0 | y0 + 1);
+ * one outside the window is the pad (CONSTANT; with REPLICATE such a neighbour only ever carries weight 0 and its index is
+ * clamped).  The blend is resize = 1's for the same colour: REFERENCE hy (hx v00 + lx v01) + ly (hx v10 + lx v11), hx = 1 - lx,
+ * hy = 1 - ly; otherwise a + l (b - a) along the rows, then between them.  The output encoding is resize = 1's too: REFERENCE U8
+ * rounds halves up, REFERENCE floats are (v / 255 - mean) / std, otherwise U8 rint(v) and floats v; alpha is 255 / 1.0.
+ * REMAP_NEAREST: xi = floor(cx + 0.5f), the sum rounded in fp32, yi likewise; the value is S(xi, yi) (CONSTANT: the pad outside;
+ * REPLICATE: never outside), encoded the same way.
+ * There is NO antialiasing: a map that shrinks the picture aliases exactly as cv2.remap does; shrink with
+ * h264bsdmiNextOutputTensorBatchResize or a region pull instead, or supersample the map.
+ * -1, before anything is enqueued: everything h264bsdmiOutputTensorRegions refuses in spec, colour, instances and stream; maps or
+ * got NULL with nMaps > 0; nMaps > 65535; an instance index >= n; a NULL map or one that is not 8-byte aligned; filter > 1 or
+ * border > 1; a pad that is not finite or lies outside [0, 1].  nMaps == 0 returns 0 and launches nothing.  -2: the engine failed. */
+#define H264BSDMI_REMAP_NEAREST   0
+#define H264BSDMI_REMAP_BILINEAR  1
+#define H264BSDMI_BORDER_CONSTANT  0   /* outside the window: pad */
+#define H264BSDMI_BORDER_REPLICATE 1   /* outside the window: the nearest sample of the window */
+typedef struct h264bsdmi_remap      { u32 instance; const void *map; } h264bsdmi_remap;
+typedef struct h264bsdmi_remap_spec { u32 filter, border; float pad[3]; } h264bsdmi_remap_spec;
+int h264bsdmiOutputTensorRemap(u32 n, storage_t *const *pStorage, u32 nMaps, const h264bsdmi_remap *maps,
+                               const h264bsdmi_tensor_spec *spec, const h264bsdmi_colour_spec *colour,
+                               const h264bsdmi_remap_spec *remap, void *stream,
+                               u32 *got, u32 *current, u32 *picId);
+
 /* Motion-field tensors: the motion vectors the decoder resolved for a picture (P_Skip prediction included), resampled onto the
  * grid of a tensor pull — for carrying boxes across pictures, gating inference on motion, flow-conditioned networks.
  * Keep the motion side information of every picture of this instance beside its frame buffer (74 bytes per macroblock and frame

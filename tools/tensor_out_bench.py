@@ -24,7 +24,13 @@ letterboxed.  Every repetition decodes one more picture per instance and pops it
 
 usage: tensor_out_bench.py [--streams 256] [--reps 20] [--warmup 3] [--old-reps 3] [--colour reference|auto|bt601|bt709|...]
                            [--range auto|limited|full] [--chroma nearest|bilinear] [--filter bilinear|bilinear_aa|bicubic_aa]
-                           [--fit stretch|letterbox] [--only-b] [--no-old] [--regions K]"""
+                           [--fit stretch|letterbox] [--only-b] [--no-old] [--regions K] [--remap]
+
+--remap is a leg of its own (h264bsdmiOutputTensorRemap / pull_remap), on the current pictures, HIP events, the median of 10:
+  (g) one pull_remap call: every picture through ONE shared smooth (barrel) map -> [N, 3, 540, 960] f16, bilinear
+  (h) the same with calls the library had before: a full-size pull_tensor, then grid_sample(align_corners=True) with that map
+  (i) 4 rotated 128 x 64 boxes per picture (affine_maps) in one pull_remap call -> [4 N, 3, 64, 128]
+  (j) the same boxes as pull_regions of their axis-aligned hulls (-> 160 x 160, bilinear), then grid_sample with the rotation"""
 import argparse
 import json
 import os
@@ -51,6 +57,7 @@ ap.add_argument("--fit", default="stretch", choices=sorted(h.capi.FITS))
 ap.add_argument("--only-b", action="store_true", help="time (b) and (d) only")
 ap.add_argument("--no-old", action="store_true", help="skip (c), (d) and the copy ceiling")
 ap.add_argument("--regions", type=int, default=0, help="K boxes per instance: time (e), (f) and (b) with bilinear_aa only")
+ap.add_argument("--remap", action="store_true", help="time (g) .. (j) only: pull_remap against the full-size pull + grid_sample")
 args = ap.parse_args()
 if args.regions:
     args.filter, args.fit, args.only_b, args.no_old = "bilinear_aa", "stretch", True, True
@@ -60,6 +67,8 @@ N = args.streams
 rounds = 2 * (args.warmup + args.reps) + 3 * (1 + args.old_reps) + 2
 if args.regions:
     rounds += args.warmup + args.reps + 1 + args.old_reps
+if args.remap:
+    rounds = 2 * (args.warmup + 10) + 2 * (1 + args.old_reps) + 2
 decs = [h.Decoder(no_output_reordering=1) for _ in range(N)]
 drv = h.BatchDriver(decs, [data * (rounds // 73 + 2)] * N)
 L = h.api_lib()
@@ -219,11 +228,92 @@ def copy_ceiling_gbs():
     return 10 * 2 * src.numel() / (e0.elapsed_time(e1) * 1e-3) / 1e9
 
 
+def remap_legs():
+    import math
+    import numpy as np
+    H, W, K, BH, BW, HULL = 540, 960, 4, 64, 128, 160
+    i, j = np.meshgrid(np.arange(H, dtype=np.float64), np.arange(W, dtype=np.float64), indexing="ij")
+    u, t = 2 * (j + 0.5) / W - 1, 2 * (i + 0.5) / H - 1
+    s = (1 + 0.35 * (u * u + t * t) / 2) / 1.35                        # barrel: pulled towards the centre, the corners stay
+    barrel = torch.from_numpy(np.stack([959.5 + u * s * 964.5, 539.5 + t * s * 544.5], axis=-1).astype(np.float32)).cuda()
+    grid = torch.stack([barrel[..., 0] / 959.5 - 1, barrel[..., 1] / 539.5 - 1], dim=-1).half()       # x = (gx + 1) (W - 1) / 2
+    rng = np.random.default_rng(1024)
+    ang, cx, cy = rng.uniform(0, 2 * math.pi, N * K), rng.uniform(100, 1820, N * K), rng.uniform(100, 980, N * K)
+    co, si = np.cos(ang), np.sin(ang)
+    # output (i, j) of a BH x BW box <- centre + R (j - (BW - 1) / 2, i - (BH - 1) / 2)
+    theta = np.stack([np.stack([co, -si, cx - co * (BW - 1) / 2 + si * (BH - 1) / 2], -1),
+                      np.stack([si, co, cy - si * (BW - 1) / 2 - co * (BH - 1) / 2], -1)], 1)
+    rot_maps = h.affine_maps(theta, (BH, BW))
+    inst = [k // K for k in range(N * K)]
+    hulls = [(k // K, int(round(cx[k])) - HULL // 2, int(round(cy[k])) - HULL // 2, HULL, HULL) for k in range(N * K)]
+    # the same rotation inside the hull, as a normalised align_corners=True grid over its HULL samples
+    hx = (rot_maps[..., 0] - torch.tensor([b[1] for b in hulls], device="cuda").view(-1, 1, 1)) / ((HULL - 1) / 2) - 1
+    hy = (rot_maps[..., 1] - torch.tensor([b[2] for b in hulls], device="cuda").view(-1, 1, 1)) / ((HULL - 1) / 2) - 1
+    hull_grid = torch.stack([hx, hy], dim=-1).half()
+    st = torch.cuda.Stream()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+
+    def timed(reps, fn, pop=True):
+        ms = []
+        for rep in range(reps[0] + reps[1]):
+            next_round()
+            for d in decs if pop else []:
+                assert d.next_output_info() is not None
+            torch.cuda.synchronize()
+            e0.record(st)
+            fn()
+            e1.record(st)
+            st.synchronize()
+            if rep >= reps[0]:
+                ms.append(e0.elapsed_time(e1))
+        return sorted(ms)[len(ms) // 2], min(ms)
+
+    out_g = torch.empty((N, 3, H, W), dtype=torch.float16, device="cuda")
+    out_i = torch.empty((N * K, 3, BH, BW), dtype=torch.float16, device="cuda")
+    kw = dict(dtype=torch.float16, mean=MEAN, std=STD, stream=st, **COLOUR)
+
+    def leg_g():
+        assert all(h.pull_remap(decs, [barrel] * N, out=out_g, **kw)[1])
+
+    def leg_i():
+        assert all(h.pull_remap(decs, rot_maps, instances=inst, out=out_i, **kw)[1])
+
+    g_ms, g_min = timed((args.warmup, 10), leg_g)
+    i_ms, i_min = timed((args.warmup, 10), leg_i)
+    del out_g, out_i
+    full = torch.empty((N, 3, 1080, 1920), dtype=torch.float16, device="cuda")
+    hull_t = torch.empty((N * K, 3, HULL, HULL), dtype=torch.float16, device="cuda")
+
+    def leg_h():
+        h.pull_tensor(decs, out=full, **kw)             # pops the pictures itself
+        with torch.cuda.stream(st):
+            F.grid_sample(full, grid.expand(N, H, W, 2), mode="bilinear", padding_mode="zeros", align_corners=True)
+
+    def leg_j():
+        h.pull_regions(decs, hulls, (HULL, HULL), out=hull_t, **kw)
+        with torch.cuda.stream(st):
+            F.grid_sample(hull_t, hull_grid, mode="bilinear", padding_mode="zeros", align_corners=True)
+
+    h_ms, h_min = timed((1, args.old_reps), leg_h, pop=False)
+    j_ms, j_min = timed((1, args.old_reps), leg_j)
+    print(json.dumps(dict(streams=N, colour=args.colour, chroma=args.chroma, g_ms=round(g_ms, 3), g_min_ms=round(g_min, 3),
+                          h_ms=round(h_ms, 3), h_min_ms=round(h_min, 3), speedup_g=round(h_ms / g_ms, 2),
+                          g_ns_per_element=round(g_ms * 1e6 / (N * 3 * H * W), 5),
+                          boxes=N * K, i_ms=round(i_ms, 3), i_min_ms=round(i_min, 3), j_ms=round(j_ms, 3), j_min_ms=round(j_min, 3),
+                          speedup_i=round(j_ms / i_ms, 2), device_errors=h.device_errors())))
+
+
 COLOUR = {} if args.colour == "reference" else dict(colour=args.colour, colour_range=args.range, chroma=args.chroma)
 FILTER = {"bilinear": ("bilinear", False), "bilinear_aa": ("bilinear", True), "bicubic_aa": ("bicubic", True)}
 RESIZE = dict(mode=FILTER[args.filter][0], antialias=FILTER[args.filter][1], fit=args.fit)
 nan = float("nan")
 next_round()            # warm-up of the decoders (pinned staging, lanes); its pictures are dropped by the next round
+if args.remap:
+    remap_legs()
+    for d in decs:
+        d.close()
+    sys.exit(0)
 a_ms = a_wall = a_min = nan
 if not args.only_b:
     out_a = torch.empty((N, 3, 1080, 1920), dtype=torch.float16, device="cuda")
