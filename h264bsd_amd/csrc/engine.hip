@@ -1127,23 +1127,31 @@ void sink_close(void *user)
 }
 
 /* ---- the next pictures of many instances into one caller-owned tensor (h264bsdmiNextOutputTensorBatch[Colour|Resize]) ---- */
-/* one kernel per dtype, layout, number of channels and REF; the channel order and the whole colour transform are in the items
- * (colour_item) */
-/* (k_tensor_aa: one more family on the same four parameters, filter and fit at run time; k_tensor_roi: the same for regions;
- * k_tensor_remap: the same for coordinate maps, filter and border at run time) */
+/* five kernel families, each one kernel per dtype, layout, number of channels and REF; the channel order and the whole colour transform
+ * are in the items (colour_item); filter, fit and border are run-time arguments */
 enum { TK_OUT, TK_RESIZE, TK_AA, TK_ROI, TK_REMAP };
 template <int DT, int L, int C> static const void *tensor_kernel_of(int kind, bool ref)
 {
-    if (kind == TK_REMAP) return ref ? reinterpret_cast<const void *>(&h264k::k_tensor_remap<DT, L, C, true>) : reinterpret_cast<const void *>(&h264k::k_tensor_remap<DT, L, C, false>);
-    if (kind == TK_ROI) return ref ? reinterpret_cast<const void *>(&h264k::k_tensor_roi<DT, L, C, true>) : reinterpret_cast<const void *>(&h264k::k_tensor_roi<DT, L, C, false>);
-    if (kind == TK_AA) return ref ? reinterpret_cast<const void *>(&h264k::k_tensor_aa<DT, L, C, true>) : reinterpret_cast<const void *>(&h264k::k_tensor_aa<DT, L, C, false>);
-    const bool resize = kind == TK_RESIZE;
-    if (ref) return resize ? reinterpret_cast<const void *>(&h264k::k_tensor_resize<DT, L, C, true>) : reinterpret_cast<const void *>(&h264k::k_tensor_out<DT, L, C, true>);
-    return resize ? reinterpret_cast<const void *>(&h264k::k_tensor_resize<DT, L, C, false>) : reinterpret_cast<const void *>(&h264k::k_tensor_out<DT, L, C, false>);
+#define TK_CASE(K, NAME) \
+    case K: return ref ? reinterpret_cast<const void *>(&h264k::NAME<DT, L, C, true>) : reinterpret_cast<const void *>(&h264k::NAME<DT, L, C, false>)
+    switch (kind) {
+    TK_CASE(TK_OUT, k_tensor_out);
+    TK_CASE(TK_RESIZE, k_tensor_resize);
+    TK_CASE(TK_AA, k_tensor_aa);
+    TK_CASE(TK_ROI, k_tensor_roi);
+    TK_CASE(TK_REMAP, k_tensor_remap);
+    }
+#undef TK_CASE
+    return nullptr;
 }
-template <int DT> static const void *tensor_kernel_dt(int kind, bool ref, uint32_t layout, uint32_t ch)
+/* the channels of a spec's slice and its size in bytes */
+static size_t spec_channels(const h264bsdmi_tensor_spec &t) { return t.channels == h264k::TO_Y ? 1 : t.channels >= h264k::TO_RGBA ? 4 : 3; }
+static size_t spec_slice_bytes(const h264bsdmi_tensor_spec &t)
 {
-    const int C = ch == h264k::TO_Y ? 1 : ch >= h264k::TO_RGBA ? 4 : 3;
+    return spec_channels(t) * t.width * t.height * (t.dtype == h264k::TO_U8 ? 1 : t.dtype == h264k::TO_F16 ? 2 : 4);
+}
+template <int DT> static const void *tensor_kernel_dt(int kind, bool ref, uint32_t layout, size_t C)
+{
     if (layout == h264k::TO_NCHW) {
         if (C == 1) return tensor_kernel_of<DT, h264k::TO_NCHW, 1>(kind, ref);
         if (C == 3) return tensor_kernel_of<DT, h264k::TO_NCHW, 3>(kind, ref);
@@ -1154,13 +1162,12 @@ template <int DT> static const void *tensor_kernel_dt(int kind, bool ref, uint32
     }
     return nullptr;
 }
-static const void *tensor_kernel(const h264bsdmi_tensor_spec &t, bool aa, bool ref, bool roi = false, bool remap = false)
+static const void *tensor_kernel(int kind, const h264bsdmi_tensor_spec &t, bool ref)
 {
-    const int kind = remap ? TK_REMAP : roi ? TK_ROI : aa ? TK_AA : t.resize ? TK_RESIZE : TK_OUT;
     switch (t.dtype) {
-    case h264k::TO_U8: return tensor_kernel_dt<h264k::TO_U8>(kind, ref, t.layout, t.channels);
-    case h264k::TO_F16: return tensor_kernel_dt<h264k::TO_F16>(kind, ref, t.layout, t.channels);
-    case h264k::TO_F32: return tensor_kernel_dt<h264k::TO_F32>(kind, ref, t.layout, t.channels);
+    case h264k::TO_U8: return tensor_kernel_dt<h264k::TO_U8>(kind, ref, t.layout, spec_channels(t));
+    case h264k::TO_F16: return tensor_kernel_dt<h264k::TO_F16>(kind, ref, t.layout, spec_channels(t));
+    case h264k::TO_F32: return tensor_kernel_dt<h264k::TO_F32>(kind, ref, t.layout, spec_channels(t));
     }
     return nullptr;
 }
@@ -1209,7 +1216,7 @@ static void colour_item(h264k::TensorItem &it, const h264bsdmi_tensor_spec &t, u
     }
 }
 
-/* The three steps every pull shares (tensor_out_locked, motion_out_locked, remap_out_locked), under the engine's mutex.
+/* The three steps every pull shares, under the engine's mutex.
  * pull_begin_locked: the instances' queued jobs are enqueued, once for the batch; half e->titem_flip of the item staging is made
  * large enough for n_items and free (the launch before the last one read it). */
 static int pull_begin_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, uint32_t n_items)
@@ -1275,111 +1282,166 @@ static int pull_end_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, hip
     return 0;
 }
 
-/* Under the engine's mutex.  Ordering without host waits: the instances' queued jobs are enqueued once for the batch, the output
- * stream waits for each picture's producing tick (deduplicated per lane launch, as lane_launch does), ONE launch lays out every
- * picture, and a fence recorded behind it is handed to every instance: lane_launch makes an instance's next tick wait for it, and
- * the frame buffers are not cleared or freed before it has passed (fence_drop).  *fence_ev: the fence's event.
- * regs != nullptr (h264bsdmiOutputTensorRegions): the items are the n_regs regions, each a box of one of the n pictures, which were
- * popped earlier and are read where they lie; k_tensor_roi for every filter and fit.  The pictures are still one per instance, so
- * the producers' events and the fence are taken once per instance however many regions name it. */
-static int tensor_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, uint32_t n_regs, const SinkRegion *regs,
-                             const h264bsdmi_tensor_spec &t, uint32_t chroma, const h264bsdmi_resize_spec *rs, hipStream_t st,
-                             hipEvent_t *fence_ev)
+/* ---- what the pulls (whole pictures, regions, motion regions, coordinate maps) share, under the engine's mutex ---- */
+static const StreamCtx *pic_stream(const SinkTensorPic &p) { return static_cast<SinkUser *>(p.sink->user)->s; }
+/* The refusals per picture: a slot of its instance, frames, a window inside the coded size; for pixels also a matrix that agrees
+ * with ref (one kernel: every picture of the call takes the reference conversion, or none) and an even window.  motion: the side
+ * information instead of the frames, no matrix and no parity rule. */
+static bool pull_pictures_ok(uint32_t n, const SinkTensorPic *pics, bool ref, bool motion)
 {
-    const bool ref = pics[0].matrix == H264BSDMI_MATRIX_REFERENCE;      /* one kernel: every picture of the call, or none */
-    /* k_tensor_aa for every filter and fit but resize = 1's own bilinear stretch, which stays on k_tensor_resize */
-    const bool aa = !regs && rs && (rs->filter != H264BSDMI_FILTER_BILINEAR || rs->fit != H264BSDMI_FIT_STRETCH);
-    if ((aa || regs) && (!rs || !t.resize || rs->filter > H264BSDMI_FILTER_BICUBIC_AA || rs->fit > H264BSDMI_FIT_LETTERBOX)) return -1;
-    const void *fn = tensor_kernel(t, aa, ref, regs != nullptr);
-    if (!fn) return -1;
-    const uint32_t n_items = regs ? n_regs : n;
-    if (!n_items || n_items > 65535u) return -1;                        /* grid.y */
     for (uint32_t i = 0; i < n; i++) {
-        const StreamCtx *s = static_cast<SinkUser *>(pics[i].sink->user)->s;
         const SinkTensorPic &p = pics[i];
-        if (p.slot >= s->n_slots || !s->d_frames || !p.w || !p.h || p.x0 + p.w > s->wmb * 16 || p.y0 + p.h > s->hmb * 16) return -1;
+        const StreamCtx *s = pic_stream(p);
+        if (p.slot >= s->n_slots || !p.w || !p.h || p.x0 + p.w > s->wmb * 16 || p.y0 + p.h > s->hmb * 16) return false;
+        if (motion ? !s->motion || !s->d_motion : !s->d_frames) return false;
+        if (motion) continue;
         if ((p.matrix == H264BSDMI_MATRIX_REFERENCE) != ref || (!ref && (p.matrix < H264BSDMI_MATRIX_BT601 || p.matrix > H264BSDMI_MATRIX_SMPTE240)))
-            return -1;
-        if ((p.x0 | p.y0 | p.w | p.h) & 1u) return -1;
-        if (aa && (!p.box[2] || !p.box[3] || p.box[0] + p.box[2] > t.width || p.box[1] + p.box[3] > t.height)) return -1;
+            return false;
+        if ((p.x0 | p.y0 | p.w | p.h) & 1u) return false;
     }
-    for (uint32_t r = 0; regs && r < n_regs; r++) {
+    return true;
+}
+/* an inner rectangle (left, top, w, h) of a width x height slice */
+static bool pull_box_ok(const uint32_t *box, uint32_t width, uint32_t height)
+{
+    return box[2] && box[3] && box[0] + box[2] <= width && box[1] + box[3] <= height;
+}
+/* the refusals per region: a picture of the call, a box within the limits of the interface, an inner rectangle inside the slice */
+static bool pull_regions_ok(uint32_t n, uint32_t n_regs, const SinkRegion *regs, uint32_t width, uint32_t height)
+{
+    for (uint32_t r = 0; r < n_regs; r++) {
         const SinkRegion &g = regs[r];
-        if (g.pic >= n || !g.w || !g.h || g.w > 16384u || g.h > 16384u || abs(g.x) > 16384 || abs(g.y) > 16384) return -1;
-        if (!g.box[2] || !g.box[3] || g.box[0] + g.box[2] > t.width || g.box[1] + g.box[3] > t.height) return -1;
+        if (g.pic >= n || !g.w || !g.h || g.w > 16384u || g.h > 16384u || abs(g.x) > 16384 || abs(g.y) > 16384) return false;
+        if (!pull_box_ok(g.box, width, height)) return false;
     }
-    if (pull_begin_locked(e, n, pics, n_items)) return -1;
-    const int f = e->titem_flip;
-    const size_t half = (size_t)f * e->titem_cap * TITEM_BYTES;
-    h264k::TensorItem *items = reinterpret_cast<h264k::TensorItem *>(e->h_titems + half);
-    h264k::AaItem *aa_items = reinterpret_cast<h264k::AaItem *>(e->h_titems + half);
-    h264k::RoiItem *roi_items = reinterpret_cast<h264k::RoiItem *>(e->h_titems + half);
-    const size_t C = t.channels == h264k::TO_Y ? 1 : t.channels >= h264k::TO_RGBA ? 4 : 3;
-    const size_t pic_bytes = C * t.width * t.height * (t.dtype == h264k::TO_U8 ? 1 : t.dtype == h264k::TO_F16 ? 2 : 4);
-    for (uint32_t i = 0; i < n; i++) {
-        const StreamCtx *s = static_cast<SinkUser *>(pics[i].sink->user)->s;
-        const SinkTensorPic &p = pics[i];
-        if (!regs) {
-            h264k::TensorItem &ti = aa ? aa_items[i].t : items[i];
-            ti = h264k::TensorItem{ s->d_frames + (size_t)p.slot * s->frame_bytes, static_cast<uint8_t *>(t.data) + p.index * pic_bytes,
-                                    s->wmb, p.x0, p.y0, p.w, p.h, 0u };
-            colour_item(ti, t, p.matrix, p.range);
-            if (aa) { aa_items[i].left = p.box[0]; aa_items[i].top = p.box[1]; aa_items[i].iw = p.box[2]; aa_items[i].ih = p.box[3]; }
-        }
+    return true;
+}
+/* the item of one picture: its frame, its window and its colour map, into slice `index` of the tensor */
+static h264k::TensorItem picture_item(const SinkTensorPic &p, const h264bsdmi_tensor_spec &t, size_t index)
+{
+    const StreamCtx *s = pic_stream(p);
+    h264k::TensorItem it{ s->d_frames + (size_t)p.slot * s->frame_bytes, static_cast<uint8_t *>(t.data) + index * spec_slice_bytes(t),
+                          s->wmb, p.x0, p.y0, p.w, p.h, 0u };
+    colour_item(it, t, p.matrix, p.range);
+    return it;
+}
+static void copy3(float *d, const float *s) { d[0] = s[0]; d[1] = s[1]; d[2] = s[2]; }
+/* The call's pad in [0, 1] per channel, folded in double, ONE rule for every family (their bit-for-bit equalities rest on it).  pad:
+ * under the output's scale, written where there is nothing to interpolate (U8 floor(255 pad + 0.5), floats (pad - mean) / std).  spad:
+ * around the picture, under the scale of the samples that are interpolated — REF the 8-bit value whatever the dtype, else 255 pad (U8) / as pad. */
+struct PullPad { float pad[3], spad[3]; };
+static PullPad fold_pad(const float *pad, uint32_t dtype, const float *mean, const float *std, bool ref)
+{
+    PullPad pp;
+    for (int c = 0; c < 3; c++) {
+        const double q = std::floor(255.0 * pad[c] + 0.5), nrm = ((double)pad[c] - mean[c]) / std[c];
+        pp.pad[c] = dtype == h264k::TO_U8 ? (float)q : (float)nrm;
+        pp.spad[c] = ref ? (float)q : dtype == h264k::TO_U8 ? (float)(255.0 * pad[c]) : (float)nrm;
     }
+    return pp;
+}
+/* grid.x walks the slice's tiles of cols x rows (per_block of them at a time in a workgroup), at most 1024 workgroups; grid.y = the items */
+static dim3 pull_grid(uint32_t width, uint32_t height, uint32_t cols, uint32_t rows, uint32_t n_items, uint32_t per_block = 1)
+{
+    const uint32_t tiles = (width + cols - 1u) / cols * ((height + rows - 1u) / rows);
+    return dim3(std::min((tiles + per_block - 1u) / per_block, 1024u), n_items);
+}
+/* half e->titem_flip of the item staging (pull_begin_locked), as the host fills it and as the kernel reads it */
+static size_t staged_half(const Engine *e) { return (size_t)e->titem_flip * e->titem_cap * TITEM_BYTES; }
+template <typename Item> static Item *staged_items(Engine *e) { return reinterpret_cast<Item *>(e->h_titems + staged_half(e)); }
+template <typename Item> static const Item *staged_items_dev(Engine *e)
+{
+    return reinterpret_cast<const Item *>(e->h_titems.dev() + staged_half(e));
+}
+/* behind the filled items: st waits for the pictures' ticks, ONE launch of 256-lane workgroups, the fence */
+static int pull_launch_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, hipStream_t st, const void *fn, dim3 grid, void *kargs,
+                              hipEvent_t *fence_ev)
+{
     if (pull_wait_pictures(e, n, pics, st)) return -1;
-    if (regs) {
-        /* the colour map once per picture, then one item per region */
-        std::vector<h264k::TensorItem> of_pic(n);
-        for (uint32_t i = 0; i < n; i++) {
-            const StreamCtx *s = static_cast<SinkUser *>(pics[i].sink->user)->s;
-            const SinkTensorPic &p = pics[i];
-            of_pic[i] = h264k::TensorItem{ s->d_frames + (size_t)p.slot * s->frame_bytes, nullptr, s->wmb, p.x0, p.y0, p.w, p.h, 0u };
-            colour_item(of_pic[i], t, p.matrix, p.range);
-        }
-        for (uint32_t r = 0; r < n_regs; r++) {
-            const SinkRegion &g = regs[r];
-            roi_items[r] = h264k::RoiItem{ of_pic[g.pic], g.x, g.y, g.w, g.h, g.box[0], g.box[1], g.box[2], g.box[3] };
-            roi_items[r].t.dst = static_cast<uint8_t *>(t.data) + g.index * pic_bytes;
-        }
-    }
-    h264k::TensorArgs ta{ reinterpret_cast<const h264k::TensorItem *>(e->h_titems.dev() + half), t.width, t.height, chroma,
-                          { t.mean[0], t.mean[1], t.mean[2] }, { t.std[0], t.std[1], t.std[2] } };
-    if (regs) {
-        /* pad: outside the inner rectangle, under the output scale (as for k_tensor_aa); spad: the pad around the picture under the
-         * scale of the samples k_tensor_roi interpolates — REF the 8-bit value whatever the dtype, otherwise 255 pad / (pad - mean) / std */
-        h264k::RoiArgs rargs{ reinterpret_cast<const h264k::RoiItem *>(e->h_titems.dev() + half), t.width, t.height, chroma, rs->filter,
-                              { t.mean[0], t.mean[1], t.mean[2] }, { t.std[0], t.std[1], t.std[2] }, { 0, 0, 0 }, { 0, 0, 0 } };
-        for (int c = 0; c < 3; c++) {
-            const double q = std::floor(255.0 * rs->pad[c] + 0.5), nrm = ((double)rs->pad[c] - t.mean[c]) / t.std[c];
-            rargs.pad[c] = t.dtype == h264k::TO_U8 ? (float)q : (float)nrm;
-            rargs.spad[c] = ref ? (float)q : t.dtype == h264k::TO_U8 ? (float)(255.0 * rs->pad[c]) : (float)nrm;
-        }
-        const uint32_t blocks = (t.width + h264k::TAA_COLS - 1u) / h264k::TAA_COLS * ((t.height + h264k::TAA_ROWS - 1u) / h264k::TAA_ROWS);
-        void *args[] = { &rargs };
-        HIP_TRY(hipLaunchKernel(fn, dim3(std::min(blocks, 1024u), n_regs), dim3(256), args, 0, st));
-    } else if (aa) {
-        /* the pad under the output scale, per output channel: U8 floor(255 pad + 0.5), floats (pad - mean) / std, in double */
-        h264k::AaArgs aargs{ reinterpret_cast<const h264k::AaItem *>(e->h_titems.dev() + half), t.width, t.height, chroma, rs->filter,
-                             { t.mean[0], t.mean[1], t.mean[2] }, { t.std[0], t.std[1], t.std[2] }, { 0, 0, 0 } };
-        for (int c = 0; c < 3; c++)
-            aargs.pad[c] = t.dtype == h264k::TO_U8 ? (float)std::floor(255.0 * rs->pad[c] + 0.5) : (float)(((double)rs->pad[c] - t.mean[c]) / t.std[c]);
-        const uint32_t blocks = (t.width + h264k::TAA_COLS - 1u) / h264k::TAA_COLS * ((t.height + h264k::TAA_ROWS - 1u) / h264k::TAA_ROWS);
-        void *args[] = { &aargs };
-        HIP_TRY(hipLaunchKernel(fn, dim3(std::min(blocks, 1024u), n), dim3(256), args, 0, st));
-    } else {
-        const uint32_t blocks = t.resize ? (t.width + h264k::TCR_COLS - 1u) / h264k::TCR_COLS * ((t.height + h264k::TCR_ROWS - 1u) / h264k::TCR_ROWS)
-                                         : ((t.width + 63u) / 64u * ((t.height + 15u) / 16u) + 3u) / 4u;
-        void *args[] = { &ta };
-        HIP_TRY(hipLaunchKernel(fn, dim3(std::min(blocks, 1024u), n), dim3(256), args, 0, st));
-    }
+    void *args[] = { kargs };
+    HIP_TRY(hipLaunchKernel(fn, grid, dim3(256), args, 0, st));
     return pull_end_locked(e, n, pics, st, fence_ev);
 }
 
-/* h264bsdmiOutputMotionRegions, under the engine's mutex: the regions of tensor_out_locked, read from the side information beside
- * each picture's frame buffer instead of from its pixels, by one k_motion_roi launch.  The same ordering: behind the ticks that made
- * the pictures (k_motion_keep runs in front of a tick's ring event), and the same fence, so that the next picture decoded into one of
- * these slots — and the k_motion_keep behind it — waits for this launch. */
+/* The pulls below take the same steps in the same order, without host waits: the refusals; pull_begin_locked;
+ * the items and the arguments are filled; pull_launch_locked: st waits for each picture's producing tick, ONE launch lays out every
+ * item, and a fence recorded behind it is handed to every instance: lane_launch makes an instance's next tick wait for it, and the
+ * frame buffers are not cleared or freed before it has passed (fence_drop).  *fence_ev: the fence's event. */
+/* h264bsdmiNextOutputTensorBatchResize with any filter and fit but resize = 1's own bilinear stretch: one AaItem per picture,
+ * k_tensor_aa */
+static int aa_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, const h264bsdmi_tensor_spec &t, uint32_t chroma,
+                         const h264bsdmi_resize_spec &rs, hipStream_t st, hipEvent_t *fence_ev)
+{
+    const bool ref = pics[0].matrix == H264BSDMI_MATRIX_REFERENCE;
+    if (!t.resize || rs.filter > H264BSDMI_FILTER_BICUBIC_AA || rs.fit > H264BSDMI_FIT_LETTERBOX) return -1;
+    const void *fn = tensor_kernel(TK_AA, t, ref);
+    if (!fn || n > 65535u) return -1;                                   /* grid.y */
+    if (!pull_pictures_ok(n, pics, ref, false)) return -1;
+    for (uint32_t i = 0; i < n; i++)
+        if (!pull_box_ok(pics[i].box, t.width, t.height)) return -1;
+    if (pull_begin_locked(e, n, pics, n)) return -1;
+    h264k::AaItem *items = staged_items<h264k::AaItem>(e);
+    for (uint32_t i = 0; i < n; i++) {
+        const uint32_t *box = pics[i].box;
+        items[i] = h264k::AaItem{ picture_item(pics[i], t, pics[i].index), box[0], box[1], box[2], box[3] };
+    }
+    h264k::AaArgs aargs{ staged_items_dev<h264k::AaItem>(e), t.width, t.height, chroma, rs.filter, {}, {}, {} };
+    copy3(aargs.mean, t.mean); copy3(aargs.std, t.std); copy3(aargs.pad, fold_pad(rs.pad, t.dtype, t.mean, t.std, ref).pad);
+    return pull_launch_locked(e, n, pics, st, fn, pull_grid(t.width, t.height, h264k::TAA_COLS, h264k::TAA_ROWS, n), &aargs, fence_ev);
+}
+
+/* h264bsdmiNextOutputTensorBatch[Colour|Resize]: one TensorItem per picture, k_tensor_out without resize, k_tensor_resize for
+ * resize = 1's own bilinear stretch; every other filter and fit is aa_out_locked's */
+static int tensor_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, const h264bsdmi_tensor_spec &t, uint32_t chroma,
+                             const h264bsdmi_resize_spec *rs, hipStream_t st, hipEvent_t *fence_ev)
+{
+    if (rs && (rs->filter != H264BSDMI_FILTER_BILINEAR || rs->fit != H264BSDMI_FIT_STRETCH))
+        return aa_out_locked(e, n, pics, t, chroma, *rs, st, fence_ev);
+    const bool ref = pics[0].matrix == H264BSDMI_MATRIX_REFERENCE;
+    const void *fn = tensor_kernel(t.resize ? TK_RESIZE : TK_OUT, t, ref);
+    if (!fn || n > 65535u) return -1;                                   /* grid.y */
+    if (!pull_pictures_ok(n, pics, ref, false)) return -1;
+    if (pull_begin_locked(e, n, pics, n)) return -1;
+    h264k::TensorItem *items = staged_items<h264k::TensorItem>(e);
+    for (uint32_t i = 0; i < n; i++) items[i] = picture_item(pics[i], t, pics[i].index);
+    h264k::TensorArgs targs{ staged_items_dev<h264k::TensorItem>(e), t.width, t.height, chroma, {}, {} };
+    copy3(targs.mean, t.mean); copy3(targs.std, t.std);
+    /* k_tensor_out: a wavefront per unit of 64 x 16, four to a workgroup */
+    const dim3 grid = t.resize ? pull_grid(t.width, t.height, h264k::TCR_COLS, h264k::TCR_ROWS, n) : pull_grid(t.width, t.height, 64, 16, n, 4);
+    return pull_launch_locked(e, n, pics, st, fn, grid, &targs, fence_ev);
+}
+
+/* h264bsdmiOutputTensorRegions: the items are the n_regs regions, each a box of one of the n pictures, which were popped earlier and
+ * are read where they lie; k_tensor_roi for every filter and fit.  The pictures are still one per instance, so the producers'
+ * events and the fence are taken once per instance however many regions name it. */
+static int regions_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, uint32_t n_regs, const SinkRegion *regs,
+                              const h264bsdmi_tensor_spec &t, uint32_t chroma, const h264bsdmi_resize_spec &rs, hipStream_t st,
+                              hipEvent_t *fence_ev)
+{
+    const bool ref = pics[0].matrix == H264BSDMI_MATRIX_REFERENCE;
+    if (!t.resize || rs.filter > H264BSDMI_FILTER_BICUBIC_AA || rs.fit > H264BSDMI_FIT_LETTERBOX) return -1;
+    const void *fn = tensor_kernel(TK_ROI, t, ref);
+    if (!fn || n_regs > 65535u) return -1;                              /* grid.y */
+    if (!pull_pictures_ok(n, pics, ref, false) || !pull_regions_ok(n, n_regs, regs, t.width, t.height)) return -1;
+    if (pull_begin_locked(e, n, pics, n_regs)) return -1;
+    h264k::RoiItem *items = staged_items<h264k::RoiItem>(e);
+    std::vector<h264k::TensorItem> of_pic(n);                           /* the colour map once per picture */
+    for (uint32_t i = 0; i < n; i++) of_pic[i] = picture_item(pics[i], t, 0);
+    for (uint32_t r = 0; r < n_regs; r++) {
+        const SinkRegion &g = regs[r];
+        items[r] = h264k::RoiItem{ of_pic[g.pic], g.x, g.y, g.w, g.h, g.box[0], g.box[1], g.box[2], g.box[3] };
+        items[r].t.dst += g.index * spec_slice_bytes(t);
+    }
+    h264k::RoiArgs rargs{ staged_items_dev<h264k::RoiItem>(e), t.width, t.height, chroma, rs.filter, {}, {}, {}, {} };
+    const PullPad pp = fold_pad(rs.pad, t.dtype, t.mean, t.std, ref);
+    copy3(rargs.mean, t.mean); copy3(rargs.std, t.std); copy3(rargs.pad, pp.pad); copy3(rargs.spad, pp.spad);
+    return pull_launch_locked(e, n, pics, st, fn, pull_grid(t.width, t.height, h264k::TAA_COLS, h264k::TAA_ROWS, n_regs), &rargs, fence_ev);
+}
+
+/* h264bsdmiOutputMotionRegions: the regions of regions_out_locked, read from the side information beside each picture's frame
+ * buffer instead of from its pixels, by one k_motion_roi launch.  The same ordering: behind the ticks that made the pictures
+ * (k_motion_keep runs in front of a tick's ring event), and the same fence, so that the next picture decoded into one of these
+ * slots — and the k_motion_keep behind it — waits for this launch. */
 static int motion_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, uint32_t n_regs, const SinkRegion *regs,
                              const h264bsdmi_motion_spec &m, hipStream_t st, hipEvent_t *fence_ev)
 {
@@ -1389,104 +1451,61 @@ static int motion_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, u
     const uint32_t all = H264BSDMI_MOTION_PLANE_MV | H264BSDMI_MOTION_PLANE_VALID | H264BSDMI_MOTION_PLANE_AGE | H264BSDMI_MOTION_PLANE_QP;
     if (!m.data || !m.width || !m.height || m.layout > h264k::TO_NHWC || (m.dtype != h264k::TO_F16 && m.dtype != h264k::TO_F32) ||
         !m.planes || (m.planes & ~all) || m.sampler > H264BSDMI_MOTION_AREA || m.units > H264BSDMI_MOTION_UNITS_OUTPUT || m.per_picture > 1u) return -1;
-    if (!n_regs || n_regs > 65535u) return -1;                          /* grid.y */
-    for (uint32_t i = 0; i < n; i++) {
-        const StreamCtx *s = static_cast<SinkUser *>(pics[i].sink->user)->s;
-        const SinkTensorPic &p = pics[i];
-        if (!s->motion || !s->d_motion || p.slot >= s->n_slots || !p.w || !p.h || p.x0 + p.w > s->wmb * 16 || p.y0 + p.h > s->hmb * 16) return -1;
-    }
-    for (uint32_t r = 0; r < n_regs; r++) {
-        const SinkRegion &g = regs[r];
-        if (g.pic >= n || !g.w || !g.h || g.w > 16384u || g.h > 16384u || abs(g.x) > 16384 || abs(g.y) > 16384) return -1;
-        if (!g.box[2] || !g.box[3] || g.box[0] + g.box[2] > m.width || g.box[1] + g.box[3] > m.height) return -1;
-    }
+    if (n_regs > 65535u) return -1;                                     /* grid.y */
+    if (!pull_pictures_ok(n, pics, false, true) || !pull_regions_ok(n, n_regs, regs, m.width, m.height)) return -1;
     if (pull_begin_locked(e, n, pics, n_regs)) return -1;
-    const size_t half = (size_t)e->titem_flip * e->titem_cap * TITEM_BYTES;
-    h264k::MotionItem *items = reinterpret_cast<h264k::MotionItem *>(e->h_titems + half);
+    h264k::MotionItem *items = staged_items<h264k::MotionItem>(e);
     const size_t C = ((m.planes & H264BSDMI_MOTION_PLANE_MV) ? 2 : 0) + ((m.planes & H264BSDMI_MOTION_PLANE_VALID) ? 1 : 0) +
                      ((m.planes & H264BSDMI_MOTION_PLANE_AGE) ? 1 : 0) + ((m.planes & H264BSDMI_MOTION_PLANE_QP) ? 1 : 0);
-    const size_t slice_bytes = C * m.width * m.height * (m.dtype == h264k::TO_F16 ? 2 : 4);
+    const size_t slice = C * m.width * m.height * (m.dtype == h264k::TO_F16 ? 2 : 4);
     for (uint32_t r = 0; r < n_regs; r++) {
         const SinkRegion &g = regs[r];
         const SinkTensorPic &p = pics[g.pic];
-        const StreamCtx *s = static_cast<SinkUser *>(p.sink->user)->s;
-        items[r] = h264k::MotionItem{ s->d_motion + (size_t)p.slot * s->motion_bytes, static_cast<uint8_t *>(m.data) + g.index * slice_bytes,
+        const StreamCtx *s = pic_stream(p);
+        items[r] = h264k::MotionItem{ s->d_motion + (size_t)p.slot * s->motion_bytes, static_cast<uint8_t *>(m.data) + g.index * slice,
                                       s->wmb, s->hmb, p.x0, p.y0, p.w, p.h, g.x, g.y, g.w, g.h, g.box[0], g.box[1], g.box[2], g.box[3] };
     }
-    if (pull_wait_pictures(e, n, pics, st)) return -1;
-    h264k::MotionArgs margs{ reinterpret_cast<const h264k::MotionItem *>(e->h_titems.dev() + half), m.width, m.height, m.planes, m.sampler,
-                             m.units, m.per_picture };
-    const uint32_t blocks = (m.width + h264k::TAA_COLS - 1u) / h264k::TAA_COLS * ((m.height + h264k::TAA_ROWS - 1u) / h264k::TAA_ROWS);
-    void *args[] = { &margs };
-    HIP_TRY(hipLaunchKernel(fns[m.dtype == h264k::TO_F32][m.layout], dim3(std::min(blocks, 1024u), n_regs), dim3(256), args, 0, st));
-    return pull_end_locked(e, n, pics, st, fence_ev);
+    h264k::MotionArgs margs{ staged_items_dev<h264k::MotionItem>(e), m.width, m.height, m.planes, m.sampler, m.units, m.per_picture };
+    return pull_launch_locked(e, n, pics, st, fns[m.dtype == h264k::TO_F32][m.layout],
+                              pull_grid(m.width, m.height, h264k::TAA_COLS, h264k::TAA_ROWS, n_regs), &margs, fence_ev);
 }
 
-/* h264bsdmiOutputTensorRemap, under the engine's mutex: the current pictures of the n instances sampled through n_maps coordinate
- * maps by one k_tensor_remap launch, map r into slice maps[r].index.  The ordering of tensor_out_locked's regions: the instances'
- * queued jobs are enqueued, st waits for the ticks that made the pictures, and one fence behind the launch goes to each distinct
- * instance, so that the next picture decoded into one of these slots waits for this launch.  The maps are the caller's: read on st. */
+/* h264bsdmiOutputTensorRemap: the current pictures of the n instances sampled through n_maps coordinate maps by one k_tensor_remap
+ * launch, map r into slice maps[r].index.  The fence goes to each distinct instance, so that the next picture decoded into one of
+ * these slots waits for this launch.  The maps are the caller's: read on st. */
 static int remap_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, uint32_t n_maps, const SinkRemap *maps,
                             const h264bsdmi_tensor_spec &t, uint32_t chroma, const h264bsdmi_remap_spec &rm, hipStream_t st,
                             hipEvent_t *fence_ev)
 {
-    const bool ref = pics[0].matrix == H264BSDMI_MATRIX_REFERENCE;      /* one kernel: every picture of the call, or none */
+    const bool ref = pics[0].matrix == H264BSDMI_MATRIX_REFERENCE;
     if (!t.resize || rm.filter > H264BSDMI_REMAP_BILINEAR || rm.border > H264BSDMI_BORDER_REPLICATE) return -1;
-    const void *fn = tensor_kernel(t, false, ref, false, true);
-    if (!fn) return -1;
-    if (!n_maps || n_maps > 65535u) return -1;                          /* grid.y */
-    for (uint32_t i = 0; i < n; i++) {
-        const StreamCtx *s = static_cast<SinkUser *>(pics[i].sink->user)->s;
-        const SinkTensorPic &p = pics[i];
-        if (p.slot >= s->n_slots || !s->d_frames || !p.w || !p.h || p.x0 + p.w > s->wmb * 16 || p.y0 + p.h > s->hmb * 16) return -1;
-        if ((p.matrix == H264BSDMI_MATRIX_REFERENCE) != ref || (!ref && (p.matrix < H264BSDMI_MATRIX_BT601 || p.matrix > H264BSDMI_MATRIX_SMPTE240)))
-            return -1;
-        if ((p.x0 | p.y0 | p.w | p.h) & 1u) return -1;
-    }
+    const void *fn = tensor_kernel(TK_REMAP, t, ref);
+    if (!fn || n_maps > 65535u) return -1;                              /* grid.y */
+    if (!pull_pictures_ok(n, pics, ref, false)) return -1;
     for (uint32_t r = 0; r < n_maps; r++)
         if (maps[r].pic >= n || !maps[r].map || (reinterpret_cast<uintptr_t>(maps[r].map) & 7u)) return -1;
     if (pull_begin_locked(e, n, pics, n_maps)) return -1;
-    const size_t half = (size_t)e->titem_flip * e->titem_cap * TITEM_BYTES;
-    h264k::RemapItem *items = reinterpret_cast<h264k::RemapItem *>(e->h_titems + half);
-    const size_t C = t.channels == h264k::TO_Y ? 1 : t.channels >= h264k::TO_RGBA ? 4 : 3;
-    const size_t pic_bytes = C * t.width * t.height * (t.dtype == h264k::TO_U8 ? 1 : t.dtype == h264k::TO_F16 ? 2 : 4);
-    /* the colour map once per picture, then one item per map */
-    std::vector<h264k::TensorItem> of_pic(n);
-    for (uint32_t i = 0; i < n; i++) {
-        const StreamCtx *s = static_cast<SinkUser *>(pics[i].sink->user)->s;
-        const SinkTensorPic &p = pics[i];
-        of_pic[i] = h264k::TensorItem{ s->d_frames + (size_t)p.slot * s->frame_bytes, nullptr, s->wmb, p.x0, p.y0, p.w, p.h, 0u };
-        colour_item(of_pic[i], t, p.matrix, p.range);
-    }
+    h264k::RemapItem *items = staged_items<h264k::RemapItem>(e);
+    std::vector<h264k::TensorItem> of_pic(n);                           /* the colour map once per picture */
+    for (uint32_t i = 0; i < n; i++) of_pic[i] = picture_item(pics[i], t, 0);
     for (uint32_t r = 0; r < n_maps; r++) {
         items[r] = h264k::RemapItem{ of_pic[maps[r].pic], static_cast<const float *>(maps[r].map) };
-        items[r].t.dst = static_cast<uint8_t *>(t.data) + maps[r].index * pic_bytes;
+        items[r].t.dst += maps[r].index * spec_slice_bytes(t);
     }
-    if (pull_wait_pictures(e, n, pics, st)) return -1;
-    /* pad and spad as for k_tensor_roi: a non-finite coordinate under the output scale, outside the window under the samples' */
-    h264k::RemapArgs rargs{ reinterpret_cast<const h264k::RemapItem *>(e->h_titems.dev() + half), t.width, t.height, chroma, rm.filter, rm.border,
-                            { t.mean[0], t.mean[1], t.mean[2] }, { t.std[0], t.std[1], t.std[2] }, { 0, 0, 0 }, { 0, 0, 0 } };
-    for (int c = 0; c < 3; c++) {
-        const double q = std::floor(255.0 * rm.pad[c] + 0.5), nrm = ((double)rm.pad[c] - t.mean[c]) / t.std[c];
-        rargs.pad[c] = t.dtype == h264k::TO_U8 ? (float)q : (float)nrm;
-        rargs.spad[c] = ref ? (float)q : t.dtype == h264k::TO_U8 ? (float)(255.0 * rm.pad[c]) : (float)nrm;
-    }
-    const uint32_t blocks = (t.width + h264k::TRM_COLS - 1u) / h264k::TRM_COLS * ((t.height + h264k::TRM_ROWS - 1u) / h264k::TRM_ROWS);
-    void *args[] = { &rargs };
-    HIP_TRY(hipLaunchKernel(fn, dim3(std::min(blocks, 1024u), n_maps), dim3(256), args, 0, st));
-    return pull_end_locked(e, n, pics, st, fence_ev);
+    /* pad: a non-finite coordinate; spad: outside the window */
+    h264k::RemapArgs rargs{ staged_items_dev<h264k::RemapItem>(e), t.width, t.height, chroma, rm.filter, rm.border, {}, {}, {}, {} };
+    const PullPad pp = fold_pad(rm.pad, t.dtype, t.mean, t.std, ref);
+    copy3(rargs.mean, t.mean); copy3(rargs.std, t.std); copy3(rargs.pad, pp.pad); copy3(rargs.spad, pp.spad);
+    return pull_launch_locked(e, n, pics, st, fn, pull_grid(t.width, t.height, h264k::TRM_COLS, h264k::TRM_ROWS, n_maps), &rargs, fence_ev);
 }
 
-/* JobSink.tensor_out (h264bsdmiNextOutputTensorBatch[Colour|Resize]), JobSink.tensor_regions (regions != nullptr),
- * JobSink.motion_regions (motion != nullptr: spec, chroma and resize are not used) and JobSink.tensor_remap (rmaps != nullptr: n_regions
- * counts the maps) */
-static int sink_tensor_call(uint32_t n, const SinkTensorPic *pics, uint32_t n_regions, const SinkRegion *regions,
-                            const h264bsdmi_tensor_spec *spec, uint32_t chroma, const h264bsdmi_resize_spec *resize, void *stream,
-                            const h264bsdmi_motion_spec *motion = nullptr, const SinkRemap *rmaps = nullptr,
-                            const h264bsdmi_remap_spec *remap = nullptr)
+/* What JobSink.tensor_out, tensor_regions, motion_regions and tensor_remap share: one engine (one device) per call, its mutex, the
+ * refusal of a capturing stream, and, when the caller gave no stream, the wait for the fence and the device's error words.
+ * body(e, st, &fence_ev): the call's own *_out_locked. */
+template <typename Body> static int sink_tensor_call(uint32_t n, const SinkTensorPic *pics, void *stream, Body body)
 {
     if (!n) return 0;
-    if (!pics || (!spec && !motion)) return -1;
+    if (!pics) return -1;
     Engine *e = static_cast<SinkUser *>(pics[0].sink->user)->e;
     for (uint32_t i = 1; i < n; i++)
         if (static_cast<SinkUser *>(pics[i].sink->user)->e != e) return -1;        /* one device per call */
@@ -1500,9 +1519,7 @@ static int sink_tensor_call(uint32_t n, const SinkTensorPic *pics, uint32_t n_re
             HIP_TRY(hipStreamIsCapturing(st, &cs));
             if (cs != hipStreamCaptureStatusNone) return -1;                      /* graph capture of this call is not supported */
         }
-        if (rmaps ? remap_out_locked(e, n, pics, n_regions, rmaps, *spec, chroma, *remap, st, &fence_ev)
-            : motion ? motion_out_locked(e, n, pics, n_regions, regions, *motion, st, &fence_ev)
-                   : tensor_out_locked(e, n, pics, n_regions, regions, *spec, chroma, resize, st, &fence_ev)) return -1;
+        if (body(e, st, &fence_ev)) return -1;
     }
     if (stream) return 0;
     if (hipEventSynchronize(fence_ev) != hipSuccess) return -1;        /* (a later call may have recorded it again: that only waits longer) */
@@ -1513,28 +1530,37 @@ static int sink_tensor_call(uint32_t n, const SinkTensorPic *pics, uint32_t n_re
 int sink_tensor_out(uint32_t n, const SinkTensorPic *pics, const h264bsdmi_tensor_spec *spec, uint32_t chroma,
                     const h264bsdmi_resize_spec *resize, void *stream)
 {
-    return sink_tensor_call(n, pics, 0, nullptr, spec, chroma, resize, stream);
+    if (n && !spec) return -1;
+    return sink_tensor_call(n, pics, stream, [&](Engine *e, hipStream_t st, hipEvent_t *fence_ev) {
+        return tensor_out_locked(e, n, pics, *spec, chroma, resize, st, fence_ev);
+    });
 }
 int sink_tensor_regions(uint32_t n, const SinkTensorPic *pics, uint32_t n_regions, const SinkRegion *regions,
                         const h264bsdmi_tensor_spec *spec, uint32_t chroma, const h264bsdmi_resize_spec *resize, void *stream)
 {
     if (!n_regions) return 0;
-    if (!regions || !resize) return -1;
-    return sink_tensor_call(n, pics, n_regions, regions, spec, chroma, resize, stream);
+    if (!regions || !resize || (n && !spec)) return -1;
+    return sink_tensor_call(n, pics, stream, [&](Engine *e, hipStream_t st, hipEvent_t *fence_ev) {
+        return regions_out_locked(e, n, pics, n_regions, regions, *spec, chroma, *resize, st, fence_ev);
+    });
 }
 int sink_motion_regions(uint32_t n, const SinkTensorPic *pics, uint32_t n_regions, const SinkRegion *regions,
                         const h264bsdmi_motion_spec *spec, void *stream)
 {
     if (!n_regions) return 0;
     if (!regions || !spec) return -1;
-    return sink_tensor_call(n, pics, n_regions, regions, nullptr, 0, nullptr, stream, spec);
+    return sink_tensor_call(n, pics, stream, [&](Engine *e, hipStream_t st, hipEvent_t *fence_ev) {
+        return motion_out_locked(e, n, pics, n_regions, regions, *spec, st, fence_ev);
+    });
 }
 int sink_tensor_remap(uint32_t n, const SinkTensorPic *pics, uint32_t n_maps, const SinkRemap *maps,
                       const h264bsdmi_tensor_spec *spec, uint32_t chroma, const h264bsdmi_remap_spec *remap, void *stream)
 {
     if (!n_maps) return 0;
     if (!maps || !spec || !remap) return -1;
-    return sink_tensor_call(n, pics, n_maps, nullptr, spec, chroma, nullptr, stream, nullptr, maps, remap);
+    return sink_tensor_call(n, pics, stream, [&](Engine *e, hipStream_t st, hipEvent_t *fence_ev) {
+        return remap_out_locked(e, n, pics, n_maps, maps, *spec, chroma, *remap, st, fence_ev);
+    });
 }
 /* JobSink.set_motion (h264bsdmiSetMotionExport): before the instance's first sequence is configured */
 int sink_set_motion(void *user, int on)

@@ -1,7 +1,9 @@
 /* kernels/k_tensor_out.hip.h — k_tensor_out / k_tensor_resize: the next pictures of many decoder instances into ONE dense
- * caller-owned tensor (h264bsdmiNextOutputTensorBatch[Colour]), one launch per call, grid.y = one item per picture.  Included by
- * engine.hip AFTER kernels.hip.h (whose helpers it uses: luma_at, chroma_at, yuv_pixel); not part of the kernel sources that key the committed
- * counter tables (srchash.py).
+ * caller-owned tensor (h264bsdmiNextOutputTensorBatch[Colour]), one launch per call, grid.y = one item per picture — and the pieces
+ * the other tensor headers share, one definition each: the item and the element encoders, the window's chroma (TcWin), the colour of
+ * a sample (tc_pixel), the 8-sample segment (tc_chroma_seg, tc_seg) and the 2 x 2 blend (tc_blend).  Included by engine.hip AFTER
+ * kernels.hip.h (whose helpers it uses: luma_at, chroma_at, yuv_pixel) and BEFORE k_tensor_aa.hip.h, k_tensor_roi.hip.h and
+ * k_tensor_remap.hip.h, in that order; not part of the kernel sources that key the committed counter tables (srchash.py).
  *
  * Colour: per source pixel and output channel c, v = med3(k[c][0] Y + k[c][3] + k[c][1] (Cb - 128) + k[c][2] (Cr - 128), lo[c], hi[c])
  * in fp32 on the 8-bit samples (Cb, Cr upsampled first when bilinear; centred, and luma first, so that no intermediate holds a large
@@ -126,6 +128,71 @@ __device__ __forceinline__ void tc_chroma_seg(float *out, const uint8_t *__restr
     for (int k = 0; k < TO_SEG; k++) out[k] = ((k & 1) ? 0.5f * (v[k >> 1] + v[(k >> 1) + 1]) : v[k >> 1]) - 128.0f;
 }
 
+/* The chroma of a picture's source window, once per kernel: bil (bilinear upsampling; never for REF), the window's last chroma column
+ * chi and its first and last chroma rows rlo, rhi (what the neighbours of the bilinear chroma are clamped to), and the coded chroma
+ * width ccw */
+struct TcWin {
+    bool bil;
+    uint32_t chi, rlo, rhi, ccw;
+    /* the neighbour chroma row of luma row sy: the one above for even sy, below for odd sy, inside the window */
+    __device__ __forceinline__ uint32_t nb(uint32_t sy) const
+    {
+        const uint32_t cy = sy >> 1;
+        return (sy & 1u) ? min(cy + 1u, rhi) : max(cy, rlo + 1u) - 1u;
+    }
+};
+template <bool REF> __device__ __forceinline__ TcWin tc_win(const TensorItem &it, uint32_t chroma)
+{
+    return TcWin{ !REF && chroma == TC_BILINEAR, (it.x0 + it.w) / 2u - 1u, it.y0 / 2u, (it.y0 + it.h) / 2u - 1u, it.wmb * 8u };
+}
+
+/* the colour of one sample (y, cb, cr: luma and chroma minus 128) into p[0 .. NC); REF: the 8-bit values */
+template <int NC, bool REF> __device__ __forceinline__ void tc_pixel(float *p, const TensorItem &it, float y, float cb, float cr)
+{
+    if constexpr (NC == 1) p[0] = __builtin_amdgcn_fmed3f(fmaf(it.k[0][0], y, it.k[0][3]), it.lo[0], it.hi[0]);
+    else {
+#pragma unroll
+        for (int c = 0; c < 3; c++) p[c] = tc_value(it, c, y, cb, cr);
+    }
+    if constexpr (REF) {
+#pragma unroll
+        for (int c = 0; c < NC; c++) p[c] = __builtin_truncf(p[c]);
+    }
+}
+
+/* the 8 luma samples yv (byte k = column sx + k, sx even) of row sy with their chroma (word loads, tc_chroma_seg) converted by
+ * tc_pixel: put(k, p) receives sample k's p[0 .. NC) */
+template <int NC, bool REF, typename Put>
+__device__ __forceinline__ void tc_seg(const TensorItem &it, int wmb, const TcWin &w, unsigned long long yv, uint32_t sx, uint32_t sy, Put &&put)
+{
+    float cb[TO_SEG] = {}, cr[TO_SEG] = {};     /* (NC == 1: not read by tc_pixel, but passed to it) */
+    if constexpr (NC == 3) {
+        const uint32_t nb = w.nb(sy);
+        tc_chroma_seg(cb, it.src, wmb, 0, sx, sy, w.ccw, w.bil, nb, w.chi);
+        tc_chroma_seg(cr, it.src, wmb, 1, sx, sy, w.ccw, w.bil, nb, w.chi);
+    }
+#pragma unroll
+    for (int k = 0; k < TO_SEG; k++) {
+        float p[NC];
+        tc_pixel<NC, REF>(p, it, (float)(uint32_t)((yv >> (8 * k)) & 255u), cb[k], cr[k]);
+        put(k, p);
+    }
+}
+
+/* the 2 x 2 blend of the resampling kernels with the weights lx, ly of the second column and row: a + l (b - a), which keeps equal
+ * neighbours exact; REF as the reference path has it: hy (hx v00 + lx v01) + ly (hx v10 + lx v11) with three FMAs in a fixed order */
+template <bool REF> __device__ __forceinline__ float tc_blend(float v00, float v01, float v10, float v11, float lx, float ly)
+{
+    if constexpr (REF) {
+#pragma clang fp contract(off)
+        const float hx = 1.0f - lx, hy = 1.0f - ly;
+        return fmaf(hy, fmaf(hx, v00, lx * v01), ly * fmaf(hx, v10, lx * v11));
+    } else {
+        const float top = fmaf(lx, v01 - v00, v00), bot = fmaf(lx, v11 - v10, v10);
+        return fmaf(ly, bot - top, top);
+    }
+}
+
 /* No resize: the output is the source window pixel for pixel.  A wavefront covers 64 output columns x 16 rows in two passes of 8 rows; a
  * lane takes 8 horizontally adjacent pixels of one row: ONE 8-byte luma load when the window starts on a multiple of 8 columns (the two
  * rows of a chroma row pair are in the same pass), two otherwise (funnel shift).  Chroma: 2 word loads per plane and row when the window
@@ -147,8 +214,7 @@ __global__ __launch_bounds__(256) void k_tensor_out(TensorArgs a)
     const TensorItem it = a.items[blockIdx.y];
     const uint32_t W = a.width, H = a.height, cw = it.wmb * 16u;
     const int wmb = (int)it.wmb;
-    const bool bil = !REF && a.chroma == TC_BILINEAR;
-    const uint32_t chi = (it.x0 + it.w) / 2u - 1u, rlo = it.y0 / 2u, rhi = (it.y0 + it.h) / 2u - 1u;      /* the window's chroma */
+    const TcWin win = tc_win<REF>(it, a.chroma);
     const uint32_t nux = (W + 63u) / 64u, units = nux * ((H + 15u) / 16u);
     const uint32_t lane = threadIdx.x & 63u, wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const uint32_t seg = lane & 7u, r = lane >> 3;
@@ -183,9 +249,9 @@ __global__ __launch_bounds__(256) void k_tensor_out(TensorArgs a)
                     cbw >>= cs; crw >>= cs;
                 }
             } else if constexpr (NC == 3) {
-                const uint32_t cy = sy >> 1, nb = (sy & 1u) ? min(cy + 1u, rhi) : max(cy, rlo + 1u) - 1u;
-                tc_chroma_seg(cb, it.src, wmb, 0, sx, sy, cw >> 1, bil, nb, chi);
-                tc_chroma_seg(cr, it.src, wmb, 1, sx, sy, cw >> 1, bil, nb, chi);
+                const uint32_t nb = win.nb(sy);
+                tc_chroma_seg(cb, it.src, wmb, 0, sx, sy, cw >> 1, win.bil, nb, win.chi);
+                tc_chroma_seg(cr, it.src, wmb, 1, sx, sy, cw >> 1, win.bil, nb, win.chi);
             }
             E v[TO_SEG * C];
 #pragma unroll
@@ -236,21 +302,18 @@ template <bool REF> __device__ __forceinline__ void tcr_coord(uint32_t o, float 
 
 /* the colour of source pixel (x, y) of the window (absolute coordinates), into p[0 .. NC); REF: the 8-bit values */
 template <int NC, bool REF>
-__device__ __forceinline__ void tcr_convert(float *p, const TensorItem &it, int wmb, bool bil, uint32_t x, uint32_t y,
-                                            uint32_t chi, uint32_t rlo, uint32_t rhi)
+__device__ __forceinline__ void tcr_convert(float *p, const TensorItem &it, int wmb, const TcWin &w, uint32_t x, uint32_t y)
 {
     const uint8_t *__restrict__ src = it.src;
     const float Y = (float)src[luma_at(wmb, (int)x, (int)y)];
-    if constexpr (NC == 1) {
-        p[0] = __builtin_amdgcn_fmed3f(fmaf(it.k[0][0], Y, it.k[0][3]), it.lo[0], it.hi[0]);
-    } else {
+    float cc[2] = { 0.0f, 0.0f };
+    if constexpr (NC == 3) {
         const uint32_t c0 = x >> 1, r0 = y >> 1;
-        float cc[2];
-        if (!bil) {
+        if (!w.bil) {
 #pragma unroll
             for (int q = 0; q < 2; q++) cc[q] = (float)src[chroma_at(wmb, q, (int)c0, (int)r0)];
         } else {
-            const uint32_t c1 = min(c0 + (x & 1u), chi), r1 = (y & 1u) ? min(r0 + 1u, rhi) : max(r0, rlo + 1u) - 1u;
+            const uint32_t c1 = min(c0 + (x & 1u), w.chi), r1 = w.nb(y);
 #pragma unroll
             for (int q = 0; q < 2; q++) {
                 const float a0 = (float)src[chroma_at(wmb, q, (int)c0, (int)r0)], a1 = (float)src[chroma_at(wmb, q, (int)c1, (int)r0)];
@@ -258,20 +321,14 @@ __device__ __forceinline__ void tcr_convert(float *p, const TensorItem &it, int 
                 cc[q] = fmaf(0.25f, 0.5f * (b0 + b1), 0.75f * (0.5f * (a0 + a1)));
             }
         }
-#pragma unroll
-        for (int c = 0; c < 3; c++) p[c] = tc_value(it, c, Y, cc[0] - 128.0f, cc[1] - 128.0f);
     }
-    if constexpr (REF) {
-#pragma unroll
-        for (int c = 0; c < NC; c++) p[c] = __builtin_truncf(p[c]);
-    }
+    tc_pixel<NC, REF>(p, it, Y, cc[0] - 128.0f, cc[1] - 128.0f);
 }
 
 /* Resize.  A workgroup takes an output tile of 64 columns x 8 rows at a time.  Phase 1: the tile's 8 x 2 source rows (y0, y1 of each
  * output row) times its 64 x 2 source columns (x0, x1 of each output column) are converted, one source pixel per slot and lane, 8 per
  * lane, into LDS; the loads of the 2048 slots are independent of each other.  Phase 2: each lane interpolates 2 output pixels from LDS
- * as a + l (b - a), which keeps equal neighbours exact (U8 rounds exact halves to even, as the model does), and stores them; REF as
- * the reference path has: hy (hx v00 + lx v01) + ly (hx v10 + lx v11) with three FMAs in a fixed order, U8 rounding halves up.  Slots
+ * (tc_blend; U8 rounds exact halves to even, as the model does, REF halves up) and stores them.  Slots
  * are not shared between neighbouring output rows or columns: when upscaling, a source pixel may be converted once per slot that
  * names it. */
 template <int DT, int LAYOUT, int C, bool REF>
@@ -283,8 +340,7 @@ __global__ __launch_bounds__(256) void k_tensor_resize(TensorArgs a)
     const TensorItem it = a.items[blockIdx.y];
     const uint32_t W = a.width, H = a.height;
     const int wmb = (int)it.wmb;
-    const bool bil = !REF && a.chroma == TC_BILINEAR;
-    const uint32_t chi = (it.x0 + it.w) / 2u - 1u, rlo = it.y0 / 2u, rhi = (it.y0 + it.h) / 2u - 1u;
+    const TcWin win = tc_win<REF>(it, a.chroma);
     const float scale_x = (float)it.w / (float)W, scale_y = (float)it.h / (float)H;
     const uint32_t nux = (W + TCR_COLS - 1u) / TCR_COLS, units = nux * ((H + TCR_ROWS - 1u) / TCR_ROWS);
     const size_t plane = (size_t)W * H;
@@ -302,7 +358,7 @@ __global__ __launch_bounds__(256) void k_tensor_resize(TensorArgs a)
             tcr_coord<REF>(oy, scale_y, yi, ly);
             const uint32_t x = (cb & 1u) ? (uint32_t)min(xi + 1, (int)it.w - 1) : (uint32_t)xi;
             const uint32_t y = (ra & 1u) ? (uint32_t)min(yi + 1, (int)it.h - 1) : (uint32_t)yi;
-            tcr_convert<NC, REF>(lds[ra][cb], it, wmb, bil, it.x0 + x, it.y0 + y, chi, rlo, rhi);
+            tcr_convert<NC, REF>(lds[ra][cb], it, wmb, win, it.x0 + x, it.y0 + y);
         }
         __syncthreads();
 #pragma unroll
@@ -320,18 +376,11 @@ __global__ __launch_bounds__(256) void k_tensor_resize(TensorArgs a)
                 E e;
                 if (c == 3) e = tc_alpha<DT>();
                 else {
-                    const float v00 = lds[2 * r][2 * j][c], v01 = lds[2 * r][2 * j + 1][c];
-                    const float v10 = lds[2 * r + 1][2 * j][c], v11 = lds[2 * r + 1][2 * j + 1][c];
-                    if constexpr (REF) {
-#pragma clang fp contract(off)
-                        const float hx = 1.0f - lx, hy = 1.0f - ly;
-                        const float v = fmaf(hy, fmaf(hx, v00, lx * v01), ly * fmaf(hx, v10, lx * v11));
-                        if constexpr (DT == TO_U8) e = (E)min(255, (int)(v + 0.5f));
-                        else e = to_enc<DT>((v / 255.0f - a.mean[c]) / a.std[c]);
-                    } else {
-                        const float top = fmaf(lx, v01 - v00, v00), bot = fmaf(lx, v11 - v10, v10);
-                        e = tc_enc<DT>(fmaf(ly, bot - top, top));
-                    }
+                    const float v = tc_blend<REF>(lds[2 * r][2 * j][c], lds[2 * r][2 * j + 1][c], lds[2 * r + 1][2 * j][c],
+                                                  lds[2 * r + 1][2 * j + 1][c], lx, ly);
+                    if constexpr (!REF) e = tc_enc<DT>(v);
+                    else if constexpr (DT == TO_U8) e = (E)min(255, (int)(v + 0.5f));     /* (not the shared tail's fmed3 form) */
+                    else e = to_enc<DT>((v / 255.0f - a.mean[c]) / a.std[c]);
                 }
                 if constexpr (LAYOUT == TO_NCHW) dst[c * plane + pix] = e;
                 else dst[pix * C + c] = e;

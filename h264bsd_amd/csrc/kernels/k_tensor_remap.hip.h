@@ -1,7 +1,7 @@
 /* kernels/k_tensor_remap.hip.h — k_tensor_remap: current pictures sampled through caller-supplied coordinate maps, each map into its
  * own slice of the caller's tensor (h264bsdmiOutputTensorRemap), one launch per call, grid.y = one item per map.  Included by
- * engine.hip AFTER k_tensor_roi.hip.h; it uses the helpers of k_tensor_out.hip.h (tc_value, the element encoders) and, like the other
- * tensor kernels, is not part of the kernel sources that key the committed counter tables (srchash.py).
+ * engine.hip AFTER k_tensor_roi.hip.h; it uses the helpers of k_tensor_out.hip.h (TcWin, tc_pixel, tc_blend, the element encoders) and,
+ * like the other tensor kernels, is not part of the kernel sources that key the committed counter tables (srchash.py).
  *
  * The coordinates are data: map[oy][ox] = (mx, my), a position in luma samples of the picture's source WINDOW (x0, y0, w, h of the
  * TensorItem), sample (u, v) AT (u, v).  There is no projective arithmetic here: a finite map value is clamped in fp32 ([-1, w]
@@ -14,8 +14,9 @@
  * pad under the scale of the converted samples (spad, as in k_tensor_roi).  The four neighbours share their chroma: per plane the
  * quad needs at most the chroma columns cA, cA + 1 (cA that of the first neighbour) and the rows rA - 1, rA, rA + 1, so 2 x 3 samples
  * per plane are loaded once (2 x 2 with nearest chroma) and every neighbour picks its own by comparing indices — 4 + 12 byte loads
- * for a pixel instead of the 36 of four independent conversions.  The chroma arithmetic per neighbour is tcr_convert's, the blend and
- * the output encoding are k_tensor_resize's for the same REF; NEAREST is the same path with one neighbour and weights 0.  No
+ * for a pixel instead of the 36 of four independent conversions.  The chroma arithmetic per neighbour is tcr_convert's, the blend is
+ * k_tensor_resize's (tc_blend) and the store tail is the one of k_tensor_aa.hip.h's tile body for the same REF; NEAREST is the same
+ * path with one neighbour and weights 0.  No
  * antialiasing: a map that shrinks the picture aliases. */
 #pragma once
 namespace h264k {
@@ -33,9 +34,11 @@ struct RemapArgs { const RemapItem *items; uint32_t width, height, chroma, filte
  * X, Y: absolute frame coordinates INSIDE the window with X[1] - X[0], Y[1] - Y[0] in {0, 1}; ok[k]: the neighbour is part of the
  * picture (else it takes spad and nothing is loaded for it). */
 template <int NC, bool REF>
-__device__ __forceinline__ void trm_quad(float (*q)[NC], const TensorItem &it, int wmb, bool bil, int nk, const uint32_t *X, const uint32_t *Y,
-                                         const bool *ok, uint32_t chi, uint32_t rlo, uint32_t rhi, const float *spad)
+__device__ __forceinline__ void trm_quad(float (*q)[NC], const TensorItem &it, int wmb, const TcWin &w, int nk, const uint32_t *X, const uint32_t *Y,
+                                         const bool *ok, const float *spad)
 {
+    const bool bil = w.bil;
+    const uint32_t chi = w.chi, rlo = w.rlo, rhi = w.rhi;
     const uint8_t *__restrict__ src = it.src;
     const bool any = ok[0] || ok[1] || ok[2] || ok[3];
     float P[2][3][2];       /* plane, chroma row R[.], chroma column cA / cB */
@@ -56,14 +59,11 @@ __device__ __forceinline__ void trm_quad(float (*q)[NC], const TensorItem &it, i
         if (k >= nk) continue;
         const uint32_t x = X[k & 1], y = Y[k >> 1];
         const float Yv = ok[k] ? (float)src[luma_at(wmb, (int)x, (int)y)] : 0.0f;
-        float t[NC];
-        if constexpr (NC == 1) {
-            t[0] = __builtin_amdgcn_fmed3f(fmaf(it.k[0][0], Yv, it.k[0][3]), it.lo[0], it.hi[0]);
-        } else {
+        float t[NC], cc[2] = { 0.0f, 0.0f };
+        if constexpr (NC == 3) {
             const uint32_t c0 = x >> 1, r0 = y >> 1;
             const uint32_t c1 = bil ? min(c0 + (x & 1u), chi) : c0;
-            const uint32_t r1 = !bil ? r0 : (y & 1u) ? min(r0 + 1u, rhi) : max(r0, rlo + 1u) - 1u;
-            float cc[2];
+            const uint32_t r1 = !bil ? r0 : w.nb(y);
 #pragma unroll
             for (int p = 0; p < 2; p++) {
                 /* rows r0, r1 of the patch: equal indices hold equal samples, so the comparison picks the right one under the clamps */
@@ -74,11 +74,10 @@ __device__ __forceinline__ void trm_quad(float (*q)[NC], const TensorItem &it, i
                 const float rb0 = c0 == cA ? b0 : b1, rb1 = c1 == cA ? b0 : b1;
                 cc[p] = bil ? fmaf(0.25f, 0.5f * (rb0 + rb1), 0.75f * (0.5f * (ra0 + ra1))) : ra0;
             }
-#pragma unroll
-            for (int c = 0; c < 3; c++) t[c] = tc_value(it, c, Yv, cc[0] - 128.0f, cc[1] - 128.0f);
         }
+        tc_pixel<NC, REF>(t, it, Yv, cc[0] - 128.0f, cc[1] - 128.0f);
 #pragma unroll
-        for (int c = 0; c < NC; c++) q[k][c] = !ok[k] ? spad[c] : REF ? __builtin_truncf(t[c]) : t[c];
+        for (int c = 0; c < NC; c++) q[k][c] = !ok[k] ? spad[c] : t[c];
     }
 }
 
@@ -93,8 +92,8 @@ __global__ __launch_bounds__(256) void k_tensor_remap(RemapArgs a)
     const TensorItem &it = ri.t;
     const uint32_t W = a.width, H = a.height, tid = threadIdx.x;
     const int wmb = (int)it.wmb, ww = (int)it.w, wh = (int)it.h;
-    const bool bil = !REF && a.chroma == TC_BILINEAR, nearest = a.filter == TR_NEAREST, rep = a.border == TR_REPLICATE;
-    const uint32_t chi = (it.x0 + it.w) / 2u - 1u, rlo = it.y0 / 2u, rhi = (it.y0 + it.h) / 2u - 1u;
+    const bool nearest = a.filter == TR_NEAREST, rep = a.border == TR_REPLICATE;
+    const TcWin win = tc_win<REF>(it, a.chroma);
     const float xlo = rep ? 0.0f : -1.0f, xhi = rep ? (float)(ww - 1) : (float)ww;
     const float ylo = rep ? 0.0f : -1.0f, yhi = rep ? (float)(wh - 1) : (float)wh;
     const uint32_t nux = (W + TRM_COLS - 1u) / TRM_COLS, units = nux * ((H + TRM_ROWS - 1u) / TRM_ROWS);
@@ -124,24 +123,16 @@ __global__ __launch_bounds__(256) void k_tensor_remap(RemapArgs a)
             const uint32_t X[2] = { it.x0 + (uint32_t)min(max(xi[0], 0), ww - 1), it.x0 + (uint32_t)min(max(xi[1], 0), ww - 1) };
             const uint32_t Y[2] = { it.y0 + (uint32_t)min(max(yi[0], 0), wh - 1), it.y0 + (uint32_t)min(max(yi[1], 0), wh - 1) };
             float q[4][NC];
-            trm_quad<NC, REF>(q, it, wmb, bil, nearest ? 1 : 4, X, Y, ok, chi, rlo, rhi, spad);
+            trm_quad<NC, REF>(q, it, wmb, win, nearest ? 1 : 4, X, Y, ok, spad);
             if (nearest) {
 #pragma unroll
                 for (int c = 0; c < NC; c++) acc[c] = q[0][c];
             } else {
 #pragma unroll
-                for (int c = 0; c < NC; c++) {
-                    if constexpr (REF) {
-#pragma clang fp contract(off)
-                        const float hx = 1.0f - lx, hy = 1.0f - ly;
-                        acc[c] = fmaf(hy, fmaf(hx, q[0][c], lx * q[1][c]), ly * fmaf(hx, q[2][c], lx * q[3][c]));
-                    } else {
-                        const float top = fmaf(lx, q[1][c] - q[0][c], q[0][c]), bot = fmaf(lx, q[3][c] - q[2][c], q[2][c]);
-                        acc[c] = fmaf(ly, bot - top, top);
-                    }
-                }
+                for (int c = 0; c < NC; c++) acc[c] = tc_blend<REF>(q[0][c], q[1][c], q[2][c], q[3][c], lx, ly);
             }
         }
+        /* the store tail of ta_tile_body (k_tensor_aa.hip.h), statement for statement: change both or neither */
 #pragma unroll
         for (int c = 0; c < C; c++) {
             E e;
