@@ -1,7 +1,7 @@
 /*
  * engine.hip — host side of the HIP engine: device context, per-decoder DPB in HBM (macroblock tiles,
- * kernels.hip.h), lazy batched execution of queued frame jobs ("ticks"), and the HBM-resident replay sets used by
- * bench.py and the kernel tests (exported by the bench library only, include/h264bsd_mi355x_bench.h).
+ * kernels.hip.h), lazy batched execution of queued frame jobs ("ticks").  The HBM-resident replay sets used by bench.py and
+ * the kernel tests (the bench library's include/h264bsd_mi355x_bench.h) are replay.hip.h, included at the end.
  *
  * Execution model.  A tick holds at most one picture per stream (pictures of one stream depend on each other
  * through the DPB; pictures of different streams never do).  A tick of N pictures is SIX launches (launch_tick):
@@ -38,6 +38,7 @@
 #include "kernels/k_motion.hip.h"
 #include "engine.h"
 #include "hip_owned.h"
+#include "tick_plan.h"
 #include "../../include/h264bsd_mi355x_bench.h"
 
 #define HIP_TRY(expr)                                                                              \
@@ -121,14 +122,9 @@ struct Lane {
     hipStream_t st = nullptr;                  /* own_st, or the engine's stream (single-lane engine) */
     Stream own_st;
     DeviceMem<uint8_t> d_arena; size_t arena_cap = 0;      /* device copies of the blobs of one tick */
-    DeviceMem<FrameDesc> d_desc; Pinned<FrameDesc> h_desc; size_t desc_cap = 0;    /* h_desc: pinned staging, 2 halves */
-    Pinned<h264k::H2dItem> h_items;            /* pinned, 2 halves like h_desc: the tick's jobs for k_h2d (h_items.dev(): the device's view of it) */
-    /* k_motion_keep's items: pinned, 2 halves of mitem_cap used in turn, each guarded by the event behind the launch that read it
-     * (allocated by the first tick that holds a picture of an instance with motion export) */
-    Pinned<h264k::MotionKeepItem> h_mitems; size_t mitem_cap = 0;
-    Event mitem_ev[2]; bool mitem_used[2] = { false, false }; int mitem_flip = 0;
-    int flip = 0; unsigned ticks = 0;
-    Event desc_ev[2];
+    DeviceMem<FrameDesc> d_desc; Staged<FrameDesc> descs;      /* the tick's descriptors: device copy (descs.cap() of them), staging ring */
+    Pinned<h264k::H2dItem> h_items;            /* pinned, 2 halves of descs.cap() under the guard of descs' halves: the tick's jobs for k_h2d (h_items.dev(): the device's view of it) */
+    Staged<h264k::MotionKeepItem> mitems;      /* k_motion_keep's items (allocated by the first tick that holds a picture of an instance with motion export) */
     static constexpr unsigned RING = 64;
     Event ring[RING];
     unsigned long long launches = 0;
@@ -153,6 +149,11 @@ constexpr unsigned CONVERT_WGS = CONVERT_WGS_N;      /* workgroups per picture o
 #endif
 constexpr uint32_t LANE_DBK_WAVES = LANE_DBK_WAVES_N;
 
+/* the item stride of the tensor pulls' staging ring: k_tensor_out / k_tensor_resize read TensorItems, k_tensor_aa AaItems, k_tensor_roi
+ * RoiItems, k_motion_roi MotionItems, k_tensor_remap RemapItems */
+constexpr size_t TITEM_BYTES = std::max({ sizeof(h264k::TensorItem), sizeof(h264k::AaItem), sizeof(h264k::RoiItem), sizeof(h264k::MotionItem),
+                                          sizeof(h264k::RemapItem) });
+struct TItemSlot { uint8_t bytes[TITEM_BYTES]; };
 struct Engine {
     std::mutex mu;
     int device = 0;
@@ -173,10 +174,8 @@ struct Engine {
     uint32_t error_events = 0;                 /* how often a tripwire fired, ever: monotonic, so that a NEW occurrence of a bit that is
                                                   already set is visible (per-decoder copy-elision guard, the tests' delta) */
     DeviceMem<unsigned long long> tail_prof;   /* debug: per-wave cycle accounting of the per-picture kernels (block 0) */
-    /* tensor pulls (tensor_out_locked): TensorItems (AaItems for k_tensor_aa) staged in pinned memory, two halves of titem_cap items
-     * used in turn, each guarded by the event recorded behind the launch that read it; fence events that no instance holds any more */
-    Pinned<uint8_t> h_titems; size_t titem_cap = 0;
-    Event titem_ev[2]; bool titem_used[2] = { false, false }; int titem_flip = 0;
+    /* tensor pulls (tensor_out_locked): the staging ring of their items; fence events that no instance holds any more */
+    Staged<TItemSlot> titems;
     std::vector<Fence *> fences;
 };
 
@@ -278,8 +277,6 @@ static int lanes_create(Engine *e)
         Lane &l = lanes[i];
         if (g == 1 && i == 0) { l.st = e->stream; l.side = &e->side; }      /* the single-lane engine: k_dbk next to the reconstruction kernels */
         else { HIP_TRY(l.own_st.create()); l.st = l.own_st; }
-        HIP_TRY(l.desc_ev[0].create(hipEventDisableTiming));
-        HIP_TRY(l.desc_ev[1].create(hipEventDisableTiming));
         HIP_TRY(l.tail.create(hipEventDisableTiming));
         for (auto &ev : l.ring) HIP_TRY(ev.create(hipEventDisableTiming));
     }
@@ -311,25 +308,7 @@ Engine *engine_get(int device = -1)
     return g_engines[device] = e.release();
 }
 
-/* ---- how the two per-picture kernels split a picture (row bands, kernels.hip.h) ----
- * rows per band for light / heavy pictures (heavy = more than a quarter of the macroblocks intra coded), wavefronts per
- * workgroup, and a cap on the bands of one launch.  H264BSDMI_TAIL="dbk_rows_light,dbk_rows_heavy,dbk_waves,intra_rows_light,
- * intra_rows_heavy,intra_waves" overrides the defaults (0 rows = one band); h264bsdmiDebugSetTail() does the same for tests. */
-struct TailConfig {
-    uint32_t dbk_rows_light = 17, dbk_rows_heavy = 9, dbk_waves = 12;
-    uint32_t dbk_chroma_waves = 0;        /* wavefronts of a k_frame_dbk workgroup that start on the chroma graph; 0 = five twelfths */
-    uint32_t intra_rows_light = 0, intra_rows_heavy = 9, intra_waves = 12;
-    /* A picture is only split where that puts idle compute units to work: a launch gets at most band_budget workgroups
-     * (bands per picture <= band_budget / pictures of the tick, at least 1).  256 pictures in lock-step: one workgroup per
-     * picture and compute unit (measured: 4 bands x 4 wavefronts 92 instead of 57 ms per step in k_frame_dbk — a picture's
-     * filtering needs about one compute unit's worth of instruction issue whichever way it is cut); the small ticks of
-     * stream groups and heavy lanes: several workgroups per picture.  H264BSDMI_BAND_BUDGET overrides. */
-    uint32_t band_budget = 320;
-    /* ... and the heavy pictures of a tick that has the device to itself share heavy_budget further workgroups: the compute
-     * units the tick's light pictures leave idle long before its heavy ones are done (H264BSDMI_HEAVY_BUDGET) */
-    uint32_t heavy_budget = 64;
-    bool from_env = false;
-};
+/* how the two per-picture kernels split a picture: TailConfig (tick_plan.h), with the overrides of the environment read once */
 TailConfig g_tail;
 std::mutex g_tail_mu;
 TailConfig tail_config()
@@ -393,25 +372,7 @@ static void tickets_rezero(int dev)
     for (auto &p : g_tickets[dev]) (void)hipMemsetAsync(p.second, 0, 64, p.first);
 }
 
-/* ---- launch of one tick ---- */
-struct TickShape {
-    uint32_t n_frames = 0, max_mbs = 0;
-    uint32_t max_copy = 0, max_gen = 0, max_gen_uni = 0, max_gen_quad = 0, max_gen_rest = 0, max_dbk = 0, max_levels = 0, max_w = 0, max_h = 0;
-    bool any_tail = false, any_deblock = false;
-    uint32_t dbk_waves = 0;          /* wavefronts per workgroup of k_frame_dbk; 0 = the configured default (launch_tick) */
-    /* row bands of the two per-picture kernels: most bands a light / a heavy picture of the tick wants, for k_frame_dbk [0]
-     * and k_frame_intra [1]; number of heavy pictures (more than a quarter of the macroblocks intra coded) */
-    uint32_t want_light[2] = { 1, 1 }, want_heavy[2] = { 1, 1 }, n_heavy = 0;
-    /* a picture of the tick whose intra schedule may wait for macroblocks BELOW (concealment, FjHeader.intra_down_deps) must
-     * stay in ONE band of k_frame_intra: the launch's rows-per-band cap (which the kernel applies to every picture) must
-     * then cover a whole picture, whatever the other pictures of the tick want */
-    bool intra_whole = false;
-    uint32_t load = 0;               /* pictures the device works on at the same time as this tick (other lanes' ticks included): the
-                                        band budget is shared between them; 0 = this tick only */
-    /* hosted colour conversion (FrameDesc.conv_*): descriptors of this tick name a finished picture to convert */
-    bool conv = false;
-    uint32_t conv_waves = 0;         /* wavefronts of a k_frame_dbk workgroup that convert before they filter; 0 = CONV_WAVES_N */
-};
+/* ---- launch of one tick (TickShape: tick_plan.h) ---- */
 
 /* descriptor of one picture: device addresses of the sections of its (device-resident) frame job */
 void make_desc(FrameDesc &d, const uint8_t *host_blob, const uint8_t *dev_blob, uint8_t *dev_frames, uint32_t frame_bytes,
@@ -474,19 +435,35 @@ void make_desc(FrameDesc &d, const uint8_t *host_blob, const uint8_t *dev_blob, 
 
 struct TickTimers { Event ev[6]; Event sev[5]; bool on = false; bool copy_timed = false; unsigned mask = 31u; };   /* copy_timed: sev[3..4] were recorded by the latest launch_tick */   /* mask bit k: kernel k of KERNELS is timed */   /* boundaries of the 5 kernels of a tick; sev[1..2] = k_dbk on the side stream, sev[3..4] = k_copy on the copy stream */
 
-/* k_dbk of one tick on the side stream (which must already wait for whatever frees the tick's deblocking scratch);
- * records the join event behind it */
-static int launch_kdbk_aside(const SideLane *side, const FrameDesc *d_desc, const TickShape &s, TickTimers *tt, uint32_t launches[5], unsigned stages)
+/* k_dbk of one tick on st: the side stream beside the reconstruction kernels (SideLane), or the tick's own stream */
+static void launch_kdbk(hipStream_t st, const FrameDesc *d_desc, const TickShape &s, uint32_t launches[5])
 {
-    const bool do_dbk = (stages & 4u) && s.any_deblock && s.max_dbk;
-    const bool timed = tt && tt->on && (tt->mask & 4u);
-    if (timed && tt->sev[1]) HIP_TRY(hipEventRecord(tt->sev[1], side->stream));
-    if (do_dbk) {
-        hipLaunchKernelGGL(h264k::k_dbk, dim3(std::min<uint32_t>((s.max_dbk + 4 * DBK_WG_WAVES - 1) / (4 * DBK_WG_WAVES), DBK_WGS * 4 / DBK_WG_WAVES), s.n_frames), dim3(64 * DBK_WG_WAVES), 0, side->stream, d_desc);
-        if (launches) launches[2]++;
+    hipLaunchKernelGGL(h264k::k_dbk, dim3(std::min<uint32_t>((s.max_dbk + 4 * DBK_WG_WAVES - 1) / (4 * DBK_WG_WAVES), DBK_WGS * 4 / DBK_WG_WAVES), s.n_frames), dim3(64 * DBK_WG_WAVES), 0, st, d_desc);
+    if (launches) launches[2]++;
+}
+/* k_recon_inter for one partition class (0: one motion vector, 1: one per 8x8 quadrant, 2: finer), n_max entries in the longest list of the tick */
+template <int PATH> static void launch_inter(hipStream_t st, const FrameDesc *d_desc, uint32_t n_max, uint32_t n_frames)
+{
+    constexpr uint32_t per_wg = INTER_WG_WAVES * h264k::inter_per_wave<PATH>();
+    if (n_max) hipLaunchKernelGGL(h264k::k_recon_inter<PATH>, dim3((n_max + per_wg - 1) / per_wg, n_frames), dim3(64 * INTER_WG_WAVES), 0, st, d_desc);
+}
+/* the dynamic LDS every device has allowed the per-picture kernels so far: [0 k_frame_dbk, 1 k_frame_intra][plain, banded variant][device] */
+std::mutex g_tail_lds_mu;
+size_t g_tail_lds[2][2][MAX_DEVICES] = {};
+/* What the two per-picture kernels share between plan and launch on st.  *tickets: the stream's ticket counters when the launch is banded, else
+ * nullptr; fn, the variant about to be launched, gets its LDS limit raised when this device has not yet seen one as large as the plan's for it. */
+static int tail_prepare(hipStream_t st, int which, const BandPlan &bp, const void *fn, uint32_t **tickets)
+{
+    const bool banded = bp.bands > 1;
+    *tickets = banded ? tickets_for(st) : nullptr;
+    if (banded && !*tickets) return -1;
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lk(g_tail_lds_mu);
+    if (bp.lds > g_tail_lds[which][banded][dev]) {
+        HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bp.lds));
+        g_tail_lds[which][banded][dev] = bp.lds;
     }
-    if (timed && tt->sev[2]) HIP_TRY(hipEventRecord(tt->sev[2], side->stream));
-    HIP_TRY(hipEventRecord(side->join, side->stream));
     return 0;
 }
 
@@ -495,8 +472,12 @@ int launch_tick(hipStream_t st, const FrameDesc *d_desc, const TickShape &s, Tic
 {
     const bool timed = tt && tt->on;
     const unsigned tmask = timed ? tt->mask : 0u;
-#define EV_NEEDED(i) ((((tmask << 1) | tmask) >> (i)) & 1u)      /* boundary i closes kernel i-1 and opens kernel i */
-    if (EV_NEEDED(0)) HIP_TRY(hipEventRecord(tt->ev[0], st));
+    /* timer boundary i closes kernel i-1 and opens kernel i: recorded where either of the two is timed */
+    auto boundary = [&](unsigned i) -> int {
+        if ((((tmask << 1) | tmask) >> i) & 1u) HIP_TRY(hipEventRecord(tt->ev[i], st));
+        return 0;
+    };
+    if (boundary(0)) return -1;
     const bool do_dbk = (stages & 4u) && s.any_deblock && s.max_dbk;
     const bool do_copy = (stages & 1u) && s.max_copy;
     const bool aside = side && side->stream && do_dbk;
@@ -521,117 +502,58 @@ int launch_tick(hipStream_t st, const FrameDesc *d_desc, const TickShape &s, Tic
             if (ctimed) HIP_TRY(hipEventRecord(tt->sev[4], side->copy_stream));
             HIP_TRY(hipEventRecord(side->copy_join, side->copy_stream));
         }
-        if (launch_kdbk_aside(side, d_desc, s, tt, launches, stages)) return -1;
+        /* k_dbk on the side stream, which now waits for whatever frees the tick's deblocking scratch; the join event behind it */
+        const bool dtimed = timed && (tmask & 4u);
+        if (dtimed && tt->sev[1]) HIP_TRY(hipEventRecord(tt->sev[1], side->stream));
+        launch_kdbk(side->stream, d_desc, s, launches);
+        if (dtimed && tt->sev[2]) HIP_TRY(hipEventRecord(tt->sev[2], side->stream));
+        HIP_TRY(hipEventRecord(side->join, side->stream));
     }
     if (do_copy && !copy_aside) launch_copy(st);
-    if (EV_NEEDED(1)) HIP_TRY(hipEventRecord(tt->ev[1], st));
+    if (boundary(1)) return -1;
     if ((stages & 1u) && s.max_gen) {
-        if (s.max_gen_uni) hipLaunchKernelGGL(h264k::k_recon_inter<0>, dim3((s.max_gen_uni + INTER_WG_WAVES * h264k::inter_per_wave<0>() - 1) / (INTER_WG_WAVES * h264k::inter_per_wave<0>()), s.n_frames), dim3(64 * INTER_WG_WAVES), 0, st, d_desc);
-        if (s.max_gen_quad) hipLaunchKernelGGL(h264k::k_recon_inter<1>, dim3((s.max_gen_quad + INTER_WG_WAVES * h264k::inter_per_wave<1>() - 1) / (INTER_WG_WAVES * h264k::inter_per_wave<1>()), s.n_frames), dim3(64 * INTER_WG_WAVES), 0, st, d_desc);
-        if (s.max_gen_rest) hipLaunchKernelGGL(h264k::k_recon_inter<2>, dim3((s.max_gen_rest + INTER_WG_WAVES * h264k::inter_per_wave<2>() - 1) / (INTER_WG_WAVES * h264k::inter_per_wave<2>()), s.n_frames), dim3(64 * INTER_WG_WAVES), 0, st, d_desc);
+        launch_inter<0>(st, d_desc, s.max_gen_uni, s.n_frames);
+        launch_inter<1>(st, d_desc, s.max_gen_quad, s.n_frames);
+        launch_inter<2>(st, d_desc, s.max_gen_rest, s.n_frames);
         if (launches) launches[1]++;
     }
-    if (EV_NEEDED(2)) HIP_TRY(hipEventRecord(tt->ev[2], st));
-    if (do_dbk && !aside) {
-        hipLaunchKernelGGL(h264k::k_dbk, dim3(std::min<uint32_t>((s.max_dbk + 4 * DBK_WG_WAVES - 1) / (4 * DBK_WG_WAVES), DBK_WGS * 4 / DBK_WG_WAVES), s.n_frames), dim3(64 * DBK_WG_WAVES), 0, st, d_desc);
-        if (launches) launches[2]++;
-    }
-    if (EV_NEEDED(3)) HIP_TRY(hipEventRecord(tt->ev[3], st));
-    /* The two per-picture kernels keep per-macroblock scheduling state in LDS next to their wavefronts' tiles: for
-     * pictures that leave less than 16 wavefronts' worth of tile space in the 160 KB of a CU, fewer wavefronts run. */
-    constexpr size_t LDS_BUDGET = 160 * 1024 - 512;
-    /* Row bands of the per-picture kernels (kernels.hip.h).  A picture is split only where that puts IDLE compute units to
-     * work — measured: with 256 pictures on 256 compute units every split loses (a picture's work is about one compute unit's
-     * worth of instruction issue however it is cut: 4 bands x 4 wavefronts 92 instead of 57 ms per step in k_frame_dbk, bands on
-     * the heavy lanes of a saturated desynchronised schedule 775 instead of 827 M MB/s); with few pictures on the device it wins
-     * (4-32 streams: +18-20 %), and so it does for the few heavy pictures of a tick that is otherwise done long before them.
-     *   light_cap: bands a light picture may use = band_budget / pictures on the device (this tick, or all lanes' ticks: load)
-     *   heavy_cap: when the tick is (nearly) alone on the device, its heavy pictures share what the budget leaves */
-    const TailConfig tc = tail_config();
-    const uint32_t on_device = std::max<uint32_t>(1u, std::max(s.n_frames, s.load));
-    const uint32_t light_cap = std::max<uint32_t>(1u, tc.band_budget / on_device);
-    uint32_t heavy_cap = light_cap;
-    if (s.n_heavy && 2u * s.n_frames >= s.load) heavy_cap = std::max(light_cap, 1u + tc.heavy_budget / s.n_heavy);
-    struct BandPlan { uint32_t bands, rows, waves; size_t lds; };
-    auto plan = [&](int which, uint32_t waves, size_t (*lds_bytes)(uint32_t, uint32_t, uint32_t), bool may_shorten, BandPlan &bp) -> int {
-        const uint32_t eff_l = std::min(s.want_light[which], light_cap), eff_h = std::min(s.want_heavy[which], heavy_cap);
-        /* rows a band can have: the picture with the fewest bands decides (all pictures of a tick have the tick's size in
-         * practice; max_h / fewest bands is the bound) */
-        uint32_t fewest = s.n_heavy >= s.n_frames ? eff_h : s.n_heavy ? std::min(eff_l, eff_h) : eff_l;
-        /* (band_split() clamps a picture's rows per band to this cap: a picture that wants ONE band gets it only if the cap is
-         * the picture's height — for k_frame_intra that is a matter of correctness, see TickShape::intra_whole) */
-        if (which == 1 && s.intra_whole) fewest = 1;
-        uint32_t rows = (s.max_h + fewest - 1) / std::max<uint32_t>(1u, fewest);
-        rows = std::max<uint32_t>(1u, std::min<uint32_t>(rows, s.max_h));
-        while (may_shorten && lds_bytes(waves, s.max_w, rows) > LDS_BUDGET && rows > 1) rows = (rows + 1) / 2;      /* (rows is a cap the kernel applies to every picture) */
-        while (lds_bytes(waves, s.max_w, rows) > LDS_BUDGET && waves > 1) waves--;
-        if (lds_bytes(waves, s.max_w, rows) > LDS_BUDGET) return -1;
-        bp.rows = rows; bp.waves = waves; bp.lds = lds_bytes(waves, s.max_w, rows);
-        bp.bands = std::max<uint32_t>(std::max(s.n_heavy < s.n_frames ? eff_l : 1u, s.n_heavy ? eff_h : 1u), (s.max_h + rows - 1) / rows);
-        return 0;
-    };
+    if (boundary(2)) return -1;
+    if (do_dbk && !aside) launch_kdbk(st, d_desc, s, launches);
+    if (boundary(3)) return -1;
+    const TailConfig tc = tail_config();                         /* the row bands of the two per-picture kernels: plan_bands (tick_plan.h) */
     if (copy_aside) HIP_TRY(hipStreamWaitEvent(st, side->copy_join, 0));      /* (the copies have to be there before the intra macroblocks read them) */
     if (s.max_levels && (stages & 2u)) {
         BandPlan bp;
         /* a picture with concealed macroblocks must stay in one band (FjHeader.intra_down_deps): fewer wavefronts, never
          * shorter bands */
-        if (plan(1, std::max<uint32_t>(1u, std::min<uint32_t>(tc.intra_waves, h264k::TAIL_WAVES)), h264k::intra_lds_bytes, false, bp)) {
+        if (plan_bands(s, tc, 1, std::max<uint32_t>(1u, std::min<uint32_t>(tc.intra_waves, h264k::TAIL_WAVES)), h264k::intra_lds_bytes, false, bp)) {
             fprintf(stderr, "h264bsd-mi355x: picture of %u x %u macroblocks is too large for k_frame_intra\n", s.max_w, s.max_h); return -1;
         }
-        const uint32_t bands = bp.bands, rows = bp.rows, waves = bp.waves;
-        const size_t lds = bp.lds;
-        uint32_t *tickets = bands > 1 ? tickets_for(st) : nullptr;
-        if (bands > 1 && !tickets) return -1;
-        int dev = 0;
-        HIP_TRY(hipGetDevice(&dev));
-        static size_t lds_enabled[2][MAX_DEVICES] = {};
-        static std::mutex lds_mu;
-        {
-            std::lock_guard<std::mutex> lk(lds_mu);
-            if (lds > lds_enabled[bands > 1][dev]) {
-                HIP_TRY(hipFuncSetAttribute(bands > 1 ? (const void *)h264k::k_frame_intra<true> : (const void *)h264k::k_frame_intra<false>,
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                lds_enabled[bands > 1][dev] = lds;
-            }
-        }
-        if (bands > 1) hipLaunchKernelGGL(h264k::k_frame_intra<true>, dim3(s.n_frames * bands), dim3(64 * waves), lds, st, d_desc, prof, tickets + 2, bands, rows, light_cap);
-        else hipLaunchKernelGGL(h264k::k_frame_intra<false>, dim3(s.n_frames), dim3(64 * waves), lds, st, d_desc, prof, nullptr, 1u, rows, 1u);
+        uint32_t *tickets;
+        if (tail_prepare(st, 1, bp, bp.bands > 1 ? (const void *)h264k::k_frame_intra<true> : (const void *)h264k::k_frame_intra<false>, &tickets)) return -1;
+        if (bp.bands > 1) hipLaunchKernelGGL(h264k::k_frame_intra<true>, dim3(s.n_frames * bp.bands), dim3(64 * bp.waves), bp.lds, st, d_desc, prof, tickets + 2, bp.bands, bp.rows, bp.light_cap);
+        else hipLaunchKernelGGL(h264k::k_frame_intra<false>, dim3(s.n_frames), dim3(64 * bp.waves), bp.lds, st, d_desc, prof, nullptr, 1u, bp.rows, 1u);
         if (launches) launches[3]++;
     }
-    if (EV_NEEDED(4)) HIP_TRY(hipEventRecord(tt->ev[4], st));
+    if (boundary(4)) return -1;
     if (aside) HIP_TRY(hipStreamWaitEvent(st, side->join, 0));
     if (s.any_deblock && (stages & 4u)) {
         BandPlan bp;
-        if (plan(0, std::max<uint32_t>(1u, std::min<uint32_t>(s.dbk_waves ? s.dbk_waves : tc.dbk_waves, h264k::DBK_WAVES)), h264k::dbk_lds_bytes, true, bp)) {
+        if (plan_bands(s, tc, 0, std::max<uint32_t>(1u, std::min<uint32_t>(s.dbk_waves ? s.dbk_waves : tc.dbk_waves, h264k::DBK_WAVES)), h264k::dbk_lds_bytes, true, bp)) {
             fprintf(stderr, "h264bsd-mi355x: picture %u macroblocks wide is too large for k_frame_dbk\n", s.max_w); return -1;
         }
-        const uint32_t bands = bp.bands, rows = bp.rows, waves = bp.waves;
-        /* five twelfths of a workgroup's wavefronts start on the chroma graph (k_frame_dbk.hip.h); the seventh number of H264BSDMI_TAIL overrides */
+        const uint32_t waves = bp.waves;      /* five twelfths of a workgroup's wavefronts start on the chroma graph (k_frame_dbk.hip.h); the seventh number of H264BSDMI_TAIL overrides */
         const uint32_t chroma_waves = tc.dbk_chroma_waves ? tc.dbk_chroma_waves : std::max<uint32_t>(1u, (waves * 5u + 6u) / 12u);     /* 12 -> 5 (4 / 5 / 6: 31.6 / 30.3 / 30.3 ms per step), 8 -> 3 */
-        const size_t lds = bp.lds;
-        uint32_t *tickets = bands > 1 ? tickets_for(st) : nullptr;
-        if (bands > 1 && !tickets) return -1;
-        int dev = 0;
-        HIP_TRY(hipGetDevice(&dev));
-        static size_t lds_enabled[2][MAX_DEVICES] = {};
-        static std::mutex lds_mu;
-        {
-            std::lock_guard<std::mutex> lk(lds_mu);
-            if (lds > lds_enabled[bands > 1][dev]) {
-                HIP_TRY(hipFuncSetAttribute(bands > 1 ? (const void *)h264k::k_frame_dbk<true> : (const void *)h264k::k_frame_dbk<false>,
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                lds_enabled[bands > 1][dev] = lds;
-            }
-        }
         const uint32_t conv_waves = !s.conv ? 0u : std::min<uint32_t>(s.conv_waves ? s.conv_waves : (uint32_t)CONV_WAVES_N, waves > chroma_waves + 1u ? waves - chroma_waves - 1u : 0u);
-        if (bands > 1) hipLaunchKernelGGL(h264k::k_frame_dbk<true>, dim3(s.n_frames * bands), dim3(64 * waves), lds, st, d_desc, prof, tickets, bands, rows, light_cap, chroma_waves, conv_waves);
-        else hipLaunchKernelGGL(h264k::k_frame_dbk<false>, dim3(s.n_frames), dim3(64 * waves), lds, st, d_desc, prof, nullptr, 1u, rows, 1u, chroma_waves, conv_waves);
+        uint32_t *tickets;
+        if (tail_prepare(st, 0, bp, bp.bands > 1 ? (const void *)h264k::k_frame_dbk<true> : (const void *)h264k::k_frame_dbk<false>, &tickets)) return -1;
+        if (bp.bands > 1) hipLaunchKernelGGL(h264k::k_frame_dbk<true>, dim3(s.n_frames * bp.bands), dim3(64 * waves), bp.lds, st, d_desc, prof, tickets, bp.bands, bp.rows, bp.light_cap, chroma_waves, conv_waves);
+        else hipLaunchKernelGGL(h264k::k_frame_dbk<false>, dim3(s.n_frames), dim3(64 * waves), bp.lds, st, d_desc, prof, nullptr, 1u, bp.rows, 1u, chroma_waves, conv_waves);
         if (launches) launches[4]++;
     }
     if (s.conv && !(s.any_deblock && (stages & 4u)))             /* no k_frame_dbk in this tick: nobody hosted the conversion */
         hipLaunchKernelGGL(h264k::k_convert_rest, dim3(CONVERT_WGS, s.n_frames), dim3(256), 0, st, d_desc);
-    if (EV_NEEDED(5)) HIP_TRY(hipEventRecord(tt->ev[5], st));
-#undef EV_NEEDED
+    if (boundary(5)) return -1;
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -710,24 +632,14 @@ static void motion_keep_item(StreamCtx *s, const uint8_t *host_blob, const uint8
 /* one k_motion_keep launch for the tick just enqueued on lane l; it reads the jobs where the tick's kernels read them */
 static int motion_keep_launch(Lane &l, const std::vector<h264k::MotionKeepItem> &keep)
 {
-    if (keep.size() > l.mitem_cap) {
-        HIP_TRY(hipStreamSynchronize(l.st));               /* earlier launches may still read the old staging */
-        l.mitem_cap = 0;
-        const size_t cap = std::max<size_t>(2 * keep.size(), 64);
-        HIP_TRY(l.h_mitems.alloc(2 * cap * sizeof(h264k::MotionKeepItem), true));
-        for (auto &ev : l.mitem_ev) if (!ev) HIP_TRY(ev.create(hipEventDisableTiming));
-        l.mitem_cap = cap; l.mitem_used[0] = l.mitem_used[1] = false; l.mitem_flip = 0;
-    }
-    const int f = l.mitem_flip;
-    if (l.mitem_used[f]) HIP_TRY(hipEventSynchronize(l.mitem_ev[f]));       /* the launch before the last one read this half */
-    memcpy(l.h_mitems + (size_t)f * l.mitem_cap, keep.data(), keep.size() * sizeof(h264k::MotionKeepItem));
+    HIP_TRY(l.mitems.reserve(keep.size(), std::max<size_t>(2 * keep.size(), 64)));
+    memcpy(l.mitems.host(), keep.data(), keep.size() * sizeof(h264k::MotionKeepItem));
     uint32_t max_mbs = 0;
     for (const auto &it : keep) max_mbs = std::max(max_mbs, it.n_mbs);
     hipLaunchKernelGGL(h264k::k_motion_keep, dim3(std::min<uint32_t>((max_mbs + 15u) / 16u, 1024u), (uint32_t)keep.size()), dim3(256), 0, l.st,
-                       l.h_mitems.dev() + (size_t)f * l.mitem_cap);
+                       l.mitems.dev());
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(l.mitem_ev[f], l.st));
-    l.mitem_used[f] = true; l.mitem_flip ^= 1;
+    HIP_TRY(l.mitems.submit(l.st));
     return 0;
 }
 
@@ -745,19 +657,15 @@ static int lane_launch(Engine *e, unsigned lane_idx, const std::vector<StreamCtx
         l.arena_cap = bytes + bytes / 4;
         HIP_TRY(l.d_arena.alloc(l.arena_cap));
     }
-    if (part.size() > l.desc_cap) {
-        HIP_TRY(hipStreamSynchronize(l.st));
-        l.desc_cap = part.size() * 2;
-        HIP_TRY(l.d_desc.alloc(l.desc_cap * sizeof(FrameDesc)));
-        HIP_TRY(l.h_desc.alloc(2 * l.desc_cap * sizeof(FrameDesc)));
-        HIP_TRY(l.h_items.alloc(2 * l.desc_cap * sizeof(h264k::H2dItem), true));
-        l.flip = 0; l.ticks = 0;
+    if (part.size() > l.descs.cap()) {
+        HIP_TRY(hipStreamSynchronize(l.st));               /* earlier ticks may still read the old descriptors */
+        HIP_TRY(l.d_desc.alloc(2 * part.size() * sizeof(FrameDesc)));
+        HIP_TRY(l.h_items.alloc(2 * 2 * part.size() * sizeof(h264k::H2dItem), true));
     }
-    /* descriptors are staged in pinned memory (two halves, alternating) so that the copy can be asynchronous;
-     * before reusing a half, the tick that used it two ticks ago must have consumed it */
-    if (l.ticks >= 2) HIP_TRY(hipEventSynchronize(l.desc_ev[l.flip]));
-    FrameDesc *descs = l.h_desc + (size_t)l.flip * l.desc_cap;
-    h264k::H2dItem *items = l.h_items + (size_t)l.flip * l.desc_cap;
+    HIP_TRY(l.descs.reserve(part.size(), 2 * part.size()));      /* staged in pinned memory so that the copy can be asynchronous; the k_h2d items ride on the same half */
+    FrameDesc *descs = l.descs.host();
+    const size_t items_half = (size_t)l.descs.half() * l.descs.cap();
+    h264k::H2dItem *items = l.h_items + items_half;
     /* how the jobs reach the device: one k_h2d launch that reads the pinned staging buffers (256 hipMemcpyAsync calls per tick before) */
     TickShape shape;
     size_t off = 0;
@@ -790,11 +698,9 @@ static int lane_launch(Engine *e, unsigned lane_idx, const std::vector<StreamCtx
         e->inflight_recorded = false;
         s->last_lane = (int)lane_idx; s->last_launch = l.launches;
     }
-    hipLaunchKernelGGL(h264k::k_h2d, dim3(h264k::H2D_CHUNKS, (uint32_t)part.size()), dim3(256), 0, l.st, l.h_items.dev() + (size_t)l.flip * l.desc_cap);
+    hipLaunchKernelGGL(h264k::k_h2d, dim3(h264k::H2D_CHUNKS, (uint32_t)part.size()), dim3(256), 0, l.st, l.h_items.dev() + items_half);
     HIP_TRY(hipMemcpyAsync(l.d_desc, descs, part.size() * sizeof(FrameDesc), hipMemcpyHostToDevice, l.st));
-    HIP_TRY(hipEventRecord(l.desc_ev[l.flip], l.st));
-    l.flip ^= 1;
-    l.ticks++;
+    HIP_TRY(l.descs.submit(l.st));
     if (e->lanes.size() > 1) shape.dbk_waves = LANE_DBK_WAVES;
     shape.load = (uint32_t)e->streams.size();
     if (launch_tick(l.st, l.d_desc, shape, nullptr, nullptr, 7u, l.side)) return -1;
@@ -1171,10 +1077,6 @@ static const void *tensor_kernel(int kind, const h264bsdmi_tensor_spec &t, bool 
     }
     return nullptr;
 }
-/* the staging ring's item stride: k_tensor_out / k_tensor_resize read TensorItems, k_tensor_aa AaItems, k_tensor_roi RoiItems,
- * k_motion_roi MotionItems, k_tensor_remap RemapItems */
-constexpr size_t TITEM_BYTES = std::max({ sizeof(h264k::TensorItem), sizeof(h264k::AaItem), sizeof(h264k::RoiItem), sizeof(h264k::MotionItem),
-                                          sizeof(h264k::RemapItem) });
 
 /* The colour map of one picture's item (matrix, range): per output channel c the affine map of the 8-bit (Y, Cb - 128, Cr - 128) to
  * the value written, and the clamp bounds of [0, 1] under the output scale (U8: 255 v; floats: (v - mean[c]) / std[c]), folded in
@@ -1216,9 +1118,8 @@ static void colour_item(h264k::TensorItem &it, const h264bsdmi_tensor_spec &t, u
     }
 }
 
-/* The three steps every pull shares, under the engine's mutex.
- * pull_begin_locked: the instances' queued jobs are enqueued, once for the batch; half e->titem_flip of the item staging is made
- * large enough for n_items and free (the launch before the last one read it). */
+/* The three steps every pull shares, under the engine's mutex.  pull_begin_locked: the instances' queued jobs are enqueued, once for
+ * the batch; the current half of the item staging is made large enough for n_items and free. */
 static int pull_begin_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, uint32_t n_items)
 {
     bool mine = false;
@@ -1228,18 +1129,7 @@ static int pull_begin_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, u
         mine = !s->pending.empty();
     }
     if (mine && flush_locked(e, false)) return -1;
-    if (n_items > e->titem_cap) {
-        for (int k = 0; k < 2; k++)
-            if (e->titem_used[k]) HIP_TRY(hipEventSynchronize(e->titem_ev[k]));
-        e->titem_cap = 0;
-        const size_t cap = std::max<size_t>(n_items, 256);
-        HIP_TRY(e->h_titems.alloc(2 * cap * TITEM_BYTES, true));
-        for (int k = 0; k < 2; k++)
-            if (!e->titem_ev[k]) HIP_TRY(e->titem_ev[k].create(hipEventDisableTiming));
-        e->titem_cap = cap; e->titem_used[0] = e->titem_used[1] = false; e->titem_flip = 0;
-    }
-    const int f = e->titem_flip;
-    if (e->titem_used[f]) HIP_TRY(hipEventSynchronize(e->titem_ev[f]));      /* the launch before the last one read this half */
+    HIP_TRY(e->titems.reserve(n_items, 256));
     return 0;
 }
 /* st waits for the tick that produced each picture (deduplicated per lane launch) */
@@ -1261,9 +1151,7 @@ static int pull_wait_pictures(Engine *e, uint32_t n, const SinkTensorPic *pics, 
  * fence is handed to every instance */
 static int pull_end_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, hipStream_t st, hipEvent_t *fence_ev)
 {
-    const int f = e->titem_flip;
-    HIP_TRY(hipEventRecord(e->titem_ev[f], st));
-    e->titem_used[f] = true; e->titem_flip ^= 1;
+    HIP_TRY(e->titems.submit(st));
     hipLaunchKernelGGL(k_err_words, dim3(1), dim3(64), 0, st, e->d_err, e->h_err.dev());
     HIP_TRY(hipGetLastError());
     Fence *fc;
@@ -1346,13 +1234,6 @@ static dim3 pull_grid(uint32_t width, uint32_t height, uint32_t cols, uint32_t r
     const uint32_t tiles = (width + cols - 1u) / cols * ((height + rows - 1u) / rows);
     return dim3(std::min((tiles + per_block - 1u) / per_block, 1024u), n_items);
 }
-/* half e->titem_flip of the item staging (pull_begin_locked), as the host fills it and as the kernel reads it */
-static size_t staged_half(const Engine *e) { return (size_t)e->titem_flip * e->titem_cap * TITEM_BYTES; }
-template <typename Item> static Item *staged_items(Engine *e) { return reinterpret_cast<Item *>(e->h_titems + staged_half(e)); }
-template <typename Item> static const Item *staged_items_dev(Engine *e)
-{
-    return reinterpret_cast<const Item *>(e->h_titems.dev() + staged_half(e));
-}
 /* behind the filled items: st waits for the pictures' ticks, ONE launch of 256-lane workgroups, the fence */
 static int pull_launch_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, hipStream_t st, const void *fn, dim3 grid, void *kargs,
                               hipEvent_t *fence_ev)
@@ -1380,12 +1261,12 @@ static int aa_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, const
     for (uint32_t i = 0; i < n; i++)
         if (!pull_box_ok(pics[i].box, t.width, t.height)) return -1;
     if (pull_begin_locked(e, n, pics, n)) return -1;
-    h264k::AaItem *items = staged_items<h264k::AaItem>(e);
+    h264k::AaItem *items = e->titems.host<h264k::AaItem>();
     for (uint32_t i = 0; i < n; i++) {
         const uint32_t *box = pics[i].box;
         items[i] = h264k::AaItem{ picture_item(pics[i], t, pics[i].index), box[0], box[1], box[2], box[3] };
     }
-    h264k::AaArgs aargs{ staged_items_dev<h264k::AaItem>(e), t.width, t.height, chroma, rs.filter, {}, {}, {} };
+    h264k::AaArgs aargs{ e->titems.dev<h264k::AaItem>(), t.width, t.height, chroma, rs.filter, {}, {}, {} };
     copy3(aargs.mean, t.mean); copy3(aargs.std, t.std); copy3(aargs.pad, fold_pad(rs.pad, t.dtype, t.mean, t.std, ref).pad);
     return pull_launch_locked(e, n, pics, st, fn, pull_grid(t.width, t.height, h264k::TAA_COLS, h264k::TAA_ROWS, n), &aargs, fence_ev);
 }
@@ -1402,9 +1283,9 @@ static int tensor_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, c
     if (!fn || n > 65535u) return -1;                                   /* grid.y */
     if (!pull_pictures_ok(n, pics, ref, false)) return -1;
     if (pull_begin_locked(e, n, pics, n)) return -1;
-    h264k::TensorItem *items = staged_items<h264k::TensorItem>(e);
+    h264k::TensorItem *items = e->titems.host<h264k::TensorItem>();
     for (uint32_t i = 0; i < n; i++) items[i] = picture_item(pics[i], t, pics[i].index);
-    h264k::TensorArgs targs{ staged_items_dev<h264k::TensorItem>(e), t.width, t.height, chroma, {}, {} };
+    h264k::TensorArgs targs{ e->titems.dev<h264k::TensorItem>(), t.width, t.height, chroma, {}, {} };
     copy3(targs.mean, t.mean); copy3(targs.std, t.std);
     /* k_tensor_out: a wavefront per unit of 64 x 16, four to a workgroup */
     const dim3 grid = t.resize ? pull_grid(t.width, t.height, h264k::TCR_COLS, h264k::TCR_ROWS, n) : pull_grid(t.width, t.height, 64, 16, n, 4);
@@ -1424,7 +1305,7 @@ static int regions_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, 
     if (!fn || n_regs > 65535u) return -1;                              /* grid.y */
     if (!pull_pictures_ok(n, pics, ref, false) || !pull_regions_ok(n, n_regs, regs, t.width, t.height)) return -1;
     if (pull_begin_locked(e, n, pics, n_regs)) return -1;
-    h264k::RoiItem *items = staged_items<h264k::RoiItem>(e);
+    h264k::RoiItem *items = e->titems.host<h264k::RoiItem>();
     std::vector<h264k::TensorItem> of_pic(n);                           /* the colour map once per picture */
     for (uint32_t i = 0; i < n; i++) of_pic[i] = picture_item(pics[i], t, 0);
     for (uint32_t r = 0; r < n_regs; r++) {
@@ -1432,7 +1313,7 @@ static int regions_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, 
         items[r] = h264k::RoiItem{ of_pic[g.pic], g.x, g.y, g.w, g.h, g.box[0], g.box[1], g.box[2], g.box[3] };
         items[r].t.dst += g.index * spec_slice_bytes(t);
     }
-    h264k::RoiArgs rargs{ staged_items_dev<h264k::RoiItem>(e), t.width, t.height, chroma, rs.filter, {}, {}, {}, {} };
+    h264k::RoiArgs rargs{ e->titems.dev<h264k::RoiItem>(), t.width, t.height, chroma, rs.filter, {}, {}, {}, {} };
     const PullPad pp = fold_pad(rs.pad, t.dtype, t.mean, t.std, ref);
     copy3(rargs.mean, t.mean); copy3(rargs.std, t.std); copy3(rargs.pad, pp.pad); copy3(rargs.spad, pp.spad);
     return pull_launch_locked(e, n, pics, st, fn, pull_grid(t.width, t.height, h264k::TAA_COLS, h264k::TAA_ROWS, n_regs), &rargs, fence_ev);
@@ -1454,7 +1335,7 @@ static int motion_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, u
     if (n_regs > 65535u) return -1;                                     /* grid.y */
     if (!pull_pictures_ok(n, pics, false, true) || !pull_regions_ok(n, n_regs, regs, m.width, m.height)) return -1;
     if (pull_begin_locked(e, n, pics, n_regs)) return -1;
-    h264k::MotionItem *items = staged_items<h264k::MotionItem>(e);
+    h264k::MotionItem *items = e->titems.host<h264k::MotionItem>();
     const size_t C = ((m.planes & H264BSDMI_MOTION_PLANE_MV) ? 2 : 0) + ((m.planes & H264BSDMI_MOTION_PLANE_VALID) ? 1 : 0) +
                      ((m.planes & H264BSDMI_MOTION_PLANE_AGE) ? 1 : 0) + ((m.planes & H264BSDMI_MOTION_PLANE_QP) ? 1 : 0);
     const size_t slice = C * m.width * m.height * (m.dtype == h264k::TO_F16 ? 2 : 4);
@@ -1465,7 +1346,7 @@ static int motion_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, u
         items[r] = h264k::MotionItem{ s->d_motion + (size_t)p.slot * s->motion_bytes, static_cast<uint8_t *>(m.data) + g.index * slice,
                                       s->wmb, s->hmb, p.x0, p.y0, p.w, p.h, g.x, g.y, g.w, g.h, g.box[0], g.box[1], g.box[2], g.box[3] };
     }
-    h264k::MotionArgs margs{ staged_items_dev<h264k::MotionItem>(e), m.width, m.height, m.planes, m.sampler, m.units, m.per_picture };
+    h264k::MotionArgs margs{ e->titems.dev<h264k::MotionItem>(), m.width, m.height, m.planes, m.sampler, m.units, m.per_picture };
     return pull_launch_locked(e, n, pics, st, fns[m.dtype == h264k::TO_F32][m.layout],
                               pull_grid(m.width, m.height, h264k::TAA_COLS, h264k::TAA_ROWS, n_regs), &margs, fence_ev);
 }
@@ -1485,7 +1366,7 @@ static int remap_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, ui
     for (uint32_t r = 0; r < n_maps; r++)
         if (maps[r].pic >= n || !maps[r].map || (reinterpret_cast<uintptr_t>(maps[r].map) & 7u)) return -1;
     if (pull_begin_locked(e, n, pics, n_maps)) return -1;
-    h264k::RemapItem *items = staged_items<h264k::RemapItem>(e);
+    h264k::RemapItem *items = e->titems.host<h264k::RemapItem>();
     std::vector<h264k::TensorItem> of_pic(n);                           /* the colour map once per picture */
     for (uint32_t i = 0; i < n; i++) of_pic[i] = picture_item(pics[i], t, 0);
     for (uint32_t r = 0; r < n_maps; r++) {
@@ -1493,7 +1374,7 @@ static int remap_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, ui
         items[r].t.dst += maps[r].index * spec_slice_bytes(t);
     }
     /* pad: a non-finite coordinate; spad: outside the window */
-    h264k::RemapArgs rargs{ staged_items_dev<h264k::RemapItem>(e), t.width, t.height, chroma, rm.filter, rm.border, {}, {}, {}, {} };
+    h264k::RemapArgs rargs{ e->titems.dev<h264k::RemapItem>(), t.width, t.height, chroma, rm.filter, rm.border, {}, {}, {}, {} };
     const PullPad pp = fold_pad(rm.pad, t.dtype, t.mean, t.std, ref);
     copy3(rargs.mean, t.mean); copy3(rargs.std, t.std); copy3(rargs.pad, pp.pad); copy3(rargs.spad, pp.spad);
     return pull_launch_locked(e, n, pics, st, fn, pull_grid(t.width, t.height, h264k::TRM_COLS, h264k::TRM_ROWS, n_maps), &rargs, fence_ev);
@@ -1679,7 +1560,8 @@ int eng_device_cpus(int device, int *cpus, int max)
     return n;
 }
 
-unsigned h264bsdmiDeviceErrors(void)
+/* after waiting for every device: their sticky error bits or-ed together, or (events) how often their tripwires fired; 0xFFFFFFFF = HIP error */
+static unsigned poll_all_devices(bool events)
 {
     unsigned all = 0;
     for (int d = 0; d < MAX_DEVICES; d++) {
@@ -1688,41 +1570,11 @@ unsigned h264bsdmiDeviceErrors(void)
         if (!e) continue;
         std::lock_guard<std::mutex> lk(e->mu);
         if (hipSetDevice(e->device) != hipSuccess || poll_errors(e)) return 0xFFFFFFFFu;
-        all |= e->errors;
+        all = events ? all + e->error_events : all | e->errors;
     }
     return all;
 }
-
-/* test harness (bench library): tripwire events of all devices so far, after waiting for the devices — monotonic, unlike the
- * sticky bits of h264bsdmiDeviceErrors(): a test asserts that its own pictures added none */
-unsigned h264bsdmiDebugDeviceErrorEvents(void)
-{
-    unsigned all = 0;
-    for (int d = 0; d < MAX_DEVICES; d++) {
-        Engine *e;
-        { std::lock_guard<std::mutex> lk(g_engine_mu); e = g_engines[d]; }
-        if (!e) continue;
-        std::lock_guard<std::mutex> lk(e->mu);
-        if (hipSetDevice(e->device) != hipSuccess || poll_errors(e)) return 0xFFFFFFFFu;
-        all += e->error_events;
-    }
-    return all;
-}
-
-#ifdef H264K_INTER_PROFILE
-/* profiling build only: the 24 64-bit counters behind the device error word (k_recon_inter's cycle accounting), read and zeroed */
-int h264bsdmiDebugReadCounters(unsigned long long *out)
-{
-    Engine *e = engine_get();
-    if (!e) return -1;
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(out, reinterpret_cast<uint8_t *>(e->d_err) + 64, 192, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemset(reinterpret_cast<uint8_t *>(e->d_err) + 64, 0, 192));
-    HIP_TRY(hipDeviceSynchronize());
-    return 0;
-}
-#endif
+unsigned h264bsdmiDeviceErrors(void) { return poll_all_devices(false); }
 
 static int flush_all(bool wait)
 {
@@ -1740,664 +1592,6 @@ static int flush_all(bool wait)
 }
 
 int h264bsdmiFlush(void) { return flush_all(true); }
-
 int h264bsdmiFlushAsync(void) { return flush_all(false); }
-
-/* ------------------------------------------------------------------ replay sets */
-struct h264bsdmi_replay {
-    Engine *e;
-    uint32_t n_pics, n_streams, n_slots, wmb, hmb, frame_bytes;
-    size_t blob_stride;               /* bytes of all blobs of one stream (256-aligned) */
-    unsigned long long job_bytes;     /* sum of the blob sizes of one stream */
-    DeviceMem<uint8_t> d_blobs;       /* n_streams * blob_stride */
-    DeviceMem<uint8_t> d_frames;      /* n_streams * n_slots * frame_bytes */
-    DeviceMem<uint8_t> d_dbk;         /* n_streams * n_mbs * 32 */
-    DeviceMem<FrameDesc> d_desc;      /* n_pics * n_streams */
-    DeviceMem<uint32_t> d_conv;       /* n_streams * w*h (lazy) */
-    DeviceMem<uint8_t> d_planar;      /* one frame, planar (h264bsdmiReplayFetch) */
-    DeviceMem<unsigned long long> d_sums;
-    std::vector<TickShape> shapes;
-    std::vector<uint8_t> cur_slot;
-    std::vector<TickTimers> timers;
-    uint32_t timed_first, timed_count;
-    Event ev_begin, ev_end, gdone_any;
-    uint32_t launches[5];
-    unsigned stages;
-    uint32_t n_groups;
-    Stream gstream[8];
-    Event gdone[8];
-    bool overlap_dbk = true;
-    unsigned timed_mask = 31u;
-    /* desynchronised sets with heavy lanes (h264bsdmiReplayCreateDesync, lanes > 0): a static launch schedule */
-    struct Launch { size_t first; TickShape shape; int lane; std::vector<int> waits; int record_ev; bool light; };
-    std::vector<Launch> sched;
-    std::vector<Event> sched_ev;
-    static constexpr int MAX_LANES = 72;  /* lanes 0..n_light-1: one per stream group (light pictures), then the heavy lanes */
-    Stream lanes[MAX_LANES];
-    SideLane lane_side[MAX_LANES];        /* k_dbk next to the reconstruction kernels, per light lane */
-    uint32_t n_lanes = 0, n_light = 0;
-    /* HIP streams of earlier schedules of this set, reused by the next one (normal priority: light lanes and stream groups; highest: heavy
-     * lanes; side-stream pairs).  A process that creates and destroys a dozen streams per schedule falls off the runtime's stream cliff after
-     * a few of them (a 12-lane schedule then takes seconds per lap, the same schedule in a fresh process 0.13 s): nothing is destroyed before the set is. */
-    std::vector<Stream> pool_normal, pool_high;
-    std::vector<SideLane> pool_side;
-    void retire_stream(Stream &st) { if (st) (st.high ? pool_high : pool_normal).push_back(std::move(st)); }
-    void retire_streams()
-    {
-        for (uint32_t k = 0; k < (uint32_t)MAX_LANES; k++) {
-            retire_stream(lanes[k]);
-            if (lane_side[k].stream) pool_side.push_back(std::move(lane_side[k]));
-        }
-    }
-    bool take_stream(Stream *st, bool high, int prio)
-    {
-        std::vector<Stream> &pool = high ? pool_high : pool_normal;
-        if (!pool.empty()) { *st = std::move(pool.back()); pool.pop_back(); return true; }
-        return (high ? st->create(prio) : st->create()) == hipSuccess;
-    }
-    bool take_side(SideLane *sl)
-    {
-        if (!pool_side.empty()) { *sl = std::move(pool_side.back()); pool_side.pop_back(); return true; }
-        return sl->create(0, false);
-    }
-    std::vector<uint32_t> offsets;    /* first picture of every stream */
-    /* what a schedule is built from (replay_schedule: at creation and again for every h264bsdmiReplayReschedule) */
-    std::vector<FjHeader> heads;      /* the headers of the n_pics jobs (host copies) */
-    std::vector<size_t> blob_off;     /* where job p lies inside a stream's blobs */
-    size_t frames_per_stream = 0, dbk_half = 0, dbk_stride = 0;
-    /* config 3 ("ARGB conversion on-GPU"): colour conversion of every produced picture inside the run, timed */
-    int convert_fmt = -1;
-    std::vector<Event> cev;           /* 2 per tick */
-    /* ... hosted by the NEXT tick's k_frame_dbk where that is possible (kernels/convert.hip.h, conv_drain): descriptors with the
-     * conversion of the stream's previous picture written in, which ticks host */
-    DeviceMem<FrameDesc> d_desc_conv;
-    std::vector<uint8_t> hosted;      /* tick i converts the pictures of tick i - 1 while it filters its own */
-    std::vector<uint8_t> cev_on;      /* tick i was followed by a stand-alone conversion launch in the last run */
-    bool host_convert = true, convert_trailing = true;
-    uint32_t conv_waves = 0;
-};
-
-h264bsdmi_replay *h264bsdmiReplayCreateSched(const u8 *const *blobs, const u32 *bytes, u32 n_pics, u32 n_streams,
-                                             const u32 *offsets, u32 heavy_lanes, u32 heavy_delay, u32 groups);
-
-/* Descriptors and launch schedule of a replay set for the offsets in r->offsets: lock-step / staggered / common ticks
- * (heavy_lanes == 0, groups <= 1: tick i = picture (i + offset) mod n_pics of every stream) or the static schedule of
- * stream groups and heavy lanes (h264bsdmiReplayCreateDesync).  Called at creation and by h264bsdmiReplayReschedule,
- * which has torn the previous schedule down. */
-static bool replay_schedule(h264bsdmi_replay *r, u32 heavy_lanes, u32 heavy_delay, u32 groups)
-{
-    Engine *e = r->e;
-    const u32 n_pics = r->n_pics, n_streams = r->n_streams;
-    const size_t total = r->blob_stride, frames_per_stream = r->frames_per_stream, dbk_stride = r->dbk_stride;
-    const std::vector<size_t> &offs = r->blob_off;
-    auto blob_of = [&](u32 p) { return reinterpret_cast<const uint8_t *>(&r->heads[p]); };     /* make_desc reads the header only */
-    bool ok = true;
-    r->shapes.assign(n_pics, TickShape());
-    for (u32 i = 0; i < n_pics; i++) {
-        TickShape s0;
-        FrameDesc tmp;
-        make_desc(tmp, blob_of(i), nullptr, nullptr, 0, nullptr, &s0, nullptr);
-        s0.n_frames = n_streams;
-        r->shapes[i] = s0;
-    }
-    if (ok) {
-        std::vector<FrameDesc> descs((size_t)n_pics * n_streams);
-        auto desc_of = [&](FrameDesc &d, u32 s, u32 p, TickShape *shape, u32 tick = 0) {
-            make_desc(d, blob_of(p), r->d_blobs + (size_t)s * total + offs[p], r->d_frames + (size_t)s * frames_per_stream,
-                      r->frame_bytes, r->d_dbk + (size_t)s * dbk_stride, shape, e->d_err);
-        };
-        if (!heavy_lanes && groups <= 1) {
-            for (u32 i = 0; i < n_pics; i++) {
-                TickShape shape;                          /* a tick is as large as the largest of its pictures */
-                for (u32 s = 0; s < n_streams; s++) desc_of(descs[(size_t)i * n_streams + s], s, (i + r->offsets[s]) % n_pics, &shape, i);
-                r->shapes[i] = shape;
-            }
-        } else {
-            /* static schedule: every group's light ticks on its own lane, heavy pictures round-robin on the heavy lanes */
-            std::vector<u32> done(n_streams, 0), ready_at(n_streams, 0);
-            std::vector<int> last_ev(n_streams, -1);     /* event of the heavy launch a stream's previous picture ran in */
-            size_t n_desc = 0;
-            u32 left = n_streams, heavy_count = 0;
-            auto is_heavy = [&](u32 p) { const FjHeader *h = reinterpret_cast<const FjHeader *>(blob_of(p)); return heavy_lanes && h->n_intra * 4u > h->n_mbs; };      /* (no heavy lanes: heavy pictures stay in their group's tick) */
-            /* Cost-affine groups: a group's tick lasts as long as its slowest picture, so streams whose next pictures cost
-             * about the same belong together.  Every REGROUP rounds the streams are sorted by the estimated per-picture
-             * kernel time of their next REGROUP pictures (from the job headers: intra and filtered macroblock counts) and
-             * dealt to the groups in that order; a stream that changes groups makes its new lane wait for the event its
-             * old lane recorded after the last round before the regrouping. */
-#ifndef REGROUP_ROUNDS
-#define REGROUP_ROUNDS 32      /* measured: 4: 681, 8: 664, 16: 699, 32: 709-733 M MB/s (8-9 groups); every regrouping costs cross-lane waits */
-#endif
-            constexpr u32 REGROUP = REGROUP_ROUNDS;
-            std::vector<std::vector<u32>> members(groups);
-            std::vector<u32> group_of(n_streams, 0);
-            std::vector<int> pre_regroup_ev(groups, -1);
-            auto upcoming_cost = [&](u32 s) {
-                uint64_t c = 0;
-                for (u32 i = 0; i < REGROUP && done[s] + i < n_pics; i++) {
-                    const FjHeader *h = &r->heads[(r->offsets[s] + done[s] + i) % n_pics];
-                    c += 11u * h->n_intra + 4u * h->n_dbk;          /* ~0.55 us per intra macroblock, ~0.2 us per filtered one */
-                }
-                return c;
-            };
-            auto new_event = [&]() { r->sched_ev.emplace_back(); return (int)r->sched_ev.size() - 1; };
-            for (u32 t = 0; left && t < 16u * n_pics; t++) {
-                /* one heavy launch per round for the heavy pictures of all groups: it waits for the light launch of
-                 * every group it takes a stream from (the previous picture of that stream ran there or earlier) */
-                std::vector<u32> hs;
-                std::vector<int> hwaits;
-                if (t % REGROUP == 0) {
-                    std::vector<std::pair<uint64_t, u32>> order;
-                    for (u32 s = 0; s < n_streams; s++) if (done[s] < n_pics) order.emplace_back(upcoming_cost(s), s);
-                    std::sort(order.begin(), order.end());
-                    for (auto &m : members) m.clear();
-                    for (size_t i = 0; i < order.size(); i++) {
-                        const u32 s = order[i].second, g = (u32)(i * groups / order.size());
-                        if (t && g != group_of[s] && last_ev[s] < 0) last_ev[s] = pre_regroup_ev[group_of[s]];
-                        group_of[s] = g;
-                        members[g].push_back(s);
-                    }
-                    for (auto &m : members) std::sort(m.begin(), m.end());
-                }
-                const bool before_regroup = (t + 1) % REGROUP == 0;
-                for (u32 g = 0; g < groups; g++) {
-                    h264bsdmi_replay::Launch light{ n_desc, TickShape(), (int)g, {}, -1, true };
-                    bool group_has_heavy = false;
-                    for (u32 s : members[g]) {
-                        if (done[s] >= n_pics || ready_at[s] > t) continue;
-                        const u32 p = (r->offsets[s] + done[s]) % n_pics;
-                        if (is_heavy(p)) { hs.push_back(s); group_has_heavy = true; continue; }
-                        if (last_ev[s] >= 0) {               /* rejoining after a heavy picture */
-                            if (std::find(light.waits.begin(), light.waits.end(), last_ev[s]) == light.waits.end()) light.waits.push_back(last_ev[s]);
-                            last_ev[s] = -1;
-                        }
-                        desc_of(descs[n_desc++], s, p, &light.shape);
-                        if (++done[s] == n_pics) left--;
-                    }
-                    const bool have_light = light.shape.n_frames != 0;
-                    if (have_light) {
-                        if (group_has_heavy || before_regroup) light.record_ev = new_event();
-                        if (group_has_heavy) hwaits.push_back(light.record_ev);
-                        if (before_regroup) pre_regroup_ev[g] = light.record_ev;
-                        light.shape.dbk_waves = LANE_DBK_WAVES;
-                        r->sched.push_back(light);
-                    } else {
-                        if (group_has_heavy) hwaits.push_back(-2 - (int)g);        /* "everything enqueued on light lane g so far" */
-                        if (before_regroup) {                                      /* an empty launch: only the event */
-                            light.record_ev = pre_regroup_ev[g] = new_event();
-                            r->sched.push_back(light);
-                        }
-                    }
-                }
-                if (!hs.empty()) {
-                    h264bsdmi_replay::Launch heavy{ n_desc, TickShape(), (int)(groups + heavy_count++ % heavy_lanes), hwaits, -1, false };
-                    for (u32 s : hs) {
-                        if (last_ev[s] >= 0 && std::find(heavy.waits.begin(), heavy.waits.end(), last_ev[s]) == heavy.waits.end()) heavy.waits.push_back(last_ev[s]);
-                        desc_of(descs[n_desc++], s, (r->offsets[s] + done[s]) % n_pics, &heavy.shape);
-                        if (++done[s] == n_pics) left--;
-                        ready_at[s] = t + 1 + heavy_delay;
-                    }
-                    heavy.record_ev = new_event();
-                    for (u32 s : hs) last_ev[s] = heavy.record_ev;
-                    r->sched.push_back(heavy);
-                }
-            }
-            if (left || n_desc != descs.size()) ok = false;
-            r->n_light = groups;
-            r->n_lanes = groups + heavy_lanes;
-            /* the heavy pictures' workgroups need a whole compute unit each: highest priority (measured: no
-             * difference on this runtime, kept because it states the intent) */
-            int prio_least = 0, prio_greatest = 0;
-            if (hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest) != hipSuccess) prio_greatest = 0;
-            for (u32 k = 0; ok && k < r->n_lanes; k++) {
-                if (k < groups) {
-                    ok = r->take_stream(&r->lanes[k], false, 0);
-                    if (ok && groups <= 2)        /* with more groups the other groups are the overlap, and busy HIP streams are scarce (Lane, above) */
-                        ok = r->take_side(&r->lane_side[k]);
-                } else ok = r->take_stream(&r->lanes[k], true, prio_greatest);
-            }
-            for (auto &ev : r->sched_ev) if (ok) ok = ev.create(hipEventDisableTiming) == hipSuccess;
-        }
-        if (ok) ok = hipMemcpyAsync(r->d_desc, descs.data(), descs.size() * sizeof(FrameDesc), hipMemcpyHostToDevice, e->stream) == hipSuccess &&
-                     hipStreamSynchronize(e->stream) == hipSuccess;
-    }
-    return ok;
-}
-
-h264bsdmi_replay *h264bsdmiReplayCreate(const u8 *const *blobs, const u32 *bytes, u32 n_pics, u32 n_streams)
-{
-    return h264bsdmiReplayCreateDesync(blobs, bytes, n_pics, n_streams, nullptr, 0, 0);
-}
-
-/* odd_offset != 0: the "staggered" variant of SURVEY.md §8d config 4 — odd-numbered streams run picture
- * (i + odd_offset) mod n_pics in tick i (odd_offset must be the index of an IDR picture, so that both the
- * start and the wrap-around are clean decoder starts); every tick then mixes two different pictures */
-h264bsdmi_replay *h264bsdmiReplayCreateStaggered(const u8 *const *blobs, const u32 *bytes, u32 n_pics, u32 n_streams, u32 odd_offset)
-{
-    if (odd_offset >= n_pics) return nullptr;
-    std::vector<u32> offs(n_streams, 0);
-    for (u32 s = 1; s < n_streams; s += 2) offs[s] = odd_offset;
-    return h264bsdmiReplayCreateDesync(blobs, bytes, n_pics, n_streams, offs.data(), 0, 0);
-}
-
-/* Streams that are NOT in step: stream s starts at picture offsets[s] (nullptr = all 0) and runs n_pics pictures,
- * wrapping around (picture 0 must be an IDR picture).  heavy_lanes == 0: tick i holds picture (i + offsets[s]) mod
- * n_pics of every stream — a tick then lasts as long as its slowest picture.  heavy_lanes > 0: a static schedule of
- * what a scheduler achieves that keeps light pictures from waiting for heavy ones:
- *   - the streams are split into `groups` groups (stream s -> group s % groups), every group runs its own ticks on its
- *     own HIP stream ("light lane"): a group's tick lasts as long as ITS slowest picture, and the workgroups of the
- *     other groups fill the compute units it leaves idle (tail kernels are one workgroup per picture);
- *   - pictures that are mostly intra-coded ("heavy", more than a quarter of their macroblocks) leave their group's
- *     tick and run on one of heavy_lanes extra HIP streams; their stream of pictures rejoins its group heavy_delay
- *     ticks later (an event makes the group's tick wait if the heavy picture is not finished by then). */
-h264bsdmi_replay *h264bsdmiReplayCreateDesync(const u8 *const *blobs, const u32 *bytes, u32 n_pics, u32 n_streams,
-                                              const u32 *offsets, u32 heavy_lanes, u32 heavy_delay)
-{
-    return h264bsdmiReplayCreateSched(blobs, bytes, n_pics, n_streams, offsets, heavy_lanes, heavy_delay, 1);
-}
-
-h264bsdmi_replay *h264bsdmiReplayCreateSched(const u8 *const *blobs, const u32 *bytes, u32 n_pics, u32 n_streams,
-                                             const u32 *offsets, u32 heavy_lanes, u32 heavy_delay, u32 groups)
-{
-    if (groups < 1) groups = 1;
-    if (groups > 16 || groups > n_streams) return nullptr;
-    if (heavy_lanes + groups > (u32)h264bsdmi_replay::MAX_LANES) return nullptr;
-    for (u32 s = 0; offsets && s < n_streams; s++) if (offsets[s] >= n_pics) return nullptr;
-    Engine *e = engine_get();
-    if (!e || !n_pics || !n_streams) {
-        if (!e) fprintf(stderr, "h264bsd-mi355x: h264bsdmiReplayCreate: no usable HIP device\n");
-        return nullptr;
-    }
-    std::lock_guard<std::mutex> lk(e->mu);
-    if (hipSetDevice(e->device) != hipSuccess) return nullptr;
-    h264bsdmi_replay *r = new h264bsdmi_replay();
-    r->e = e; r->n_pics = n_pics; r->n_streams = n_streams;
-    r->offsets.assign(n_streams, 0);
-    if (offsets) r->offsets.assign(offsets, offsets + n_streams);
-    const FjHeader *h0 = reinterpret_cast<const FjHeader *>(blobs[0]);
-    r->wmb = h0->width_mbs; r->hmb = h0->height_mbs; r->n_slots = h0->n_slots;
-    r->frame_bytes = fj_frame_bytes(r->wmb, r->hmb);
-    std::vector<size_t> offs(n_pics);
-    size_t total = 0;
-    r->job_bytes = 0;
-    for (u32 i = 0; i < n_pics; i++) { offs[i] = total; total += ((size_t)bytes[i] + 255u) & ~(size_t)255u; r->job_bytes += bytes[i]; }
-    r->blob_stride = total;
-    r->blob_off = offs;
-    const size_t frames_per_stream = (size_t)r->n_slots * r->frame_bytes;
-    const size_t dbk_half = (DBK_SCRATCH_BYTES(h0->n_mbs) + 255) & ~(size_t)255, dbk_stride = dbk_half;
-    r->frames_per_stream = frames_per_stream; r->dbk_half = dbk_half; r->dbk_stride = dbk_stride;
-    bool ok = r->d_blobs.alloc(total * n_streams) == hipSuccess &&
-              r->d_frames.alloc(frames_per_stream * n_streams + 256) == hipSuccess &&
-              r->d_desc.alloc(sizeof(FrameDesc) * (size_t)n_pics * n_streams) == hipSuccess &&
-              r->d_sums.alloc(sizeof(unsigned long long) * n_streams) == hipSuccess &&
-              r->d_dbk.alloc((size_t)n_streams * dbk_stride) == hipSuccess;
-    if (ok) ok = hipMemsetAsync(r->d_dbk, 0, (size_t)n_streams * dbk_stride, e->stream) == hipSuccess;
-    if (ok) ok = hipMemsetAsync(r->d_frames, 0, frames_per_stream * n_streams + 256, e->stream) == hipSuccess;
-    /* stream 0 from the host, the other copies device-to-device: every stream owns private jobs */
-    for (u32 i = 0; ok && i < n_pics; i++) {
-        ok = hipMemcpyAsync(r->d_blobs + offs[i], blobs[i], bytes[i], hipMemcpyHostToDevice, e->stream) == hipSuccess;
-        const FjHeader *h = reinterpret_cast<const FjHeader *>(blobs[i]);
-        if (h->width_mbs != r->wmb || h->height_mbs != r->hmb || h->n_slots != r->n_slots) ok = false;
-        r->heads.push_back(*h);
-        r->cur_slot.push_back(h->cur_slot);
-    }
-    if (ok) ok = hipStreamSynchronize(e->stream) == hipSuccess;
-    for (u32 s = 1; ok && s < n_streams; s++)
-        ok = hipMemcpyAsync(r->d_blobs + (size_t)s * total, r->d_blobs, total, hipMemcpyDeviceToDevice, e->stream) == hipSuccess;
-    if (ok) ok = replay_schedule(r, heavy_lanes, heavy_delay, groups);
-    r->timers.resize(n_pics);
-    for (auto &t : r->timers) {
-        for (auto &ev : t.ev) if (ok) ok = ev.create() == hipSuccess;
-        for (auto &ev : t.sev) if (ok) ok = ev.create() == hipSuccess;
-    }
-    if (ok) ok = r->ev_begin.create() == hipSuccess && r->ev_end.create() == hipSuccess && r->gdone_any.create(hipEventDisableTiming) == hipSuccess;
-    r->timed_first = r->timed_count = 0;
-    r->stages = 7u;
-    r->n_groups = 1;
-    if (!ok) {
-        fprintf(stderr, "h264bsd-mi355x: h264bsdmiReplayCreate failed (%s)\n", hipGetErrorString(hipGetLastError()));
-        delete r;
-        return nullptr;
-    }
-    return r;
-}
-
-void h264bsdmiReplayDestroy(h264bsdmi_replay *r)
-{
-    if (!r) return;
-    std::lock_guard<std::mutex> lk(r->e->mu);
-    hipSetDevice(r->e->device);
-    hipStreamSynchronize(r->e->stream);           /* (every lane and stream group of the set is joined into it: h264bsdmiReplayRun) */
-    delete r;
-}
-
-/* The same resident jobs and frame buffers under another schedule (other first pictures, heavy lanes, stream groups): what
- * a second h264bsdmiReplayCreate* would build, without allocating and uploading 20 GB again.  Frame buffers and deblocking
- * scratch start from zero like those of a new set.  0 = ok; after a failure the set can only be destroyed. */
-int h264bsdmiReplayReschedule(h264bsdmi_replay *r, const u32 *offsets, u32 heavy_lanes, u32 heavy_delay, u32 groups)
-{
-    if (!r) return -1;
-    if (groups < 1) groups = 1;
-    if (groups > 16 || groups > r->n_streams || heavy_lanes + groups > (u32)h264bsdmi_replay::MAX_LANES) return -1;
-    for (u32 s = 0; offsets && s < r->n_streams; s++) if (offsets[s] >= r->n_pics) return -1;
-    Engine *e = r->e;
-    std::lock_guard<std::mutex> lk(e->mu);
-    HIP_TRY(hipSetDevice(e->device));
-    /* everything the old schedule launched has to be over before its streams and events go */
-    for (auto &st : r->lanes) if (st) HIP_TRY(hipStreamSynchronize(st));
-    for (int g = 0; g < 8; g++) if (r->gstream[g]) HIP_TRY(hipStreamSynchronize(r->gstream[g]));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    if (poll_errors(e)) return -1;
-    r->sched_ev.clear(); r->sched.clear();
-    r->retire_streams();                               /* (kept for the next schedule: h264bsdmi_replay::pool_*) */
-    for (auto &st : r->gstream) r->retire_stream(st);  /* h264bsdmiReplaySetGroups takes them back */
-    r->n_lanes = r->n_light = 0;
-    r->n_groups = 1;                                  /* (h264bsdmiReplaySetGroups: a property of the schedule it was set for) */
-    r->convert_fmt = -1; r->timed_mask = 31u; r->stages = 7u;
-    r->offsets.assign(r->n_streams, 0);
-    if (offsets) r->offsets.assign(offsets, offsets + r->n_streams);
-    HIP_TRY(hipMemsetAsync(r->d_dbk, 0, (size_t)r->n_streams * r->dbk_stride, e->stream));
-    HIP_TRY(hipMemsetAsync(r->d_frames, 0, r->frames_per_stream * r->n_streams + 256, e->stream));
-    if (!replay_schedule(r, heavy_lanes, heavy_delay, groups)) return -1;
-    r->timed_first = r->timed_count = 0;
-    return 0;
-}
-
-int h264bsdmiReplayRun(h264bsdmi_replay *r, u32 first, u32 count)
-{
-    if (!r || first + count > r->n_pics) return -1;
-    std::lock_guard<std::mutex> lk(r->e->mu);
-    HIP_TRY(hipSetDevice(r->e->device));
-    r->timed_first = first; r->timed_count = count;
-    for (auto &l : r->launches) l = 0;
-    HIP_TRY(hipEventRecord(r->ev_begin, r->e->stream));
-    if (!r->sched.empty()) {
-        /* desynchronised set with lanes: one whole lap of the static schedule (first / count are ignored) */
-        r->timed_count = 0;
-        for (u32 k = 0; k < r->n_lanes; k++) HIP_TRY(hipStreamWaitEvent(r->lanes[k], r->ev_begin, 0));   /* the previous lap is complete */
-        std::vector<hipEvent_t> lane_mark(r->n_light, nullptr);
-        for (const auto &l : r->sched) {
-            hipStream_t st = r->lanes[l.lane];
-            for (int w : l.waits) {
-                if (w >= 0) HIP_TRY(hipStreamWaitEvent(st, r->sched_ev[w], 0));
-                else {                                   /* -2 - g: everything enqueued on light lane g so far */
-                    HIP_TRY(hipEventRecord(r->gdone_any, r->lanes[-2 - w]));
-                    HIP_TRY(hipStreamWaitEvent(st, r->gdone_any, 0));
-                }
-            }
-            if (l.shape.n_frames && launch_tick(st, r->d_desc + l.first, [&] { TickShape sh = l.shape; sh.load = r->n_streams; return sh; }(), nullptr, r->launches, r->stages,
-                                                (l.light && r->overlap_dbk && !(r->stages & 8u) && r->lane_side[l.lane].stream) ? &r->lane_side[l.lane] : nullptr)) return -1;
-            if (l.record_ev >= 0) HIP_TRY(hipEventRecord(r->sched_ev[l.record_ev], st));
-        }
-        for (u32 k = 0; k < r->n_lanes; k++) {               /* the lap ends when every lane has drained */
-            HIP_TRY(hipEventRecord(r->gdone_any, r->lanes[k]));
-            HIP_TRY(hipStreamWaitEvent(r->e->stream, r->gdone_any, 0));
-        }
-    } else if (r->n_groups <= 1) {
-        for (u32 i = first; i < first + count; i++) { r->timers[i].on = true; r->timers[i].mask = r->timed_mask; }
-        r->cev_on.assign(r->n_pics, 0);
-        for (u32 i = first; i < first + count; i++) {
-            /* config 3: the pictures of tick i - 1 are converted by tick i's k_frame_dbk workgroups where the schedule allows it */
-            const bool host = r->convert_fmt >= 0 && r->host_convert && i > first && r->hosted[i];
-            TickShape shape = r->shapes[i];
-            shape.conv = host; shape.conv_waves = r->conv_waves;
-            if (launch_tick(r->e->stream, (host ? r->d_desc_conv : r->d_desc) + (size_t)i * r->n_streams, shape, &r->timers[i], r->launches, r->stages, (r->overlap_dbk && !(r->stages & 8u)) ? &r->e->side : nullptr, r->e->tail_prof)) return -1;
-            const bool next_hosts = r->convert_fmt >= 0 && r->host_convert && i + 1 < first + count && r->hosted[i + 1];
-            if (r->convert_fmt >= 0 && !next_hosts && (r->convert_trailing || i + 1 < first + count)) {
-                /* the picture every stream has just produced, converted where it lies (tiles -> packed 32-bit pixels) */
-                const uint32_t w = r->wmb * 16, h = r->hmb * 16;
-                HIP_TRY(hipEventRecord(r->cev[2 * i], r->e->stream));
-                hipLaunchKernelGGL(h264k::k_convert_tiles, CONVERT_GRID(r->n_streams), dim3(256), 0, r->e->stream,
-                                   r->d_frames + (size_t)r->cur_slot[i] * r->frame_bytes, r->d_conv, r->wmb, r->hmb, r->convert_fmt,
-                                   (size_t)r->n_slots * r->frame_bytes, (size_t)w * h);
-                HIP_TRY(hipEventRecord(r->cev[2 * i + 1], r->e->stream));
-                r->cev_on[i] = 1;
-            }
-        }
-    } else {
-        /* stream groups on separate HIP streams: the latency-bound per-picture tail of one group overlaps
-         * with the throughput-bound inter reconstruction of another (pictures of different streams are
-         * independent; every group still runs its own pictures strictly in order) */
-        const u32 G = r->n_groups, per = (r->n_streams + G - 1) / G;
-        for (u32 g = 0; g < G; g++) HIP_TRY(hipStreamWaitEvent(r->gstream[g], r->ev_begin, 0));
-        for (u32 i = first; i < first + count; i++) {
-            for (u32 g = 0; g < G; g++) {
-                const u32 s0 = g * per, s1 = std::min(r->n_streams, s0 + per);
-                if (s0 >= s1) continue;
-                TickShape sh = r->shapes[i];
-                sh.n_frames = s1 - s0;
-                sh.load = r->n_streams;
-                TickTimers &tt = r->timers[(size_t)g * r->n_pics + i];
-                tt.on = true; tt.mask = r->timed_mask;
-                /* (making the groups take turns at the list-driven kernels — a ring of events — works as designed in the kernel
-                 * trace and loses: docs/EXPERIMENTS.md) */
-                if (i == first && g > 0) HIP_TRY(hipStreamWaitEvent(r->gstream[g], r->timers[(size_t)(g - 1) * r->n_pics + i].ev[3], 0));
-                if (launch_tick(r->gstream[g], r->d_desc + (size_t)i * r->n_streams + s0, sh, &tt, r->launches, r->stages)) return -1;
-            }
-        }
-        for (u32 g = 0; g < G; g++) {
-            HIP_TRY(hipEventRecord(r->gdone[g], r->gstream[g]));
-            HIP_TRY(hipStreamWaitEvent(r->e->stream, r->gdone[g], 0));
-        }
-    }
-    HIP_TRY(hipEventRecord(r->ev_end, r->e->stream));
-    return 0;
-}
-
-int h264bsdmiReplaySetGroups(h264bsdmi_replay *r, u32 n_groups)
-{
-    if (!r || n_groups < 1 || n_groups > 8) return -1;
-    std::lock_guard<std::mutex> lk(r->e->mu);
-    HIP_TRY(hipSetDevice(r->e->device));
-    while (r->timers.size() < (size_t)n_groups * r->n_pics) {
-        TickTimers t;
-        for (auto &ev : t.ev) HIP_TRY(ev.create());
-        r->timers.push_back(std::move(t));
-    }
-    for (u32 g = 0; g < n_groups; g++) {
-        if (!r->gstream[g] && !r->take_stream(&r->gstream[g], false, 0)) return -1;
-        if (!r->gdone[g]) HIP_TRY(r->gdone[g].create(hipEventDisableTiming));
-    }
-    r->n_groups = n_groups;
-    return 0;
-}
-
-int h264bsdmiReplaySync(h264bsdmi_replay *r)
-{
-    if (!r) return -1;
-    HIP_TRY(hipSetDevice(r->e->device));
-    HIP_TRY(hipStreamSynchronize(r->e->stream));
-    return 0;
-}
-
-int h264bsdmiReplayTimings(h264bsdmi_replay *r, float out_ms[6], u32 launches[5])
-{
-    if (!r) return -1;
-    HIP_TRY(hipSetDevice(r->e->device));
-    HIP_TRY(hipStreamSynchronize(r->e->stream));
-    for (int k = 0; k < 6; k++) out_ms[k] = 0.f;
-    for (u32 g = 0; g < r->n_groups; g++)
-        for (u32 i0 = r->timed_first; i0 < r->timed_first + r->timed_count; i0++) {
-            const size_t i = (size_t)g * r->n_pics + i0;
-            for (int k = 0; k < 5; k++) {
-                float ms;
-                if (!((r->timed_mask >> k) & 1u)) continue;
-                HIP_TRY(hipEventElapsedTime(&ms, r->timers[i].ev[k], r->timers[i].ev[k + 1]));
-                out_ms[k] += ms;
-            }
-            if ((r->timed_mask & 4u) && r->overlap_dbk && !(r->stages & 8u) && r->n_groups == 1 && r->timers[i].sev[0] &&
-                hipEventQuery(r->timers[i].sev[2]) == hipSuccess) {
-                float ms;                                /* k_dbk ran on the side stream, next to the kernels above */
-                if (hipEventElapsedTime(&ms, r->timers[i].sev[1], r->timers[i].sev[2]) == hipSuccess) out_ms[2] += ms;
-            }
-            if (r->timers[i].copy_timed && hipEventQuery(r->timers[i].sev[4]) == hipSuccess) {
-                float ms;                                /* and so did k_copy, on a stream of its own (zero when the tick had no copy to launch) */
-                if (hipEventElapsedTime(&ms, r->timers[i].sev[3], r->timers[i].sev[4]) == hipSuccess) out_ms[0] += ms;
-            }
-        }
-    if (r->timed_count || !r->sched.empty()) HIP_TRY(hipEventElapsedTime(&out_ms[5], r->ev_begin, r->ev_end));
-    if (launches) for (int k = 0; k < 5; k++) launches[k] = r->launches[k];
-    return 0;
-}
-
-int h264bsdmiReplayFetch(h264bsdmi_replay *r, u32 stream, u32 slot, u8 *dst)
-{
-    if (!r || stream >= r->n_streams || slot >= r->n_slots) return -1;
-    HIP_TRY(hipSetDevice(r->e->device));
-    std::lock_guard<std::mutex> lk(r->e->mu);
-    if (!r->d_planar) HIP_TRY(r->d_planar.alloc(r->frame_bytes));
-    hipLaunchKernelGGL(h264k::k_detile, dim3(512, 1), dim3(256), 0, r->e->stream, r->d_frames + ((size_t)stream * r->n_slots + slot) * r->frame_bytes,
-                       r->d_planar, r->wmb, r->hmb, (size_t)0, (size_t)0);
-    HIP_TRY(hipMemcpyAsync(dst, r->d_planar, r->frame_bytes, hipMemcpyDeviceToHost, r->e->stream));
-    HIP_TRY(hipStreamSynchronize(r->e->stream));
-    return 0;
-}
-
-int h264bsdmiReplayChecksums(h264bsdmi_replay *r, u32 slot, unsigned long long *sums)
-{
-    if (!r || slot >= r->n_slots) return -1;
-    std::lock_guard<std::mutex> lk(r->e->mu);
-    HIP_TRY(hipSetDevice(r->e->device));
-    hipLaunchKernelGGL(h264k::k_checksum, dim3(r->n_streams), dim3(256), 0, r->e->stream,
-                       r->d_frames + (size_t)slot * r->frame_bytes, (size_t)r->n_slots * r->frame_bytes, r->wmb, r->hmb, r->d_sums);
-    HIP_TRY(hipMemcpyAsync(sums, r->d_sums, sizeof(unsigned long long) * r->n_streams, hipMemcpyDeviceToHost, r->e->stream));
-    if (poll_errors(r->e)) return -1;
-    return 0;
-}
-
-int h264bsdmiReplayConvert(h264bsdmi_replay *r, u32 slot, int fmt)
-{
-    if (!r || slot >= r->n_slots || fmt < 0 || fmt > 2) return -1;
-    std::lock_guard<std::mutex> lk(r->e->mu);
-    HIP_TRY(hipSetDevice(r->e->device));
-    const uint32_t w = r->wmb * 16, h = r->hmb * 16;
-    if (!r->d_conv) HIP_TRY(r->d_conv.alloc((size_t)w * h * 4 * r->n_streams));
-    hipLaunchKernelGGL(h264k::k_convert_tiles, CONVERT_GRID(r->n_streams), dim3(256), 0, r->e->stream,
-                       r->d_frames + (size_t)slot * r->frame_bytes, r->d_conv, r->wmb, r->hmb, fmt,
-                       (size_t)r->n_slots * r->frame_bytes, (size_t)w * h);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-int h264bsdmiReplayFetchConverted(h264bsdmi_replay *r, u32 stream, u32 *dst)
-{
-    if (!r || stream >= r->n_streams || !r->d_conv) return -1;
-    HIP_TRY(hipSetDevice(r->e->device));
-    HIP_TRY(hipStreamSynchronize(r->e->stream));
-    const size_t n = (size_t)r->wmb * 16 * r->hmb * 16;
-    HIP_TRY(hipMemcpy(dst, r->d_conv + (size_t)stream * n, n * 4, hipMemcpyDeviceToHost));
-    return 0;
-}
-
-/* fmt 0..2: every h264bsdmiReplayRun() tick (lock-step sets, one group) is followed by the colour conversion of the
- * pictures it produced, inside the timed region; fmt < 0: off.  h264bsdmiReplayConvertTimings: k_convert time of the last run. */
-int h264bsdmiReplaySetConvert(h264bsdmi_replay *r, int fmt_and_flags)
-{
-    /* flags (tests and A/B runs): 0x100 = no conversion launch behind the LAST tick of a run (what the conversion buffer then holds
-     * is the work of the last tick's hosts), 0x200 = no hosting (every tick followed by its own conversion launch) */
-    const int fmt = fmt_and_flags < 0 ? -1 : (fmt_and_flags & 0xFF);
-    const bool no_trailing = fmt_and_flags >= 0 && (fmt_and_flags & 0x100), no_hosting = fmt_and_flags >= 0 && (fmt_and_flags & 0x200);
-    if (!r || fmt > 2 || !r->sched.empty()) return -1;
-    std::lock_guard<std::mutex> lk(r->e->mu);
-    HIP_TRY(hipSetDevice(r->e->device));
-    if (fmt >= 0) {
-        const size_t n = (size_t)r->wmb * 16 * r->hmb * 16;
-        if (!r->d_conv) HIP_TRY(r->d_conv.alloc(n * 4 * r->n_streams));
-        while (r->cev.size() < 2 * (size_t)r->n_pics) { Event ev; HIP_TRY(ev.create()); r->cev.push_back(std::move(ev)); }
-        /* Hosting.  Tick i can
-         * convert the pictures of tick i - 1 while it decodes its own if no stream decodes INTO the frame buffer its previous
-         * picture lies in (an IDR picture may); the stand-alone launch converts one frame buffer number for all streams, so the
-         * streams have to be in step. */
-        HIP_TRY(hipStreamSynchronize(r->e->stream));
-        r->host_convert = !no_hosting;
-        r->convert_trailing = !no_trailing;
-        r->conv_waves = ((uint32_t)fmt_and_flags >> 16) & 15u;
-        bool in_step = true;
-        for (u32 s = 1; s < r->n_streams; s++) if (r->offsets[s] != r->offsets[0]) in_step = false;
-        r->hosted.assign(r->n_pics, 0);
-        for (u32 i = 1; in_step && i < r->n_pics; i++) r->hosted[i] = r->cur_slot[i] != r->cur_slot[i - 1];
-        const size_t n_desc = (size_t)r->n_pics * r->n_streams;
-        if (!r->d_desc_conv) HIP_TRY(r->d_desc_conv.alloc(sizeof(FrameDesc) * n_desc));
-        std::vector<FrameDesc> descs(n_desc);
-        HIP_TRY(hipMemcpy(descs.data(), r->d_desc, sizeof(FrameDesc) * n_desc, hipMemcpyDeviceToHost));
-        for (u32 i = 1; i < r->n_pics; i++)
-            for (u32 s = 0; s < r->n_streams && r->hosted[i]; s++) {
-                FrameDesc &d = descs[(size_t)i * r->n_streams + s];
-                d.conv_src = r->d_frames + (size_t)s * r->frames_per_stream + (size_t)r->cur_slot[i - 1] * r->frame_bytes;
-                d.conv_dst = r->d_conv + (size_t)s * n;
-                d.conv_fmt = (uint32_t)fmt;
-            }
-        HIP_TRY(hipMemcpy(r->d_desc_conv, descs.data(), sizeof(FrameDesc) * n_desc, hipMemcpyHostToDevice));
-    }
-    r->convert_fmt = fmt;
-    return 0;
-}
-
-int h264bsdmiReplayConvertTimings(h264bsdmi_replay *r, float *ms, u32 *launches)
-{
-    if (!r || r->convert_fmt < 0) return -1;
-    HIP_TRY(hipSetDevice(r->e->device));
-    HIP_TRY(hipStreamSynchronize(r->e->stream));
-    *ms = 0.f; *launches = 0;
-    for (u32 i = r->timed_first; i < r->timed_first + r->timed_count; i++) {
-        float t;
-        if (i >= r->cev_on.size() || !r->cev_on[i]) continue;      /* converted by the next tick's k_frame_dbk: no launch of its own */
-        HIP_TRY(hipEventElapsedTime(&t, r->cev[2 * i], r->cev[2 * i + 1]));
-        *ms += t; (*launches)++;
-    }
-    return 0;
-}
-
-int h264bsdmiReplaySetTimedKernels(h264bsdmi_replay *r, unsigned mask)
-{
-    if (!r) return -1;
-    r->timed_mask = mask & 31u;     /* bit k: HIP events around kernel k (k_copy, k_recon_inter, k_dbk, k_frame_intra, k_frame_dbk) */
-    return 0;
-}
-
-int h264bsdmiReplaySetStages(h264bsdmi_replay *r, unsigned mask)
-{
-    if (!r) return -1;
-    r->stages = mask & 15u;        /* bit 3: keep k_dbk on the main stream (no overlap) */
-    return 0;
-}
-
-/* Debug hook: cycle accounting of k_frame_tail's deblocking loop (workgroup 0 of the next launches).
- * out[16][8]: per wave {pick, filter, extra rounds, own-memory wait, filtered count, barrier wait}. */
-int h264bsdmiDebugTailProfile(int enable, unsigned long long *out)
-{
-    Engine *e = engine_get();
-    if (!e) return -1;
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(hipDeviceSynchronize());
-    if (enable) {
-        if (!e->tail_prof) HIP_TRY(e->tail_prof.alloc((16 * 16 + 16 * 8) * sizeof(unsigned long long)));
-        HIP_TRY(hipMemset(e->tail_prof, 0, (16 * 16 + 16 * 8) * sizeof(unsigned long long)));
-        HIP_TRY(hipDeviceSynchronize());
-    } else if (e->tail_prof) {
-        if (out) HIP_TRY(hipMemcpy(out, e->tail_prof, (16 * 16 + 16 * 8) * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        e->tail_prof.reset();
-    }
-    return 0;
-}
-
-/* Test / tuning hook: how the per-picture kernels split pictures from now on (TailConfig; descriptors built earlier keep their
- * bands): rows per band for light and heavy pictures (0 = one band) and wavefronts per workgroup, for k_frame_dbk and
- * k_frame_intra.  A value of 0xFFFFFFFF leaves that setting alone. */
-int h264bsdmiDebugSetTail(u32 dbk_rows_light, u32 dbk_rows_heavy, u32 dbk_waves, u32 intra_rows_light, u32 intra_rows_heavy, u32 intra_waves, u32 band_budget)
-{
-    (void)tail_config();                                     /* the environment first, once */
-    std::lock_guard<std::mutex> lk(g_tail_mu);
-    if (dbk_rows_light != 0xFFFFFFFFu) g_tail.dbk_rows_light = dbk_rows_light;
-    if (dbk_rows_heavy != 0xFFFFFFFFu) g_tail.dbk_rows_heavy = dbk_rows_heavy;
-    if (dbk_waves != 0xFFFFFFFFu && dbk_waves >= 1) g_tail.dbk_waves = dbk_waves;
-    if (intra_rows_light != 0xFFFFFFFFu) g_tail.intra_rows_light = intra_rows_light;
-    if (intra_rows_heavy != 0xFFFFFFFFu) g_tail.intra_rows_heavy = intra_rows_heavy;
-    if (intra_waves != 0xFFFFFFFFu && intra_waves >= 1) g_tail.intra_waves = intra_waves;
-    if (band_budget != 0xFFFFFFFFu) g_tail.band_budget = band_budget;
-    return 0;
-}
-
-unsigned long long h264bsdmiReplayJobBytes(h264bsdmi_replay *r) { return r ? r->job_bytes : 0; }
-u32 h264bsdmiReplayFrameBytes(h264bsdmi_replay *r) { return r ? r->frame_bytes : 0; }
-
 } /* extern "C" */
+#include "replay.hip.h"      /* the bench library's replay sets and debug hooks (include/h264bsd_mi355x_bench.h) */

@@ -1,9 +1,10 @@
-/* hip_owned.h — move-only owners of the engine's HIP objects (engine.hip): stream, event, device and pinned host allocation.  An owner
+/* hip_owned.h — move-only owners of the engine's HIP objects (engine.hip): stream, event, device and pinned host allocation (Staged: a ring of two).  An owner
  * releases its object when it goes or is reset, and nothing else in the engine does (tests/test_abi.py); waiting for the device first is
  * the holder's business.  A creation that fails leaves the owner empty and returns the HIP error. */
 #ifndef H264BSD_AMD_HIP_OWNED_H
 #define H264BSD_AMD_HIP_OWNED_H
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <utility>
 
 void tickets_release(hipStream_t st);       /* engine.hip: the ticket counters of the stream's banded launches */
@@ -49,5 +50,41 @@ template <class T> struct Pinned : Owned<T *, host_free<T>> {
     T *dev() const { return this->h_ ? d_ : nullptr; }
 private:
     T *d_ = nullptr;
+};
+/* Pinned staging that launches read while the host fills the next one's: two halves of cap() elements used in turn, each guarded by an
+ * event recorded behind the launch that read it.  A half is free when nothing was submitted from it yet or its event has passed — with
+ * two halves, the launch before the last one read it.  Per use: reserve(), fill host(), launch with dev(), submit() on that stream. */
+template <class T> class Staged {
+public:
+    /* room for n elements in the current half, and that half free; a ring that is too small waits for the readers of both halves, is
+     * allocated again with max(n, min_cap) elements per half and starts over at half 0 */
+    hipError_t reserve(size_t n, size_t min_cap = 0)
+    {
+        hipError_t err;
+        if (n > cap_) {
+            for (int k = 0; k < 2; k++)
+                if (used_[k] && (err = hipEventSynchronize(ev_[k])) != hipSuccess) return err;
+            cap_ = 0; cur_ = 0; used_[0] = used_[1] = false;
+            if ((err = mem_.alloc(2 * std::max(n, min_cap) * sizeof(T), true)) != hipSuccess) return err;
+            for (Event &ev : ev_)
+                if (!ev && (err = ev.create(hipEventDisableTiming)) != hipSuccess) return err;
+            cap_ = std::max(n, min_cap);
+        }
+        return used_[cur_] ? hipEventSynchronize(ev_[cur_]) : hipSuccess;
+    }
+    /* the current half as the host fills it / as the device reads it (U: what the elements hold); half(): for a buffer kept beside the ring under its guard */
+    template <class U = T> U *host() const { return reinterpret_cast<U *>(mem_.get() + (size_t)cur_ * cap_); }
+    template <class U = T> const U *dev() const { return reinterpret_cast<const U *>(mem_.dev() + (size_t)cur_ * cap_); }
+    size_t cap() const { return cap_; }    int half() const { return cur_; }
+    /* the launch that reads the current half is on st: guard the half, go on to the other */
+    hipError_t submit(hipStream_t st)
+    {
+        const hipError_t err = hipEventRecord(ev_[cur_], st);
+        if (err == hipSuccess) { used_[cur_] = true; cur_ ^= 1; }
+        return err;
+    }
+private:
+    Pinned<T> mem_; Event ev_[2]; bool used_[2] = { false, false };
+    size_t cap_ = 0; int cur_ = 0;
 };
 #endif
