@@ -28,7 +28,7 @@ EXPORTED_SYMBOLS = [
     "h264bsdCroppingParams", "h264bsdSampleAspectRatio", "h264bsdCheckValidParamSets", "h264bsdFlushBuffer",
     "h264bsdProfile", "h264bsdAlloc", "h264bsdFree", "h264bsdConvertToRGBA", "h264bsdConvertToBGRA",
     "h264bsdConvertToYCbCrA",
-    "h264bsdmiInitCapture", "h264bsdmiNextOutputInfo", "h264bsdmiNextOutputPictureDevice", "h264bsdmiNextOutputTensorBatch", "h264bsdmiNextOutputTensorBatchColour", "h264bsdmiNextOutputTensorBatchResize", "h264bsdmiOutputTensorRegions", "h264bsdmiOutputTensorRemap", "h264bsdmiSetMotionExport", "h264bsdmiOutputMotionRegions", "h264bsdmiJobFinalize", "h264bsdmiDeviceCount", "h264bsdmiSetDevice", "h264bsdmiFlush", "h264bsdmiFlushAsync", "h264bsdmiDeviceErrors",
+    "h264bsdmiInitCapture", "h264bsdmiNextOutputInfo", "h264bsdmiNextOutputPictureDevice", "h264bsdmiNextOutputTensorBatch", "h264bsdmiNextOutputTensorBatchColour", "h264bsdmiNextOutputTensorBatchResize", "h264bsdmiOutputTensorRegions", "h264bsdmiOutputTensorRemap", "h264bsdmiSetMotionExport", "h264bsdmiOutputMotionRegions", "h264bsdmiOutputRegionStats", "h264bsdmiJobFinalize", "h264bsdmiDeviceCount", "h264bsdmiSetDevice", "h264bsdmiFlush", "h264bsdmiFlushAsync", "h264bsdmiDeviceErrors",
     "h264bsdmiDecodePicture", "h264bsdmiDecodePictureBatch", "h264bsdmiNextOutputPictureBatch", "h264bsdmiPullAndDecodePictureBatch", "h264bsdmiSetParserThreads", "h264bsdmiSetInputReadOnly", "h264bsdmiSetCopyElision",
     "h264bsdmiReplayCreate", "h264bsdmiReplayCreateStaggered", "h264bsdmiReplayCreateDesync", "h264bsdmiReplayCreateSched", "h264bsdmiReplayReschedule", "h264bsdmiReplayDestroy", "h264bsdmiReplayRun", "h264bsdmiReplaySync",
     "h264bsdmiReplayFetch", "h264bsdmiReplayChecksums", "h264bsdmiReplayConvert", "h264bsdmiReplayFetchConverted",
@@ -84,6 +84,13 @@ class MotionSpec(ctypes.Structure):
                 ("sampler", ctypes.c_uint32), ("units", ctypes.c_uint32), ("per_picture", ctypes.c_uint32)]
 
 
+class StatsSpec(ctypes.Structure):
+    """h264bsdmi_stats_spec (include/h264bsd_mi355x.h)"""
+    _fields_ = [("data", ctypes.c_void_p), ("source", ctypes.c_uint32), ("bins", ctypes.c_uint32), ("crop", ctypes.c_uint32)]
+
+
+STATS_SOURCES = {"y": (0, 1), "ycbcr": (1, 3), "rgb": (2, 3)}                    # name -> (H264BSDMI_STATS_*, channels)
+STATS_BINS = (0, 16, 32, 64, 128, 256)
 MOTION_PLANES = {"mv": (1, 2), "valid": (2, 1), "age": (4, 1), "qp": (8, 1)}     # name -> (H264BSDMI_MOTION_PLANE_*, channels), in channel order
 MOTION_SAMPLERS = {"nearest": 0, "area": 1}                                      # H264BSDMI_MOTION_*
 MOTION_UNITS = {"source": 0, "output": 1}                                        # H264BSDMI_MOTION_UNITS_*
@@ -213,6 +220,8 @@ def _declare(L, harness):
     L.h264bsdmiOutputMotionRegions.argtypes = [u32, ctypes.POINTER(vp), u32, ctypes.POINTER(Region), ctypes.POINTER(MotionSpec), vp,
                                                P32, P32, P32, P32]
     L.h264bsdmiOutputMotionRegions.restype = ctypes.c_int
+    L.h264bsdmiOutputRegionStats.argtypes = [u32, ctypes.POINTER(vp), u32, ctypes.POINTER(Region), ctypes.POINTER(StatsSpec), vp, P32, P32, P32]
+    L.h264bsdmiOutputRegionStats.restype = ctypes.c_int
     L.h264bsdmiDecodePicture.argtypes = [vp, u8p, u32, u32, P32, P32]
     L.h264bsdmiDecodePicture.restype = u32
     L.h264bsdmiDecodePictureBatch.argtypes = [u32, ctypes.POINTER(vp), ctypes.POINTER(vp), P32, P32, P32, P32, P32]
@@ -798,6 +807,77 @@ def pull_motion(decoders, regions=None, size=None, layout="NCHW", dtype=None, pl
     if rc != 0:
         raise RuntimeError(f"h264bsdmiOutputMotionRegions failed ({rc})")
     return (out, list(got)[:K], [tuple(box[4 * k: 4 * k + 4]) if got[k] else None for k in range(K)], list(cur)[:n], list(ids)[:n])
+
+
+def stats_record_bytes(source, bins):
+    """the stride of one record of h264bsdmiOutputRegionStats: 8 + 24 C + 4 C B bytes"""
+    if source not in STATS_SOURCES or bins not in STATS_BINS:
+        raise ValueError(f"stats_record_bytes: unsupported source / bins {source} {bins}")
+    C = STATS_SOURCES[source][1]
+    return 8 + 24 * C + 4 * C * bins
+
+
+class RegionStats:
+    """what pull_stats returns: count [R] int32; sum, sumsq [R, C] int64; min, max [R, C] int32; hist [R, C, B] int32 or None — views
+    of `records` ([R, stride] uint8, one allocation, the C layout); got [R], current and pic_id per decoder, lists of ints"""
+
+    def __init__(self, records, C, B, got, current, pic_id):
+        import torch
+        w32, w64 = records.view(torch.int32), records.view(torch.int64)
+        self.records = records
+        self.count = w32[:, 0]
+        self.sum, self.sumsq = w64[:, 1:1 + 3 * C:3], w64[:, 2:2 + 3 * C:3]
+        self.min, self.max = w32[:, 6:6 + 6 * C:6], w32[:, 7:7 + 6 * C:6]
+        self.hist = w32[:, 2 + 6 * C:].unflatten(1, (C, B)) if B else None
+        self.got, self.current, self.pic_id = got, current, pic_id
+
+
+def pull_stats(decoders, regions=None, source="ycbcr", bins=256, crop=True, out=None, stream=None):
+    """h264bsdmiOutputRegionStats: integer statistics of boxes of the decoders' CURRENT pictures (as for pull_regions), computed by one
+    kernel launch where the pictures lie — nothing is popped and no pixel is pulled.  regions as for pull_regions; None: one region
+    per decoder, its whole source window.  source "y" (1 channel), "ycbcr" or "rgb" (3; the reference's integer conversion); bins
+    0 (no histogram), 16, 32, 64, 128 or 256 (bin = value >> (8 - log2 bins)).  A record covers the part of its box inside the
+    window: count, and per channel sum, sumsq, min, max (255 / 0 when count is 0) and hist.  out: a contiguous CUDA uint8 tensor
+    [R, stats_record_bytes(source, bins)] to write into (None: allocated); records of decoders without a current picture are left
+    untouched there (got[r] = 0).  stream as for pull_tensor.  Returns a RegionStats."""
+    import torch
+    n = len(decoders)
+    if source not in STATS_SOURCES or bins not in STATS_BINS:
+        raise ValueError(f"pull_stats: unsupported source / bins {source} {bins}")
+    src, C = STATS_SOURCES[source]
+    regs = None
+    if regions is not None:
+        regs = []
+        for r in regions:
+            r = tuple(r)
+            if len(r) != 5 or not all(isinstance(v, int) for v in r):
+                raise ValueError(f"pull_stats: a region is (decoder_index, x, y, w, h) in host integers, not {r}")
+            i, x, y, w, h = r
+            if not 0 <= i < n or not 1 <= w <= 16384 or not 1 <= h <= 16384 or abs(x) > 16384 or abs(y) > 16384:
+                raise ValueError(f"pull_stats: region {r} names no decoder of the call or is out of range (1 <= w, h <= 16384, |x|, |y| <= 16384)")
+            regs.append(Region(i, x, y, w, h))
+    K = n if regs is None else len(regs)
+    if K > 65535:
+        raise ValueError("pull_stats: at most 65535 regions per call")
+    shape = (K, stats_record_bytes(source, bins))
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device="cuda")
+    elif not out.is_cuda or out.dtype != torch.uint8 or tuple(out.shape) != shape or not out.is_contiguous() or out.data_ptr() % 8:
+        raise ValueError(f"pull_stats: out must be a contiguous, 8-byte aligned CUDA uint8 tensor of shape {shape}")
+    if stream is None:
+        stream = torch.cuda.current_stream(out.device)
+    if not stream.cuda_stream:
+        stream.synchronize()        # torch's legacy default stream, as in _tensor_call: the C call uses the library's own stream and waits
+    got = (ctypes.c_uint32 * max(K, 1))()
+    cur, ids = (ctypes.c_uint32 * max(n, 1))(), (ctypes.c_uint32 * max(n, 1))()
+    if K:
+        spec = StatsSpec(out.data_ptr(), src, bins, 1 if crop else 0)
+        rc = api_lib().h264bsdmiOutputRegionStats(n, (ctypes.c_void_p * max(n, 1))(*[d._st for d in decoders]), K,
+                                                  None if regs is None else (Region * K)(*regs), ctypes.byref(spec),
+                                                  stream.cuda_stream, got, cur, ids)
+        if rc != 0:
+            raise RuntimeError(f"h264bsdmiOutputRegionStats failed ({rc})")
+    return RegionStats(out, C, bins, list(got)[:K], list(cur)[:n], list(ids)[:n])
 
 
 def job_header(blob):

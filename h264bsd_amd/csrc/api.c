@@ -349,7 +349,8 @@ int h264bsdmiNextOutputTensorBatchResize(u32 n, storage_t *const *dec, const h26
     return 0;
 }
 
-/* What the pulls of CURRENT pictures share (h264bsdmiOutputTensorRegions, h264bsdmiOutputTensorRemap, h264bsdmiOutputMotionRegions).
+/* What the pulls of CURRENT pictures share (h264bsdmiOutputTensorRegions, h264bsdmiOutputTensorRemap, h264bsdmiOutputMotionRegions,
+ * h264bsdmiOutputRegionStats).
  * current_instances_refused: 1 when an instance is no decoder of this library, is in capture mode (it has no pixels: `remap`
  * chooses the sink entry the call needs) or is repeated. */
 static int current_instances_refused(u32 n, storage_t *const *dec, int remap)
@@ -533,6 +534,55 @@ int h264bsdmiOutputMotionRegions(u32 n, storage_t *const *dec, u32 nRegions, con
             got[regs[j].index] = 1;
             if (box) memcpy(box + 4 * regs[j].index, regs[j].box, sizeof(regs[j].box));
         }
+        report_current(n, dec, current, picId);
+    }
+    free(pics);
+    free(regs);
+    free(pic_of);
+    return rc;
+}
+
+/* Integer statistics of h264bsdmiOutputTensorRegions' regions over the current pictures: the same checks of regions and instances
+ * in the same order, the same windows (tensor_pic); regions == NULL as in the motion pull; nothing popped. */
+int h264bsdmiOutputRegionStats(u32 n, storage_t *const *dec, u32 nRegions, const h264bsdmi_region *regions,
+                               const h264bsdmi_stats_spec *spec, void *stream,
+                               u32 *got, u32 *current, u32 *picId)
+{
+    static const h264bsdmi_colour_spec reference = { H264BSDMI_MATRIX_REFERENCE, 0, 0, 0 };
+    const int LIMIT = 16384;
+    if (!spec || !spec->data || ((uintptr_t)spec->data & 7u) || spec->source > H264BSDMI_STATS_RGB || spec->crop > 1) return -1;
+    if (spec->bins != 0 && spec->bins != 16 && spec->bins != 32 && spec->bins != 64 && spec->bins != 128 && spec->bins != 256) return -1;
+    if (nRegions && !got) return -1;
+    if (nRegions > 65535u || (!regions && nRegions != n)) return -1;
+    for (u32 r = 0; regions && r < nRegions; r++) {
+        const h264bsdmi_region *g = &regions[r];
+        if (g->instance >= n || !g->w || !g->h || g->w > (u32)LIMIT || g->h > (u32)LIMIT) return -1;
+        if (g->x > LIMIT || g->x < -LIMIT || g->y > LIMIT || g->y < -LIMIT) return -1;
+    }
+    if (n && !dec) return -1;
+    if (current_instances_refused(n, dec, 0)) return -1;
+    for (u32 i = 0; i < n; i++)
+        if (!dec_of(dec[i])->hd->sink.region_stats) return -1;               /* an engine without the statistics kernel */
+    const h264bsdmi_tensor_spec window = { spec->data, 1, 1, 0, 0, 0, spec->crop, 1, { 0, 0, 0 }, { 1, 1, 1 } };
+    SinkTensorPic *pics = (SinkTensorPic *)malloc((n ? n : 1) * sizeof(SinkTensorPic));
+    SinkRegion *regs = (SinkRegion *)malloc((nRegions ? nRegions : 1) * sizeof(SinkRegion));
+    u32 *pic_of = (u32 *)malloc((n ? n : 1) * sizeof(u32));
+    if (!pics || !regs || !pic_of) { free(pics); free(regs); free(pic_of); return -1; }
+    u32 m = 0, k = 0;
+    for (u32 i = 0; i < n; i++) pic_of[i] = 0xFFFFFFFFu;
+    for (u32 r = 0; r < nRegions; r++) {
+        const u32 inst = regions ? regions[r].instance : r;
+        const ApiDec *a = dec_of(dec[inst]);
+        if (!a->has_cur || !a->hd->active_sps) continue;                     /* got[r] = 0 */
+        const SinkTensorPic *p = &pics[current_pic(pics, &m, pic_of, a, inst, &window, &reference)];
+        if (regions) regs[k++] = (SinkRegion){ pic_of[inst], r, regions[r].x, regions[r].y, regions[r].w, regions[r].h, { 0, 0, 1, 1 } };
+        else regs[k++] = (SinkRegion){ pic_of[inst], r, 0, 0, p->w, p->h, { 0, 0, 1, 1 } };      /* the whole window */
+    }
+    int rc = 0;
+    if (k && pics[0].sink->region_stats(m, pics, k, regs, spec, stream)) rc = -2;
+    if (!rc) {
+        for (u32 r = 0; r < nRegions; r++) got[r] = 0;
+        for (u32 j = 0; j < k; j++) got[regs[j].index] = 1;
         report_current(n, dec, current, picId);
     }
     free(pics);

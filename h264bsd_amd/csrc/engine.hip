@@ -36,6 +36,7 @@
 #include "kernels/k_tensor_roi.hip.h"
 #include "kernels/k_tensor_remap.hip.h"
 #include "kernels/k_motion.hip.h"
+#include "kernels/k_region_stats.hip.h"
 #include "engine.h"
 #include "hip_owned.h"
 #include "tick_plan.h"
@@ -150,9 +151,9 @@ constexpr unsigned CONVERT_WGS = CONVERT_WGS_N;      /* workgroups per picture o
 constexpr uint32_t LANE_DBK_WAVES = LANE_DBK_WAVES_N;
 
 /* the item stride of the tensor pulls' staging ring: k_tensor_out / k_tensor_resize read TensorItems, k_tensor_aa AaItems, k_tensor_roi
- * RoiItems, k_motion_roi MotionItems, k_tensor_remap RemapItems */
+ * RoiItems, k_motion_roi MotionItems, k_tensor_remap RemapItems, k_region_stats StatsItems */
 constexpr size_t TITEM_BYTES = std::max({ sizeof(h264k::TensorItem), sizeof(h264k::AaItem), sizeof(h264k::RoiItem), sizeof(h264k::MotionItem),
-                                          sizeof(h264k::RemapItem) });
+                                          sizeof(h264k::RemapItem), sizeof(h264k::StatsItem) });
 struct TItemSlot { uint8_t bytes[TITEM_BYTES]; };
 struct Engine {
     std::mutex mu;
@@ -177,6 +178,10 @@ struct Engine {
     /* tensor pulls (tensor_out_locked): the staging ring of their items; fence events that no instance holds any more */
     Staged<TItemSlot> titems;
     std::vector<Fence *> fences;
+    /* region statistics with row bands (stats_out_locked): the regions' tickets (STATS_MAX_PARTIALS words, zero between launches),
+     * then the bands' partial records; stats_ev is recorded behind the latest launch that used them, and the next one waits for it */
+    DeviceMem<uint8_t> d_stats;
+    Event stats_ev;
 };
 
 /* One engine per HIP device, created on first use.  A decoder instance (or replay set) lives on the device that is
@@ -1170,7 +1175,7 @@ static int pull_end_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, hip
     return 0;
 }
 
-/* ---- what the pulls (whole pictures, regions, motion regions, coordinate maps) share, under the engine's mutex ---- */
+/* ---- what the pulls (whole pictures, regions, motion regions, coordinate maps, region statistics) share, under the engine's mutex ---- */
 static const StreamCtx *pic_stream(const SinkTensorPic &p) { return static_cast<SinkUser *>(p.sink->user)->s; }
 /* The refusals per picture: a slot of its instance, frames, a window inside the coded size; for pixels also a matrix that agrees
  * with ref (one kernel: every picture of the call takes the reference conversion, or none) and an even window.  motion: the side
@@ -1351,6 +1356,60 @@ static int motion_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, u
                               pull_grid(m.width, m.height, h264k::TAA_COLS, h264k::TAA_ROWS, n_regs), &margs, fence_ev);
 }
 
+/* h264bsdmiOutputRegionStats: one StatsItem per region, box ∩ window in luma samples of the coded frame, ONE k_region_stats launch
+ * of S row bands per region: S is one value for the launch, about 1024 workgroups in all, at most the macroblock rows of the tallest
+ * box ∩ window, 1 from 1024 regions on.  With S > 1 the bands meet in the engine's scratch (Engine.d_stats), which two launches
+ * must not use at once: st waits for the event behind the previous such launch.  The same ordering and fence as the other pulls. */
+static int stats_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, uint32_t n_regs, const SinkRegion *regs,
+                            const h264bsdmi_stats_spec &sp, hipStream_t st, hipEvent_t *fence_ev)
+{
+    static const void *const fns[3][2] = {
+        { reinterpret_cast<const void *>(&h264k::k_region_stats<h264k::ST_Y, false>), reinterpret_cast<const void *>(&h264k::k_region_stats<h264k::ST_Y, true>) },
+        { reinterpret_cast<const void *>(&h264k::k_region_stats<h264k::ST_YCBCR, false>), reinterpret_cast<const void *>(&h264k::k_region_stats<h264k::ST_YCBCR, true>) },
+        { reinterpret_cast<const void *>(&h264k::k_region_stats<h264k::ST_RGB, false>), reinterpret_cast<const void *>(&h264k::k_region_stats<h264k::ST_RGB, true>) } };
+    uint32_t shift = 8u;
+    while (shift > 0u && (256u >> shift) != sp.bins) shift--;               /* bins == 256 >> shift; shift == 0 also stands for "no such shift" */
+    if (!sp.data || (reinterpret_cast<uintptr_t>(sp.data) & 7u) || sp.source > H264BSDMI_STATS_RGB || sp.crop > 1u) return -1;
+    if (sp.bins && (sp.bins < 16u || (256u >> shift) != sp.bins)) return -1;
+    if (n_regs > 65535u) return -1;                                     /* grid.y */
+    if (!pull_pictures_ok(n, pics, true, false) || !pull_regions_ok(n, n_regs, regs, 1u, 1u)) return -1;
+    if (pull_begin_locked(e, n, pics, n_regs)) return -1;
+    h264k::StatsItem *items = e->titems.host<h264k::StatsItem>();
+    const uint32_t stride = h264k::stats_record_bytes(sp.source == H264BSDMI_STATS_Y ? 1u : 3u, sp.bins);
+    uint32_t tallest = 1u;
+    for (uint32_t r = 0; r < n_regs; r++) {
+        const SinkRegion &g = regs[r];
+        const SinkTensorPic &p = pics[g.pic];
+        const StreamCtx *s = pic_stream(p);
+        const int64_t bx0 = std::max<int64_t>(g.x, 0), bx1 = std::min<int64_t>((int64_t)g.x + g.w, p.w);
+        const int64_t by0 = std::max<int64_t>(g.y, 0), by1 = std::min<int64_t>((int64_t)g.y + g.h, p.h);
+        h264k::StatsItem it{ s->d_frames + (size_t)p.slot * s->frame_bytes, static_cast<uint8_t *>(sp.data) + (size_t)g.index * stride, s->wmb, 0u, 0u, 0u, 0u };
+        if (bx1 > bx0 && by1 > by0) {
+            it.x0 = p.x0 + (uint32_t)bx0; it.x1 = p.x0 + (uint32_t)bx1;
+            it.y0 = p.y0 + (uint32_t)by0; it.y1 = p.y0 + (uint32_t)by1;
+            tallest = std::max(tallest, ((it.y1 + 15u) >> 4) - (it.y0 >> 4));
+        }
+        items[r] = it;
+    }
+    const uint32_t S = n_regs >= h264k::STATS_MAX_PARTIALS ? 1u : std::min(h264k::STATS_MAX_PARTIALS / n_regs, tallest);
+    h264k::StatsArgs sargs{ e->titems.dev<h264k::StatsItem>(), nullptr, nullptr, sp.bins, sp.bins ? shift : 0u };
+    if (S > 1u) {
+        const size_t tickets = h264k::STATS_MAX_PARTIALS * sizeof(uint32_t);
+        if (!e->d_stats) {
+            DeviceMem<uint8_t> fresh;
+            HIP_TRY(e->stats_ev.create(hipEventDisableTiming));
+            HIP_TRY(fresh.alloc(tickets + (size_t)h264k::STATS_MAX_PARTIALS * h264k::STATS_MAX_RECORD));
+            HIP_TRY(hipMemsetAsync(fresh, 0, tickets, st));
+            e->d_stats = std::move(fresh);
+        } else HIP_TRY(hipStreamWaitEvent(st, e->stats_ev, 0));
+        sargs.tickets = reinterpret_cast<uint32_t *>(e->d_stats.get());
+        sargs.partials = e->d_stats.get() + tickets;
+    }
+    if (pull_launch_locked(e, n, pics, st, fns[sp.source][sp.bins != 0u], dim3(S, n_regs), &sargs, fence_ev)) return -1;
+    if (S > 1u) HIP_TRY(hipEventRecord(e->stats_ev, st));
+    return 0;
+}
+
 /* h264bsdmiOutputTensorRemap: the current pictures of the n instances sampled through n_maps coordinate maps by one k_tensor_remap
  * launch, map r into slice maps[r].index.  The fence goes to each distinct instance, so that the next picture decoded into one of
  * these slots waits for this launch.  The maps are the caller's: read on st. */
@@ -1380,7 +1439,7 @@ static int remap_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, ui
     return pull_launch_locked(e, n, pics, st, fn, pull_grid(t.width, t.height, h264k::TRM_COLS, h264k::TRM_ROWS, n_maps), &rargs, fence_ev);
 }
 
-/* What JobSink.tensor_out, tensor_regions, motion_regions and tensor_remap share: one engine (one device) per call, its mutex, the
+/* What JobSink.tensor_out, tensor_regions, motion_regions, tensor_remap and region_stats share: one engine (one device) per call, its mutex, the
  * refusal of a capturing stream, and, when the caller gave no stream, the wait for the fence and the device's error words.
  * body(e, st, &fence_ev): the call's own *_out_locked. */
 template <typename Body> static int sink_tensor_call(uint32_t n, const SinkTensorPic *pics, void *stream, Body body)
@@ -1443,6 +1502,15 @@ int sink_tensor_remap(uint32_t n, const SinkTensorPic *pics, uint32_t n_maps, co
         return remap_out_locked(e, n, pics, n_maps, maps, *spec, chroma, *remap, st, fence_ev);
     });
 }
+int sink_region_stats(uint32_t n, const SinkTensorPic *pics, uint32_t n_regions, const SinkRegion *regions,
+                      const h264bsdmi_stats_spec *spec, void *stream)
+{
+    if (!n_regions) return 0;
+    if (!regions || !spec) return -1;
+    return sink_tensor_call(n, pics, stream, [&](Engine *e, hipStream_t st, hipEvent_t *fence_ev) {
+        return stats_out_locked(e, n, pics, n_regions, regions, *spec, st, fence_ev);
+    });
+}
 /* JobSink.set_motion (h264bsdmiSetMotionExport): before the instance's first sequence is configured */
 int sink_set_motion(void *user, int on)
 {
@@ -1482,6 +1550,7 @@ int eng_attach(JobSink *sink)
     sink->tensor_regions = sink_tensor_regions;
     sink->motion_regions = sink_motion_regions;
     sink->tensor_remap = sink_tensor_remap;
+    sink->region_stats = sink_region_stats;
     sink->set_motion = sink_set_motion;
     return 0;
 }

@@ -220,6 +220,7 @@ struct h264bsdmi_tensor_spec;
 struct h264bsdmi_resize_spec;
 struct h264bsdmi_motion_spec;
 struct h264bsdmi_remap_spec;
+struct h264bsdmi_stats_spec;
 struct JobSink;
 /* one picture of a batched tensor pull (JobSink.tensor_out): the frame buffer `slot` of the instance behind `sink`, its window
  * (x0, y0, w, h), and the picture's index in the output tensor */
@@ -293,6 +294,10 @@ typedef struct JobSink {
                         void *stream);
     /* optional: keep the motion side information of this instance's pictures (h264bsdmiSetMotionExport).  0 = ok, <0: too late */
     int (*set_motion)(void *user, int on);
+    /* optional: integer statistics of the same regions (their box[] is not used), record `index` of spec->data each, with one launch
+     * — h264bsdmiOutputRegionStats.  0 = ok; <0 = error, nothing enqueued */
+    int (*region_stats)(uint32_t n, const SinkTensorPic *pics, uint32_t n_regions, const SinkRegion *regions,
+                        const struct h264bsdmi_stats_spec *spec, void *stream);
 } JobSink;
 
 /* ---------------------------------------------------------------- decoder instance */

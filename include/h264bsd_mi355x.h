@@ -279,6 +279,44 @@ int h264bsdmiOutputMotionRegions(u32 n, storage_t *const *pStorage, u32 nRegions
                                  const h264bsdmi_motion_spec *spec, void *stream,
                                  u32 *got, u32 *box, u32 *current, u32 *picId);
 
+/* Region statistics: sums, extrema and histograms of boxes of the instances' CURRENT pictures (above), computed where the pictures
+ * lie, with one launch — camera health (black, blown out, covered), exposure (the mean and spread to hand the next tensor pull as
+ * mean / std), scene cuts (histogram distance between consecutive pictures), the colour of a detector's box — without pulling a
+ * pixel.  A sibling of h264bsdmiOutputTensorRegions: the same region struct and limits (1 <= w, h <= 16384, |x|, |y| <= 16384,
+ * negative origins, boxes that leave the source window or miss it), the same source window (the SPS cropping window when
+ * spec->crop, else the coded frame), the same current-picture rule and lifetime, the same got (per REGION) / current / picId (per
+ * instance, each may be NULL), the same stream rule (not capturing; NULL: the library's own stream, and the call waits) and the
+ * same fence: later decoding of the instances waits for the kernel, not for the caller.  It pops nothing and may be repeated.
+ * regions == NULL with nRegions == n: region i is the whole window of instance i, as in the motion pull.
+ * Record r is written at spec->data + r * stride, stride = 8 + 24 C + 4 C B bytes, C = 1 (STATS_Y) or 3 channels in the order of
+ * the source, B = spec->bins, little endian:
+ *     u32 count; u32 zero;
+ *     C x { u64 sum; u64 sumsq; u32 min; u32 max; }
+ *     C x B x u32 hist                                   hist[c][b]
+ * A record covers every luma position (x + u, y + v), 0 <= u < w, 0 <= v < h, that lies inside the window; count is their number,
+ * the same for every channel, at most 2^28; sum and sumsq are over the 8-bit values at those positions (below 2^44), min and max
+ * their extrema; hist[c][value >> (8 - log2 B)] counts them, so every hist[c] sums to count.  count == 0 (the box misses the
+ * window): sums 0, min 255, max 0, histogram all zero.  Everything is an integer and exact: no order of summation shows.
+ * The call writes the WHOLE record with plain stores: the caller does not clear it.  got[r] = 1, or 0 when that instance has no
+ * current picture: record r is then untouched.
+ * -1, before anything is enqueued: everything h264bsdmiOutputTensorRegions refuses in regions, instances and stream (got NULL
+ * with nRegions > 0; nRegions > 65535; an instance index >= n; a w or h of 0 or above the limit, an x or y beyond it; an instance
+ * in capture mode; repeated instances; a capturing stream); spec or data NULL, data not 8-byte aligned; source > 2; bins not one of
+ * 0, 16, 32, 64, 128, 256; crop > 1; regions == NULL with nRegions != n.  nRegions == 0 returns 0 and launches nothing.  -2: the
+ * engine failed. */
+#define H264BSDMI_STATS_Y      0   /* 1 channel : the decoded luma sample */
+#define H264BSDMI_STATS_YCBCR  1   /* 3 channels: Y, Cb, Cr as decoded; the chroma of luma sample (X, Y) of the coded frame is chroma sample (X >> 1, Y >> 1), as the reference's conversion pairs them */
+#define H264BSDMI_STATS_RGB    2   /* 3 channels: R, G, B of h264bsdNextOutputPictureRGBA's integer BT.601 conversion, 8 bit */
+typedef struct h264bsdmi_stats_spec {
+    void *data;      /* DEVICE pointer, caller-owned, 8-byte aligned: record r at data + r * stride */
+    u32   source;    /* H264BSDMI_STATS_* */
+    u32   bins;      /* 0 (no histogram), 16, 32, 64, 128 or 256: bin = value >> (8 - log2 bins) */
+    u32   crop;      /* as h264bsdmi_tensor_spec.crop */
+} h264bsdmi_stats_spec;
+int h264bsdmiOutputRegionStats(u32 n, storage_t *const *pStorage, u32 nRegions, const h264bsdmi_region *regions,
+                               const h264bsdmi_stats_spec *spec, void *stream,
+                               u32 *got, u32 *current, u32 *picId);
+
 /* ---- host parse pipeline at scale ----
  * h264bsdDecode() consumes one NAL unit of one stream per call; a caller that feeds hundreds of streams needs the
  * loop of posix/test_h264bsd.c:146-177 for each of them and its own threading.  These entry points move both into
