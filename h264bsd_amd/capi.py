@@ -527,6 +527,60 @@ def pull_batch(decoders, frame_bytes=None):
     return views, list(ids)
 
 
+def _regions_arg(who, n, regions):
+    """the regions of pull_regions, pull_motion and pull_stats, checked: (K, the Region array); None (one whole window per decoder): (n, None)"""
+    if regions is None:
+        K, regs = n, None
+    else:
+        regs = []
+        for r in regions:
+            r = tuple(r)
+            if len(r) != 5 or not all(isinstance(v, int) for v in r):
+                raise ValueError(f"{who}: a region is (decoder_index, x, y, w, h) in host integers, not {r}")
+            i, x, y, w, h = r
+            if not 0 <= i < n or not 1 <= w <= 16384 or not 1 <= h <= 16384 or abs(x) > 16384 or abs(y) > 16384:
+                raise ValueError(f"{who}: region {r} names no decoder of the call or is out of range (1 <= w, h <= 16384, |x|, |y| <= 16384)")
+            regs.append(Region(i, x, y, w, h))
+        K = len(regs)
+    if K > 65535:
+        raise ValueError(f"{who}: at most 65535 regions per call")
+    return K, None if regs is None else (Region * max(K, 1))(*regs)
+
+
+def _out_and_stream(who, out, shape, dtype, stream, aligned=False):
+    """`out` checked (aligned: to 8 bytes as well) or allocated, and the stream the C call gets; returns (out, stream)"""
+    import torch
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device="cuda")
+    elif not out.is_cuda or out.dtype != dtype or tuple(out.shape) != shape or not out.is_contiguous() or (aligned and out.data_ptr() % 8):
+        what = "contiguous, 8-byte aligned CUDA uint8" if aligned else f"contiguous CUDA {dtype}"
+        raise ValueError(f"{who}: out must be a {what} tensor of shape {shape}")
+    if stream is None:
+        stream = torch.cuda.current_stream(out.device)
+    if not stream.cuda_stream:
+        # torch's legacy default stream is handle 0, which the C call reads as "the library's own stream, wait": that stream is not
+        # ordered behind torch's work, so what is queued for `out` must be done before the call
+        stream.synchronize()
+    return out, stream
+
+
+def _current_pull(name, decoders, K, items, specs, stream, boxes=False, call=True):
+    """one pull of current pictures, C entry `name`: K items (a ctypes array, or None) of the decoders, the entry's spec arguments,
+    then the stream and the output arrays.  Returns [got[:K], boxes (where the entry has them), current, pic_ids]"""
+    n = len(decoders)
+    got, box = (ctypes.c_uint32 * max(K, 1))(), (ctypes.c_uint32 * (4 * max(K, 1)))()
+    cur, ids = (ctypes.c_uint32 * max(n, 1))(), (ctypes.c_uint32 * max(n, 1))()
+    if call:
+        rc = getattr(api_lib(), name)(n, (ctypes.c_void_p * max(n, 1))(*[d._st for d in decoders]), K, items, *specs, stream.cuda_stream,
+                                      got, *([box] if boxes else []), cur, ids)
+        if rc != 0:
+            raise RuntimeError(f"{name} failed ({rc})")
+    res = [list(got)[:K]]
+    if boxes:
+        res.append([tuple(box[4 * k: 4 * k + 4]) if got[k] else None for k in range(K)])
+    return res + [list(cur)[:n], list(ids)[:n]]
+
+
 def _tensor_call(who, n, decoders, size, layout, dtype, channels, mean, std, crop, out, stream, colour, colour_range, chroma, unspecified,
                  mode, antialias, fit, pad):
     """the argument checks, the output tensor of n slices, the stream handling and the three specs that pull_tensor and pull_regions
@@ -559,16 +613,7 @@ def _tensor_call(who, n, decoders, size, layout, dtype, channels, mean, std, cro
     else:
         H, W = (size, size) if isinstance(size, int) else (int(size[0]), int(size[1]))
     shape = (n, C, H, W) if layout == "NCHW" else (n, H, W, C)
-    if out is None:
-        out = torch.empty(shape, dtype=dtype, device="cuda")
-    elif not out.is_cuda or out.dtype != dtype or tuple(out.shape) != shape or not out.is_contiguous():
-        raise ValueError(f"{who}: out must be a contiguous CUDA {dtype} tensor of shape {shape}")
-    if stream is None:
-        stream = torch.cuda.current_stream(out.device)
-    if not stream.cuda_stream:
-        # torch's legacy default stream is handle 0, which the C call reads as "the library's own stream, wait": that stream is not
-        # ordered behind torch's work, so what is queued for `out` must be done before the call
-        stream.synchronize()
+    out, stream = _out_and_stream(who, out, shape, dtype, stream)
     spec = TensorSpec(out.data_ptr(), W, H, LAYOUTS[layout], dtypes[dtype], ch, 1 if crop else 0, 0 if size is None else 1,
                       (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std))
     cs = ColourSpec() if colour == "reference" else ColourSpec(MATRICES[colour], RANGES[colour_range], CHROMA[chroma], MATRICES[unspecified])
@@ -626,32 +671,14 @@ def pull_regions(decoders, regions, size, layout="NCHW", dtype=None, channels="R
     fills or None, current[i] / pic_ids[i] per decoder."""
     if size is None:
         raise ValueError("pull_regions: a size is required")
-    regs = []
     n = len(decoders)
-    for r in regions:
-        r = tuple(r)
-        if len(r) != 5 or not all(isinstance(v, int) for v in r):
-            raise ValueError(f"pull_regions: a region is (decoder_index, x, y, w, h) in host integers, not {r}")
-        i, x, y, w, h = r
-        if not 0 <= i < n or not 1 <= w <= 16384 or not 1 <= h <= 16384 or abs(x) > 16384 or abs(y) > 16384:
-            raise ValueError(f"pull_regions: region {r} names no decoder of the call or is out of range (1 <= w, h <= 16384, |x|, |y| <= 16384)")
-        regs.append(Region(i, x, y, w, h))
-    K = len(regs)
-    if K > 65535:
-        raise ValueError("pull_regions: at most 65535 regions per call")
+    K, regs = _regions_arg("pull_regions", n, list(regions))
     out, spec, cs, rs, stream = _tensor_call("pull_regions", K, decoders, size, layout, dtype, channels, mean, std, crop, out, stream, colour,
                                              colour_range, chroma, unspecified, mode, antialias, fit, pad)
     if rs is None:          # bilinear stretch: still a spec of its own here, the pad is what a box reads outside the picture
         rs = ResizeSpec(FILTERS[("bilinear", False)], FITS["stretch"], (ctypes.c_float * 3)(*[float(p) for p in pad]))
-    L = api_lib()
-    got, box = (ctypes.c_uint32 * max(K, 1))(), (ctypes.c_uint32 * (4 * max(K, 1)))()
-    cur, ids = (ctypes.c_uint32 * max(n, 1))(), (ctypes.c_uint32 * max(n, 1))()
-    rc = L.h264bsdmiOutputTensorRegions(n, (ctypes.c_void_p * max(n, 1))(*[d._st for d in decoders]), K, (Region * max(K, 1))(*regs),
-                                        ctypes.byref(spec), ctypes.byref(cs), None if rs is None else ctypes.byref(rs),
-                                        stream.cuda_stream, got, box, cur, ids)
-    if rc != 0:
-        raise RuntimeError(f"h264bsdmiOutputTensorRegions failed ({rc})")
-    return (out, list(got)[:K], [tuple(box[4 * k: 4 * k + 4]) if got[k] else None for k in range(K)], list(cur)[:n], list(ids)[:n])
+    return (out, *_current_pull("h264bsdmiOutputTensorRegions", decoders, K, regs, (ctypes.byref(spec), ctypes.byref(cs), ctypes.byref(rs)),
+                                stream, boxes=True))
 
 
 def pull_remap(decoders, maps, instances=None, layout="NCHW", dtype=None, channels="RGB", mean=(0, 0, 0), std=(1, 1, 1), crop=True,
@@ -711,15 +738,8 @@ def pull_remap(decoders, maps, instances=None, layout="NCHW", dtype=None, channe
     if pop:
         for d in decoders:
             d.next_output_info()
-    L = api_lib()
-    got = (ctypes.c_uint32 * R)()
-    cur, ids = (ctypes.c_uint32 * max(n, 1))(), (ctypes.c_uint32 * max(n, 1))()
-    rc = L.h264bsdmiOutputTensorRemap(n, (ctypes.c_void_p * max(n, 1))(*[d._st for d in decoders]), R,
-                                      (Remap * R)(*[Remap(i, t.data_ptr()) for i, t in zip(instances, maps)]), ctypes.byref(spec),
-                                      ctypes.byref(cs), ctypes.byref(rs), stream.cuda_stream, got, cur, ids)
-    if rc != 0:
-        raise RuntimeError(f"h264bsdmiOutputTensorRemap failed ({rc})")
-    return out, list(got), list(cur)[:n], list(ids)[:n]
+    items = (Remap * R)(*[Remap(i, t.data_ptr()) for i, t in zip(instances, maps)])
+    return (out, *_current_pull("h264bsdmiOutputTensorRemap", decoders, R, items, (ctypes.byref(spec), ctypes.byref(cs), ctypes.byref(rs)), stream))
 
 
 def affine_maps(theta, size, device="cuda"):
@@ -759,20 +779,7 @@ def pull_motion(decoders, regions=None, size=None, layout="NCHW", dtype=None, pl
         raise ValueError(f"pull_motion: unsupported fit / sampler / units {fit} {sampler} {units}")
     mask = sum(MOTION_PLANES[p][0] for p in set(planes))
     C = sum(c for bit, c in MOTION_PLANES.values() if mask & bit)
-    regs = None
-    if regions is not None:
-        regs = []
-        for r in regions:
-            r = tuple(r)
-            if len(r) != 5 or not all(isinstance(v, int) for v in r):
-                raise ValueError(f"pull_motion: a region is (decoder_index, x, y, w, h) in host integers, not {r}")
-            i, x, y, w, h = r
-            if not 0 <= i < n or not 1 <= w <= 16384 or not 1 <= h <= 16384 or abs(x) > 16384 or abs(y) > 16384:
-                raise ValueError(f"pull_motion: region {r} names no decoder of the call or is out of range (1 <= w, h <= 16384, |x|, |y| <= 16384)")
-            regs.append(Region(i, x, y, w, h))
-    K = n if regs is None else len(regs)
-    if K > 65535:
-        raise ValueError("pull_motion: at most 65535 regions per call")
+    K, regs = _regions_arg("pull_motion", n, regions)
     if size is None:
         if regs is not None:
             raise ValueError("pull_motion: regions need a size")
@@ -788,25 +795,10 @@ def pull_motion(decoders, regions=None, size=None, layout="NCHW", dtype=None, pl
     else:
         H, W = (size, size) if isinstance(size, int) else (int(size[0]), int(size[1]))
     shape = (K, C, H, W) if layout == "NCHW" else (K, H, W, C)
-    if out is None:
-        out = torch.empty(shape, dtype=dtype, device="cuda")
-    elif not out.is_cuda or out.dtype != dtype or tuple(out.shape) != shape or not out.is_contiguous():
-        raise ValueError(f"pull_motion: out must be a contiguous CUDA {dtype} tensor of shape {shape}")
-    if stream is None:
-        stream = torch.cuda.current_stream(out.device)
-    if not stream.cuda_stream:
-        stream.synchronize()        # torch's legacy default stream, as in _tensor_call: the C call uses the library's own stream and waits
+    out, stream = _out_and_stream("pull_motion", out, shape, dtype, stream)
     spec = MotionSpec(out.data_ptr(), W, H, LAYOUTS[layout], dtypes[dtype], mask, 1 if crop else 0, FITS[fit],
                       MOTION_SAMPLERS[sampler], MOTION_UNITS[units], 1 if per_picture else 0)
-    L = api_lib()
-    got, box = (ctypes.c_uint32 * max(K, 1))(), (ctypes.c_uint32 * (4 * max(K, 1)))()
-    cur, ids = (ctypes.c_uint32 * max(n, 1))(), (ctypes.c_uint32 * max(n, 1))()
-    rc = L.h264bsdmiOutputMotionRegions(n, (ctypes.c_void_p * max(n, 1))(*[d._st for d in decoders]), K,
-                                        None if regs is None else (Region * max(K, 1))(*regs), ctypes.byref(spec),
-                                        stream.cuda_stream, got, box, cur, ids)
-    if rc != 0:
-        raise RuntimeError(f"h264bsdmiOutputMotionRegions failed ({rc})")
-    return (out, list(got)[:K], [tuple(box[4 * k: 4 * k + 4]) if got[k] else None for k in range(K)], list(cur)[:n], list(ids)[:n])
+    return (out, *_current_pull("h264bsdmiOutputMotionRegions", decoders, K, regs, (ctypes.byref(spec),), stream, boxes=True))
 
 
 def stats_record_bytes(source, bins):
@@ -845,39 +837,12 @@ def pull_stats(decoders, regions=None, source="ycbcr", bins=256, crop=True, out=
     if source not in STATS_SOURCES or bins not in STATS_BINS:
         raise ValueError(f"pull_stats: unsupported source / bins {source} {bins}")
     src, C = STATS_SOURCES[source]
-    regs = None
-    if regions is not None:
-        regs = []
-        for r in regions:
-            r = tuple(r)
-            if len(r) != 5 or not all(isinstance(v, int) for v in r):
-                raise ValueError(f"pull_stats: a region is (decoder_index, x, y, w, h) in host integers, not {r}")
-            i, x, y, w, h = r
-            if not 0 <= i < n or not 1 <= w <= 16384 or not 1 <= h <= 16384 or abs(x) > 16384 or abs(y) > 16384:
-                raise ValueError(f"pull_stats: region {r} names no decoder of the call or is out of range (1 <= w, h <= 16384, |x|, |y| <= 16384)")
-            regs.append(Region(i, x, y, w, h))
-    K = n if regs is None else len(regs)
-    if K > 65535:
-        raise ValueError("pull_stats: at most 65535 regions per call")
+    K, regs = _regions_arg("pull_stats", n, regions)
     shape = (K, stats_record_bytes(source, bins))
-    if out is None:
-        out = torch.empty(shape, dtype=torch.uint8, device="cuda")
-    elif not out.is_cuda or out.dtype != torch.uint8 or tuple(out.shape) != shape or not out.is_contiguous() or out.data_ptr() % 8:
-        raise ValueError(f"pull_stats: out must be a contiguous, 8-byte aligned CUDA uint8 tensor of shape {shape}")
-    if stream is None:
-        stream = torch.cuda.current_stream(out.device)
-    if not stream.cuda_stream:
-        stream.synchronize()        # torch's legacy default stream, as in _tensor_call: the C call uses the library's own stream and waits
-    got = (ctypes.c_uint32 * max(K, 1))()
-    cur, ids = (ctypes.c_uint32 * max(n, 1))(), (ctypes.c_uint32 * max(n, 1))()
-    if K:
-        spec = StatsSpec(out.data_ptr(), src, bins, 1 if crop else 0)
-        rc = api_lib().h264bsdmiOutputRegionStats(n, (ctypes.c_void_p * max(n, 1))(*[d._st for d in decoders]), K,
-                                                  None if regs is None else (Region * K)(*regs), ctypes.byref(spec),
-                                                  stream.cuda_stream, got, cur, ids)
-        if rc != 0:
-            raise RuntimeError(f"h264bsdmiOutputRegionStats failed ({rc})")
-    return RegionStats(out, C, bins, list(got)[:K], list(cur)[:n], list(ids)[:n])
+    out, stream = _out_and_stream("pull_stats", out, shape, torch.uint8, stream, aligned=True)
+    spec = StatsSpec(out.data_ptr(), src, bins, 1 if crop else 0)
+    got, cur, ids = _current_pull("h264bsdmiOutputRegionStats", decoders, K, regs, (ctypes.byref(spec),), stream, call=K > 0)     # no records: no call
+    return RegionStats(out, C, bins, got, cur, ids)
 
 
 def job_header(blob):

@@ -177,6 +177,20 @@ int h264bsdmiNextOutputInfo(storage_t *s, u32 *picId, u32 *isIdrPic, u32 *numErr
     return o ? (int)o->slot : -1;
 }
 
+/* The source window of an SPS in luma samples: the coded frame, or (crop) its frame-cropping window where it has one */
+static void sps_window(const Sps *sps, int crop, u32 *x0, u32 *y0, u32 *w, u32 *h)
+{
+    *x0 = *y0 = 0;
+    *w = 16 * sps->width_mbs;
+    *h = 16 * sps->height_mbs;
+    if (crop && sps->cropping) {
+        *x0 = 2 * sps->crop_left;
+        *y0 = 2 * sps->crop_top;
+        *w -= 2 * (sps->crop_left + sps->crop_right);
+        *h -= 2 * (sps->crop_top + sps->crop_bottom);
+    }
+}
+
 int h264bsdmiNextOutputPictureDevice(storage_t *s, int format, int crop, h264bsdmi_device_picture *out)
 {
     ApiDec *a = dec_of(s);
@@ -187,13 +201,8 @@ int h264bsdmiNextOutputPictureDevice(storage_t *s, int format, int crop, h264bsd
     u32 id = 0, idr = 0, nerr = 0;
     const OutPic *o = pop_output(a, &id, &idr, &nerr);
     if (!o) return 0;
-    u32 x0 = 0, y0 = 0, w = 16 * sps->width_mbs, h = 16 * sps->height_mbs;
-    if (crop && sps->cropping) {
-        x0 = 2 * sps->crop_left;
-        y0 = 2 * sps->crop_top;
-        w -= 2 * (sps->crop_left + sps->crop_right);
-        h -= 2 * (sps->crop_top + sps->crop_bottom);
-    }
+    u32 x0, y0, w, h;
+    sps_window(sps, crop, &x0, &y0, &w, &h);
     void *stream = NULL;
     void *p = a->hd->sink.fetch_device(a->hd->sink.user, o->slot, format, x0, y0, w, h, &stream);
     if (!p) return -2;
@@ -261,16 +270,16 @@ static void letterbox(u32 W, u32 H, u32 w, u32 h, u32 *box)
 }
 
 /* What every tensor pull refuses in its three specs (1 = refused).  *colour == NULL becomes REFERENCE, the reference's conversion. */
+static const h264bsdmi_colour_spec REFERENCE_COLOUR = { H264BSDMI_MATRIX_REFERENCE, 0, 0, 0 };
 static int tensor_specs_refused(const h264bsdmi_tensor_spec *spec, const h264bsdmi_colour_spec **pcolour, const h264bsdmi_resize_spec *resize)
 {
-    static const h264bsdmi_colour_spec reference = { H264BSDMI_MATRIX_REFERENCE, 0, 0, 0 };
     if (!spec || !spec->data || !spec->width || !spec->height) return 1;
     if (resize) {
         if (resize->filter > H264BSDMI_FILTER_BICUBIC_AA || resize->fit > H264BSDMI_FIT_LETTERBOX || spec->resize != 1) return 1;
         for (int c = 0; c < 3; c++)
             if (!(resize->pad[c] >= 0.0f && resize->pad[c] <= 1.0f)) return 1;        /* NaN and the infinities too */
     }
-    if (!*pcolour) *pcolour = &reference;
+    if (!*pcolour) *pcolour = &REFERENCE_COLOUR;
     const h264bsdmi_colour_spec *colour = *pcolour;
     if (colour->matrix > H264BSDMI_MATRIX_SMPTE240 || colour->range > H264BSDMI_RANGE_FULL || colour->chroma > H264BSDMI_CHROMA_BILINEAR)
         return 1;
@@ -291,13 +300,8 @@ static int tensor_specs_refused(const h264bsdmi_tensor_spec *spec, const h264bsd
 static void tensor_pic(SinkTensorPic *p, const ApiDec *a, u32 slot, u32 index, const h264bsdmi_tensor_spec *spec, const h264bsdmi_colour_spec *colour)
 {
     const Sps *sps = a->hd->active_sps;
-    u32 x0 = 0, y0 = 0, w = 16 * sps->width_mbs, h = 16 * sps->height_mbs;
-    if (spec->crop && sps->cropping) {
-        x0 = 2 * sps->crop_left;
-        y0 = 2 * sps->crop_top;
-        w -= 2 * (sps->crop_left + sps->crop_right);
-        h -= 2 * (sps->crop_top + sps->crop_bottom);
-    }
+    u32 x0, y0, w, h;
+    sps_window(sps, spec->crop != 0, &x0, &y0, &w, &h);
     u32 matrix = colour->matrix, range = colour->range;
     if (matrix == H264BSDMI_MATRIX_AUTO) matrix = matrix_of(sps_matrix_coefficients(sps), colour->unspecified);
     if (matrix != H264BSDMI_MATRIX_REFERENCE && range == H264BSDMI_RANGE_AUTO) range = sps_full_range(sps) ? H264BSDMI_RANGE_FULL : H264BSDMI_RANGE_LIMITED;
@@ -349,246 +353,186 @@ int h264bsdmiNextOutputTensorBatchResize(u32 n, storage_t *const *dec, const h26
     return 0;
 }
 
-/* What the pulls of CURRENT pictures share (h264bsdmiOutputTensorRegions, h264bsdmiOutputTensorRemap, h264bsdmiOutputMotionRegions,
- * h264bsdmiOutputRegionStats).
- * current_instances_refused: 1 when an instance is no decoder of this library, is in capture mode (it has no pixels: `remap`
- * chooses the sink entry the call needs) or is repeated. */
-static int current_instances_refused(u32 n, storage_t *const *dec, int remap)
+/* ---- The pulls of CURRENT pictures (pop_output, drop_current): h264bsdmiOutputTensorRegions, h264bsdmiOutputTensorRemap,
+ * h264bsdmiOutputMotionRegions, h264bsdmiOutputRegionStats.  Each checks its own spec; everything else is one path:
+ *   regions_refused   got, the count and the range of every region — before the instances are looked at
+ *   pull_begin        dec and the instances (of this library, with the sink entry the call needs, distinct), then the lists
+ *   pull_pic          an instance's current picture in the picture list, appended at its first use
+ *   pull_regions      the regions (or one whole window per instance) of the pictures that exist, each with its rectangle
+ *   pull_finish       after the sink: got, box, current and picId — unless the sink failed (-2 writes nothing) — and the lists freed
+ * A refused call returns -1 and has called no sink, written nothing; no call pops anything. */
+enum { PULL_REGIONS, PULL_REMAP, PULL_MOTION, PULL_STATS };
+#define NO_PIC 0xFFFFFFFFu
+typedef struct CurrentPull {
+    u32 n, m, k;                /* instances; pictures and items gathered so far */
+    storage_t *const *dec;
+    SinkTensorPic *pics;        /* one per instance that has a current picture and at least one item, in the order of first use */
+    u32 *pic_of;                /* per instance: its index in pics, NO_PIC before its first use */
+    SinkRegion *regs;           /* the items for the sink: regions, or (PULL_REMAP) maps */
+    SinkRemap *maps;
+} CurrentPull;
+
+/* regions == NULL: no regions at all, or (whole: one whole window per instance) exactly n */
+static int regions_refused(u32 n, u32 nRegions, const h264bsdmi_region *regions, const u32 *got, int whole)
 {
-    for (u32 i = 0; i < n; i++) {
-        const ApiDec *a = dec_of(dec[i]);
-        if (!a || !(remap ? a->hd->sink.tensor_remap != NULL : a->hd->sink.tensor_regions != NULL)) return 1;
-        for (u32 k = 0; k < i; k++)
-            if (dec[k] == dec[i]) return 1;
+    const int LIMIT = 16384;
+    if (nRegions && !got) return 1;
+    if (nRegions > 65535u) return 1;
+    if (!regions) return nRegions != (whole ? n : 0u);
+    for (u32 r = 0; r < nRegions; r++) {
+        const h264bsdmi_region *g = &regions[r];
+        if (g->instance >= n || !g->w || !g->h || g->w > (u32)LIMIT || g->h > (u32)LIMIT) return 1;
+        if (g->x > LIMIT || g->x < -LIMIT || g->y > LIMIT || g->y < -LIMIT) return 1;
     }
     return 0;
 }
-/* the index in pics[0 .. *m) of instance inst's current picture (a: the instance, which has one), appended at its first use */
-static u32 current_pic(SinkTensorPic *pics, u32 *m, u32 *pic_of, const ApiDec *a, u32 inst, const h264bsdmi_tensor_spec *spec,
-                       const h264bsdmi_colour_spec *colour)
+/* 1 when the sink has what a pull of `kind` calls (capture mode has none of it: there are no pixels) */
+static int sink_pulls(const ApiDec *a, int kind)
 {
-    if (pic_of[inst] == 0xFFFFFFFFu) {
-        pic_of[inst] = *m;
-        tensor_pic(&pics[(*m)++], a, a->cur.slot, inst, spec, colour);
+    const JobSink *k = &a->hd->sink;
+    switch (kind) {
+    case PULL_REMAP:  return k->tensor_remap != NULL;
+    case PULL_MOTION: return k->motion_regions != NULL && a->motion;          /* ... and motion export is on */
+    case PULL_STATS:  return k->tensor_regions != NULL && k->region_stats != NULL;
     }
-    return pic_of[inst];
+    return k->tensor_regions != NULL;
 }
-/* current[i] / picId[i] (each may be NULL) of every instance */
-static void report_current(u32 n, storage_t *const *dec, u32 *current, u32 *picId)
+static void pull_free(CurrentPull *c) { free(c->pics); free(c->pic_of); free(c->regs); free(c->maps); }
+static int pull_begin(CurrentPull *c, u32 n, storage_t *const *dec, u32 n_items, int kind)
 {
+    if (n && !dec) return -1;
     for (u32 i = 0; i < n; i++) {
         const ApiDec *a = dec_of(dec[i]);
-        const int cur = a->has_cur && a->hd->active_sps;
-        if (current) current[i] = cur ? 1 : 0;
-        if (picId) picId[i] = cur ? a->cur.pic_id : 0;
+        if (!a || !sink_pulls(a, kind)) return -1;
+        for (u32 k = 0; k < i; k++)
+            if (dec[k] == dec[i]) return -1;
+    }
+    *c = (CurrentPull){ n, 0, 0, dec, (SinkTensorPic *)malloc((n ? n : 1) * sizeof(SinkTensorPic)), (u32 *)malloc((n ? n : 1) * sizeof(u32)),
+                        kind == PULL_REMAP ? NULL : (SinkRegion *)malloc((n_items ? n_items : 1) * sizeof(SinkRegion)),
+                        kind == PULL_REMAP ? (SinkRemap *)malloc((n_items ? n_items : 1) * sizeof(SinkRemap)) : NULL };
+    if (!c->pics || !c->pic_of || !(c->regs || c->maps)) { pull_free(c); return -1; }
+    for (u32 i = 0; i < n; i++) c->pic_of[i] = NO_PIC;
+    return 0;
+}
+/* the index in pics of instance inst's current picture, NO_PIC when it has none (got = 0 for what names it) */
+static u32 pull_pic(CurrentPull *c, u32 inst, const h264bsdmi_tensor_spec *spec, const h264bsdmi_colour_spec *colour)
+{
+    const ApiDec *a = dec_of(c->dec[inst]);
+    if (!a->has_cur || !a->hd->active_sps) return NO_PIC;
+    if (c->pic_of[inst] == NO_PIC) {
+        c->pic_of[inst] = c->m;
+        tensor_pic(&c->pics[c->m++], a, a->cur.slot, inst, spec, colour);
+    }
+    return c->pic_of[inst];
+}
+/* regions (NULL: instance r's whole window is region r) into the rectangle a W x H output gives each: all of it, or its letterbox */
+static void pull_regions(CurrentPull *c, u32 nRegions, const h264bsdmi_region *regions, const h264bsdmi_tensor_spec *spec,
+                         const h264bsdmi_colour_spec *colour, u32 W, u32 H, int letterboxed)
+{
+    for (u32 r = 0; r < nRegions; r++) {
+        const u32 pic = pull_pic(c, regions ? regions[r].instance : r, spec, colour);
+        if (pic == NO_PIC) continue;
+        SinkRegion *q = &c->regs[c->k++];
+        if (regions) *q = (SinkRegion){ pic, r, regions[r].x, regions[r].y, regions[r].w, regions[r].h, { 0, 0, W, H } };
+        else *q = (SinkRegion){ pic, r, 0, 0, c->pics[pic].w, c->pics[pic].h, { 0, 0, W, H } };
+        if (letterboxed) letterbox(W, H, q->w, q->h, q->box);
     }
 }
+/* failed: what the sink returned.  got[0 .. n_items), box (NULL, or 4 per item: regions only), current / picId (each may be NULL) */
+static int pull_finish(CurrentPull *c, int failed, u32 n_items, u32 *got, u32 *box, u32 *current, u32 *picId)
+{
+    if (!failed) {
+        for (u32 r = 0; r < n_items; r++) got[r] = 0;
+        if (box) memset(box, 0, 4 * sizeof(u32) * n_items);
+        for (u32 j = 0; j < c->k; j++) {
+            const u32 index = c->regs ? c->regs[j].index : c->maps[j].index;
+            got[index] = 1;
+            if (box) memcpy(box + 4 * index, c->regs[j].box, sizeof(c->regs[j].box));
+        }
+        for (u32 i = 0; i < c->n; i++) {
+            const ApiDec *a = dec_of(c->dec[i]);
+            const int cur = a->has_cur && a->hd->active_sps;
+            if (current) current[i] = cur ? 1 : 0;
+            if (picId) picId[i] = cur ? a->cur.pic_id : 0;
+        }
+    }
+    pull_free(c);
+    return failed ? -2 : 0;
+}
 
-/* Boxes of the instances' current pictures (pop_output, drop_current), each into its own slice.  Specs and regions are checked
- * before the instances are looked at; nothing is popped. */
+/* Boxes of the instances' current pictures, each into its own slice */
 int h264bsdmiOutputTensorRegions(u32 n, storage_t *const *dec, u32 nRegions, const h264bsdmi_region *regions,
                                  const h264bsdmi_tensor_spec *spec, const h264bsdmi_colour_spec *colour,
                                  const h264bsdmi_resize_spec *resize, void *stream,
                                  u32 *got, u32 *box, u32 *current, u32 *picId)
 {
     static const h264bsdmi_resize_spec stretch = { H264BSDMI_FILTER_BILINEAR, H264BSDMI_FIT_STRETCH, { 0.0f, 0.0f, 0.0f } };
-    const int LIMIT = 16384;
+    CurrentPull c;
     if (tensor_specs_refused(spec, &colour, resize) || spec->resize != 1) return -1;
-    if (nRegions && (!regions || !got)) return -1;
-    if (nRegions > 65535u) return -1;
-    for (u32 r = 0; r < nRegions; r++) {
-        const h264bsdmi_region *g = &regions[r];
-        if (g->instance >= n || !g->w || !g->h || g->w > (u32)LIMIT || g->h > (u32)LIMIT) return -1;
-        if (g->x > LIMIT || g->x < -LIMIT || g->y > LIMIT || g->y < -LIMIT) return -1;
-    }
-    if (n && !dec) return -1;
     if (!resize) resize = &stretch;
-    if (current_instances_refused(n, dec, 0)) return -1;
-    /* one SinkTensorPic per instance that has a current picture and at least one region */
-    SinkTensorPic *pics = (SinkTensorPic *)malloc((n ? n : 1) * sizeof(SinkTensorPic));
-    SinkRegion *regs = (SinkRegion *)malloc((nRegions ? nRegions : 1) * sizeof(SinkRegion));
-    u32 *pic_of = (u32 *)malloc((n ? n : 1) * sizeof(u32));
-    if (!pics || !regs || !pic_of) { free(pics); free(regs); free(pic_of); return -1; }
-    u32 m = 0, k = 0;
-    for (u32 i = 0; i < n; i++) pic_of[i] = 0xFFFFFFFFu;
-    for (u32 r = 0; r < nRegions; r++) {
-        const h264bsdmi_region *g = &regions[r];
-        const ApiDec *a = dec_of(dec[g->instance]);
-        if (!a->has_cur || !a->hd->active_sps) continue;                     /* got[r] = 0 */
-        SinkRegion *q = &regs[k++];
-        *q = (SinkRegion){ current_pic(pics, &m, pic_of, a, g->instance, spec, colour), r, g->x, g->y, g->w, g->h, { 0, 0, spec->width, spec->height } };
-        if (resize->fit == H264BSDMI_FIT_LETTERBOX) letterbox(spec->width, spec->height, g->w, g->h, q->box);
-    }
-    int rc = 0;
-    if (k && pics[0].sink->tensor_regions(m, pics, k, regs, spec, colour->chroma, resize, stream)) rc = -2;
-    if (!rc) {
-        for (u32 r = 0; r < nRegions; r++) got[r] = 0;
-        if (box) memset(box, 0, 4 * sizeof(u32) * nRegions);
-        for (u32 j = 0; j < k; j++) {
-            got[regs[j].index] = 1;
-            if (box) memcpy(box + 4 * regs[j].index, regs[j].box, sizeof(regs[j].box));
-        }
-        report_current(n, dec, current, picId);
-    }
-    free(pics);
-    free(regs);
-    free(pic_of);
-    return rc;
+    if (regions_refused(n, nRegions, regions, got, 0) || pull_begin(&c, n, dec, nRegions, PULL_REGIONS)) return -1;
+    pull_regions(&c, nRegions, regions, spec, colour, spec->width, spec->height, resize->fit == H264BSDMI_FIT_LETTERBOX);
+    const int failed = c.k && c.pics[0].sink->tensor_regions(c.m, c.pics, c.k, c.regs, spec, colour->chroma, resize, stream);
+    return pull_finish(&c, failed, nRegions, got, box, current, picId);
 }
 
-/* The instances' current pictures through coordinate maps, each map into its own slice: h264bsdmiOutputTensorRegions' checks of
- * spec, colour and instances in the same order, with the maps in the place of the regions; nothing is popped. */
+/* The instances' current pictures through coordinate maps, each map into its own slice */
 int h264bsdmiOutputTensorRemap(u32 n, storage_t *const *dec, u32 nMaps, const h264bsdmi_remap *maps,
                                const h264bsdmi_tensor_spec *spec, const h264bsdmi_colour_spec *colour,
                                const h264bsdmi_remap_spec *remap, void *stream,
                                u32 *got, u32 *current, u32 *picId)
 {
     static const h264bsdmi_remap_spec plain = { H264BSDMI_REMAP_BILINEAR, H264BSDMI_BORDER_CONSTANT, { 0.0f, 0.0f, 0.0f } };
+    CurrentPull c;
     if (tensor_specs_refused(spec, &colour, NULL) || spec->resize != 1) return -1;
     if (!remap) remap = &plain;
     if (remap->filter > H264BSDMI_REMAP_BILINEAR || remap->border > H264BSDMI_BORDER_REPLICATE) return -1;
-    for (int c = 0; c < 3; c++)
-        if (!(remap->pad[c] >= 0.0f && remap->pad[c] <= 1.0f)) return -1;      /* NaN and the infinities too */
+    for (int ch = 0; ch < 3; ch++)
+        if (!(remap->pad[ch] >= 0.0f && remap->pad[ch] <= 1.0f)) return -1;    /* NaN and the infinities too */
     if (nMaps && (!maps || !got)) return -1;
     if (nMaps > 65535u) return -1;
     for (u32 r = 0; r < nMaps; r++)
         if (maps[r].instance >= n || !maps[r].map || ((uintptr_t)maps[r].map & 7u)) return -1;
-    if (n && !dec) return -1;
-    if (current_instances_refused(n, dec, 1)) return -1;
-    /* one SinkTensorPic per instance that has a current picture and at least one map */
-    SinkTensorPic *pics = (SinkTensorPic *)malloc((n ? n : 1) * sizeof(SinkTensorPic));
-    SinkRemap *sm = (SinkRemap *)malloc((nMaps ? nMaps : 1) * sizeof(SinkRemap));
-    u32 *pic_of = (u32 *)malloc((n ? n : 1) * sizeof(u32));
-    if (!pics || !sm || !pic_of) { free(pics); free(sm); free(pic_of); return -1; }
-    u32 m = 0, k = 0;
-    for (u32 i = 0; i < n; i++) pic_of[i] = 0xFFFFFFFFu;
+    if (pull_begin(&c, n, dec, nMaps, PULL_REMAP)) return -1;
     for (u32 r = 0; r < nMaps; r++) {
-        const ApiDec *a = dec_of(dec[maps[r].instance]);
-        if (!a->has_cur || !a->hd->active_sps) continue;                     /* got[r] = 0 */
-        const u32 pic = current_pic(pics, &m, pic_of, a, maps[r].instance, spec, colour);
-        sm[k++] = (SinkRemap){ pic, r, maps[r].map };
+        const u32 pic = pull_pic(&c, maps[r].instance, spec, colour);
+        if (pic != NO_PIC) c.maps[c.k++] = (SinkRemap){ pic, r, maps[r].map };
     }
-    int rc = 0;
-    if (k && pics[0].sink->tensor_remap(m, pics, k, sm, spec, colour->chroma, remap, stream)) rc = -2;
-    if (!rc) {
-        for (u32 r = 0; r < nMaps; r++) got[r] = 0;
-        for (u32 j = 0; j < k; j++) got[sm[j].index] = 1;
-        report_current(n, dec, current, picId);
-    }
-    free(pics);
-    free(sm);
-    free(pic_of);
-    return rc;
+    const int failed = c.k && c.pics[0].sink->tensor_remap(c.m, c.pics, c.k, c.maps, spec, colour->chroma, remap, stream);
+    return pull_finish(&c, failed, nMaps, got, NULL, current, picId);
 }
 
-/* h264bsdmiOutputTensorRegions' regions over the motion side information of the current pictures: the same checks in the same
- * order, the same windows (tensor_pic) and rectangles (letterbox), nothing popped. */
+/* h264bsdmiOutputTensorRegions' regions over the motion side information of the current pictures: the same windows and rectangles */
 int h264bsdmiOutputMotionRegions(u32 n, storage_t *const *dec, u32 nRegions, const h264bsdmi_region *regions,
                                  const h264bsdmi_motion_spec *spec, void *stream,
                                  u32 *got, u32 *box, u32 *current, u32 *picId)
 {
-    static const h264bsdmi_colour_spec reference = { H264BSDMI_MATRIX_REFERENCE, 0, 0, 0 };
     const u32 planes = H264BSDMI_MOTION_PLANE_MV | H264BSDMI_MOTION_PLANE_VALID | H264BSDMI_MOTION_PLANE_AGE | H264BSDMI_MOTION_PLANE_QP;
-    const int LIMIT = 16384;
+    CurrentPull c;
     if (!spec || !spec->data || !spec->width || !spec->height || spec->layout > H264BSDMI_LAYOUT_NHWC) return -1;
     if (spec->dtype != H264BSDMI_DTYPE_F16 && spec->dtype != H264BSDMI_DTYPE_F32) return -1;
     if (!spec->planes || (spec->planes & ~planes) || spec->fit > H264BSDMI_FIT_LETTERBOX || spec->sampler > H264BSDMI_MOTION_AREA ||
         spec->units > H264BSDMI_MOTION_UNITS_OUTPUT || spec->per_picture > 1) return -1;
-    if (nRegions && !got) return -1;
-    if (nRegions > 65535u || (!regions && nRegions != n)) return -1;
-    for (u32 r = 0; regions && r < nRegions; r++) {
-        const h264bsdmi_region *g = &regions[r];
-        if (g->instance >= n || !g->w || !g->h || g->w > (u32)LIMIT || g->h > (u32)LIMIT) return -1;
-        if (g->x > LIMIT || g->x < -LIMIT || g->y > LIMIT || g->y < -LIMIT) return -1;
-    }
-    if (n && !dec) return -1;
-    for (u32 i = 0; i < n; i++) {
-        const ApiDec *a = dec_of(dec[i]);
-        if (!a || !a->hd->sink.motion_regions || !a->motion) return -1;      /* capture mode, or no motion export */
-        for (u32 k = 0; k < i; k++)
-            if (dec[k] == dec[i]) return -1;
-    }
+    if (regions_refused(n, nRegions, regions, got, 1) || pull_begin(&c, n, dec, nRegions, PULL_MOTION)) return -1;
     const h264bsdmi_tensor_spec window = { spec->data, spec->width, spec->height, spec->layout, spec->dtype, 0, spec->crop, 1, { 0, 0, 0 }, { 1, 1, 1 } };
-    SinkTensorPic *pics = (SinkTensorPic *)malloc((n ? n : 1) * sizeof(SinkTensorPic));
-    SinkRegion *regs = (SinkRegion *)malloc((nRegions ? nRegions : 1) * sizeof(SinkRegion));
-    u32 *pic_of = (u32 *)malloc((n ? n : 1) * sizeof(u32));
-    if (!pics || !regs || !pic_of) { free(pics); free(regs); free(pic_of); return -1; }
-    u32 m = 0, k = 0;
-    for (u32 i = 0; i < n; i++) pic_of[i] = 0xFFFFFFFFu;
-    for (u32 r = 0; r < nRegions; r++) {
-        const u32 inst = regions ? regions[r].instance : r;
-        const ApiDec *a = dec_of(dec[inst]);
-        if (!a->has_cur || !a->hd->active_sps) continue;                     /* got[r] = 0 */
-        const SinkTensorPic *p = &pics[current_pic(pics, &m, pic_of, a, inst, &window, &reference)];
-        SinkRegion *q = &regs[k++];
-        if (regions) *q = (SinkRegion){ pic_of[inst], r, regions[r].x, regions[r].y, regions[r].w, regions[r].h, { 0, 0, spec->width, spec->height } };
-        else *q = (SinkRegion){ pic_of[inst], r, 0, 0, p->w, p->h, { 0, 0, spec->width, spec->height } };      /* the whole window */
-        if (spec->fit == H264BSDMI_FIT_LETTERBOX) letterbox(spec->width, spec->height, q->w, q->h, q->box);
-    }
-    int rc = 0;
-    if (k && pics[0].sink->motion_regions(m, pics, k, regs, spec, stream)) rc = -2;
-    if (!rc) {
-        for (u32 r = 0; r < nRegions; r++) got[r] = 0;
-        if (box) memset(box, 0, 4 * sizeof(u32) * nRegions);
-        for (u32 j = 0; j < k; j++) {
-            got[regs[j].index] = 1;
-            if (box) memcpy(box + 4 * regs[j].index, regs[j].box, sizeof(regs[j].box));
-        }
-        report_current(n, dec, current, picId);
-    }
-    free(pics);
-    free(regs);
-    free(pic_of);
-    return rc;
+    pull_regions(&c, nRegions, regions, &window, &REFERENCE_COLOUR, spec->width, spec->height, spec->fit == H264BSDMI_FIT_LETTERBOX);
+    const int failed = c.k && c.pics[0].sink->motion_regions(c.m, c.pics, c.k, c.regs, spec, stream);
+    return pull_finish(&c, failed, nRegions, got, box, current, picId);
 }
 
-/* Integer statistics of h264bsdmiOutputTensorRegions' regions over the current pictures: the same checks of regions and instances
- * in the same order, the same windows (tensor_pic); regions == NULL as in the motion pull; nothing popped. */
+/* Integer statistics of h264bsdmiOutputTensorRegions' regions over the current pictures: the same windows, no rectangles */
 int h264bsdmiOutputRegionStats(u32 n, storage_t *const *dec, u32 nRegions, const h264bsdmi_region *regions,
                                const h264bsdmi_stats_spec *spec, void *stream,
                                u32 *got, u32 *current, u32 *picId)
 {
-    static const h264bsdmi_colour_spec reference = { H264BSDMI_MATRIX_REFERENCE, 0, 0, 0 };
-    const int LIMIT = 16384;
+    CurrentPull c;
     if (!spec || !spec->data || ((uintptr_t)spec->data & 7u) || spec->source > H264BSDMI_STATS_RGB || spec->crop > 1) return -1;
     if (spec->bins != 0 && spec->bins != 16 && spec->bins != 32 && spec->bins != 64 && spec->bins != 128 && spec->bins != 256) return -1;
-    if (nRegions && !got) return -1;
-    if (nRegions > 65535u || (!regions && nRegions != n)) return -1;
-    for (u32 r = 0; regions && r < nRegions; r++) {
-        const h264bsdmi_region *g = &regions[r];
-        if (g->instance >= n || !g->w || !g->h || g->w > (u32)LIMIT || g->h > (u32)LIMIT) return -1;
-        if (g->x > LIMIT || g->x < -LIMIT || g->y > LIMIT || g->y < -LIMIT) return -1;
-    }
-    if (n && !dec) return -1;
-    if (current_instances_refused(n, dec, 0)) return -1;
-    for (u32 i = 0; i < n; i++)
-        if (!dec_of(dec[i])->hd->sink.region_stats) return -1;               /* an engine without the statistics kernel */
+    if (regions_refused(n, nRegions, regions, got, 1) || pull_begin(&c, n, dec, nRegions, PULL_STATS)) return -1;
     const h264bsdmi_tensor_spec window = { spec->data, 1, 1, 0, 0, 0, spec->crop, 1, { 0, 0, 0 }, { 1, 1, 1 } };
-    SinkTensorPic *pics = (SinkTensorPic *)malloc((n ? n : 1) * sizeof(SinkTensorPic));
-    SinkRegion *regs = (SinkRegion *)malloc((nRegions ? nRegions : 1) * sizeof(SinkRegion));
-    u32 *pic_of = (u32 *)malloc((n ? n : 1) * sizeof(u32));
-    if (!pics || !regs || !pic_of) { free(pics); free(regs); free(pic_of); return -1; }
-    u32 m = 0, k = 0;
-    for (u32 i = 0; i < n; i++) pic_of[i] = 0xFFFFFFFFu;
-    for (u32 r = 0; r < nRegions; r++) {
-        const u32 inst = regions ? regions[r].instance : r;
-        const ApiDec *a = dec_of(dec[inst]);
-        if (!a->has_cur || !a->hd->active_sps) continue;                     /* got[r] = 0 */
-        const SinkTensorPic *p = &pics[current_pic(pics, &m, pic_of, a, inst, &window, &reference)];
-        if (regions) regs[k++] = (SinkRegion){ pic_of[inst], r, regions[r].x, regions[r].y, regions[r].w, regions[r].h, { 0, 0, 1, 1 } };
-        else regs[k++] = (SinkRegion){ pic_of[inst], r, 0, 0, p->w, p->h, { 0, 0, 1, 1 } };      /* the whole window */
-    }
-    int rc = 0;
-    if (k && pics[0].sink->region_stats(m, pics, k, regs, spec, stream)) rc = -2;
-    if (!rc) {
-        for (u32 r = 0; r < nRegions; r++) got[r] = 0;
-        for (u32 j = 0; j < k; j++) got[regs[j].index] = 1;
-        report_current(n, dec, current, picId);
-    }
-    free(pics);
-    free(regs);
-    free(pic_of);
-    return rc;
+    pull_regions(&c, nRegions, regions, &window, &REFERENCE_COLOUR, 1, 1, 0);
+    const int failed = c.k && c.pics[0].sink->region_stats(c.m, c.pics, c.k, c.regs, spec, stream);
+    return pull_finish(&c, failed, nRegions, got, NULL, current, picId);
 }
 
 static u32 *next_converted(storage_t *s, u32 *picId, u32 *isIdrPic, u32 *numErrMbs, int fmt)
@@ -621,10 +565,7 @@ void h264bsdCroppingParams(storage_t *s, u32 *croppingFlag, u32 *left, u32 *widt
     const Sps *p = active_sps(s);
     if (p && p->cropping) {
         *croppingFlag = 1;
-        *left = 2 * p->crop_left;
-        *width = 16 * p->width_mbs - 2 * (p->crop_left + p->crop_right);
-        *top = 2 * p->crop_top;
-        *height = 16 * p->height_mbs - 2 * (p->crop_top + p->crop_bottom);
+        sps_window(p, 1, left, top, width, height);
     } else {
         *croppingFlag = 0;
         *left = *width = *top = *height = 0;
