@@ -74,6 +74,25 @@ static uint32_t job_capacity(uint32_t n_mbs)
            + n_mbs * 64u /* sparse vectors, at worst all of them */ + job_dense_mv_bytes(n_mbs);
 }
 
+/* start a header for this geometry: all else zero, the records right behind it */
+static FjHeader *job_header_start(uint8_t *job, uint32_t width_mbs, uint32_t height_mbs)
+{
+    FjHeader *h = (FjHeader *)job;
+    memset(h, 0, sizeof(*h));
+    h->magic = FJ_MAGIC;
+    h->width_mbs = (uint16_t)width_mbs;
+    h->height_mbs = (uint16_t)height_mbs;
+    h->n_mbs = width_mbs * height_mbs;
+    h->rec_off = 128;
+    return h;
+}
+
+/* a job that runs in front of the picture's own job, into the same slot: stamped like it */
+static void job_stamp_like(FjHeader *h, const FjHeader *own)
+{
+    h->cur_slot = own->cur_slot; h->n_slots = own->n_slots; h->is_idr = own->is_idr; h->pic_seq = own->pic_seq;
+}
+
 int hd_job_begin(HostDec *d)
 {
     const uint32_t n = d->pic_size_mbs, cap = job_capacity(n);
@@ -89,13 +108,7 @@ int hd_job_begin(HostDec *d)
         if (!d->job) { d->job_cap = 0; return -1; }
         d->job_cap = cap;
     }
-    FjHeader *h = (FjHeader *)d->job;
-    memset(h, 0, sizeof(*h));
-    h->magic = FJ_MAGIC;
-    h->width_mbs = (uint16_t)d->width_mbs;
-    h->height_mbs = (uint16_t)d->height_mbs;
-    h->n_mbs = n;
-    h->rec_off = 128;
+    FjHeader *h = job_header_start(d->job, d->width_mbs, d->height_mbs);
     h->coef_off = h->rec_off + n * 32u;
     h->mv_off = (cap - n * 64u) & ~31u;             /* host only, behind everything the finished job can hold (job_capacity) */
     /* records and motion vectors are NOT pre-initialised: every decoded macroblock writes both, and
@@ -120,213 +133,247 @@ static int in_intra_schedule(int kind)
     return kind == FJ_MB_I4x4 || kind == FJ_MB_I16x16 || kind == FJ_MB_IPCM || kind == FJ_MB_CONCEAL_I;
 }
 
+static int makes_pixels(int kind)
+{
+    return kind == FJ_MB_INTER || kind == FJ_MB_I4x4 || kind == FJ_MB_I16x16 || kind == FJ_MB_IPCM;
+}
+static uint32_t rec_blocks(const FjMbRec *r)
+{
+    return r->kind == FJ_MB_IPCM ? 12u : (uint32_t)__builtin_popcount(r->coded & 0x03FFFFFFu);
+}
+
 /* per-thread scratch of fj_finalize (lists are built in one raster pass and copied behind the sections whose sizes
  * are only known afterwards); grows on demand, never shrinks */
 static __thread uint8_t *tl_scratch;
 static __thread size_t tl_scratch_cap;
 
-int fj_finalize(uint8_t *job, uint32_t cap, uint32_t coef_blocks) { return fj_finalize_ex(job, cap, coef_blocks, NULL); }
+/* what the steps of fj_finalize_ex share: the job's inputs, the lists in the scratch, their counters */
+typedef struct FjCtx {
+    FjHeader *h;                   /* the job */
+    FjMbRec *recs;
+    const int16_t (*mvs)[16][2];   /* the dense vectors */
+    uint32_t n, w, coef_blocks;
+    int recon_all;                 /* 0: a deblock-only job reconstructs only its FJ_PRED_PHASE2 macroblocks */
+    FjGen *gen_tmp;                /* scratch, 16-byte entries first for alignment */
+    FjCopy *copy_tmp;
+    uint32_t *hist, *ord;          /* intra MBs per level; the concealed macroblocks in concealment order */
+    uint16_t *dbk_tmp, *ilist, *mvx_list;      /* ilist: intra-schedule MBs, mvx_list: inter macroblocks with more than one vector; raster order */
+    uint8_t *cls;                  /* bit0: uniform (16 equal mvs, one reference, no coefficients); bit1: additionally whole-sample for
+                                    * luma and chroma -> pure copy */
+    uint32_t max_level, n_levels, n_intra, n_absent, n_conceal, n_copy, n_gen, n_dbk, n_mvx;
+    uint8_t any_dbk;
+} FjCtx;
+static const uint32_t FJ_NO_MB = 0xFFFFFFFFu;      /* fj_schedule: no neighbour on this side */
 
-int fj_finalize_ex(uint8_t *job, uint32_t cap, uint32_t coef_blocks, FjElide *elide)
+/* is this macroblock reconstructed by this job? */
+static inline int fj_recon(const FjCtx *c, const FjMbRec *r) { return c->recon_all || (r->pred & FJ_PRED_PHASE2); }
+
+/* invariant of the job format, checked where the kernels' lists are made: a macroblock that will be reconstructed
+ * has its coefficient blocks inside the section (a parser bug must end in a failed decode, not in a kernel
+ * reading past the job) */
+static inline int fj_coefs_inside(const FjCtx *c, uint32_t a, const FjMbRec *r)
 {
-    FjHeader *h = (FjHeader *)job;
-    const uint32_t n = h->n_mbs, w = h->width_mbs;
-    FjMbRec *recs = (FjMbRec *)(job + h->rec_off);
-    const int16_t (*mvs)[16][2] = (const int16_t (*)[16][2])(job + h->mv_off);
-    /* the dense vectors (n x 64 bytes, read from here on) must lie inside the buffer, and whole: in front of the coefficients
-     * (hand-built jobs) or behind them; that they also clear the finished job is checked once its size is known (ADVICE r4) */
-    if ((size_t)h->mv_off + (size_t)n * 64u > cap) return -1;
-    if (h->mv_off < h->coef_off && (size_t)h->mv_off + (size_t)n * 64u > h->coef_off) return -1;
-    {
-        const size_t need_bytes = (size_t)n * (1 + 8 + 16 + 2 + 2 + 2) + ((size_t)n + 2) * 4 + 64;
-        if (tl_scratch_cap < need_bytes) {
-            free(tl_scratch);
-            tl_scratch = (uint8_t *)malloc(need_bytes);
-            tl_scratch_cap = tl_scratch ? need_bytes : 0;
-            if (!tl_scratch) return -1;
-        }
-    }
-    /* scratch layout (16-byte entries first for alignment) */
-    FjGen *gen_tmp = (FjGen *)tl_scratch;
-    FjCopy *copy_tmp = (FjCopy *)(gen_tmp + n);
-    uint32_t *hist = (uint32_t *)(copy_tmp + n);                 /* intra MBs per level */
-    uint16_t *dbk_tmp = (uint16_t *)(hist + n + 2);
-    uint16_t *ilist = dbk_tmp + n;                               /* intra-schedule MBs in raster order */
-    uint16_t *mvx_list = ilist + n;                              /* inter macroblocks with more than one vector, raster order */
-    uint8_t *cls = (uint8_t *)(mvx_list + n);
-    uint32_t max_level = 0, n_intra = 0, n_absent = 0, n_conceal = 0, n_copy = 0, n_gen = 0, n_dbk = 0, n_mvx = 0;
-    uint8_t any_dbk = 0;
-    memset(hist, 0, ((size_t)n + 2) * 4);
+    if (!makes_pixels(r->kind)) return 1;
+    if (r->kind != FJ_MB_IPCM && !(r->coded & 0x03FFFFFFu)) return 1;      /* (most macroblocks have none: no population count for them) */
+    const uint32_t nb = rec_blocks(r), coef_blocks = c->coef_blocks;
+    if (r->coef_idx <= coef_blocks && nb <= coef_blocks - r->coef_idx) return 1;
+    if (hd_trace) fprintf(stderr, "TRACE fj_finalize: mb %u kind %u pred %#x needs blocks %u..%u of %u (ghost %u dbk_only %u)\n", a, r->kind, r->pred, r->coef_idx, r->coef_idx + nb, coef_blocks, c->h->ghost, c->h->dbk_only);
+    return 0;
+}
 
-    /* ---- one raster pass: intra dependency levels + FJ_NEED masks, classification of the inter macroblocks, copy
-     * runs, general-inter entries, deblocking index ---- */
-    const int recon_all = !h->dbk_only;       /* a deblock-only job reconstructs only its FJ_PRED_PHASE2 macroblocks */
-#define RECON(r_) (recon_all || ((r_)->pred & FJ_PRED_PHASE2))
-    for (uint32_t a = 0; a < n; a++) {
-        FjMbRec *r = &recs[a];
-        const int recon = RECON(r);
-        any_dbk |= r->dbk;
-        /* seven of ten macroblocks of a P picture: one vector (the parser's hint), one reference, no coefficients — nothing of
-         * the general path below applies to them but the classification and, off the whole-sample grid, a list entry */
-        if (r->kind == FJ_MB_INTER && (r->pred & FJ_PRED_UNIFORM_MV) && r->coded == 0) {
-            const int whole = ((r->mv[0] | r->mv[1]) & 7) == 0;
-            cls[a] = whole ? 3 : 1;
-            r->mvx = 0;
-            if (recon && !whole) {
-                FjGen *gi = &gen_tmp[n_gen++];
-                gi->mb = (uint16_t)a; gi->uniform = 1; gi->slot = r->ref_slot[0];
-                gi->mvx = r->mv[0]; gi->mvy = r->mv[1]; gi->coef_idx = FJ_GEN_COEF(r->coef_idx, r->qp_y, r->qp_c); gi->coded = 0;
-            }
-            goto deblock_index;
-        }
-        cls[a] = 0;
-        /* invariant of the job format, checked where the kernels' lists are made: a macroblock that will be reconstructed
-         * has its coefficient blocks inside the section (a parser bug must end in a failed decode, not in a kernel
-         * reading past the job) */
-        if (recon && (r->kind == FJ_MB_INTER || r->kind == FJ_MB_I4x4 || r->kind == FJ_MB_I16x16 || r->kind == FJ_MB_IPCM)) {
-            const uint32_t cm = r->coded & 0x03FFFFFFu;         /* (most macroblocks have none: no population count for them) */
-            const uint32_t nb = r->kind == FJ_MB_IPCM ? 12u : cm ? (uint32_t)__builtin_popcount(cm) : 0u;
-            if (nb && (r->coef_idx > coef_blocks || nb > coef_blocks - r->coef_idx)) {
-                if (hd_trace) fprintf(stderr, "TRACE fj_finalize: mb %u kind %u pred %#x needs blocks %u..%u of %u (ghost %u dbk_only %u)\n", a, r->kind, r->pred, r->coef_idx, r->coef_idx + nb, coef_blocks, h->ghost, h->dbk_only);
-                return -1;
-            }
-        }
-        if (r->kind == FJ_MB_ABSENT || r->kind == FJ_MB_STALE) n_absent++;
-        else if (r->kind == FJ_MB_CONCEAL_I) n_conceal += (uint32_t)recon;
-        else if (in_intra_schedule(r->kind)) {
-            if (!recon) goto deblock_index;
-            const uint32_t x = a % w, y = a / w;
-            int lvl = -1;
-            /* which neighbouring macroblocks does the prediction of this one actually read? (8.3.1.2, 8.3.3, 8.3.4) */
-            unsigned need = 0;
-            if (r->kind == FJ_MB_I16x16) {
-                const int m = r->pred & 3;
-                need |= m == 0 ? FJ_AVAIL_B : m == 1 ? FJ_AVAIL_A : m == 2 ? (FJ_AVAIL_A | FJ_AVAIL_B) : (FJ_AVAIL_A | FJ_AVAIL_B | FJ_AVAIL_D);
-            } else if (r->kind == FJ_MB_I4x4) {
-                for (int z = 0; z < 16; z++) {
-                    const int bx = ((z >> 2) & 1) * 2 + (z & 1), by = (z >> 3) * 2 + ((z >> 1) & 1);
-                    if (bx && by) continue;
-                    const int m = (r->i4mode[z >> 1] >> ((z & 1) * 4)) & 15;
-                    const int uses_left = m == 1 || m == 2 || m == 4 || m == 5 || m == 6 || m == 8;
-                    const int uses_top = m == 0 || m == 2 || m == 3 || m == 4 || m == 5 || m == 6 || m == 7;
-                    const int uses_corner = m == 4 || m == 5 || m == 6;
-                    if (bx == 0 && (uses_left || uses_corner)) need |= FJ_AVAIL_A;
-                    if (by == 0 && (uses_top || uses_corner)) need |= FJ_AVAIL_B;
-                    if (bx == 0 && by == 0 && uses_corner) need |= FJ_AVAIL_D;
-                    if (bx == 3 && by == 0 && (m == 3 || m == 7)) need |= FJ_AVAIL_C;
-                }
-            }
-            if (r->kind != FJ_MB_IPCM) {
-                const int m = (r->pred >> 2) & 3;
-                need |= m == 0 ? (FJ_AVAIL_A | FJ_AVAIL_B) : m == 1 ? FJ_AVAIL_A : m == 2 ? FJ_AVAIL_B : (FJ_AVAIL_A | FJ_AVAIL_B | FJ_AVAIL_D);
-            }
-            need &= r->avail;             /* an unavailable neighbour is never read (its samples are replaced by 128) */
-#define DEP(cond, idx) do { if (cond) { const FjMbRec *q = &recs[idx]; \
-            if (in_intra_schedule(q->kind) && RECON(q) && (int)q->intra_level > lvl) lvl = q->intra_level; } } while (0)
-            DEP(x > 0 && (need & FJ_AVAIL_A), a - 1);
-            DEP(y > 0 && (need & FJ_AVAIL_B), a - w);
-            DEP(y > 0 && x + 1 < w && (need & FJ_AVAIL_C), a - w + 1);
-            DEP(y > 0 && x > 0 && (need & FJ_AVAIL_D), a - w - 1);
-#undef DEP
-            r->intra_level = (uint16_t)(lvl + 1);
-            if ((uint32_t)(lvl + 1) > max_level) max_level = (uint32_t)(lvl + 1);
-            hist[lvl + 1]++;
-            ilist[n_intra++] = (uint16_t)a;
-            /* the same information for the device's dataflow scheduler: which of the 8 surrounding macroblocks this
-             * one waits for (FJ_NEED_*; the device ignores neighbours that are not in the intra schedule).  Intra
-             * macroblocks have no reference slots, so the mask travels in ref_slot[0]. */
-            r->ref_slot[0] = (uint8_t)(((need & FJ_AVAIL_A) ? FJ_NEED_L : 0) | ((need & FJ_AVAIL_D) ? FJ_NEED_UL : 0) |
-                                       ((need & FJ_AVAIL_B) ? FJ_NEED_U : 0) | ((need & FJ_AVAIL_C) ? FJ_NEED_UR : 0));
-            r->ref_slot[1] = r->ref_slot[2] = r->ref_slot[3] = 0;
-        } else if (r->kind == FJ_MB_CONCEAL_P) {
-            cls[a] = 6;                                            /* copy list, never "uniform" (bit0) */
-        } else if (r->kind == FJ_MB_INTER) {
-            /* cls bit0: uniform (16 equal mvs, one reference, no coefficients); bit1: additionally whole-sample for
-             * luma and chroma -> pure copy */
-            /* the parser's hint: one vector, already in the record, the macroblock's dense entry was never written (framejob.h) */
-            const int hinted = (r->pred & FJ_PRED_UNIFORM_MV) != 0;
-            const int16_t *m0 = hinted ? r->mv : mvs[a][0];
-            uint32_t refs;
-            memcpy(&refs, r->ref_slot, 4);
-            const int one_ref = refs == (refs & 255u) * 0x01010101u;
-            int same_mv = one_ref || hinted;
-            if (same_mv && !hinted) {                           /* 16 equal vectors: eight 64-bit words equal to the doubled first */
-                uint64_t w[8], acc = 0;
-                uint32_t first;
-                memcpy(w, mvs[a], 64);
-                memcpy(&first, m0, 4);
-                const uint64_t two = (uint64_t)first << 32 | first;
-                for (int k = 0; k < 8; k++) acc |= w[k] ^ two;
-                same_mv = acc == 0;
-            }
-            /* where the finished job keeps the vectors: one in the record, or sixteen in the sparse section (framejob.h) */
-            if (!hinted) { r->mv[0] = m0[0]; r->mv[1] = m0[1]; }
-            if (same_mv) { r->pred |= FJ_PRED_UNIFORM_MV; r->mvx = 0; }
-            else { r->pred &= (uint8_t)~FJ_PRED_UNIFORM_MV; r->mvx = n_mvx; mvx_list[n_mvx++] = (uint16_t)a; }
-            const int uni = same_mv && r->coded == 0;
-            cls[a] = (uint8_t)(uni ? (((m0[0] | m0[1]) & 7) == 0 ? 3 : 1) : 0);
-            if (recon && !(cls[a] & 2)) {
-                FjGen *gi = &gen_tmp[n_gen++];
-                int quad = 0;
-                if (!same_mv) {                               /* one motion vector per 8x8 quadrant (16x8, 8x16, 8x8 partitions)? */
-                    quad = 1;
-                    for (int q = 0; q < 4 && quad; q++) {
-                        const int b0 = (q >> 1) * 8 + (q & 1) * 2;
-                        const int16_t *m = mvs[a][b0];
-                        quad = mvs[a][b0 + 1][0] == m[0] && mvs[a][b0 + 1][1] == m[1] && mvs[a][b0 + 4][0] == m[0] &&
-                               mvs[a][b0 + 4][1] == m[1] && mvs[a][b0 + 5][0] == m[0] && mvs[a][b0 + 5][1] == m[1];
-                    }
-                }
-                gi->mb = (uint16_t)a; gi->uniform = (uint8_t)(same_mv ? 1 : quad ? 2 : 0); gi->slot = r->ref_slot[0];
-                gi->mvx = m0[0]; gi->mvy = m0[1]; gi->coef_idx = FJ_GEN_COEF(r->coef_idx, r->qp_y, r->qp_c); gi->coded = r->coded;
-                if (!same_mv) memcpy(&gi->mvx, &r->mvx, 4);      /* partitioned: the two fields hold the index of its sixteen vectors */
-            }
-        }
-deblock_index:
-        {
-            /* deblocking: a uniform MB whose filtered left/top neighbours are uniform too, with the same reference and
-             * mv components closer than 4 quarter samples, has all-zero strengths (8.7.2.1) — never visited again */
-            int trivial = r->kind == FJ_MB_ABSENT || r->dbk == 0;
-            if (!trivial && (cls[a] & 1)) {
-                trivial = 1;
-                const uint32_t nb[2] = { a - 1, a - w };
-                const uint8_t want[2] = { (uint8_t)(r->dbk & FJ_DBK_LEFT), (uint8_t)(r->dbk & FJ_DBK_TOP) };
-                for (int k = 0; k < 2 && trivial; k++) {
-                    if (!want[k]) continue;
-                    const uint32_t p = nb[k];
-                    if (cls[p] & 1) {
-                        const int dx = r->mv[0] - recs[p].mv[0], dy = r->mv[1] - recs[p].mv[1];
-                        trivial = recs[p].ref_slot[0] == r->ref_slot[0] && dx > -4 && dx < 4 && dy > -4 && dy < 4;
-                    } else if (recs[p].kind == FJ_MB_INTER) {
-                        /* a coded or partitioned inter neighbour: the four 4x4 blocks of it that touch the edge decide (8.7.2.1: a
-                         * coded block, another reference or a vector 4 quarter samples away give a strength).  A fifth of what
-                         * k_dbk used to visit turned out strength-free: most of it is this case */
-                        for (int i = 0; i < 4 && trivial; i++) {
-                            const int bx = k ? i : 3, by = k ? 3 : i;
-                            const int z = ((by >> 1) << 3) | ((bx >> 1) << 2) | ((by & 1) << 1) | (bx & 1);
-                            const int16_t *pm = (recs[p].pred & FJ_PRED_UNIFORM_MV) ? recs[p].mv : mvs[p][4 * by + bx];
-                            const int dx = r->mv[0] - pm[0], dy = r->mv[1] - pm[1];
-                            trivial = !((recs[p].coded >> z) & 1u) && recs[p].ref_slot[(by >> 1) * 2 + (bx >> 1)] == r->ref_slot[0] &&
-                                      dx > -4 && dx < 4 && dy > -4 && dy < 4;
-                        }
-                    } else trivial = 0;
-                }
-            }
-            r->dbk_trivial = (uint8_t)trivial;
-            if (!trivial) dbk_tmp[n_dbk++] = (uint16_t)a;
+/* which neighbouring macroblocks does the prediction of this one actually read? (8.3.1.2, 8.3.3, 8.3.4) */
+static inline unsigned fj_intra_reads(const FjMbRec *r)
+{
+    unsigned need = 0;
+    if (r->kind == FJ_MB_I16x16) {
+        const int m = r->pred & 3;
+        need |= m == 0 ? FJ_AVAIL_B : m == 1 ? FJ_AVAIL_A : m == 2 ? (FJ_AVAIL_A | FJ_AVAIL_B) : (FJ_AVAIL_A | FJ_AVAIL_B | FJ_AVAIL_D);
+    } else if (r->kind == FJ_MB_I4x4) {
+        for (int z = 0; z < 16; z++) {
+            const int bx = ((z >> 2) & 1) * 2 + (z & 1), by = (z >> 3) * 2 + ((z >> 1) & 1);
+            if (bx && by) continue;
+            const int m = (r->i4mode[z >> 1] >> ((z & 1) * 4)) & 15;
+            const int uses_left = m == 1 || m == 2 || m == 4 || m == 5 || m == 6 || m == 8;
+            const int uses_top = m == 0 || m == 2 || m == 3 || m == 4 || m == 5 || m == 6 || m == 7;
+            const int uses_corner = m == 4 || m == 5 || m == 6;
+            if (bx == 0 && (uses_left || uses_corner)) need |= FJ_AVAIL_A;
+            if (by == 0 && (uses_top || uses_corner)) need |= FJ_AVAIL_B;
+            if (bx == 0 && by == 0 && uses_corner) need |= FJ_AVAIL_D;
+            if (bx == 3 && by == 0 && (m == 3 || m == 7)) need |= FJ_AVAIL_C;
         }
     }
-    /* ---- copy list: runs of up to FJ_COPY_RUN copy MBs with consecutive addresses, equal reference and mv; a run whose
-     * displacement is zero may continue into the next row (tiles are contiguous in address order).  Built after the raster
-     * pass because copy elision looks at the deblocking verdict of the macroblocks to the right and below: a zero-motion
-     * copy is CLEAN when neither its own filter nor that of the two macroblocks that could reach into its tile runs; a
-     * clean copy makes the destination tile equal to the source tile, so its tile inherits the source's number, and when
-     * the destination carried that number already the copy would write what is there — it is left out. ---- */
-    if (elide && !recon_all) elide = NULL;                 /* (callers do not ask for it either) */
+    if (r->kind != FJ_MB_IPCM) {
+        const int m = (r->pred >> 2) & 3;
+        need |= m == 0 ? (FJ_AVAIL_A | FJ_AVAIL_B) : m == 1 ? FJ_AVAIL_A : m == 2 ? FJ_AVAIL_B : (FJ_AVAIL_A | FJ_AVAIL_B | FJ_AVAIL_D);
+    }
+    return need & r->avail;           /* an unavailable neighbour is never read (its samples are replaced by 128) */
+}
+
+/* Schedule this macroblock behind these neighbours (FJ_NO_MB: none on that side): one level above the deepest of them that is in
+ * the intra schedule and reconstructed.  need: the same information for the device's dataflow scheduler, which of the 8 surrounding
+ * macroblocks this one waits for (FJ_NEED_*; the device ignores neighbours that are not in the intra schedule).  Macroblocks of the
+ * intra schedule have no reference slots, so the mask travels in ref_slot[0]. */
+static inline void fj_schedule(FjCtx *c, FjMbRec *r, const uint32_t nb[4], unsigned need)
+{
+    int lvl = -1;
+    for (int k = 0; k < 4; k++) {
+        if (nb[k] == FJ_NO_MB) continue;
+        const FjMbRec *q = &c->recs[nb[k]];
+        if (in_intra_schedule(q->kind) && fj_recon(c, q) && (int)q->intra_level > lvl) lvl = q->intra_level;
+    }
+    r->intra_level = (uint16_t)(lvl + 1);
+    if ((uint32_t)(lvl + 1) > c->max_level) c->max_level = (uint32_t)(lvl + 1);
+    c->hist[lvl + 1]++;
+    c->n_intra++;
+    r->ref_slot[0] = (uint8_t)need;
+    r->ref_slot[1] = r->ref_slot[2] = r->ref_slot[3] = 0;
+}
+
+/* Synthesised macroblocks read the neighbours that were decoded or concealed BEFORE them in the reference's
+ * concealment order (coef_idx), on any of the four sides: walk them in that order. */
+static void fj_schedule_concealed(FjCtx *c)
+{
+    const uint32_t n = c->n, w = c->w;
+    FjMbRec *recs = c->recs;
+    uint32_t *ord = c->ord, k = 0;
+    for (uint32_t a = 0; a < n; a++) if (recs[a].kind == FJ_MB_CONCEAL_I && fj_recon(c, &recs[a])) ord[k++] = a;
+    for (uint32_t i = 1; i < k; i++) {              /* insertion sort by sequence number */
+        const uint32_t v = ord[i];
+        uint32_t j = i;
+        while (j > 0 && recs[ord[j - 1]].coef_idx > recs[v].coef_idx) { ord[j] = ord[j - 1]; j--; }
+        ord[j] = v;
+    }
+    for (uint32_t i = 0; i < k; i++) {
+        const uint32_t a = ord[i], x = a % w, av = recs[a].avail;
+        const uint32_t nb[4] = { (av & FJ_CONC_LEFT) && x > 0 ? a - 1 : FJ_NO_MB, (av & FJ_CONC_RIGHT) && x + 1 < w ? a + 1 : FJ_NO_MB,
+                                 (av & FJ_CONC_ABOVE) && a >= w ? a - w : FJ_NO_MB, (av & FJ_CONC_BELOW) && a + w < n ? a + w : FJ_NO_MB };
+        fj_schedule(c, &recs[a], nb, ((av & FJ_CONC_LEFT) ? FJ_NEED_L : 0) | ((av & FJ_CONC_ABOVE) ? FJ_NEED_U : 0) |
+                                     ((av & FJ_CONC_RIGHT) ? FJ_NEED_R : 0) | ((av & FJ_CONC_BELOW) ? FJ_NEED_D : 0));
+    }
+}
+
+/* the entry of an inter macroblock in the general-inter list (uniform: FjGen.uniform); the record holds the vector of block 0 */
+static inline void fj_gen_entry(FjCtx *c, uint32_t a, const FjMbRec *r, int uniform)
+{
+    FjGen *gi = &c->gen_tmp[c->n_gen++];
+    gi->mb = (uint16_t)a; gi->uniform = (uint8_t)uniform; gi->slot = r->ref_slot[0];
+    gi->mvx = r->mv[0]; gi->mvy = r->mv[1]; gi->coef_idx = FJ_GEN_COEF(r->coef_idx, r->qp_y, r->qp_c); gi->coded = r->coded;
+    if (uniform != 1) memcpy(&gi->mvx, &r->mvx, 4);      /* partitioned: the two fields hold the index of its sixteen vectors */
+}
+
+/* 16 equal vectors: eight 64-bit words equal to the doubled first */
+static inline int mvs_all_equal(const int16_t mv[16][2])
+{
+    uint64_t w[8], acc = 0;
+    uint32_t first;
+    memcpy(w, mv, 64);
+    memcpy(&first, mv, 4);
+    const uint64_t two = (uint64_t)first << 32 | first;
+    for (int k = 0; k < 8; k++) acc |= w[k] ^ two;
+    return acc == 0;
+}
+
+/* one motion vector per 8x8 quadrant (16x8, 8x16, 8x8 partitions)? */
+static inline int mvs_equal_in_quadrants(const int16_t mv[16][2])
+{
+    int quad = 1;
+    for (int q = 0; q < 4 && quad; q++) {
+        const int b0 = (q >> 1) * 8 + (q & 1) * 2;
+        const int16_t *m = mv[b0];
+        quad = mv[b0 + 1][0] == m[0] && mv[b0 + 1][1] == m[1] && mv[b0 + 4][0] == m[0] &&
+               mv[b0 + 4][1] == m[1] && mv[b0 + 5][0] == m[0] && mv[b0 + 5][1] == m[1];
+    }
+    return quad;
+}
+
+/* Everything but the one-vector macroblocks that fj_finalize_ex deals with itself: the intra macroblocks get their dependency
+ * level and FJ_NEED mask, the inter ones their class, where their vectors are kept and a list entry.  -1: the job is refused */
+static inline int fj_classify(FjCtx *c, uint32_t a, FjMbRec *r, int recon)
+{
+    c->cls[a] = 0;
+    if (recon && !fj_coefs_inside(c, a, r)) return -1;
+    if (r->kind == FJ_MB_ABSENT || r->kind == FJ_MB_STALE) c->n_absent++;
+    else if (r->kind == FJ_MB_CONCEAL_I) c->n_conceal += (uint32_t)recon;       /* (scheduled after the raster pass: fj_schedule_concealed) */
+    else if (in_intra_schedule(r->kind) && recon) {
+        /* behind the neighbours A, B, C, D that it reads: they precede it in raster order */
+        const uint32_t w = c->w, x = a % w, y = a / w, need = fj_intra_reads(r);
+        const uint32_t nb[4] = { x > 0 && (need & FJ_AVAIL_A) ? a - 1 : FJ_NO_MB, y > 0 && (need & FJ_AVAIL_B) ? a - w : FJ_NO_MB,
+                                 y > 0 && x + 1 < w && (need & FJ_AVAIL_C) ? a - w + 1 : FJ_NO_MB,
+                                 y > 0 && x > 0 && (need & FJ_AVAIL_D) ? a - w - 1 : FJ_NO_MB };
+        c->ilist[c->n_intra] = (uint16_t)a;
+        fj_schedule(c, r, nb, ((need & FJ_AVAIL_A) ? FJ_NEED_L : 0) | ((need & FJ_AVAIL_D) ? FJ_NEED_UL : 0) |
+                              ((need & FJ_AVAIL_B) ? FJ_NEED_U : 0) | ((need & FJ_AVAIL_C) ? FJ_NEED_UR : 0));
+    } else if (r->kind == FJ_MB_CONCEAL_P) {
+        c->cls[a] = 6;                                         /* copy list, never "uniform" (bit0) */
+    } else if (r->kind == FJ_MB_INTER) {
+        /* the parser's hint: one vector, already in the record, the macroblock's dense entry was never written (framejob.h) */
+        const int hinted = (r->pred & FJ_PRED_UNIFORM_MV) != 0;
+        uint32_t refs;
+        memcpy(&refs, r->ref_slot, 4);
+        const int one_ref = refs == (refs & 255u) * 0x01010101u;
+        const int same_mv = hinted || (one_ref && mvs_all_equal(c->mvs[a]));
+        /* where the finished job keeps the vectors: one in the record, or sixteen in the sparse section (framejob.h) */
+        if (!hinted) { r->mv[0] = c->mvs[a][0][0]; r->mv[1] = c->mvs[a][0][1]; }
+        if (same_mv) { r->pred |= FJ_PRED_UNIFORM_MV; r->mvx = 0; }
+        else { r->pred &= (uint8_t)~FJ_PRED_UNIFORM_MV; r->mvx = c->n_mvx; c->mvx_list[c->n_mvx++] = (uint16_t)a; }
+        const int uni = same_mv && r->coded == 0;
+        c->cls[a] = (uint8_t)(uni ? (((r->mv[0] | r->mv[1]) & 7) == 0 ? 3 : 1) : 0);
+        if (recon && !(c->cls[a] & 2)) fj_gen_entry(c, a, r, same_mv ? 1 : mvs_equal_in_quadrants(c->mvs[a]) ? 2 : 0);
+    }
+    return 0;
+}
+
+/* deblocking: a uniform MB whose filtered left/top neighbours are uniform too, with the same reference and
+ * mv components closer than 4 quarter samples, has all-zero strengths (8.7.2.1) — never visited again */
+static inline int fj_dbk_trivial(const FjCtx *c, uint32_t a)
+{
+    const FjMbRec *recs = c->recs, *r = &recs[a];
+    const uint8_t *cls = c->cls;
+    if (r->kind == FJ_MB_ABSENT || r->dbk == 0) return 1;
+    if (!(cls[a] & 1)) return 0;
+    int trivial = 1;
+    const uint32_t nb[2] = { a - 1, a - c->w };
+    const uint8_t want[2] = { (uint8_t)(r->dbk & FJ_DBK_LEFT), (uint8_t)(r->dbk & FJ_DBK_TOP) };
+    for (int k = 0; k < 2 && trivial; k++) {
+        if (!want[k]) continue;
+        const uint32_t p = nb[k];
+        if (cls[p] & 1) {
+            const int dx = r->mv[0] - recs[p].mv[0], dy = r->mv[1] - recs[p].mv[1];
+            trivial = recs[p].ref_slot[0] == r->ref_slot[0] && dx > -4 && dx < 4 && dy > -4 && dy < 4;
+        } else if (recs[p].kind == FJ_MB_INTER) {
+            /* a coded or partitioned inter neighbour: the four 4x4 blocks of it that touch the edge decide (8.7.2.1: a
+             * coded block, another reference or a vector 4 quarter samples away give a strength).  A fifth of what
+             * k_dbk used to visit turned out strength-free: most of it is this case */
+            for (int i = 0; i < 4 && trivial; i++) {
+                const int bx = k ? i : 3, by = k ? 3 : i;
+                const int z = ((by >> 1) << 3) | ((bx >> 1) << 2) | ((by & 1) << 1) | (bx & 1);
+                const int16_t *pm = (recs[p].pred & FJ_PRED_UNIFORM_MV) ? recs[p].mv : c->mvs[p][4 * by + bx];
+                const int dx = r->mv[0] - pm[0], dy = r->mv[1] - pm[1];
+                trivial = !((recs[p].coded >> z) & 1u) && recs[p].ref_slot[(by >> 1) * 2 + (bx >> 1)] == r->ref_slot[0] &&
+                          dx > -4 && dx < 4 && dy > -4 && dy < 4;
+            }
+        } else trivial = 0;
+    }
+    return trivial;
+}
+
+/* ---- copy list: runs of up to FJ_COPY_RUN copy MBs with consecutive addresses, equal reference and mv; a run whose
+ * displacement is zero may continue into the next row (tiles are contiguous in address order).  Built after the raster
+ * pass because copy elision looks at the deblocking verdict of the macroblocks to the right and below: a zero-motion
+ * copy is CLEAN when neither its own filter nor that of the two macroblocks that could reach into its tile runs; a
+ * clean copy makes the destination tile equal to the source tile, so its tile inherits the source's number, and when
+ * the destination carried that number already the copy would write what is there — it is left out. ---- */
+static void fj_copy_runs(FjCtx *c, FjElide *elide)
+{
+    const uint32_t n = c->n, w = c->w;
+    const FjMbRec *recs = c->recs;
+    FjCopy *copy_tmp = c->copy_tmp;
+    uint32_t n_copy = 0;
+    if (elide && !c->recon_all) elide = NULL;                 /* (callers do not ask for it either) */
     for (uint32_t a = 0, x = 0; a < n; a++, x = x + 1 == w ? 0 : x + 1) {     /* x = a % w without the division */
         const FjMbRec *r = &recs[a];
         if (elide) elide->out[a] = elide->serial;
-        if (!(RECON(r) && (cls[a] & 2))) continue;
+        if (!(fj_recon(c, r) && (c->cls[a] & 2))) continue;
         const int16_t *m0 = r->mv;
         if (elide && (m0[0] | m0[1]) == 0 && r->ref_slot[0] < elide->n_slots && r->ref_slot[0] != elide->cur_slot && r->dbk_trivial &&
             (x + 1 == w || recs[a + 1].dbk_trivial) && (a + w >= n || recs[a + w].dbk_trivial)) {
@@ -344,95 +391,116 @@ deblock_index:
             n_copy++;
         }
     }
-    if (n_conceal) {
-        /* Synthesised macroblocks read the neighbours that were decoded or concealed BEFORE them in the reference's
-         * concealment order (coef_idx), on any of the four sides: walk them in that order. */
-        uint32_t *ord = (uint32_t *)malloc(n_conceal * sizeof(uint32_t));
-        if (!ord) return -1;
-        uint32_t k = 0;
-        for (uint32_t a = 0; a < n; a++) if (recs[a].kind == FJ_MB_CONCEAL_I && RECON(&recs[a])) ord[k++] = a;
-        for (uint32_t i = 1; i < k; i++) {              /* insertion sort by sequence number */
-            const uint32_t v = ord[i];
-            uint32_t j = i;
-            while (j > 0 && recs[ord[j - 1]].coef_idx > recs[v].coef_idx) { ord[j] = ord[j - 1]; j--; }
-            ord[j] = v;
-        }
-        for (uint32_t i = 0; i < k; i++) {
-            const uint32_t a = ord[i], x = a % w;
-            FjMbRec *r = &recs[a];
-            int lvl = -1;
-#define DEP(cond, idx) do { if (cond) { const FjMbRec *q = &recs[idx]; \
-            if (in_intra_schedule(q->kind) && RECON(q) && (int)q->intra_level > lvl) lvl = q->intra_level; } } while (0)
-            DEP((r->avail & FJ_CONC_LEFT) && x > 0, a - 1);
-            DEP((r->avail & FJ_CONC_RIGHT) && x + 1 < w, a + 1);
-            DEP((r->avail & FJ_CONC_ABOVE) && a >= w, a - w);
-            DEP((r->avail & FJ_CONC_BELOW) && a + w < n, a + w);
-#undef DEP
-            r->intra_level = (uint16_t)(lvl + 1);
-            if ((uint32_t)(lvl + 1) > max_level) max_level = (uint32_t)(lvl + 1);
-            hist[lvl + 1]++;
-            n_intra++;
-            r->ref_slot[0] = (uint8_t)(((r->avail & FJ_CONC_LEFT) ? FJ_NEED_L : 0) | ((r->avail & FJ_CONC_ABOVE) ? FJ_NEED_U : 0) |
-                                       ((r->avail & FJ_CONC_RIGHT) ? FJ_NEED_R : 0) | ((r->avail & FJ_CONC_BELOW) ? FJ_NEED_D : 0));
-            r->ref_slot[1] = r->ref_slot[2] = r->ref_slot[3] = 0;
-        }
-        free(ord);
+    c->n_copy = n_copy;
+}
+
+/* ---- sections behind the coefficients: level starts | intra index | copy runs | general-inter | deblocking index | sparse vectors.
+ * One walk over them gives every offset, refuses a job that does not fit and zeroes the alignment gaps, so that a frame job is a
+ * pure function of the bitstream; then the lists move from the scratch into their sections ---- */
+static int fj_emit(FjCtx *c, uint32_t cap)
+{
+    FjHeader *h = c->h;
+    uint8_t *job = (uint8_t *)h;
+    c->n_levels = c->n_intra ? c->max_level + 1 : 0;
+    h->n_coef_blocks = c->coef_blocks;
+    h->n_copy = c->n_copy; h->n_gen = c->n_gen; h->n_dbk = c->n_dbk; h->n_mvx = c->n_mvx;
+    const struct { uint32_t *off, count, size; } sec[6] = {
+        { &h->lvl_off, c->n_levels + 1, 4 }, { &h->idx_off, c->n_intra, 2 }, { &h->copy_off, c->n_copy, 8 },
+        { &h->gen_off, c->n_gen, 16 }, { &h->dbk_off, c->n_dbk, 2 }, { &h->mvx_off, c->n_mvx, 64 } };
+    uint32_t end = h->coef_off + c->coef_blocks * 32u;
+    for (int i = 0; i < 6; i++) {
+        const uint32_t off = fj_align32(end);
+        if (off > cap) return -1;
+        memset(job + end, 0, off - end);
+        *sec[i].off = off;
+        end = off + sec[i].count * sec[i].size;
     }
-    /* ---- sections behind the coefficients: level starts | intra index | copy runs | general-inter | deblocking index */
-    const uint32_t n_levels = n_intra ? max_level + 1 : 0;
-    h->n_coef_blocks = coef_blocks;
-    h->lvl_off = fj_align32(h->coef_off + coef_blocks * 32u);
-    h->idx_off = fj_align32(h->lvl_off + (n_levels + 1) * 4u);
-    h->copy_off = fj_align32(h->idx_off + n_intra * 2u);
-    h->n_copy = n_copy;
-    h->n_gen = n_gen;
-    h->gen_off = fj_align32(h->copy_off + n_copy * 8u);
-    h->dbk_off = fj_align32(h->gen_off + n_gen * 16u);
-    h->n_dbk = n_dbk;
-    h->mvx_off = fj_align32(h->dbk_off + n_dbk * 2u);
-    h->n_mvx = n_mvx;
-    h->total_bytes = fj_align32(h->mvx_off + n_mvx * 64u);
+    h->total_bytes = fj_align32(end);
     if (h->total_bytes > cap) return -1;
     /* the dense vectors are read below: they lie in front of the coefficients (hand-built jobs) or behind everything (the parser) */
     if (h->mv_off >= h->coef_off && h->mv_off < h->total_bytes) return -1;       /* (behind the coefficients = behind the whole job) */
-    for (uint32_t i = 0; i < n_mvx; i++) memcpy(job + h->mvx_off + (size_t)i * 64u, mvs[mvx_list[i]], 64);
-    memcpy(job + h->copy_off, copy_tmp, (size_t)n_copy * 8u);
-    {   /* general-inter list: the entries with one motion vector per macroblock first (k_recon_inter<0>), then those with
-         * one per 8x8 quadrant (<1>), then the finer partitions (<2>); every part keeps raster order */
-        FjGen *dst = (FjGen *)(job + h->gen_off);
-        uint32_t k = 0;
-        for (uint32_t i = 0; i < n_gen; i++) if (gen_tmp[i].uniform == 1) dst[k++] = gen_tmp[i];
-        h->n_gen_uniform = k;
-        for (uint32_t i = 0; i < n_gen; i++) if (gen_tmp[i].uniform == 2) dst[k++] = gen_tmp[i];
-        h->n_gen_quad = k - h->n_gen_uniform;
-        for (uint32_t i = 0; i < n_gen; i++) if (gen_tmp[i].uniform == 0) dst[k++] = gen_tmp[i];
+    for (uint32_t i = 0; i < c->n_mvx; i++) memcpy(job + h->mvx_off + (size_t)i * 64u, c->mvs[c->mvx_list[i]], 64);
+    memcpy(job + h->copy_off, c->copy_tmp, (size_t)c->n_copy * 8u);
+    /* general-inter list: the entries with one motion vector per macroblock first (k_recon_inter<0>), then those with
+     * one per 8x8 quadrant (<1>), then the finer partitions (<2>); every part keeps raster order */
+    static const uint8_t part[3] = { 1, 2, 0 };
+    FjGen *dst = (FjGen *)(job + h->gen_off);
+    uint32_t ends[3], k = 0;
+    for (int p = 0; p < 3; p++) {
+        for (uint32_t i = 0; i < c->n_gen; i++) if (c->gen_tmp[i].uniform == part[p]) dst[k++] = c->gen_tmp[i];
+        ends[p] = k;
     }
-    memcpy(job + h->dbk_off, dbk_tmp, (size_t)n_dbk * 2u);
-    {   /* intra schedule: the scheduled MB addresses sorted by dependency level, ascending address inside a level */
-        uint32_t *lvl_start = (uint32_t *)(job + h->lvl_off);
-        uint16_t *idx = (uint16_t *)(job + h->idx_off);
-        lvl_start[0] = 0;
-        for (uint32_t l = 0; l < n_levels; l++) lvl_start[l + 1] = lvl_start[l] + hist[l];
-        for (uint32_t l = 0; l < n_levels; l++) hist[l] = lvl_start[l];           /* hist becomes the cursor */
-        if (!n_conceal) {
-            for (uint32_t i = 0; i < n_intra; i++) idx[hist[recs[ilist[i]].intra_level]++] = ilist[i];
-        } else {
-            for (uint32_t a = 0; a < n; a++)
-                if (in_intra_schedule(recs[a].kind) && RECON(&recs[a])) idx[hist[recs[a].intra_level]++] = (uint16_t)a;
-        }
+    h->n_gen_uniform = ends[0];
+    h->n_gen_quad = ends[1] - ends[0];
+    memcpy(job + h->dbk_off, c->dbk_tmp, (size_t)c->n_dbk * 2u);
+    /* intra schedule: the scheduled MB addresses sorted by dependency level, ascending address inside a level */
+    uint32_t *lvl_start = (uint32_t *)(job + h->lvl_off), *hist = c->hist;
+    uint16_t *idx = (uint16_t *)(job + h->idx_off);
+    lvl_start[0] = 0;
+    for (uint32_t l = 0; l < c->n_levels; l++) lvl_start[l + 1] = lvl_start[l] + hist[l];
+    for (uint32_t l = 0; l < c->n_levels; l++) hist[l] = lvl_start[l];           /* hist becomes the cursor */
+    if (!c->n_conceal) {
+        for (uint32_t i = 0; i < c->n_intra; i++) idx[hist[c->recs[c->ilist[i]].intra_level]++] = c->ilist[i];
+    } else {
+        for (uint32_t a = 0; a < c->n; a++)
+            if (in_intra_schedule(c->recs[a].kind) && fj_recon(c, &c->recs[a])) idx[hist[c->recs[a].intra_level]++] = (uint16_t)a;
     }
-    {   /* zero the alignment gaps so that a frame job is a pure function of the bitstream */
-        const uint32_t ends[6] = { h->coef_off + coef_blocks * 32u, h->lvl_off + (n_levels + 1) * 4u,
-                                   h->idx_off + n_intra * 2u, h->copy_off + h->n_copy * 8u, h->gen_off + h->n_gen * 16u,
-                                   h->dbk_off + h->n_dbk * 2u };
-        const uint32_t nexts[6] = { h->lvl_off, h->idx_off, h->copy_off, h->gen_off, h->dbk_off, h->mvx_off };
-        for (int i = 0; i < 6; i++) if (nexts[i] > ends[i]) memset(job + ends[i], 0, nexts[i] - ends[i]);
+    return 0;
+}
+
+int fj_finalize(uint8_t *job, uint32_t cap, uint32_t coef_blocks) { return fj_finalize_ex(job, cap, coef_blocks, NULL); }
+
+int fj_finalize_ex(uint8_t *job, uint32_t cap, uint32_t coef_blocks, FjElide *elide)
+{
+    FjHeader *h = (FjHeader *)job;
+    const uint32_t n = h->n_mbs;
+    FjCtx c = { .h = h, .recs = (FjMbRec *)(job + h->rec_off), .mvs = (const int16_t (*)[16][2])(job + h->mv_off),
+                .n = n, .w = h->width_mbs, .coef_blocks = coef_blocks, .recon_all = !h->dbk_only };
+    /* the dense vectors (n x 64 bytes, read from here on) must lie inside the buffer, and whole: in front of the coefficients
+     * (hand-built jobs) or behind them; that they also clear the finished job is checked once its size is known (ADVICE r4) */
+    if ((size_t)h->mv_off + (size_t)n * 64u > cap) return -1;
+    if (h->mv_off < h->coef_off && (size_t)h->mv_off + (size_t)n * 64u > h->coef_off) return -1;
+    const size_t need_bytes = (size_t)n * (1 + 8 + 16 + 4 + 2 + 2 + 2) + ((size_t)n + 2) * 4 + 64;
+    if (tl_scratch_cap < need_bytes) {
+        free(tl_scratch);
+        tl_scratch = (uint8_t *)malloc(need_bytes);
+        tl_scratch_cap = tl_scratch ? need_bytes : 0;
+        if (!tl_scratch) return -1;
     }
-    h->n_intra = n_intra;
-    h->n_intra_levels = n_levels;
-    h->intra_down_deps = n_conceal ? 1 : 0;      /* concealed macroblocks may wait for the macroblock below them (FJ_NEED_D) */
-    h->n_inter = n - n_intra - n_absent;
-    h->any_deblock = any_dbk ? 1 : 0;
+    c.gen_tmp = (FjGen *)tl_scratch;
+    c.copy_tmp = (FjCopy *)(c.gen_tmp + n);
+    c.hist = (uint32_t *)(c.copy_tmp + n);
+    c.ord = c.hist + n + 2;
+    c.dbk_tmp = (uint16_t *)(c.ord + n);
+    c.ilist = c.dbk_tmp + n;
+    c.mvx_list = c.ilist + n;
+    c.cls = (uint8_t *)(c.mvx_list + n);
+    memset(c.hist, 0, ((size_t)n + 2) * 4);
+    /* ---- one raster pass: intra dependency levels + FJ_NEED masks, classification of the inter macroblocks,
+     * general-inter entries, deblocking index ---- */
+    for (uint32_t a = 0; a < n; a++) {
+        FjMbRec *r = &c.recs[a];
+        const int recon = fj_recon(&c, r);
+        c.any_dbk |= r->dbk;
+        /* seven of ten macroblocks of a P picture: one vector (the parser's hint), one reference, no coefficients — nothing of
+         * the general path (fj_classify) applies to them but the classification and, off the whole-sample grid, a list entry */
+        if (r->kind == FJ_MB_INTER && (r->pred & FJ_PRED_UNIFORM_MV) && r->coded == 0) {
+            const int whole = ((r->mv[0] | r->mv[1]) & 7) == 0;
+            c.cls[a] = whole ? 3 : 1;
+            r->mvx = 0;
+            if (recon && !whole) fj_gen_entry(&c, a, r, 1);
+        } else if (fj_classify(&c, a, r, recon)) return -1;
+        r->dbk_trivial = (uint8_t)fj_dbk_trivial(&c, a);
+        if (!r->dbk_trivial) c.dbk_tmp[c.n_dbk++] = (uint16_t)a;
+    }
+    fj_copy_runs(&c, elide);
+    if (c.n_conceal) fj_schedule_concealed(&c);
+    if (fj_emit(&c, cap)) return -1;
+    h->n_intra = c.n_intra;
+    h->n_intra_levels = c.n_levels;
+    h->intra_down_deps = c.n_conceal ? 1 : 0;      /* concealed macroblocks may wait for the macroblock below them (FJ_NEED_D) */
+    h->n_inter = n - c.n_intra - c.n_absent;
+    h->any_deblock = c.any_dbk ? 1 : 0;
     return 0;
 }
 
@@ -773,14 +841,6 @@ void hd_dense_mv_read(const FjMbRec *r, const int16_t *dense, int16_t out[32])
     else memcpy(out, dense, 64);
 }
 
-static int makes_pixels(int kind)
-{
-    return kind == FJ_MB_INTER || kind == FJ_MB_I4x4 || kind == FJ_MB_I16x16 || kind == FJ_MB_IPCM;
-}
-static uint32_t rec_blocks(const FjMbRec *r)
-{
-    return r->kind == FJ_MB_IPCM ? 12u : (uint32_t)__builtin_popcount(r->coded & 0x03FFFFFFu);
-}
 typedef struct GhostMb { uint32_t addr, n_blocks; FjMbRec rec; int16_t mv[32]; } GhostMb;   /* + n_blocks * 32 bytes */
 
 /* first decode of a macroblock that a redundant slice decoded again (RedoMb), or NULL */
@@ -791,22 +851,32 @@ static const struct RedoMb *redo_first_of(const HostDec *d, uint32_t addr)
     return NULL;
 }
 
+/* The record that the ghost job of slice sid stores for macroblock a (*first: the first decode it is, if it is one), or NULL.
+ * The macroblocks this slice WROTE (first decode), and with them those it only decoded again (a redundant slice:
+ * pixels of their first decode stay): the written ones may have predicted from them — same slice id — and the
+ * ghost job runs before the job that reconstructs first decodes, so it brings them along in that first version. */
+static const FjMbRec *ghost_rec_of(const HostDec *d, const FjMbRec *recs, uint32_t sid, uint32_t a, const struct RedoMb **first)
+{
+    *first = NULL;
+    if (d->mb_slice_id[a] != sid) return NULL;
+    /* recs[a] belongs to this slice only while no later (redundant) decode replaced it: after such a decode was rolled
+     * back (counter 2 -> 1) the record — and the coefficient blocks it points to — are the discarded decode's */
+    const int own_rec = d->mb_decoded[a] == 1 && d->mb_rec_sid[a] == sid;
+    if (!own_rec && d->mb_decoded[a] >= 1) *first = redo_first_of(d, a);
+    const FjMbRec *r = own_rec ? &recs[a] : *first ? &(*first)->rec : NULL;
+    return r && makes_pixels(r->kind) ? r : NULL;
+}
+
 static void ghost_store_slice(HostDec *d, uint32_t sid)
 {
     const FjHeader *h = (const FjHeader *)d->job;
-    const FjMbRec *recs = (const FjMbRec *)(d->job + h->rec_off);
+    const FjMbRec *recs = (const FjMbRec *)(d->job + h->rec_off), *r;
+    const struct RedoMb *f;
     const uint32_t n = d->pic_size_mbs;
     size_t need = sizeof(uint32_t);
     uint32_t count = 0, wrote = 0;
-    /* The macroblocks this slice WROTE (first decode), and with them those it only decoded again (a redundant slice:
-     * pixels of their first decode stay): the written ones may have predicted from them — same slice id — and the
-     * ghost job runs before the job that reconstructs first decodes, so it brings them along in that first version. */
     for (uint32_t a = 0; a < n; a++) {
-        if (d->mb_slice_id[a] != sid) continue;
-        const int own_rec = d->mb_decoded[a] == 1 && d->mb_rec_sid[a] == sid;      /* (see the second loop) */
-        const struct RedoMb *f = !own_rec && d->mb_decoded[a] >= 1 ? redo_first_of(d, a) : NULL;
-        const FjMbRec *r = own_rec ? &recs[a] : f ? &f->rec : NULL;
-        if (!r || !makes_pixels(r->kind)) continue;
+        if (!(r = ghost_rec_of(d, recs, sid, a, &f))) continue;
         need += sizeof(GhostMb) + (size_t)rec_blocks(r) * 32u;
         count++;
         wrote += d->mb_decoded[a] == 1;
@@ -825,13 +895,7 @@ static void ghost_store_slice(HostDec *d, uint32_t sid)
     uint8_t *p = d->ghost_buf + d->ghost_len;
     memcpy(p, &count, sizeof(count)); p += sizeof(count);
     for (uint32_t a = 0; a < n; a++) {
-        if (d->mb_slice_id[a] != sid) continue;
-        /* recs[a] belongs to this slice only while no later (redundant) decode replaced it: after such a decode was rolled
-         * back (counter 2 -> 1) the record — and the coefficient blocks it points to — are the discarded decode's */
-        const int own_rec = d->mb_decoded[a] == 1 && d->mb_rec_sid[a] == sid;
-        const struct RedoMb *f = !own_rec && d->mb_decoded[a] >= 1 ? redo_first_of(d, a) : NULL;
-        const FjMbRec *r = own_rec ? &recs[a] : f ? &f->rec : NULL;
-        if (!r || !makes_pixels(r->kind)) continue;
+        if (!(r = ghost_rec_of(d, recs, sid, a, &f))) continue;
         GhostMb g;
         g.addr = a; g.n_blocks = rec_blocks(r); g.rec = *r;
         g.rec.pred &= (uint8_t)~FJ_PRED_PHASE2;
@@ -855,10 +919,8 @@ static int ghost_submit(HostDec *d)
     for (const uint8_t *p = d->ghost_buf, *end = d->ghost_buf + d->ghost_len; p < end && !rc;) {
         uint32_t count, blocks = 0;
         memcpy(&count, p, sizeof(count)); p += sizeof(count);
-        FjHeader *h = (FjHeader *)blob;
-        memset(h, 0, sizeof(*h));
-        h->magic = FJ_MAGIC; h->width_mbs = mh->width_mbs; h->height_mbs = mh->height_mbs; h->n_mbs = n;
-        h->rec_off = 128; h->mv_off = h->rec_off + n * 32u; h->coef_off = h->mv_off + n * 64u;
+        FjHeader *h = job_header_start(blob, mh->width_mbs, mh->height_mbs);
+        h->mv_off = h->rec_off + n * 32u; h->coef_off = h->mv_off + n * 64u;
         FjMbRec *recs = (FjMbRec *)(blob + h->rec_off);
         memset(recs, 0, (size_t)n * 32u);
         for (uint32_t a = 0; a < n; a++) recs[a].kind = FJ_MB_ABSENT;
@@ -875,7 +937,7 @@ static int ghost_submit(HostDec *d)
             blocks += g.n_blocks;
         }
         if (fj_finalize(blob, cap, blocks)) { rc = -1; break; }
-        h->cur_slot = mh->cur_slot; h->n_slots = mh->n_slots; h->is_idr = mh->is_idr; h->pic_seq = mh->pic_seq;
+        job_stamp_like(h, mh);
         h->ghost = 1;
         if (d->sink.submit && d->sink.submit(d->sink.user, blob, h->total_bytes)) rc = -1;
     }
@@ -944,16 +1006,24 @@ static void restamp_slice_edges(HostDec *d)
     }
 }
 
+/* a copy of the open job: the used prefix, and the dense vectors, which live at the tail of the buffer */
+static uint8_t *job_clone_open(const HostDec *d)
+{
+    const FjHeader *h = (const FjHeader *)d->job;
+    uint8_t *blob = (uint8_t *)malloc(d->job_cap);
+    if (!blob) return NULL;
+    memcpy(blob, d->job, (size_t)h->coef_off + (size_t)d->coef_blocks * 32u);
+    memcpy(blob + h->mv_off, d->job + h->mv_off, (size_t)d->pic_size_mbs * 64u);
+    return blob;
+}
+
 static uint8_t *redo_split(HostDec *d, uint8_t **between)
 {
     *between = NULL;
     FjHeader *h = (FjHeader *)d->job;
     const uint32_t n = d->pic_size_mbs;
-    const size_t used = (size_t)h->coef_off + (size_t)d->coef_blocks * 32u;
-    uint8_t *blob = (uint8_t *)malloc(d->job_cap);
+    uint8_t *blob = job_clone_open(d);
     if (!blob) return NULL;
-    memcpy(blob, d->job, used);
-    memcpy(blob + h->mv_off, d->job + h->mv_off, (size_t)n * 64u);        /* the dense vectors live at the tail of the buffer */
     FjHeader *gh = (FjHeader *)blob;
     FjMbRec *grecs = (FjMbRec *)(blob + gh->rec_off);
     for (uint32_t i = 0; i < d->n_redo; i++) {
@@ -963,10 +1033,8 @@ static uint8_t *redo_split(HostDec *d, uint8_t **between)
     }
     if (d->n_redo2) {
         /* versions written over a first decode and hidden again by later metadata: a job that reconstructs only them */
-        uint8_t *mid = (uint8_t *)malloc(d->job_cap);
+        uint8_t *mid = job_clone_open(d);
         if (!mid) { free(blob); return NULL; }
-        memcpy(mid, d->job, used);
-        memcpy(mid + h->mv_off, d->job + h->mv_off, (size_t)n * 64u);
         FjHeader *mh = (FjHeader *)mid;
         FjMbRec *mrecs = (FjMbRec *)(mid + mh->rec_off);
         for (uint32_t a = 0; a < n; a++) { mrecs[a].pred &= (uint8_t)~FJ_PRED_PHASE2; mrecs[a].dbk = 0; }
@@ -1043,6 +1111,38 @@ static void mark_slice_corrupted(HostDec *d, uint32_t first_mb)
     d->coef_blocks = cut;
 }
 
+/* the walk of plan_concealment; whole: nothing of the picture survived (not filtered); count: macroblocks concealed so far */
+typedef struct Conceal { HostDec *d; FjMbRec *recs; int16_t (*mvs)[16][2]; int ref_slot, whole; uint32_t count; } Conceal;
+
+/* the next macroblock in the reference's walking order */
+static void conceal_one(Conceal *c, uint32_t a)
+{
+    HostDec *d = c->d;
+    const uint32_t w = d->width_mbs;
+    FjMbRec *r = &c->recs[a];
+    /* pixels of an earlier slice under a macroblock that a failed redundant slice un-decoded: other macroblocks may
+     * have predicted from them; they are reconstructed first, the concealment replaces them afterwards (RedoMb) */
+    const int over = d->mb_rec_sid[a] && makes_pixels(r->kind) && !hd_redo_keep_first(d, a, r, &c->mvs[a][0][0]);
+    memset(r, 0, sizeof(*r));
+    if (over) r->pred = FJ_PRED_PHASE2;
+    d->mb_rec_sid[a] = 0;
+    r->qp_y = 40; r->qp_c = 36;          /* QPc of QP 40 with chroma_qp_index_offset 0 */
+    r->dbk = c->whole ? 0 : (uint8_t)(FJ_DBK_INNER | ((a % w) ? FJ_DBK_LEFT : 0) | (a >= w ? FJ_DBK_TOP : 0));
+    r->coef_idx = c->count++;
+    if (c->ref_slot >= 0) {
+        r->kind = FJ_MB_CONCEAL_P;
+        memset(r->ref_slot, c->ref_slot, 4);
+    } else {
+        const uint32_t row = a / w, col = a % w;
+        r->kind = FJ_MB_CONCEAL_I;
+        r->avail = (uint8_t)((row && d->mb_decoded[a - w] ? FJ_CONC_ABOVE : 0) |
+                             (row != d->height_mbs - 1 && d->mb_decoded[a + w] ? FJ_CONC_BELOW : 0) |
+                             (col && d->mb_decoded[a - 1] ? FJ_CONC_LEFT : 0) |
+                             (col != w - 1 && d->mb_decoded[a + 1] ? FJ_CONC_RIGHT : 0));
+    }
+    d->mb_decoded[a] = 1;
+}
+
 /* Plan the concealment of every macroblock that is still not decoded when the access unit ends — reference
  * h264bsdConceal, src/h264bsd_conceal.c:124-260.  The PIXELS are produced on the device: a lost macroblock of a P
  * picture becomes a copy of the co-located macroblock of the first usable reference (FJ_MB_CONCEAL_P, copy list);
@@ -1054,7 +1154,6 @@ static uint32_t plan_concealment(HostDec *d, int p_type)
 {
     FjHeader *h = (FjHeader *)d->job;
     FjMbRec *recs = (FjMbRec *)(d->job + h->rec_off);
-    int16_t (*mvs)[16][2] = (int16_t (*)[16][2])(d->job + h->mv_off);
     const uint32_t n = d->pic_size_mbs, w = d->width_mbs, hgt = d->height_mbs;
     int ref_slot = -1;
     if (p_type)
@@ -1062,34 +1161,7 @@ static uint32_t plan_concealment(HostDec *d, int p_type)
     uint32_t first = 0;
     while (first < n && !d->mb_decoded[first]) first++;
     if (hd_trace) { fprintf(stderr, "TRACE conceal p_type %d ref %d decoded:", p_type, ref_slot); for (uint32_t a = 0; a < n; a++) fprintf(stderr, " %u", d->mb_decoded[a]); fprintf(stderr, "\n"); }
-    uint32_t seq = 0, count = 0;
-
-#define CONCEAL_ONE(a_, whole_) do { \
-        const uint32_t a__ = (a_); \
-        FjMbRec *r = &recs[a__]; \
-        /* pixels of an earlier slice under a macroblock that a failed redundant slice un-decoded: other macroblocks may \
-         * have predicted from them; they are reconstructed first, the concealment replaces them afterwards (RedoMb) */ \
-        const int over__ = d->mb_rec_sid[a__] && makes_pixels(r->kind) && !hd_redo_keep_first(d, a__, r, &mvs[a__][0][0]); \
-        memset(r, 0, sizeof(*r)); \
-        if (over__) r->pred = FJ_PRED_PHASE2; \
-        d->mb_rec_sid[a__] = 0; \
-        r->qp_y = 40; r->qp_c = 36;          /* QPc of QP 40 with chroma_qp_index_offset 0 */ \
-        r->dbk = (whole_) ? 0 : (uint8_t)(FJ_DBK_INNER | ((a__ % w) ? FJ_DBK_LEFT : 0) | (a__ >= w ? FJ_DBK_TOP : 0)); \
-        r->coef_idx = seq++; \
-        if (ref_slot >= 0) { \
-            r->kind = FJ_MB_CONCEAL_P; \
-            memset(r->ref_slot, ref_slot, 4); \
-        } else { \
-            const uint32_t row__ = a__ / w, col__ = a__ % w; \
-            r->kind = FJ_MB_CONCEAL_I; \
-            r->avail = (uint8_t)((row__ && d->mb_decoded[a__ - w] ? FJ_CONC_ABOVE : 0) | \
-                                 (row__ != hgt - 1 && d->mb_decoded[a__ + w] ? FJ_CONC_BELOW : 0) | \
-                                 (col__ && d->mb_decoded[a__ - 1] ? FJ_CONC_LEFT : 0) | \
-                                 (col__ != w - 1 && d->mb_decoded[a__ + 1] ? FJ_CONC_RIGHT : 0)); \
-        } \
-        d->mb_decoded[a__] = 1; \
-        count++; \
-    } while (0)
+    Conceal c = { d, recs, (int16_t (*)[16][2])(d->job + h->mv_off), ref_slot, first == n, 0 };
 
     if (first == n) {
         /* nothing of the picture survived: no pixel of it is shown or was predicted from by anything that remains, so
@@ -1098,7 +1170,7 @@ static uint32_t plan_concealment(HostDec *d, int p_type)
         d->n_redo = 0; d->n_redo2 = 0;
         memset(d->mb_rec_sid, 0, (size_t)n * sizeof(uint32_t));
         if (ref_slot >= 0) {
-            for (uint32_t a = 0; a < n; a++) CONCEAL_ONE(a, 1);
+            for (uint32_t a = 0; a < n; a++) conceal_one(&c, a);
         } else {
             /* constant 128: every macroblock is an I_PCM that reads the same twelve blocks of 0x80 bytes */
             d->coef_blocks = 0;                      /* no macroblock is left that owns a coefficient block */
@@ -1112,23 +1184,22 @@ static uint32_t plan_concealment(HostDec *d, int p_type)
                 d->mb_decoded[a] = 1;
             }
             d->coef_blocks += 12;
-            count = n;
+            c.count = n;
         }
-        return count;
+        return c.count;
     }
     const uint32_t row = first / w, col = first % w;
     /* the row of the first good macroblock: leftwards from it, then rightwards */
-    for (uint32_t j = col; j--;) CONCEAL_ONE(row * w + j, 0);
-    for (uint32_t j = col + 1; j < w; j++) if (!d->mb_decoded[row * w + j]) CONCEAL_ONE(row * w + j, 0);
+    for (uint32_t j = col; j--;) conceal_one(&c, row * w + j);
+    for (uint32_t j = col + 1; j < w; j++) if (!d->mb_decoded[row * w + j]) conceal_one(&c, row * w + j);
     /* the rows above it: column by column, upwards */
     if (row)
         for (uint32_t j = 0; j < w; j++)
-            for (uint32_t i = row; i--;) CONCEAL_ONE(i * w + j, 0);
+            for (uint32_t i = row; i--;) conceal_one(&c, i * w + j);
     /* the rows below it, in raster order */
     for (uint32_t i = row + 1; i < hgt; i++)
-        for (uint32_t j = 0; j < w; j++) if (!d->mb_decoded[i * w + j]) CONCEAL_ONE(i * w + j, 0);
-#undef CONCEAL_ONE
-    return count;
+        for (uint32_t j = 0; j < w; j++) if (!d->mb_decoded[i * w + j]) conceal_one(&c, i * w + j);
+    return c.count;
 }
 
 /* ---------------------------------------------------------------- one NAL unit */
@@ -1290,7 +1361,7 @@ int hd_decode(HostDec *d, uint8_t *stream, uint32_t len, uint32_t pic_id, uint32
             FjHeader *gh = (FjHeader *)earlier[k];
             const FjHeader *mh = (const FjHeader *)d->job;
             rc = fj_finalize(earlier[k], d->job_cap, mh->n_coef_blocks);
-            gh->cur_slot = mh->cur_slot; gh->n_slots = mh->n_slots; gh->is_idr = mh->is_idr; gh->pic_seq = mh->pic_seq;
+            job_stamp_like(gh, mh);
             if (!rc && d->sink.submit && d->sink.submit(d->sink.user, earlier[k], gh->total_bytes)) rc = -1;
         }
         free(earlier[k]);
