@@ -27,6 +27,8 @@
  *   concealment of lost macroblocks           src/h264bsd_conceal.c:266-637 (ConcealMb, Transform); the walking
  *                                             order of h264bsdConceal (:124-260) arrives in the frame job
  * (tests/test_damaged_streams.py pins the concealment against the compiled reference on damaged streams)
+ * oracle_deblock_census() is oracle_deblock() that also counts which decisions the filter takes (strength rules, gates, clips,
+ * saturation): tests/test_structured_jobs.py holds the hand-built test pictures to taking every one of them.
  * Known, deliberate gap: the reference turns a residual outside [-512,511] into a decode error
  * (transform.c:184-188); the oracle (like the kernels) just clips after prediction.
  */
@@ -585,39 +587,104 @@ static inline int is_intra_kind(int k)
     return k == FJ_MB_I4x4 || k == FJ_MB_I16x16 || k == FJ_MB_IPCM || k == FJ_MB_CONCEAL_I || k == FJ_MB_CONCEAL_P || k == FJ_MB_STALE;
 }
 
+/* ------------------------------------------------------------------ decision census (oracle_deblock_census)
+ * Which of the filter's decisions a picture takes: bs_of() and filter_line() count into cn[] when it is given (NULL: nothing is
+ * counted, the arithmetic is the same).  Filter classes are counted per line of samples, threshold classes per edge of a
+ * macroblock, strength classes per 4-sample segment: S_* below, once for each of vertical macroblock edge, vertical inner
+ * edge, horizontal macroblock edge, horizontal inner edge (CN_S + CN_S_N * (2 * dir + inner) + S_*).
+ * Classes that cannot occur keep their slot and stay zero: strength 4 on an inner edge and strength 3 on a macroblock edge
+ * (an intra side gives 4 exactly on macroblock edges), and "strength 0 by partition type" on a macroblock edge (the type
+ * rules only inner edges); tests/test_structured_jobs.py leaves them off its list. */
+#define CENSUS_FILTER(X) \
+    X(L_CLOSED_ALPHA_ONLY) X(L_CLOSED_P1_ONLY) X(L_CLOSED_Q1_ONLY) \
+    X(L_OPEN_AP0_AQ0) X(L_OPEN_AP1_AQ0) X(L_OPEN_AP0_AQ1) X(L_OPEN_AP1_AQ1) \
+    X(L_D_CLIP_POS) X(L_D_CLIP_NEG) X(L_D_UNCLIPPED_NONZERO) X(L_D_ZERO) \
+    X(L_P1Q1_CLIPPED) X(L_P1Q1_UNCLIPPED) X(L_OPEN_TC0_ZERO) X(L_SAT_0) X(L_SAT_255) \
+    X(L4_WEAK) X(L4_STRONG_AP0_AQ0) X(L4_STRONG_AP1_AQ0) X(L4_STRONG_AP0_AQ1) X(L4_STRONG_AP1_AQ1) \
+    X(C_D_CLIP_POS) X(C_D_CLIP_NEG) X(C_D_UNCLIPPED) X(C_SAT_0) X(C_SAT_255) X(C_BS4) \
+    X(T_INDEXA_CLIP_0) X(T_INDEXA_CLIP_51) X(T_QP_SUM_ODD) X(T_MBEDGE_QP_AND_CQP_OFF_DIFFER) X(T_ALPHA_ZERO)
+#define CENSUS_STRENGTH(X) \
+    X(BS4) X(BS3) X(BS2) X(BS1_REF) X(BS1_DX_PLUS4_ONLY) X(BS1_DX_MINUS4_ONLY) X(BS1_DY_PLUS4_ONLY) X(BS1_DY_MINUS4_ONLY) \
+    X(BS0_MAX_3) X(BS0_BY_TYPE_MV_4_OR_MORE)
+#define X(n) CN_##n,
+enum { CENSUS_FILTER(X) CN_S };
+#undef X
+#define X(n) S_##n,
+enum { CENSUS_STRENGTH(X) CN_S_N };
+#undef X
+#define CN_TOTAL (CN_S + 4 * CN_S_N)
+#define CNT(i) do { if (cn) cn[i]++; } while (0)
+
+int oracle_census_classes(void) { return CN_TOTAL; }
+
+/* name of class i ("" past the end); the returned string lives until the next call */
+const char *oracle_census_name(int i)
+{
+#define X(n) #n,
+    static const char *const filt[] = { CENSUS_FILTER(X) };
+    static const char *const str[] = { CENSUS_STRENGTH(X) };
+#undef X
+    static const char *const where[4] = { "V_MB_", "V_INNER_", "H_MB_", "H_INNER_" };
+    static char buf[64];
+    if (i < 0 || i >= CN_TOTAL) return "";
+    if (i < CN_S) return filt[i];
+    strcpy(buf, where[(i - CN_S) / CN_S_N]);
+    strcat(buf, str[(i - CN_S) % CN_S_N]);
+    return buf;
+}
+
 /* boundary strength between the 4x4 block (qx,qy) of MB q and its left (dir 0) / upper (dir 1)
  * neighbour block, which lies in MB p (== q for inner edges) */
 static int bs_of(const FjMbRec *q, const int16_t (*qmv)[2], const FjMbRec *p, const int16_t (*pmv)[2],
-                 int qx, int qy, int px, int py, int mb_edge)
+                 int qx, int qy, int px, int py, int mb_edge, uint64_t *cn)
 {
-    if (is_intra_kind(q->kind) || is_intra_kind(p->kind)) return mb_edge ? 4 : 3;
-    if (((q->coded >> z_of(qx, qy)) & 1) || ((p->coded >> z_of(px, py)) & 1)) return 2;
+    if (cn) cn += CN_S + CN_S_N * (2 * (qx == px) + !mb_edge);      /* the segment's group of strength classes */
+    if (is_intra_kind(q->kind) || is_intra_kind(p->kind)) { CNT(mb_edge ? S_BS4 : S_BS3); return mb_edge ? 4 : 3; }
+    if (((q->coded >> z_of(qx, qy)) & 1) || ((p->coded >> z_of(px, py)) & 1)) { CNT(S_BS2); return 2; }
+    const int16_t *a = qmv[4 * qy + qx], *b = pmv[4 * py + px];
+    const int dx = a[0] - b[0], dy = a[1] - b[1];
     if (!mb_edge) {
         /* inside a macroblock the reference compares motion only across the partition boundaries its TYPE has
          * (deblocking.c:1266-1345): none for 16x16 / P_Skip, the middle horizontal edge for 16x8, the middle vertical one
          * for 8x16.  The same thing as comparing everywhere unless the type and the vectors disagree, which happens
          * when a redundant decode changed the type and then failed before it wrote its vectors (FJ_PRED_PARTS) */
         const int parts = (q->pred >> FJ_PRED_PARTS_SHIFT) & 3, hor = qx == px, mid = hor ? qy == 2 : qx == 2;
-        if (parts == FJ_PARTS_16x16 || (parts == FJ_PARTS_16x8 && !(hor && mid)) || (parts == FJ_PARTS_8x16 && !(!hor && mid))) return 0;
+        if (parts == FJ_PARTS_16x16 || (parts == FJ_PARTS_16x8 && !(hor && mid)) || (parts == FJ_PARTS_8x16 && !(!hor && mid))) {
+            if (iabs(dx) >= 4 || iabs(dy) >= 4) CNT(S_BS0_BY_TYPE_MV_4_OR_MORE);
+            return 0;
+        }
     }
-    if (q->ref_slot[(qy >> 1) * 2 + (qx >> 1)] != p->ref_slot[(py >> 1) * 2 + (px >> 1)]) return 1;
-    const int16_t *a = qmv[4 * qy + qx], *b = pmv[4 * py + px];
-    if (iabs(a[0] - b[0]) >= 4 || iabs(a[1] - b[1]) >= 4) return 1;
+    if (q->ref_slot[(qy >> 1) * 2 + (qx >> 1)] != p->ref_slot[(py >> 1) * 2 + (px >> 1)]) { CNT(S_BS1_REF); return 1; }
+    if (iabs(dx) >= 4 || iabs(dy) >= 4) {
+        if (iabs(dx) == 4 && iabs(dy) < 4) CNT(dx > 0 ? S_BS1_DX_PLUS4_ONLY : S_BS1_DX_MINUS4_ONLY);
+        if (iabs(dy) == 4 && iabs(dx) < 4) CNT(dy > 0 ? S_BS1_DY_PLUS4_ONLY : S_BS1_DY_MINUS4_ONLY);
+        return 1;
+    }
+    if (iabs(dx) == 3 || iabs(dy) == 3) CNT(S_BS0_MAX_3);
     return 0;
 }
 
 /* filter one line of samples across an edge; pix points at q0, step = distance between samples */
-static void filter_line(u8 *pix, ptrdiff_t step, int bs, int alpha, int beta, int tc0, int chroma)
+static void filter_line(u8 *pix, ptrdiff_t step, int bs, int alpha, int beta, int tc0, int chroma, uint64_t *cn)
 {
     int p0 = pix[-step], p1 = pix[-2 * step], q0 = pix[0], q1 = pix[step];
-    if (!(iabs(p0 - q0) < alpha && iabs(p1 - p0) < beta && iabs(q1 - q0) < beta)) return;
+    const int ga = iabs(p0 - q0) < alpha, gp = iabs(p1 - p0) < beta, gq = iabs(q1 - q0) < beta;
+    if (!(ga && gp && gq)) {
+        if (cn && !chroma && bs < 4 && ga + gp + gq == 2) cn[!ga ? CN_L_CLOSED_ALPHA_ONLY : !gp ? CN_L_CLOSED_P1_ONLY : CN_L_CLOSED_Q1_ONLY]++;
+        return;
+    }
     if (chroma) {
         if (bs < 4) {
             int tc = tc0 + 1;
-            int d = clip3(-tc, tc, (((q0 - p0) * 4) + (p1 - q1) + 4) >> 3);
+            const int raw = (((q0 - p0) * 4) + (p1 - q1) + 4) >> 3;
+            int d = clip3(-tc, tc, raw);
+            CNT(raw > tc ? CN_C_D_CLIP_POS : raw < -tc ? CN_C_D_CLIP_NEG : CN_C_D_UNCLIPPED);
+            if (p0 + d < 0 || q0 - d < 0) CNT(CN_C_SAT_0);
+            if (p0 + d > 255 || q0 - d > 255) CNT(CN_C_SAT_255);
             pix[-step] = (u8)clip255(p0 + d);
             pix[0] = (u8)clip255(q0 - d);
         } else {
+            CNT(CN_C_BS4);
             pix[-step] = (u8)((2 * p1 + p0 + q1 + 2) >> 2);
             pix[0] = (u8)((2 * q1 + q0 + p1 + 2) >> 2);
         }
@@ -627,14 +694,26 @@ static void filter_line(u8 *pix, ptrdiff_t step, int bs, int alpha, int beta, in
     int ap = iabs(p2 - p0), aq = iabs(q2 - q0);
     if (bs < 4) {
         int tc = tc0 + (ap < beta) + (aq < beta);
-        int d = clip3(-tc, tc, (((q0 - p0) * 4) + (p1 - q1) + 4) >> 3);
-        if (ap < beta) pix[-2 * step] = (u8)(p1 + clip3(-tc0, tc0, (p2 + ((p0 + q0 + 1) >> 1) - 2 * p1) >> 1));
-        if (aq < beta) pix[step] = (u8)(q1 + clip3(-tc0, tc0, (q2 + ((p0 + q0 + 1) >> 1) - 2 * q1) >> 1));
+        const int raw = (((q0 - p0) * 4) + (p1 - q1) + 4) >> 3;
+        int d = clip3(-tc, tc, raw);
+        const int rp = (p2 + ((p0 + q0 + 1) >> 1) - 2 * p1) >> 1, rq = (q2 + ((p0 + q0 + 1) >> 1) - 2 * q1) >> 1;
+        if (cn) {
+            cn[CN_L_OPEN_AP0_AQ0 + (ap < beta) + 2 * (aq < beta)]++;
+            cn[raw > tc ? CN_L_D_CLIP_POS : raw < -tc ? CN_L_D_CLIP_NEG : raw ? CN_L_D_UNCLIPPED_NONZERO : CN_L_D_ZERO]++;
+            if (ap < beta) cn[rp > tc0 || rp < -tc0 ? CN_L_P1Q1_CLIPPED : CN_L_P1Q1_UNCLIPPED]++;
+            if (aq < beta) cn[rq > tc0 || rq < -tc0 ? CN_L_P1Q1_CLIPPED : CN_L_P1Q1_UNCLIPPED]++;
+            if (tc0 == 0) cn[CN_L_OPEN_TC0_ZERO]++;
+            if (p0 + d < 0 || q0 - d < 0) cn[CN_L_SAT_0]++;
+            if (p0 + d > 255 || q0 - d > 255) cn[CN_L_SAT_255]++;
+        }
+        if (ap < beta) pix[-2 * step] = (u8)(p1 + clip3(-tc0, tc0, rp));
+        if (aq < beta) pix[step] = (u8)(q1 + clip3(-tc0, tc0, rq));
         pix[-step] = (u8)clip255(p0 + d);
         pix[0] = (u8)clip255(q0 - d);
     } else {
         int p3 = pix[-4 * step], q3 = pix[3 * step];
         const int strong = iabs(p0 - q0) < ((alpha >> 2) + 2);
+        CNT(strong ? CN_L4_STRONG_AP0_AQ0 + (ap < beta) + 2 * (aq < beta) : CN_L4_WEAK);
         if (strong && ap < beta) {
             pix[-step] = (u8)((p2 + 2 * p1 + 2 * p0 + 2 * q0 + q1 + 4) >> 3);
             pix[-2 * step] = (u8)((p2 + p1 + p0 + q0 + 2) >> 2);
@@ -648,7 +727,7 @@ static void filter_line(u8 *pix, ptrdiff_t step, int bs, int alpha, int beta, in
     }
 }
 
-int oracle_deblock(const uint8_t *blob, uint8_t *frame)
+static int deblock_walk(const uint8_t *blob, uint8_t *frame, uint64_t *cn)
 {
     if (check_blob(blob)) return -1;
     const FjHeader *h = (const FjHeader *)blob;
@@ -675,16 +754,23 @@ int oracle_deblock(const uint8_t *blob, uint8_t *frame)
                 const int qpc = (qcq + qcp + 1) >> 1;
                 const int ia_l = clip3(0, 51, qpl + q->alpha_off), ib_l = clip3(0, 51, qpl + q->beta_off);
                 const int ia_c = clip3(0, 51, qpc + q->alpha_off), ib_c = clip3(0, 51, qpc + q->beta_off);
+                if (cn) {
+                    if (qpl + q->alpha_off < 0) cn[CN_T_INDEXA_CLIP_0]++;
+                    if (qpl + q->alpha_off > 51) cn[CN_T_INDEXA_CLIP_51]++;
+                    if ((q->qp_y + p->qp_y) & 1) cn[CN_T_QP_SUM_ODD]++;
+                    if (mb_edge && q->qp_y != p->qp_y && q->cqp_off != p->cqp_off) cn[CN_T_MBEDGE_QP_AND_CQP_OFF_DIFFER]++;
+                    if (alpha_tab[ia_l] == 0) cn[CN_T_ALPHA_ZERO]++;
+                }
                 for (int k = 0; k < 4; k++) {               /* four 4-sample segments along the edge */
                     const int qx = dir ? k : e, qy = dir ? e : k;
                     const int px = dir ? k : (mb_edge ? 3 : e - 1), py = dir ? (mb_edge ? 3 : e - 1) : k;
-                    const int bs = bs_of(q, mvs[a], p, mvs[pa], qx, qy, px, py, mb_edge);
+                    const int bs = bs_of(q, mvs[a], p, mvs[pa], qx, qy, px, py, mb_edge, cn);
                     if (!bs) continue;
                     const int tl = bs < 4 ? tc0_tab[ia_l][bs - 1] : 0;
                     for (int i = 0; i < 4; i++) {
                         u8 *pix = dir ? f.y + (size_t)(mby * 16 + 4 * e) * W + mbx * 16 + 4 * k + i
                                       : f.y + (size_t)(mby * 16 + 4 * k + i) * W + mbx * 16 + 4 * e;
-                        filter_line(pix, dir ? W : 1, bs, alpha_tab[ia_l], beta_tab[ib_l], tl, 0);
+                        filter_line(pix, dir ? W : 1, bs, alpha_tab[ia_l], beta_tab[ib_l], tl, 0, cn);
                     }
                     if (e & 1) continue;                    /* chroma has edges only at luma 0 and 8 */
                     const int tcc = bs < 4 ? tc0_tab[ia_c][bs - 1] : 0;
@@ -693,7 +779,7 @@ int oracle_deblock(const uint8_t *blob, uint8_t *frame)
                         for (int i = 0; i < 2; i++) {
                             u8 *pix = dir ? P + (size_t)(mby * 8 + 2 * e) * CW + mbx * 8 + 2 * k + i
                                           : P + (size_t)(mby * 8 + 2 * k + i) * CW + mbx * 8 + 2 * e;
-                            filter_line(pix, dir ? CW : 1, bs, alpha_tab[ia_c], beta_tab[ib_c], tcc, 1);
+                            filter_line(pix, dir ? CW : 1, bs, alpha_tab[ia_c], beta_tab[ib_c], tcc, 1, cn);
                         }
                     }
                 }
@@ -703,6 +789,11 @@ int oracle_deblock(const uint8_t *blob, uint8_t *frame)
     free(mvs);
     return 0;
 }
+
+int oracle_deblock(const uint8_t *blob, uint8_t *frame) { return deblock_walk(blob, frame, NULL); }
+
+/* oracle_deblock() that also counts the decisions it takes: counts[oracle_census_classes()], added to (the caller zeroes them) */
+int oracle_deblock_census(const uint8_t *blob, uint8_t *frame, uint64_t *counts) { return deblock_walk(blob, frame, counts); }
 
 int oracle_decode_picture(const uint8_t *blob, uint8_t *const *slots)
 {
@@ -755,7 +846,7 @@ int oracle_strengths(const uint8_t *blob, uint8_t *out)
                 for (int k = 0; k < 4; k++) {
                     const int qx = dir ? k : e, qy = dir ? e : k;
                     const int px = dir ? k : (mb_edge ? 3 : e - 1), py = dir ? (mb_edge ? 3 : e - 1) : k;
-                    out[32 * a + 16 * dir + 4 * e + k] = (uint8_t)bs_of(q, mvs[a], &recs[pa], mvs[pa], qx, qy, px, py, mb_edge);
+                    out[32 * a + 16 * dir + 4 * e + k] = (uint8_t)bs_of(q, mvs[a], &recs[pa], mvs[pa], qx, qy, px, py, mb_edge, NULL);
                 }
             }
     }

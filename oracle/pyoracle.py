@@ -37,6 +37,10 @@ def oracle_lib():
         lib.oracle_decode_picture.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]
         lib.oracle_recon.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]
         lib.oracle_deblock.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        lib.oracle_deblock_census.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        lib.oracle_strengths.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        lib.oracle_census_name.argtypes = [ctypes.c_int]
+        lib.oracle_census_name.restype = ctypes.c_char_p
         lib.oracle_convert.argtypes = [ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]
         lib.oracle_convert.restype = None
         lib.oracle_idct4x4.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
@@ -74,6 +78,34 @@ class OracleDpb:
         if fn(buf, self._ptrs) != 0:
             raise RuntimeError("oracle rejected the frame job")
         return self.slots[blob_header(blob)["cur_slot"]][: self.frame_bytes]
+
+
+def census_names():
+    """The names of the decision classes of oracle_deblock_census (oracle/pixel_oracle.c), in counter order."""
+    lib = oracle_lib()
+    return [lib.oracle_census_name(i).decode() for i in range(lib.oracle_census_classes())]
+
+
+def deblock_census(blob, frame):
+    """Deblock `frame` (np.uint8, the un-deblocked picture of `blob`) in place like oracle_deblock and return
+    {class name: count} of the decisions that the filter took."""
+    lib = oracle_lib()
+    names = census_names()
+    counts = np.zeros(len(names), dtype=np.uint64)
+    buf = ctypes.create_string_buffer(blob, len(blob))
+    if lib.oracle_deblock_census(buf, frame.ctypes.data, counts.ctypes.data) != 0:
+        raise RuntimeError("oracle rejected the frame job")
+    return {n: int(c) for n, c in zip(names, counts)}
+
+
+def strengths(blob):
+    """Boundary strengths [n_mbs][2][4][4] (direction, edge, segment) of a frame job: oracle_strengths."""
+    n = blob_header(blob)["n_mbs"]
+    out = np.zeros(n * 32, dtype=np.uint8)
+    buf = ctypes.create_string_buffer(blob, len(blob))
+    if oracle_lib().oracle_strengths(buf, out.ctypes.data) != 0:
+        raise RuntimeError("oracle rejected the frame job")
+    return out.reshape(n, 2, 4, 4)
 
 
 def oracle_convert(fmt, width, height, yuv):

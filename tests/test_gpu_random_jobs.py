@@ -7,42 +7,14 @@ import pytest
 
 from oracle import pyoracle
 from jobgen import build_job
+from replay_compare import RANDOM_PIPELINE, random_pipeline_jobs, run_and_compare as _run, tail  # noqa: F401 (tail is a fixture)
 
 pytestmark = pytest.mark.gpu
 
 
-def _run(built, jobs, n_streams=2, stages=7):
-    rep = built.Replay(jobs, n_streams=n_streams)
-    rep.set_stages(stages)
-    dpb = pyoracle.OracleDpb(jobs[0])
-    try:
-        for i, job in enumerate(jobs):
-            rep.run(i, 1)
-            want = dpb.decode(job, deblock=bool(stages & 4))
-            cur = pyoracle.blob_header(job)["cur_slot"]
-            for s in range(n_streams):
-                got = rep.fetch(s, cur)
-                if not np.array_equal(got, want):
-                    d = np.nonzero(got != want)[0]
-                    h = pyoracle.blob_header(job)
-                    W = h["width_mbs"] * 16
-                    i0 = int(d[0])
-                    where = f"luma x={i0 % W} y={i0 // W}" if i0 < W * h["height_mbs"] * 16 else f"chroma byte {i0 - W * h['height_mbs'] * 16}"
-                    pytest.fail(f"picture {i} stream {s}: {d.size} bytes differ, first at {where}: got {got[i0]} want {want[i0]}")
-    finally:
-        rep.close()
-
-
-@pytest.mark.parametrize("seed,wmb,hmb", [(1, 6, 5), (2, 11, 7), (3, 1, 1), (4, 1, 9), (5, 9, 1), (6, 20, 12), (7, 5, 4)])
+@pytest.mark.parametrize("seed,wmb,hmb", RANDOM_PIPELINE)
 def test_random_pictures_full_pipeline(built, seed, wmb, hmb):
-    rng = np.random.default_rng(seed)
-    lib = built.lib()
-    jobs = [build_job(lib, rng, wmb, hmb, 0, 4, [])]                       # intra / PCM only
-    jobs.append(build_job(lib, rng, wmb, hmb, 1, 4, [0]))
-    jobs.append(build_job(lib, rng, wmb, hmb, 2, 4, [0, 1]))
-    jobs.append(build_job(lib, rng, wmb, hmb, 3, 4, [0, 1, 2], p_inter=0.9))
-    jobs.append(build_job(lib, rng, wmb, hmb, 0, 4, [1, 2, 3], p_inter=0.97, mv_range=64))
-    _run(built, jobs)
+    _run(built, random_pipeline_jobs(built.lib(), seed, wmb, hmb))
 
 
 @pytest.mark.parametrize("seed", [11, 12])
@@ -84,19 +56,7 @@ def test_no_deblocking_at_all(built):
     _run(built, jobs)
 
 
-# ---- row bands of the two per-picture kernels (k_frame_dbk / k_frame_intra, kernels.hip.h): a picture split over several
-# workgroups with the hand-over through HBM must give the same samples as one workgroup ----
-DEFAULT_TAIL = (17, 9, 8, 0, 9, 12, 320)       # TailConfig (csrc/tick_plan.h)
-
-
-@pytest.fixture
-def tail(built):
-    def set_(*cfg):
-        built.set_tail(*cfg)
-    yield set_
-    built.set_tail(*DEFAULT_TAIL)
-
-
+# ---- row bands of the two per-picture kernels (replay_compare.tail) ----
 @pytest.mark.parametrize("rows,waves", [(1, 1), (1, 4), (2, 2), (3, 12)])
 @pytest.mark.parametrize("seed,wmb,hmb", [(31, 6, 5), (32, 11, 7), (33, 1, 1), (34, 1, 9), (35, 9, 1), (36, 20, 12)])
 def test_random_pictures_in_row_bands(built, tail, seed, wmb, hmb, rows, waves):

@@ -21,7 +21,7 @@ import pytest
 
 from oracle import pyoracle
 import h264bsd_amd
-from jobgen import QPC, Z_X, Z_Y, _i4_modes, build_job
+from jobgen import I_4x4, I_16x16_BASE, I_PCM, QPC, Z_X, Z_Y, _i4_modes, _patch_partitions, build_job
 
 
 class MvT(ctypes.Structure):             # reference src/h264bsd_macroblock_layer.h:117-122
@@ -61,9 +61,6 @@ class MacroblockLayer(ctypes.Structure):  # :152-160
 class ImageT(ctypes.Structure):          # reference src/h264bsd_image.h:46-55
     _fields_ = [("data", ctypes.c_void_p), ("width", ctypes.c_uint32), ("height", ctypes.c_uint32),
                 ("luma", ctypes.c_void_p), ("cb", ctypes.c_void_p), ("cr", ctypes.c_void_p)]
-
-
-P_SKIP, P_16x16, P_16x8, P_8x16, P_8x8, I_4x4, I_16x16_BASE, I_PCM = 0, 1, 2, 3, 4, 6, 7, 31   # mbType_e, :52-84
 
 
 @pytest.fixture(scope="module")
@@ -204,56 +201,15 @@ def test_intra_prediction_matches_the_reference_functions(ref, built, avail):
 
 
 # ------------------------------------------------------------------ deblocking
-def _patch_partitions(recs, mvs16, rng):
-    """give every inter macroblock of a jobgen picture (records and dense vectors, before the job is finished) a macroblock
-    type (Skip / 16x16 / 16x8 / 8x16 / 8x8) with motion and references to match, and the FJ_PARTS_* hint the parser would
-    set; returns the types"""
-    n = recs.shape[0]
-    mvs = mvs16.reshape(n, 4, 4, 2)                                   # [mb][by][bx][xy], raster
-    types = []
-    for a in range(n):
-        if recs[a, 0] != 0:
-            types.append(I_4x4 if recs[a, 0] in (1, 3) else I_16x16_BASE)
-            continue
-        t = int(rng.choice([P_SKIP, P_16x16, P_16x8, P_8x16, P_8x8]))
-        base = rng.integers(-40, 41, 2)
-        small = lambda: base + rng.integers(-6, 7, 2)                 # differences around the threshold of 4 quarter samples
-        refs = recs[a, 16:20].copy()
-        if t in (P_SKIP, P_16x16):
-            mvs[a, :, :] = small(); refs[:] = refs[0]; parts = 1
-        elif t == P_16x8:
-            mvs[a, :2] = small(); mvs[a, 2:] = small(); refs[1] = refs[0]; refs[3] = refs[2]; parts = 2
-        elif t == P_8x16:
-            mvs[a, :, :2] = small(); mvs[a, :, 2:] = small(); refs[2] = refs[0]; refs[3] = refs[1]; parts = 3
-        else:
-            for by in range(4):
-                for bx in range(4): mvs[a, by, bx] = small()
-            parts = 0
-        recs[a, 16:20] = refs
-        recs[a, 4] = (int(recs[a, 4]) & 0x8F) | (parts << 4)
-        types.append(t)
-    return types
-
-
-@pytest.mark.parametrize("seed", range(24))
-def test_deblocking_matches_h264bsdFilterPicture(ref, built, seed):
-    orc = pyoracle.oracle_lib()
-    rng = np.random.default_rng(5000 + seed)
-    wmb, hmb = int(rng.integers(1, 7)), int(rng.integers(1, 6))
-    n = wmb * hmb
-    types = []
-    blob = build_job(built.lib(), rng, wmb, hmb, 3, 4, [0, 1, 2], p_inter=0.75 if seed % 4 else 0.3, p_pcm=0.02,
-                     patch=lambda recs_, mvs_: types.extend(_patch_partitions(recs_, mvs_, rng)))
+def ref_filter_picture(ref, blob, types, start):
+    """h264bsdFilterPicture of the compiled reference on the picture `start` (I420 bytes, un-deblocked) with the mbStorage_t array
+    that the finished frame job `blob` describes; types: the mbType of every macroblock (jobgen._patch_partitions, jobgen.mb_types).
+    Returns the filtered picture."""
     h = pyoracle.blob_header(blob)
+    wmb, hmb, n = h["width_mbs"], h["height_mbs"], h["n_mbs"]
     recs = np.frombuffer(blob, dtype=np.uint8, count=n * 32, offset=h["rec_off"]).reshape(n, 32)
     mvs = h264bsd_amd.job_mvs(blob)
     W, H = wmb * 16, hmb * 16
-    start = rng.integers(0, 256, W * H * 3 // 2, dtype=np.uint8)
-    if seed % 3 == 0:                                                 # smooth content: the filters switch on far more often
-        start = (np.clip(rng.normal(128, 6, W * H * 3 // 2), 0, 255)).astype(np.uint8)
-    ours = start.copy()
-    buf = ctypes.create_string_buffer(blob, len(blob))
-    assert orc.oracle_deblock(buf, ctypes.c_void_p(ours.ctypes.data)) == 0
     theirs = np.concatenate([start, np.zeros(64, dtype=np.uint8)])
     mbs = (MbStorage * n)()
     for a in range(n):
@@ -272,6 +228,26 @@ def test_deblocking_matches_h264bsdFilterPicture(ref, built, seed):
         if dbk & 2: m.mbB = ctypes.pointer(mbs[a - wmb])
     img = ImageT(theirs.ctypes.data, wmb, hmb, theirs.ctypes.data, theirs.ctypes.data + W * H, theirs.ctypes.data + W * H + W * H // 4)
     ref.h264bsdFilterPicture(ctypes.byref(img), mbs)
+    return theirs[:start.size]
+
+
+@pytest.mark.parametrize("seed", range(24))
+def test_deblocking_matches_h264bsdFilterPicture(ref, built, seed):
+    orc = pyoracle.oracle_lib()
+    rng = np.random.default_rng(5000 + seed)
+    wmb, hmb = int(rng.integers(1, 7)), int(rng.integers(1, 6))
+    n = wmb * hmb
+    types = []
+    blob = build_job(built.lib(), rng, wmb, hmb, 3, 4, [0, 1, 2], p_inter=0.75 if seed % 4 else 0.3, p_pcm=0.02,
+                     patch=lambda recs_, mvs_: types.extend(_patch_partitions(recs_, mvs_, rng)))
+    W, H = wmb * 16, hmb * 16
+    start = rng.integers(0, 256, W * H * 3 // 2, dtype=np.uint8)
+    if seed % 3 == 0:                                                 # smooth content: the filters switch on far more often
+        start = (np.clip(rng.normal(128, 6, W * H * 3 // 2), 0, 255)).astype(np.uint8)
+    ours = start.copy()
+    buf = ctypes.create_string_buffer(blob, len(blob))
+    assert orc.oracle_deblock(buf, ctypes.c_void_p(ours.ctypes.data)) == 0
+    theirs = ref_filter_picture(ref, blob, types, start)
     diff = np.nonzero(ours != theirs[:ours.size])[0]
     assert diff.size == 0, f"{wmb}x{hmb}: {diff.size} samples differ, first at byte {int(diff[0])}"
     if seed % 3 == 0 and n >= 4: assert np.count_nonzero(ours != start) > 0, "the smooth pictures must actually get filtered"

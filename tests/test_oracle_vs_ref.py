@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from oracle import pyoracle
+from jobgen import FRACTIONS, _edge_component, window_targets
 
 pytestmark = pytest.mark.skipif(not os.path.exists(pyoracle.REF_SO), reason="oracle/_ref not built (needs /root/reference)")
 
@@ -92,14 +93,29 @@ def test_inter_prediction_matches_h264bsdPredictSamples(ref):
     cb = frame[W * H:].ctypes.data
     cr = frame[W * H + W * H // 4:].ctypes.data
     sizes = [(16, 16), (16, 8), (8, 16), (8, 8), (8, 4), (4, 8), (4, 4)]
-    for it in range(1500):
-        pw, ph = sizes[it % 7]
+    # after the random vectors, for every partition size: the reference window (luma: block - 2 .. block + 3, chroma: block .. block + 1)
+    # with its first column / row at -1, 0, +1 and its last at size - 2, size - 1, size, for luma and for chroma, every horizontal
+    # position with every vertical one, in macroblocks at the four corners and on the four borders, the fraction class taking turns
+    at = [(0, 0), (wmb - 1, 0), (0, hmb - 1), (wmb - 1, hmb - 1), (1, 0), (1, hmb - 1), (0, 1), (wmb - 1, 1)]
+    edges = [(size, tx, ty) for size in sizes for tx in window_targets(W) for ty in window_targets(H)]
+    for it in range(1500 + len(edges)):
+        if it < 1500:
+            pw, ph = sizes[it % 7]
+        else:
+            (pw, ph), tx, ty = edges[it - 1500]
         px = int(rng.integers(0, 16 // pw)) * pw
         py = int(rng.integers(0, 16 // ph)) * ph
         mbx, mby = int(rng.integers(0, wmb)), int(rng.integers(0, hmb))
         big = rng.random() < 0.3
         mvx = int(rng.integers(-8192, 8192)) if big else int(rng.integers(-90, 91))
         mvy = int(rng.integers(-2048, 2048)) if big else int(rng.integers(-90, 91))
+        if it >= 1500:
+            mbx, mby = at[it % 8]
+            fx, fy = FRACTIONS[(it // 8) % len(FRACTIONS)]
+            mvx, mvy = _edge_component(16 * mbx + px, pw, tx, fx), _edge_component(16 * mby + py, ph, ty, fy)
+            for (plane, end, t), pos, blk, mvc in ((tx, 16 * mbx + px, pw, mvx), (ty, 16 * mby + py, ph, mvy)):
+                first, last = (pos + (mvc >> 2) - 2, pos + (mvc >> 2) + blk + 2) if plane == "luma" else (pos // 2 + (mvc >> 3), pos // 2 + (mvc >> 3) + blk // 2)
+                assert (first if end == "first" else last) == t, "the window is not where the case says"
         mv = MvT(mvx, mvy)
         data = np.zeros(384 + 64, dtype=np.uint8)
         base = data.ctypes.data
