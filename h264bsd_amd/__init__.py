@@ -9,6 +9,9 @@ from .capi import (  # noqa: F401
     EXPORTED_SYMBOLS, LIB_PATH, FMT_RGBA, FMT_BGRA, FMT_YCBCRA, FMT_I420, Decoder, DevicePicture, BatchDriver, Replay, build, capture_stream, job_header, job_mvs, convert, device_count, device_errors, device_error_events, lib, api_lib, use_product_library, set_tail, pull_batch,
     TensorSpec, ColourSpec, ResizeSpec, pull_tensor, Region, pull_regions, MotionSpec, pull_motion, Remap, RemapSpec, pull_remap, affine_maps,
     StatsSpec, RegionStats, pull_stats, stats_record_bytes,
+    ChangeSpec, RegionChange, keep_pictures, pull_change, change_record_bytes,
 )
 
-__version__ = "0.3.0"      # 0.2: pull_remap / affine_maps (h264bsdmiOutputTensorRemap); 0.3: pull_stats (h264bsdmiOutputRegionStats)
+# 0.2: pull_remap / affine_maps (h264bsdmiOutputTensorRemap); 0.3: pull_stats (h264bsdmiOutputRegionStats);
+# 0.4: keep_pictures / pull_change (h264bsdmiKeepCurrentPictures, h264bsdmiOutputRegionChange)
+__version__ = "0.4.0"

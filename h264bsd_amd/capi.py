@@ -28,7 +28,7 @@ EXPORTED_SYMBOLS = [
     "h264bsdCroppingParams", "h264bsdSampleAspectRatio", "h264bsdCheckValidParamSets", "h264bsdFlushBuffer",
     "h264bsdProfile", "h264bsdAlloc", "h264bsdFree", "h264bsdConvertToRGBA", "h264bsdConvertToBGRA",
     "h264bsdConvertToYCbCrA",
-    "h264bsdmiInitCapture", "h264bsdmiNextOutputInfo", "h264bsdmiNextOutputPictureDevice", "h264bsdmiNextOutputTensorBatch", "h264bsdmiNextOutputTensorBatchColour", "h264bsdmiNextOutputTensorBatchResize", "h264bsdmiOutputTensorRegions", "h264bsdmiOutputTensorRemap", "h264bsdmiSetMotionExport", "h264bsdmiOutputMotionRegions", "h264bsdmiOutputRegionStats", "h264bsdmiJobFinalize", "h264bsdmiDeviceCount", "h264bsdmiSetDevice", "h264bsdmiFlush", "h264bsdmiFlushAsync", "h264bsdmiDeviceErrors",
+    "h264bsdmiInitCapture", "h264bsdmiNextOutputInfo", "h264bsdmiNextOutputPictureDevice", "h264bsdmiNextOutputTensorBatch", "h264bsdmiNextOutputTensorBatchColour", "h264bsdmiNextOutputTensorBatchResize", "h264bsdmiOutputTensorRegions", "h264bsdmiOutputTensorRemap", "h264bsdmiSetMotionExport", "h264bsdmiOutputMotionRegions", "h264bsdmiOutputRegionStats", "h264bsdmiKeepCurrentPictures", "h264bsdmiOutputRegionChange", "h264bsdmiJobFinalize", "h264bsdmiDeviceCount", "h264bsdmiSetDevice", "h264bsdmiFlush", "h264bsdmiFlushAsync", "h264bsdmiDeviceErrors",
     "h264bsdmiDecodePicture", "h264bsdmiDecodePictureBatch", "h264bsdmiNextOutputPictureBatch", "h264bsdmiPullAndDecodePictureBatch", "h264bsdmiSetParserThreads", "h264bsdmiSetInputReadOnly", "h264bsdmiSetCopyElision",
     "h264bsdmiReplayCreate", "h264bsdmiReplayCreateStaggered", "h264bsdmiReplayCreateDesync", "h264bsdmiReplayCreateSched", "h264bsdmiReplayReschedule", "h264bsdmiReplayDestroy", "h264bsdmiReplayRun", "h264bsdmiReplaySync",
     "h264bsdmiReplayFetch", "h264bsdmiReplayChecksums", "h264bsdmiReplayConvert", "h264bsdmiReplayFetchConverted",
@@ -87,6 +87,12 @@ class MotionSpec(ctypes.Structure):
 class StatsSpec(ctypes.Structure):
     """h264bsdmi_stats_spec (include/h264bsd_mi355x.h)"""
     _fields_ = [("data", ctypes.c_void_p), ("source", ctypes.c_uint32), ("bins", ctypes.c_uint32), ("crop", ctypes.c_uint32)]
+
+
+class ChangeSpec(ctypes.Structure):
+    """h264bsdmi_change_spec (include/h264bsd_mi355x.h)"""
+    _fields_ = [("data", ctypes.c_void_p), ("source", ctypes.c_uint32), ("bins", ctypes.c_uint32), ("crop", ctypes.c_uint32),
+                ("threshold", ctypes.c_uint32 * 3), ("keep_after", ctypes.c_uint32)]
 
 
 STATS_SOURCES = {"y": (0, 1), "ycbcr": (1, 3), "rgb": (2, 3)}                    # name -> (H264BSDMI_STATS_*, channels)
@@ -222,6 +228,11 @@ def _declare(L, harness):
     L.h264bsdmiOutputMotionRegions.restype = ctypes.c_int
     L.h264bsdmiOutputRegionStats.argtypes = [u32, ctypes.POINTER(vp), u32, ctypes.POINTER(Region), ctypes.POINTER(StatsSpec), vp, P32, P32, P32]
     L.h264bsdmiOutputRegionStats.restype = ctypes.c_int
+    L.h264bsdmiKeepCurrentPictures.argtypes = [u32, ctypes.POINTER(vp), vp, P32, P32]
+    L.h264bsdmiKeepCurrentPictures.restype = ctypes.c_int
+    L.h264bsdmiOutputRegionChange.argtypes = [u32, ctypes.POINTER(vp), u32, ctypes.POINTER(Region), ctypes.POINTER(ChangeSpec), vp,
+                                              P32, P32, P32, P32, P32]
+    L.h264bsdmiOutputRegionChange.restype = ctypes.c_int
     L.h264bsdmiDecodePicture.argtypes = [vp, u8p, u32, u32, P32, P32]
     L.h264bsdmiDecodePicture.restype = u32
     L.h264bsdmiDecodePictureBatch.argtypes = [u32, ctypes.POINTER(vp), ctypes.POINTER(vp), P32, P32, P32, P32, P32]
@@ -528,7 +539,7 @@ def pull_batch(decoders, frame_bytes=None):
 
 
 def _regions_arg(who, n, regions):
-    """the regions of pull_regions, pull_motion and pull_stats, checked: (K, the Region array); None (one whole window per decoder): (n, None)"""
+    """the regions of pull_regions, pull_motion, pull_stats and pull_change, checked: (K, the Region array); None (one whole window per decoder): (n, None)"""
     if regions is None:
         K, regs = n, None
     else:
@@ -843,6 +854,94 @@ def pull_stats(decoders, regions=None, source="ycbcr", bins=256, crop=True, out=
     spec = StatsSpec(out.data_ptr(), src, bins, 1 if crop else 0)
     got, cur, ids = _current_pull("h264bsdmiOutputRegionStats", decoders, K, regs, (ctypes.byref(spec),), stream, call=K > 0)     # no records: no call
     return RegionStats(out, C, bins, got, cur, ids)
+
+
+def change_record_bytes(source, bins):
+    """the stride of one record of h264bsdmiOutputRegionChange: 8 + 32 C + 4 C B bytes"""
+    if source not in STATS_SOURCES or bins not in STATS_BINS:
+        raise ValueError(f"change_record_bytes: unsupported source / bins {source} {bins}")
+    C = STATS_SOURCES[source][1]
+    return 8 + 32 * C + 4 * C * bins
+
+
+def _call_stream(stream):
+    """the torch stream a call without an output tensor runs on (as _out_and_stream: the legacy default stream is waited for)"""
+    import torch
+    if stream is None:
+        stream = torch.cuda.current_stream()
+    if not stream.cuda_stream:
+        stream.synchronize()
+    return stream
+
+
+def keep_pictures(decoders, stream=None):
+    """h264bsdmiKeepCurrentPictures: the CURRENT picture of every decoder becomes its kept picture, what pull_change compares later
+    pictures with; one launch copies them all.  stream as for pull_tensor.  Returns (kept, pic_ids): per decoder 1 when it had a
+    current picture (0: what it kept before stays), and the picId of the picture it keeps now (0: none)."""
+    n = len(decoders)
+    kept, ids = (ctypes.c_uint32 * max(n, 1))(), (ctypes.c_uint32 * max(n, 1))()
+    if n:
+        rc = api_lib().h264bsdmiKeepCurrentPictures(n, (ctypes.c_void_p * n)(*[d._st for d in decoders]), _call_stream(stream).cuda_stream, kept, ids)
+        if rc != 0:
+            raise RuntimeError(f"h264bsdmiKeepCurrentPictures failed ({rc})")
+    return list(kept)[:n], list(ids)[:n]
+
+
+class RegionChange:
+    """what pull_change returns: count [R] int32; sad, ssd, sum [R, C] int64; max, above [R, C] int32; hist [R, C, B] int32 or None —
+    views of `records` ([R, stride] uint8, one allocation, the C layout); got [R], and per decoder current, kept, pic_id, kept_pic_id,
+    lists of ints"""
+
+    def __init__(self, records, C, B, got, current, kept, pic_id, kept_pic_id):
+        import torch
+        w32, w64 = records.view(torch.int32), records.view(torch.int64)
+        self.records = records
+        self.count = w32[:, 0]
+        self.sad, self.ssd, self.sum = w64[:, 1:1 + 4 * C:4], w64[:, 2:2 + 4 * C:4], w64[:, 3:3 + 4 * C:4]
+        self.max, self.above = w32[:, 8:8 + 8 * C:8], w32[:, 9:9 + 8 * C:8]
+        self.hist = w32[:, 2 + 8 * C:].unflatten(1, (C, B)) if B else None
+        self.got, self.current, self.kept, self.pic_id, self.kept_pic_id = got, current, kept, pic_id, kept_pic_id
+
+    def mse(self):
+        """[R, C] float64: ssd / count (nan where count is 0)"""
+        import torch
+        return self.ssd.to(torch.float64) / self.count.to(torch.float64)[:, None]
+
+    def psnr(self):
+        """[R, C] float64 in dB against a peak of 255: inf where ssd is 0"""
+        import torch
+        return 10.0 * torch.log10(255.0 * 255.0 / self.mse())
+
+
+def pull_change(decoders, regions=None, source="y", bins=0, threshold=0, crop=True, keep=False, out=None, stream=None):
+    """h264bsdmiOutputRegionChange: integer statistics of (current picture - kept picture, keep_pictures) over boxes, computed by one
+    kernel launch where the two pictures lie — nothing is popped and no pixel is pulled.  regions, source, bins, crop, out and stream as
+    for pull_stats (out: [R, change_record_bytes(source, bins)]).  threshold: one int 0..255 or one per channel; `above` counts the
+    samples with |d| > threshold.  A record: count, per channel sad, ssd, sum (signed), max, above and hist of |d|.  got[r] = 1 only
+    where the decoder has a current AND a kept picture: other records are left untouched.  keep=True: behind the comparison the
+    current pictures become the kept ones (decoders without a kept picture included: a per-picture loop starts itself); kept and
+    kept_pic_id report what the comparison saw.  Returns a RegionChange."""
+    import torch
+    n = len(decoders)
+    if source not in STATS_SOURCES or bins not in STATS_BINS:
+        raise ValueError(f"pull_change: unsupported source / bins {source} {bins}")
+    src, C = STATS_SOURCES[source]
+    thr = [threshold] * 3 if isinstance(threshold, int) else list(threshold) + [0] * (3 - C) if isinstance(threshold, (tuple, list)) else []
+    if len(thr) != 3 or not all(isinstance(t, int) and 0 <= t <= 255 for t in thr):
+        raise ValueError(f"pull_change: threshold is one int in 0..255, or one per channel, not {threshold}")
+    K, regs = _regions_arg("pull_change", n, regions)
+    shape = (K, change_record_bytes(source, bins))
+    out, stream = _out_and_stream("pull_change", out, shape, torch.uint8, stream, aligned=True)
+    spec = ChangeSpec(out.data_ptr(), src, bins, 1 if crop else 0, (ctypes.c_uint32 * 3)(*thr), 1 if keep else 0)
+    got = (ctypes.c_uint32 * max(K, 1))()
+    per = [(ctypes.c_uint32 * max(n, 1))() for _ in range(4)]                # current, kept, picId, keptPicId
+    if n:
+        rc = api_lib().h264bsdmiOutputRegionChange(n, (ctypes.c_void_p * n)(*[d._st for d in decoders]), K, regs, ctypes.byref(spec),
+                                                   stream.cuda_stream, got, *per)
+        if rc != 0:
+            raise RuntimeError(f"h264bsdmiOutputRegionChange failed ({rc})")
+    cur, kept, ids, kept_ids = [list(a)[:n] for a in per]
+    return RegionChange(out, C, bins, list(got)[:K], cur, kept, ids, kept_ids)
 
 
 def job_header(blob):

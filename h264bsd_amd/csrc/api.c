@@ -34,6 +34,11 @@ typedef struct ApiDec {
     int has_cur;
     int fed;        /* h264bsdDecode has been called: too late for h264bsdmiSetMotionExport */
     int motion;     /* motion export is on (h264bsdmiSetMotionExport) */
+    /* the kept picture (h264bsdmiKeepCurrentPictures): the engine holds its bytes, this is what is known about it without asking.  It
+     * counts only while kept_wmb x kept_hmb is the HostDec's coded size (has_kept_picture): the engine frees the buffer when a sequence
+     * of another size is configured, and h264bsdDecode forgets it for good when it sees the size change */
+    int has_kept;
+    u32 kept_id, kept_wmb, kept_hmb;
 } ApiDec;
 
 /* Every H264BSDMI_* variable this library reads (tests/test_abi.py compares the list with the sources and INTEGRATION.md).  A
@@ -56,6 +61,7 @@ __attribute__((constructor)) static void report_unknown_switches(void)
 
 static ApiDec *dec_of(storage_t *s) { return s ? (ApiDec *)s->opaque : NULL; }
 static void drop_current(ApiDec *a) { if (a) a->has_cur = 0; }
+static int has_kept_picture(const ApiDec *a) { return a->has_kept && a->kept_wmb == a->hd->width_mbs && a->kept_hmb == a->hd->height_mbs; }
 
 /* ---- capture sink ---- */
 static int cap_configure(void *u, uint32_t w, uint32_t h, uint32_t n) { (void)u; (void)w; (void)h; (void)n; return 0; }
@@ -120,7 +126,9 @@ u32 h264bsdDecode(storage_t *s, u8 *byteStrm, u32 len, u32 picId, u32 *readBytes
     drop_current(a);
     if (!a || !byteStrm || !len || !readBytes) return H264BSD_ERROR;
     a->fed = 1;
-    return (u32)hd_decode(a->hd, byteStrm, len, picId, readBytes);
+    const u32 r = (u32)hd_decode(a->hd, byteStrm, len, picId, readBytes);
+    if (a->has_kept && !has_kept_picture(a)) a->has_kept = 0;          /* a sequence of another coded size: the kept picture is gone */
+    return r;
 }
 
 static const OutPic *pop_output(ApiDec *a, u32 *picId, u32 *isIdrPic, u32 *numErrMbs)
@@ -354,14 +362,15 @@ int h264bsdmiNextOutputTensorBatchResize(u32 n, storage_t *const *dec, const h26
 }
 
 /* ---- The pulls of CURRENT pictures (pop_output, drop_current): h264bsdmiOutputTensorRegions, h264bsdmiOutputTensorRemap,
- * h264bsdmiOutputMotionRegions, h264bsdmiOutputRegionStats.  Each checks its own spec; everything else is one path:
+ * h264bsdmiOutputMotionRegions, h264bsdmiOutputRegionStats, h264bsdmiOutputRegionChange (which needs the kept picture as well), and
+ * their small sibling h264bsdmiKeepCurrentPictures (the picture list only).  Each checks its own spec; everything else is one path:
  *   regions_refused   got, the count and the range of every region — before the instances are looked at
  *   pull_begin        dec and the instances (of this library, with the sink entry the call needs, distinct), then the lists
  *   pull_pic          an instance's current picture in the picture list, appended at its first use
  *   pull_regions      the regions (or one whole window per instance) of the pictures that exist, each with its rectangle
  *   pull_finish       after the sink: got, box, current and picId — unless the sink failed (-2 writes nothing) — and the lists freed
  * A refused call returns -1 and has called no sink, written nothing; no call pops anything. */
-enum { PULL_REGIONS, PULL_REMAP, PULL_MOTION, PULL_STATS };
+enum { PULL_REGIONS, PULL_REMAP, PULL_MOTION, PULL_STATS, PULL_CHANGE, PULL_KEEP };
 #define NO_PIC 0xFFFFFFFFu
 typedef struct CurrentPull {
     u32 n, m, k;                /* instances; pictures and items gathered so far */
@@ -370,6 +379,7 @@ typedef struct CurrentPull {
     u32 *pic_of;                /* per instance: its index in pics, NO_PIC before its first use */
     SinkRegion *regs;           /* the items for the sink: regions, or (PULL_REMAP) maps */
     SinkRemap *maps;
+    int kind;                   /* PULL_* */
 } CurrentPull;
 
 /* regions == NULL: no regions at all, or (whole: one whole window per instance) exactly n */
@@ -394,6 +404,8 @@ static int sink_pulls(const ApiDec *a, int kind)
     case PULL_REMAP:  return k->tensor_remap != NULL;
     case PULL_MOTION: return k->motion_regions != NULL && a->motion;          /* ... and motion export is on */
     case PULL_STATS:  return k->tensor_regions != NULL && k->region_stats != NULL;
+    case PULL_CHANGE: return k->tensor_regions != NULL && k->region_change != NULL && k->keep_pictures != NULL;
+    case PULL_KEEP:   return k->tensor_regions != NULL && k->keep_pictures != NULL;
     }
     return k->tensor_regions != NULL;
 }
@@ -409,16 +421,18 @@ static int pull_begin(CurrentPull *c, u32 n, storage_t *const *dec, u32 n_items,
     }
     *c = (CurrentPull){ n, 0, 0, dec, (SinkTensorPic *)malloc((n ? n : 1) * sizeof(SinkTensorPic)), (u32 *)malloc((n ? n : 1) * sizeof(u32)),
                         kind == PULL_REMAP ? NULL : (SinkRegion *)malloc((n_items ? n_items : 1) * sizeof(SinkRegion)),
-                        kind == PULL_REMAP ? (SinkRemap *)malloc((n_items ? n_items : 1) * sizeof(SinkRemap)) : NULL };
+                        kind == PULL_REMAP ? (SinkRemap *)malloc((n_items ? n_items : 1) * sizeof(SinkRemap)) : NULL, kind };
     if (!c->pics || !c->pic_of || !(c->regs || c->maps)) { pull_free(c); return -1; }
     for (u32 i = 0; i < n; i++) c->pic_of[i] = NO_PIC;
     return 0;
 }
-/* the index in pics of instance inst's current picture, NO_PIC when it has none (got = 0 for what names it) */
+/* the index in pics of instance inst's current picture, NO_PIC when it has none (got = 0 for what names it); PULL_CHANGE: when it has
+ * no kept picture either */
 static u32 pull_pic(CurrentPull *c, u32 inst, const h264bsdmi_tensor_spec *spec, const h264bsdmi_colour_spec *colour)
 {
     const ApiDec *a = dec_of(c->dec[inst]);
     if (!a->has_cur || !a->hd->active_sps) return NO_PIC;
+    if (c->kind == PULL_CHANGE && !has_kept_picture(a)) return NO_PIC;
     if (c->pic_of[inst] == NO_PIC) {
         c->pic_of[inst] = c->m;
         tensor_pic(&c->pics[c->m++], a, a->cur.slot, inst, spec, colour);
@@ -532,6 +546,74 @@ int h264bsdmiOutputRegionStats(u32 n, storage_t *const *dec, u32 nRegions, const
     const h264bsdmi_tensor_spec window = { spec->data, 1, 1, 0, 0, 0, spec->crop, 1, { 0, 0, 0 }, { 1, 1, 1 } };
     pull_regions(&c, nRegions, regions, &window, &REFERENCE_COLOUR, 1, 1, 0);
     const int failed = c.k && c.pics[0].sink->region_stats(c.m, c.pics, c.k, c.regs, spec, stream);
+    return pull_finish(&c, failed, nRegions, got, NULL, current, picId);
+}
+
+/* The current pictures of the instances as the sink's keep_pictures takes them: whole coded frames, one per instance that has one.
+ * mark_kept: after the sink has taken them */
+static const h264bsdmi_tensor_spec KEEP_WINDOW = { NULL, 1, 1, 0, 0, 0, 0, 1, { 0, 0, 0 }, { 1, 1, 1 } };
+static int keep_begin(CurrentPull *c, u32 n, storage_t *const *dec)
+{
+    if (pull_begin(c, n, dec, 0, PULL_KEEP)) return -1;
+    for (u32 i = 0; i < n; i++) (void)pull_pic(c, i, &KEEP_WINDOW, &REFERENCE_COLOUR);
+    return 0;
+}
+static void mark_kept(const CurrentPull *c)
+{
+    for (u32 i = 0; i < c->n; i++) {
+        ApiDec *a = dec_of(c->dec[i]);
+        if (c->pic_of[i] == NO_PIC) continue;
+        a->has_kept = 1;
+        a->kept_id = a->cur.pic_id;
+        a->kept_wmb = a->hd->width_mbs;
+        a->kept_hmb = a->hd->height_mbs;
+    }
+}
+
+/* The current picture of each instance becomes its kept picture */
+int h264bsdmiKeepCurrentPictures(u32 n, storage_t *const *dec, void *stream, u32 *kept, u32 *picId)
+{
+    CurrentPull c;
+    if (!n) return 0;
+    if (!kept || keep_begin(&c, n, dec)) return -1;
+    const int failed = c.m && c.pics[0].sink->keep_pictures(c.m, c.pics, stream);
+    if (!failed) {
+        mark_kept(&c);
+        for (u32 i = 0; i < n; i++) {
+            const ApiDec *a = dec_of(dec[i]);
+            kept[i] = c.pic_of[i] != NO_PIC;
+            if (picId) picId[i] = has_kept_picture(a) ? a->kept_id : 0;
+        }
+    }
+    pull_free(&c);
+    return failed ? -2 : 0;
+}
+
+/* Integer statistics of (current picture - kept picture) over h264bsdmiOutputRegionStats' regions; keep_after: then the keep call's
+ * launch for every instance with a current picture.  kept / keptPicId are what the comparison saw; -2 writes nothing, marks nothing */
+int h264bsdmiOutputRegionChange(u32 n, storage_t *const *dec, u32 nRegions, const h264bsdmi_region *regions,
+                                const h264bsdmi_change_spec *spec, void *stream,
+                                u32 *got, u32 *current, u32 *kept, u32 *picId, u32 *keptPicId)
+{
+    CurrentPull c, k;
+    if (!spec || !spec->data || ((uintptr_t)spec->data & 7u) || spec->source > H264BSDMI_STATS_RGB || spec->crop > 1 || spec->keep_after > 1) return -1;
+    if (spec->bins != 0 && spec->bins != 16 && spec->bins != 32 && spec->bins != 64 && spec->bins != 128 && spec->bins != 256) return -1;
+    if (spec->threshold[0] > 255 || spec->threshold[1] > 255 || spec->threshold[2] > 255) return -1;
+    if (regions_refused(n, nRegions, regions, got, 1) || pull_begin(&c, n, dec, nRegions, PULL_CHANGE)) return -1;
+    if (spec->keep_after && keep_begin(&k, n, dec)) { pull_free(&c); return -1; }
+    const h264bsdmi_tensor_spec window = { spec->data, 1, 1, 0, 0, 0, spec->crop, 1, { 0, 0, 0 }, { 1, 1, 1 } };
+    pull_regions(&c, nRegions, regions, &window, &REFERENCE_COLOUR, 1, 1, 0);
+    int failed = c.k && c.pics[0].sink->region_change(c.m, c.pics, c.k, c.regs, spec, stream);
+    if (spec->keep_after && !failed) failed = k.m && k.pics[0].sink->keep_pictures(k.m, k.pics, stream);
+    if (!failed) {
+        for (u32 i = 0; i < n; i++) {
+            const ApiDec *a = dec_of(dec[i]);
+            if (kept) kept[i] = has_kept_picture(a) ? 1 : 0;
+            if (keptPicId) keptPicId[i] = has_kept_picture(a) ? a->kept_id : 0;
+        }
+        if (spec->keep_after) mark_kept(&k);
+    }
+    if (spec->keep_after) pull_free(&k);
     return pull_finish(&c, failed, nRegions, got, NULL, current, picId);
 }
 

@@ -37,6 +37,8 @@
 #include "kernels/k_tensor_remap.hip.h"
 #include "kernels/k_motion.hip.h"
 #include "kernels/k_region_stats.hip.h"
+#include "kernels/k_keep.hip.h"
+#include "kernels/k_region_change.hip.h"
 #include "engine.h"
 #include "hip_owned.h"
 #include "tick_plan.h"
@@ -88,6 +90,9 @@ struct StreamCtx {
     bool motion = false;
     DeviceMem<uint8_t> d_motion; size_t motion_bytes = 0;      /* n_slots x motion_bytes */
     uint32_t slot_seq[FJ_MAX_SLOTS] = {}; bool slot_has[FJ_MAX_SLOTS] = {};
+    /* the kept picture (h264bsdmiKeepCurrentPictures): one frame of kept_wmb x kept_hmb macroblock tiles, allocated at the instance's
+     * first keep; it outlives sink_configure with the same size and goes, behind Engine.kept_ev, with another size or the instance */
+    DeviceMem<uint8_t> d_kept; uint32_t kept_wmb = 0, kept_hmb = 0;
 };
 
 /* k_dbk (boundary strengths) needs only the frame job, not pixels: it runs on a second HIP stream next to the
@@ -151,9 +156,9 @@ constexpr unsigned CONVERT_WGS = CONVERT_WGS_N;      /* workgroups per picture o
 constexpr uint32_t LANE_DBK_WAVES = LANE_DBK_WAVES_N;
 
 /* the item stride of the tensor pulls' staging ring: k_tensor_out / k_tensor_resize read TensorItems, k_tensor_aa AaItems, k_tensor_roi
- * RoiItems, k_motion_roi MotionItems, k_tensor_remap RemapItems, k_region_stats StatsItems */
+ * RoiItems, k_motion_roi MotionItems, k_tensor_remap RemapItems, k_region_stats StatsItems, k_keep KeepItems, k_region_change ChangeItems */
 constexpr size_t TITEM_BYTES = std::max({ sizeof(h264k::TensorItem), sizeof(h264k::AaItem), sizeof(h264k::RoiItem), sizeof(h264k::MotionItem),
-                                          sizeof(h264k::RemapItem), sizeof(h264k::StatsItem) });
+                                          sizeof(h264k::RemapItem), sizeof(h264k::StatsItem), sizeof(h264k::KeepItem), sizeof(h264k::ChangeItem) });
 struct TItemSlot { uint8_t bytes[TITEM_BYTES]; };
 struct Engine {
     std::mutex mu;
@@ -178,10 +183,15 @@ struct Engine {
     /* tensor pulls (tensor_out_locked): the staging ring of their items; fence events that no instance holds any more */
     Staged<TItemSlot> titems;
     std::vector<Fence *> fences;
-    /* region statistics with row bands (stats_out_locked): the regions' tickets (STATS_MAX_PARTIALS words, zero between launches),
-     * then the bands' partial records; stats_ev is recorded behind the latest launch that used them, and the next one waits for it */
+    /* region and change statistics with row bands (stats_scratch_locked): the regions' tickets (STATS_MAX_PARTIALS words, zero between
+     * launches), then the bands' partial records; stats_ev is recorded behind the latest launch that used them, and the next one waits for it */
     DeviceMem<uint8_t> d_stats;
     Event stats_ev;
+    /* kept pictures (StreamCtx.d_kept) are written on one caller's stream and read on another's: kept_ev is recorded behind EVERY launch
+     * that reads or writes any of them and waited for by the next such launch, which puts them in one total order: the latest
+     * recording covers all earlier ones, and a kept buffer is freed behind it (kept_drop) */
+    Event kept_ev;
+    bool kept_recorded = false;
 };
 
 /* One engine per HIP device, created on first use.  A decoder instance (or replay set) lives on the device that is
@@ -618,6 +628,15 @@ static void fence_drop(Engine *e, StreamCtx *s)
     fence_unref(e, s);
 }
 
+/* s's kept picture is about to be freed: every launch that reads or writes a kept buffer must have finished */
+static void kept_drop(Engine *e, StreamCtx *s)
+{
+    if (!s->d_kept) return;
+    if (e->kept_recorded) (void)hipEventSynchronize(e->kept_ev);
+    s->d_kept.reset();
+    s->kept_wmb = s->kept_hmb = 0;
+}
+
 /* ---- motion export: the side information of a picture kept beside its frame buffer (kernels/k_motion.hip.h) ----
  * The job about to be launched for instance s, as an item of the tick's k_motion_keep launch.  The side information of a frame
  * buffer is that of the last job decoded into it that is no ghost: ghost jobs (pre-passes of the picture that follows in the same
@@ -793,6 +812,7 @@ int sink_configure(void *user, uint32_t wmb, uint32_t hmb, uint32_t n_slots)
     HIP_TRY(hipSetDevice(u->e->device));
     if (u->e->out_stream) HIP_TRY(hipStreamSynchronize(u->e->out_stream));
     fence_drop(u->e, u->s);
+    if (u->s->kept_wmb != wmb || u->s->kept_hmb != hmb) kept_drop(u->e, u->s);        /* the same coded size keeps the kept picture */
     stream_release(u->s, true);
     u->s->wmb = wmb; u->s->hmb = hmb; u->s->n_slots = n_slots;
     u->s->frame_bytes = fj_frame_bytes(wmb, hmb);
@@ -1029,6 +1049,7 @@ void sink_close(void *user)
         hipStreamSynchronize(u->e->stream);
         if (u->e->out_stream) hipStreamSynchronize(u->e->out_stream);      /* (a pull that failed half way may have left its kernel behind) */
         fence_drop(u->e, u->s);
+        kept_drop(u->e, u->s);
         stream_release(u->s);
         auto &v = u->e->streams;
         v.erase(std::remove(v.begin(), v.end(), u->s), v.end());
@@ -1356,6 +1377,24 @@ static int motion_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, u
                               pull_grid(m.width, m.height, h264k::TAA_COLS, h264k::TAA_ROWS, n_regs), &margs, fence_ev);
 }
 
+/* The scratch in which the row bands of k_region_stats and k_region_change meet (Engine.d_stats), allocated at its first use for the
+ * larger of the two records; two launches must not use it at once: st waits for the event behind the previous one (the caller records
+ * stats_ev behind its launch). */
+static int stats_scratch_locked(Engine *e, hipStream_t st, uint32_t **tickets, uint8_t **partials)
+{
+    const size_t ticket_bytes = h264k::STATS_MAX_PARTIALS * sizeof(uint32_t);
+    if (!e->d_stats) {
+        DeviceMem<uint8_t> fresh;
+        HIP_TRY(e->stats_ev.create(hipEventDisableTiming));
+        HIP_TRY(fresh.alloc(ticket_bytes + (size_t)h264k::STATS_MAX_PARTIALS * std::max(h264k::STATS_MAX_RECORD, h264k::CHANGE_MAX_RECORD)));
+        HIP_TRY(hipMemsetAsync(fresh, 0, ticket_bytes, st));
+        e->d_stats = std::move(fresh);
+    } else HIP_TRY(hipStreamWaitEvent(st, e->stats_ev, 0));
+    *tickets = reinterpret_cast<uint32_t *>(e->d_stats.get());
+    *partials = e->d_stats.get() + ticket_bytes;
+    return 0;
+}
+
 /* h264bsdmiOutputRegionStats: one StatsItem per region, box ∩ window in luma samples of the coded frame, ONE k_region_stats launch
  * of S row bands per region: S is one value for the launch, about 1024 workgroups in all, at most the macroblock rows of the tallest
  * box ∩ window, 1 from 1024 regions on.  With S > 1 the bands meet in the engine's scratch (Engine.d_stats), which two launches
@@ -1393,21 +1432,104 @@ static int stats_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, ui
     }
     const uint32_t S = n_regs >= h264k::STATS_MAX_PARTIALS ? 1u : std::min(h264k::STATS_MAX_PARTIALS / n_regs, tallest);
     h264k::StatsArgs sargs{ e->titems.dev<h264k::StatsItem>(), nullptr, nullptr, sp.bins, sp.bins ? shift : 0u };
-    if (S > 1u) {
-        const size_t tickets = h264k::STATS_MAX_PARTIALS * sizeof(uint32_t);
-        if (!e->d_stats) {
-            DeviceMem<uint8_t> fresh;
-            HIP_TRY(e->stats_ev.create(hipEventDisableTiming));
-            HIP_TRY(fresh.alloc(tickets + (size_t)h264k::STATS_MAX_PARTIALS * h264k::STATS_MAX_RECORD));
-            HIP_TRY(hipMemsetAsync(fresh, 0, tickets, st));
-            e->d_stats = std::move(fresh);
-        } else HIP_TRY(hipStreamWaitEvent(st, e->stats_ev, 0));
-        sargs.tickets = reinterpret_cast<uint32_t *>(e->d_stats.get());
-        sargs.partials = e->d_stats.get() + tickets;
-    }
+    if (S > 1u && stats_scratch_locked(e, st, &sargs.tickets, &sargs.partials)) return -1;
     if (pull_launch_locked(e, n, pics, st, fns[sp.source][sp.bins != 0u], dim3(S, n_regs), &sargs, fence_ev)) return -1;
     if (S > 1u) HIP_TRY(hipEventRecord(e->stats_ev, st));
     return 0;
+}
+
+/* launches that touch kept pictures run one behind the other, whatever streams they are on (Engine.kept_ev) */
+static int kept_order_begin(Engine *e, hipStream_t st)
+{
+    if (!e->kept_ev) HIP_TRY(e->kept_ev.create(hipEventDisableTiming));
+    if (e->kept_recorded) HIP_TRY(hipStreamWaitEvent(st, e->kept_ev, 0));
+    return 0;
+}
+static int kept_order_end(Engine *e, hipStream_t st)
+{
+    HIP_TRY(hipEventRecord(e->kept_ev, st));
+    e->kept_recorded = true;
+    return 0;
+}
+
+/* h264bsdmiKeepCurrentPictures: the frame buffer of every picture into its instance's kept-picture buffer (allocated here at the first
+ * keep, and at the first after sink_configure dropped it for a change of size), ONE k_keep launch, the same ordering and fence as the
+ * pulls: the next picture decoded into one of these slots waits for the copy. */
+static int keep_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, hipStream_t st, hipEvent_t *fence_ev)
+{
+    if (n > 65535u) return -1;                                          /* grid.y */
+    if (!pull_pictures_ok(n, pics, true, false)) return -1;
+    for (uint32_t i = 0; i < n; i++)
+        for (uint32_t k = 0; k < i; k++)
+            if (pics[k].sink == pics[i].sink) return -1;                /* one kept picture per instance */
+    if (pull_begin_locked(e, n, pics, n)) return -1;
+    if (kept_order_begin(e, st)) return -1;
+    h264k::KeepItem *items = e->titems.host<h264k::KeepItem>();
+    uint32_t largest = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        StreamCtx *s = static_cast<SinkUser *>(pics[i].sink->user)->s;
+        if (!s->d_kept) {
+            HIP_TRY(s->d_kept.alloc(s->frame_bytes));
+            s->kept_wmb = s->wmb; s->kept_hmb = s->hmb;
+        }
+        items[i] = h264k::KeepItem{ s->d_frames + (size_t)pics[i].slot * s->frame_bytes, s->d_kept.get(), s->frame_bytes };
+        largest = std::max(largest, s->frame_bytes);
+    }
+    const uint32_t chunks = std::min((largest / 16u + 1023u) / 1024u, h264k::KEEP_MAX_CHUNKS);     /* about four 16-byte moves per lane */
+    if (pull_wait_pictures(e, n, pics, st)) return -1;
+    hipLaunchKernelGGL(h264k::k_keep, dim3(std::max(chunks, 1u), n), dim3(256), 0, st, e->titems.dev<h264k::KeepItem>());
+    HIP_TRY(hipGetLastError());
+    if (pull_end_locked(e, n, pics, st, fence_ev)) return -1;
+    return kept_order_end(e, st);
+}
+
+/* h264bsdmiOutputRegionChange: one ChangeItem per region, the current picture and the kept picture of its instance at box ∩ window,
+ * ONE k_region_change launch of S row bands per region, S chosen as in stats_out_locked; with S > 1 the bands meet in the same
+ * scratch.  A picture whose instance has no kept picture of its coded size is refused (api.c names only instances that have one). */
+static int change_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, uint32_t n_regs, const SinkRegion *regs,
+                             const h264bsdmi_change_spec &sp, hipStream_t st, hipEvent_t *fence_ev)
+{
+    static const void *const fns[3][2] = {
+        { reinterpret_cast<const void *>(&h264k::k_region_change<h264k::ST_Y, false>), reinterpret_cast<const void *>(&h264k::k_region_change<h264k::ST_Y, true>) },
+        { reinterpret_cast<const void *>(&h264k::k_region_change<h264k::ST_YCBCR, false>), reinterpret_cast<const void *>(&h264k::k_region_change<h264k::ST_YCBCR, true>) },
+        { reinterpret_cast<const void *>(&h264k::k_region_change<h264k::ST_RGB, false>), reinterpret_cast<const void *>(&h264k::k_region_change<h264k::ST_RGB, true>) } };
+    uint32_t shift = 8u;
+    while (shift > 0u && (256u >> shift) != sp.bins) shift--;               /* bins == 256 >> shift; shift == 0 also stands for "no such shift" */
+    if (!sp.data || (reinterpret_cast<uintptr_t>(sp.data) & 7u) || sp.source > H264BSDMI_STATS_RGB || sp.crop > 1u || sp.keep_after > 1u) return -1;
+    if (sp.bins && (sp.bins < 16u || (256u >> shift) != sp.bins)) return -1;
+    if (sp.threshold[0] > 255u || sp.threshold[1] > 255u || sp.threshold[2] > 255u) return -1;
+    if (n_regs > 65535u) return -1;                                     /* grid.y */
+    if (!pull_pictures_ok(n, pics, true, false) || !pull_regions_ok(n, n_regs, regs, 1u, 1u)) return -1;
+    for (uint32_t i = 0; i < n; i++) {
+        const StreamCtx *s = pic_stream(pics[i]);
+        if (!s->d_kept || s->kept_wmb != s->wmb || s->kept_hmb != s->hmb) return -1;
+    }
+    if (pull_begin_locked(e, n, pics, n_regs)) return -1;
+    h264k::ChangeItem *items = e->titems.host<h264k::ChangeItem>();
+    const uint32_t stride = h264k::change_record_bytes(sp.source == H264BSDMI_STATS_Y ? 1u : 3u, sp.bins);
+    uint32_t tallest = 1u;
+    for (uint32_t r = 0; r < n_regs; r++) {
+        const SinkRegion &g = regs[r];
+        const SinkTensorPic &p = pics[g.pic];
+        const StreamCtx *s = pic_stream(p);
+        const int64_t bx0 = std::max<int64_t>(g.x, 0), bx1 = std::min<int64_t>((int64_t)g.x + g.w, p.w);
+        const int64_t by0 = std::max<int64_t>(g.y, 0), by1 = std::min<int64_t>((int64_t)g.y + g.h, p.h);
+        h264k::ChangeItem it{ s->d_frames + (size_t)p.slot * s->frame_bytes, s->d_kept.get(), static_cast<uint8_t *>(sp.data) + (size_t)g.index * stride,
+                              s->wmb, 0u, 0u, 0u, 0u };
+        if (bx1 > bx0 && by1 > by0) {
+            it.x0 = p.x0 + (uint32_t)bx0; it.x1 = p.x0 + (uint32_t)bx1;
+            it.y0 = p.y0 + (uint32_t)by0; it.y1 = p.y0 + (uint32_t)by1;
+            tallest = std::max(tallest, ((it.y1 + 15u) >> 4) - (it.y0 >> 4));
+        }
+        items[r] = it;
+    }
+    const uint32_t S = n_regs >= h264k::STATS_MAX_PARTIALS ? 1u : std::min(h264k::STATS_MAX_PARTIALS / n_regs, tallest);
+    h264k::ChangeArgs cargs{ e->titems.dev<h264k::ChangeItem>(), nullptr, nullptr, sp.bins, sp.bins ? shift : 0u, { sp.threshold[0], sp.threshold[1], sp.threshold[2] } };
+    if (S > 1u && stats_scratch_locked(e, st, &cargs.tickets, &cargs.partials)) return -1;
+    if (kept_order_begin(e, st)) return -1;
+    if (pull_launch_locked(e, n, pics, st, fns[sp.source][sp.bins != 0u], dim3(S, n_regs), &cargs, fence_ev)) return -1;
+    if (S > 1u) HIP_TRY(hipEventRecord(e->stats_ev, st));
+    return kept_order_end(e, st);
 }
 
 /* h264bsdmiOutputTensorRemap: the current pictures of the n instances sampled through n_maps coordinate maps by one k_tensor_remap
@@ -1439,7 +1561,7 @@ static int remap_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, ui
     return pull_launch_locked(e, n, pics, st, fn, pull_grid(t.width, t.height, h264k::TRM_COLS, h264k::TRM_ROWS, n_maps), &rargs, fence_ev);
 }
 
-/* What JobSink.tensor_out, tensor_regions, motion_regions, tensor_remap and region_stats share: one engine (one device) per call, its mutex, the
+/* What JobSink.tensor_out, tensor_regions, motion_regions, tensor_remap, region_stats, keep_pictures and region_change share: one engine (one device) per call, its mutex, the
  * refusal of a capturing stream, and, when the caller gave no stream, the wait for the fence and the device's error words.
  * body(e, st, &fence_ev): the call's own *_out_locked. */
 template <typename Body> static int sink_tensor_call(uint32_t n, const SinkTensorPic *pics, void *stream, Body body)
@@ -1511,6 +1633,21 @@ int sink_region_stats(uint32_t n, const SinkTensorPic *pics, uint32_t n_regions,
         return stats_out_locked(e, n, pics, n_regions, regions, *spec, st, fence_ev);
     });
 }
+int sink_keep_pictures(uint32_t n, const SinkTensorPic *pics, void *stream)
+{
+    return sink_tensor_call(n, pics, stream, [&](Engine *e, hipStream_t st, hipEvent_t *fence_ev) {
+        return keep_out_locked(e, n, pics, st, fence_ev);
+    });
+}
+int sink_region_change(uint32_t n, const SinkTensorPic *pics, uint32_t n_regions, const SinkRegion *regions,
+                       const h264bsdmi_change_spec *spec, void *stream)
+{
+    if (!n_regions) return 0;
+    if (!regions || !spec) return -1;
+    return sink_tensor_call(n, pics, stream, [&](Engine *e, hipStream_t st, hipEvent_t *fence_ev) {
+        return change_out_locked(e, n, pics, n_regions, regions, *spec, st, fence_ev);
+    });
+}
 /* JobSink.set_motion (h264bsdmiSetMotionExport): before the instance's first sequence is configured */
 int sink_set_motion(void *user, int on)
 {
@@ -1552,6 +1689,8 @@ int eng_attach(JobSink *sink)
     sink->tensor_remap = sink_tensor_remap;
     sink->region_stats = sink_region_stats;
     sink->set_motion = sink_set_motion;
+    sink->keep_pictures = sink_keep_pictures;
+    sink->region_change = sink_region_change;
     return 0;
 }
 

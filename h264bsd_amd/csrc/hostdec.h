@@ -221,6 +221,7 @@ struct h264bsdmi_resize_spec;
 struct h264bsdmi_motion_spec;
 struct h264bsdmi_remap_spec;
 struct h264bsdmi_stats_spec;
+struct h264bsdmi_change_spec;
 struct JobSink;
 /* one picture of a batched tensor pull (JobSink.tensor_out): the frame buffer `slot` of the instance behind `sink`, its window
  * (x0, y0, w, h), and the picture's index in the output tensor */
@@ -298,6 +299,14 @@ typedef struct JobSink {
      * — h264bsdmiOutputRegionStats.  0 = ok; <0 = error, nothing enqueued */
     int (*region_stats)(uint32_t n, const SinkTensorPic *pics, uint32_t n_regions, const SinkRegion *regions,
                         const struct h264bsdmi_stats_spec *spec, void *stream);
+    /* optional: the whole frame buffer of each of the n pictures (distinct instances; of pics[i] the sink and the slot are used) into
+     * its instance's kept-picture buffer, which the sink owns, with one launch — h264bsdmiKeepCurrentPictures.  0 = ok; <0 = error */
+    int (*keep_pictures)(uint32_t n, const SinkTensorPic *pics, void *stream);
+    /* optional: integer statistics of (picture - its instance's kept picture) over the same regions, record `index` of spec->data
+     * each, with one launch — h264bsdmiOutputRegionChange.  Every picture's instance has a kept picture of its coded size; the sink
+     * does not look at spec->keep_after (the caller follows up with keep_pictures).  0 = ok; <0 = error, nothing enqueued */
+    int (*region_change)(uint32_t n, const SinkTensorPic *pics, uint32_t n_regions, const SinkRegion *regions,
+                         const struct h264bsdmi_change_spec *spec, void *stream);
 } JobSink;
 
 /* ---------------------------------------------------------------- decoder instance */

@@ -317,6 +317,53 @@ int h264bsdmiOutputRegionStats(u32 n, storage_t *const *pStorage, u32 nRegions, 
                                const h264bsdmi_stats_spec *spec, void *stream,
                                u32 *got, u32 *current, u32 *picId);
 
+/* Kept pictures: one picture per instance that the library holds on to, for h264bsdmiOutputRegionChange below.  A frame buffer stops
+ * being current at the next decode call and is decoded into a few pictures later; this call copies the CURRENT picture (above) of
+ * each of n distinct instances — the whole coded frame, as it lies on the device — into that instance's kept-picture buffer, with
+ * one launch for the call.  The buffer is one frame, owned by the library, allocated at the instance's first keep: instances that never
+ * keep pay nothing.  kept[i] = 1 when instance i had a current picture and it was copied, else 0: a picture kept earlier then stays
+ * as it was.  picId (may be NULL): the picId of the picture instance i now keeps, or 0.
+ * The kept picture survives decoding, popping and h264bsdFlushBuffer.  It is dropped at h264bsdShutdown / h264bsdInit and when a
+ * sequence of another coded size is activated; a new sequence of the same coded size keeps it.
+ * The stream rule and the fence are those of the pulls of current pictures: not capturing; NULL: the library's own stream, and the call
+ * waits; the next decode into the source frame buffer waits for the copy, not for the caller.
+ * -1, before anything is enqueued: pStorage NULL or kept NULL with n > 0, an instance in capture mode, repeated instances, a
+ * capturing stream.  -2: the engine failed, nothing is marked kept and nothing is written.  n == 0 returns 0. */
+int h264bsdmiKeepCurrentPictures(u32 n, storage_t *const *pStorage, void *stream, u32 *kept, u32 *picId);
+
+/* Change statistics: integer statistics of (current picture - kept picture) over boxes, computed where the two pictures lie, with one
+ * launch — did anything change since the last picture or since the background I stored, is the feed frozen, is this a cut or only a
+ * brightness shift, what is the PSNR against the picture I kept — without pulling a pixel.  A sibling of h264bsdmiOutputRegionStats:
+ * the same region struct and limits, the same source window (spec->crop), regions == NULL with nRegions == n meaning whole windows,
+ * the same sources — the channels exactly as region statistics defines them; RGB is the reference conversion of each picture, then
+ * the difference —, the same stream rule and fence, nRegions <= 65535.  It pops nothing and may be repeated.
+ * Record r is written at spec->data + r * stride, stride = 8 + 32 C + 4 C B bytes, little endian; d = current - kept per channel at
+ * every luma position of box ∩ window:
+ *     u32 count; u32 zero;
+ *     C x { u64 sad; u64 ssd; i64 sum; u32 max; u32 above; }     sum of |d|, of d * d, of d (signed); max |d|; #(|d| > threshold[c])
+ *     C x B x u32 hist                                           of |d|: hist[c][|d| >> (8 - log2 B)]; every hist[c] sums to count
+ * count == 0 (the box misses the window): all zeros.  Everything is an integer and exact.  The call writes the WHOLE record with plain
+ * stores: the caller does not clear it.  got[r] = 1 only when the region's instance has a current picture AND a kept one; otherwise 0,
+ * and record r is untouched.  current, kept, picId, keptPicId: per instance, each may be NULL; kept / keptPicId report what the
+ * comparison saw.
+ * keep_after = 1: behind the comparison, on the same stream, the current picture of every instance of the call that has one becomes
+ * its kept picture (one more launch), whether or not it had a kept picture before: a per-tick loop starts itself, call t gives the
+ * difference to the picture of call t - 1.
+ * -1, before anything is enqueued, nothing written: everything h264bsdmiOutputRegionStats refuses in regions, instances, stream,
+ * data and bins; source > 2; crop > 1; a threshold above 255; keep_after > 1.  -2: the engine failed: nothing is written by the
+ * host and nothing is marked kept. */
+typedef struct h264bsdmi_change_spec {
+    void *data;          /* DEVICE pointer, caller-owned, 8-byte aligned: record r at data + r * stride */
+    u32   source;        /* H264BSDMI_STATS_* */
+    u32   bins;          /* 0 (no histogram), 16, 32, 64, 128 or 256: bin = |d| >> (8 - log2 bins) */
+    u32   crop;          /* as h264bsdmi_tensor_spec.crop */
+    u32   threshold[3];  /* per channel, 0..255 (STATS_Y: [0] only) */
+    u32   keep_after;    /* 0 / 1 */
+} h264bsdmi_change_spec;
+int h264bsdmiOutputRegionChange(u32 n, storage_t *const *pStorage, u32 nRegions, const h264bsdmi_region *regions,
+                                const h264bsdmi_change_spec *spec, void *stream,
+                                u32 *got, u32 *current, u32 *kept, u32 *picId, u32 *keptPicId);
+
 /* ---- host parse pipeline at scale ----
  * h264bsdDecode() consumes one NAL unit of one stream per call; a caller that feeds hundreds of streams needs the
  * loop of posix/test_h264bsd.c:146-177 for each of them and its own threading.  These entry points move both into
