@@ -28,7 +28,7 @@ EXPORTED_SYMBOLS = [
     "h264bsdCroppingParams", "h264bsdSampleAspectRatio", "h264bsdCheckValidParamSets", "h264bsdFlushBuffer",
     "h264bsdProfile", "h264bsdAlloc", "h264bsdFree", "h264bsdConvertToRGBA", "h264bsdConvertToBGRA",
     "h264bsdConvertToYCbCrA",
-    "h264bsdmiInitCapture", "h264bsdmiNextOutputInfo", "h264bsdmiNextOutputPictureDevice", "h264bsdmiNextOutputTensorBatch", "h264bsdmiNextOutputTensorBatchColour", "h264bsdmiNextOutputTensorBatchResize", "h264bsdmiOutputTensorRegions", "h264bsdmiOutputTensorRemap", "h264bsdmiSetMotionExport", "h264bsdmiOutputMotionRegions", "h264bsdmiOutputRegionStats", "h264bsdmiKeepCurrentPictures", "h264bsdmiOutputRegionChange", "h264bsdmiJobFinalize", "h264bsdmiDeviceCount", "h264bsdmiSetDevice", "h264bsdmiFlush", "h264bsdmiFlushAsync", "h264bsdmiDeviceErrors",
+    "h264bsdmiInitCapture", "h264bsdmiNextOutputInfo", "h264bsdmiNextOutputPictureDevice", "h264bsdmiNextOutputTensorBatch", "h264bsdmiNextOutputTensorBatchColour", "h264bsdmiNextOutputTensorBatchResize", "h264bsdmiOutputTensorRegions", "h264bsdmiOutputTensorRemap", "h264bsdmiSetMotionExport", "h264bsdmiOutputMotionRegions", "h264bsdmiOutputRegionStats", "h264bsdmiKeepCurrentPictures", "h264bsdmiOutputRegionChange", "h264bsdmiOutputCellMaps", "h264bsdmiJobFinalize", "h264bsdmiDeviceCount", "h264bsdmiSetDevice", "h264bsdmiFlush", "h264bsdmiFlushAsync", "h264bsdmiDeviceErrors",
     "h264bsdmiDecodePicture", "h264bsdmiDecodePictureBatch", "h264bsdmiNextOutputPictureBatch", "h264bsdmiPullAndDecodePictureBatch", "h264bsdmiSetParserThreads", "h264bsdmiSetInputReadOnly", "h264bsdmiSetCopyElision",
     "h264bsdmiReplayCreate", "h264bsdmiReplayCreateStaggered", "h264bsdmiReplayCreateDesync", "h264bsdmiReplayCreateSched", "h264bsdmiReplayReschedule", "h264bsdmiReplayDestroy", "h264bsdmiReplayRun", "h264bsdmiReplaySync",
     "h264bsdmiReplayFetch", "h264bsdmiReplayChecksums", "h264bsdmiReplayConvert", "h264bsdmiReplayFetchConverted",
@@ -95,6 +95,16 @@ class ChangeSpec(ctypes.Structure):
                 ("threshold", ctypes.c_uint32 * 3), ("keep_after", ctypes.c_uint32)]
 
 
+class CellsSpec(ctypes.Structure):
+    """h264bsdmi_cells_spec (include/h264bsd_mi355x.h)"""
+    _fields_ = [("data", ctypes.c_void_p), ("cols", ctypes.c_uint32), ("rows", ctypes.c_uint32), ("cell", ctypes.c_uint32),
+                ("source", ctypes.c_uint32), ("crop", ctypes.c_uint32), ("mode", ctypes.c_uint32), ("planes", ctypes.c_uint32),
+                ("threshold", ctypes.c_uint32 * 3), ("keep_after", ctypes.c_uint32)]
+
+
+# per mode (H264BSDMI_CELLS_PICTURE, _CHANGE): name -> H264BSDMI_CELL_*, in the order of the maps
+CELL_PLANES = ({"count": 1, "sum": 2, "sumsq": 4, "min": 8, "max": 16}, {"count": 1, "sad": 2, "ssd": 4, "dsum": 8, "dmax": 16, "above": 32})
+CELL_SIZES = (4, 8, 16, 32, 64)
 STATS_SOURCES = {"y": (0, 1), "ycbcr": (1, 3), "rgb": (2, 3)}                    # name -> (H264BSDMI_STATS_*, channels)
 STATS_BINS = (0, 16, 32, 64, 128, 256)
 MOTION_PLANES = {"mv": (1, 2), "valid": (2, 1), "age": (4, 1), "qp": (8, 1)}     # name -> (H264BSDMI_MOTION_PLANE_*, channels), in channel order
@@ -233,6 +243,9 @@ def _declare(L, harness):
     L.h264bsdmiOutputRegionChange.argtypes = [u32, ctypes.POINTER(vp), u32, ctypes.POINTER(Region), ctypes.POINTER(ChangeSpec), vp,
                                               P32, P32, P32, P32, P32]
     L.h264bsdmiOutputRegionChange.restype = ctypes.c_int
+    L.h264bsdmiOutputCellMaps.argtypes = [u32, ctypes.POINTER(vp), u32, ctypes.POINTER(Region), ctypes.POINTER(CellsSpec), vp,
+                                          P32, P32, P32, P32, P32]
+    L.h264bsdmiOutputCellMaps.restype = ctypes.c_int
     L.h264bsdmiDecodePicture.argtypes = [vp, u8p, u32, u32, P32, P32]
     L.h264bsdmiDecodePicture.restype = u32
     L.h264bsdmiDecodePictureBatch.argtypes = [u32, ctypes.POINTER(vp), ctypes.POINTER(vp), P32, P32, P32, P32, P32]
@@ -942,6 +955,77 @@ def pull_change(decoders, regions=None, source="y", bins=0, threshold=0, crop=Tr
             raise RuntimeError(f"h264bsdmiOutputRegionChange failed ({rc})")
     cur, kept, ids, kept_ids = [list(a)[:n] for a in per]
     return RegionChange(out, C, bins, list(got)[:K], cur, kept, ids, kept_ids)
+
+
+class CellMaps:
+    """what pull_cells returns: maps [R, P, rows, cols] int32, the C layout, and views of it by name: count [R, rows, cols]; per
+    requested plane (PICTURE: sum, sumsq, min, max; CHANGE: sad, ssd, dsum, dmax, above) [R, C, rows, cols]; a plane of the mode that
+    was not requested is None.  got [R], and per decoder current, kept, pic_id, kept_pic_id, lists of ints"""
+
+    def __init__(self, maps, mode, C, planes, got, current, kept, pic_id, kept_pic_id):
+        self.maps, self.mode, self.planes = maps, mode, planes
+        at = 0
+        for name, bit in CELL_PLANES[mode].items():
+            width = 0 if not planes & bit else 1 if bit == 1 else C
+            view = None if not width else maps[:, at] if bit == 1 else maps[:, at:at + C]
+            setattr(self, name, view)
+            at += width
+        self.got, self.current, self.kept, self.pic_id, self.kept_pic_id = got, current, kept, pic_id, kept_pic_id
+
+
+def pull_cells(decoders, regions=None, cell=16, grid=None, source="y", planes=("count", "sum"), against=None, threshold=0, crop=True,
+               keep=False, out=None, stream=None):
+    """h264bsdmiOutputCellMaps: dense integer maps, one value per cell x cell luma samples, over boxes of the decoders' CURRENT pictures,
+    computed by one kernel launch where the pictures lie.  regions, source, crop and stream as for pull_stats.  cell: 4, 8, 16, 32 or 64.
+    grid: (rows, cols) of every slice; None: (ceil(h / cell), ceil(w / cell)) of the largest box (regions=None: source window) of the
+    call.  against=None: statistics of the picture, planes out of "count", "sum", "sumsq", "min", "max"; against="kept": of d = current -
+    kept picture (keep_pictures), planes out of "count", "sad", "ssd", "dsum", "dmax", "above" (#|d| > threshold: one int 0..255 or one
+    per channel); keep=True: behind the comparison the current pictures become the kept ones, as for pull_change.  Cell (i, j) of a
+    region holds what pull_stats / pull_change give for the box (x + j cell, y + i cell, min(cell, w - j cell), min(cell, h - i cell));
+    cells the box or the window do not reach have count 0.  out: a contiguous CUDA int32 tensor [R, P, rows, cols] to write into;
+    slices of decoders without a current (against="kept": or kept) picture are left untouched (got[r] = 0).  Returns a CellMaps."""
+    import torch
+    n = len(decoders)
+    if against not in (None, "kept"):
+        raise ValueError(f"pull_cells: against is None or 'kept', not {against}")
+    mode = 1 if against == "kept" else 0
+    if source not in STATS_SOURCES or cell not in CELL_SIZES:
+        raise ValueError(f"pull_cells: unsupported source / cell {source} {cell}")
+    src, C = STATS_SOURCES[source]
+    names = (planes,) if isinstance(planes, str) else tuple(planes)
+    if not names or any(p not in CELL_PLANES[mode] for p in names):
+        raise ValueError(f"pull_cells: planes is a non-empty choice of {tuple(CELL_PLANES[mode])}, not {planes}")
+    bits = sum({CELL_PLANES[mode][p] for p in names})
+    thr = [threshold] * 3 if isinstance(threshold, int) else list(threshold) + [0] * (3 - C) if isinstance(threshold, (tuple, list)) else []
+    if len(thr) != 3 or not all(isinstance(t, int) and 0 <= t <= 255 for t in thr):
+        raise ValueError(f"pull_cells: threshold is one int in 0..255, or one per channel, not {threshold}")
+    if not mode and (any(thr) or keep):
+        raise ValueError("pull_cells: threshold and keep need against='kept'")
+    K, regs = _regions_arg("pull_cells", n, regions)
+    if grid is None:
+        if regs is not None:
+            sizes = [(r.h, r.w) for r in regs[:K]]
+        else:
+            sizes = []
+            for d in decoders:
+                flag, _, cw, _, ch = d.cropping_params()
+                sizes.append((ch, cw) if crop and flag else (16 * d.pic_height(), 16 * d.pic_width()))
+        grid = (max([-(-h // cell) for h, _ in sizes] + [1]), max([-(-w // cell) for _, w in sizes] + [1]))
+    if not (isinstance(grid, (tuple, list)) and len(grid) == 2 and all(isinstance(g, int) and 1 <= g <= 4096 for g in grid)):
+        raise ValueError(f"pull_cells: grid is (rows, cols), 1..4096 each, not {grid}")
+    P = (bits & 1) + C * bin(bits >> 1).count("1")
+    shape = (K, P, grid[0], grid[1])
+    out, stream = _out_and_stream("pull_cells", out, shape, torch.int32, stream)
+    spec = CellsSpec(out.data_ptr(), grid[1], grid[0], cell, src, 1 if crop else 0, mode, bits, (ctypes.c_uint32 * 3)(*thr), 1 if keep else 0)
+    got = (ctypes.c_uint32 * max(K, 1))()
+    per = [(ctypes.c_uint32 * max(n, 1))() for _ in range(4)]                # current, kept, picId, keptPicId
+    if n and K:
+        rc = api_lib().h264bsdmiOutputCellMaps(n, (ctypes.c_void_p * n)(*[d._st for d in decoders]), K, regs, ctypes.byref(spec),
+                                               stream.cuda_stream, got, *per)
+        if rc != 0:
+            raise RuntimeError(f"h264bsdmiOutputCellMaps failed ({rc})")
+    cur, kept, ids, kept_ids = [list(a)[:n] for a in per]
+    return CellMaps(out, mode, C, bits, list(got)[:K], cur, kept, ids, kept_ids)
 
 
 def job_header(blob):

@@ -362,15 +362,15 @@ int h264bsdmiNextOutputTensorBatchResize(u32 n, storage_t *const *dec, const h26
 }
 
 /* ---- The pulls of CURRENT pictures (pop_output, drop_current): h264bsdmiOutputTensorRegions, h264bsdmiOutputTensorRemap,
- * h264bsdmiOutputMotionRegions, h264bsdmiOutputRegionStats, h264bsdmiOutputRegionChange (which needs the kept picture as well), and
- * their small sibling h264bsdmiKeepCurrentPictures (the picture list only).  Each checks its own spec; everything else is one path:
+ * h264bsdmiOutputMotionRegions, h264bsdmiOutputRegionStats, h264bsdmiOutputRegionChange (which needs the kept picture as well),
+ * h264bsdmiOutputCellMaps (which needs it in CHANGE mode), and their small sibling h264bsdmiKeepCurrentPictures (the picture list only).  Each checks its own spec; everything else is one path:
  *   regions_refused   got, the count and the range of every region — before the instances are looked at
  *   pull_begin        dec and the instances (of this library, with the sink entry the call needs, distinct), then the lists
  *   pull_pic          an instance's current picture in the picture list, appended at its first use
  *   pull_regions      the regions (or one whole window per instance) of the pictures that exist, each with its rectangle
  *   pull_finish       after the sink: got, box, current and picId — unless the sink failed (-2 writes nothing) — and the lists freed
  * A refused call returns -1 and has called no sink, written nothing; no call pops anything. */
-enum { PULL_REGIONS, PULL_REMAP, PULL_MOTION, PULL_STATS, PULL_CHANGE, PULL_KEEP };
+enum { PULL_REGIONS, PULL_REMAP, PULL_MOTION, PULL_STATS, PULL_CHANGE, PULL_KEEP, PULL_CELLS };
 #define NO_PIC 0xFFFFFFFFu
 typedef struct CurrentPull {
     u32 n, m, k;                /* instances; pictures and items gathered so far */
@@ -380,6 +380,7 @@ typedef struct CurrentPull {
     SinkRegion *regs;           /* the items for the sink: regions, or (PULL_REMAP) maps */
     SinkRemap *maps;
     int kind;                   /* PULL_* */
+    int vs_kept;                /* only instances that have a kept picture too: PULL_CHANGE, and PULL_CELLS in CHANGE mode */
 } CurrentPull;
 
 /* regions == NULL: no regions at all, or (whole: one whole window per instance) exactly n */
@@ -406,6 +407,7 @@ static int sink_pulls(const ApiDec *a, int kind)
     case PULL_STATS:  return k->tensor_regions != NULL && k->region_stats != NULL;
     case PULL_CHANGE: return k->tensor_regions != NULL && k->region_change != NULL && k->keep_pictures != NULL;
     case PULL_KEEP:   return k->tensor_regions != NULL && k->keep_pictures != NULL;
+    case PULL_CELLS:  return k->tensor_regions != NULL && k->cell_maps != NULL;      /* CHANGE mode: keep_pictures too (the entry asks) */
     }
     return k->tensor_regions != NULL;
 }
@@ -421,18 +423,18 @@ static int pull_begin(CurrentPull *c, u32 n, storage_t *const *dec, u32 n_items,
     }
     *c = (CurrentPull){ n, 0, 0, dec, (SinkTensorPic *)malloc((n ? n : 1) * sizeof(SinkTensorPic)), (u32 *)malloc((n ? n : 1) * sizeof(u32)),
                         kind == PULL_REMAP ? NULL : (SinkRegion *)malloc((n_items ? n_items : 1) * sizeof(SinkRegion)),
-                        kind == PULL_REMAP ? (SinkRemap *)malloc((n_items ? n_items : 1) * sizeof(SinkRemap)) : NULL, kind };
+                        kind == PULL_REMAP ? (SinkRemap *)malloc((n_items ? n_items : 1) * sizeof(SinkRemap)) : NULL, kind, kind == PULL_CHANGE };
     if (!c->pics || !c->pic_of || !(c->regs || c->maps)) { pull_free(c); return -1; }
     for (u32 i = 0; i < n; i++) c->pic_of[i] = NO_PIC;
     return 0;
 }
-/* the index in pics of instance inst's current picture, NO_PIC when it has none (got = 0 for what names it); PULL_CHANGE: when it has
+/* the index in pics of instance inst's current picture, NO_PIC when it has none (got = 0 for what names it); vs_kept: when it has
  * no kept picture either */
 static u32 pull_pic(CurrentPull *c, u32 inst, const h264bsdmi_tensor_spec *spec, const h264bsdmi_colour_spec *colour)
 {
     const ApiDec *a = dec_of(c->dec[inst]);
     if (!a->has_cur || !a->hd->active_sps) return NO_PIC;
-    if (c->kind == PULL_CHANGE && !has_kept_picture(a)) return NO_PIC;
+    if (c->vs_kept && !has_kept_picture(a)) return NO_PIC;
     if (c->pic_of[inst] == NO_PIC) {
         c->pic_of[inst] = c->m;
         tensor_pic(&c->pics[c->m++], a, a->cur.slot, inst, spec, colour);
@@ -604,6 +606,50 @@ int h264bsdmiOutputRegionChange(u32 n, storage_t *const *dec, u32 nRegions, cons
     const h264bsdmi_tensor_spec window = { spec->data, 1, 1, 0, 0, 0, spec->crop, 1, { 0, 0, 0 }, { 1, 1, 1 } };
     pull_regions(&c, nRegions, regions, &window, &REFERENCE_COLOUR, 1, 1, 0);
     int failed = c.k && c.pics[0].sink->region_change(c.m, c.pics, c.k, c.regs, spec, stream);
+    if (spec->keep_after && !failed) failed = k.m && k.pics[0].sink->keep_pictures(k.m, k.pics, stream);
+    if (!failed) {
+        for (u32 i = 0; i < n; i++) {
+            const ApiDec *a = dec_of(dec[i]);
+            if (kept) kept[i] = has_kept_picture(a) ? 1 : 0;
+            if (keptPicId) keptPicId[i] = has_kept_picture(a) ? a->kept_id : 0;
+        }
+        if (spec->keep_after) mark_kept(&k);
+    }
+    if (spec->keep_after) pull_free(&k);
+    return pull_finish(&c, failed, nRegions, got, NULL, current, picId);
+}
+
+/* Dense per-cell maps of h264bsdmiOutputRegionStats' (PICTURE) or h264bsdmiOutputRegionChange's (CHANGE) quantities over the same
+ * regions: the host path of the one or of the other, the mode carried by CurrentPull.vs_kept */
+static int cells_spec_refused(const h264bsdmi_cells_spec *s)
+{
+    const u32 allowed = s && s->mode == H264BSDMI_CELLS_CHANGE
+        ? H264BSDMI_CELL_COUNT | H264BSDMI_CELL_SAD | H264BSDMI_CELL_SSD | H264BSDMI_CELL_DSUM | H264BSDMI_CELL_DMAX | H264BSDMI_CELL_ABOVE
+        : H264BSDMI_CELL_COUNT | H264BSDMI_CELL_SUM | H264BSDMI_CELL_SUMSQ | H264BSDMI_CELL_MIN | H264BSDMI_CELL_MAX;
+    if (!s || !s->data || ((uintptr_t)s->data & 3u)) return 1;
+    if (!s->cols || s->cols > 4096u || !s->rows || s->rows > 4096u) return 1;
+    if (s->cell != 4 && s->cell != 8 && s->cell != 16 && s->cell != 32 && s->cell != 64) return 1;
+    if (s->source > H264BSDMI_STATS_RGB || s->crop > 1 || s->mode > H264BSDMI_CELLS_CHANGE || s->keep_after > 1) return 1;
+    if (!s->planes || (s->planes & ~allowed)) return 1;
+    if (s->threshold[0] > 255 || s->threshold[1] > 255 || s->threshold[2] > 255) return 1;
+    if (s->mode == H264BSDMI_CELLS_PICTURE && (s->threshold[0] || s->threshold[1] || s->threshold[2] || s->keep_after)) return 1;
+    return 0;
+}
+int h264bsdmiOutputCellMaps(u32 n, storage_t *const *dec, u32 nRegions, const h264bsdmi_region *regions,
+                            const h264bsdmi_cells_spec *spec, void *stream,
+                            u32 *got, u32 *current, u32 *kept, u32 *picId, u32 *keptPicId)
+{
+    CurrentPull c, k;
+    if (cells_spec_refused(spec)) return -1;
+    const int change = spec->mode == H264BSDMI_CELLS_CHANGE;
+    if (regions_refused(n, nRegions, regions, got, 1) || pull_begin(&c, n, dec, nRegions, PULL_CELLS)) return -1;
+    c.vs_kept = change;
+    for (u32 i = 0; change && i < n; i++)
+        if (!dec_of(dec[i])->hd->sink.keep_pictures) { pull_free(&c); return -1; }
+    if (spec->keep_after && keep_begin(&k, n, dec)) { pull_free(&c); return -1; }
+    const h264bsdmi_tensor_spec window = { spec->data, 1, 1, 0, 0, 0, spec->crop, 1, { 0, 0, 0 }, { 1, 1, 1 } };
+    pull_regions(&c, nRegions, regions, &window, &REFERENCE_COLOUR, 1, 1, 0);
+    int failed = c.k && c.pics[0].sink->cell_maps(c.m, c.pics, c.k, c.regs, spec, stream);
     if (spec->keep_after && !failed) failed = k.m && k.pics[0].sink->keep_pictures(k.m, k.pics, stream);
     if (!failed) {
         for (u32 i = 0; i < n; i++) {

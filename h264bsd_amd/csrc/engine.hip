@@ -39,6 +39,7 @@
 #include "kernels/k_region_stats.hip.h"
 #include "kernels/k_keep.hip.h"
 #include "kernels/k_region_change.hip.h"
+#include "kernels/k_cell_maps.hip.h"
 #include "engine.h"
 #include "hip_owned.h"
 #include "tick_plan.h"
@@ -156,9 +157,11 @@ constexpr unsigned CONVERT_WGS = CONVERT_WGS_N;      /* workgroups per picture o
 constexpr uint32_t LANE_DBK_WAVES = LANE_DBK_WAVES_N;
 
 /* the item stride of the tensor pulls' staging ring: k_tensor_out / k_tensor_resize read TensorItems, k_tensor_aa AaItems, k_tensor_roi
- * RoiItems, k_motion_roi MotionItems, k_tensor_remap RemapItems, k_region_stats StatsItems, k_keep KeepItems, k_region_change ChangeItems */
+ * RoiItems, k_motion_roi MotionItems, k_tensor_remap RemapItems, k_region_stats StatsItems, k_keep KeepItems, k_region_change ChangeItems,
+ * k_cell_maps CellItems */
 constexpr size_t TITEM_BYTES = std::max({ sizeof(h264k::TensorItem), sizeof(h264k::AaItem), sizeof(h264k::RoiItem), sizeof(h264k::MotionItem),
-                                          sizeof(h264k::RemapItem), sizeof(h264k::StatsItem), sizeof(h264k::KeepItem), sizeof(h264k::ChangeItem) });
+                                          sizeof(h264k::RemapItem), sizeof(h264k::StatsItem), sizeof(h264k::KeepItem), sizeof(h264k::ChangeItem),
+                                          sizeof(h264k::CellItem) });
 struct TItemSlot { uint8_t bytes[TITEM_BYTES]; };
 struct Engine {
     std::mutex mu;
@@ -1532,6 +1535,63 @@ static int change_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, u
     return kept_order_end(e, st);
 }
 
+/* h264bsdmiOutputCellMaps: one CellItem per region — the frame, in CHANGE mode the kept frame, the slice, the box's origin (signed) and
+ * box ∩ window in luma samples of the coded frame — and ONE k_cell_maps launch of (rectangles of the grid, regions) workgroups.  Every
+ * cell is owned by one workgroup: no scratch.  CHANGE: the kept pictures' ordering, and a picture whose instance has no kept picture
+ * of its coded size is refused (api.c names only instances that have one). */
+template <int MODE, int SRC> static const void *cells_kernel(bool quad)
+{
+    return quad ? reinterpret_cast<const void *>(&h264k::k_cell_maps<MODE, SRC, true>) : reinterpret_cast<const void *>(&h264k::k_cell_maps<MODE, SRC, false>);
+}
+static int cells_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, uint32_t n_regs, const SinkRegion *regs,
+                            const h264bsdmi_cells_spec &sp, hipStream_t st, hipEvent_t *fence_ev)
+{
+    const bool change = sp.mode == H264BSDMI_CELLS_CHANGE;
+    uint32_t shift = 2u;
+    while (shift < 6u && (1u << shift) != sp.cell) shift++;
+    if (!sp.data || (reinterpret_cast<uintptr_t>(sp.data) & 3u) || (1u << shift) != sp.cell) return -1;
+    if (!sp.cols || sp.cols > h264k::CELLS_MAX_GRID || !sp.rows || sp.rows > h264k::CELLS_MAX_GRID) return -1;
+    if (sp.source > H264BSDMI_STATS_RGB || sp.crop > 1u || sp.mode > H264BSDMI_CELLS_CHANGE || sp.keep_after > 1u) return -1;
+    if (!sp.planes || (sp.planes & ~(change ? 63u : 31u))) return -1;
+    if (sp.threshold[0] > 255u || sp.threshold[1] > 255u || sp.threshold[2] > 255u) return -1;
+    if (!change && (sp.threshold[0] || sp.threshold[1] || sp.threshold[2] || sp.keep_after)) return -1;
+    if (n_regs > 65535u) return -1;                                     /* grid.y */
+    if (!pull_pictures_ok(n, pics, true, false) || !pull_regions_ok(n, n_regs, regs, 1u, 1u)) return -1;
+    for (uint32_t i = 0; change && i < n; i++) {
+        const StreamCtx *s = pic_stream(pics[i]);
+        if (!s->d_kept || s->kept_wmb != s->wmb || s->kept_hmb != s->hmb) return -1;
+    }
+    const uint32_t rw = h264k::CELLS_RECT_W >> shift, rh = h264k::CELLS_RECT_H >> shift;
+    const uint32_t rects_x = (sp.cols + rw - 1u) / rw, rects = rects_x * ((sp.rows + rh - 1u) / rh);
+    if ((uint64_t)rects * n_regs > h264k::CELLS_MAX_WORKGROUPS) return -1;
+    if (pull_begin_locked(e, n, pics, n_regs)) return -1;
+    h264k::CellItem *items = e->titems.host<h264k::CellItem>();
+    const uint32_t channels = sp.source == H264BSDMI_STATS_Y ? 1u : 3u;
+    const size_t slice = ((sp.planes & 1u) + channels * (size_t)__builtin_popcount(sp.planes >> 1)) * sp.rows * sp.cols;      /* words */
+    for (uint32_t r = 0; r < n_regs; r++) {
+        const SinkRegion &g = regs[r];
+        const SinkTensorPic &p = pics[g.pic];
+        const StreamCtx *s = pic_stream(p);
+        const int64_t bx0 = std::max<int64_t>(g.x, 0), bx1 = std::min<int64_t>((int64_t)g.x + g.w, p.w);
+        const int64_t by0 = std::max<int64_t>(g.y, 0), by1 = std::min<int64_t>((int64_t)g.y + g.h, p.h);
+        h264k::CellItem it{ s->d_frames + (size_t)p.slot * s->frame_bytes, change ? s->d_kept.get() : nullptr,
+                            static_cast<uint32_t *>(sp.data) + (size_t)g.index * slice, s->wmb, (int32_t)p.x0 + g.x, (int32_t)p.y0 + g.y, 0u, 0u, 0u, 0u };
+        if (bx1 > bx0 && by1 > by0) {
+            it.x0 = p.x0 + (uint32_t)bx0; it.x1 = p.x0 + (uint32_t)bx1;
+            it.y0 = p.y0 + (uint32_t)by0; it.y1 = p.y0 + (uint32_t)by1;
+        }
+        items[r] = it;
+    }
+    const bool quad = sp.cell >= 16u;
+    const void *const fns[2][3] = {
+        { cells_kernel<0, h264k::ST_Y>(quad), cells_kernel<0, h264k::ST_YCBCR>(quad), cells_kernel<0, h264k::ST_RGB>(quad) },
+        { cells_kernel<1, h264k::ST_Y>(quad), cells_kernel<1, h264k::ST_YCBCR>(quad), cells_kernel<1, h264k::ST_RGB>(quad) } };
+    h264k::CellArgs cargs{ e->titems.dev<h264k::CellItem>(), sp.cols, sp.rows, shift, rects_x, sp.planes, { sp.threshold[0], sp.threshold[1], sp.threshold[2] } };
+    if (change && kept_order_begin(e, st)) return -1;
+    if (pull_launch_locked(e, n, pics, st, fns[sp.mode][sp.source], dim3(rects, n_regs), &cargs, fence_ev)) return -1;
+    return change ? kept_order_end(e, st) : 0;
+}
+
 /* h264bsdmiOutputTensorRemap: the current pictures of the n instances sampled through n_maps coordinate maps by one k_tensor_remap
  * launch, map r into slice maps[r].index.  The fence goes to each distinct instance, so that the next picture decoded into one of
  * these slots waits for this launch.  The maps are the caller's: read on st. */
@@ -1561,7 +1621,7 @@ static int remap_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, ui
     return pull_launch_locked(e, n, pics, st, fn, pull_grid(t.width, t.height, h264k::TRM_COLS, h264k::TRM_ROWS, n_maps), &rargs, fence_ev);
 }
 
-/* What JobSink.tensor_out, tensor_regions, motion_regions, tensor_remap, region_stats, keep_pictures and region_change share: one engine (one device) per call, its mutex, the
+/* What JobSink.tensor_out, tensor_regions, motion_regions, tensor_remap, region_stats, keep_pictures, region_change and cell_maps share: one engine (one device) per call, its mutex, the
  * refusal of a capturing stream, and, when the caller gave no stream, the wait for the fence and the device's error words.
  * body(e, st, &fence_ev): the call's own *_out_locked. */
 template <typename Body> static int sink_tensor_call(uint32_t n, const SinkTensorPic *pics, void *stream, Body body)
@@ -1648,6 +1708,15 @@ int sink_region_change(uint32_t n, const SinkTensorPic *pics, uint32_t n_regions
         return change_out_locked(e, n, pics, n_regions, regions, *spec, st, fence_ev);
     });
 }
+int sink_cell_maps(uint32_t n, const SinkTensorPic *pics, uint32_t n_regions, const SinkRegion *regions,
+                   const h264bsdmi_cells_spec *spec, void *stream)
+{
+    if (!n_regions) return 0;
+    if (!regions || !spec) return -1;
+    return sink_tensor_call(n, pics, stream, [&](Engine *e, hipStream_t st, hipEvent_t *fence_ev) {
+        return cells_out_locked(e, n, pics, n_regions, regions, *spec, st, fence_ev);
+    });
+}
 /* JobSink.set_motion (h264bsdmiSetMotionExport): before the instance's first sequence is configured */
 int sink_set_motion(void *user, int on)
 {
@@ -1691,6 +1760,7 @@ int eng_attach(JobSink *sink)
     sink->set_motion = sink_set_motion;
     sink->keep_pictures = sink_keep_pictures;
     sink->region_change = sink_region_change;
+    sink->cell_maps = sink_cell_maps;
     return 0;
 }
 

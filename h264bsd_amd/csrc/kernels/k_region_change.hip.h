@@ -52,7 +52,11 @@ __device__ __forceinline__ void change_load(const uint8_t *tile, uint32_t lane, 
             v[0] = v[1] = v[2] = 0u;
 #pragma unroll
             for (int k = 0; k < 4; k++) {
-                const uint32_t px = yuv_pixel(0, (int)((yv >> (8 * k)) & 255u), (int)((cb2 >> (8 * (k >> 1))) & 255u), (int)((cr2 >> (8 * (k >> 1))) & 255u));
+                uint32_t px = yuv_pixel(0, (int)((yv >> (8 * k)) & 255u), (int)((cb2 >> (8 * (k >> 1))) & 255u), (int)((cr2 >> (8 * (k >> 1))) & 255u));
+                /* the pixel is opaque from here on: seen through, the shift-and-clamp of two neighbours and their packing below were
+                 * fused into one v_ashr_pk_u8_i32 in k_cell_maps (and nowhere else), whose results on the device differed from
+                 * clip255(x >> 8) in a few samples per picture (docs/EXPERIMENTS.md, "Cell maps") */
+                asm volatile("" : "+v"(px));
                 v[0] |= (px & 255u) << (8 * k);
                 v[1] |= ((px >> 8) & 255u) << (8 * k);
                 v[2] |= ((px >> 16) & 255u) << (8 * k);

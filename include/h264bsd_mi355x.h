@@ -364,6 +364,56 @@ int h264bsdmiOutputRegionChange(u32 n, storage_t *const *pStorage, u32 nRegions,
                                 const h264bsdmi_change_spec *spec, void *stream,
                                 u32 *got, u32 *current, u32 *kept, u32 *picId, u32 *keptPicId);
 
+/* Cell maps: WHERE did the picture change, where is it dark, flat or blown out — dense maps with one value per small square cell of a
+ * box, computed where the pictures lie with one launch, small enough to threshold in torch and turn into the boxes of the calls above.
+ * A sibling of h264bsdmiOutputRegionStats (mode PICTURE) and h264bsdmiOutputRegionChange (mode CHANGE): the same region struct and
+ * limits, negative origins, boxes that leave the window or miss it, regions == NULL with nRegions == n meaning whole windows, the same
+ * source window (spec->crop), the same channels, the current-picture rule, in CHANGE mode the kept-picture rule, got, current, kept,
+ * picId and keptPicId (each may be NULL), the stream rule, the fence and keep_after.
+ * Every region gets a grid of rows x cols cells of cell x cell luma samples laid over its box from the box's origin: cell (i, j),
+ * 0 <= i < rows, 0 <= j < cols, covers the box-relative positions u in [j cell, (j + 1) cell), v in [i cell, (i + 1) cell), intersected
+ * with the box [0, w) x [0, h) and with the window.  THE DEFINITION: cell (i, j) of region (x, y, w, h) holds what the record, at
+ * bins = 0, of h264bsdmiOutputRegionStats (PICTURE) or h264bsdmiOutputRegionChange (CHANGE) holds for the box
+ * (x + j cell, y + i cell, min(cell, w - j cell), min(cell, h - i cell)).  Cells of the box beyond the grid are not reported; cells of
+ * the grid beyond the box or outside the window have count 0, and with count 0 PICTURE gives sum 0, sumsq 0, min 255, max 0 and CHANGE
+ * all zeros.
+ * Slice r is written at (u32 *)spec->data + r * P * rows * cols: P maps of rows x cols u32 each, row-major, in this order: COUNT if
+ * asked, then per set bit of spec->planes in ascending order C maps, in the channel order of the source.  The call writes the WHOLE
+ * slice with plain stores: the caller does not clear it.  Everything is exact: the largest value is 64 * 64 * 255^2 < 2^31, which
+ * is why cell stops at 64 and why u32 (int32 in torch) suffices; DSUM is an i32 in two's complement.  got[r] = 0 (no current picture;
+ * CHANGE: or no kept one): slice r is untouched.
+ * -1, before anything is enqueued, nothing written: everything h264bsdmiOutputRegionStats refuses in regions, instances and stream;
+ * spec or data NULL or data not 4-byte aligned; cols or rows 0 or above 4096; a cell not in {4, 8, 16, 32, 64}; source > 2; crop > 1;
+ * mode > 1; planes 0 or with bits outside the mode's set; a threshold above 255; PICTURE with a non-zero threshold or keep_after;
+ * keep_after > 1.  -2: the engine failed (also: more than 2^23 workgroups — 128 x 64 luma samples of grid each, times the regions —
+ * in one call): nothing is written by the host and nothing is marked kept.  nRegions == 0 returns 0 and launches nothing. */
+#define H264BSDMI_CELLS_PICTURE 0      /* statistics of the current picture            */
+#define H264BSDMI_CELLS_CHANGE  1      /* of d = current - kept, as region change      */
+#define H264BSDMI_CELL_COUNT  1u       /* 1 map, both modes                            */
+/* PICTURE, C maps each: */
+#define H264BSDMI_CELL_SUM    2u
+#define H264BSDMI_CELL_SUMSQ  4u
+#define H264BSDMI_CELL_MIN    8u
+#define H264BSDMI_CELL_MAX    16u
+/* CHANGE, C maps each: */
+#define H264BSDMI_CELL_SAD    2u       /* sum |d|  */
+#define H264BSDMI_CELL_SSD    4u       /* sum d*d  */
+#define H264BSDMI_CELL_DSUM   8u       /* sum d, i32 two's complement */
+#define H264BSDMI_CELL_DMAX   16u      /* max |d|  */
+#define H264BSDMI_CELL_ABOVE  32u      /* #(|d| > threshold[c]) */
+typedef struct h264bsdmi_cells_spec {
+    void *data;            /* DEVICE, caller-owned, 4-byte aligned: slice r at data + r * P*rows*cols u32 */
+    u32 cols, rows;        /* grid of every slice, 1..4096 each */
+    u32 cell;              /* 4, 8, 16, 32 or 64 luma samples a side */
+    u32 source, crop;      /* H264BSDMI_STATS_*; as everywhere */
+    u32 mode, planes;      /* planes: non-empty subset of the mode's bits */
+    u32 threshold[3];      /* CHANGE: 0..255 per channel; PICTURE: must be 0 */
+    u32 keep_after;        /* CHANGE: 0 / 1 as h264bsdmiOutputRegionChange; PICTURE: must be 0 */
+} h264bsdmi_cells_spec;
+int h264bsdmiOutputCellMaps(u32 n, storage_t *const *pStorage, u32 nRegions, const h264bsdmi_region *regions,
+                            const h264bsdmi_cells_spec *spec, void *stream,
+                            u32 *got, u32 *current, u32 *kept, u32 *picId, u32 *keptPicId);
+
 /* ---- host parse pipeline at scale ----
  * h264bsdDecode() consumes one NAL unit of one stream per call; a caller that feeds hundreds of streams needs the
  * loop of posix/test_h264bsd.c:146-177 for each of them and its own threading.  These entry points move both into
