@@ -51,6 +51,46 @@ def test_bgra_output_matches_reference(built, golden):
     dec.close()
 
 
+@pytest.mark.parametrize("name", ["test_1920x1080", "test_1920x1080_fullRange"])
+def test_converted_output_of_every_picture(name, built, golden):
+    """h264bsdNextOutputPictureRGBA, ...BGRA and ...YCbCrA of the product library, one decoder per format, on all 73 pictures of a
+    1080p stream: the pictures the reference's harness recorded (golden.json convert_sha256) by hash, every other one against the
+    oracle's conversion (the reference's formula) of the I420 picture a twin decoder gives"""
+    from oracle import pyoracle
+    g = golden[name]
+    W, H = 16 * g["width_mbs"], 16 * g["height_mbs"]
+    data = stream_bytes(name)
+    decs = [built.Decoder() for _ in range(4)]              # RGBA, BGRA, YCbCrA, and the twin
+    bufs = [ctypes.create_string_buffer(data, len(data)) for _ in decs]
+    off, n = 0, 0
+    while off < len(data):
+        res = {d.decode(ctypes.addressof(b) + off, len(data) - off) for d, b in zip(decs, bufs)}
+        assert len(res) == 1
+        (r, rb), = res
+        off += rb
+        assert r < built.H264BSD_ERROR
+        if r != built.H264BSD_PIC_RDY:
+            continue
+        while True:
+            twin = decs[3].next_output_picture()
+            pics = [d.next_output_picture_converted(fmt) for fmt, d in enumerate(decs[:3])]
+            if twin is None:
+                assert pics == [None] * 3
+                break
+            assert hashlib.sha256(twin[0].tobytes()).hexdigest() == g["frame_sha256"][n]
+            for fmt, pic in enumerate(pics):
+                assert pic is not None and pic[1:] == twin[1:] and pic[0].size == W * H
+                if str(n) in g["convert_sha256"]:
+                    assert hashlib.sha256(pic[0].tobytes()).hexdigest() == g["convert_sha256"][str(n)][fmt], (n, fmt)
+                else:
+                    assert np.array_equal(pic[0], pyoracle.oracle_convert(fmt, W, H, twin[0])), (n, fmt)
+            n += 1
+    assert n == 73
+    assert built.device_errors() == 0
+    for d in decs:
+        d.close()
+
+
 def test_many_instances_round_robin_are_batched_and_exact(built, golden):
     """8 decoder instances advanced in lock step: every flush reconstructs 8 pictures in one tick"""
     name = "test_640x360"

@@ -181,7 +181,7 @@ def test_one_replay_set_under_one_schedule_after_the_other(built, captured, gold
         rep.close()
 
 
-@pytest.mark.parametrize("name", ["test_640x360", "test_1920x1080_fullRange"])
+@pytest.mark.parametrize("name", ["test_640x360", "test_1920x1080", "test_1920x1080_fullRange"])
 def test_on_device_colour_conversion(name, built, captured, golden):
     jobs, _, info = captured(name)
     g = golden[name]
