@@ -11,8 +11,10 @@ from .capi import (  # noqa: F401
     StatsSpec, RegionStats, pull_stats, stats_record_bytes,
     ChangeSpec, RegionChange, keep_pictures, pull_change, change_record_bytes,
     CellsSpec, CellMaps, pull_cells,
+    BoxesSpec, CellBoxes, pull_boxes,
 )
 
 # 0.2: pull_remap / affine_maps (h264bsdmiOutputTensorRemap); 0.3: pull_stats (h264bsdmiOutputRegionStats);
 # 0.4: keep_pictures / pull_change (h264bsdmiKeepCurrentPictures, h264bsdmiOutputRegionChange); 0.5: pull_cells (h264bsdmiOutputCellMaps)
-__version__ = "0.5.0"
+# 0.6: pull_boxes (h264bsdmiOutputCellBoxes)
+__version__ = "0.6.0"

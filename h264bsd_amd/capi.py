@@ -28,7 +28,7 @@ EXPORTED_SYMBOLS = [
     "h264bsdCroppingParams", "h264bsdSampleAspectRatio", "h264bsdCheckValidParamSets", "h264bsdFlushBuffer",
     "h264bsdProfile", "h264bsdAlloc", "h264bsdFree", "h264bsdConvertToRGBA", "h264bsdConvertToBGRA",
     "h264bsdConvertToYCbCrA",
-    "h264bsdmiInitCapture", "h264bsdmiNextOutputInfo", "h264bsdmiNextOutputPictureDevice", "h264bsdmiNextOutputTensorBatch", "h264bsdmiNextOutputTensorBatchColour", "h264bsdmiNextOutputTensorBatchResize", "h264bsdmiOutputTensorRegions", "h264bsdmiOutputTensorRemap", "h264bsdmiSetMotionExport", "h264bsdmiOutputMotionRegions", "h264bsdmiOutputRegionStats", "h264bsdmiKeepCurrentPictures", "h264bsdmiOutputRegionChange", "h264bsdmiOutputCellMaps", "h264bsdmiJobFinalize", "h264bsdmiDeviceCount", "h264bsdmiSetDevice", "h264bsdmiFlush", "h264bsdmiFlushAsync", "h264bsdmiDeviceErrors",
+    "h264bsdmiInitCapture", "h264bsdmiNextOutputInfo", "h264bsdmiNextOutputPictureDevice", "h264bsdmiNextOutputTensorBatch", "h264bsdmiNextOutputTensorBatchColour", "h264bsdmiNextOutputTensorBatchResize", "h264bsdmiOutputTensorRegions", "h264bsdmiOutputTensorRemap", "h264bsdmiSetMotionExport", "h264bsdmiOutputMotionRegions", "h264bsdmiOutputRegionStats", "h264bsdmiKeepCurrentPictures", "h264bsdmiOutputRegionChange", "h264bsdmiOutputCellMaps", "h264bsdmiOutputCellBoxes", "h264bsdmiJobFinalize", "h264bsdmiDeviceCount", "h264bsdmiSetDevice", "h264bsdmiFlush", "h264bsdmiFlushAsync", "h264bsdmiDeviceErrors",
     "h264bsdmiDecodePicture", "h264bsdmiDecodePictureBatch", "h264bsdmiNextOutputPictureBatch", "h264bsdmiPullAndDecodePictureBatch", "h264bsdmiSetParserThreads", "h264bsdmiSetInputReadOnly", "h264bsdmiSetCopyElision",
     "h264bsdmiReplayCreate", "h264bsdmiReplayCreateStaggered", "h264bsdmiReplayCreateDesync", "h264bsdmiReplayCreateSched", "h264bsdmiReplayReschedule", "h264bsdmiReplayDestroy", "h264bsdmiReplayRun", "h264bsdmiReplaySync",
     "h264bsdmiReplayFetch", "h264bsdmiReplayChecksums", "h264bsdmiReplayConvert", "h264bsdmiReplayFetchConverted",
@@ -102,6 +102,14 @@ class CellsSpec(ctypes.Structure):
                 ("threshold", ctypes.c_uint32 * 3), ("keep_after", ctypes.c_uint32)]
 
 
+class BoxesSpec(ctypes.Structure):
+    """h264bsdmi_boxes_spec (include/h264bsd_mi355x.h)"""
+    _fields_ = [("data", ctypes.c_void_p), ("max_boxes", ctypes.c_uint32), ("plane", ctypes.c_uint32), ("channel", ctypes.c_uint32),
+                ("sense", ctypes.c_uint32), ("level", ctypes.c_uint32), ("connectivity", ctypes.c_uint32), ("min_cells", ctypes.c_uint32)]
+
+
+BOXES_MAX_CELLS, BOXES_MAX_BOXES = 16384, 512                                     # H264BSDMI_BOXES_MAX_*
+BOXES_SENSES = {"above": 0, "below": 1}                                          # H264BSDMI_BOXES_*
 # per mode (H264BSDMI_CELLS_PICTURE, _CHANGE): name -> H264BSDMI_CELL_*, in the order of the maps
 CELL_PLANES = ({"count": 1, "sum": 2, "sumsq": 4, "min": 8, "max": 16}, {"count": 1, "sad": 2, "ssd": 4, "dsum": 8, "dmax": 16, "above": 32})
 CELL_SIZES = (4, 8, 16, 32, 64)
@@ -246,6 +254,9 @@ def _declare(L, harness):
     L.h264bsdmiOutputCellMaps.argtypes = [u32, ctypes.POINTER(vp), u32, ctypes.POINTER(Region), ctypes.POINTER(CellsSpec), vp,
                                           P32, P32, P32, P32, P32]
     L.h264bsdmiOutputCellMaps.restype = ctypes.c_int
+    L.h264bsdmiOutputCellBoxes.argtypes = [u32, ctypes.POINTER(vp), u32, ctypes.POINTER(Region), ctypes.POINTER(CellsSpec), ctypes.POINTER(BoxesSpec), vp,
+                                           P32, P32, P32, P32, P32]
+    L.h264bsdmiOutputCellBoxes.restype = ctypes.c_int
     L.h264bsdmiDecodePicture.argtypes = [vp, u8p, u32, u32, P32, P32]
     L.h264bsdmiDecodePicture.restype = u32
     L.h264bsdmiDecodePictureBatch.argtypes = [u32, ctypes.POINTER(vp), ctypes.POINTER(vp), P32, P32, P32, P32, P32]
@@ -973,6 +984,39 @@ class CellMaps:
         self.got, self.current, self.kept, self.pic_id, self.kept_pic_id = got, current, kept, pic_id, kept_pic_id
 
 
+def _cells_args(who, decoders, regions, cell, grid, source, planes, against, threshold, crop, keep):
+    """the argument checks and the grid of pull_cells, for it and for pull_boxes -> (mode, src, C, bits, thr, K, regs, grid)"""
+    n = len(decoders)
+    if against not in (None, "kept"):
+        raise ValueError(f"{who}: against is None or 'kept', not {against}")
+    mode = 1 if against == "kept" else 0
+    if source not in STATS_SOURCES or cell not in CELL_SIZES:
+        raise ValueError(f"{who}: unsupported source / cell {source} {cell}")
+    src, C = STATS_SOURCES[source]
+    names = (planes,) if isinstance(planes, str) else tuple(planes)
+    if not names or any(p not in CELL_PLANES[mode] for p in names):
+        raise ValueError(f"{who}: planes is a non-empty choice of {tuple(CELL_PLANES[mode])}, not {planes}")
+    bits = sum({CELL_PLANES[mode][p] for p in names})
+    thr = [threshold] * 3 if isinstance(threshold, int) else list(threshold) + [0] * (3 - C) if isinstance(threshold, (tuple, list)) else []
+    if len(thr) != 3 or not all(isinstance(t, int) and 0 <= t <= 255 for t in thr):
+        raise ValueError(f"{who}: threshold is one int in 0..255, or one per channel, not {threshold}")
+    if not mode and (any(thr) or keep):
+        raise ValueError(f"{who}: threshold and keep need against='kept'")
+    K, regs = _regions_arg(who, n, regions)
+    if grid is None:
+        if regs is not None:
+            sizes = [(r.h, r.w) for r in regs[:K]]
+        else:
+            sizes = []
+            for d in decoders:
+                flag, _, cw, _, ch = d.cropping_params()
+                sizes.append((ch, cw) if crop and flag else (16 * d.pic_height(), 16 * d.pic_width()))
+        grid = (max([-(-h // cell) for h, _ in sizes] + [1]), max([-(-w // cell) for _, w in sizes] + [1]))
+    if not (isinstance(grid, (tuple, list)) and len(grid) == 2 and all(isinstance(g, int) and 1 <= g <= 4096 for g in grid)):
+        raise ValueError(f"{who}: grid is (rows, cols), 1..4096 each, not {grid}")
+    return mode, src, C, bits, thr, K, regs, grid
+
+
 def pull_cells(decoders, regions=None, cell=16, grid=None, source="y", planes=("count", "sum"), against=None, threshold=0, crop=True,
                keep=False, out=None, stream=None):
     """h264bsdmiOutputCellMaps: dense integer maps, one value per cell x cell luma samples, over boxes of the decoders' CURRENT pictures,
@@ -986,33 +1030,7 @@ def pull_cells(decoders, regions=None, cell=16, grid=None, source="y", planes=("
     slices of decoders without a current (against="kept": or kept) picture are left untouched (got[r] = 0).  Returns a CellMaps."""
     import torch
     n = len(decoders)
-    if against not in (None, "kept"):
-        raise ValueError(f"pull_cells: against is None or 'kept', not {against}")
-    mode = 1 if against == "kept" else 0
-    if source not in STATS_SOURCES or cell not in CELL_SIZES:
-        raise ValueError(f"pull_cells: unsupported source / cell {source} {cell}")
-    src, C = STATS_SOURCES[source]
-    names = (planes,) if isinstance(planes, str) else tuple(planes)
-    if not names or any(p not in CELL_PLANES[mode] for p in names):
-        raise ValueError(f"pull_cells: planes is a non-empty choice of {tuple(CELL_PLANES[mode])}, not {planes}")
-    bits = sum({CELL_PLANES[mode][p] for p in names})
-    thr = [threshold] * 3 if isinstance(threshold, int) else list(threshold) + [0] * (3 - C) if isinstance(threshold, (tuple, list)) else []
-    if len(thr) != 3 or not all(isinstance(t, int) and 0 <= t <= 255 for t in thr):
-        raise ValueError(f"pull_cells: threshold is one int in 0..255, or one per channel, not {threshold}")
-    if not mode and (any(thr) or keep):
-        raise ValueError("pull_cells: threshold and keep need against='kept'")
-    K, regs = _regions_arg("pull_cells", n, regions)
-    if grid is None:
-        if regs is not None:
-            sizes = [(r.h, r.w) for r in regs[:K]]
-        else:
-            sizes = []
-            for d in decoders:
-                flag, _, cw, _, ch = d.cropping_params()
-                sizes.append((ch, cw) if crop and flag else (16 * d.pic_height(), 16 * d.pic_width()))
-        grid = (max([-(-h // cell) for h, _ in sizes] + [1]), max([-(-w // cell) for _, w in sizes] + [1]))
-    if not (isinstance(grid, (tuple, list)) and len(grid) == 2 and all(isinstance(g, int) and 1 <= g <= 4096 for g in grid)):
-        raise ValueError(f"pull_cells: grid is (rows, cols), 1..4096 each, not {grid}")
+    mode, src, C, bits, thr, K, regs, grid = _cells_args("pull_cells", decoders, regions, cell, grid, source, planes, against, threshold, crop, keep)
     P = (bits & 1) + C * bin(bits >> 1).count("1")
     shape = (K, P, grid[0], grid[1])
     out, stream = _out_and_stream("pull_cells", out, shape, torch.int32, stream)
@@ -1026,6 +1044,97 @@ def pull_cells(decoders, regions=None, cell=16, grid=None, source="y", planes=("
             raise RuntimeError(f"h264bsdmiOutputCellMaps failed ({rc})")
     cur, kept, ids, kept_ids = [list(a)[:n] for a in per]
     return CellMaps(out, mode, C, bits, list(got)[:K], cur, kept, ids, kept_ids)
+
+
+class CellBoxes:
+    """what pull_boxes returns: cells, the CellMaps of the same call; boxes [R, 1 + M, 8] int32, the C layout, with the views header
+    [R, 8] (found, written, foreground_cells, dropped, 0, 0, 0, 0) and records [R, M, 8] (x, y, w, h, cells, peak, sum_lo, sum_hi; zero
+    beyond `written`); sums() the 64-bit sums; regions() and found, which make ONE small copy of boxes to the host, kept for both"""
+
+    def __init__(self, cells, boxes, instances, stream=None):
+        self.cells, self.boxes, self.instances, self.stream = cells, boxes, instances, stream
+        self.header, self.records = boxes[:, 0], boxes[:, 1:]
+        self._host = None
+
+    def sums(self):
+        """[R, M] int64: sum_lo | sum_hi << 32"""
+        import torch
+        lo, hi = self.records[..., 6].to(torch.int64), self.records[..., 7].to(torch.int64)
+        return (lo & 0xFFFFFFFF) | (hi << 32)
+
+    def host(self):
+        """boxes as a host int64 array [R, 1 + M, 8] of the unsigned words: copied once, behind the call's stream"""
+        if self._host is None:
+            import numpy as np
+            if self.stream is not None:
+                self.stream.synchronize()
+            self._host = self.boxes.cpu().numpy().astype(np.int64) & 0xFFFFFFFF
+        return self._host
+
+    @property
+    def found(self):
+        """per region: the components that remain (0 where got is 0); more than M of them are not all written"""
+        return [int(h[0, 0]) if g else 0 for h, g in zip(self.host(), self.cells.got)]
+
+    def regions(self, pad=0):
+        """[(decoder_index, x, y, w, h)] of all written boxes in slice order, each grown by pad luma samples a side: regions for
+        pull_regions, pull_stats, pull_change, pull_cells (boxes may leave the window: those calls allow it)"""
+        import numpy as np
+        out = []
+        for r, (slice_, g) in enumerate(zip(self.host(), self.cells.got)):
+            if not g:
+                continue
+            rec = slice_[1:1 + int(slice_[0, 1]), :4]
+            rows = np.column_stack([np.full(len(rec), self.instances[r]), rec[:, 0] - pad, rec[:, 1] - pad, rec[:, 2] + 2 * pad, rec[:, 3] + 2 * pad])
+            out += map(tuple, rows.tolist())
+        return out
+
+
+def pull_boxes(decoders, regions=None, cell=16, grid=None, source="y", planes=("sad",), against="kept", threshold=0,
+               plane=None, channel=0, level=0, sense="above", connectivity=8, min_cells=1, max_boxes=64,
+               crop=True, keep=False, out=None, boxes_out=None, stream=None):
+    """h264bsdmiOutputCellBoxes: pull_cells, and behind it, on the device, the bounding boxes of the connected groups of cells whose
+    value in one of the maps passes a level.  decoders ... planes, against, threshold, crop, keep, out and stream as for pull_cells
+    (here against defaults to "kept" and planes to ("sad",): where did the picture change).  plane: the map that is thresholded, one of
+    planes but not "dsum" (None: the first of planes that is not "count", or "count"); channel: of source (count: 0); sense "above":
+    foreground is value > level, "below": value < level, as unsigned 32-bit; cells the box or the window do not reach are never
+    foreground.  connectivity 4 or 8; components of fewer than min_cells cells are dropped; the rest are numbered by their first cell
+    in raster order and the first max_boxes (1..512) are written.  The grid has at most 16384 cells.  boxes_out: a contiguous CUDA
+    int32 tensor [R, 1 + max_boxes, 8] to write into; slices of regions with got[r] = 0 are left untouched.  Returns a CellBoxes."""
+    import torch
+    n = len(decoders)
+    mode, src, C, bits, thr, K, regs, grid = _cells_args("pull_boxes", decoders, regions, cell, grid, source, planes, against, threshold, crop, keep)
+    names = (planes,) if isinstance(planes, str) else tuple(planes)
+    if plane is None:
+        plane = next((p for p in names if p != "count"), "count")
+    if plane not in names or plane == "dsum":
+        raise ValueError(f"pull_boxes: plane is one of planes and not 'dsum', not {plane}")
+    if not isinstance(channel, int) or not 0 <= channel < (1 if plane == "count" else C):
+        raise ValueError(f"pull_boxes: channel is 0..{(1 if plane == 'count' else C) - 1} for {plane} of {source}, not {channel}")
+    if sense not in BOXES_SENSES or connectivity not in (4, 8):
+        raise ValueError(f"pull_boxes: sense is 'above' or 'below' and connectivity 4 or 8, not {sense} {connectivity}")
+    if not all(isinstance(v, int) for v in (level, min_cells, max_boxes)) or not 0 <= level < 2 ** 32 or not 1 <= min_cells < 2 ** 32 or \
+            not 1 <= max_boxes <= BOXES_MAX_BOXES:
+        raise ValueError(f"pull_boxes: level is 0..2^32 - 1, min_cells at least 1, max_boxes 1..{BOXES_MAX_BOXES}, not {level} {min_cells} {max_boxes}")
+    if grid[0] * grid[1] > BOXES_MAX_CELLS:
+        raise ValueError(f"pull_boxes: a grid of {grid[0]} x {grid[1]} cells is above the cap of {BOXES_MAX_CELLS} cells; use a larger cell or smaller regions")
+    P = (bits & 1) + C * bin(bits >> 1).count("1")
+    out, stream = _out_and_stream("pull_boxes", out, (K, P, grid[0], grid[1]), torch.int32, stream)
+    boxes_out, _ = _out_and_stream("pull_boxes", boxes_out, (K, 1 + max_boxes, 8), torch.int32, stream)
+    if boxes_out.device != out.device:
+        raise ValueError("pull_boxes: out and boxes_out must be on the same device")
+    spec = CellsSpec(out.data_ptr(), grid[1], grid[0], cell, src, 1 if crop else 0, mode, bits, (ctypes.c_uint32 * 3)(*thr), 1 if keep else 0)
+    bspec = BoxesSpec(boxes_out.data_ptr(), max_boxes, CELL_PLANES[mode][plane], channel, BOXES_SENSES[sense], level, connectivity, min_cells)
+    got = (ctypes.c_uint32 * max(K, 1))()
+    per = [(ctypes.c_uint32 * max(n, 1))() for _ in range(4)]                # current, kept, picId, keptPicId
+    if n and K:
+        rc = api_lib().h264bsdmiOutputCellBoxes(n, (ctypes.c_void_p * n)(*[d._st for d in decoders]), K, regs, ctypes.byref(spec),
+                                                ctypes.byref(bspec), stream.cuda_stream, got, *per)
+        if rc != 0:
+            raise RuntimeError(f"h264bsdmiOutputCellBoxes failed ({rc})")
+    cur, kept, ids, kept_ids = [list(a)[:n] for a in per]
+    instances = [r.instance for r in regs[:K]] if regs is not None else list(range(K))
+    return CellBoxes(CellMaps(out, mode, C, bits, list(got)[:K], cur, kept, ids, kept_ids), boxes_out, instances, stream)
 
 
 def job_header(blob):

@@ -363,14 +363,14 @@ int h264bsdmiNextOutputTensorBatchResize(u32 n, storage_t *const *dec, const h26
 
 /* ---- The pulls of CURRENT pictures (pop_output, drop_current): h264bsdmiOutputTensorRegions, h264bsdmiOutputTensorRemap,
  * h264bsdmiOutputMotionRegions, h264bsdmiOutputRegionStats, h264bsdmiOutputRegionChange (which needs the kept picture as well),
- * h264bsdmiOutputCellMaps (which needs it in CHANGE mode), and their small sibling h264bsdmiKeepCurrentPictures (the picture list only).  Each checks its own spec; everything else is one path:
+ * h264bsdmiOutputCellMaps and h264bsdmiOutputCellBoxes (which need it in CHANGE mode), and their small sibling h264bsdmiKeepCurrentPictures (the picture list only).  Each checks its own spec; everything else is one path:
  *   regions_refused   got, the count and the range of every region — before the instances are looked at
  *   pull_begin        dec and the instances (of this library, with the sink entry the call needs, distinct), then the lists
  *   pull_pic          an instance's current picture in the picture list, appended at its first use
  *   pull_regions      the regions (or one whole window per instance) of the pictures that exist, each with its rectangle
  *   pull_finish       after the sink: got, box, current and picId — unless the sink failed (-2 writes nothing) — and the lists freed
  * A refused call returns -1 and has called no sink, written nothing; no call pops anything. */
-enum { PULL_REGIONS, PULL_REMAP, PULL_MOTION, PULL_STATS, PULL_CHANGE, PULL_KEEP, PULL_CELLS };
+enum { PULL_REGIONS, PULL_REMAP, PULL_MOTION, PULL_STATS, PULL_CHANGE, PULL_KEEP, PULL_CELLS, PULL_BOXES };
 #define NO_PIC 0xFFFFFFFFu
 typedef struct CurrentPull {
     u32 n, m, k;                /* instances; pictures and items gathered so far */
@@ -380,7 +380,7 @@ typedef struct CurrentPull {
     SinkRegion *regs;           /* the items for the sink: regions, or (PULL_REMAP) maps */
     SinkRemap *maps;
     int kind;                   /* PULL_* */
-    int vs_kept;                /* only instances that have a kept picture too: PULL_CHANGE, and PULL_CELLS in CHANGE mode */
+    int vs_kept;                /* only instances that have a kept picture too: PULL_CHANGE, and PULL_CELLS / PULL_BOXES in CHANGE mode */
 } CurrentPull;
 
 /* regions == NULL: no regions at all, or (whole: one whole window per instance) exactly n */
@@ -408,6 +408,7 @@ static int sink_pulls(const ApiDec *a, int kind)
     case PULL_CHANGE: return k->tensor_regions != NULL && k->region_change != NULL && k->keep_pictures != NULL;
     case PULL_KEEP:   return k->tensor_regions != NULL && k->keep_pictures != NULL;
     case PULL_CELLS:  return k->tensor_regions != NULL && k->cell_maps != NULL;      /* CHANGE mode: keep_pictures too (the entry asks) */
+    case PULL_BOXES:  return k->tensor_regions != NULL && k->cell_maps != NULL && k->cell_boxes != NULL;
     }
     return k->tensor_regions != NULL;
 }
@@ -635,21 +636,35 @@ static int cells_spec_refused(const h264bsdmi_cells_spec *s)
     if (s->mode == H264BSDMI_CELLS_PICTURE && (s->threshold[0] || s->threshold[1] || s->threshold[2] || s->keep_after)) return 1;
     return 0;
 }
-int h264bsdmiOutputCellMaps(u32 n, storage_t *const *dec, u32 nRegions, const h264bsdmi_region *regions,
-                            const h264bsdmi_cells_spec *spec, void *stream,
-                            u32 *got, u32 *current, u32 *kept, u32 *picId, u32 *keptPicId)
+/* The boxes spec against the cells spec it labels a map of (which has passed cells_spec_refused) */
+static int boxes_spec_refused(const h264bsdmi_cells_spec *c, const h264bsdmi_boxes_spec *b)
+{
+    if (!b || !b->data || ((uintptr_t)b->data & 3u)) return 1;
+    if (!b->max_boxes || b->max_boxes > H264BSDMI_BOXES_MAX_BOXES) return 1;
+    if (!b->plane || (b->plane & (b->plane - 1u)) || !(b->plane & c->planes)) return 1;
+    if (c->mode == H264BSDMI_CELLS_CHANGE && b->plane == H264BSDMI_CELL_DSUM) return 1;
+    if (b->channel >= (b->plane == H264BSDMI_CELL_COUNT || c->source == H264BSDMI_STATS_Y ? 1u : 3u)) return 1;
+    if (b->sense > H264BSDMI_BOXES_BELOW || (b->connectivity != 4 && b->connectivity != 8) || !b->min_cells) return 1;
+    return c->rows * c->cols > H264BSDMI_BOXES_MAX_CELLS;                   /* (4096 each at the most: no overflow) */
+}
+/* The host path of both: kind PULL_CELLS calls the sink's cell_maps, PULL_BOXES its cell_boxes with the boxes spec */
+static int cells_pull(int kind, u32 n, storage_t *const *dec, u32 nRegions, const h264bsdmi_region *regions,
+                      const h264bsdmi_cells_spec *spec, const h264bsdmi_boxes_spec *boxes, void *stream,
+                      u32 *got, u32 *current, u32 *kept, u32 *picId, u32 *keptPicId)
 {
     CurrentPull c, k;
-    if (cells_spec_refused(spec)) return -1;
+    if (cells_spec_refused(spec) || (kind == PULL_BOXES && boxes_spec_refused(spec, boxes))) return -1;
     const int change = spec->mode == H264BSDMI_CELLS_CHANGE;
-    if (regions_refused(n, nRegions, regions, got, 1) || pull_begin(&c, n, dec, nRegions, PULL_CELLS)) return -1;
+    if (regions_refused(n, nRegions, regions, got, 1) || pull_begin(&c, n, dec, nRegions, kind)) return -1;
     c.vs_kept = change;
     for (u32 i = 0; change && i < n; i++)
         if (!dec_of(dec[i])->hd->sink.keep_pictures) { pull_free(&c); return -1; }
     if (spec->keep_after && keep_begin(&k, n, dec)) { pull_free(&c); return -1; }
     const h264bsdmi_tensor_spec window = { spec->data, 1, 1, 0, 0, 0, spec->crop, 1, { 0, 0, 0 }, { 1, 1, 1 } };
     pull_regions(&c, nRegions, regions, &window, &REFERENCE_COLOUR, 1, 1, 0);
-    int failed = c.k && c.pics[0].sink->cell_maps(c.m, c.pics, c.k, c.regs, spec, stream);
+    int failed = 0;
+    if (c.k) failed = kind == PULL_BOXES ? c.pics[0].sink->cell_boxes(c.m, c.pics, c.k, c.regs, spec, boxes, stream)
+                                         : c.pics[0].sink->cell_maps(c.m, c.pics, c.k, c.regs, spec, stream);
     if (spec->keep_after && !failed) failed = k.m && k.pics[0].sink->keep_pictures(k.m, k.pics, stream);
     if (!failed) {
         for (u32 i = 0; i < n; i++) {
@@ -661,6 +676,19 @@ int h264bsdmiOutputCellMaps(u32 n, storage_t *const *dec, u32 nRegions, const h2
     }
     if (spec->keep_after) pull_free(&k);
     return pull_finish(&c, failed, nRegions, got, NULL, current, picId);
+}
+int h264bsdmiOutputCellMaps(u32 n, storage_t *const *dec, u32 nRegions, const h264bsdmi_region *regions,
+                            const h264bsdmi_cells_spec *spec, void *stream,
+                            u32 *got, u32 *current, u32 *kept, u32 *picId, u32 *keptPicId)
+{
+    return cells_pull(PULL_CELLS, n, dec, nRegions, regions, spec, NULL, stream, got, current, kept, picId, keptPicId);
+}
+/* The cell maps, and behind them the boxes of the connected groups of cells that pass a level */
+int h264bsdmiOutputCellBoxes(u32 n, storage_t *const *dec, u32 nRegions, const h264bsdmi_region *regions,
+                             const h264bsdmi_cells_spec *cells, const h264bsdmi_boxes_spec *boxes, void *stream,
+                             u32 *got, u32 *current, u32 *kept, u32 *picId, u32 *keptPicId)
+{
+    return cells_pull(PULL_BOXES, n, dec, nRegions, regions, cells, boxes, stream, got, current, kept, picId, keptPicId);
 }
 
 static u32 *next_converted(storage_t *s, u32 *picId, u32 *isIdrPic, u32 *numErrMbs, int fmt)

@@ -40,6 +40,7 @@
 #include "kernels/k_keep.hip.h"
 #include "kernels/k_region_change.hip.h"
 #include "kernels/k_cell_maps.hip.h"
+#include "kernels/k_cell_boxes.hip.h"
 #include "engine.h"
 #include "hip_owned.h"
 #include "tick_plan.h"
@@ -158,10 +159,10 @@ constexpr uint32_t LANE_DBK_WAVES = LANE_DBK_WAVES_N;
 
 /* the item stride of the tensor pulls' staging ring: k_tensor_out / k_tensor_resize read TensorItems, k_tensor_aa AaItems, k_tensor_roi
  * RoiItems, k_motion_roi MotionItems, k_tensor_remap RemapItems, k_region_stats StatsItems, k_keep KeepItems, k_region_change ChangeItems,
- * k_cell_maps CellItems */
+ * k_cell_maps CellItems (k_cell_boxes: the same, and its BoxItems in slots of their own behind them) */
 constexpr size_t TITEM_BYTES = std::max({ sizeof(h264k::TensorItem), sizeof(h264k::AaItem), sizeof(h264k::RoiItem), sizeof(h264k::MotionItem),
                                           sizeof(h264k::RemapItem), sizeof(h264k::StatsItem), sizeof(h264k::KeepItem), sizeof(h264k::ChangeItem),
-                                          sizeof(h264k::CellItem) });
+                                          sizeof(h264k::CellItem), sizeof(h264k::BoxItem) });
 struct TItemSlot { uint8_t bytes[TITEM_BYTES]; };
 struct Engine {
     std::mutex mu;
@@ -1543,8 +1544,11 @@ template <int MODE, int SRC> static const void *cells_kernel(bool quad)
 {
     return quad ? reinterpret_cast<const void *>(&h264k::k_cell_maps<MODE, SRC, true>) : reinterpret_cast<const void *>(&h264k::k_cell_maps<MODE, SRC, false>);
 }
-static int cells_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, uint32_t n_regs, const SinkRegion *regs,
-                            const h264bsdmi_cells_spec &sp, hipStream_t st, hipEvent_t *fence_ev)
+/* What cells_out_locked and cell_boxes_out_locked share: the refusals, pull_begin_locked with room for `extra` more item slots behind
+ * the CellItems, the CellItems, and the k_cell_maps launch as CellsLaunch describes it (not made yet) */
+struct CellsLaunch { const void *fn; dim3 grid; h264k::CellArgs args; bool change; uint32_t shift, channels; };
+static int cells_prepare_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, uint32_t n_regs, const SinkRegion *regs,
+                                const h264bsdmi_cells_spec &sp, uint32_t extra, CellsLaunch *L)
 {
     const bool change = sp.mode == H264BSDMI_CELLS_CHANGE;
     uint32_t shift = 2u;
@@ -1564,7 +1568,7 @@ static int cells_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, ui
     const uint32_t rw = h264k::CELLS_RECT_W >> shift, rh = h264k::CELLS_RECT_H >> shift;
     const uint32_t rects_x = (sp.cols + rw - 1u) / rw, rects = rects_x * ((sp.rows + rh - 1u) / rh);
     if ((uint64_t)rects * n_regs > h264k::CELLS_MAX_WORKGROUPS) return -1;
-    if (pull_begin_locked(e, n, pics, n_regs)) return -1;
+    if (pull_begin_locked(e, n, pics, n_regs + extra)) return -1;
     h264k::CellItem *items = e->titems.host<h264k::CellItem>();
     const uint32_t channels = sp.source == H264BSDMI_STATS_Y ? 1u : 3u;
     const size_t slice = ((sp.planes & 1u) + channels * (size_t)__builtin_popcount(sp.planes >> 1)) * sp.rows * sp.cols;      /* words */
@@ -1586,10 +1590,55 @@ static int cells_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, ui
     const void *const fns[2][3] = {
         { cells_kernel<0, h264k::ST_Y>(quad), cells_kernel<0, h264k::ST_YCBCR>(quad), cells_kernel<0, h264k::ST_RGB>(quad) },
         { cells_kernel<1, h264k::ST_Y>(quad), cells_kernel<1, h264k::ST_YCBCR>(quad), cells_kernel<1, h264k::ST_RGB>(quad) } };
-    h264k::CellArgs cargs{ e->titems.dev<h264k::CellItem>(), sp.cols, sp.rows, shift, rects_x, sp.planes, { sp.threshold[0], sp.threshold[1], sp.threshold[2] } };
-    if (change && kept_order_begin(e, st)) return -1;
-    if (pull_launch_locked(e, n, pics, st, fns[sp.mode][sp.source], dim3(rects, n_regs), &cargs, fence_ev)) return -1;
-    return change ? kept_order_end(e, st) : 0;
+    *L = CellsLaunch{ fns[sp.mode][sp.source], dim3(rects, n_regs),
+                      { e->titems.dev<h264k::CellItem>(), sp.cols, sp.rows, shift, rects_x, sp.planes, { sp.threshold[0], sp.threshold[1], sp.threshold[2] } },
+                      change, shift, channels };
+    return 0;
+}
+static int cells_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, uint32_t n_regs, const SinkRegion *regs,
+                            const h264bsdmi_cells_spec &sp, hipStream_t st, hipEvent_t *fence_ev)
+{
+    CellsLaunch L;
+    if (cells_prepare_locked(e, n, pics, n_regs, regs, sp, 0u, &L)) return -1;
+    if (L.change && kept_order_begin(e, st)) return -1;
+    if (pull_launch_locked(e, n, pics, st, L.fn, L.grid, &L.args, fence_ev)) return -1;
+    return L.change ? kept_order_end(e, st) : 0;
+}
+
+/* h264bsdmiOutputCellBoxes: what cells_out_locked enqueues, and between its k_cell_maps launch and the fence ONE k_cell_boxes launch
+ * of one workgroup per region, which labels the chosen map of the slice the launch before it wrote: the fence and the error words
+ * stand behind both, and in CHANGE mode the kept pictures' ordering encloses both.  One BoxItem per region in the staging slots behind
+ * the CellItems: the boxes slice and the origin of the source window, which the CellItem does not carry. */
+static int cell_boxes_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, uint32_t n_regs, const SinkRegion *regs,
+                                 const h264bsdmi_cells_spec &sp, const h264bsdmi_boxes_spec &bs, hipStream_t st, hipEvent_t *fence_ev)
+{
+    const uint32_t channels = sp.source == H264BSDMI_STATS_Y ? 1u : 3u;
+    if (!bs.data || (reinterpret_cast<uintptr_t>(bs.data) & 3u) || !bs.max_boxes || bs.max_boxes > h264k::BOXES_MAX_BOXES) return -1;
+    if (!bs.plane || (bs.plane & (bs.plane - 1u)) || !(bs.plane & sp.planes)) return -1;
+    if (sp.mode == H264BSDMI_CELLS_CHANGE && bs.plane == H264BSDMI_CELL_DSUM) return -1;
+    if (bs.channel >= (bs.plane == H264BSDMI_CELL_COUNT ? 1u : channels)) return -1;
+    if (bs.sense > H264BSDMI_BOXES_BELOW || (bs.connectivity != 4u && bs.connectivity != 8u) || !bs.min_cells) return -1;
+    if (!sp.cols || !sp.rows || (uint64_t)sp.cols * sp.rows > h264k::BOXES_MAX_CELLS) return -1;       /* what one workgroup's LDS holds */
+    CellsLaunch L;
+    if (cells_prepare_locked(e, n, pics, n_regs, regs, sp, n_regs, &L)) return -1;
+    h264k::BoxItem *items = reinterpret_cast<h264k::BoxItem *>(e->titems.host<TItemSlot>() + n_regs);
+    const size_t words = (size_t)(1u + bs.max_boxes) * 8u;
+    for (uint32_t r = 0; r < n_regs; r++) {
+        const SinkTensorPic &p = pics[regs[r].pic];
+        items[r] = h264k::BoxItem{ static_cast<uint32_t *>(bs.data) + (size_t)regs[r].index * words, (int32_t)p.x0, (int32_t)p.y0 };
+    }
+    /* COUNT, then per set bit of planes in ascending order `channels` maps */
+    const uint32_t before = bs.plane == H264BSDMI_CELL_COUNT ? 0u
+        : (sp.planes & 1u) + L.channels * (uint32_t)__builtin_popcount(sp.planes & (bs.plane - 1u) & ~1u) + bs.channel;
+    h264k::BoxArgs bargs{ L.args.items, reinterpret_cast<const h264k::BoxItem *>(e->titems.dev<TItemSlot>() + n_regs), sp.cols, sp.rows, L.shift,
+                          before * sp.rows * sp.cols, bs.max_boxes, bs.sense, bs.level, bs.connectivity, bs.min_cells };
+    if (L.change && kept_order_begin(e, st)) return -1;
+    if (pull_wait_pictures(e, n, pics, st)) return -1;
+    void *cell_args[] = { &L.args }, *box_args[] = { &bargs };
+    HIP_TRY(hipLaunchKernel(L.fn, L.grid, dim3(256), cell_args, 0, st));
+    HIP_TRY(hipLaunchKernel(reinterpret_cast<const void *>(&h264k::k_cell_boxes), dim3(n_regs), dim3(256), box_args, 0, st));
+    if (pull_end_locked(e, n, pics, st, fence_ev)) return -1;
+    return L.change ? kept_order_end(e, st) : 0;
 }
 
 /* h264bsdmiOutputTensorRemap: the current pictures of the n instances sampled through n_maps coordinate maps by one k_tensor_remap
@@ -1621,7 +1670,7 @@ static int remap_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, ui
     return pull_launch_locked(e, n, pics, st, fn, pull_grid(t.width, t.height, h264k::TRM_COLS, h264k::TRM_ROWS, n_maps), &rargs, fence_ev);
 }
 
-/* What JobSink.tensor_out, tensor_regions, motion_regions, tensor_remap, region_stats, keep_pictures, region_change and cell_maps share: one engine (one device) per call, its mutex, the
+/* What JobSink.tensor_out, tensor_regions, motion_regions, tensor_remap, region_stats, keep_pictures, region_change, cell_maps and cell_boxes share: one engine (one device) per call, its mutex, the
  * refusal of a capturing stream, and, when the caller gave no stream, the wait for the fence and the device's error words.
  * body(e, st, &fence_ev): the call's own *_out_locked. */
 template <typename Body> static int sink_tensor_call(uint32_t n, const SinkTensorPic *pics, void *stream, Body body)
@@ -1717,6 +1766,15 @@ int sink_cell_maps(uint32_t n, const SinkTensorPic *pics, uint32_t n_regions, co
         return cells_out_locked(e, n, pics, n_regions, regions, *spec, st, fence_ev);
     });
 }
+int sink_cell_boxes(uint32_t n, const SinkTensorPic *pics, uint32_t n_regions, const SinkRegion *regions,
+                    const h264bsdmi_cells_spec *cells, const h264bsdmi_boxes_spec *boxes, void *stream)
+{
+    if (!n_regions) return 0;
+    if (!regions || !cells || !boxes) return -1;
+    return sink_tensor_call(n, pics, stream, [&](Engine *e, hipStream_t st, hipEvent_t *fence_ev) {
+        return cell_boxes_out_locked(e, n, pics, n_regions, regions, *cells, *boxes, st, fence_ev);
+    });
+}
 /* JobSink.set_motion (h264bsdmiSetMotionExport): before the instance's first sequence is configured */
 int sink_set_motion(void *user, int on)
 {
@@ -1761,6 +1819,7 @@ int eng_attach(JobSink *sink)
     sink->keep_pictures = sink_keep_pictures;
     sink->region_change = sink_region_change;
     sink->cell_maps = sink_cell_maps;
+    sink->cell_boxes = sink_cell_boxes;
     return 0;
 }
 

@@ -223,6 +223,7 @@ struct h264bsdmi_remap_spec;
 struct h264bsdmi_stats_spec;
 struct h264bsdmi_change_spec;
 struct h264bsdmi_cells_spec;
+struct h264bsdmi_boxes_spec;
 struct JobSink;
 /* one picture of a batched tensor pull (JobSink.tensor_out): the frame buffer `slot` of the instance behind `sink`, its window
  * (x0, y0, w, h), and the picture's index in the output tensor */
@@ -313,6 +314,10 @@ typedef struct JobSink {
      * caller follows up with keep_pictures).  0 = ok; <0 = error, nothing enqueued */
     int (*cell_maps)(uint32_t n, const SinkTensorPic *pics, uint32_t n_regions, const SinkRegion *regions,
                      const struct h264bsdmi_cells_spec *spec, void *stream);
+    /* optional: cell_maps, and behind its launch, on the same stream, the boxes of the connected groups of cells that pass boxes->level,
+     * slice `index` of boxes->data each — h264bsdmiOutputCellBoxes.  Everything said of cell_maps holds.  0 = ok; <0 = error, nothing enqueued */
+    int (*cell_boxes)(uint32_t n, const SinkTensorPic *pics, uint32_t n_regions, const SinkRegion *regions,
+                      const struct h264bsdmi_cells_spec *cells, const struct h264bsdmi_boxes_spec *boxes, void *stream);
 } JobSink;
 
 /* ---------------------------------------------------------------- decoder instance */

@@ -414,6 +414,53 @@ int h264bsdmiOutputCellMaps(u32 n, storage_t *const *pStorage, u32 nRegions, con
                             const h264bsdmi_cells_spec *spec, void *stream,
                             u32 *got, u32 *current, u32 *kept, u32 *picId, u32 *keptPicId);
 
+/* Cell boxes: the step from a cell map to the boxes of the calls above — threshold, connected regions, bounding boxes — made where the
+ * map lies, so that a few hundred bytes per region cross to the host instead of the map.
+ * THE MAPS: the call does everything h264bsdmiOutputCellMaps(..., cells, ...) does, with the same result in cells->data, byte for byte,
+ * keep_after and all the output arrays included.  Behind that launch, on the same stream, it fills the boxes slices.
+ * FOREGROUND: cell (i, j) of region r is foreground iff box ∩ window reaches it (its count is above 0: decided from the geometry,
+ * whether or not COUNT was asked for) and its value in map `plane`, channel `channel`, passes the level: value > level (ABOVE) or
+ * value < level (BELOW), both as u32.  Cells the box or the window do not reach are never foreground, under BELOW too, where their sum
+ * of 0 would pass.
+ * COMPONENTS: a component is a maximal set of foreground cells connected through 4 (left, right, up, down) or 8 (the diagonals too)
+ * neighbours within the slice's grid.  Components of fewer than min_cells cells are dropped.  NUMBERING: the rest are numbered by the
+ * raster index (i * cols + j) of their first cell in raster order, ascending.
+ * SLICE LAYOUT: slice r, at (u32 *)boxes->data + r * (1 + M) * 8 with M = max_boxes, is (1 + M) records of 8 u32, and the call writes
+ * the WHOLE slice with plain stores: the caller does not clear it.
+ *     record 0           found, written, foreground_cells, dropped, 0, 0, 0, 0
+ *                        found: the components that remain; written = min(found, M); dropped: the components removed by min_cells
+ *     records 1..written x, y, w, h, cells, peak, sum_lo, sum_hi        the first `written` components in that order
+ *     the records beyond all zero
+ * x, y, w, h: the bounding rectangle of the component's cells, (x_r + jmin cell, y_r + imin cell) to (x_r + (jmax + 1) cell,
+ * y_r + (imax + 1) cell), intersected with the box and with the window, in the coordinates regions use: { instance, x, y, w, h } is a
+ * valid h264bsdmi_region of the same instance, w, h >= 1.  cells: the number of cells; peak: the largest value under ABOVE, the smallest
+ * under BELOW; sum: the 64-bit sum of the values (16384 cells x 64 * 64 * 255^2 passes 2^32: two words, low first).  Everything is an
+ * integer and exact, and no result depends on scheduling.  got[r] = 0: neither slice r of the maps nor slice r of the boxes is touched.
+ * THE CAP: rows * cols of the grid is at most H264BSDMI_BOXES_MAX_CELLS, so that the labels and the per-component counters of a slice
+ * live in one workgroup's LDS as plain 32-bit words: 1080p fits at cell 16 (68 x 120 = 8160), 32 and 64; 1080p at cell 8 and 4K at
+ * cell 16 do not and are refused.  Larger grids are not part of this interface yet.
+ * -1, before anything is enqueued, nothing written: everything h264bsdmiOutputCellMaps refuses; boxes or boxes->data NULL or data not
+ * 4-byte aligned; max_boxes 0 or above 512; plane not exactly one bit of cells->planes, or DSUM in CHANGE mode (signed); channel not
+ * below the channels of cells->source (COUNT: not 0); sense > 1; connectivity not 4 or 8; min_cells 0; cells->rows * cells->cols above
+ * 16384.  -2: the engine failed, as for the siblings: nothing is written by the host and nothing is marked kept.  nRegions == 0 returns
+ * 0 and launches nothing. */
+#define H264BSDMI_BOXES_MAX_CELLS 16384u   /* rows * cols of a slice that can be labelled */
+#define H264BSDMI_BOXES_MAX_BOXES 512u
+#define H264BSDMI_BOXES_ABOVE 0u           /* foreground: value >  level */
+#define H264BSDMI_BOXES_BELOW 1u           /* foreground: value <  level */
+typedef struct h264bsdmi_boxes_spec {
+    void *data;          /* DEVICE, caller-owned, 4-byte aligned: slice r at (u32 *)data + r * (1 + max_boxes) * 8 */
+    u32 max_boxes;       /* M, 1..512 */
+    u32 plane;           /* ONE H264BSDMI_CELL_* bit, contained in cells->planes; not DSUM (signed) */
+    u32 channel;         /* 0 .. C-1 of cells->source (COUNT: 0) */
+    u32 sense, level;    /* ABOVE / BELOW; unsigned comparison with the u32 of the cell */
+    u32 connectivity;    /* 4 or 8 */
+    u32 min_cells;       /* >= 1: components of fewer cells are dropped before numbering */
+} h264bsdmi_boxes_spec;
+int h264bsdmiOutputCellBoxes(u32 n, storage_t *const *pStorage, u32 nRegions, const h264bsdmi_region *regions,
+                             const h264bsdmi_cells_spec *cells, const h264bsdmi_boxes_spec *boxes, void *stream,
+                             u32 *got, u32 *current, u32 *kept, u32 *picId, u32 *keptPicId);
+
 /* ---- host parse pipeline at scale ----
  * h264bsdDecode() consumes one NAL unit of one stream per call; a caller that feeds hundreds of streams needs the
  * loop of posix/test_h264bsd.c:146-177 for each of them and its own threading.  These entry points move both into

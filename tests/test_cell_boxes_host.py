@@ -1,0 +1,181 @@
+"""What an ACCEPTED cell-boxes call hands to the engine and writes back, without a GPU: api.c's h264bsdmiOutputCellBoxes bound to a
+recording device stand-in (tests/fuzz_asan/mock_engine_boxes.c) by a stand-alone C program (tests/fuzz_asan/cell_boxes.c), which drives
+a fixed sequence of named calls over the instances of tests/test_cell_maps_host.py (and X: as A, on a sink that has cell_maps but no
+cell_boxes) and prints what the sink was given and what the output arrays hold afterwards.  Built with gcc, plain and with Address-,
+UB- and LeakSanitizer: a host program on the CPU that is run directly.  The older stand-ins under tests/fuzz_asan/ know nothing of the
+new sink entry and must still compile."""
+import os
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "h264bsd_amd", "csrc")
+HOST_SOURCES = ("hd_nal.c", "hd_params.c", "hd_slice.c", "hd_dpb.c", "hd_cavlc.c", "hd_resid.c", "hd_mb.c", "hd_core.c", "api.c")
+STREAMS = [os.path.join(ROOT, "tests", "golden", n) for n in ("test_640x360.h264", "test_1920x1080.h264")]
+PICTURE = " spec 0x1000 grid=23x40 cell=16 source=1 crop=1 mode=0 planes=31 thr=0,0,0 keep_after=0"
+CHANGE = " spec 0x1004 grid=68x120 cell=16 source=0 crop=1 mode=1 planes=35 thr=3,2,1 keep_after=0"
+CHAIN = " spec 0x2000 grid=5x6 cell=4 source=2 crop=1 mode=1 planes=63 thr=0,0,255 keep_after=1"
+CAP = " spec 0x1000 grid=128x128 cell=4 source=0 crop=1 mode=0 planes=16 thr=0,0,0 keep_after=0"
+ABOVE = " boxes 0x3000 max=64 plane=2 channel=0 sense=0 level=700 conn=8 min_cells=2"
+BELOW = " boxes 0x3004 max=512 plane=16 channel=2 sense=1 level=40 conn=4 min_cells=1"
+COUNT = " boxes 0x3000 max=1 plane=1 channel=0 sense=0 level=0 conn=8 min_cells=1"
+PEAK = " boxes 0x3000 max=7 plane=16 channel=0 sense=0 level=0 conn=8 min_cells=1"
+BLANK = dict(got="untouched", current="untouched", kept="untouched", picId="untouched", keptPicId="untouched")
+
+pytestmark = pytest.mark.skipif(not shutil.which("gcc"), reason="no gcc")
+
+
+@pytest.fixture(scope="module", params=[None, "address,undefined"], ids=["plain", "sanitizers"])
+def records(request, tmp_path_factory):
+    """name -> the lines of that call's record; "pops": the pop lines in order; "final": the lines behind #final"""
+    exe = os.path.join(str(tmp_path_factory.mktemp("cell_boxes")), "cell_boxes")
+    srcs = [os.path.join(ROOT, "tests", "fuzz_asan", f) for f in ("cell_boxes.c", "mock_engine_boxes.c")] + [os.path.join(CSRC, f) for f in HOST_SOURCES]
+    cmd = ["gcc", "-O1", "-g", "-std=gnu11", "-Wall", f"-I{CSRC}", "-DH264BSD_BUILD"]
+    if request.param:
+        cmd += [f"-fsanitize={request.param}", "-fno-omit-frame-pointer"]
+    b = subprocess.run(cmd + srcs + ["-lpthread", "-lm", "-o", exe], capture_output=True, text=True)
+    assert b.returncode == 0, b.stderr[-3000:]
+    r = subprocess.run([exe] + STREAMS, capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"), timeout=600)
+    assert r.returncode == 0, (r.returncode, r.stdout[-500:], r.stderr[-3000:])
+    err = "\n".join(ln for ln in r.stderr.splitlines() if "left shift of negative" not in ln)      # (mirrors the reference's arithmetic)
+    assert "ERROR: AddressSanitizer" not in err and "ERROR: LeakSanitizer" not in err and "runtime error" not in err, err[-2000:]
+    out = {"pops": []}
+    name = None
+    for ln in r.stdout.splitlines():
+        if ln.startswith("pop "):
+            out["pops"].append(ln)
+        elif ln.startswith("#"):
+            name = ln[1:]
+            assert name not in out
+            out[name] = []
+        else:
+            out[name].append(ln)
+    return out
+
+
+def _arrays(rec):
+    return dict(ln.split("=", 1) for ln in rec if ln and ln[0] != " " and "=" in ln and not ln.startswith(("rc=", "keep ", "cells ", "boxes ")))
+
+
+def _slots(records):
+    """slot of the pops in order: A (picId 100), N, X, B, T, A (101)"""
+    return [int(ln.split("slot=")[1].split()[0]) for ln in records["pops"]]
+
+
+def test_the_pops_are_what_the_calls_should_see(records):
+    pops = records["pops"]
+    assert [p.split()[1] for p in pops] == ["A", "N", "X", "B", "T", "A"]
+    assert "picId=100 size=40x23" in pops[0] and "picId=500" in pops[2] and "picId=200 size=120x68" in pops[3] and "picId=101" in pops[5]
+
+
+def test_the_sink_gets_both_specs_as_the_caller_gave_them(records):
+    slot_a, slot_b = _slots(records)[0], _slots(records)[3]
+    rec = records["picture_a_only"]                                # before anything was kept; B has no current picture yet
+    assert rec[:6] == ["rc=0", "boxes m=1 k=1 stream=0x0", f" pic 0 slot={slot_a} win=0,0,640,360 mr=0,0", " reg 0 index=0 0,0,640,360", PICTURE, BELOW]
+    assert _arrays(rec) == dict(got="1,0", current="1,0", kept="0,0", picId="100,0", keptPicId="0,0")
+    rec = records["picture_both"]                                  # A kept, B not: PICTURE takes both
+    assert rec[:2] == ["rc=0", "boxes m=2 k=2 stream=0x0"] and f" pic 1 slot={slot_b} win=0,0,1920,1080 mr=0,0" in rec
+    assert " reg 1 index=1 0,0,1920,1080" in rec and rec[-7:-5] == [PICTURE, BELOW]
+    assert _arrays(rec) == dict(got="1,1", current="1,1", kept="1,0", picId="100,200", keptPicId="100,0")
+    assert records["count_plane"][-7:-5] == [PICTURE, COUNT]
+    assert records["at_the_cap"][0] == "rc=0" and records["at_the_cap"][-7:-5] == [CAP, PEAK]
+    assert not any(ln.startswith("cells ") for name in ("picture_a_only", "picture_both", "count_plane", "at_the_cap") for ln in records[name])
+
+
+def test_change_mode_names_only_instances_with_both_pictures(records):
+    slot_a = _slots(records)[0]
+    rec = records["nothing_kept"]
+    assert rec[:2] == ["rc=0", "sink: not called"]
+    assert _arrays(rec) == dict(got="0,0", current="1,0", kept="0,0", picId="100,0", keptPicId="0,0")
+    rec = records["a_has_both"]
+    assert rec[:6] == ["rc=0", "boxes m=1 k=1 stream=0x0", f" pic 0 slot={slot_a} win=0,0,640,360 mr=0,0", " reg 0 index=0 0,0,640,360", CHANGE, ABOVE]
+    assert _arrays(rec) == dict(got="1,0", current="1,1", kept="1,0", picId="100,200", keptPicId="100,0")
+    rec = records["a_not_current"]
+    assert rec[:2] == ["rc=0", "sink: not called"] and _arrays(rec) == dict(got="0", current="0", kept="1", picId="0", keptPicId="100")
+    rec = records["a_next_picture"]
+    assert rec[1] == "boxes m=1 k=1 stream=0x0" and rec[2] == f" pic 0 slot={_slots(records)[5]} win=0,0,640,360 mr=0,0"
+    assert _arrays(rec) == dict(got="1", current="1", kept="1", picId="101", keptPicId="100")
+
+
+def test_explicit_regions_in_both_modes(records):
+    slot_a, slot_b = _slots(records)[0], _slots(records)[3]
+    rec = records["boxes_mixed_order"]                             # B, A: B has nothing kept, the regions that name A (instance 1) are 0 and 2
+    assert rec[:7] == ["rc=0", "boxes m=1 k=2 stream=0x5000", f" pic 1 slot={slot_a} win=0,0,640,360 mr=0,0", " reg 0 index=0 0,0,64,64",
+                       " reg 0 index=2 700,10,8,8", CHANGE, ABOVE]
+    assert _arrays(rec) == dict(got="1,0,1,0", current="1,1", kept="0,1", picId="200,100", keptPicId="0,100")
+    rec = records["picture_boxes"]                                 # A is named first: picture 0 of the list, though instance 1 of the call
+    assert rec[:8] == ["rc=0", "boxes m=2 k=4 stream=0x5000", f" pic 1 slot={slot_a} win=0,0,640,360 mr=0,0", f" pic 0 slot={slot_b} win=0,0,1920,1080 mr=0,0",
+                       " reg 0 index=0 0,0,64,64", " reg 1 index=1 -5,7,100,30", " reg 0 index=2 700,10,8,8", " reg 1 index=3 0,0,640,360"]
+    assert _arrays(rec) == dict(got="1,1,1,1", current="1,1", kept="0,1", picId="200,100", keptPicId="0,100")
+    rec = records["null_arrays"]
+    assert rec[0] == "rc=0" and rec[1].startswith("boxes m=1 k=1")
+    assert _arrays(rec) == dict(got="1,0", current="null", kept="null", picId="null", keptPicId="null")
+    rec = records["no_regions"]
+    assert rec[:2] == ["rc=0", "sink: not called"] and _arrays(rec)["got"] == "null"
+
+
+def test_failed_calls_write_nothing_and_mark_nothing(records):
+    rec = records["boxes_fail"]
+    assert rec[0] == "rc=-2" and rec[1].startswith("boxes m=1 k=1") and not any(ln.startswith("keep ") for ln in rec)
+    assert _arrays(rec) == BLANK
+    rec = records["picture_fails"]
+    assert rec[0] == "rc=-2" and rec[1].startswith("boxes m=2 k=2") and _arrays(rec) == BLANK
+    rec = records["keep_after_fails"]
+    assert rec[0] == "rc=-2" and rec[1].startswith("boxes m=1 k=1") and "keep m=2 k=0 stream=0x0" in rec
+    assert _arrays(rec) == BLANK
+    assert _arrays(records["b_still_not_kept"]) == dict(got="1,0", current="1,1", kept="1,0", picId="100,200", keptPicId="100,0")
+
+
+def test_keep_after_follows_the_boxes_and_keeps_everyone(records):
+    slot_a, slot_b = _slots(records)[0], _slots(records)[3]
+    rec = records["keep_after"]
+    assert rec[0] == "rc=0" and rec[1] == "boxes m=1 k=1 stream=0x0" and CHAIN in rec
+    at = rec.index("keep m=2 k=0 stream=0x0")
+    assert at == rec.index(ABOVE) + 1 == rec.index(CHAIN) + 2
+    assert rec[at + 1:at + 3] == [f" pic 0 slot={slot_a} win=0,0,640,368 mr=0,0", f" pic 1 slot={slot_b} win=0,0,1920,1088 mr=0,0"]
+    assert _arrays(rec) == dict(got="1,0", current="1,1", kept="1,0", picId="100,200", keptPicId="100,0")
+    rec = records["both_kept"]
+    assert rec[1] == "boxes m=2 k=2 stream=0x0" and f" pic 1 slot={slot_b} win=0,0,1920,1080 mr=0,0" in rec
+    assert _arrays(rec) == dict(got="1,1", current="1,1", kept="1,1", picId="100,200", keptPicId="100,200")
+
+
+def test_the_maps_entry_goes_on_calling_cell_maps(records):
+    rec = records["maps_entry_still_calls_cell_maps"]
+    assert rec[:2] == ["rc=0", "cells m=2 k=2 stream=0x0"] and CHANGE in rec and not any(ln.startswith((" boxes", "boxes ")) for ln in rec)
+
+
+@pytest.mark.parametrize("name", ["refused_repeated", "refused_capture", "refused_got_null", "refused_boxes_null", "refused_cells_threshold",
+                                  "refused_above_the_cap", "refused_data_null", "refused_data_misaligned", "refused_max_boxes", "refused_no_boxes",
+                                  "refused_plane_not_asked", "refused_two_planes", "refused_dsum", "refused_channel", "refused_sense",
+                                  "refused_connectivity", "refused_min_cells", "refused_no_keep_change", "refused_sink_without_boxes"])
+def test_refused_calls_call_no_sink_and_write_nothing(records, name):
+    rec = records[name]
+    assert rec[:2] == ["rc=-1", "sink: not called"]
+    assert all(v in ("untouched", "null") for v in _arrays(rec).values()), rec
+
+
+def test_sinks_that_lack_an_entry_serve_what_they_can(records):
+    rec = records["no_keep_picture"]                               # cannot keep: PICTURE mode is served
+    assert rec[:2] == ["rc=0", "boxes m=2 k=2 stream=0x0"] and rec[-7:-5] == [PICTURE, BELOW]
+    assert _arrays(rec) == dict(got="1,1", current="1,1", kept="1,0", picId="100,400", keptPicId="100,0")
+    rec = records["sink_without_boxes_serves_maps"]                # cannot label: the maps alone are served
+    assert rec[:2] == ["rc=0", "cells m=2 k=2 stream=0x0"] and rec[-6] == PICTURE
+    assert _arrays(rec) == dict(got="1,1", current="1,1", kept="1,0", picId="100,500", keptPicId="100,0")
+
+
+def test_the_twins_output_queue_is_untouched(records):
+    final = records["final"]
+    assert "twin=1" in final and final[0].split("=")[1] == final[1].split("=")[1]
+
+
+def test_the_older_stand_ins_compile_and_leave_the_new_entry_null(tmp_path):
+    """mock_engine.c, mock_engine_keep.c and mock_engine_cells.c set the entries they know by name: JobSink grew at its end, and what
+    they do not set is the calloc'ed NULL (hd_create) that api.c reads as "this sink has no cell boxes" """
+    for f in ("mock_engine.c", "mock_engine_keep.c", "mock_engine_cells.c", "stub_engine.c"):
+        path = os.path.join(ROOT, "tests", "fuzz_asan", f)
+        assert "cell_boxes" not in open(path).read()
+        b = subprocess.run(["gcc", "-O1", "-std=gnu11", "-Wall", "-Werror", f"-I{CSRC}", "-DH264BSD_BUILD", "-c", path, "-o", str(tmp_path / (f + ".o"))],
+                           capture_output=True, text=True)
+        assert b.returncode == 0, b.stderr[-3000:]
