@@ -10,11 +10,12 @@ from .capi import (  # noqa: F401
     TensorSpec, ColourSpec, ResizeSpec, pull_tensor, Region, pull_regions, MotionSpec, pull_motion, Remap, RemapSpec, pull_remap, affine_maps,
     StatsSpec, RegionStats, pull_stats, stats_record_bytes,
     ChangeSpec, RegionChange, keep_pictures, pull_change, change_record_bytes,
+    ShiftSpec, RegionShift, pull_shift, shift_record_bytes,
     CellsSpec, CellMaps, pull_cells,
     BoxesSpec, CellBoxes, pull_boxes,
 )
 
 # 0.2: pull_remap / affine_maps (h264bsdmiOutputTensorRemap); 0.3: pull_stats (h264bsdmiOutputRegionStats);
 # 0.4: keep_pictures / pull_change (h264bsdmiKeepCurrentPictures, h264bsdmiOutputRegionChange); 0.5: pull_cells (h264bsdmiOutputCellMaps)
-# 0.6: pull_boxes (h264bsdmiOutputCellBoxes)
-__version__ = "0.6.0"
+# 0.6: pull_boxes (h264bsdmiOutputCellBoxes); 0.7: pull_shift (h264bsdmiOutputRegionShift)
+__version__ = "0.7.0"

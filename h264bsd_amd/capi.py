@@ -28,7 +28,7 @@ EXPORTED_SYMBOLS = [
     "h264bsdCroppingParams", "h264bsdSampleAspectRatio", "h264bsdCheckValidParamSets", "h264bsdFlushBuffer",
     "h264bsdProfile", "h264bsdAlloc", "h264bsdFree", "h264bsdConvertToRGBA", "h264bsdConvertToBGRA",
     "h264bsdConvertToYCbCrA",
-    "h264bsdmiInitCapture", "h264bsdmiNextOutputInfo", "h264bsdmiNextOutputPictureDevice", "h264bsdmiNextOutputTensorBatch", "h264bsdmiNextOutputTensorBatchColour", "h264bsdmiNextOutputTensorBatchResize", "h264bsdmiOutputTensorRegions", "h264bsdmiOutputTensorRemap", "h264bsdmiSetMotionExport", "h264bsdmiOutputMotionRegions", "h264bsdmiOutputRegionStats", "h264bsdmiKeepCurrentPictures", "h264bsdmiOutputRegionChange", "h264bsdmiOutputCellMaps", "h264bsdmiOutputCellBoxes", "h264bsdmiJobFinalize", "h264bsdmiDeviceCount", "h264bsdmiSetDevice", "h264bsdmiFlush", "h264bsdmiFlushAsync", "h264bsdmiDeviceErrors",
+    "h264bsdmiInitCapture", "h264bsdmiNextOutputInfo", "h264bsdmiNextOutputPictureDevice", "h264bsdmiNextOutputTensorBatch", "h264bsdmiNextOutputTensorBatchColour", "h264bsdmiNextOutputTensorBatchResize", "h264bsdmiOutputTensorRegions", "h264bsdmiOutputTensorRemap", "h264bsdmiSetMotionExport", "h264bsdmiOutputMotionRegions", "h264bsdmiOutputRegionStats", "h264bsdmiKeepCurrentPictures", "h264bsdmiOutputRegionChange", "h264bsdmiOutputRegionShift", "h264bsdmiOutputCellMaps", "h264bsdmiOutputCellBoxes", "h264bsdmiJobFinalize", "h264bsdmiDeviceCount", "h264bsdmiSetDevice", "h264bsdmiFlush", "h264bsdmiFlushAsync", "h264bsdmiDeviceErrors",
     "h264bsdmiDecodePicture", "h264bsdmiDecodePictureBatch", "h264bsdmiNextOutputPictureBatch", "h264bsdmiPullAndDecodePictureBatch", "h264bsdmiSetParserThreads", "h264bsdmiSetInputReadOnly", "h264bsdmiSetCopyElision",
     "h264bsdmiReplayCreate", "h264bsdmiReplayCreateStaggered", "h264bsdmiReplayCreateDesync", "h264bsdmiReplayCreateSched", "h264bsdmiReplayReschedule", "h264bsdmiReplayDestroy", "h264bsdmiReplayRun", "h264bsdmiReplaySync",
     "h264bsdmiReplayFetch", "h264bsdmiReplayChecksums", "h264bsdmiReplayConvert", "h264bsdmiReplayFetchConverted",
@@ -95,6 +95,12 @@ class ChangeSpec(ctypes.Structure):
                 ("threshold", ctypes.c_uint32 * 3), ("keep_after", ctypes.c_uint32)]
 
 
+class ShiftSpec(ctypes.Structure):
+    """h264bsdmi_shift_spec (include/h264bsd_mi355x.h)"""
+    _fields_ = [("data", ctypes.c_void_p), ("radius", ctypes.c_uint32), ("surface", ctypes.c_uint32), ("crop", ctypes.c_uint32),
+                ("keep_after", ctypes.c_uint32)]
+
+
 class CellsSpec(ctypes.Structure):
     """h264bsdmi_cells_spec (include/h264bsd_mi355x.h)"""
     _fields_ = [("data", ctypes.c_void_p), ("cols", ctypes.c_uint32), ("rows", ctypes.c_uint32), ("cell", ctypes.c_uint32),
@@ -108,6 +114,7 @@ class BoxesSpec(ctypes.Structure):
                 ("sense", ctypes.c_uint32), ("level", ctypes.c_uint32), ("connectivity", ctypes.c_uint32), ("min_cells", ctypes.c_uint32)]
 
 
+SHIFT_MAX_RADIUS, SHIFT_MAX_SIDE = 16, 4096                                       # H264BSDMI_SHIFT_MAX_*
 BOXES_MAX_CELLS, BOXES_MAX_BOXES = 16384, 512                                     # H264BSDMI_BOXES_MAX_*
 BOXES_SENSES = {"above": 0, "below": 1}                                          # H264BSDMI_BOXES_*
 # per mode (H264BSDMI_CELLS_PICTURE, _CHANGE): name -> H264BSDMI_CELL_*, in the order of the maps
@@ -251,6 +258,9 @@ def _declare(L, harness):
     L.h264bsdmiOutputRegionChange.argtypes = [u32, ctypes.POINTER(vp), u32, ctypes.POINTER(Region), ctypes.POINTER(ChangeSpec), vp,
                                               P32, P32, P32, P32, P32]
     L.h264bsdmiOutputRegionChange.restype = ctypes.c_int
+    L.h264bsdmiOutputRegionShift.argtypes = [u32, ctypes.POINTER(vp), u32, ctypes.POINTER(Region), ctypes.POINTER(ShiftSpec), vp,
+                                             P32, P32, P32, P32, P32]
+    L.h264bsdmiOutputRegionShift.restype = ctypes.c_int
     L.h264bsdmiOutputCellMaps.argtypes = [u32, ctypes.POINTER(vp), u32, ctypes.POINTER(Region), ctypes.POINTER(CellsSpec), vp,
                                           P32, P32, P32, P32, P32]
     L.h264bsdmiOutputCellMaps.restype = ctypes.c_int
@@ -563,7 +573,7 @@ def pull_batch(decoders, frame_bytes=None):
 
 
 def _regions_arg(who, n, regions):
-    """the regions of pull_regions, pull_motion, pull_stats and pull_change, checked: (K, the Region array); None (one whole window per decoder): (n, None)"""
+    """the regions of pull_regions, pull_motion, pull_stats, pull_change and pull_shift, checked: (K, the Region array); None (one whole window per decoder): (n, None)"""
     if regions is None:
         K, regs = n, None
     else:
@@ -966,6 +976,70 @@ def pull_change(decoders, regions=None, source="y", bins=0, threshold=0, crop=Tr
             raise RuntimeError(f"h264bsdmiOutputRegionChange failed ({rc})")
     cur, kept, ids, kept_ids = [list(a)[:n] for a in per]
     return RegionChange(out, C, bins, list(got)[:K], cur, kept, ids, kept_ids)
+
+
+def shift_record_bytes(radius, surface):
+    """the stride of one record of h264bsdmiOutputRegionShift: 32 bytes, with the surface 32 + 4 (D D + 1), D = 2 radius + 1"""
+    if not isinstance(radius, int) or isinstance(radius, bool) or not 0 <= radius <= SHIFT_MAX_RADIUS:
+        raise ValueError(f"shift_record_bytes: radius is an int in 0..{SHIFT_MAX_RADIUS}, not {radius}")
+    D = 2 * radius + 1
+    return 32 + 4 * (D * D + 1) if surface else 32
+
+
+class RegionShift:
+    """what pull_shift returns: count, dx, dy, best, still, ties [R] int32 (best and still are u32 in the record: above 2^31 they read
+    negative, as the u32 fields of RegionChange do; & 0xFFFFFFFF in int64 gives the value); surface [R, D, D] int32 or None,
+    surface[r, dy + radius, dx + radius] — views of `records` ([R, stride] uint8, one allocation, the C layout); got [R], and per decoder
+    current, kept, pic_id, kept_pic_id, lists of ints"""
+
+    def __init__(self, records, radius, surface, got, current, kept, pic_id, kept_pic_id):
+        import torch
+        w32 = records.view(torch.int32)
+        D = 2 * radius + 1
+        self.records, self.radius = records, radius
+        self.count, self.dx, self.dy, self.best, self.still, self.ties = w32[:, 0], w32[:, 2], w32[:, 3], w32[:, 4], w32[:, 5], w32[:, 6]
+        self.surface = w32[:, 8:8 + D * D].unflatten(1, (D, D)) if surface else None
+        self.got, self.current, self.kept, self.pic_id, self.kept_pic_id = got, current, kept, pic_id, kept_pic_id
+
+    def moved(self, regions):
+        """the regions the call was given, each translated by its (dx, dy), for those with got: (decoder_index, x + dx, y + dy, w, h),
+        ready for pull_regions / pull_stats / pull_shift — the tracking step.  After pull_shift(regions=None) the records are of whole
+        windows, whose sizes this object does not hold: pass them as [(i, 0, 0, W_i, H_i), ...] (None raises ValueError).  One copy of
+        two columns to the host."""
+        if regions is None:
+            raise ValueError("RegionShift.moved: pass the regions of the call; after regions=None, the windows as [(i, 0, 0, W, H), ...]")
+        regions = [tuple(r) for r in regions]
+        if len(regions) != len(self.got):
+            raise ValueError(f"RegionShift.moved: {len(regions)} regions for {len(self.got)} records")
+        d = self.records.view(self.count.dtype)[:, 2:4].cpu().tolist()
+        return [(i, x + d[k][0], y + d[k][1], w, h) for k, (i, x, y, w, h) in enumerate(regions) if self.got[k]]
+
+
+def pull_shift(decoders, regions=None, radius=4, crop=True, surface=False, keep=False, out=None, stream=None):
+    """h264bsdmiOutputRegionShift: where the boxes of the decoders' KEPT pictures (keep_pictures) lie in their CURRENT pictures — a SAD
+    search over every displacement |dx|, |dy| <= radius (0..16) in luma, by one kernel launch where the two pictures lie; nothing is
+    popped and no pixel is pulled.  regions, crop, out and stream as for pull_change (w, h <= 4096; out: [R, shift_record_bytes(radius,
+    surface)]).  A record: count, the displacement (dx, dy) of the smallest SAD (ties: the smallest dx^2 + dy^2, then dy, then dx),
+    best = that SAD, still = SAD(0, 0), ties, and with surface=True all (2 radius + 1)^2 SADs.  The current picture is replicated at
+    the border of the source window.  got[r] = 1 only where the decoder has a current AND a kept picture: other records are left
+    untouched.  keep=True: behind the search the current pictures become the kept ones, as for pull_change.  Returns a RegionShift."""
+    import torch
+    n = len(decoders)
+    K, regs = _regions_arg("pull_shift", n, regions)
+    if regs is not None and any(r.w > SHIFT_MAX_SIDE or r.h > SHIFT_MAX_SIDE for r in regs[:K]):
+        raise ValueError(f"pull_shift: a region is at most {SHIFT_MAX_SIDE} x {SHIFT_MAX_SIDE}")
+    shape = (K, shift_record_bytes(radius, surface))
+    out, stream = _out_and_stream("pull_shift", out, shape, torch.uint8, stream, aligned=True)
+    spec = ShiftSpec(out.data_ptr(), radius, 1 if surface else 0, 1 if crop else 0, 1 if keep else 0)
+    got = (ctypes.c_uint32 * max(K, 1))()
+    per = [(ctypes.c_uint32 * max(n, 1))() for _ in range(4)]                # current, kept, picId, keptPicId
+    if n:
+        rc = api_lib().h264bsdmiOutputRegionShift(n, (ctypes.c_void_p * n)(*[d._st for d in decoders]), K, regs, ctypes.byref(spec),
+                                                  stream.cuda_stream, got, *per)
+        if rc != 0:
+            raise RuntimeError(f"h264bsdmiOutputRegionShift failed ({rc})")
+    cur, kept, ids, kept_ids = [list(a)[:n] for a in per]
+    return RegionShift(out, radius, bool(surface), list(got)[:K], cur, kept, ids, kept_ids)
 
 
 class CellMaps:

@@ -362,7 +362,7 @@ int h264bsdmiNextOutputTensorBatchResize(u32 n, storage_t *const *dec, const h26
 }
 
 /* ---- The pulls of CURRENT pictures (pop_output, drop_current): h264bsdmiOutputTensorRegions, h264bsdmiOutputTensorRemap,
- * h264bsdmiOutputMotionRegions, h264bsdmiOutputRegionStats, h264bsdmiOutputRegionChange (which needs the kept picture as well),
+ * h264bsdmiOutputMotionRegions, h264bsdmiOutputRegionStats, h264bsdmiOutputRegionChange and h264bsdmiOutputRegionShift (which need the kept picture as well),
  * h264bsdmiOutputCellMaps and h264bsdmiOutputCellBoxes (which need it in CHANGE mode), and their small sibling h264bsdmiKeepCurrentPictures (the picture list only).  Each checks its own spec; everything else is one path:
  *   regions_refused   got, the count and the range of every region — before the instances are looked at
  *   pull_begin        dec and the instances (of this library, with the sink entry the call needs, distinct), then the lists
@@ -370,7 +370,7 @@ int h264bsdmiNextOutputTensorBatchResize(u32 n, storage_t *const *dec, const h26
  *   pull_regions      the regions (or one whole window per instance) of the pictures that exist, each with its rectangle
  *   pull_finish       after the sink: got, box, current and picId — unless the sink failed (-2 writes nothing) — and the lists freed
  * A refused call returns -1 and has called no sink, written nothing; no call pops anything. */
-enum { PULL_REGIONS, PULL_REMAP, PULL_MOTION, PULL_STATS, PULL_CHANGE, PULL_KEEP, PULL_CELLS, PULL_BOXES };
+enum { PULL_REGIONS, PULL_REMAP, PULL_MOTION, PULL_STATS, PULL_CHANGE, PULL_KEEP, PULL_CELLS, PULL_BOXES, PULL_SHIFT };
 #define NO_PIC 0xFFFFFFFFu
 typedef struct CurrentPull {
     u32 n, m, k;                /* instances; pictures and items gathered so far */
@@ -380,7 +380,7 @@ typedef struct CurrentPull {
     SinkRegion *regs;           /* the items for the sink: regions, or (PULL_REMAP) maps */
     SinkRemap *maps;
     int kind;                   /* PULL_* */
-    int vs_kept;                /* only instances that have a kept picture too: PULL_CHANGE, and PULL_CELLS / PULL_BOXES in CHANGE mode */
+    int vs_kept;                /* only instances that have a kept picture too: PULL_CHANGE, PULL_SHIFT, and PULL_CELLS / PULL_BOXES in CHANGE mode */
 } CurrentPull;
 
 /* regions == NULL: no regions at all, or (whole: one whole window per instance) exactly n */
@@ -406,6 +406,7 @@ static int sink_pulls(const ApiDec *a, int kind)
     case PULL_MOTION: return k->motion_regions != NULL && a->motion;          /* ... and motion export is on */
     case PULL_STATS:  return k->tensor_regions != NULL && k->region_stats != NULL;
     case PULL_CHANGE: return k->tensor_regions != NULL && k->region_change != NULL && k->keep_pictures != NULL;
+    case PULL_SHIFT:  return k->tensor_regions != NULL && k->region_shift != NULL && k->keep_pictures != NULL;
     case PULL_KEEP:   return k->tensor_regions != NULL && k->keep_pictures != NULL;
     case PULL_CELLS:  return k->tensor_regions != NULL && k->cell_maps != NULL;      /* CHANGE mode: keep_pictures too (the entry asks) */
     case PULL_BOXES:  return k->tensor_regions != NULL && k->cell_maps != NULL && k->cell_boxes != NULL;
@@ -424,7 +425,7 @@ static int pull_begin(CurrentPull *c, u32 n, storage_t *const *dec, u32 n_items,
     }
     *c = (CurrentPull){ n, 0, 0, dec, (SinkTensorPic *)malloc((n ? n : 1) * sizeof(SinkTensorPic)), (u32 *)malloc((n ? n : 1) * sizeof(u32)),
                         kind == PULL_REMAP ? NULL : (SinkRegion *)malloc((n_items ? n_items : 1) * sizeof(SinkRegion)),
-                        kind == PULL_REMAP ? (SinkRemap *)malloc((n_items ? n_items : 1) * sizeof(SinkRemap)) : NULL, kind, kind == PULL_CHANGE };
+                        kind == PULL_REMAP ? (SinkRemap *)malloc((n_items ? n_items : 1) * sizeof(SinkRemap)) : NULL, kind, kind == PULL_CHANGE || kind == PULL_SHIFT };
     if (!c->pics || !c->pic_of || !(c->regs || c->maps)) { pull_free(c); return -1; }
     for (u32 i = 0; i < n; i++) c->pic_of[i] = NO_PIC;
     return 0;
@@ -607,6 +608,35 @@ int h264bsdmiOutputRegionChange(u32 n, storage_t *const *dec, u32 nRegions, cons
     const h264bsdmi_tensor_spec window = { spec->data, 1, 1, 0, 0, 0, spec->crop, 1, { 0, 0, 0 }, { 1, 1, 1 } };
     pull_regions(&c, nRegions, regions, &window, &REFERENCE_COLOUR, 1, 1, 0);
     int failed = c.k && c.pics[0].sink->region_change(c.m, c.pics, c.k, c.regs, spec, stream);
+    if (spec->keep_after && !failed) failed = k.m && k.pics[0].sink->keep_pictures(k.m, k.pics, stream);
+    if (!failed) {
+        for (u32 i = 0; i < n; i++) {
+            const ApiDec *a = dec_of(dec[i]);
+            if (kept) kept[i] = has_kept_picture(a) ? 1 : 0;
+            if (keptPicId) keptPicId[i] = has_kept_picture(a) ? a->kept_id : 0;
+        }
+        if (spec->keep_after) mark_kept(&k);
+    }
+    if (spec->keep_after) pull_free(&k);
+    return pull_finish(&c, failed, nRegions, got, NULL, current, picId);
+}
+
+/* Where the boxes of the kept pictures lie in the current ones: h264bsdmiOutputRegionChange's host path with the sink's region_shift */
+int h264bsdmiOutputRegionShift(u32 n, storage_t *const *dec, u32 nRegions, const h264bsdmi_region *regions,
+                               const h264bsdmi_shift_spec *spec, void *stream,
+                               u32 *got, u32 *current, u32 *kept, u32 *picId, u32 *keptPicId)
+{
+    CurrentPull c, k;
+    if (!spec || !spec->data || ((uintptr_t)spec->data & 7u) || spec->radius > H264BSDMI_SHIFT_MAX_RADIUS || spec->surface > 1 || spec->crop > 1 ||
+        spec->keep_after > 1) return -1;
+    if (regions_refused(n, nRegions, regions, got, 1)) return -1;
+    for (u32 r = 0; regions && r < nRegions; r++)
+        if (regions[r].w > H264BSDMI_SHIFT_MAX_SIDE || regions[r].h > H264BSDMI_SHIFT_MAX_SIDE) return -1;
+    if (pull_begin(&c, n, dec, nRegions, PULL_SHIFT)) return -1;
+    if (spec->keep_after && keep_begin(&k, n, dec)) { pull_free(&c); return -1; }
+    const h264bsdmi_tensor_spec window = { spec->data, 1, 1, 0, 0, 0, spec->crop, 1, { 0, 0, 0 }, { 1, 1, 1 } };
+    pull_regions(&c, nRegions, regions, &window, &REFERENCE_COLOUR, 1, 1, 0);
+    int failed = c.k && c.pics[0].sink->region_shift(c.m, c.pics, c.k, c.regs, spec, stream);
     if (spec->keep_after && !failed) failed = k.m && k.pics[0].sink->keep_pictures(k.m, k.pics, stream);
     if (!failed) {
         for (u32 i = 0; i < n; i++) {

@@ -39,6 +39,7 @@
 #include "kernels/k_region_stats.hip.h"
 #include "kernels/k_keep.hip.h"
 #include "kernels/k_region_change.hip.h"
+#include "kernels/k_region_shift.hip.h"
 #include "kernels/k_cell_maps.hip.h"
 #include "kernels/k_cell_boxes.hip.h"
 #include "engine.h"
@@ -158,11 +159,11 @@ constexpr unsigned CONVERT_WGS = CONVERT_WGS_N;      /* workgroups per picture o
 constexpr uint32_t LANE_DBK_WAVES = LANE_DBK_WAVES_N;
 
 /* the item stride of the tensor pulls' staging ring: k_tensor_out / k_tensor_resize read TensorItems, k_tensor_aa AaItems, k_tensor_roi
- * RoiItems, k_motion_roi MotionItems, k_tensor_remap RemapItems, k_region_stats StatsItems, k_keep KeepItems, k_region_change ChangeItems,
+ * RoiItems, k_motion_roi MotionItems, k_tensor_remap RemapItems, k_region_stats StatsItems, k_keep KeepItems, k_region_change ChangeItems, k_region_shift ShiftItems,
  * k_cell_maps CellItems (k_cell_boxes: the same, and its BoxItems in slots of their own behind them) */
 constexpr size_t TITEM_BYTES = std::max({ sizeof(h264k::TensorItem), sizeof(h264k::AaItem), sizeof(h264k::RoiItem), sizeof(h264k::MotionItem),
                                           sizeof(h264k::RemapItem), sizeof(h264k::StatsItem), sizeof(h264k::KeepItem), sizeof(h264k::ChangeItem),
-                                          sizeof(h264k::CellItem), sizeof(h264k::BoxItem) });
+                                          sizeof(h264k::CellItem), sizeof(h264k::BoxItem), sizeof(h264k::ShiftItem) });
 struct TItemSlot { uint8_t bytes[TITEM_BYTES]; };
 struct Engine {
     std::mutex mu;
@@ -187,7 +188,7 @@ struct Engine {
     /* tensor pulls (tensor_out_locked): the staging ring of their items; fence events that no instance holds any more */
     Staged<TItemSlot> titems;
     std::vector<Fence *> fences;
-    /* region and change statistics with row bands (stats_scratch_locked): the regions' tickets (STATS_MAX_PARTIALS words, zero between
+    /* region and change statistics and the region shift with row bands (stats_scratch_locked): the regions' tickets (STATS_MAX_PARTIALS words, zero between
      * launches), then the bands' partial records; stats_ev is recorded behind the latest launch that used them, and the next one waits for it */
     DeviceMem<uint8_t> d_stats;
     Event stats_ev;
@@ -1381,8 +1382,8 @@ static int motion_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, u
                               pull_grid(m.width, m.height, h264k::TAA_COLS, h264k::TAA_ROWS, n_regs), &margs, fence_ev);
 }
 
-/* The scratch in which the row bands of k_region_stats and k_region_change meet (Engine.d_stats), allocated at its first use for the
- * larger of the two records; two launches must not use it at once: st waits for the event behind the previous one (the caller records
+/* The scratch in which the row bands of k_region_stats, k_region_change and k_region_shift meet (Engine.d_stats), allocated at its first
+ * use for the largest of the three (two records and a partial SAD surface); two launches must not use it at once: st waits for the event behind the previous one (the caller records
  * stats_ev behind its launch). */
 static int stats_scratch_locked(Engine *e, hipStream_t st, uint32_t **tickets, uint8_t **partials)
 {
@@ -1390,7 +1391,7 @@ static int stats_scratch_locked(Engine *e, hipStream_t st, uint32_t **tickets, u
     if (!e->d_stats) {
         DeviceMem<uint8_t> fresh;
         HIP_TRY(e->stats_ev.create(hipEventDisableTiming));
-        HIP_TRY(fresh.alloc(ticket_bytes + (size_t)h264k::STATS_MAX_PARTIALS * std::max(h264k::STATS_MAX_RECORD, h264k::CHANGE_MAX_RECORD)));
+        HIP_TRY(fresh.alloc(ticket_bytes + (size_t)h264k::STATS_MAX_PARTIALS * std::max({ h264k::STATS_MAX_RECORD, h264k::CHANGE_MAX_RECORD, h264k::SHIFT_MAX_PARTIAL })));
         HIP_TRY(hipMemsetAsync(fresh, 0, ticket_bytes, st));
         e->d_stats = std::move(fresh);
     } else HIP_TRY(hipStreamWaitEvent(st, e->stats_ev, 0));
@@ -1536,6 +1537,55 @@ static int change_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, u
     return kept_order_end(e, st);
 }
 
+/* h264bsdmiOutputRegionShift: one ShiftItem per region — the current picture and the kept picture of its instance, the record, box ∩
+ * window and the window itself (the search clamps there), in luma samples of the coded frame — and ONE k_region_shift launch of S row
+ * bands per region, S chosen as in stats_out_locked; with S > 1 the bands' partial SAD surfaces meet in the same scratch.  The kept
+ * pictures' ordering as in change_out_locked; the sink does not look at keep_after. */
+static int shift_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, uint32_t n_regs, const SinkRegion *regs,
+                            const h264bsdmi_shift_spec &sp, hipStream_t st, hipEvent_t *fence_ev)
+{
+    if (!sp.data || (reinterpret_cast<uintptr_t>(sp.data) & 7u) || sp.radius > H264BSDMI_SHIFT_MAX_RADIUS || sp.surface > 1u || sp.crop > 1u ||
+        sp.keep_after > 1u) return -1;
+    if (n_regs > 65535u) return -1;                                     /* grid.y */
+    if (!pull_pictures_ok(n, pics, true, false) || !pull_regions_ok(n, n_regs, regs, 1u, 1u)) return -1;
+    for (uint32_t r = 0; r < n_regs; r++)
+        if (regs[r].w > H264BSDMI_SHIFT_MAX_SIDE || regs[r].h > H264BSDMI_SHIFT_MAX_SIDE) return -1;        /* the 32-bit sums */
+    for (uint32_t i = 0; i < n; i++) {
+        const StreamCtx *s = pic_stream(pics[i]);
+        if (!s->d_kept || s->kept_wmb != s->wmb || s->kept_hmb != s->hmb) return -1;
+    }
+    if (pull_begin_locked(e, n, pics, n_regs)) return -1;
+    h264k::ShiftItem *items = e->titems.host<h264k::ShiftItem>();
+    const uint32_t stride = h264k::shift_record_bytes(sp.radius, sp.surface);
+    uint32_t tallest = 1u;
+    for (uint32_t r = 0; r < n_regs; r++) {
+        const SinkRegion &g = regs[r];
+        const SinkTensorPic &p = pics[g.pic];
+        const StreamCtx *s = pic_stream(p);
+        const int64_t bx0 = std::max<int64_t>(g.x, 0), bx1 = std::min<int64_t>((int64_t)g.x + g.w, p.w);
+        const int64_t by0 = std::max<int64_t>(g.y, 0), by1 = std::min<int64_t>((int64_t)g.y + g.h, p.h);
+        h264k::ShiftItem it{ s->d_frames + (size_t)p.slot * s->frame_bytes, s->d_kept.get(), static_cast<uint8_t *>(sp.data) + (size_t)g.index * stride,
+                             s->wmb, 0u, 0u, 0u, 0u, p.x0, p.y0, p.x0 + p.w, p.y0 + p.h };
+        if (bx1 > bx0 && by1 > by0) {
+            it.x0 = p.x0 + (uint32_t)bx0; it.x1 = p.x0 + (uint32_t)bx1;
+            it.y0 = p.y0 + (uint32_t)by0; it.y1 = p.y0 + (uint32_t)by1;
+            tallest = std::max(tallest, ((it.y1 + 15u) >> 4) - (it.y0 >> 4));
+        }
+        items[r] = it;
+    }
+    const uint32_t S = n_regs >= h264k::STATS_MAX_PARTIALS ? 1u : std::min(h264k::STATS_MAX_PARTIALS / n_regs, tallest);
+    /* from radius 4 on a thread takes three quads of displacements per template dword, below that one: as measured, each is the faster
+     * on its side (docs/EXPERIMENTS.md, "Region shift") */
+    const void *fn = sp.radius >= h264k::SHIFT_QUADS_FROM ? reinterpret_cast<const void *>(&h264k::k_region_shift<h264k::SHIFT_QUADS>)
+                                                           : reinterpret_cast<const void *>(&h264k::k_region_shift<1u>);
+    h264k::ShiftArgs sargs{ e->titems.dev<h264k::ShiftItem>(), nullptr, nullptr, sp.radius, sp.surface };
+    if (S > 1u && stats_scratch_locked(e, st, &sargs.tickets, &sargs.partials)) return -1;
+    if (kept_order_begin(e, st)) return -1;
+    if (pull_launch_locked(e, n, pics, st, fn, dim3(S, n_regs), &sargs, fence_ev)) return -1;
+    if (S > 1u) HIP_TRY(hipEventRecord(e->stats_ev, st));
+    return kept_order_end(e, st);
+}
+
 /* h264bsdmiOutputCellMaps: one CellItem per region — the frame, in CHANGE mode the kept frame, the slice, the box's origin (signed) and
  * box ∩ window in luma samples of the coded frame — and ONE k_cell_maps launch of (rectangles of the grid, regions) workgroups.  Every
  * cell is owned by one workgroup: no scratch.  CHANGE: the kept pictures' ordering, and a picture whose instance has no kept picture
@@ -1670,7 +1720,7 @@ static int remap_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, ui
     return pull_launch_locked(e, n, pics, st, fn, pull_grid(t.width, t.height, h264k::TRM_COLS, h264k::TRM_ROWS, n_maps), &rargs, fence_ev);
 }
 
-/* What JobSink.tensor_out, tensor_regions, motion_regions, tensor_remap, region_stats, keep_pictures, region_change, cell_maps and cell_boxes share: one engine (one device) per call, its mutex, the
+/* What JobSink.tensor_out, tensor_regions, motion_regions, tensor_remap, region_stats, keep_pictures, region_change, region_shift, cell_maps and cell_boxes share: one engine (one device) per call, its mutex, the
  * refusal of a capturing stream, and, when the caller gave no stream, the wait for the fence and the device's error words.
  * body(e, st, &fence_ev): the call's own *_out_locked. */
 template <typename Body> static int sink_tensor_call(uint32_t n, const SinkTensorPic *pics, void *stream, Body body)
@@ -1757,6 +1807,15 @@ int sink_region_change(uint32_t n, const SinkTensorPic *pics, uint32_t n_regions
         return change_out_locked(e, n, pics, n_regions, regions, *spec, st, fence_ev);
     });
 }
+int sink_region_shift(uint32_t n, const SinkTensorPic *pics, uint32_t n_regions, const SinkRegion *regions,
+                      const h264bsdmi_shift_spec *spec, void *stream)
+{
+    if (!n_regions) return 0;
+    if (!regions || !spec) return -1;
+    return sink_tensor_call(n, pics, stream, [&](Engine *e, hipStream_t st, hipEvent_t *fence_ev) {
+        return shift_out_locked(e, n, pics, n_regions, regions, *spec, st, fence_ev);
+    });
+}
 int sink_cell_maps(uint32_t n, const SinkTensorPic *pics, uint32_t n_regions, const SinkRegion *regions,
                    const h264bsdmi_cells_spec *spec, void *stream)
 {
@@ -1818,6 +1877,7 @@ int eng_attach(JobSink *sink)
     sink->set_motion = sink_set_motion;
     sink->keep_pictures = sink_keep_pictures;
     sink->region_change = sink_region_change;
+    sink->region_shift = sink_region_shift;
     sink->cell_maps = sink_cell_maps;
     sink->cell_boxes = sink_cell_boxes;
     return 0;

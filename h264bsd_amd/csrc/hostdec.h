@@ -222,6 +222,7 @@ struct h264bsdmi_motion_spec;
 struct h264bsdmi_remap_spec;
 struct h264bsdmi_stats_spec;
 struct h264bsdmi_change_spec;
+struct h264bsdmi_shift_spec;
 struct h264bsdmi_cells_spec;
 struct h264bsdmi_boxes_spec;
 struct JobSink;
@@ -309,6 +310,11 @@ typedef struct JobSink {
      * does not look at spec->keep_after (the caller follows up with keep_pictures).  0 = ok; <0 = error, nothing enqueued */
     int (*region_change)(uint32_t n, const SinkTensorPic *pics, uint32_t n_regions, const SinkRegion *regions,
                          const struct h264bsdmi_change_spec *spec, void *stream);
+    /* optional: where the boxes of the instances' kept pictures lie in the pictures (a SAD search within spec->radius), record `index` of
+     * spec->data each, with one launch — h264bsdmiOutputRegionShift.  Every picture's instance has a kept picture of its coded size; the
+     * sink does not look at spec->keep_after (the caller follows up with keep_pictures).  0 = ok; <0 = error, nothing enqueued */
+    int (*region_shift)(uint32_t n, const SinkTensorPic *pics, uint32_t n_regions, const SinkRegion *regions,
+                        const struct h264bsdmi_shift_spec *spec, void *stream);
     /* optional: dense per-cell maps over the same regions, slice `index` of spec->data each, with one launch — h264bsdmiOutputCellMaps.
      * In CHANGE mode every picture's instance has a kept picture of its coded size; the sink does not look at spec->keep_after (the
      * caller follows up with keep_pictures).  0 = ok; <0 = error, nothing enqueued */

@@ -1,0 +1,238 @@
+/* kernels/k_region_shift.hip.h — WHERE did a box go: block-matching SAD search of boxes of the KEPT picture (k_keep.hip.h) in the
+ * CURRENT picture of the same instance (h264bsdmiOutputRegionShift), luma only, both read from their macroblock tiles where they lie.
+ * Included by engine.hip after k_region_change.hip.h, whose band / ticket scheme (k_region_stats.hip.h) and wave reduction it uses;
+ * like them, not part of the kernel sources that key the committed counter tables (srchash.py).
+ *
+ * One record, R = radius (0 .. 16), D = 2 R + 1, little endian, 32 bytes, with the surface 32 + 4 (D D + 1):
+ *     u32 count; u32 D; i32 dx; i32 dy; u32 best; u32 still; u32 ties; u32 zero;   [ D x D x u32 sad[(dy + R) D + (dx + R)]; u32 zero ]
+ *     SAD(dx, dy) = sum over (u, v) of T = box ∩ window of | kept(u, v) - current(clamp(u + dx), clamp(v + dy)) |, clamped at the WINDOW
+ * grid (S row bands, regions) x 256.  A band is walked in tiles of at most SHIFT_ROWS x 4 SHIFT_COLS4 template samples, column chunk
+ * by column chunk, by the same workgroup.  Per tile both pictures are read from memory ONCE and staged in LDS as raster rows of dwords
+ * (shift_stage: two aligned tile dwords and v_alignbyte per staged dword; bytewise where the clamp at the window is active): the
+ * template with its first sample in byte 0 of dword 0, the current picture from R rows above and R columns left of it, th + 2 R rows of
+ * tw4 + Q dwords, Q = ceil(D / 4) rounded up to whole threads.  The halo is what is read more than once: R rows per tile above and
+ * below, R columns beside it.
+ * LDS (160 KiB per compute unit): 32 x 64 dwords of template (8 KiB), 64 rows at a pitch of 75 dwords of current picture (18.75 KiB;
+ * the odd pitch keeps rows that differ by dy on different banks) and 33 x 36 sums (4.6 KiB): 31.5 KiB per workgroup whatever the
+ * radius, five workgroups of 256 to a compute unit.  A taller band or a wider box does not grow it: they take more tiles.
+ * The sums: a QUAD is four displacements dx = 4 q - R .. + 3 of one row dy of the surface.  v_qsad_pk_u16_u8 takes the template
+ * dword u and the eight bytes of the current picture from dword u + q of row v + dy and adds the four SADs of the four byte offsets
+ * to four packed 16-bit sums: sixteen differences per instruction.  A thread takes QUADS adjacent quads of one row dy (a PAIR) and
+ * walks a segment of a template row: per template dword it reads that dword and ONE new dword of the current picture (the others are
+ * the step before's), so with QUADS = 3 two LDS reads feed three instructions.  QUADS is 3 from radius SHIFT_QUADS_FROM on and 1 below
+ * it, where whole threads of three quads would mostly compute displacements beyond 2 R: each measured faster on its side.  The pairs
+ * are dealt to the threads SHIFT_SPLIT / P ways (P pairs), each share a set of row segments of the tile, so that 256 threads are busy
+ * at every radius; a thread unpacks its packed sums after every segment (at most SHIFT_FOLD instructions), keeps 32-bit sums per tile
+ * and adds them to the workgroup's surface in LDS (ds_add_u32, integers: no order shows).  The last template dword of a row, when the
+ * width is no multiple of 4, goes through v_sad_u8 with a byte mask on both operands instead.  Displacements beyond 2 R in the last
+ * pair of a row are computed and dropped.
+ * Two other inner loops were measured and lost (docs/EXPERIMENTS.md, "Region shift"): v_sad_u8 per displacement, and
+ * v_mqsad_pk_u16_u8, which SKIPS bytes that are 0 in its reference operand and so needs a guard; tools/experiments/shift_inner_loops.patch
+ * puts them back behind -DSHIFT_INNER for whoever wants to measure again.
+ * S == 1: the workgroup closes the record.  S > 1: the bands' D D partial sums meet in the engine's scratch under k_region_stats'
+ * ticket hand-over; the band that draws the last ticket adds them up and closes the record: argmin with the tie rule (smallest SAD,
+ * then smallest dx^2 + dy^2, then smallest dy, then smallest dx) as ONE 64-bit key per displacement, the number of ties, the header and
+ * the surface with plain vector stores.  All integers: the result does not depend on which band arrives last. */
+#pragma once
+namespace h264k {
+
+constexpr uint32_t SHIFT_QUADS = 3, SHIFT_QUADS_FROM = 4;       /* quads of displacements a thread takes per template dword, from which radius on (below: 1) */
+constexpr uint32_t SHIFT_MAX_RADIUS = 16, SHIFT_MAX_D = 2 * SHIFT_MAX_RADIUS + 1;
+constexpr uint32_t SHIFT_MAX_Q = ((SHIFT_MAX_D + 3) / 4 + SHIFT_QUADS - 1) / SHIFT_QUADS * SHIFT_QUADS;      /* quads per row of the surface, in whole threads: 9 */
+constexpr uint32_t SHIFT_ROWS = 32, SHIFT_COLS4 = 64;                               /* a tile of template: rows, dwords per row */
+constexpr uint32_t SHIFT_CUR_ROWS = SHIFT_ROWS + 2 * SHIFT_MAX_RADIUS, SHIFT_PITCH = SHIFT_COLS4 + SHIFT_MAX_Q + 2;     /* 64, 75 */
+/* v_qsad_pk_u16_u8 instructions a packed 16-bit sum takes before it is unpacked: each adds at most 4 x 255 = 1020, and
+ * 64 x 1020 = 65280 <= 65535.  A segment is at most SHIFT_COLS4 = 64 dwords of one row.  The 32-bit sums behind it: a region has at most
+ * 4096 x 4096 samples (H264BSDMI_SHIFT_MAX_SIDE), 2^24 x 255 < 2^32 */
+constexpr uint32_t SHIFT_FOLD = 64;
+static_assert(SHIFT_COLS4 <= SHIFT_FOLD && SHIFT_FOLD * 4 * 255 <= 65535, "a segment's packed sums must fit 16 bits");
+constexpr uint32_t SHIFT_SPLIT = 1024;                                              /* (pair, share) work items a workgroup aims at */
+constexpr uint32_t SHIFT_MAX_PARTIAL = 4 * SHIFT_MAX_D * SHIFT_MAX_D;               /* a band's partial surface, bytes */
+
+__host__ __device__ constexpr uint32_t shift_record_bytes(uint32_t radius, uint32_t surface)
+{
+    return 32u + (surface ? 4u * ((2u * radius + 1u) * (2u * radius + 1u) + 1u) : 0u);
+}
+
+/* one region: the two frames, the record, box ∩ window [x0, x1) x [y0, y1) and the window [wx0, wx1) x [wy0, wy1) itself, all in luma
+ * samples of the coded frame (x1 <= x0: empty) */
+struct ShiftItem { const uint8_t *cur; const uint8_t *kept; uint8_t *dst; uint32_t wmb, x0, y0, x1, y1, wx0, wy0, wx1, wy1; };
+/* partials: region r's band b at ((r S + b) D D) words; tickets: as StatsArgs */
+struct ShiftArgs { const ShiftItem *items; uint8_t *partials; uint32_t *tickets; uint32_t radius, surface; };
+
+/* rows x cols4 dwords of a frame's luma into LDS as raster rows: byte k of dword j of row i is the sample at
+ * (clamp(X0 + 4 j + k, wx0, wx1 - 1), clamp(Y0 + i, wy0, wy1 - 1)).  Every SAMPLE taken is inside the window; the aligned dwords of the
+ * fast path may start up to 3 bytes left of wx0 or end up to 3 bytes right of wx1 - 1, but they lie in the 16-byte tile rows of samples of
+ * the window, so inside the frame */
+__device__ __forceinline__ void shift_stage(const uint8_t *frame, const ShiftItem &it, int X0, int Y0, uint32_t cols4, uint32_t rows,
+                                            uint32_t *lds, uint32_t pitch, uint32_t tid)
+{
+    for (uint32_t i = tid; i < rows * cols4; i += 256u) {
+        const uint32_t r = i / cols4, j = i - r * cols4;
+        const uint32_t Y = (uint32_t)min(max(Y0 + (int)r, (int)it.wy0), (int)it.wy1 - 1);
+        const int X = X0 + 4 * (int)j;
+        const uint8_t *row = frame + (size_t)(Y >> 4) * it.wmb * TILE + (Y & 15u) * 16u;
+        uint32_t v;
+        if (X >= (int)it.wx0 && X + 3 < (int)it.wx1) {
+            const uint32_t xa = (uint32_t)X & ~3u, sh = (uint32_t)X & 3u, xb = sh ? xa + 4u : xa;       /* xb <= X + 3: inside as well */
+            const uint32_t lo = *reinterpret_cast<const uint32_t *>(row + (size_t)(xa >> 4) * TILE + (xa & 15u));
+            const uint32_t hi = *reinterpret_cast<const uint32_t *>(row + (size_t)(xb >> 4) * TILE + (xb & 15u));
+            v = __builtin_amdgcn_alignbyte(hi, lo, sh);
+        } else {
+            v = 0u;
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const uint32_t x = (uint32_t)min(max(X + k, (int)it.wx0), (int)it.wx1 - 1);
+                v |= (uint32_t)row[(size_t)(x >> 4) * TILE + (x & 15u)] << (8 * k);
+            }
+        }
+        lds[r * pitch + j] = v;
+    }
+}
+
+/* the four SADs of template dword t against the bytes k .. k + 3 of c1:c0, k = 0 .. 3, bytes outside m left out, added to sum[] */
+__device__ __forceinline__ void shift_sad4(uint32_t c0, uint32_t c1, uint32_t t, uint32_t m, uint32_t *sum)
+{
+#pragma unroll
+    for (int k = 0; k < 4; k++) sum[k] = __builtin_amdgcn_sad_u8(__builtin_amdgcn_alignbyte(c1, c0, (uint32_t)k) & m, t & m, sum[k]);
+}
+
+template <uint32_t QUADS>
+__global__ __launch_bounds__(256) void k_region_shift(ShiftArgs a)
+{
+    __shared__ uint32_t s_t[SHIFT_ROWS * SHIFT_COLS4];
+    __shared__ uint32_t s_c[SHIFT_CUR_ROWS * SHIFT_PITCH];
+    __shared__ uint32_t s_sad[SHIFT_MAX_D * 4u * SHIFT_MAX_Q];              /* row dy + R at a pitch of SP */
+    __shared__ unsigned long long s_key[4];
+    __shared__ uint32_t s_ties[4];
+    __shared__ uint32_t s_last;
+    const ShiftItem it = a.items[blockIdx.y];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t R = a.radius, D = 2u * R + 1u, Q3 = ((D + 3u) / 4u + QUADS - 1u) / QUADS, P = D * Q3, G = (SHIFT_SPLIT + P - 1u) / P;
+    const uint32_t SP = 4u * QUADS * Q3;
+    const uint32_t S = gridDim.x, band = blockIdx.x, n = D * D;
+    for (uint32_t i = tid; i < D * SP; i += 256u) s_sad[i] = 0u;
+
+    const bool empty = it.x1 <= it.x0 || it.y1 <= it.y0;
+    const uint32_t mby0 = it.y0 >> 4, rows = empty ? 0u : ((it.y1 + 15u) >> 4) - mby0;
+    const uint32_t r0 = mby0 + rows * band / S, r1 = mby0 + rows * (band + 1u) / S;
+    const uint32_t ya = max(it.y0, r0 * 16u), yb = empty ? ya : min(it.y1, r1 * 16u);           /* this band's template rows */
+    for (uint32_t ys = ya; ys < yb; ys += SHIFT_ROWS) {
+        const uint32_t th = min(SHIFT_ROWS, yb - ys);
+        for (uint32_t xs = it.x0; xs < it.x1; xs += 4u * SHIFT_COLS4) {
+            const uint32_t tw = min(4u * SHIFT_COLS4, it.x1 - xs), tw4 = (tw + 3u) >> 2;
+            const uint32_t tail = (tw & 3u) ? (1u << (8u * (tw & 3u))) - 1u : 0xFFFFFFFFu;      /* the bytes of a row's last dword that count */
+            __syncthreads();                                                /* the sums are zero / the tile before has been read */
+            shift_stage(it.kept, it, (int)xs, (int)ys, tw4, th, s_t, SHIFT_COLS4, tid);
+            shift_stage(it.cur, it, (int)xs - (int)R, (int)ys - (int)R, tw4 + QUADS * Q3, th + 2u * R, s_c, SHIFT_PITCH, tid);
+            __syncthreads();
+            /* segments of L dwords of one row, about four per share */
+            uint32_t L = 1u;
+            while (L < SHIFT_COLS4 && 2u * L * 4u * G <= th * tw4) L *= 2u;
+            const uint32_t spr = (tw4 + L - 1u) / L, ns = th * spr;
+            for (uint32_t vp = tid; vp < P * G; vp += 256u) {
+                const uint32_t g = vp / P, p = vp - g * P, dyi = p / Q3, q = (p - dyi * Q3) * QUADS;
+                uint32_t sum[QUADS][4] = {};
+                for (uint32_t s = g; s < ns; s += G) {
+                    const uint32_t v = s / spr, u0 = (s - v * spr) * L, u1 = min(u0 + L, tw4);
+                    const uint32_t *tp = s_t + v * SHIFT_COLS4, *cp = s_c + (v + dyi) * SHIFT_PITCH + q;
+                    unsigned long long acc[QUADS] = {};
+                    uint32_t c[QUADS + 1];
+#pragma unroll
+                    for (uint32_t j = 0; j < QUADS; j++) c[j] = cp[u0 + j];
+                    for (uint32_t u = u0; u < u1; u++) {
+                        const uint32_t t = tp[u];
+                        c[QUADS] = cp[u + QUADS];
+                        if (u + 1u == tw4 && tail != 0xFFFFFFFFu) {
+#pragma unroll
+                            for (uint32_t j = 0; j < QUADS; j++) shift_sad4(c[j], c[j + 1u], t, tail, sum[j]);
+                        } else {
+#pragma unroll
+                            for (uint32_t j = 0; j < QUADS; j++) {
+                                const unsigned long long cc = (unsigned long long)c[j + 1u] << 32 | c[j];
+                                acc[j] = __builtin_amdgcn_qsad_pk_u16_u8(cc, t, acc[j]);
+                            }
+                        }
+#pragma unroll
+                        for (uint32_t j = 0; j < QUADS; j++) c[j] = c[j + 1u];
+                    }
+#pragma unroll
+                    for (uint32_t j = 0; j < QUADS; j++)
+#pragma unroll
+                        for (int k = 0; k < 4; k++) sum[j][k] += (uint32_t)(acc[j] >> (16 * k)) & 0xFFFFu;
+                }
+#pragma unroll
+                for (uint32_t j = 0; j < QUADS; j++)
+#pragma unroll
+                    for (uint32_t k = 0; k < 4u; k++) {
+                        const uint32_t dxi = 4u * (q + j) + k;
+                        if (dxi < D && sum[j][k]) stats_hist_add(&s_sad[dyi * SP + dxi], sum[j][k]);
+                    }
+            }
+        }
+    }
+    __syncthreads();
+
+    if (S > 1u) {
+        /* the hand-over of k_region_stats: every storing wavefront drains, one lane releases at device scope and takes the ticket */
+        uint32_t *part = reinterpret_cast<uint32_t *>(a.partials) + ((size_t)blockIdx.y * S + band) * n;
+        for (uint32_t i = tid; i < n; i += 256u) part[i] = s_sad[(i / D) * SP + i % D];
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        if (tid == 0u) {
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            const uint32_t t = __hip_atomic_fetch_add(&a.tickets[blockIdx.y], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            s_last = t == S - 1u ? 1u : 0u;
+            if (t == S - 1u) {
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            }
+        }
+        __syncthreads();
+        if (!s_last) return;
+        const uint32_t *pp = reinterpret_cast<const uint32_t *>(a.partials) + (size_t)blockIdx.y * S * n;
+        for (uint32_t i = tid; i < n; i += 256u) {
+            uint32_t t = 0u;
+            for (uint32_t b = 0; b < S; b++) t += pp[(size_t)b * n + i];
+            s_sad[(i / D) * SP + i % D] = t;
+        }
+        __syncthreads();
+    }
+
+    /* the smallest (SAD, dx^2 + dy^2, dy, dx) as one key; then how many displacements share its SAD */
+    unsigned long long key = ~0ull;
+    for (uint32_t i = tid; i < n; i += 256u) {
+        const uint32_t dyi = i / D, dxi = i - dyi * D;
+        const int dx = (int)dxi - (int)R, dy = (int)dyi - (int)R;
+        key = min(key, (unsigned long long)s_sad[dyi * SP + dxi] << 32 | (unsigned long long)(uint32_t)(dx * dx + dy * dy) << 12 | dyi << 6 | dxi);
+    }
+#pragma unroll
+    for (int d = 32; d; d >>= 1) key = min(key, (unsigned long long)__shfl_xor(key, d));
+    if (lane == 0u) s_key[wave] = key;
+    __syncthreads();
+    key = min(min(s_key[0], s_key[1]), min(s_key[2], s_key[3]));
+    const uint32_t best = (uint32_t)(key >> 32);
+    uint32_t ties = 0u;
+    for (uint32_t i = tid; i < n; i += 256u) ties += s_sad[(i / D) * SP + i % D] == best ? 1u : 0u;
+    ties = stats_wave_sum(ties);
+    if (lane == 0u) s_ties[wave] = ties;
+    __syncthreads();
+    uint32_t *dst32 = reinterpret_cast<uint32_t *>(it.dst);
+    if (tid == 0u) {
+        dst32[0] = empty ? 0u : (it.x1 - it.x0) * (it.y1 - it.y0);
+        dst32[1] = D;
+        dst32[2] = (uint32_t)((int)(key & 63u) - (int)R);
+        dst32[3] = (uint32_t)((int)((key >> 6) & 63u) - (int)R);
+        dst32[4] = best;
+        dst32[5] = s_sad[R * SP + R];
+        dst32[6] = s_ties[0] + s_ties[1] + s_ties[2] + s_ties[3];
+        dst32[7] = 0u;
+    }
+    if (a.surface) {
+        for (uint32_t i = tid; i <= n; i += 256u) dst32[8u + i] = i < n ? s_sad[(i / D) * SP + i % D] : 0u;
+    }
+    if (S > 1u && tid == 0u) __hip_atomic_store(&a.tickets[blockIdx.y], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+} // namespace h264k

@@ -461,6 +461,48 @@ int h264bsdmiOutputCellBoxes(u32 n, storage_t *const *pStorage, u32 nRegions, co
                              const h264bsdmi_cells_spec *cells, const h264bsdmi_boxes_spec *boxes, void *stream,
                              u32 *got, u32 *current, u32 *kept, u32 *picId, u32 *keptPicId);
 
+/* Region shift: WHERE did a box go — a block-matching search of boxes of the instances' KEPT pictures in their CURRENT pictures, luma
+ * only, computed where the two pictures lie, with one launch: boxes that follow the content between two runs of a detector, a camera that
+ * was knocked or shakes (the whole window moved by (dx, dy), which h264bsdmiOutputRegionChange cannot tell from a scene change), crops
+ * stabilised before h264bsdmiOutputTensorRegions — without pulling a pixel.  A sibling of h264bsdmiOutputRegionChange, and everything not
+ * said here is that call's, word for word: the region struct and its limits, negative origins, boxes that leave the source window or miss
+ * it, regions == NULL with nRegions == n meaning whole windows, the source window (spec->crop: W x H, coordinates relative to it), the
+ * current-picture and the kept-picture rule, got (per REGION), current, kept, picId, keptPicId (per instance, each may be NULL), the stream
+ * rule, the fence, the ordering of launches that touch kept pictures, keep_after, nRegions <= 65535.  It pops nothing and may be repeated.
+ * THE QUANTITY: the region's box lies in the KEPT picture and is the template, T = box ∩ window; it is searched in the CURRENT picture.
+ * For every displacement (dx, dy), |dx|, |dy| <= R = spec->radius, D = 2 R + 1:
+ *     SAD(dx, dy) = sum over (u, v) in T of | kept(u, v) - current(clamp(u + dx, 0, W - 1), clamp(v + dy, 0, H - 1)) |
+ * DIRECTION: (dx, dy) is where the content of the box lies in the current picture relative to where it lay in the kept one: content that
+ * moved 3 samples right and 2 up answers (3, -2), and the box to use from now on is (x + dx, y + dy, w, h).
+ * BORDER: the current picture is replicated at the border of the WINDOW, not of the coded frame, so every displacement sums over the same
+ * count = |T| samples and the SADs are comparable.
+ * TIES: the answer is the displacement of the smallest SAD; among equal SADs the smallest dx^2 + dy^2, then the smallest dy, then the
+ * smallest dx: a flat or unchanged box answers (0, 0).
+ * Record r is written at spec->data + r * stride, little endian; stride = 32 without the surface, 32 + 4 (D D + 1) with it (the last u32
+ * is a zero pad that keeps records 8-byte aligned):
+ *     u32 count; u32 D; i32 dx; i32 dy; u32 best; u32 still; u32 ties; u32 zero;
+ *     [ D x D x u32 sad;   sad[(dy + R) * D + (dx + R)];   u32 zero ]
+ * best = SAD(dx, dy); still = SAD(0, 0), which is h264bsdmiOutputRegionChange's luma sad of the same box; ties = the number of
+ * displacements whose SAD equals best (1: a unique minimum).  count == 0 (the box misses the window): dx = dy = best = still = 0, ties =
+ * D D, the surface all zero — the formula applied to nothing.  w, h <= H264BSDMI_SHIFT_MAX_SIDE keeps count <= 2^24, so every SAD fits 32
+ * bits (4096^2 * 255 < 2^32).  Everything is an integer and exact.  The call writes the WHOLE record with plain stores: the caller does
+ * not clear it.  got[r] = 0 (no current picture, or no kept one): record r is untouched.
+ * -1, before anything is enqueued, nothing written: everything h264bsdmiOutputRegionChange refuses in regions, instances, stream and data;
+ * radius > 16; surface > 1; crop > 1; keep_after > 1; a region with w or h above 4096.  -2: the engine failed: nothing is written by the
+ * host and nothing is marked kept.  nRegions == 0 returns 0 and launches nothing. */
+#define H264BSDMI_SHIFT_MAX_RADIUS 16
+#define H264BSDMI_SHIFT_MAX_SIDE   4096     /* w, h of a region: count <= 2^24, so every SAD fits 32 bits (4096^2 * 255 < 2^32) */
+typedef struct h264bsdmi_shift_spec {
+    void *data;        /* DEVICE pointer, caller-owned, 8-byte aligned: record r at data + r * stride */
+    u32   radius;      /* R, 0 .. 16; D = 2R + 1 */
+    u32   surface;     /* 0 / 1: the D x D SADs behind the header */
+    u32   crop;        /* as h264bsdmi_tensor_spec.crop */
+    u32   keep_after;  /* 0 / 1, as h264bsdmi_change_spec.keep_after */
+} h264bsdmi_shift_spec;
+int h264bsdmiOutputRegionShift(u32 n, storage_t *const *pStorage, u32 nRegions, const h264bsdmi_region *regions,
+                               const h264bsdmi_shift_spec *spec, void *stream,
+                               u32 *got, u32 *current, u32 *kept, u32 *picId, u32 *keptPicId);
+
 /* ---- host parse pipeline at scale ----
  * h264bsdDecode() consumes one NAL unit of one stream per call; a caller that feeds hundreds of streams needs the
  * loop of posix/test_h264bsd.c:146-177 for each of them and its own threading.  These entry points move both into
