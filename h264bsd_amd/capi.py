@@ -31,7 +31,7 @@ EXPORTED_SYMBOLS = [
     "h264bsdmiInitCapture", "h264bsdmiNextOutputInfo", "h264bsdmiNextOutputPictureDevice", "h264bsdmiNextOutputTensorBatch", "h264bsdmiNextOutputTensorBatchColour", "h264bsdmiNextOutputTensorBatchResize", "h264bsdmiOutputTensorRegions", "h264bsdmiOutputTensorRemap", "h264bsdmiSetMotionExport", "h264bsdmiOutputMotionRegions", "h264bsdmiOutputRegionStats", "h264bsdmiKeepCurrentPictures", "h264bsdmiOutputRegionChange", "h264bsdmiOutputRegionShift", "h264bsdmiOutputCellMaps", "h264bsdmiOutputCellBoxes", "h264bsdmiJobFinalize", "h264bsdmiDeviceCount", "h264bsdmiSetDevice", "h264bsdmiFlush", "h264bsdmiFlushAsync", "h264bsdmiDeviceErrors",
     "h264bsdmiDecodePicture", "h264bsdmiDecodePictureBatch", "h264bsdmiNextOutputPictureBatch", "h264bsdmiPullAndDecodePictureBatch", "h264bsdmiSetParserThreads", "h264bsdmiSetInputReadOnly", "h264bsdmiSetCopyElision",
     "h264bsdmiReplayCreate", "h264bsdmiReplayCreateStaggered", "h264bsdmiReplayCreateDesync", "h264bsdmiReplayCreateSched", "h264bsdmiReplayReschedule", "h264bsdmiReplayDestroy", "h264bsdmiReplayRun", "h264bsdmiReplaySync",
-    "h264bsdmiReplayFetch", "h264bsdmiReplayChecksums", "h264bsdmiReplayConvert", "h264bsdmiReplayFetchConverted",
+    "h264bsdmiReplayFetch", "h264bsdmiReplayDbkRecords", "h264bsdmiReplayChecksums", "h264bsdmiReplayConvert", "h264bsdmiReplayFetchConverted",
     "h264bsdmiReplayTimings", "h264bsdmiReplaySetConvert", "h264bsdmiReplayConvertTimings", "h264bsdmiReplaySetStages", "h264bsdmiReplaySetTimedKernels", "h264bsdmiReplaySetGroups", "h264bsdmiDebugTailProfile", "h264bsdmiDebugSetTail", "h264bsdmiDebugDeviceErrorEvents", "h264bsdmiReplayJobBytes", "h264bsdmiReplayFrameBytes",
 ]
 
@@ -295,6 +295,7 @@ def _declare(L, harness):
     L.h264bsdmiReplayRun.argtypes = [vp, u32, u32]
     L.h264bsdmiReplaySync.argtypes = [vp]
     L.h264bsdmiReplayFetch.argtypes = [vp, u32, u32, vp]
+    L.h264bsdmiReplayDbkRecords.argtypes = [vp, u32, u32, vp, u32]
     L.h264bsdmiReplayChecksums.argtypes = [vp, u32, vp]
     L.h264bsdmiReplayConvert.argtypes = [vp, u32, ctypes.c_int]
     L.h264bsdmiReplayFetchConverted.argtypes = [vp, u32, vp]
@@ -1332,6 +1333,14 @@ class Replay:
         if self._L.h264bsdmiReplayFetch(self._h, stream, slot, out.ctypes.data) != 0:
             raise RuntimeError("h264bsdmiReplayFetch failed")
         return out
+
+    def dbk_records(self, picture, stream):
+        """k_dbk alone for tick `picture`: (records [n_mbs, 48], flag bytes [n_mbs]) of `stream` (h264bsdmiReplayDbkRecords)"""
+        n = self.frame_bytes // 384
+        out = np.empty(n * 48 + ((n + 3) & ~3), dtype=np.uint8)
+        if self._L.h264bsdmiReplayDbkRecords(self._h, picture, stream, out.ctypes.data, out.size) != 0:
+            raise RuntimeError("h264bsdmiReplayDbkRecords failed")
+        return out[:n * 48].reshape(n, 48), out[n * 48:n * 48 + n]
 
     def checksums(self, slot):
         out = np.empty(self.n_streams, dtype=np.uint64)

@@ -10,7 +10,7 @@
  *     k_recon_inter<0>  grid (n_uni/4, N)     x 256  inter macroblocks with one motion vector, one wavefront each
  *     k_recon_inter<1>  grid (n_quad/4, N)    x 256  inter macroblocks with one motion vector per 8x8 quadrant
  *     k_recon_inter<2>  grid (n_rest/4, N)    x 256  finer partitions
- *     k_dbk             grid (32, N)          x 256  boundary strengths from metadata; on a third HIP stream, next to the four above, joined before k_frame_dbk
+ *     k_dbk             grid (n_dbk/512, N)   x 512  boundary strengths from metadata, one macroblock per lane; on a third HIP stream, next to the four above, joined before k_frame_dbk
  *     k_frame_intra     grid (N)              x 768  one workgroup per picture: intra macroblocks, dataflow-scheduled in LDS
  *     k_frame_dbk       grid (N)              x 768  one workgroup per picture: in-loop filter, dataflow-scheduled in LDS
  * Occupancy of the two per-picture kernels comes from batching streams: 256 pictures = one workgroup per CU.
@@ -458,7 +458,8 @@ struct TickTimers { Event ev[6]; Event sev[5]; bool on = false; bool copy_timed 
 /* k_dbk of one tick on st: the side stream beside the reconstruction kernels (SideLane), or the tick's own stream */
 static void launch_kdbk(hipStream_t st, const FrameDesc *d_desc, const TickShape &s, uint32_t launches[5])
 {
-    hipLaunchKernelGGL(h264k::k_dbk, dim3(std::min<uint32_t>((s.max_dbk + 4 * DBK_WG_WAVES - 1) / (4 * DBK_WG_WAVES), DBK_WGS * 4 / DBK_WG_WAVES), s.n_frames), dim3(64 * DBK_WG_WAVES), 0, st, d_desc);
+    /* one macroblock per lane, no stride loop: the grid is as long as the tick's longest list (a 1080p picture: at most 16 workgroups) */
+    hipLaunchKernelGGL(h264k::k_dbk, dim3((s.max_dbk + 64 * DBK_WG_WAVES - 1) / (64 * DBK_WG_WAVES), s.n_frames), dim3(64 * DBK_WG_WAVES), 0, st, d_desc);
     if (launches) launches[2]++;
 }
 /* k_recon_inter for one partition class (0: one motion vector, 1: one per 8x8 quadrant, 2: finer), n_max entries in the longest list of the tick */

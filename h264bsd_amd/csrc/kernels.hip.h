@@ -16,7 +16,7 @@
  *                       reference: src/h264bsd_reconstruct.c, src/h264bsd_inter_prediction.c:361-482,
  *                                  src/h264bsd_transform.c, src/h264bsd_image.c:172
  *   k_dbk         : boundary strengths + alpha / beta / tc0 VALUES of every macroblock the host could not prove strength-free
- *                   (metadata only, four MBs per wavefront) -> 48-byte deblocking records + one flag byte per MB
+ *                   (metadata only, one MB per lane, strengths as packed nibbles) -> 48-byte deblocking records + one flag byte per MB
  *                   (DBKF_*: filtered at all / touches the left / the upper neighbour / has an active inner edge).
  *                       reference: src/h264bsd_deblocking.c:1187-1541
  *   k_frame_intra : ONE workgroup per picture (a picture never leaves its CU): intra and concealed macroblocks,

@@ -529,6 +529,30 @@ int h264bsdmiReplayFetch(h264bsdmi_replay *r, u32 stream, u32 slot, u8 *dst)
     return 0;
 }
 
+/* k_dbk alone for the descriptors of tick `picture`, then what it left in the deblocking scratch of `stream`: the n_mbs 48-byte records
+ * and the n4 flag bytes behind them (DBK_SCRATCH_BYTES).  The flag bytes of every stream of the tick are zeroed again afterwards: "flags are
+ * zero between pictures" is what k_frame_dbk's last band normally restores.  Lock-step sets with one group only. */
+int h264bsdmiReplayDbkRecords(h264bsdmi_replay *r, u32 picture, u32 stream, u8 *dst, u32 bytes)
+{
+    if (!r || picture >= r->n_pics || stream >= r->n_streams || !r->sched.empty() || r->n_groups > 1) return -1;
+    const size_t n_mbs = (size_t)r->wmb * r->hmb, n4 = (n_mbs + 3u) & ~(size_t)3u;
+    if (!dst || bytes != n_mbs * DBK_REC_BYTES + n4) return -1;
+    Engine *e = r->e;
+    std::lock_guard<std::mutex> lk(e->mu);
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    const TickShape &s = r->shapes[picture];
+    if (s.any_deblock && s.max_dbk) {
+        launch_kdbk(e->stream, r->d_desc + (size_t)picture * r->n_streams, s, nullptr);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipMemcpyAsync(dst, r->d_dbk + (size_t)stream * r->dbk_stride, bytes, hipMemcpyDeviceToHost, e->stream));
+    for (u32 k = 0; k < r->n_streams; k++)
+        HIP_TRY(hipMemsetAsync(r->d_dbk + (size_t)k * r->dbk_stride + n_mbs * DBK_REC_BYTES, 0, n4, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return 0;
+}
+
 int h264bsdmiReplayChecksums(h264bsdmi_replay *r, u32 slot, unsigned long long *sums)
 {
     if (!r || slot >= r->n_slots) return -1;

@@ -58,6 +58,11 @@ int  h264bsdmiReplayRun(h264bsdmi_replay *r, u32 first, u32 count);
 int  h264bsdmiReplaySync(h264bsdmi_replay *r);
 /* Copy the current content of DPB slot `slot` of stream `stream` to host memory (frame_bytes). */
 int  h264bsdmiReplayFetch(h264bsdmi_replay *r, u32 stream, u32 slot, u8 *dst);
+/* Test hook: what k_dbk writes for tick `picture`.  Waits for the engine's stream, launches k_dbk alone for that tick's descriptors,
+ * waits, and copies the deblocking scratch of stream `stream` to dst: n_mbs 48-byte records, then n4 = n_mbs rounded up to a multiple
+ * of 4 flag bytes (bytes must be n_mbs * 48 + n4).  The flag bytes of all streams are then zeroed again, as k_frame_dbk leaves them
+ * between pictures.  Lock-step sets with one group only.  0 = ok. */
+int  h264bsdmiReplayDbkRecords(h264bsdmi_replay *r, u32 picture, u32 stream, u8 *dst, u32 bytes);
 /* 64-bit checksum (computed on the device) of slot `slot` of every stream into sums[n_streams]. */
 int  h264bsdmiReplayChecksums(h264bsdmi_replay *r, u32 slot, unsigned long long *sums);
 /* On-device colour conversion of slot `slot` of every stream (fmt 0 RGBA, 1 BGRA, 2 YCbCrA) into the
