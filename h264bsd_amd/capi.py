@@ -627,6 +627,28 @@ def _current_pull(name, decoders, K, items, specs, stream, boxes=False, call=Tru
     return res + [list(cur)[:n], list(ids)[:n]]
 
 
+def _kept_pull(name, decoders, K, regs, specs, stream, call):
+    """one pull that may compare against kept pictures, C entry `name`: K regions (a ctypes array, or None) of the decoders, the
+    entry's spec arguments, then the stream and the output arrays; call: whether the C call is made at all.  Returns (got[:K], current,
+    kept, pic_id, kept_pic_id), the last four per decoder"""
+    n = len(decoders)
+    got = (ctypes.c_uint32 * max(K, 1))()
+    per = [(ctypes.c_uint32 * max(n, 1))() for _ in range(4)]                # current, kept, picId, keptPicId
+    if call:
+        rc = getattr(api_lib(), name)(n, (ctypes.c_void_p * n)(*[d._st for d in decoders]), K, regs, *specs, stream.cuda_stream, got, *per)
+        if rc != 0:
+            raise RuntimeError(f"{name} failed ({rc})")
+    return (list(got)[:K], *[list(a)[:n] for a in per])
+
+
+def _thresholds(who, threshold, C):
+    """threshold (one int, or one per channel of C) as the three words of a spec"""
+    thr = [threshold] * 3 if isinstance(threshold, int) else list(threshold) + [0] * (3 - C) if isinstance(threshold, (tuple, list)) else []
+    if len(thr) != 3 or not all(isinstance(t, int) and 0 <= t <= 255 for t in thr):
+        raise ValueError(f"{who}: threshold is one int in 0..255, or one per channel, not {threshold}")
+    return thr
+
+
 def _tensor_call(who, n, decoders, size, layout, dtype, channels, mean, std, crop, out, stream, colour, colour_range, chroma, unspecified,
                  mode, antialias, fit, pad):
     """the argument checks, the output tensor of n slices, the stream handling and the three specs that pull_tensor and pull_regions
@@ -961,22 +983,12 @@ def pull_change(decoders, regions=None, source="y", bins=0, threshold=0, crop=Tr
     if source not in STATS_SOURCES or bins not in STATS_BINS:
         raise ValueError(f"pull_change: unsupported source / bins {source} {bins}")
     src, C = STATS_SOURCES[source]
-    thr = [threshold] * 3 if isinstance(threshold, int) else list(threshold) + [0] * (3 - C) if isinstance(threshold, (tuple, list)) else []
-    if len(thr) != 3 or not all(isinstance(t, int) and 0 <= t <= 255 for t in thr):
-        raise ValueError(f"pull_change: threshold is one int in 0..255, or one per channel, not {threshold}")
+    thr = _thresholds("pull_change", threshold, C)
     K, regs = _regions_arg("pull_change", n, regions)
     shape = (K, change_record_bytes(source, bins))
     out, stream = _out_and_stream("pull_change", out, shape, torch.uint8, stream, aligned=True)
     spec = ChangeSpec(out.data_ptr(), src, bins, 1 if crop else 0, (ctypes.c_uint32 * 3)(*thr), 1 if keep else 0)
-    got = (ctypes.c_uint32 * max(K, 1))()
-    per = [(ctypes.c_uint32 * max(n, 1))() for _ in range(4)]                # current, kept, picId, keptPicId
-    if n:
-        rc = api_lib().h264bsdmiOutputRegionChange(n, (ctypes.c_void_p * n)(*[d._st for d in decoders]), K, regs, ctypes.byref(spec),
-                                                   stream.cuda_stream, got, *per)
-        if rc != 0:
-            raise RuntimeError(f"h264bsdmiOutputRegionChange failed ({rc})")
-    cur, kept, ids, kept_ids = [list(a)[:n] for a in per]
-    return RegionChange(out, C, bins, list(got)[:K], cur, kept, ids, kept_ids)
+    return RegionChange(out, C, bins, *_kept_pull("h264bsdmiOutputRegionChange", decoders, K, regs, (ctypes.byref(spec),), stream, n > 0))
 
 
 def shift_record_bytes(radius, surface):
@@ -1032,15 +1044,8 @@ def pull_shift(decoders, regions=None, radius=4, crop=True, surface=False, keep=
     shape = (K, shift_record_bytes(radius, surface))
     out, stream = _out_and_stream("pull_shift", out, shape, torch.uint8, stream, aligned=True)
     spec = ShiftSpec(out.data_ptr(), radius, 1 if surface else 0, 1 if crop else 0, 1 if keep else 0)
-    got = (ctypes.c_uint32 * max(K, 1))()
-    per = [(ctypes.c_uint32 * max(n, 1))() for _ in range(4)]                # current, kept, picId, keptPicId
-    if n:
-        rc = api_lib().h264bsdmiOutputRegionShift(n, (ctypes.c_void_p * n)(*[d._st for d in decoders]), K, regs, ctypes.byref(spec),
-                                                  stream.cuda_stream, got, *per)
-        if rc != 0:
-            raise RuntimeError(f"h264bsdmiOutputRegionShift failed ({rc})")
-    cur, kept, ids, kept_ids = [list(a)[:n] for a in per]
-    return RegionShift(out, radius, bool(surface), list(got)[:K], cur, kept, ids, kept_ids)
+    return RegionShift(out, radius, bool(surface),
+                       *_kept_pull("h264bsdmiOutputRegionShift", decoders, K, regs, (ctypes.byref(spec),), stream, n > 0))
 
 
 class CellMaps:
@@ -1072,9 +1077,7 @@ def _cells_args(who, decoders, regions, cell, grid, source, planes, against, thr
     if not names or any(p not in CELL_PLANES[mode] for p in names):
         raise ValueError(f"{who}: planes is a non-empty choice of {tuple(CELL_PLANES[mode])}, not {planes}")
     bits = sum({CELL_PLANES[mode][p] for p in names})
-    thr = [threshold] * 3 if isinstance(threshold, int) else list(threshold) + [0] * (3 - C) if isinstance(threshold, (tuple, list)) else []
-    if len(thr) != 3 or not all(isinstance(t, int) and 0 <= t <= 255 for t in thr):
-        raise ValueError(f"{who}: threshold is one int in 0..255, or one per channel, not {threshold}")
+    thr = _thresholds(who, threshold, C)
     if not mode and (any(thr) or keep):
         raise ValueError(f"{who}: threshold and keep need against='kept'")
     K, regs = _regions_arg(who, n, regions)
@@ -1110,15 +1113,8 @@ def pull_cells(decoders, regions=None, cell=16, grid=None, source="y", planes=("
     shape = (K, P, grid[0], grid[1])
     out, stream = _out_and_stream("pull_cells", out, shape, torch.int32, stream)
     spec = CellsSpec(out.data_ptr(), grid[1], grid[0], cell, src, 1 if crop else 0, mode, bits, (ctypes.c_uint32 * 3)(*thr), 1 if keep else 0)
-    got = (ctypes.c_uint32 * max(K, 1))()
-    per = [(ctypes.c_uint32 * max(n, 1))() for _ in range(4)]                # current, kept, picId, keptPicId
-    if n and K:
-        rc = api_lib().h264bsdmiOutputCellMaps(n, (ctypes.c_void_p * n)(*[d._st for d in decoders]), K, regs, ctypes.byref(spec),
-                                               stream.cuda_stream, got, *per)
-        if rc != 0:
-            raise RuntimeError(f"h264bsdmiOutputCellMaps failed ({rc})")
-    cur, kept, ids, kept_ids = [list(a)[:n] for a in per]
-    return CellMaps(out, mode, C, bits, list(got)[:K], cur, kept, ids, kept_ids)
+    return CellMaps(out, mode, C, bits,
+                    *_kept_pull("h264bsdmiOutputCellMaps", decoders, K, regs, (ctypes.byref(spec),), stream, n > 0 and K > 0))
 
 
 class CellBoxes:
@@ -1200,16 +1196,9 @@ def pull_boxes(decoders, regions=None, cell=16, grid=None, source="y", planes=("
         raise ValueError("pull_boxes: out and boxes_out must be on the same device")
     spec = CellsSpec(out.data_ptr(), grid[1], grid[0], cell, src, 1 if crop else 0, mode, bits, (ctypes.c_uint32 * 3)(*thr), 1 if keep else 0)
     bspec = BoxesSpec(boxes_out.data_ptr(), max_boxes, CELL_PLANES[mode][plane], channel, BOXES_SENSES[sense], level, connectivity, min_cells)
-    got = (ctypes.c_uint32 * max(K, 1))()
-    per = [(ctypes.c_uint32 * max(n, 1))() for _ in range(4)]                # current, kept, picId, keptPicId
-    if n and K:
-        rc = api_lib().h264bsdmiOutputCellBoxes(n, (ctypes.c_void_p * n)(*[d._st for d in decoders]), K, regs, ctypes.byref(spec),
-                                                ctypes.byref(bspec), stream.cuda_stream, got, *per)
-        if rc != 0:
-            raise RuntimeError(f"h264bsdmiOutputCellBoxes failed ({rc})")
-    cur, kept, ids, kept_ids = [list(a)[:n] for a in per]
+    res = _kept_pull("h264bsdmiOutputCellBoxes", decoders, K, regs, (ctypes.byref(spec), ctypes.byref(bspec)), stream, n > 0 and K > 0)
     instances = [r.instance for r in regs[:K]] if regs is not None else list(range(K))
-    return CellBoxes(CellMaps(out, mode, C, bits, list(got)[:K], cur, kept, ids, kept_ids), boxes_out, instances, stream)
+    return CellBoxes(CellMaps(out, mode, C, bits, *res), boxes_out, instances, stream)
 
 
 def job_header(blob):

@@ -538,6 +538,9 @@ int h264bsdmiOutputMotionRegions(u32 n, storage_t *const *dec, u32 nRegions, con
     return pull_finish(&c, failed, nRegions, got, box, current, picId);
 }
 
+/* a histogram of `bins` bins: none, or a power of two from 16 to 256 */
+static int bins_refused(u32 bins) { return bins != 0 && bins != 16 && bins != 32 && bins != 64 && bins != 128 && bins != 256; }
+
 /* Integer statistics of h264bsdmiOutputTensorRegions' regions over the current pictures: the same windows, no rectangles */
 int h264bsdmiOutputRegionStats(u32 n, storage_t *const *dec, u32 nRegions, const h264bsdmi_region *regions,
                                const h264bsdmi_stats_spec *spec, void *stream,
@@ -545,7 +548,7 @@ int h264bsdmiOutputRegionStats(u32 n, storage_t *const *dec, u32 nRegions, const
 {
     CurrentPull c;
     if (!spec || !spec->data || ((uintptr_t)spec->data & 7u) || spec->source > H264BSDMI_STATS_RGB || spec->crop > 1) return -1;
-    if (spec->bins != 0 && spec->bins != 16 && spec->bins != 32 && spec->bins != 64 && spec->bins != 128 && spec->bins != 256) return -1;
+    if (bins_refused(spec->bins)) return -1;
     if (regions_refused(n, nRegions, regions, got, 1) || pull_begin(&c, n, dec, nRegions, PULL_STATS)) return -1;
     const h264bsdmi_tensor_spec window = { spec->data, 1, 1, 0, 0, 0, spec->crop, 1, { 0, 0, 0 }, { 1, 1, 1 } };
     pull_regions(&c, nRegions, regions, &window, &REFERENCE_COLOUR, 1, 1, 0);
@@ -593,61 +596,69 @@ int h264bsdmiKeepCurrentPictures(u32 n, storage_t *const *dec, void *stream, u32
     return failed ? -2 : 0;
 }
 
-/* Integer statistics of (current picture - kept picture) over h264bsdmiOutputRegionStats' regions; keep_after: then the keep call's
- * launch for every instance with a current picture.  kept / keptPicId are what the comparison saw; -2 writes nothing, marks nothing */
+/* The host path of the pulls that may compare against kept pictures and may keep afterwards, behind their own spec checks:
+ * h264bsdmiOutputRegionChange (PULL_CHANGE), h264bsdmiOutputRegionShift (PULL_SHIFT), h264bsdmiOutputCellMaps (PULL_CELLS) and
+ * h264bsdmiOutputCellBoxes (PULL_BOXES, spec2 its boxes spec).  vs_kept: only instances that have a kept picture too; max_side: the
+ * longest side a region may have (0: whatever regions_refused allows); keep_after: behind the sink's entry the keep call's launch for
+ * every instance with a current picture.  kept / keptPicId are what the comparison saw; -2 writes nothing, marks nothing */
+static int kept_pull(int kind, int vs_kept, u32 n, storage_t *const *dec, u32 nRegions, const h264bsdmi_region *regions, u32 max_side,
+                     const void *spec, const void *spec2, u32 crop, u32 keep_after, void *stream,
+                     u32 *got, u32 *current, u32 *kept, u32 *picId, u32 *keptPicId)
+{
+    CurrentPull c, k;
+    if (regions_refused(n, nRegions, regions, got, 1)) return -1;
+    for (u32 r = 0; max_side && regions && r < nRegions; r++)
+        if (regions[r].w > max_side || regions[r].h > max_side) return -1;
+    if (pull_begin(&c, n, dec, nRegions, kind)) return -1;
+    c.vs_kept = vs_kept;            /* (pull_begin knows it of PULL_CHANGE and PULL_SHIFT; the cells have it from their mode) */
+    for (u32 i = 0; vs_kept && i < n; i++)
+        if (!dec_of(dec[i])->hd->sink.keep_pictures) { pull_free(&c); return -1; }
+    if (keep_after && keep_begin(&k, n, dec)) { pull_free(&c); return -1; }
+    const h264bsdmi_tensor_spec window = { NULL, 1, 1, 0, 0, 0, crop, 1, { 0, 0, 0 }, { 1, 1, 1 } };
+    pull_regions(&c, nRegions, regions, &window, &REFERENCE_COLOUR, 1, 1, 0);
+    int failed = 0;
+    if (c.k) {
+        const JobSink *sink = c.pics[0].sink;
+        switch (kind) {
+        case PULL_CHANGE: failed = sink->region_change(c.m, c.pics, c.k, c.regs, (const h264bsdmi_change_spec *)spec, stream); break;
+        case PULL_SHIFT:  failed = sink->region_shift(c.m, c.pics, c.k, c.regs, (const h264bsdmi_shift_spec *)spec, stream); break;
+        case PULL_CELLS:  failed = sink->cell_maps(c.m, c.pics, c.k, c.regs, (const h264bsdmi_cells_spec *)spec, stream); break;
+        default:          failed = sink->cell_boxes(c.m, c.pics, c.k, c.regs, (const h264bsdmi_cells_spec *)spec, (const h264bsdmi_boxes_spec *)spec2, stream);
+        }
+    }
+    if (keep_after && !failed) failed = k.m && k.pics[0].sink->keep_pictures(k.m, k.pics, stream);
+    if (!failed) {
+        for (u32 i = 0; i < n; i++) {
+            const ApiDec *a = dec_of(dec[i]);
+            if (kept) kept[i] = has_kept_picture(a) ? 1 : 0;
+            if (keptPicId) keptPicId[i] = has_kept_picture(a) ? a->kept_id : 0;
+        }
+        if (keep_after) mark_kept(&k);
+    }
+    if (keep_after) pull_free(&k);
+    return pull_finish(&c, failed, nRegions, got, NULL, current, picId);
+}
+
+/* Integer statistics of (current picture - kept picture) over h264bsdmiOutputRegionStats' regions */
 int h264bsdmiOutputRegionChange(u32 n, storage_t *const *dec, u32 nRegions, const h264bsdmi_region *regions,
                                 const h264bsdmi_change_spec *spec, void *stream,
                                 u32 *got, u32 *current, u32 *kept, u32 *picId, u32 *keptPicId)
 {
-    CurrentPull c, k;
     if (!spec || !spec->data || ((uintptr_t)spec->data & 7u) || spec->source > H264BSDMI_STATS_RGB || spec->crop > 1 || spec->keep_after > 1) return -1;
-    if (spec->bins != 0 && spec->bins != 16 && spec->bins != 32 && spec->bins != 64 && spec->bins != 128 && spec->bins != 256) return -1;
+    if (bins_refused(spec->bins)) return -1;
     if (spec->threshold[0] > 255 || spec->threshold[1] > 255 || spec->threshold[2] > 255) return -1;
-    if (regions_refused(n, nRegions, regions, got, 1) || pull_begin(&c, n, dec, nRegions, PULL_CHANGE)) return -1;
-    if (spec->keep_after && keep_begin(&k, n, dec)) { pull_free(&c); return -1; }
-    const h264bsdmi_tensor_spec window = { spec->data, 1, 1, 0, 0, 0, spec->crop, 1, { 0, 0, 0 }, { 1, 1, 1 } };
-    pull_regions(&c, nRegions, regions, &window, &REFERENCE_COLOUR, 1, 1, 0);
-    int failed = c.k && c.pics[0].sink->region_change(c.m, c.pics, c.k, c.regs, spec, stream);
-    if (spec->keep_after && !failed) failed = k.m && k.pics[0].sink->keep_pictures(k.m, k.pics, stream);
-    if (!failed) {
-        for (u32 i = 0; i < n; i++) {
-            const ApiDec *a = dec_of(dec[i]);
-            if (kept) kept[i] = has_kept_picture(a) ? 1 : 0;
-            if (keptPicId) keptPicId[i] = has_kept_picture(a) ? a->kept_id : 0;
-        }
-        if (spec->keep_after) mark_kept(&k);
-    }
-    if (spec->keep_after) pull_free(&k);
-    return pull_finish(&c, failed, nRegions, got, NULL, current, picId);
+    return kept_pull(PULL_CHANGE, 1, n, dec, nRegions, regions, 0, spec, NULL, spec->crop, spec->keep_after, stream, got, current, kept, picId, keptPicId);
 }
 
-/* Where the boxes of the kept pictures lie in the current ones: h264bsdmiOutputRegionChange's host path with the sink's region_shift */
+/* Where the boxes of the kept pictures lie in the current ones */
 int h264bsdmiOutputRegionShift(u32 n, storage_t *const *dec, u32 nRegions, const h264bsdmi_region *regions,
                                const h264bsdmi_shift_spec *spec, void *stream,
                                u32 *got, u32 *current, u32 *kept, u32 *picId, u32 *keptPicId)
 {
-    CurrentPull c, k;
     if (!spec || !spec->data || ((uintptr_t)spec->data & 7u) || spec->radius > H264BSDMI_SHIFT_MAX_RADIUS || spec->surface > 1 || spec->crop > 1 ||
         spec->keep_after > 1) return -1;
-    if (regions_refused(n, nRegions, regions, got, 1)) return -1;
-    for (u32 r = 0; regions && r < nRegions; r++)
-        if (regions[r].w > H264BSDMI_SHIFT_MAX_SIDE || regions[r].h > H264BSDMI_SHIFT_MAX_SIDE) return -1;
-    if (pull_begin(&c, n, dec, nRegions, PULL_SHIFT)) return -1;
-    if (spec->keep_after && keep_begin(&k, n, dec)) { pull_free(&c); return -1; }
-    const h264bsdmi_tensor_spec window = { spec->data, 1, 1, 0, 0, 0, spec->crop, 1, { 0, 0, 0 }, { 1, 1, 1 } };
-    pull_regions(&c, nRegions, regions, &window, &REFERENCE_COLOUR, 1, 1, 0);
-    int failed = c.k && c.pics[0].sink->region_shift(c.m, c.pics, c.k, c.regs, spec, stream);
-    if (spec->keep_after && !failed) failed = k.m && k.pics[0].sink->keep_pictures(k.m, k.pics, stream);
-    if (!failed) {
-        for (u32 i = 0; i < n; i++) {
-            const ApiDec *a = dec_of(dec[i]);
-            if (kept) kept[i] = has_kept_picture(a) ? 1 : 0;
-            if (keptPicId) keptPicId[i] = has_kept_picture(a) ? a->kept_id : 0;
-        }
-        if (spec->keep_after) mark_kept(&k);
-    }
-    if (spec->keep_after) pull_free(&k);
-    return pull_finish(&c, failed, nRegions, got, NULL, current, picId);
+    return kept_pull(PULL_SHIFT, 1, n, dec, nRegions, regions, H264BSDMI_SHIFT_MAX_SIDE, spec, NULL, spec->crop, spec->keep_after, stream,
+                     got, current, kept, picId, keptPicId);
 }
 
 /* Dense per-cell maps of h264bsdmiOutputRegionStats' (PICTURE) or h264bsdmiOutputRegionChange's (CHANGE) quantities over the same
@@ -677,35 +688,14 @@ static int boxes_spec_refused(const h264bsdmi_cells_spec *c, const h264bsdmi_box
     if (b->sense > H264BSDMI_BOXES_BELOW || (b->connectivity != 4 && b->connectivity != 8) || !b->min_cells) return 1;
     return c->rows * c->cols > H264BSDMI_BOXES_MAX_CELLS;                   /* (4096 each at the most: no overflow) */
 }
-/* The host path of both: kind PULL_CELLS calls the sink's cell_maps, PULL_BOXES its cell_boxes with the boxes spec */
+/* The host path of both is kept_pull's: kind PULL_CELLS calls the sink's cell_maps, PULL_BOXES its cell_boxes with the boxes spec */
 static int cells_pull(int kind, u32 n, storage_t *const *dec, u32 nRegions, const h264bsdmi_region *regions,
                       const h264bsdmi_cells_spec *spec, const h264bsdmi_boxes_spec *boxes, void *stream,
                       u32 *got, u32 *current, u32 *kept, u32 *picId, u32 *keptPicId)
 {
-    CurrentPull c, k;
     if (cells_spec_refused(spec) || (kind == PULL_BOXES && boxes_spec_refused(spec, boxes))) return -1;
-    const int change = spec->mode == H264BSDMI_CELLS_CHANGE;
-    if (regions_refused(n, nRegions, regions, got, 1) || pull_begin(&c, n, dec, nRegions, kind)) return -1;
-    c.vs_kept = change;
-    for (u32 i = 0; change && i < n; i++)
-        if (!dec_of(dec[i])->hd->sink.keep_pictures) { pull_free(&c); return -1; }
-    if (spec->keep_after && keep_begin(&k, n, dec)) { pull_free(&c); return -1; }
-    const h264bsdmi_tensor_spec window = { spec->data, 1, 1, 0, 0, 0, spec->crop, 1, { 0, 0, 0 }, { 1, 1, 1 } };
-    pull_regions(&c, nRegions, regions, &window, &REFERENCE_COLOUR, 1, 1, 0);
-    int failed = 0;
-    if (c.k) failed = kind == PULL_BOXES ? c.pics[0].sink->cell_boxes(c.m, c.pics, c.k, c.regs, spec, boxes, stream)
-                                         : c.pics[0].sink->cell_maps(c.m, c.pics, c.k, c.regs, spec, stream);
-    if (spec->keep_after && !failed) failed = k.m && k.pics[0].sink->keep_pictures(k.m, k.pics, stream);
-    if (!failed) {
-        for (u32 i = 0; i < n; i++) {
-            const ApiDec *a = dec_of(dec[i]);
-            if (kept) kept[i] = has_kept_picture(a) ? 1 : 0;
-            if (keptPicId) keptPicId[i] = has_kept_picture(a) ? a->kept_id : 0;
-        }
-        if (spec->keep_after) mark_kept(&k);
-    }
-    if (spec->keep_after) pull_free(&k);
-    return pull_finish(&c, failed, nRegions, got, NULL, current, picId);
+    return kept_pull(kind, spec->mode == H264BSDMI_CELLS_CHANGE, n, dec, nRegions, regions, 0, spec, boxes, spec->crop, spec->keep_after, stream,
+                     got, current, kept, picId, keptPicId);
 }
 int h264bsdmiOutputCellMaps(u32 n, storage_t *const *dec, u32 nRegions, const h264bsdmi_region *regions,
                             const h264bsdmi_cells_spec *spec, void *stream,

@@ -36,6 +36,7 @@
 #include "kernels/k_tensor_roi.hip.h"
 #include "kernels/k_tensor_remap.hip.h"
 #include "kernels/k_motion.hip.h"
+#include "kernels/region_common.hip.h"
 #include "kernels/k_region_stats.hip.h"
 #include "kernels/k_keep.hip.h"
 #include "kernels/k_region_change.hip.h"
@@ -1384,8 +1385,8 @@ static int motion_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, u
 }
 
 /* The scratch in which the row bands of k_region_stats, k_region_change and k_region_shift meet (Engine.d_stats), allocated at its first
- * use for the largest of the three (two records and a partial SAD surface); two launches must not use it at once: st waits for the event behind the previous one (the caller records
- * stats_ev behind its launch). */
+ * use for the largest of the three (two records and a partial SAD surface); two launches must not use it at once: st waits for the event behind the previous one
+ * (banded_launch_locked, the one caller, records stats_ev behind its launch). */
 static int stats_scratch_locked(Engine *e, hipStream_t st, uint32_t **tickets, uint8_t **partials)
 {
     const size_t ticket_bytes = h264k::STATS_MAX_PARTIALS * sizeof(uint32_t);
@@ -1401,47 +1402,56 @@ static int stats_scratch_locked(Engine *e, hipStream_t st, uint32_t **tickets, u
     return 0;
 }
 
-/* h264bsdmiOutputRegionStats: one StatsItem per region, box ∩ window in luma samples of the coded frame, ONE k_region_stats launch
- * of S row bands per region: S is one value for the launch, about 1024 workgroups in all, at most the macroblock rows of the tallest
- * box ∩ window, 1 from 1024 regions on.  With S > 1 the bands meet in the engine's scratch (Engine.d_stats), which two launches
- * must not use at once: st waits for the event behind the previous such launch.  The same ordering and fence as the other pulls. */
-static int stats_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, uint32_t n_regs, const SinkRegion *regs,
-                            const h264bsdmi_stats_spec &sp, hipStream_t st, hipEvent_t *fence_ev)
+/* What the picture-analysis pulls below share (region statistics, change statistics, region shift, cell maps and cell boxes).
+ * region_clip: box ∩ window of region g of picture p in luma samples of the coded frame, all zero when empty, and its height in
+ * macroblock rows (0 when empty). */
+struct RegionClip { uint32_t x0, y0, x1, y1, mb_rows; };
+static RegionClip region_clip(const SinkTensorPic &p, const SinkRegion &g)
 {
-    static const void *const fns[3][2] = {
-        { reinterpret_cast<const void *>(&h264k::k_region_stats<h264k::ST_Y, false>), reinterpret_cast<const void *>(&h264k::k_region_stats<h264k::ST_Y, true>) },
-        { reinterpret_cast<const void *>(&h264k::k_region_stats<h264k::ST_YCBCR, false>), reinterpret_cast<const void *>(&h264k::k_region_stats<h264k::ST_YCBCR, true>) },
-        { reinterpret_cast<const void *>(&h264k::k_region_stats<h264k::ST_RGB, false>), reinterpret_cast<const void *>(&h264k::k_region_stats<h264k::ST_RGB, true>) } };
-    uint32_t shift = 8u;
-    while (shift > 0u && (256u >> shift) != sp.bins) shift--;               /* bins == 256 >> shift; shift == 0 also stands for "no such shift" */
-    if (!sp.data || (reinterpret_cast<uintptr_t>(sp.data) & 7u) || sp.source > H264BSDMI_STATS_RGB || sp.crop > 1u) return -1;
-    if (sp.bins && (sp.bins < 16u || (256u >> shift) != sp.bins)) return -1;
-    if (n_regs > 65535u) return -1;                                     /* grid.y */
-    if (!pull_pictures_ok(n, pics, true, false) || !pull_regions_ok(n, n_regs, regs, 1u, 1u)) return -1;
-    if (pull_begin_locked(e, n, pics, n_regs)) return -1;
-    h264k::StatsItem *items = e->titems.host<h264k::StatsItem>();
-    const uint32_t stride = h264k::stats_record_bytes(sp.source == H264BSDMI_STATS_Y ? 1u : 3u, sp.bins);
-    uint32_t tallest = 1u;
-    for (uint32_t r = 0; r < n_regs; r++) {
-        const SinkRegion &g = regs[r];
-        const SinkTensorPic &p = pics[g.pic];
-        const StreamCtx *s = pic_stream(p);
-        const int64_t bx0 = std::max<int64_t>(g.x, 0), bx1 = std::min<int64_t>((int64_t)g.x + g.w, p.w);
-        const int64_t by0 = std::max<int64_t>(g.y, 0), by1 = std::min<int64_t>((int64_t)g.y + g.h, p.h);
-        h264k::StatsItem it{ s->d_frames + (size_t)p.slot * s->frame_bytes, static_cast<uint8_t *>(sp.data) + (size_t)g.index * stride, s->wmb, 0u, 0u, 0u, 0u };
-        if (bx1 > bx0 && by1 > by0) {
-            it.x0 = p.x0 + (uint32_t)bx0; it.x1 = p.x0 + (uint32_t)bx1;
-            it.y0 = p.y0 + (uint32_t)by0; it.y1 = p.y0 + (uint32_t)by1;
-            tallest = std::max(tallest, ((it.y1 + 15u) >> 4) - (it.y0 >> 4));
-        }
-        items[r] = it;
+    const int64_t bx0 = std::max<int64_t>(g.x, 0), bx1 = std::min<int64_t>((int64_t)g.x + g.w, p.w);
+    const int64_t by0 = std::max<int64_t>(g.y, 0), by1 = std::min<int64_t>((int64_t)g.y + g.h, p.h);
+    RegionClip c{ 0u, 0u, 0u, 0u, 0u };
+    if (bx1 > bx0 && by1 > by0) {
+        c.x0 = p.x0 + (uint32_t)bx0; c.x1 = p.x0 + (uint32_t)bx1;
+        c.y0 = p.y0 + (uint32_t)by0; c.y1 = p.y0 + (uint32_t)by1;
+        c.mb_rows = ((c.y1 + 15u) >> 4) - (c.y0 >> 4);
     }
-    const uint32_t S = n_regs >= h264k::STATS_MAX_PARTIALS ? 1u : std::min(h264k::STATS_MAX_PARTIALS / n_regs, tallest);
-    h264k::StatsArgs sargs{ e->titems.dev<h264k::StatsItem>(), nullptr, nullptr, sp.bins, sp.bins ? shift : 0u };
-    if (S > 1u && stats_scratch_locked(e, st, &sargs.tickets, &sargs.partials)) return -1;
-    if (pull_launch_locked(e, n, pics, st, fns[sp.source][sp.bins != 0u], dim3(S, n_regs), &sargs, fence_ev)) return -1;
-    if (S > 1u) HIP_TRY(hipEventRecord(e->stats_ev, st));
-    return 0;
+    return c;
+}
+/* the row bands per region of a banded launch: one value for the launch, about 1024 workgroups in all, at most the macroblock rows of
+ * the tallest box ∩ window, 1 from 1024 regions on */
+static uint32_t band_count(uint32_t n_regs, uint32_t tallest)
+{
+    return n_regs >= h264k::STATS_MAX_PARTIALS ? 1u : std::min(h264k::STATS_MAX_PARTIALS / n_regs, std::max(tallest, 1u));
+}
+/* every picture's instance has a kept picture of its coded size (api.c names only instances that have one) */
+static bool kept_pictures_ok(uint32_t n, const SinkTensorPic *pics)
+{
+    for (uint32_t i = 0; i < n; i++) {
+        const StreamCtx *s = pic_stream(pics[i]);
+        if (!s->d_kept || s->kept_wmb != s->wmb || s->kept_hmb != s->hmb) return false;
+    }
+    return true;
+}
+/* the refusals of `source` and `bins` (0, or a power of two 16 .. 256); *shift = 8 - log2 bins, 0 without a histogram */
+static bool source_bins_ok(uint32_t source, uint32_t bins, uint32_t *shift)
+{
+    uint32_t sh = 8u;
+    while (sh > 0u && (256u >> sh) != bins) sh--;                           /* bins == 256 >> sh; sh == 0 also stands for "no such shift" */
+    *shift = bins ? sh : 0u;
+    return source <= H264BSDMI_STATS_RGB && (!bins || (bins >= 16u && (256u >> sh) == bins));
+}
+/* k_region_stats or k_region_change of a source, with or without the histogram */
+template <int SRC> static const void *banded_kernel_of(bool change, bool hist)
+{
+    if (change) return hist ? reinterpret_cast<const void *>(&h264k::k_region_change<SRC, true>) : reinterpret_cast<const void *>(&h264k::k_region_change<SRC, false>);
+    return hist ? reinterpret_cast<const void *>(&h264k::k_region_stats<SRC, true>) : reinterpret_cast<const void *>(&h264k::k_region_stats<SRC, false>);
+}
+static const void *banded_kernel(bool change, uint32_t source, bool hist)
+{
+    const void *const fns[3] = { banded_kernel_of<h264k::ST_Y>(change, hist), banded_kernel_of<h264k::ST_YCBCR>(change, hist),
+                                 banded_kernel_of<h264k::ST_RGB>(change, hist) };
+    return fns[source];
 }
 
 /* launches that touch kept pictures run one behind the other, whatever streams they are on (Engine.kept_ev) */
@@ -1456,6 +1466,48 @@ static int kept_order_end(Engine *e, hipStream_t st)
     HIP_TRY(hipEventRecord(e->kept_ev, st));
     e->kept_recorded = true;
     return 0;
+}
+
+/* Behind the filled items of k_region_stats, k_region_change and k_region_shift: ONE launch of S = band_count row bands per region.
+ * With S > 1 the bands meet in the engine's scratch (Engine.d_stats), which two launches must not use at once: st waits for the event
+ * behind the previous such launch, and stats_ev is recorded behind this one.  kept: the launch reads kept pictures, whose ordering
+ * encloses it.  The same ordering and fence as the other pulls. */
+template <typename Args>
+static int banded_launch_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, hipStream_t st, const void *fn, uint32_t n_regs,
+                                uint32_t tallest, Args *kargs, bool kept, hipEvent_t *fence_ev)
+{
+    const uint32_t S = band_count(n_regs, tallest);
+    if (S > 1u && stats_scratch_locked(e, st, &kargs->tickets, &kargs->partials)) return -1;
+    if (kept && kept_order_begin(e, st)) return -1;
+    if (pull_launch_locked(e, n, pics, st, fn, dim3(S, n_regs), kargs, fence_ev)) return -1;
+    if (S > 1u) HIP_TRY(hipEventRecord(e->stats_ev, st));
+    return kept ? kept_order_end(e, st) : 0;
+}
+
+/* h264bsdmiOutputRegionStats: one StatsItem per region, box ∩ window in luma samples of the coded frame, ONE banded k_region_stats
+ * launch */
+static int stats_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, uint32_t n_regs, const SinkRegion *regs,
+                            const h264bsdmi_stats_spec &sp, hipStream_t st, hipEvent_t *fence_ev)
+{
+    uint32_t shift;
+    if (!sp.data || (reinterpret_cast<uintptr_t>(sp.data) & 7u) || sp.crop > 1u || !source_bins_ok(sp.source, sp.bins, &shift)) return -1;
+    if (n_regs > 65535u) return -1;                                     /* grid.y */
+    if (!pull_pictures_ok(n, pics, true, false) || !pull_regions_ok(n, n_regs, regs, 1u, 1u)) return -1;
+    if (pull_begin_locked(e, n, pics, n_regs)) return -1;
+    h264k::StatsItem *items = e->titems.host<h264k::StatsItem>();
+    const uint32_t stride = h264k::stats_record_bytes(sp.source == H264BSDMI_STATS_Y ? 1u : 3u, sp.bins);
+    uint32_t tallest = 0u;
+    for (uint32_t r = 0; r < n_regs; r++) {
+        const SinkRegion &g = regs[r];
+        const SinkTensorPic &p = pics[g.pic];
+        const StreamCtx *s = pic_stream(p);
+        const RegionClip c = region_clip(p, g);
+        items[r] = h264k::StatsItem{ s->d_frames + (size_t)p.slot * s->frame_bytes, static_cast<uint8_t *>(sp.data) + (size_t)g.index * stride,
+                                     s->wmb, c.x0, c.y0, c.x1, c.y1 };
+        tallest = std::max(tallest, c.mb_rows);
+    }
+    h264k::StatsArgs sargs{ e->titems.dev<h264k::StatsItem>(), nullptr, nullptr, sp.bins, shift };
+    return banded_launch_locked(e, n, pics, st, banded_kernel(false, sp.source, sp.bins != 0u), n_regs, tallest, &sargs, false, fence_ev);
 }
 
 /* h264bsdmiKeepCurrentPictures: the frame buffer of every picture into its instance's kept-picture buffer (allocated here at the first
@@ -1490,58 +1542,36 @@ static int keep_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, hip
 }
 
 /* h264bsdmiOutputRegionChange: one ChangeItem per region, the current picture and the kept picture of its instance at box ∩ window,
- * ONE k_region_change launch of S row bands per region, S chosen as in stats_out_locked; with S > 1 the bands meet in the same
- * scratch.  A picture whose instance has no kept picture of its coded size is refused (api.c names only instances that have one). */
+ * ONE banded k_region_change launch.  A picture whose instance has no kept picture of its coded size is refused. */
 static int change_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, uint32_t n_regs, const SinkRegion *regs,
                              const h264bsdmi_change_spec &sp, hipStream_t st, hipEvent_t *fence_ev)
 {
-    static const void *const fns[3][2] = {
-        { reinterpret_cast<const void *>(&h264k::k_region_change<h264k::ST_Y, false>), reinterpret_cast<const void *>(&h264k::k_region_change<h264k::ST_Y, true>) },
-        { reinterpret_cast<const void *>(&h264k::k_region_change<h264k::ST_YCBCR, false>), reinterpret_cast<const void *>(&h264k::k_region_change<h264k::ST_YCBCR, true>) },
-        { reinterpret_cast<const void *>(&h264k::k_region_change<h264k::ST_RGB, false>), reinterpret_cast<const void *>(&h264k::k_region_change<h264k::ST_RGB, true>) } };
-    uint32_t shift = 8u;
-    while (shift > 0u && (256u >> shift) != sp.bins) shift--;               /* bins == 256 >> shift; shift == 0 also stands for "no such shift" */
-    if (!sp.data || (reinterpret_cast<uintptr_t>(sp.data) & 7u) || sp.source > H264BSDMI_STATS_RGB || sp.crop > 1u || sp.keep_after > 1u) return -1;
-    if (sp.bins && (sp.bins < 16u || (256u >> shift) != sp.bins)) return -1;
+    uint32_t shift;
+    if (!sp.data || (reinterpret_cast<uintptr_t>(sp.data) & 7u) || sp.crop > 1u || sp.keep_after > 1u ||
+        !source_bins_ok(sp.source, sp.bins, &shift)) return -1;
     if (sp.threshold[0] > 255u || sp.threshold[1] > 255u || sp.threshold[2] > 255u) return -1;
     if (n_regs > 65535u) return -1;                                     /* grid.y */
-    if (!pull_pictures_ok(n, pics, true, false) || !pull_regions_ok(n, n_regs, regs, 1u, 1u)) return -1;
-    for (uint32_t i = 0; i < n; i++) {
-        const StreamCtx *s = pic_stream(pics[i]);
-        if (!s->d_kept || s->kept_wmb != s->wmb || s->kept_hmb != s->hmb) return -1;
-    }
+    if (!pull_pictures_ok(n, pics, true, false) || !pull_regions_ok(n, n_regs, regs, 1u, 1u) || !kept_pictures_ok(n, pics)) return -1;
     if (pull_begin_locked(e, n, pics, n_regs)) return -1;
     h264k::ChangeItem *items = e->titems.host<h264k::ChangeItem>();
     const uint32_t stride = h264k::change_record_bytes(sp.source == H264BSDMI_STATS_Y ? 1u : 3u, sp.bins);
-    uint32_t tallest = 1u;
+    uint32_t tallest = 0u;
     for (uint32_t r = 0; r < n_regs; r++) {
         const SinkRegion &g = regs[r];
         const SinkTensorPic &p = pics[g.pic];
         const StreamCtx *s = pic_stream(p);
-        const int64_t bx0 = std::max<int64_t>(g.x, 0), bx1 = std::min<int64_t>((int64_t)g.x + g.w, p.w);
-        const int64_t by0 = std::max<int64_t>(g.y, 0), by1 = std::min<int64_t>((int64_t)g.y + g.h, p.h);
-        h264k::ChangeItem it{ s->d_frames + (size_t)p.slot * s->frame_bytes, s->d_kept.get(), static_cast<uint8_t *>(sp.data) + (size_t)g.index * stride,
-                              s->wmb, 0u, 0u, 0u, 0u };
-        if (bx1 > bx0 && by1 > by0) {
-            it.x0 = p.x0 + (uint32_t)bx0; it.x1 = p.x0 + (uint32_t)bx1;
-            it.y0 = p.y0 + (uint32_t)by0; it.y1 = p.y0 + (uint32_t)by1;
-            tallest = std::max(tallest, ((it.y1 + 15u) >> 4) - (it.y0 >> 4));
-        }
-        items[r] = it;
+        const RegionClip c = region_clip(p, g);
+        items[r] = h264k::ChangeItem{ s->d_frames + (size_t)p.slot * s->frame_bytes, s->d_kept.get(),
+                                      static_cast<uint8_t *>(sp.data) + (size_t)g.index * stride, s->wmb, c.x0, c.y0, c.x1, c.y1 };
+        tallest = std::max(tallest, c.mb_rows);
     }
-    const uint32_t S = n_regs >= h264k::STATS_MAX_PARTIALS ? 1u : std::min(h264k::STATS_MAX_PARTIALS / n_regs, tallest);
-    h264k::ChangeArgs cargs{ e->titems.dev<h264k::ChangeItem>(), nullptr, nullptr, sp.bins, sp.bins ? shift : 0u, { sp.threshold[0], sp.threshold[1], sp.threshold[2] } };
-    if (S > 1u && stats_scratch_locked(e, st, &cargs.tickets, &cargs.partials)) return -1;
-    if (kept_order_begin(e, st)) return -1;
-    if (pull_launch_locked(e, n, pics, st, fns[sp.source][sp.bins != 0u], dim3(S, n_regs), &cargs, fence_ev)) return -1;
-    if (S > 1u) HIP_TRY(hipEventRecord(e->stats_ev, st));
-    return kept_order_end(e, st);
+    h264k::ChangeArgs cargs{ e->titems.dev<h264k::ChangeItem>(), nullptr, nullptr, sp.bins, shift, { sp.threshold[0], sp.threshold[1], sp.threshold[2] } };
+    return banded_launch_locked(e, n, pics, st, banded_kernel(true, sp.source, sp.bins != 0u), n_regs, tallest, &cargs, true, fence_ev);
 }
 
 /* h264bsdmiOutputRegionShift: one ShiftItem per region — the current picture and the kept picture of its instance, the record, box ∩
- * window and the window itself (the search clamps there), in luma samples of the coded frame — and ONE k_region_shift launch of S row
- * bands per region, S chosen as in stats_out_locked; with S > 1 the bands' partial SAD surfaces meet in the same scratch.  The kept
- * pictures' ordering as in change_out_locked; the sink does not look at keep_after. */
+ * window and the window itself (the search clamps there), in luma samples of the coded frame — and ONE banded k_region_shift launch,
+ * the bands' partial SAD surfaces in the scratch.  The kept pictures as in change_out_locked; the sink does not look at keep_after. */
 static int shift_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, uint32_t n_regs, const SinkRegion *regs,
                             const h264bsdmi_shift_spec &sp, hipStream_t st, hipEvent_t *fence_ev)
 {
@@ -1551,40 +1581,27 @@ static int shift_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, ui
     if (!pull_pictures_ok(n, pics, true, false) || !pull_regions_ok(n, n_regs, regs, 1u, 1u)) return -1;
     for (uint32_t r = 0; r < n_regs; r++)
         if (regs[r].w > H264BSDMI_SHIFT_MAX_SIDE || regs[r].h > H264BSDMI_SHIFT_MAX_SIDE) return -1;        /* the 32-bit sums */
-    for (uint32_t i = 0; i < n; i++) {
-        const StreamCtx *s = pic_stream(pics[i]);
-        if (!s->d_kept || s->kept_wmb != s->wmb || s->kept_hmb != s->hmb) return -1;
-    }
+    if (!kept_pictures_ok(n, pics)) return -1;
     if (pull_begin_locked(e, n, pics, n_regs)) return -1;
     h264k::ShiftItem *items = e->titems.host<h264k::ShiftItem>();
     const uint32_t stride = h264k::shift_record_bytes(sp.radius, sp.surface);
-    uint32_t tallest = 1u;
+    uint32_t tallest = 0u;
     for (uint32_t r = 0; r < n_regs; r++) {
         const SinkRegion &g = regs[r];
         const SinkTensorPic &p = pics[g.pic];
         const StreamCtx *s = pic_stream(p);
-        const int64_t bx0 = std::max<int64_t>(g.x, 0), bx1 = std::min<int64_t>((int64_t)g.x + g.w, p.w);
-        const int64_t by0 = std::max<int64_t>(g.y, 0), by1 = std::min<int64_t>((int64_t)g.y + g.h, p.h);
-        h264k::ShiftItem it{ s->d_frames + (size_t)p.slot * s->frame_bytes, s->d_kept.get(), static_cast<uint8_t *>(sp.data) + (size_t)g.index * stride,
-                             s->wmb, 0u, 0u, 0u, 0u, p.x0, p.y0, p.x0 + p.w, p.y0 + p.h };
-        if (bx1 > bx0 && by1 > by0) {
-            it.x0 = p.x0 + (uint32_t)bx0; it.x1 = p.x0 + (uint32_t)bx1;
-            it.y0 = p.y0 + (uint32_t)by0; it.y1 = p.y0 + (uint32_t)by1;
-            tallest = std::max(tallest, ((it.y1 + 15u) >> 4) - (it.y0 >> 4));
-        }
-        items[r] = it;
+        const RegionClip c = region_clip(p, g);
+        items[r] = h264k::ShiftItem{ s->d_frames + (size_t)p.slot * s->frame_bytes, s->d_kept.get(),
+                                     static_cast<uint8_t *>(sp.data) + (size_t)g.index * stride, s->wmb, c.x0, c.y0, c.x1, c.y1,
+                                     p.x0, p.y0, p.x0 + p.w, p.y0 + p.h };
+        tallest = std::max(tallest, c.mb_rows);
     }
-    const uint32_t S = n_regs >= h264k::STATS_MAX_PARTIALS ? 1u : std::min(h264k::STATS_MAX_PARTIALS / n_regs, tallest);
     /* from radius 4 on a thread takes three quads of displacements per template dword, below that one: as measured, each is the faster
      * on its side (docs/EXPERIMENTS.md, "Region shift") */
     const void *fn = sp.radius >= h264k::SHIFT_QUADS_FROM ? reinterpret_cast<const void *>(&h264k::k_region_shift<h264k::SHIFT_QUADS>)
                                                            : reinterpret_cast<const void *>(&h264k::k_region_shift<1u>);
     h264k::ShiftArgs sargs{ e->titems.dev<h264k::ShiftItem>(), nullptr, nullptr, sp.radius, sp.surface };
-    if (S > 1u && stats_scratch_locked(e, st, &sargs.tickets, &sargs.partials)) return -1;
-    if (kept_order_begin(e, st)) return -1;
-    if (pull_launch_locked(e, n, pics, st, fn, dim3(S, n_regs), &sargs, fence_ev)) return -1;
-    if (S > 1u) HIP_TRY(hipEventRecord(e->stats_ev, st));
-    return kept_order_end(e, st);
+    return banded_launch_locked(e, n, pics, st, fn, n_regs, tallest, &sargs, true, fence_ev);
 }
 
 /* h264bsdmiOutputCellMaps: one CellItem per region — the frame, in CHANGE mode the kept frame, the slice, the box's origin (signed) and
@@ -1612,10 +1629,7 @@ static int cells_prepare_locked(Engine *e, uint32_t n, const SinkTensorPic *pics
     if (!change && (sp.threshold[0] || sp.threshold[1] || sp.threshold[2] || sp.keep_after)) return -1;
     if (n_regs > 65535u) return -1;                                     /* grid.y */
     if (!pull_pictures_ok(n, pics, true, false) || !pull_regions_ok(n, n_regs, regs, 1u, 1u)) return -1;
-    for (uint32_t i = 0; change && i < n; i++) {
-        const StreamCtx *s = pic_stream(pics[i]);
-        if (!s->d_kept || s->kept_wmb != s->wmb || s->kept_hmb != s->hmb) return -1;
-    }
+    if (change && !kept_pictures_ok(n, pics)) return -1;
     const uint32_t rw = h264k::CELLS_RECT_W >> shift, rh = h264k::CELLS_RECT_H >> shift;
     const uint32_t rects_x = (sp.cols + rw - 1u) / rw, rects = rects_x * ((sp.rows + rh - 1u) / rh);
     if ((uint64_t)rects * n_regs > h264k::CELLS_MAX_WORKGROUPS) return -1;
@@ -1627,15 +1641,10 @@ static int cells_prepare_locked(Engine *e, uint32_t n, const SinkTensorPic *pics
         const SinkRegion &g = regs[r];
         const SinkTensorPic &p = pics[g.pic];
         const StreamCtx *s = pic_stream(p);
-        const int64_t bx0 = std::max<int64_t>(g.x, 0), bx1 = std::min<int64_t>((int64_t)g.x + g.w, p.w);
-        const int64_t by0 = std::max<int64_t>(g.y, 0), by1 = std::min<int64_t>((int64_t)g.y + g.h, p.h);
-        h264k::CellItem it{ s->d_frames + (size_t)p.slot * s->frame_bytes, change ? s->d_kept.get() : nullptr,
-                            static_cast<uint32_t *>(sp.data) + (size_t)g.index * slice, s->wmb, (int32_t)p.x0 + g.x, (int32_t)p.y0 + g.y, 0u, 0u, 0u, 0u };
-        if (bx1 > bx0 && by1 > by0) {
-            it.x0 = p.x0 + (uint32_t)bx0; it.x1 = p.x0 + (uint32_t)bx1;
-            it.y0 = p.y0 + (uint32_t)by0; it.y1 = p.y0 + (uint32_t)by1;
-        }
-        items[r] = it;
+        const RegionClip c = region_clip(p, g);
+        items[r] = h264k::CellItem{ s->d_frames + (size_t)p.slot * s->frame_bytes, change ? s->d_kept.get() : nullptr,
+                                    static_cast<uint32_t *>(sp.data) + (size_t)g.index * slice, s->wmb, (int32_t)p.x0 + g.x, (int32_t)p.y0 + g.y,
+                                    c.x0, c.y0, c.x1, c.y1 };
     }
     const bool quad = sp.cell >= 16u;
     const void *const fns[2][3] = {
@@ -1757,39 +1766,38 @@ int sink_tensor_out(uint32_t n, const SinkTensorPic *pics, const h264bsdmi_tenso
         return tensor_out_locked(e, n, pics, *spec, chroma, resize, st, fence_ev);
     });
 }
+/* the calls that take a list (regions, maps): nothing to do without items, a refusal without one of the pointers */
+template <typename Body> static int sink_list_call(uint32_t n, const SinkTensorPic *pics, uint32_t n_items, bool pointers, void *stream, Body body)
+{
+    if (!n_items) return 0;
+    if (!pointers) return -1;
+    return sink_tensor_call(n, pics, stream, body);
+}
 int sink_tensor_regions(uint32_t n, const SinkTensorPic *pics, uint32_t n_regions, const SinkRegion *regions,
                         const h264bsdmi_tensor_spec *spec, uint32_t chroma, const h264bsdmi_resize_spec *resize, void *stream)
 {
-    if (!n_regions) return 0;
-    if (!regions || !resize || (n && !spec)) return -1;
-    return sink_tensor_call(n, pics, stream, [&](Engine *e, hipStream_t st, hipEvent_t *fence_ev) {
+    return sink_list_call(n, pics, n_regions, regions && resize && (!n || spec), stream, [&](Engine *e, hipStream_t st, hipEvent_t *fence_ev) {
         return regions_out_locked(e, n, pics, n_regions, regions, *spec, chroma, *resize, st, fence_ev);
     });
 }
 int sink_motion_regions(uint32_t n, const SinkTensorPic *pics, uint32_t n_regions, const SinkRegion *regions,
                         const h264bsdmi_motion_spec *spec, void *stream)
 {
-    if (!n_regions) return 0;
-    if (!regions || !spec) return -1;
-    return sink_tensor_call(n, pics, stream, [&](Engine *e, hipStream_t st, hipEvent_t *fence_ev) {
+    return sink_list_call(n, pics, n_regions, regions && spec, stream, [&](Engine *e, hipStream_t st, hipEvent_t *fence_ev) {
         return motion_out_locked(e, n, pics, n_regions, regions, *spec, st, fence_ev);
     });
 }
 int sink_tensor_remap(uint32_t n, const SinkTensorPic *pics, uint32_t n_maps, const SinkRemap *maps,
                       const h264bsdmi_tensor_spec *spec, uint32_t chroma, const h264bsdmi_remap_spec *remap, void *stream)
 {
-    if (!n_maps) return 0;
-    if (!maps || !spec || !remap) return -1;
-    return sink_tensor_call(n, pics, stream, [&](Engine *e, hipStream_t st, hipEvent_t *fence_ev) {
+    return sink_list_call(n, pics, n_maps, maps && spec && remap, stream, [&](Engine *e, hipStream_t st, hipEvent_t *fence_ev) {
         return remap_out_locked(e, n, pics, n_maps, maps, *spec, chroma, *remap, st, fence_ev);
     });
 }
 int sink_region_stats(uint32_t n, const SinkTensorPic *pics, uint32_t n_regions, const SinkRegion *regions,
                       const h264bsdmi_stats_spec *spec, void *stream)
 {
-    if (!n_regions) return 0;
-    if (!regions || !spec) return -1;
-    return sink_tensor_call(n, pics, stream, [&](Engine *e, hipStream_t st, hipEvent_t *fence_ev) {
+    return sink_list_call(n, pics, n_regions, regions && spec, stream, [&](Engine *e, hipStream_t st, hipEvent_t *fence_ev) {
         return stats_out_locked(e, n, pics, n_regions, regions, *spec, st, fence_ev);
     });
 }
@@ -1802,36 +1810,28 @@ int sink_keep_pictures(uint32_t n, const SinkTensorPic *pics, void *stream)
 int sink_region_change(uint32_t n, const SinkTensorPic *pics, uint32_t n_regions, const SinkRegion *regions,
                        const h264bsdmi_change_spec *spec, void *stream)
 {
-    if (!n_regions) return 0;
-    if (!regions || !spec) return -1;
-    return sink_tensor_call(n, pics, stream, [&](Engine *e, hipStream_t st, hipEvent_t *fence_ev) {
+    return sink_list_call(n, pics, n_regions, regions && spec, stream, [&](Engine *e, hipStream_t st, hipEvent_t *fence_ev) {
         return change_out_locked(e, n, pics, n_regions, regions, *spec, st, fence_ev);
     });
 }
 int sink_region_shift(uint32_t n, const SinkTensorPic *pics, uint32_t n_regions, const SinkRegion *regions,
                       const h264bsdmi_shift_spec *spec, void *stream)
 {
-    if (!n_regions) return 0;
-    if (!regions || !spec) return -1;
-    return sink_tensor_call(n, pics, stream, [&](Engine *e, hipStream_t st, hipEvent_t *fence_ev) {
+    return sink_list_call(n, pics, n_regions, regions && spec, stream, [&](Engine *e, hipStream_t st, hipEvent_t *fence_ev) {
         return shift_out_locked(e, n, pics, n_regions, regions, *spec, st, fence_ev);
     });
 }
 int sink_cell_maps(uint32_t n, const SinkTensorPic *pics, uint32_t n_regions, const SinkRegion *regions,
                    const h264bsdmi_cells_spec *spec, void *stream)
 {
-    if (!n_regions) return 0;
-    if (!regions || !spec) return -1;
-    return sink_tensor_call(n, pics, stream, [&](Engine *e, hipStream_t st, hipEvent_t *fence_ev) {
+    return sink_list_call(n, pics, n_regions, regions && spec, stream, [&](Engine *e, hipStream_t st, hipEvent_t *fence_ev) {
         return cells_out_locked(e, n, pics, n_regions, regions, *spec, st, fence_ev);
     });
 }
 int sink_cell_boxes(uint32_t n, const SinkTensorPic *pics, uint32_t n_regions, const SinkRegion *regions,
                     const h264bsdmi_cells_spec *cells, const h264bsdmi_boxes_spec *boxes, void *stream)
 {
-    if (!n_regions) return 0;
-    if (!regions || !cells || !boxes) return -1;
-    return sink_tensor_call(n, pics, stream, [&](Engine *e, hipStream_t st, hipEvent_t *fence_ev) {
+    return sink_list_call(n, pics, n_regions, regions && cells && boxes, stream, [&](Engine *e, hipStream_t st, hipEvent_t *fence_ev) {
         return cell_boxes_out_locked(e, n, pics, n_regions, regions, *cells, *boxes, st, fence_ev);
     });
 }

@@ -1,7 +1,7 @@
 /* kernels/k_cell_maps.hip.h — dense per-cell maps of the quantities of k_region_stats (MODE 0, PICTURE) or k_region_change (MODE 1,
  * CHANGE) over a grid of square cells laid over a box (h264bsdmiOutputCellMaps): one u32 per cell and map, read from the macroblock
- * tiles where the pictures lie.  Included by engine.hip after k_region_change.hip.h, whose loader (change_load) and whose arithmetic
- * per dword it uses; like it, not part of the kernel sources that key the committed counter tables (srchash.py).
+ * tiles where the pictures lie.  Included by engine.hip after k_region_change.hip.h, whose arithmetic per dword it uses, with the
+ * loader and the mask of region_common.hip.h (region_load, region_mask); like them, not part of the kernel sources that key the committed counter tables (srchash.py).
  *
  * A slice: P maps of rows x cols u32, row-major: COUNT if asked, then per selected plane, in ascending bit order, C maps.
  * grid (rectangles of cells, regions) x 256.  A workgroup OWNS a rectangle of CELLS_RECT_W x CELLS_RECT_H luma samples of the grid,
@@ -84,12 +84,7 @@ __global__ __launch_bounds__(256) void k_cell_maps(CellArgs a)
             const uint32_t mby = mby0 + i / mcols, mbx = mbx0 + i % mcols;
             const size_t at = ((size_t)mby * it.wmb + mbx) * TILE;
             const int px = (int)mbx * 16 + col4, py = (int)mby * 16 + row;
-            uint32_t m = 0u;
-            if (py >= ry0 && py < ry1) {
-#pragma unroll
-                for (int k = 0; k < 4; k++)
-                    if (px + k >= rx0 && px + k < rx1) m |= 0xFFu << (8 * k);
-            }
+            const uint32_t m = region_mask(px, py, rx0, ry0, rx1, ry1);
             /* the cut: the first cell boundary behind `from` (the row's first sample, or this lane's); part 0 before it, part 1 from it on */
             const int from = QUAD ? (int)mbx * 16 : px, ub = from - it.ox;
             const int cut = min(max(from + cell - (ub & (cell - 1)) - px, 0), 4);
@@ -105,8 +100,8 @@ __global__ __launch_bounds__(256) void k_cell_maps(CellArgs a)
                 part[p] = __builtin_amdgcn_ballot_w64(pm[p] != 0u) != 0ull;
             }
             uint32_t va[C], vb[C];
-            change_load<SRC>(it.cur + at, lane, va);
-            if constexpr (MODE == 1) change_load<SRC>(it.kept + at, lane, vb);
+            region_load<SRC>(it.cur + at, lane, va);
+            if constexpr (MODE == 1) region_load<SRC>(it.kept + at, lane, vb);
 #pragma unroll
             for (int c = 0; c < C; c++) {
                 const uint32_t base = (uint32_t)c * NP * ncell + at0;      /* (at0 may be one before its row: only at0 + 1 is used then) */
@@ -118,11 +113,11 @@ __global__ __launch_bounds__(256) void k_cell_maps(CellArgs a)
                     if constexpr (MODE == 0) {
                         if (planes & 2u) {
                             const uint32_t s = cells_row_sum<QUAD>(__builtin_amdgcn_udot4(av, 0x01010101u, 0u, false));
-                            if (commit[p]) stats_hist_add(acc, s);
+                            if (commit[p]) region_lds_add(acc, s);
                         }
                         if (planes & 4u) {
                             const uint32_t q = cells_row_sum<QUAD>(__builtin_amdgcn_udot4(av, av, 0u, false));
-                            if (commit[p]) stats_hist_add(acc + ncell, q);
+                            if (commit[p]) region_lds_add(acc + ncell, q);
                         }
                         if (planes & 8u) {
                             const uint32_t lo4 = va[c] | ~pm[p];
@@ -146,15 +141,15 @@ __global__ __launch_bounds__(256) void k_cell_maps(CellArgs a)
                         }
                         if (planes & 2u) {
                             const uint32_t s = cells_row_sum<QUAD>(__builtin_amdgcn_udot4(ad, 0x01010101u, 0u, false));
-                            if (commit[p]) stats_hist_add(acc, s);
+                            if (commit[p]) region_lds_add(acc, s);
                         }
                         if (planes & 4u) {
                             const uint32_t q = cells_row_sum<QUAD>(__builtin_amdgcn_udot4(ad, ad, 0u, false));
-                            if (commit[p]) stats_hist_add(acc + ncell, q);
+                            if (commit[p]) region_lds_add(acc + ncell, q);
                         }
                         if (planes & 8u) {                                      /* the signed sum, modulo 2^32 */
                             const uint32_t g = cells_row_sum<QUAD>(__builtin_amdgcn_udot4(av, 0x01010101u, 0u, false) - __builtin_amdgcn_udot4(bv, 0x01010101u, 0u, false));
-                            if (commit[p]) stats_hist_add(acc + 2u * ncell, g);
+                            if (commit[p]) region_lds_add(acc + 2u * ncell, g);
                         }
                         if (planes & 16u) {
                             hi = cells_row_max<QUAD>(hi);
@@ -162,7 +157,7 @@ __global__ __launch_bounds__(256) void k_cell_maps(CellArgs a)
                         }
                         if (planes & 32u) {
                             ab = cells_row_sum<QUAD>(ab);
-                            if (commit[p]) stats_hist_add(acc + 4u * ncell, ab);
+                            if (commit[p]) region_lds_add(acc + 4u * ncell, ab);
                         }
                     }
                 }

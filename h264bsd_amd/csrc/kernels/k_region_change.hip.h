@@ -1,7 +1,7 @@
 /* kernels/k_region_change.hip.h — integer statistics of the DIFFERENCE between two pictures over boxes (h264bsdmiOutputRegionChange):
  * an instance's current picture against the picture it kept (k_keep.hip.h), both read from their macroblock tiles where they lie, at
- * the same tile offset.  Included by engine.hip after k_region_stats.hip.h, whose scheme, constants and wave reduction it uses; like
- * it, not part of the kernel sources that key the committed counter tables (srchash.py).
+ * the same tile offset.  Included by engine.hip after k_region_stats.hip.h, whose scheme and constants it uses, with the shared
+ * pieces of region_common.hip.h; like them, not part of the kernel sources that key the committed counter tables (srchash.py).
  *
  * One record, C channels (1 or 3) and B bins (0, 16 .. 256), little endian, 8 + 32 C + 4 C B bytes; d = current - kept per sample:
  *     u32 count; u32 zero;  C x { u64 sad; u64 ssd; i64 sum; u32 max; u32 above; }  C x B x u32 hist      (hist of |d|)
@@ -18,9 +18,8 @@
  * does as well as k_region_stats' four lane-replicated copies on moving pictures and, at a quarter of the LDS, better on equal ones
  * (both measured, with and without bin 0 in LDS: docs/EXPERIMENTS.md, "Change statistics").
  * S == 1: the workgroup writes the record.  S > 1: partial records (the same layout, bin 0 still open) meet in the engine's scratch
- * and the ticket hand-over is k_region_stats': every storing wavefront drains, one lane releases at agent scope and takes the
- * region's ticket; the band that draws the last one acquires, adds the S partials up, writes the record with plain vector stores and
- * zeroes the ticket.  All integers: the result does not depend on which band arrives last. */
+ * behind region_hand_over: the band that draws the last ticket adds the S partials up, writes the record with plain vector stores
+ * and zeroes the ticket.  All integers: the result does not depend on which band arrives last. */
 #pragma once
 namespace h264k {
 
@@ -36,35 +35,6 @@ struct ChangeItem { const uint8_t *cur; const uint8_t *kept; uint8_t *dst; uint3
 /* partials, tickets: as StatsArgs (region r's partial records at (r S + band) stride); shift = 8 - log2 bins; thr: per channel */
 struct ChangeArgs { const ChangeItem *items; uint8_t *partials; uint32_t *tickets; uint32_t bins, shift, thr[3]; };
 
-/* the four samples of every channel of one lane's place in a tile, one per byte */
-template <int SRC>
-__device__ __forceinline__ void change_load(const uint8_t *tile, uint32_t lane, uint32_t *v)
-{
-    v[0] = reinterpret_cast<const uint32_t *>(tile)[lane];
-    if constexpr (SRC != ST_Y) {
-        const uint32_t at = (lane >> 3) * 8u + (lane & 3u) * 2u;          /* chroma row (l >> 2) >> 1, columns 2 (l & 3), + 1 */
-        const uint32_t cb2 = *reinterpret_cast<const uint16_t *>(tile + T_CB + at), cr2 = *reinterpret_cast<const uint16_t *>(tile + T_CR + at);
-        if constexpr (SRC == ST_YCBCR) {
-            v[1] = (cb2 & 255u) * 0x0101u | (cb2 >> 8) * 0x01010000u;
-            v[2] = (cr2 & 255u) * 0x0101u | (cr2 >> 8) * 0x01010000u;
-        } else {
-            const uint32_t yv = v[0];
-            v[0] = v[1] = v[2] = 0u;
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                uint32_t px = yuv_pixel(0, (int)((yv >> (8 * k)) & 255u), (int)((cb2 >> (8 * (k >> 1))) & 255u), (int)((cr2 >> (8 * (k >> 1))) & 255u));
-                /* the pixel is opaque from here on: seen through, the shift-and-clamp of two neighbours and their packing below were
-                 * fused into one v_ashr_pk_u8_i32 in k_cell_maps (and nowhere else), whose results on the device differed from
-                 * clip255(x >> 8) in a few samples per picture (docs/EXPERIMENTS.md, "Cell maps") */
-                asm volatile("" : "+v"(px));
-                v[0] |= (px & 255u) << (8 * k);
-                v[1] |= ((px >> 8) & 255u) << (8 * k);
-                v[2] |= ((px >> 16) & 255u) << (8 * k);
-            }
-        }
-    }
-}
-
 /* per channel, what a lane carries between folds (32 bits) */
 struct ChangeAcc { uint32_t sad, ssd, sc, sk; };
 
@@ -75,8 +45,8 @@ __device__ __forceinline__ void change_mb(const uint8_t *tc, const uint8_t *tk, 
 {
     constexpr int C = SRC == ST_Y ? 1 : 3;
     uint32_t a[C], b[C];
-    change_load<SRC>(tc, lane, a);
-    change_load<SRC>(tk, lane, b);
+    region_load<SRC>(tc, lane, a);
+    region_load<SRC>(tk, lane, b);
 #pragma unroll
     for (int c = 0; c < C; c++) {
         const uint32_t av = INNER ? a[c] : a[c] & m, bv = INNER ? b[c] : b[c] & m;
@@ -98,14 +68,14 @@ __device__ __forceinline__ void change_mb(const uint8_t *tc, const uint8_t *tk, 
             if (INNER && SRC == ST_YCBCR && c > 0) {
                 if (!(lane & 4u)) {                                        /* the even luma row of the pair that shares these two samples */
                     const uint32_t b0 = (ad & 255u) >> shift, b1 = (ad >> 24) >> shift;
-                    if (b0) stats_hist_add(hc + b0, 4u);
-                    if (b1) stats_hist_add(hc + b1, 4u);
+                    if (b0) region_lds_add(hc + b0, 4u);
+                    if (b1) region_lds_add(hc + b1, 4u);
                 }
             } else {
 #pragma unroll
                 for (int k = 0; k < 4; k++) {
                     const uint32_t bin = ((ad >> (8 * k)) & 255u) >> shift;
-                    if ((INNER || ((m >> (8 * k)) & 1u)) && bin) stats_hist_add(hc + bin, 1u);
+                    if ((INNER || ((m >> (8 * k)) & 1u)) && bin) region_lds_add(hc + bin, 1u);
                 }
             }
         }
@@ -121,7 +91,6 @@ __global__ __launch_bounds__(256) void k_region_change(ChangeArgs a)
     __shared__ unsigned long long s_sum[4][C][3];
     __shared__ uint32_t s_mm[4][C][2];
     __shared__ uint32_t s_rest[3];                                          /* per channel: what the bins other than 0 hold */
-    __shared__ uint32_t s_last;
     const ChangeItem it = a.items[blockIdx.y];
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
     const uint32_t B = a.bins, S = gridDim.x, band = blockIdx.x, stride = change_record_bytes(C, B);
@@ -131,10 +100,9 @@ __global__ __launch_bounds__(256) void k_region_change(ChangeArgs a)
         for (uint32_t i = tid; i < 4u * HCAP; i += 256u) s_hist[i] = 0u;
     }
     __syncthreads();
-    const bool empty = it.x1 <= it.x0 || it.y1 <= it.y0;
-    const uint32_t mbx0 = it.x0 >> 4, mby0 = it.y0 >> 4;
-    const uint32_t cols = empty ? 0u : ((it.x1 + 15u) >> 4) - mbx0, rows = empty ? 0u : ((it.y1 + 15u) >> 4) - mby0;
-    const uint32_t r0 = mby0 + rows * band / S, r1 = mby0 + rows * (band + 1u) / S, n = (r1 - r0) * cols;
+    const RegionBand bd = region_band(it.x0, it.y0, it.x1, it.y1, band, S);
+    const bool empty = bd.empty;
+    const uint32_t mbx0 = bd.mbx0, cols = bd.cols, r0 = bd.r0, n = (bd.r1 - r0) * cols;
     const uint32_t col4 = (lane & 3u) * 4u, row = lane >> 2;
     uint32_t *h = s_hist + (HIST ? wave * HCAP : 0u);
 
@@ -152,15 +120,10 @@ __global__ __launch_bounds__(256) void k_region_change(ChangeArgs a)
             const uint32_t mby = r0 + i / cols, mbx = mbx0 + i % cols;
             const size_t at = ((size_t)mby * it.wmb + mbx) * TILE;
             const uint32_t X = mbx * 16u, Y = mby * 16u;
-            if (X >= it.x0 && X + 16u <= it.x1 && Y >= it.y0 && Y + 16u <= it.y1) {
+            if (REGION_MB_INNER(X, Y, it)) {
                 change_mb<SRC, HIST, true>(it.cur + at, it.kept + at, lane, 0xFFFFFFFFu, h, B, a.shift, thr, acc, mx, above);
             } else {
-                uint32_t m = 0u;
-                if (Y + row >= it.y0 && Y + row < it.y1) {
-#pragma unroll
-                    for (int k = 0; k < 4; k++)
-                        if (X + col4 + k >= it.x0 && X + col4 + k < it.x1) m |= 0xFFu << (8 * k);
-                }
+                const uint32_t m = region_mask(X + col4, Y + row, it.x0, it.y0, it.x1, it.y1);
                 change_mb<SRC, HIST, false>(it.cur + at, it.kept + at, lane, m, h, B, a.shift, thr, acc, mx, above);
             }
         }
@@ -199,7 +162,7 @@ __global__ __launch_bounds__(256) void k_region_change(ChangeArgs a)
             for (uint32_t k = 0; k < 4u; k++) t += s_hist[k * HCAP + i];
             if (closes && !(i & bmask)) continue;
             out32[2u + 8u * C + i] = t;
-            if (closes && t) stats_hist_add(&s_rest[i >> blog], t);
+            if (closes && t) region_lds_add(&s_rest[i >> blog], t);
         }
         if (closes) {
             __syncthreads();
@@ -208,21 +171,7 @@ __global__ __launch_bounds__(256) void k_region_change(ChangeArgs a)
     }
     if (S == 1u) return;
 
-    /* the hand-over: every storing wavefront drains, one lane releases at device scope and takes the ticket; the last acquires */
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0u) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const uint32_t t = __hip_atomic_fetch_add(&a.tickets[blockIdx.y], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        s_last = t == S - 1u ? 1u : 0u;
-        if (t == S - 1u) {
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-    }
-    __syncthreads();
-    if (!s_last) return;
+    if (!region_hand_over(a.tickets, S)) return;
     const uint8_t *pp = a.partials + (size_t)blockIdx.y * S * stride;
     uint32_t *dst32 = reinterpret_cast<uint32_t *>(it.dst);
     if (tid == 0u) { dst32[0] = count; dst32[1] = 0u; }
@@ -247,12 +196,12 @@ __global__ __launch_bounds__(256) void k_region_change(ChangeArgs a)
             for (uint32_t b = 0; b < S; b++) t += reinterpret_cast<const uint32_t *>(pp + (size_t)b * stride)[2u + 8u * C + i];
             if (!(i & bmask)) continue;
             dst32[2u + 8u * C + i] = t;
-            if (t) stats_hist_add(&s_rest[i >> blog], t);
+            if (t) region_lds_add(&s_rest[i >> blog], t);
         }
         __syncthreads();
         if (tid < (uint32_t)C) dst32[2u + 8u * C + tid * B] = count - s_rest[tid];
     }
-    if (tid == 0u) __hip_atomic_store(&a.tickets[blockIdx.y], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    region_ticket_rezero(a.tickets);
 }
 
 } // namespace h264k

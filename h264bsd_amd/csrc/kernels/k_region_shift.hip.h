@@ -1,6 +1,6 @@
 /* kernels/k_region_shift.hip.h — WHERE did a box go: block-matching SAD search of boxes of the KEPT picture (k_keep.hip.h) in the
  * CURRENT picture of the same instance (h264bsdmiOutputRegionShift), luma only, both read from their macroblock tiles where they lie.
- * Included by engine.hip after k_region_change.hip.h, whose band / ticket scheme (k_region_stats.hip.h) and wave reduction it uses;
+ * Included by engine.hip after k_region_change.hip.h; the band / ticket scheme and the wave reduction are region_common.hip.h's;
  * like them, not part of the kernel sources that key the committed counter tables (srchash.py).
  *
  * One record, R = radius (0 .. 16), D = 2 R + 1, little endian, 32 bytes, with the surface 32 + 4 (D D + 1):
@@ -29,8 +29,8 @@
  * Two other inner loops were measured and lost (docs/EXPERIMENTS.md, "Region shift"): v_sad_u8 per displacement, and
  * v_mqsad_pk_u16_u8, which SKIPS bytes that are 0 in its reference operand and so needs a guard; tools/experiments/shift_inner_loops.patch
  * puts them back behind -DSHIFT_INNER for whoever wants to measure again.
- * S == 1: the workgroup closes the record.  S > 1: the bands' D D partial sums meet in the engine's scratch under k_region_stats'
- * ticket hand-over; the band that draws the last ticket adds them up and closes the record: argmin with the tie rule (smallest SAD,
+ * S == 1: the workgroup closes the record.  S > 1: the bands' D D partial sums meet in the engine's scratch under
+ * region_hand_over; the band that draws the last ticket adds them up and closes the record: argmin with the tie rule (smallest SAD,
  * then smallest dx^2 + dy^2, then smallest dy, then smallest dx) as ONE 64-bit key per displacement, the number of ties, the header and
  * the surface with plain vector stores.  All integers: the result does not depend on which band arrives last. */
 #pragma once
@@ -105,7 +105,6 @@ __global__ __launch_bounds__(256) void k_region_shift(ShiftArgs a)
     __shared__ uint32_t s_sad[SHIFT_MAX_D * 4u * SHIFT_MAX_Q];              /* row dy + R at a pitch of SP */
     __shared__ unsigned long long s_key[4];
     __shared__ uint32_t s_ties[4];
-    __shared__ uint32_t s_last;
     const ShiftItem it = a.items[blockIdx.y];
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint32_t R = a.radius, D = 2u * R + 1u, Q3 = ((D + 3u) / 4u + QUADS - 1u) / QUADS, P = D * Q3, G = (SHIFT_SPLIT + P - 1u) / P;
@@ -113,9 +112,9 @@ __global__ __launch_bounds__(256) void k_region_shift(ShiftArgs a)
     const uint32_t S = gridDim.x, band = blockIdx.x, n = D * D;
     for (uint32_t i = tid; i < D * SP; i += 256u) s_sad[i] = 0u;
 
-    const bool empty = it.x1 <= it.x0 || it.y1 <= it.y0;
-    const uint32_t mby0 = it.y0 >> 4, rows = empty ? 0u : ((it.y1 + 15u) >> 4) - mby0;
-    const uint32_t r0 = mby0 + rows * band / S, r1 = mby0 + rows * (band + 1u) / S;
+    const RegionBand bd = region_band(it.x0, it.y0, it.x1, it.y1, band, S);
+    const bool empty = bd.empty;
+    const uint32_t r0 = bd.r0, r1 = bd.r1;
     const uint32_t ya = max(it.y0, r0 * 16u), yb = empty ? ya : min(it.y1, r1 * 16u);           /* this band's template rows */
     for (uint32_t ys = ya; ys < yb; ys += SHIFT_ROWS) {
         const uint32_t th = min(SHIFT_ROWS, yb - ys);
@@ -166,7 +165,7 @@ __global__ __launch_bounds__(256) void k_region_shift(ShiftArgs a)
 #pragma unroll
                     for (uint32_t k = 0; k < 4u; k++) {
                         const uint32_t dxi = 4u * (q + j) + k;
-                        if (dxi < D && sum[j][k]) stats_hist_add(&s_sad[dyi * SP + dxi], sum[j][k]);
+                        if (dxi < D && sum[j][k]) region_lds_add(&s_sad[dyi * SP + dxi], sum[j][k]);
                     }
             }
         }
@@ -174,23 +173,10 @@ __global__ __launch_bounds__(256) void k_region_shift(ShiftArgs a)
     __syncthreads();
 
     if (S > 1u) {
-        /* the hand-over of k_region_stats: every storing wavefront drains, one lane releases at device scope and takes the ticket */
+        /* the bands' partial surfaces meet in the scratch */
         uint32_t *part = reinterpret_cast<uint32_t *>(a.partials) + ((size_t)blockIdx.y * S + band) * n;
         for (uint32_t i = tid; i < n; i += 256u) part[i] = s_sad[(i / D) * SP + i % D];
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (tid == 0u) {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            const uint32_t t = __hip_atomic_fetch_add(&a.tickets[blockIdx.y], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            s_last = t == S - 1u ? 1u : 0u;
-            if (t == S - 1u) {
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            }
-        }
-        __syncthreads();
-        if (!s_last) return;
+        if (!region_hand_over(a.tickets, S)) return;
         const uint32_t *pp = reinterpret_cast<const uint32_t *>(a.partials) + (size_t)blockIdx.y * S * n;
         for (uint32_t i = tid; i < n; i += 256u) {
             uint32_t t = 0u;
@@ -232,7 +218,7 @@ __global__ __launch_bounds__(256) void k_region_shift(ShiftArgs a)
     if (a.surface) {
         for (uint32_t i = tid; i <= n; i += 256u) dst32[8u + i] = i < n ? s_sad[(i / D) * SP + i % D] : 0u;
     }
-    if (S > 1u && tid == 0u) __hip_atomic_store(&a.tickets[blockIdx.y], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    region_ticket_rezero(a.tickets, S > 1u);
 }
 
 } // namespace h264k

@@ -1,7 +1,7 @@
 /* kernels/k_region_stats.hip.h — integer statistics of boxes of decoded pictures, read from the macroblock tiles where they lie
  * (h264bsdmiOutputRegionStats): per region the number of samples, and per channel their sum, sum of squares, minimum, maximum and
- * a histogram.  Included by engine.hip after the k_tensor_* headers; like them, not part of the kernel sources that key the
- * committed counter tables (srchash.py).
+ * a histogram.  Included by engine.hip after region_common.hip.h, whose loader, masks, band geometry and hand-over it uses; like it,
+ * not part of the kernel sources that key the committed counter tables (srchash.py).
  *
  * One record, C channels (1 or 3) and B bins (0, 16 .. 256), little endian, 8 + 24 C + 4 C B bytes:
  *     u32 count; u32 zero;  C x { u64 sum; u64 sumsq; u32 min; u32 max; }  C x B x u32 hist
@@ -11,14 +11,12 @@
  * mask: a masked byte is 0 for the sums and the maximum, 255 for the minimum, and is not counted).  Moments stay in registers per
  * lane (32-bit partial sums folded into 64 bits every STATS_FOLD macroblocks) and are reduced once per workgroup; histograms are
  * wavefront-private in LDS (STATS_HIST_COPIES lane-replicated copies each), filled by LDS adds without return.
- * S == 1: the workgroup writes the record.  S > 1: every band writes a partial record (the same layout) to the engine's scratch,
- * drains its stores, and one lane releases them at device scope and takes the region's ticket; the band that draws the last ticket
- * acquires, adds the S partials up and writes the record with plain stores, then zeroes the ticket for the next launch.  All
- * integers: the result does not depend on which band arrives last. */
+ * S == 1: the workgroup writes the record.  S > 1: every band writes a partial record (the same layout) to the engine's scratch;
+ * behind region_hand_over the band that drew the last ticket adds the S partials up and writes the record with plain stores, then
+ * zeroes the ticket for the next launch.  All integers: the result does not depend on which band arrives last. */
 #pragma once
 namespace h264k {
 
-enum { ST_Y = 0, ST_YCBCR = 1, ST_RGB = 2 };
 /* the two ways of taking pressure off one LDS bin, both on as measured (docs/EXPERIMENTS.md, "Region statistics"): copies of a
  * wavefront's histogram chosen by lane % STATS_HIST_COPIES, one bank apart (4 copies: 48 KB of LDS for three channels; a flat picture,
  * where all 64 lanes add to one bin, costs 3.0-3.8 times less than with one copy); and, in an interior macroblock, ONE add of 4 per
@@ -41,11 +39,6 @@ struct StatsItem { const uint8_t *src; uint8_t *dst; uint32_t wmb, x0, y0, x1, y
  * between launches; shift = 8 - log2 bins */
 struct StatsArgs { const StatsItem *items; uint8_t *partials; uint32_t *tickets; uint32_t bins, shift; };
 
-__device__ __forceinline__ void stats_hist_add(uint32_t *p, uint32_t v)
-{
-    (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);      /* no return value used: ds_add_u32 */
-}
-
 /* the four samples v (one per byte) of channel c of one lane; m: 0xFF in the bytes that count */
 template <bool INNER>
 __device__ __forceinline__ void stats_moments(uint32_t v, uint32_t m, uint32_t &s32, uint32_t &q32, uint32_t &mn, uint32_t &mx)
@@ -67,25 +60,7 @@ __device__ __forceinline__ void stats_mb(const uint8_t *tile, uint32_t lane, uin
 {
     constexpr int C = SRC == ST_Y ? 1 : 3;
     uint32_t v[C];
-    v[0] = reinterpret_cast<const uint32_t *>(tile)[lane];
-    if constexpr (C == 3) {
-        const uint32_t at = (lane >> 3) * 8u + (lane & 3u) * 2u;          /* chroma row (l >> 2) >> 1, columns 2 (l & 3), + 1 */
-        const uint32_t cb2 = *reinterpret_cast<const uint16_t *>(tile + T_CB + at), cr2 = *reinterpret_cast<const uint16_t *>(tile + T_CR + at);
-        if constexpr (SRC == ST_YCBCR) {
-            v[1] = (cb2 & 255u) * 0x0101u | (cb2 >> 8) * 0x01010000u;
-            v[2] = (cr2 & 255u) * 0x0101u | (cr2 >> 8) * 0x01010000u;
-        } else {
-            const uint32_t yv = v[0];
-            v[0] = v[1] = v[2] = 0u;
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                const uint32_t px = yuv_pixel(0, (int)((yv >> (8 * k)) & 255u), (int)((cb2 >> (8 * (k >> 1))) & 255u), (int)((cr2 >> (8 * (k >> 1))) & 255u));
-                v[0] |= (px & 255u) << (8 * k);
-                v[1] |= ((px >> 8) & 255u) << (8 * k);
-                v[2] |= ((px >> 16) & 255u) << (8 * k);
-            }
-        }
-    }
+    region_load<SRC>(tile, lane, v);
 #pragma unroll
     for (int c = 0; c < C; c++) {
         stats_moments<INNER>(v[c], m, s32[c], q32[c], mn[c], mx[c]);
@@ -93,23 +68,16 @@ __device__ __forceinline__ void stats_mb(const uint8_t *tile, uint32_t lane, uin
             uint32_t *hc = h + (uint32_t)c * B;
             if (STATS_CHROMA_MULT && INNER && SRC == ST_YCBCR && c > 0) {
                 if (!(lane & 4u)) {                                        /* the even luma row of the pair that shares these two samples */
-                    stats_hist_add(hc + ((v[c] & 255u) >> shift), 4u);
-                    stats_hist_add(hc + ((v[c] >> 24) >> shift), 4u);
+                    region_lds_add(hc + ((v[c] & 255u) >> shift), 4u);
+                    region_lds_add(hc + ((v[c] >> 24) >> shift), 4u);
                 }
             } else {
 #pragma unroll
                 for (int k = 0; k < 4; k++)
-                    if (INNER || ((m >> (8 * k)) & 1u)) stats_hist_add(hc + (((v[c] >> (8 * k)) & 255u) >> shift), 1u);
+                    if (INNER || ((m >> (8 * k)) & 1u)) region_lds_add(hc + (((v[c] >> (8 * k)) & 255u) >> shift), 1u);
             }
         }
     }
-}
-
-template <class T> __device__ __forceinline__ T stats_wave_sum(T v)
-{
-#pragma unroll
-    for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d);
-    return v;
 }
 
 template <int SRC, bool HIST>
@@ -120,7 +88,6 @@ __global__ __launch_bounds__(256) void k_region_stats(StatsArgs a)
     __shared__ uint32_t s_hist[HIST ? 4u * R * HCAP : 1u];
     __shared__ unsigned long long s_sum[4][C][2];
     __shared__ uint32_t s_mm[4][C][2];
-    __shared__ uint32_t s_last;
     const StatsItem it = a.items[blockIdx.y];
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
     const uint32_t B = a.bins, S = gridDim.x, band = blockIdx.x, stride = stats_record_bytes(C, B);
@@ -128,10 +95,9 @@ __global__ __launch_bounds__(256) void k_region_stats(StatsArgs a)
         for (uint32_t i = tid; i < 4u * R * HCAP; i += 256u) s_hist[i] = 0u;
         __syncthreads();
     }
-    const bool empty = it.x1 <= it.x0 || it.y1 <= it.y0;
-    const uint32_t mbx0 = it.x0 >> 4, mby0 = it.y0 >> 4;
-    const uint32_t cols = empty ? 0u : ((it.x1 + 15u) >> 4) - mbx0, rows = empty ? 0u : ((it.y1 + 15u) >> 4) - mby0;
-    const uint32_t r0 = mby0 + rows * band / S, r1 = mby0 + rows * (band + 1u) / S, n = (r1 - r0) * cols;
+    const RegionBand bd = region_band(it.x0, it.y0, it.x1, it.y1, band, S);
+    const bool empty = bd.empty;
+    const uint32_t mbx0 = bd.mbx0, cols = bd.cols, r0 = bd.r0, n = (bd.r1 - r0) * cols;
     const uint32_t col4 = (lane & 3u) * 4u, row = lane >> 2;
     uint32_t *h = s_hist + (HIST ? (wave * R + lane % R) * HCAP : 0u);
 
@@ -148,15 +114,10 @@ __global__ __launch_bounds__(256) void k_region_stats(StatsArgs a)
             const uint32_t mby = r0 + i / cols, mbx = mbx0 + i % cols;
             const uint8_t *tile = it.src + ((size_t)mby * it.wmb + mbx) * TILE;
             const uint32_t X = mbx * 16u, Y = mby * 16u;
-            if (X >= it.x0 && X + 16u <= it.x1 && Y >= it.y0 && Y + 16u <= it.y1) {
+            if (REGION_MB_INNER(X, Y, it)) {
                 stats_mb<SRC, HIST, true>(tile, lane, 0xFFFFFFFFu, h, B, a.shift, s32, q32, mn, mx);
             } else {
-                uint32_t m = 0u;
-                if (Y + row >= it.y0 && Y + row < it.y1) {
-#pragma unroll
-                    for (int k = 0; k < 4; k++)
-                        if (X + col4 + k >= it.x0 && X + col4 + k < it.x1) m |= 0xFFu << (8 * k);
-                }
+                const uint32_t m = region_mask(X + col4, Y + row, it.x0, it.y0, it.x1, it.y1);
                 stats_mb<SRC, HIST, false>(tile, lane, m, h, B, a.shift, s32, q32, mn, mx);
             }
         }
@@ -195,21 +156,7 @@ __global__ __launch_bounds__(256) void k_region_stats(StatsArgs a)
     }
     if (S == 1u) return;
 
-    /* the hand-over: every storing wavefront drains, one lane releases at device scope and takes the ticket; the last acquires */
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0u) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const uint32_t t = __hip_atomic_fetch_add(&a.tickets[blockIdx.y], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        s_last = t == S - 1u ? 1u : 0u;
-        if (t == S - 1u) {
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-    }
-    __syncthreads();
-    if (!s_last) return;
+    if (!region_hand_over(a.tickets, S)) return;
     const uint8_t *pp = a.partials + (size_t)blockIdx.y * S * stride;
     uint32_t *dst32 = reinterpret_cast<uint32_t *>(it.dst);
     if (tid == 0u) { dst32[0] = count; dst32[1] = 0u; }
@@ -234,7 +181,7 @@ __global__ __launch_bounds__(256) void k_region_stats(StatsArgs a)
             dst32[2u + 6u * C + i] = t;
         }
     }
-    if (tid == 0u) __hip_atomic_store(&a.tickets[blockIdx.y], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    region_ticket_rezero(a.tickets);
 }
 
 } // namespace h264k

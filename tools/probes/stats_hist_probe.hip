@@ -6,6 +6,7 @@
 // build: hipcc -O3 -std=c++17 --offload-arch=gfx950 [-DSTATS_HIST_COPIES=4] [-DSTATS_CHROMA_MULT=0] -I../../h264bsd_amd/csrc
 //        stats_hist_probe.hip -o stats_hist_probe ; run: ./stats_hist_probe [frames = 256]
 #include "kernels.hip.h"
+#include "kernels/region_common.hip.h"
 #include "kernels/k_region_stats.hip.h"
 #include <cstdio>
 #include <cstdlib>
