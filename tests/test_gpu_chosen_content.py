@@ -572,9 +572,10 @@ def test_resampling_at_hard_edges(built, name, filt):
         v = rm.resample_hwc(tr._source(pp.i420(pic), geo, colour, ch), (ih, iw), filt, fma=colour == "reference")
         if filt == "bicubic_aa":
             assert v.min() < 0 and v.max() > (255 if colour == "reference" else 1), (s, fit, v.min(), v.max())
-        tol = 1e-4 / 255 / min(std) if colour == "reference" and filt == "bilinear" else tr._tol(colour, dt, std)
+        tol = tr._tol_bilinear_ref(dt, std) if colour == "reference" and filt == "bilinear" else tr._tol(colour, dt, std)
         g = tr._hwc(t[0], lay)
-        tr._check(g[top:top + ih, left:left + iw], tr._finish(v, colour, dt, ch, mean, std), dt, tol, what=(name, filt, s, fit, dt, colour))
+        tr._check(g[top:top + ih, left:left + iw], tr._finish(v, colour, dt, ch, mean, std), dt, tol, what=(name, filt, s, fit, dt, colour),
+                  half_up=colour == "reference")
         if fit == "letterbox":
             import torch
             border = np.ones(g.shape[:2], bool)

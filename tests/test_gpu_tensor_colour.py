@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import colour_model as cm
+import rounding_model as rd
 from conftest import stream_bytes
 from h264writer import BitWriter, StreamWriter, nal
 
@@ -67,7 +68,9 @@ def _torch_dtype(dt):
 
 def _check(got, want, dt, std=IMAGENET_STD, what=""):
     """got: a tensor slice, want: the model's float64 values of the same shape.  f16: within one f16 ulp of the model, plus the
-    fp32 evaluation's absolute error (1e-6 / |std|), which only matters near 0, where the f16 ulp is finer than fp32's at 1"""
+    fp32 evaluation's absolute error (1e-6 / |std|), which only matters near 0, where the f16 ulp is finer than fp32's at 1 — and
+    equal to the model rounded to nearest even wherever the model lies further than that error from a midpoint of two float16
+    values (tests/rounding_model.py); the decided share is printed and must reach rounding_model.F16_FLOOR"""
     g = got.cpu().double().numpy()
     assert g.shape == want.shape, what
     d = np.abs(g - want)
@@ -77,9 +80,8 @@ def _check(got, want, dt, std=IMAGENET_STD, what=""):
     elif dt == "f32":
         assert d.max() <= 1e-5 / min(abs(s) for s in std), (what, d.max())
     else:
-        a = np.maximum(np.abs(want), 2.0 ** -14)
-        ulp = np.exp2(np.floor(np.log2(a)) - 10)
-        assert (d <= ulp + 1e-6 / min(abs(s) for s in std)).all(), (what, (d / ulp).max())
+        eps = 1e-6 / min(abs(s) for s in std)
+        rd.check_share([rd.check_f16(g, want, eps, eps, what=what)], "f16", what)
 
 
 def _pull(built, decs, dt, lay, ch, crop, size, **colour):

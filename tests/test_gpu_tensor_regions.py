@@ -11,8 +11,8 @@ import region_model as gm
 import resize_model as rm
 from h264writer import StreamWriter
 from test_gpu_tensor_colour import Feed, _geometry
-from test_gpu_tensor_resize import (FILTERS, IMAGENET_MEAN, IMAGENET_STD, _check, _finish, _hwc, _source, _streams, _tol,
-                                    _torch_dtype)
+from test_gpu_tensor_resize import (FILTERS, IMAGENET_MEAN, IMAGENET_STD, _check, _check_shares, _finish, _hwc, _source, _streams,
+                                    _tol, _torch_dtype)
 
 pytestmark = pytest.mark.gpu
 
@@ -88,7 +88,7 @@ class Sources:
         return self.memo[key]
 
 
-def _check_region(g, v, box, dt, ch, size, filt, colour, fit, pad, rect, what):
+def _check_region(g, v, box, dt, ch, size, filt, colour, fit, pad, rect, what, shares=None):
     """g: [H, W, C'] float64 of one slice; v: the converted window; box: (x, y, w, h).  The rectangle is the model's, its inside the
     model's resampled crop, the border the normalised pad exactly; a box wholly outside is one value per channel"""
     mean, std = _norm(dt)
@@ -97,7 +97,9 @@ def _check_region(g, v, box, dt, ch, size, filt, colour, fit, pad, rect, what):
     assert rect == want_rect, (what, rect, want_rect)
     left, top, iw, ih = want_rect
     got_inner = g[top:top + ih, left:left + iw]
-    _check(got_inner, _finish(inner, colour, dt, ch, mean, std), dt, _tol(colour, dt, std), what=what)
+    # (a box wholly outside the picture is one pad value per channel: decided, but it says nothing about the resampling's rounding)
+    _check(got_inner, _finish(inner, colour, dt, ch, mean, std), dt, _tol(colour, dt, std), what=what, half_up=ref,
+           shares=None if gm.whole_outside(box, v.shape[1], v.shape[0]) else shares)
     border = np.ones(g.shape[:2], bool)
     border[top:top + ih, left:left + iw] = False
     if border.any():
@@ -141,13 +143,15 @@ def test_regions_inside_match_the_model(built, filt, colour):
     feeds, refs = _open(built, _streams())
     pics = _pop_all(feeds, refs)
     src = Sources(pics, [r.dec for r in refs])
+    shares = {}
     for k, (dt, lay, ch, size) in enumerate(CONFIGS):
         for fit in ("stretch", "letterbox"):
             t, got, boxes, cur, ids = _regions(built, [f.dec for f in feeds], INSIDE, dt, lay, ch, size, filt, colour, fit)
             assert got == [1] * len(INSIDE) and cur == [1] * 4 and ids == [p[1] for p in pics]
             for r, (i, x, y, w, h) in enumerate(INSIDE):
                 _check_region(_hwc(t[r], lay), src.get(i, colour, ch), (x, y, w, h), dt, ch, size, filt, colour, fit, PAD, boxes[r],
-                              what=(k, fit, r))
+                              what=("regions", filt, colour, k, fit, r, dt), shares=shares)
+    _check_shares(shares, ("regions", filt, colour))
     for f in feeds + refs:
         f.close()
 
@@ -243,7 +247,7 @@ def test_identity_scale_is_the_slice_of_the_full_size_pull(built, colour):
             if dt == "u8":
                 assert (g == want).all(), (dt, lay, ch, r)
             else:
-                _check(g, want, dt, _tol(colour, dt, std), what=(dt, lay, ch, r))
+                _check(g, want, dt, _tol(colour, dt, std), what=(dt, lay, ch, r), half_up=colour == "reference")
         tw.close()
     feed.close()
     twin.close()

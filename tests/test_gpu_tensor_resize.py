@@ -8,6 +8,7 @@ import pytest
 
 import colour_model as cm
 import resize_model as rm
+import rounding_model as rd
 from conftest import stream_bytes
 from h264writer import StreamWriter
 from test_gpu_tensor_colour import Feed, _geometry, _write_sps
@@ -63,36 +64,50 @@ def _source(frame, geo, colour, ch):
 
 
 def _finish(v, colour, dt, ch, mean, std):
-    """the values the tensor holds, [h, w, C'] float64: the output scale of include/h264bsd_mi355x.h, alpha appended"""
+    """the values the tensor holds, [h, w, C'] float64: the output scale of include/h264bsd_mi355x.h, alpha appended.  U8: the value
+    on the 0 .. 255 scale after the clamp and BEFORE the rounding, which is _check's (REF halves up, otherwise halves to even)"""
     C = v.shape[2]
     m, s = np.asarray(mean[:C], np.float64), np.asarray(std[:C], np.float64)
     if colour == "reference":
-        out = np.floor(np.clip(v, 0, 255) + 0.5) if dt == "u8" else (v / 255 - m) / s
+        out = np.clip(v, 0, 255) if dt == "u8" else (v / 255 - m) / s
     else:
-        out = np.rint(np.clip(np.round(255 * v, 9), 0, 255)) if dt == "u8" else (v - m) / s
+        out = np.clip(np.round(255 * v, 9), 0, 255) if dt == "u8" else (v - m) / s
     if ch in ("RGBA", "BGRA"):
         out = np.concatenate([out, np.full(out.shape[:2] + (1,), 255.0 if dt == "u8" else 1.0)], axis=2)
     return out
 
 
 def _tol(colour, dt, std):
-    """f32 (and the fp32 part of f16): REF 2e-3 on the 0..255 scale, colour 1e-5 on the [0, 1] scale, scaled by 1 / std"""
+    """f32 (and the fp32 part of f16): REF 2e-3 on the 0..255 scale, colour 1e-5 on the [0, 1] scale, scaled by 1 / std.  U8: the
+    same number on the 0..255 scale (std is 1), the eps of the rounding rule: what the float32 pull of the same configuration is
+    held to, so a uint8 value further than this from a half-integer cannot legitimately round the other way"""
     base = 2e-3 / 255 if colour == "reference" else 1e-5
-    return base / min(abs(x) for x in std) if dt != "u8" else 0.0
+    return base * (255 if dt == "u8" else 1) / min(abs(x) for x in std)
 
 
-def _check(got, want, dt, tol, what=""):
-    """got: [h, w, C'] float64 from the tensor, want: the model's.  U8 within 1; f32 within tol; f16 within one f16 ulp + tol"""
+def _tol_bilinear_ref(dt, std):
+    """the tighter bound of the reference colour's bilinear without antialiasing: 1e-4 on the 0..255 scale"""
+    return 1e-4 / 255 * (255 if dt == "u8" else 1) / min(abs(x) for x in std)
+
+
+def _check(got, want, dt, tol, what="", half_up=False, shares=None):
+    """got: [h, w, C'] float64 from the tensor, want: _finish's.  f32 within tol.  U8 and f16 under tests/rounding_model.py's rule
+    with eps = tol: equal to want rounded (U8: halves up when half_up, the reference colour, else to even; f16: to nearest even)
+    wherever want lies further than tol from a rounding boundary, elsewhere U8 within 1 and f16 within one f16 ulp + tol.  The decided
+    share is printed and appended to shares[dt] for the caller's rd.check_share"""
     assert got.shape == want.shape, what
-    d = np.abs(got - want)
-    if dt == "u8":
-        assert d.max() <= 1, (what, d.max())
-    elif dt == "f32":
+    if dt == "f32":
+        d = np.abs(got - want)
         assert d.max() <= tol, (what, d.max(), tol)
-    else:
-        a = np.maximum(np.abs(want), 2.0 ** -14)
-        ulp = np.exp2(np.floor(np.log2(a)) - 10)
-        assert (d <= ulp + tol).all(), (what, (d / ulp).max())
+        return
+    share = rd.check_u8(got, want, tol, half_up, what) if dt == "u8" else rd.check_f16(got, want, tol, tol, what)
+    if shares is not None:
+        shares.setdefault(dt, []).append(share)
+
+
+def _check_shares(shares, what):
+    for dt in ("u8", "f16"):
+        rd.check_share(shares.get(dt), dt, what)
 
 
 def _hwc(t, lay):
@@ -114,11 +129,13 @@ STRETCH = [("f32", "NCHW", "RGB", (224, 224)), ("u8", "NHWC", "RGBA", (257, 333)
 
 
 @pytest.mark.parametrize("colour", ["reference", "bt709"])
-@pytest.mark.parametrize("filt", ["bilinear_aa", "bicubic_aa"])
+@pytest.mark.parametrize("filt", ["bilinear", "bilinear_aa", "bicubic_aa"])
 def test_stretch_matches_the_model(built, filt, colour):
-    """four decoders of different frame sizes per call, every configuration of STRETCH, against torch's antialiased weights applied
-    in float64 to the oracle's (REF) or the colour model's values of the twin decoders' host pictures"""
+    """four decoders of different frame sizes per call, every configuration of STRETCH, against torch's weights (antialiased, or
+    bilinear without antialiasing: k_tensor_resize) applied in float64 to the oracle's (REF) or the colour model's values of the
+    twin decoders' host pictures; uint8 and float16 pinned in their rounding (_check)"""
     names = _streams()
+    shares = {}
     feeds, refs = [Feed(built, d) for d in names], [Feed(built, d) for d in names]
     for k, (dt, lay, ch, size) in enumerate(STRETCH):
         for f in feeds + refs:
@@ -129,9 +146,13 @@ def test_stretch_matches_the_model(built, filt, colour):
         assert boxes == [(0, 0, size[1], size[0])] * 4
         std = IMAGENET_STD if dt != "u8" else (1, 1, 1)
         for i, (p, r) in enumerate(zip(pics, refs)):
-            v = rm.resample_hwc(_source(p[0], _geometry(r.dec, True), colour, ch), size, filt)
+            v = rm.resample_hwc(_source(p[0], _geometry(r.dec, True), colour, ch), size, filt, fma=colour == "reference")
             want = _finish(v, colour, dt, ch, IMAGENET_MEAN, std)
-            _check(_hwc(t[i], lay), want, dt, _tol(colour, dt, std), what=(k, i, dt, lay, ch, size))
+            tol = _tol_bilinear_ref(dt, std) if colour == "reference" and filt == "bilinear" else _tol(colour, dt, std)
+            # 720 x 1280 is a rational scale of every stream (1/2, 3/2): values pile onto exact halves; the rule holds, the share does not count
+            _check(_hwc(t[i], lay), want, dt, tol, what=("stretch", filt, colour, k, i, dt, lay, ch, size), half_up=colour == "reference",
+                   shares=shares if size != (720, 1280) else None)
+    _check_shares(shares, ("stretch", filt, colour))
     for f in feeds + refs:
         f.close()
 
@@ -145,6 +166,7 @@ def test_letterbox_mixes_aspect_ratios(built, filt, colour):
     names = ["test_1920x1080", _synthetic(6, 4, seed=11), "test_640x360"]
     feeds, refs = [Feed(built, d) for d in names], [Feed(built, d) for d in names]
     pad = (0.25, 114 / 255, 1.0)
+    shares = {}
     for k, (dt, lay, ch, size) in enumerate([("f32", "NCHW", "RGB", (320, 320)), ("u8", "NHWC", "BGR", (256, 512)),
                                              ("f16", "NHWC", "RGBA", (320, 320)), ("f32", "NHWC", "Y", (256, 512))]):
         for f in feeds + refs:
@@ -160,8 +182,9 @@ def test_letterbox_mixes_aspect_ratios(built, filt, colour):
             assert boxes[i] == (left, top, iw, ih), (k, i)
             g = _hwc(t[i], lay)
             v = rm.resample_hwc(_source(p[0], geo, colour, ch), (ih, iw), filt, fma=colour == "reference")
-            tol = 1e-4 / 255 / min(std) if colour == "reference" and filt == "bilinear" else _tol(colour, dt, std)
-            _check(g[top:top + ih, left:left + iw], _finish(v, colour, dt, ch, mean, std), dt, tol, what=(k, i, filt))
+            tol = _tol_bilinear_ref(dt, std) if colour == "reference" and filt == "bilinear" else _tol(colour, dt, std)
+            _check(g[top:top + ih, left:left + iw], _finish(v, colour, dt, ch, mean, std), dt, tol, what=("letterbox", filt, colour, k, i, dt),
+                   half_up=colour == "reference", shares=shares)
             border = np.ones(g.shape[:2], bool)
             border[top:top + ih, left:left + iw] = False
             assert border.any()
@@ -171,6 +194,7 @@ def test_letterbox_mixes_aspect_ratios(built, filt, colour):
             if ch in ("RGBA", "BGRA"):
                 want = np.append(want, 255.0 if dt == "u8" else 1.0)
             assert (g[border] == want[None, :]).all(), (k, i, np.unique(g[border], axis=0)[:4], want)
+    _check_shares(shares, ("letterbox", filt, colour))
     for f in feeds + refs:
         f.close()
 
@@ -308,7 +332,7 @@ def test_256_1080p_instances_in_one_call(built):
         want = _finish(rm.resample_hwc(_source(frame, _geometry(ref.dec, True), "reference", "RGB"), (224, 224), "bilinear_aa"),
                        "reference", "f16", "RGB", IMAGENET_MEAN, IMAGENET_STD)
         first = t[0]
-        _check(_hwc(first, "NCHW"), want, "f16", _tol("reference", "f16", IMAGENET_STD), what=rnd)
+        _check(_hwc(first, "NCHW"), want, "f16", _tol("reference", "f16", IMAGENET_STD), what=("256 x 1080p", rnd), half_up=True)
         for i in range(1, N):
             assert torch.equal(t[i], first), (rnd, i)
     for d in decs:
