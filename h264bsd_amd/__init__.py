@@ -13,9 +13,11 @@ from .capi import (  # noqa: F401
     ShiftSpec, RegionShift, pull_shift, shift_record_bytes,
     CellsSpec, CellMaps, pull_cells,
     BoxesSpec, CellBoxes, pull_boxes,
+    BlendSpec, BLEND_FROZEN, blend_pictures, pull_kept,
 )
 
 # 0.2: pull_remap / affine_maps (h264bsdmiOutputTensorRemap); 0.3: pull_stats (h264bsdmiOutputRegionStats);
 # 0.4: keep_pictures / pull_change (h264bsdmiKeepCurrentPictures, h264bsdmiOutputRegionChange); 0.5: pull_cells (h264bsdmiOutputCellMaps)
 # 0.6: pull_boxes (h264bsdmiOutputCellBoxes); 0.7: pull_shift (h264bsdmiOutputRegionShift)
-__version__ = "0.7.0"
+# 0.8: blend_pictures / pull_kept (h264bsdmiBlendCurrentPictures, h264bsdmiOutputKeptPictures)
+__version__ = "0.8.0"

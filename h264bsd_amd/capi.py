@@ -28,7 +28,7 @@ EXPORTED_SYMBOLS = [
     "h264bsdCroppingParams", "h264bsdSampleAspectRatio", "h264bsdCheckValidParamSets", "h264bsdFlushBuffer",
     "h264bsdProfile", "h264bsdAlloc", "h264bsdFree", "h264bsdConvertToRGBA", "h264bsdConvertToBGRA",
     "h264bsdConvertToYCbCrA",
-    "h264bsdmiInitCapture", "h264bsdmiNextOutputInfo", "h264bsdmiNextOutputPictureDevice", "h264bsdmiNextOutputTensorBatch", "h264bsdmiNextOutputTensorBatchColour", "h264bsdmiNextOutputTensorBatchResize", "h264bsdmiOutputTensorRegions", "h264bsdmiOutputTensorRemap", "h264bsdmiSetMotionExport", "h264bsdmiOutputMotionRegions", "h264bsdmiOutputRegionStats", "h264bsdmiKeepCurrentPictures", "h264bsdmiOutputRegionChange", "h264bsdmiOutputRegionShift", "h264bsdmiOutputCellMaps", "h264bsdmiOutputCellBoxes", "h264bsdmiJobFinalize", "h264bsdmiDeviceCount", "h264bsdmiSetDevice", "h264bsdmiFlush", "h264bsdmiFlushAsync", "h264bsdmiDeviceErrors",
+    "h264bsdmiInitCapture", "h264bsdmiNextOutputInfo", "h264bsdmiNextOutputPictureDevice", "h264bsdmiNextOutputTensorBatch", "h264bsdmiNextOutputTensorBatchColour", "h264bsdmiNextOutputTensorBatchResize", "h264bsdmiOutputTensorRegions", "h264bsdmiOutputTensorRemap", "h264bsdmiSetMotionExport", "h264bsdmiOutputMotionRegions", "h264bsdmiOutputRegionStats", "h264bsdmiKeepCurrentPictures", "h264bsdmiBlendCurrentPictures", "h264bsdmiOutputKeptPictures", "h264bsdmiOutputRegionChange", "h264bsdmiOutputRegionShift", "h264bsdmiOutputCellMaps", "h264bsdmiOutputCellBoxes", "h264bsdmiJobFinalize", "h264bsdmiDeviceCount", "h264bsdmiSetDevice", "h264bsdmiFlush", "h264bsdmiFlushAsync", "h264bsdmiDeviceErrors",
     "h264bsdmiDecodePicture", "h264bsdmiDecodePictureBatch", "h264bsdmiNextOutputPictureBatch", "h264bsdmiPullAndDecodePictureBatch", "h264bsdmiSetParserThreads", "h264bsdmiSetInputReadOnly", "h264bsdmiSetCopyElision",
     "h264bsdmiReplayCreate", "h264bsdmiReplayCreateStaggered", "h264bsdmiReplayCreateDesync", "h264bsdmiReplayCreateSched", "h264bsdmiReplayReschedule", "h264bsdmiReplayDestroy", "h264bsdmiReplayRun", "h264bsdmiReplaySync",
     "h264bsdmiReplayFetch", "h264bsdmiReplayDbkRecords", "h264bsdmiReplayChecksums", "h264bsdmiReplayConvert", "h264bsdmiReplayFetchConverted",
@@ -93,6 +93,14 @@ class ChangeSpec(ctypes.Structure):
     """h264bsdmi_change_spec (include/h264bsd_mi355x.h)"""
     _fields_ = [("data", ctypes.c_void_p), ("source", ctypes.c_uint32), ("bins", ctypes.c_uint32), ("crop", ctypes.c_uint32),
                 ("threshold", ctypes.c_uint32 * 3), ("keep_after", ctypes.c_uint32)]
+
+
+class BlendSpec(ctypes.Structure):
+    """h264bsdmi_blend_spec (include/h264bsd_mi355x.h)"""
+    _fields_ = [("shift", ctypes.c_uint32), ("hold", ctypes.c_uint32), ("moving_shift", ctypes.c_uint32), ("moving", ctypes.c_void_p)]
+
+
+BLEND_FROZEN = 8                                                                 # H264BSDMI_BLEND_FROZEN
 
 
 class ShiftSpec(ctypes.Structure):
@@ -255,6 +263,10 @@ def _declare(L, harness):
     L.h264bsdmiOutputRegionStats.restype = ctypes.c_int
     L.h264bsdmiKeepCurrentPictures.argtypes = [u32, ctypes.POINTER(vp), vp, P32, P32]
     L.h264bsdmiKeepCurrentPictures.restype = ctypes.c_int
+    L.h264bsdmiBlendCurrentPictures.argtypes = [u32, ctypes.POINTER(vp), ctypes.POINTER(BlendSpec), vp, P32, P32, P32]
+    L.h264bsdmiBlendCurrentPictures.restype = ctypes.c_int
+    L.h264bsdmiOutputKeptPictures.argtypes = [u32, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), vp, P32, P32]
+    L.h264bsdmiOutputKeptPictures.restype = ctypes.c_int
     L.h264bsdmiOutputRegionChange.argtypes = [u32, ctypes.POINTER(vp), u32, ctypes.POINTER(Region), ctypes.POINTER(ChangeSpec), vp,
                                               P32, P32, P32, P32, P32]
     L.h264bsdmiOutputRegionChange.restype = ctypes.c_int
@@ -942,6 +954,64 @@ def keep_pictures(decoders, stream=None):
         if rc != 0:
             raise RuntimeError(f"h264bsdmiKeepCurrentPictures failed ({rc})")
     return list(kept)[:n], list(ids)[:n]
+
+
+def blend_pictures(decoders, shift=4, hold=255, moving_shift=None, count_moving=False, stream=None):
+    """h264bsdmiBlendCurrentPictures: the CURRENT picture of every decoder is blended into its kept picture, which becomes a running
+    average — a background model that pull_change, pull_shift, pull_cells(against="kept") and pull_boxes read as they read a copied
+    picture; one launch blends them all.  Per sample the state is S = 256 hi + lo (hi: the kept picture), T = 256 c + 128, and
+    S' = S + floor((T - S + 2^(shift-1)) / 2^shift); shift 0..7, 0 copies.  hold 0..255: a luma sample with |c - hi| > hold is moving,
+    and so is a chroma sample over one; moving samples take moving_shift instead: None (as shift), 0..7, or "frozen" (left as they
+    are).  A decoder without a kept picture starts its model with a copy.  count_moving: also the number of moving luma samples of
+    every decoder's coded frame.  stream as for pull_tensor.  Returns (kept, blended, pic_ids): per decoder 1 when it had a current
+    picture, 1 when that was blended into an existing kept picture (0: the model started), and the picId the kept picture now carries
+    — and with count_moving an int32 CUDA tensor [n] behind them."""
+    import torch
+    n = len(decoders)
+    if moving_shift is None:
+        moving_shift = shift
+    elif moving_shift == "frozen":
+        moving_shift = BLEND_FROZEN
+    for name, v, top in (("shift", shift, 7), ("hold", hold, 255), ("moving_shift", moving_shift, BLEND_FROZEN)):
+        if not isinstance(v, int) or isinstance(v, bool) or not 0 <= v <= top:
+            raise ValueError(f"blend_pictures: {name} is an int in 0..{top}" + (' or "frozen"' if name == "moving_shift" else "") + f", not {v}")
+    kept, blended, ids = ((ctypes.c_uint32 * max(n, 1))() for _ in range(3))
+    moving = None
+    if count_moving:
+        with torch.cuda.stream(stream or torch.cuda.current_stream()):
+            moving = torch.zeros((n,), dtype=torch.int32, device="cuda")
+    stream = _call_stream(stream)                       # (behind the fill: the legacy default stream is waited for)
+    if n:
+        spec = BlendSpec(shift, hold, moving_shift, moving.data_ptr() if count_moving else None)
+        rc = api_lib().h264bsdmiBlendCurrentPictures(n, (ctypes.c_void_p * n)(*[d._st for d in decoders]), ctypes.byref(spec), stream.cuda_stream,
+                                                     kept, blended, ids)
+        if rc != 0:
+            raise RuntimeError(f"h264bsdmiBlendCurrentPictures failed ({rc})")
+    res = (list(kept)[:n], list(blended)[:n], list(ids)[:n])
+    return res + (moving,) if count_moving else res
+
+
+def pull_kept(decoders, fraction=False, stream=None):
+    """h264bsdmiOutputKeptPictures: the kept picture of every decoder (keep_pictures, blend_pictures) as the planar I420 coded frame —
+    Y, Cb, Cr, what next_output_picture returns for a decoded picture — by one launch: to look at the background.  fraction=True:
+    also the low byte of every sample of the background model in the same order (128 where a plain keep came last).  stream as for
+    pull_tensor.  Returns per decoder a CUDA uint8 tensor [384 * macroblocks] (with fraction a pair of them), or None where it has no
+    kept picture."""
+    import torch
+    n = len(decoders)
+    stream = _call_stream(stream)
+    sizes = [384 * d.pic_width() * d.pic_height() for d in decoders]
+    with torch.cuda.stream(stream):
+        pics = [torch.empty((b,), dtype=torch.uint8, device="cuda") if b else None for b in sizes]
+        fracs = [torch.empty((b,), dtype=torch.uint8, device="cuda") if b and fraction else None for b in sizes]
+    got = (ctypes.c_uint32 * max(n, 1))()
+    if n:
+        ptrs = lambda ts: (ctypes.c_void_p * n)(*[t.data_ptr() if t is not None else None for t in ts])
+        rc = api_lib().h264bsdmiOutputKeptPictures(n, (ctypes.c_void_p * n)(*[d._st for d in decoders]), ptrs(pics), ptrs(fracs) if fraction else None,
+                                                   stream.cuda_stream, got, None)
+        if rc != 0:
+            raise RuntimeError(f"h264bsdmiOutputKeptPictures failed ({rc})")
+    return [None if not got[i] else (pics[i], fracs[i]) if fraction else pics[i] for i in range(n)]
 
 
 class RegionChange:

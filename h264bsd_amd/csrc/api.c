@@ -363,7 +363,7 @@ int h264bsdmiNextOutputTensorBatchResize(u32 n, storage_t *const *dec, const h26
 
 /* ---- The pulls of CURRENT pictures (pop_output, drop_current): h264bsdmiOutputTensorRegions, h264bsdmiOutputTensorRemap,
  * h264bsdmiOutputMotionRegions, h264bsdmiOutputRegionStats, h264bsdmiOutputRegionChange and h264bsdmiOutputRegionShift (which need the kept picture as well),
- * h264bsdmiOutputCellMaps and h264bsdmiOutputCellBoxes (which need it in CHANGE mode), and their small sibling h264bsdmiKeepCurrentPictures (the picture list only).  Each checks its own spec; everything else is one path:
+ * h264bsdmiOutputCellMaps and h264bsdmiOutputCellBoxes (which need it in CHANGE mode), and their small siblings h264bsdmiKeepCurrentPictures and h264bsdmiBlendCurrentPictures (the picture list only).  Each checks its own spec; everything else is one path:
  *   regions_refused   got, the count and the range of every region — before the instances are looked at
  *   pull_begin        dec and the instances (of this library, with the sink entry the call needs, distinct), then the lists
  *   pull_pic          an instance's current picture in the picture list, appended at its first use
@@ -593,6 +593,76 @@ int h264bsdmiKeepCurrentPictures(u32 n, storage_t *const *dec, void *stream, u32
         }
     }
     pull_free(&c);
+    return failed ? -2 : 0;
+}
+
+/* The current picture of each instance blended into its kept picture (the background model); where it has none, the model starts as a
+ * copy.  keep_begin and mark_kept are the keep call's; fresh: per picture, what the sink is told of the instance's kept picture */
+int h264bsdmiBlendCurrentPictures(u32 n, storage_t *const *dec, const h264bsdmi_blend_spec *spec, void *stream,
+                                  u32 *kept, u32 *blended, u32 *picId)
+{
+    CurrentPull c;
+    if (!n) return 0;
+    if (!spec || spec->shift > 7 || spec->hold > 255 || (spec->moving_shift > 7 && spec->moving_shift != H264BSDMI_BLEND_FROZEN)) return -1;
+    if (!kept || keep_begin(&c, n, dec)) return -1;
+    u32 *fresh = (u32 *)malloc(n * sizeof(u32));
+    int refused = !fresh;
+    for (u32 i = 0; i < n && !refused; i++) {
+        refused = !dec_of(dec[i])->hd->sink.blend_pictures;
+        if (c.pic_of[i] != NO_PIC) fresh[c.pic_of[i]] = !has_kept_picture(dec_of(dec[i]));
+    }
+    if (refused) { free(fresh); pull_free(&c); return -1; }
+    const int failed = c.m && c.pics[0].sink->blend_pictures(c.m, c.pics, fresh, spec, n, stream);
+    if (!failed) {
+        for (u32 i = 0; i < n; i++) {
+            kept[i] = c.pic_of[i] != NO_PIC;
+            if (blended) blended[i] = kept[i] && !fresh[c.pic_of[i]];
+        }
+        mark_kept(&c);
+        for (u32 i = 0; picId && i < n; i++) {
+            const ApiDec *a = dec_of(dec[i]);
+            picId[i] = has_kept_picture(a) ? a->kept_id : 0;
+        }
+    }
+    free(fresh);
+    pull_free(&c);
+    return failed ? -2 : 0;
+}
+
+/* The kept pictures of the instances that have one, as planar I420 coded frames, and their fractions */
+int h264bsdmiOutputKeptPictures(u32 n, storage_t *const *dec, void *const *picture, void *const *fraction, void *stream,
+                                u32 *got, u32 *keptPicId)
+{
+    if (!n) return 0;
+    if (!dec || !picture || !got) return -1;
+    for (u32 i = 0; i < n; i++) {
+        const ApiDec *a = dec_of(dec[i]);
+        if (!a || !a->hd->sink.kept_pictures_out) return -1;
+        for (u32 k = 0; k < i; k++)
+            if (dec[k] == dec[i]) return -1;
+        if (!has_kept_picture(a)) continue;
+        if (!picture[i] || ((uintptr_t)picture[i] & 15u) || (fraction && ((uintptr_t)fraction[i] & 15u))) return -1;
+    }
+    SinkTensorPic *pics = (SinkTensorPic *)calloc(n, sizeof(SinkTensorPic));
+    void **bufs = (void **)malloc(2 * (size_t)n * sizeof(void *));
+    if (!pics || !bufs) { free(pics); free(bufs); return -1; }
+    u32 m = 0;
+    for (u32 i = 0; i < n; i++) {
+        const ApiDec *a = dec_of(dec[i]);
+        if (!has_kept_picture(a)) continue;
+        pics[m].sink = &a->hd->sink;
+        pics[m].index = i;
+        bufs[m] = picture[i];
+        bufs[n + m] = fraction ? fraction[i] : NULL;
+        m++;
+    }
+    const int failed = m && pics[0].sink->kept_pictures_out(m, pics, bufs, bufs + n, stream);
+    for (u32 i = 0; !failed && i < n; i++) {
+        const ApiDec *a = dec_of(dec[i]);
+        got[i] = has_kept_picture(a) ? 1 : 0;
+        if (keptPicId) keptPicId[i] = has_kept_picture(a) ? a->kept_id : 0;
+    }
+    free(pics); free(bufs);
     return failed ? -2 : 0;
 }
 

@@ -39,6 +39,7 @@
 #include "kernels/region_common.hip.h"
 #include "kernels/k_region_stats.hip.h"
 #include "kernels/k_keep.hip.h"
+#include "kernels/k_blend.hip.h"
 #include "kernels/k_region_change.hip.h"
 #include "kernels/k_region_shift.hip.h"
 #include "kernels/k_cell_maps.hip.h"
@@ -97,6 +98,9 @@ struct StreamCtx {
     /* the kept picture (h264bsdmiKeepCurrentPictures): one frame of kept_wmb x kept_hmb macroblock tiles, allocated at the instance's
      * first keep; it outlives sink_configure with the same size and goes, behind Engine.kept_ev, with another size or the instance */
     DeviceMem<uint8_t> d_kept; uint32_t kept_wmb = 0, kept_hmb = 0;
+    /* the background model (h264bsdmiBlendCurrentPictures): the low byte of every sample of the kept picture, a second frame in the
+     * same tiles, allocated at the instance's first blend and freed with d_kept; not valid (it reads as 0x80) after a plain keep */
+    DeviceMem<uint8_t> d_kept_lo; bool kept_lo_valid = false;
 };
 
 /* k_dbk (boundary strengths) needs only the frame job, not pixels: it runs on a second HIP stream next to the
@@ -160,11 +164,12 @@ constexpr unsigned CONVERT_WGS = CONVERT_WGS_N;      /* workgroups per picture o
 constexpr uint32_t LANE_DBK_WAVES = LANE_DBK_WAVES_N;
 
 /* the item stride of the tensor pulls' staging ring: k_tensor_out / k_tensor_resize read TensorItems, k_tensor_aa AaItems, k_tensor_roi
- * RoiItems, k_motion_roi MotionItems, k_tensor_remap RemapItems, k_region_stats StatsItems, k_keep KeepItems, k_region_change ChangeItems, k_region_shift ShiftItems,
+ * RoiItems, k_motion_roi MotionItems, k_tensor_remap RemapItems, k_region_stats StatsItems, k_keep KeepItems, k_blend BlendItems, k_kept_out KeptOutItems, k_region_change ChangeItems, k_region_shift ShiftItems,
  * k_cell_maps CellItems (k_cell_boxes: the same, and its BoxItems in slots of their own behind them) */
 constexpr size_t TITEM_BYTES = std::max({ sizeof(h264k::TensorItem), sizeof(h264k::AaItem), sizeof(h264k::RoiItem), sizeof(h264k::MotionItem),
                                           sizeof(h264k::RemapItem), sizeof(h264k::StatsItem), sizeof(h264k::KeepItem), sizeof(h264k::ChangeItem),
-                                          sizeof(h264k::CellItem), sizeof(h264k::BoxItem), sizeof(h264k::ShiftItem) });
+                                          sizeof(h264k::CellItem), sizeof(h264k::BoxItem), sizeof(h264k::ShiftItem), sizeof(h264k::BlendItem),
+                                          sizeof(h264k::KeptOutItem) });
 struct TItemSlot { uint8_t bytes[TITEM_BYTES]; };
 struct Engine {
     std::mutex mu;
@@ -640,8 +645,8 @@ static void kept_drop(Engine *e, StreamCtx *s)
 {
     if (!s->d_kept) return;
     if (e->kept_recorded) (void)hipEventSynchronize(e->kept_ev);
-    s->d_kept.reset();
-    s->kept_wmb = s->kept_hmb = 0;
+    s->d_kept.reset(); s->d_kept_lo.reset();
+    s->kept_wmb = s->kept_hmb = 0; s->kept_lo_valid = false;
 }
 
 /* ---- motion export: the side information of a picture kept beside its frame buffer (kernels/k_motion.hip.h) ----
@@ -1538,6 +1543,86 @@ static int keep_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, hip
     hipLaunchKernelGGL(h264k::k_keep, dim3(std::max(chunks, 1u), n), dim3(256), 0, st, e->titems.dev<h264k::KeepItem>());
     HIP_TRY(hipGetLastError());
     if (pull_end_locked(e, n, pics, st, fence_ev)) return -1;
+    for (uint32_t i = 0; i < n; i++) static_cast<SinkUser *>(pics[i].sink->user)->s->kept_lo_valid = false;      /* a copy: the fraction is 0x80 */
+    return kept_order_end(e, st);
+}
+
+/* h264bsdmiBlendCurrentPictures: keep_out_locked's pictures, checks, ordering and fence, with ONE k_blend launch that blends every
+ * frame buffer into its instance's kept picture (d_kept: the high bytes, d_kept_lo: the low bytes, allocated here at the first blend).
+ * An instance that holds no kept picture, or of which api.c knows none (fresh), starts with a copy.  sp.moving: n_moving words,
+ * zeroed on st ahead of the launch; picture i counts into word pics[i].index. */
+static int blend_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, const uint32_t *fresh, const h264bsdmi_blend_spec &sp,
+                            uint32_t n_moving, hipStream_t st, hipEvent_t *fence_ev)
+{
+    if (n > 65535u) return -1;                                          /* grid.y */
+    if (sp.shift > 7u || sp.hold > 255u || (sp.moving_shift > 7u && sp.moving_shift != H264BSDMI_BLEND_FROZEN)) return -1;
+    if (!pull_pictures_ok(n, pics, true, false)) return -1;
+    for (uint32_t i = 0; i < n; i++) {
+        if (sp.moving && pics[i].index >= n_moving) return -1;
+        for (uint32_t k = 0; k < i; k++)
+            if (pics[k].sink == pics[i].sink) return -1;                /* one kept picture per instance */
+    }
+    if (pull_begin_locked(e, n, pics, n)) return -1;
+    if (kept_order_begin(e, st)) return -1;
+    h264k::BlendItem *items = e->titems.host<h264k::BlendItem>();
+    uint32_t largest = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        StreamCtx *s = static_cast<SinkUser *>(pics[i].sink->user)->s;
+        uint32_t flags = fresh[i] ? (uint32_t)h264k::BLEND_FRESH : 0u;
+        if (!s->d_kept) {
+            HIP_TRY(s->d_kept.alloc(s->frame_bytes));
+            s->kept_wmb = s->wmb; s->kept_hmb = s->hmb;
+            flags |= h264k::BLEND_FRESH;
+        }
+        if (!s->d_kept_lo) {
+            s->kept_lo_valid = false;
+            HIP_TRY(s->d_kept_lo.alloc(s->frame_bytes));
+        }
+        if (!s->kept_lo_valid) flags |= h264k::BLEND_LO_UNSET;
+        items[i] = h264k::BlendItem{ s->d_frames + (size_t)pics[i].slot * s->frame_bytes, s->d_kept.get(), s->d_kept_lo.get(), s->frame_bytes,
+                                     flags, pics[i].index };
+        largest = std::max(largest, s->frame_bytes);
+    }
+    /* 16 tiles per workgroup and step, about four steps per workgroup */
+    const uint32_t chunks = std::min((largest / 384u + 63u) / 64u, h264k::BLEND_MAX_CHUNKS);
+    if (sp.moving) HIP_TRY(hipMemsetAsync(sp.moving, 0, (size_t)n_moving * sizeof(uint32_t), st));
+    if (pull_wait_pictures(e, n, pics, st)) return -1;
+    const h264k::BlendArgs bargs{ e->titems.dev<h264k::BlendItem>(), static_cast<uint32_t *>(sp.moving), sp.shift, sp.hold,
+                                  sp.moving_shift == H264BSDMI_BLEND_FROZEN ? h264k::BLEND_FROZEN : sp.moving_shift };
+    hipLaunchKernelGGL(h264k::k_blend, dim3(std::max(chunks, 1u), n), dim3(256), 0, st, bargs);
+    HIP_TRY(hipGetLastError());
+    if (pull_end_locked(e, n, pics, st, fence_ev)) return -1;
+    for (uint32_t i = 0; i < n; i++) static_cast<SinkUser *>(pics[i].sink->user)->s->kept_lo_valid = true;
+    return kept_order_end(e, st);
+}
+
+/* h264bsdmiOutputKeptPictures: the kept pictures of the instances pics[i].sink (each holds one of its coded size, or the call is
+ * refused) as planar I420 into the caller's buffers, ONE k_kept_out launch inside the kept pictures' ordering.  No frame buffer is
+ * read: nothing is flushed and no picture is waited for; the fence only carries the wait of a call without a stream. */
+static int kept_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, void *const *picture, void *const *fraction, hipStream_t st,
+                           hipEvent_t *fence_ev)
+{
+    if (n > 65535u || !picture) return -1;                              /* grid.y */
+    for (uint32_t i = 0; i < n; i++) {
+        if (!picture[i] || (reinterpret_cast<uintptr_t>(picture[i]) & 15u) || (fraction && (reinterpret_cast<uintptr_t>(fraction[i]) & 15u))) return -1;
+        for (uint32_t k = 0; k < i; k++)
+            if (pics[k].sink == pics[i].sink) return -1;
+    }
+    if (!kept_pictures_ok(n, pics)) return -1;
+    HIP_TRY(e->titems.reserve(n, 256));
+    if (kept_order_begin(e, st)) return -1;
+    h264k::KeptOutItem *items = e->titems.host<h264k::KeptOutItem>();
+    uint32_t largest = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        const StreamCtx *s = pic_stream(pics[i]);
+        items[i] = h264k::KeptOutItem{ s->d_kept.get(), s->kept_lo_valid ? s->d_kept_lo.get() : nullptr, static_cast<uint8_t *>(picture[i]),
+                                       fraction ? static_cast<uint8_t *>(fraction[i]) : nullptr, s->kept_wmb, s->kept_hmb };
+        largest = std::max(largest, s->kept_wmb * s->kept_hmb * 24u);
+    }
+    const uint32_t chunks = std::min((largest + 1023u) / 1024u, h264k::BLEND_MAX_CHUNKS);          /* about four 16-byte pieces per lane */
+    hipLaunchKernelGGL(h264k::k_kept_out, dim3(std::max(chunks, 1u), n), dim3(256), 0, st, e->titems.dev<h264k::KeptOutItem>());
+    HIP_TRY(hipGetLastError());
+    if (pull_end_locked(e, n, pics, st, fence_ev)) return -1;
     return kept_order_end(e, st);
 }
 
@@ -1730,7 +1815,7 @@ static int remap_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, ui
     return pull_launch_locked(e, n, pics, st, fn, pull_grid(t.width, t.height, h264k::TRM_COLS, h264k::TRM_ROWS, n_maps), &rargs, fence_ev);
 }
 
-/* What JobSink.tensor_out, tensor_regions, motion_regions, tensor_remap, region_stats, keep_pictures, region_change, region_shift, cell_maps and cell_boxes share: one engine (one device) per call, its mutex, the
+/* What JobSink.tensor_out, tensor_regions, motion_regions, tensor_remap, region_stats, keep_pictures, blend_pictures, kept_pictures_out, region_change, region_shift, cell_maps and cell_boxes share: one engine (one device) per call, its mutex, the
  * refusal of a capturing stream, and, when the caller gave no stream, the wait for the fence and the device's error words.
  * body(e, st, &fence_ev): the call's own *_out_locked. */
 template <typename Body> static int sink_tensor_call(uint32_t n, const SinkTensorPic *pics, void *stream, Body body)
@@ -1807,6 +1892,20 @@ int sink_keep_pictures(uint32_t n, const SinkTensorPic *pics, void *stream)
         return keep_out_locked(e, n, pics, st, fence_ev);
     });
 }
+int sink_blend_pictures(uint32_t n, const SinkTensorPic *pics, const uint32_t *fresh, const h264bsdmi_blend_spec *spec, uint32_t n_moving,
+                        void *stream)
+{
+    if (n && (!spec || !fresh)) return -1;
+    return sink_tensor_call(n, pics, stream, [&](Engine *e, hipStream_t st, hipEvent_t *fence_ev) {
+        return blend_out_locked(e, n, pics, fresh, *spec, n_moving, st, fence_ev);
+    });
+}
+int sink_kept_pictures_out(uint32_t n, const SinkTensorPic *pics, void *const *picture, void *const *fraction, void *stream)
+{
+    return sink_tensor_call(n, pics, stream, [&](Engine *e, hipStream_t st, hipEvent_t *fence_ev) {
+        return kept_out_locked(e, n, pics, picture, fraction, st, fence_ev);
+    });
+}
 int sink_region_change(uint32_t n, const SinkTensorPic *pics, uint32_t n_regions, const SinkRegion *regions,
                        const h264bsdmi_change_spec *spec, void *stream)
 {
@@ -1881,6 +1980,8 @@ int eng_attach(JobSink *sink)
     sink->region_shift = sink_region_shift;
     sink->cell_maps = sink_cell_maps;
     sink->cell_boxes = sink_cell_boxes;
+    sink->blend_pictures = sink_blend_pictures;
+    sink->kept_pictures_out = sink_kept_pictures_out;
     return 0;
 }
 

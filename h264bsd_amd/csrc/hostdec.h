@@ -225,6 +225,7 @@ struct h264bsdmi_change_spec;
 struct h264bsdmi_shift_spec;
 struct h264bsdmi_cells_spec;
 struct h264bsdmi_boxes_spec;
+struct h264bsdmi_blend_spec;
 struct JobSink;
 /* one picture of a batched tensor pull (JobSink.tensor_out): the frame buffer `slot` of the instance behind `sink`, its window
  * (x0, y0, w, h), and the picture's index in the output tensor */
@@ -324,6 +325,17 @@ typedef struct JobSink {
      * slice `index` of boxes->data each — h264bsdmiOutputCellBoxes.  Everything said of cell_maps holds.  0 = ok; <0 = error, nothing enqueued */
     int (*cell_boxes)(uint32_t n, const SinkTensorPic *pics, uint32_t n_regions, const SinkRegion *regions,
                       const struct h264bsdmi_cells_spec *cells, const struct h264bsdmi_boxes_spec *boxes, void *stream);
+    /* optional: keep_pictures' pictures blended into their instances' kept pictures, a running average with a hold mask (spec: shift,
+     * hold, moving_shift, checked by the sink as well), with one launch — h264bsdmiBlendCurrentPictures.  fresh[i] != 0: the caller
+     * knows of no kept picture of pics[i]'s instance, the model starts as a copy; the sink starts it so too where it holds none.
+     * spec->moving: NULL, or n_moving words on the device, zeroed on `stream` ahead of the launch, word pics[i].index the moving luma
+     * samples of picture i.  0 = ok; <0 = error, nothing enqueued */
+    int (*blend_pictures)(uint32_t n, const SinkTensorPic *pics, const uint32_t *fresh, const struct h264bsdmi_blend_spec *spec,
+                          uint32_t n_moving, void *stream);
+    /* optional: the kept pictures of the n instances pics[i].sink (distinct; nothing else of pics[i] is used), each of which holds one
+     * of its coded size, as planar I420 coded frames into picture[i], and their fractions (0x80 where a plain keep came last) into
+     * fraction[i] where fraction and fraction[i] are not NULL, with one launch — h264bsdmiOutputKeptPictures.  0 = ok; <0 = error */
+    int (*kept_pictures_out)(uint32_t n, const SinkTensorPic *pics, void *const *picture, void *const *fraction, void *stream);
 } JobSink;
 
 /* ---------------------------------------------------------------- decoder instance */

@@ -331,6 +331,51 @@ int h264bsdmiOutputRegionStats(u32 n, storage_t *const *pStorage, u32 nRegions, 
  * capturing stream.  -2: the engine failed, nothing is marked kept and nothing is written.  n == 0 returns 0. */
 int h264bsdmiKeepCurrentPictures(u32 n, storage_t *const *pStorage, void *stream, u32 *kept, u32 *picId);
 
+/* Background model: the kept picture as a RUNNING AVERAGE of the current pictures, with a hold mask — a background that slow and
+ * stopped objects do not vanish from after one picture, that movers leave no ghost in, and in which sensor noise is averaged away.  It
+ * lives where the kept picture lives, so every consumer (h264bsdmiOutputRegionChange, h264bsdmiOutputRegionShift,
+ * h264bsdmiOutputCellMaps and h264bsdmiOutputCellBoxes in CHANGE mode) reads it as it reads a copied picture.
+ * The state of a sample is 16-bit fixed point, S = hi * 256 + lo: hi is the kept picture, lo a second frame that the library allocates
+ * at an instance's first blend.  With the current sample c, T = c * 256 + 128 and a shift k,
+ *     S' = S + floor((T - S + 2^(k-1)) / 2^k)        k = 1 .. 7;        S' = T        k = 0
+ * S' lies between S and T and S stays in [128, 65408]; for constant input hi reaches c and stays there for every k <= 7.
+ * A luma sample is MOVING when |c - hi| > hold (strict: hold = 255 means nothing is moving; the test of h264bsdmiOutputRegionChange's
+ * `above` with source Y and threshold = hold), a chroma sample when one of the four luma samples it covers is; the test uses the
+ * values from before the update.  Still samples take `shift`, moving samples `moving_shift`: 0 copies the current value, 1 .. 7 blends
+ * at that rate, H264BSDMI_BLEND_FROZEN leaves S as it is.  Everything is an integer and exact.
+ * One launch for the call, the whole coded frame of each of n distinct instances.  kept[i] = 1 when instance i had a current picture,
+ * as for h264bsdmiKeepCurrentPictures; blended[i] (may be NULL) = 1 when it was blended into an existing kept picture of the coded
+ * size, 0 when the model started with a copy (S = T: what a plain keep leaves); picId (may be NULL): the picId the kept picture now
+ * carries, the current picture's.  A plain keep (h264bsdmiKeepCurrentPictures, or any keep_after) stays what it is and resets the
+ * fraction: lo reads as 0x80 everywhere until the next blend.
+ * spec->moving: NULL, or a DEVICE pointer to u32[n]: word i receives the number of moving luma samples of the whole coded frame of
+ * instance i (0 without a current picture, or where the model started); the words are zeroed on the stream ahead of the launch when
+ * any instance of the call has a current picture, else untouched.
+ * The stream rule, the fence and the ordering of launches that touch kept pictures are those of h264bsdmiKeepCurrentPictures.
+ * -1, before anything is enqueued: what h264bsdmiKeepCurrentPictures refuses; spec NULL; shift > 7; hold > 255; a moving_shift that is
+ * neither 0 .. 7 nor H264BSDMI_BLEND_FROZEN.  -2: the engine failed, nothing is marked kept and nothing is written.  n == 0 returns 0. */
+#define H264BSDMI_BLEND_FROZEN 8u
+typedef struct h264bsdmi_blend_spec {
+    u32   shift;         /* 0 .. 7: still samples */
+    u32   hold;          /* 0 .. 255 */
+    u32   moving_shift;  /* 0 .. 7 or H264BSDMI_BLEND_FROZEN: moving samples */
+    void *moving;        /* NULL, or DEVICE pointer to u32[n] */
+} h264bsdmi_blend_spec;
+int h264bsdmiBlendCurrentPictures(u32 n, storage_t *const *pStorage, const h264bsdmi_blend_spec *spec, void *stream,
+                                  u32 *kept, u32 *blended, u32 *picId);
+
+/* The kept pictures handed out, for viewing the background: picture[i], a DEVICE buffer of 384 * (macroblocks of the coded frame)
+ * bytes, 16-byte aligned, receives the kept picture of instance i as the planar I420 coded frame (Y, Cb, Cr: what
+ * h264bsdNextOutputPicture returns for a decoded one).  fraction (may be NULL, and so may fraction[i]): the same for lo, 0x80 where a
+ * plain keep came last.  One launch for the call, inside the ordering of launches that touch kept pictures; the stream rule is that
+ * of h264bsdmiKeepCurrentPictures.  got[i] = 1, or 0 where the instance has no kept picture of its coded size: its buffers are then
+ * untouched.  keptPicId (may be NULL): the picId of the kept picture, or 0.
+ * -1, before anything is enqueued: pStorage, picture or got NULL with n > 0; a picture[i] that is NULL or a buffer that is not 16-byte
+ * aligned, for an instance that has a kept picture; an instance in capture mode; repeated instances; a capturing stream.  -2: the
+ * engine failed, nothing is written by the host.  n == 0 returns 0. */
+int h264bsdmiOutputKeptPictures(u32 n, storage_t *const *pStorage, void *const *picture, void *const *fraction, void *stream,
+                                u32 *got, u32 *keptPicId);
+
 /* Change statistics: integer statistics of (current picture - kept picture) over boxes, computed where the two pictures lie, with one
  * launch — did anything change since the last picture or since the background I stored, is the feed frozen, is this a cut or only a
  * brightness shift, what is the PSNR against the picture I kept — without pulling a pixel.  A sibling of h264bsdmiOutputRegionStats:
