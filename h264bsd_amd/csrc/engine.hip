@@ -7,7 +7,8 @@
  * through the DPB; pictures of different streams never do).  A tick of N pictures is SIX launches (launch_tick):
  *     k_copy            grid (32, N)          x 256  whole-sample copy macroblocks, one run of <= 8 tiles per wavefront; on a HIP stream of its own
  *                                                    next to the inter kernels (single-lane engine and replay sets: SideLane), joined before k_frame_intra
- *     k_recon_inter<0>  grid (n_uni/4, N)     x 256  inter macroblocks with one motion vector, one wavefront each
+ *     k_recon_inter_lb  grid (n_uni/32, N)    x 64   inter macroblocks with one motion vector: a chunk of 32 list entries per wavefront, binned by
+ *                                                    interpolation class, four macroblocks at a time, a 4x4 block per lane (-DINTER_LANE_BLOCKS=0: k_recon_inter<0>)
  *     k_recon_inter<1>  grid (n_quad/4, N)    x 256  inter macroblocks with one motion vector per 8x8 quadrant
  *     k_recon_inter<2>  grid (n_rest/4, N)    x 256  finer partitions
  *     k_dbk             grid (n_dbk/512, N)   x 512  boundary strengths from metadata, one macroblock per lane; on a third HIP stream, next to the four above, joined before k_frame_dbk
@@ -471,8 +472,15 @@ static void launch_kdbk(hipStream_t st, const FrameDesc *d_desc, const TickShape
 /* k_recon_inter for one partition class (0: one motion vector, 1: one per 8x8 quadrant, 2: finer), n_max entries in the longest list of the tick */
 template <int PATH> static void launch_inter(hipStream_t st, const FrameDesc *d_desc, uint32_t n_max, uint32_t n_frames)
 {
+#if INTER_LANE_BLOCKS
+    if constexpr (PATH == 0) {                       /* one wavefront per chunk of INTER_LB_CHUNK entries, a 4x4 block per lane */
+        if (n_max) hipLaunchKernelGGL(h264k::k_recon_inter_lb, dim3((n_max + INTER_LB_CHUNK - 1) / INTER_LB_CHUNK, n_frames), dim3(64), 0, st, d_desc);
+    } else
+#endif
+    {
     constexpr uint32_t per_wg = INTER_WG_WAVES * h264k::inter_per_wave<PATH>();
     if (n_max) hipLaunchKernelGGL(h264k::k_recon_inter<PATH>, dim3((n_max + per_wg - 1) / per_wg, n_frames), dim3(64 * INTER_WG_WAVES), 0, st, d_desc);
+    }
 }
 /* the dynamic LDS every device has allowed the per-picture kernels so far: [0 k_frame_dbk, 1 k_frame_intra][plain, banded variant][device] */
 std::mutex g_tail_lds_mu;

@@ -9,6 +9,8 @@
  *                   block of count x 384 bytes, 16 bytes per lane per access, every load before the first store.
  *                       reference: the P_Skip / integer-mv path of src/h264bsd_inter_prediction.c:361-482,
  *                                  h264bsdFillBlock src/h264bsd_reconstruct.c:2244, src/h264bsd_image.c:81
+ *   k_recon_inter_lb : inter macroblocks with ONE motion vector (most of the list): a chunk of 32 list entries per wavefront, sorted by
+ *                   interpolation class, four macroblocks at a time, a 4x4 luma block per lane (kernels/inter_lane_block.hip.h).
  *   k_recon_inter : every other inter macroblock, one wavefront each (= one workgroup: the wavefronts share nothing), list-driven.
  *                   Reference windows staged in LDS tile row by tile row (aligned 16-byte loads), 6-tap luma on packed
  *                   sample pairs / bilinear chroma, dequant + 4x4 inverse transform with DPP quad transposes, residual
@@ -42,6 +44,7 @@
 #include "kernels/common.hip.h"
 #include "kernels/k_dbk.hip.h"
 #include "kernels/k_copy.hip.h"
+#include "kernels/inter_lane_block.hip.h"
 #include "kernels/k_recon_inter.hip.h"
 #include "kernels/convert.hip.h"
 #include "kernels/tail_common.hip.h"

@@ -1,4 +1,6 @@
-/* kernels/k_recon_inter.hip.h — k_recon_inter: every other inter macroblock (interpolation, residual, write-back).  Part of kernels.hip.h (which see); not a stand-alone header. */
+/* kernels/k_recon_inter.hip.h — k_recon_inter<PATH> and k_recon_inter_lb: every inter macroblock that is no plain copy (interpolation, residual,
+ * write-back).  k_recon_inter_lb (at the end of the file) takes the one-vector part of the list, k_recon_inter<1>, <2> the partitioned parts;
+ * k_recon_inter<0> is the previous one-vector kernel, built with -DINTER_LANE_BLOCKS=0.  Part of kernels.hip.h (which see); not a stand-alone header. */
 #pragma once
 namespace h264k {
 /* ------------------------------------------------------------------ inter prediction */
@@ -241,7 +243,9 @@ struct __attribute__((packed, aligned(4))) U2a4 { uint32_t x, y; };
 /* Reference windows are staged tile row by tile row: a window row is the 16-byte rows of the 2-3 tiles it crosses,
  * loaded whole (aligned 16-byte / 8-byte requests) and laid side by side in LDS, so byte 0 of a staged row is the first
  * column of the window's first tile. */
-constexpr int IW_STRIDE = 52;                        /* luma window: 21 rows x 3 tiles x 16 bytes; 13-dword stride: no bank conflicts for row-per-lane reads */
+constexpr int IW_STRIDE = 52;                        /* luma window: 21 rows x 3 tiles x 16 bytes; 13-dword stride.  Not free of bank conflicts, as this line used to say:
+                                                        measured, SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE was 48.8 % for k_recon_inter<0> (profiles/r06_sq_counters.txt);
+                                                        for k_recon_inter_lb see LB_SLOT_LDS below and docs/EXPERIMENTS.md */
 constexpr int IC_STRIDE = 20;                        /* chroma windows: 9 rows x 2 tiles x 8 bytes, two planes */
 constexpr int QW_STRIDE = 36;                        /* quadrant luma windows: 13 rows x 2 tiles x 16 bytes, 9-dword stride */
 constexpr int QC_STRIDE = 20;                        /* quadrant chroma windows: 5 rows x 2 tiles x 8 bytes, two planes */
@@ -595,6 +599,327 @@ __global__ __launch_bounds__(64 * INTER_WG_WAVES, PATH == 0 ? INTER_OCC : INTER_
 #endif
     wave_sync();          /* the staged windows are overwritten by the next entry's */
   }
+}
+
+/* ------------------------------------------------------------------ the one-vector list, a 4x4 block per lane
+ * k_recon_inter_lb replaces k_recon_inter<0> (INTER_LANE_BLOCKS = 1, the default; 0 keeps the kernel above for A/B runs).
+ * A workgroup is ONE wavefront and takes INTER_LB_CHUNK consecutive entries of the picture's one-vector list.
+ *   Binning.  Lane i reads entry i of the chunk and computes its bin, {not coded, coded} x {whole, hor, ver, diag, centre}; a counting
+ *     sort (the histogram is ten ballots, the ranks are prefix counts of them) lays the entries out in LDS ordered by bin.
+ *   Groups.  The wavefront then works through the sorted chunk four entries at a time: lane = (slot 0..3, 4x4 luma block 0..15).
+ *     Everything an entry decides — macroblock, vector, reference, window origin, quantisers, coded bits — is a per-lane value, so the
+ *     scalar work and the address set-up of the old kernel are paid once for four macroblocks.  Every interpolation class runs
+ *     under the mask of the lanes that are in it (a wavefront-uniform skip when nobody is): a group of one bin pays for one class, a
+ *     group that mixes bins (the remainders of a chunk) for each class it holds.  A slot past the end of the chunk idles: it loads
+ *     from a fixed valid address, stages nothing and stores nothing.
+ *   Staging.  Per slot one 21 x 48 luma and two 9 x 16 chroma windows as before; the 16 lanes of a slot fetch its 63 + 36 aligned
+ *     pieces (4 + 3 loads per lane), and with the coefficient blocks (32 bytes of luma block b, 32 bytes of chroma block b & 7, the 8
+ *     DC bytes of its plane) all loads of all four slots are issued before the first is used.
+ *   Arithmetic.  kernels/inter_lane_block.hip.h: the lane filters its block from a 9 x 12-byte window (9 window rows for 4 output
+ *     rows where four lanes used to fetch 6 each) and transforms its residual block without leaving its registers; lanes b and b + 8
+ *     both transform chroma block b & 7 (in the high halves of the packed transform: it costs nothing) and keep two rows each.
+ *   Stores.  A 4x4 dword transpose inside each quad of lanes (the four blocks of a block row) gives every lane one whole 16-byte row
+ *     of the tile: one global_store_dwordx4 covers the four 256-byte luma tiles; neighbouring lanes swap a dword and store 8-byte
+ *     chroma rows, 128 contiguous bytes per slot. */
+#ifndef INTER_LANE_BLOCKS
+#define INTER_LANE_BLOCKS 1
+#endif
+#ifndef INTER_LB_CHUNK
+#define INTER_LB_CHUNK 32    /* list entries per workgroup (= wavefront), a multiple of 4 up to 64 */
+#endif
+#ifndef INTER_LB_OCC
+#define INTER_LB_OCC 4       /* wavefronts per SIMD the register budget is sized for (128 VGPRs): 16 macroblocks in flight per SIMD */
+#endif
+static_assert(INTER_LB_CHUNK % 4 == 0 && INTER_LB_CHUNK >= 4 && INTER_LB_CHUNK <= 64, "INTER_LB_CHUNK");
+/* A slot's windows: 21 luma rows at IW_STRIDE, then two planes of 9 chroma rows at IC_STRIDE (1452 bytes), padded to 368 dwords =
+ * 16 (mod 32): the sixteen lanes of a slot read dword 13 * (4 * by + r) + bx + const — sixteen different banks of 32, {0..3, 8..11,
+ * 20..23, 28..31} + const — and the other slot of the same half-wavefront the other sixteen when the two windows start at the same
+ * dword of their tiles; otherwise they are up to 2-way.  Measured over the whole kernel (staging writes included):
+ * SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE = 32.1 % (profiles/inter_lane_blocks_sq_counters.txt). */
+constexpr int LB_SLOT_LDS = 1472;
+constexpr int LB_LDS = INTER_LB_CHUNK * 16 + 4 * LB_SLOT_LDS;
+__global__ __launch_bounds__(64, INTER_LB_OCC) void k_recon_inter_lb(const FrameDesc *__restrict__ frames)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t lds[LB_LDS];
+    const FrameDesc &fd = FD_REF(frames, blockIdx.y);
+    /* chunk of this workgroup: the XCD mapping of k_recon_inter (which see), in chunks instead of entries */
+#if INTER_XCD == 1
+    const uint32_t cls8 = blockIdx.x & 7u, per8 = gridDim.x >> 3, rem8 = gridDim.x & 7u;
+    const uint32_t bx_ = cls8 * per8 + (cls8 < rem8 ? cls8 : rem8) + (blockIdx.x >> 3);
+#elif INTER_XCD > 1
+    const uint32_t C_ = INTER_XCD, full_ = (gridDim.x / (8u * C_)) * (8u * C_);
+    const uint32_t b_ = blockIdx.x, o_ = b_ % (8u * C_);
+    const uint32_t bx_ = b_ >= full_ ? b_ : (b_ - o_) + (o_ & 7u) * C_ + (o_ >> 3);
+#else
+    const uint32_t bx_ = blockIdx.x;
+#endif
+    const uint32_t n_uni = fd.n_gen_uni, first = bx_ * INTER_LB_CHUNK;
+    if (first >= n_uni) return;
+    const uint32_t n_here = min(n_uni - first, (uint32_t)INTER_LB_CHUNK);            /* wave-uniform */
+    const int lane = threadIdx.x & 63;
+    const int wmb = fd.wmb, W = wmb * 16, H = fd.hmb * 16, CW = W >> 1, CH = H >> 1;
+    const uint32_t frame_bytes = (uint32_t)wmb * fd.hmb * (uint32_t)TILE;            /* a stream's slots are contiguous (slot_ptr): at most 17 x 14 MB */
+    const H264K_GLOBAL uint8_t *ref0 = (const H264K_GLOBAL uint8_t *)fd.slot[0];
+    const H264K_GLOBAL uint8_t *cf = (const H264K_GLOBAL uint8_t *)fd.coefs;
+    H264K_GLOBAL uint8_t *cur = (H264K_GLOBAL uint8_t *)fd.cur;
+
+    /* ---- bin the chunk: lane i < n_here holds entry first + i ---- */
+    {
+        const bool have = (uint32_t)lane < n_here;
+        uint4 e = make_uint4(0u, 0u, 0u, 0u);
+        if (have) e = ld16g((const H264K_GLOBAL uint8_t *)fd.gen + 16u * (first + (uint32_t)lane));
+        const int fx = (int)(e.y & 3u), fy = (int)((e.y >> 16) & 3u);
+        const int cls = (fx | fy) == 0 ? 0 : fy == 0 ? 1 : fx == 0 ? 2 : (fx != 2 && fy != 2) ? 3 : 4;
+        /* class first: a group that mixes classes runs a class pass more (110 .. 700 vector instructions), one that mixes coded and
+         * not coded only gives its uncoded slots the residual pass (150) — coded first cost 8 class changes per chunk, this order 4 */
+        const int bin = have ? 2 * cls + ((e.w & 0x03FFFFFFu) ? 1 : 0) : 10;
+        uint32_t rank = 0, seen = 0;
+#pragma unroll
+        for (int k = 0; k < 10; k++) {
+            const unsigned long long m = __ballot(bin == k);
+            const uint32_t before = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+            if (bin == k) rank = seen + before;
+            seen += (uint32_t)__popcll(m);
+        }
+        if (have) *reinterpret_cast<uint4 *>(lds + 16u * rank) = e;                   /* rank < n_here */
+        wave_sync();
+    }
+
+    /* The body below runs in four phases — loads and staging | luma | chroma | residual and store — and each of them derives what it
+     * needs from the lane number and the four dwords of the list entry AGAIN (LB_FRESH makes them values of unknown origin): left to
+     * itself the compiler computes every address of the body at its top and carries them, with the loop-invariant lane geometry, through
+     * the centre-class filter, where the registers are needed (23 spilled VGPRs at 128). */
+#define LB_FRESH() asm volatile("" : "+v"(ln), "+v"(ge.x), "+v"(ge.y), "+v"(ge.z), "+v"(ge.w))
+#define LB_LANE() const int s = ln >> 4, b = ln & 15, bx = b & 3, by = b >> 2; \
+                  uint8_t *lw = lds + INTER_LB_CHUNK * 16 + s * LB_SLOT_LDS, *lc = lw + 21 * IW_STRIDE; (void)bx; (void)by; (void)lc
+#pragma unroll 1
+    for (uint32_t g = 0; g < n_here; g += 4) {
+        int ln = lane;
+        const bool on = g + (uint32_t)(lane >> 4) < n_here;                           /* g + slot <= INTER_LB_CHUNK - 1 */
+        uint4 ge = *reinterpret_cast<const uint4 *>(lds + 16u * (g + (uint32_t)(lane >> 4)));
+        if (!on) ge = make_uint4(0u, 0u, 0u, 0u);
+        uint32_t yl[8] = { 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u }, cl[8] = { 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u }, dcl[2] = { 0u, 0u };
+        const bool any_coded = __ballot((ge.w & 0x03FFFFFFu) != 0u) != 0ull;          /* wave-uniform */
+      {                                              /* ======== loads and staging ======== */
+        LB_FRESH();
+        LB_LANE();
+        const uint32_t mb = ge.x & 0xFFFFu, refoff = (ge.x >> 24) * frame_bytes;
+        const int mvx = (int16_t)(ge.y & 0xFFFFu), mvy = (int32_t)ge.y >> 16;
+        const uint32_t coded = ge.w;
+        const int mby = wmb == 1 ? (int)mb : (int)__umulhi(mb, fd.wmb_magic), mbx = (int)mb - mby * wmb;
+        const int xi = mbx * 16 + (mvx >> 2) - 2, yi = mby * 16 + (mvy >> 2) - 2, xs = (xi >> 4) << 4;
+        const int cxi = mbx * 8 + (mvx >> 3), cyi = mby * 8 + (mvy >> 3), cxs = (cxi >> 3) << 3;
+        const bool lfast = on && xi >= 0 && xi + 21 <= W && yi >= 0 && yi + 21 <= H;
+        const bool cfast = on && cxi >= 0 && cxi + 9 <= CW && cyi >= 0 && cyi + 9 <= CH;
+
+        /* ---- every global load of the group, back to back (a lane without a piece reads the first bytes of slot 0 and drops them).
+         * Windows that leave the picture (h264bsdFillBlock: every sample clamped to the picture) need no gather: pictures are whole tiles,
+         * so a piece — one tile row — lies wholly inside the picture, wholly left of it (sixteen times the first sample of the clamped
+         * row) or wholly right of it (its last sample); the piece is loaded from the clamped tile and row and spread after it arrived. ---- */
+        uint4 vl[4];
+        uint2 vc[3];
+        bool l_on[4], c_on[3];
+        const bool any_edge = __ballot(on && !(lfast && cfast)) != 0ull;              /* wave-uniform */
+#pragma unroll
+        for (int i = 0; i < 4; i++) {                /* luma piece p = 3 * row + tile of the slot's window, p = b + 16 * i < 63 */
+            const int p = b + 16 * i, lr = (p * 43) >> 7, lk = p - 3 * lr;
+            const int lx = clip3(0, W - 16, xs + 16 * lk), yy = clip3(0, H - 1, yi + lr);
+            /* (the window's 21 columns reach into the third tile only when they start in the last four columns of the first) */
+            l_on[i] = on && p < 63 && (lk < 2 || xi - xs >= 12);
+            const uint32_t off = refoff + (uint32_t)((yy >> 4) * wmb + (lx >> 4)) * (uint32_t)TILE + (uint32_t)((yy & 15) << 4);
+            vl[i] = ld16g(ref0 + (l_on[i] ? off : 0u));
+        }
+#pragma unroll
+        for (int i = 0; i < 3; i++) {                /* chroma piece p = 18 * plane + 2 * row + tile, p = b + 16 * i < 36 */
+            const int p = b + 16 * i, cp = p >= 18, rem = cp ? p - 18 : p, cr = rem >> 1, ck = rem & 1;
+            const int cx = clip3(0, CW - 8, cxs + 8 * ck), yy = clip3(0, CH - 1, cyi + cr);
+            c_on[i] = on && p < 36;
+            const uint32_t off = refoff + (uint32_t)((yy >> 3) * wmb + (cx >> 3)) * (uint32_t)TILE + (uint32_t)(T_CB + (cp << 6) + ((yy & 7) << 3));
+            vc[i] = ld8g(ref0 + (c_on[i] ? off : 0u));
+        }
+        /* coefficient blocks: luma block b, chroma block k = b & 7, the DC levels of its plane */
+        if (any_coded) {
+            const int k8 = b & 7;
+            const int z = z_of(bx, by);
+            const uint32_t cidx = FJ_GEN_COEF_IDX(ge.z), nl = (uint32_t)__popc(coded & 0xFFFFu), has_cdc = (coded >> 25) & 1u;
+            const bool ybit = (coded >> z) & 1u, cbit = (coded >> (16 + k8)) & 1u;
+            const uint32_t yoff = 32u * (cidx + (uint32_t)__popc(coded & ((1u << z) - 1u)));
+            const uint32_t coff = 32u * (cidx + nl + has_cdc + (uint32_t)__popc((coded >> 16) & ((1u << k8) - 1u)));
+            const uint32_t doff = 32u * (cidx + nl) + 8u * (uint32_t)(k8 >> 2);
+            const H264K_GLOBAL uint8_t *py = ybit ? cf + yoff : ref0, *pc = cbit ? cf + coff : ref0, *pd = has_cdc ? cf + doff : ref0;
+            const uint4 y0 = ld16g(py), y1 = ld16g(py + 16), c0 = ld16g(pc), c1 = ld16g(pc + 16);
+            const uint2 d0 = ld8g(pd);
+            const uint32_t ym = ybit ? ~0u : 0u, cm = cbit ? ~0u : 0u, dm = has_cdc ? ~0u : 0u;
+            yl[0] = y0.x & ym; yl[1] = y0.y & ym; yl[2] = y0.z & ym; yl[3] = y0.w & ym; yl[4] = y1.x & ym; yl[5] = y1.y & ym; yl[6] = y1.z & ym; yl[7] = y1.w & ym;
+            cl[0] = c0.x & cm; cl[1] = c0.y & cm; cl[2] = c0.z & cm; cl[3] = c0.w & cm; cl[4] = c1.x & cm; cl[5] = c1.y & cm; cl[6] = c1.z & cm; cl[7] = c1.w & cm;
+            dcl[0] = d0.x & dm; dcl[1] = d0.y & dm;
+        }
+        /* ---- stage ---- */
+        if (any_edge) {
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                const int p = b + 16 * i, lr = (p * 43) >> 7, lk = p - 3 * lr, lx = xs + 16 * lk;
+                const uint32_t first = (vl[i].x & 255u) * 0x01010101u, last = (vl[i].w >> 24) * 0x01010101u;
+                if (lx < 0) vl[i] = make_uint4(first, first, first, first);
+                else if (lx >= W) vl[i] = make_uint4(last, last, last, last);
+            }
+#pragma unroll
+            for (int i = 0; i < 3; i++) {
+                const int p = b + 16 * i, cp = p >= 18, rem = cp ? p - 18 : p, ck = rem & 1, cx = cxs + 8 * ck;
+                const uint32_t first = (vc[i].x & 255u) * 0x01010101u, last = (vc[i].y >> 24) * 0x01010101u;
+                if (cx < 0) vc[i] = make_uint2(first, first);
+                else if (cx >= CW) vc[i] = make_uint2(last, last);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const int p = b + 16 * i, lr = (p * 43) >> 7, lk = p - 3 * lr;
+            if (l_on[i]) {
+                uint32_t *d32 = reinterpret_cast<uint32_t *>(lw + lr * IW_STRIDE + 16 * lk);
+                d32[0] = vl[i].x; d32[1] = vl[i].y; d32[2] = vl[i].z; d32[3] = vl[i].w;
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 3; i++) {
+            const int p = b + 16 * i, cp = p >= 18, rem = cp ? p - 18 : p, cr = rem >> 1, ck = rem & 1;
+            if (c_on[i]) {
+                uint32_t *d32 = reinterpret_cast<uint32_t *>(lc + cp * 9 * IC_STRIDE + cr * IC_STRIDE + 8 * ck);
+                d32[0] = vc[i].x; d32[1] = vc[i].y;
+            }
+        }
+        wave_sync();
+      }
+
+        /* ======== luma: window rows 4 * by .. + 8, bytes o .. o + 11 with o = (xi - xs) + 4 * bx; each class reads the rows and dwords it
+         * uses.  xi - xs = xi mod 16, and the macroblock's own 16 * mbx drops out of it ======== */
+        s2 pl[4][2];
+#pragma unroll
+        for (int r = 0; r < 4; r++) pl[r][0] = pl[r][1] = pk(0);
+        {
+            LB_FRESH();
+            LB_LANE();
+            const int mvx = (int16_t)(ge.y & 0xFFFFu), mvy = (int32_t)ge.y >> 16;
+            const int o = (((mvx >> 2) - 2) & 15) + 4 * bx, sh = 8 * (o & 3), fx = mvx & 3, fy = mvy & 3;
+            const uint8_t *src = lw + 4 * by * IW_STRIDE + (o & ~3);
+            const int cls = !on ? -1 : (fx | fy) == 0 ? 0 : fy == 0 ? 1 : fx == 0 ? 2 : (fx != 2 && fy != 2) ? 3 : 4;
+            auto row = [&](uint32_t rw[3], int r, int nd) {      /* dwords 0 .. nd - 1 of window row r */
+                const uint32_t *q = reinterpret_cast<const uint32_t *>(src + r * IW_STRIDE);
+                uint32_t d[4];
+#pragma unroll
+                for (int k = 0; k < 4; k++) if (k <= nd) d[k] = q[k];
+#pragma unroll
+                for (int k = 0; k < 3; k++) rw[k] = k < nd ? (uint32_t)(((unsigned long long)d[k + 1] << 32 | d[k]) >> sh) : 0u;
+            };
+            if (cls == 0) {
+                uint32_t rw[9][3] = {};
+#pragma unroll
+                for (int r = 2; r < 6; r++) row(rw[r], r, 2);
+                lb_luma_whole(rw, pl);
+            } else if (cls == 1) {
+                uint32_t rw[9][3] = {};
+#pragma unroll
+                for (int r = 2; r < 6; r++) row(rw[r], r, 3);
+                lb_luma_hor(rw, fx, pl);
+            } else if (cls == 2) {
+                uint32_t rw[9][3] = {};
+#pragma unroll
+                for (int r = 0; r < 9; r++) row(rw[r], r, 2);
+                lb_luma_ver(rw, fy, pl);
+            } else if (cls == 3) {
+                uint32_t rw[9][3] = {};
+#pragma unroll
+                for (int r = 0; r < 9; r++) row(rw[r], r, (r >= 2 && r <= 6) ? 3 : 2);
+                lb_luma_diag(rw, fx, fy, pl);
+            } else if (cls == 4) {
+                uint32_t rw[9][3] = {};
+#pragma unroll
+                for (int r = 0; r < 9; r++) row(rw[r], r, 3);
+                lb_luma_centre(rw, fx, fy, pl);
+            }
+        }
+        /* ======== chroma: block k8 = 4 * plane + 2 * cby + cbx, rows 2 * half, 2 * half + 1 of it (cxi - cxs = cxi mod 8) ======== */
+#define LB_CHROMA_LANE() const int k8 = b & 7, plane = k8 >> 2, cbx = k8 & 1, cby = (k8 >> 1) & 1, half = b >> 3; (void)cbx
+        s2 pc[2][2];
+        {
+            LB_FRESH();
+            LB_LANE();
+            LB_CHROMA_LANE();
+            const int mvx = (int16_t)(ge.y & 0xFFFFu), mvy = (int32_t)ge.y >> 16;
+            const int ob = ((mvx >> 3) & 7) + 4 * cbx, cfx = mvx & 7, cfy = mvy & 7;
+            const uint32_t *q = reinterpret_cast<const uint32_t *>(lc + plane * 9 * IC_STRIDE + (cby * 4 + 2 * half) * IC_STRIDE + (ob & ~3));
+            uint32_t lo[3], hi[3];
+#pragma unroll
+            for (int t = 0; t < 3; t++) {
+                const uint32_t q0 = q[5 * t], q1 = q[5 * t + 1], q2 = q[5 * t + 2];   /* IC_STRIDE = 5 dwords */
+                lo[t] = __builtin_amdgcn_alignbyte(q1, q0, (uint32_t)(ob & 3)); hi[t] = __builtin_amdgcn_alignbyte(q2, q1, (uint32_t)(ob & 3));
+            }
+            const s2 w00 = as_s2((uint32_t)((8 - cfx) * (8 - cfy)) * 0x00010001u), w10 = as_s2((uint32_t)(cfx * (8 - cfy)) * 0x00010001u);
+            const s2 w01 = as_s2((uint32_t)((8 - cfx) * cfy) * 0x00010001u), w11 = as_s2((uint32_t)(cfx * cfy) * 0x00010001u);
+            lb_chroma_row(lo[0], hi[0], lo[1], hi[1], w00, w10, w01, w11, pc[0][0], pc[0][1]);
+            lb_chroma_row(lo[1], hi[1], lo[2], hi[2], w00, w10, w01, w11, pc[1][0], pc[1][1]);
+        }
+
+        /* ======== residual add, clip: the lane's four luma rows and two chroma rows as dwords ======== */
+        LB_FRESH();
+        LB_LANE();
+        LB_CHROMA_LANE();
+        const uint32_t mb = ge.x & 0xFFFFu, coded = ge.w;
+        const int qp_y = (int)FJ_GEN_QP_Y(ge.z), qp_c = (int)FJ_GEN_QP_C(ge.z);
+        uint32_t ldw[4], cdw[2];
+        if (!any_coded) {                                                            /* wave-uniform: the prediction as it is */
+#pragma unroll
+            for (int r = 0; r < 4; r++) ldw[r] = perm(as_u32(pl[r][1]), as_u32(pl[r][0]), 0x06040200u);
+#pragma unroll
+            for (int t = 0; t < 2; t++) cdw[t] = perm(as_u32(pc[t][1]), as_u32(pc[t][0]), 0x06040200u);
+        } else {
+            const int dc = lb_chroma_dc(dcl[0], dcl[1], k8 & 3, qp_c);
+            if (__ballot((coded & FJ_CODED_WIDE) != 0u) == 0ull) {                    /* wave-uniform: 16 bits hold every intermediate of every slot */
+                uint32_t rr[4][4];
+                lb_residual_pk(yl, cl, qp_y, qp_c, dc, rr);
+                const s2 lo = pk(0), hi = pk(255);
+#pragma unroll
+                for (int r = 0; r < 4; r++) {
+                    const s2 l01 = pk_clip(lo, hi, pl[r][0] + as_s2(perm(rr[r][1], rr[r][0], 0x05040100u)));
+                    const s2 l23 = pk_clip(lo, hi, pl[r][1] + as_s2(perm(rr[r][3], rr[r][2], 0x05040100u)));
+                    ldw[r] = perm(as_u32(l23), as_u32(l01), 0x06040200u);
+                }
+#pragma unroll
+                for (int t = 0; t < 2; t++) {
+                    const uint32_t r0 = half ? rr[2 + t][0] : rr[t][0], r1 = half ? rr[2 + t][1] : rr[t][1];
+                    const uint32_t r2 = half ? rr[2 + t][2] : rr[t][2], r3 = half ? rr[2 + t][3] : rr[t][3];
+                    const s2 k01 = pk_clip(lo, hi, pc[t][0] + as_s2(perm(r1, r0, 0x07060302u)));
+                    const s2 k23 = pk_clip(lo, hi, pc[t][1] + as_s2(perm(r3, r2, 0x07060302u)));
+                    cdw[t] = perm(as_u32(k23), as_u32(k01), 0x06040200u);
+                }
+            } else {                                                                 /* some slot is FJ_CODED_WIDE: 32 bits for all (equal where 16 would do) */
+                int ry[4][4], rc[4][4];
+                const bool over_y = lb_residual_32(yl, qp_y, false, 0, ry), over_c = lb_residual_32(cl, qp_c, true, dc, rc);
+                report_residual_range(fd, over_y || over_c, lane);
+#pragma unroll
+                for (int r = 0; r < 4; r++)
+                    ldw[r] = pack4(clip255(pl[r][0].x + ry[r][0]), clip255(pl[r][0].y + ry[r][1]), clip255(pl[r][1].x + ry[r][2]), clip255(pl[r][1].y + ry[r][3]));
+#pragma unroll
+                for (int t = 0; t < 2; t++) {
+                    const int c0 = half ? rc[2 + t][0] : rc[t][0], c1 = half ? rc[2 + t][1] : rc[t][1], c2 = half ? rc[2 + t][2] : rc[t][2], c3 = half ? rc[2 + t][3] : rc[t][3];
+                    cdw[t] = pack4(clip255(pc[t][0].x + c0), clip255(pc[t][0].y + c1), clip255(pc[t][1].x + c2), clip255(pc[t][1].y + c3));
+                }
+            }
+        }
+        /* ---- store: after the transpose lane (by, bx) holds row 4 * by + bx of the tile, 16 bytes; lanes b, b ^ 1 hold the left and the right
+         * half of two chroma rows, the even one takes the upper row whole, the odd one the lower ---- */
+        quad_transpose4(ldw[0], ldw[1], ldw[2], ldw[3], ln);
+        const uint32_t got = (uint32_t)quad_xor1((int)((b & 1) ? cdw[0] : cdw[1]));
+        H264K_GLOBAL uint8_t *T = cur + (size_t)mb * TILE;
+        if (on) {
+            st16g(T + (4 * by + bx) * 16, make_uint4(ldw[0], ldw[1], ldw[2], ldw[3]));
+            const u32x2 v = (b & 1) ? (u32x2){ got, cdw[1] } : (u32x2){ cdw[0], got };
+            *(H264K_GLOBAL u32x2 *)(T + T_CB + plane * 64 + (cby * 4 + 2 * half + (b & 1)) * 8) = v;
+        }
+        wave_sync();          /* the staged windows are overwritten by the next group's */
+    }
+#undef LB_FRESH
+#undef LB_LANE
+#undef LB_CHROMA_LANE
 }
 
 
