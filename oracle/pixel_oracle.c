@@ -26,7 +26,9 @@
  *   colour conversion                         src/h264bsd_decoder.c:1163-1370 (h264bsdConvertTo*)
  *   concealment of lost macroblocks           src/h264bsd_conceal.c:266-637 (ConcealMb, Transform); the walking
  *                                             order of h264bsdConceal (:124-260) arrives in the frame job
- * (tests/test_damaged_streams.py pins the concealment against the compiled reference on damaged streams)
+ * (the concealment is pinned twice: tests/test_damaged_streams.py against the compiled reference on damaged streams, which
+ *  reach what they happen to lose; tests/test_concealed_jobs.py on chosen neighbour masks and border samples — against a plain
+ *  integer model on hand-built jobs, and against the compiled reference on all-I_PCM streams that leave a slice group out)
  * oracle_deblock_census() is oracle_deblock() that also counts which decisions the filter takes (strength rules, gates, clips,
  * saturation): tests/test_structured_jobs.py holds the hand-built test pictures to taking every one of them.
  * Known, deliberate gap: the reference turns a residual outside [-512,511] into a decode error

@@ -7,7 +7,8 @@ slots, I_PCM, every intra mode under every neighbour-availability pattern, arbit
 per-MB deblocking flags.  The derived sections (schedules) are completed by the product's own
 h264bsdmiJobFinalize(), i.e. by the same code the parser uses.
 The second half of the file gives pictures structure on purpose (patch_typed, patch_sub8x8, patch_coherent, patch_copy_runs,
-patch_window_edges, build_job(smooth=...)): what white-noise motion and content never produce."""
+patch_window_edges, build_job(smooth=...)): what white-noise motion and content never produce.  The end of it loses macroblocks
+(patch_lost, chosen_samples, build_job(pcm=...)): concealed macroblocks under chosen neighbour masks over chosen border samples."""
 import ctypes
 import struct
 
@@ -23,31 +24,33 @@ def z_of(x, y):
     return ((y >> 1) << 3) | ((x >> 1) << 2) | ((y & 1) << 1) | (x & 1)
 
 
+def _i4_ok(avail, z):
+    """the Intra4x4 modes of block z that are valid under the MB-level availability bits"""
+    A, B, D = avail & 1, avail & 2, avail & 8
+    bx, by = Z_X[z], Z_Y[z]
+    left = bx > 0 or A
+    top = by > 0 or B
+    if bx > 0 and by > 0:
+        tl = True
+    elif by > 0:
+        tl = bool(A)
+    elif bx > 0:
+        tl = bool(B)
+    else:
+        tl = bool(D)
+    ok = [2]
+    if top:
+        ok += [0, 3, 7]
+    if left:
+        ok += [1, 8]
+    if top and left and tl:
+        ok += [4, 5, 6]
+    return ok
+
+
 def _i4_modes(rng, avail):
     """16 Intra4x4 modes (z order) valid for the MB-level availability bits"""
-    A, B, C, D = avail & 1, avail & 2, avail & 4, avail & 8
-    modes = []
-    for z in range(16):
-        bx, by = Z_X[z], Z_Y[z]
-        left = bx > 0 or A
-        top = by > 0 or B
-        if bx > 0 and by > 0:
-            tl = True
-        elif by > 0:
-            tl = bool(A)
-        elif bx > 0:
-            tl = bool(B)
-        else:
-            tl = bool(D)
-        ok = [2]
-        if top:
-            ok += [0, 3, 7]
-        if left:
-            ok += [1, 8]
-        if top and left and tl:
-            ok += [4, 5, 6]
-        modes.append(int(rng.choice(ok)))
-    return modes
+    return [int(rng.choice(_i4_ok(avail, z))) for z in range(16)]
 
 
 def _coef_block(rng, ac_only=False, density=0.3, amp=12):
@@ -128,14 +131,15 @@ def _pcm_gradient(rng, ramps, mbx, mby):
 
 
 def build_job(lib, rng, wmb, hmb, cur_slot, n_slots, ref_slots, *, p_inter=0.6, p_pcm=0.03, mv_range=None, any_deblock=True, patch=None, near_bound=False,
-              smooth=False, extra_blocks=0):
+              smooth=False, extra_blocks=0, pcm=None):
     """One random picture.  ref_slots: slots holding valid pictures (empty -> intra only).
     patch(recs, mvs): called on the records [n][32] and the dense vectors [n][16][2] before the job is finished — a finished
     job carries its vectors in the records and the sparse section (framejob.h), the dense array here is only h264bsdmiJobFinalize's input.
     smooth: content that opens the deblocking filter — few and small coefficients, I_PCM macroblocks that hold ramps (_pcm_gradient), so
     that neighbouring samples usually pass the alpha / beta gates at mid QPs.
     extra_blocks: that many more coefficient blocks (one level of +-1 each) behind the last macroblock's; patch is then called as
-    patch(recs, mvs, first) with the index of the first of them, for macroblocks it wants to give a coded block (coef_idx, bytes 12..15)."""
+    patch(recs, mvs, first) with the index of the first of them, for macroblocks it wants to give a coded block (coef_idx, bytes 12..15).
+    pcm: {macroblock address: 384 samples (Y[256], Cb[64], Cr[64], raster)} — these macroblocks are I_PCM with exactly those samples."""
     coef_block = _coef_block_smooth if smooth else _coef_block
     ramps = smooth if isinstance(smooth, list) else draw_ramps(rng) if smooth else None
     n = wmb * hmb
@@ -165,7 +169,11 @@ def build_job(lib, rng, wmb, hmb, cur_slot, n_slots, ref_slots, *, p_inter=0.6, 
         struct.pack_into("<I", r, 12, nblk)
         u = rng.random()
         coded = 0
-        if ref_slots and u < p_inter:
+        if pcm is not None and a in pcm:
+            r[0], r[1], r[2] = 3, 0, QPC[min(51, max(0, cqp))]
+            buf[coef_off + 32 * nblk: coef_off + 32 * nblk + 384] = np.asarray(pcm[a], dtype=np.uint8).reshape(384)
+            nblk += 12
+        elif ref_slots and u < p_inter:
             r[0] = 0                                                   # inter
             style = rng.random()
             if style < 0.35:                                           # uniform, often whole-sample
@@ -574,4 +582,85 @@ def patch_window_edges(rng, wmb, first=0):
                 mvs[a, by, bx] = mv
                 parts = 0
             recs[a, 4] = (int(recs[a, 4]) & 0x8F) | (parts << 4)
+    return patch
+
+
+# ------------------------------------------------------------------ lost macroblocks (patch_lost, chosen_samples)
+# No random job holds a concealed macroblock.  patch_lost rewrites the macroblocks that a decoded mask leaves out the way the
+# parser's conceal_one (hd_core.c) does when the access unit ends; chosen_samples gives the surviving I_PCM macroblocks (build_job's
+# pcm=) the borders that the concealment arithmetic is sensitive to.
+FJ_MB_CONCEAL_I, FJ_MB_CONCEAL_P = 4, 5
+CONTENTS = ["noise", "split", "flat0", "flat255", "ramp"]
+
+
+def chosen_samples(content, rng, mbx=0, mby=0):
+    """384 samples of one I_PCM macroblock.  noise; split: every border of the macroblock is one half 0 and one half 255 (which way
+    round is drawn per plane), the largest "first half minus second half" a side can have, so that two sides together leave 0..255
+    in both directions; flat0 / flat255; ramp: a level and slopes of at most half a level per sample, which give the small negative
+    odd slopes whose >> 1 rounds down; mixed: one of these, drawn per macroblock."""
+    pick = content if content != "mixed" else CONTENTS[int(rng.integers(0, len(CONTENTS)))]
+    out = []
+    for size in (16, 8, 8):
+        yy, xx = np.mgrid[0:size, 0:size]
+        if pick == "noise":
+            v = rng.integers(0, 256, (size, size))
+        elif pick == "split":
+            v = 255 * (((xx < size // 2) == (yy < size // 2)) ^ bool(rng.integers(0, 2)))
+        elif pick in ("flat0", "flat255"):
+            v = np.full((size, size), 0 if pick == "flat0" else 255)
+        elif pick == "ramp":
+            sx, sy = rng.integers(-2, 3, 2)
+            v = int(rng.integers(0, 256)) + (sx * (xx + size * mbx) + sy * (yy + size * mby)) // 4
+        else:
+            raise ValueError(content)
+        out.append(np.clip(v, 0, 255).astype(np.uint8).ravel())
+    return np.concatenate(out)
+
+
+def patch_lost(wmb, hmb, decoded, ref_slot=None):
+    """The macroblocks that `decoded` (one truth value per macroblock) leaves out become what conceal_one writes for them, in the
+    reference's walking order (conceal_model.walk): zeroed records of kind FJ_MB_CONCEAL_I with avail = the neighbours decoded or
+    concealed before them — or, with ref_slot, FJ_MB_CONCEAL_P whose four ref_slot bytes name that slot —, QP 40 / 36, filtered on
+    every edge inside the picture, coef_idx = position in the walk.  (FJ_PRED_PHASE2 is the parser's business and stays clear.)
+    A surviving intra macroblock no longer has a lost neighbour available, as in a stream, where a macroblock that was never
+    decoded belongs to no slice: the availability bits towards lost macroblocks are cleared and a prediction mode that needs one of
+    them becomes DC.  (Left set, such a macroblock would wait for the concealed one that in turn waits for it.)"""
+    import conceal_model
+    order = conceal_model.walk(wmb, hmb, decoded)
+    lost = {mb for mb, _ in order}
+
+    def patch(recs, mvs16, first_extra=None):
+        n = wmb * hmb
+        for a in range(n):
+            if a in lost or recs[a, 0] not in (1, 2):
+                continue
+            x, y = a % wmb, a // wmb
+            avail = int(recs[a, 3])
+            if x > 0 and a - 1 in lost: avail &= ~1
+            if y > 0 and a - wmb in lost: avail &= ~2
+            if y > 0 and x + 1 < wmb and a - wmb + 1 in lost: avail &= ~4
+            if y > 0 and x > 0 and a - wmb - 1 in lost: avail &= ~8
+            recs[a, 3] = avail
+            luma, chroma = int(recs[a, 4]) & 3, (int(recs[a, 4]) >> 2) & 3
+            if chroma not in [0] + ([1] if avail & 1 else []) + ([2] if avail & 2 else []) + ([3] if (avail & 11) == 11 else []):
+                chroma = 0
+            if recs[a, 0] == 2:
+                if luma not in [2] + ([0] if avail & 2 else []) + ([1] if avail & 1 else []) + ([3] if (avail & 11) == 11 else []):
+                    luma = 2
+            else:
+                for z in range(16):
+                    if (int(recs[a, 24 + (z >> 1)]) >> ((z & 1) * 4)) & 15 not in _i4_ok(avail, z):
+                        recs[a, 24 + (z >> 1)] = (int(recs[a, 24 + (z >> 1)]) & ~(15 << ((z & 1) * 4))) | (2 << ((z & 1) * 4))
+            recs[a, 4] = (int(recs[a, 4]) & 0xF0) | luma | (chroma << 2)
+        for k, (a, avail) in enumerate(order):
+            recs[a, :] = 0
+            mvs16[a] = 0
+            recs[a, 1], recs[a, 2] = 40, 36
+            recs[a, 5] = 4 | (1 if a % wmb else 0) | (2 if a >= wmb else 0)
+            struct.pack_into("<I", recs[a], 12, k)
+            if ref_slot is None:
+                recs[a, 0], recs[a, 3] = FJ_MB_CONCEAL_I, avail
+            else:
+                recs[a, 0] = FJ_MB_CONCEAL_P
+                recs[a, 16:20] = ref_slot
     return patch

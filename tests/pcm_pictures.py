@@ -26,38 +26,55 @@ def _macroblocks(Y, Cb, Cr):
     return np.concatenate([y, cb, cr], axis=1)
 
 
-def pcm_stream(pictures, crop=None, idc=1, level=51):
+def pcm_stream(pictures, crop=None, idc=1, level=51, groups=None, omit=None):
     """An Annex-B stream that decodes to exactly `pictures`, a list of (Y[H, W], Cb[H/2, W/2], Cr[H/2, W/2]) uint8 arrays, H and W
     multiples of 16.  poc_type 2, one reference frame, deblocking_control 1; crop: (left, right, top, bottom) in chroma samples
     (frame_crop_*_offset).  Every picture is an IDR I slice (slice_type 7) with its own idr_pic_id.  idc is
     disable_deblocking_filter_idc: with 0 the offsets are 0 and, I_PCM having QP 0, alpha is 0 and the filter changes no sample, but the
-    picture is a filtered one for whoever decodes it."""
+    picture is a filtered one for whoever decodes it.
+    groups: an explicit macroblock-to-slice-group map (one group number per macroblock, 0 .. at most 7, every number up to the
+    largest in use: slice_group_map_type 6); every picture is then one slice per group, in ascending group order, each holding the
+    group's macroblocks in raster order.  omit: {picture index: the groups whose slice NAL unit is left out of that picture} — a
+    decoder finds those macroblocks missing when the next picture begins and conceals them."""
     Y0 = np.asarray(pictures[0][0])
     H, W = Y0.shape
     assert H % 16 == 0 and W % 16 == 0 and H and W and idc in (0, 1, 2)
     sps = dict(poc_type=2, num_ref_frames=1, wmb=W // 16, hmb=H // 16, crop=crop, level=level, log2_max_frame_num=4)
     pps = dict(deblocking_control=1)
+    n_mbs = (H // 16) * (W // 16)
+    if groups is None:
+        members = [np.arange(n_mbs)]
+    else:
+        groups = [int(g) for g in groups]
+        assert len(groups) == n_mbs and sorted(set(groups)) == list(range(max(groups) + 1)) and 1 <= max(groups) <= 7
+        pps["fmo"] = dict(type=6, groups=max(groups) + 1, ids=groups)
+        members = [np.nonzero(np.array(groups) == g)[0] for g in range(max(groups) + 1)]
+    omit = omit or {}
     out = [write_sps(sps), write_pps(pps, sps)]
     for k, (Y, Cb, Cr) in enumerate(pictures):
         Y, Cb, Cr = (np.ascontiguousarray(p, dtype=np.uint8) for p in (Y, Cb, Cr))
         assert Y.shape == (H, W) and Cb.shape == Cr.shape == (H // 2, W // 2)
-        bw = BitWriter()
-        bw.ue(0); bw.ue(7); bw.ue(0)                       # first_mb_in_slice, slice_type, pic_parameter_set_id
-        bw.u(4, 0)                                         # frame_num
-        bw.ue(k & 0xFFFF)                                  # idr_pic_id
-        bw.u(1, 0); bw.u(1, 0)                             # no_output_of_prior_pics, long_term_reference_flag
-        bw.se(0)                                           # slice_qp_delta
-        bw.ue(idc)
-        if idc != 1:
-            bw.se(0); bw.se(0)                             # slice_alpha_c0_offset_div2, slice_beta_offset_div2
-        bw.ue(25)                                          # mb_type I_PCM of macroblock 0
-        bw.align_zero()
-        mbs = _macroblocks(Y, Cb, Cr)
-        body = np.empty((mbs.shape[0], 386), dtype=np.uint8)
-        body[:, 0], body[:, 1] = 0x0D, 0x00
-        body[:, 2:] = mbs
-        rbsp = bw.bytes() + body.reshape(-1)[2:].tobytes() + b"\x80"
-        out.append(b"\x00\x00\x00\x01\x65" + _EMULATION.sub(b"\x00\x00\x03", rbsp))
+        all_mbs = _macroblocks(Y, Cb, Cr)
+        for g, member in enumerate(members):
+            if g in omit.get(k, ()):
+                continue
+            bw = BitWriter()
+            bw.ue(int(member[0])); bw.ue(7); bw.ue(0)          # first_mb_in_slice, slice_type, pic_parameter_set_id
+            bw.u(4, 0)                                         # frame_num
+            bw.ue(k & 0xFFFF)                                  # idr_pic_id
+            bw.u(1, 0); bw.u(1, 0)                             # no_output_of_prior_pics, long_term_reference_flag
+            bw.se(0)                                           # slice_qp_delta
+            bw.ue(idc)
+            if idc != 1:
+                bw.se(0); bw.se(0)                             # slice_alpha_c0_offset_div2, slice_beta_offset_div2
+            bw.ue(25)                                          # mb_type I_PCM of the slice's first macroblock
+            bw.align_zero()
+            mbs = all_mbs[member]
+            body = np.empty((mbs.shape[0], 386), dtype=np.uint8)
+            body[:, 0], body[:, 1] = 0x0D, 0x00
+            body[:, 2:] = mbs
+            rbsp = bw.bytes() + body.reshape(-1)[2:].tobytes() + b"\x80"
+            out.append(b"\x00\x00\x00\x01\x65" + _EMULATION.sub(b"\x00\x00\x03", rbsp))
     return b"".join(out)
 
 

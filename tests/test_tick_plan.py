@@ -58,6 +58,53 @@ def test_plan_equals_the_pins(plans):
     assert not wrong, f"{len(wrong)} of {len(pins)} plans differ, the first: {wrong[0]}"
 
 
+LARGEST = r"""
+#include <cstdio>
+#include "tick_plan.h"
+#define __host__
+#define __device__
+namespace h264k {
+KERNEL_TEXT
+}
+int main()
+{
+    /* one tick: the concealed picture of 256 x 144 macroblocks alone, and next to an intact one that wants a band per row */
+    for (unsigned n = 1; n <= 2; n++)
+        for (unsigned rows_asked = 0; rows_asked <= 18; rows_asked += 1 + 16 * (rows_asked > 0)) {
+            TickShape s;
+            s.n_frames = n; s.n_heavy = n; s.max_w = 256; s.max_h = 144; s.intra_whole = true;
+            s.want_heavy[1] = n == 1 || !rows_asked ? 1 : (144 + rows_asked - 1) / rows_asked;
+            TailConfig tc;
+            tc.band_budget = 1u << 20;
+            BandPlan bp = {};
+            if (plan_bands(s, tc, 1, WAVES, h264k::intra_lds_bytes, false, bp)) { printf("refused\n"); continue; }
+            printf("%u %u %u %zu %zu %zu\n", bp.bands, bp.rows, bp.waves, bp.lds, h264k::intra_lds_bytes(bp.waves + 1, 256, bp.rows), (size_t)TAIL_LDS_BUDGET);
+        }
+    return 0;
+}
+"""
+
+
+def test_largest_concealed_picture_is_one_band_next_to_two_wavefronts(tmp_path):
+    """What tests/test_gpu_concealed_jobs.py::test_huge_concealed_picture_in_one_band runs must be what it says: with the kernel's own
+    LDS need (intra_lds_bytes and its constants, taken from k_frame_intra.hip.h as they stand) a picture of 256 x 144 macroblocks
+    that must stay whole is planned as bands of 144 rows — one per picture of the tick — with at most two wavefronts, because a third no longer
+    fits next to the scheduling state; alone or next to an intact picture, whatever rows per band are asked for."""
+    import subprocess
+    text = open(os.path.join(CSRC, "kernels", "k_frame_intra.hip.h")).read()
+    parts = [re.search(r"^constexpr int %s = [^;]*;" % name, text, flags=re.M).group(0) for name in ("I4TAB_BYTES", "INTRA_SLOT", "INTRA_WAVE_LDS")]
+    parts.append(re.search(r"^__host__ __device__ inline size_t intra_lds_bytes\(.*?^}", text, flags=re.M | re.S).group(0))
+    src, exe = str(tmp_path / "largest.cpp"), str(tmp_path / "largest")
+    open(src, "w").write(LARGEST.replace("KERNEL_TEXT", "\n".join(parts)))
+    subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", f"-DWAVES={gen.WAVES}", f"-I{CSRC}", src, "-o", exe], check=True)
+    out = subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split("\n")
+    rows = [[int(v) for v in line.split()] for line in out if line]
+    assert len(rows) == 6
+    for bands, rows_per_band, waves, lds, lds_one_more, budget in rows:
+        assert rows_per_band == 144 and 1 <= waves <= 2 and lds <= budget < lds_one_more, (bands, rows_per_band, waves, lds, lds_one_more, budget)
+    assert rows[0][0] == 1 and {r[0] for r in rows[:3]} == {1}, "alone, the picture is one workgroup"
+
+
 def test_whole_pictures_stay_in_one_band(plans):
     """intra_whole: k_frame_intra's rows-per-band cap covers the whole picture wherever the plan succeeds — whatever the other
     pictures of the tick want, and however little LDS is left (fewer wavefronts, never shorter bands)"""
