@@ -9,7 +9,8 @@
  *                                                    next to the inter kernels (single-lane engine and replay sets: SideLane), joined before k_frame_intra
  *     k_recon_inter_lb  grid (n_uni/32, N)    x 64   inter macroblocks with one motion vector: a chunk of 32 list entries per wavefront, binned by
  *                                                    interpolation class, four macroblocks at a time, a 4x4 block per lane (-DINTER_LANE_BLOCKS=0: k_recon_inter<0>)
- *     k_recon_inter<1>  grid (n_quad/4, N)    x 256  inter macroblocks with one motion vector per 8x8 quadrant
+ *     k_recon_inter_lq  grid (n_quad/8, N)    x 64   inter macroblocks with one motion vector per 8x8 quadrant: a chunk of 8 list entries per wavefront, their quadrants
+ *                                                    binned by interpolation class, 16 quadrants at a time, a 4x4 block per lane (-DINTER_LANE_QUADS=0: k_recon_inter<1>)
  *     k_recon_inter<2>  grid (n_rest/4, N)    x 256  finer partitions
  *     k_dbk             grid (n_dbk/512, N)   x 512  boundary strengths from metadata, one macroblock per lane; on a third HIP stream, next to the four above, joined before k_frame_dbk
  *     k_frame_intra     grid (N)              x 768  one workgroup per picture: intra macroblocks, dataflow-scheduled in LDS
@@ -475,6 +476,11 @@ template <int PATH> static void launch_inter(hipStream_t st, const FrameDesc *d_
 #if INTER_LANE_BLOCKS
     if constexpr (PATH == 0) {                       /* one wavefront per chunk of INTER_LB_CHUNK entries, a 4x4 block per lane */
         if (n_max) hipLaunchKernelGGL(h264k::k_recon_inter_lb, dim3((n_max + INTER_LB_CHUNK - 1) / INTER_LB_CHUNK, n_frames), dim3(64), 0, st, d_desc);
+    } else
+#endif
+#if INTER_LANE_QUADS
+    if constexpr (PATH == 1) {                       /* one wavefront per chunk of INTER_LQ_CHUNK entries, a quadrant per four lanes */
+        if (n_max) hipLaunchKernelGGL(h264k::k_recon_inter_lq, dim3((n_max + INTER_LQ_CHUNK - 1) / INTER_LQ_CHUNK, n_frames), dim3(64), 0, st, d_desc);
     } else
 #endif
     {

@@ -11,7 +11,9 @@
  *                                  h264bsdFillBlock src/h264bsd_reconstruct.c:2244, src/h264bsd_image.c:81
  *   k_recon_inter_lb : inter macroblocks with ONE motion vector (most of the list): a chunk of 32 list entries per wavefront, sorted by
  *                   interpolation class, four macroblocks at a time, a 4x4 luma block per lane (kernels/inter_lane_block.hip.h).
- *   k_recon_inter : every other inter macroblock, one wavefront each (= one workgroup: the wavefronts share nothing), list-driven.
+ *   k_recon_inter_lq : inter macroblocks with one motion vector per 8x8 QUADRANT: a chunk of 8 list entries per wavefront, the quadrants sorted
+ *                   by interpolation class, 16 quadrants at a time, a 4x4 luma block per lane (the same arithmetic).
+ *   k_recon_inter : every other inter macroblock (finer partitions), one wavefront each (= one workgroup: the wavefronts share nothing), list-driven.
  *                   Reference windows staged in LDS tile row by tile row (aligned 16-byte loads), 6-tap luma on packed
  *                   sample pairs / bilinear chroma, dequant + 4x4 inverse transform with DPP quad transposes, residual
  *                   add; the macroblock leaves as its tile (24 x 16 bytes).

@@ -1,5 +1,5 @@
-/* kernels/inter_lane_block.hip.h — the register arithmetic of k_recon_inter_lb (k_recon_inter.hip.h): one lane owns a whole 4x4 luma block
- * and half a 4x4 chroma block.  Nothing here touches memory or other lanes.  Part of kernels.hip.h (which see); not a stand-alone header. */
+/* kernels/inter_lane_block.hip.h — the register arithmetic of k_recon_inter_lb and k_recon_inter_lq (k_recon_inter.hip.h): one lane owns a whole
+ * 4x4 luma block and half a 4x4 chroma block.  Nothing here touches memory or other lanes.  Part of kernels.hip.h (which see); not a stand-alone header. */
 #pragma once
 namespace h264k {
 
@@ -212,5 +212,26 @@ __device__ __forceinline__ bool lb_residual_32(const uint32_t lv[8], int qp, boo
     }
     return over > 1023u;
 }
+
+/* ------------------------------------------------------------------ a quadrant per four lanes (k_recon_inter_lq)
+ * Lane j = 0..3 of a slot owns 4x4 luma block (j & 1, j >> 1) of 8x8 quadrant q (raster in the macroblock) — block z = 4 * q + j in H.264
+ * block order — and rows 2 * (j & 1), 2 * (j & 1) + 1 of 4x4 chroma block q of plane j >> 1. */
+/* the bits of FjMbRec.coded that reach quadrant q: its four luma blocks, its chroma block in both planes, the chroma DC block */
+__device__ __forceinline__ uint32_t lq_coded_mask(uint32_t q) { return (0xFu << (4u * q)) | (0x00110000u << q) | FJ_CODED_CHROMA_DC; }
+/* byte of the quadrant's window column 0 (sample column x - 2) in the staged row, which begins at the window's first tile:
+ * (16 * mbx + 8 * (q & 1) + (mvx >> 2) - 2) mod 16; and of its first chroma column, (8 * mbx + 4 * (q & 1) + (mvx >> 3)) mod 8 */
+__device__ __forceinline__ int lq_window_byte(int q, int mvx) { return (8 * (q & 1) + (mvx >> 2) - 2) & 15; }
+__device__ __forceinline__ int lq_chroma_byte(int q, int mvx) { return (4 * (q & 1) + (mvx >> 3)) & 7; }
+/* Store exchange: the lanes jbx = 0, 1 of a block row hold the left and the right 4x4 block as four row dwords each.  The left lane sends
+ * rows 2, 3 and the right lane rows 0, 1 (got0, got1 = what the other lane sent); r0, r1 = two whole 8-byte rows: rows 0, 1 in the left lane,
+ * rows 2, 3 in the right one. */
+__device__ __forceinline__ void lq_pair_rows(const uint32_t ldw[4], uint32_t got0, uint32_t got1, int jbx, uint32_t r0[2], uint32_t r1[2])
+{
+    r0[0] = jbx ? got0 : ldw[0]; r0[1] = jbx ? ldw[2] : got0;
+    r1[0] = jbx ? got1 : ldw[1]; r1[1] = jbx ? ldw[3] : got1;
+}
+/* where r0 goes in the macroblock's tile (r1: the row below, + 16), and the lane's first chroma row (the second: + 8) */
+__device__ __forceinline__ int lq_luma_store_offset(int q, int j) { return (8 * (q >> 1) + 4 * (j >> 1) + 2 * (j & 1)) * 16 + 8 * (q & 1); }
+__device__ __forceinline__ int lq_chroma_store_offset(int q, int j) { return T_CB + (j >> 1) * 64 + (4 * (q >> 1) + 2 * (j & 1)) * 8 + 4 * (q & 1); }
 
 } // namespace h264k

@@ -1,6 +1,7 @@
-/* kernels/k_recon_inter.hip.h — k_recon_inter<PATH> and k_recon_inter_lb: every inter macroblock that is no plain copy (interpolation, residual,
- * write-back).  k_recon_inter_lb (at the end of the file) takes the one-vector part of the list, k_recon_inter<1>, <2> the partitioned parts;
- * k_recon_inter<0> is the previous one-vector kernel, built with -DINTER_LANE_BLOCKS=0.  Part of kernels.hip.h (which see); not a stand-alone header. */
+/* kernels/k_recon_inter.hip.h — k_recon_inter<PATH>, k_recon_inter_lb and k_recon_inter_lq: every inter macroblock that is no plain copy (interpolation,
+ * residual, write-back).  k_recon_inter_lb takes the one-vector part of the list, k_recon_inter_lq (both at the end of the file) the part with one vector
+ * per 8x8 quadrant, k_recon_inter<2> the finer partitions; k_recon_inter<0> and <1> are the previous kernels of the first two parts, launched with
+ * -DINTER_LANE_BLOCKS=0 / -DINTER_LANE_QUADS=0.  Part of kernels.hip.h (which see); not a stand-alone header. */
 #pragma once
 namespace h264k {
 /* ------------------------------------------------------------------ inter prediction */
@@ -631,6 +632,125 @@ __global__ __launch_bounds__(64 * INTER_WG_WAVES, PATH == 0 ? INTER_OCC : INTER_
 #define INTER_LB_OCC 4       /* wavefronts per SIMD the register budget is sized for (128 VGPRs): 16 macroblocks in flight per SIMD */
 #endif
 static_assert(INTER_LB_CHUNK % 4 == 0 && INTER_LB_CHUNK >= 4 && INTER_LB_CHUNK <= 64, "INTER_LB_CHUNK");
+/* ---- what k_recon_inter_lb and k_recon_inter_lq (below) share: the chunk of a workgroup, and the three steps between the staged windows
+ * and the lane's finished dwords.  The arithmetic itself is kernels/inter_lane_block.hip.h. ---- */
+/* chunk of this workgroup: the XCD mapping of k_recon_inter (which see), in chunks instead of entries */
+__device__ __forceinline__ uint32_t inter_chunk_of_block()
+{
+#if INTER_XCD == 1
+    const uint32_t cls8 = blockIdx.x & 7u, per8 = gridDim.x >> 3, rem8 = gridDim.x & 7u;
+    return cls8 * per8 + (cls8 < rem8 ? cls8 : rem8) + (blockIdx.x >> 3);
+#elif INTER_XCD > 1
+    const uint32_t C_ = INTER_XCD, full_ = (gridDim.x / (8u * C_)) * (8u * C_);
+    const uint32_t b_ = blockIdx.x, o_ = b_ % (8u * C_);
+    return b_ >= full_ ? b_ : (b_ - o_) + (o_ & 7u) * C_ + (o_ >> 3);
+#else
+    return blockIdx.x;
+#endif
+}
+/* The lane's 4x4 luma block from its staged window: src = window row 0 of the block (two rows above its first sample row) at the dword that holds window column 0, sh = 8 * (byte of that column in its dword), STRIDE = bytes per staged row.  cls = the
+ * lane's interpolation class (-1: none); every class reads the rows and dwords it uses and runs under the mask of its lanes. */
+template <int STRIDE>
+__device__ __forceinline__ void lb_luma_from_lds(const uint8_t *src, int sh, int cls, int fx, int fy, s2 pl[4][2])
+{
+    auto row = [&](uint32_t rw[3], int r, int nd) {      /* dwords 0 .. nd - 1 of window row r */
+        const uint32_t *q = reinterpret_cast<const uint32_t *>(src + r * STRIDE);
+        uint32_t d[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) if (k <= nd) d[k] = q[k];
+#pragma unroll
+        for (int k = 0; k < 3; k++) rw[k] = k < nd ? (uint32_t)(((unsigned long long)d[k + 1] << 32 | d[k]) >> sh) : 0u;
+    };
+    if (cls == 0) {
+        uint32_t rw[9][3] = {};
+#pragma unroll
+        for (int r = 2; r < 6; r++) row(rw[r], r, 2);
+        lb_luma_whole(rw, pl);
+    } else if (cls == 1) {
+        uint32_t rw[9][3] = {};
+#pragma unroll
+        for (int r = 2; r < 6; r++) row(rw[r], r, 3);
+        lb_luma_hor(rw, fx, pl);
+    } else if (cls == 2) {
+        uint32_t rw[9][3] = {};
+#pragma unroll
+        for (int r = 0; r < 9; r++) row(rw[r], r, 2);
+        lb_luma_ver(rw, fy, pl);
+    } else if (cls == 3) {
+        uint32_t rw[9][3] = {};
+#pragma unroll
+        for (int r = 0; r < 9; r++) row(rw[r], r, (r >= 2 && r <= 6) ? 3 : 2);
+        lb_luma_diag(rw, fx, fy, pl);
+    } else if (cls == 4) {
+        uint32_t rw[9][3] = {};
+#pragma unroll
+        for (int r = 0; r < 9; r++) row(rw[r], r, 3);
+        lb_luma_centre(rw, fx, fy, pl);
+    }
+}
+/* Two chroma rows of four samples from three staged rows of DW dwords: q = the first of them at the dword that holds the first sample,
+ * ob & 3 = that sample's byte in it */
+template <int DW>
+__device__ __forceinline__ void lb_chroma_from_lds(const uint32_t *q, int ob, int cfx, int cfy, s2 pc[2][2])
+{
+    uint32_t lo[3], hi[3];
+#pragma unroll
+    for (int t = 0; t < 3; t++) {
+        const uint32_t q0 = q[DW * t], q1 = q[DW * t + 1], q2 = q[DW * t + 2];
+        lo[t] = __builtin_amdgcn_alignbyte(q1, q0, (uint32_t)(ob & 3)); hi[t] = __builtin_amdgcn_alignbyte(q2, q1, (uint32_t)(ob & 3));
+    }
+    const s2 w00 = as_s2((uint32_t)((8 - cfx) * (8 - cfy)) * 0x00010001u), w10 = as_s2((uint32_t)(cfx * (8 - cfy)) * 0x00010001u);
+    const s2 w01 = as_s2((uint32_t)((8 - cfx) * cfy) * 0x00010001u), w11 = as_s2((uint32_t)(cfx * cfy) * 0x00010001u);
+    lb_chroma_row(lo[0], hi[0], lo[1], hi[1], w00, w10, w01, w11, pc[0][0], pc[0][1]);
+    lb_chroma_row(lo[1], hi[1], lo[2], hi[2], w00, w10, w01, w11, pc[1][0], pc[1][1]);
+}
+/* Residual add and clip: the lane's four luma rows (ldw) and the two rows 2 * half, 2 * half + 1 of its chroma block (cdw) as dwords.
+ * yl, cl, dcl: the level blocks as loaded (zero where there is none), dci: the chroma block's place in its plane.  any_coded is wave-uniform,
+ * and so is the choice of the 32-bit path: all lanes take it when one of them is FJ_CODED_WIDE (equal where 16 bits would do). */
+__device__ __forceinline__ void lb_add_residual(const FrameDesc &fd, int lane, bool any_coded, uint32_t coded, int qp_y, int qp_c, const uint32_t yl[8],
+                                                const uint32_t cl[8], const uint32_t dcl[2], int dci, int half, const s2 pl[4][2], const s2 pc[2][2],
+                                                uint32_t ldw[4], uint32_t cdw[2])
+{
+    if (!any_coded) {                                                                /* the prediction as it is */
+#pragma unroll
+        for (int r = 0; r < 4; r++) ldw[r] = perm(as_u32(pl[r][1]), as_u32(pl[r][0]), 0x06040200u);
+#pragma unroll
+        for (int t = 0; t < 2; t++) cdw[t] = perm(as_u32(pc[t][1]), as_u32(pc[t][0]), 0x06040200u);
+        return;
+    }
+    const int dc = lb_chroma_dc(dcl[0], dcl[1], dci, qp_c);
+    if (__ballot((coded & FJ_CODED_WIDE) != 0u) == 0ull) {                            /* 16 bits hold every intermediate of every slot */
+        uint32_t rr[4][4];
+        lb_residual_pk(yl, cl, qp_y, qp_c, dc, rr);
+        const s2 lo = pk(0), hi = pk(255);
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            const s2 l01 = pk_clip(lo, hi, pl[r][0] + as_s2(perm(rr[r][1], rr[r][0], 0x05040100u)));
+            const s2 l23 = pk_clip(lo, hi, pl[r][1] + as_s2(perm(rr[r][3], rr[r][2], 0x05040100u)));
+            ldw[r] = perm(as_u32(l23), as_u32(l01), 0x06040200u);
+        }
+#pragma unroll
+        for (int t = 0; t < 2; t++) {
+            const uint32_t r0 = half ? rr[2 + t][0] : rr[t][0], r1 = half ? rr[2 + t][1] : rr[t][1];
+            const uint32_t r2 = half ? rr[2 + t][2] : rr[t][2], r3 = half ? rr[2 + t][3] : rr[t][3];
+            const s2 k01 = pk_clip(lo, hi, pc[t][0] + as_s2(perm(r1, r0, 0x07060302u)));
+            const s2 k23 = pk_clip(lo, hi, pc[t][1] + as_s2(perm(r3, r2, 0x07060302u)));
+            cdw[t] = perm(as_u32(k23), as_u32(k01), 0x06040200u);
+        }
+    } else {
+        int ry[4][4], rc[4][4];
+        const bool over_y = lb_residual_32(yl, qp_y, false, 0, ry), over_c = lb_residual_32(cl, qp_c, true, dc, rc);
+        report_residual_range(fd, over_y || over_c, lane);
+#pragma unroll
+        for (int r = 0; r < 4; r++)
+            ldw[r] = pack4(clip255(pl[r][0].x + ry[r][0]), clip255(pl[r][0].y + ry[r][1]), clip255(pl[r][1].x + ry[r][2]), clip255(pl[r][1].y + ry[r][3]));
+#pragma unroll
+        for (int t = 0; t < 2; t++) {
+            const int c0 = half ? rc[2 + t][0] : rc[t][0], c1 = half ? rc[2 + t][1] : rc[t][1], c2 = half ? rc[2 + t][2] : rc[t][2], c3 = half ? rc[2 + t][3] : rc[t][3];
+            cdw[t] = pack4(clip255(pc[t][0].x + c0), clip255(pc[t][0].y + c1), clip255(pc[t][1].x + c2), clip255(pc[t][1].y + c3));
+        }
+    }
+}
 /* A slot's windows: 21 luma rows at IW_STRIDE, then two planes of 9 chroma rows at IC_STRIDE (1452 bytes), padded to 368 dwords =
  * 16 (mod 32): the sixteen lanes of a slot read dword 13 * (4 * by + r) + bx + const — sixteen different banks of 32, {0..3, 8..11,
  * 20..23, 28..31} + const — and the other slot of the same half-wavefront the other sixteen when the two windows start at the same
@@ -642,17 +762,7 @@ __global__ __launch_bounds__(64, INTER_LB_OCC) void k_recon_inter_lb(const Frame
 {
     __shared__ __attribute__((aligned(16))) uint8_t lds[LB_LDS];
     const FrameDesc &fd = FD_REF(frames, blockIdx.y);
-    /* chunk of this workgroup: the XCD mapping of k_recon_inter (which see), in chunks instead of entries */
-#if INTER_XCD == 1
-    const uint32_t cls8 = blockIdx.x & 7u, per8 = gridDim.x >> 3, rem8 = gridDim.x & 7u;
-    const uint32_t bx_ = cls8 * per8 + (cls8 < rem8 ? cls8 : rem8) + (blockIdx.x >> 3);
-#elif INTER_XCD > 1
-    const uint32_t C_ = INTER_XCD, full_ = (gridDim.x / (8u * C_)) * (8u * C_);
-    const uint32_t b_ = blockIdx.x, o_ = b_ % (8u * C_);
-    const uint32_t bx_ = b_ >= full_ ? b_ : (b_ - o_) + (o_ & 7u) * C_ + (o_ >> 3);
-#else
-    const uint32_t bx_ = blockIdx.x;
-#endif
+    const uint32_t bx_ = inter_chunk_of_block();
     const uint32_t n_uni = fd.n_gen_uni, first = bx_ * INTER_LB_CHUNK;
     if (first >= n_uni) return;
     const uint32_t n_here = min(n_uni - first, (uint32_t)INTER_LB_CHUNK);            /* wave-uniform */
@@ -802,40 +912,7 @@ __global__ __launch_bounds__(64, INTER_LB_OCC) void k_recon_inter_lb(const Frame
             const int o = (((mvx >> 2) - 2) & 15) + 4 * bx, sh = 8 * (o & 3), fx = mvx & 3, fy = mvy & 3;
             const uint8_t *src = lw + 4 * by * IW_STRIDE + (o & ~3);
             const int cls = !on ? -1 : (fx | fy) == 0 ? 0 : fy == 0 ? 1 : fx == 0 ? 2 : (fx != 2 && fy != 2) ? 3 : 4;
-            auto row = [&](uint32_t rw[3], int r, int nd) {      /* dwords 0 .. nd - 1 of window row r */
-                const uint32_t *q = reinterpret_cast<const uint32_t *>(src + r * IW_STRIDE);
-                uint32_t d[4];
-#pragma unroll
-                for (int k = 0; k < 4; k++) if (k <= nd) d[k] = q[k];
-#pragma unroll
-                for (int k = 0; k < 3; k++) rw[k] = k < nd ? (uint32_t)(((unsigned long long)d[k + 1] << 32 | d[k]) >> sh) : 0u;
-            };
-            if (cls == 0) {
-                uint32_t rw[9][3] = {};
-#pragma unroll
-                for (int r = 2; r < 6; r++) row(rw[r], r, 2);
-                lb_luma_whole(rw, pl);
-            } else if (cls == 1) {
-                uint32_t rw[9][3] = {};
-#pragma unroll
-                for (int r = 2; r < 6; r++) row(rw[r], r, 3);
-                lb_luma_hor(rw, fx, pl);
-            } else if (cls == 2) {
-                uint32_t rw[9][3] = {};
-#pragma unroll
-                for (int r = 0; r < 9; r++) row(rw[r], r, 2);
-                lb_luma_ver(rw, fy, pl);
-            } else if (cls == 3) {
-                uint32_t rw[9][3] = {};
-#pragma unroll
-                for (int r = 0; r < 9; r++) row(rw[r], r, (r >= 2 && r <= 6) ? 3 : 2);
-                lb_luma_diag(rw, fx, fy, pl);
-            } else if (cls == 4) {
-                uint32_t rw[9][3] = {};
-#pragma unroll
-                for (int r = 0; r < 9; r++) row(rw[r], r, 3);
-                lb_luma_centre(rw, fx, fy, pl);
-            }
+            lb_luma_from_lds<IW_STRIDE>(src, sh, cls, fx, fy, pl);
         }
         /* ======== chroma: block k8 = 4 * plane + 2 * cby + cbx, rows 2 * half, 2 * half + 1 of it (cxi - cxs = cxi mod 8) ======== */
 #define LB_CHROMA_LANE() const int k8 = b & 7, plane = k8 >> 2, cbx = k8 & 1, cby = (k8 >> 1) & 1, half = b >> 3; (void)cbx
@@ -847,16 +924,7 @@ __global__ __launch_bounds__(64, INTER_LB_OCC) void k_recon_inter_lb(const Frame
             const int mvx = (int16_t)(ge.y & 0xFFFFu), mvy = (int32_t)ge.y >> 16;
             const int ob = ((mvx >> 3) & 7) + 4 * cbx, cfx = mvx & 7, cfy = mvy & 7;
             const uint32_t *q = reinterpret_cast<const uint32_t *>(lc + plane * 9 * IC_STRIDE + (cby * 4 + 2 * half) * IC_STRIDE + (ob & ~3));
-            uint32_t lo[3], hi[3];
-#pragma unroll
-            for (int t = 0; t < 3; t++) {
-                const uint32_t q0 = q[5 * t], q1 = q[5 * t + 1], q2 = q[5 * t + 2];   /* IC_STRIDE = 5 dwords */
-                lo[t] = __builtin_amdgcn_alignbyte(q1, q0, (uint32_t)(ob & 3)); hi[t] = __builtin_amdgcn_alignbyte(q2, q1, (uint32_t)(ob & 3));
-            }
-            const s2 w00 = as_s2((uint32_t)((8 - cfx) * (8 - cfy)) * 0x00010001u), w10 = as_s2((uint32_t)(cfx * (8 - cfy)) * 0x00010001u);
-            const s2 w01 = as_s2((uint32_t)((8 - cfx) * cfy) * 0x00010001u), w11 = as_s2((uint32_t)(cfx * cfy) * 0x00010001u);
-            lb_chroma_row(lo[0], hi[0], lo[1], hi[1], w00, w10, w01, w11, pc[0][0], pc[0][1]);
-            lb_chroma_row(lo[1], hi[1], lo[2], hi[2], w00, w10, w01, w11, pc[1][0], pc[1][1]);
+            lb_chroma_from_lds<IC_STRIDE / 4>(q, ob, cfx, cfy, pc);
         }
 
         /* ======== residual add, clip: the lane's four luma rows and two chroma rows as dwords ======== */
@@ -866,45 +934,7 @@ __global__ __launch_bounds__(64, INTER_LB_OCC) void k_recon_inter_lb(const Frame
         const uint32_t mb = ge.x & 0xFFFFu, coded = ge.w;
         const int qp_y = (int)FJ_GEN_QP_Y(ge.z), qp_c = (int)FJ_GEN_QP_C(ge.z);
         uint32_t ldw[4], cdw[2];
-        if (!any_coded) {                                                            /* wave-uniform: the prediction as it is */
-#pragma unroll
-            for (int r = 0; r < 4; r++) ldw[r] = perm(as_u32(pl[r][1]), as_u32(pl[r][0]), 0x06040200u);
-#pragma unroll
-            for (int t = 0; t < 2; t++) cdw[t] = perm(as_u32(pc[t][1]), as_u32(pc[t][0]), 0x06040200u);
-        } else {
-            const int dc = lb_chroma_dc(dcl[0], dcl[1], k8 & 3, qp_c);
-            if (__ballot((coded & FJ_CODED_WIDE) != 0u) == 0ull) {                    /* wave-uniform: 16 bits hold every intermediate of every slot */
-                uint32_t rr[4][4];
-                lb_residual_pk(yl, cl, qp_y, qp_c, dc, rr);
-                const s2 lo = pk(0), hi = pk(255);
-#pragma unroll
-                for (int r = 0; r < 4; r++) {
-                    const s2 l01 = pk_clip(lo, hi, pl[r][0] + as_s2(perm(rr[r][1], rr[r][0], 0x05040100u)));
-                    const s2 l23 = pk_clip(lo, hi, pl[r][1] + as_s2(perm(rr[r][3], rr[r][2], 0x05040100u)));
-                    ldw[r] = perm(as_u32(l23), as_u32(l01), 0x06040200u);
-                }
-#pragma unroll
-                for (int t = 0; t < 2; t++) {
-                    const uint32_t r0 = half ? rr[2 + t][0] : rr[t][0], r1 = half ? rr[2 + t][1] : rr[t][1];
-                    const uint32_t r2 = half ? rr[2 + t][2] : rr[t][2], r3 = half ? rr[2 + t][3] : rr[t][3];
-                    const s2 k01 = pk_clip(lo, hi, pc[t][0] + as_s2(perm(r1, r0, 0x07060302u)));
-                    const s2 k23 = pk_clip(lo, hi, pc[t][1] + as_s2(perm(r3, r2, 0x07060302u)));
-                    cdw[t] = perm(as_u32(k23), as_u32(k01), 0x06040200u);
-                }
-            } else {                                                                 /* some slot is FJ_CODED_WIDE: 32 bits for all (equal where 16 would do) */
-                int ry[4][4], rc[4][4];
-                const bool over_y = lb_residual_32(yl, qp_y, false, 0, ry), over_c = lb_residual_32(cl, qp_c, true, dc, rc);
-                report_residual_range(fd, over_y || over_c, lane);
-#pragma unroll
-                for (int r = 0; r < 4; r++)
-                    ldw[r] = pack4(clip255(pl[r][0].x + ry[r][0]), clip255(pl[r][0].y + ry[r][1]), clip255(pl[r][1].x + ry[r][2]), clip255(pl[r][1].y + ry[r][3]));
-#pragma unroll
-                for (int t = 0; t < 2; t++) {
-                    const int c0 = half ? rc[2 + t][0] : rc[t][0], c1 = half ? rc[2 + t][1] : rc[t][1], c2 = half ? rc[2 + t][2] : rc[t][2], c3 = half ? rc[2 + t][3] : rc[t][3];
-                    cdw[t] = pack4(clip255(pc[t][0].x + c0), clip255(pc[t][0].y + c1), clip255(pc[t][1].x + c2), clip255(pc[t][1].y + c3));
-                }
-            }
-        }
+        lb_add_residual(fd, lane, any_coded, coded, qp_y, qp_c, yl, cl, dcl, k8 & 3, half, pl, pc, ldw, cdw);
         /* ---- store: after the transpose lane (by, bx) holds row 4 * by + bx of the tile, 16 bytes; lanes b, b ^ 1 hold the left and the right
          * half of two chroma rows, the even one takes the upper row whole, the odd one the lower ---- */
         quad_transpose4(ldw[0], ldw[1], ldw[2], ldw[3], ln);
@@ -920,6 +950,259 @@ __global__ __launch_bounds__(64, INTER_LB_OCC) void k_recon_inter_lb(const Frame
 #undef LB_FRESH
 #undef LB_LANE
 #undef LB_CHROMA_LANE
+}
+
+/* ------------------------------------------------------------------ the quadrant list, a 4x4 block per lane
+ * k_recon_inter_lq replaces k_recon_inter<1> (INTER_LANE_QUADS = 1, the default; 0 keeps the kernel above for A/B runs).  It follows
+ * k_recon_inter_lb; what is sorted and assigned to lanes is the 8x8 QUADRANT, not the macroblock (the quadrants of a macroblock are in two
+ * interpolation classes more often than in one: four macroblocks per group in list order would run four class passes per group).
+ *   Binning.  A single-wavefront workgroup takes INTER_LQ_CHUNK consecutive entries of the quadrant part of the list.  Lane i fetches entry i,
+ *     its four quadrant vectors (vectors 0, 2, 8, 10 of the sixteen in the sparse section) and the ref_slot dword of its record, and leaves
+ *     them in LDS; in rounds of 64, lane j then makes the ITEM of quadrant j & 3 of entry 16 * round + (j >> 2) — four dwords laid out like a
+ *     one-vector list entry: macroblock | quadrant << 16 | reference slot << 24, the vector, the coef_idx word, the coded word — and the
+ *     counting sort of k_recon_inter_lb (ten ballots per round, class first, then quadrant coded / not coded) lays the items out ordered by
+ *     bin.  The sort is stable: the two quadrants of a 16x8 / 8x16 partition stay neighbours.
+ *   Groups.  16 items at a time: lane = (slot 0..15, 4x4 luma block j = 0..3 of the quadrant, raster).  A slot past the end idles.
+ *   Staging.  Per slot one 13 x 32 luma window and two 5 x 16 chroma windows (the quadrant windows of k_recon_inter<1>, rows packed); the four lanes of a slot fetch its
+ *     26 + 20 aligned pieces (7 + 5 loads per lane) and their coefficient blocks (luma block z = 4 * quadrant + j, chroma block `quadrant`
+ *     of plane j >> 1, that plane's DC levels), all before the first use.  Windows that leave the picture: the clamped tile row, spread.
+ *   Arithmetic.  kernels/inter_lane_block.hip.h through the steps shared with k_recon_inter_lb; lanes 2 * plane, 2 * plane + 1 both transform
+ *     the plane's chroma block and keep two rows each.
+ *   Stores.  The two lanes of a block row swap two dwords: the left one stores rows 0, 1 of the pair of blocks, the right one rows 2, 3,
+ *     8 bytes each; the chroma rows are 4 bytes wide. */
+#ifndef INTER_LANE_QUADS
+#define INTER_LANE_QUADS 1
+#endif
+#ifndef INTER_LQ_CHUNK
+#define INTER_LQ_CHUNK 8     /* list entries per workgroup (= wavefront), a multiple of 4 up to 64.  The step with 8 / 12 / 16 / 24 / 32 / 64: 77.4 / 77.5 / 78.0 /
+                                78.5 / 79.1 / 80.5 ms (parent 81.2): a picture has at most 707 of these entries, and more and shorter wavefronts beat fewer class
+                                passes; 4 (one group, nothing to sort) equals 8 within the spread (docs/EXPERIMENTS.md) */
+#endif
+#ifndef INTER_LQ_OCC
+#define INTER_LQ_OCC 4       /* wavefronts per SIMD the register budget is sized for (128 VGPRs; the kernel takes 126).  With the strides below the LDS allows
+                                as many: 16 wavefronts of 9.7 KB in a compute unit's 160 KB */
+#endif
+/* bytes per staged luma row (32 used) and chroma row (16 used).  QW_STRIDE / QC_STRIDE (36 / 20: 11.2 KB per wavefront, 14 per compute unit, 3 per SIMD
+ * by the register budget) cost 0.5-0.6 ms per step against the tight rows, bank conflicts and all */
+#ifndef INTER_LQ_WSTRIDE
+#define INTER_LQ_WSTRIDE 32
+#endif
+#ifndef INTER_LQ_CSTRIDE
+#define INTER_LQ_CSTRIDE 16
+#endif
+static_assert(INTER_LQ_CHUNK % 4 == 0 && INTER_LQ_CHUNK >= 4 && INTER_LQ_CHUNK <= 64, "INTER_LQ_CHUNK");
+constexpr int LQ_ROUNDS = (INTER_LQ_CHUNK + 15) / 16;       /* sort rounds of 64 items */
+constexpr int LQ_W_STRIDE = INTER_LQ_WSTRIDE, LQ_C_STRIDE = INTER_LQ_CSTRIDE;
+static_assert(LQ_W_STRIDE >= 32 && LQ_W_STRIDE % 4 == 0 && LQ_C_STRIDE >= 16 && LQ_C_STRIDE % 4 == 0, "staged rows");
+constexpr int LQ_SLOT_LDS = 13 * LQ_W_STRIDE + 2 * 5 * LQ_C_STRIDE;
+constexpr int LQ_ITEMS_LDS = INTER_LQ_CHUNK * 4 * 16;
+constexpr int LQ_LDS = LQ_ITEMS_LDS + 16 * LQ_SLOT_LDS;
+static_assert(INTER_LQ_CHUNK * 32 + LQ_ROUNDS * 64 <= 16 * LQ_SLOT_LDS, "the fetched entries lie where the windows will");
+__global__ __launch_bounds__(64, INTER_LQ_OCC) void k_recon_inter_lq(const FrameDesc *__restrict__ frames)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t lds[LQ_LDS];
+    const FrameDesc &fd = FD_REF(frames, blockIdx.y);
+    const uint32_t n_quad = fd.n_gen_quad, first = inter_chunk_of_block() * INTER_LQ_CHUNK;
+    if (first >= n_quad) return;
+    const uint32_t n_here = min(n_quad - first, (uint32_t)INTER_LQ_CHUNK), n_items = 4u * n_here;      /* wave-uniform */
+    const int lane = threadIdx.x & 63;
+    const int wmb = fd.wmb, W = wmb * 16, H = fd.hmb * 16, CW = W >> 1, CH = H >> 1;
+    const uint32_t frame_bytes = (uint32_t)wmb * fd.hmb * (uint32_t)TILE;
+    const H264K_GLOBAL uint8_t *ref0 = (const H264K_GLOBAL uint8_t *)fd.slot[0];
+    const H264K_GLOBAL uint8_t *cf = (const H264K_GLOBAL uint8_t *)fd.coefs;
+    H264K_GLOBAL uint8_t *cur = (H264K_GLOBAL uint8_t *)fd.cur;
+
+    /* ---- fetch: lane i < n_here holds entry n_gen_uni + first + i ---- */
+    {
+        uint4 *raw_e = reinterpret_cast<uint4 *>(lds + LQ_ITEMS_LDS), *raw_mv = raw_e + INTER_LQ_CHUNK;
+        uint32_t *raw_ref = reinterpret_cast<uint32_t *>(raw_mv + INTER_LQ_CHUNK);
+        if ((uint32_t)lane < n_here) {
+            const uint4 e = ld16g((const H264K_GLOBAL uint8_t *)fd.gen + 16u * (fd.n_gen_uni + first + (uint32_t)lane));
+            /* the entry's vector fields hold the index of the macroblock's sixteen vectors (x | y << 16 each, raster) in the sparse section */
+            const H264K_GLOBAL uint32_t *mvc = (const H264K_GLOBAL uint32_t *)fd.mvx + 16 * (size_t)e.y;
+            const uint32_t refs = *(const H264K_GLOBAL uint32_t *)((const H264K_GLOBAL uint8_t *)fd.recs + sizeof(FjMbRec) * (size_t)(e.x & 0xFFFFu) + offsetof(FjMbRec, ref_slot));
+            raw_e[lane] = e;
+            raw_mv[lane] = make_uint4(mvc[0], mvc[2], mvc[8], mvc[10]);
+            raw_ref[lane] = refs;
+        }
+        wave_sync();
+        /* ---- bin: item (round, lane j) = quadrant j & 3 of entry 16 * round + (j >> 2), so the item order is the list order ---- */
+        uint4 it[LQ_ROUNDS];
+        int bin[LQ_ROUNDS];
+        bool have[LQ_ROUNDS];
+#pragma unroll
+        for (int r = 0; r < LQ_ROUNDS; r++) {
+            const uint32_t ent = 16u * r + ((uint32_t)lane >> 2), q = (uint32_t)lane & 3u;
+            have[r] = ent < n_here;
+            const uint4 e = raw_e[ent], m4 = raw_mv[ent];
+            const uint32_t mv = q == 0u ? m4.x : q == 1u ? m4.y : q == 2u ? m4.z : m4.w;
+            it[r] = make_uint4((e.x & 0xFFFFu) | (q << 16) | (((raw_ref[ent] >> (8u * q)) & 255u) << 24), mv, e.z, e.w);
+            const int fx = (int)(mv & 3u), fy = (int)((mv >> 16) & 3u);
+            const int cls = (fx | fy) == 0 ? 0 : fy == 0 ? 1 : fx == 0 ? 2 : (fx != 2 && fy != 2) ? 3 : 4;
+            bin[r] = have[r] ? 2 * cls + ((e.w & lq_coded_mask(q)) ? 1 : 0) : 10;
+        }
+        uint32_t rank[LQ_ROUNDS] = {}, seen = 0;
+#pragma unroll
+        for (int k = 0; k < 10; k++)
+#pragma unroll
+            for (int r = 0; r < LQ_ROUNDS; r++) {
+                const unsigned long long m = __ballot(bin[r] == k);
+                const uint32_t before = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+                if (bin[r] == k) rank[r] = seen + before;
+                seen += (uint32_t)__popcll(m);
+            }
+        wave_sync();
+#pragma unroll
+        for (int r = 0; r < LQ_ROUNDS; r++)
+            if (have[r]) *reinterpret_cast<uint4 *>(lds + 16u * rank[r]) = it[r];     /* rank < n_items */
+        wave_sync();
+    }
+
+    /* the four phases of k_recon_inter_lb's body, each deriving what it needs from the lane number and the item again (which see) */
+#define LQ_FRESH() asm volatile("" : "+v"(ln), "+v"(ge.x), "+v"(ge.y), "+v"(ge.z), "+v"(ge.w))
+#define LQ_LANE() const int s = ln >> 2, j = ln & 3, jbx = j & 1, jby = j >> 1, qd = (int)((ge.x >> 16) & 3u), plane = j >> 1, half = j & 1; \
+                  uint8_t *lw = lds + LQ_ITEMS_LDS + s * LQ_SLOT_LDS, *lc = lw + 13 * LQ_W_STRIDE; (void)jbx; (void)jby; (void)qd; (void)plane; (void)half; (void)lc
+#pragma unroll 1
+    for (uint32_t g = 0; g < n_items; g += 16) {
+        int ln = lane;
+        const bool on = g + (uint32_t)(lane >> 2) < n_items;                          /* g + slot <= 4 * INTER_LQ_CHUNK - 1 */
+        uint4 ge = *reinterpret_cast<const uint4 *>(lds + 16u * (g + (uint32_t)(lane >> 2)));
+        if (!on) ge = make_uint4(0u, 0u, 0u, 0u);
+        uint32_t yl[8] = { 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u }, cl[8] = { 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u }, dcl[2] = { 0u, 0u };
+        const bool any_coded = __ballot((ge.w & lq_coded_mask((ge.x >> 16) & 3u)) != 0u) != 0ull;       /* wave-uniform */
+      {                                              /* ======== loads and staging ======== */
+        LQ_FRESH();
+        LQ_LANE();
+        const uint32_t mb = ge.x & 0xFFFFu, refoff = (ge.x >> 24) * frame_bytes;
+        const int mvx = (int16_t)(ge.y & 0xFFFFu), mvy = (int32_t)ge.y >> 16;
+        const uint32_t coded = ge.w;
+        const int mby = wmb == 1 ? (int)mb : (int)__umulhi(mb, fd.wmb_magic), mbx = (int)mb - mby * wmb;
+        const int xi = mbx * 16 + 8 * (qd & 1) + (mvx >> 2) - 2, yi = mby * 16 + 8 * (qd >> 1) + (mvy >> 2) - 2, xs = (xi >> 4) << 4;
+        const int cxi = mbx * 8 + 4 * (qd & 1) + (mvx >> 3), cyi = mby * 8 + 4 * (qd >> 1) + (mvy >> 3), cxs = (cxi >> 3) << 3;
+        const bool lfast = on && xi >= 0 && xi + 13 <= W && yi >= 0 && yi + 13 <= H;
+        const bool cfast = on && cxi >= 0 && cxi + 5 <= CW && cyi >= 0 && cyi + 5 <= CH;
+
+        /* ---- every global load of the group, back to back; every address clamped into the picture, also where the lane is off (it then
+         * reads the first bytes of slot 0 and drops them).  Edge windows: k_recon_inter_lb, which see ---- */
+        uint4 vl[7];
+        uint2 vc[5];
+        bool l_on[7], c_on[5];
+        const bool any_edge = __ballot(on && !(lfast && cfast)) != 0ull;              /* wave-uniform */
+#pragma unroll
+        for (int i = 0; i < 7; i++) {                /* luma piece p = 2 * row + tile of the slot's window, p = j + 4 * i < 26 */
+            const int p = j + 4 * i, lr = p >> 1, lk = p & 1;
+            const int lx = clip3(0, W - 16, xs + 16 * lk), yy = clip3(0, H - 1, yi + lr);
+            /* (the window's 13 columns reach into the second tile only when they start behind the first four columns of the first) */
+            l_on[i] = on && p < 26 && (lk == 0 || xi - xs >= 4);
+            const uint32_t off = refoff + (uint32_t)((yy >> 4) * wmb + (lx >> 4)) * (uint32_t)TILE + (uint32_t)((yy & 15) << 4);
+            vl[i] = ld16g(ref0 + (l_on[i] ? off : 0u));
+        }
+#pragma unroll
+        for (int i = 0; i < 5; i++) {                /* chroma piece p = 10 * plane + 2 * row + tile, p = j + 4 * i < 20 */
+            const int p = j + 4 * i, cp = p >= 10, rem = cp ? p - 10 : p, cr = rem >> 1, ck = rem & 1;
+            const int cx = clip3(0, CW - 8, cxs + 8 * ck), yy = clip3(0, CH - 1, cyi + cr);
+            c_on[i] = on;
+            const uint32_t off = refoff + (uint32_t)((yy >> 3) * wmb + (cx >> 3)) * (uint32_t)TILE + (uint32_t)(T_CB + (cp << 6) + ((yy & 7) << 3));
+            vc[i] = ld8g(ref0 + (c_on[i] ? off : 0u));
+        }
+        /* coefficient blocks: luma block z = 4 * quadrant + j (H.264 block order), chroma block `quadrant` of the lane's plane, its DC levels */
+        if (any_coded) {
+            const int z = 4 * qd + j, k8 = 4 * plane + qd;
+            const uint32_t cidx = FJ_GEN_COEF_IDX(ge.z), nl = (uint32_t)__popc(coded & 0xFFFFu), has_cdc = (coded >> 25) & 1u;
+            const bool ybit = (coded >> z) & 1u, cbit = (coded >> (16 + k8)) & 1u;
+            const uint32_t yoff = 32u * (cidx + (uint32_t)__popc(coded & ((1u << z) - 1u)));
+            const uint32_t coff = 32u * (cidx + nl + has_cdc + (uint32_t)__popc((coded >> 16) & ((1u << k8) - 1u)));
+            const uint32_t doff = 32u * (cidx + nl) + 8u * (uint32_t)plane;
+            const H264K_GLOBAL uint8_t *py = ybit ? cf + yoff : ref0, *pc = cbit ? cf + coff : ref0, *pd = has_cdc ? cf + doff : ref0;
+            const uint4 y0 = ld16g(py), y1 = ld16g(py + 16), c0 = ld16g(pc), c1 = ld16g(pc + 16);
+            const uint2 d0 = ld8g(pd);
+            const uint32_t ym = ybit ? ~0u : 0u, cm = cbit ? ~0u : 0u, dm = has_cdc ? ~0u : 0u;
+            yl[0] = y0.x & ym; yl[1] = y0.y & ym; yl[2] = y0.z & ym; yl[3] = y0.w & ym; yl[4] = y1.x & ym; yl[5] = y1.y & ym; yl[6] = y1.z & ym; yl[7] = y1.w & ym;
+            cl[0] = c0.x & cm; cl[1] = c0.y & cm; cl[2] = c0.z & cm; cl[3] = c0.w & cm; cl[4] = c1.x & cm; cl[5] = c1.y & cm; cl[6] = c1.z & cm; cl[7] = c1.w & cm;
+            dcl[0] = d0.x & dm; dcl[1] = d0.y & dm;
+        }
+        /* ---- stage ---- */
+        if (any_edge) {
+#pragma unroll
+            for (int i = 0; i < 7; i++) {
+                const int p = j + 4 * i, lk = p & 1, lx = xs + 16 * lk;
+                const uint32_t first = (vl[i].x & 255u) * 0x01010101u, last = (vl[i].w >> 24) * 0x01010101u;
+                if (lx < 0) vl[i] = make_uint4(first, first, first, first);
+                else if (lx >= W) vl[i] = make_uint4(last, last, last, last);
+            }
+#pragma unroll
+            for (int i = 0; i < 5; i++) {
+                const int p = j + 4 * i, ck = p & 1, cx = cxs + 8 * ck;                /* (10 is even: the tile of piece p is p & 1 in both planes) */
+                const uint32_t first = (vc[i].x & 255u) * 0x01010101u, last = (vc[i].y >> 24) * 0x01010101u;
+                if (cx < 0) vc[i] = make_uint2(first, first);
+                else if (cx >= CW) vc[i] = make_uint2(last, last);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 7; i++) {
+            const int p = j + 4 * i, lr = p >> 1, lk = p & 1;
+            if (l_on[i]) {
+                uint32_t *d32 = reinterpret_cast<uint32_t *>(lw + lr * LQ_W_STRIDE + 16 * lk);
+                d32[0] = vl[i].x; d32[1] = vl[i].y; d32[2] = vl[i].z; d32[3] = vl[i].w;
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 5; i++) {
+            const int p = j + 4 * i, cp = p >= 10, rem = cp ? p - 10 : p, cr = rem >> 1, ck = rem & 1;
+            if (c_on[i]) {
+                uint32_t *d32 = reinterpret_cast<uint32_t *>(lc + cp * 5 * LQ_C_STRIDE + cr * LQ_C_STRIDE + 8 * ck);
+                d32[0] = vc[i].x; d32[1] = vc[i].y;
+            }
+        }
+        wave_sync();
+      }
+
+        /* ======== luma: window rows 4 * jby .. + 8, bytes o .. o + 11 with o = xi mod 16 + 4 * jbx (the macroblock's own 16 * mbx drops out) ======== */
+        s2 pl[4][2];
+#pragma unroll
+        for (int r = 0; r < 4; r++) pl[r][0] = pl[r][1] = pk(0);
+        {
+            LQ_FRESH();
+            LQ_LANE();
+            const int mvx = (int16_t)(ge.y & 0xFFFFu), mvy = (int32_t)ge.y >> 16;
+            const int o = lq_window_byte(qd, mvx) + 4 * jbx, sh = 8 * (o & 3), fx = mvx & 3, fy = mvy & 3;
+            const uint8_t *src = lw + 4 * jby * LQ_W_STRIDE + (o & ~3);
+            const int cls = !on ? -1 : (fx | fy) == 0 ? 0 : fy == 0 ? 1 : fx == 0 ? 2 : (fx != 2 && fy != 2) ? 3 : 4;
+            lb_luma_from_lds<LQ_W_STRIDE>(src, sh, cls, fx, fy, pl);
+        }
+        /* ======== chroma: 4x4 block `quadrant` of the lane's plane, rows 2 * half, 2 * half + 1 of it ======== */
+        s2 pc[2][2];
+        {
+            LQ_FRESH();
+            LQ_LANE();
+            const int mvx = (int16_t)(ge.y & 0xFFFFu), mvy = (int32_t)ge.y >> 16;
+            const int ob = lq_chroma_byte(qd, mvx), cfx = mvx & 7, cfy = mvy & 7;
+            const uint32_t *q = reinterpret_cast<const uint32_t *>(lc + plane * 5 * LQ_C_STRIDE + 2 * half * LQ_C_STRIDE + (ob & ~3));
+            lb_chroma_from_lds<LQ_C_STRIDE / 4>(q, ob, cfx, cfy, pc);
+        }
+
+        /* ======== residual add, clip, exchange, store ======== */
+        LQ_FRESH();
+        LQ_LANE();
+        const uint32_t mb = ge.x & 0xFFFFu, coded = ge.w;
+        const int qp_y = (int)FJ_GEN_QP_Y(ge.z), qp_c = (int)FJ_GEN_QP_C(ge.z);
+        uint32_t ldw[4], cdw[2];
+        lb_add_residual(fd, lane, any_coded, coded, qp_y, qp_c, yl, cl, dcl, qd, half, pl, pc, ldw, cdw);
+        uint32_t r0[2], r1[2];
+        lq_pair_rows(ldw, (uint32_t)quad_xor1((int)(jbx ? ldw[0] : ldw[2])), (uint32_t)quad_xor1((int)(jbx ? ldw[1] : ldw[3])), jbx, r0, r1);
+        H264K_GLOBAL uint8_t *T = cur + (size_t)mb * TILE;
+        if (on) {
+            H264K_GLOBAL uint8_t *L = T + lq_luma_store_offset(qd, j);
+            *(H264K_GLOBAL u32x2 *)L = (u32x2){ r0[0], r0[1] };
+            *(H264K_GLOBAL u32x2 *)(L + 16) = (u32x2){ r1[0], r1[1] };
+            H264K_GLOBAL uint8_t *C = T + lq_chroma_store_offset(qd, j);
+            *(H264K_GLOBAL uint32_t *)C = cdw[0];
+            *(H264K_GLOBAL uint32_t *)(C + 8) = cdw[1];
+        }
+        wave_sync();          /* the staged windows are overwritten by the next group's */
+    }
+#undef LQ_FRESH
+#undef LQ_LANE
 }
 
 
