@@ -28,7 +28,13 @@
  *                                             order of h264bsdConceal (:124-260) arrives in the frame job
  * (the concealment is pinned twice: tests/test_damaged_streams.py against the compiled reference on damaged streams, which
  *  reach what they happen to lose; tests/test_concealed_jobs.py on chosen neighbour masks and border samples — against a plain
- *  integer model on hand-built jobs, and against the compiled reference on all-I_PCM streams that leave a slice group out)
+ *  integer model on hand-built jobs, and against the compiled reference on all-I_PCM streams that leave a slice group out;
+ *  intra prediction and the intra residual likewise: tests/test_oracle_stage_pins.py against the reference's three prediction
+ *  functions, under every availability mask on random modes and on every enumerated (block, mode) cell of Intra4x4, with no
+ *  residual; tests/test_intra_jobs.py against a plain integer model, tests/intra_model.py, on hand-built jobs that hold every
+ *  cell, the above-right rule of block 5, both luma DC and the chroma DC scalings, FJ_CODED_LUMA_DC_RAW, residuals at both ends
+ *  of [-512, 511] and both clips; the transforms themselves against h264bsdProcessBlock / LumaDc / ChromaDc in
+ *  tests/test_oracle_vs_ref.py)
  * oracle_deblock_census() is oracle_deblock() that also counts which decisions the filter takes (strength rules, gates, clips,
  * saturation): tests/test_structured_jobs.py holds the hand-built test pictures to taking every one of them.
  * Known, deliberate gap: the reference turns a residual outside [-512,511] into a decode error

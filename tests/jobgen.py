@@ -8,7 +8,9 @@ per-MB deblocking flags.  The derived sections (schedules) are completed by the 
 h264bsdmiJobFinalize(), i.e. by the same code the parser uses.
 The second half of the file gives pictures structure on purpose (patch_typed, patch_sub8x8, patch_coherent, patch_copy_runs,
 patch_window_edges, build_job(smooth=...)): what white-noise motion and content never produce.  The end of it loses macroblocks
-(patch_lost, chosen_samples, build_job(pcm=...)): concealed macroblocks under chosen neighbour masks over chosen border samples."""
+(patch_lost, chosen_samples, build_job(pcm=...)): concealed macroblocks under chosen neighbour masks over chosen border samples;
+and it describes intra macroblocks one by one (build_job(chosen=...), put_chosen, border_samples, intra_to_range): chosen kind,
+availability, modes, QPs and coefficient blocks next to chosen border samples."""
 import ctypes
 import struct
 
@@ -131,7 +133,7 @@ def _pcm_gradient(rng, ramps, mbx, mby):
 
 
 def build_job(lib, rng, wmb, hmb, cur_slot, n_slots, ref_slots, *, p_inter=0.6, p_pcm=0.03, mv_range=None, any_deblock=True, patch=None, near_bound=False,
-              smooth=False, extra_blocks=0, pcm=None):
+              smooth=False, extra_blocks=0, pcm=None, chosen=None):
     """One random picture.  ref_slots: slots holding valid pictures (empty -> intra only).
     patch(recs, mvs): called on the records [n][32] and the dense vectors [n][16][2] before the job is finished — a finished
     job carries its vectors in the records and the sparse section (framejob.h), the dense array here is only h264bsdmiJobFinalize's input.
@@ -139,7 +141,9 @@ def build_job(lib, rng, wmb, hmb, cur_slot, n_slots, ref_slots, *, p_inter=0.6, 
     that neighbouring samples usually pass the alpha / beta gates at mid QPs.
     extra_blocks: that many more coefficient blocks (one level of +-1 each) behind the last macroblock's; patch is then called as
     patch(recs, mvs, first) with the index of the first of them, for macroblocks it wants to give a coded block (coef_idx, bytes 12..15).
-    pcm: {macroblock address: 384 samples (Y[256], Cb[64], Cr[64], raster)} — these macroblocks are I_PCM with exactly those samples."""
+    pcm: {macroblock address: 384 samples (Y[256], Cb[64], Cr[64], raster)} — these macroblocks are I_PCM with exactly those samples.
+    chosen: {macroblock address: description of an Intra4x4 / Intra16x16 macroblock (put_chosen)} — these macroblocks are exactly that.
+    Neither pcm nor chosen changes what a seed draws for the other macroblocks' records."""
     coef_block = _coef_block_smooth if smooth else _coef_block
     ramps = smooth if isinstance(smooth, list) else draw_ramps(rng) if smooth else None
     n = wmb * hmb
@@ -173,6 +177,8 @@ def build_job(lib, rng, wmb, hmb, cur_slot, n_slots, ref_slots, *, p_inter=0.6, 
             r[0], r[1], r[2] = 3, 0, QPC[min(51, max(0, cqp))]
             buf[coef_off + 32 * nblk: coef_off + 32 * nblk + 384] = np.asarray(pcm[a], dtype=np.uint8).reshape(384)
             nblk += 12
+        elif chosen is not None and a in chosen:
+            coded, nblk = put_chosen(r, chosen[a], coefs, nblk, x, y, wmb)
         elif ref_slots and u < p_inter:
             r[0] = 0                                                   # inter
             style = rng.random()
@@ -664,3 +670,80 @@ def patch_lost(wmb, hmb, decoded, ref_slot=None):
                 recs[a, 0] = FJ_MB_CONCEAL_P
                 recs[a, 16:20] = ref_slot
     return patch
+
+
+# ------------------------------------------------------------------ chosen intra macroblocks (build_job(chosen=...), border_samples)
+# Random jobs draw intra macroblocks with small levels under whatever availability and modes come up.  put_chosen writes the record
+# and the coefficient blocks of ONE described macroblock; border_samples gives its I_PCM neighbours the samples that the
+# prediction arithmetic is sensitive to; intra_to_range scales levels against tests/intra_model.py's own residual.
+BORDERS = ["noise", "ramp", "flat0", "flat255", "step_up", "step_down"]
+
+
+def natural_avail(x, y, wmb):
+    return (1 if x > 0 else 0) | (2 if y > 0 else 0) | (4 if y > 0 and x + 1 < wmb else 0) | (8 if x > 0 and y > 0 else 0)
+
+
+def put_chosen(r, d, coefs, nblk, x, y, wmb):
+    """Write the record r (coef_idx is set already) and the coefficient blocks of the macroblock that the dict d describes; returns
+    (coded, nblk).  Keys: kind (1 Intra4x4, 2 Intra16x16); avail (default: what the position gives); qp_y, cqp_off (qp_c follows);
+    modes (16, block order) / l16; chroma; luma {z: 16 levels, raster}; luma_dc (16 levels) with raw=True for FJ_CODED_LUMA_DC_RAW;
+    chroma_dc (8 levels); chroma_ac {k: 16 levels}.  Nothing is checked here: tests/intra_model.py rejects what is not valid."""
+    qp, off = int(d.get("qp_y", 26)), int(d.get("cqp_off", 0))
+    r[0], r[1], r[2] = d["kind"], qp, QPC[min(51, max(0, qp + off))]
+    r[20] = np.int8(off).view(np.uint8)
+    r[3] = d.get("avail", natural_avail(x, y, wmb))
+    r[4] = (int(d.get("l16", 0)) if d["kind"] == 2 else 0) | (int(d.get("chroma", 0)) << 2)
+    r[24:32] = 0
+    if d["kind"] == 1:
+        for z, m in enumerate(d["modes"]): r[24 + (z >> 1)] |= m << ((z & 1) * 4)
+    coded = 0
+
+    def put(levels, bit):
+        nonlocal nblk, coded
+        blk = np.zeros(16, dtype=np.int16)
+        blk[:len(levels)] = levels
+        coefs[16 * nblk:16 * nblk + 16] = blk
+        nblk += 1
+        coded |= bit
+    if d["kind"] == 2 and d.get("luma_dc") is not None:
+        put(d["luma_dc"], (1 << 24) | ((1 << 26) if d.get("raw") else 0))
+    for z in sorted(d.get("luma", {})): put(d["luma"][z], 1 << z)
+    if d.get("chroma_dc") is not None: put(d["chroma_dc"], 1 << 25)
+    for k in sorted(d.get("chroma_ac", {})): put(d["chroma_ac"][k], 1 << (16 + k))
+    return coded, nblk
+
+
+def border_samples(content, rng):
+    """384 samples of an I_PCM neighbour of a chosen intra macroblock.  step_up: 255 in the lower right quadrant and 0 elsewhere, so that
+    the last row and the last column are each half 0, half 255 — next to a corner macroblock of flat0 the largest H and V of plane
+    prediction; step_down: its complement (next to flat255 the most negative ones); ramp: a level and slopes of up to 3 per sample"""
+    out = []
+    for size in (16, 8, 8):
+        yy, xx = np.mgrid[0:size, 0:size]
+        if content == "noise": v = rng.integers(0, 256, (size, size))
+        elif content == "ramp": v = int(rng.integers(0, 256)) + int(rng.integers(-3, 4)) * (xx - size // 2) + int(rng.integers(-3, 4)) * (yy - size // 2)
+        elif content == "flat0": v = np.zeros((size, size), int)
+        elif content == "flat255": v = np.full((size, size), 255)
+        elif content == "step_up": v = 255 * ((xx >= size // 2) & (yy >= size // 2))
+        elif content == "step_down": v = 255 - 255 * ((xx >= size // 2) & (yy >= size // 2))
+        else: raise ValueError(content)
+        out.append(np.clip(v, 0, 255).astype(np.uint8).ravel())
+    return np.concatenate(out)
+
+
+def intra_to_range(levels, qp, towards, dc=None):
+    """The analogue of _to_bound for intra macroblocks: the 16 levels times the largest factor (in steps of 1/16) at which
+    tests/intra_model.py's own residual of the block stays inside [-512, 511] and its extreme in the direction `towards` (-1: the
+    minimum, +1: the maximum) comes as close to that end as the level grid allows.  The levels come back as Python ints."""
+    import intra_model
+    base = [int(v) for v in levels]
+    best = None
+    for k in range(1, 64 * 16):
+        lv = [max(-2047, min(2047, (v * k) // 16 if v >= 0 else -((-v * k) // 16))) for v in base]
+        try:
+            r = intra_model.residual_block(lv, qp, dc)
+        except ValueError:
+            break
+        reach = -min(map(min, r)) if towards < 0 else max(map(max, r))
+        if best is None or reach >= best[0]: best = (reach, lv)
+    return best[1] if best else base

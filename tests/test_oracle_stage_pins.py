@@ -21,7 +21,7 @@ import pytest
 
 from oracle import pyoracle
 import h264bsd_amd
-from jobgen import I_4x4, I_16x16_BASE, I_PCM, QPC, Z_X, Z_Y, _i4_modes, _patch_partitions, build_job
+from jobgen import I_4x4, I_16x16_BASE, I_PCM, QPC, Z_X, Z_Y, _i4_modes, _i4_ok, _patch_partitions, build_job
 
 
 class MvT(ctypes.Structure):             # reference src/h264bsd_macroblock_layer.h:117-122
@@ -146,13 +146,50 @@ def _prev_rem(modes_z, avail):
     return prev, rem
 
 
+def _predict_both(ref, lib, rng, avail, kind, m16, cmode, i4):
+    """(the macroblock as the reference's three prediction functions give it, as oracle_recon() gives it) for one case of _intra_blob"""
+    wmb, hmb = 3, 2
+    blob = _intra_blob(lib, rng, kind, avail, m16, cmode, i4)
+    dpb = pyoracle.OracleDpb(blob)
+    frame = dpb.decode(blob, deblock=False).copy()
+    want = _mb_from_frame(frame, wmb, hmb, 1, 1)
+    above, left = _neighbour_pels(frame, wmb, hmb, 1, 1)
+    mbs = (MbStorage * 6)()
+    for a in range(6): mbs[a].mbType = I_PCM; mbs[a].sliceId = 0
+    cur = mbs[4]
+    cur.mbType = I_4x4 if kind == 1 else I_16x16_BASE + m16
+    if avail & 1: cur.mbA = ctypes.pointer(mbs[3])
+    if avail & 2: cur.mbB = ctypes.pointer(mbs[1])
+    if avail & 4: cur.mbC = ctypes.pointer(mbs[2])
+    if avail & 8: cur.mbD = ctypes.pointer(mbs[0])
+    layer = MacroblockLayer()
+    layer.mbType = cur.mbType
+    layer.mbPred.intraChromaPredMode = cmode
+    data = np.zeros(384 + 64, dtype=np.uint8)
+    if kind == 1:
+        prev, rem = _prev_rem(i4, avail)
+        for z in range(16):
+            layer.mbPred.prevIntra4x4PredModeFlag[z] = prev[z]; layer.mbPred.remIntra4x4PredMode[z] = rem[z]
+        rc = ref.h264bsdIntra4x4Prediction(ctypes.byref(cur), ctypes.c_void_p(data.ctypes.data), ctypes.byref(layer),
+                                           ctypes.c_void_p(above.ctypes.data), ctypes.c_void_p(left.ctypes.data), 0)
+        assert rc == 0
+        assert [cur.intra4x4PredMode[z] for z in range(16)] == i4, "the reference derived other modes than the job carries"
+    else:
+        rc = ref.h264bsdIntra16x16Prediction(ctypes.byref(cur), ctypes.c_void_p(data.ctypes.data), ctypes.byref(layer.residual.level),
+                                             ctypes.c_void_p(above.ctypes.data), ctypes.c_void_p(left.ctypes.data), 0)
+        assert rc == 0
+    level16 = ctypes.cast(ctypes.byref(layer.residual.level, 16 * 16 * 4), ctypes.c_void_p)
+    rc = ref.h264bsdIntraChromaPrediction(ctypes.byref(cur), ctypes.c_void_p(data.ctypes.data + 256), level16,
+                                          ctypes.c_void_p(above.ctypes.data + 21), ctypes.c_void_p(left.ctypes.data + 16), cmode, 0)
+    assert rc == 0
+    return data[:384], want
+
+
 @pytest.mark.parametrize("avail", range(16))
 def test_intra_prediction_matches_the_reference_functions(ref, built, avail):
     """every availability pattern of (A, B, C, D) x every Intra16x16 / chroma / Intra4x4 mode it allows"""
-    orc = pyoracle.oracle_lib()
     lib = built.lib()
     rng = np.random.default_rng(1000 + avail)
-    wmb, hmb = 3, 2
     cases = []
     l16 = [2] + ([0] if avail & 2 else []) + ([1] if avail & 1 else []) + ([3] if (avail & 11) == 11 else [])
     cm = [0] + ([1] if avail & 1 else []) + ([2] if avail & 2 else []) + ([3] if (avail & 11) == 11 else [])
@@ -161,43 +198,37 @@ def test_intra_prediction_matches_the_reference_functions(ref, built, avail):
     for _ in range(24): cases.append((1, 0, int(rng.choice(cm)), _i4_modes(rng, avail)))
     seen_modes = set()
     for kind, m16, cmode, i4 in cases:
-        blob = _intra_blob(lib, rng, kind, avail, m16, cmode, i4)
-        dpb = pyoracle.OracleDpb(blob)
-        frame = dpb.decode(blob, deblock=False).copy()
-        want = _mb_from_frame(frame, wmb, hmb, 1, 1)
-        above, left = _neighbour_pels(frame, wmb, hmb, 1, 1)
-        mbs = (MbStorage * 6)()
-        for a in range(6): mbs[a].mbType = I_PCM; mbs[a].sliceId = 0
-        cur = mbs[4]
-        cur.mbType = I_4x4 if kind == 1 else I_16x16_BASE + m16
-        if avail & 1: cur.mbA = ctypes.pointer(mbs[3])
-        if avail & 2: cur.mbB = ctypes.pointer(mbs[1])
-        if avail & 4: cur.mbC = ctypes.pointer(mbs[2])
-        if avail & 8: cur.mbD = ctypes.pointer(mbs[0])
-        layer = MacroblockLayer()
-        layer.mbType = cur.mbType
-        layer.mbPred.intraChromaPredMode = cmode
-        data = np.zeros(384 + 64, dtype=np.uint8)
-        if kind == 1:
-            prev, rem = _prev_rem(i4, avail)
-            for z in range(16):
-                layer.mbPred.prevIntra4x4PredModeFlag[z] = prev[z]; layer.mbPred.remIntra4x4PredMode[z] = rem[z]
-                seen_modes.add(i4[z])
-            rc = ref.h264bsdIntra4x4Prediction(ctypes.byref(cur), ctypes.c_void_p(data.ctypes.data), ctypes.byref(layer),
-                                               ctypes.c_void_p(above.ctypes.data), ctypes.c_void_p(left.ctypes.data), 0)
-            assert rc == 0
-            assert [cur.intra4x4PredMode[z] for z in range(16)] == i4, "the reference derived other modes than the job carries"
-        else:
-            rc = ref.h264bsdIntra16x16Prediction(ctypes.byref(cur), ctypes.c_void_p(data.ctypes.data), ctypes.byref(layer.residual.level),
-                                                 ctypes.c_void_p(above.ctypes.data), ctypes.c_void_p(left.ctypes.data), 0)
-            assert rc == 0
-        level16 = ctypes.cast(ctypes.byref(layer.residual.level, 16 * 16 * 4), ctypes.c_void_p)
-        rc = ref.h264bsdIntraChromaPrediction(ctypes.byref(cur), ctypes.c_void_p(data.ctypes.data + 256), level16,
-                                              ctypes.c_void_p(above.ctypes.data + 21), ctypes.c_void_p(left.ctypes.data + 16), cmode, 0)
-        assert rc == 0
-        got = data[:384]
+        got, want = _predict_both(ref, lib, rng, avail, kind, m16, cmode, i4)
+        if kind == 1: seen_modes |= set(i4)
         assert np.array_equal(got, want), f"kind {kind} mode {m16} chroma {cmode} i4 {i4} avail {avail}: {np.count_nonzero(got != want)} samples differ"
     if avail == 15: assert seen_modes == set(range(9))
+
+
+@pytest.mark.parametrize("avail", range(16))
+def test_intra4x4_prediction_matches_the_reference_on_every_enumerated_cell(ref, built, avail):
+    """The 24 random draws per mask above leave cells out (block 5 with B available and C missing under modes 3 and 7 among them).
+    Here picture m gives every block mode m where its neighbours allow it and DC elsewhere, as the cells4 family of
+    tests/test_intra_jobs.py does: every (block, mode) that the mask allows is compared with the reference's functions, over two
+    draws of the I_PCM neighbours."""
+    import test_intra_jobs
+    lib = built.lib()
+    rng = np.random.default_rng(2000 + avail)
+    cm = [0] + ([1] if avail & 1 else []) + ([2] if avail & 2 else []) + ([3] if (avail & 11) == 11 else [])
+    seen = set()
+    for draw in range(2):
+        for m in range(9):
+            i4 = [m if m in _i4_ok(avail, z) else 2 for z in range(16)]
+            got, want = _predict_both(ref, lib, rng, avail, 1, 0, cm[(m + draw) % len(cm)], i4)
+            seen |= {(z, i4[z]) for z in range(16)}
+            assert np.array_equal(got, want), f"mode {m} where allowed, avail {avail}: {np.count_nonzero(got != want)} samples differ"
+    cells = {(c[1], c[2]) for c in test_intra_jobs.enumerate_cells() if c[0] == "i4" and c[3:] == _block_sees(avail, c[1])}
+    assert seen == cells and len(cells) >= 16
+
+
+def _block_sees(avail, z):
+    """(left, top, corner, above-right) of block z under a mask, as the cells of tests/test_intra_jobs.py name them"""
+    import intra_model
+    return intra_model.block_availability(z, avail)
 
 
 # ------------------------------------------------------------------ deblocking
