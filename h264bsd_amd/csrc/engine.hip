@@ -8,10 +8,10 @@
  *     k_copy            grid (32, N)          x 256  whole-sample copy macroblocks, one run of <= 8 tiles per wavefront; on a HIP stream of its own
  *                                                    next to the inter kernels (single-lane engine and replay sets: SideLane), joined before k_frame_intra
  *     k_recon_inter_lb  grid (n_uni/32, N)    x 64   inter macroblocks with one motion vector: a chunk of 32 list entries per wavefront, binned by
- *                                                    interpolation class, four macroblocks at a time, a 4x4 block per lane (-DINTER_LANE_BLOCKS=0: k_recon_inter<0>)
+ *                                                    interpolation class, four macroblocks at a time, a 4x4 block per lane
  *     k_recon_inter_lq  grid (n_quad/8, N)    x 64   inter macroblocks with one motion vector per 8x8 quadrant: a chunk of 8 list entries per wavefront, their quadrants
- *                                                    binned by interpolation class, 16 quadrants at a time, a 4x4 block per lane (-DINTER_LANE_QUADS=0: k_recon_inter<1>)
- *     k_recon_inter<2>  grid (n_rest/4, N)    x 256  finer partitions
+ *                                                    binned by interpolation class, 16 quadrants at a time, a 4x4 block per lane
+ *     k_recon_inter     grid (n_rest, N)      x 64   inter macroblocks with finer partitions, one list entry per wavefront (launched when a picture has any)
  *     k_dbk             grid (n_dbk/512, N)   x 512  boundary strengths from metadata, one macroblock per lane; on a third HIP stream, next to the four above, joined before k_frame_dbk
  *     k_frame_intra     grid (N)              x 768  one workgroup per picture: intra macroblocks, dataflow-scheduled in LDS
  *     k_frame_dbk       grid (N)              x 768  one workgroup per picture: in-loop filter, dataflow-scheduled in LDS
@@ -470,23 +470,13 @@ static void launch_kdbk(hipStream_t st, const FrameDesc *d_desc, const TickShape
     hipLaunchKernelGGL(h264k::k_dbk, dim3((s.max_dbk + 64 * DBK_WG_WAVES - 1) / (64 * DBK_WG_WAVES), s.n_frames), dim3(64 * DBK_WG_WAVES), 0, st, d_desc);
     if (launches) launches[2]++;
 }
-/* k_recon_inter for one partition class (0: one motion vector, 1: one per 8x8 quadrant, 2: finer), n_max entries in the longest list of the tick */
-template <int PATH> static void launch_inter(hipStream_t st, const FrameDesc *d_desc, uint32_t n_max, uint32_t n_frames)
+/* The three inter kernels of one tick, one per part of the general-inter list; n_uni, n_quad, n_rest: the entries in the tick's longest part of each
+ * kind.  Single-wavefront workgroups: a chunk of entries each in the first two, one entry in the third. */
+static void launch_inter(hipStream_t st, const FrameDesc *d_desc, uint32_t n_uni, uint32_t n_quad, uint32_t n_rest, uint32_t n_frames)
 {
-#if INTER_LANE_BLOCKS
-    if constexpr (PATH == 0) {                       /* one wavefront per chunk of INTER_LB_CHUNK entries, a 4x4 block per lane */
-        if (n_max) hipLaunchKernelGGL(h264k::k_recon_inter_lb, dim3((n_max + INTER_LB_CHUNK - 1) / INTER_LB_CHUNK, n_frames), dim3(64), 0, st, d_desc);
-    } else
-#endif
-#if INTER_LANE_QUADS
-    if constexpr (PATH == 1) {                       /* one wavefront per chunk of INTER_LQ_CHUNK entries, a quadrant per four lanes */
-        if (n_max) hipLaunchKernelGGL(h264k::k_recon_inter_lq, dim3((n_max + INTER_LQ_CHUNK - 1) / INTER_LQ_CHUNK, n_frames), dim3(64), 0, st, d_desc);
-    } else
-#endif
-    {
-    constexpr uint32_t per_wg = INTER_WG_WAVES * h264k::inter_per_wave<PATH>();
-    if (n_max) hipLaunchKernelGGL(h264k::k_recon_inter<PATH>, dim3((n_max + per_wg - 1) / per_wg, n_frames), dim3(64 * INTER_WG_WAVES), 0, st, d_desc);
-    }
+    if (n_uni) hipLaunchKernelGGL(h264k::k_recon_inter_lb, dim3((n_uni + INTER_LB_CHUNK - 1) / INTER_LB_CHUNK, n_frames), dim3(64), 0, st, d_desc);
+    if (n_quad) hipLaunchKernelGGL(h264k::k_recon_inter_lq, dim3((n_quad + INTER_LQ_CHUNK - 1) / INTER_LQ_CHUNK, n_frames), dim3(64), 0, st, d_desc);
+    if (n_rest) hipLaunchKernelGGL(h264k::k_recon_inter, dim3(n_rest, n_frames), dim3(64), 0, st, d_desc);
 }
 /* the dynamic LDS every device has allowed the per-picture kernels so far: [0 k_frame_dbk, 1 k_frame_intra][plain, banded variant][device] */
 std::mutex g_tail_lds_mu;
@@ -553,9 +543,7 @@ int launch_tick(hipStream_t st, const FrameDesc *d_desc, const TickShape &s, Tic
     if (do_copy && !copy_aside) launch_copy(st);
     if (boundary(1)) return -1;
     if ((stages & 1u) && s.max_gen) {
-        launch_inter<0>(st, d_desc, s.max_gen_uni, s.n_frames);
-        launch_inter<1>(st, d_desc, s.max_gen_quad, s.n_frames);
-        launch_inter<2>(st, d_desc, s.max_gen_rest, s.n_frames);
+        launch_inter(st, d_desc, s.max_gen_uni, s.max_gen_quad, s.max_gen_rest, s.n_frames);
         if (launches) launches[1]++;
     }
     if (boundary(2)) return -1;

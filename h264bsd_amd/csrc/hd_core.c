@@ -421,8 +421,8 @@ static int fj_emit(FjCtx *c, uint32_t cap)
     if (h->mv_off >= h->coef_off && h->mv_off < h->total_bytes) return -1;       /* (behind the coefficients = behind the whole job) */
     for (uint32_t i = 0; i < c->n_mvx; i++) memcpy(job + h->mvx_off + (size_t)i * 64u, c->mvs[c->mvx_list[i]], 64);
     memcpy(job + h->copy_off, c->copy_tmp, (size_t)c->n_copy * 8u);
-    /* general-inter list: the entries with one motion vector per macroblock first (k_recon_inter<0>), then those with
-     * one per 8x8 quadrant (<1>), then the finer partitions (<2>); every part keeps raster order */
+    /* general-inter list: the entries with one motion vector per macroblock first (k_recon_inter_lb), then those with
+     * one per 8x8 quadrant (k_recon_inter_lq), then the finer partitions (k_recon_inter); every part keeps raster order */
     static const uint8_t part[3] = { 1, 2, 0 };
     FjGen *dst = (FjGen *)(job + h->gen_off);
     uint32_t ends[3], k = 0;

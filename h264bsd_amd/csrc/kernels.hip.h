@@ -13,9 +13,11 @@
  *                   interpolation class, four macroblocks at a time, a 4x4 luma block per lane (kernels/inter_lane_block.hip.h).
  *   k_recon_inter_lq : inter macroblocks with one motion vector per 8x8 QUADRANT: a chunk of 8 list entries per wavefront, the quadrants sorted
  *                   by interpolation class, 16 quadrants at a time, a 4x4 luma block per lane (the same arithmetic).
- *   k_recon_inter : every other inter macroblock (finer partitions), one wavefront each (= one workgroup: the wavefronts share nothing), list-driven.
- *                   Reference windows staged in LDS tile row by tile row (aligned 16-byte loads), 6-tap luma on packed
- *                   sample pairs / bilinear chroma, dequant + 4x4 inverse transform with DPP quad transposes, residual
+ *                   Both (kernels/k_recon_inter_lanes.hip.h) stage the reference windows of a group of slots in LDS tile row by tile row
+ *                   (aligned 16-byte loads) and share every step but their lane geometry.
+ *   k_recon_inter : every other inter macroblock (partitions finer than 8x8), one wavefront each (= one workgroup: the wavefronts share nothing),
+ *                   list-driven, a lane per row of a 4x4 block, every lane's window straight from global memory.
+ *                   All three: 6-tap luma on packed sample pairs / bilinear chroma, dequant + 4x4 inverse transform, residual
  *                   add; the macroblock leaves as its tile (24 x 16 bytes).
  *                       reference: src/h264bsd_reconstruct.c, src/h264bsd_inter_prediction.c:361-482,
  *                                  src/h264bsd_transform.c, src/h264bsd_image.c:172
@@ -48,6 +50,7 @@
 #include "kernels/k_copy.hip.h"
 #include "kernels/inter_lane_block.hip.h"
 #include "kernels/k_recon_inter.hip.h"
+#include "kernels/k_recon_inter_lanes.hip.h"
 #include "kernels/convert.hip.h"
 #include "kernels/tail_common.hip.h"
 #include "kernels/k_frame_intra.hip.h"

@@ -1,14 +1,18 @@
-/* kernels/inter_lane_block.hip.h — the register arithmetic of k_recon_inter_lb and k_recon_inter_lq (k_recon_inter.hip.h): one lane owns a whole
- * 4x4 luma block and half a 4x4 chroma block.  Nothing here touches memory or other lanes.  Part of kernels.hip.h (which see); not a stand-alone header. */
+/* kernels/inter_lane_block.hip.h — the register arithmetic and the window geometry of k_recon_inter_lb and k_recon_inter_lq
+ * (kernels/k_recon_inter_lanes.hip.h): one lane owns a whole 4x4 luma block and half a 4x4 chroma block.  Nothing here touches memory or other
+ * lanes, so tools/probes/lane_quads_host.cpp runs this file on the CPU.  Part of kernels.hip.h (which see); not a stand-alone header. */
 #pragma once
 namespace h264k {
 
 /* ------------------------------------------------------------------ luma: a 4x4 block from its 9x9 window
  * rw[r][k] = dword k of window row r: rows y-2 .. y+6, columns x-2 .. x+9 (9 used).  Output row r = window row r + 2, output
  * column i = window column i + 2.  Result o[r][0] = samples (0, 1) of row r, o[r][1] = samples (2, 3), packed 16-bit, 0..255 —
- * bit for bit what luma_pred_lds gives the four lanes that used to share the block: the same packed first stage, the same rounding,
+ * bit for bit what luma_from_window (k_recon_inter.hip.h) gives a lane per row of the block: the same packed first stage, the same rounding,
  * "vertical sums first" for j.  fx, fy are PER-LANE values here (a wavefront holds four motion vectors): what differs between the
  * letters of one class is a select or a byte selector in a register, the class itself is the caller's branch. */
+/* the interpolation class of a quarter-sample fraction: 0 whole (G), 1 horizontal (a, b, c), 2 vertical (d, h, n), 3 diagonal (e, g, p, r),
+ * 4 centre (j, f, q, i, k) */
+constexpr int lb_class_of(int fx, int fy) { return (fx | fy) == 0 ? 0 : fy == 0 ? 1 : fx == 0 ? 2 : (fx != 2 && fy != 2) ? 3 : 4; }
 constexpr uint32_t lb_sel(int c) { return 0x0C000C00u | (uint32_t)c | ((uint32_t)(c + 1) << 16); }      /* bytes (c, c + 1) of 8 -> two 16-bit halves */
 /* (column c, column c + 1) of a window row, c = 0 .. 9 */
 #define LB_CP(row, c) as_s2((c) <= 6 ? perm((row)[1], (row)[0], lb_sel((c) <= 6 ? (c) : 0)) : perm((row)[2], (row)[1], lb_sel((c) <= 6 ? 0 : (c) - 4)))
@@ -135,7 +139,7 @@ __device__ __forceinline__ void lb_luma_centre(const uint32_t rw[9][3], int fx, 
 
 /* ------------------------------------------------------------------ chroma: one row of four samples
  * (a_lo, a_hi) = bytes 0..7 of the upper source row from the first sample on (five used), (b_lo, b_hi) those of the row below;
- * w = the four bilinear weights, each in both halves.  The arithmetic of chroma_pair_lds, for both pairs of the row. */
+ * w = the four bilinear weights, each in both halves.  8.4.2.2.2 in packed 16 bit (weights at most 64, samples at most 255: every partial sum fits a signed half), both pairs of the row. */
 __device__ __forceinline__ void lb_chroma_row(uint32_t a_lo, uint32_t a_hi, uint32_t b_lo, uint32_t b_hi, s2 w00, s2 w10, s2 w01, s2 w11, s2 &o01, s2 &o23)
 {
     const s2 p0 = as_s2(perm(a_hi, a_lo, lb_sel(0))), p1 = as_s2(perm(a_hi, a_lo, lb_sel(1))), p2 = as_s2(perm(a_hi, a_lo, lb_sel(2))), p3 = as_s2(perm(a_hi, a_lo, lb_sel(3)));
@@ -233,5 +237,75 @@ __device__ __forceinline__ void lq_pair_rows(const uint32_t ldw[4], uint32_t got
 /* where r0 goes in the macroblock's tile (r1: the row below, + 16), and the lane's first chroma row (the second: + 8) */
 __device__ __forceinline__ int lq_luma_store_offset(int q, int j) { return (8 * (q >> 1) + 4 * (j >> 1) + 2 * (j & 1)) * 16 + 8 * (q & 1); }
 __device__ __forceinline__ int lq_chroma_store_offset(int q, int j) { return T_CB + (j >> 1) * 64 + (4 * (q >> 1) + 2 * (j & 1)) * 8 + 4 * (q & 1); }
+
+/* ------------------------------------------------------------------ a slot's staged windows: which lane fetches what, and where it goes
+ * A slot (a macroblock in k_recon_inter_lb, a quadrant in k_recon_inter_lq) stages one luma window of ROWS x ROWS samples and two chroma
+ * windows of CROWS x CROWS.  A window is staged tile row by tile row: a window row is the 16-byte (chroma: 8-byte) rows of the TILES (chroma:
+ * 2) tiles it may cross, loaded whole and laid side by side, so byte 0 of a staged row is the first column of the window's first tile.  These
+ * aligned PIECES are numbered luma p = TILES * row + tile and chroma p = 2 * CROWS * plane + 2 * row + tile; the LANES lanes of a slot take
+ * them in turn, lane j the pieces j, j + LANES, ...  Pure index arithmetic: the loads and LDS stores are k_recon_inter_lanes.hip.h's. */
+template <int ROWS_, int TILES_, int CROWS_, int LANES_>
+struct LaneWin {
+    static constexpr int ROWS = ROWS_, COLS = ROWS_, TILES = TILES_, CROWS = CROWS_, LANES = LANES_;
+    static constexpr int NL = (ROWS * TILES + LANES - 1) / LANES, NC = (4 * CROWS + LANES - 1) / LANES;      /* pieces per lane */
+    static_assert((TILES == 2 || TILES == 3) && 15 + COLS <= 16 * TILES && 7 + CROWS <= 16 && NL * LANES <= 128, "window shape");
+    static constexpr bool luma_piece(int p) { return p < ROWS * TILES; }
+    static constexpr int luma_row(int p) { return TILES == 2 ? p >> 1 : (p * 43) >> 7; }                      /* p / TILES for p < 128 */
+    static constexpr int luma_tile(int p) { return p - TILES * luma_row(p); }
+    /* tile k of a window row is fetched only if the window's COLS columns, which begin rel = xi - xs columns into tile 0, reach it:
+     * nothing reads the bytes it would have filled */
+    static constexpr bool tile_needed(int k, int rel) { return rel + COLS > 16 * k; }
+    static constexpr bool chroma_piece(int p) { return p < 4 * CROWS; }
+    static constexpr int chroma_plane(int p) { return p >= 2 * CROWS; }
+    static constexpr int chroma_row(int p) { return (p - 2 * CROWS * chroma_plane(p)) >> 1; }
+    static constexpr int chroma_tile(int p) { return (p - 2 * CROWS * chroma_plane(p)) & 1; }
+    /* bytes of the slot's windows at staged rows of WSTRIDE / CSTRIDE bytes (luma, then the two chroma planes), and where a piece lies in them */
+    static constexpr int bytes(int wstride, int cstride) { return ROWS * wstride + 2 * CROWS * cstride; }
+    static constexpr int luma_at(int wstride, int row, int tile) { return row * wstride + 16 * tile; }
+    static constexpr int chroma_at(int wstride, int cstride, int plane, int row, int tile) { return ROWS * wstride + (plane * CROWS + row) * cstride + 8 * tile; }
+};
+typedef LaneWin<21, 3, 9, 16> LbWin;                 /* a macroblock: 16 + 5 luma rows and columns, 8 + 1 chroma; a lane per 4x4 block */
+typedef LaneWin<13, 2, 5, 4> LqWin;                  /* a quadrant: 8 + 5 and 4 + 1 */
+/* A piece is a tile row of the reference picture, pictures are whole tiles: a piece lies wholly inside the picture, wholly left of it or wholly
+ * right of it.  It is loaded from the tile and row clamped into the picture (byte offset in the picture's tiles; x a multiple of 16 / 8, w x h
+ * the plane), and where lw_side says it lay outside, its first (-1) or last (+1) sample is spread over it: h264bsdFillBlock's clamping of every
+ * sample, src/h264bsd_reconstruct.c:2244. */
+__device__ __forceinline__ uint32_t lw_luma_piece(int wmb, int w, int h, int x, int y)
+{
+    const int xx = clip3(0, w - 16, x), yy = clip3(0, h - 1, y);
+    return (uint32_t)((yy >> 4) * wmb + (xx >> 4)) * (uint32_t)TILE + (uint32_t)((yy & 15) << 4);
+}
+__device__ __forceinline__ uint32_t lw_chroma_piece(int wmb, int plane, int w, int h, int x, int y)
+{
+    const int xx = clip3(0, w - 8, x), yy = clip3(0, h - 1, y);
+    return (uint32_t)((yy >> 3) * wmb + (xx >> 3)) * (uint32_t)TILE + (uint32_t)(T_CB + (plane << 6) + ((yy & 7) << 3));
+}
+constexpr int lw_side(int x, int w) { return x < 0 ? -1 : x >= w ? 1 : 0; }
+/* the shared rules above are the ones the two kernels used to spell out by hand, for every piece and every rel */
+constexpr bool lb_win_as_written()
+{
+    for (int rel = 0; rel < 16; rel++)
+        for (int p = 0; p < 64; p++) {
+            const int lr = p / 3, lk = p % 3, cp = p >= 18, rem = cp ? p - 18 : p;
+            if (LbWin::luma_row(p) != lr || LbWin::luma_tile(p) != lk || LbWin::luma_piece(p) != (p < 63)) return false;
+            if (LbWin::tile_needed(lk, rel) != (lk < 2 || rel >= 12)) return false;
+            if (p < 48 && LbWin::chroma_piece(p) != (p < 36)) return false;
+            if (p < 36 && (LbWin::chroma_plane(p) != cp || LbWin::chroma_row(p) != (rem >> 1) || LbWin::chroma_tile(p) != (rem & 1))) return false;
+        }
+    return LbWin::NL == 4 && LbWin::NC == 3;
+}
+constexpr bool lq_win_as_written()
+{
+    for (int rel = 0; rel < 16; rel++)
+        for (int p = 0; p < 28; p++) {
+            const int lr = p >> 1, lk = p & 1, cp = p >= 10, rem = cp ? p - 10 : p;
+            if (LqWin::luma_row(p) != lr || LqWin::luma_tile(p) != lk || LqWin::luma_piece(p) != (p < 26)) return false;
+            if (LqWin::tile_needed(lk, rel) != (lk == 0 || rel >= 4)) return false;
+            if (p < 20 && (!LqWin::chroma_piece(p) || LqWin::chroma_plane(p) != cp || LqWin::chroma_row(p) != (rem >> 1) || LqWin::chroma_tile(p) != (rem & 1))) return false;
+        }
+    return LqWin::NL == 7 && LqWin::NC == 5;
+}
+static_assert(lb_win_as_written(), "21 x 48 window: p / 3, p < 63, lk < 2 || rel >= 12, p < 36");
+static_assert(lq_win_as_written(), "13 x 32 window: p >> 1, p < 26, lk == 0 || rel >= 4, every chroma piece");
 
 } // namespace h264k

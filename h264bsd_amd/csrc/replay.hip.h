@@ -8,21 +8,6 @@ extern "C" {
  * sticky bits of h264bsdmiDeviceErrors(): a test asserts that its own pictures added none */
 unsigned h264bsdmiDebugDeviceErrorEvents(void) { return poll_all_devices(true); }
 
-#ifdef H264K_INTER_PROFILE
-/* profiling build only: the 24 64-bit counters behind the device error word (k_recon_inter's cycle accounting), read and zeroed */
-int h264bsdmiDebugReadCounters(unsigned long long *out)
-{
-    Engine *e = engine_get();
-    if (!e) return -1;
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(out, reinterpret_cast<uint8_t *>(e->d_err) + 64, 192, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemset(reinterpret_cast<uint8_t *>(e->d_err) + 64, 0, 192));
-    HIP_TRY(hipDeviceSynchronize());
-    return 0;
-}
-#endif
-
 /* ------------------------------------------------------------------ replay sets */
 struct h264bsdmi_replay {
     Engine *e;

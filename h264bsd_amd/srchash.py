@@ -5,7 +5,8 @@ import hashlib
 import os
 import re
 
-_FILES = ("kernels.hip.h", "kernels/common.hip.h", "kernels/k_dbk.hip.h", "kernels/k_copy.hip.h", "kernels/inter_lane_block.hip.h", "kernels/k_recon_inter.hip.h", "kernels/convert.hip.h",
+_FILES = ("kernels.hip.h", "kernels/common.hip.h", "kernels/k_dbk.hip.h", "kernels/k_copy.hip.h", "kernels/inter_lane_block.hip.h", "kernels/k_recon_inter.hip.h", "kernels/k_recon_inter_lanes.hip.h",
+          "kernels/convert.hip.h",
           "kernels/tail_common.hip.h", "kernels/k_frame_intra.hip.h", "kernels/k_frame_dbk.hip.h", "kernels/k_pixels_io.hip.h", "framejob.h")
 
 

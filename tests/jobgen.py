@@ -538,7 +538,7 @@ def _edge_component(pos, block, target, frac):
 def patch_window_edges(rng, wmb, first=0):
     """Every inter macroblock gets reference windows whose ends lie one sample inside, on, and one sample outside a picture border
     (window_targets), horizontally and vertically at once, so corners occur too: the flip between the in-picture fast paths
-    and the clamped gathers (lfast / cfast in k_recon_inter, the x0 test of k_copy).  Macroblocks take turns between one
+    and the clamped gathers (lfast / cfast in the staging of k_recon_inter_lb / _lq, the x0 test of k_copy).  Macroblocks take turns between one
     vector (16x16 window), one vector per quadrant (the window of one 8x8 quadrant is placed, the others get vectors NEAR) and
     one per 4x4 block; the fraction class cycles through FRACTIONS.
     Luma inside / chroma outside cannot be placed: the luma window [X - 2, X + B + 2] of a block at X contains twice the

@@ -15,7 +15,7 @@ from replay_compare import run_and_compare
 
 pytestmark = pytest.mark.gpu
 
-CHUNK = 8                                                      # INTER_LQ_CHUNK (kernels/k_recon_inter.hip.h)
+CHUNK = 8                                                      # INTER_LQ_CHUNK (kernels/k_recon_inter_lanes.hip.h)
 CLASSES, CLASS_FRACTIONS, RESIDUALS, FJ_CODED_WIDE = lb.CLASSES, lb.CLASS_FRACTIONS, lb.RESIDUALS, lb.FJ_CODED_WIDE
 FJ_PARTS_8x8, FJ_PARTS_16x8, FJ_PARTS_8x16 = 0, 2, 3
 

@@ -1,6 +1,6 @@
 """GPU parity on the structured hand-built frame jobs (tests/test_structured_jobs.py: STRUCTURED_SET): kernels vs CPU oracle,
 bit-exact.  What the random jobs of test_gpu_random_jobs.py never reach, on pictures of at most 19 x 2 macroblocks: macroblocks
-with one vector per quadrant (k_recon_inter<1>), every partition type and the no_motion_edge rule of k_dbk, sub-8x8 partitions,
+with one vector per quadrant (k_recon_inter_lq), every partition type and the no_motion_edge rule of k_dbk, sub-8x8 partitions,
 motion fields whose neighbours differ by 0, 3 and 4 quarter samples (the >= 4 of k_dbk and of fj_dbk_trivial), copy runs of every
 length with and without displacement (k_copy's run body, its tail, row ends, borders), reference windows one sample inside, on and
 one sample outside every picture border (lfast / cfast), and content on which the filter takes every one of its decisions.

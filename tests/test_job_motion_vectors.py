@@ -46,7 +46,7 @@ def test_finished_job_reproduces_the_dense_vectors_it_was_built_from(lib, seed):
     idx = np.frombuffer(rec[:, 28:32].tobytes(), dtype=np.uint32)
     assert np.array_equal(idx[many], np.arange(len(many)))
     assert h["mvx_off"] % 32 == 0 and h["total_bytes"] == ((h["mvx_off"] + 64 * len(many) + 31) & ~31)
-    # partitioned list entries carry the same index (k_recon_inter<1> / <2> start from the entry, not from the record)
+    # partitioned list entries carry the same index (k_recon_inter_lq and k_recon_inter start from the entry, not from the record)
     for i in range(h["n_gen"]):
         mb, uni = struct.unpack_from("<HB", blob, h["gen_off"] + 16 * i)
         if uni != 1:

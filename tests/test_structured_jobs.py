@@ -145,7 +145,7 @@ def window_keys(v):
             for b in range(16):
                 pos = (x + 4 * (b & 3), y + 4 * (b >> 2))
                 window("4x4", 4, pos, mv[b])
-                if not (mv[b][0] & 3 or mv[b][1] & 3):                # whole samples: the block itself decides (k_recon_inter, PATH 2)
+                if not (mv[b][0] & 3 or mv[b][1] & 3):                # whole samples: the block itself decides (k_recon_inter)
                     for ax in range(2):
                         first = pos[ax] + (mv[b][ax] >> 2)
                         if first in (-1, 0, 1): keys.add(("4x4 block", ax, "first", first))
@@ -201,7 +201,7 @@ def test_the_structured_set_reaches_what_it_is_for(built):
     low = {n: c for n, c in total.items() if n not in UNREACHABLE and c < 10}
     assert not low, f"census classes taken fewer than 10 times: {low}\n{table}"
     assert all(total[n] == 0 for n in UNREACHABLE), table
-    assert quad > 0, "no macroblock with one vector per quadrant (k_recon_inter<1>)"
+    assert quad > 0, "no macroblock with one vector per quadrant (k_recon_inter_lq)"
     assert parts == {0, 1, 2, 3}, f"FJ_PARTS_* values that occur: {parts}"
     want = set(range(2, FJ_COPY_RUN + 1))
     assert want <= run_lengths[False] and want <= run_lengths[True], f"copy-run lengths: zero motion {run_lengths[False]}, displaced {run_lengths[True]}"

@@ -2,8 +2,9 @@
 //   clang++ -O1 -g -std=c++20 -fsanitize=address,undefined tools/probes/lane_quads_host.cpp -o /tmp/lane_quads_host && /tmp/lane_quads_host
 // It includes kernels/inter_lane_block.hip.h as it is (shims for the few device builtins it uses) and checks, for random pictures,
 // macroblocks, quadrants and vectors (windows inside, across and outside the picture):
-//   1. the quadrant window cut: the staged 13 x 32 window (clamped tile rows, spread), lq_window_byte and the five class filters give every
-//      lane the 4x4 block that 8.4.2.2.1 gives at that place;
+//   1. the quadrant window cut: the 13 x 32 window staged by the kernels' own rules (LqWin: which lane takes which piece, whether its tile is
+//      needed, the clamped tile row lw_luma_piece / lw_chroma_piece, the spread lw_side, the place in the slot), lq_window_byte and the five
+//      class filters give every lane the 4x4 block that 8.4.2.2.1 gives at that place;
 //   2. the 2-lane chroma split: lq_chroma_byte and two lb_chroma_row per lane give the plane's 4x4 block of 8.4.2.2.2;
 //   3. the store exchange: lq_pair_rows, lq_luma_store_offset, lq_chroma_store_offset fill the quadrant's part of the tile exactly once.
 #include <algorithm>
@@ -76,30 +77,38 @@ static long n_luma, n_chroma, n_store, bad;
 
 static void one_quadrant(int mbx, int mby, int q, int mvx, int mvy, uint8_t *tile_out, int *written)
 {
-    alignas(16) uint8_t lds[13 * QW_STRIDE + 2 * 5 * QC_STRIDE + 16];
+    alignas(16) uint8_t lds[LqWin::bytes(QW_STRIDE, QC_STRIDE) + 16];
     memset(lds, 0xA5, sizeof lds);
-    uint8_t *lw = lds, *lc = lds + 13 * QW_STRIDE;
+    uint8_t *lw = lds, *lc = lds + LqWin::chroma_at(QW_STRIDE, QC_STRIDE, 0, 0, 0);
     const int CW = W >> 1, CH = H >> 1;
     const int xi = mbx * 16 + 8 * (q & 1) + (mvx >> 2) - 2, yi = mby * 16 + 8 * (q >> 1) + (mvy >> 2) - 2, xs = (xi >> 4) << 4;
     const int cxi = mbx * 8 + 4 * (q & 1) + (mvx >> 3), cyi = mby * 8 + 4 * (q >> 1) + (mvy >> 3), cxs = (cxi >> 3) << 3;
-    // staging as the kernel's four lanes do it: clamped tile row, spread where the tile is left or right of the picture
-    for (int p = 0; p < 26; p++) {
-        const int lr = p >> 1, lk = p & 1, lx0 = xs + 16 * lk, lx = clip3(0, W - 16, lx0), yy = clip3(0, H - 1, yi + lr);
-        if (!(lk == 0 || xi - xs >= 4)) continue;
-        CHECK((lx & 15) == 0, "luma piece not a tile row");
-        uint8_t v[16];
-        memcpy(v, &frame[(size_t)((yy >> 4) * wmb + (lx >> 4)) * TILE + ((yy & 15) << 4)], 16);
-        if (lx0 < 0) memset(v, v[0], 16); else if (lx0 >= W) memset(v, v[15], 16);
-        memcpy(lw + lr * QW_STRIDE + 16 * lk, v, 16);
+    // staging as the kernel's four lanes do it (lane_window_load / lane_window_store of k_recon_inter_lanes.hip.h, memcpy for the loads and stores):
+    // lane j takes the pieces j, j + 4, ...; clamped tile row, spread where the tile is left or right of the picture
+    int staged = 0;
+    for (int j = 0; j < LqWin::LANES; j++) {
+        for (int i = 0; i < LqWin::NL; i++) {
+            const int p = j + LqWin::LANES * i, lr = LqWin::luma_row(p), lk = LqWin::luma_tile(p);
+            if (!(LqWin::luma_piece(p) && LqWin::tile_needed(lk, xi - xs))) continue;
+            uint8_t v[16];
+            memcpy(v, &frame[lw_luma_piece(wmb, W, H, xs + 16 * lk, yi + lr)], 16);
+            const int side = lw_side(xs + 16 * lk, W);
+            if (side < 0) memset(v, v[0], 16); else if (side > 0) memset(v, v[15], 16);
+            memcpy(lw + LqWin::luma_at(QW_STRIDE, lr, lk), v, 16);
+            staged++;
+        }
+        for (int i = 0; i < LqWin::NC; i++) {
+            const int p = j + LqWin::LANES * i, cp = LqWin::chroma_plane(p), cr = LqWin::chroma_row(p), ck = LqWin::chroma_tile(p);
+            if (!LqWin::chroma_piece(p)) continue;
+            uint8_t v[8];
+            memcpy(v, &frame[lw_chroma_piece(wmb, cp, CW, CH, cxs + 8 * ck, cyi + cr)], 8);
+            const int side = lw_side(cxs + 8 * ck, CW);
+            if (side < 0) memset(v, v[0], 8); else if (side > 0) memset(v, v[7], 8);
+            memcpy(lds + LqWin::chroma_at(QW_STRIDE, QC_STRIDE, cp, cr, ck), v, 8);
+            staged++;
+        }
     }
-    for (int p = 0; p < 20; p++) {
-        const int cp = p >= 10, rem = cp ? p - 10 : p, cr = rem >> 1, ck = rem & 1, cx0 = cxs + 8 * ck, cx = clip3(0, CW - 8, cx0), yy = clip3(0, CH - 1, cyi + cr);
-        CHECK(ck == (p & 1), "chroma tile of a piece");
-        uint8_t v[8];
-        memcpy(v, &frame[(size_t)((yy >> 3) * wmb + (cx >> 3)) * TILE + T_CB + (cp << 6) + ((yy & 7) << 3)], 8);
-        if (cx0 < 0) memset(v, v[0], 8); else if (cx0 >= CW) memset(v, v[7], 8);
-        memcpy(lc + cp * 5 * QC_STRIDE + cr * QC_STRIDE + 8 * ck, v, 8);
-    }
+    CHECK(staged == (xi - xs >= 4 ? 26 : 13) + 20, "pieces staged: %d", staged);
     uint32_t ldw[4][4], cdw[4][2];
     for (int j = 0; j < 4; j++) {
         const int jbx = j & 1, jby = j >> 1, plane = j >> 1, half = j & 1;
@@ -107,7 +116,7 @@ static void one_quadrant(int mbx, int mby, int q, int mvx, int mvy, uint8_t *til
         const int o = lq_window_byte(q, mvx) + 4 * jbx, sh = 8 * (o & 3), fx = mvx & 3, fy = mvy & 3;
         CHECK(o == (xi - xs) + 4 * jbx, "window byte %d vs %d", o, (xi - xs) + 4 * jbx);
         const uint8_t *src = lw + 4 * jby * QW_STRIDE + (o & ~3);
-        const int cls = (fx | fy) == 0 ? 0 : fy == 0 ? 1 : fx == 0 ? 2 : (fx != 2 && fy != 2) ? 3 : 4;
+        const int cls = lb_class_of(fx, fy);
         uint32_t rw[9][3] = {};
         auto row = [&](int r, int nd) {
             uint32_t d[4] = {};

@@ -20,9 +20,10 @@ kern = {}
 for l in body.splitlines():
     m = re.match(r"(?:void )?h264k::(\w+)(<\w+>)?\(.*?\s+(FETCH_SIZE|WRITE_SIZE)\s+total=\S+ per_dispatch=(\S+)", l)
     if m:
-        # k_recon_inter<0> and <1> are the two halves of one tick's inter reconstruction: their bytes add up (the banded and the
-        # single-band instantiations of the per-picture kernels never run in the same tick of this command)
-        k = kern.setdefault(m.group(1), {})
+        # k_recon_inter_lb and k_recon_inter_lq are the two halves of one tick's inter reconstruction: their bytes add up under the name
+        # bench.py knows, k_recon_inter (the banded and the single-band instantiations of the per-picture kernels never run in the same
+        # tick of this command)
+        k = kern.setdefault("k_recon_inter" if m.group(1).startswith("k_recon_inter") else m.group(1), {})
         key = "fetch_bytes_per_launch" if m.group(3) == "FETCH_SIZE" else "write_bytes_per_launch"
         k[key] = k.get(key, 0.0) + float(m.group(4)) * 1024
 # Calibration on a known byte count in our own access pattern (MI355X_MICROARCH.md, HBM section): k_copy moves exactly
