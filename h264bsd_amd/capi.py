@@ -28,7 +28,7 @@ EXPORTED_SYMBOLS = [
     "h264bsdCroppingParams", "h264bsdSampleAspectRatio", "h264bsdCheckValidParamSets", "h264bsdFlushBuffer",
     "h264bsdProfile", "h264bsdAlloc", "h264bsdFree", "h264bsdConvertToRGBA", "h264bsdConvertToBGRA",
     "h264bsdConvertToYCbCrA",
-    "h264bsdmiInitCapture", "h264bsdmiNextOutputInfo", "h264bsdmiNextOutputPictureDevice", "h264bsdmiNextOutputTensorBatch", "h264bsdmiNextOutputTensorBatchColour", "h264bsdmiNextOutputTensorBatchResize", "h264bsdmiOutputTensorRegions", "h264bsdmiOutputTensorRemap", "h264bsdmiSetMotionExport", "h264bsdmiOutputMotionRegions", "h264bsdmiOutputRegionStats", "h264bsdmiKeepCurrentPictures", "h264bsdmiBlendCurrentPictures", "h264bsdmiOutputKeptPictures", "h264bsdmiOutputRegionChange", "h264bsdmiOutputRegionShift", "h264bsdmiOutputCellMaps", "h264bsdmiOutputCellBoxes", "h264bsdmiJobFinalize", "h264bsdmiDeviceCount", "h264bsdmiSetDevice", "h264bsdmiFlush", "h264bsdmiFlushAsync", "h264bsdmiDeviceErrors",
+    "h264bsdmiInitCapture", "h264bsdmiNextOutputInfo", "h264bsdmiNextOutputPictureDevice", "h264bsdmiNextOutputTensorBatch", "h264bsdmiNextOutputTensorBatchColour", "h264bsdmiNextOutputTensorBatchResize", "h264bsdmiOutputTensorRegions", "h264bsdmiOutputTensorRemap", "h264bsdmiSetMotionExport", "h264bsdmiOutputMotionRegions", "h264bsdmiOutputRegionStats", "h264bsdmiKeepCurrentPictures", "h264bsdmiBlendCurrentPictures", "h264bsdmiOutputKeptPictures", "h264bsdmiOutputRegionChange", "h264bsdmiOutputRegionShift", "h264bsdmiOutputCornerPoints", "h264bsdmiOutputCellMaps", "h264bsdmiOutputCellBoxes", "h264bsdmiJobFinalize", "h264bsdmiDeviceCount", "h264bsdmiSetDevice", "h264bsdmiFlush", "h264bsdmiFlushAsync", "h264bsdmiDeviceErrors",
     "h264bsdmiDecodePicture", "h264bsdmiDecodePictureBatch", "h264bsdmiNextOutputPictureBatch", "h264bsdmiPullAndDecodePictureBatch", "h264bsdmiSetParserThreads", "h264bsdmiSetInputReadOnly", "h264bsdmiSetCopyElision",
     "h264bsdmiReplayCreate", "h264bsdmiReplayCreateStaggered", "h264bsdmiReplayCreateDesync", "h264bsdmiReplayCreateSched", "h264bsdmiReplayReschedule", "h264bsdmiReplayDestroy", "h264bsdmiReplayRun", "h264bsdmiReplaySync",
     "h264bsdmiReplayFetch", "h264bsdmiReplayDbkRecords", "h264bsdmiReplayChecksums", "h264bsdmiReplayConvert", "h264bsdmiReplayFetchConverted",
@@ -109,6 +109,12 @@ class ShiftSpec(ctypes.Structure):
                 ("keep_after", ctypes.c_uint32)]
 
 
+class CornersSpec(ctypes.Structure):
+    """h264bsdmi_corners_spec (include/h264bsd_mi355x.h)"""
+    _fields_ = [("data", ctypes.c_void_p), ("score", ctypes.c_uint32), ("block", ctypes.c_uint32), ("nms", ctypes.c_uint32),
+                ("max_points", ctypes.c_uint32), ("crop", ctypes.c_uint32), ("zero", ctypes.c_uint32), ("min_score", ctypes.c_uint64)]
+
+
 class CellsSpec(ctypes.Structure):
     """h264bsdmi_cells_spec (include/h264bsd_mi355x.h)"""
     _fields_ = [("data", ctypes.c_void_p), ("cols", ctypes.c_uint32), ("rows", ctypes.c_uint32), ("cell", ctypes.c_uint32),
@@ -123,6 +129,8 @@ class BoxesSpec(ctypes.Structure):
 
 
 SHIFT_MAX_RADIUS, SHIFT_MAX_SIDE = 16, 4096                                       # H264BSDMI_SHIFT_MAX_*
+CORNER_SCORES = {"min_eigen": 0, "harris": 1}                                    # H264BSDMI_CORNERS_*
+CORNERS_MAX_NMS, CORNERS_MAX_POINTS = 7, 256                                     # H264BSDMI_CORNERS_MAX_*
 BOXES_MAX_CELLS, BOXES_MAX_BOXES = 16384, 512                                     # H264BSDMI_BOXES_MAX_*
 BOXES_SENSES = {"above": 0, "below": 1}                                          # H264BSDMI_BOXES_*
 # per mode (H264BSDMI_CELLS_PICTURE, _CHANGE): name -> H264BSDMI_CELL_*, in the order of the maps
@@ -273,6 +281,8 @@ def _declare(L, harness):
     L.h264bsdmiOutputRegionShift.argtypes = [u32, ctypes.POINTER(vp), u32, ctypes.POINTER(Region), ctypes.POINTER(ShiftSpec), vp,
                                              P32, P32, P32, P32, P32]
     L.h264bsdmiOutputRegionShift.restype = ctypes.c_int
+    L.h264bsdmiOutputCornerPoints.argtypes = [u32, ctypes.POINTER(vp), u32, ctypes.POINTER(Region), ctypes.POINTER(CornersSpec), vp, P32, P32, P32]
+    L.h264bsdmiOutputCornerPoints.restype = ctypes.c_int
     L.h264bsdmiOutputCellMaps.argtypes = [u32, ctypes.POINTER(vp), u32, ctypes.POINTER(Region), ctypes.POINTER(CellsSpec), vp,
                                           P32, P32, P32, P32, P32]
     L.h264bsdmiOutputCellMaps.restype = ctypes.c_int
@@ -1116,6 +1126,80 @@ def pull_shift(decoders, regions=None, radius=4, crop=True, surface=False, keep=
     spec = ShiftSpec(out.data_ptr(), radius, 1 if surface else 0, 1 if crop else 0, 1 if keep else 0)
     return RegionShift(out, radius, bool(surface),
                        *_kept_pull("h264bsdmiOutputRegionShift", decoders, K, regs, (ctypes.byref(spec),), stream, n > 0))
+
+
+def corners_record_bytes(max_points):
+    """the stride of one record of h264bsdmiOutputCornerPoints: 32 + 16 K bytes, K = max_points"""
+    if not isinstance(max_points, int) or isinstance(max_points, bool) or not 1 <= max_points <= CORNERS_MAX_POINTS:
+        raise ValueError(f"corners_record_bytes: max_points is an int in 1..{CORNERS_MAX_POINTS}, not {max_points}")
+    return 32 + 16 * max_points
+
+
+class CornerPoints:
+    """what pull_corners returns: count, found, written [R] int32; energy [R] int64; x, y [R, K] int32 in the regions' coordinates (the
+    source window's); score [R, K] int64; the slots from `written` on are zero — views of `records` ([R, stride] uint8, one allocation,
+    the C layout); got [R], current and pic_id per decoder, lists of ints"""
+
+    def __init__(self, records, max_points, got, current, pic_id):
+        import torch
+        w32, w64 = records.view(torch.int32), records.view(torch.int64)
+        K = max_points
+        self.records, self.max_points = records, K
+        self.count, self.found, self.written, self.energy = w32[:, 0], w32[:, 1], w32[:, 2], w64[:, 2]
+        self.x, self.y, self.score = w32[:, 8:8 + 4 * K:4], w32[:, 9:9 + 4 * K:4], w64[:, 5:5 + 2 * K:2]
+        self.got, self.current, self.pic_id = got, current, pic_id
+
+    def _host(self):
+        """(written [R], points [R, K, 2] int64 of x, y, scores [R, K]) as host lists: one copy of the records"""
+        import torch
+        rec = self.records.cpu()
+        w32, w64 = rec.view(torch.int32), rec.view(torch.int64)
+        K = self.max_points
+        return w32[:, 2].tolist(), w32[:, 8:8 + 4 * K:4].tolist(), w32[:, 9:9 + 4 * K:4].tolist(), w64[:, 5:5 + 2 * K:2].tolist()
+
+    def points(self, r):
+        """the written points of record r as a host list of (x, y, score), in the record's order"""
+        written, x, y, score = self._host()
+        return [(x[r][k], y[r][k], score[r][k]) for k in range(written[r])]
+
+    def regions(self, side, regions):
+        """a side x side box around every written point of every record with got: (decoder_index, x - side // 2, y - side // 2, side,
+        side), ready for pull_shift / pull_regions / pull_stats; the decoder index comes from `regions`, those of the call (after
+        regions=None: the windows as [(i, 0, 0, W_i, H_i), ...], as for RegionShift.moved), to whose origin the points are relative as
+        the boxes are.  One copy of the records to the host."""
+        if regions is None:
+            raise ValueError("CornerPoints.regions: pass the regions of the call; after regions=None, the windows as [(i, 0, 0, W, H), ...]")
+        if not isinstance(side, int) or isinstance(side, bool) or side < 1:
+            raise ValueError(f"CornerPoints.regions: side is a positive int, not {side}")
+        regions = [tuple(r) for r in regions]
+        if len(regions) != len(self.got):
+            raise ValueError(f"CornerPoints.regions: {len(regions)} regions for {len(self.got)} records")
+        written, x, y, _ = self._host()
+        return [(reg[0], x[r][k] - side // 2, y[r][k] - side // 2, side, side)
+                for r, reg in enumerate(regions) if self.got[r] for k in range(written[r])]
+
+
+def pull_corners(decoders, regions=None, score="min_eigen", block=3, nms=3, max_points=64, min_score=0, crop=True, out=None, stream=None):
+    """h264bsdmiOutputCornerPoints: the corner points of boxes of the decoders' CURRENT pictures — Sobel gradients, the structure tensor
+    over block x block samples (3 or 5), the score "min_eigen" (Shi-Tomasi: about twice the smaller eigenvalue) or "harris" (k = 1/16),
+    non-maximum suppression within Chebyshev distance nms (1..7), the strongest max_points (1..256) with score > min_score — and the
+    gradient energy of every box, by one kernel launch where the pictures lie, in exact integers; nothing is popped and no pixel is
+    pulled.  regions, crop, out and stream as for pull_stats (out: [R, corners_record_bytes(max_points)]); the luma is replicated at the
+    border of the source window.  Records of decoders without a current picture are left untouched (got[r] = 0).  Returns a
+    CornerPoints, whose .regions(side, regions) are boxes for pull_shift on the next picture."""
+    import torch
+    n = len(decoders)
+    ints = lambda *vs: all(isinstance(v, int) and not isinstance(v, bool) for v in vs)
+    if score not in CORNER_SCORES or not ints(block, nms, min_score) or block not in (3, 5) or not 1 <= nms <= CORNERS_MAX_NMS:
+        raise ValueError(f"pull_corners: unsupported score / block / nms {score} {block} {nms}")
+    if not 0 <= min_score < (1 << 63 if score == "harris" else 1 << 64):
+        raise ValueError(f"pull_corners: min_score {min_score} is out of range")
+    K, regs = _regions_arg("pull_corners", n, regions)
+    shape = (K, corners_record_bytes(max_points))
+    out, stream = _out_and_stream("pull_corners", out, shape, torch.uint8, stream, aligned=True)
+    spec = CornersSpec(out.data_ptr(), CORNER_SCORES[score], block, nms, max_points, 1 if crop else 0, 0, min_score)
+    got, cur, ids = _current_pull("h264bsdmiOutputCornerPoints", decoders, K, regs, (ctypes.byref(spec),), stream, call=K > 0)
+    return CornerPoints(out, max_points, got, cur, ids)
 
 
 class CellMaps:

@@ -362,7 +362,7 @@ int h264bsdmiNextOutputTensorBatchResize(u32 n, storage_t *const *dec, const h26
 }
 
 /* ---- The pulls of CURRENT pictures (pop_output, drop_current): h264bsdmiOutputTensorRegions, h264bsdmiOutputTensorRemap,
- * h264bsdmiOutputMotionRegions, h264bsdmiOutputRegionStats, h264bsdmiOutputRegionChange and h264bsdmiOutputRegionShift (which need the kept picture as well),
+ * h264bsdmiOutputMotionRegions, h264bsdmiOutputRegionStats, h264bsdmiOutputCornerPoints, h264bsdmiOutputRegionChange and h264bsdmiOutputRegionShift (which need the kept picture as well),
  * h264bsdmiOutputCellMaps and h264bsdmiOutputCellBoxes (which need it in CHANGE mode), and their small siblings h264bsdmiKeepCurrentPictures and h264bsdmiBlendCurrentPictures (the picture list only).  Each checks its own spec; everything else is one path:
  *   regions_refused   got, the count and the range of every region — before the instances are looked at
  *   pull_begin        dec and the instances (of this library, with the sink entry the call needs, distinct), then the lists
@@ -370,7 +370,7 @@ int h264bsdmiNextOutputTensorBatchResize(u32 n, storage_t *const *dec, const h26
  *   pull_regions      the regions (or one whole window per instance) of the pictures that exist, each with its rectangle
  *   pull_finish       after the sink: got, box, current and picId — unless the sink failed (-2 writes nothing) — and the lists freed
  * A refused call returns -1 and has called no sink, written nothing; no call pops anything. */
-enum { PULL_REGIONS, PULL_REMAP, PULL_MOTION, PULL_STATS, PULL_CHANGE, PULL_KEEP, PULL_CELLS, PULL_BOXES, PULL_SHIFT };
+enum { PULL_REGIONS, PULL_REMAP, PULL_MOTION, PULL_STATS, PULL_CHANGE, PULL_KEEP, PULL_CELLS, PULL_BOXES, PULL_SHIFT, PULL_CORNERS };
 #define NO_PIC 0xFFFFFFFFu
 typedef struct CurrentPull {
     u32 n, m, k;                /* instances; pictures and items gathered so far */
@@ -405,6 +405,7 @@ static int sink_pulls(const ApiDec *a, int kind)
     case PULL_REMAP:  return k->tensor_remap != NULL;
     case PULL_MOTION: return k->motion_regions != NULL && a->motion;          /* ... and motion export is on */
     case PULL_STATS:  return k->tensor_regions != NULL && k->region_stats != NULL;
+    case PULL_CORNERS: return k->tensor_regions != NULL && k->corner_points != NULL;
     case PULL_CHANGE: return k->tensor_regions != NULL && k->region_change != NULL && k->keep_pictures != NULL;
     case PULL_SHIFT:  return k->tensor_regions != NULL && k->region_shift != NULL && k->keep_pictures != NULL;
     case PULL_KEEP:   return k->tensor_regions != NULL && k->keep_pictures != NULL;
@@ -553,6 +554,22 @@ int h264bsdmiOutputRegionStats(u32 n, storage_t *const *dec, u32 nRegions, const
     const h264bsdmi_tensor_spec window = { spec->data, 1, 1, 0, 0, 0, spec->crop, 1, { 0, 0, 0 }, { 1, 1, 1 } };
     pull_regions(&c, nRegions, regions, &window, &REFERENCE_COLOUR, 1, 1, 0);
     const int failed = c.k && c.pics[0].sink->region_stats(c.m, c.pics, c.k, c.regs, spec, stream);
+    return pull_finish(&c, failed, nRegions, got, NULL, current, picId);
+}
+
+/* Corner points of h264bsdmiOutputRegionStats' regions over the current pictures: the same windows and path, no kept picture */
+int h264bsdmiOutputCornerPoints(u32 n, storage_t *const *dec, u32 nRegions, const h264bsdmi_region *regions,
+                                const h264bsdmi_corners_spec *spec, void *stream,
+                                u32 *got, u32 *current, u32 *picId)
+{
+    CurrentPull c;
+    if (!spec || !spec->data || ((uintptr_t)spec->data & 7u) || spec->score > H264BSDMI_CORNERS_HARRIS || (spec->block != 3 && spec->block != 5)) return -1;
+    if (spec->nms < 1 || spec->nms > H264BSDMI_CORNERS_MAX_NMS || spec->max_points < 1 || spec->max_points > H264BSDMI_CORNERS_MAX_POINTS) return -1;
+    if (spec->crop > 1 || spec->zero || (spec->score == H264BSDMI_CORNERS_HARRIS && spec->min_score >> 63)) return -1;
+    if (regions_refused(n, nRegions, regions, got, 1) || pull_begin(&c, n, dec, nRegions, PULL_CORNERS)) return -1;
+    const h264bsdmi_tensor_spec window = { spec->data, 1, 1, 0, 0, 0, spec->crop, 1, { 0, 0, 0 }, { 1, 1, 1 } };
+    pull_regions(&c, nRegions, regions, &window, &REFERENCE_COLOUR, 1, 1, 0);
+    const int failed = c.k && c.pics[0].sink->corner_points(c.m, c.pics, c.k, c.regs, spec, stream);
     return pull_finish(&c, failed, nRegions, got, NULL, current, picId);
 }
 

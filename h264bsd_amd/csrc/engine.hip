@@ -44,6 +44,7 @@
 #include "kernels/k_blend.hip.h"
 #include "kernels/k_region_change.hip.h"
 #include "kernels/k_region_shift.hip.h"
+#include "kernels/k_corner_points.hip.h"
 #include "kernels/k_cell_maps.hip.h"
 #include "kernels/k_cell_boxes.hip.h"
 #include "engine.h"
@@ -166,12 +167,12 @@ constexpr unsigned CONVERT_WGS = CONVERT_WGS_N;      /* workgroups per picture o
 constexpr uint32_t LANE_DBK_WAVES = LANE_DBK_WAVES_N;
 
 /* the item stride of the tensor pulls' staging ring: k_tensor_out / k_tensor_resize read TensorItems, k_tensor_aa AaItems, k_tensor_roi
- * RoiItems, k_motion_roi MotionItems, k_tensor_remap RemapItems, k_region_stats StatsItems, k_keep KeepItems, k_blend BlendItems, k_kept_out KeptOutItems, k_region_change ChangeItems, k_region_shift ShiftItems,
+ * RoiItems, k_motion_roi MotionItems, k_tensor_remap RemapItems, k_region_stats StatsItems, k_keep KeepItems, k_blend BlendItems, k_kept_out KeptOutItems, k_region_change ChangeItems, k_region_shift ShiftItems, k_corner_points CornerItems,
  * k_cell_maps CellItems (k_cell_boxes: the same, and its BoxItems in slots of their own behind them) */
 constexpr size_t TITEM_BYTES = std::max({ sizeof(h264k::TensorItem), sizeof(h264k::AaItem), sizeof(h264k::RoiItem), sizeof(h264k::MotionItem),
                                           sizeof(h264k::RemapItem), sizeof(h264k::StatsItem), sizeof(h264k::KeepItem), sizeof(h264k::ChangeItem),
                                           sizeof(h264k::CellItem), sizeof(h264k::BoxItem), sizeof(h264k::ShiftItem), sizeof(h264k::BlendItem),
-                                          sizeof(h264k::KeptOutItem) });
+                                          sizeof(h264k::KeptOutItem), sizeof(h264k::CornerItem) });
 struct TItemSlot { uint8_t bytes[TITEM_BYTES]; };
 struct Engine {
     std::mutex mu;
@@ -1391,8 +1392,8 @@ static int motion_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, u
                               pull_grid(m.width, m.height, h264k::TAA_COLS, h264k::TAA_ROWS, n_regs), &margs, fence_ev);
 }
 
-/* The scratch in which the row bands of k_region_stats, k_region_change and k_region_shift meet (Engine.d_stats), allocated at its first
- * use for the largest of the three (two records and a partial SAD surface); two launches must not use it at once: st waits for the event behind the previous one
+/* The scratch in which the row bands of k_region_stats, k_region_change, k_region_shift and k_corner_points meet (Engine.d_stats), allocated at its first
+ * use for the largest of the four (two records, a partial SAD surface, a band's best points); two launches must not use it at once: st waits for the event behind the previous one
  * (banded_launch_locked, the one caller, records stats_ev behind its launch). */
 static int stats_scratch_locked(Engine *e, hipStream_t st, uint32_t **tickets, uint8_t **partials)
 {
@@ -1400,7 +1401,7 @@ static int stats_scratch_locked(Engine *e, hipStream_t st, uint32_t **tickets, u
     if (!e->d_stats) {
         DeviceMem<uint8_t> fresh;
         HIP_TRY(e->stats_ev.create(hipEventDisableTiming));
-        HIP_TRY(fresh.alloc(ticket_bytes + (size_t)h264k::STATS_MAX_PARTIALS * std::max({ h264k::STATS_MAX_RECORD, h264k::CHANGE_MAX_RECORD, h264k::SHIFT_MAX_PARTIAL })));
+        HIP_TRY(fresh.alloc(ticket_bytes + (size_t)h264k::STATS_MAX_PARTIALS * std::max({ h264k::STATS_MAX_RECORD, h264k::CHANGE_MAX_RECORD, h264k::SHIFT_MAX_PARTIAL, h264k::CORNER_PARTIAL })));
         HIP_TRY(hipMemsetAsync(fresh, 0, ticket_bytes, st));
         e->d_stats = std::move(fresh);
     } else HIP_TRY(hipStreamWaitEvent(st, e->stats_ev, 0));
@@ -1475,7 +1476,7 @@ static int kept_order_end(Engine *e, hipStream_t st)
     return 0;
 }
 
-/* Behind the filled items of k_region_stats, k_region_change and k_region_shift: ONE launch of S = band_count row bands per region.
+/* Behind the filled items of k_region_stats, k_region_change, k_region_shift and k_corner_points: ONE launch of S = band_count row bands per region.
  * With S > 1 the bands meet in the engine's scratch (Engine.d_stats), which two launches must not use at once: st waits for the event
  * behind the previous such launch, and stats_ev is recorded behind this one.  kept: the launch reads kept pictures, whose ordering
  * encloses it.  The same ordering and fence as the other pulls. */
@@ -1691,6 +1692,38 @@ static int shift_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, ui
     return banded_launch_locked(e, n, pics, st, fn, n_regs, tallest, &sargs, true, fence_ev);
 }
 
+/* h264bsdmiOutputCornerPoints: one CornerItem per region — the current picture, the record, box ∩ window and the window itself (the
+ * luma is replicated there) in luma samples of the coded frame — and ONE banded k_corner_points launch of the score's kernel, the
+ * bands' best points in the scratch.  No kept picture is read. */
+static int corners_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, uint32_t n_regs, const SinkRegion *regs,
+                              const h264bsdmi_corners_spec &sp, hipStream_t st, hipEvent_t *fence_ev)
+{
+    if (!sp.data || (reinterpret_cast<uintptr_t>(sp.data) & 7u) || sp.score > H264BSDMI_CORNERS_HARRIS || (sp.block != 3u && sp.block != 5u) ||
+        sp.nms < 1u || sp.nms > H264BSDMI_CORNERS_MAX_NMS || sp.max_points < 1u || sp.max_points > H264BSDMI_CORNERS_MAX_POINTS ||
+        sp.crop > 1u || sp.zero || (sp.score == H264BSDMI_CORNERS_HARRIS && sp.min_score >> 63)) return -1;
+    if (n_regs > 65535u) return -1;                                     /* grid.y */
+    if (!pull_pictures_ok(n, pics, true, false) || !pull_regions_ok(n, n_regs, regs, 1u, 1u)) return -1;
+    if (pull_begin_locked(e, n, pics, n_regs)) return -1;
+    h264k::CornerItem *items = e->titems.host<h264k::CornerItem>();
+    const uint32_t stride = h264k::corner_record_bytes(sp.max_points);
+    uint32_t tallest = 0u;
+    for (uint32_t r = 0; r < n_regs; r++) {
+        const SinkRegion &g = regs[r];
+        const SinkTensorPic &p = pics[g.pic];
+        const StreamCtx *s = pic_stream(p);
+        const RegionClip c = region_clip(p, g);
+        items[r] = h264k::CornerItem{ s->d_frames + (size_t)p.slot * s->frame_bytes, static_cast<uint8_t *>(sp.data) + (size_t)g.index * stride,
+                                      s->wmb, c.x0, c.y0, c.x1, c.y1, p.x0, p.y0, p.x0 + p.w, p.y0 + p.h };
+        tallest = std::max(tallest, c.mb_rows);
+    }
+    const void *const fns[2][2] = {
+        { reinterpret_cast<const void *>(&h264k::k_corner_points<h264k::CORNER_MIN_EIGEN, 3>), reinterpret_cast<const void *>(&h264k::k_corner_points<h264k::CORNER_MIN_EIGEN, 5>) },
+        { reinterpret_cast<const void *>(&h264k::k_corner_points<h264k::CORNER_HARRIS, 3>), reinterpret_cast<const void *>(&h264k::k_corner_points<h264k::CORNER_HARRIS, 5>) } };
+    const void *fn = fns[sp.score][sp.block == 5u];
+    h264k::CornerArgs cargs{ e->titems.dev<h264k::CornerItem>(), nullptr, nullptr, sp.nms, sp.max_points, sp.min_score };
+    return banded_launch_locked(e, n, pics, st, fn, n_regs, tallest, &cargs, false, fence_ev);
+}
+
 /* h264bsdmiOutputCellMaps: one CellItem per region — the frame, in CHANGE mode the kept frame, the slice, the box's origin (signed) and
  * box ∩ window in luma samples of the coded frame — and ONE k_cell_maps launch of (rectangles of the grid, regions) workgroups.  Every
  * cell is owned by one workgroup: no scratch.  CHANGE: the kept pictures' ordering, and a picture whose instance has no kept picture
@@ -1817,7 +1850,7 @@ static int remap_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, ui
     return pull_launch_locked(e, n, pics, st, fn, pull_grid(t.width, t.height, h264k::TRM_COLS, h264k::TRM_ROWS, n_maps), &rargs, fence_ev);
 }
 
-/* What JobSink.tensor_out, tensor_regions, motion_regions, tensor_remap, region_stats, keep_pictures, blend_pictures, kept_pictures_out, region_change, region_shift, cell_maps and cell_boxes share: one engine (one device) per call, its mutex, the
+/* What JobSink.tensor_out, tensor_regions, motion_regions, tensor_remap, region_stats, keep_pictures, blend_pictures, kept_pictures_out, region_change, region_shift, corner_points, cell_maps and cell_boxes share: one engine (one device) per call, its mutex, the
  * refusal of a capturing stream, and, when the caller gave no stream, the wait for the fence and the device's error words.
  * body(e, st, &fence_ev): the call's own *_out_locked. */
 template <typename Body> static int sink_tensor_call(uint32_t n, const SinkTensorPic *pics, void *stream, Body body)
@@ -1922,6 +1955,13 @@ int sink_region_shift(uint32_t n, const SinkTensorPic *pics, uint32_t n_regions,
         return shift_out_locked(e, n, pics, n_regions, regions, *spec, st, fence_ev);
     });
 }
+int sink_corner_points(uint32_t n, const SinkTensorPic *pics, uint32_t n_regions, const SinkRegion *regions,
+                       const h264bsdmi_corners_spec *spec, void *stream)
+{
+    return sink_list_call(n, pics, n_regions, regions && spec, stream, [&](Engine *e, hipStream_t st, hipEvent_t *fence_ev) {
+        return corners_out_locked(e, n, pics, n_regions, regions, *spec, st, fence_ev);
+    });
+}
 int sink_cell_maps(uint32_t n, const SinkTensorPic *pics, uint32_t n_regions, const SinkRegion *regions,
                    const h264bsdmi_cells_spec *spec, void *stream)
 {
@@ -1984,6 +2024,7 @@ int eng_attach(JobSink *sink)
     sink->cell_boxes = sink_cell_boxes;
     sink->blend_pictures = sink_blend_pictures;
     sink->kept_pictures_out = sink_kept_pictures_out;
+    sink->corner_points = sink_corner_points;
     return 0;
 }
 

@@ -226,6 +226,7 @@ struct h264bsdmi_shift_spec;
 struct h264bsdmi_cells_spec;
 struct h264bsdmi_boxes_spec;
 struct h264bsdmi_blend_spec;
+struct h264bsdmi_corners_spec;
 struct JobSink;
 /* one picture of a batched tensor pull (JobSink.tensor_out): the frame buffer `slot` of the instance behind `sink`, its window
  * (x0, y0, w, h), and the picture's index in the output tensor */
@@ -336,6 +337,11 @@ typedef struct JobSink {
      * of its coded size, as planar I420 coded frames into picture[i], and their fractions (0x80 where a plain keep came last) into
      * fraction[i] where fraction and fraction[i] are not NULL, with one launch — h264bsdmiOutputKeptPictures.  0 = ok; <0 = error */
     int (*kept_pictures_out)(uint32_t n, const SinkTensorPic *pics, void *const *picture, void *const *fraction, void *stream);
+    /* optional: the corner points of the same regions as region_stats (their box[] is not used), record `index` of spec->data each,
+     * with one launch — h264bsdmiOutputCornerPoints.  No kept picture is read.  The LAST member: stand-ins that were written before it
+     * leave it NULL.  0 = ok; <0 = error, nothing enqueued */
+    int (*corner_points)(uint32_t n, const SinkTensorPic *pics, uint32_t n_regions, const SinkRegion *regions,
+                         const struct h264bsdmi_corners_spec *spec, void *stream);
 } JobSink;
 
 /* ---------------------------------------------------------------- decoder instance */

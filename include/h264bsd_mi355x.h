@@ -548,6 +548,58 @@ int h264bsdmiOutputRegionShift(u32 n, storage_t *const *pStorage, u32 nRegions, 
                                const h264bsdmi_shift_spec *spec, void *stream,
                                u32 *got, u32 *current, u32 *kept, u32 *picId, u32 *keptPicId);
 
+/* Corner points: WHICH boxes are worth following — Shi-Tomasi (minimum eigenvalue) or Harris corner points of boxes of the instances'
+ * CURRENT pictures, luma only, computed where the pictures lie with one launch: gradients, the structure tensor, a corner score,
+ * non-maximum suppression, the strongest K — the good-features-to-track step ahead of h264bsdmiOutputRegionShift, whose search means
+ * something on textured templates only — and a focus measure (the gradient energy) from the same pass.  A sibling of
+ * h264bsdmiOutputRegionStats, and everything not said here is that call's, word for word: the region struct and its limits, negative
+ * origins, boxes that leave the source window or miss it, regions == NULL with nRegions == n meaning whole windows, the source window
+ * (spec->crop: W x H, coordinates relative to it), the current-picture rule, got (per REGION), current, picId (per instance, each may be
+ * NULL), the stream rule, the fence, nRegions <= 65535.  It needs no kept picture, pops nothing and may be repeated.
+ * THE QUANTITY, all integers, T = box ∩ window:
+ *     replicated luma   L~(u, v) = L(clamp(u, 0, W - 1), clamp(v, 0, H - 1)): the clamp is at the WINDOW, as for the region shift, and
+ *                       it is the only border rule
+ *     gradients         at any (u, v): gx = [L~(u+1, v-1) + 2 L~(u+1, v) + L~(u+1, v+1)] - [the same at u-1], gy the same transposed
+ *                       (Sobel); |g| <= 1020
+ *     structure tensor  b = spec->block, 3 or 5: A = sum gx gx, B = sum gy gy, C = sum gx gy over the b x b samples centred on (u, v),
+ *                       taken from the replicated picture as well; A, B, |C| <= 25 * 1020^2 < 2^25
+ *     score S(u, v)     for (u, v) in the window.  MIN_EIGEN: A + B - isqrt((A - B)^2 + 4 C^2), isqrt the exact floor square root:
+ *                       about twice the smaller eigenvalue, 0 <= S < 2^26.  HARRIS: 16 (A B - C^2) - (A + B)^2, k = 1 / 16, signed,
+ *                       |S| < 2^54
+ *     candidates        a window sample p with S(p) > min_score (strictly) that no OTHER window sample q within Chebyshev distance
+ *                       spec->nms beats: q beats p when S(q) > S(p), or S(q) == S(p) and q comes earlier in raster order (smaller y,
+ *                       then smaller x).  Samples outside the window do not compete.  Candidacy does not depend on the box:
+ *                       candidates(box) = candidates(whole window) ∩ box
+ *     points            the candidates inside T, sorted by (score descending, y ascending, x ascending); the first K = max_points
+ *     energy            the sum over T of gx^2 + gy^2 (the Tenengrad focus measure), at most 2^28 * 2^21
+ * Record r is written at spec->data + r * stride, little endian, stride = 32 + 16 K:
+ *     u32 count; u32 found; u32 written; u32 zero; u64 energy; u64 zero;
+ *     K x { i32 x; i32 y; i64 score; }       x, y in the regions' own coordinates (the source window's); slots >= written all zero
+ * count = |T|, found = the candidates in T, written = min(found, K).  count == 0 (the box misses the window): everything zero.
+ * Everything is an integer and exact, and no result depends on scheduling.  The call writes the WHOLE record with plain stores: the
+ * caller does not clear it.  got[r] = 0 (no current picture): record r is untouched.
+ * -1, before anything is enqueued, nothing written: everything h264bsdmiOutputRegionStats refuses in regions, instances and stream;
+ * spec or data NULL or data not 8-byte aligned; score > 1; block not 3 or 5; nms outside 1 .. 7; max_points outside 1 .. 256; crop > 1;
+ * zero != 0; HARRIS with min_score >= 2^63.  -2: the engine failed: nothing is written by the host.  nRegions == 0 returns 0 and
+ * launches nothing. */
+#define H264BSDMI_CORNERS_MIN_EIGEN  0u
+#define H264BSDMI_CORNERS_HARRIS     1u
+#define H264BSDMI_CORNERS_MAX_NMS    7u
+#define H264BSDMI_CORNERS_MAX_POINTS 256u
+typedef struct h264bsdmi_corners_spec {
+    void *data;        /* DEVICE pointer, caller-owned, 8-byte aligned: record r at data + r * (32 + 16 * max_points) */
+    u32   score;       /* H264BSDMI_CORNERS_* */
+    u32   block;       /* b: 3 or 5 */
+    u32   nms;         /* 1 .. 7, Chebyshev distance */
+    u32   max_points;  /* K, 1 .. 256 */
+    u32   crop;        /* as h264bsdmi_tensor_spec.crop */
+    u32   zero;        /* must be 0 */
+    unsigned long long min_score;   /* a candidate has S > min_score */
+} h264bsdmi_corners_spec;
+int h264bsdmiOutputCornerPoints(u32 n, storage_t *const *pStorage, u32 nRegions, const h264bsdmi_region *regions,
+                                const h264bsdmi_corners_spec *spec, void *stream,
+                                u32 *got, u32 *current, u32 *picId);
+
 /* ---- host parse pipeline at scale ----
  * h264bsdDecode() consumes one NAL unit of one stream per call; a caller that feeds hundreds of streams needs the
  * loop of posix/test_h264bsd.c:146-177 for each of them and its own threading.  These entry points move both into
