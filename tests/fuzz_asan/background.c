@@ -1,52 +1,13 @@
 /* The host path of the background model (api.c: h264bsdmiBlendCurrentPictures, h264bsdmiOutputKeptPictures) without a GPU: bound to
- * tests/fuzz_asan/mock_engine_blend.c, whose entries record what they are handed.  Prints per call "#<name>", rc, the sink's record or
+ * tests/fuzz_asan/mock_engine.c, whose entries record what they are handed.  Prints per call "#<name>", rc, the sink's record or
  * "sink: not called", and the output arrays, which start as a sentinel ("untouched" when none of it was written).
  * tests/test_background_host.py builds it, plain and under sanitizers, and reads the records.
  * usage: background <test_640x360.h264> <test_1920x1080.h264>
  * Instances: A the 640x360 stream (picIds from 100), B the 1920x1080 stream (from 200), each popped once; C initialised and never fed. */
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-#include "../../include/h264bsd_mi355x.h"
-void mock_call(uint32_t n, void *const *users);
-const char *mock_record(void);
-void *mock_last_attached(void);
-extern int mock_fail, mock_no_blend;
+#include "host_harness.h"
 
-#define SENT 0xA5A5A5A5u
-typedef struct Inst { storage_t *s; void *user; u8 *buf; u32 len, off, id; } Inst;      /* id: the picId its next picture carries */
-
-static u8 *load(const char *path, u32 *len)
-{
-    FILE *f = fopen(path, "rb");
-    if (!f) { fprintf(stderr, "cannot read %s\n", path); exit(2); }
-    fseek(f, 0, SEEK_END); const long n = ftell(f); fseek(f, 0, SEEK_SET);
-    u8 *p = malloc((size_t)n);
-    if (!p || fread(p, 1, (size_t)n, f) != (size_t)n) exit(2);
-    fclose(f);
-    *len = (u32)n;
-    return p;
-}
-/* one more picture decoded, and popped: it is the current picture */
-static void next_picture(Inst *t)
-{
-    int stalls = 0;
-    while (t->off < t->len && stalls <= 3) {
-        u32 rb = 0;
-        const u32 r = h264bsdDecode(t->s, t->buf + t->off, t->len - t->off, t->id, &rb);
-        t->off += rb;
-        stalls = rb ? 0 : stalls + 1;
-        if (r == H264BSD_PIC_RDY) {
-            t->id++;
-            if (h264bsdmiNextOutputInfo(t->s, NULL, NULL, NULL) < 0) break;
-            return;
-        }
-    }
-    fprintf(stderr, "stream ended before a picture\n"); exit(2);
-}
 /* an instance over the bytes of one stream, or of two, one after the other; pictures: how many it decodes and pops at once */
-static void make(Inst *t, const u8 *a, u32 len_a, const u8 *b, u32 len_b, u32 id, int pictures)
+static void make_joined(Inst *t, const u8 *a, u32 len_a, const u8 *b, u32 len_b, u32 id, int pictures)
 {
     memset(t, 0, sizeof(*t));
     t->s = h264bsdAlloc();
@@ -59,46 +20,29 @@ static void make(Inst *t, const u8 *a, u32 len_a, const u8 *b, u32 len_b, u32 id
     if (len_b) memcpy(t->buf + len_a, b, len_b);
     for (int k = 0; k < pictures; k++) next_picture(t);
 }
-static void unmake(Inst *t) { h264bsdShutdown(t->s); h264bsdFree(t->s); free(t->buf); }
-
-static void show(const char *name, const u32 *a, size_t n)
-{
-    int touched = 0;
-    for (size_t i = 0; i < n; i++) touched |= a[i] != SENT;
-    printf("%s=", name);
-    if (!touched) printf("untouched");
-    else for (size_t i = 0; i < n; i++) { if (a[i] == SENT) printf("%sS", i ? "," : ""); else printf("%s%u", i ? "," : "", a[i]); }
-    printf("\n");
-}
-static void head(const char *name, int rc) { printf("#%s\nrc=%d\n%s", name, rc, *mock_record() ? mock_record() : "sink: not called\n"); }
 
 #define MAXN 4
 /* one blend over t[0 .. n); spec NULL: the call gets none; dec_null / kept_null: those arguments NULL */
-static void blend(const char *name, u32 n, Inst *const *t, const h264bsdmi_blend_spec *spec, void *stream, int fail, int dec_null, int kept_null)
+static void blend(const char *name, u32 n, Inst *const *t, const h264bsdmi_blend_spec *spec, void *stream, unsigned fail, int dec_null, int kept_null)
 {
     storage_t *dec[MAXN]; void *users[MAXN];
     u32 kept[MAXN], blended[MAXN], ids[MAXN];
-    for (u32 i = 0; i < n; i++) { dec[i] = t[i]->s; users[i] = t[i]->user; kept[i] = blended[i] = ids[i] = SENT; }
-    mock_fail = fail;
-    mock_call(n, users);
+    for (u32 i = 0; i < n; i++) kept[i] = blended[i] = ids[i] = SENT;
+    aim(n, t, dec, users, fail);
     const int rc = h264bsdmiBlendCurrentPictures(n, dec_null ? NULL : dec, spec, stream, kept_null ? NULL : kept, blended, ids);
     head(name, rc);
-    show("kept", kept, n); show("blended", blended, n); show("picId", ids, n);
-    mock_fail = 0;
+    show("kept", kept, n, 1); show("blended", blended, n, 1); show("picId", ids, n, 1);
 }
-static void kept_out(const char *name, u32 n, Inst *const *t, void *const *picture, void *const *fraction, void *stream, int fail)
+static void kept_out(const char *name, u32 n, Inst *const *t, void *const *picture, void *const *fraction, void *stream, unsigned fail)
 {
     storage_t *dec[MAXN]; void *users[MAXN];
     u32 got[MAXN], ids[MAXN];
-    for (u32 i = 0; i < n; i++) { dec[i] = t[i]->s; users[i] = t[i]->user; got[i] = ids[i] = SENT; }
-    mock_fail = fail;
-    mock_call(n, users);
+    for (u32 i = 0; i < n; i++) got[i] = ids[i] = SENT;
+    aim(n, t, dec, users, fail);
     const int rc = h264bsdmiOutputKeptPictures(n, dec, picture, fraction, stream, got, ids);
     head(name, rc);
-    show("got", got, n); show("keptPicId", ids, n);
-    mock_fail = 0;
+    show("got", got, n, 1); show("keptPicId", ids, n, 1);
 }
-static void discard_job(void *user, const u8 *blob, u32 bytes) { (void)user; (void)blob; (void)bytes; }
 
 int main(int argc, char **argv)
 {
@@ -106,9 +50,9 @@ int main(int argc, char **argv)
     u32 len_a = 0, len_b = 0;
     u8 *sa = load(argv[1], &len_a), *sb = load(argv[2], &len_b);
     Inst A, B, C, D, E;
-    make(&A, sa, len_a, NULL, 0, 100, 1);
-    make(&B, sb, len_b, NULL, 0, 200, 1);
-    make(&C, NULL, 0, NULL, 0, 300, 0);
+    make_joined(&A, sa, len_a, NULL, 0, 100, 1);
+    make_joined(&B, sb, len_b, NULL, 0, 200, 1);
+    make_joined(&C, NULL, 0, NULL, 0, 300, 0);
     Inst *const abc[3] = { &A, &B, &C }, *const aa[2] = { &A, &A };
     const h264bsdmi_blend_spec plain = { 4, 255, 4, NULL }, gated = { 3, 12, H264BSDMI_BLEND_FROZEN, (void *)(uintptr_t)0x3000 };
     void *const stream = (void *)(uintptr_t)0x77;
@@ -125,12 +69,12 @@ int main(int argc, char **argv)
         Inst cap;
         memset(&cap, 0, sizeof(cap));
         cap.s = h264bsdAlloc();
-        if (h264bsdmiInitCapture(cap.s, 1, discard_job, NULL) != HANTRO_OK) return 3;
+        if (h264bsdmiInitCapture(cap.s, 1, no_job, NULL) != HANTRO_OK) return 3;
         Inst *const ac[2] = { &A, &cap };
         void *const pic2[2] = { (void *)(uintptr_t)0x10000, (void *)(uintptr_t)0x20000 };
         blend("refused_capture_mode", 2, ac, &plain, NULL, 0, 0, 0);
         kept_out("kept_out_refused_capture_mode", 2, ac, pic2, NULL, NULL, 0);
-        h264bsdShutdown(cap.s); h264bsdFree(cap.s);
+        unmake(&cap);
     }
     blend("nothing_to_do", 0, abc, &plain, NULL, 0, 0, 0);
 
@@ -138,15 +82,15 @@ int main(int argc, char **argv)
     void *const pics[3] = { (void *)(uintptr_t)0x10000, (void *)(uintptr_t)0x20000, (void *)(uintptr_t)0x30000 };
     void *const fracs[3] = { (void *)(uintptr_t)0x40000, NULL, (void *)(uintptr_t)0x50000 };
     kept_out("kept_out_nothing_kept", 3, abc, pics, fracs, NULL, 0);
-    blend("first_fails", 3, abc, &plain, NULL, 1, 0, 0);
+    blend("first_fails", 3, abc, &plain, NULL, MOCK_BLEND_PICTURES, 0, 0);
     blend("first", 3, abc, &plain, NULL, 0, 0, 0);                 /* ... which marked nothing: both start now */
     next_picture(&A);
     blend("second", 3, abc, &gated, stream, 0, 0, 0);
     next_picture(&A);
-    blend("third_fails", 3, abc, &gated, stream, 1, 0, 0);
+    blend("third_fails", 3, abc, &gated, stream, MOCK_BLEND_PICTURES, 0, 0);
     kept_out("kept_out", 3, abc, pics, fracs, stream, 0);          /* A still holds 101 */
     kept_out("kept_out_no_fractions", 3, abc, pics, NULL, NULL, 0);
-    kept_out("kept_out_fails", 3, abc, pics, fracs, NULL, 1);
+    kept_out("kept_out_fails", 3, abc, pics, fracs, NULL, MOCK_KEPT_PICTURES_OUT);
     {
         void *const unaligned[3] = { (void *)(uintptr_t)0x10008, (void *)(uintptr_t)0x20000, NULL };
         void *const no_pic[3] = { (void *)(uintptr_t)0x10000, NULL, NULL };
@@ -160,29 +104,30 @@ int main(int argc, char **argv)
 
     /* a plain keep and a blend share what is known of the kept picture */
     {
-        storage_t *const dec[1] = { A.s };
+        Inst *const a[1] = { &A };
+        storage_t *dec[1]; void *users[1];
         u32 kept[1];
+        aim(1, a, dec, users, 0);
         if (h264bsdmiKeepCurrentPictures(1, dec, NULL, kept, NULL) != 0 || kept[0] != 1) return 3;      /* A keeps 102 */
         next_picture(&A);
-        Inst *const a[1] = { &A };
         blend("after_a_keep", 1, a, &plain, NULL, 0, 0, 0);
     }
 
     /* blended and picId may be NULL */
     {
-        storage_t *const dec[1] = { B.s };
-        void *users[1] = { B.user };
+        Inst *const b[1] = { &B };
+        storage_t *dec[1]; void *users[1];
         u32 kept[1] = { SENT };
-        mock_call(1, users);
+        aim(1, b, dec, users, 0);
         const int rc = h264bsdmiBlendCurrentPictures(1, dec, &plain, NULL, kept, NULL, NULL);
         head("optional_arrays", rc);
-        show("kept", kept, 1);
+        show("kept", kept, 1, 1);
     }
 
     /* a sink without the new entries */
-    mock_no_blend = 1;
-    make(&D, sa, len_a, NULL, 0, 400, 1);
-    mock_no_blend = 0;
+    mock_without = MOCK_BLEND_PICTURES | MOCK_KEPT_PICTURES_OUT;
+    make_joined(&D, sa, len_a, NULL, 0, 400, 1);
+    mock_without = 0;
     {
         Inst *const ad[2] = { &A, &D };
         blend("refused_sink_without_the_entry", 2, ad, &plain, NULL, 0, 0, 0);
@@ -190,7 +135,7 @@ int main(int argc, char **argv)
     }
 
     /* a kept picture of another coded size counts as none */
-    make(&E, sa, len_a, sb, len_b, 500, 1);
+    make_joined(&E, sa, len_a, sb, len_b, 500, 1);
     {
         Inst *const e[1] = { &E };
         blend("size_a_first", 1, e, &plain, NULL, 0, 0, 0);

@@ -7,7 +7,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include "../../include/h264bsd_mi355x.h"
-long mock_jobs(void);
+#include "mock_engine.h"
 #define MAXN 64
 int main(int argc, char **argv)
 {

@@ -1,5 +1,5 @@
 /* What the host path of the cell boxes (api.c: h264bsdmiOutputCellBoxes) hands to the engine and writes back, without a GPU: bound to
- * tests/fuzz_asan/mock_engine_boxes.c, whose entries record all they are given.  Drives a fixed sequence of named calls and prints per
+ * tests/fuzz_asan/mock_engine.c, whose entries record all they are given.  Drives a fixed sequence of named calls and prints per
  * call "#name", rc, the sink's record or "sink: not called", and the output arrays, which start as a sentinel ("untouched" when none
  * of it was written, "null" when NULL was passed); at the end what the output queues of B and of its untouched twin T give.
  * tests/test_cell_boxes_host.py builds it, plain and under sanitizers, and checks every record.
@@ -7,104 +7,18 @@
  * Instances: A the 640x360 stream (640x368 coded, cropped), popped once; B the 1920x1080 stream, fed to its first picture and popped
  * later; T as B, never named in a call; G capture mode; N as A, bound to a sink that cannot keep pictures; X as A, bound to a sink
  * that has cell_maps but no cell_boxes. */
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-#include "../../include/h264bsd_mi355x.h"
-void mock_call(uint32_t n, void *const *users);
-const char *mock_record(void);
-void *mock_last_attached(void);
-uint32_t mock_configured(const void *user);
-extern int mock_fail, mock_without_keep, mock_without_boxes;
+#include "host_harness.h"
 
-#define SENT 0xA5A5A5A5u
-typedef struct Inst { storage_t *s; void *user; u8 *buf; u32 len, off, id; } Inst;      /* id: the picId its next picture carries */
-
-static void no_job(void *user, const u8 *blob, u32 bytes) { (void)user; (void)blob; (void)bytes; }
-static u8 *load(const char *path, u32 *len)
-{
-    FILE *f = fopen(path, "rb");
-    if (!f) { fprintf(stderr, "cannot read %s\n", path); exit(2); }
-    fseek(f, 0, SEEK_END); const long n = ftell(f); fseek(f, 0, SEEK_SET);
-    u8 *p = malloc((size_t)n);
-    if (!p || fread(p, 1, (size_t)n, f) != (size_t)n) exit(2);
-    fclose(f);
-    *len = (u32)n;
-    return p;
-}
-/* one more picture decoded */
-static void feed(Inst *t)
-{
-    int stalls = 0;
-    while (t->off < t->len && stalls <= 3) {
-        u32 rb = 0;
-        const u32 r = h264bsdDecode(t->s, t->buf + t->off, t->len - t->off, t->id, &rb);
-        t->off += rb;
-        stalls = rb ? 0 : stalls + 1;
-        if (r == H264BSD_PIC_RDY) { t->id++; return; }
-    }
-    fprintf(stderr, "stream ended before a picture\n"); exit(2);
-}
-static void give(Inst *t, const u8 *stream, u32 len)
-{
-    free(t->buf);
-    t->buf = malloc(len); memcpy(t->buf, stream, len); t->len = len; t->off = 0;
-}
-static void make(Inst *t, int capture, const u8 *stream, u32 len, u32 id)
-{
-    memset(t, 0, sizeof(*t));
-    t->s = h264bsdAlloc();
-    t->id = id;
-    if (capture) { if (h264bsdmiInitCapture(t->s, 0, no_job, NULL) != HANTRO_OK) exit(2); }
-    else { if (h264bsdInit(t->s, 1) != HANTRO_OK) exit(2); t->user = mock_last_attached(); }
-    give(t, stream, len);
-    feed(t);
-}
-static void pop(const char *name, Inst *t)
-{
-    u32 id = SENT;
-    const int slot = h264bsdmiNextOutputInfo(t->s, &id, NULL, NULL);
-    printf("pop %s slot=%d picId=%u size=%ux%u configured=%u\n", name, slot, id, h264bsdPicWidth(t->s), h264bsdPicHeight(t->s), t->user ? mock_configured(t->user) : 0);
-}
-
-static void show(const char *name, const u32 *a, size_t n, int passed)
-{
-    int touched = 0;
-    for (size_t i = 0; i < n; i++) touched |= a[i] != SENT;
-    printf("%s=", name);
-    if (!passed) printf("null");
-    else if (!touched) printf("untouched");
-    else for (size_t i = 0; i < n; i++) { if (a[i] == SENT) printf("%sS", i ? "," : ""); else printf("%s%u", i ? "," : "", a[i]); }
-    printf("\n");
-}
-static void head(const char *name, int rc) { printf("#%s\nrc=%d\n%s", name, rc, *mock_record() ? mock_record() : "sink: not called\n"); }
-
-/* flags: 1 kept NULL, 2 picId NULL */
-static void keep(const char *name, u32 n, Inst *const *inst, int fail, int flags)
-{
-    storage_t *dec[4]; void *users[4];
-    u32 kept[4] = { SENT, SENT, SENT, SENT }, ids[4] = { SENT, SENT, SENT, SENT };
-    for (u32 i = 0; i < n; i++) { dec[i] = inst[i]->s; users[i] = inst[i]->user; }
-    mock_fail = fail;
-    mock_call(n, users);
-    const int rc = h264bsdmiKeepCurrentPictures(n, dec, NULL, flags & 1 ? NULL : kept, flags & 2 ? NULL : ids);
-    head(name, rc);
-    show("kept", kept, n, !(flags & 1));
-    show("picId", ids, n, !(flags & 2));
-}
 /* flags: 1 got, 2 current, 4 kept, 8 picId, 16 keptPicId are NULL; 32 a stream is named; 64 the boxes spec is NULL; 128 the maps' entry
  * instead (h264bsdmiOutputCellMaps: boxes is not used) */
 static void boxes(const char *name, u32 n, Inst *const *inst, u32 nr, const h264bsdmi_region *regs, const h264bsdmi_cells_spec *spec,
-                  const h264bsdmi_boxes_spec *bspec, int fail, int flags)
+                  const h264bsdmi_boxes_spec *bspec, unsigned fail, int flags)
 {
     storage_t *dec[4]; void *users[4];
     u32 got[8], arr[4][4];
-    for (u32 i = 0; i < n; i++) { dec[i] = inst[i]->s; users[i] = inst[i]->user; }
     for (int i = 0; i < 8; i++) got[i] = SENT;
     for (int k = 0; k < 4; k++) for (int i = 0; i < 4; i++) arr[k][i] = SENT;
-    mock_fail = fail;
-    mock_call(n, users);
+    aim(n, inst, dec, users, fail);
     void *stream = flags & 32 ? (void *)(uintptr_t)0x5000 : NULL;
     u32 *a0 = flags & 2 ? NULL : arr[0], *a1 = flags & 4 ? NULL : arr[1], *a2 = flags & 8 ? NULL : arr[2], *a3 = flags & 16 ? NULL : arr[3];
     const int rc = flags & 128 ? h264bsdmiOutputCellMaps(n, dec, nr, regs, spec, stream, flags & 1 ? NULL : got, a0, a1, a2, a3)
@@ -127,12 +41,11 @@ int main(int argc, char **argv)
     make(&B, 0, sb, len_b, 200);
     make(&T, 0, sb, len_b, 200);
     make(&G, 1, sa, len_a, 300);
-    mock_without_keep = 1;
+    mock_without = MOCK_KEEP_PICTURES;
     make(&N, 0, sa, len_a, 400);
-    mock_without_keep = 0;
-    mock_without_boxes = 1;
+    mock_without = MOCK_CELL_BOXES;
     make(&X, 0, sa, len_a, 500);
-    mock_without_boxes = 0;
+    mock_without = 0;
     Inst *const ab[] = { &A, &B }, *const ba[] = { &B, &A }, *const aa[] = { &A, &A }, *const ag[] = { &A, &G }, *const an[] = { &A, &N },
          *const ax[] = { &A, &X };
     /*                                  data                        cols rows cell source crop mode planes threshold keep_after */
@@ -148,14 +61,14 @@ int main(int argc, char **argv)
     h264bsdmi_cells_spec bad;
     h264bsdmi_boxes_spec badb;
     const h264bsdmi_region regs[] = { { 1, 0, 0, 64, 64 }, { 0, -5, 7, 100, 30 }, { 1, 700, 10, 8, 8 }, { 0, 0, 0, 640, 360 } };
-    pop("A", &A); pop("N", &N); pop("X", &X);
+    pop_sized("A", &A); pop_sized("N", &N); pop_sized("X", &X);
 
     /* PICTURE needs no kept picture: A has a current one, B none yet */
     boxes("picture_a_only", 2, ab, 2, NULL, &picture, &below, 0, 0);
     /* CHANGE: nobody has kept anything: no pair, no sink */
     boxes("nothing_kept", 2, ab, 2, NULL, &change, &above, 0, 0);
     keep("keep_a_only", 2, ab, 0, 0);
-    pop("B", &B); pop("T", &T);
+    pop_sized("B", &B); pop_sized("T", &T);
     boxes("a_has_both", 2, ab, 2, NULL, &change, &above, 0, 0);           /* B: current, nothing kept -> got 1,0 */
     boxes("picture_both", 2, ab, 2, NULL, &picture, &below, 0, 0);
     boxes("count_plane", 2, ab, 2, NULL, &picture, &count, 0, 0);
@@ -164,9 +77,9 @@ int main(int argc, char **argv)
     boxes("picture_boxes", 2, ba, 4, regs, &picture, &below, 0, 32);
     boxes("null_arrays", 2, ab, 2, NULL, &change, &above, 0, 2 | 4 | 8 | 16);
     boxes("no_regions", 2, ab, 0, regs, &change, &above, 0, 1);           /* nRegions == 0: 0, nothing launched, got may be NULL */
-    boxes("boxes_fail", 2, ab, 2, NULL, &chain, &above, 1, 0);            /* -2: nothing written, and keep_after marked nothing */
-    boxes("picture_fails", 2, ab, 2, NULL, &picture, &below, 1, 0);
-    boxes("keep_after_fails", 2, ab, 2, NULL, &chain, &above, 2, 0);      /* the boxes went, the keep behind them failed: -2 all the same */
+    boxes("boxes_fail", 2, ab, 2, NULL, &chain, &above, MOCK_CELL_BOXES, 0);            /* -2: nothing written, and keep_after marked nothing */
+    boxes("picture_fails", 2, ab, 2, NULL, &picture, &below, MOCK_CELL_BOXES, 0);
+    boxes("keep_after_fails", 2, ab, 2, NULL, &chain, &above, MOCK_KEEP_PICTURES, 0);   /* the boxes went, the keep behind them failed: -2 all the same */
     boxes("b_still_not_kept", 2, ab, 2, NULL, &change, &above, 0, 0);
     boxes("keep_after", 2, ab, 2, NULL, &chain, &above, 0, 0);            /* reports what the comparison saw (1,0), then keeps A and B */
     boxes("both_kept", 2, ab, 2, NULL, &change, &above, 0, 0);
@@ -212,7 +125,7 @@ int main(int argc, char **argv)
     /* A decodes on: no current picture, the kept one stays */
     feed(&A);
     boxes("a_not_current", 1, ab, 1, NULL, &change, &above, 0, 0);
-    pop("A", &A);
+    pop_sized("A", &A);
     boxes("a_next_picture", 1, ab, 1, NULL, &change, &above, 0, 0);       /* picId 101 against the kept 100 */
 
     printf("#final\n");
@@ -220,7 +133,7 @@ int main(int argc, char **argv)
     const int slot_b = h264bsdmiNextOutputInfo(B.s, &idb, NULL, NULL), slot_t = h264bsdmiNextOutputInfo(T.s, &idt, NULL, NULL);
     printf("B next=%d,%u\nT next=%d,%u\ntwin=%d\n", slot_b, idb, slot_t, idt, slot_b == slot_t && idb == idt);
     Inst *all[] = { &A, &B, &T, &G, &N, &X };
-    for (int i = 0; i < 6; i++) { h264bsdShutdown(all[i]->s); h264bsdFree(all[i]->s); free(all[i]->buf); }
+    for (int i = 0; i < 6; i++) unmake(all[i]);
     free(sa); free(sb);
     return 0;
 }

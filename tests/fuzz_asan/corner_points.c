@@ -1,89 +1,23 @@
 /* What the host path of the corner points (api.c: h264bsdmiOutputCornerPoints) hands to the engine and writes back, without a GPU:
- * bound to tests/fuzz_asan/mock_engine_corners.c, whose entry records all it is given.  Drives a fixed sequence of named calls and
+ * bound to tests/fuzz_asan/mock_engine.c, whose entry records all it is given.  Drives a fixed sequence of named calls and
  * prints per call "#name", rc, the sink's record or "sink: not called", and the output arrays, which start as a sentinel ("untouched"
  * when none of it was written, "null" when NULL was passed).  tests/test_corner_points_host.py builds it, plain and under sanitizers,
  * and checks every record.       usage: corner_points <test_640x360.h264> <test_1920x1080.h264>
  * Instances: A the 640x360 stream (640x368 coded, cropped), B the 1920x1080 stream, each popped once; O as A on a sink without the
  * corner_points entry; G capture mode. */
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-#include "../../include/h264bsd_mi355x.h"
-void mock_call(uint32_t n, void *const *users);
-const char *mock_record(void);
-void *mock_last_attached(void);
-extern int mock_fail, mock_no_corners;
-
-#define SENT 0xA5A5A5A5u
-typedef struct Inst { storage_t *s; void *user; u8 *buf; u32 len, off, id; } Inst;      /* id: the picId its next picture carries */
-
-static void no_job(void *user, const u8 *blob, u32 bytes) { (void)user; (void)blob; (void)bytes; }
-static u8 *load(const char *path, u32 *len)
-{
-    FILE *f = fopen(path, "rb");
-    if (!f) { fprintf(stderr, "cannot read %s\n", path); exit(2); }
-    fseek(f, 0, SEEK_END); const long n = ftell(f); fseek(f, 0, SEEK_SET);
-    u8 *p = malloc((size_t)n);
-    if (!p || fread(p, 1, (size_t)n, f) != (size_t)n) exit(2);
-    fclose(f);
-    *len = (u32)n;
-    return p;
-}
-/* one more picture decoded */
-static void feed(Inst *t)
-{
-    int stalls = 0;
-    while (t->off < t->len && stalls <= 3) {
-        u32 rb = 0;
-        const u32 r = h264bsdDecode(t->s, t->buf + t->off, t->len - t->off, t->id, &rb);
-        t->off += rb;
-        stalls = rb ? 0 : stalls + 1;
-        if (r == H264BSD_PIC_RDY) { t->id++; return; }
-    }
-    fprintf(stderr, "stream ended before a picture\n"); exit(2);
-}
-static void make(Inst *t, int capture, const u8 *stream, u32 len, u32 id)
-{
-    memset(t, 0, sizeof(*t));
-    t->s = h264bsdAlloc();
-    t->id = id;
-    if (capture) { if (h264bsdmiInitCapture(t->s, 0, no_job, NULL) != HANTRO_OK) exit(2); }
-    else { if (h264bsdInit(t->s, 1) != HANTRO_OK) exit(2); t->user = mock_last_attached(); }
-    t->buf = malloc(len); memcpy(t->buf, stream, len); t->len = len;
-    feed(t);
-}
-static void pop(const char *name, Inst *t)
-{
-    u32 id = SENT;
-    const int slot = h264bsdmiNextOutputInfo(t->s, &id, NULL, NULL);
-    printf("pop %s slot=%d picId=%u\n", name, slot, id);
-}
-
-static void show(const char *name, const u32 *a, size_t n, int passed)
-{
-    int touched = 0;
-    for (size_t i = 0; i < n; i++) touched |= a[i] != SENT;
-    printf("%s=", name);
-    if (!passed) printf("null");
-    else if (!touched) printf("untouched");
-    else for (size_t i = 0; i < n; i++) { if (a[i] == SENT) printf("%sS", i ? "," : ""); else printf("%s%u", i ? "," : "", a[i]); }
-    printf("\n");
-}
+#include "host_harness.h"
 
 /* flags: 1 got, 2 current, 4 picId are NULL; 8 a stream is named; 16 dec is NULL */
-static void corners(const char *name, u32 n, Inst *const *inst, u32 nr, const h264bsdmi_region *regs, const h264bsdmi_corners_spec *spec, int fail, int flags)
+static void corners(const char *name, u32 n, Inst *const *inst, u32 nr, const h264bsdmi_region *regs, const h264bsdmi_corners_spec *spec, unsigned fail, int flags)
 {
     storage_t *dec[4]; void *users[4];
     u32 got[8], arr[2][4];
-    for (u32 i = 0; i < n; i++) { dec[i] = inst[i]->s; users[i] = inst[i]->user; }
     for (int i = 0; i < 8; i++) got[i] = SENT;
     for (int k = 0; k < 2; k++) for (int i = 0; i < 4; i++) arr[k][i] = SENT;
-    mock_fail = fail;
-    mock_call(n, users);
+    aim(n, inst, dec, users, fail);
     const int rc = h264bsdmiOutputCornerPoints(n, flags & 16 ? NULL : dec, nr, regs, spec, flags & 8 ? (void *)(uintptr_t)0x5000 : NULL,
                                                flags & 1 ? NULL : got, flags & 2 ? NULL : arr[0], flags & 4 ? NULL : arr[1]);
-    printf("#%s\nrc=%d\n%s", name, rc, *mock_record() ? mock_record() : "sink: not called\n");
+    head(name, rc);
     show("got", got, nr < 8 ? nr : 8, !(flags & 1));
     show("current", arr[0], n, !(flags & 2));
     show("picId", arr[1], n, !(flags & 4));
@@ -98,9 +32,9 @@ int main(int argc, char **argv)
     Inst A, B, O, G;
     make(&A, 0, sa, len_a, 100);
     make(&B, 0, sb, len_b, 200);
-    mock_no_corners = 1;
+    mock_without = MOCK_CORNER_POINTS;
     make(&O, 0, sa, len_a, 400);
-    mock_no_corners = 0;
+    mock_without = 0;
     make(&G, 1, sa, len_a, 300);
     Inst *const ab[] = { &A, &B }, *const ba[] = { &B, &A }, *const aa[] = { &A, &A }, *const ag[] = { &A, &G }, *const a[] = { &A }, *const o[] = { &O };
     /*                                    data  score block nms K  crop zero min_score */
@@ -124,7 +58,7 @@ int main(int argc, char **argv)
     corners("least", 1, a, 1, NULL, &least, 0, 0);
     corners("null_arrays", 2, ab, 2, NULL, &plain, 0, 2 | 4);
     corners("no_regions", 2, ab, 0, boxes, &plain, 0, 1);              /* nRegions == 0: 0, nothing called, got may be NULL */
-    corners("engine_fails", 2, ab, 2, NULL, &plain, 1, 0);             /* -2: nothing written */
+    corners("engine_fails", 2, ab, 2, NULL, &plain, MOCK_CORNER_POINTS, 0);            /* -2: nothing written */
 
     /* refused: -1, no sink, nothing written */
     corners("refused_spec_null", 2, ab, 2, NULL, NULL, 0, 0);
@@ -160,7 +94,7 @@ int main(int argc, char **argv)
     corners("a_next_picture", 1, a, 1, NULL, &plain, 0, 0);
 
     Inst *all[] = { &A, &B, &O, &G };
-    for (int i = 0; i < 4; i++) { h264bsdShutdown(all[i]->s); h264bsdFree(all[i]->s); free(all[i]->buf); }
+    for (int i = 0; i < 4; i++) unmake(all[i]);
     free(sa); free(sb);
     return 0;
 }

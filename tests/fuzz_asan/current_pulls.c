@@ -5,35 +5,13 @@
  * still gives.       usage: current_pulls <test_640x360.h264> <test_1920x1080_fullRange.h264> < cases
  * Instances: A, B popped once (motion export on); C fed to its first picture, nothing popped; D never fed; E popped, then decoded on;
  * F popped, then flushed; G capture mode; H as A without motion export; T as A, never named in a call (the untouched twin). */
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-#include "../../include/h264bsd_mi355x.h"
-void mock_call(uint32_t n, void *const *users);
-const char *mock_record(void);
-void *mock_last_attached(void);
-extern int mock_fail;
+#include "host_harness.h"
 
-#define SENT 0xA5A5A5A5u
 static const char LETTERS[] = "ABCDEFGHT";
-typedef struct Inst { storage_t *s; void *user; u8 *buf; u32 len, off, id; } Inst;      /* id: the picId its pictures carry */
 static Inst g_inst[sizeof(LETTERS) - 1];
 
-static void no_job(void *user, const u8 *blob, u32 bytes) { (void)user; (void)blob; (void)bytes; }
-static u8 *load(const char *path, u32 *len)
-{
-    FILE *f = fopen(path, "rb");
-    if (!f) { fprintf(stderr, "cannot read %s\n", path); exit(2); }
-    fseek(f, 0, SEEK_END); const long n = ftell(f); fseek(f, 0, SEEK_SET);
-    u8 *p = malloc((size_t)n);
-    if (!p || fread(p, 1, (size_t)n, f) != (size_t)n) exit(2);
-    fclose(f);
-    *len = (u32)n;
-    return p;
-}
-/* h264bsdDecode until it answers `want` (or the stream ends) */
-static void feed(Inst *t, u32 want)
+/* h264bsdDecode until it answers `want` (or the stream ends); every picture of an instance carries the one picId */
+static void feed_until(Inst *t, u32 want)
 {
     while (t->off < t->len) {
         u32 rb = 0;
@@ -43,7 +21,7 @@ static void feed(Inst *t, u32 want)
     }
     fprintf(stderr, "stream ended before status %u\n", want); exit(2);
 }
-static void make(Inst *t, char letter, const u8 *stream, u32 len)
+static void make_lettered(Inst *t, char letter, const u8 *stream, u32 len)
 {
     t->s = h264bsdAlloc();
     t->buf = malloc(len); memcpy(t->buf, stream, len); t->len = len; t->off = 0; t->id = 100u + (u32)(letter == 'T' ? 'A' : letter);
@@ -56,7 +34,7 @@ static void make(Inst *t, char letter, const u8 *stream, u32 len)
         if (letter != 'H' && h264bsdmiSetMotionExport(t->s, 1)) exit(2);
     }
     if (letter == 'D') return;
-    feed(t, H264BSD_PIC_RDY);
+    feed_until(t, H264BSD_PIC_RDY);
     if (letter == 'C' || letter == 'G') return;
     if (h264bsdmiNextOutputInfo(t->s, NULL, NULL, NULL) < 0) exit(2);
     if (letter == 'E') { u32 rb = 0; h264bsdDecode(t->s, t->buf + t->off, t->len - t->off, t->id + 1, &rb); }
@@ -77,7 +55,8 @@ static u32 *sentinels(size_t n)
     for (size_t i = 0; i < (n ? n : 1); i++) p[i] = SENT;
     return p;
 }
-static void show(const char *name, const u32 *a, size_t n, int passed)
+/* as show(), over all of sentinels(n), and what was written shows though NULL was passed */
+static void show_all(const char *name, const u32 *a, size_t n, int passed)
 {
     int touched = 0;
     n = n ? n : 1;
@@ -93,7 +72,7 @@ int main(int argc, char **argv)
     if (argc < 3) return 2;
     u32 len_a = 0, len_b = 0;
     u8 *sa = load(argv[1], &len_a), *sb = load(argv[2], &len_b);
-    for (size_t i = 0; LETTERS[i]; i++) make(&g_inst[i], LETTERS[i], LETTERS[i] == 'B' ? sb : sa, LETTERS[i] == 'B' ? len_b : len_a);
+    for (size_t i = 0; LETTERS[i]; i++) make_lettered(&g_inst[i], LETTERS[i], LETTERS[i] == 'B' ? sb : sa, LETTERS[i] == 'B' ? len_b : len_a);
     static char line[1 << 16];
     for (int idx = 0; fgets(line, sizeof(line), stdin); idx++) {
         char *tok[9], *save = NULL;
@@ -145,7 +124,7 @@ int main(int argc, char **argv)
         u32 *pgot = flags & 1 ? NULL : got, *pbox = flags & 2 ? NULL : box, *pcur = flags & 4 ? NULL : cur, *pids = flags & 8 ? NULL : ids;
         void *stream = flags & 32 ? (void *)(uintptr_t)0x5000 : NULL;
         storage_t *const *pdec = !strcmp(tok[2], "0") ? NULL : dec;
-        mock_fail = flags & 16 ? 1 : 0;
+        mock_fail = flags & 16 ? ~0u : 0;                /* every entry */
         mock_call(n < 16 ? n : 16, users);
         int rc = 99;
         if (entry == 'r') rc = h264bsdmiOutputTensorRegions(n, pdec, nr, null_items ? NULL : regs, null_spec ? NULL : &ts, null_colour ? NULL : &cs, null_aux ? NULL : &rs, stream, pgot, pbox, pcur, pids);
@@ -153,11 +132,13 @@ int main(int argc, char **argv)
         else if (entry == 'v') rc = h264bsdmiOutputMotionRegions(n, pdec, nr, null_items ? NULL : regs, null_spec ? NULL : &ms, stream, pgot, pbox, pcur, pids);
         else if (entry == 's') rc = h264bsdmiOutputRegionStats(n, pdec, nr, null_items ? NULL : regs, null_spec ? NULL : &ss, stream, pgot, pcur, pids);
         else { fprintf(stderr, "case %d: entry %c\n", idx, entry); return 2; }
-        printf("#%d\nrc=%d\n%s", idx, rc, *mock_record() ? mock_record() : "sink: not called\n");
-        show("got", got, nr, pgot != NULL);
-        if (entry == 'r' || entry == 'v') show("box", box, 4 * (size_t)nr, pbox != NULL);
-        show("current", cur, n, pcur != NULL);
-        show("picId", ids, n, pids != NULL);
+        char name[16];
+        snprintf(name, sizeof(name), "%d", idx);
+        head(name, rc);
+        show_all("got", got, nr, pgot != NULL);
+        if (entry == 'r' || entry == 'v') show_all("box", box, 4 * (size_t)nr, pbox != NULL);
+        show_all("current", cur, n, pcur != NULL);
+        show_all("picId", ids, n, pids != NULL);
         free(got); free(box); free(cur); free(ids);
     }
     /* nothing was popped: what every instance's queue gives now, and A against its untouched twin */
@@ -171,7 +152,7 @@ int main(int argc, char **argv)
         if (LETTERS[i] == 'T') printf("twin=%d\n", memcmp(first, now, sizeof(now)) == 0);
         printf("%c next=%d,%u,%u,%u\n", LETTERS[i], slot, id, idr, nerr);
     }
-    for (size_t i = 0; LETTERS[i]; i++) { h264bsdShutdown(g_inst[i].s); h264bsdFree(g_inst[i].s); free(g_inst[i].buf); }
+    for (size_t i = 0; LETTERS[i]; i++) unmake(&g_inst[i]);
     free(sa); free(sb);
     return 0;
 }

@@ -19,7 +19,6 @@ import hashlib
 import json
 import math
 import os
-import subprocess
 import sys
 import tempfile
 
@@ -27,7 +26,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 PINS = os.path.join(HERE, "current_pull_pins.json")
 STREAMS = [os.path.join(HERE, "test_640x360.h264"), os.path.join(HERE, "test_1920x1080_fullRange.h264")]
-HOST_SOURCES = ("hd_nal.c", "hd_params.c", "hd_slice.c", "hd_dpb.c", "hd_cavlc.c", "hd_resid.c", "hd_mb.c", "hd_core.c", "api.c")
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import host_program  # noqa: E402
 LIMIT = 16384
 TEXT_LIMIT = 150                # records up to this many characters are stored as they are
 MAP = 0x2000
@@ -181,25 +181,16 @@ def cases():
 def build(csrc, workdir, sanitize=None):
     """the stand-alone program — current_pulls.c and the device stand-in of this tree, the host parser and api.c of `csrc` —
     built with gcc; no HIP, no Python"""
-    exe = os.path.join(workdir, "current_pulls" + ("_san" if sanitize else ""))
-    srcs = [os.path.join(ROOT, "tests", "fuzz_asan", f) for f in ("current_pulls.c", "mock_engine.c")] + [os.path.join(csrc, f) for f in HOST_SOURCES]
-    cmd = ["gcc", "-O1", "-g", "-std=gnu11", "-Wall", f"-I{csrc}", "-DH264BSD_BUILD"]
-    if sanitize:
-        cmd += [f"-fsanitize={sanitize}", "-fno-omit-frame-pointer"]
-    b = subprocess.run(cmd + srcs + ["-lpthread", "-lm", "-o", exe], capture_output=True, text=True)
-    assert b.returncode == 0, b.stderr[-3000:]
-    return exe
+    return host_program.build("current_pulls", workdir, sanitize, csrc)
 
 
-def run(exe, env=None):
-    """(records, final, stderr): one record per case of cases(), what the instances' queues give at the end"""
+def run(exe):
+    """(records, final): one record per case of cases(), what the instances' queues give at the end; the run must be clean"""
     grid = cases()
-    r = subprocess.run([exe] + STREAMS, input="".join(c + "\n" for c in grid), capture_output=True, text=True, env=env, timeout=600)
-    assert r.returncode == 0, (r.returncode, r.stdout[-500:], r.stderr[-3000:])
-    body, final = r.stdout.split("#final\n")
+    body, final = host_program.run(exe, STREAMS, stdin="".join(c + "\n" for c in grid)).split("#final\n")
     records = ["\n".join(part.split("\n")[1:]) for part in body.split("#")[1:]]
     assert len(records) == len(grid), (len(records), len(grid))
-    return records, final, r.stderr
+    return records, final
 
 
 def pin(record):
@@ -210,7 +201,7 @@ if __name__ == "__main__":
     if len(sys.argv) != 3:
         sys.exit("usage: make_current_pull_pins.py <csrc of the commit the pins are taken from> <its name>")
     with tempfile.TemporaryDirectory() as tmp:
-        records, final, _ = run(build(os.path.abspath(sys.argv[1]), tmp))
+        records, final = run(build(os.path.abspath(sys.argv[1]), tmp))
     with open(PINS, "w") as f:
         json.dump({"recorded_from": sys.argv[2], "cases": len(records), "final": final, "pins": [pin(r) for r in records]}, f, separators=(",", ":"))
         f.write("\n")

@@ -1,44 +1,20 @@
 """What the background model's two calls — h264bsdmiBlendCurrentPictures and h264bsdmiOutputKeptPictures — hand to the engine and write
-back, without a GPU: api.c bound to a recording device stand-in (tests/fuzz_asan/mock_engine_blend.c) and driven by a stand-alone C
+back, without a GPU: api.c bound to a recording device stand-in (tests/fuzz_asan/mock_engine.c) and driven by a stand-alone C
 program (tests/fuzz_asan/background.c), built with gcc, plain and with Address-, UB- and LeakSanitizer: a host program on the CPU that
 is run directly.  Instances: A the 640x360 stream (picIds from 100), B the 1920x1080 stream (from 200), C never fed."""
-import os
 import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "h264bsd_amd", "csrc")
-HOST_SOURCES = ("hd_nal.c", "hd_params.c", "hd_slice.c", "hd_dpb.c", "hd_cavlc.c", "hd_resid.c", "hd_mb.c", "hd_core.c", "api.c")
-STREAMS = [os.path.join(ROOT, "tests", "golden", n) for n in ("test_640x360.h264", "test_1920x1080.h264")]
+import host_program
 
 pytestmark = pytest.mark.skipif(not shutil.which("gcc"), reason="no gcc")
 
 
-@pytest.fixture(scope="module", params=[None, "address,undefined"], ids=["plain", "sanitizers"])
+@pytest.fixture(scope="module", params=host_program.SANITIZERS, ids=host_program.SANITIZER_IDS)
 def records(request, tmp_path_factory):
     """name -> the lines of that call's record"""
-    exe = os.path.join(str(tmp_path_factory.mktemp("background")), "background")
-    srcs = [os.path.join(ROOT, "tests", "fuzz_asan", f) for f in ("background.c", "mock_engine_blend.c")] + [os.path.join(CSRC, f) for f in HOST_SOURCES]
-    cmd = ["gcc", "-O1", "-g", "-std=gnu11", "-Wall", f"-I{CSRC}", "-DH264BSD_BUILD"]
-    if request.param:
-        cmd += [f"-fsanitize={request.param}", "-fno-omit-frame-pointer"]
-    b = subprocess.run(cmd + srcs + ["-lpthread", "-lm", "-o", exe], capture_output=True, text=True)
-    assert b.returncode == 0, b.stderr[-3000:]
-    r = subprocess.run([exe] + STREAMS, capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"), timeout=600)
-    assert r.returncode == 0, (r.returncode, r.stdout[-500:], r.stderr[-3000:])
-    err = "\n".join(ln for ln in r.stderr.splitlines() if "left shift of negative" not in ln)      # (mirrors the reference's arithmetic)
-    assert "ERROR: AddressSanitizer" not in err and "ERROR: LeakSanitizer" not in err and "runtime error" not in err, err[-2000:]
-    out, name = {}, None
-    for ln in r.stdout.splitlines():
-        if ln.startswith("#"):
-            name = ln[1:]
-            assert name not in out
-            out[name] = []
-        else:
-            out[name].append(ln)
-    return out
+    return host_program.records("background", str(tmp_path_factory.mktemp("background")), request.param)
 
 
 def _sink(rec):
@@ -130,17 +106,3 @@ def test_the_readback_names_the_instances_that_keep_a_picture_and_their_buffers(
 def test_a_refused_readback_calls_no_sink_and_writes_nothing(records, what):
     rec = records[f"kept_out_refused_{what}"]
     assert _sink(rec) == ("rc=-1", NOT_CALLED) and _arrays(rec) == OUT_BLANK
-
-
-def test_the_mock_engines_of_the_siblings_leave_the_new_entries_unset():
-    """mock_engine_keep.c, mock_engine_kept.c and the others set the entries they know by name: JobSink grew at its end, and what they
-    do not set is the NULL of the zeroed struct they are handed (hd_create), which the two calls refuse"""
-    fuzz = os.path.join(ROOT, "tests", "fuzz_asan")
-    for f in sorted(os.listdir(fuzz)):
-        if f.startswith("mock_engine") and f != "mock_engine_blend.c":
-            assert "blend_pictures" not in open(os.path.join(fuzz, f)).read(), f
-    core = open(os.path.join(CSRC, "hd_core.c")).read()
-    assert "(HostDec *)calloc(1, sizeof(HostDec))" in core
-    hostdec = open(os.path.join(CSRC, "hostdec.h")).read()
-    members = hostdec[hostdec.index("typedef struct JobSink {"):hostdec.index("} JobSink;")]
-    assert members.index("(*cell_boxes)") < members.index("(*blend_pictures)") < members.index("(*kept_pictures_out)")

@@ -1,19 +1,14 @@
 """What an ACCEPTED cell-map call hands to the engine and writes back, without a GPU: api.c's h264bsdmiOutputCellMaps bound to a
-recording device stand-in (tests/fuzz_asan/mock_engine_cells.c) by a stand-alone C program (tests/fuzz_asan/cell_maps.c), which drives
+recording device stand-in (tests/fuzz_asan/mock_engine.c) by a stand-alone C program (tests/fuzz_asan/cell_maps.c), which drives
 a fixed sequence of named calls over two instances (A: 640x360 cropped out of 640x368 coded; B: 1920x1080 out of 1920x1088; N: as A, on
 a sink that cannot keep pictures) and prints what the sink was given and what the output arrays hold afterwards.  Built with gcc, plain
-and with Address-, UB- and LeakSanitizer: a host program on the CPU that is run directly.  The older stand-ins under tests/fuzz_asan/
-know nothing of the new sink entry and must still compile."""
-import os
+and with Address-, UB- and LeakSanitizer: a host program on the CPU that is run directly (tests/host_program.py)."""
 import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "h264bsd_amd", "csrc")
-HOST_SOURCES = ("hd_nal.c", "hd_params.c", "hd_slice.c", "hd_dpb.c", "hd_cavlc.c", "hd_resid.c", "hd_mb.c", "hd_core.c", "api.c")
-STREAMS = [os.path.join(ROOT, "tests", "golden", n) for n in ("test_640x360.h264", "test_1920x1080.h264")]
+import host_program
+
 PICTURE = " spec 0x1000 grid=23x40 cell=16 source=1 crop=1 mode=0 planes=31 thr=0,0,0 keep_after=0"
 CHANGE = " spec 0x1004 grid=68x120 cell=8 source=0 crop=1 mode=1 planes=35 thr=3,2,1 keep_after=0"
 CHAIN = " spec 0x2000 grid=5x6 cell=4 source=2 crop=1 mode=1 planes=63 thr=0,0,255 keep_after=1"
@@ -22,32 +17,10 @@ BLANK = dict(got="untouched", current="untouched", kept="untouched", picId="unto
 pytestmark = pytest.mark.skipif(not shutil.which("gcc"), reason="no gcc")
 
 
-@pytest.fixture(scope="module", params=[None, "address,undefined"], ids=["plain", "sanitizers"])
+@pytest.fixture(scope="module", params=host_program.SANITIZERS, ids=host_program.SANITIZER_IDS)
 def records(request, tmp_path_factory):
     """name -> the lines of that call's record; "pops": the pop lines in order; "final": the lines behind #final"""
-    exe = os.path.join(str(tmp_path_factory.mktemp("cell_maps")), "cell_maps")
-    srcs = [os.path.join(ROOT, "tests", "fuzz_asan", f) for f in ("cell_maps.c", "mock_engine_cells.c")] + [os.path.join(CSRC, f) for f in HOST_SOURCES]
-    cmd = ["gcc", "-O1", "-g", "-std=gnu11", "-Wall", f"-I{CSRC}", "-DH264BSD_BUILD"]
-    if request.param:
-        cmd += [f"-fsanitize={request.param}", "-fno-omit-frame-pointer"]
-    b = subprocess.run(cmd + srcs + ["-lpthread", "-lm", "-o", exe], capture_output=True, text=True)
-    assert b.returncode == 0, b.stderr[-3000:]
-    r = subprocess.run([exe] + STREAMS, capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"), timeout=600)
-    assert r.returncode == 0, (r.returncode, r.stdout[-500:], r.stderr[-3000:])
-    err = "\n".join(ln for ln in r.stderr.splitlines() if "left shift of negative" not in ln)      # (mirrors the reference's arithmetic)
-    assert "ERROR: AddressSanitizer" not in err and "ERROR: LeakSanitizer" not in err and "runtime error" not in err, err[-2000:]
-    out = {"pops": []}
-    name = None
-    for ln in r.stdout.splitlines():
-        if ln.startswith("pop "):
-            out["pops"].append(ln)
-        elif ln.startswith("#"):
-            name = ln[1:]
-            assert name not in out
-            out[name] = []
-        else:
-            out[name].append(ln)
-    return out
+    return host_program.records("cell_maps", str(tmp_path_factory.mktemp("cell_maps")), request.param)
 
 
 def _arrays(rec):
@@ -154,14 +127,3 @@ def test_a_sink_that_cannot_keep_serves_picture_mode(records):
 def test_the_twins_output_queue_is_untouched(records):
     final = records["final"]
     assert "twin=1" in final and final[0].split("=")[1] == final[1].split("=")[1]
-
-
-def test_the_older_stand_ins_compile_and_leave_the_new_entry_null(tmp_path):
-    """mock_engine.c and mock_engine_keep.c set the entries they know by name: JobSink grew at its end, and what they do not set is the
-    calloc'ed NULL (hd_create) that api.c reads as "this sink has no cell maps" """
-    for f in ("mock_engine.c", "mock_engine_keep.c"):
-        path = os.path.join(ROOT, "tests", "fuzz_asan", f)
-        assert "cell_maps" not in open(path).read()
-        b = subprocess.run(["gcc", "-O1", "-std=gnu11", "-Wall", "-Werror", f"-I{CSRC}", "-DH264BSD_BUILD", "-c", path, "-o", str(tmp_path / (f + ".o"))],
-                           capture_output=True, text=True)
-        assert b.returncode == 0, b.stderr[-3000:]

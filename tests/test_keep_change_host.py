@@ -1,48 +1,21 @@
 """What an ACCEPTED keep or comparison hands to the engine and writes back, without a GPU: api.c's h264bsdmiKeepCurrentPictures and
-h264bsdmiOutputRegionChange bound to a recording device stand-in (tests/fuzz_asan/mock_engine_keep.c) by a stand-alone C program
+h264bsdmiOutputRegionChange bound to a recording device stand-in (tests/fuzz_asan/mock_engine.c) by a stand-alone C program
 (tests/fuzz_asan/keep_change.c), which drives a fixed sequence of named calls over two instances (A: 640x360 cropped out of 640x368
 coded; B: 1920x1080 out of 1920x1088) and prints what the sink was given and what the output arrays hold afterwards.  Built with gcc,
 plain and with Address-, UB- and LeakSanitizer: a host program on the CPU that is run directly."""
-import os
 import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "h264bsd_amd", "csrc")
-HOST_SOURCES = ("hd_nal.c", "hd_params.c", "hd_slice.c", "hd_dpb.c", "hd_cavlc.c", "hd_resid.c", "hd_mb.c", "hd_core.c", "api.c")
-STREAMS = [os.path.join(ROOT, "tests", "golden", n) for n in ("test_640x360.h264", "test_1920x1080.h264")]
+import host_program
 
 pytestmark = pytest.mark.skipif(not shutil.which("gcc"), reason="no gcc")
 
 
-@pytest.fixture(scope="module", params=[None, "address,undefined"], ids=["plain", "sanitizers"])
+@pytest.fixture(scope="module", params=host_program.SANITIZERS, ids=host_program.SANITIZER_IDS)
 def records(request, tmp_path_factory):
     """name -> the lines of that call's record; "pops": the pop lines in order; "final": the lines behind #final"""
-    exe = os.path.join(str(tmp_path_factory.mktemp("keep_change")), "keep_change")
-    srcs = [os.path.join(ROOT, "tests", "fuzz_asan", f) for f in ("keep_change.c", "mock_engine_keep.c")] + [os.path.join(CSRC, f) for f in HOST_SOURCES]
-    cmd = ["gcc", "-O1", "-g", "-std=gnu11", "-Wall", f"-I{CSRC}", "-DH264BSD_BUILD"]
-    if request.param:
-        cmd += [f"-fsanitize={request.param}", "-fno-omit-frame-pointer"]
-    b = subprocess.run(cmd + srcs + ["-lpthread", "-lm", "-o", exe], capture_output=True, text=True)
-    assert b.returncode == 0, b.stderr[-3000:]
-    r = subprocess.run([exe] + STREAMS, capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"), timeout=600)
-    assert r.returncode == 0, (r.returncode, r.stdout[-500:], r.stderr[-3000:])
-    err = "\n".join(ln for ln in r.stderr.splitlines() if "left shift of negative" not in ln)      # (mirrors the reference's arithmetic)
-    assert "ERROR: AddressSanitizer" not in err and "ERROR: LeakSanitizer" not in err and "runtime error" not in err, err[-2000:]
-    out = {"pops": []}
-    name = None
-    for ln in r.stdout.splitlines():
-        if ln.startswith("pop "):
-            out["pops"].append(ln)
-        elif ln.startswith("#"):
-            name = ln[1:]
-            assert name not in out
-            out[name] = []
-        else:
-            out[name].append(ln)
-    return out
+    return host_program.records("keep_change", str(tmp_path_factory.mktemp("keep_change")), request.param)
 
 
 def _arrays(rec):

@@ -158,13 +158,8 @@ def test_batch_calls_under_sanitizers(tmp_path, sanitizer):
     if not shutil.which("gcc"):
         pytest.skip("no gcc")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    C = os.path.join(root, "h264bsd_amd", "csrc")
-    exe = str(tmp_path / "batch_san")
-    srcs = [os.path.join(root, "tests", "fuzz_asan", f) for f in ("batch_tsan.c", "mock_engine.c")] + \
-           [os.path.join(C, f) for f in ("hd_nal.c", "hd_params.c", "hd_slice.c", "hd_dpb.c", "hd_cavlc.c", "hd_resid.c", "hd_mb.c", "hd_core.c", "api.c")]
-    b = subprocess.run(["gcc", "-O1", "-g", f"-fsanitize={sanitizer}", "-fno-omit-frame-pointer", "-std=gnu11", f"-I{C}", "-DH264BSD_BUILD"] + srcs +
-                       ["-lpthread", "-o", exe], capture_output=True, text=True, timeout=600)
-    assert b.returncode == 0, b.stderr[-2000:]
+    import host_program
+    exe = host_program.build("batch_tsan", str(tmp_path), sanitizer)
     r = subprocess.run([exe, os.path.join(root, "tests", "golden", "test_640x360.h264"), "12", "6"], capture_output=True, text=True, timeout=900,
                        env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1", TSAN_OPTIONS="halt_on_error=0"))
     out = "\n".join(ln for ln in (r.stdout + r.stderr).splitlines() if "left shift of negative" not in ln)   # (mirrors the reference's arithmetic)
