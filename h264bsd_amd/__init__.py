@@ -14,6 +14,7 @@ from .capi import (  # noqa: F401
     CornersSpec, CornerPoints, pull_corners, corners_record_bytes,
     CellsSpec, CellMaps, pull_cells,
     BoxesSpec, CellBoxes, pull_boxes,
+    CellShiftSpec, CellShift, pull_flow,
     BlendSpec, BLEND_FROZEN, blend_pictures, pull_kept,
 )
 
@@ -21,5 +22,5 @@ from .capi import (  # noqa: F401
 # 0.4: keep_pictures / pull_change (h264bsdmiKeepCurrentPictures, h264bsdmiOutputRegionChange); 0.5: pull_cells (h264bsdmiOutputCellMaps)
 # 0.6: pull_boxes (h264bsdmiOutputCellBoxes); 0.7: pull_shift (h264bsdmiOutputRegionShift)
 # 0.8: blend_pictures / pull_kept (h264bsdmiBlendCurrentPictures, h264bsdmiOutputKeptPictures)
-# 0.9: pull_corners (h264bsdmiOutputCornerPoints)
-__version__ = "0.9.0"
+# 0.9: pull_corners (h264bsdmiOutputCornerPoints); 0.10: pull_flow (h264bsdmiOutputCellShift)
+__version__ = "0.10.0"

@@ -28,7 +28,7 @@ EXPORTED_SYMBOLS = [
     "h264bsdCroppingParams", "h264bsdSampleAspectRatio", "h264bsdCheckValidParamSets", "h264bsdFlushBuffer",
     "h264bsdProfile", "h264bsdAlloc", "h264bsdFree", "h264bsdConvertToRGBA", "h264bsdConvertToBGRA",
     "h264bsdConvertToYCbCrA",
-    "h264bsdmiInitCapture", "h264bsdmiNextOutputInfo", "h264bsdmiNextOutputPictureDevice", "h264bsdmiNextOutputTensorBatch", "h264bsdmiNextOutputTensorBatchColour", "h264bsdmiNextOutputTensorBatchResize", "h264bsdmiOutputTensorRegions", "h264bsdmiOutputTensorRemap", "h264bsdmiSetMotionExport", "h264bsdmiOutputMotionRegions", "h264bsdmiOutputRegionStats", "h264bsdmiKeepCurrentPictures", "h264bsdmiBlendCurrentPictures", "h264bsdmiOutputKeptPictures", "h264bsdmiOutputRegionChange", "h264bsdmiOutputRegionShift", "h264bsdmiOutputCornerPoints", "h264bsdmiOutputCellMaps", "h264bsdmiOutputCellBoxes", "h264bsdmiJobFinalize", "h264bsdmiDeviceCount", "h264bsdmiSetDevice", "h264bsdmiFlush", "h264bsdmiFlushAsync", "h264bsdmiDeviceErrors",
+    "h264bsdmiInitCapture", "h264bsdmiNextOutputInfo", "h264bsdmiNextOutputPictureDevice", "h264bsdmiNextOutputTensorBatch", "h264bsdmiNextOutputTensorBatchColour", "h264bsdmiNextOutputTensorBatchResize", "h264bsdmiOutputTensorRegions", "h264bsdmiOutputTensorRemap", "h264bsdmiSetMotionExport", "h264bsdmiOutputMotionRegions", "h264bsdmiOutputRegionStats", "h264bsdmiKeepCurrentPictures", "h264bsdmiBlendCurrentPictures", "h264bsdmiOutputKeptPictures", "h264bsdmiOutputRegionChange", "h264bsdmiOutputRegionShift", "h264bsdmiOutputCornerPoints", "h264bsdmiOutputCellMaps", "h264bsdmiOutputCellBoxes", "h264bsdmiOutputCellShift", "h264bsdmiJobFinalize", "h264bsdmiDeviceCount", "h264bsdmiSetDevice", "h264bsdmiFlush", "h264bsdmiFlushAsync", "h264bsdmiDeviceErrors",
     "h264bsdmiDecodePicture", "h264bsdmiDecodePictureBatch", "h264bsdmiNextOutputPictureBatch", "h264bsdmiPullAndDecodePictureBatch", "h264bsdmiSetParserThreads", "h264bsdmiSetInputReadOnly", "h264bsdmiSetCopyElision",
     "h264bsdmiReplayCreate", "h264bsdmiReplayCreateStaggered", "h264bsdmiReplayCreateDesync", "h264bsdmiReplayCreateSched", "h264bsdmiReplayReschedule", "h264bsdmiReplayDestroy", "h264bsdmiReplayRun", "h264bsdmiReplaySync",
     "h264bsdmiReplayFetch", "h264bsdmiReplayDbkRecords", "h264bsdmiReplayChecksums", "h264bsdmiReplayConvert", "h264bsdmiReplayFetchConverted",
@@ -122,6 +122,12 @@ class CellsSpec(ctypes.Structure):
                 ("threshold", ctypes.c_uint32 * 3), ("keep_after", ctypes.c_uint32)]
 
 
+class CellShiftSpec(ctypes.Structure):
+    """h264bsdmi_cell_shift_spec (include/h264bsd_mi355x.h)"""
+    _fields_ = [("data", ctypes.c_void_p), ("cols", ctypes.c_uint32), ("rows", ctypes.c_uint32), ("cell", ctypes.c_uint32),
+                ("radius", ctypes.c_uint32), ("planes", ctypes.c_uint32), ("crop", ctypes.c_uint32), ("keep_after", ctypes.c_uint32)]
+
+
 class BoxesSpec(ctypes.Structure):
     """h264bsdmi_boxes_spec (include/h264bsd_mi355x.h)"""
     _fields_ = [("data", ctypes.c_void_p), ("max_boxes", ctypes.c_uint32), ("plane", ctypes.c_uint32), ("channel", ctypes.c_uint32),
@@ -136,6 +142,8 @@ BOXES_SENSES = {"above": 0, "below": 1}                                         
 # per mode (H264BSDMI_CELLS_PICTURE, _CHANGE): name -> H264BSDMI_CELL_*, in the order of the maps
 CELL_PLANES = ({"count": 1, "sum": 2, "sumsq": 4, "min": 8, "max": 16}, {"count": 1, "sad": 2, "ssd": 4, "dsum": 8, "dmax": 16, "above": 32})
 CELL_SIZES = (4, 8, 16, 32, 64)
+FLOW_PLANES = {"count": 1, "dx": 2, "dy": 4, "best": 8, "still": 16, "ties": 32}    # name -> H264BSDMI_FLOW_*, in the order of the maps
+FLOW_CELL_SIZES = (8, 16, 32, 64)
 STATS_SOURCES = {"y": (0, 1), "ycbcr": (1, 3), "rgb": (2, 3)}                    # name -> (H264BSDMI_STATS_*, channels)
 STATS_BINS = (0, 16, 32, 64, 128, 256)
 MOTION_PLANES = {"mv": (1, 2), "valid": (2, 1), "age": (4, 1), "qp": (8, 1)}     # name -> (H264BSDMI_MOTION_PLANE_*, channels), in channel order
@@ -289,6 +297,9 @@ def _declare(L, harness):
     L.h264bsdmiOutputCellBoxes.argtypes = [u32, ctypes.POINTER(vp), u32, ctypes.POINTER(Region), ctypes.POINTER(CellsSpec), ctypes.POINTER(BoxesSpec), vp,
                                            P32, P32, P32, P32, P32]
     L.h264bsdmiOutputCellBoxes.restype = ctypes.c_int
+    L.h264bsdmiOutputCellShift.argtypes = [u32, ctypes.POINTER(vp), u32, ctypes.POINTER(Region), ctypes.POINTER(CellShiftSpec), vp,
+                                           P32, P32, P32, P32, P32]
+    L.h264bsdmiOutputCellShift.restype = ctypes.c_int
     L.h264bsdmiDecodePicture.argtypes = [vp, u8p, u32, u32, P32, P32]
     L.h264bsdmiDecodePicture.restype = u32
     L.h264bsdmiDecodePictureBatch.argtypes = [u32, ctypes.POINTER(vp), ctypes.POINTER(vp), P32, P32, P32, P32, P32]
@@ -1269,6 +1280,56 @@ def pull_cells(decoders, regions=None, cell=16, grid=None, source="y", planes=("
     spec = CellsSpec(out.data_ptr(), grid[1], grid[0], cell, src, 1 if crop else 0, mode, bits, (ctypes.c_uint32 * 3)(*thr), 1 if keep else 0)
     return CellMaps(out, mode, C, bits,
                     *_kept_pull("h264bsdmiOutputCellMaps", decoders, K, regs, (ctypes.byref(spec),), stream, n > 0 and K > 0))
+
+
+class CellShift:
+    """what pull_flow returns: maps [R, P, rows, cols] int32, the C layout, and views of it by name, [R, rows, cols] each: count, dx, dy,
+    best, still, ties; a plane that was not requested is None.  gain: still - best, computed on the device.  got [R], and per decoder
+    current, kept, pic_id, kept_pic_id, lists of ints"""
+
+    def __init__(self, maps, cell, radius, planes, got, current, kept, pic_id, kept_pic_id):
+        self.maps, self.cell, self.radius, self.planes = maps, cell, radius, planes
+        at = 0
+        for name, bit in FLOW_PLANES.items():
+            setattr(self, name, maps[:, at] if planes & bit else None)
+            at += 1 if planes & bit else 0
+        self.got, self.current, self.kept, self.pic_id, self.kept_pic_id = got, current, kept, pic_id, kept_pic_id
+
+    @property
+    def gain(self):
+        """[R, rows, cols] int32: still - best, what the best displacement explains of the change; 0 where nothing moved or nothing helps"""
+        if self.still is None or self.best is None:
+            raise ValueError("CellShift.gain: needs the planes 'still' and 'best'")
+        return self.still - self.best
+
+
+def pull_flow(decoders, regions=None, cell=16, grid=None, radius=4, planes=("dx", "dy", "best"), crop=True, keep=False, out=None, stream=None):
+    """h264bsdmiOutputCellShift: dense block-matching motion maps — for every cell x cell luma samples of boxes of the decoders' KEPT
+    pictures (keep_pictures, blend_pictures) where it lies in their CURRENT pictures, pull_shift's SAD search over every displacement
+    |dx|, |dy| <= radius (0..16) once per cell, by one kernel launch where the two pictures lie; nothing is popped and no pixel is
+    pulled.  regions, crop and stream as for pull_shift (no limit on w, h beyond the regions' own); cell: 8, 16, 32 or 64; grid as for
+    pull_cells.  planes out of "count", "dx", "dy", "best", "still", "ties".  Cell (i, j) of a region holds what pull_shift gives for the
+    box (x + j cell, y + i cell, min(cell, w - j cell), min(cell, h - i cell)); the current picture is replicated at the border of the
+    source window, not of the cell; cells the box or the window do not reach have count 0, (0, 0) and ties (2 radius + 1)^2.  out: a
+    contiguous CUDA int32 tensor [R, P, rows, cols] to write into; slices of decoders without a current or without a kept picture are
+    left untouched (got[r] = 0).  keep=True: behind the search the current pictures become the kept ones, as for pull_change.  Returns
+    a CellShift."""
+    import torch
+    n = len(decoders)
+    if cell not in FLOW_CELL_SIZES:
+        raise ValueError(f"pull_flow: cell is one of {FLOW_CELL_SIZES}, not {cell}")
+    if not isinstance(radius, int) or isinstance(radius, bool) or not 0 <= radius <= SHIFT_MAX_RADIUS:
+        raise ValueError(f"pull_flow: radius is an int in 0..{SHIFT_MAX_RADIUS}, not {radius}")
+    names = (planes,) if isinstance(planes, str) else tuple(planes)
+    if not names or any(p not in FLOW_PLANES for p in names):
+        raise ValueError(f"pull_flow: planes is a non-empty choice of {tuple(FLOW_PLANES)}, not {planes}")
+    bits = sum({FLOW_PLANES[p] for p in names})
+    _, _, _, _, _, K, regs, grid = _cells_args("pull_flow", decoders, regions, cell, grid, "y", ("count",), "kept", 0, crop, keep)
+    shape = (K, bin(bits).count("1"), grid[0], grid[1])
+    out, stream = _out_and_stream("pull_flow", out, shape, torch.int32, stream)
+    spec = CellShiftSpec(out.data_ptr(), grid[1], grid[0], cell, radius, bits, 1 if crop else 0, 1 if keep else 0)
+    return CellShift(out, cell, radius, bits,
+                     *_kept_pull("h264bsdmiOutputCellShift", decoders, K, regs, (ctypes.byref(spec),), stream, n > 0 and K > 0))
 
 
 class CellBoxes:

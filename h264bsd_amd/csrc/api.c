@@ -19,6 +19,8 @@
 #include "../../include/h264bsd_mi355x_bench.h"
 #include "hostdec.h"
 #include "engine.h"
+#pragma weak eng_sink_entries     /* an engine without it (a device stand-in of the tests) gives NULL: the calls that need an entry of it refuse */
+static const EngSinkEntries *sink_entries(const JobSink *k) { return eng_sink_entries ? eng_sink_entries(k) : NULL; }
 
 HostDec *hd_create(int no_output_reordering);
 void hd_destroy(HostDec *d);
@@ -370,7 +372,7 @@ int h264bsdmiNextOutputTensorBatchResize(u32 n, storage_t *const *dec, const h26
  *   pull_regions      the regions (or one whole window per instance) of the pictures that exist, each with its rectangle
  *   pull_finish       after the sink: got, box, current and picId — unless the sink failed (-2 writes nothing) — and the lists freed
  * A refused call returns -1 and has called no sink, written nothing; no call pops anything. */
-enum { PULL_REGIONS, PULL_REMAP, PULL_MOTION, PULL_STATS, PULL_CHANGE, PULL_KEEP, PULL_CELLS, PULL_BOXES, PULL_SHIFT, PULL_CORNERS };
+enum { PULL_REGIONS, PULL_REMAP, PULL_MOTION, PULL_STATS, PULL_CHANGE, PULL_KEEP, PULL_CELLS, PULL_BOXES, PULL_SHIFT, PULL_CORNERS, PULL_FLOW };
 #define NO_PIC 0xFFFFFFFFu
 typedef struct CurrentPull {
     u32 n, m, k;                /* instances; pictures and items gathered so far */
@@ -380,7 +382,7 @@ typedef struct CurrentPull {
     SinkRegion *regs;           /* the items for the sink: regions, or (PULL_REMAP) maps */
     SinkRemap *maps;
     int kind;                   /* PULL_* */
-    int vs_kept;                /* only instances that have a kept picture too: PULL_CHANGE, PULL_SHIFT, and PULL_CELLS / PULL_BOXES in CHANGE mode */
+    int vs_kept;                /* only instances that have a kept picture too: PULL_CHANGE, PULL_SHIFT, PULL_FLOW, and PULL_CELLS / PULL_BOXES in CHANGE mode */
 } CurrentPull;
 
 /* regions == NULL: no regions at all, or (whole: one whole window per instance) exactly n */
@@ -411,6 +413,7 @@ static int sink_pulls(const ApiDec *a, int kind)
     case PULL_KEEP:   return k->tensor_regions != NULL && k->keep_pictures != NULL;
     case PULL_CELLS:  return k->tensor_regions != NULL && k->cell_maps != NULL;      /* CHANGE mode: keep_pictures too (the entry asks) */
     case PULL_BOXES:  return k->tensor_regions != NULL && k->cell_maps != NULL && k->cell_boxes != NULL;
+    case PULL_FLOW:   return k->tensor_regions != NULL && k->keep_pictures != NULL && sink_entries(k) && sink_entries(k)->cell_shift != NULL;      /* (engine.h) */
     }
     return k->tensor_regions != NULL;
 }
@@ -685,7 +688,7 @@ int h264bsdmiOutputKeptPictures(u32 n, storage_t *const *dec, void *const *pictu
 
 /* The host path of the pulls that may compare against kept pictures and may keep afterwards, behind their own spec checks:
  * h264bsdmiOutputRegionChange (PULL_CHANGE), h264bsdmiOutputRegionShift (PULL_SHIFT), h264bsdmiOutputCellMaps (PULL_CELLS) and
- * h264bsdmiOutputCellBoxes (PULL_BOXES, spec2 its boxes spec).  vs_kept: only instances that have a kept picture too; max_side: the
+ * h264bsdmiOutputCellBoxes (PULL_BOXES, spec2 its boxes spec), h264bsdmiOutputCellShift (PULL_FLOW).  vs_kept: only instances that have a kept picture too; max_side: the
  * longest side a region may have (0: whatever regions_refused allows); keep_after: behind the sink's entry the keep call's launch for
  * every instance with a current picture.  kept / keptPicId are what the comparison saw; -2 writes nothing, marks nothing */
 static int kept_pull(int kind, int vs_kept, u32 n, storage_t *const *dec, u32 nRegions, const h264bsdmi_region *regions, u32 max_side,
@@ -710,6 +713,7 @@ static int kept_pull(int kind, int vs_kept, u32 n, storage_t *const *dec, u32 nR
         case PULL_CHANGE: failed = sink->region_change(c.m, c.pics, c.k, c.regs, (const h264bsdmi_change_spec *)spec, stream); break;
         case PULL_SHIFT:  failed = sink->region_shift(c.m, c.pics, c.k, c.regs, (const h264bsdmi_shift_spec *)spec, stream); break;
         case PULL_CELLS:  failed = sink->cell_maps(c.m, c.pics, c.k, c.regs, (const h264bsdmi_cells_spec *)spec, stream); break;
+        case PULL_FLOW:   failed = sink_entries(sink)->cell_shift(c.m, c.pics, c.k, c.regs, (const h264bsdmi_cell_shift_spec *)spec, stream); break;
         default:          failed = sink->cell_boxes(c.m, c.pics, c.k, c.regs, (const h264bsdmi_cells_spec *)spec, (const h264bsdmi_boxes_spec *)spec2, stream);
         }
     }
@@ -796,6 +800,24 @@ int h264bsdmiOutputCellBoxes(u32 n, storage_t *const *dec, u32 nRegions, const h
                              u32 *got, u32 *current, u32 *kept, u32 *picId, u32 *keptPicId)
 {
     return cells_pull(PULL_BOXES, n, dec, nRegions, regions, cells, boxes, stream, got, current, kept, picId, keptPicId);
+}
+
+/* Per cell of a grid where it went: h264bsdmiOutputCellMaps' regions and grid in CHANGE mode, h264bsdmiOutputRegionShift's search */
+static int cell_shift_spec_refused(const h264bsdmi_cell_shift_spec *s)
+{
+    const u32 allowed = H264BSDMI_FLOW_COUNT | H264BSDMI_FLOW_DX | H264BSDMI_FLOW_DY | H264BSDMI_FLOW_BEST | H264BSDMI_FLOW_STILL | H264BSDMI_FLOW_TIES;
+    if (!s || !s->data || ((uintptr_t)s->data & 3u)) return 1;
+    if (!s->cols || s->cols > 4096u || !s->rows || s->rows > 4096u) return 1;
+    if (s->cell != 8 && s->cell != 16 && s->cell != 32 && s->cell != 64) return 1;
+    if (s->radius > H264BSDMI_SHIFT_MAX_RADIUS || s->crop > 1 || s->keep_after > 1) return 1;
+    return !s->planes || (s->planes & ~allowed);
+}
+int h264bsdmiOutputCellShift(u32 n, storage_t *const *dec, u32 nRegions, const h264bsdmi_region *regions,
+                             const h264bsdmi_cell_shift_spec *spec, void *stream,
+                             u32 *got, u32 *current, u32 *kept, u32 *picId, u32 *keptPicId)
+{
+    if (cell_shift_spec_refused(spec)) return -1;
+    return kept_pull(PULL_FLOW, 1, n, dec, nRegions, regions, 0, spec, NULL, spec->crop, spec->keep_after, stream, got, current, kept, picId, keptPicId);
 }
 
 static u32 *next_converted(storage_t *s, u32 *picId, u32 *isIdrPic, u32 *numErrMbs, int fmt)

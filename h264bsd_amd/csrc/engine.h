@@ -19,6 +19,21 @@ void eng_convert_host(int fmt, uint32_t width, uint32_t height, const uint8_t *d
  * many were written to cpus[]; 0 when the topology cannot be read). */
 int  eng_sink_device(const JobSink *sink);
 int  eng_device_cpus(int device, int *cpus, int max);
+/* The entries of the engine that came after the last member of JobSink, per sink: what eng_attach would have set in the sink had they
+ * been members, NULL for a sink that is not this engine's or has none of them.  A function of the engine beside the sink, to which
+ * api.c refers WEAKLY: a device stand-in that was written before it (tests/fuzz_asan) links unchanged, the address is NULL there and
+ * api.c refuses the calls that need an entry — refused, not broken — and no stand-in has to grow with the table.  An entry that is
+ * NULL in the table is refused likewise.
+ *   cell_shift  h264bsdmiOutputCellShift: per cell of a grid over n_regions boxes of the n pictures (distinct instances of one device,
+ *               as for JobSink.region_shift) where it lies in the picture against its instance's kept picture — region_shift's search,
+ *               one per cell — slice `index` of spec->data each, with one launch.  Every picture's instance has a kept picture of its
+ *               coded size; spec->keep_after is not looked at (the caller follows up with keep_pictures).  Called through the table
+ *               of any of the n sinks.  0 = ok; <0 = error, nothing enqueued */
+typedef struct EngSinkEntries {
+    int (*cell_shift)(uint32_t n, const SinkTensorPic *pics, uint32_t n_regions, const SinkRegion *regions,
+                      const struct h264bsdmi_cell_shift_spec *spec, void *stream);
+} EngSinkEntries;
+const EngSinkEntries *eng_sink_entries(const JobSink *sink);
 
 #ifdef __cplusplus
 }

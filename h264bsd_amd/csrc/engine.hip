@@ -44,6 +44,7 @@
 #include "kernels/k_blend.hip.h"
 #include "kernels/k_region_change.hip.h"
 #include "kernels/k_region_shift.hip.h"
+#include "kernels/k_cell_shift.hip.h"
 #include "kernels/k_corner_points.hip.h"
 #include "kernels/k_cell_maps.hip.h"
 #include "kernels/k_cell_boxes.hip.h"
@@ -168,11 +169,11 @@ constexpr uint32_t LANE_DBK_WAVES = LANE_DBK_WAVES_N;
 
 /* the item stride of the tensor pulls' staging ring: k_tensor_out / k_tensor_resize read TensorItems, k_tensor_aa AaItems, k_tensor_roi
  * RoiItems, k_motion_roi MotionItems, k_tensor_remap RemapItems, k_region_stats StatsItems, k_keep KeepItems, k_blend BlendItems, k_kept_out KeptOutItems, k_region_change ChangeItems, k_region_shift ShiftItems, k_corner_points CornerItems,
- * k_cell_maps CellItems (k_cell_boxes: the same, and its BoxItems in slots of their own behind them) */
+ * k_cell_maps CellItems (k_cell_boxes: the same, and its BoxItems in slots of their own behind them), k_cell_shift FlowItems */
 constexpr size_t TITEM_BYTES = std::max({ sizeof(h264k::TensorItem), sizeof(h264k::AaItem), sizeof(h264k::RoiItem), sizeof(h264k::MotionItem),
                                           sizeof(h264k::RemapItem), sizeof(h264k::StatsItem), sizeof(h264k::KeepItem), sizeof(h264k::ChangeItem),
                                           sizeof(h264k::CellItem), sizeof(h264k::BoxItem), sizeof(h264k::ShiftItem), sizeof(h264k::BlendItem),
-                                          sizeof(h264k::KeptOutItem), sizeof(h264k::CornerItem) });
+                                          sizeof(h264k::KeptOutItem), sizeof(h264k::CornerItem), sizeof(h264k::FlowItem) });
 struct TItemSlot { uint8_t bytes[TITEM_BYTES]; };
 struct Engine {
     std::mutex mu;
@@ -1821,6 +1822,45 @@ static int cell_boxes_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pic
     return L.change ? kept_order_end(e, st) : 0;
 }
 
+/* h264bsdmiOutputCellShift: one FlowItem per region — the current picture and the kept picture of its instance, the slice, the box's
+ * origin (signed), box ∩ window and the window itself (the search clamps there) in luma samples of the coded frame — and ONE k_cell_shift
+ * launch of (rectangles of the grid, regions) workgroups inside the kept pictures' ordering.  Every cell is owned by one workgroup: no
+ * scratch.  The kept pictures as in shift_out_locked; keep_after is not looked at. */
+static int flow_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, uint32_t n_regs, const SinkRegion *regs,
+                           const h264bsdmi_cell_shift_spec &sp, hipStream_t st, hipEvent_t *fence_ev)
+{
+    const uint32_t all = H264BSDMI_FLOW_COUNT | H264BSDMI_FLOW_DX | H264BSDMI_FLOW_DY | H264BSDMI_FLOW_BEST | H264BSDMI_FLOW_STILL | H264BSDMI_FLOW_TIES;
+    uint32_t shift = h264k::FLOW_MIN_SHIFT;
+    while (shift < h264k::FLOW_MAX_SHIFT && (1u << shift) != sp.cell) shift++;
+    if (!sp.data || (reinterpret_cast<uintptr_t>(sp.data) & 3u) || (1u << shift) != sp.cell) return -1;
+    if (!sp.cols || sp.cols > h264k::FLOW_MAX_GRID || !sp.rows || sp.rows > h264k::FLOW_MAX_GRID) return -1;
+    if (sp.radius > H264BSDMI_SHIFT_MAX_RADIUS || !sp.planes || (sp.planes & ~all) || sp.crop > 1u || sp.keep_after > 1u) return -1;
+    if (n_regs > 65535u) return -1;                                     /* grid.y */
+    if (!pull_pictures_ok(n, pics, true, false) || !pull_regions_ok(n, n_regs, regs, 1u, 1u) || !kept_pictures_ok(n, pics)) return -1;
+    const uint32_t rw = h264k::FLOW_RECT_W >> shift, rh = h264k::FLOW_RECT_H >> shift;
+    const uint32_t rects_x = (sp.cols + rw - 1u) / rw, rects = rects_x * ((sp.rows + rh - 1u) / rh);
+    if ((uint64_t)rects * n_regs > h264k::FLOW_MAX_WORKGROUPS) return -1;
+    if (pull_begin_locked(e, n, pics, n_regs)) return -1;
+    h264k::FlowItem *items = e->titems.host<h264k::FlowItem>();
+    const size_t slice = (size_t)__builtin_popcount(sp.planes) * sp.rows * sp.cols;                   /* words */
+    for (uint32_t r = 0; r < n_regs; r++) {
+        const SinkRegion &g = regs[r];
+        const SinkTensorPic &p = pics[g.pic];
+        const StreamCtx *s = pic_stream(p);
+        const RegionClip c = region_clip(p, g);
+        items[r] = h264k::FlowItem{ s->d_frames + (size_t)p.slot * s->frame_bytes, s->d_kept.get(),
+                                    static_cast<uint32_t *>(sp.data) + (size_t)g.index * slice, s->wmb, (int32_t)p.x0 + g.x, (int32_t)p.y0 + g.y,
+                                    c.x0, c.y0, c.x1, c.y1, p.x0, p.y0, p.x0 + p.w, p.y0 + p.h };
+    }
+    /* three quads of displacements per thread from radius 4 on, one below: the sibling's measured choice */
+    const void *fn = sp.radius >= h264k::SHIFT_QUADS_FROM ? reinterpret_cast<const void *>(&h264k::k_cell_shift<h264k::SHIFT_QUADS>)
+                                                           : reinterpret_cast<const void *>(&h264k::k_cell_shift<1u>);
+    h264k::FlowArgs fargs{ e->titems.dev<h264k::FlowItem>(), sp.cols, sp.rows, shift, rects_x, sp.planes, sp.radius };
+    if (kept_order_begin(e, st)) return -1;
+    if (pull_launch_locked(e, n, pics, st, fn, dim3(rects, n_regs), &fargs, fence_ev)) return -1;
+    return kept_order_end(e, st);
+}
+
 /* h264bsdmiOutputTensorRemap: the current pictures of the n instances sampled through n_maps coordinate maps by one k_tensor_remap
  * launch, map r into slice maps[r].index.  The fence goes to each distinct instance, so that the next picture decoded into one of
  * these slots waits for this launch.  The maps are the caller's: read on st. */
@@ -1850,7 +1890,7 @@ static int remap_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, ui
     return pull_launch_locked(e, n, pics, st, fn, pull_grid(t.width, t.height, h264k::TRM_COLS, h264k::TRM_ROWS, n_maps), &rargs, fence_ev);
 }
 
-/* What JobSink.tensor_out, tensor_regions, motion_regions, tensor_remap, region_stats, keep_pictures, blend_pictures, kept_pictures_out, region_change, region_shift, corner_points, cell_maps and cell_boxes share: one engine (one device) per call, its mutex, the
+/* What JobSink.tensor_out, tensor_regions, motion_regions, tensor_remap, region_stats, keep_pictures, blend_pictures, kept_pictures_out, region_change, region_shift, corner_points, cell_maps and cell_boxes, and EngSinkEntries.cell_shift, share: one engine (one device) per call, its mutex, the
  * refusal of a capturing stream, and, when the caller gave no stream, the wait for the fence and the device's error words.
  * body(e, st, &fence_ev): the call's own *_out_locked. */
 template <typename Body> static int sink_tensor_call(uint32_t n, const SinkTensorPic *pics, void *stream, Body body)
@@ -1976,6 +2016,13 @@ int sink_cell_boxes(uint32_t n, const SinkTensorPic *pics, uint32_t n_regions, c
         return cell_boxes_out_locked(e, n, pics, n_regions, regions, *cells, *boxes, st, fence_ev);
     });
 }
+int sink_cell_shift(uint32_t n, const SinkTensorPic *pics, uint32_t n_regions, const SinkRegion *regions,
+                    const h264bsdmi_cell_shift_spec *spec, void *stream)
+{
+    return sink_list_call(n, pics, n_regions, regions && spec, stream, [&](Engine *e, hipStream_t st, hipEvent_t *fence_ev) {
+        return flow_out_locked(e, n, pics, n_regions, regions, *spec, st, fence_ev);
+    });
+}
 /* JobSink.set_motion (h264bsdmiSetMotionExport): before the instance's first sequence is configured */
 int sink_set_motion(void *user, int on)
 {
@@ -2026,6 +2073,13 @@ int eng_attach(JobSink *sink)
     sink->kept_pictures_out = sink_kept_pictures_out;
     sink->corner_points = sink_corner_points;
     return 0;
+}
+
+/* engine.h: the entries behind the last member of JobSink, for a sink eng_attach has bound */
+const EngSinkEntries *eng_sink_entries(const JobSink *sink)
+{
+    static const EngSinkEntries entries = { sink_cell_shift };
+    return sink && sink->configure == sink_configure ? &entries : nullptr;
 }
 
 void eng_convert_host(int fmt, uint32_t width, uint32_t height, const uint8_t *data, uint32_t *out)

@@ -548,6 +548,53 @@ int h264bsdmiOutputRegionShift(u32 n, storage_t *const *pStorage, u32 nRegions, 
                                const h264bsdmi_shift_spec *spec, void *stream,
                                u32 *got, u32 *current, u32 *kept, u32 *picId, u32 *keptPicId);
 
+/* Cell shift: WHERE did every cell go — the dense sibling of h264bsdmiOutputRegionShift, as h264bsdmiOutputCellMaps is the dense sibling
+ * of h264bsdmiOutputRegionChange: one block-matching search per cell of a grid, all in one launch, the answers as maps with one integer
+ * per cell: motion segmentation against the kept picture (a frame from a second ago, or the background model of
+ * h264bsdmiBlendCurrentPictures), a camera shift as the mode of the map, objects as the cells that leave it, and per cell the gain
+ * still - best that tells motion from noise.  Nothing is pulled.
+ * A sibling of h264bsdmiOutputCellMaps in CHANGE mode, and everything about regions, grids and instances is that call's, word for word:
+ * the region struct and its limits, negative origins, boxes that leave the window or miss it, regions == NULL with nRegions == n
+ * meaning whole windows, the source window (spec->crop), the grid of rows x cols cells of cell x cell luma samples laid over the box
+ * from its origin, the current-picture and the kept-picture rule (got[r] = 0 when either is missing: slice r is untouched), got,
+ * current, kept, picId, keptPicId (each may be NULL), the stream rule, the fence, the ordering of launches that touch kept pictures,
+ * keep_after, nRegions <= 65535.  A sibling of h264bsdmiOutputRegionShift for the arithmetic.
+ * THE DEFINITION: cell (i, j) of region (x, y, w, h) holds the fields count, dx, dy, best, still, ties of the record that
+ * h264bsdmiOutputRegionShift, at the same radius and crop, writes for the box
+ * (x + j cell, y + i cell, min(cell, w - j cell), min(cell, h - i cell)): the template is that box ∩ window in the KEPT picture; the
+ * CURRENT picture is clamped at the WINDOW, not at the cell or the box, so a cell searches into its neighbours' samples; the same tie
+ * rule (smallest SAD, then smallest dx^2 + dy^2, then smallest dy, then smallest dx).  Cells of the grid beyond the box or outside the
+ * window are the formula applied to nothing: count 0, dx = dy = best = still = 0, ties = D D, D = 2 radius + 1.  Cells of the box beyond
+ * the grid are not reported.
+ * Slice r is written at (u32 *)spec->data + r * P * rows * cols: P maps of rows x cols u32 each, row-major, one per set bit of
+ * spec->planes in ascending order (dx and dy are i32 in two's complement).  The call writes the WHOLE slice with plain stores: the
+ * caller does not clear it.  Everything is an integer and exact, and no result depends on scheduling.  A cell's SAD is at most
+ * 64 * 64 * 255 < 2^20, so u32 (int32 in torch) suffices, and regions need no H264BSDMI_SHIFT_MAX_SIDE cap: no sum spans more than a
+ * cell.  Cell 4 is left out on purpose: sixteen samples are no template, and D D displacements per 16 samples is the worst ratio of
+ * argmin to search.
+ * -1, before anything is enqueued, nothing written: everything h264bsdmiOutputCellMaps refuses in regions, instances and stream; spec
+ * or data NULL or data not 4-byte aligned; cols or rows 0 or above 4096; a cell not in {8, 16, 32, 64}; radius > 16; planes 0 or with
+ * bits outside the set; crop > 1; keep_after > 1.  -2: the engine failed (also: more than 2^23 workgroups — 64 x 64 luma samples of grid
+ * each, times the regions — in one call): nothing is written by the host and nothing is marked kept.  nRegions == 0 returns 0 and
+ * launches nothing. */
+#define H264BSDMI_FLOW_COUNT 1u
+#define H264BSDMI_FLOW_DX    2u    /* i32 */
+#define H264BSDMI_FLOW_DY    4u    /* i32 */
+#define H264BSDMI_FLOW_BEST  8u
+#define H264BSDMI_FLOW_STILL 16u
+#define H264BSDMI_FLOW_TIES  32u
+typedef struct h264bsdmi_cell_shift_spec {
+    void *data;        /* DEVICE, caller-owned, 4-byte aligned: slice r at (u32 *)data + r * P * rows * cols */
+    u32 cols, rows;    /* 1..4096 each */
+    u32 cell;          /* 8, 16, 32 or 64 */
+    u32 radius;        /* 0..16 */
+    u32 planes;        /* non-empty subset of the bits above; P = their number */
+    u32 crop, keep_after;
+} h264bsdmi_cell_shift_spec;
+int h264bsdmiOutputCellShift(u32 n, storage_t *const *pStorage, u32 nRegions, const h264bsdmi_region *regions,
+                             const h264bsdmi_cell_shift_spec *spec, void *stream,
+                             u32 *got, u32 *current, u32 *kept, u32 *picId, u32 *keptPicId);
+
 /* Corner points: WHICH boxes are worth following — Shi-Tomasi (minimum eigenvalue) or Harris corner points of boxes of the instances'
  * CURRENT pictures, luma only, computed where the pictures lie with one launch: gradients, the structure tensor, a corner score,
  * non-maximum suppression, the strongest K — the good-features-to-track step ahead of h264bsdmiOutputRegionShift, whose search means
