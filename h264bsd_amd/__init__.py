@@ -15,6 +15,7 @@ from .capi import (  # noqa: F401
     CellsSpec, CellMaps, pull_cells,
     BoxesSpec, CellBoxes, pull_boxes,
     CellShiftSpec, CellShift, pull_flow,
+    MatchesSpec, PointMatches, pull_matches, matches_record_bytes, descriptor_pattern,
     BlendSpec, BLEND_FROZEN, blend_pictures, pull_kept,
 )
 
@@ -23,4 +24,5 @@ from .capi import (  # noqa: F401
 # 0.6: pull_boxes (h264bsdmiOutputCellBoxes); 0.7: pull_shift (h264bsdmiOutputRegionShift)
 # 0.8: blend_pictures / pull_kept (h264bsdmiBlendCurrentPictures, h264bsdmiOutputKeptPictures)
 # 0.9: pull_corners (h264bsdmiOutputCornerPoints); 0.10: pull_flow (h264bsdmiOutputCellShift)
-__version__ = "0.10.0"
+# 0.11: pull_matches (h264bsdmiOutputPointMatches)
+__version__ = "0.11.0"

@@ -28,7 +28,7 @@ EXPORTED_SYMBOLS = [
     "h264bsdCroppingParams", "h264bsdSampleAspectRatio", "h264bsdCheckValidParamSets", "h264bsdFlushBuffer",
     "h264bsdProfile", "h264bsdAlloc", "h264bsdFree", "h264bsdConvertToRGBA", "h264bsdConvertToBGRA",
     "h264bsdConvertToYCbCrA",
-    "h264bsdmiInitCapture", "h264bsdmiNextOutputInfo", "h264bsdmiNextOutputPictureDevice", "h264bsdmiNextOutputTensorBatch", "h264bsdmiNextOutputTensorBatchColour", "h264bsdmiNextOutputTensorBatchResize", "h264bsdmiOutputTensorRegions", "h264bsdmiOutputTensorRemap", "h264bsdmiSetMotionExport", "h264bsdmiOutputMotionRegions", "h264bsdmiOutputRegionStats", "h264bsdmiKeepCurrentPictures", "h264bsdmiBlendCurrentPictures", "h264bsdmiOutputKeptPictures", "h264bsdmiOutputRegionChange", "h264bsdmiOutputRegionShift", "h264bsdmiOutputCornerPoints", "h264bsdmiOutputCellMaps", "h264bsdmiOutputCellBoxes", "h264bsdmiOutputCellShift", "h264bsdmiJobFinalize", "h264bsdmiDeviceCount", "h264bsdmiSetDevice", "h264bsdmiFlush", "h264bsdmiFlushAsync", "h264bsdmiDeviceErrors",
+    "h264bsdmiInitCapture", "h264bsdmiNextOutputInfo", "h264bsdmiNextOutputPictureDevice", "h264bsdmiNextOutputTensorBatch", "h264bsdmiNextOutputTensorBatchColour", "h264bsdmiNextOutputTensorBatchResize", "h264bsdmiOutputTensorRegions", "h264bsdmiOutputTensorRemap", "h264bsdmiSetMotionExport", "h264bsdmiOutputMotionRegions", "h264bsdmiOutputRegionStats", "h264bsdmiKeepCurrentPictures", "h264bsdmiBlendCurrentPictures", "h264bsdmiOutputKeptPictures", "h264bsdmiOutputRegionChange", "h264bsdmiOutputRegionShift", "h264bsdmiOutputCornerPoints", "h264bsdmiOutputCellMaps", "h264bsdmiOutputCellBoxes", "h264bsdmiOutputCellShift", "h264bsdmiOutputPointMatches", "h264bsdmiDescriptorPattern", "h264bsdmiJobFinalize", "h264bsdmiDeviceCount", "h264bsdmiSetDevice", "h264bsdmiFlush", "h264bsdmiFlushAsync", "h264bsdmiDeviceErrors",
     "h264bsdmiDecodePicture", "h264bsdmiDecodePictureBatch", "h264bsdmiNextOutputPictureBatch", "h264bsdmiPullAndDecodePictureBatch", "h264bsdmiSetParserThreads", "h264bsdmiSetInputReadOnly", "h264bsdmiSetCopyElision",
     "h264bsdmiReplayCreate", "h264bsdmiReplayCreateStaggered", "h264bsdmiReplayCreateDesync", "h264bsdmiReplayCreateSched", "h264bsdmiReplayReschedule", "h264bsdmiReplayDestroy", "h264bsdmiReplayRun", "h264bsdmiReplaySync",
     "h264bsdmiReplayFetch", "h264bsdmiReplayDbkRecords", "h264bsdmiReplayChecksums", "h264bsdmiReplayConvert", "h264bsdmiReplayFetchConverted",
@@ -128,6 +128,13 @@ class CellShiftSpec(ctypes.Structure):
                 ("radius", ctypes.c_uint32), ("planes", ctypes.c_uint32), ("crop", ctypes.c_uint32), ("keep_after", ctypes.c_uint32)]
 
 
+class MatchesSpec(ctypes.Structure):
+    """h264bsdmi_matches_spec (include/h264bsd_mi355x.h)"""
+    _fields_ = [("data", ctypes.c_void_p), ("kept_points", ctypes.c_void_p), ("current_points", ctypes.c_void_p),
+                ("max_points", ctypes.c_uint32), ("max_distance", ctypes.c_uint32), ("ratio", ctypes.c_uint32), ("max_move", ctypes.c_uint32),
+                ("mutual_only", ctypes.c_uint32), ("crop", ctypes.c_uint32), ("keep_after", ctypes.c_uint32), ("zero", ctypes.c_uint32)]
+
+
 class BoxesSpec(ctypes.Structure):
     """h264bsdmi_boxes_spec (include/h264bsd_mi355x.h)"""
     _fields_ = [("data", ctypes.c_void_p), ("max_boxes", ctypes.c_uint32), ("plane", ctypes.c_uint32), ("channel", ctypes.c_uint32),
@@ -144,6 +151,8 @@ CELL_PLANES = ({"count": 1, "sum": 2, "sumsq": 4, "min": 8, "max": 16}, {"count"
 CELL_SIZES = (4, 8, 16, 32, 64)
 FLOW_PLANES = {"count": 1, "dx": 2, "dy": 4, "best": 8, "still": 16, "ties": 32}    # name -> H264BSDMI_FLOW_*, in the order of the maps
 FLOW_CELL_SIZES = (8, 16, 32, 64)
+MATCH_FLAGS = {"valid": 1, "mutual": 2, "accepted": 4}                           # H264BSDMI_MATCH_*
+MATCHES_MAX_POINTS = 256
 STATS_SOURCES = {"y": (0, 1), "ycbcr": (1, 3), "rgb": (2, 3)}                    # name -> (H264BSDMI_STATS_*, channels)
 STATS_BINS = (0, 16, 32, 64, 128, 256)
 MOTION_PLANES = {"mv": (1, 2), "valid": (2, 1), "age": (4, 1), "qp": (8, 1)}     # name -> (H264BSDMI_MOTION_PLANE_*, channels), in channel order
@@ -300,6 +309,11 @@ def _declare(L, harness):
     L.h264bsdmiOutputCellShift.argtypes = [u32, ctypes.POINTER(vp), u32, ctypes.POINTER(Region), ctypes.POINTER(CellShiftSpec), vp,
                                            P32, P32, P32, P32, P32]
     L.h264bsdmiOutputCellShift.restype = ctypes.c_int
+    L.h264bsdmiOutputPointMatches.argtypes = [u32, ctypes.POINTER(vp), u32, ctypes.POINTER(Region), ctypes.POINTER(MatchesSpec), vp,
+                                              P32, P32, P32, P32, P32]
+    L.h264bsdmiOutputPointMatches.restype = ctypes.c_int
+    L.h264bsdmiDescriptorPattern.argtypes = []
+    L.h264bsdmiDescriptorPattern.restype = ctypes.POINTER(ctypes.c_int8)
     L.h264bsdmiDecodePicture.argtypes = [vp, u8p, u32, u32, P32, P32]
     L.h264bsdmiDecodePicture.restype = u32
     L.h264bsdmiDecodePictureBatch.argtypes = [u32, ctypes.POINTER(vp), ctypes.POINTER(vp), P32, P32, P32, P32, P32]
@@ -1330,6 +1344,128 @@ def pull_flow(decoders, regions=None, cell=16, grid=None, radius=4, planes=("dx"
     spec = CellShiftSpec(out.data_ptr(), grid[1], grid[0], cell, radius, bits, 1 if crop else 0, 1 if keep else 0)
     return CellShift(out, cell, radius, bits,
                      *_kept_pull("h264bsdmiOutputCellShift", decoders, K, regs, (ctypes.byref(spec),), stream, n > 0 and K > 0))
+
+
+def matches_record_bytes(max_points):
+    """the stride of one record of h264bsdmiOutputPointMatches: 32 + 80 K bytes, K = max_points"""
+    if not isinstance(max_points, int) or isinstance(max_points, bool) or not 1 <= max_points <= MATCHES_MAX_POINTS:
+        raise ValueError(f"matches_record_bytes: max_points is an int in 1..{MATCHES_MAX_POINTS}, not {max_points}")
+    return 32 + 80 * max_points
+
+
+def descriptor_pattern():
+    """h264bsdmiDescriptorPattern: the 256 tests (px, py, qx, qy) of the binary descriptor, [256, 4] int8 (numpy; needs no device)"""
+    p = api_lib().h264bsdmiDescriptorPattern()
+    return np.ctypeslib.as_array(p, (256, 4)).copy()
+
+
+class PointMatches:
+    """what pull_matches returns: kept_valid, current_valid, accepted, mutual, sum_dx, sum_dy [R] int32; j, best, second, flags [R, K]
+    int32 (j = -1 and best = second = 257 where a kept slot is invalid or has no candidate; flags: MATCH_FLAGS); kept_descriptors,
+    current_descriptors [R, K, 32] uint8 — views of `records` ([R, stride] uint8, one allocation, the C layout); got [R], and per decoder
+    current, kept, pic_id, kept_pic_id, lists of ints.  Slot indices are those of the point records"""
+
+    def __init__(self, records, max_points, got, current, kept, pic_id, kept_pic_id):
+        import torch
+        w32 = records.view(torch.int32)
+        K = max_points
+        self.records, self.max_points = records, K
+        self.kept_valid, self.current_valid, self.accepted, self.mutual, self.sum_dx, self.sum_dy = (w32[:, k] for k in range(6))
+        self.j, self.best, self.second, self.flags = (w32[:, 8 + k:8 + 4 * K:4] for k in range(4))
+        self.kept_descriptors = records[:, 32 + 16 * K:32 + 48 * K].unflatten(1, (K, 32))
+        self.current_descriptors = records[:, 32 + 48 * K:32 + 80 * K].unflatten(1, (K, 32))
+        self.got, self.current, self.kept, self.pic_id, self.kept_pic_id = got, current, kept, pic_id, kept_pic_id
+
+    @staticmethod
+    def _points(who, points, R, K):
+        """x, y [R, K] of point records (a CornerPoints or a tensor of records) as host lists"""
+        import torch
+        rec = points.records if isinstance(points, CornerPoints) else points
+        if tuple(rec.shape) != (R, 32 + 16 * K):
+            raise ValueError(f"{who}: the point records are not those of the call ({tuple(rec.shape)} for {(R, 32 + 16 * K)})")
+        w32 = rec.cpu().contiguous().view(torch.int32)
+        return w32[:, 8:8 + 4 * K:4].tolist(), w32[:, 9:9 + 4 * K:4].tolist()
+
+    def _accepted(self):
+        """(j, best, flags) [R, K] as host lists: one copy of the slots"""
+        import torch
+        K = self.max_points
+        w32 = self.records[:, :32 + 16 * K].cpu().contiguous().view(torch.int32)
+        return w32[:, 8:8 + 4 * K:4].tolist(), w32[:, 9:9 + 4 * K:4].tolist(), w32[:, 11:11 + 4 * K:4].tolist()
+
+    def pairs(self, r, kept_points, current_points):
+        """the accepted slots of record r as a host list of (xk, yk, xc, yc, distance), in slot order; the point records are those of
+        the call"""
+        R, K = len(self.got), self.max_points
+        xk, yk = self._points("PointMatches.pairs", kept_points, R, K)
+        xc, yc = self._points("PointMatches.pairs", current_points, R, K)
+        j, best, flags = self._accepted()
+        return [(xk[r][i], yk[r][i], xc[r][j[r][i]], yc[r][j[r][i]], best[r][i]) for i in range(K) if flags[r][i] & MATCH_FLAGS["accepted"]]
+
+    def moved(self, side, regions, current_points):
+        """a side x side box around the matched current point of every accepted slot of every record with got: (decoder_index,
+        x - side // 2, y - side // 2, side, side), ready for pull_shift / pull_regions / pull_stats; regions as for CornerPoints.regions"""
+        if regions is None:
+            raise ValueError("PointMatches.moved: pass the regions of the call; after regions=None, the windows as [(i, 0, 0, W, H), ...]")
+        if not isinstance(side, int) or isinstance(side, bool) or side < 1:
+            raise ValueError(f"PointMatches.moved: side is a positive int, not {side}")
+        regions = [tuple(r) for r in regions]
+        if len(regions) != len(self.got):
+            raise ValueError(f"PointMatches.moved: {len(regions)} regions for {len(self.got)} records")
+        K = self.max_points
+        xc, yc = self._points("PointMatches.moved", current_points, len(self.got), K)
+        j, _, flags = self._accepted()
+        return [(reg[0], xc[r][j[r][i]] - side // 2, yc[r][j[r][i]] - side // 2, side, side)
+                for r, reg in enumerate(regions) if self.got[r] for i in range(K) if flags[r][i] & MATCH_FLAGS["accepted"]]
+
+
+def _point_records(who, points, K_regions):
+    """the point records of pull_matches, checked: (the tensor [R, 32 + 16 K], K)"""
+    if isinstance(points, CornerPoints):
+        rec, K = points.records, points.max_points
+    else:
+        rec = points
+        import torch
+        if not isinstance(rec, torch.Tensor) or not rec.is_cuda or rec.dtype != torch.uint8 or rec.dim() != 2 or not rec.is_contiguous() or \
+                rec.data_ptr() % 8 or rec.shape[1] < 48 or (rec.shape[1] - 32) % 16:
+            raise ValueError(f"{who}: point records are a CornerPoints or a contiguous, 8-byte aligned CUDA uint8 tensor [R, 32 + 16 K]")
+        K = (rec.shape[1] - 32) // 16
+    if not 1 <= K <= MATCHES_MAX_POINTS or tuple(rec.shape) != (K_regions, 32 + 16 * K) or not rec.is_contiguous() or rec.data_ptr() % 8:
+        raise ValueError(f"{who}: point records of shape {tuple(rec.shape)} for {K_regions} regions (K in 1..{MATCHES_MAX_POINTS}, contiguous, 8-byte aligned)")
+    return rec, K
+
+
+def pull_matches(decoders, kept_points, current_points, regions=None, max_distance=64, ratio=205, max_move=0, mutual=True, crop=True,
+                 keep=False, out=None, stream=None):
+    """h264bsdmiOutputPointMatches: where the corner points of the decoders' KEPT pictures (keep_pictures) lie in their CURRENT pictures,
+    at any distance — a 256-bit binary descriptor per point (comparisons of 5 x 5 box sums around it, a fixed pattern:
+    descriptor_pattern()) on either picture and the Hamming matching of the two sets, by two kernel launches where the pictures lie;
+    nothing is popped and no pixel is pulled.  kept_points, current_points: the CornerPoints of two pull_corners calls over the same
+    regions (on the picture that was then kept, and on the current one) at the same max_points, or their records as CUDA uint8 tensors
+    [R, 32 + 16 K].  regions, crop, out and stream as for pull_shift (out: [R, matches_record_bytes(K)]).  A kept slot is matched to the
+    current slot of the smallest Hamming distance (then the smallest index) among those within max_move (Chebyshev; 0: anywhere), and
+    accepted when that distance is <= max_distance (0..256), below ratio / 256 of the second smallest (ratio 1..256; 256: no test) and,
+    with mutual=True, the best among the kept slots for that current slot as well.  got[r] = 1 only where the decoder has a current AND
+    a kept picture: other records are left untouched.  keep=True: behind the matching the current pictures become the kept ones.
+    Returns a PointMatches; the loop: c0 = pull_corners(decs); keep_pictures(decs); then per picture c1 = pull_corners(decs);
+    m = pull_matches(decs, c0, c1, keep=True); c0 = c1."""
+    import torch
+    n = len(decoders)
+    ints = lambda *vs: all(isinstance(v, int) and not isinstance(v, bool) for v in vs)
+    if not ints(max_distance, ratio, max_move) or not 0 <= max_distance <= 256 or not 1 <= ratio <= 256 or not 0 <= max_move <= 65535:
+        raise ValueError(f"pull_matches: max_distance is an int in 0..256, ratio in 1..256, max_move in 0..65535, not {max_distance} {ratio} {max_move}")
+    K, regs = _regions_arg("pull_matches", n, regions)
+    if regs is not None and any(r.w > SHIFT_MAX_SIDE or r.h > SHIFT_MAX_SIDE for r in regs[:K]):
+        raise ValueError(f"pull_matches: a region is at most {SHIFT_MAX_SIDE} x {SHIFT_MAX_SIDE}")
+    krec, P = _point_records("pull_matches", kept_points, K)
+    crec, Pc = _point_records("pull_matches", current_points, K)
+    if P != Pc:
+        raise ValueError(f"pull_matches: the two point records have max_points {P} and {Pc}")
+    shape = (K, matches_record_bytes(P))
+    out, stream = _out_and_stream("pull_matches", out, shape, torch.uint8, stream, aligned=True)
+    spec = MatchesSpec(out.data_ptr(), krec.data_ptr(), crec.data_ptr(), P, max_distance, ratio, max_move, 1 if mutual else 0,
+                       1 if crop else 0, 1 if keep else 0, 0)
+    return PointMatches(out, P, *_kept_pull("h264bsdmiOutputPointMatches", decoders, K, regs, (ctypes.byref(spec),), stream, n > 0 and K > 0))
 
 
 class CellBoxes:

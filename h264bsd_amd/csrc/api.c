@@ -19,6 +19,7 @@
 #include "../../include/h264bsd_mi355x_bench.h"
 #include "hostdec.h"
 #include "engine.h"
+#include "descriptor_pattern.h"
 #pragma weak eng_sink_entries     /* an engine without it (a device stand-in of the tests) gives NULL: the calls that need an entry of it refuse */
 static const EngSinkEntries *sink_entries(const JobSink *k) { return eng_sink_entries ? eng_sink_entries(k) : NULL; }
 
@@ -372,7 +373,7 @@ int h264bsdmiNextOutputTensorBatchResize(u32 n, storage_t *const *dec, const h26
  *   pull_regions      the regions (or one whole window per instance) of the pictures that exist, each with its rectangle
  *   pull_finish       after the sink: got, box, current and picId — unless the sink failed (-2 writes nothing) — and the lists freed
  * A refused call returns -1 and has called no sink, written nothing; no call pops anything. */
-enum { PULL_REGIONS, PULL_REMAP, PULL_MOTION, PULL_STATS, PULL_CHANGE, PULL_KEEP, PULL_CELLS, PULL_BOXES, PULL_SHIFT, PULL_CORNERS, PULL_FLOW };
+enum { PULL_REGIONS, PULL_REMAP, PULL_MOTION, PULL_STATS, PULL_CHANGE, PULL_KEEP, PULL_CELLS, PULL_BOXES, PULL_SHIFT, PULL_CORNERS, PULL_FLOW, PULL_MATCHES };
 #define NO_PIC 0xFFFFFFFFu
 typedef struct CurrentPull {
     u32 n, m, k;                /* instances; pictures and items gathered so far */
@@ -382,7 +383,7 @@ typedef struct CurrentPull {
     SinkRegion *regs;           /* the items for the sink: regions, or (PULL_REMAP) maps */
     SinkRemap *maps;
     int kind;                   /* PULL_* */
-    int vs_kept;                /* only instances that have a kept picture too: PULL_CHANGE, PULL_SHIFT, PULL_FLOW, and PULL_CELLS / PULL_BOXES in CHANGE mode */
+    int vs_kept;                /* only instances that have a kept picture too: PULL_CHANGE, PULL_SHIFT, PULL_FLOW, PULL_MATCHES, and PULL_CELLS / PULL_BOXES in CHANGE mode */
 } CurrentPull;
 
 /* regions == NULL: no regions at all, or (whole: one whole window per instance) exactly n */
@@ -414,6 +415,7 @@ static int sink_pulls(const ApiDec *a, int kind)
     case PULL_CELLS:  return k->tensor_regions != NULL && k->cell_maps != NULL;      /* CHANGE mode: keep_pictures too (the entry asks) */
     case PULL_BOXES:  return k->tensor_regions != NULL && k->cell_maps != NULL && k->cell_boxes != NULL;
     case PULL_FLOW:   return k->tensor_regions != NULL && k->keep_pictures != NULL && sink_entries(k) && sink_entries(k)->cell_shift != NULL;      /* (engine.h) */
+    case PULL_MATCHES: return k->tensor_regions != NULL && k->keep_pictures != NULL && sink_entries(k) && sink_entries(k)->point_matches != NULL;
     }
     return k->tensor_regions != NULL;
 }
@@ -688,7 +690,7 @@ int h264bsdmiOutputKeptPictures(u32 n, storage_t *const *dec, void *const *pictu
 
 /* The host path of the pulls that may compare against kept pictures and may keep afterwards, behind their own spec checks:
  * h264bsdmiOutputRegionChange (PULL_CHANGE), h264bsdmiOutputRegionShift (PULL_SHIFT), h264bsdmiOutputCellMaps (PULL_CELLS) and
- * h264bsdmiOutputCellBoxes (PULL_BOXES, spec2 its boxes spec), h264bsdmiOutputCellShift (PULL_FLOW).  vs_kept: only instances that have a kept picture too; max_side: the
+ * h264bsdmiOutputCellBoxes (PULL_BOXES, spec2 its boxes spec), h264bsdmiOutputCellShift (PULL_FLOW), h264bsdmiOutputPointMatches (PULL_MATCHES).  vs_kept: only instances that have a kept picture too; max_side: the
  * longest side a region may have (0: whatever regions_refused allows); keep_after: behind the sink's entry the keep call's launch for
  * every instance with a current picture.  kept / keptPicId are what the comparison saw; -2 writes nothing, marks nothing */
 static int kept_pull(int kind, int vs_kept, u32 n, storage_t *const *dec, u32 nRegions, const h264bsdmi_region *regions, u32 max_side,
@@ -714,6 +716,7 @@ static int kept_pull(int kind, int vs_kept, u32 n, storage_t *const *dec, u32 nR
         case PULL_SHIFT:  failed = sink->region_shift(c.m, c.pics, c.k, c.regs, (const h264bsdmi_shift_spec *)spec, stream); break;
         case PULL_CELLS:  failed = sink->cell_maps(c.m, c.pics, c.k, c.regs, (const h264bsdmi_cells_spec *)spec, stream); break;
         case PULL_FLOW:   failed = sink_entries(sink)->cell_shift(c.m, c.pics, c.k, c.regs, (const h264bsdmi_cell_shift_spec *)spec, stream); break;
+        case PULL_MATCHES: failed = sink_entries(sink)->point_matches(c.m, c.pics, c.k, c.regs, (const h264bsdmi_matches_spec *)spec, stream); break;
         default:          failed = sink->cell_boxes(c.m, c.pics, c.k, c.regs, (const h264bsdmi_cells_spec *)spec, (const h264bsdmi_boxes_spec *)spec2, stream);
         }
     }
@@ -818,6 +821,29 @@ int h264bsdmiOutputCellShift(u32 n, storage_t *const *dec, u32 nRegions, const h
 {
     if (cell_shift_spec_refused(spec)) return -1;
     return kept_pull(PULL_FLOW, 1, n, dec, nRegions, regions, 0, spec, NULL, spec->crop, spec->keep_after, stream, got, current, kept, picId, keptPicId);
+}
+
+/* Where the points of the kept pictures lie in the current ones, at any distance: binary descriptors and their Hamming matching over
+ * h264bsdmiOutputRegionShift's regions.  The pattern of the descriptor is descriptor_pattern.h's, the kernel's copy of the same numbers */
+const signed char *h264bsdmiDescriptorPattern(void)
+{
+    static const signed char pattern[4 * DESCRIPTOR_TESTS] = { DESCRIPTOR_PATTERN_VALUES };
+    return pattern;
+}
+static int matches_spec_refused(const h264bsdmi_matches_spec *s)
+{
+    if (!s || !s->data || ((uintptr_t)s->data & 7u) || !s->kept_points || ((uintptr_t)s->kept_points & 7u) ||
+        !s->current_points || ((uintptr_t)s->current_points & 7u)) return 1;
+    if (s->max_points < 1 || s->max_points > H264BSDMI_MATCHES_MAX_POINTS || s->max_distance > 256 || s->ratio < 1 || s->ratio > 256) return 1;
+    return s->max_move > 65535 || s->mutual_only > 1 || s->crop > 1 || s->keep_after > 1 || s->zero;
+}
+int h264bsdmiOutputPointMatches(u32 n, storage_t *const *dec, u32 nRegions, const h264bsdmi_region *regions,
+                                const h264bsdmi_matches_spec *spec, void *stream,
+                                u32 *got, u32 *current, u32 *kept, u32 *picId, u32 *keptPicId)
+{
+    if (matches_spec_refused(spec)) return -1;
+    return kept_pull(PULL_MATCHES, 1, n, dec, nRegions, regions, H264BSDMI_SHIFT_MAX_SIDE, spec, NULL, spec->crop, spec->keep_after, stream,
+                     got, current, kept, picId, keptPicId);
 }
 
 static u32 *next_converted(storage_t *s, u32 *picId, u32 *isIdrPic, u32 *numErrMbs, int fmt)

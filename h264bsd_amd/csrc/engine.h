@@ -28,10 +28,16 @@ int  eng_device_cpus(int device, int *cpus, int max);
  *               as for JobSink.region_shift) where it lies in the picture against its instance's kept picture — region_shift's search,
  *               one per cell — slice `index` of spec->data each, with one launch.  Every picture's instance has a kept picture of its
  *               coded size; spec->keep_after is not looked at (the caller follows up with keep_pictures).  Called through the table
- *               of any of the n sinks.  0 = ok; <0 = error, nothing enqueued */
+ *               of any of the n sinks.  0 = ok; <0 = error, nothing enqueued
+ *   point_matches  h264bsdmiOutputPointMatches: per region the binary descriptors of the points of spec->kept_points (on the kept
+ *               picture of the region's instance) and of spec->current_points (on its current picture), record `index` of each, and
+ *               their Hamming matching, into record `index` of spec->data, with two launches on one stream.  The pictures, the kept
+ *               pictures, keep_after and the return value as for cell_shift */
 typedef struct EngSinkEntries {
     int (*cell_shift)(uint32_t n, const SinkTensorPic *pics, uint32_t n_regions, const SinkRegion *regions,
                       const struct h264bsdmi_cell_shift_spec *spec, void *stream);
+    int (*point_matches)(uint32_t n, const SinkTensorPic *pics, uint32_t n_regions, const SinkRegion *regions,
+                         const struct h264bsdmi_matches_spec *spec, void *stream);
 } EngSinkEntries;
 const EngSinkEntries *eng_sink_entries(const JobSink *sink);
 

@@ -46,6 +46,7 @@
 #include "kernels/k_region_shift.hip.h"
 #include "kernels/k_cell_shift.hip.h"
 #include "kernels/k_corner_points.hip.h"
+#include "kernels/k_point_matches.hip.h"
 #include "kernels/k_cell_maps.hip.h"
 #include "kernels/k_cell_boxes.hip.h"
 #include "engine.h"
@@ -169,11 +170,12 @@ constexpr uint32_t LANE_DBK_WAVES = LANE_DBK_WAVES_N;
 
 /* the item stride of the tensor pulls' staging ring: k_tensor_out / k_tensor_resize read TensorItems, k_tensor_aa AaItems, k_tensor_roi
  * RoiItems, k_motion_roi MotionItems, k_tensor_remap RemapItems, k_region_stats StatsItems, k_keep KeepItems, k_blend BlendItems, k_kept_out KeptOutItems, k_region_change ChangeItems, k_region_shift ShiftItems, k_corner_points CornerItems,
- * k_cell_maps CellItems (k_cell_boxes: the same, and its BoxItems in slots of their own behind them), k_cell_shift FlowItems */
+ * k_cell_maps CellItems (k_cell_boxes: the same, and its BoxItems in slots of their own behind them), k_cell_shift FlowItems,
+ * k_point_describe / k_point_match MatchItems */
 constexpr size_t TITEM_BYTES = std::max({ sizeof(h264k::TensorItem), sizeof(h264k::AaItem), sizeof(h264k::RoiItem), sizeof(h264k::MotionItem),
                                           sizeof(h264k::RemapItem), sizeof(h264k::StatsItem), sizeof(h264k::KeepItem), sizeof(h264k::ChangeItem),
                                           sizeof(h264k::CellItem), sizeof(h264k::BoxItem), sizeof(h264k::ShiftItem), sizeof(h264k::BlendItem),
-                                          sizeof(h264k::KeptOutItem), sizeof(h264k::CornerItem), sizeof(h264k::FlowItem) });
+                                          sizeof(h264k::KeptOutItem), sizeof(h264k::CornerItem), sizeof(h264k::FlowItem), sizeof(h264k::MatchItem) });
 struct TItemSlot { uint8_t bytes[TITEM_BYTES]; };
 struct Engine {
     std::mutex mu;
@@ -1861,6 +1863,45 @@ static int flow_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, uin
     return kept_order_end(e, st);
 }
 
+/* h264bsdmiOutputPointMatches: one MatchItem per region — the current picture and the kept picture of its instance, the record, the two
+ * point records (the caller's, read on st), box ∩ window and the window itself (the luma is replicated there) in luma samples of the coded
+ * frame — and TWO launches inside the kept pictures' ordering, the fence and the error words behind both: k_point_describe of (groups of
+ * slots, regions) workgroups writes the descriptors into the record, k_point_match of one workgroup per region reads them there and
+ * writes the rest.  No scratch of the engine.  The kept pictures as in shift_out_locked; keep_after is not looked at. */
+static int matches_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, uint32_t n_regs, const SinkRegion *regs,
+                              const h264bsdmi_matches_spec &sp, hipStream_t st, hipEvent_t *fence_ev)
+{
+    const auto misaligned = [](const void *p) { return !p || (reinterpret_cast<uintptr_t>(p) & 7u); };
+    if (misaligned(sp.data) || misaligned(sp.kept_points) || misaligned(sp.current_points)) return -1;
+    if (sp.max_points < 1u || sp.max_points > h264k::MATCH_MAX_K || sp.max_distance > 256u || sp.ratio < 1u || sp.ratio > 256u ||
+        sp.max_move > 65535u || sp.mutual_only > 1u || sp.crop > 1u || sp.keep_after > 1u || sp.zero) return -1;
+    if (n_regs > 65535u) return -1;                                     /* grid.y */
+    if (!pull_pictures_ok(n, pics, true, false) || !pull_regions_ok(n, n_regs, regs, 1u, 1u) || !kept_pictures_ok(n, pics)) return -1;
+    if (pull_begin_locked(e, n, pics, n_regs)) return -1;
+    h264k::MatchItem *items = e->titems.host<h264k::MatchItem>();
+    const size_t stride = h264k::matches_record_bytes(sp.max_points), pstride = h264k::corner_record_bytes(sp.max_points);
+    for (uint32_t r = 0; r < n_regs; r++) {
+        const SinkRegion &g = regs[r];
+        const SinkTensorPic &p = pics[g.pic];
+        const StreamCtx *s = pic_stream(p);
+        const RegionClip c = region_clip(p, g);
+        items[r] = h264k::MatchItem{ s->d_frames + (size_t)p.slot * s->frame_bytes, s->d_kept.get(),
+                                     static_cast<uint8_t *>(sp.data) + (size_t)g.index * stride,
+                                     static_cast<const uint8_t *>(sp.kept_points) + (size_t)g.index * pstride,
+                                     static_cast<const uint8_t *>(sp.current_points) + (size_t)g.index * pstride,
+                                     s->wmb, c.x0, c.y0, c.x1, c.y1, p.x0, p.y0, p.x0 + p.w, p.y0 + p.h };
+    }
+    h264k::MatchArgs margs{ e->titems.dev<h264k::MatchItem>(), sp.max_points, sp.max_distance, sp.ratio, sp.max_move, sp.mutual_only };
+    if (kept_order_begin(e, st)) return -1;
+    if (pull_wait_pictures(e, n, pics, st)) return -1;
+    void *args[] = { &margs };
+    const uint32_t groups = (2u * sp.max_points + h264k::MATCH_GROUP - 1u) / h264k::MATCH_GROUP;
+    HIP_TRY(hipLaunchKernel(reinterpret_cast<const void *>(&h264k::k_point_describe), dim3(groups, n_regs), dim3(256), args, 0, st));
+    HIP_TRY(hipLaunchKernel(reinterpret_cast<const void *>(&h264k::k_point_match), dim3(n_regs), dim3(256), args, 0, st));
+    if (pull_end_locked(e, n, pics, st, fence_ev)) return -1;
+    return kept_order_end(e, st);
+}
+
 /* h264bsdmiOutputTensorRemap: the current pictures of the n instances sampled through n_maps coordinate maps by one k_tensor_remap
  * launch, map r into slice maps[r].index.  The fence goes to each distinct instance, so that the next picture decoded into one of
  * these slots waits for this launch.  The maps are the caller's: read on st. */
@@ -1890,7 +1931,7 @@ static int remap_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, ui
     return pull_launch_locked(e, n, pics, st, fn, pull_grid(t.width, t.height, h264k::TRM_COLS, h264k::TRM_ROWS, n_maps), &rargs, fence_ev);
 }
 
-/* What JobSink.tensor_out, tensor_regions, motion_regions, tensor_remap, region_stats, keep_pictures, blend_pictures, kept_pictures_out, region_change, region_shift, corner_points, cell_maps and cell_boxes, and EngSinkEntries.cell_shift, share: one engine (one device) per call, its mutex, the
+/* What JobSink.tensor_out, tensor_regions, motion_regions, tensor_remap, region_stats, keep_pictures, blend_pictures, kept_pictures_out, region_change, region_shift, corner_points, cell_maps and cell_boxes, and EngSinkEntries.cell_shift and point_matches, share: one engine (one device) per call, its mutex, the
  * refusal of a capturing stream, and, when the caller gave no stream, the wait for the fence and the device's error words.
  * body(e, st, &fence_ev): the call's own *_out_locked. */
 template <typename Body> static int sink_tensor_call(uint32_t n, const SinkTensorPic *pics, void *stream, Body body)
@@ -2023,6 +2064,13 @@ int sink_cell_shift(uint32_t n, const SinkTensorPic *pics, uint32_t n_regions, c
         return flow_out_locked(e, n, pics, n_regions, regions, *spec, st, fence_ev);
     });
 }
+int sink_point_matches(uint32_t n, const SinkTensorPic *pics, uint32_t n_regions, const SinkRegion *regions,
+                       const h264bsdmi_matches_spec *spec, void *stream)
+{
+    return sink_list_call(n, pics, n_regions, regions && spec, stream, [&](Engine *e, hipStream_t st, hipEvent_t *fence_ev) {
+        return matches_out_locked(e, n, pics, n_regions, regions, *spec, st, fence_ev);
+    });
+}
 /* JobSink.set_motion (h264bsdmiSetMotionExport): before the instance's first sequence is configured */
 int sink_set_motion(void *user, int on)
 {
@@ -2078,7 +2126,7 @@ int eng_attach(JobSink *sink)
 /* engine.h: the entries behind the last member of JobSink, for a sink eng_attach has bound */
 const EngSinkEntries *eng_sink_entries(const JobSink *sink)
 {
-    static const EngSinkEntries entries = { sink_cell_shift };
+    static const EngSinkEntries entries = { sink_cell_shift, sink_point_matches };
     return sink && sink->configure == sink_configure ? &entries : nullptr;
 }
 

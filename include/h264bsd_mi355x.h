@@ -647,6 +647,74 @@ int h264bsdmiOutputCornerPoints(u32 n, storage_t *const *pStorage, u32 nRegions,
                                 const h264bsdmi_corners_spec *spec, void *stream,
                                 u32 *got, u32 *current, u32 *picId);
 
+/* Point matches: WHERE did the points go, at any distance — a 256-bit binary descriptor of every corner point of the KEPT and of the
+ * CURRENT picture and the Hamming matching of the two sets, computed where the pictures lie: what h264bsdmiOutputRegionShift cannot
+ * answer beyond its radius of 16 (a camera that pans or was knocked, an object that crosses the picture between two detector runs, a
+ * point that reappears, a scene reference from a minute ago), because distance in the picture does not enter.  The inputs are the records
+ * of two h264bsdmiOutputCornerPoints calls at the same max_points and the two pictures.  Nothing is pulled.
+ * A sibling of h264bsdmiOutputRegionShift, and everything about the following is that call's, word for word: the region struct and its
+ * limits, regions == NULL with nRegions == n meaning whole windows, the source window (spec->crop), the current-and-kept-picture rule
+ * (got[r] = 0 when either is missing: record r is untouched), got, current, kept, picId, keptPicId (each may be NULL), the stream rule,
+ * the fence, the ordering of launches that touch kept pictures, keep_after, nRegions <= 65535.
+ * THE DEFINITION, all integers, T = box ∩ window, L~ the luma replicated at the WINDOW (h264bsdmiOutputCornerPoints' clamp, the only
+ * border rule):
+ *     pattern           256 tests (px, py, qx, qy), every coordinate in -12 .. 12, from this generator, fixed forever: xorshift32 with
+ *                       state s = 0x9E3779B9; one draw is s ^= s << 13; s ^= s >> 17; s ^= s << 5 (mod 2^32) and gives s; one
+ *                       coordinate is ((draw >> 8) % 13 - 6) + ((draw >> 8) % 13 - 6), from two draws; one test is four coordinates in
+ *                       the order px, py, qx, qy; a test with p == q, or one equal to an earlier test or its swap, is dropped and drawn
+ *                       again (none occurs in the first 256).  The first three tests are (-6, 5, 4, -1), (0, -10, -10, -4) and
+ *                       (-7, -10, -6, 1), the last is (-2, -2, -4, -11), the sum of all 1024 numbers is 86 and of their absolute values
+ *                       4464.  h264bsdmiDescriptorPattern() gives the 1024 numbers, test after test; it is host-only, needs no device.
+ *     smoothed sample   B(u, v) = the sum of L~ over the 5 x 5 samples centred on (u, v), 0 .. 6375: a descriptor reads L~ within 14
+ *                       samples of its point, a 29 x 29 patch
+ *     descriptor        of a point (x, y): bit t is 1 iff B(x + px_t, y + py_t) < B(x + qx_t, y + qy_t); bit t is bit t % 32 of
+ *                       little-endian dword t / 32: 32 bytes.  Upright, no orientation: fixed cameras are the use
+ *     valid slots       slot i of a point record is valid iff i < min(written, K) and (x, y) in T, `written` the u32 at byte 8 of the
+ *                       record, read as it is and clamped.  The records are caller memory: garbage in them leads to no access outside
+ *                       the picture or the record.  Kept slots are described on the KEPT picture, current slots on the CURRENT one;
+ *                       the descriptor of an invalid slot is 32 zero bytes
+ *     candidates        of kept slot i: the valid current slots j, with max_move > 0 those with max(|xk - xc|, |yk - yc|) <= max_move;
+ *                       d(i, j) = popcount(Dk[i] xor Dc[j]), 0 .. 256
+ *     best match        of i: the candidate j of smallest d, then smallest j; best = that d; second = the smallest d among the OTHER
+ *                       candidates, 257 if there is none; with no candidates j = -1 and best = second = 257
+ *     mutual            i is mutual iff, among the valid kept slots that have best(i) as a candidate, i has the smallest d to it,
+ *                       then the smallest i
+ *     accepted          i is valid and has a candidate, best <= max_distance, ratio == 256 or best * 256 < ratio * second, and
+ *                       !mutual_only or i is mutual
+ * Record r is written at spec->data + r * stride, little endian, stride = 32 + 80 K:
+ *     u32 kept_valid; u32 current_valid; u32 accepted; u32 mutual; i32 sum_dx; i32 sum_dy; u32 zero[2];
+ *     K x { i32 j; u32 best; u32 second; u32 flags; }      flags: H264BSDMI_MATCH_*; an invalid kept slot holds -1, 257, 257, 0
+ *     K x 32 bytes of kept descriptors; K x 32 bytes of current descriptors
+ * Slot indices are those of the point records, not compacted.  kept_valid, current_valid, accepted and mutual count the slots of each
+ * kind; sum_dx, sum_dy are the sums of xc - xk, yc - yk over the accepted slots: the mean displacement, a camera shift, without a host
+ * loop.  Everything is an integer and exact, and no result depends on scheduling.  The call writes the WHOLE record with plain stores:
+ * the caller does not clear it.  data must not overlap the point records (undefined, not checked); kept_points == current_points is
+ * allowed.
+ * -1, before anything is enqueued, nothing written: everything h264bsdmiOutputRegionShift refuses in regions, instances and stream;
+ * spec NULL; data, kept_points or current_points NULL or not 8-byte aligned; max_points outside 1 .. 256; max_distance > 256; ratio
+ * outside 1 .. 256; max_move > 65535; mutual_only, crop or keep_after > 1; zero != 0; a sink without the entry or one that cannot keep
+ * pictures.  -2: the engine failed: nothing is written by the host and nothing is marked kept.  nRegions == 0 returns 0 and launches
+ * nothing. */
+#define H264BSDMI_MATCH_VALID    1u
+#define H264BSDMI_MATCH_MUTUAL   2u
+#define H264BSDMI_MATCH_ACCEPTED 4u
+#define H264BSDMI_MATCHES_MAX_POINTS 256u
+typedef struct h264bsdmi_matches_spec {
+    void       *data;            /* DEVICE, caller-owned, 8-byte aligned: record r at data + r * (32 + 80 K) */
+    const void *kept_points;     /* DEVICE, 8-byte aligned: records of h264bsdmiOutputCornerPoints at max_points == K, */
+    const void *current_points;  /*   record r at + r * (32 + 16 K); r's points belong to region r's picture (kept / current) */
+    u32 max_points;              /* K, 1 .. 256 */
+    u32 max_distance;            /* 0 .. 256 */
+    u32 ratio;                   /* 1 .. 256, in 256ths; 256: no ratio test */
+    u32 max_move;                /* 0: no gate; else 1 .. 65535, Chebyshev */
+    u32 mutual_only;             /* 0 / 1 */
+    u32 crop, keep_after, zero;  /* zero must be 0 */
+} h264bsdmi_matches_spec;
+int h264bsdmiOutputPointMatches(u32 n, storage_t *const *pStorage, u32 nRegions, const h264bsdmi_region *regions,
+                                const h264bsdmi_matches_spec *spec, void *stream,
+                                u32 *got, u32 *current, u32 *kept, u32 *picId, u32 *keptPicId);
+const signed char *h264bsdmiDescriptorPattern(void);
+
 /* ---- host parse pipeline at scale ----
  * h264bsdDecode() consumes one NAL unit of one stream per call; a caller that feeds hundreds of streams needs the
  * loop of posix/test_h264bsd.c:146-177 for each of them and its own threading.  These entry points move both into
