@@ -20,8 +20,10 @@
  * many cells as FLOW_SURF_WORDS hold.  An ITEM is (cell, share g of G, row dy of the surface, QUADS adjacent quads of displacements):
  * the thread walks the rows va + g, va + g + G, .. of the cell's template, per template dword one new dword of the current picture and
  * QUADS v_qsad_pk_u16_u8, exactly the sibling's loop; the packed 16-bit sums are unpacked before they could have taken more than
- * SHIFT_FOLD instructions (a cell's row is at most 16 dwords, so every fourth row at the worst).  A dword of which only some bytes
- * belong to the cell (its first or last, where box or window cut it) goes through v_sad_u8 with a byte mask instead.  G is 1 where the
+ * SHIFT_FOLD instructions (a cell's row is at most 16 dwords, so every fourth row at the worst; a sum takes exactly SHIFT_FOLD for cells
+ * of 32 from radius 8 and of 64 from radius 6 on, and no unpacking happens on the way below that: tests/test_saturated_motion_reach.py).
+ * A dword of which only some bytes belong to the cell (its first or last, where box or window cut it) goes through v_sad_u8 with a
+ * byte mask instead.  G is 1 where the
  * group has FLOW_SPLIT items without it and grows where cells are large and the radius small (radius 0 has one item per cell), up to one
  * row per share.  The final sums are added to the cell's surface with ds_add_u32: integers, no order shows.
  * ARGMIN: after the barrier LPC lanes (a power of two, 64 where the group has four cells or fewer, 256 / cells otherwise) take a cell:

@@ -22,7 +22,8 @@
  * the step before's), so with QUADS = 3 two LDS reads feed three instructions.  QUADS is 3 from radius SHIFT_QUADS_FROM on and 1 below
  * it, where whole threads of three quads would mostly compute displacements beyond 2 R: each measured faster on its side.  The pairs
  * are dealt to the threads SHIFT_SPLIT / P ways (P pairs), each share a set of row segments of the tile, so that 256 threads are busy
- * at every radius; a thread unpacks its packed sums after every segment (at most SHIFT_FOLD instructions), keeps 32-bit sums per tile
+ * at every radius; a thread unpacks its packed sums after every segment (SHIFT_FOLD instructions would fit; as the tile and SHIFT_SPLIT
+ * stand a segment has 32 dwords at the most, from radius 12 on: tests/test_saturated_motion_reach.py), keeps 32-bit sums per tile
  * and adds them to the workgroup's surface in LDS (ds_add_u32, integers: no order shows).  The last template dword of a row, when the
  * width is no multiple of 4, goes through v_sad_u8 with a byte mask on both operands instead.  Displacements beyond 2 R in the last
  * pair of a row are computed and dropped.
@@ -42,7 +43,8 @@ constexpr uint32_t SHIFT_MAX_Q = ((SHIFT_MAX_D + 3) / 4 + SHIFT_QUADS - 1) / SHI
 constexpr uint32_t SHIFT_ROWS = 32, SHIFT_COLS4 = 64;                               /* a tile of template: rows, dwords per row */
 constexpr uint32_t SHIFT_CUR_ROWS = SHIFT_ROWS + 2 * SHIFT_MAX_RADIUS, SHIFT_PITCH = SHIFT_COLS4 + SHIFT_MAX_Q + 2;     /* 64, 75 */
 /* v_qsad_pk_u16_u8 instructions a packed 16-bit sum takes before it is unpacked: each adds at most 4 x 255 = 1020, and
- * 64 x 1020 = 65280 <= 65535.  A segment is at most SHIFT_COLS4 = 64 dwords of one row.  The 32-bit sums behind it: a region has at most
+ * 64 x 1020 = 65280 <= 65535.  A segment can never exceed SHIFT_COLS4 = 64 dwords of one row (the rule for L in the kernel keeps it at 32);
+ * k_cell_shift's items do reach 64.  The 32-bit sums behind it: a region has at most
  * 4096 x 4096 samples (H264BSDMI_SHIFT_MAX_SIDE), 2^24 x 255 < 2^32 */
 constexpr uint32_t SHIFT_FOLD = 64;
 static_assert(SHIFT_COLS4 <= SHIFT_FOLD && SHIFT_FOLD * 4 * 255 <= 65535, "a segment's packed sums must fit 16 bits");
