@@ -16,6 +16,7 @@ from .capi import (  # noqa: F401
     BoxesSpec, CellBoxes, pull_boxes,
     CellShiftSpec, CellShift, pull_flow,
     MatchesSpec, PointMatches, pull_matches, matches_record_bytes, descriptor_pattern,
+    ModelSpec, PointModel, pull_model, model_record_bytes,
     BlendSpec, BLEND_FROZEN, blend_pictures, pull_kept,
 )
 
@@ -24,5 +25,5 @@ from .capi import (  # noqa: F401
 # 0.6: pull_boxes (h264bsdmiOutputCellBoxes); 0.7: pull_shift (h264bsdmiOutputRegionShift)
 # 0.8: blend_pictures / pull_kept (h264bsdmiBlendCurrentPictures, h264bsdmiOutputKeptPictures)
 # 0.9: pull_corners (h264bsdmiOutputCornerPoints); 0.10: pull_flow (h264bsdmiOutputCellShift)
-# 0.11: pull_matches (h264bsdmiOutputPointMatches)
-__version__ = "0.11.0"
+# 0.11: pull_matches (h264bsdmiOutputPointMatches); 0.12: pull_model (h264bsdmiOutputPointModel)
+__version__ = "0.12.0"

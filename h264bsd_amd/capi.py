@@ -28,7 +28,7 @@ EXPORTED_SYMBOLS = [
     "h264bsdCroppingParams", "h264bsdSampleAspectRatio", "h264bsdCheckValidParamSets", "h264bsdFlushBuffer",
     "h264bsdProfile", "h264bsdAlloc", "h264bsdFree", "h264bsdConvertToRGBA", "h264bsdConvertToBGRA",
     "h264bsdConvertToYCbCrA",
-    "h264bsdmiInitCapture", "h264bsdmiNextOutputInfo", "h264bsdmiNextOutputPictureDevice", "h264bsdmiNextOutputTensorBatch", "h264bsdmiNextOutputTensorBatchColour", "h264bsdmiNextOutputTensorBatchResize", "h264bsdmiOutputTensorRegions", "h264bsdmiOutputTensorRemap", "h264bsdmiSetMotionExport", "h264bsdmiOutputMotionRegions", "h264bsdmiOutputRegionStats", "h264bsdmiKeepCurrentPictures", "h264bsdmiBlendCurrentPictures", "h264bsdmiOutputKeptPictures", "h264bsdmiOutputRegionChange", "h264bsdmiOutputRegionShift", "h264bsdmiOutputCornerPoints", "h264bsdmiOutputCellMaps", "h264bsdmiOutputCellBoxes", "h264bsdmiOutputCellShift", "h264bsdmiOutputPointMatches", "h264bsdmiDescriptorPattern", "h264bsdmiJobFinalize", "h264bsdmiDeviceCount", "h264bsdmiSetDevice", "h264bsdmiFlush", "h264bsdmiFlushAsync", "h264bsdmiDeviceErrors",
+    "h264bsdmiInitCapture", "h264bsdmiNextOutputInfo", "h264bsdmiNextOutputPictureDevice", "h264bsdmiNextOutputTensorBatch", "h264bsdmiNextOutputTensorBatchColour", "h264bsdmiNextOutputTensorBatchResize", "h264bsdmiOutputTensorRegions", "h264bsdmiOutputTensorRemap", "h264bsdmiSetMotionExport", "h264bsdmiOutputMotionRegions", "h264bsdmiOutputRegionStats", "h264bsdmiKeepCurrentPictures", "h264bsdmiBlendCurrentPictures", "h264bsdmiOutputKeptPictures", "h264bsdmiOutputRegionChange", "h264bsdmiOutputRegionShift", "h264bsdmiOutputCornerPoints", "h264bsdmiOutputCellMaps", "h264bsdmiOutputCellBoxes", "h264bsdmiOutputCellShift", "h264bsdmiOutputPointMatches", "h264bsdmiDescriptorPattern", "h264bsdmiOutputPointModel", "h264bsdmiJobFinalize", "h264bsdmiDeviceCount", "h264bsdmiSetDevice", "h264bsdmiFlush", "h264bsdmiFlushAsync", "h264bsdmiDeviceErrors",
     "h264bsdmiDecodePicture", "h264bsdmiDecodePictureBatch", "h264bsdmiNextOutputPictureBatch", "h264bsdmiPullAndDecodePictureBatch", "h264bsdmiSetParserThreads", "h264bsdmiSetInputReadOnly", "h264bsdmiSetCopyElision",
     "h264bsdmiReplayCreate", "h264bsdmiReplayCreateStaggered", "h264bsdmiReplayCreateDesync", "h264bsdmiReplayCreateSched", "h264bsdmiReplayReschedule", "h264bsdmiReplayDestroy", "h264bsdmiReplayRun", "h264bsdmiReplaySync",
     "h264bsdmiReplayFetch", "h264bsdmiReplayDbkRecords", "h264bsdmiReplayChecksums", "h264bsdmiReplayConvert", "h264bsdmiReplayFetchConverted",
@@ -135,6 +135,13 @@ class MatchesSpec(ctypes.Structure):
                 ("mutual_only", ctypes.c_uint32), ("crop", ctypes.c_uint32), ("keep_after", ctypes.c_uint32), ("zero", ctypes.c_uint32)]
 
 
+class ModelSpec(ctypes.Structure):
+    """h264bsdmi_model_spec (include/h264bsd_mi355x.h)"""
+    _fields_ = [("data", ctypes.c_void_p), ("matches", ctypes.c_void_p), ("kept_points", ctypes.c_void_p), ("current_points", ctypes.c_void_p),
+                ("max_points", ctypes.c_uint32), ("model", ctypes.c_uint32), ("tolerance", ctypes.c_uint32), ("max_scale", ctypes.c_uint32),
+                ("min_inliers", ctypes.c_uint32), ("zero", ctypes.c_uint32 * 3)]
+
+
 class BoxesSpec(ctypes.Structure):
     """h264bsdmi_boxes_spec (include/h264bsd_mi355x.h)"""
     _fields_ = [("data", ctypes.c_void_p), ("max_boxes", ctypes.c_uint32), ("plane", ctypes.c_uint32), ("channel", ctypes.c_uint32),
@@ -153,6 +160,8 @@ FLOW_PLANES = {"count": 1, "dx": 2, "dy": 4, "best": 8, "still": 16, "ties": 32}
 FLOW_CELL_SIZES = (8, 16, 32, 64)
 MATCH_FLAGS = {"valid": 1, "mutual": 2, "accepted": 4}                           # H264BSDMI_MATCH_*
 MATCHES_MAX_POINTS = 256
+MODEL_KINDS = {"translation": 0, "similarity": 1}                                 # name -> H264BSDMI_MODEL_*
+MODEL_FLAGS = {"usable": 1, "inlier": 2}                                         # H264BSDMI_MODEL_USABLE / _INLIER
 STATS_SOURCES = {"y": (0, 1), "ycbcr": (1, 3), "rgb": (2, 3)}                    # name -> (H264BSDMI_STATS_*, channels)
 STATS_BINS = (0, 16, 32, 64, 128, 256)
 MOTION_PLANES = {"mv": (1, 2), "valid": (2, 1), "age": (4, 1), "qp": (8, 1)}     # name -> (H264BSDMI_MOTION_PLANE_*, channels), in channel order
@@ -312,6 +321,8 @@ def _declare(L, harness):
     L.h264bsdmiOutputPointMatches.argtypes = [u32, ctypes.POINTER(vp), u32, ctypes.POINTER(Region), ctypes.POINTER(MatchesSpec), vp,
                                               P32, P32, P32, P32, P32]
     L.h264bsdmiOutputPointMatches.restype = ctypes.c_int
+    L.h264bsdmiOutputPointModel.argtypes = [u32, ctypes.POINTER(vp), u32, ctypes.POINTER(ModelSpec), vp]
+    L.h264bsdmiOutputPointModel.restype = ctypes.c_int
     L.h264bsdmiDescriptorPattern.argtypes = []
     L.h264bsdmiDescriptorPattern.restype = ctypes.POINTER(ctypes.c_int8)
     L.h264bsdmiDecodePicture.argtypes = [vp, u8p, u32, u32, P32, P32]
@@ -1466,6 +1477,144 @@ def pull_matches(decoders, kept_points, current_points, regions=None, max_distan
     spec = MatchesSpec(out.data_ptr(), krec.data_ptr(), crec.data_ptr(), P, max_distance, ratio, max_move, 1 if mutual else 0,
                        1 if crop else 0, 1 if keep else 0, 0)
     return PointMatches(out, P, *_kept_pull("h264bsdmiOutputPointMatches", decoders, K, regs, (ctypes.byref(spec),), stream, n > 0 and K > 0))
+
+
+def model_record_bytes(max_points):
+    """the stride of one record of h264bsdmiOutputPointModel: 128 + 4 K bytes, K = max_points"""
+    if not isinstance(max_points, int) or isinstance(max_points, bool) or not 1 <= max_points <= MATCHES_MAX_POINTS:
+        raise ValueError(f"model_record_bytes: max_points is an int in 1..{MATCHES_MAX_POINTS}, not {max_points}")
+    return 128 + 4 * max_points
+
+
+class PointModel:
+    """what pull_model returns: usable, hypotheses, inliers, found, a, b [R] int32 (a, b: the slots that span the best hypothesis, -1
+    where not found, b = -1 for a translation); sums [R, 12] int64 over the inliers, (x, y) the kept and (u, v) the current point:
+    Σx, Σy, Σu, Σv, Σxx, Σxy, Σyy, Σxu, Σyu, Σxv, Σyv, Σ(uu + vv); flags [R, K] int32 (MODEL_FLAGS) — usable .. flags are views of
+    `records` ([R, 128 + 4 K] uint8, one allocation, the C layout), sums a copy made when it is read (a record is 4-byte aligned only).
+    Slot indices are those of the point records; `matches` is the records tensor of the matches the call was given"""
+
+    def __init__(self, records, max_points, model, matches=None):
+        import torch
+        w32 = records.view(torch.int32)
+        self.records, self.max_points, self.model, self.matches = records, max_points, model, matches
+        self.usable, self.hypotheses, self.inliers, self.found, self.a, self.b = (w32[:, k] for k in range(6))
+        self.flags = w32[:, 32:32 + max_points]
+
+    @property
+    def sums(self):
+        import torch
+        packed = torch.empty((self.records.shape[0], 96), dtype=torch.uint8, device=self.records.device)
+        return packed.copy_(self.records[:, 32:128]).view(torch.int64)
+
+    def inlier_slots(self, r):
+        """the slots of record r with the inlier flag, ascending, as a host list"""
+        return [i for i, f in enumerate(self.flags[r].tolist()) if f & MODEL_FLAGS["inlier"]]
+
+    def pairs(self, r, kept_points, current_points, inliers=True):
+        """the matched coordinates (xk, yk, xc, yc) of the inliers of record r — inliers=False: of its usable pairs that are not — as a
+        host list in slot order; the point records are those of the call"""
+        import torch
+        if self.matches is None:
+            raise ValueError("PointModel.pairs: this PointModel was not made by pull_model (no matches)")
+        R, K = self.records.shape[0], self.max_points
+        xk, yk = PointMatches._points("PointModel.pairs", kept_points, R, K)
+        xc, yc = PointMatches._points("PointModel.pairs", current_points, R, K)
+        j = self.matches[r, 32:32 + 16 * K].cpu().contiguous().view(torch.int32)[0::4].tolist()
+        want = MODEL_FLAGS["usable"] | MODEL_FLAGS["inlier"] if inliers else MODEL_FLAGS["usable"]
+        return [(xk[r][i], yk[r][i], xc[r][j[i]], yc[r][j[i]]) for i, f in enumerate(self.flags[r].tolist()) if f == want]
+
+    def theta(self, kind="similarity"):
+        """the least-squares transform kept -> current of every record's inliers, from `sums` in closed form: float64 numpy [R, 2, 3],
+        (u, v) = theta @ (x, y, 1) in window samples, ready for affine_maps.  kind "translation", "similarity" (rotation, uniform
+        scale, translation: no reflection) or "affine", whatever the model of the call.  The moments are centred exactly in integers
+        (N Σxx - Σx Σx, ...), the normal equations solved in float64.  A row is NaN where nothing was found or the centred moments are
+        singular for the kind: a similarity needs two distinct kept points among the inliers, an affine transform three that are not
+        collinear"""
+        if kind not in ("translation", "similarity", "affine"):
+            raise ValueError(f"PointModel.theta: kind is 'translation', 'similarity' or 'affine', not {kind!r}")
+        sums, counts, found = self.sums.tolist(), self.inliers.tolist(), self.found.tolist()
+        out = np.full((len(sums), 2, 3), np.nan, np.float64)
+        for r, (s, N) in enumerate(zip(sums, counts)):
+            if not found[r] or N < 1:
+                continue
+            sx, sy, su, sv, sxx, sxy, syy, sxu, syu, sxv, syv, _ = s
+            cxx, cxy, cyy = N * sxx - sx * sx, N * sxy - sx * sy, N * syy - sy * sy        # N^2 x the centred moments, exact
+            cxu, cyu, cxv, cyv = N * sxu - sx * su, N * syu - sy * su, N * sxv - sx * sv, N * syv - sy * sv
+            if kind == "translation":
+                A = ((1.0, 0.0), (0.0, 1.0))
+            elif kind == "similarity":
+                if cxx + cyy == 0:
+                    continue
+                re, im = float(cxu + cyv) / float(cxx + cyy), float(cxv - cyu) / float(cxx + cyy)
+                A = ((re, -im), (im, re))
+            else:
+                det = cxx * cyy - cxy * cxy
+                if det == 0:
+                    continue
+                det = float(det)
+                A = ((float(cxu * cyy - cyu * cxy) / det, float(cyu * cxx - cxu * cxy) / det),
+                     (float(cxv * cyy - cyv * cxy) / det, float(cyv * cxx - cxv * cxy) / det))
+            mx, my, mu, mv = sx / N, sy / N, su / N, sv / N
+            out[r] = ((A[0][0], A[0][1], mu - A[0][0] * mx - A[0][1] * my), (A[1][0], A[1][1], mv - A[1][0] * mx - A[1][1] * my))
+        return out
+
+
+def pull_model(decoders, matches, kept_points, current_points, model="similarity", tolerance=2, max_scale=0, min_inliers=None, out=None,
+               stream=None):
+    """h264bsdmiOutputPointModel: which motion the accepted matches of every region agree on — an exhaustive, deterministic, all-integer
+    consensus fit of a translation or a similarity (rotation + uniform scale + translation), one kernel launch where the records lie;
+    no picture is read and nothing crosses to the host.  decoders: at least one, they only name the device.  matches: the PointMatches
+    of pull_matches or its records tensor [R, 32 + 80 K]; kept_points, current_points: the two point arguments that call was given
+    (CornerPoints or records [R, 32 + 16 K]).  model "translation" (a hypothesis is one match) or "similarity" (a pair of matches);
+    a match is an inlier within `tolerance` (0..255) luma samples of where the hypothesis sends its kept point; max_scale (similarity:
+    0, or 256..4096 in 256ths) bounds the scale of a hypothesis and its inverse; found needs min_inliers (None: 1 for a translation, 2
+    for a similarity; up to 256).  The best hypothesis has the most inliers, then the smallest slots.  out: [R, model_record_bytes(K)]
+    uint8; out and stream as for pull_matches.  Returns a PointModel; the loop:
+        c1 = pull_corners(decs)
+        m = pull_matches(decs, c0, c1)
+        g = pull_model(decs, m, c0, c1)
+        maps = affine_maps(g.theta(), (H, W))
+        pull_remap(decs, maps)
+    gives the current pictures registered on the kept ones."""
+    import torch
+    n = len(decoders)
+    ints = lambda *vs: all(isinstance(v, int) and not isinstance(v, bool) for v in vs)
+    if model not in MODEL_KINDS:
+        raise ValueError(f"pull_model: model is 'translation' or 'similarity', not {model!r}")
+    kind = MODEL_KINDS[model]
+    if min_inliers is None:
+        min_inliers = 1 + kind
+    if not ints(tolerance, max_scale, min_inliers) or not 0 <= tolerance <= 255 or not 1 + kind <= min_inliers <= 256:
+        raise ValueError(f"pull_model: tolerance is an int in 0..255 and min_inliers in {1 + kind}..256, not {tolerance} {min_inliers}")
+    if max_scale != 0 and (kind == 0 or not 256 <= max_scale <= 4096):
+        raise ValueError(f"pull_model: max_scale is 0, or for a similarity an int in 256..4096, not {max_scale}")
+    if n < 1 or len({id(d) for d in decoders}) != n or any(not isinstance(d, Decoder) or not d._st for d in decoders):
+        raise ValueError("pull_model: decoders are at least one open Decoder, each once")
+    mrec = matches.records if isinstance(matches, PointMatches) else matches
+    if not isinstance(mrec, torch.Tensor) or not mrec.is_cuda or mrec.dtype != torch.uint8 or mrec.dim() != 2 or not mrec.is_contiguous() or \
+            mrec.data_ptr() % 8 or mrec.shape[1] < 112 or (mrec.shape[1] - 32) % 80 or (mrec.shape[1] - 32) // 80 > MATCHES_MAX_POINTS:
+        raise ValueError("pull_model: matches are a PointMatches or a contiguous, 8-byte aligned CUDA uint8 tensor [R, 32 + 80 K]")
+    R, K = mrec.shape[0], (mrec.shape[1] - 32) // 80
+    if R > 65535:
+        raise ValueError("pull_model: at most 65535 records per call")
+    krec, Pk = _point_records("pull_model", kept_points, R)
+    crec, Pc = _point_records("pull_model", current_points, R)
+    if Pk != K or Pc != K:
+        raise ValueError(f"pull_model: the matches have max_points {K}, the point records {Pk} and {Pc}")
+    out, stream = _out_and_stream("pull_model", out, (R, model_record_bytes(K)), torch.uint8, stream, aligned=True)
+    spec = ModelSpec(out.data_ptr(), mrec.data_ptr(), krec.data_ptr(), crec.data_ptr(), K, kind, tolerance, max_scale, min_inliers, (ctypes.c_uint32 * 3)())
+    _model_call(decoders, R, spec, stream)
+    return PointModel(out, K, model, mrec)
+
+
+def _model_call(decoders, R, spec, stream):
+    """the C call of pull_model: what it refuses is a ValueError as well"""
+    n = len(decoders)
+    rc = api_lib().h264bsdmiOutputPointModel(n, (ctypes.c_void_p * n)(*[d._st for d in decoders]), R, ctypes.byref(spec), stream.cuda_stream)
+    if rc == -1:
+        raise ValueError("pull_model: h264bsdmiOutputPointModel refused the call (a decoder in capture mode, decoders on several devices)")
+    if rc != 0:
+        raise RuntimeError(f"h264bsdmiOutputPointModel failed ({rc})")
 
 
 class CellBoxes:

@@ -846,6 +846,34 @@ int h264bsdmiOutputPointMatches(u32 n, storage_t *const *dec, u32 nRegions, cons
                      got, current, kept, picId, keptPicId);
 }
 
+/* Which motion the point matches agree on: the consensus fit of h264bsdmiOutputPointMatches' records.  The one call here without
+ * pictures: the instances only name the device, so none of the pull steps applies — the spec, then the instances (each on a sink of the
+ * engine with the entry, distinct, one device), then the entry of instance 0's sink with that sink */
+static int model_spec_refused(const h264bsdmi_model_spec *s)
+{
+    if (!s || !s->data || ((uintptr_t)s->data & 7u) || !s->matches || ((uintptr_t)s->matches & 7u) || !s->kept_points ||
+        ((uintptr_t)s->kept_points & 7u) || !s->current_points || ((uintptr_t)s->current_points & 7u)) return 1;
+    if (s->max_points < 1 || s->max_points > H264BSDMI_MODEL_MAX_POINTS || s->model > H264BSDMI_MODEL_SIMILARITY || s->tolerance > 255) return 1;
+    if (s->model == H264BSDMI_MODEL_SIMILARITY ? s->max_scale && (s->max_scale < 256 || s->max_scale > 4096) : s->max_scale != 0) return 1;
+    return s->min_inliers < 1 + s->model || s->min_inliers > 256 || s->zero[0] || s->zero[1] || s->zero[2];
+}
+int h264bsdmiOutputPointModel(u32 n, storage_t *const *dec, u32 nRecords, const h264bsdmi_model_spec *spec, void *stream)
+{
+    if (model_spec_refused(spec) || nRecords > 65535u || (n && !dec) || (!n && nRecords)) return -1;
+    for (u32 i = 0; i < n; i++) {
+        const ApiDec *a = dec_of(dec[i]);
+        if (!a || a->hd->sink.configure == cap_configure) return -1;           /* capture mode: there is no device */
+        const EngSinkEntries *entries = sink_entries(&a->hd->sink);
+        if (!entries || !entries->point_model) return -1;
+        if (eng_sink_device(&a->hd->sink) != eng_sink_device(&dec_of(dec[0])->hd->sink)) return -1;
+        for (u32 k = 0; k < i; k++)
+            if (dec[k] == dec[i]) return -1;
+    }
+    if (!nRecords) return 0;
+    const JobSink *sink = &dec_of(dec[0])->hd->sink;
+    return sink_entries(sink)->point_model(sink, nRecords, spec, stream) ? -2 : 0;
+}
+
 static u32 *next_converted(storage_t *s, u32 *picId, u32 *isIdrPic, u32 *numErrMbs, int fmt)
 {
     ApiDec *a = dec_of(s);

@@ -32,12 +32,17 @@ int  eng_device_cpus(int device, int *cpus, int max);
  *   point_matches  h264bsdmiOutputPointMatches: per region the binary descriptors of the points of spec->kept_points (on the kept
  *               picture of the region's instance) and of spec->current_points (on its current picture), record `index` of each, and
  *               their Hamming matching, into record `index` of spec->data, with two launches on one stream.  The pictures, the kept
- *               pictures, keep_after and the return value as for cell_shift */
+ *               pictures, keep_after and the return value as for cell_shift
+ *   point_model  h264bsdmiOutputPointModel: per record r < n_records the consensus fit of record r of spec->matches, spec->kept_points
+ *               and spec->current_points into record r of spec->data, with one launch.  The first entry without pictures: `sink`, the
+ *               sink of the call's first instance, only names the engine and its device; nothing of any instance is read, waited for
+ *               or marked.  0 = ok; <0 = error, nothing enqueued */
 typedef struct EngSinkEntries {
     int (*cell_shift)(uint32_t n, const SinkTensorPic *pics, uint32_t n_regions, const SinkRegion *regions,
                       const struct h264bsdmi_cell_shift_spec *spec, void *stream);
     int (*point_matches)(uint32_t n, const SinkTensorPic *pics, uint32_t n_regions, const SinkRegion *regions,
                          const struct h264bsdmi_matches_spec *spec, void *stream);
+    int (*point_model)(const JobSink *sink, uint32_t n_records, const struct h264bsdmi_model_spec *spec, void *stream);
 } EngSinkEntries;
 const EngSinkEntries *eng_sink_entries(const JobSink *sink);
 

@@ -47,6 +47,7 @@
 #include "kernels/k_cell_shift.hip.h"
 #include "kernels/k_corner_points.hip.h"
 #include "kernels/k_point_matches.hip.h"
+#include "kernels/k_point_model.hip.h"
 #include "kernels/k_cell_maps.hip.h"
 #include "kernels/k_cell_boxes.hip.h"
 #include "engine.h"
@@ -209,6 +210,8 @@ struct Engine {
      * recording covers all earlier ones, and a kept buffer is freed behind it (kept_drop) */
     Event kept_ev;
     bool kept_recorded = false;
+    /* h264bsdmiOutputPointModel without a caller's stream: recorded behind its launch on the engine's stream, and waited for */
+    Event model_ev;
 };
 
 /* One engine per HIP device, created on first use.  A decoder instance (or replay set) lives on the device that is
@@ -2071,6 +2074,48 @@ int sink_point_matches(uint32_t n, const SinkTensorPic *pics, uint32_t n_regions
         return matches_out_locked(e, n, pics, n_regions, regions, *spec, st, fence_ev);
     });
 }
+/* EngSinkEntries.point_model (h264bsdmiOutputPointModel): the first entry without pictures — the sink only names the engine, nothing is
+ * staged (the kernel finds record r of the four arrays by its stride), no fence goes to an instance and no kept picture is touched, so
+ * none of pull_begin_locked / pull_end_locked / the kept pictures' ordering applies.  One launch of a workgroup per record; without a
+ * caller's stream the device's error words follow it and the call waits for an event of the engine's own. */
+int sink_point_model(const JobSink *sink, uint32_t n_records, const h264bsdmi_model_spec *spec, void *stream)
+{
+    if (!n_records) return 0;
+    if (!sink || sink->configure != sink_configure || !spec) return -1;
+    const h264bsdmi_model_spec &sp = *spec;
+    const auto misaligned = [](const void *p) { return !p || (reinterpret_cast<uintptr_t>(p) & 7u); };
+    if (misaligned(sp.data) || misaligned(sp.matches) || misaligned(sp.kept_points) || misaligned(sp.current_points)) return -1;
+    if (sp.max_points < 1u || sp.max_points > h264k::MODEL_MAX_K || sp.model > h264k::MODEL_SIMILARITY || sp.tolerance > 255u) return -1;
+    if (sp.model == h264k::MODEL_SIMILARITY ? sp.max_scale && (sp.max_scale < 256u || sp.max_scale > 4096u) : sp.max_scale != 0u) return -1;
+    if (sp.min_inliers < 1u + sp.model || sp.min_inliers > 256u || sp.zero[0] || sp.zero[1] || sp.zero[2]) return -1;
+    if (n_records > 65535u) return -1;
+    Engine *e = static_cast<SinkUser *>(sink->user)->e;
+    hipEvent_t done = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(e->mu);
+        HIP_TRY(hipSetDevice(e->device));
+        hipStream_t st = stream ? static_cast<hipStream_t>(stream) : e->stream;
+        if (stream) {
+            hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+            HIP_TRY(hipStreamIsCapturing(st, &cs));
+            if (cs != hipStreamCaptureStatusNone) return -1;                      /* graph capture of this call is not supported */
+        }
+        h264k::ModelArgs margs{ static_cast<uint8_t *>(sp.data), static_cast<const uint8_t *>(sp.matches), static_cast<const uint8_t *>(sp.kept_points),
+                                static_cast<const uint8_t *>(sp.current_points), sp.max_points, sp.model, sp.tolerance, sp.max_scale, sp.min_inliers };
+        void *args[] = { &margs };
+        HIP_TRY(hipLaunchKernel(reinterpret_cast<const void *>(&h264k::k_point_model), dim3(n_records), dim3(h264k::MODEL_THREADS), args, 0, st));
+        if (stream) return 0;
+        hipLaunchKernelGGL(k_err_words, dim3(1), dim3(64), 0, st, e->d_err, e->h_err.dev());
+        HIP_TRY(hipGetLastError());
+        if (!e->model_ev) HIP_TRY(e->model_ev.create(hipEventDisableTiming));
+        HIP_TRY(hipEventRecord(e->model_ev, st));
+        done = e->model_ev;
+    }
+    if (hipEventSynchronize(done) != hipSuccess) return -1;            /* (a later call may have recorded it again: that only waits longer) */
+    std::lock_guard<std::mutex> lk(e->mu);
+    fold_errors(e);
+    return 0;
+}
 /* JobSink.set_motion (h264bsdmiSetMotionExport): before the instance's first sequence is configured */
 int sink_set_motion(void *user, int on)
 {
@@ -2126,7 +2171,7 @@ int eng_attach(JobSink *sink)
 /* engine.h: the entries behind the last member of JobSink, for a sink eng_attach has bound */
 const EngSinkEntries *eng_sink_entries(const JobSink *sink)
 {
-    static const EngSinkEntries entries = { sink_cell_shift, sink_point_matches };
+    static const EngSinkEntries entries = { sink_cell_shift, sink_point_matches, sink_point_model };
     return sink && sink->configure == sink_configure ? &entries : nullptr;
 }
 

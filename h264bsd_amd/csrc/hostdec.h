@@ -229,6 +229,7 @@ struct h264bsdmi_blend_spec;
 struct h264bsdmi_corners_spec;
 struct h264bsdmi_cell_shift_spec;
 struct h264bsdmi_matches_spec;
+struct h264bsdmi_model_spec;
 struct JobSink;
 /* one picture of a batched tensor pull (JobSink.tensor_out): the frame buffer `slot` of the instance behind `sink`, its window
  * (x0, y0, w, h), and the picture's index in the output tensor */

@@ -715,6 +715,69 @@ int h264bsdmiOutputPointMatches(u32 n, storage_t *const *pStorage, u32 nRegions,
                                 u32 *got, u32 *current, u32 *kept, u32 *picId, u32 *keptPicId);
 const signed char *h264bsdmiDescriptorPattern(void);
 
+/* Point model: WHICH motion do the matches agree on — an exhaustive, deterministic, all-integer consensus fit of a translation or of a
+ * similarity (rotation + uniform scale + translation) to the accepted matches of every region, computed where the records lie: the step
+ * behind h264bsdmiOutputPointMatches, whose sum_dx, sum_dy is a translation only and is pulled by every mismatch and every object that
+ * moves.  Not random-sample consensus: EVERY hypothesis is tried, which K <= 256 allows.  The output is the inlier set, the two slots that
+ * span the best hypothesis and the exact integer moment sums of the inliers, from which a least-squares translation, similarity or affine
+ * transform kept -> current follows on the host in closed form; the inlier and outlier flags separate "the camera" from "what moved in
+ * front of it".
+ * The call needs NO PICTURE: the instances only name the device.  n >= 1 instances, each non-NULL and distinct, each on a sink of this
+ * engine that has the entry, all on one device; no instance needs a current or a kept picture or to have been fed anything; nothing is
+ * popped or marked.  There are no `got` arrays: every record r < nRecords is written WHOLE with plain stores, the caller does not clear
+ * it.  nRecords == 0 returns 0 and launches nothing; nRecords <= 65535.  The stream rule is the siblings': with a stream the call is
+ * enqueued there and returns; with NULL it runs on the engine's stream and returns after completion, the device's error words folded; a
+ * capturing stream is refused.
+ * The three inputs are caller memory, read as they are: record r of `matches` at + r * (32 + 80 K) (h264bsdmiOutputPointMatches at K), of
+ * kept_points and current_points at + r * (32 + 16 K) (h264bsdmiOutputCornerPoints at K).  Garbage in them leads to no access outside
+ * the three records of that r and to no arithmetic overflow.  data must not overlap the inputs (undefined, not checked).
+ * THE DEFINITION, all integers:
+ *     pair of slot i    slot i (0 <= i < K) gives a USABLE PAIR iff the matches slot's flags have H264BSDMI_MATCH_ACCEPTED, its j
+ *                       satisfies 0 <= j < K, i < min(kept `written`, K) and j < min(current `written`, K), and all four coordinates
+ *                       p = (xk, yk) (kept slot i) and q = (xc, yc) (current slot j) lie in 0 .. 16383.  That bound makes every
+ *                       quantity below fit 64 bits: differences are < 2^14, components of complex products of differences < 2^30,
+ *                       their squared norm < 2^61
+ *     TRANSLATION       a hypothesis is one usable slot a, with t = q_a - p_a; slot i is an inlier iff |q_i - p_i - t|^2 <= tolerance^2
+ *     SIMILARITY        a hypothesis is a pair of usable slots a < b with p_a != p_b and q_a != q_b; with max_scale = S > 0 the pair
+ *                       must also satisfy 65536 |q_b - q_a|^2 <= S^2 |p_b - p_a|^2 and 65536 |p_b - p_a|^2 <= S^2 |q_b - q_a|^2.
+ *                       Points are read as complex numbers x + iy; slot i is an inlier iff
+ *                           |(q_i - q_a)(p_b - p_a) - (q_b - q_a)(p_i - p_a)|^2 <= tolerance^2 |p_b - p_a|^2
+ *                       which is |q_i - (q_a + s (p_i - p_a))| <= tolerance for s = (q_b - q_a) / (p_b - p_a), without a division.
+ *                       It preserves orientation: no reflections
+ *     best hypothesis   the one with the most inliers, then the smallest a, then the smallest b
+ *     found             iff a hypothesis exists and its inlier count >= min_inliers
+ * Record r is written at spec->data + r * stride, little endian, stride = 128 + 4 K:
+ *     u32 usable; u32 hypotheses; u32 inliers; u32 found; i32 a; i32 b; u32 zero[2];
+ *     i64 sum[12]         over the inliers, with (x, y) = p and (u, v) = q:
+ *                         Σx, Σy, Σu, Σv, Σxx, Σxy, Σyy, Σxu, Σyu, Σxv, Σyv, Σ(uu + vv)
+ *     K x u32 flags       H264BSDMI_MODEL_USABLE, H264BSDMI_MODEL_INLIER
+ * usable counts the usable pairs, hypotheses those that passed the gates (TRANSLATION: the usable slots); b = -1 for TRANSLATION; not
+ * found gives inliers = 0, a = b = -1, all sums 0 and no inlier bit.  Slot indices are those of the point records.  Everything is an
+ * integer and exact, and no result depends on scheduling.  (With K odd a record is 4-byte aligned only: read the sums accordingly.)
+ * -1, before anything is enqueued, nothing written: spec NULL; data, matches, kept_points or current_points NULL or not 8-byte aligned;
+ * max_points outside 1 .. 256; model > 1; tolerance > 255; max_scale neither 0 nor in 256 .. 4096, or not 0 for TRANSLATION; min_inliers
+ * outside 1 .. 256, or 1 for SIMILARITY; zero != 0; n == 0 with nRecords > 0; a NULL or repeated instance; nRecords > 65535; a
+ * capture-mode instance; a sink without the entry; instances on more than one device.  -2: the engine failed, or refused a capturing
+ * stream: nothing was enqueued. */
+#define H264BSDMI_MODEL_TRANSLATION 0u
+#define H264BSDMI_MODEL_SIMILARITY  1u
+#define H264BSDMI_MODEL_USABLE 1u
+#define H264BSDMI_MODEL_INLIER 2u
+#define H264BSDMI_MODEL_MAX_POINTS 256u
+typedef struct h264bsdmi_model_spec {
+    void       *data;            /* DEVICE, caller-owned, 8-byte aligned: record r at data + r * (128 + 4 K) */
+    const void *matches;         /* DEVICE, 8-byte aligned: records of h264bsdmiOutputPointMatches at max_points == K, stride 32 + 80 K */
+    const void *kept_points;     /* DEVICE, 8-byte aligned: records of h264bsdmiOutputCornerPoints at max_points == K, */
+    const void *current_points;  /*   stride 32 + 16 K: the two the matches were made from */
+    u32 max_points;              /* K, 1 .. 256 */
+    u32 model;                   /* H264BSDMI_MODEL_TRANSLATION / _SIMILARITY */
+    u32 tolerance;               /* 0 .. 255, whole luma samples */
+    u32 max_scale;               /* in 256ths: 0 = no gate, else 256 .. 4096; SIMILARITY only, 0 for TRANSLATION */
+    u32 min_inliers;             /* 1 .. 256; SIMILARITY: 2 .. 256 */
+    u32 zero[3];                 /* must be 0 */
+} h264bsdmi_model_spec;
+int h264bsdmiOutputPointModel(u32 n, storage_t *const *pStorage, u32 nRecords, const h264bsdmi_model_spec *spec, void *stream);
+
 /* ---- host parse pipeline at scale ----
  * h264bsdDecode() consumes one NAL unit of one stream per call; a caller that feeds hundreds of streams needs the
  * loop of posix/test_h264bsd.c:146-177 for each of them and its own threading.  These entry points move both into
