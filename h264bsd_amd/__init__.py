@@ -18,6 +18,7 @@ from .capi import (  # noqa: F401
     MatchesSpec, PointMatches, pull_matches, matches_record_bytes, descriptor_pattern,
     ModelSpec, PointModel, pull_model, model_record_bytes,
     BlendSpec, BLEND_FROZEN, blend_pictures, pull_kept,
+    WarpSpec, WarpMap, WARP_OUTSIDE, WARP_MAX_COEFFICIENT, warp_coefficients, warp_kept,
 )
 
 # 0.2: pull_remap / affine_maps (h264bsdmiOutputTensorRemap); 0.3: pull_stats (h264bsdmiOutputRegionStats);
@@ -26,4 +27,5 @@ from .capi import (  # noqa: F401
 # 0.8: blend_pictures / pull_kept (h264bsdmiBlendCurrentPictures, h264bsdmiOutputKeptPictures)
 # 0.9: pull_corners (h264bsdmiOutputCornerPoints); 0.10: pull_flow (h264bsdmiOutputCellShift)
 # 0.11: pull_matches (h264bsdmiOutputPointMatches); 0.12: pull_model (h264bsdmiOutputPointModel)
-__version__ = "0.12.0"
+# 0.13: warp_kept / warp_coefficients (h264bsdmiWarpKeptPictures)
+__version__ = "0.13.0"

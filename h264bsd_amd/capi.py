@@ -28,7 +28,7 @@ EXPORTED_SYMBOLS = [
     "h264bsdCroppingParams", "h264bsdSampleAspectRatio", "h264bsdCheckValidParamSets", "h264bsdFlushBuffer",
     "h264bsdProfile", "h264bsdAlloc", "h264bsdFree", "h264bsdConvertToRGBA", "h264bsdConvertToBGRA",
     "h264bsdConvertToYCbCrA",
-    "h264bsdmiInitCapture", "h264bsdmiNextOutputInfo", "h264bsdmiNextOutputPictureDevice", "h264bsdmiNextOutputTensorBatch", "h264bsdmiNextOutputTensorBatchColour", "h264bsdmiNextOutputTensorBatchResize", "h264bsdmiOutputTensorRegions", "h264bsdmiOutputTensorRemap", "h264bsdmiSetMotionExport", "h264bsdmiOutputMotionRegions", "h264bsdmiOutputRegionStats", "h264bsdmiKeepCurrentPictures", "h264bsdmiBlendCurrentPictures", "h264bsdmiOutputKeptPictures", "h264bsdmiOutputRegionChange", "h264bsdmiOutputRegionShift", "h264bsdmiOutputCornerPoints", "h264bsdmiOutputCellMaps", "h264bsdmiOutputCellBoxes", "h264bsdmiOutputCellShift", "h264bsdmiOutputPointMatches", "h264bsdmiDescriptorPattern", "h264bsdmiOutputPointModel", "h264bsdmiJobFinalize", "h264bsdmiDeviceCount", "h264bsdmiSetDevice", "h264bsdmiFlush", "h264bsdmiFlushAsync", "h264bsdmiDeviceErrors",
+    "h264bsdmiInitCapture", "h264bsdmiNextOutputInfo", "h264bsdmiNextOutputPictureDevice", "h264bsdmiNextOutputTensorBatch", "h264bsdmiNextOutputTensorBatchColour", "h264bsdmiNextOutputTensorBatchResize", "h264bsdmiOutputTensorRegions", "h264bsdmiOutputTensorRemap", "h264bsdmiSetMotionExport", "h264bsdmiOutputMotionRegions", "h264bsdmiOutputRegionStats", "h264bsdmiKeepCurrentPictures", "h264bsdmiBlendCurrentPictures", "h264bsdmiOutputKeptPictures", "h264bsdmiWarpKeptPictures", "h264bsdmiOutputRegionChange", "h264bsdmiOutputRegionShift", "h264bsdmiOutputCornerPoints", "h264bsdmiOutputCellMaps", "h264bsdmiOutputCellBoxes", "h264bsdmiOutputCellShift", "h264bsdmiOutputPointMatches", "h264bsdmiDescriptorPattern", "h264bsdmiOutputPointModel", "h264bsdmiJobFinalize", "h264bsdmiDeviceCount", "h264bsdmiSetDevice", "h264bsdmiFlush", "h264bsdmiFlushAsync", "h264bsdmiDeviceErrors",
     "h264bsdmiDecodePicture", "h264bsdmiDecodePictureBatch", "h264bsdmiNextOutputPictureBatch", "h264bsdmiPullAndDecodePictureBatch", "h264bsdmiSetParserThreads", "h264bsdmiSetInputReadOnly", "h264bsdmiSetCopyElision",
     "h264bsdmiReplayCreate", "h264bsdmiReplayCreateStaggered", "h264bsdmiReplayCreateDesync", "h264bsdmiReplayCreateSched", "h264bsdmiReplayReschedule", "h264bsdmiReplayDestroy", "h264bsdmiReplayRun", "h264bsdmiReplaySync",
     "h264bsdmiReplayFetch", "h264bsdmiReplayDbkRecords", "h264bsdmiReplayChecksums", "h264bsdmiReplayConvert", "h264bsdmiReplayFetchConverted",
@@ -101,6 +101,20 @@ class BlendSpec(ctypes.Structure):
 
 
 BLEND_FROZEN = 8                                                                 # H264BSDMI_BLEND_FROZEN
+
+
+class WarpMap(ctypes.Structure):
+    """h264bsdmi_warp_map (include/h264bsd_mi355x.h): output -> source, 16.16 fixed point"""
+    _fields_ = [(k, ctypes.c_int32) for k in "abcdef"]
+
+
+class WarpSpec(ctypes.Structure):
+    """h264bsdmi_warp_spec (include/h264bsd_mi355x.h)"""
+    _fields_ = [("maps", ctypes.POINTER(WarpMap)), ("outside", ctypes.c_uint32), ("crop", ctypes.c_uint32), ("count", ctypes.c_void_p)]
+
+
+WARP_OUTSIDE = {"replicate": 0, "current": 1}                                    # H264BSDMI_WARP_*
+WARP_MAX_COEFFICIENT = 16 * 65536                                                # H264BSDMI_WARP_MAX_COEFFICIENT
 
 
 class ShiftSpec(ctypes.Structure):
@@ -321,6 +335,8 @@ def _declare(L, harness):
     L.h264bsdmiOutputPointMatches.argtypes = [u32, ctypes.POINTER(vp), u32, ctypes.POINTER(Region), ctypes.POINTER(MatchesSpec), vp,
                                               P32, P32, P32, P32, P32]
     L.h264bsdmiOutputPointMatches.restype = ctypes.c_int
+    L.h264bsdmiWarpKeptPictures.argtypes = [u32, ctypes.POINTER(vp), ctypes.POINTER(WarpSpec), vp, P32, P32]
+    L.h264bsdmiWarpKeptPictures.restype = ctypes.c_int
     L.h264bsdmiOutputPointModel.argtypes = [u32, ctypes.POINTER(vp), u32, ctypes.POINTER(ModelSpec), vp]
     L.h264bsdmiOutputPointModel.restype = ctypes.c_int
     L.h264bsdmiDescriptorPattern.argtypes = []
@@ -1058,6 +1074,102 @@ def pull_kept(decoders, fraction=False, stream=None):
         if rc != 0:
             raise RuntimeError(f"h264bsdmiOutputKeptPictures failed ({rc})")
     return [None if not got[i] else (pics[i], fracs[i]) if fraction else pics[i] for i in range(n)]
+
+
+def _warp_row_refused(row):
+    """what h264bsdmiWarpKeptPictures refuses of one map a b c d e f of Python ints, as a message, or None"""
+    a, b, c, d, e, f = row
+    if max(abs(a), abs(b), abs(d), abs(e)) > WARP_MAX_COEFFICIENT:
+        return f"|a|, |b|, |d|, |e| are at most 16 * 65536, not {(a, b, d, e)}"
+    if not (-2 ** 31 <= c < 2 ** 31 and -2 ** 31 <= f < 2 ** 31):
+        return f"c and f are int32, not {(c, f)}"
+    return None
+
+
+def warp_coefficients(theta):
+    """The maps warp_kept takes, from transforms kept -> current as PointModel.theta() returns them: float64 [n, 2, 3] with
+    (u, v) = theta @ (x, y, 1) in window samples.  The warp wants the way back, output -> source: every row is inverted in float64,
+    scaled by 65536 and rounded with np.rint.  Returns a list of n entries: an int32 numpy array [6] (a b c d e f, 16.16 fixed point),
+    or None for a row that holds a NaN or an infinity or is singular.  A row whose coefficients leave the range of the call (|a|, |b|,
+    |d|, |e| <= 16 * 65536; c, f int32) raises ValueError."""
+    theta = np.asarray(theta, np.float64)
+    if theta.ndim != 3 or theta.shape[1:] != (2, 3):
+        raise ValueError(f"warp_coefficients: theta is [n, 2, 3], not {list(theta.shape)}")
+    out = []
+    for r, ((p, q, tx), (s, t, ty)) in enumerate(theta.tolist()):
+        det = p * t - q * s
+        if not np.isfinite([p, q, tx, s, t, ty]).all() or det == 0.0 or not np.isfinite(det):
+            out.append(None)
+            continue
+        inv = np.array([t / det, -q / det, (q * ty - t * tx) / det, -s / det, p / det, (s * tx - p * ty) / det], np.float64)
+        fixed = np.rint(inv * 65536.0)
+        if not np.isfinite(fixed).all():
+            raise ValueError(f"warp_coefficients: row {r} has no finite inverse in 16.16 fixed point")
+        row = [int(v) for v in fixed]
+        refused = _warp_row_refused(row)
+        if refused:
+            raise ValueError(f"warp_coefficients: row {r}: {refused}")
+        out.append(np.array(row, np.int32))
+    return out
+
+
+def warp_kept(decoders, theta=None, coefficients=None, outside="replicate", crop=True, count_outside=False, stream=None):
+    """h264bsdmiWarpKeptPictures: the kept picture of every decoder (keep_pictures, blend_pictures) is resampled IN PLACE through an
+    affine map, the picture and the fraction of the background model, by one launch — the background moved to where the camera now
+    looks, so that pull_change, pull_shift, pull_cells(against="kept"), pull_boxes, pull_flow, pull_matches and blend_pictures read it
+    registered on the current picture.  theta: float64 [n, 2, 3] kept -> current, as PointModel.theta() returns it (it goes through
+    warp_coefficients); or coefficients: per decoder a b c d e f, int32 in 16.16 fixed point, the map from OUTPUT to SOURCE in luma
+    samples of the window (crop: the frame-cropping window, else the coded frame) — an [n, 6] array, or a list whose entries may be
+    None.  Bilinear on the 16-bit state S = 256 hi + lo, all integers and exact (tests/warp_model.py restates it); the identity changes
+    no byte, whole-sample translations are index shifts.  outside "replicate": a source position outside the window takes the nearest
+    sample of it; "current": the output sample takes the CURRENT picture's there, as a starting blend writes it (a decoder without a
+    current picture is then left alone).  A decoder whose row is None or NaN is left out of the call, one without a kept picture is
+    left alone.  count_outside: also the number of luma samples of every decoder's window whose source was outside.  stream as for
+    pull_tensor.  Returns (warped, kept_pic_ids): per decoder 1 when its kept picture was resampled, and the picId it carries (0: it
+    has none) — and with count_outside an int32 CUDA tensor [n] behind them.  Repeated resampling softens the picture; the 16-bit
+    state delays that and does not remove it."""
+    import torch
+    n = len(decoders)
+    if (theta is None) == (coefficients is None):
+        raise ValueError("warp_kept: give theta or coefficients, one of them")
+    if outside not in WARP_OUTSIDE:
+        raise ValueError(f'warp_kept: outside is "replicate" or "current", not {outside!r}')
+    rows = warp_coefficients(theta) if coefficients is None else [None if c is None else np.asarray(c) for c in coefficients]
+    if len(rows) != n:
+        raise ValueError(f"warp_kept: {len(rows)} maps for {n} decoders")
+    for r, row in enumerate(rows):
+        if row is None:
+            continue
+        if row.shape != (6,) or row.dtype.kind not in "iu":
+            raise ValueError(f"warp_kept: row {r} of coefficients is six integers, not {row.dtype} {list(row.shape)}")
+        refused = _warp_row_refused([int(v) for v in row])
+        if refused:
+            raise ValueError(f"warp_kept: row {r}: {refused}")
+    sel = [i for i in range(n) if rows[i] is not None]
+    m = len(sel)
+    warped, ids = [0] * n, [0] * n
+    counts = None
+    if count_outside:
+        with torch.cuda.stream(stream or torch.cuda.current_stream()):
+            counts = torch.zeros((n,), dtype=torch.int32, device="cuda")
+            part = torch.zeros((max(m, 1),), dtype=torch.int32, device="cuda")
+    stream = _call_stream(stream)                       # (behind the fill: the legacy default stream is waited for)
+    if m:
+        maps = (WarpMap * m)(*[WarpMap(*[int(v) for v in rows[i]]) for i in sel])
+        spec = WarpSpec(maps, WARP_OUTSIDE[outside], 1 if crop else 0, part.data_ptr() if count_outside else None)
+        got, kid = (ctypes.c_uint32 * m)(), (ctypes.c_uint32 * m)()
+        rc = api_lib().h264bsdmiWarpKeptPictures(m, (ctypes.c_void_p * m)(*[decoders[i]._st for i in sel]), ctypes.byref(spec), stream.cuda_stream,
+                                                 got, kid)
+        if rc == -1:
+            raise ValueError("warp_kept: h264bsdmiWarpKeptPictures refused the call (a decoder in capture mode, a decoder named twice)")
+        if rc != 0:
+            raise RuntimeError(f"h264bsdmiWarpKeptPictures failed ({rc})")
+        for k, i in enumerate(sel):
+            warped[i], ids[i] = got[k], kid[k]
+        if count_outside:
+            with torch.cuda.stream(stream):
+                counts[torch.tensor(sel, dtype=torch.int64, device="cuda")] = part[:m]
+    return (warped, ids, counts) if count_outside else (warped, ids)
 
 
 class RegionChange:

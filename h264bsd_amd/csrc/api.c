@@ -688,6 +688,53 @@ int h264bsdmiOutputKeptPictures(u32 n, storage_t *const *dec, void *const *pictu
     return failed ? -2 : 0;
 }
 
+/* The kept pictures of the instances that have one resampled in place through an affine map each.  The checks in the keep call's order
+ * behind the spec's; then one picture per instance that is warped — its window, and under CURRENT its current picture's slot — with
+ * its map beside it, through the engine's warp_kept entry (engine.h) */
+static int warp_map_refused(const h264bsdmi_warp_map *m)
+{
+    const int top = H264BSDMI_WARP_MAX_COEFFICIENT;
+    return m->a > top || m->a < -top || m->b > top || m->b < -top || m->d > top || m->d < -top || m->e > top || m->e < -top;
+}
+int h264bsdmiWarpKeptPictures(u32 n, storage_t *const *dec, const h264bsdmi_warp_spec *spec, void *stream, u32 *warped, u32 *keptPicId)
+{
+    if (!n) return 0;
+    if (!spec || !spec->maps || spec->outside > H264BSDMI_WARP_CURRENT || spec->crop > 1) return -1;
+    for (u32 i = 0; i < n; i++)
+        if (warp_map_refused(&spec->maps[i])) return -1;
+    if (!dec || !warped) return -1;
+    for (u32 i = 0; i < n; i++) {
+        const ApiDec *a = dec_of(dec[i]);
+        if (!a || !sink_pulls(a, PULL_KEEP)) return -1;
+        const EngSinkEntries *entries = sink_entries(&a->hd->sink);
+        if (!entries || !entries->warp_kept) return -1;
+        for (u32 k = 0; k < i; k++)
+            if (dec[k] == dec[i]) return -1;
+    }
+    SinkTensorPic *pics = (SinkTensorPic *)malloc(n * sizeof(SinkTensorPic));
+    h264bsdmi_warp_map *maps = (h264bsdmi_warp_map *)malloc(n * sizeof(h264bsdmi_warp_map));
+    u32 *took = (u32 *)calloc(n, sizeof(u32));
+    if (!pics || !maps || !took) { free(pics); free(maps); free(took); return -1; }
+    const h264bsdmi_tensor_spec window = { NULL, 1, 1, 0, 0, 0, spec->crop, 1, { 0, 0, 0 }, { 1, 1, 1 } };
+    u32 m = 0;
+    for (u32 i = 0; i < n; i++) {
+        const ApiDec *a = dec_of(dec[i]);
+        const int cur = a->has_cur && a->hd->active_sps;
+        if (!has_kept_picture(a) || !a->hd->active_sps || (spec->outside == H264BSDMI_WARP_CURRENT && !cur)) continue;
+        tensor_pic(&pics[m], a, cur ? a->cur.slot : 0, i, &window, &REFERENCE_COLOUR);
+        maps[m++] = spec->maps[i];
+        took[i] = 1;
+    }
+    const int failed = m && sink_entries(pics[0].sink)->warp_kept(m, pics, maps, spec, n, stream);
+    for (u32 i = 0; !failed && i < n; i++) {
+        const ApiDec *a = dec_of(dec[i]);
+        warped[i] = took[i];
+        if (keptPicId) keptPicId[i] = has_kept_picture(a) ? a->kept_id : 0;
+    }
+    free(pics); free(maps); free(took);
+    return failed ? -2 : 0;
+}
+
 /* The host path of the pulls that may compare against kept pictures and may keep afterwards, behind their own spec checks:
  * h264bsdmiOutputRegionChange (PULL_CHANGE), h264bsdmiOutputRegionShift (PULL_SHIFT), h264bsdmiOutputCellMaps (PULL_CELLS) and
  * h264bsdmiOutputCellBoxes (PULL_BOXES, spec2 its boxes spec), h264bsdmiOutputCellShift (PULL_FLOW), h264bsdmiOutputPointMatches (PULL_MATCHES).  vs_kept: only instances that have a kept picture too; max_side: the

@@ -36,13 +36,23 @@ int  eng_device_cpus(int device, int *cpus, int max);
  *   point_model  h264bsdmiOutputPointModel: per record r < n_records the consensus fit of record r of spec->matches, spec->kept_points
  *               and spec->current_points into record r of spec->data, with one launch.  The first entry without pictures: `sink`, the
  *               sink of the call's first instance, only names the engine and its device; nothing of any instance is read, waited for
- *               or marked.  0 = ok; <0 = error, nothing enqueued */
+ *               or marked.  0 = ok; <0 = error, nothing enqueued
+ *   warp_kept   h264bsdmiWarpKeptPictures: the kept picture of every pics[i].sink (distinct instances of one device; each holds one of
+ *               its coded size) resampled through maps[i] inside the window pics[i] names, with one launch, and, under
+ *               H264BSDMI_WARP_CURRENT, filled from the current picture in pics[i].slot where the source was outside (under REPLICATE
+ *               the slot is not looked at: no frame buffer is read).  spec->maps is the caller's list and is not looked at; spec->count:
+ *               n_count words, zeroed on the stream ahead of the launch, picture i counts into word pics[i].index.  Called through the
+ *               table of any of the n sinks.  0 = ok; <0 = error, nothing enqueued */
+struct h264bsdmi_warp_map;
+struct h264bsdmi_warp_spec;
 typedef struct EngSinkEntries {
     int (*cell_shift)(uint32_t n, const SinkTensorPic *pics, uint32_t n_regions, const SinkRegion *regions,
                       const struct h264bsdmi_cell_shift_spec *spec, void *stream);
     int (*point_matches)(uint32_t n, const SinkTensorPic *pics, uint32_t n_regions, const SinkRegion *regions,
                          const struct h264bsdmi_matches_spec *spec, void *stream);
     int (*point_model)(const JobSink *sink, uint32_t n_records, const struct h264bsdmi_model_spec *spec, void *stream);
+    int (*warp_kept)(uint32_t n, const SinkTensorPic *pics, const struct h264bsdmi_warp_map *maps, const struct h264bsdmi_warp_spec *spec,
+                     uint32_t n_count, void *stream);
 } EngSinkEntries;
 const EngSinkEntries *eng_sink_entries(const JobSink *sink);
 

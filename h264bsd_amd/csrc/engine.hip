@@ -42,6 +42,7 @@
 #include "kernels/k_region_stats.hip.h"
 #include "kernels/k_keep.hip.h"
 #include "kernels/k_blend.hip.h"
+#include "kernels/k_warp_kept.hip.h"
 #include "kernels/k_region_change.hip.h"
 #include "kernels/k_region_shift.hip.h"
 #include "kernels/k_cell_shift.hip.h"
@@ -107,6 +108,9 @@ struct StreamCtx {
     /* the background model (h264bsdmiBlendCurrentPictures): the low byte of every sample of the kept picture, a second frame in the
      * same tiles, allocated at the instance's first blend and freed with d_kept; not valid (it reads as 0x80) after a plain keep */
     DeviceMem<uint8_t> d_kept_lo; bool kept_lo_valid = false;
+    /* warped kept pictures (h264bsdmiWarpKeptPictures): the frames a warp writes, hi and (where lo is valid) lo, swapped with the live
+     * ones behind its launch; allocated at the instance's first warp and freed with d_kept */
+    DeviceMem<uint8_t> d_kept_spare, d_kept_lo_spare;
 };
 
 /* k_dbk (boundary strengths) needs only the frame job, not pixels: it runs on a second HIP stream next to the
@@ -170,13 +174,13 @@ constexpr unsigned CONVERT_WGS = CONVERT_WGS_N;      /* workgroups per picture o
 constexpr uint32_t LANE_DBK_WAVES = LANE_DBK_WAVES_N;
 
 /* the item stride of the tensor pulls' staging ring: k_tensor_out / k_tensor_resize read TensorItems, k_tensor_aa AaItems, k_tensor_roi
- * RoiItems, k_motion_roi MotionItems, k_tensor_remap RemapItems, k_region_stats StatsItems, k_keep KeepItems, k_blend BlendItems, k_kept_out KeptOutItems, k_region_change ChangeItems, k_region_shift ShiftItems, k_corner_points CornerItems,
+ * RoiItems, k_motion_roi MotionItems, k_tensor_remap RemapItems, k_region_stats StatsItems, k_keep KeepItems, k_blend BlendItems, k_warp_kept WarpItems, k_kept_out KeptOutItems, k_region_change ChangeItems, k_region_shift ShiftItems, k_corner_points CornerItems,
  * k_cell_maps CellItems (k_cell_boxes: the same, and its BoxItems in slots of their own behind them), k_cell_shift FlowItems,
  * k_point_describe / k_point_match MatchItems */
 constexpr size_t TITEM_BYTES = std::max({ sizeof(h264k::TensorItem), sizeof(h264k::AaItem), sizeof(h264k::RoiItem), sizeof(h264k::MotionItem),
                                           sizeof(h264k::RemapItem), sizeof(h264k::StatsItem), sizeof(h264k::KeepItem), sizeof(h264k::ChangeItem),
                                           sizeof(h264k::CellItem), sizeof(h264k::BoxItem), sizeof(h264k::ShiftItem), sizeof(h264k::BlendItem),
-                                          sizeof(h264k::KeptOutItem), sizeof(h264k::CornerItem), sizeof(h264k::FlowItem), sizeof(h264k::MatchItem) });
+                                          sizeof(h264k::KeptOutItem), sizeof(h264k::CornerItem), sizeof(h264k::FlowItem), sizeof(h264k::MatchItem), sizeof(h264k::WarpItem) });
 struct TItemSlot { uint8_t bytes[TITEM_BYTES]; };
 struct Engine {
     std::mutex mu;
@@ -654,7 +658,7 @@ static void kept_drop(Engine *e, StreamCtx *s)
 {
     if (!s->d_kept) return;
     if (e->kept_recorded) (void)hipEventSynchronize(e->kept_ev);
-    s->d_kept.reset(); s->d_kept_lo.reset();
+    s->d_kept.reset(); s->d_kept_lo.reset(); s->d_kept_spare.reset(); s->d_kept_lo_spare.reset();
     s->kept_wmb = s->kept_hmb = 0; s->kept_lo_valid = false;
 }
 
@@ -1605,6 +1609,62 @@ static int blend_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, co
     return kept_order_end(e, st);
 }
 
+/* h264bsdmiWarpKeptPictures: the kept picture of every pics[i].sink (each holds one of its coded size, or the call is refused)
+ * resampled through maps[i] inside the window of pics[i], with ONE k_warp_kept launch inside the kept pictures' ordering: from the live
+ * buffers into the instance's spare ones (allocated here at the first warp; the lo spare only while lo is valid), every byte of which
+ * the launch writes; then live and spare change places on the host.  The ordering makes that safe across streams: every launch that
+ * reads or writes a kept buffer, this one included, is enqueued behind the previous one, so the next reader of d_kept runs behind this
+ * launch and the next warp, which writes the buffers that are live now, behind every reader of them.  Under CURRENT the current
+ * pictures are read: the checks, the flush, the wait and the fence of keep_out_locked; under REPLICATE no frame buffer is read, as in
+ * kept_out_locked.  sp.count: n_count words, zeroed on st ahead of the launch; picture i counts into word pics[i].index. */
+static int warp_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, const h264bsdmi_warp_map *maps, const h264bsdmi_warp_spec &sp,
+                           uint32_t n_count, hipStream_t st, hipEvent_t *fence_ev)
+{
+    const bool current = sp.outside == H264BSDMI_WARP_CURRENT;
+    if (n > 65535u || !maps || sp.outside > H264BSDMI_WARP_CURRENT) return -1;                 /* grid.y */
+    if (current && !pull_pictures_ok(n, pics, true, false)) return -1;
+    for (uint32_t i = 0; i < n; i++) {
+        const SinkTensorPic &p = pics[i];
+        const StreamCtx *s = pic_stream(p);
+        if (!p.w || !p.h || p.x0 + p.w > s->wmb * 16 || p.y0 + p.h > s->hmb * 16 || ((p.x0 | p.y0 | p.w | p.h) & 1u)) return -1;
+        if (sp.count && p.index >= n_count) return -1;
+        const int32_t lin[4] = { maps[i].a, maps[i].b, maps[i].d, maps[i].e };
+        for (int32_t v : lin)
+            if (v > H264BSDMI_WARP_MAX_COEFFICIENT || v < -H264BSDMI_WARP_MAX_COEFFICIENT) return -1;
+        for (uint32_t k = 0; k < i; k++)
+            if (pics[k].sink == p.sink) return -1;                      /* one kept picture per instance */
+    }
+    if (!kept_pictures_ok(n, pics)) return -1;
+    if (current ? pull_begin_locked(e, n, pics, n) : (e->titems.reserve(n, 256) != hipSuccess)) return -1;
+    if (kept_order_begin(e, st)) return -1;
+    h264k::WarpItem *items = e->titems.host<h264k::WarpItem>();
+    uint32_t most = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        const SinkTensorPic &p = pics[i];
+        StreamCtx *s = static_cast<SinkUser *>(p.sink->user)->s;
+        const size_t bytes = (size_t)s->kept_wmb * s->kept_hmb * h264k::TILE;
+        const bool lo = s->kept_lo_valid && s->d_kept_lo;
+        if (!s->d_kept_spare) HIP_TRY(s->d_kept_spare.alloc(bytes));
+        if (lo && !s->d_kept_lo_spare) HIP_TRY(s->d_kept_lo_spare.alloc(bytes));
+        items[i] = h264k::WarpItem{ current ? s->d_frames + (size_t)p.slot * s->frame_bytes : nullptr, s->d_kept.get(), lo ? s->d_kept_lo.get() : nullptr,
+                                    s->d_kept_spare.get(), lo ? s->d_kept_lo_spare.get() : nullptr, s->kept_wmb, s->kept_hmb, p.x0, p.y0, p.w, p.h,
+                                    p.index, { maps[i].a, maps[i].b, maps[i].c, maps[i].d, maps[i].e, maps[i].f } };
+        most = std::max(most, ((s->kept_wmb + 3u) / 4u) * s->kept_hmb);
+    }
+    if (sp.count) HIP_TRY(hipMemsetAsync(sp.count, 0, (size_t)n_count * sizeof(uint32_t), st));
+    if (current && pull_wait_pictures(e, n, pics, st)) return -1;
+    const h264k::WarpArgs wargs{ e->titems.dev<h264k::WarpItem>(), static_cast<uint32_t *>(sp.count), sp.outside };
+    hipLaunchKernelGGL(h264k::k_warp_kept, dim3(std::min(std::max(most, 1u), h264k::WARP_MAX_BLOCKS), n), dim3(256), 0, st, wargs);
+    HIP_TRY(hipGetLastError());
+    if (pull_end_locked(e, n, pics, st, fence_ev)) return -1;
+    for (uint32_t i = 0; i < n; i++) {
+        StreamCtx *s = static_cast<SinkUser *>(pics[i].sink->user)->s;
+        std::swap(s->d_kept, s->d_kept_spare);
+        if (s->kept_lo_valid && s->d_kept_lo) std::swap(s->d_kept_lo, s->d_kept_lo_spare);
+    }
+    return kept_order_end(e, st);
+}
+
 /* h264bsdmiOutputKeptPictures: the kept pictures of the instances pics[i].sink (each holds one of its coded size, or the call is
  * refused) as planar I420 into the caller's buffers, ONE k_kept_out launch inside the kept pictures' ordering.  No frame buffer is
  * read: nothing is flushed and no picture is waited for; the fence only carries the wait of a call without a stream. */
@@ -2074,6 +2134,15 @@ int sink_point_matches(uint32_t n, const SinkTensorPic *pics, uint32_t n_regions
         return matches_out_locked(e, n, pics, n_regions, regions, *spec, st, fence_ev);
     });
 }
+/* EngSinkEntries.warp_kept (h264bsdmiWarpKeptPictures) */
+int sink_warp_kept(uint32_t n, const SinkTensorPic *pics, const h264bsdmi_warp_map *maps, const h264bsdmi_warp_spec *spec, uint32_t n_count,
+                   void *stream)
+{
+    if (n && (!spec || !maps)) return -1;
+    return sink_tensor_call(n, pics, stream, [&](Engine *e, hipStream_t st, hipEvent_t *fence_ev) {
+        return warp_out_locked(e, n, pics, maps, *spec, n_count, st, fence_ev);
+    });
+}
 /* EngSinkEntries.point_model (h264bsdmiOutputPointModel): the first entry without pictures — the sink only names the engine, nothing is
  * staged (the kernel finds record r of the four arrays by its stride), no fence goes to an instance and no kept picture is touched, so
  * none of pull_begin_locked / pull_end_locked / the kept pictures' ordering applies.  One launch of a workgroup per record; without a
@@ -2171,7 +2240,7 @@ int eng_attach(JobSink *sink)
 /* engine.h: the entries behind the last member of JobSink, for a sink eng_attach has bound */
 const EngSinkEntries *eng_sink_entries(const JobSink *sink)
 {
-    static const EngSinkEntries entries = { sink_cell_shift, sink_point_matches, sink_point_model };
+    static const EngSinkEntries entries = { sink_cell_shift, sink_point_matches, sink_point_model, sink_warp_kept };
     return sink && sink->configure == sink_configure ? &entries : nullptr;
 }
 

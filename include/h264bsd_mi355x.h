@@ -376,6 +376,50 @@ int h264bsdmiBlendCurrentPictures(u32 n, storage_t *const *pStorage, const h264b
 int h264bsdmiOutputKeptPictures(u32 n, storage_t *const *pStorage, void *const *picture, void *const *fraction, void *stream,
                                 u32 *got, u32 *keptPicId);
 
+/* Warped kept pictures: the kept picture of each of n distinct instances RESAMPLED IN PLACE through an affine map, the picture (hi)
+ * and, where the instance has one, the fraction (lo) — a background that follows a camera which shakes or pans.  Afterwards the kept
+ * picture lies in the coordinates the map leads to, and every consumer (h264bsdmiOutputRegionChange, h264bsdmiOutputRegionShift,
+ * h264bsdmiOutputCellMaps / CellBoxes in CHANGE mode, h264bsdmiOutputCellShift, h264bsdmiOutputPointMatches, the blend) reads it
+ * unchanged.  maps[i]: six coefficients a b c d e f in 16.16 fixed point, the map from OUTPUT to SOURCE in luma samples of the window
+ * (spec->crop as h264bsdmi_tensor_spec.crop: 1 the frame-cropping window, 0 the coded frame).  For the output luma sample (x, y) of a
+ * window w x h, in 64-bit integers,
+ *     X = a x + b y + c      Y = d x + e y + f                          (units of 2^-16 sample)
+ *     outside = X < 0 || X > (w-1) << 16 || Y < 0 || Y > (h-1) << 16;   X, Y clamped to those ranges
+ *     x0 = X >> 16, x1 = min(x0 + 1, w - 1), fx = (X >> 8) & 255;       y0, y1, fy likewise
+ *     V = (S00 (256 - fx) + S01 fx)(256 - fy) + (S10 (256 - fx) + S11 fx) fy;     S' = (V + 32768) >> 16
+ * with S = 256 hi + lo the state of h264bsdmiBlendCurrentPictures (lo reads as 128 where a plain keep came last).  S' is a rounded
+ * convex combination of its four neighbours and stays in the blend's [128, 65408].  A chroma sample (cx, cy) sits at luma
+ * (2 cx + 1/2, 2 cy + 1/2): in units of 2^-18 chroma sample U = 2 (a 2cx + b 2cy + c) + a + b - 65536, V' the same with d e f, both
+ * clamped to the chroma window (w/2, h/2); index U >> 18, weight (U >> 10) & 255, the same blend; whether a chroma sample is outside is
+ * decided on its own U, V' before the clamp.  The identity (a = e = 65536, the rest 0) changes no byte; a translation by an even number
+ * of whole samples is an index shift on all three planes; a = e = -65536, c = (w-1) << 16, f = (h-1) << 16 is the exact half turn.
+ * spec->outside: H264BSDMI_WARP_REPLICATE — the clamp decides; H264BSDMI_WARP_CURRENT — an output sample whose source was outside takes
+ * T = 256 c + 128 of the CURRENT picture's sample at the output position, what a starting blend writes; an instance without a current
+ * picture is then left alone.  Samples of the coded frame outside the window keep their state.  hi is always written, lo only where
+ * the instance's lo is valid (after a plain keep none is allocated and it keeps reading as 0x80).  The kept picId does not change.
+ * warped[i] = 1 when instance i's kept picture was resampled, 0 when it was left alone (no kept picture of its coded size, or none
+ * current under CURRENT); keptPicId (may be NULL): the picId of the kept picture, or 0.
+ * spec->count: NULL, or a DEVICE pointer to u32[n]: word i receives the number of luma samples of instance i's window whose source was
+ * outside (0 where it was left alone); the words are zeroed on the stream ahead of the launch when any instance is warped.
+ * Repeated bilinear resampling softens the picture: the 16-bit state delays the loss and does not remove it; whole-sample translations
+ * are exact.  One launch for the call.  The stream rule and the ordering of launches that touch kept pictures are those of
+ * h264bsdmiKeepCurrentPictures; under CURRENT the fence of a pull of current pictures applies.
+ * -1, before anything is enqueued: what h264bsdmiKeepCurrentPictures refuses (warped NULL in place of kept); spec or spec->maps NULL;
+ * outside > 1; crop > 1; |a|, |b|, |d| or |e| above 16 * 65536 (c, f: any int32).  -2: the engine failed, nothing is written by the
+ * host.  n == 0 returns 0. */
+#define H264BSDMI_WARP_REPLICATE 0u
+#define H264BSDMI_WARP_CURRENT   1u
+#define H264BSDMI_WARP_MAX_COEFFICIENT (16 * 65536)
+typedef struct h264bsdmi_warp_map { int a, b, c, d, e, f; } h264bsdmi_warp_map;      /* 32-bit, 16.16 fixed point */
+typedef struct h264bsdmi_warp_spec {
+    const h264bsdmi_warp_map *maps;  /* HOST, n */
+    u32   outside;       /* H264BSDMI_WARP_* */
+    u32   crop;          /* 0, 1 */
+    void *count;         /* NULL, or DEVICE pointer to u32[n] */
+} h264bsdmi_warp_spec;
+int h264bsdmiWarpKeptPictures(u32 n, storage_t *const *pStorage, const h264bsdmi_warp_spec *spec, void *stream,
+                              u32 *warped, u32 *keptPicId);
+
 /* Change statistics: integer statistics of (current picture - kept picture) over boxes, computed where the two pictures lie, with one
  * launch — did anything change since the last picture or since the background I stored, is the feed frozen, is this a cut or only a
  * brightness shift, what is the PSNR against the picture I kept — without pulling a pixel.  A sibling of h264bsdmiOutputRegionStats:
