@@ -10,7 +10,9 @@ The second half of the file gives pictures structure on purpose (patch_typed, pa
 patch_window_edges, build_job(smooth=...)): what white-noise motion and content never produce.  The end of it loses macroblocks
 (patch_lost, chosen_samples, build_job(pcm=...)): concealed macroblocks under chosen neighbour masks over chosen border samples;
 and it describes intra macroblocks one by one (build_job(chosen=...), put_chosen, border_samples, intra_to_range): chosen kind,
-availability, modes, QPs and coefficient blocks next to chosen border samples."""
+availability, modes, QPs and coefficient blocks next to chosen border samples.  The last part does the same for inter reconstruction:
+reference pictures of chosen samples (picture_samples, pcm_of: all-I_PCM jobs through build_job(pcm=...)) and inter macroblocks with exact
+vectors, references, QPs and level blocks (build_job(inter=...), put_inter)."""
 import ctypes
 import struct
 
@@ -133,7 +135,7 @@ def _pcm_gradient(rng, ramps, mbx, mby):
 
 
 def build_job(lib, rng, wmb, hmb, cur_slot, n_slots, ref_slots, *, p_inter=0.6, p_pcm=0.03, mv_range=None, any_deblock=True, patch=None, near_bound=False,
-              smooth=False, extra_blocks=0, pcm=None, chosen=None):
+              smooth=False, extra_blocks=0, pcm=None, chosen=None, inter=None):
     """One random picture.  ref_slots: slots holding valid pictures (empty -> intra only).
     patch(recs, mvs): called on the records [n][32] and the dense vectors [n][16][2] before the job is finished — a finished
     job carries its vectors in the records and the sparse section (framejob.h), the dense array here is only h264bsdmiJobFinalize's input.
@@ -143,7 +145,8 @@ def build_job(lib, rng, wmb, hmb, cur_slot, n_slots, ref_slots, *, p_inter=0.6, 
     patch(recs, mvs, first) with the index of the first of them, for macroblocks it wants to give a coded block (coef_idx, bytes 12..15).
     pcm: {macroblock address: 384 samples (Y[256], Cb[64], Cr[64], raster)} — these macroblocks are I_PCM with exactly those samples.
     chosen: {macroblock address: description of an Intra4x4 / Intra16x16 macroblock (put_chosen)} — these macroblocks are exactly that.
-    Neither pcm nor chosen changes what a seed draws for the other macroblocks' records."""
+    inter: {macroblock address: description of an inter macroblock (put_inter)} — these macroblocks are exactly that.
+    None of pcm, chosen and inter changes what a seed draws for the other macroblocks' records."""
     coef_block = _coef_block_smooth if smooth else _coef_block
     ramps = smooth if isinstance(smooth, list) else draw_ramps(rng) if smooth else None
     n = wmb * hmb
@@ -179,6 +182,8 @@ def build_job(lib, rng, wmb, hmb, cur_slot, n_slots, ref_slots, *, p_inter=0.6, 
             nblk += 12
         elif chosen is not None and a in chosen:
             coded, nblk = put_chosen(r, chosen[a], coefs, nblk, x, y, wmb)
+        elif inter is not None and a in inter:
+            coded, nblk = put_inter(r, mvs[a], inter[a], coefs, nblk)
         elif ref_slots and u < p_inter:
             r[0] = 0                                                   # inter
             style = rng.random()
@@ -747,3 +752,75 @@ def intra_to_range(levels, qp, towards, dc=None):
         reach = -min(map(min, r)) if towards < 0 else max(map(max, r))
         if best is None or reach >= best[0]: best = (reach, lv)
     return best[1] if best else base
+
+
+# ------------------------------------------------------------------ chosen reference pictures and chosen inter macroblocks
+# Random jobs predict from noise and draw small levels.  picture_samples gives a reference picture the samples that the interpolation
+# arithmetic is sensitive to (an all-I_PCM job carries them verbatim); put_inter writes ONE described inter macroblock.
+PICTURES = ["flat0", "flat255", "cols+", "cols-", "rows+", "rows-", "lattice+", "lattice-", "checker", "ramp", "dark", "bright"]
+
+
+def picture_samples(content, wmb, hmb, rng=None):
+    """(Y[H][W], Cb, Cr) uint8, every plane of the named content.  With the signs (+, -, +) of period 3 along an axis: cols+ / rows+ are 255
+    where the column's / row's sign is +, lattice+ where the signs of column and row agree; the - forms are the complements.  A row of cols+
+    gives the six-tap sum 10710 at one phase in three and cols- gives -2550 there; six such rows with the signs (+, -, +, +, -, +) give the
+    second-stage sums 475320 and -214200.  checker: one-sample squares of 0 and 255; ramp: 6 x + 5 y - 60 cut off at 0 and 255, so a flat
+    run at either end with a slope between; dark / bright: noise in 0 .. 5 / 250 .. 255 (drawn from rng)."""
+    out = []
+    for w, h in ((16 * wmb, 16 * hmb), (8 * wmb, 8 * hmb), (8 * wmb, 8 * hmb)):
+        yy, xx = np.mgrid[0:h, 0:w]
+        sx, sy = xx % 3 != 1, yy % 3 != 1
+        if content in ("flat0", "flat255"): v = np.full((h, w), 0 if content == "flat0" else 255)
+        elif content[:-1] == "cols": v = 255 * (sx == (content[-1] == "+"))
+        elif content[:-1] == "rows": v = 255 * (sy == (content[-1] == "+"))
+        elif content[:-1] == "lattice": v = 255 * ((sx == sy) == (content[-1] == "+"))
+        elif content == "checker": v = 255 * ((xx + yy) & 1)
+        elif content == "ramp": v = 6 * xx + 5 * yy - 60
+        elif content == "dark": v = rng.integers(0, 6, (h, w))
+        elif content == "bright": v = 255 - rng.integers(0, 6, (h, w))
+        else: raise ValueError(content)
+        out.append(np.clip(v, 0, 255).astype(np.uint8))
+    return tuple(out)
+
+
+def pcm_of(picture):
+    """build_job's pcm= for a whole picture (Y, Cb, Cr): {macroblock address: its 384 samples}"""
+    Y, Cb, Cr = picture
+    hmb, wmb = Y.shape[0] // 16, Y.shape[1] // 16
+    out = {}
+    for a in range(wmb * hmb):
+        x, y = a % wmb, a // wmb
+        out[a] = np.concatenate([P[s * y:s * y + s, s * x:s * x + s].ravel() for P, s in ((Y, 16), (Cb, 8), (Cr, 8))])
+    return out
+
+
+def put_inter(r, mv, d, coefs, nblk):
+    """Write the record r (coef_idx is set already), the dense vectors mv[16][2] and the coefficient blocks of the inter macroblock that the
+    dict d describes; returns (coded, nblk).  Keys: mv — one vector, four (one per quadrant, raster) or sixteen (raster 4x4 blocks), quarter
+    samples; slots — one reference slot or four; qp_y, qp_c (both given outright: any pair); luma {z: 16 levels, raster}; chroma_dc (8
+    levels: Cb, Cr); chroma_ac {k: 16 levels}.  The FJ_PARTS_* bits follow the vectors and slots.  Nothing is checked here."""
+    vec = [tuple(int(c) for c in v) for v in d["mv"]]
+    slots = list(d.get("slots", [0]))
+    slots = slots * 4 if len(slots) == 1 else slots
+    if len(vec) == 1: vec = vec * 16
+    elif len(vec) == 4: vec = [vec[(k >> 3) * 2 + ((k & 3) >> 1)] for k in range(16)]
+    mv[:] = vec
+    quad = [(vec[(q >> 1) * 8 + (q & 1) * 2], slots[q]) for q in range(4)]
+    parts = 1 if len(set(quad)) == 1 else 2 if quad[0] == quad[1] and quad[2] == quad[3] else 3 if quad[0] == quad[2] and quad[1] == quad[3] else 0
+    if any(vec[k] != vec[(k >> 3) * 8 + ((k & 3) >> 1) * 2] for k in range(16)): parts = 0      # finer than quadrants: P_8x8
+    r[0], r[1], r[2] = 0, int(d.get("qp_y", 26)), int(d.get("qp_c", 26))
+    r[4] = parts << 4
+    r[16:20] = slots
+    coded = 0
+
+    def put(levels, bit):
+        nonlocal nblk, coded
+        blk = np.zeros(16, dtype=np.int16)
+        blk[:len(levels)] = levels
+        coefs[16 * nblk:16 * nblk + 16] = blk
+        nblk += 1
+        coded |= bit
+    for z in sorted(d.get("luma", {})): put(d["luma"][z], 1 << z)
+    if d.get("chroma_dc") is not None: put(d["chroma_dc"], 1 << 25)
+    for k in sorted(d.get("chroma_ac", {})): put(d["chroma_ac"][k], 1 << (16 + k))
+    return coded, nblk

@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 from oracle import pyoracle
-from jobgen import FRACTIONS, _edge_component, window_targets
+from jobgen import FRACTIONS, PICTURES, _edge_component, picture_samples, window_targets
 
 pytestmark = pytest.mark.skipif(not os.path.exists(pyoracle.REF_SO), reason="oracle/_ref not built (needs /root/reference)")
 
@@ -90,8 +90,6 @@ def test_inter_prediction_matches_h264bsdPredictSamples(ref):
     img = ImageT(frame.ctypes.data, wmb, hmb, None, None, None)
     ref.h264bsdPredictSamples.argtypes = [ctypes.c_void_p, ctypes.POINTER(MvT), ctypes.POINTER(ImageT)] + [ctypes.c_uint32] * 6
     ref.h264bsdPredictSamples.restype = None
-    cb = frame[W * H:].ctypes.data
-    cr = frame[W * H + W * H // 4:].ctypes.data
     sizes = [(16, 16), (16, 8), (8, 16), (8, 8), (8, 4), (4, 8), (4, 4)]
     # after the random vectors, for every partition size: the reference window (luma: block - 2 .. block + 3, chroma: block .. block + 1)
     # with its first column / row at -1, 0, +1 and its last at size - 2, size - 1, size, for luma and for chroma, every horizontal
@@ -116,23 +114,56 @@ def test_inter_prediction_matches_h264bsdPredictSamples(ref):
             for (plane, end, t), pos, blk, mvc in ((tx, 16 * mbx + px, pw, mvx), (ty, 16 * mby + py, ph, mvy)):
                 first, last = (pos + (mvc >> 2) - 2, pos + (mvc >> 2) + blk + 2) if plane == "luma" else (pos // 2 + (mvc >> 3), pos // 2 + (mvc >> 3) + blk // 2)
                 assert (first if end == "first" else last) == t, "the window is not where the case says"
-        mv = MvT(mvx, mvy)
-        data = np.zeros(384 + 64, dtype=np.uint8)
-        base = data.ctypes.data
-        off = (-base) % 16
-        ref.h264bsdPredictSamples(base + off, ctypes.byref(mv), ctypes.byref(img), mbx * 16, mby * 16, px, py, pw, ph)
-        got = data[off:off + 384]
-        for y in range(ph):
-            for x in range(pw):
-                xa, ya = mbx * 16 + px + x, mby * 16 + py + y
-                want = orc.oracle_luma_sample(frame.ctypes.data, W, H, xa + (mvx >> 2), ya + (mvy >> 2), mvx & 3, mvy & 3)
-                assert got[16 * (py + y) + px + x] == want, (it, pw, ph, mvx, mvy, x, y)
-        for y in range(ph // 2):
-            for x in range(pw // 2):
-                xc, yc = mbx * 8 + px // 2 + x, mby * 8 + py // 2 + y
-                a = (xc + (mvx >> 3), yc + (mvy >> 3), mvx & 7, mvy & 7)
-                assert got[256 + 8 * (py // 2 + y) + px // 2 + x] == orc.oracle_chroma_sample(cb, W // 2, H // 2, *a)
-                assert got[320 + 8 * (py // 2 + y) + px // 2 + x] == orc.oracle_chroma_sample(cr, W // 2, H // 2, *a)
+        _predict_and_compare(ref, orc, frame, img, W, H, mbx, mby, px, py, pw, ph, mvx, mvy, it)
+
+
+def _predict_and_compare(ref, orc, frame, img, W, H, mbx, mby, px, py, pw, ph, mvx, mvy, tag):
+    """h264bsdPredictSamples of one partition against oracle_luma_sample / oracle_chroma_sample, sample by sample"""
+    cb = frame[W * H:].ctypes.data
+    cr = frame[W * H + W * H // 4:].ctypes.data
+    mv = MvT(mvx, mvy)
+    data = np.zeros(384 + 64, dtype=np.uint8)
+    base = data.ctypes.data
+    off = (-base) % 16
+    ref.h264bsdPredictSamples(base + off, ctypes.byref(mv), ctypes.byref(img), mbx * 16, mby * 16, px, py, pw, ph)
+    got = data[off:off + 384]
+    for y in range(ph):
+        for x in range(pw):
+            xa, ya = mbx * 16 + px + x, mby * 16 + py + y
+            want = orc.oracle_luma_sample(frame.ctypes.data, W, H, xa + (mvx >> 2), ya + (mvy >> 2), mvx & 3, mvy & 3)
+            assert got[16 * (py + y) + px + x] == want, (tag, pw, ph, mvx, mvy, x, y)
+    for y in range(ph // 2):
+        for x in range(pw // 2):
+            xc, yc = mbx * 8 + px // 2 + x, mby * 8 + py // 2 + y
+            a = (xc + (mvx >> 3), yc + (mvy >> 3), mvx & 7, mvy & 7)
+            assert got[256 + 8 * (py // 2 + y) + px // 2 + x] == orc.oracle_chroma_sample(cb, W // 2, H // 2, *a), (tag, "cb", pw, ph, mvx, mvy, x, y)
+            assert got[320 + 8 * (py // 2 + y) + px // 2 + x] == orc.oracle_chroma_sample(cr, W // 2, H // 2, *a), (tag, "cr", pw, ph, mvx, mvy, x, y)
+
+
+@pytest.mark.parametrize("content", PICTURES)
+def test_inter_prediction_matches_h264bsdPredictSamples_on_chosen_pictures(ref, content):
+    """the same pin over the pictures of chosen samples that the inter set predicts from (jobgen.picture_samples: flat, the period-3 columns,
+    rows and lattice, the checkerboard, the saturating ramp, the dark / bright noise): every partition size with every luma fraction and
+    both values of the chroma fraction's third bit, the window inside the picture and across its borders and corners"""
+    orc = pyoracle.oracle_lib()
+    wmb, hmb = 4, 3
+    W, H = wmb * 16, hmb * 16
+    frame = np.concatenate([p.ravel() for p in picture_samples(content, wmb, hmb, np.random.default_rng(7))])
+    img = ImageT(frame.ctypes.data, wmb, hmb, None, None, None)
+    ref.h264bsdPredictSamples.argtypes = [ctypes.c_void_p, ctypes.POINTER(MvT), ctypes.POINTER(ImageT)] + [ctypes.c_uint32] * 6
+    ref.h264bsdPredictSamples.restype = None
+    at = [(1, 1), (0, 0), (wmb - 1, 0), (0, hmb - 1), (wmb - 1, hmb - 1), (2, 0), (1, hmb - 1), (0, 1), (wmb - 1, 1)]
+    whole = [(0, 0), (-5, 2), (3, -4), (-21, -19), (41, 30), (7, -9), (-2, 33)]
+    k = 0
+    for pw, ph in [(16, 16), (16, 8), (8, 16), (8, 8), (8, 4), (4, 8), (4, 4)]:
+        for fy in range(4):
+            for fx in range(4):
+                for _ in range(3):
+                    mbx, mby = at[k % len(at)]
+                    wx, wy = whole[k % len(whole)]
+                    px, py = (k % (16 // pw)) * pw, ((k // 3) % (16 // ph)) * ph
+                    _predict_and_compare(ref, orc, frame, img, W, H, mbx, mby, px, py, pw, ph, 4 * wx + fx, 4 * wy + fy, (content, k))
+                    k += 1
 
 
 def test_colour_conversion_matches_reference_on_random_frames():

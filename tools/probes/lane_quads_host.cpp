@@ -1,46 +1,13 @@
 // tools/probes/lane_quads_host.cpp — the lane geometry of k_recon_inter_lq against plain H.264 arithmetic, on the CPU.
 //   clang++ -O1 -g -std=c++20 -fsanitize=address,undefined tools/probes/lane_quads_host.cpp -o /tmp/lane_quads_host && /tmp/lane_quads_host
-// It includes kernels/inter_lane_block.hip.h as it is (shims for the few device builtins it uses) and checks, for random pictures,
+// It includes kernels/inter_lane_block.hip.h as it is (tests/lane_arith/lane_shims.h: the few device builtins it uses) and checks, for random pictures,
 // macroblocks, quadrants and vectors (windows inside, across and outside the picture):
 //   1. the quadrant window cut: the 13 x 32 window staged by the kernels' own rules (LqWin: which lane takes which piece, whether its tile is
 //      needed, the clamped tile row lw_luma_piece / lw_chroma_piece, the spread lw_side, the place in the slot), lq_window_byte and the five
 //      class filters give every lane the 4x4 block that 8.4.2.2.1 gives at that place;
 //   2. the 2-lane chroma split: lq_chroma_byte and two lb_chroma_row per lane give the plane's 4x4 block of 8.4.2.2.2;
 //   3. the store exchange: lq_pair_rows, lq_luma_store_offset, lq_chroma_store_offset fill the quadrant's part of the tile exactly once.
-#include <algorithm>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
-using std::max; using std::min;
-#define __device__
-#define __forceinline__ inline
-typedef short s2 __attribute__((ext_vector_type(2)));
-static inline s2 pk(int x) { return (s2){ (short)x, (short)x }; }
-static inline s2 pk_clip(s2 lo, s2 hi, s2 v) { return __builtin_elementwise_min(__builtin_elementwise_max(v, lo), hi); }
-static inline s2 as_s2(uint32_t x) { s2 r; memcpy(&r, &x, 4); return r; }
-static inline uint32_t as_u32(s2 x) { uint32_t r; memcpy(&r, &x, 4); return r; }
-static inline uint32_t perm(uint32_t hi, uint32_t lo, uint32_t sel)
-{
-    const uint64_t v = ((uint64_t)hi << 32) | lo;
-    uint32_t r = 0;
-    for (int i = 0; i < 4; i++) {
-        const uint32_t s = (sel >> (8 * i)) & 255u;
-        const uint32_t b = s < 8 ? (uint32_t)((v >> (8 * s)) & 255u) : s == 12 ? 0u : (abort(), 0u);
-        r |= b << (8 * i);
-    }
-    return r;
-}
-static inline int clip255(int v) { return min(max(v, 0), 255); }
-static inline int clip3(int lo, int hi, int v) { return min(max(v, lo), hi); }
-static inline int level_scale(int m, int cls)
-{
-    const uint32_t c = cls == 0 ? 0x2507356Au : cls == 1 ? 0x2F4941CDu : 0x3B9BD250u;
-    return (int)((c >> (5 * m)) & 31u);
-}
-constexpr int TILE = 384, T_CB = 256;
-#define FJ_CODED_CHROMA_DC (1u << 25)
+#include "../../tests/lane_arith/lane_shims.h"
 #include "../../h264bsd_amd/csrc/kernels/inter_lane_block.hip.h"
 using namespace h264k;
 
