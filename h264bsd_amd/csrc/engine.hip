@@ -28,6 +28,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <deque>
+#include <initializer_list>
 #include <memory>
 #include <mutex>
 #include <vector>
@@ -39,6 +40,7 @@
 #include "kernels/k_tensor_remap.hip.h"
 #include "kernels/k_motion.hip.h"
 #include "kernels/region_common.hip.h"
+#include "kernels/luma_search.hip.h"
 #include "kernels/k_region_stats.hip.h"
 #include "kernels/k_keep.hip.h"
 #include "kernels/k_blend.hip.h"
@@ -1285,13 +1287,17 @@ static dim3 pull_grid(uint32_t width, uint32_t height, uint32_t cols, uint32_t r
     const uint32_t tiles = (width + cols - 1u) / cols * ((height + rows - 1u) / rows);
     return dim3(std::min((tiles + per_block - 1u) / per_block, 1024u), n_items);
 }
-/* behind the filled items: st waits for the pictures' ticks, ONE launch of 256-lane workgroups, the fence */
-static int pull_launch_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, hipStream_t st, const void *fn, dim3 grid, void *kargs,
+/* behind the filled items: st waits for the pictures' ticks, the launches of 256-lane workgroups one behind the other (ONE for most
+ * pulls; where there are two the second reads what the first wrote), the fence and the error words behind the last */
+struct PullLaunch { const void *fn; dim3 grid; void *kargs; };
+static int pull_launch_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, hipStream_t st, std::initializer_list<PullLaunch> launches,
                               hipEvent_t *fence_ev)
 {
     if (pull_wait_pictures(e, n, pics, st)) return -1;
-    void *args[] = { kargs };
-    HIP_TRY(hipLaunchKernel(fn, grid, dim3(256), args, 0, st));
+    for (const PullLaunch &l : launches) {
+        void *args[] = { l.kargs };
+        HIP_TRY(hipLaunchKernel(l.fn, l.grid, dim3(256), args, 0, st));
+    }
     return pull_end_locked(e, n, pics, st, fence_ev);
 }
 
@@ -1319,7 +1325,7 @@ static int aa_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, const
     }
     h264k::AaArgs aargs{ e->titems.dev<h264k::AaItem>(), t.width, t.height, chroma, rs.filter, {}, {}, {} };
     copy3(aargs.mean, t.mean); copy3(aargs.std, t.std); copy3(aargs.pad, fold_pad(rs.pad, t.dtype, t.mean, t.std, ref).pad);
-    return pull_launch_locked(e, n, pics, st, fn, pull_grid(t.width, t.height, h264k::TAA_COLS, h264k::TAA_ROWS, n), &aargs, fence_ev);
+    return pull_launch_locked(e, n, pics, st, { { fn, pull_grid(t.width, t.height, h264k::TAA_COLS, h264k::TAA_ROWS, n), &aargs } }, fence_ev);
 }
 
 /* h264bsdmiNextOutputTensorBatch[Colour|Resize]: one TensorItem per picture, k_tensor_out without resize, k_tensor_resize for
@@ -1340,7 +1346,7 @@ static int tensor_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, c
     copy3(targs.mean, t.mean); copy3(targs.std, t.std);
     /* k_tensor_out: a wavefront per unit of 64 x 16, four to a workgroup */
     const dim3 grid = t.resize ? pull_grid(t.width, t.height, h264k::TCR_COLS, h264k::TCR_ROWS, n) : pull_grid(t.width, t.height, 64, 16, n, 4);
-    return pull_launch_locked(e, n, pics, st, fn, grid, &targs, fence_ev);
+    return pull_launch_locked(e, n, pics, st, { { fn, grid, &targs } }, fence_ev);
 }
 
 /* h264bsdmiOutputTensorRegions: the items are the n_regs regions, each a box of one of the n pictures, which were popped earlier and
@@ -1367,7 +1373,7 @@ static int regions_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, 
     h264k::RoiArgs rargs{ e->titems.dev<h264k::RoiItem>(), t.width, t.height, chroma, rs.filter, {}, {}, {}, {} };
     const PullPad pp = fold_pad(rs.pad, t.dtype, t.mean, t.std, ref);
     copy3(rargs.mean, t.mean); copy3(rargs.std, t.std); copy3(rargs.pad, pp.pad); copy3(rargs.spad, pp.spad);
-    return pull_launch_locked(e, n, pics, st, fn, pull_grid(t.width, t.height, h264k::TAA_COLS, h264k::TAA_ROWS, n_regs), &rargs, fence_ev);
+    return pull_launch_locked(e, n, pics, st, { { fn, pull_grid(t.width, t.height, h264k::TAA_COLS, h264k::TAA_ROWS, n_regs), &rargs } }, fence_ev);
 }
 
 /* h264bsdmiOutputMotionRegions: the regions of regions_out_locked, read from the side information beside each picture's frame
@@ -1398,8 +1404,8 @@ static int motion_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, u
                                       s->wmb, s->hmb, p.x0, p.y0, p.w, p.h, g.x, g.y, g.w, g.h, g.box[0], g.box[1], g.box[2], g.box[3] };
     }
     h264k::MotionArgs margs{ e->titems.dev<h264k::MotionItem>(), m.width, m.height, m.planes, m.sampler, m.units, m.per_picture };
-    return pull_launch_locked(e, n, pics, st, fns[m.dtype == h264k::TO_F32][m.layout],
-                              pull_grid(m.width, m.height, h264k::TAA_COLS, h264k::TAA_ROWS, n_regs), &margs, fence_ev);
+    return pull_launch_locked(e, n, pics, st, { { fns[m.dtype == h264k::TO_F32][m.layout],
+                                                  pull_grid(m.width, m.height, h264k::TAA_COLS, h264k::TAA_ROWS, n_regs), &margs } }, fence_ev);
 }
 
 /* The scratch in which the row bands of k_region_stats, k_region_change, k_region_shift and k_corner_points meet (Engine.d_stats), allocated at its first
@@ -1451,6 +1457,52 @@ static bool kept_pictures_ok(uint32_t n, const SinkTensorPic *pics)
     }
     return true;
 }
+/* What the item of region g reads: the frame of its picture, the kept picture of its instance (null without one), box ∩ window, the
+ * window itself and the box's origin, which may be negative or beyond the frame, all in luma samples of the coded frame.  *tallest,
+ * where the launch is banded, takes the clip's macroblock rows */
+struct RegionSource { const uint8_t *frame; const uint8_t *kept; uint32_t wmb; RegionClip c; uint32_t wx0, wy0, wx1, wy1; int32_t ox, oy; };
+static RegionSource region_source(const SinkTensorPic *pics, const SinkRegion &g, uint32_t *tallest = nullptr)
+{
+    const SinkTensorPic &p = pics[g.pic];
+    const StreamCtx *s = pic_stream(p);
+    const RegionClip c = region_clip(p, g);
+    if (tallest) *tallest = std::max(*tallest, c.mb_rows);
+    return RegionSource{ s->d_frames + (size_t)p.slot * s->frame_bytes, s->d_kept.get(), s->wmb, c, p.x0, p.y0, p.x0 + p.w, p.y0 + p.h,
+                         (int32_t)p.x0 + g.x, (int32_t)p.y0 + g.y };
+}
+/* the refusals every analysis pull makes behind those of its own spec: regions that fit grid.y, pictures, regions, and with vs_kept
+ * the kept pictures */
+static bool analysis_regions_ok(uint32_t n, const SinkTensorPic *pics, uint32_t n_regs, const SinkRegion *regs, bool vs_kept)
+{
+    if (n_regs > 65535u) return false;                                  /* grid.y */
+    if (!pull_pictures_ok(n, pics, true, false) || !pull_regions_ok(n, n_regs, regs, 1u, 1u)) return false;
+    return !vs_kept || kept_pictures_ok(n, pics);
+}
+/* A grid of cols x rows square cells of side `cell` over rectangles of rect_w x rect_h luma samples, one workgroup each: the cell side
+ * as a shift (min_shift .. max_shift), the rectangles per row of rectangles and per region; refused: a side that is none of these, a
+ * grid beyond max_grid either way, more than max_workgroups in the launch.  Both callers ask behind analysis_regions_ok, where the
+ * side and the grid used to be refused ahead of it: every refusal returns -1 with nothing done, so the order does not show */
+struct CellLimits { uint32_t min_shift, max_shift, rect_w, rect_h, max_grid, max_workgroups; };
+static const CellLimits CELLS_LIMITS{ 2u, 6u, h264k::CELLS_RECT_W, h264k::CELLS_RECT_H, h264k::CELLS_MAX_GRID, h264k::CELLS_MAX_WORKGROUPS };
+static const CellLimits FLOW_LIMITS{ h264k::FLOW_MIN_SHIFT, h264k::FLOW_MAX_SHIFT, h264k::FLOW_RECT_W, h264k::FLOW_RECT_H, h264k::FLOW_MAX_GRID,
+                                     h264k::FLOW_MAX_WORKGROUPS };
+struct CellGrid { uint32_t shift, rects_x, rects; };
+static bool cell_grid(uint32_t cell, uint32_t cols, uint32_t rows, uint32_t n_regs, const CellLimits &lim, CellGrid *g)
+{
+    uint32_t shift = lim.min_shift;
+    while (shift < lim.max_shift && (1u << shift) != cell) shift++;
+    if ((1u << shift) != cell || !cols || cols > lim.max_grid || !rows || rows > lim.max_grid) return false;
+    const uint32_t rw = lim.rect_w >> shift, rh = lim.rect_h >> shift;
+    const uint32_t rects_x = (cols + rw - 1u) / rw, rects = rects_x * ((rows + rh - 1u) / rh);
+    *g = CellGrid{ shift, rects_x, rects };
+    return (uint64_t)rects * n_regs <= lim.max_workgroups;
+}
+/* k_region_shift or k_cell_shift of a radius: from radius SHIFT_QUADS_FROM on a thread takes SHIFT_QUADS quads of displacements per
+ * template dword, below that one: as measured, each is the faster on its side (docs/EXPERIMENTS.md, "Region shift") */
+template <typename Args> static const void *shift_kernel_of(uint32_t radius, void (*quads)(Args), void (*one)(Args))
+{
+    return reinterpret_cast<const void *>(radius >= h264k::SHIFT_QUADS_FROM ? quads : one);
+}
 /* the refusals of `source` and `bins` (0, or a power of two 16 .. 256); *shift = 8 - log2 bins, 0 without a histogram */
 static bool source_bins_ok(uint32_t source, uint32_t bins, uint32_t *shift)
 {
@@ -1497,7 +1549,7 @@ static int banded_launch_locked(Engine *e, uint32_t n, const SinkTensorPic *pics
     const uint32_t S = band_count(n_regs, tallest);
     if (S > 1u && stats_scratch_locked(e, st, &kargs->tickets, &kargs->partials)) return -1;
     if (kept && kept_order_begin(e, st)) return -1;
-    if (pull_launch_locked(e, n, pics, st, fn, dim3(S, n_regs), kargs, fence_ev)) return -1;
+    if (pull_launch_locked(e, n, pics, st, { { fn, dim3(S, n_regs), kargs } }, fence_ev)) return -1;
     if (S > 1u) HIP_TRY(hipEventRecord(e->stats_ev, st));
     return kept ? kept_order_end(e, st) : 0;
 }
@@ -1509,20 +1561,14 @@ static int stats_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, ui
 {
     uint32_t shift;
     if (!sp.data || (reinterpret_cast<uintptr_t>(sp.data) & 7u) || sp.crop > 1u || !source_bins_ok(sp.source, sp.bins, &shift)) return -1;
-    if (n_regs > 65535u) return -1;                                     /* grid.y */
-    if (!pull_pictures_ok(n, pics, true, false) || !pull_regions_ok(n, n_regs, regs, 1u, 1u)) return -1;
+    if (!analysis_regions_ok(n, pics, n_regs, regs, false)) return -1;
     if (pull_begin_locked(e, n, pics, n_regs)) return -1;
     h264k::StatsItem *items = e->titems.host<h264k::StatsItem>();
     const uint32_t stride = h264k::stats_record_bytes(sp.source == H264BSDMI_STATS_Y ? 1u : 3u, sp.bins);
     uint32_t tallest = 0u;
     for (uint32_t r = 0; r < n_regs; r++) {
-        const SinkRegion &g = regs[r];
-        const SinkTensorPic &p = pics[g.pic];
-        const StreamCtx *s = pic_stream(p);
-        const RegionClip c = region_clip(p, g);
-        items[r] = h264k::StatsItem{ s->d_frames + (size_t)p.slot * s->frame_bytes, static_cast<uint8_t *>(sp.data) + (size_t)g.index * stride,
-                                     s->wmb, c.x0, c.y0, c.x1, c.y1 };
-        tallest = std::max(tallest, c.mb_rows);
+        const RegionSource s = region_source(pics, regs[r], &tallest);
+        items[r] = h264k::StatsItem{ s.frame, static_cast<uint8_t *>(sp.data) + (size_t)regs[r].index * stride, s.wmb, s.c.x0, s.c.y0, s.c.x1, s.c.y1 };
     }
     h264k::StatsArgs sargs{ e->titems.dev<h264k::StatsItem>(), nullptr, nullptr, sp.bins, shift };
     return banded_launch_locked(e, n, pics, st, banded_kernel(false, sp.source, sp.bins != 0u), n_regs, tallest, &sargs, false, fence_ev);
@@ -1704,20 +1750,14 @@ static int change_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, u
     if (!sp.data || (reinterpret_cast<uintptr_t>(sp.data) & 7u) || sp.crop > 1u || sp.keep_after > 1u ||
         !source_bins_ok(sp.source, sp.bins, &shift)) return -1;
     if (sp.threshold[0] > 255u || sp.threshold[1] > 255u || sp.threshold[2] > 255u) return -1;
-    if (n_regs > 65535u) return -1;                                     /* grid.y */
-    if (!pull_pictures_ok(n, pics, true, false) || !pull_regions_ok(n, n_regs, regs, 1u, 1u) || !kept_pictures_ok(n, pics)) return -1;
+    if (!analysis_regions_ok(n, pics, n_regs, regs, true)) return -1;
     if (pull_begin_locked(e, n, pics, n_regs)) return -1;
     h264k::ChangeItem *items = e->titems.host<h264k::ChangeItem>();
     const uint32_t stride = h264k::change_record_bytes(sp.source == H264BSDMI_STATS_Y ? 1u : 3u, sp.bins);
     uint32_t tallest = 0u;
     for (uint32_t r = 0; r < n_regs; r++) {
-        const SinkRegion &g = regs[r];
-        const SinkTensorPic &p = pics[g.pic];
-        const StreamCtx *s = pic_stream(p);
-        const RegionClip c = region_clip(p, g);
-        items[r] = h264k::ChangeItem{ s->d_frames + (size_t)p.slot * s->frame_bytes, s->d_kept.get(),
-                                      static_cast<uint8_t *>(sp.data) + (size_t)g.index * stride, s->wmb, c.x0, c.y0, c.x1, c.y1 };
-        tallest = std::max(tallest, c.mb_rows);
+        const RegionSource s = region_source(pics, regs[r], &tallest);
+        items[r] = h264k::ChangeItem{ s.frame, s.kept, static_cast<uint8_t *>(sp.data) + (size_t)regs[r].index * stride, s.wmb, s.c.x0, s.c.y0, s.c.x1, s.c.y1 };
     }
     h264k::ChangeArgs cargs{ e->titems.dev<h264k::ChangeItem>(), nullptr, nullptr, sp.bins, shift, { sp.threshold[0], sp.threshold[1], sp.threshold[2] } };
     return banded_launch_locked(e, n, pics, st, banded_kernel(true, sp.source, sp.bins != 0u), n_regs, tallest, &cargs, true, fence_ev);
@@ -1731,29 +1771,19 @@ static int shift_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, ui
 {
     if (!sp.data || (reinterpret_cast<uintptr_t>(sp.data) & 7u) || sp.radius > H264BSDMI_SHIFT_MAX_RADIUS || sp.surface > 1u || sp.crop > 1u ||
         sp.keep_after > 1u) return -1;
-    if (n_regs > 65535u) return -1;                                     /* grid.y */
-    if (!pull_pictures_ok(n, pics, true, false) || !pull_regions_ok(n, n_regs, regs, 1u, 1u)) return -1;
     for (uint32_t r = 0; r < n_regs; r++)
         if (regs[r].w > H264BSDMI_SHIFT_MAX_SIDE || regs[r].h > H264BSDMI_SHIFT_MAX_SIDE) return -1;        /* the 32-bit sums */
-    if (!kept_pictures_ok(n, pics)) return -1;
+    if (!analysis_regions_ok(n, pics, n_regs, regs, true)) return -1;
     if (pull_begin_locked(e, n, pics, n_regs)) return -1;
     h264k::ShiftItem *items = e->titems.host<h264k::ShiftItem>();
     const uint32_t stride = h264k::shift_record_bytes(sp.radius, sp.surface);
     uint32_t tallest = 0u;
     for (uint32_t r = 0; r < n_regs; r++) {
-        const SinkRegion &g = regs[r];
-        const SinkTensorPic &p = pics[g.pic];
-        const StreamCtx *s = pic_stream(p);
-        const RegionClip c = region_clip(p, g);
-        items[r] = h264k::ShiftItem{ s->d_frames + (size_t)p.slot * s->frame_bytes, s->d_kept.get(),
-                                     static_cast<uint8_t *>(sp.data) + (size_t)g.index * stride, s->wmb, c.x0, c.y0, c.x1, c.y1,
-                                     p.x0, p.y0, p.x0 + p.w, p.y0 + p.h };
-        tallest = std::max(tallest, c.mb_rows);
+        const RegionSource s = region_source(pics, regs[r], &tallest);
+        items[r] = h264k::ShiftItem{ s.frame, s.kept, static_cast<uint8_t *>(sp.data) + (size_t)regs[r].index * stride, s.wmb, s.c.x0, s.c.y0, s.c.x1, s.c.y1,
+                                     s.wx0, s.wy0, s.wx1, s.wy1 };
     }
-    /* from radius 4 on a thread takes three quads of displacements per template dword, below that one: as measured, each is the faster
-     * on its side (docs/EXPERIMENTS.md, "Region shift") */
-    const void *fn = sp.radius >= h264k::SHIFT_QUADS_FROM ? reinterpret_cast<const void *>(&h264k::k_region_shift<h264k::SHIFT_QUADS>)
-                                                           : reinterpret_cast<const void *>(&h264k::k_region_shift<1u>);
+    const void *fn = shift_kernel_of(sp.radius, &h264k::k_region_shift<h264k::SHIFT_QUADS>, &h264k::k_region_shift<1u>);
     h264k::ShiftArgs sargs{ e->titems.dev<h264k::ShiftItem>(), nullptr, nullptr, sp.radius, sp.surface };
     return banded_launch_locked(e, n, pics, st, fn, n_regs, tallest, &sargs, true, fence_ev);
 }
@@ -1767,20 +1797,15 @@ static int corners_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, 
     if (!sp.data || (reinterpret_cast<uintptr_t>(sp.data) & 7u) || sp.score > H264BSDMI_CORNERS_HARRIS || (sp.block != 3u && sp.block != 5u) ||
         sp.nms < 1u || sp.nms > H264BSDMI_CORNERS_MAX_NMS || sp.max_points < 1u || sp.max_points > H264BSDMI_CORNERS_MAX_POINTS ||
         sp.crop > 1u || sp.zero || (sp.score == H264BSDMI_CORNERS_HARRIS && sp.min_score >> 63)) return -1;
-    if (n_regs > 65535u) return -1;                                     /* grid.y */
-    if (!pull_pictures_ok(n, pics, true, false) || !pull_regions_ok(n, n_regs, regs, 1u, 1u)) return -1;
+    if (!analysis_regions_ok(n, pics, n_regs, regs, false)) return -1;
     if (pull_begin_locked(e, n, pics, n_regs)) return -1;
     h264k::CornerItem *items = e->titems.host<h264k::CornerItem>();
     const uint32_t stride = h264k::corner_record_bytes(sp.max_points);
     uint32_t tallest = 0u;
     for (uint32_t r = 0; r < n_regs; r++) {
-        const SinkRegion &g = regs[r];
-        const SinkTensorPic &p = pics[g.pic];
-        const StreamCtx *s = pic_stream(p);
-        const RegionClip c = region_clip(p, g);
-        items[r] = h264k::CornerItem{ s->d_frames + (size_t)p.slot * s->frame_bytes, static_cast<uint8_t *>(sp.data) + (size_t)g.index * stride,
-                                      s->wmb, c.x0, c.y0, c.x1, c.y1, p.x0, p.y0, p.x0 + p.w, p.y0 + p.h };
-        tallest = std::max(tallest, c.mb_rows);
+        const RegionSource s = region_source(pics, regs[r], &tallest);
+        items[r] = h264k::CornerItem{ s.frame, static_cast<uint8_t *>(sp.data) + (size_t)regs[r].index * stride, s.wmb, s.c.x0, s.c.y0, s.c.x1, s.c.y1,
+                                      s.wx0, s.wy0, s.wx1, s.wy1 };
     }
     const void *const fns[2][2] = {
         { reinterpret_cast<const void *>(&h264k::k_corner_points<h264k::CORNER_MIN_EIGEN, 3>), reinterpret_cast<const void *>(&h264k::k_corner_points<h264k::CORNER_MIN_EIGEN, 5>) },
@@ -1805,40 +1830,30 @@ static int cells_prepare_locked(Engine *e, uint32_t n, const SinkTensorPic *pics
                                 const h264bsdmi_cells_spec &sp, uint32_t extra, CellsLaunch *L)
 {
     const bool change = sp.mode == H264BSDMI_CELLS_CHANGE;
-    uint32_t shift = 2u;
-    while (shift < 6u && (1u << shift) != sp.cell) shift++;
-    if (!sp.data || (reinterpret_cast<uintptr_t>(sp.data) & 3u) || (1u << shift) != sp.cell) return -1;
-    if (!sp.cols || sp.cols > h264k::CELLS_MAX_GRID || !sp.rows || sp.rows > h264k::CELLS_MAX_GRID) return -1;
+    if (!sp.data || (reinterpret_cast<uintptr_t>(sp.data) & 3u)) return -1;
     if (sp.source > H264BSDMI_STATS_RGB || sp.crop > 1u || sp.mode > H264BSDMI_CELLS_CHANGE || sp.keep_after > 1u) return -1;
     if (!sp.planes || (sp.planes & ~(change ? 63u : 31u))) return -1;
     if (sp.threshold[0] > 255u || sp.threshold[1] > 255u || sp.threshold[2] > 255u) return -1;
     if (!change && (sp.threshold[0] || sp.threshold[1] || sp.threshold[2] || sp.keep_after)) return -1;
-    if (n_regs > 65535u) return -1;                                     /* grid.y */
-    if (!pull_pictures_ok(n, pics, true, false) || !pull_regions_ok(n, n_regs, regs, 1u, 1u)) return -1;
-    if (change && !kept_pictures_ok(n, pics)) return -1;
-    const uint32_t rw = h264k::CELLS_RECT_W >> shift, rh = h264k::CELLS_RECT_H >> shift;
-    const uint32_t rects_x = (sp.cols + rw - 1u) / rw, rects = rects_x * ((sp.rows + rh - 1u) / rh);
-    if ((uint64_t)rects * n_regs > h264k::CELLS_MAX_WORKGROUPS) return -1;
+    if (!analysis_regions_ok(n, pics, n_regs, regs, change)) return -1;
+    CellGrid G;
+    if (!cell_grid(sp.cell, sp.cols, sp.rows, n_regs, CELLS_LIMITS, &G)) return -1;
     if (pull_begin_locked(e, n, pics, n_regs + extra)) return -1;
     h264k::CellItem *items = e->titems.host<h264k::CellItem>();
     const uint32_t channels = sp.source == H264BSDMI_STATS_Y ? 1u : 3u;
     const size_t slice = ((sp.planes & 1u) + channels * (size_t)__builtin_popcount(sp.planes >> 1)) * sp.rows * sp.cols;      /* words */
     for (uint32_t r = 0; r < n_regs; r++) {
-        const SinkRegion &g = regs[r];
-        const SinkTensorPic &p = pics[g.pic];
-        const StreamCtx *s = pic_stream(p);
-        const RegionClip c = region_clip(p, g);
-        items[r] = h264k::CellItem{ s->d_frames + (size_t)p.slot * s->frame_bytes, change ? s->d_kept.get() : nullptr,
-                                    static_cast<uint32_t *>(sp.data) + (size_t)g.index * slice, s->wmb, (int32_t)p.x0 + g.x, (int32_t)p.y0 + g.y,
-                                    c.x0, c.y0, c.x1, c.y1 };
+        const RegionSource s = region_source(pics, regs[r]);
+        items[r] = h264k::CellItem{ s.frame, change ? s.kept : nullptr, static_cast<uint32_t *>(sp.data) + (size_t)regs[r].index * slice, s.wmb, s.ox, s.oy,
+                                    s.c.x0, s.c.y0, s.c.x1, s.c.y1 };
     }
     const bool quad = sp.cell >= 16u;
     const void *const fns[2][3] = {
         { cells_kernel<0, h264k::ST_Y>(quad), cells_kernel<0, h264k::ST_YCBCR>(quad), cells_kernel<0, h264k::ST_RGB>(quad) },
         { cells_kernel<1, h264k::ST_Y>(quad), cells_kernel<1, h264k::ST_YCBCR>(quad), cells_kernel<1, h264k::ST_RGB>(quad) } };
-    *L = CellsLaunch{ fns[sp.mode][sp.source], dim3(rects, n_regs),
-                      { e->titems.dev<h264k::CellItem>(), sp.cols, sp.rows, shift, rects_x, sp.planes, { sp.threshold[0], sp.threshold[1], sp.threshold[2] } },
-                      change, shift, channels };
+    *L = CellsLaunch{ fns[sp.mode][sp.source], dim3(G.rects, n_regs),
+                      { e->titems.dev<h264k::CellItem>(), sp.cols, sp.rows, G.shift, G.rects_x, sp.planes, { sp.threshold[0], sp.threshold[1], sp.threshold[2] } },
+                      change, G.shift, channels };
     return 0;
 }
 static int cells_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, uint32_t n_regs, const SinkRegion *regs,
@@ -1847,7 +1862,7 @@ static int cells_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, ui
     CellsLaunch L;
     if (cells_prepare_locked(e, n, pics, n_regs, regs, sp, 0u, &L)) return -1;
     if (L.change && kept_order_begin(e, st)) return -1;
-    if (pull_launch_locked(e, n, pics, st, L.fn, L.grid, &L.args, fence_ev)) return -1;
+    if (pull_launch_locked(e, n, pics, st, { { L.fn, L.grid, &L.args } }, fence_ev)) return -1;
     return L.change ? kept_order_end(e, st) : 0;
 }
 
@@ -1879,11 +1894,8 @@ static int cell_boxes_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pic
     h264k::BoxArgs bargs{ L.args.items, reinterpret_cast<const h264k::BoxItem *>(e->titems.dev<TItemSlot>() + n_regs), sp.cols, sp.rows, L.shift,
                           before * sp.rows * sp.cols, bs.max_boxes, bs.sense, bs.level, bs.connectivity, bs.min_cells };
     if (L.change && kept_order_begin(e, st)) return -1;
-    if (pull_wait_pictures(e, n, pics, st)) return -1;
-    void *cell_args[] = { &L.args }, *box_args[] = { &bargs };
-    HIP_TRY(hipLaunchKernel(L.fn, L.grid, dim3(256), cell_args, 0, st));
-    HIP_TRY(hipLaunchKernel(reinterpret_cast<const void *>(&h264k::k_cell_boxes), dim3(n_regs), dim3(256), box_args, 0, st));
-    if (pull_end_locked(e, n, pics, st, fence_ev)) return -1;
+    if (pull_launch_locked(e, n, pics, st, { { L.fn, L.grid, &L.args }, { reinterpret_cast<const void *>(&h264k::k_cell_boxes), dim3(n_regs), &bargs } },
+                           fence_ev)) return -1;
     return L.change ? kept_order_end(e, st) : 0;
 }
 
@@ -1895,34 +1907,23 @@ static int flow_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, uin
                            const h264bsdmi_cell_shift_spec &sp, hipStream_t st, hipEvent_t *fence_ev)
 {
     const uint32_t all = H264BSDMI_FLOW_COUNT | H264BSDMI_FLOW_DX | H264BSDMI_FLOW_DY | H264BSDMI_FLOW_BEST | H264BSDMI_FLOW_STILL | H264BSDMI_FLOW_TIES;
-    uint32_t shift = h264k::FLOW_MIN_SHIFT;
-    while (shift < h264k::FLOW_MAX_SHIFT && (1u << shift) != sp.cell) shift++;
-    if (!sp.data || (reinterpret_cast<uintptr_t>(sp.data) & 3u) || (1u << shift) != sp.cell) return -1;
-    if (!sp.cols || sp.cols > h264k::FLOW_MAX_GRID || !sp.rows || sp.rows > h264k::FLOW_MAX_GRID) return -1;
+    if (!sp.data || (reinterpret_cast<uintptr_t>(sp.data) & 3u)) return -1;
     if (sp.radius > H264BSDMI_SHIFT_MAX_RADIUS || !sp.planes || (sp.planes & ~all) || sp.crop > 1u || sp.keep_after > 1u) return -1;
-    if (n_regs > 65535u) return -1;                                     /* grid.y */
-    if (!pull_pictures_ok(n, pics, true, false) || !pull_regions_ok(n, n_regs, regs, 1u, 1u) || !kept_pictures_ok(n, pics)) return -1;
-    const uint32_t rw = h264k::FLOW_RECT_W >> shift, rh = h264k::FLOW_RECT_H >> shift;
-    const uint32_t rects_x = (sp.cols + rw - 1u) / rw, rects = rects_x * ((sp.rows + rh - 1u) / rh);
-    if ((uint64_t)rects * n_regs > h264k::FLOW_MAX_WORKGROUPS) return -1;
+    if (!analysis_regions_ok(n, pics, n_regs, regs, true)) return -1;
+    CellGrid G;
+    if (!cell_grid(sp.cell, sp.cols, sp.rows, n_regs, FLOW_LIMITS, &G)) return -1;
     if (pull_begin_locked(e, n, pics, n_regs)) return -1;
     h264k::FlowItem *items = e->titems.host<h264k::FlowItem>();
     const size_t slice = (size_t)__builtin_popcount(sp.planes) * sp.rows * sp.cols;                   /* words */
     for (uint32_t r = 0; r < n_regs; r++) {
-        const SinkRegion &g = regs[r];
-        const SinkTensorPic &p = pics[g.pic];
-        const StreamCtx *s = pic_stream(p);
-        const RegionClip c = region_clip(p, g);
-        items[r] = h264k::FlowItem{ s->d_frames + (size_t)p.slot * s->frame_bytes, s->d_kept.get(),
-                                    static_cast<uint32_t *>(sp.data) + (size_t)g.index * slice, s->wmb, (int32_t)p.x0 + g.x, (int32_t)p.y0 + g.y,
-                                    c.x0, c.y0, c.x1, c.y1, p.x0, p.y0, p.x0 + p.w, p.y0 + p.h };
+        const RegionSource s = region_source(pics, regs[r]);
+        items[r] = h264k::FlowItem{ s.frame, s.kept, static_cast<uint32_t *>(sp.data) + (size_t)regs[r].index * slice, s.wmb, s.ox, s.oy,
+                                    s.c.x0, s.c.y0, s.c.x1, s.c.y1, s.wx0, s.wy0, s.wx1, s.wy1 };
     }
-    /* three quads of displacements per thread from radius 4 on, one below: the sibling's measured choice */
-    const void *fn = sp.radius >= h264k::SHIFT_QUADS_FROM ? reinterpret_cast<const void *>(&h264k::k_cell_shift<h264k::SHIFT_QUADS>)
-                                                           : reinterpret_cast<const void *>(&h264k::k_cell_shift<1u>);
-    h264k::FlowArgs fargs{ e->titems.dev<h264k::FlowItem>(), sp.cols, sp.rows, shift, rects_x, sp.planes, sp.radius };
+    const void *fn = shift_kernel_of(sp.radius, &h264k::k_cell_shift<h264k::SHIFT_QUADS>, &h264k::k_cell_shift<1u>);
+    h264k::FlowArgs fargs{ e->titems.dev<h264k::FlowItem>(), sp.cols, sp.rows, G.shift, G.rects_x, sp.planes, sp.radius };
     if (kept_order_begin(e, st)) return -1;
-    if (pull_launch_locked(e, n, pics, st, fn, dim3(rects, n_regs), &fargs, fence_ev)) return -1;
+    if (pull_launch_locked(e, n, pics, st, { { fn, dim3(G.rects, n_regs), &fargs } }, fence_ev)) return -1;
     return kept_order_end(e, st);
 }
 
@@ -1938,30 +1939,22 @@ static int matches_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, 
     if (misaligned(sp.data) || misaligned(sp.kept_points) || misaligned(sp.current_points)) return -1;
     if (sp.max_points < 1u || sp.max_points > h264k::MATCH_MAX_K || sp.max_distance > 256u || sp.ratio < 1u || sp.ratio > 256u ||
         sp.max_move > 65535u || sp.mutual_only > 1u || sp.crop > 1u || sp.keep_after > 1u || sp.zero) return -1;
-    if (n_regs > 65535u) return -1;                                     /* grid.y */
-    if (!pull_pictures_ok(n, pics, true, false) || !pull_regions_ok(n, n_regs, regs, 1u, 1u) || !kept_pictures_ok(n, pics)) return -1;
+    if (!analysis_regions_ok(n, pics, n_regs, regs, true)) return -1;
     if (pull_begin_locked(e, n, pics, n_regs)) return -1;
     h264k::MatchItem *items = e->titems.host<h264k::MatchItem>();
     const size_t stride = h264k::matches_record_bytes(sp.max_points), pstride = h264k::corner_record_bytes(sp.max_points);
     for (uint32_t r = 0; r < n_regs; r++) {
-        const SinkRegion &g = regs[r];
-        const SinkTensorPic &p = pics[g.pic];
-        const StreamCtx *s = pic_stream(p);
-        const RegionClip c = region_clip(p, g);
-        items[r] = h264k::MatchItem{ s->d_frames + (size_t)p.slot * s->frame_bytes, s->d_kept.get(),
-                                     static_cast<uint8_t *>(sp.data) + (size_t)g.index * stride,
-                                     static_cast<const uint8_t *>(sp.kept_points) + (size_t)g.index * pstride,
-                                     static_cast<const uint8_t *>(sp.current_points) + (size_t)g.index * pstride,
-                                     s->wmb, c.x0, c.y0, c.x1, c.y1, p.x0, p.y0, p.x0 + p.w, p.y0 + p.h };
+        const RegionSource s = region_source(pics, regs[r]);
+        const size_t index = regs[r].index;
+        items[r] = h264k::MatchItem{ s.frame, s.kept, static_cast<uint8_t *>(sp.data) + index * stride,
+                                     static_cast<const uint8_t *>(sp.kept_points) + index * pstride, static_cast<const uint8_t *>(sp.current_points) + index * pstride,
+                                     s.wmb, s.c.x0, s.c.y0, s.c.x1, s.c.y1, s.wx0, s.wy0, s.wx1, s.wy1 };
     }
     h264k::MatchArgs margs{ e->titems.dev<h264k::MatchItem>(), sp.max_points, sp.max_distance, sp.ratio, sp.max_move, sp.mutual_only };
     if (kept_order_begin(e, st)) return -1;
-    if (pull_wait_pictures(e, n, pics, st)) return -1;
-    void *args[] = { &margs };
     const uint32_t groups = (2u * sp.max_points + h264k::MATCH_GROUP - 1u) / h264k::MATCH_GROUP;
-    HIP_TRY(hipLaunchKernel(reinterpret_cast<const void *>(&h264k::k_point_describe), dim3(groups, n_regs), dim3(256), args, 0, st));
-    HIP_TRY(hipLaunchKernel(reinterpret_cast<const void *>(&h264k::k_point_match), dim3(n_regs), dim3(256), args, 0, st));
-    if (pull_end_locked(e, n, pics, st, fence_ev)) return -1;
+    if (pull_launch_locked(e, n, pics, st, { { reinterpret_cast<const void *>(&h264k::k_point_describe), dim3(groups, n_regs), &margs },
+                                             { reinterpret_cast<const void *>(&h264k::k_point_match), dim3(n_regs), &margs } }, fence_ev)) return -1;
     return kept_order_end(e, st);
 }
 
@@ -1991,20 +1984,16 @@ static int remap_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, ui
     h264k::RemapArgs rargs{ e->titems.dev<h264k::RemapItem>(), t.width, t.height, chroma, rm.filter, rm.border, {}, {}, {}, {} };
     const PullPad pp = fold_pad(rm.pad, t.dtype, t.mean, t.std, ref);
     copy3(rargs.mean, t.mean); copy3(rargs.std, t.std); copy3(rargs.pad, pp.pad); copy3(rargs.spad, pp.spad);
-    return pull_launch_locked(e, n, pics, st, fn, pull_grid(t.width, t.height, h264k::TRM_COLS, h264k::TRM_ROWS, n_maps), &rargs, fence_ev);
+    return pull_launch_locked(e, n, pics, st, { { fn, pull_grid(t.width, t.height, h264k::TRM_COLS, h264k::TRM_ROWS, n_maps), &rargs } }, fence_ev);
 }
 
-/* What JobSink.tensor_out, tensor_regions, motion_regions, tensor_remap, region_stats, keep_pictures, blend_pictures, kept_pictures_out, region_change, region_shift, corner_points, cell_maps and cell_boxes, and EngSinkEntries.cell_shift and point_matches, share: one engine (one device) per call, its mutex, the
- * refusal of a capturing stream, and, when the caller gave no stream, the wait for the fence and the device's error words.
- * body(e, st, &fence_ev): the call's own *_out_locked. */
-template <typename Body> static int sink_tensor_call(uint32_t n, const SinkTensorPic *pics, void *stream, Body body)
+/* What every entry that enqueues on a caller's stream or the engine's own shares: the engine's mutex, its device, the refusal of a
+ * capturing stream, and, when the caller gave no stream, the wait for the event the body names and the device's error words.
+ * body(st, &done): enqueues on st under the mutex; *done: the event behind everything it enqueued, which is looked at only without a
+ * caller's stream (a body may leave it unset on one). */
+template <typename Body> static int engine_call(Engine *e, void *stream, Body body)
 {
-    if (!n) return 0;
-    if (!pics) return -1;
-    Engine *e = static_cast<SinkUser *>(pics[0].sink->user)->e;
-    for (uint32_t i = 1; i < n; i++)
-        if (static_cast<SinkUser *>(pics[i].sink->user)->e != e) return -1;        /* one device per call */
-    hipEvent_t fence_ev = nullptr;
+    hipEvent_t done = nullptr;
     {
         std::lock_guard<std::mutex> lk(e->mu);
         HIP_TRY(hipSetDevice(e->device));
@@ -2014,13 +2003,24 @@ template <typename Body> static int sink_tensor_call(uint32_t n, const SinkTenso
             HIP_TRY(hipStreamIsCapturing(st, &cs));
             if (cs != hipStreamCaptureStatusNone) return -1;                      /* graph capture of this call is not supported */
         }
-        if (body(e, st, &fence_ev)) return -1;
+        if (body(st, &done)) return -1;
     }
     if (stream) return 0;
-    if (hipEventSynchronize(fence_ev) != hipSuccess) return -1;        /* (a later call may have recorded it again: that only waits longer) */
+    if (hipEventSynchronize(done) != hipSuccess) return -1;            /* (a later call may have recorded it again: that only waits longer) */
     std::lock_guard<std::mutex> lk(e->mu);
     fold_errors(e);
     return 0;
+}
+/* What JobSink.tensor_out, tensor_regions, motion_regions, tensor_remap, region_stats, keep_pictures, blend_pictures, kept_pictures_out, region_change, region_shift, corner_points, cell_maps and cell_boxes, and EngSinkEntries.cell_shift and point_matches, share: one engine (one device) per call, and engine_call
+ * around the call's own *_out_locked, body(e, st, &fence_ev), with the fence as the event to wait for. */
+template <typename Body> static int sink_tensor_call(uint32_t n, const SinkTensorPic *pics, void *stream, Body body)
+{
+    if (!n) return 0;
+    if (!pics) return -1;
+    Engine *e = static_cast<SinkUser *>(pics[0].sink->user)->e;
+    for (uint32_t i = 1; i < n; i++)
+        if (static_cast<SinkUser *>(pics[i].sink->user)->e != e) return -1;        /* one device per call */
+    return engine_call(e, stream, [&](hipStream_t st, hipEvent_t *fence_ev) { return body(e, st, fence_ev); });
 }
 int sink_tensor_out(uint32_t n, const SinkTensorPic *pics, const h264bsdmi_tensor_spec *spec, uint32_t chroma,
                     const h264bsdmi_resize_spec *resize, void *stream)
@@ -2159,16 +2159,7 @@ int sink_point_model(const JobSink *sink, uint32_t n_records, const h264bsdmi_mo
     if (sp.min_inliers < 1u + sp.model || sp.min_inliers > 256u || sp.zero[0] || sp.zero[1] || sp.zero[2]) return -1;
     if (n_records > 65535u) return -1;
     Engine *e = static_cast<SinkUser *>(sink->user)->e;
-    hipEvent_t done = nullptr;
-    {
-        std::lock_guard<std::mutex> lk(e->mu);
-        HIP_TRY(hipSetDevice(e->device));
-        hipStream_t st = stream ? static_cast<hipStream_t>(stream) : e->stream;
-        if (stream) {
-            hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-            HIP_TRY(hipStreamIsCapturing(st, &cs));
-            if (cs != hipStreamCaptureStatusNone) return -1;                      /* graph capture of this call is not supported */
-        }
+    return engine_call(e, stream, [&](hipStream_t st, hipEvent_t *done) {
         h264k::ModelArgs margs{ static_cast<uint8_t *>(sp.data), static_cast<const uint8_t *>(sp.matches), static_cast<const uint8_t *>(sp.kept_points),
                                 static_cast<const uint8_t *>(sp.current_points), sp.max_points, sp.model, sp.tolerance, sp.max_scale, sp.min_inliers };
         void *args[] = { &margs };
@@ -2178,12 +2169,9 @@ int sink_point_model(const JobSink *sink, uint32_t n_records, const h264bsdmi_mo
         HIP_TRY(hipGetLastError());
         if (!e->model_ev) HIP_TRY(e->model_ev.create(hipEventDisableTiming));
         HIP_TRY(hipEventRecord(e->model_ev, st));
-        done = e->model_ev;
-    }
-    if (hipEventSynchronize(done) != hipSuccess) return -1;            /* (a later call may have recorded it again: that only waits longer) */
-    std::lock_guard<std::mutex> lk(e->mu);
-    fold_errors(e);
-    return 0;
+        *done = e->model_ev;
+        return 0;
+    });
 }
 /* JobSink.set_motion (h264bsdmiSetMotionExport): before the instance's first sequence is configured */
 int sink_set_motion(void *user, int on)

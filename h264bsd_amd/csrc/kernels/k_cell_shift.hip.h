@@ -1,8 +1,8 @@
 /* kernels/k_cell_shift.hip.h — WHERE did every cell go: the block-matching SAD search of k_region_shift.hip.h for every cell of a grid
  * of square cells laid over a box (h264bsdmiOutputCellShift): cell (i, j) of a region holds count, dx, dy, best, still and ties of the
  * record k_region_shift writes for the cell's box, template from the KEPT picture, searched in the CURRENT picture clamped at the
- * WINDOW, luma only.  Included by engine.hip after k_region_shift.hip.h, whose staging (shift_stage), masked path (shift_sad4), inner
- * loop and constants it uses, with the ownership scheme of k_cell_maps.hip.h; like them, not part of the kernel sources that key the
+ * WINDOW, luma only.  Included by engine.hip after k_region_shift.hip.h, whose constants and inner loop it uses, with the staging (luma_stage), the
+ * masked path (shift_sad4) and the argmin's key (shift_key) of luma_search.hip.h and the ownership scheme of k_cell_maps.hip.h; like them, not part of the kernel sources that key the
  * committed counter tables (srchash.py).
  *
  * A slice: P maps of rows x cols u32, row-major, in ascending bit order of H264BSDMI_FLOW_*: count, dx (i32), dy (i32), best, still, ties.
@@ -11,7 +11,7 @@
  * ticket, no hand-over between workgroups, and nothing depends on scheduling.
  * STAGING, once per rectangle: box ∩ window ∩ rectangle of the kept picture as raster rows of dwords from the rectangle's left edge
  * (rounded down to the dword that holds the first sample that counts, so a cell starts on a dword), and the current picture from R rows
- * above and R columns left of it: th + 2 R rows of tw4 + Q dwords, clamped at the window by shift_stage.  The halo is what is read more
+ * above and R columns left of it: th + 2 R rows of tw4 + Q dwords, clamped at the window by luma_stage.  The halo is what is read more
  * than once: at R = 16, 96 x 96 samples for 64 x 64 of template.
  * LDS (160 KiB per compute unit): 64 x 16 dwords of template (4 KiB), 96 rows at a pitch of 27 dwords of current picture (10.1 KiB, the
  * odd pitch keeps rows that differ by dy on different banks), FLOW_SURF_WORDS of SAD surfaces (16 KiB) and 5 x 64 results: 31.5 KiB,
@@ -77,9 +77,9 @@ __global__ __launch_bounds__(256) void k_cell_shift(FlowArgs a)
     if (it.x1 > it.x0 && it.y1 > it.y0 && rx1 > rx0 && ry1 > ry0) {
         const int SX = rectx + (int)(((uint32_t)(rx0 - rectx) >> 2) << 2), SY = ry0;                /* the template's first staged sample */
         const uint32_t tw4 = (uint32_t)(rx1 - SX + 3) >> 2, th = (uint32_t)(ry1 - ry0);
-        const ShiftItem si{ it.cur, it.kept, nullptr, it.wmb, it.x0, it.y0, it.x1, it.y1, it.wx0, it.wy0, it.wx1, it.wy1 };
-        shift_stage(it.kept, si, SX, SY, tw4, th, s_t, FLOW_COLS4, tid);
-        shift_stage(it.cur, si, SX - (int)R, SY - (int)R, tw4 + QUADS * Q3, th + 2u * R, s_c, FLOW_PITCH, tid);
+        const LumaWindow win{ it.wmb, it.wx0, it.wy0, it.wx1, it.wy1 };
+        luma_stage(it.kept, win, SX, SY, tw4, th, s_t, FLOW_COLS4, tid);
+        luma_stage(it.cur, win, SX - (int)R, SY - (int)R, tw4 + QUADS * Q3, th + 2u * R, s_c, FLOW_PITCH, tid);
 
         const uint32_t gc = min(ncell, FLOW_SURF_WORDS / n);               /* cells per group */
         const uint32_t G = min(max((FLOW_SPLIT + gc * P - 1u) / (gc * P), 1u), (uint32_t)cell);       /* shares of a cell's rows */
@@ -133,7 +133,7 @@ __global__ __launch_bounds__(256) void k_cell_shift(FlowArgs a)
 #pragma unroll
                         for (uint32_t j = 0; j < QUADS; j++) {
 #pragma unroll
-                            for (int k = 0; k < 4; k++) sum[j][k] += (uint32_t)(acc[j] >> (16 * k)) & 0xFFFFu;
+                            for (uint32_t k = 0; k < 4u; k++) sum[j][k] += shift_field(acc[j], k);
                             acc[j] = 0ull;
                         }
                         pending = 0u;
@@ -144,7 +144,7 @@ __global__ __launch_bounds__(256) void k_cell_shift(FlowArgs a)
                 for (uint32_t j = 0; j < QUADS; j++)
 #pragma unroll
                     for (uint32_t k = 0; k < 4u; k++) {
-                        const uint32_t dxi = 4u * (q + j) + k, s = sum[j][k] + ((uint32_t)(acc[j] >> (16u * k)) & 0xFFFFu);
+                        const uint32_t dxi = 4u * (q + j) + k, s = sum[j][k] + shift_field(acc[j], k);
                         if (dxi < D && s) region_lds_add(&surf[dxi], s);
                     }
             }
@@ -158,18 +158,17 @@ __global__ __launch_bounds__(256) void k_cell_shift(FlowArgs a)
                 unsigned long long key = ~0ull;
                 for (uint32_t i = sub; valid && i < n; i += LPC) {
                     const uint32_t dyi = (i * magic) >> 16, dxi = i - dyi * D;
-                    const int dx = (int)dxi - (int)R, dy = (int)dyi - (int)R;
-                    key = min(key, (unsigned long long)surf[i] << 32 | (unsigned long long)(uint32_t)(dx * dx + dy * dy) << 12 | dyi << 6 | dxi);
+                    key = min(key, shift_key(surf[i], dxi, dyi, R));
                 }
                 for (uint32_t d = LPC >> 1; d; d >>= 1) key = min(key, (unsigned long long)__shfl_xor(key, (int)d));
-                const uint32_t best = (uint32_t)(key >> 32);
+                const uint32_t best = shift_key_best(key);
                 uint32_t ties = 0u;
                 for (uint32_t i = sub; valid && i < n; i += LPC) ties += surf[i] == best ? 1u : 0u;
                 for (uint32_t d = LPC >> 1; d; d >>= 1) ties += __shfl_xor(ties, (int)d);
                 if (valid && sub == 0u) {
                     const uint32_t c = g0 + cl;
-                    s_out[0][c] = (uint32_t)((int)(key & 63u) - (int)R);
-                    s_out[1][c] = (uint32_t)((int)((key >> 6) & 63u) - (int)R);
+                    s_out[0][c] = shift_key_dx(key, R);
+                    s_out[1][c] = shift_key_dy(key, R);
                     s_out[2][c] = best;
                     s_out[3][c] = surf[R * D + R];
                     s_out[4][c] = ties;

@@ -1,10 +1,10 @@
 /* kernels/k_corner_points.hip.h — WHICH boxes are worth following: Shi-Tomasi / Harris corner points of boxes of CURRENT pictures
  * (h264bsdmiOutputCornerPoints), luma only, read from the macroblock tiles where they lie.  Included by engine.hip after
- * k_region_shift.hip.h, whose shift_stage stages the luma; the band / ticket scheme and the wave sums are region_common.hip.h's; like
+ * k_region_shift.hip.h; luma_stage (luma_search.hip.h) stages the luma; the band / ticket scheme and the wave sums are region_common.hip.h's; like
  * them, not part of the kernel sources that key the committed counter tables (srchash.py).
  *
  * The quantity (include/h264bsd_mi355x.h has it in full), all integers, T = box ∩ window:
- *     L~        the luma replicated at the border of the WINDOW (the clamp of shift_stage), the only border rule
+ *     L~        the luma replicated at the border of the WINDOW (the clamp of luma_stage), the only border rule
  *     gx, gy    the 3 x 3 Sobel gradients of L~, |g| <= 1020
  *     A, B, C   the sums of gx gx, gy gy, gx gy over the b x b samples around a sample, b = 3 or 5: below 2^25
  *     S         MIN_EIGEN: A + B - isqrt((A - B)^2 + 4 C^2), in [0, 2^26)       HARRIS: 16 (A B - C C) - (A + B)^2, |S| < 2^54
@@ -14,7 +14,7 @@
  *               candidates in T by (score descending, y, x ascending), the first K; 32 + 16 K bytes, written whole
  * grid (S row bands, regions) x 256.  A band walks its rows of T in tiles of at most CORNER_ROWS x COLS samples, by the same
  * workgroup.  Per tile, with h = nms and hb = b / 2, five steps through LDS, a barrier between them:
- *     luma      (th + 2 (h + hb + 1)) rows of dwords, staged once by shift_stage
+ *     luma      (th + 2 (h + hb + 1)) rows of dwords, staged once by luma_stage
  *     gradient  gx, gy as the two 16-bit halves of a dword, one sample less on every side; a thread makes four in a row from two
  *               dwords of each of three rows
  *     score     (th + 2 h) x (tw + 2 h); a thread makes four in a row from the sums down 4 + 2 hb columns of the b rows (18 reads for
@@ -122,7 +122,7 @@ __global__ __launch_bounds__(256) void k_corner_points(CornerArgs a)
     uint32_t *const s_l = reinterpret_cast<uint32_t *>(s_lgr), *const s_g = s_l + L_WORDS;
     score_t *const s_r = reinterpret_cast<score_t *>(s_lgr);
     const CornerItem it = a.items[blockIdx.y];
-    const ShiftItem si{ it.frame, nullptr, it.dst, it.wmb, it.x0, it.y0, it.x1, it.y1, it.wx0, it.wy0, it.wx1, it.wy1 };
+    const LumaWindow win{ it.wmb, it.wx0, it.wy0, it.wx1, it.wy1 };
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint32_t h = a.nms, halo = h + HB + 1u, K = a.max_points;
     const uint32_t S = gridDim.x, band = blockIdx.x;
@@ -141,7 +141,7 @@ __global__ __launch_bounds__(256) void k_corner_points(CornerArgs a)
             const uint32_t lw = tw + 2u * halo, lh = th + 2u * halo, gw = lw - 2u, gh = lh - 2u, sw = tw + 2u * h, sh = th + 2u * h;
             const uint32_t lq = (lw + 3u) >> 2, gq = (gw + 3u) >> 2, sq = (sw + 3u) >> 2;
             __syncthreads();                                                /* the tile before has been read */
-            shift_stage(it.frame, si, (int)xs - (int)halo, (int)ys - (int)halo, lq, lh, s_l, LP, tid);
+            luma_stage(it.frame, win, (int)xs - (int)halo, (int)ys - (int)halo, lq, lh, s_l, LP, tid);
             __syncthreads();
             /* gradient (i, j) is at luma (i + 1, j + 1); four in a row from two dwords of each of three rows */
             for (uint32_t idx = tid; idx < gh * gq; idx += 256u) {

@@ -1,10 +1,10 @@
 /* kernels/k_point_matches.hip.h — WHERE did the points go, at any distance: a 256-bit binary descriptor of every corner point of a kept and
  * of a current picture, and the Hamming matching of the two sets (h264bsdmiOutputPointMatches), luma only, read from the macroblock tiles
- * where they lie.  Included by engine.hip after k_corner_points.hip.h; shift_stage (k_region_shift.hip.h) stages the luma, the wave sums
+ * where they lie.  Included by engine.hip after k_corner_points.hip.h; luma_stage (luma_search.hip.h) stages the luma, the wave sums
  * are region_common.hip.h's; like them, not part of the kernel sources that key the committed counter tables (srchash.py).
  *
  * The quantity (include/h264bsd_mi355x.h has it in full), all integers, T = box ∩ window:
- *     L~          the luma replicated at the border of the WINDOW (the clamp of shift_stage), the only border rule
+ *     L~          the luma replicated at the border of the WINDOW (the clamp of luma_stage), the only border rule
  *     B(u, v)     the sum of L~ over the 5 x 5 samples around (u, v), 0 .. 6375
  *     bit t       of the descriptor of (x, y): B(x + px_t, y + py_t) < B(x + qx_t, y + qy_t), the 256 tests of descriptor_pattern.h
  *     valid       slot i of a point record: i < min(written, K) and (x, y) in T; the descriptor of an invalid slot is zero
@@ -14,7 +14,7 @@
  *                 K x 32 bytes of kept descriptors; K x 32 bytes of current descriptors: 32 + 80 K bytes, written whole by the two kernels
  * k_point_describe, grid (groups of MATCH_GROUP slots, regions) x 256.  The 2 K slots of a region are the K kept ones and behind them the
  * K current ones, as their descriptors lie in the record.  A wavefront takes one slot at a time, the workgroup four: the 29 x 29 patch
- * around the point is staged by shift_stage as 29 rows of 8 dwords (the clamp at the window happens there), a lane makes four horizontal
+ * around the point is staged by luma_stage as 29 rows of 8 dwords (the clamp at the window happens there), a lane makes four horizontal
  * 5-sums from two dwords (u16, 29 x 28), a lane makes two vertical 5-sums from five dwords of those (u16, 25 x 26: the 25 x 25 values of
  * B the tests can name), and lane l evaluates the tests l, l + 64, l + 128 and l + 192, whose eight LDS offsets it computed once from
  * the pattern; four ballots are the 256 bits, which lanes 0 .. 7 store.  The point records are the caller's memory: `written` is clamped
@@ -65,7 +65,7 @@ __global__ __launch_bounds__(256) void k_point_describe(MatchArgs a)
     __shared__ uint32_t s_h[4][MATCH_PATCH * MATCH_HP / 2u];                /* u16 pairs */
     __shared__ uint32_t s_b[4][MATCH_B * MATCH_BP / 2u];
     const MatchItem it = a.items[blockIdx.y];
-    const ShiftItem si{ it.cur, it.kept, it.dst, it.wmb, it.x0, it.y0, it.x1, it.y1, it.wx0, it.wy0, it.wx1, it.wy1 };
+    const LumaWindow win{ it.wmb, it.wx0, it.wy0, it.wx1, it.wy1 };
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6, K = a.max_points;
     /* this lane's four tests as offsets into B, once */
     uint32_t op[4], oq[4];
@@ -90,7 +90,7 @@ __global__ __launch_bounds__(256) void k_point_describe(MatchArgs a)
 #pragma unroll
         for (uint32_t k = 0; k < 4u; k++)
             if (ok[k])
-                shift_stage(s0 + k < K ? it.kept : it.cur, si, (int)it.wx0 + px[k] - (int)MATCH_HALO, (int)it.wy0 + py[k] - (int)MATCH_HALO,
+                luma_stage(s0 + k < K ? it.kept : it.cur, win, (int)it.wx0 + px[k] - (int)MATCH_HALO, (int)it.wy0 + py[k] - (int)MATCH_HALO,
                             MATCH_PP, MATCH_PATCH, s_p[k], MATCH_PP, tid);
         __syncthreads();
         const bool mine = wave == 0u ? ok[0] : wave == 1u ? ok[1] : wave == 2u ? ok[2] : ok[3];      /* wave-uniform */

@@ -1,14 +1,14 @@
 /* kernels/k_region_shift.hip.h — WHERE did a box go: block-matching SAD search of boxes of the KEPT picture (k_keep.hip.h) in the
  * CURRENT picture of the same instance (h264bsdmiOutputRegionShift), luma only, both read from their macroblock tiles where they lie.
- * Included by engine.hip after k_region_change.hip.h; the band / ticket scheme and the wave reduction are region_common.hip.h's;
- * like them, not part of the kernel sources that key the committed counter tables (srchash.py).
+ * Included by engine.hip after k_region_change.hip.h; the band / ticket scheme and the wave reduction are region_common.hip.h's, the
+ * staging (luma_stage, here on the ShiftItem itself), the masked path (shift_sad4) and the argmin's key (shift_key) luma_search.hip.h's; like them, not part of the kernel sources that key the committed counter tables (srchash.py).
  *
  * One record, R = radius (0 .. 16), D = 2 R + 1, little endian, 32 bytes, with the surface 32 + 4 (D D + 1):
  *     u32 count; u32 D; i32 dx; i32 dy; u32 best; u32 still; u32 ties; u32 zero;   [ D x D x u32 sad[(dy + R) D + (dx + R)]; u32 zero ]
  *     SAD(dx, dy) = sum over (u, v) of T = box ∩ window of | kept(u, v) - current(clamp(u + dx), clamp(v + dy)) |, clamped at the WINDOW
  * grid (S row bands, regions) x 256.  A band is walked in tiles of at most SHIFT_ROWS x 4 SHIFT_COLS4 template samples, column chunk
  * by column chunk, by the same workgroup.  Per tile both pictures are read from memory ONCE and staged in LDS as raster rows of dwords
- * (shift_stage: two aligned tile dwords and v_alignbyte per staged dword; bytewise where the clamp at the window is active): the
+ * (luma_stage: two aligned tile dwords and v_alignbyte per staged dword; bytewise where the clamp at the window is active): the
  * template with its first sample in byte 0 of dword 0, the current picture from R rows above and R columns left of it, th + 2 R rows of
  * tw4 + Q dwords, Q = ceil(D / 4) rounded up to whole threads.  The halo is what is read more than once: R rows per tile above and
  * below, R columns beside it.
@@ -62,43 +62,6 @@ struct ShiftItem { const uint8_t *cur; const uint8_t *kept; uint8_t *dst; uint32
 /* partials: region r's band b at ((r S + b) D D) words; tickets: as StatsArgs */
 struct ShiftArgs { const ShiftItem *items; uint8_t *partials; uint32_t *tickets; uint32_t radius, surface; };
 
-/* rows x cols4 dwords of a frame's luma into LDS as raster rows: byte k of dword j of row i is the sample at
- * (clamp(X0 + 4 j + k, wx0, wx1 - 1), clamp(Y0 + i, wy0, wy1 - 1)).  Every SAMPLE taken is inside the window; the aligned dwords of the
- * fast path may start up to 3 bytes left of wx0 or end up to 3 bytes right of wx1 - 1, but they lie in the 16-byte tile rows of samples of
- * the window, so inside the frame */
-__device__ __forceinline__ void shift_stage(const uint8_t *frame, const ShiftItem &it, int X0, int Y0, uint32_t cols4, uint32_t rows,
-                                            uint32_t *lds, uint32_t pitch, uint32_t tid)
-{
-    for (uint32_t i = tid; i < rows * cols4; i += 256u) {
-        const uint32_t r = i / cols4, j = i - r * cols4;
-        const uint32_t Y = (uint32_t)min(max(Y0 + (int)r, (int)it.wy0), (int)it.wy1 - 1);
-        const int X = X0 + 4 * (int)j;
-        const uint8_t *row = frame + (size_t)(Y >> 4) * it.wmb * TILE + (Y & 15u) * 16u;
-        uint32_t v;
-        if (X >= (int)it.wx0 && X + 3 < (int)it.wx1) {
-            const uint32_t xa = (uint32_t)X & ~3u, sh = (uint32_t)X & 3u, xb = sh ? xa + 4u : xa;       /* xb <= X + 3: inside as well */
-            const uint32_t lo = *reinterpret_cast<const uint32_t *>(row + (size_t)(xa >> 4) * TILE + (xa & 15u));
-            const uint32_t hi = *reinterpret_cast<const uint32_t *>(row + (size_t)(xb >> 4) * TILE + (xb & 15u));
-            v = __builtin_amdgcn_alignbyte(hi, lo, sh);
-        } else {
-            v = 0u;
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                const uint32_t x = (uint32_t)min(max(X + k, (int)it.wx0), (int)it.wx1 - 1);
-                v |= (uint32_t)row[(size_t)(x >> 4) * TILE + (x & 15u)] << (8 * k);
-            }
-        }
-        lds[r * pitch + j] = v;
-    }
-}
-
-/* the four SADs of template dword t against the bytes k .. k + 3 of c1:c0, k = 0 .. 3, bytes outside m left out, added to sum[] */
-__device__ __forceinline__ void shift_sad4(uint32_t c0, uint32_t c1, uint32_t t, uint32_t m, uint32_t *sum)
-{
-#pragma unroll
-    for (int k = 0; k < 4; k++) sum[k] = __builtin_amdgcn_sad_u8(__builtin_amdgcn_alignbyte(c1, c0, (uint32_t)k) & m, t & m, sum[k]);
-}
-
 template <uint32_t QUADS>
 __global__ __launch_bounds__(256) void k_region_shift(ShiftArgs a)
 {
@@ -124,8 +87,8 @@ __global__ __launch_bounds__(256) void k_region_shift(ShiftArgs a)
             const uint32_t tw = min(4u * SHIFT_COLS4, it.x1 - xs), tw4 = (tw + 3u) >> 2;
             const uint32_t tail = (tw & 3u) ? (1u << (8u * (tw & 3u))) - 1u : 0xFFFFFFFFu;      /* the bytes of a row's last dword that count */
             __syncthreads();                                                /* the sums are zero / the tile before has been read */
-            shift_stage(it.kept, it, (int)xs, (int)ys, tw4, th, s_t, SHIFT_COLS4, tid);
-            shift_stage(it.cur, it, (int)xs - (int)R, (int)ys - (int)R, tw4 + QUADS * Q3, th + 2u * R, s_c, SHIFT_PITCH, tid);
+            luma_stage(it.kept, it, (int)xs, (int)ys, tw4, th, s_t, SHIFT_COLS4, tid);
+            luma_stage(it.cur, it, (int)xs - (int)R, (int)ys - (int)R, tw4 + QUADS * Q3, th + 2u * R, s_c, SHIFT_PITCH, tid);
             __syncthreads();
             /* segments of L dwords of one row, about four per share */
             uint32_t L = 1u;
@@ -160,7 +123,7 @@ __global__ __launch_bounds__(256) void k_region_shift(ShiftArgs a)
 #pragma unroll
                     for (uint32_t j = 0; j < QUADS; j++)
 #pragma unroll
-                        for (int k = 0; k < 4; k++) sum[j][k] += (uint32_t)(acc[j] >> (16 * k)) & 0xFFFFu;
+                        for (uint32_t k = 0; k < 4u; k++) sum[j][k] += shift_field(acc[j], k);
                 }
 #pragma unroll
                 for (uint32_t j = 0; j < QUADS; j++)
@@ -192,15 +155,14 @@ __global__ __launch_bounds__(256) void k_region_shift(ShiftArgs a)
     unsigned long long key = ~0ull;
     for (uint32_t i = tid; i < n; i += 256u) {
         const uint32_t dyi = i / D, dxi = i - dyi * D;
-        const int dx = (int)dxi - (int)R, dy = (int)dyi - (int)R;
-        key = min(key, (unsigned long long)s_sad[dyi * SP + dxi] << 32 | (unsigned long long)(uint32_t)(dx * dx + dy * dy) << 12 | dyi << 6 | dxi);
+        key = min(key, shift_key(s_sad[dyi * SP + dxi], dxi, dyi, R));
     }
 #pragma unroll
     for (int d = 32; d; d >>= 1) key = min(key, (unsigned long long)__shfl_xor(key, d));
     if (lane == 0u) s_key[wave] = key;
     __syncthreads();
     key = min(min(s_key[0], s_key[1]), min(s_key[2], s_key[3]));
-    const uint32_t best = (uint32_t)(key >> 32);
+    const uint32_t best = shift_key_best(key);
     uint32_t ties = 0u;
     for (uint32_t i = tid; i < n; i += 256u) ties += s_sad[(i / D) * SP + i % D] == best ? 1u : 0u;
     ties = stats_wave_sum(ties);
@@ -210,8 +172,8 @@ __global__ __launch_bounds__(256) void k_region_shift(ShiftArgs a)
     if (tid == 0u) {
         dst32[0] = empty ? 0u : (it.x1 - it.x0) * (it.y1 - it.y0);
         dst32[1] = D;
-        dst32[2] = (uint32_t)((int)(key & 63u) - (int)R);
-        dst32[3] = (uint32_t)((int)((key >> 6) & 63u) - (int)R);
+        dst32[2] = shift_key_dx(key, R);
+        dst32[3] = shift_key_dy(key, R);
         dst32[4] = best;
         dst32[5] = s_sad[R * SP + R];
         dst32[6] = s_ties[0] + s_ties[1] + s_ties[2] + s_ties[3];
