@@ -17,7 +17,7 @@ from .capi import (  # noqa: F401
     CellShiftSpec, CellShift, pull_flow,
     MatchesSpec, PointMatches, pull_matches, matches_record_bytes, descriptor_pattern,
     ModelSpec, PointModel, pull_model, model_record_bytes,
-    BlendSpec, BLEND_FROZEN, blend_pictures, pull_kept,
+    BlendSpec, BLEND_FROZEN, blend_pictures, pull_kept, SpreadSpec, SPREAD_UPDATES,
     WarpSpec, WarpMap, WARP_OUTSIDE, WARP_MAX_COEFFICIENT, warp_coefficients, warp_kept,
 )
 
@@ -28,4 +28,6 @@ from .capi import (  # noqa: F401
 # 0.9: pull_corners (h264bsdmiOutputCornerPoints); 0.10: pull_flow (h264bsdmiOutputCellShift)
 # 0.11: pull_matches (h264bsdmiOutputPointMatches); 0.12: pull_model (h264bsdmiOutputPointModel)
 # 0.13: warp_kept / warp_coefficients (h264bsdmiWarpKeptPictures)
-__version__ = "0.13.0"
+# 0.14: blend_pictures(spread=), pull_kept(spread=), pull_cells / pull_boxes(against="spread") (h264bsdmiBlendCurrentPicturesSpread,
+#       h264bsdmiOutputKeptSpread, H264BSDMI_CELLS_SPREAD)
+__version__ = "0.14.0"

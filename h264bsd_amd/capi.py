@@ -28,7 +28,7 @@ EXPORTED_SYMBOLS = [
     "h264bsdCroppingParams", "h264bsdSampleAspectRatio", "h264bsdCheckValidParamSets", "h264bsdFlushBuffer",
     "h264bsdProfile", "h264bsdAlloc", "h264bsdFree", "h264bsdConvertToRGBA", "h264bsdConvertToBGRA",
     "h264bsdConvertToYCbCrA",
-    "h264bsdmiInitCapture", "h264bsdmiNextOutputInfo", "h264bsdmiNextOutputPictureDevice", "h264bsdmiNextOutputTensorBatch", "h264bsdmiNextOutputTensorBatchColour", "h264bsdmiNextOutputTensorBatchResize", "h264bsdmiOutputTensorRegions", "h264bsdmiOutputTensorRemap", "h264bsdmiSetMotionExport", "h264bsdmiOutputMotionRegions", "h264bsdmiOutputRegionStats", "h264bsdmiKeepCurrentPictures", "h264bsdmiBlendCurrentPictures", "h264bsdmiOutputKeptPictures", "h264bsdmiWarpKeptPictures", "h264bsdmiOutputRegionChange", "h264bsdmiOutputRegionShift", "h264bsdmiOutputCornerPoints", "h264bsdmiOutputCellMaps", "h264bsdmiOutputCellBoxes", "h264bsdmiOutputCellShift", "h264bsdmiOutputPointMatches", "h264bsdmiDescriptorPattern", "h264bsdmiOutputPointModel", "h264bsdmiJobFinalize", "h264bsdmiDeviceCount", "h264bsdmiSetDevice", "h264bsdmiFlush", "h264bsdmiFlushAsync", "h264bsdmiDeviceErrors",
+    "h264bsdmiInitCapture", "h264bsdmiNextOutputInfo", "h264bsdmiNextOutputPictureDevice", "h264bsdmiNextOutputTensorBatch", "h264bsdmiNextOutputTensorBatchColour", "h264bsdmiNextOutputTensorBatchResize", "h264bsdmiOutputTensorRegions", "h264bsdmiOutputTensorRemap", "h264bsdmiSetMotionExport", "h264bsdmiOutputMotionRegions", "h264bsdmiOutputRegionStats", "h264bsdmiKeepCurrentPictures", "h264bsdmiBlendCurrentPictures", "h264bsdmiBlendCurrentPicturesSpread", "h264bsdmiOutputKeptPictures", "h264bsdmiOutputKeptSpread", "h264bsdmiWarpKeptPictures", "h264bsdmiOutputRegionChange", "h264bsdmiOutputRegionShift", "h264bsdmiOutputCornerPoints", "h264bsdmiOutputCellMaps", "h264bsdmiOutputCellBoxes", "h264bsdmiOutputCellShift", "h264bsdmiOutputPointMatches", "h264bsdmiDescriptorPattern", "h264bsdmiOutputPointModel", "h264bsdmiJobFinalize", "h264bsdmiDeviceCount", "h264bsdmiSetDevice", "h264bsdmiFlush", "h264bsdmiFlushAsync", "h264bsdmiDeviceErrors",
     "h264bsdmiDecodePicture", "h264bsdmiDecodePictureBatch", "h264bsdmiNextOutputPictureBatch", "h264bsdmiPullAndDecodePictureBatch", "h264bsdmiSetParserThreads", "h264bsdmiSetInputReadOnly", "h264bsdmiSetCopyElision",
     "h264bsdmiReplayCreate", "h264bsdmiReplayCreateStaggered", "h264bsdmiReplayCreateDesync", "h264bsdmiReplayCreateSched", "h264bsdmiReplayReschedule", "h264bsdmiReplayDestroy", "h264bsdmiReplayRun", "h264bsdmiReplaySync",
     "h264bsdmiReplayFetch", "h264bsdmiReplayDbkRecords", "h264bsdmiReplayChecksums", "h264bsdmiReplayConvert", "h264bsdmiReplayFetchConverted",
@@ -103,6 +103,14 @@ class BlendSpec(ctypes.Structure):
 BLEND_FROZEN = 8                                                                 # H264BSDMI_BLEND_FROZEN
 
 
+class SpreadSpec(ctypes.Structure):
+    """h264bsdmi_spread_spec (include/h264bsd_mi355x.h)"""
+    _fields_ = [("gain", ctypes.c_uint32), ("lowest", ctypes.c_uint32), ("highest", ctypes.c_uint32), ("update", ctypes.c_uint32)]
+
+
+SPREAD_UPDATES = {"none": 0, "all": 1, "still": 2}                               # H264BSDMI_SPREAD_*
+
+
 class WarpMap(ctypes.Structure):
     """h264bsdmi_warp_map (include/h264bsd_mi355x.h): output -> source, 16.16 fixed point"""
     _fields_ = [(k, ctypes.c_int32) for k in "abcdef"]
@@ -169,6 +177,9 @@ BOXES_MAX_CELLS, BOXES_MAX_BOXES = 16384, 512                                   
 BOXES_SENSES = {"above": 0, "below": 1}                                          # H264BSDMI_BOXES_*
 # per mode (H264BSDMI_CELLS_PICTURE, _CHANGE): name -> H264BSDMI_CELL_*, in the order of the maps
 CELL_PLANES = ({"count": 1, "sum": 2, "sumsq": 4, "min": 8, "max": 16}, {"count": 1, "sad": 2, "ssd": 4, "dsum": 8, "dmax": 16, "above": 32})
+CELL_SPREAD_PLANES = {"count": 1, "fore": 2, "excess": 4, "spread": 8}              # ... and of H264BSDMI_CELLS_SPREAD
+CELL_MODE_PLANES = CELL_PLANES + (CELL_SPREAD_PLANES,)                            # by H264BSDMI_CELLS_*
+CELL_AGAINST = {None: 0, "kept": 1, "spread": 2}                                  # pull_cells(against=) -> H264BSDMI_CELLS_*
 CELL_SIZES = (4, 8, 16, 32, 64)
 FLOW_PLANES = {"count": 1, "dx": 2, "dy": 4, "best": 8, "still": 16, "ties": 32}    # name -> H264BSDMI_FLOW_*, in the order of the maps
 FLOW_CELL_SIZES = (8, 16, 32, 64)
@@ -315,6 +326,10 @@ def _declare(L, harness):
     L.h264bsdmiBlendCurrentPictures.restype = ctypes.c_int
     L.h264bsdmiOutputKeptPictures.argtypes = [u32, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), vp, P32, P32]
     L.h264bsdmiOutputKeptPictures.restype = ctypes.c_int
+    L.h264bsdmiBlendCurrentPicturesSpread.argtypes = [u32, ctypes.POINTER(vp), ctypes.POINTER(BlendSpec), ctypes.POINTER(SpreadSpec), vp, P32, P32, P32]
+    L.h264bsdmiBlendCurrentPicturesSpread.restype = ctypes.c_int
+    L.h264bsdmiOutputKeptSpread.argtypes = [u32, ctypes.POINTER(vp), ctypes.POINTER(vp), vp, P32, P32]
+    L.h264bsdmiOutputKeptSpread.restype = ctypes.c_int
     L.h264bsdmiOutputRegionChange.argtypes = [u32, ctypes.POINTER(vp), u32, ctypes.POINTER(Region), ctypes.POINTER(ChangeSpec), vp,
                                               P32, P32, P32, P32, P32]
     L.h264bsdmiOutputRegionChange.restype = ctypes.c_int
@@ -1018,7 +1033,19 @@ def keep_pictures(decoders, stream=None):
     return list(kept)[:n], list(ids)[:n]
 
 
-def blend_pictures(decoders, shift=4, hold=255, moving_shift=None, count_moving=False, stream=None):
+def _spread_spec(spread):
+    """the SpreadSpec of blend_pictures(spread=dict(...)), checked as h264bsdmiBlendCurrentPicturesSpread checks it"""
+    if not isinstance(spread, dict) or set(spread) - {"gain", "lowest", "highest", "update"}:
+        raise ValueError(f"blend_pictures: spread is None or a dict of gain, lowest, highest, update, not {spread}")
+    gain, lowest, highest, update = spread.get("gain", 2), spread.get("lowest", 2), spread.get("highest", 255), spread.get("update", "all")
+    if any(not isinstance(v, int) or isinstance(v, bool) for v in (gain, lowest, highest)) or not 1 <= gain <= 8 or not 0 <= lowest <= highest <= 255:
+        raise ValueError(f"blend_pictures: spread has gain 1..8 and 0 <= lowest <= highest <= 255, not {gain} {lowest} {highest}")
+    if update not in SPREAD_UPDATES:
+        raise ValueError(f"blend_pictures: spread update is one of {tuple(SPREAD_UPDATES)}, not {update}")
+    return SpreadSpec(gain, lowest, highest, SPREAD_UPDATES[update])
+
+
+def blend_pictures(decoders, shift=4, hold=255, moving_shift=None, count_moving=False, stream=None, spread=None):
     """h264bsdmiBlendCurrentPictures: the CURRENT picture of every decoder is blended into its kept picture, which becomes a running
     average — a background model that pull_change, pull_shift, pull_cells(against="kept") and pull_boxes read as they read a copied
     picture; one launch blends them all.  Per sample the state is S = 256 hi + lo (hi: the kept picture), T = 256 c + 128, and
@@ -1027,9 +1054,14 @@ def blend_pictures(decoders, shift=4, hold=255, moving_shift=None, count_moving=
     are).  A decoder without a kept picture starts its model with a copy.  count_moving: also the number of moving luma samples of
     every decoder's coded frame.  stream as for pull_tensor.  Returns (kept, blended, pic_ids): per decoder 1 when it had a current
     picture, 1 when that was blended into an existing kept picture (0: the model started), and the picId the kept picture now carries
-    — and with count_moving an int32 CUDA tensor [n] behind them."""
+    — and with count_moving an int32 CUDA tensor [n] behind them.
+    spread=dict(gain=2, lowest=2, highest=255, update="all" | "still" | "none"): h264bsdmiBlendCurrentPicturesSpread — beside the kept
+    picture a per-sample noise level V (one byte, read with pull_kept(spread=True)): a luma sample is moving when |c - hi| >
+    max(hold, V), and V takes one step a call towards min(255, gain |c - hi|), clamped to lowest..highest — on every sample, on the
+    still ones only, or not at all.  V reads as lowest until the first such call and after every plain keep."""
     import torch
     n = len(decoders)
+    vspec = None if spread is None else _spread_spec(spread)
     if moving_shift is None:
         moving_shift = shift
     elif moving_shift == "frozen":
@@ -1045,20 +1077,24 @@ def blend_pictures(decoders, shift=4, hold=255, moving_shift=None, count_moving=
     stream = _call_stream(stream)                       # (behind the fill: the legacy default stream is waited for)
     if n:
         spec = BlendSpec(shift, hold, moving_shift, moving.data_ptr() if count_moving else None)
-        rc = api_lib().h264bsdmiBlendCurrentPictures(n, (ctypes.c_void_p * n)(*[d._st for d in decoders]), ctypes.byref(spec), stream.cuda_stream,
-                                                     kept, blended, ids)
+        decs = (ctypes.c_void_p * n)(*[d._st for d in decoders])
+        if vspec is None:
+            rc = api_lib().h264bsdmiBlendCurrentPictures(n, decs, ctypes.byref(spec), stream.cuda_stream, kept, blended, ids)
+        else:
+            rc = api_lib().h264bsdmiBlendCurrentPicturesSpread(n, decs, ctypes.byref(spec), ctypes.byref(vspec), stream.cuda_stream, kept, blended, ids)
         if rc != 0:
-            raise RuntimeError(f"h264bsdmiBlendCurrentPictures failed ({rc})")
+            raise RuntimeError(f"h264bsdmiBlendCurrentPictures{'' if vspec is None else 'Spread'} failed ({rc})")
     res = (list(kept)[:n], list(blended)[:n], list(ids)[:n])
     return res + (moving,) if count_moving else res
 
 
-def pull_kept(decoders, fraction=False, stream=None):
+def pull_kept(decoders, fraction=False, spread=False, stream=None):
     """h264bsdmiOutputKeptPictures: the kept picture of every decoder (keep_pictures, blend_pictures) as the planar I420 coded frame —
     Y, Cb, Cr, what next_output_picture returns for a decoded picture — by one launch: to look at the background.  fraction=True:
     also the low byte of every sample of the background model in the same order (128 where a plain keep came last).  stream as for
     pull_tensor.  Returns per decoder a CUDA uint8 tensor [384 * macroblocks] (with fraction a pair of them), or None where it has no
-    kept picture."""
+    kept picture.  spread=True (h264bsdmiOutputKeptSpread, one more launch): per decoder a tuple, with the spread frame of
+    blend_pictures(spread=...) appended in the same order — or None in its place where the decoder has no valid spread."""
     import torch
     n = len(decoders)
     stream = _call_stream(stream)
@@ -1073,7 +1109,17 @@ def pull_kept(decoders, fraction=False, stream=None):
                                                    stream.cuda_stream, got, None)
         if rc != 0:
             raise RuntimeError(f"h264bsdmiOutputKeptPictures failed ({rc})")
-    return [None if not got[i] else (pics[i], fracs[i]) if fraction else pics[i] for i in range(n)]
+    res = [None if not got[i] else (pics[i], fracs[i]) if fraction else pics[i] for i in range(n)]
+    if not spread:
+        return res
+    with torch.cuda.stream(stream):
+        frames = [torch.empty((b,), dtype=torch.uint8, device="cuda") if b else None for b in sizes]
+    has = (ctypes.c_uint32 * max(n, 1))()
+    if n:
+        rc = api_lib().h264bsdmiOutputKeptSpread(n, (ctypes.c_void_p * n)(*[d._st for d in decoders]), ptrs(frames), stream.cuda_stream, has, None)
+        if rc != 0:
+            raise RuntimeError(f"h264bsdmiOutputKeptSpread failed ({rc})")
+    return [None if r is None else (r if isinstance(r, tuple) else (r,)) + (frames[i] if has[i] else None,) for i, r in enumerate(res)]
 
 
 def _warp_row_refused(row):
@@ -1352,13 +1398,13 @@ def pull_corners(decoders, regions=None, score="min_eigen", block=3, nms=3, max_
 
 class CellMaps:
     """what pull_cells returns: maps [R, P, rows, cols] int32, the C layout, and views of it by name: count [R, rows, cols]; per
-    requested plane (PICTURE: sum, sumsq, min, max; CHANGE: sad, ssd, dsum, dmax, above) [R, C, rows, cols]; a plane of the mode that
+    requested plane (PICTURE: sum, sumsq, min, max; CHANGE: sad, ssd, dsum, dmax, above; SPREAD: fore, excess, spread) [R, C, rows, cols]; a plane of the mode that
     was not requested is None.  got [R], and per decoder current, kept, pic_id, kept_pic_id, lists of ints"""
 
     def __init__(self, maps, mode, C, planes, got, current, kept, pic_id, kept_pic_id):
         self.maps, self.mode, self.planes = maps, mode, planes
         at = 0
-        for name, bit in CELL_PLANES[mode].items():
+        for name, bit in CELL_MODE_PLANES[mode].items():
             width = 0 if not planes & bit else 1 if bit == 1 else C
             view = None if not width else maps[:, at] if bit == 1 else maps[:, at:at + C]
             setattr(self, name, view)
@@ -1369,19 +1415,21 @@ class CellMaps:
 def _cells_args(who, decoders, regions, cell, grid, source, planes, against, threshold, crop, keep):
     """the argument checks and the grid of pull_cells, for it and for pull_boxes -> (mode, src, C, bits, thr, K, regs, grid)"""
     n = len(decoders)
-    if against not in (None, "kept"):
-        raise ValueError(f"{who}: against is None or 'kept', not {against}")
-    mode = 1 if against == "kept" else 0
+    if not (against is None or isinstance(against, str)) or against not in CELL_AGAINST:
+        raise ValueError(f"{who}: against is None, 'kept' or 'spread', not {against}")
+    mode = CELL_AGAINST[against]
     if source not in STATS_SOURCES or cell not in CELL_SIZES:
         raise ValueError(f"{who}: unsupported source / cell {source} {cell}")
     src, C = STATS_SOURCES[source]
     names = (planes,) if isinstance(planes, str) else tuple(planes)
-    if not names or any(p not in CELL_PLANES[mode] for p in names):
-        raise ValueError(f"{who}: planes is a non-empty choice of {tuple(CELL_PLANES[mode])}, not {planes}")
-    bits = sum({CELL_PLANES[mode][p] for p in names})
+    if not names or any(p not in CELL_MODE_PLANES[mode] for p in names):
+        raise ValueError(f"{who}: planes is a non-empty choice of {tuple(CELL_MODE_PLANES[mode])}, not {planes}")
+    bits = sum({CELL_MODE_PLANES[mode][p] for p in names})
     thr = _thresholds(who, threshold, C)
     if not mode and (any(thr) or keep):
         raise ValueError(f"{who}: threshold and keep need against='kept'")
+    if mode == 2 and (keep or source == "rgb"):
+        raise ValueError(f"{who}: against='spread' has sources 'y' and 'ycbcr' and no keep (a plain keep would invalidate the spread it read)")
     K, regs = _regions_arg(who, n, regions)
     if grid is None:
         if regs is not None:
@@ -1404,7 +1452,9 @@ def pull_cells(decoders, regions=None, cell=16, grid=None, source="y", planes=("
     grid: (rows, cols) of every slice; None: (ceil(h / cell), ceil(w / cell)) of the largest box (regions=None: source window) of the
     call.  against=None: statistics of the picture, planes out of "count", "sum", "sumsq", "min", "max"; against="kept": of d = current -
     kept picture (keep_pictures), planes out of "count", "sad", "ssd", "dsum", "dmax", "above" (#|d| > threshold: one int 0..255 or one
-    per channel); keep=True: behind the comparison the current pictures become the kept ones, as for pull_change.  Cell (i, j) of a
+    per channel); against="spread": of |d| against t = max(threshold, V) per sample, V the spread of blend_pictures(spread=...), planes
+    out of "count", "fore" (#|d| > t), "excess" (sum of max(0, |d| - t)), "spread" (sum of V); sources "y" and "ycbcr", no keep, and
+    got[r] = 0 without a valid spread; keep=True: behind the comparison the current pictures become the kept ones, as for pull_change.  Cell (i, j) of a
     region holds what pull_stats / pull_change give for the box (x + j cell, y + i cell, min(cell, w - j cell), min(cell, h - i cell));
     cells the box or the window do not reach have count 0.  out: a contiguous CUDA int32 tensor [R, P, rows, cols] to write into;
     slices of decoders without a current (against="kept": or kept) picture are left untouched (got[r] = 0).  Returns a CellMaps."""
@@ -1807,7 +1857,7 @@ def pull_boxes(decoders, regions=None, cell=16, grid=None, source="y", planes=("
     if boxes_out.device != out.device:
         raise ValueError("pull_boxes: out and boxes_out must be on the same device")
     spec = CellsSpec(out.data_ptr(), grid[1], grid[0], cell, src, 1 if crop else 0, mode, bits, (ctypes.c_uint32 * 3)(*thr), 1 if keep else 0)
-    bspec = BoxesSpec(boxes_out.data_ptr(), max_boxes, CELL_PLANES[mode][plane], channel, BOXES_SENSES[sense], level, connectivity, min_cells)
+    bspec = BoxesSpec(boxes_out.data_ptr(), max_boxes, CELL_MODE_PLANES[mode][plane], channel, BOXES_SENSES[sense], level, connectivity, min_cells)
     res = _kept_pull("h264bsdmiOutputCellBoxes", decoders, K, regs, (ctypes.byref(spec), ctypes.byref(bspec)), stream, n > 0 and K > 0)
     instances = [r.instance for r in regs[:K]] if regs is not None else list(range(K))
     return CellBoxes(CellMaps(out, mode, C, bits, *res), boxes_out, instances, stream)

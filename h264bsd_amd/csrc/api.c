@@ -42,6 +42,9 @@ typedef struct ApiDec {
      * of another size is configured, and h264bsdDecode forgets it for good when it sees the size change */
     int has_kept;
     u32 kept_id, kept_wmb, kept_hmb;
+    /* the spread beside it (h264bsdmiBlendCurrentPicturesSpread): valid from a spread blend to the next plain keep, and only while the
+     * kept picture counts (has_spread) */
+    int spread_valid;
 } ApiDec;
 
 /* Every H264BSDMI_* variable this library reads (tests/test_abi.py compares the list with the sources and INTEGRATION.md).  A
@@ -65,6 +68,7 @@ __attribute__((constructor)) static void report_unknown_switches(void)
 static ApiDec *dec_of(storage_t *s) { return s ? (ApiDec *)s->opaque : NULL; }
 static void drop_current(ApiDec *a) { if (a) a->has_cur = 0; }
 static int has_kept_picture(const ApiDec *a) { return a->has_kept && a->kept_wmb == a->hd->width_mbs && a->kept_hmb == a->hd->height_mbs; }
+static int has_spread(const ApiDec *a) { return has_kept_picture(a) && a->spread_valid; }
 
 /* ---- capture sink ---- */
 static int cap_configure(void *u, uint32_t w, uint32_t h, uint32_t n) { (void)u; (void)w; (void)h; (void)n; return 0; }
@@ -130,7 +134,7 @@ u32 h264bsdDecode(storage_t *s, u8 *byteStrm, u32 len, u32 picId, u32 *readBytes
     if (!a || !byteStrm || !len || !readBytes) return H264BSD_ERROR;
     a->fed = 1;
     const u32 r = (u32)hd_decode(a->hd, byteStrm, len, picId, readBytes);
-    if (a->has_kept && !has_kept_picture(a)) a->has_kept = 0;          /* a sequence of another coded size: the kept picture is gone */
+    if (a->has_kept && !has_kept_picture(a)) a->has_kept = a->spread_valid = 0;      /* a sequence of another coded size: the kept picture is gone, and its spread */
     return r;
 }
 
@@ -384,6 +388,7 @@ typedef struct CurrentPull {
     SinkRemap *maps;
     int kind;                   /* PULL_* */
     int vs_kept;                /* only instances that have a kept picture too: PULL_CHANGE, PULL_SHIFT, PULL_FLOW, PULL_MATCHES, and PULL_CELLS / PULL_BOXES in CHANGE mode */
+    int vs_spread;              /* ... and a valid spread: PULL_CELLS / PULL_BOXES in SPREAD mode */
 } CurrentPull;
 
 /* regions == NULL: no regions at all, or (whole: one whole window per instance) exactly n */
@@ -431,7 +436,7 @@ static int pull_begin(CurrentPull *c, u32 n, storage_t *const *dec, u32 n_items,
     }
     *c = (CurrentPull){ n, 0, 0, dec, (SinkTensorPic *)malloc((n ? n : 1) * sizeof(SinkTensorPic)), (u32 *)malloc((n ? n : 1) * sizeof(u32)),
                         kind == PULL_REMAP ? NULL : (SinkRegion *)malloc((n_items ? n_items : 1) * sizeof(SinkRegion)),
-                        kind == PULL_REMAP ? (SinkRemap *)malloc((n_items ? n_items : 1) * sizeof(SinkRemap)) : NULL, kind, kind == PULL_CHANGE || kind == PULL_SHIFT };
+                        kind == PULL_REMAP ? (SinkRemap *)malloc((n_items ? n_items : 1) * sizeof(SinkRemap)) : NULL, kind, kind == PULL_CHANGE || kind == PULL_SHIFT, 0 };
     if (!c->pics || !c->pic_of || !(c->regs || c->maps)) { pull_free(c); return -1; }
     for (u32 i = 0; i < n; i++) c->pic_of[i] = NO_PIC;
     return 0;
@@ -443,6 +448,7 @@ static u32 pull_pic(CurrentPull *c, u32 inst, const h264bsdmi_tensor_spec *spec,
     const ApiDec *a = dec_of(c->dec[inst]);
     if (!a->has_cur || !a->hd->active_sps) return NO_PIC;
     if (c->vs_kept && !has_kept_picture(a)) return NO_PIC;
+    if (c->vs_spread && !has_spread(a)) return NO_PIC;
     if (c->pic_of[inst] == NO_PIC) {
         c->pic_of[inst] = c->m;
         tensor_pic(&c->pics[c->m++], a, a->cur.slot, inst, spec, colour);
@@ -587,11 +593,13 @@ static int keep_begin(CurrentPull *c, u32 n, storage_t *const *dec)
     for (u32 i = 0; i < n; i++) (void)pull_pic(c, i, &KEEP_WINDOW, &REFERENCE_COLOUR);
     return 0;
 }
-static void mark_kept(const CurrentPull *c)
+/* plain: a copy (the keep call, a keep_after), which invalidates the spread as it resets the fraction; a blend leaves it */
+static void mark_kept(const CurrentPull *c, int plain)
 {
     for (u32 i = 0; i < c->n; i++) {
         ApiDec *a = dec_of(c->dec[i]);
         if (c->pic_of[i] == NO_PIC) continue;
+        if (plain) a->spread_valid = 0;
         a->has_kept = 1;
         a->kept_id = a->cur.pic_id;
         a->kept_wmb = a->hd->width_mbs;
@@ -607,7 +615,7 @@ int h264bsdmiKeepCurrentPictures(u32 n, storage_t *const *dec, void *stream, u32
     if (!kept || keep_begin(&c, n, dec)) return -1;
     const int failed = c.m && c.pics[0].sink->keep_pictures(c.m, c.pics, stream);
     if (!failed) {
-        mark_kept(&c);
+        mark_kept(&c, 1);
         for (u32 i = 0; i < n; i++) {
             const ApiDec *a = dec_of(dec[i]);
             kept[i] = c.pic_of[i] != NO_PIC;
@@ -619,50 +627,73 @@ int h264bsdmiKeepCurrentPictures(u32 n, storage_t *const *dec, void *stream, u32
 }
 
 /* The current picture of each instance blended into its kept picture (the background model); where it has none, the model starts as a
- * copy.  keep_begin and mark_kept are the keep call's; fresh: per picture, what the sink is told of the instance's kept picture */
-int h264bsdmiBlendCurrentPictures(u32 n, storage_t *const *dec, const h264bsdmi_blend_spec *spec, void *stream,
-                                  u32 *kept, u32 *blended, u32 *picId)
+ * copy.  keep_begin and mark_kept are the keep call's; flags: per picture, what the sink is told of the instance's kept picture
+ * (ENG_SPREAD_FRESH: there is none) and, with a spread spec, of its spread (ENG_SPREAD_UNSET: none that is valid).  spread NULL: the
+ * plain blend through the sink's blend_pictures; else the engine's blend_spread entry (engine.h), behind which the spread is valid */
+static int blend_call(u32 n, storage_t *const *dec, const h264bsdmi_blend_spec *spec, const h264bsdmi_spread_spec *spread, void *stream,
+                      u32 *kept, u32 *blended, u32 *picId)
 {
     CurrentPull c;
-    if (!n) return 0;
     if (!spec || spec->shift > 7 || spec->hold > 255 || (spec->moving_shift > 7 && spec->moving_shift != H264BSDMI_BLEND_FROZEN)) return -1;
     if (!kept || keep_begin(&c, n, dec)) return -1;
-    u32 *fresh = (u32 *)malloc(n * sizeof(u32));
-    int refused = !fresh;
+    u32 *flags = (u32 *)malloc(n * sizeof(u32));
+    int refused = !flags;
     for (u32 i = 0; i < n && !refused; i++) {
-        refused = !dec_of(dec[i])->hd->sink.blend_pictures;
-        if (c.pic_of[i] != NO_PIC) fresh[c.pic_of[i]] = !has_kept_picture(dec_of(dec[i]));
+        const ApiDec *a = dec_of(dec[i]);
+        const EngSinkEntries *entries = spread ? sink_entries(&a->hd->sink) : NULL;
+        refused = spread ? !entries || !entries->blend_spread : !a->hd->sink.blend_pictures;
+        if (c.pic_of[i] != NO_PIC)
+            flags[c.pic_of[i]] = (has_kept_picture(a) ? 0u : ENG_SPREAD_FRESH) | (spread && !has_spread(a) ? ENG_SPREAD_UNSET : 0u);
     }
-    if (refused) { free(fresh); pull_free(&c); return -1; }
-    const int failed = c.m && c.pics[0].sink->blend_pictures(c.m, c.pics, fresh, spec, n, stream);
+    if (refused) { free(flags); pull_free(&c); return -1; }
+    const int failed = c.m && (spread ? sink_entries(c.pics[0].sink)->blend_spread(c.m, c.pics, flags, spec, spread, n, stream)
+                                      : c.pics[0].sink->blend_pictures(c.m, c.pics, flags, spec, n, stream));
     if (!failed) {
         for (u32 i = 0; i < n; i++) {
             kept[i] = c.pic_of[i] != NO_PIC;
-            if (blended) blended[i] = kept[i] && !fresh[c.pic_of[i]];
+            if (blended) blended[i] = kept[i] && !(flags[c.pic_of[i]] & ENG_SPREAD_FRESH);
         }
-        mark_kept(&c);
-        for (u32 i = 0; picId && i < n; i++) {
-            const ApiDec *a = dec_of(dec[i]);
-            picId[i] = has_kept_picture(a) ? a->kept_id : 0;
+        mark_kept(&c, 0);
+        for (u32 i = 0; i < n; i++) {
+            ApiDec *a = dec_of(dec[i]);
+            if (spread && c.pic_of[i] != NO_PIC) a->spread_valid = 1;
+            if (picId) picId[i] = has_kept_picture(a) ? a->kept_id : 0;
         }
     }
-    free(fresh);
+    free(flags);
     pull_free(&c);
     return failed ? -2 : 0;
 }
+int h264bsdmiBlendCurrentPictures(u32 n, storage_t *const *dec, const h264bsdmi_blend_spec *spec, void *stream,
+                                  u32 *kept, u32 *blended, u32 *picId)
+{
+    if (!n) return 0;
+    return blend_call(n, dec, spec, NULL, stream, kept, blended, picId);
+}
+/* ... and with the spread beside the kept picture: the moving test d > max(hold, V), V stepped towards gain d */
+int h264bsdmiBlendCurrentPicturesSpread(u32 n, storage_t *const *dec, const h264bsdmi_blend_spec *spec, const h264bsdmi_spread_spec *spread,
+                                        void *stream, u32 *kept, u32 *blended, u32 *picId)
+{
+    if (!n) return 0;
+    if (!spread || spread->gain < 1 || spread->gain > 8 || spread->highest > 255 || spread->lowest > spread->highest ||
+        spread->update > H264BSDMI_SPREAD_STILL) return -1;
+    return blend_call(n, dec, spec, spread, stream, kept, blended, picId);
+}
 
-/* The kept pictures of the instances that have one, as planar I420 coded frames, and their fractions */
-int h264bsdmiOutputKeptPictures(u32 n, storage_t *const *dec, void *const *picture, void *const *fraction, void *stream,
-                                u32 *got, u32 *keptPicId)
+/* The kept pictures of the instances that have one, as planar I420 coded frames, and their fractions; or (spread_only) the spreads of
+ * the instances that have a valid one, through the engine's kept_spread_out entry */
+static int kept_out_call(u32 n, storage_t *const *dec, void *const *picture, void *const *fraction, int spread_only, void *stream,
+                         u32 *got, u32 *keptPicId)
 {
     if (!n) return 0;
     if (!dec || !picture || !got) return -1;
     for (u32 i = 0; i < n; i++) {
         const ApiDec *a = dec_of(dec[i]);
         if (!a || !a->hd->sink.kept_pictures_out) return -1;
+        if (spread_only && (!sink_entries(&a->hd->sink) || !sink_entries(&a->hd->sink)->kept_spread_out)) return -1;
         for (u32 k = 0; k < i; k++)
             if (dec[k] == dec[i]) return -1;
-        if (!has_kept_picture(a)) continue;
+        if (!(spread_only ? has_spread(a) : has_kept_picture(a))) continue;
         if (!picture[i] || ((uintptr_t)picture[i] & 15u) || (fraction && ((uintptr_t)fraction[i] & 15u))) return -1;
     }
     SinkTensorPic *pics = (SinkTensorPic *)calloc(n, sizeof(SinkTensorPic));
@@ -671,21 +702,31 @@ int h264bsdmiOutputKeptPictures(u32 n, storage_t *const *dec, void *const *pictu
     u32 m = 0;
     for (u32 i = 0; i < n; i++) {
         const ApiDec *a = dec_of(dec[i]);
-        if (!has_kept_picture(a)) continue;
+        if (!(spread_only ? has_spread(a) : has_kept_picture(a))) continue;
         pics[m].sink = &a->hd->sink;
         pics[m].index = i;
         bufs[m] = picture[i];
         bufs[n + m] = fraction ? fraction[i] : NULL;
         m++;
     }
-    const int failed = m && pics[0].sink->kept_pictures_out(m, pics, bufs, bufs + n, stream);
+    const int failed = m && (spread_only ? sink_entries(pics[0].sink)->kept_spread_out(m, pics, bufs, stream)
+                                         : pics[0].sink->kept_pictures_out(m, pics, bufs, bufs + n, stream));
     for (u32 i = 0; !failed && i < n; i++) {
         const ApiDec *a = dec_of(dec[i]);
-        got[i] = has_kept_picture(a) ? 1 : 0;
+        got[i] = (spread_only ? has_spread(a) : has_kept_picture(a)) ? 1 : 0;
         if (keptPicId) keptPicId[i] = has_kept_picture(a) ? a->kept_id : 0;
     }
     free(pics); free(bufs);
     return failed ? -2 : 0;
+}
+int h264bsdmiOutputKeptPictures(u32 n, storage_t *const *dec, void *const *picture, void *const *fraction, void *stream,
+                                u32 *got, u32 *keptPicId)
+{
+    return kept_out_call(n, dec, picture, fraction, 0, stream, got, keptPicId);
+}
+int h264bsdmiOutputKeptSpread(u32 n, storage_t *const *dec, void *const *spread, void *stream, u32 *got, u32 *keptPicId)
+{
+    return kept_out_call(n, dec, spread, NULL, 1, stream, got, keptPicId);
 }
 
 /* The kept pictures of the instances that have one resampled in place through an affine map each.  The checks in the keep call's order
@@ -737,7 +778,7 @@ int h264bsdmiWarpKeptPictures(u32 n, storage_t *const *dec, const h264bsdmi_warp
 
 /* The host path of the pulls that may compare against kept pictures and may keep afterwards, behind their own spec checks:
  * h264bsdmiOutputRegionChange (PULL_CHANGE), h264bsdmiOutputRegionShift (PULL_SHIFT), h264bsdmiOutputCellMaps (PULL_CELLS) and
- * h264bsdmiOutputCellBoxes (PULL_BOXES, spec2 its boxes spec), h264bsdmiOutputCellShift (PULL_FLOW), h264bsdmiOutputPointMatches (PULL_MATCHES).  vs_kept: only instances that have a kept picture too; max_side: the
+ * h264bsdmiOutputCellBoxes (PULL_BOXES, spec2 its boxes spec), h264bsdmiOutputCellShift (PULL_FLOW), h264bsdmiOutputPointMatches (PULL_MATCHES).  vs_kept: only instances that have a kept picture too (2: and a valid spread); max_side: the
  * longest side a region may have (0: whatever regions_refused allows); keep_after: behind the sink's entry the keep call's launch for
  * every instance with a current picture.  kept / keptPicId are what the comparison saw; -2 writes nothing, marks nothing */
 static int kept_pull(int kind, int vs_kept, u32 n, storage_t *const *dec, u32 nRegions, const h264bsdmi_region *regions, u32 max_side,
@@ -749,7 +790,8 @@ static int kept_pull(int kind, int vs_kept, u32 n, storage_t *const *dec, u32 nR
     for (u32 r = 0; max_side && regions && r < nRegions; r++)
         if (regions[r].w > max_side || regions[r].h > max_side) return -1;
     if (pull_begin(&c, n, dec, nRegions, kind)) return -1;
-    c.vs_kept = vs_kept;            /* (pull_begin knows it of PULL_CHANGE and PULL_SHIFT; the cells have it from their mode) */
+    c.vs_kept = vs_kept != 0;       /* (pull_begin knows it of PULL_CHANGE and PULL_SHIFT; the cells have it from their mode) */
+    c.vs_spread = vs_kept == 2;
     for (u32 i = 0; vs_kept && i < n; i++)
         if (!dec_of(dec[i])->hd->sink.keep_pictures) { pull_free(&c); return -1; }
     if (keep_after && keep_begin(&k, n, dec)) { pull_free(&c); return -1; }
@@ -774,7 +816,7 @@ static int kept_pull(int kind, int vs_kept, u32 n, storage_t *const *dec, u32 nR
             if (kept) kept[i] = has_kept_picture(a) ? 1 : 0;
             if (keptPicId) keptPicId[i] = has_kept_picture(a) ? a->kept_id : 0;
         }
-        if (keep_after) mark_kept(&k);
+        if (keep_after) mark_kept(&k, 1);
     }
     if (keep_after) pull_free(&k);
     return pull_finish(&c, failed, nRegions, got, NULL, current, picId);
@@ -806,13 +848,16 @@ int h264bsdmiOutputRegionShift(u32 n, storage_t *const *dec, u32 nRegions, const
  * regions: the host path of the one or of the other, the mode carried by CurrentPull.vs_kept */
 static int cells_spec_refused(const h264bsdmi_cells_spec *s)
 {
-    const u32 allowed = s && s->mode == H264BSDMI_CELLS_CHANGE
+    const u32 allowed = s && s->mode == H264BSDMI_CELLS_SPREAD
+        ? H264BSDMI_CELL_COUNT | H264BSDMI_CELL_FORE | H264BSDMI_CELL_EXCESS | H264BSDMI_CELL_SPREADSUM
+        : s && s->mode == H264BSDMI_CELLS_CHANGE
         ? H264BSDMI_CELL_COUNT | H264BSDMI_CELL_SAD | H264BSDMI_CELL_SSD | H264BSDMI_CELL_DSUM | H264BSDMI_CELL_DMAX | H264BSDMI_CELL_ABOVE
         : H264BSDMI_CELL_COUNT | H264BSDMI_CELL_SUM | H264BSDMI_CELL_SUMSQ | H264BSDMI_CELL_MIN | H264BSDMI_CELL_MAX;
     if (!s || !s->data || ((uintptr_t)s->data & 3u)) return 1;
     if (!s->cols || s->cols > 4096u || !s->rows || s->rows > 4096u) return 1;
     if (s->cell != 4 && s->cell != 8 && s->cell != 16 && s->cell != 32 && s->cell != 64) return 1;
-    if (s->source > H264BSDMI_STATS_RGB || s->crop > 1 || s->mode > H264BSDMI_CELLS_CHANGE || s->keep_after > 1) return 1;
+    if (s->source > H264BSDMI_STATS_RGB || s->crop > 1 || s->mode > H264BSDMI_CELLS_SPREAD || s->keep_after > 1) return 1;
+    if (s->mode == H264BSDMI_CELLS_SPREAD && (s->source == H264BSDMI_STATS_RGB || s->keep_after)) return 1;     /* (a plain keep would invalidate what was just read) */
     if (!s->planes || (s->planes & ~allowed)) return 1;
     if (s->threshold[0] > 255 || s->threshold[1] > 255 || s->threshold[2] > 255) return 1;
     if (s->mode == H264BSDMI_CELLS_PICTURE && (s->threshold[0] || s->threshold[1] || s->threshold[2] || s->keep_after)) return 1;
@@ -835,7 +880,12 @@ static int cells_pull(int kind, u32 n, storage_t *const *dec, u32 nRegions, cons
                       u32 *got, u32 *current, u32 *kept, u32 *picId, u32 *keptPicId)
 {
     if (cells_spec_refused(spec) || (kind == PULL_BOXES && boxes_spec_refused(spec, boxes))) return -1;
-    return kept_pull(kind, spec->mode == H264BSDMI_CELLS_CHANGE, n, dec, nRegions, regions, 0, spec, boxes, spec->crop, spec->keep_after, stream,
+    /* SPREAD: CHANGE's path, for the instances that have a valid spread too (vs_kept 2), on an engine that has the spread entries */
+    for (u32 i = 0; spec->mode == H264BSDMI_CELLS_SPREAD && dec && i < n; i++) {
+        const ApiDec *a = dec_of(dec[i]);
+        if (a && (!sink_entries(&a->hd->sink) || !sink_entries(&a->hd->sink)->blend_spread)) return -1;
+    }
+    return kept_pull(kind, spec->mode == H264BSDMI_CELLS_SPREAD ? 2 : spec->mode == H264BSDMI_CELLS_CHANGE, n, dec, nRegions, regions, 0, spec, boxes, spec->crop, spec->keep_after, stream,
                      got, current, kept, picId, keptPicId);
 }
 int h264bsdmiOutputCellMaps(u32 n, storage_t *const *dec, u32 nRegions, const h264bsdmi_region *regions,

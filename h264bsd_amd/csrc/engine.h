@@ -42,9 +42,22 @@ int  eng_device_cpus(int device, int *cpus, int max);
  *               H264BSDMI_WARP_CURRENT, filled from the current picture in pics[i].slot where the source was outside (under REPLICATE
  *               the slot is not looked at: no frame buffer is read).  spec->maps is the caller's list and is not looked at; spec->count:
  *               n_count words, zeroed on the stream ahead of the launch, picture i counts into word pics[i].index.  Called through the
- *               table of any of the n sinks.  0 = ok; <0 = error, nothing enqueued */
+ *               table of any of the n sinks.  0 = ok; <0 = error, nothing enqueued
+ *   blend_spread  h264bsdmiBlendCurrentPicturesSpread: JobSink.blend_pictures with the spread beside the kept picture: the n pictures
+ *               (distinct instances of one device) blended into their kept pictures under the moving test d > max(hold, V), and V, a
+ *               third frame per instance that the engine allocates at the first call, stepped as `spread` says, with one launch.
+ *               flags[i]: ENG_SPREAD_FRESH — api.c knows no kept picture of the coded size: the model starts; ENG_SPREAD_UNSET — it
+ *               knows no valid spread: V reads as spread->lowest.  spec->moving, n_moving and the return value as for blend_pictures
+ *   kept_spread_out  h264bsdmiOutputKeptSpread: the spread of every pics[i].sink (distinct instances of one device; each holds a
+ *               kept picture of its coded size and a valid spread) as the planar I420 coded frame into spread[i], with one launch.
+ *               0 = ok; <0 = error, nothing enqueued
+ * The cell maps' H264BSDMI_CELLS_SPREAD travels through JobSink.cell_maps / cell_boxes; api.c lets it through only where the table
+ * carries blend_spread: an engine without the entry has no spread to read. */
+#define ENG_SPREAD_FRESH 1u
+#define ENG_SPREAD_UNSET 2u
 struct h264bsdmi_warp_map;
 struct h264bsdmi_warp_spec;
+struct h264bsdmi_spread_spec;
 typedef struct EngSinkEntries {
     int (*cell_shift)(uint32_t n, const SinkTensorPic *pics, uint32_t n_regions, const SinkRegion *regions,
                       const struct h264bsdmi_cell_shift_spec *spec, void *stream);
@@ -53,6 +66,9 @@ typedef struct EngSinkEntries {
     int (*point_model)(const JobSink *sink, uint32_t n_records, const struct h264bsdmi_model_spec *spec, void *stream);
     int (*warp_kept)(uint32_t n, const SinkTensorPic *pics, const struct h264bsdmi_warp_map *maps, const struct h264bsdmi_warp_spec *spec,
                      uint32_t n_count, void *stream);
+    int (*blend_spread)(uint32_t n, const SinkTensorPic *pics, const uint32_t *flags, const struct h264bsdmi_blend_spec *spec,
+                        const struct h264bsdmi_spread_spec *spread, uint32_t n_moving, void *stream);
+    int (*kept_spread_out)(uint32_t n, const SinkTensorPic *pics, void *const *spread, void *stream);
 } EngSinkEntries;
 const EngSinkEntries *eng_sink_entries(const JobSink *sink);
 

@@ -44,6 +44,7 @@
 #include "kernels/k_region_stats.hip.h"
 #include "kernels/k_keep.hip.h"
 #include "kernels/k_blend.hip.h"
+#include "kernels/k_blend_spread.hip.h"
 #include "kernels/k_warp_kept.hip.h"
 #include "kernels/k_region_change.hip.h"
 #include "kernels/k_region_shift.hip.h"
@@ -110,6 +111,10 @@ struct StreamCtx {
     /* the background model (h264bsdmiBlendCurrentPictures): the low byte of every sample of the kept picture, a second frame in the
      * same tiles, allocated at the instance's first blend and freed with d_kept; not valid (it reads as 0x80) after a plain keep */
     DeviceMem<uint8_t> d_kept_lo; bool kept_lo_valid = false;
+    /* the background spread (h264bsdmiBlendCurrentPicturesSpread): one byte per sample of the kept picture, a third frame in the same
+     * tiles, allocated at the instance's first spread blend and freed with d_kept; not valid (it reads as the call's `lowest`) after a
+     * plain keep.  A warp leaves it where it lies */
+    DeviceMem<uint8_t> d_spread; bool spread_valid = false;
     /* warped kept pictures (h264bsdmiWarpKeptPictures): the frames a warp writes, hi and (where lo is valid) lo, swapped with the live
      * ones behind its launch; allocated at the instance's first warp and freed with d_kept */
     DeviceMem<uint8_t> d_kept_spare, d_kept_lo_spare;
@@ -176,12 +181,12 @@ constexpr unsigned CONVERT_WGS = CONVERT_WGS_N;      /* workgroups per picture o
 constexpr uint32_t LANE_DBK_WAVES = LANE_DBK_WAVES_N;
 
 /* the item stride of the tensor pulls' staging ring: k_tensor_out / k_tensor_resize read TensorItems, k_tensor_aa AaItems, k_tensor_roi
- * RoiItems, k_motion_roi MotionItems, k_tensor_remap RemapItems, k_region_stats StatsItems, k_keep KeepItems, k_blend BlendItems, k_warp_kept WarpItems, k_kept_out KeptOutItems, k_region_change ChangeItems, k_region_shift ShiftItems, k_corner_points CornerItems,
+ * RoiItems, k_motion_roi MotionItems, k_tensor_remap RemapItems, k_region_stats StatsItems, k_keep KeepItems, k_blend BlendItems, k_blend_spread SpreadItems, k_warp_kept WarpItems, k_kept_out KeptOutItems, k_region_change ChangeItems, k_region_shift ShiftItems, k_corner_points CornerItems,
  * k_cell_maps CellItems (k_cell_boxes: the same, and its BoxItems in slots of their own behind them), k_cell_shift FlowItems,
  * k_point_describe / k_point_match MatchItems */
 constexpr size_t TITEM_BYTES = std::max({ sizeof(h264k::TensorItem), sizeof(h264k::AaItem), sizeof(h264k::RoiItem), sizeof(h264k::MotionItem),
                                           sizeof(h264k::RemapItem), sizeof(h264k::StatsItem), sizeof(h264k::KeepItem), sizeof(h264k::ChangeItem),
-                                          sizeof(h264k::CellItem), sizeof(h264k::BoxItem), sizeof(h264k::ShiftItem), sizeof(h264k::BlendItem),
+                                          sizeof(h264k::CellItem), sizeof(h264k::BoxItem), sizeof(h264k::ShiftItem), sizeof(h264k::BlendItem), sizeof(h264k::SpreadItem),
                                           sizeof(h264k::KeptOutItem), sizeof(h264k::CornerItem), sizeof(h264k::FlowItem), sizeof(h264k::MatchItem), sizeof(h264k::WarpItem) });
 struct TItemSlot { uint8_t bytes[TITEM_BYTES]; };
 struct Engine {
@@ -660,8 +665,8 @@ static void kept_drop(Engine *e, StreamCtx *s)
 {
     if (!s->d_kept) return;
     if (e->kept_recorded) (void)hipEventSynchronize(e->kept_ev);
-    s->d_kept.reset(); s->d_kept_lo.reset(); s->d_kept_spare.reset(); s->d_kept_lo_spare.reset();
-    s->kept_wmb = s->kept_hmb = 0; s->kept_lo_valid = false;
+    s->d_kept.reset(); s->d_kept_lo.reset(); s->d_kept_spare.reset(); s->d_kept_lo_spare.reset(); s->d_spread.reset();
+    s->kept_wmb = s->kept_hmb = 0; s->kept_lo_valid = false; s->spread_valid = false;
 }
 
 /* ---- motion export: the side information of a picture kept beside its frame buffer (kernels/k_motion.hip.h) ----
@@ -1460,7 +1465,7 @@ static bool kept_pictures_ok(uint32_t n, const SinkTensorPic *pics)
 /* What the item of region g reads: the frame of its picture, the kept picture of its instance (null without one), box ∩ window, the
  * window itself and the box's origin, which may be negative or beyond the frame, all in luma samples of the coded frame.  *tallest,
  * where the launch is banded, takes the clip's macroblock rows */
-struct RegionSource { const uint8_t *frame; const uint8_t *kept; uint32_t wmb; RegionClip c; uint32_t wx0, wy0, wx1, wy1; int32_t ox, oy; };
+struct RegionSource { const uint8_t *frame; const uint8_t *kept; uint32_t wmb; RegionClip c; uint32_t wx0, wy0, wx1, wy1; int32_t ox, oy; const uint8_t *spread; };
 static RegionSource region_source(const SinkTensorPic *pics, const SinkRegion &g, uint32_t *tallest = nullptr)
 {
     const SinkTensorPic &p = pics[g.pic];
@@ -1468,7 +1473,7 @@ static RegionSource region_source(const SinkTensorPic *pics, const SinkRegion &g
     const RegionClip c = region_clip(p, g);
     if (tallest) *tallest = std::max(*tallest, c.mb_rows);
     return RegionSource{ s->d_frames + (size_t)p.slot * s->frame_bytes, s->d_kept.get(), s->wmb, c, p.x0, p.y0, p.x0 + p.w, p.y0 + p.h,
-                         (int32_t)p.x0 + g.x, (int32_t)p.y0 + g.y };
+                         (int32_t)p.x0 + g.x, (int32_t)p.y0 + g.y, s->d_spread.get() };
 }
 /* the refusals every analysis pull makes behind those of its own spec: regions that fit grid.y, pictures, regions, and with vs_kept
  * the kept pictures */
@@ -1602,7 +1607,10 @@ static int keep_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, hip
     hipLaunchKernelGGL(h264k::k_keep, dim3(std::max(chunks, 1u), n), dim3(256), 0, st, e->titems.dev<h264k::KeepItem>());
     HIP_TRY(hipGetLastError());
     if (pull_end_locked(e, n, pics, st, fence_ev)) return -1;
-    for (uint32_t i = 0; i < n; i++) static_cast<SinkUser *>(pics[i].sink->user)->s->kept_lo_valid = false;      /* a copy: the fraction is 0x80 */
+    for (uint32_t i = 0; i < n; i++) {                                  /* a copy: the fraction is 0x80, the spread reads as `lowest` */
+        StreamCtx *s = static_cast<SinkUser *>(pics[i].sink->user)->s;
+        s->kept_lo_valid = false; s->spread_valid = false;
+    }
     return kept_order_end(e, st);
 }
 
@@ -1652,6 +1660,65 @@ static int blend_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, co
     HIP_TRY(hipGetLastError());
     if (pull_end_locked(e, n, pics, st, fence_ev)) return -1;
     for (uint32_t i = 0; i < n; i++) static_cast<SinkUser *>(pics[i].sink->user)->s->kept_lo_valid = true;
+    return kept_order_end(e, st);
+}
+
+/* h264bsdmiBlendCurrentPicturesSpread: blend_out_locked with ONE k_blend_spread launch, which beside d_kept and d_kept_lo reads and
+ * writes the instance's spread (d_spread, allocated here at the first spread blend).  flags[i]: ENG_SPREAD_* (engine.h) — what api.c
+ * knows of the instance's kept picture and of its spread; the engine adds what it knows itself (no buffer yet, a plain keep came
+ * last).  Behind the launch the spread of every instance of the call is valid. */
+static int blend_spread_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, const uint32_t *flags, const h264bsdmi_blend_spec &sp,
+                                   const h264bsdmi_spread_spec &vs, uint32_t n_moving, hipStream_t st, hipEvent_t *fence_ev)
+{
+    if (n > 65535u) return -1;                                          /* grid.y */
+    if (sp.shift > 7u || sp.hold > 255u || (sp.moving_shift > 7u && sp.moving_shift != H264BSDMI_BLEND_FROZEN)) return -1;
+    if (vs.gain < 1u || vs.gain > 8u || vs.highest > 255u || vs.lowest > vs.highest || vs.update > H264BSDMI_SPREAD_STILL) return -1;
+    if (!pull_pictures_ok(n, pics, true, false)) return -1;
+    for (uint32_t i = 0; i < n; i++) {
+        if (sp.moving && pics[i].index >= n_moving) return -1;
+        for (uint32_t k = 0; k < i; k++)
+            if (pics[k].sink == pics[i].sink) return -1;                /* one kept picture per instance */
+    }
+    if (pull_begin_locked(e, n, pics, n)) return -1;
+    if (kept_order_begin(e, st)) return -1;
+    h264k::SpreadItem *items = e->titems.host<h264k::SpreadItem>();
+    uint32_t largest = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        StreamCtx *s = static_cast<SinkUser *>(pics[i].sink->user)->s;
+        uint32_t f = flags[i] & ENG_SPREAD_FRESH ? (uint32_t)h264k::BLEND_FRESH : 0u;
+        if (flags[i] & ENG_SPREAD_UNSET) f |= h264k::BLEND_V_UNSET;
+        if (!s->d_kept) {
+            HIP_TRY(s->d_kept.alloc(s->frame_bytes));
+            s->kept_wmb = s->wmb; s->kept_hmb = s->hmb;
+            f |= h264k::BLEND_FRESH;
+        }
+        if (!s->d_kept_lo) {
+            s->kept_lo_valid = false;
+            HIP_TRY(s->d_kept_lo.alloc(s->frame_bytes));
+        }
+        if (!s->d_spread) {
+            s->spread_valid = false;
+            HIP_TRY(s->d_spread.alloc(s->frame_bytes));
+        }
+        if (!s->kept_lo_valid) f |= h264k::BLEND_LO_UNSET;
+        if (!s->spread_valid) f |= h264k::BLEND_V_UNSET;
+        items[i] = h264k::SpreadItem{ s->d_frames + (size_t)pics[i].slot * s->frame_bytes, s->d_kept.get(), s->d_kept_lo.get(), s->d_spread.get(),
+                                      s->frame_bytes, f, pics[i].index };
+        largest = std::max(largest, s->frame_bytes);
+    }
+    /* 16 tiles per workgroup and step, about four steps per workgroup */
+    const uint32_t chunks = std::min((largest / 384u + 63u) / 64u, h264k::BLEND_MAX_CHUNKS);
+    if (sp.moving) HIP_TRY(hipMemsetAsync(sp.moving, 0, (size_t)n_moving * sizeof(uint32_t), st));
+    if (pull_wait_pictures(e, n, pics, st)) return -1;
+    const h264k::SpreadArgs sargs{ e->titems.dev<h264k::SpreadItem>(), static_cast<uint32_t *>(sp.moving), sp.shift, sp.hold,
+                                   sp.moving_shift == H264BSDMI_BLEND_FROZEN ? h264k::BLEND_FROZEN : sp.moving_shift, vs.gain, vs.lowest, vs.highest, vs.update };
+    hipLaunchKernelGGL(h264k::k_blend_spread, dim3(std::max(chunks, 1u), n), dim3(256), 0, st, sargs);
+    HIP_TRY(hipGetLastError());
+    if (pull_end_locked(e, n, pics, st, fence_ev)) return -1;
+    for (uint32_t i = 0; i < n; i++) {
+        StreamCtx *s = static_cast<SinkUser *>(pics[i].sink->user)->s;
+        s->kept_lo_valid = true; s->spread_valid = true;
+    }
     return kept_order_end(e, st);
 }
 
@@ -1732,6 +1799,42 @@ static int kept_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, voi
         const StreamCtx *s = pic_stream(pics[i]);
         items[i] = h264k::KeptOutItem{ s->d_kept.get(), s->kept_lo_valid ? s->d_kept_lo.get() : nullptr, static_cast<uint8_t *>(picture[i]),
                                        fraction ? static_cast<uint8_t *>(fraction[i]) : nullptr, s->kept_wmb, s->kept_hmb };
+        largest = std::max(largest, s->kept_wmb * s->kept_hmb * 24u);
+    }
+    const uint32_t chunks = std::min((largest + 1023u) / 1024u, h264k::BLEND_MAX_CHUNKS);          /* about four 16-byte pieces per lane */
+    hipLaunchKernelGGL(h264k::k_kept_out, dim3(std::max(chunks, 1u), n), dim3(256), 0, st, e->titems.dev<h264k::KeptOutItem>());
+    HIP_TRY(hipGetLastError());
+    if (pull_end_locked(e, n, pics, st, fence_ev)) return -1;
+    return kept_order_end(e, st);
+}
+
+/* every picture's instance has, beside the kept picture, a valid spread (api.c names only instances that have one) */
+static bool spread_frames_ok(uint32_t n, const SinkTensorPic *pics)
+{
+    for (uint32_t i = 0; i < n; i++) {
+        const StreamCtx *s = pic_stream(pics[i]);
+        if (!s->d_spread || !s->spread_valid) return false;
+    }
+    return kept_pictures_ok(n, pics);
+}
+
+/* h264bsdmiOutputKeptSpread: kept_out_locked's launch with the spread in the place of hi and no fraction: k_kept_out as it stands */
+static int kept_spread_out_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, void *const *spread, hipStream_t st, hipEvent_t *fence_ev)
+{
+    if (n > 65535u || !spread) return -1;                               /* grid.y */
+    for (uint32_t i = 0; i < n; i++) {
+        if (!spread[i] || (reinterpret_cast<uintptr_t>(spread[i]) & 15u)) return -1;
+        for (uint32_t k = 0; k < i; k++)
+            if (pics[k].sink == pics[i].sink) return -1;
+    }
+    if (!spread_frames_ok(n, pics)) return -1;
+    HIP_TRY(e->titems.reserve(n, 256));
+    if (kept_order_begin(e, st)) return -1;
+    h264k::KeptOutItem *items = e->titems.host<h264k::KeptOutItem>();
+    uint32_t largest = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        const StreamCtx *s = pic_stream(pics[i]);
+        items[i] = h264k::KeptOutItem{ s->d_spread.get(), nullptr, static_cast<uint8_t *>(spread[i]), nullptr, s->kept_wmb, s->kept_hmb };
         largest = std::max(largest, s->kept_wmb * s->kept_hmb * 24u);
     }
     const uint32_t chunks = std::min((largest + 1023u) / 1024u, h264k::BLEND_MAX_CHUNKS);          /* about four 16-byte pieces per lane */
@@ -1829,13 +1932,14 @@ struct CellsLaunch { const void *fn; dim3 grid; h264k::CellArgs args; bool chang
 static int cells_prepare_locked(Engine *e, uint32_t n, const SinkTensorPic *pics, uint32_t n_regs, const SinkRegion *regs,
                                 const h264bsdmi_cells_spec &sp, uint32_t extra, CellsLaunch *L)
 {
-    const bool change = sp.mode == H264BSDMI_CELLS_CHANGE;
+    const bool spread = sp.mode == H264BSDMI_CELLS_SPREAD, change = sp.mode == H264BSDMI_CELLS_CHANGE || spread;   /* change: kept pictures are read */
     if (!sp.data || (reinterpret_cast<uintptr_t>(sp.data) & 3u)) return -1;
-    if (sp.source > H264BSDMI_STATS_RGB || sp.crop > 1u || sp.mode > H264BSDMI_CELLS_CHANGE || sp.keep_after > 1u) return -1;
-    if (!sp.planes || (sp.planes & ~(change ? 63u : 31u))) return -1;
+    if (sp.source > H264BSDMI_STATS_RGB || sp.crop > 1u || sp.mode > H264BSDMI_CELLS_SPREAD || sp.keep_after > 1u) return -1;
+    if (!sp.planes || (sp.planes & ~(spread ? 15u : change ? 63u : 31u))) return -1;
+    if (spread && (sp.source == H264BSDMI_STATS_RGB || sp.keep_after)) return -1;
     if (sp.threshold[0] > 255u || sp.threshold[1] > 255u || sp.threshold[2] > 255u) return -1;
     if (!change && (sp.threshold[0] || sp.threshold[1] || sp.threshold[2] || sp.keep_after)) return -1;
-    if (!analysis_regions_ok(n, pics, n_regs, regs, change)) return -1;
+    if (!analysis_regions_ok(n, pics, n_regs, regs, change) || (spread && !spread_frames_ok(n, pics))) return -1;
     CellGrid G;
     if (!cell_grid(sp.cell, sp.cols, sp.rows, n_regs, CELLS_LIMITS, &G)) return -1;
     if (pull_begin_locked(e, n, pics, n_regs + extra)) return -1;
@@ -1845,12 +1949,13 @@ static int cells_prepare_locked(Engine *e, uint32_t n, const SinkTensorPic *pics
     for (uint32_t r = 0; r < n_regs; r++) {
         const RegionSource s = region_source(pics, regs[r]);
         items[r] = h264k::CellItem{ s.frame, change ? s.kept : nullptr, static_cast<uint32_t *>(sp.data) + (size_t)regs[r].index * slice, s.wmb, s.ox, s.oy,
-                                    s.c.x0, s.c.y0, s.c.x1, s.c.y1 };
+                                    s.c.x0, s.c.y0, s.c.x1, s.c.y1, spread ? s.spread : nullptr };
     }
     const bool quad = sp.cell >= 16u;
-    const void *const fns[2][3] = {
+    const void *const fns[3][3] = {
         { cells_kernel<0, h264k::ST_Y>(quad), cells_kernel<0, h264k::ST_YCBCR>(quad), cells_kernel<0, h264k::ST_RGB>(quad) },
-        { cells_kernel<1, h264k::ST_Y>(quad), cells_kernel<1, h264k::ST_YCBCR>(quad), cells_kernel<1, h264k::ST_RGB>(quad) } };
+        { cells_kernel<1, h264k::ST_Y>(quad), cells_kernel<1, h264k::ST_YCBCR>(quad), cells_kernel<1, h264k::ST_RGB>(quad) },
+        { cells_kernel<2, h264k::ST_Y>(quad), cells_kernel<2, h264k::ST_YCBCR>(quad), nullptr } };                       /* SPREAD has no RGB */
     *L = CellsLaunch{ fns[sp.mode][sp.source], dim3(G.rects, n_regs),
                       { e->titems.dev<h264k::CellItem>(), sp.cols, sp.rows, G.shift, G.rects_x, sp.planes, { sp.threshold[0], sp.threshold[1], sp.threshold[2] } },
                       change, G.shift, channels };
@@ -2143,6 +2248,21 @@ int sink_warp_kept(uint32_t n, const SinkTensorPic *pics, const h264bsdmi_warp_m
         return warp_out_locked(e, n, pics, maps, *spec, n_count, st, fence_ev);
     });
 }
+/* EngSinkEntries.blend_spread (h264bsdmiBlendCurrentPicturesSpread) and kept_spread_out (h264bsdmiOutputKeptSpread) */
+int sink_blend_spread(uint32_t n, const SinkTensorPic *pics, const uint32_t *flags, const h264bsdmi_blend_spec *spec,
+                      const h264bsdmi_spread_spec *spread, uint32_t n_moving, void *stream)
+{
+    if (n && (!spec || !spread || !flags)) return -1;
+    return sink_tensor_call(n, pics, stream, [&](Engine *e, hipStream_t st, hipEvent_t *fence_ev) {
+        return blend_spread_out_locked(e, n, pics, flags, *spec, *spread, n_moving, st, fence_ev);
+    });
+}
+int sink_kept_spread_out(uint32_t n, const SinkTensorPic *pics, void *const *spread, void *stream)
+{
+    return sink_tensor_call(n, pics, stream, [&](Engine *e, hipStream_t st, hipEvent_t *fence_ev) {
+        return kept_spread_out_locked(e, n, pics, spread, st, fence_ev);
+    });
+}
 /* EngSinkEntries.point_model (h264bsdmiOutputPointModel): the first entry without pictures — the sink only names the engine, nothing is
  * staged (the kernel finds record r of the four arrays by its stride), no fence goes to an instance and no kept picture is touched, so
  * none of pull_begin_locked / pull_end_locked / the kept pictures' ordering applies.  One launch of a workgroup per record; without a
@@ -2228,7 +2348,7 @@ int eng_attach(JobSink *sink)
 /* engine.h: the entries behind the last member of JobSink, for a sink eng_attach has bound */
 const EngSinkEntries *eng_sink_entries(const JobSink *sink)
 {
-    static const EngSinkEntries entries = { sink_cell_shift, sink_point_matches, sink_point_model, sink_warp_kept };
+    static const EngSinkEntries entries = { sink_cell_shift, sink_point_matches, sink_point_model, sink_warp_kept, sink_blend_spread, sink_kept_spread_out };
     return sink && sink->configure == sink_configure ? &entries : nullptr;
 }
 

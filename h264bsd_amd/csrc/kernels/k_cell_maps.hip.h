@@ -1,5 +1,6 @@
-/* kernels/k_cell_maps.hip.h — dense per-cell maps of the quantities of k_region_stats (MODE 0, PICTURE) or k_region_change (MODE 1,
- * CHANGE) over a grid of square cells laid over a box (h264bsdmiOutputCellMaps): one u32 per cell and map, read from the macroblock
+/* kernels/k_cell_maps.hip.h — dense per-cell maps of the quantities of k_region_stats (MODE 0, PICTURE), of k_region_change (MODE 1,
+ * CHANGE), or of the change against the background spread (MODE 2, SPREAD: per sample and channel t = max(thr[c], V) with V the
+ * instance's spread byte, then #(|d| > t), the sum of max(0, |d| - t) and the sum of V; a third frame read the same way) over a grid of square cells laid over a box (h264bsdmiOutputCellMaps): one u32 per cell and map, read from the macroblock
  * tiles where the pictures lie.  Included by engine.hip after k_region_change.hip.h, whose arithmetic per dword it uses, with the
  * loader and the mask of region_common.hip.h (region_load, region_mask); like them, not part of the kernel sources that key the committed counter tables (srchash.py).
  *
@@ -28,9 +29,10 @@ constexpr uint32_t CELLS_RECT_W = 128, CELLS_RECT_H = 64;               /* luma 
 constexpr uint32_t CELLS_MAX_CELLS = (CELLS_RECT_W / 4) * (CELLS_RECT_H / 4);
 constexpr uint32_t CELLS_MAX_GRID = 4096, CELLS_MAX_WORKGROUPS = 1u << 23;
 
-/* one region: the two frames (kept: CHANGE only), the slice, the box's origin (ox, oy) in luma samples of the coded frame, which may
- * be negative or beyond the frame, and box ∩ window [x0, x1) x [y0, y1) in the same (x1 <= x0: empty) */
-struct CellItem { const uint8_t *cur; const uint8_t *kept; uint32_t *dst; uint32_t wmb; int32_t ox, oy; uint32_t x0, y0, x1, y1; };
+/* one region: the two frames (kept: CHANGE and SPREAD only), the slice, the box's origin (ox, oy) in luma samples of the coded frame,
+ * which may be negative or beyond the frame, box ∩ window [x0, x1) x [y0, y1) in the same (x1 <= x0: empty), and the spread frame of
+ * the instance (SPREAD only) */
+struct CellItem { const uint8_t *cur; const uint8_t *kept; uint32_t *dst; uint32_t wmb; int32_t ox, oy; uint32_t x0, y0, x1, y1; const uint8_t *spread; };
 /* cols x rows cells of side 1 << shift per slice; rects_x: rectangles per row of rectangles; planes: H264BSDMI_CELL_* */
 struct CellArgs { const CellItem *items; uint32_t cols, rows, shift, rects_x, planes, thr[3]; };
 
@@ -59,7 +61,7 @@ __device__ __forceinline__ void cells_lds_max(uint32_t *p, uint32_t v) { (void)_
 template <int MODE, int SRC, bool QUAD>
 __global__ __launch_bounds__(256) void k_cell_maps(CellArgs a)
 {
-    constexpr int C = SRC == ST_Y ? 1 : 3, NP = MODE ? 5 : 4;              /* planes per channel, plane q is bit 2 << q */
+    constexpr int C = SRC == ST_Y ? 1 : 3, NP = MODE == 2 ? 3 : MODE ? 5 : 4;      /* planes per channel, plane q is bit 2 << q */
     __shared__ uint32_t s_acc[CELLS_MAX_CELLS * NP * C];                    /* [channel][plane][cell row][cell column] */
     const CellItem it = a.items[blockIdx.y];
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
@@ -101,7 +103,9 @@ __global__ __launch_bounds__(256) void k_cell_maps(CellArgs a)
             }
             uint32_t va[C], vb[C];
             region_load<SRC>(it.cur + at, lane, va);
-            if constexpr (MODE == 1) region_load<SRC>(it.kept + at, lane, vb);
+            if constexpr (MODE >= 1) region_load<SRC>(it.kept + at, lane, vb);
+            [[maybe_unused]] uint32_t vv[C];
+            if constexpr (MODE == 2) region_load<SRC>(it.spread + at, lane, vv);
 #pragma unroll
             for (int c = 0; c < C; c++) {
                 const uint32_t base = (uint32_t)c * NP * ncell + at0;      /* (at0 may be one before its row: only at0 + 1 is used then) */
@@ -128,7 +132,7 @@ __global__ __launch_bounds__(256) void k_cell_maps(CellArgs a)
                             const uint32_t hi = cells_row_max<QUAD>(max(max(av & 255u, (av >> 8) & 255u), max((av >> 16) & 255u, av >> 24)));
                             if (commit[p]) cells_lds_max(acc + 3u * ncell, hi);
                         }
-                    } else {
+                    } else if constexpr (MODE == 1) {
                         const uint32_t bv = vb[c] & pm[p];
                         uint32_t ad = 0u, hi = 0u, ab = 0u;
 #pragma unroll
@@ -158,6 +162,28 @@ __global__ __launch_bounds__(256) void k_cell_maps(CellArgs a)
                         if (planes & 32u) {
                             ab = cells_row_sum<QUAD>(ab);
                             if (commit[p]) region_lds_add(acc + 4u * ncell, ab);
+                        }
+                    } else {                                                /* SPREAD: the threshold of a sample is max(thr[c], V) */
+                        const uint32_t bv = vb[c] & pm[p], sv = vv[c] & pm[p];
+                        uint32_t fore = 0u, excess = 0u;
+#pragma unroll
+                        for (int k = 0; k < 4; k++) {
+                            const int x = (int)((av >> (8 * k)) & 255u), y = (int)((bv >> (8 * k)) & 255u);
+                            const uint32_t d = (uint32_t)(x > y ? x - y : y - x), t = max(thr[c], (sv >> (8 * k)) & 255u);
+                            fore += d > t ? 1u : 0u;
+                            excess += d > t ? d - t : 0u;
+                        }
+                        if (planes & 2u) {
+                            fore = cells_row_sum<QUAD>(fore);
+                            if (commit[p]) region_lds_add(acc, fore);
+                        }
+                        if (planes & 4u) {
+                            excess = cells_row_sum<QUAD>(excess);
+                            if (commit[p]) region_lds_add(acc + ncell, excess);
+                        }
+                        if (planes & 8u) {
+                            const uint32_t g = cells_row_sum<QUAD>(__builtin_amdgcn_udot4(sv, 0x01010101u, 0u, false));
+                            if (commit[p]) region_lds_add(acc + 2u * ncell, g);
                         }
                     }
                 }

@@ -376,6 +376,47 @@ int h264bsdmiBlendCurrentPictures(u32 n, storage_t *const *pStorage, const h264b
 int h264bsdmiOutputKeptPictures(u32 n, storage_t *const *pStorage, void *const *picture, void *const *fraction, void *stream,
                                 u32 *got, u32 *keptPicId);
 
+/* Background spread: a per-sample NOISE LEVEL beside the kept picture.  One `hold` cannot serve a real camera: foliage, water, flicker
+ * and noisy dark areas need a high threshold, the quiet wall beside them a low one.  The SPREAD V is a third frame per instance, one
+ * byte per sample of the coded frame (luma, Cb, Cr) in the layout of the kept picture, that follows how much the sample usually differs
+ * from its background; the moving test then uses it as the sample's threshold.  The library allocates it at an instance's first
+ * h264bsdmiBlendCurrentPicturesSpread (instances that never ask pay nothing) and drops it wherever the kept picture is dropped.
+ * h264bsdmiBlendCurrentPicturesSpread is h264bsdmiBlendCurrentPictures with one more argument, and everything not said here is that
+ * call's.  Per sample, with the current sample c, the kept byte hi and the spread byte V, all read BEFORE the call, and d = |c - hi|:
+ *     MOVING    a luma sample when d > max(hold, V); a chroma sample when one of the four luma samples it covers is (chroma V never gates)
+ *     S         updated exactly as h264bsdmiBlendCurrentPictures does under that mask (shift, moving_shift, FROZEN)
+ *     V         A = min(255, gain d);  V' = clamp(V + sign(A - V), lowest, highest): one step a call; chroma samples with their own d
+ * update H264BSDMI_SPREAD_NONE: no byte of V changes; _ALL: the rule applies to every sample; _STILL: only to samples that are not
+ * moving (a chroma sample counts as moving by the rule above).  Where an instance's spread is NOT VALID it reads as `lowest`, and where
+ * the model starts (no kept picture of the coded size) S = T, V = lowest and nothing is moving.  spec->moving counts the moving luma
+ * samples under the new test.  With lowest = highest = 0 the call is h264bsdmiBlendCurrentPictures byte for byte.  Everything is an
+ * integer and exact, and independent of scheduling.
+ * VALIDITY: the spread becomes valid at a spread blend.  A plain keep (h264bsdmiKeepCurrentPictures and every keep_after) invalidates
+ * it without freeing the frame, as it resets the fraction; a plain h264bsdmiBlendCurrentPictures leaves it as it is.
+ * h264bsdmiWarpKeptPictures leaves it WHERE IT LIES, unresampled and still valid: after a warp the spread is that of the samples'
+ * old positions (registering it with the picture is not part of this interface yet).
+ * kept, blended, picId, the stream rule, the fence and the ordering are those of the blend.
+ * -1, before anything is enqueued: everything h264bsdmiBlendCurrentPictures refuses; spread NULL; gain outside 1 .. 8; lowest > highest
+ * or either above 255; update > 2; an engine without the entry.  -2: the engine failed, nothing is marked.  n == 0 returns 0. */
+#define H264BSDMI_SPREAD_NONE  0u
+#define H264BSDMI_SPREAD_ALL   1u
+#define H264BSDMI_SPREAD_STILL 2u
+typedef struct h264bsdmi_spread_spec {
+    u32 gain;      /* 1 .. 8 */
+    u32 lowest;    /* 0 .. 255 */
+    u32 highest;   /* lowest .. 255 */
+    u32 update;    /* H264BSDMI_SPREAD_*: 0 none, 1 every sample, 2 still samples only */
+} h264bsdmi_spread_spec;
+int h264bsdmiBlendCurrentPicturesSpread(u32 n, storage_t *const *pStorage, const h264bsdmi_blend_spec *spec,
+                                        const h264bsdmi_spread_spec *spread, void *stream, u32 *kept, u32 *blended, u32 *picId);
+
+/* The spread handed out, for viewing where the scene is busy: spread[i], a DEVICE buffer of 384 * (macroblocks of the coded frame)
+ * bytes, 16-byte aligned, receives V of instance i as a planar I420 coded frame, as h264bsdmiOutputKeptPictures hands out the kept
+ * picture: one launch, the same ordering and stream rule.  got[i] = 1, or 0 where the instance has no kept picture of its coded size
+ * or no valid spread: its buffer is then untouched.  keptPicId (may be NULL): the picId of the kept picture, or 0.
+ * -1 and -2 as for h264bsdmiOutputKeptPictures (spread in the place of picture; there is no fraction); an engine without the entry. */
+int h264bsdmiOutputKeptSpread(u32 n, storage_t *const *pStorage, void *const *spread, void *stream, u32 *got, u32 *keptPicId);
+
 /* Warped kept pictures: the kept picture of each of n distinct instances RESAMPLED IN PLACE through an affine map, the picture (hi)
  * and, where the instance has one, the fraction (lo) — a background that follows a camera which shakes or pans.  Afterwards the kept
  * picture lies in the coordinates the map leads to, and every consumer (h264bsdmiOutputRegionChange, h264bsdmiOutputRegionShift,
@@ -475,7 +516,14 @@ int h264bsdmiOutputRegionChange(u32 n, storage_t *const *pStorage, u32 nRegions,
  * spec or data NULL or data not 4-byte aligned; cols or rows 0 or above 4096; a cell not in {4, 8, 16, 32, 64}; source > 2; crop > 1;
  * mode > 1; planes 0 or with bits outside the mode's set; a threshold above 255; PICTURE with a non-zero threshold or keep_after;
  * keep_after > 1.  -2: the engine failed (also: more than 2^23 workgroups — 128 x 64 luma samples of grid each, times the regions —
- * in one call): nothing is written by the host and nothing is marked kept.  nRegions == 0 returns 0 and launches nothing. */
+ * in one call): nothing is written by the host and nothing is marked kept.  nRegions == 0 returns 0 and launches nothing.
+ * MODE SPREAD (2) reads the current picture, the kept picture and the spread of h264bsdmiBlendCurrentPicturesSpread: per sample and
+ * channel t = max(threshold[c], V) — threshold is the floor — and d = |current - kept|; the planes are COUNT, FORE = #(d > t),
+ * EXCESS = sum of max(0, d - t) and SPREADSUM = sum of V (the map of where the scene is busy), C maps each, sources Y and YCbCr (the
+ * chroma bytes of V lie under the luma positions as the chroma samples do); the largest value is 64 * 64 * 255.  got[r] = 0 and slice
+ * r untouched where the instance lacks a current picture, a kept picture or a valid spread.  Refused with -1 beyond the above: source
+ * RGB; plane bits outside 1 | 2 | 4 | 8; keep_after = 1 (a plain keep would invalidate what the call just read); an engine without
+ * the spread entries.  h264bsdmiOutputCellBoxes takes any one plane of the mode: all are unsigned. */
 #define H264BSDMI_CELLS_PICTURE 0      /* statistics of the current picture            */
 #define H264BSDMI_CELLS_CHANGE  1      /* of d = current - kept, as region change      */
 #define H264BSDMI_CELL_COUNT  1u       /* 1 map, both modes                            */
@@ -490,14 +538,19 @@ int h264bsdmiOutputRegionChange(u32 n, storage_t *const *pStorage, u32 nRegions,
 #define H264BSDMI_CELL_DSUM   8u       /* sum d, i32 two's complement */
 #define H264BSDMI_CELL_DMAX   16u      /* max |d|  */
 #define H264BSDMI_CELL_ABOVE  32u      /* #(|d| > threshold[c]) */
+/* SPREAD, C maps each: */
+#define H264BSDMI_CELLS_SPREAD  2      /* of |current - kept| against t = max(threshold[c], V) */
+#define H264BSDMI_CELL_FORE      2u    /* #(|d| > t) */
+#define H264BSDMI_CELL_EXCESS    4u    /* sum max(0, |d| - t) */
+#define H264BSDMI_CELL_SPREADSUM 8u    /* sum V */
 typedef struct h264bsdmi_cells_spec {
     void *data;            /* DEVICE, caller-owned, 4-byte aligned: slice r at data + r * P*rows*cols u32 */
     u32 cols, rows;        /* grid of every slice, 1..4096 each */
     u32 cell;              /* 4, 8, 16, 32 or 64 luma samples a side */
     u32 source, crop;      /* H264BSDMI_STATS_*; as everywhere */
     u32 mode, planes;      /* planes: non-empty subset of the mode's bits */
-    u32 threshold[3];      /* CHANGE: 0..255 per channel; PICTURE: must be 0 */
-    u32 keep_after;        /* CHANGE: 0 / 1 as h264bsdmiOutputRegionChange; PICTURE: must be 0 */
+    u32 threshold[3];      /* CHANGE, SPREAD: 0..255 per channel; PICTURE: must be 0 */
+    u32 keep_after;        /* CHANGE: 0 / 1 as h264bsdmiOutputRegionChange; PICTURE, SPREAD: must be 0 */
 } h264bsdmi_cells_spec;
 int h264bsdmiOutputCellMaps(u32 n, storage_t *const *pStorage, u32 nRegions, const h264bsdmi_region *regions,
                             const h264bsdmi_cells_spec *spec, void *stream,
